@@ -8,6 +8,12 @@ A "step" is one HPR iteration (x-half + y-half, reference src/main_iterate.cu:43
 data already resident in HBM.  Default workload: BASELINE.json config 5, the banded-random 10M x 10M,
 ~200M-nnz LP (the largest configuration; it fits one MI355X, so N=1 runs all of it and N>1
 row-partitions the SAME problem: strong scaling).  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (headline figure, ms_per_step, the
+timed steps' own half-step times).  --full adds everything else the benchmark measures or checks: the
+bare SpMVs, the KKT check after the run, the whole solve to 1e-4, configs 2-4, the ladder, the predicted
+scaling and the CPU baseline (each of them can still be left out with its --no-* switch).
+--dump-outputs DIR writes the iterates x and y as the last timed step left them to DIR/x.npy, DIR/y.npy.
 """
 import argparse
 import ctypes as C
@@ -554,6 +560,26 @@ def ladder():
     return out
 
 
+DUMP_SAMPLE = 1 << 21  # entries per dumped vector at most: x and y of config 5 as float64 stay at 32 MB together
+
+
+def dump_outputs(s, directory, cap):
+    """--dump-outputs: x and y as the timed steps left them, in the caller's numbering (hprlp_solver_get_vector; at N > 1 this
+    rank's rows / columns), float64.  A vector longer than DUMP_SAMPLE is written as the same seeded sample of DUMP_SAMPLE
+    positions on every run, so that two builds can be compared entry for entry."""
+    os.makedirs(directory, exist_ok=True)
+    L = H.lib()
+    buf = np.empty(max(cap, 1))
+    for name in ("x", "y"):
+        k = L.hprlp_solver_get_vector(s.h, name.encode(), buf.ctypes.data_as(H.c_dbl_p), len(buf))
+        if k < 0:
+            raise RuntimeError(H.last_error())
+        v = buf[:k]
+        if k > DUMP_SAMPLE:
+            v = v[np.sort(np.random.default_rng(2024).choice(k, DUMP_SAMPLE, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+
+
 def xhalf_kernel_key(tiled, description=""):
     """Short identity of the kernel avg_launch_ms covers; tools/profile_c5.sh stores the same key beside the counters it collects,
     and the bench line carries `traffic` only when the two agree.  k_tiled_fused<XEpi<false, true>, REP, PUSH, NARROW>: the key
@@ -763,9 +789,16 @@ def main():
     ap.add_argument("--no-ladder", action="store_true", help="skip the size-and-structure ladder (2e6 .. 6e7 nnz)")
     ap.add_argument("--ladder-point", default=None,
                     help="run ONE ladder point and print its record (what tools/profile_ladder.sh puts under rocprofv3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: bare SpMVs, KKT check, time to 1e-4, "
+                         "configs 2-4, ladder, predicted scaling, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write x and y after the last timed step to DIR/<name>.npy (float64; a fixed sample of longer vectors)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
+    if not args.full:  # a plain run: set-up, warm-up, the timed steps, the line
+        args.no_cpu = args.no_side = args.no_cold_start = args.no_solve = args.no_ladder = True
     if args.ladder_point:
         sys.stdout.flush()
         real = os.dup(1)
@@ -928,12 +961,16 @@ def main():
         te = torch.tensor([elapsed, tm["xhalf_ms"], tm["yhalf_ms"]], dtype=torch.float64)
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         elapsed, tm["xhalf_ms"], tm["yhalf_ms"] = float(te[0]), float(te[1]), float(te[2])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(s, args.dump_outputs, max(m, n))
 
-    spmv = s.time_iterations(2, 20, 2) if world == 1 else None  # bare SpMVs, outside the timed region
-    # sanity: the iterate must be finite and the KKT error must not have blown up
-    s.iterate(0, True)
-    res = s.residuals(args.warmup + args.steps + 1)
-    ok = np.isfinite(res["kkt"])
+    spmv = s.time_iterations(2, 20, 2) if world == 1 and args.full else None  # bare SpMVs, outside the timed region
+    res = None
+    if args.full:
+        # sanity: the iterate must be finite and the KKT error must not have blown up
+        s.iterate(0, True)
+        res = s.residuals(args.warmup + args.steps + 1)
+        ok = np.isfinite(res["kkt"])
 
     out = None
     if rank == 0:
@@ -987,11 +1024,12 @@ def main():
                          "yhalf_avg_launch_ms": y_ms,
                          "yhalf_GBps": ((12 * nnz + 4 * (m + P) + 40 * m) / P + 8 * n) / (y_ms * 1e-3) / 1e9,
                          "iteration_GBps": bytes_per_iteration(m, n, nnz) / P / (1e-3 * (x_ms + y_ms)) / 1e9},
-            "kkt_after_run": res["kkt"], "finite": bool(ok),
             # outside the timed region (rank 0): device set-up incl. transpose and tiled copies, scaling, power iteration
             "phases_s": {"device_setup": sc["setup_time"], "scaling": sc["scaling_time"], "power_iteration": sc["power_time"],
                          "power_iterations": int(pw_it)},
         }
+        if res is not None:
+            out["kkt_after_run"], out["finite"] = res["kkt"], bool(ok)
         if spmv is not None:
             # SpMV-only figure B_spmv = 12 nnz + 4 (rows+1) + 8 cols + 8 rows over the bare kernel's time,
             # against the 8.0 TB/s spec peak and the 6.3 TB/s the guide gives as achievable

@@ -11,8 +11,6 @@ import os
 import sys
 
 import numpy as np
-import torch
-import torch.distributed as dist
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
@@ -120,4 +118,8 @@ def main():
 
 
 if __name__ == "__main__":
+    # torch only in the worker process: the tests import Shard / arr from here, and a torch loaded into the test process brings
+    # its own HIP runtime and RCCL, which the library's RCCL communicators of the GPU tests in that process would then pick up
+    import torch
+    import torch.distributed as dist
     main()

@@ -418,8 +418,8 @@ def test_bench_supervisor_cascade_ends_with_a_line_on_the_one_gpu_box(gpu):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "HPRLP_TEST_HOOKS")}
     env.update(HPRLP_BENCH_ONE_DEVICE="1", HPRLP_BENCH_STALL_S="120")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "c5_tiny", "--steps", "20", "--warmup", "5"],
-                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--workload", "c5_tiny", "--steps", "20", "--warmup", "5",
+                        "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     err = r.stderr.decode()
     assert r.returncode == 0, err[-3000:]
     lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]

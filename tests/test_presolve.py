@@ -2,18 +2,29 @@
 
 CPU tests: the reduced model and the postsolve map are checked with an exact LP solver (HiGHS via scipy) --
 same optimum as the original, and the postsolved primal-dual triple satisfies the KKT conditions of the
-ORIGINAL model.  The presolver the reference vendors (PSLP v0.0.8, built unchanged into oracle/_ref by
-`make -C oracle refpslp`) is run beside ours on the same LPs as the reference point.
+ORIGINAL model.  The presolver the reference vendors (PSLP v0.0.8) is the reference point on some of the same LPs:
+what it made of them is stored in tests/golden/pslp_reference.json (tests/golden/make_pslp_golden.py).
 GPU test: solve() with use_presolve on and off gives the same optimum in the original dimensions."""
+import json
+import os
+
 import numpy as np
 import pytest
 from scipy import sparse
 from scipy.optimize import linprog
 
 from conftest import hprlp, lpgen
-from oracle import pslp_ref
 
 INF = np.inf
+PSLP_GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "pslp_reference.json")
+
+
+def pslp_record(key, lp):
+    """PSLP's status, reduced size and postsolved solution for `lp` (tests/golden/make_pslp_golden.py), checked to be of this LP."""
+    with open(PSLP_GOLDEN) as f:
+        rec = json.load(f)[key]
+    assert (rec["m"], rec["n"], rec["nnz"]) == (lp["m"], lp["n"], len(lp["values"])), key
+    return rec
 
 
 def highs(m, n, rp, ci, v, AL, AU, l, u, c):
@@ -619,7 +630,6 @@ def test_presolve_declines(model_mps_arrays):
     bad.free()
 
 
-@pytest.mark.skipif(not pslp_ref.available(), reason="oracle/_ref/libpslp_ref.so not built (make -C oracle refpslp)")
 @pytest.mark.parametrize("seed", [1, 2, 3])
 def test_against_the_reference_presolver(seed):
     """PSLP (the reference's presolver) and ours on the same LP: both reduced models have the original optimum and
@@ -628,16 +638,12 @@ def test_against_the_reference_presolver(seed):
     lp = structured_lp(seed)
     model = make_model(lp)
     f0, *_ = highs(lp["m"], lp["n"], lp["rowptr"], lp["colind"], lp["values"], lp["AL"], lp["AU"], lp["l"], lp["u"], lp["c"])
-    ref = pslp_ref.RefPresolve(lp["m"], lp["n"], lp["rowptr"], lp["colind"], lp["values"], lp["AL"], lp["AU"], lp["l"], lp["u"], lp["c"])
+    ref = pslp_record("structured_%d" % seed, lp)
     pre = hprlp.Presolved(model)
-    assert ref.status == 1  # REDUCED
-    assert ref.rm < lp["m"] and ref.rn < lp["n"] and pre.reduced.m < lp["m"] and pre.reduced.n < lp["n"]
-    if ref.rm > 0 and ref.rn > 0:
-        fr, xr, yr, zr = highs(ref.rm, ref.rn, ref.Ap, ref.Ai, ref.Ax, ref.lhs, ref.rhs, ref.lbs, ref.ubs, ref.c)
-    else:
-        xr, yr, zr = np.zeros(ref.rn), np.zeros(ref.rm), np.zeros(ref.rn)
-    xp, yp, zp = ref.postsolve(xr, yr, zr)
-    kp = hprlp.original_kkt(model, xp, yp, zp)
+    assert ref["status"] == 1  # REDUCED
+    assert ref["rm"] < lp["m"] and ref["rn"] < lp["n"] and pre.reduced.m < lp["m"] and pre.reduced.n < lp["n"]
+    # PSLP's postsolve of the exact optimum of its reduced model
+    kp = hprlp.original_kkt(model, ref["x"], ref["y"], ref["z"])
     # PSLP's obj_offset counts columns given with l == u twice (v0.0.8), so the comparison goes through c.x
     assert abs(kp["primal_obj"] - f0) <= 1e-7 * (1 + abs(f0))
     assert kp["primal_feas"] <= 1e-8
@@ -647,10 +653,9 @@ def test_against_the_reference_presolver(seed):
     k = hprlp.original_kkt(model, x, y, z)
     assert abs(k["primal_obj"] - kp["primal_obj"]) <= 1e-7 * (1 + abs(f0))
     assert max(k["primal_feas"], k["dual_feas"], k["gap"]) <= 1e-9
-    ref.close(); pre.free(); model.free()
+    pre.free(); model.free()
 
 
-@pytest.mark.skipif(not pslp_ref.available(), reason="oracle/_ref/libpslp_ref.so not built (make -C oracle refpslp)")
 @pytest.mark.parametrize("seed,free_share", [(31, 0.0), (34, 0.0), (42, 0.5), (43, 0.5)])
 def test_doubletons_and_bounds_against_the_reference_presolver(seed, free_share):
     """The LPs of the doubleton / bound-propagation tests through PSLP as well: its DtonsEq and Primal_propagation are the
@@ -662,13 +667,11 @@ def test_doubletons_and_bounds_against_the_reference_presolver(seed, free_share)
     except AssertionError:
         pytest.skip("unbounded after freeing columns")
     model = make_model(lp)
-    ref = pslp_ref.RefPresolve(lp["m"], lp["n"], lp["rowptr"], lp["colind"], lp["values"], lp["AL"], lp["AU"], lp["l"], lp["u"], lp["c"])
+    ref = pslp_record("doubleton_%d_%g" % (seed, free_share), lp)
     pre = hprlp.Presolved(model)
-    assert ref.status == 1
-    if ref.rm > 0 and ref.rn > 0:
-        fr, xr, yr, zr = highs(ref.rm, ref.rn, ref.Ap, ref.Ai, ref.Ax, ref.lhs, ref.rhs, ref.lbs, ref.ubs, ref.c)
-        xp, yp, zp = ref.postsolve(xr, yr, zr)
-        kp = hprlp.original_kkt(model, xp, yp, zp)
+    assert ref["status"] == 1
+    if ref["rm"] > 0 and ref["rn"] > 0:
+        kp = hprlp.original_kkt(model, ref["x"], ref["y"], ref["z"])
         assert abs(kp["primal_obj"] - f0) <= 1e-7 * (1 + abs(f0)) and kp["primal_feas"] <= 1e-8
     rm, rn, rp, ci, v, AL, AU, l, u, c = reduced_arrays(pre)
     fo, xo, yo, zo = highs(rm, rn, rp, ci, v, AL, AU, l, u, c)
@@ -676,9 +679,9 @@ def test_doubletons_and_bounds_against_the_reference_presolver(seed, free_share)
     x, y, z = pre.postsolve(xo, yo, zo)
     k = hprlp.original_kkt(model, x, y, z)
     assert max(k["primal_feas"], k["dual_feas"], k["gap"]) <= 1e-8
-    print(f"seed {seed}: original {lp['m']} x {lp['n']}, PSLP {ref.rm} x {ref.rn}, ours {rm} x {rn}")
-    assert rm <= 1.25 * ref.rm + 5 and rn <= 1.25 * ref.rn + 5
-    ref.close(); pre.free(); model.free()
+    print(f"seed {seed}: original {lp['m']} x {lp['n']}, PSLP {ref['rm']} x {ref['rn']}, ours {rm} x {rn}")
+    assert rm <= 1.25 * ref["rm"] + 5 and rn <= 1.25 * ref["rn"] + 5
+    pre.free(); model.free()
 
 
 @pytest.mark.gpu
