@@ -23,6 +23,7 @@ struct hprlp_solver {
     Solver s;
     Comm *comm = nullptr;   // owned; destroyed after the solver's device state
     Comm *xcomm = nullptr;  // owned; the exchange stream's own communicator (second unique id), may be null
+    bool sharded = false;   // created by hprlp_solver_create_dist* / _local* (no infeasibility detection)
     ~hprlp_solver() {}
 };
 
@@ -168,8 +169,9 @@ extern "C" int hprlp_last_solve_phases(double out[8]) {
     return 0;
 }
 
-// reference src/HPRLP.cu:116-311
-extern "C" HPRLP_results HPRLP_main_solve(const LP_info_cpu *model, const HPRLP_parameters *param) {
+// reference src/HPRLP.cu:116-311.  det (may be null: off, as in the reference) switches the infeasibility detection on; a verdict's
+// certificate goes to *cert.
+static HPRLP_results main_solve(const LP_info_cpu *model, const HPRLP_parameters *param, const Detection *det, Certificate *cert) {
     if (!model || !param) {
         std::cerr << "[error] Null model or parameter pointer" << std::endl;
         return make_error_result("ERROR");
@@ -192,9 +194,11 @@ extern "C" HPRLP_results HPRLP_main_solve(const LP_info_cpu *model, const HPRLP_
         std::cout << "ESTIMATING MAXIMUM EIGENVALUE time = " << std::fixed << std::setprecision(2) << s.power_time
                   << " seconds" << std::endl << std::defaultfloat;
         s.init_iteration_state();
+        if (det) s.detect = *det;
         const auto t_loop = time_now();
         s.solve_loop(&out);
         const double loop_s = time_since(t_loop);
+        if (cert) *cert = std::move(s.cert);
         const auto t_col = time_now();
         s.collect_solution(&out);
         g_phases[0] = s.setup_time; g_phases[1] = s.scaling_time; g_phases[2] = s.power_time; g_phases[3] = loop_s;
@@ -213,6 +217,10 @@ extern "C" HPRLP_results HPRLP_main_solve(const LP_info_cpu *model, const HPRLP_
         std::cerr << "[error] HPRLP_main_solve failed: " << e.what() << std::endl;
         return make_error_result("ERROR");
     }
+}
+
+extern "C" HPRLP_results HPRLP_main_solve(const LP_info_cpu *model, const HPRLP_parameters *param) {
+    return main_solve(model, param, nullptr, nullptr);
 }
 
 // NULL if the CSR arrays of `model` are consistent, else what is wrong with them.
@@ -236,14 +244,19 @@ static const char *invalid_model_reason(const LP_info_cpu *model) {
 // src/pslp_integration.cpp:628-713), the reduced model goes through HPRLP_main_solve and the result
 // is mapped back to the original dimensions and checked against the original model
 // (src/pslp_integration.cpp:715-787).  If the presolver declines, the original model is solved.
-extern "C" HPRLP_results solve(const LP_info_cpu *model, const HPRLP_parameters *param) {
+static bool is_verdict(const HPRLP_results &r) {
+    return std::strcmp(r.status, "PRIMAL_INFEASIBLE") == 0 || std::strcmp(r.status, "DUAL_INFEASIBLE") == 0;
+}
+
+// det / cert: infeasibility detection (hprlp_solve_detect), null for solve()
+static HPRLP_results solve_impl(const LP_info_cpu *model, const HPRLP_parameters *param, const Detection *det, Certificate *cert) {
     if (!model) {
         std::cerr << "[error] Null model pointer" << std::endl;
         return make_error_result("ERROR");
     }
     HPRLP_parameters dflt;
     const HPRLP_parameters *p = param ? param : &dflt;
-    if (!p->use_presolve) return HPRLP_main_solve(model, p);
+    if (!p->use_presolve) return main_solve(model, p, det, cert);
     const auto t_entry = time_now();  // (the fallback below charges everything since here against the caller's time limit)
 
     // The presolver indexes its work arrays by the model's column indices and trusts rowPtr: a hand-built
@@ -289,11 +302,11 @@ extern "C" HPRLP_results solve(const LP_info_cpu *model, const HPRLP_parameters 
         // (cannot happen with exact arithmetic; with rounding trouble fall back to the iteration)
         std::free(r.x); std::free(r.y); std::free(r.z);
         std::cout << "Postsolve-only solution failed the KKT check; solving original model" << std::endl;
-        return HPRLP_main_solve(model, p);
+        return main_solve(model, p, det, cert);
     }
     if (!reduced) {
         std::cout << "Presolve left the model unchanged; solving original model" << std::endl;
-        return HPRLP_main_solve(model, p);
+        return main_solve(model, p, det, cert);
     }
     const Presolve::Stats &st = pre.stats();
     std::cout << "Presolve reduced problem: (" << model->m << ", " << model->n << ") -> (" << pre.reduced()->m << ", "
@@ -326,7 +339,28 @@ extern "C" HPRLP_results solve(const LP_info_cpu *model, const HPRLP_parameters 
         std::cout << "Reduced-model tolerance " << pr.stop_tol << " (original norms |b| " << nb0 << ", |c| " << nc0 << "; reduced "
                   << nb1 << ", " << nc1 << ")" << std::endl;
     }
-    HPRLP_results r = HPRLP_main_solve(pre.reduced(), &pr);
+    HPRLP_results r = main_solve(pre.reduced(), &pr, det, cert);
+    if (det && is_verdict(r)) {
+        // a certificate of the reduced model is no certificate of the caller's: solve the model as given, with detection, within
+        // what is left of the time and iteration limits (reported times and counts include the reduced solve, as below)
+        std::free(r.x); std::free(r.y); std::free(r.z);
+        const double spent = time_since(t_entry);
+        const int it_first = r.iter;
+        std::cout << "Reduced model ended " << r.status << " at iteration " << r.iter << "; solving the original model for its certificate"
+                  << std::endl;
+        HPRLP_parameters p2 = *p;
+        p2.time_limit = std::max(p->time_limit - spent, 0.0);
+        p2.max_iter = std::max(p->max_iter - it_first, 0);
+        if (cert) *cert = Certificate();
+        HPRLP_results r2 = main_solve(model, &p2, det, cert);
+        if (std::strcmp(r2.status, "ERROR") != 0) {
+            r2.time += spent; r2.time4 += spent; r2.time6 += spent; r2.time8 += spent;
+            r2.iter += it_first; r2.iter4 += it_first; r2.iter6 += it_first; r2.iter8 += it_first;
+            if (cert && cert->kind) cert->iter += it_first;
+        }
+        return r2;
+    }
+    if (det && cert) *cert = Certificate();  // (only the original model's verdicts count)
     if (!(r.x && r.y && r.z)) return r;
     double *x = static_cast<double *>(std::malloc(sizeof(double) * std::max(model->n, 1)));
     double *y = static_cast<double *>(std::malloc(sizeof(double) * std::max(model->m, 1)));
@@ -361,12 +395,13 @@ extern "C" HPRLP_results solve(const LP_info_cpu *model, const HPRLP_parameters 
                 HPRLP_parameters p2 = *p;
                 p2.time_limit = std::max(p->time_limit - spent, 0.0);
                 p2.max_iter = std::max(p->max_iter - it_first, 0);
-                HPRLP_results r2 = HPRLP_main_solve(model, &p2);
+                HPRLP_results r2 = main_solve(model, &p2, det, cert);
                 if (std::strcmp(r2.status, "ERROR") != 0) {
                     // iter4/6/8 of a tolerance the second solve never reached are back-filled with its final count
                     // (reference src/HPRLP.cu:248-253): offset like `iter`, so they stay "<= iter"
                     r2.time += spent; r2.time4 += spent; r2.time6 += spent; r2.time8 += spent;
                     r2.iter += it_first; r2.iter4 += it_first; r2.iter6 += it_first; r2.iter8 += it_first;
+                    if (cert && cert->kind) cert->iter += it_first;  // (detection: the verdict's iteration counts the same way)
                 }
                 std::cout << "Fallback solve: reported time and iterations include presolve and the reduced solve (" << spent
                           << " s, " << it_first << " iterations)" << std::endl;
@@ -377,6 +412,80 @@ extern "C" HPRLP_results solve(const LP_info_cpu *model, const HPRLP_parameters 
         std::cout << "Skipping postsolve original KKT check since the reduced solution is not optimal" << std::endl;
     }
     return r;
+}
+
+extern "C" HPRLP_results solve(const LP_info_cpu *model, const HPRLP_parameters *param) {
+    return solve_impl(model, param, nullptr, nullptr);
+}
+
+static void clear_certificate(hprlp_certificate *c, int m, int n) {
+    std::memset(c, 0, sizeof(*c));
+    c->m = m;
+    c->n = n;
+}
+
+// Certificate -> hprlp_certificate (malloc'd arrays); false when the host allocation failed
+static bool export_certificate(const Certificate &k, hprlp_certificate *c, int m, int n) {
+    clear_certificate(c, m, n);
+    auto dup = [](const std::vector<double> &v, double **out) {
+        if (v.empty()) return true;
+        *out = static_cast<double *>(std::malloc(sizeof(double) * v.size()));
+        if (!*out) return false;
+        std::memcpy(*out, v.data(), sizeof(double) * v.size());
+        return true;
+    };
+    if (!dup(k.y, &c->y) || !dup(k.z, &c->z) || !dup(k.d, &c->d)) {
+        hprlp_free_certificate(c);
+        clear_certificate(c, m, n);
+        return false;
+    }
+    c->kind = k.kind;
+    c->iter = k.iter;
+    c->objective = k.objective;
+    c->violation = k.violation;
+    return true;
+}
+
+static bool detection_from(const hprlp_detection *d, Detection *out) {
+    if (!d) return false;
+    if (!(d->eps_primal_infeasible >= 0.0) || !(d->eps_dual_infeasible >= 0.0))
+        throw std::runtime_error("infeasibility detection: eps_primal_infeasible and eps_dual_infeasible must be >= 0");
+    out->on = true;
+    out->eps_primal = d->eps_primal_infeasible;
+    out->eps_dual = d->eps_dual_infeasible;
+    return true;
+}
+
+extern "C" HPRLP_results hprlp_solve_detect(const LP_info_cpu *model, const HPRLP_parameters *param, const hprlp_detection *det,
+                                            hprlp_certificate *cert) {
+    const int m = model ? model->m : 0, n = model ? model->n : 0;
+    if (cert) clear_certificate(cert, m, n);
+    if (!det) return solve(model, param);
+    try {
+        Detection d;
+        detection_from(det, &d);
+        Certificate k;
+        HPRLP_results r = solve_impl(model, param, &d, &k);
+        if (std::strcmp(r.status, "ERROR") == 0 && !*last_error_cstr()) set_last_error("hprlp_solve_detect: the solve failed");
+        if (cert && !export_certificate(k, cert, m, n)) {
+            std::free(r.x); std::free(r.y); std::free(r.z);
+            throw std::runtime_error("host allocation of the certificate failed");
+        }
+        return r;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        std::cerr << "[error] hprlp_solve_detect failed: " << e.what() << std::endl;
+        return make_error_result("ERROR");
+    }
+}
+
+extern "C" void hprlp_free_certificate(hprlp_certificate *cert) {
+    if (!cert) return;
+    std::free(cert->y);
+    std::free(cert->z);
+    std::free(cert->d);
+    cert->y = cert->z = cert->d = nullptr;
+    cert->kind = 0;
 }
 
 // presolve as separate steps (host only; used by the CPU tests and by callers that want the maps)
@@ -517,6 +626,7 @@ static hprlp_solver *create_sharded(const LP_info_cpu *model, const HPRLP_parame
         const HPRLP_parameters *p = param ? param : &dflt;
         if (hprlp_extract_shard(model, rank, size, &sh) != 0) throw std::runtime_error(last_error_cstr());
         h = new hprlp_solver();
+        h->sharded = true;
         h->s.verbose = false;
         HIP_CHECK(hipSetDevice(p->device_number));
         if (group) {
@@ -555,6 +665,7 @@ static hprlp_solver *create_from_shard(const hprlp_shard *sh, const HPRLP_parame
         HPRLP_parameters dflt;
         const HPRLP_parameters *p = param ? param : &dflt;
         h = new hprlp_solver();
+        h->sharded = true;
         h->s.verbose = false;
         HIP_CHECK(hipSetDevice(p->device_number));
         if (group) h->comm = make_local_comm(group->g, rank);
@@ -930,6 +1041,27 @@ extern "C" int hprlp_solver_info(hprlp_solver *h, long out[8]) {
     // bit0: A tiled, bit1: A^T tiled, bit2: normal iterations run in the single-workgroup small-LP kernel
     // bit3: a set-up time locality ordering is in place (the device works on P A Q)
     out[7] = (s.A.view.tiled.valid ? 1 : 0) + (s.AT.view.tiled.valid ? 2 : 0) + (s.use_small && !s.comm ? 4 : 0) + (s.perm_r.empty() ? 0 : 8);
+    return 0;
+    GUARD_END(-1)
+}
+
+extern "C" int hprlp_solver_set_detection(hprlp_solver *h, const hprlp_detection *det) {
+    GUARD_BEGIN
+    if (!h) throw std::runtime_error("null solver");
+    if (h->sharded && det)
+        throw std::runtime_error("hprlp_solver_set_detection: infeasibility detection runs on one GPU only; a sharded solver "
+                                 "(hprlp_solver_create_dist* / _local*) refuses it");
+    Detection d;
+    detection_from(det, &d);
+    h->s.detect = d;
+    return 0;
+    GUARD_END(-1)
+}
+
+extern "C" int hprlp_solver_get_certificate(hprlp_solver *h, hprlp_certificate *cert) {
+    GUARD_BEGIN
+    if (!h || !cert) throw std::runtime_error("null solver / certificate");
+    if (!export_certificate(h->s.cert, cert, h->s.m, h->s.n)) throw std::runtime_error("host allocation of the certificate failed");
     return 0;
     GUARD_END(-1)
 }

@@ -18,7 +18,7 @@ constexpr int kLongRow = 64;      // rows longer than this get a whole wave (vec
                                   // config-3 x-half launch (10.9 -> 9.4 us per iteration).  Rows up to 64 entries keep the plain CSR-order sum
                                   // (bit-identical to the oracle and to the single-workgroup kernel); longer ones agree to rounding.
 constexpr int kSplitRow = 4096;   // rows longer than this are cut into chunks of this many nonzeros
-constexpr int kNumScalars = 24;   // device scalar slots (see enum Slot)
+constexpr int kNumScalars = 32;   // device scalar slots (see enum Slot)
 
 // Scalar slots filled by the reduction epilogues.  0-9 follow the reference's 10-slot buffer
 // (reference include/structs.h:196-206); the rest are ours.
@@ -43,6 +43,16 @@ enum Slot : int {
     S_TMP1 = 17,
     S_SMALL_PW_LAMBDA = 18,  // single-launch power iteration (small.hip): lambda ...
     S_SMALL_PW_ITERS = 19,   // ... and the iteration it stopped at (0: the kernel did not run)
+    // infeasibility detection (Solver::ray_test), original units: k_ray_form's six, then the two ray SpMVs'
+    S_RAY_DY = 20,  // D: bound terms of the rows
+    S_RAY_CD = 21,  // c'd
+    S_RAY_VY = 22,  // V: rows (max)
+    S_RAY_WD = 23,  // W: columns (max)
+    S_RAY_YN = 24,  // |y|_inf
+    S_RAY_DN = 25,  // |d|_inf
+    S_RAY_DZ = 26,  // D: bound terms of the columns (z = -A^T y)
+    S_RAY_VZ = 27,  // V: columns (max)
+    S_RAY_WQ = 28,  // W: rows (q = A d, max)
 };
 
 // Row-block descriptor: one per wave.  {first row, number of rows, first nonzero, nonzero count}.
@@ -141,6 +151,7 @@ struct FinalizeItem {
     const double *partials;
     int count;
     int slot;
+    int max = 0;  // 1: the partials are nonnegative maxima (their maximum, not their sum)
 };
 struct FinalizeArgs {
     FinalizeItem item[8];
@@ -172,6 +183,25 @@ void launch_spmv_plain(const CsrDev &M, const double *v_full, double *out, const
                        double *partials, int stride, hipStream_t s, bool far_ready = false);
 
 void launch_finalize(const FinalizeArgs &f, double *scalars, hipStream_t s);
+
+// ---- infeasibility detection (Solver::ray_test): the candidate rays and the Farkas ratio test in original units -------------
+// k_ray_form: ds = x_bar - prev_x, ys = y_bar - prev_y, prev_* <- *_bar, and the elementwise terms; partials (kRayFormAccs x
+// nblocks): D of the rows, c'd (sums), V of the rows, W of the columns, |y|_inf, |d|_inf (maxima)
+constexpr int kRayFormAccs = 6;
+struct RayFormArgs {
+    int n, m;
+    const double *x_bar, *y_bar;
+    double *prev_x, *prev_y, *ds, *ys;
+    const double *l, *u, *c, *col_norm, *AL, *AU, *row_norm;
+    double b_scale, c_scale;
+};
+void launch_ray_form(const RayFormArgs &a, double *partials, int nblocks, hipStream_t s);
+// z = -A^T y on the scaled ray (A^T, gathered ys): partials (2 x AT.grid()) of D of the columns (sum) and V of the columns (max)
+void launch_ray_col(const CsrDev &AT, const double *ys_full, const double *l, const double *u, const double *col_norm, double b_scale,
+                    double c_scale, double *partials, hipStream_t s);
+// q = A d on the scaled ray (A, gathered ds): partials (A.grid()) of W of the rows (max)
+void launch_ray_row(const CsrDev &A, const double *ds_full, const double *AL, const double *AU, const double *row_norm, double b_scale,
+                    double *partials, hipStream_t s);
 
 // x_temp = x_bar - last_x, y_temp = y_bar - last_y, squared norms -> partials (2 x stride);
 // then last_x = x = x_bar, last_y = y = y_bar and the Halpern counter is reset

@@ -30,14 +30,21 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, kWave));
+    return v;
+}
+
 // Sum NACC per-thread accumulators over the block; thread 0 stores partials[i*stride + blockIdx.x].
+// The last NMAX of them are maxima instead of sums (the ray test's violations, RayRowEpi / RayColEpi).
 // `red`: NW * NACC doubles of LDS that no lane still uses.
-template <int NACC, int NW>
+template <int NACC, int NW, int NMAX = 0>
 __device__ __forceinline__ void block_store_partials_in(double (&acc)[NACC], double *partials, int stride, double (*red)[NACC > 0 ? NACC : 1]) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
     for (int i = 0; i < NACC; ++i) {
-        double v = wave_sum(acc[i]);
+        double v = i < NACC - NMAX ? wave_sum(acc[i]) : wave_max(acc[i]);
         if (lane == 0) red[wave][i] = v;
     }
     __syncthreads();
@@ -46,17 +53,23 @@ __device__ __forceinline__ void block_store_partials_in(double (&acc)[NACC], dou
         for (int i = 0; i < NACC; ++i) {
             double v = red[0][i];
 #pragma unroll
-            for (int w = 1; w < NW; ++w) v += red[w][i];
+            for (int w = 1; w < NW; ++w) v = i < NACC - NMAX ? v + red[w][i] : fmax(v, red[w][i]);
             partials[(size_t)i * stride + blockIdx.x] = v;
         }
     }
 }
 
-template <int NACC, int NW = kWavesPerBlock>
+template <int NACC, int NW = kWavesPerBlock, int NMAX = 0>
 __device__ __forceinline__ void block_store_partials(double (&acc)[NACC], double *partials, int stride) {
     __shared__ double red[NW][NACC > 0 ? NACC : 1];
-    block_store_partials_in<NACC, NW>(acc, partials, stride, red);
+    block_store_partials_in<NACC, NW, NMAX>(acc, partials, stride, red);
 }
+
+// Epilogues whose last kMaxAccs accumulators are maxima (default: none)
+template <class Epi, class = void>
+struct MaxAccs : std::integral_constant<int, 0> {};
+template <class Epi>
+struct MaxAccs<Epi, std::void_t<decltype(Epi::kMaxAccs)>> : std::integral_constant<int, Epi::kMaxAccs> {};
 
 // Order LDS traffic between lanes of one wave (no s_barrier needed: one wave's DS ops are in order).
 __device__ __forceinline__ void wave_lds_sync() {
@@ -267,7 +280,7 @@ __global__ void __launch_bounds__(kThreads) k_spmv_fused(CsrDev A, Epi epi) {
             }
         }
     }
-    if constexpr (NACC > 0) block_store_partials<NACC>(acc, epi.partials, epi.stride);
+    if constexpr (NACC > 0) block_store_partials<NACC, kWavesPerBlock, MaxAccs<Epi>::value>(acc, epi.partials, epi.stride);
 }
 
 
@@ -848,7 +861,7 @@ __global__ void __launch_bounds__(kTileThreads, 4) k_tiled_fused(CsrDev A, Epi e
         // the tile buffer is the scratch of the block reduction: a separate array would push the workgroup past
         // 80 KiB of LDS and leave ONE workgroup per CU (measured: 0.92 instead of 0.73 ms per launch)
         __syncthreads();
-        block_store_partials_in<NACC, kTileThreads / kWave>(racc, epi.partials, epi.stride, reinterpret_cast<double(*)[NACC]>(ytile));
+        block_store_partials_in<NACC, kTileThreads / kWave, MaxAccs<Epi>::value>(racc, epi.partials, epi.stride, reinterpret_cast<double(*)[NACC]>(ytile));
     }
 }
 
@@ -923,7 +936,7 @@ __global__ void __launch_bounds__(kTileThreads, 4) k_pb_fused(CsrDev A, Epi epi)
 #undef PB_STAMP
     if constexpr (NACC > 0) {
         __syncthreads();
-        block_store_partials_in<NACC, kTileThreads / kWave>(racc, epi.partials, epi.stride, reinterpret_cast<double(*)[NACC]>(prod));
+        block_store_partials_in<NACC, kTileThreads / kWave, MaxAccs<Epi>::value>(racc, epi.partials, epi.stride, reinterpret_cast<double(*)[NACC]>(prod));
     }
 }
 
@@ -990,7 +1003,7 @@ __global__ void __launch_bounds__(kThreads) k_tiled_finish(CsrDev A, Epi epi) {
         typename Epi::Row rw = epi.load_row(r);
         epi.apply(r, rw, sv, racc);
     }
-    if constexpr (NACC > 0) block_store_partials<NACC>(racc, epi.partials, epi.stride);
+    if constexpr (NACC > 0) block_store_partials<NACC, kWavesPerBlock, MaxAccs<Epi>::value>(racc, epi.partials, epi.stride);
 }
 
 __global__ void __launch_bounds__(kThreads) k_tiled_refresh(long n, const int *perm, const double *csr_val, double *out) {
@@ -1418,6 +1431,62 @@ struct PlainPushEpi {
     }
 };
 
+// Infeasibility detection (Solver::ray_test, DESIGN.md "Infeasibility and unboundedness"): the two SpMVs of the ray test, in
+// original units.  The device holds A_s = diag(1/row_norm) A diag(1/col_norm), bounds divided by b_scale and cost by c_scale
+// (Solver::scale); k_unscale's map turns a scaled vector back into the caller's units.  Positive scaling keeps every bound on
+// its side, so a bound is used iff it is finite.
+//
+// Column side (rows of A^T, gathered vector y_s): z_j = -(A^T y)_j; z_j > 0 pairs with l_j, z_j < 0 with u_j.  A finite bound adds
+// its term to D = acc[0]; an infinite one leaves the multiplier as violation (maximum, acc[1]).
+struct RayColEpi {
+    static constexpr int NV = 1;
+    static constexpr int NACC = 2;
+    static constexpr int kMaxAccs = 1;  // acc[1]
+    const double *gv[1];
+    const double *l, *u, *col_norm;
+    double b_scale, c_scale;
+    double *partials;
+    int stride;
+    struct Row {
+        double lo, hi, cn;
+    };
+    __device__ __forceinline__ void begin() {}
+    __device__ __forceinline__ Row load_row(int r) const { return Row{l[r], u[r], col_norm[r]}; }
+    __device__ __forceinline__ void apply(int, const Row &w, const double (&s)[1], double (&acc)[2]) const {
+        const double z = -((s[0] * w.cn) * c_scale);
+        if (z > 0.0) {
+            if (isfinite(w.lo)) acc[0] += ((w.lo / w.cn) * b_scale) * z;
+            else acc[1] = fmax(acc[1], z);
+        } else if (z < 0.0) {
+            if (isfinite(w.hi)) acc[0] += ((w.hi / w.cn) * b_scale) * z;
+            else acc[1] = fmax(acc[1], -z);
+        }
+    }
+};
+
+// Row side (rows of A, gathered vector d_s): q_i = (A d)_i must not leave the recession cone of the finite row bounds; the
+// largest step out is the violation (maximum, acc[0]).
+struct RayRowEpi {
+    static constexpr int NV = 1;
+    static constexpr int NACC = 1;
+    static constexpr int kMaxAccs = 1;
+    const double *gv[1];
+    const double *AL, *AU, *row_norm;
+    double b_scale;
+    double *partials;
+    int stride;
+    struct Row {
+        double lo, hi, rn;
+    };
+    __device__ __forceinline__ void begin() {}
+    __device__ __forceinline__ Row load_row(int r) const { return Row{AL[r], AU[r], row_norm[r]}; }
+    __device__ __forceinline__ void apply(int, const Row &w, const double (&s)[1], double (&acc)[1]) const {
+        const double q = (s[0] * w.rn) * b_scale;
+        if (isfinite(w.lo)) acc[0] = fmax(acc[0], -q);
+        if (isfinite(w.hi)) acc[0] = fmax(acc[0], q);
+    }
+};
+
 // ------------------------------------------------------------------------------------------------
 // launch wrappers of the fused kernel
 // ------------------------------------------------------------------------------------------------
@@ -1447,7 +1516,7 @@ __global__ void __launch_bounds__(kThreads) k_long_finish(CsrDev A, Epi epi, int
     }
     if constexpr (NACC > 0) {
         // block_store_partials indexes by blockIdx.x: shift the base so that the slots follow the main kernel's
-        block_store_partials<NACC>(acc, epi.partials + main_grid, epi.stride);
+        block_store_partials<NACC, kWavesPerBlock, MaxAccs<Epi>::value>(acc, epi.partials + main_grid, epi.stride);
     }
 }
 
@@ -1663,14 +1732,40 @@ void launch_spmv_plain(const CsrDev &M, const double *v_full, double *out, const
     }
 }
 
+void launch_ray_col(const CsrDev &AT, const double *ys_full, const double *l, const double *u, const double *col_norm, double b_scale,
+                    double c_scale, double *partials, hipStream_t s) {
+    RayColEpi e{{ys_full}, l, u, col_norm, b_scale, c_scale, partials, AT.grid()};
+    launch_fused(AT, e, s);
+}
+
+void launch_ray_row(const CsrDev &A, const double *ds_full, const double *AL, const double *AU, const double *row_norm, double b_scale,
+                    double *partials, hipStream_t s) {
+    RayRowEpi e{{ds_full}, AL, AU, row_norm, b_scale, partials, A.grid()};
+    launch_fused(A, e, s);
+}
+
 // ------------------------------------------------------------------------------------------------
 // scalar finalisation: out[slot] = sum of a partial array, one block per item, fixed order
 // ------------------------------------------------------------------------------------------------
+static_assert(kWavesPerBlock == 4, "k_finalize's sum adds the four waves' partials in a fixed order");
 __global__ void __launch_bounds__(kThreads) k_finalize(FinalizeArgs f, double *scalars) {
     const FinalizeItem it = f.item[blockIdx.x];
+    __shared__ double red[kWavesPerBlock];
+    if (it.max) {  // (uniform per block) partials of nonnegative maxima
+        double v = 0.0;
+        for (int i = threadIdx.x; i < it.count; i += kThreads) v = fmax(v, it.partials[i]);
+        v = wave_max(v);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            double m = red[0];
+            for (int w = 1; w < kWavesPerBlock; ++w) m = fmax(m, red[w]);
+            scalars[it.slot] = m;
+        }
+        return;
+    }
     double v = 0.0;
     for (int i = threadIdx.x; i < it.count; i += kThreads) v += it.partials[i];
-    __shared__ double red[kWavesPerBlock];
     v = wave_sum(v);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -2403,6 +2498,49 @@ void launch_pw_err(const double *z, const double *q, int m, const double *scalar
 // ------------------------------------------------------------------------------------------------
 // unscale (reference collect_solution, src/utils.cu:172-189)
 // ------------------------------------------------------------------------------------------------
+// Infeasibility detection: the candidate rays d_s = x_bar - prev_x, y_s = y_bar - prev_y (scaled units, into the gathered vectors
+// the ray SpMVs read), prev_* <- *_bar, and the elementwise parts of the ray test in original units (k_unscale's map):
+// partials of {D over the rows, c'd} (sums) and {V over the rows, W over the columns, |y|_inf, |d|_inf} (maxima), kRayFormAccs x
+// gridDim.x.  A row with y_i > 0 pairs with AL_i, y_i < 0 with AU_i; a column's step d_j must stay inside the finite bounds' cone.
+__global__ void __launch_bounds__(kThreads) k_ray_form(RayFormArgs a, double *partials) {
+    double acc[kRayFormAccs] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const int tid = blockIdx.x * kThreads + threadIdx.x, nth = gridDim.x * kThreads;
+    for (int j = tid; j < a.n; j += nth) {
+        const double xb = a.x_bar[j];
+        const double ds = xb - a.prev_x[j];
+        a.prev_x[j] = xb;
+        a.ds[j] = ds;
+        const double cn = a.col_norm[j];
+        const double d = (ds / cn) * a.b_scale;
+        acc[1] += ((a.c[j] * cn) * a.c_scale) * d;
+        if (isfinite(a.l[j])) acc[3] = fmax(acc[3], -d);
+        if (isfinite(a.u[j])) acc[3] = fmax(acc[3], d);
+        acc[5] = fmax(acc[5], fabs(d));
+    }
+    for (int i = tid; i < a.m; i += nth) {
+        const double yb = a.y_bar[i];
+        const double ys = yb - a.prev_y[i];
+        a.prev_y[i] = yb;
+        a.ys[i] = ys;
+        const double rn = a.row_norm[i];
+        const double y = (ys / rn) * a.c_scale;
+        if (y > 0.0) {
+            const double lo = a.AL[i];
+            if (isfinite(lo)) acc[0] += ((lo * rn) * a.b_scale) * y;
+            else acc[2] = fmax(acc[2], y);
+        } else if (y < 0.0) {
+            const double hi = a.AU[i];
+            if (isfinite(hi)) acc[0] += ((hi * rn) * a.b_scale) * y;
+            else acc[2] = fmax(acc[2], -y);
+        }
+        acc[4] = fmax(acc[4], fabs(y));
+    }
+    block_store_partials<kRayFormAccs, kWavesPerBlock, 4>(acc, partials, gridDim.x);
+}
+void launch_ray_form(const RayFormArgs &a, double *partials, int nblocks, hipStream_t s) {
+    hipLaunchKernelGGL(k_ray_form, dim3(nblocks), dim3(kThreads), 0, s, a, partials);
+}
+
 __global__ void __launch_bounds__(kThreads) k_unscale(int n, int m, const double *x_bar, const double *y_bar,
                                                      const double *z_bar, const double *col_norm,
                                                      const double *row_norm, double b_scale, double c_scale, double *xo,

@@ -1999,7 +1999,7 @@ static double weighted_norm_from(Solver *s, double dot_adx_dy, double dy2, doubl
     return wn;
 }
 
-void Solver::compute_residuals(int iter, bool compute_gap, Residuals *r, RestartState *rs) {
+void Solver::compute_residuals(int iter, bool compute_gap, Residuals *r, RestartState *rs, bool *ray) {
     invalidate_far();  // the residual SpMVs refill the remainder buffers for x_bar / y_bar
     finish_tiling();
     const int gx = AT.view.grid(), gyy = A.view.grid();
@@ -2020,6 +2020,7 @@ void Solver::compute_residuals(int iter, bool compute_gap, Residuals *r, Restart
     launch_finalize(f, scal.p, stream);
     allreduce_slots(this, S_CX, 8);
     if (iter == 0) allreduce_slots(this, S_LU2, 1);
+    if (ray) *ray = ray_test();  // (its scalars ride on the fetch below)
     fetch_scalars();
 
     const double obj_scale = b_scale * c_scale;
@@ -2131,6 +2132,8 @@ void Solver::solve_loop(HPRLP_results *out) {
     *out = HPRLP_results();
     std::string status = "CONTINUE";
     trace_n = 0;
+    cert = Certificate();
+    if (detect.on) ray_begin();
     if (verbose)
         std::cout << " iter     errRp        errRd         p_obj            d_obj          gap         sigma       time\n"
                   << std::flush;
@@ -2138,7 +2141,9 @@ void Solver::solve_loop(HPRLP_results *out) {
     while (true) {
         const bool at_limit = iter >= max_iter;
         const bool periodic = (iter % check_iter == 0);
-        compute_residuals(iter, periodic && iter > 0, &r, &rs);
+        bool ray = false;
+        compute_residuals(iter, periodic && iter > 0, &r, &rs, detect.on && periodic && iter > 0 ? &ray : nullptr);
+        const int verdict = ray ? ray_verdict() : 0;
         const double elapsed = t_before + time_since(t_loop);
         bool timed_out = elapsed > prm.time_limit;
         if (comm && comm->size > 1) {
@@ -2152,6 +2157,8 @@ void Solver::solve_loop(HPRLP_results *out) {
             timed_out = scal_h[S_TMP1] > 0.0;
         }
         if (r.kkt < prm.stop_tol) status = "OPTIMAL";
+        else if (verdict == 1) status = "PRIMAL_INFEASIBLE";
+        else if (verdict == 2) status = "DUAL_INFEASIBLE";
         else if (at_limit) status = "ITER_LIMIT";
         else if (timed_out) status = "TIME_LIMIT";
         if (periodic && !at_limit) check_restart(&rs, iter, check_iter, sigma, verbose);
@@ -2177,7 +2184,10 @@ void Solver::solve_loop(HPRLP_results *out) {
         mark(first4, 1e-4, out->iter4, out->time4, "1e-4");
         mark(first6, 1e-6, out->iter6, out->time6, "1e-6");
         mark(first8, 1e-8, out->iter8, out->time8, "1e-8");
-        if (status != "CONTINUE") break;
+        if (status != "CONTINUE") {
+            if (verdict && status != "OPTIMAL") collect_certificate(verdict, iter);
+            break;
+        }
 
         const int flag = rs.flag;
         update_sigma_and_restart(&rs, r);
@@ -2233,6 +2243,98 @@ void Solver::collect_solution(HPRLP_results *out) {
         unpermute(out->x, perm_c);
         unpermute(out->z, perm_c);
         unpermute(out->y, perm_r);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// infeasibility detection (DESIGN.md "Infeasibility and unboundedness"): Farkas ratio tests on the difference of the projected
+// iterates between two periodic evaluations, in the caller's units.  Single GPU only (abi.cpp refuses sharded solvers).
+// ------------------------------------------------------------------------------------------------
+void Solver::ray_begin() {
+    if (comm) throw std::runtime_error("infeasibility detection runs on one GPU only (sharded solver)");
+    if (!ray_prev_x.p) {
+        ray_prev_x.alloc_zero(static_cast<size_t>(n_loc));
+        ray_prev_y.alloc_zero(static_cast<size_t>(m_loc));
+        ray_d.alloc_zero(static_cast<size_t>(n_pad));  // gathered by the ray SpMVs: full padded length
+        ray_y.alloc_zero(static_cast<size_t>(m_pad));
+    }
+    ray_have_prev = false;
+}
+
+bool Solver::ray_test() {
+    finish_tiling();
+    const int gx = AT.view.grid(), gyy = A.view.grid();
+    const size_t need = static_cast<size_t>(kRayFormAccs) * kReduceBlocks + 2 * static_cast<size_t>(gx) + gyy;
+    if (ray_part.n < need) ray_part.alloc(need);
+    double *pf = ray_part.p, *pc = pf + static_cast<size_t>(kRayFormAccs) * kReduceBlocks, *pr = pc + 2 * static_cast<size_t>(gx);
+    const RayFormArgs a{n_loc, m_loc, x_bar, y_bar, ray_prev_x.p, ray_prev_y.p, ray_d.p, ray_y.p, l.p, u.p, c.p, col_norm.p,
+                        AL.p, AU.p, row_norm.p, b_scale, c_scale};
+    launch_ray_form(a, pf, kReduceBlocks, stream);
+    if (!ray_have_prev) {  // first periodic evaluation: only the stored iterate
+        ray_have_prev = true;
+        return false;
+    }
+    FinalizeArgs f{};
+    const int form_slots[kRayFormAccs] = {S_RAY_DY, S_RAY_CD, S_RAY_VY, S_RAY_WD, S_RAY_YN, S_RAY_DN};
+    for (int k = 0; k < kRayFormAccs; ++k) f.item[f.n++] = {pf + static_cast<size_t>(k) * kReduceBlocks, kReduceBlocks, form_slots[k], k >= 2};
+    launch_finalize(f, scal.p, stream);
+    invalidate_far();  // the ray SpMVs refill the remainder buffers
+    launch_ray_col(AT.view, ray_y.p, l.p, u.p, col_norm.p, b_scale, c_scale, pc, stream);
+    launch_ray_row(A.view, ray_d.p, AL.p, AU.p, row_norm.p, b_scale, pr, stream);
+    FinalizeArgs g{};
+    g.item[g.n++] = {pc, gx, S_RAY_DZ, 0};
+    g.item[g.n++] = {pc + gx, gx, S_RAY_VZ, 1};
+    g.item[g.n++] = {pr, gyy, S_RAY_WQ, 1};
+    launch_finalize(g, scal.p, stream);
+    return true;
+}
+
+int Solver::ray_verdict() {
+    const double D = scal_h[S_RAY_DY] + scal_h[S_RAY_DZ], V = std::max(scal_h[S_RAY_VY], scal_h[S_RAY_VZ]);
+    const double cd = scal_h[S_RAY_CD], W = std::max(scal_h[S_RAY_WD], scal_h[S_RAY_WQ]);
+    if (D > 0.0 && V <= detect.eps_primal * D) return 1;  // (NaN fails both tests)
+    if (cd < 0.0 && W <= detect.eps_dual * -cd) return 2;
+    return 0;
+}
+
+void Solver::collect_certificate(int kind, int iter) {
+    cert = Certificate();
+    cert.kind = kind;
+    cert.iter = iter;
+    std::vector<double> rn(static_cast<size_t>(m_loc)), cn(static_cast<size_t>(n_loc));
+    HIP_CHECK(hipMemcpyAsync(rn.data(), row_norm.p, sizeof(double) * m_loc, hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipMemcpyAsync(cn.data(), col_norm.p, sizeof(double) * n_loc, hipMemcpyDeviceToHost, stream));
+    auto unpermute = [](std::vector<double> &v, const std::vector<int> &perm) {
+        if (perm.empty()) return;
+        const std::vector<double> tmp(v);
+        for (size_t i = 0; i < perm.size(); ++i) v[perm[i]] = tmp[i];
+    };
+    if (kind == 1) {
+        // y and z = -A^T y of the ray, as k_unscale maps y_bar and z_bar; A^T y_s into scratch sn1 by the plain product
+        const double D = scal_h[S_RAY_DY] + scal_h[S_RAY_DZ], V = std::max(scal_h[S_RAY_VY], scal_h[S_RAY_VZ]);
+        const double yn = scal_h[S_RAY_YN];
+        invalidate_far();
+        launch_spmv_plain(AT.view, ray_y.p, sn1.p, nullptr, false, nullptr, 0, stream);
+        cert.y.resize(static_cast<size_t>(m_loc));
+        cert.z.resize(static_cast<size_t>(n_loc));
+        HIP_CHECK(hipMemcpyAsync(cert.y.data(), ray_y.p, sizeof(double) * m_loc, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipMemcpyAsync(cert.z.data(), sn1.p, sizeof(double) * n_loc, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        for (int i = 0; i < m_loc; ++i) cert.y[i] = ((cert.y[i] / rn[i]) * c_scale) / yn;
+        for (int j = 0; j < n_loc; ++j) cert.z[j] = -((cert.z[j] * cn[j]) * c_scale) / yn;
+        cert.objective = D / yn;
+        cert.violation = V / yn;
+        unpermute(cert.y, perm_r);
+        unpermute(cert.z, perm_c);
+    } else {
+        const double cd = scal_h[S_RAY_CD], W = std::max(scal_h[S_RAY_WD], scal_h[S_RAY_WQ]), dn = scal_h[S_RAY_DN];
+        cert.d.resize(static_cast<size_t>(n_loc));
+        HIP_CHECK(hipMemcpyAsync(cert.d.data(), ray_d.p, sizeof(double) * n_loc, hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        for (int j = 0; j < n_loc; ++j) cert.d[j] = ((cert.d[j] / cn[j]) * b_scale) / dn;
+        cert.objective = cd / dn;
+        cert.violation = W / dn;
+        unpermute(cert.d, perm_c);
     }
 }
 

@@ -4,6 +4,7 @@
 #pragma once
 
 #include <string>
+#include <vector>
 
 #include <functional>
 #include <future>
@@ -31,6 +32,19 @@ struct RestartState {  // reference HPRLP_restart, include/structs.h:215-228
     double best_gap = std::numeric_limits<double>::infinity();
     double best_sigma = 1.0;
     int inner = 0, sufficient = 0, necessary = 0, long_ = 0, times = 0;
+};
+
+// Infeasibility detection (opt-in, one GPU; DESIGN.md "Infeasibility and unboundedness"): the Farkas ratio tests' tolerances ...
+struct Detection {
+    bool on = false;
+    double eps_primal = 1e-8, eps_dual = 1e-8;
+};
+// ... and what a verdict leaves: kind 1 (primal infeasible: y, z = -A^T y) or 2 (dual infeasible: d), the ray in the caller's
+// units and numbering, scaled to infinity norm 1; objective = D(y) resp. c'd, violation = V(y) resp. W(d) of that ray
+struct Certificate {
+    int kind = 0, iter = 0;
+    double objective = 0.0, violation = 0.0;
+    std::vector<double> y, z, d;
 };
 
 struct TraceRow {  // same layout as hprlp_trace_row in include/hprlp_amd.h
@@ -168,6 +182,18 @@ struct Solver {
     DBuf<int> small_order_x, small_order_y;  // rows of A^T / A sorted by length (row ownership in small.hip)
     DBuf<int> small_ij, small_posA;          // per A^T entry: i | j << 16, position in the CSR order of A
 
+    // Infeasibility detection: at every periodic evaluation the rays d = x_bar - x_bar(previous evaluation), y = y_bar - y_bar(...)
+    // pass the ratio tests or not (ray_test enqueues, ray_verdict judges after the evaluation's scalar fetch).  The buffers exist
+    // only while detection is on; nothing the iteration reads is touched, so the iterates are the same bits either way.
+    Detection detect;
+    DBuf<double> ray_prev_x, ray_prev_y, ray_d, ray_y, ray_part;
+    bool ray_have_prev = false;
+    Certificate cert;  // of the last solve_loop (kind 0: no verdict)
+    void ray_begin();              // solve_loop: buffers allocated (first time) and the previous iterate forgotten
+    bool ray_test();               // enqueue the rays' kernels and reductions; false at the first evaluation (no previous iterate yet)
+    int ray_verdict();             // after fetch_scalars: 1 primal infeasible, 2 dual infeasible, 0 neither
+    void collect_certificate(int kind, int iter);
+
     std::map<int, hipGraphExec_t> graphs;
     TraceRow *trace = nullptr;
     int trace_cap = 0, trace_n = 0;
@@ -192,7 +218,8 @@ struct Solver {
     void run_normal(int count);                                     // count normal iterations (graph replay)
     void run_normal_then_check(int count);                          // count normal iterations, then one check-variant iteration
     void fetch_scalars();
-    void compute_residuals(int iter, bool compute_gap, Residuals *r, RestartState *rs);  // main_iterate.cu:229-309
+    // main_iterate.cu:229-309; ray: also the infeasibility detection's ray test (detect.on only), read by ray_verdict()
+    void compute_residuals(int iter, bool compute_gap, Residuals *r, RestartState *rs, bool *ray = nullptr);
     double weighted_norm_after_restart();                           // main_iterate.cu:486-515
     void update_sigma_and_restart(RestartState *rs, const Residuals &r);  // main_iterate.cu:312-322,367-404
     void solve_loop(HPRLP_results *out);                            // src/HPRLP.cu:154-310

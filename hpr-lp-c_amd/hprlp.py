@@ -77,6 +77,15 @@ class CTraceRow(C.Structure):
     ]
 
 
+class CDetection(C.Structure):  # hprlp_detection (include/hprlp_amd.h, 16 bytes)
+    _fields_ = [("eps_primal_infeasible", C.c_double), ("eps_dual_infeasible", C.c_double)]
+
+
+class CCertificate(C.Structure):  # hprlp_certificate (include/hprlp_amd.h, 56 bytes)
+    _fields_ = [("kind", C.c_int), ("iter", C.c_int), ("m", C.c_int), ("n", C.c_int),
+                ("objective", C.c_double), ("violation", C.c_double), ("y", c_dbl_p), ("z", c_dbl_p), ("d", c_dbl_p)]
+
+
 _lib = None
 _libc = C.CDLL(None)
 _libc.free.argtypes = [C.c_void_p]
@@ -134,6 +143,11 @@ def lib():
     L.hprlp_presolve_postsolve.argtypes = [C.c_void_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]
     L.hprlp_presolve_free.argtypes = [C.c_void_p]
     L.hprlp_original_kkt.argtypes = [C.POINTER(CLPInfo), c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]
+    L.hprlp_solve_detect.restype = CResults
+    L.hprlp_solve_detect.argtypes = [C.POINTER(CLPInfo), C.POINTER(CParameters), C.POINTER(CDetection), C.POINTER(CCertificate)]
+    L.hprlp_free_certificate.argtypes = [C.POINTER(CCertificate)]
+    L.hprlp_solver_set_detection.argtypes = [C.c_void_p, C.POINTER(CDetection)]
+    L.hprlp_solver_get_certificate.argtypes = [C.c_void_p, C.POINTER(CCertificate)]
     _lib = L
     return L
 
@@ -198,6 +212,28 @@ class Results:
         self.x = _take(cres.x, n)
         self.y = _take(cres.y, m)
         self.z = _take(cres.z, n)
+
+
+class Certificate:
+    """Infeasibility certificate (hprlp_certificate): kind 0 none, 1 primal infeasible (y, z = -A^T y), 2 dual infeasible (d);
+    the ray has infinity norm 1, objective / violation are D(y), V(y) resp. c'd, W(d) of it (include/hprlp_amd.h)."""
+
+    KINDS = {0: None, 1: "PRIMAL_INFEASIBLE", 2: "DUAL_INFEASIBLE"}
+
+    def __init__(self, cc):
+        self.kind, self.iter, self.m, self.n = cc.kind, cc.iter, cc.m, cc.n
+        self.objective, self.violation = cc.objective, cc.violation
+        g = lambda p, k: np.ctypeslib.as_array(p, shape=(k,)).copy() if p else None
+        self.y, self.z, self.d = g(cc.y, cc.m), g(cc.z, cc.n), g(cc.d, cc.n)
+        lib().hprlp_free_certificate(C.byref(cc))
+
+    @property
+    def verdict(self):
+        return self.KINDS.get(self.kind)
+
+
+def _detection(eps_primal, eps_dual):
+    return CDetection(float(eps_primal), float(eps_dual))
 
 
 class Model:
@@ -268,6 +304,18 @@ class Model:
         wall = time.perf_counter() - t0
         r = Results(res, self.m, self.n)
         r.c_call_wall_s = wall  # the caller's clock around the C call alone (before the solution vectors are wrapped)
+        return r
+
+    def solve_detect(self, param=None, eps_primal=1e-8, eps_dual=1e-8):
+        """solve() with infeasibility detection (hprlp_solve_detect): status PRIMAL_INFEASIBLE / DUAL_INFEASIBLE with the
+        certificate in `.certificate`.  eps_primal=None and eps_dual=None: detection off (exactly solve())."""
+        cp = (param or Parameters()).to_c()
+        det = None if eps_primal is None and eps_dual is None else _detection(
+            1e-8 if eps_primal is None else eps_primal, 1e-8 if eps_dual is None else eps_dual)
+        cc = CCertificate()
+        res = lib().hprlp_solve_detect(self._ptr, C.byref(cp), C.byref(det) if det is not None else None, C.byref(cc))
+        r = Results(res, self.m, self.n)
+        r.certificate = Certificate(cc)
         return r
 
     def free(self):
@@ -575,6 +623,17 @@ class Solver:
         r = Results(res, getattr(self, "m_loc", self.model.m), getattr(self, "n_loc", self.model.n))
         r.trace = [{f: getattr(trace[i], f) for f, _ in CTraceRow._fields_} for i in range(nt.value)]
         return r
+
+    def set_detection(self, eps_primal=1e-8, eps_dual=1e-8, on=True):
+        """Infeasibility detection for the following run() calls (hprlp_solver_set_detection); on=False switches it off."""
+        det = _detection(eps_primal, eps_dual) if on else None
+        self._chk(lib().hprlp_solver_set_detection(self.h, C.byref(det) if det is not None else None))
+
+    def certificate(self):
+        """The certificate of the last run() (kind 0 without a verdict)."""
+        cc = CCertificate()
+        self._chk(lib().hprlp_solver_get_certificate(self.h, C.byref(cc)))
+        return Certificate(cc)
 
     def time_iterations(self, warmup, steps, mode=0):
         t = C.c_double(0); tx = C.c_double(0); ty = C.c_double(0)

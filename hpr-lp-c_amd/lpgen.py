@@ -400,3 +400,107 @@ FAMILIES_LARGE = {
     "cont_like": lambda: pde_control_lp(700, 43),
     "staircase": lambda: staircase_lp(200, 3000, 4500, 8, 44),
 }
+
+
+# ---- infeasible and unbounded LPs with a certificate known by construction (infeasibility detection) ----------------
+def _random_matrix(rng, m, n, nnz):
+    rows, cols = _pattern(rng, m, n, nnz, dense_col_frac=0.02)
+    v = rng.normal(size=len(rows)) * 10.0 ** rng.uniform(-0.5, 0.5, size=len(rows))
+    v[np.abs(v) < 1e-2] = 1e-2
+    A = sparse.csr_matrix((v, (rows, cols)), shape=(m, n))
+    A.sort_indices()
+    return A
+
+
+def _as_lp(A, AL, AU, l, u, c, **extra):
+    out = dict(m=A.shape[0], n=A.shape[1], A=A, rowptr=A.indptr.astype(np.int32), colind=A.indices.astype(np.int32),
+               values=A.data.astype(np.float64), AL=np.asarray(AL, float), AU=np.asarray(AU, float), l=np.asarray(l, float),
+               u=np.asarray(u, float), c=np.asarray(c, float))
+    out.update(extra)
+    return out
+
+
+def planted_infeasible_lp(m, n, nnz, seed, A=None):
+    """Primal infeasible LP with a Farkas ray y* (returned as `y_cert`, z* = -A'y* as `z_cert`).  A feasible LP is built around
+    a point x0 with a finite bound wherever y* and z* need one (row i: AL_i if y*_i > 0, AU_i if y*_i < 0; column j: l_j if
+    z*_j > 0, u_j if z*_j < 0), the other sides finite or not at random; then one bound of a row with y*_i != 0 moves until
+    D(y*) = sum of the bound terms is 1 % of sum |bound term| (> 0): Farkas says no x satisfies the rows and bounds, and the
+    violation V(y*) is 0.  A (optional, m x n csr): the matrix instead of a random one of nnz entries."""
+    rng = np.random.default_rng(seed)
+    A = _random_matrix(rng, m, n, nnz) if A is None else sparse.csr_matrix(A)
+    y = rng.normal(size=m) * (rng.random(m) < 0.7)
+    z = -(A.T @ y)
+    x0 = rng.uniform(-1.0, 2.0, size=n)
+    b = A @ x0
+    AL = np.where((y > 0) | (rng.random(m) < 0.3), b - rng.uniform(0.0, 1.0, m), -np.inf)
+    AU = np.where((y < 0) | (rng.random(m) < 0.3), b + rng.uniform(0.0, 1.0, m), np.inf)
+    eq = (rng.random(m) < 0.2) & np.isfinite(AL) & np.isfinite(AU)
+    AL[eq] = AU[eq] = b[eq]
+    l = np.where((z > 0) | (rng.random(n) < 0.5), x0 - rng.uniform(0.0, 1.0, n), -np.inf)
+    u = np.where((z < 0) | (rng.random(n) < 0.3), x0 + rng.uniform(0.0, 1.0, n), np.inf)
+    terms = farkas_terms(y, z, AL, AU, l, u)
+    D = terms.sum()
+    i = int(np.argmax(np.abs(y)))
+    shift = (-D + 0.01 * np.abs(terms).sum()) / abs(y[i])   # D(y*) after the shift: 1 % of the terms' magnitudes
+    if y[i] > 0:
+        AL[i] += shift
+        AU[i] = max(AU[i], AL[i])
+    else:
+        AU[i] -= shift
+        AL[i] = min(AL[i], AU[i])
+    c = rng.normal(size=n)
+    return _as_lp(A, AL, AU, l, u, c, y_cert=y, z_cert=z, family="planted infeasible")
+
+
+def farkas_terms(y, z, AL, AU, l, u):
+    """Bound terms of D(y) = sum_{y_i>0} AL_i y_i + sum_{y_i<0} AU_i y_i + sum_{z_j>0} l_j z_j + sum_{z_j<0} u_j z_j (finite bounds)."""
+    def side(v, lo, hi):
+        t = np.zeros_like(v)
+        p, q = (v > 0) & np.isfinite(lo), (v < 0) & np.isfinite(hi)
+        t[p] = lo[p] * v[p]
+        t[q] = hi[q] * v[q]
+        return t
+    return np.concatenate([side(y, AL, AU), side(z, l, u)])
+
+
+def planted_unbounded_lp(m, n, nnz, seed, A=None):
+    """Dual infeasible (unbounded) LP with a recession direction d* (returned as `d_cert`): a feasible point x0, a direction d*
+    on a third of the columns, every bound that d* or q = A d* would leave made infinite (column j: u_j if d*_j > 0, l_j if
+    d*_j < 0; row i: AU_i if q_i > 0, AL_i if q_i < 0; rows with q_i = 0 keep both), and a cost with c'd* = -|d*|_1.  A (optional):
+    as for planted_infeasible_lp."""
+    rng = np.random.default_rng(seed)
+    A = _random_matrix(rng, m, n, nnz) if A is None else sparse.csr_matrix(A)
+    d = np.where(rng.random(n) < 0.33, rng.uniform(-1.0, 1.0, n), 0.0)
+    q = A @ d
+    x0 = rng.uniform(-1.0, 2.0, size=n)
+    b = A @ x0
+    AL = np.where(rng.random(m) < 0.7, b - rng.uniform(0.0, 1.0, m), -np.inf)
+    AU = np.where(rng.random(m) < 0.7, b + rng.uniform(0.0, 1.0, m), np.inf)
+    AU[q > 0] = np.inf
+    AL[q < 0] = -np.inf
+    l = np.where(rng.random(n) < 0.8, x0 - rng.uniform(0.0, 1.0, n), -np.inf)
+    u = np.where(rng.random(n) < 0.5, x0 + rng.uniform(0.0, 1.0, n), np.inf)
+    u[d > 0] = np.inf
+    l[d < 0] = -np.inf
+    c = 0.1 * rng.normal(size=n)
+    c -= (c @ d + np.abs(d).sum()) / (d @ d) * d   # c'd* = -|d*|_1
+    return _as_lp(A, AL, AU, l, u, c, d_cert=d, family="planted unbounded")
+
+
+def transportation_lp(supply, demand, seed, fixed=0):
+    """Transportation LP: ship from len(supply) sources to len(demand) sinks at random unit costs, x >= 0; rows sum_j x_ij <=
+    supply_i, sum_i x_ij >= demand_j.  With sum(supply) < sum(demand) it is infeasible: y = -1 on the supply rows, +1 on the
+    demand rows (returned as `y_cert`) gives z = -A'y = 0 and D(y) = sum(demand) - sum(supply) > 0.  fixed > 0: the first
+    `fixed` shipments are fixed at one unit (l = u = 1; z_j = 0 leaves them out of D) -- columns a presolver removes."""
+    rng = np.random.default_rng(seed)
+    S, T = len(supply), len(demand)
+    rows = np.concatenate([np.repeat(np.arange(S), T), S + np.tile(np.arange(T), S)])
+    cols = np.concatenate([np.arange(S * T), np.arange(S * T)])
+    A = sparse.csr_matrix((np.ones(2 * S * T), (rows, cols)), shape=(S + T, S * T))
+    A.sort_indices()
+    AL = np.concatenate([np.full(S, -np.inf), np.asarray(demand, float)])
+    AU = np.concatenate([np.asarray(supply, float), np.full(T, np.inf)])
+    y = np.concatenate([-np.ones(S), np.ones(T)])
+    l, u = np.zeros(S * T), np.full(S * T, np.inf)
+    l[:fixed] = u[:fixed] = 1.0
+    return _as_lp(A, AL, AU, l, u, rng.uniform(1.0, 5.0, S * T), y_cert=y, z_cert=np.zeros(S * T), family="transportation")

@@ -73,6 +73,39 @@ double hprlp_solver_weighted_norm(hprlp_solver *s);
 /* the whole loop from the current state (reference src/HPRLP.cu:154-310) + collect_solution */
 int hprlp_solver_run(hprlp_solver *s, HPRLP_results *out, hprlp_trace_row *trace, int max_trace, int *n_trace);
 
+/* ---- infeasibility detection (opt-in, one GPU; DESIGN.md "Infeasibility and unboundedness") ------------------------------
+ * At every periodic evaluation (iter % check_iter == 0, iter > 0) the differences of the projected iterates since the previous
+ * one, d = x_bar - x_bar' and y = y_bar - y_bar', are put to the Farkas ratio tests in the caller's units:
+ *   primal infeasible: D(y) > 0 and V(y) <= eps_primal_infeasible * D(y), with z = -A^T y,
+ *     D = sum_{y_i>0} AL_i y_i + sum_{y_i<0} AU_i y_i + sum_{z_j>0} l_j z_j + sum_{z_j<0} u_j z_j (finite bounds only),
+ *     V = the largest multiplier whose bound is infinite;
+ *   dual infeasible: c'd < 0 and W(d) <= eps_dual_infeasible * (-c'd), W = the largest step of Ad or d out of a finite bound.
+ * A verdict ends the solve with status "PRIMAL_INFEASIBLE" / "DUAL_INFEASIBLE" (OPTIMAL takes precedence, both take precedence
+ * over ITER_LIMIT / TIME_LIMIT); x, y, z of the result are the last iterate.  PDLP's tolerance 1e-8 is a good default. */
+typedef struct hprlp_detection {
+    double eps_primal_infeasible, eps_dual_infeasible;
+} hprlp_detection;
+/* kind 0: no verdict; 1: primal infeasible, y (m) and z = -A^T y (n); 2: dual infeasible, d (n).  The ray is scaled to infinity
+ * norm 1; objective = D(y) resp. c'd of it, violation = V(y) resp. W(d).  iter: the evaluation that found it.  y, z, d are
+ * malloc'd (NULL where the kind does not use them): release with hprlp_free_certificate. */
+typedef struct hprlp_certificate {
+    int kind;
+    int iter, m, n;
+    double objective, violation;
+    double *y, *z, *d;
+} hprlp_certificate;
+/* solve() with detection.  det == NULL: exactly solve().  cert (may be NULL) always gets m, n of `model` and kind 0 unless a
+ * verdict was reached.  With use_presolve and a reduced model whose solve ends in a verdict, the original model is solved
+ * again with detection within the remaining time and iteration limits: a certificate always refers to the model passed. */
+HPRLP_results hprlp_solve_detect(const LP_info_cpu *model, const HPRLP_parameters *param, const hprlp_detection *det,
+                                 hprlp_certificate *cert);
+void hprlp_free_certificate(hprlp_certificate *cert);
+/* detection for the following hprlp_solver_run calls (NULL: off).  -1 + hprlp_last_error() for a sharded solver
+ * (hprlp_solver_create_dist*, hprlp_solver_create_local*). */
+int hprlp_solver_set_detection(hprlp_solver *s, const hprlp_detection *det);
+/* the certificate of the last hprlp_solver_run (kind 0 without a verdict) */
+int hprlp_solver_get_certificate(hprlp_solver *s, hprlp_certificate *cert);
+
 /* Named device vectors: x y x_hat x_bar y_bar z_bar x_temp y_temp y_obj last_x last_y AL AU l u c
  * row_norm col_norm A_val AT_val.  get returns the length (or -1); cap is the capacity of out. */
 long hprlp_solver_get_vector(hprlp_solver *s, const char *name, double *out, long cap);
