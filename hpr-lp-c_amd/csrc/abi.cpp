@@ -488,6 +488,87 @@ extern "C" void hprlp_free_certificate(hprlp_certificate *cert) {
     cert->kind = 0;
 }
 
+// sizes and zeroed per-member arrays (kind 0 for every member), no ray arrays; false when the host allocation failed
+static bool clear_batched_certificates(hprlp_batched_certificates *c, int B, int m, int n) {
+    std::memset(c, 0, sizeof(*c));
+    c->batch_size = B;
+    c->m = m;
+    c->n = n;
+    if (B <= 0) return true;
+    c->kind = static_cast<int *>(std::calloc(B, sizeof(int)));
+    c->iter = static_cast<int *>(std::calloc(B, sizeof(int)));
+    c->objective = static_cast<double *>(std::calloc(B, sizeof(double)));
+    c->violation = static_cast<double *>(std::calloc(B, sizeof(double)));
+    return c->kind && c->iter && c->objective && c->violation;
+}
+
+// one Certificate per member -> column-major arrays (a member's columns stay zero where its kind does not use them)
+static bool export_batched_certificates(const std::vector<Certificate> &k, hprlp_batched_certificates *c) {
+    const int B = c->batch_size;
+    const size_t m = static_cast<size_t>(c->m), n = static_cast<size_t>(c->n);
+    bool any_y = false, any_d = false;
+    for (int j = 0; j < B && j < static_cast<int>(k.size()); ++j) {
+        c->kind[j] = k[j].kind;
+        c->iter[j] = k[j].iter;
+        c->objective[j] = k[j].objective;
+        c->violation[j] = k[j].violation;
+        any_y = any_y || k[j].kind == 1;
+        any_d = any_d || k[j].kind == 2;
+    }
+    auto panel = [B](size_t rows, double **out) {
+        *out = static_cast<double *>(std::calloc(std::max<size_t>(rows * B, 1), sizeof(double)));
+        return *out != nullptr;
+    };
+    if ((any_y && (!panel(m, &c->y) || !panel(n, &c->z))) || (any_d && !panel(n, &c->d))) return false;
+    for (int j = 0; j < B && j < static_cast<int>(k.size()); ++j) {
+        if (k[j].kind == 1) {
+            std::memcpy(c->y + j * m, k[j].y.data(), sizeof(double) * m);
+            std::memcpy(c->z + j * n, k[j].z.data(), sizeof(double) * n);
+        } else if (k[j].kind == 2) {
+            std::memcpy(c->d + j * n, k[j].d.data(), sizeof(double) * n);
+        }
+    }
+    return true;
+}
+
+extern "C" HPRLP_batched_results hprlp_solve_batched_detect(const LP_info_cpu *model, int batch_size, const double *C,
+                                                            const double *AL, const double *AU, const double *l, const double *u,
+                                                            const double *obj_constants, const HPRLP_parameters *param,
+                                                            const hprlp_detection *det, hprlp_batched_certificates *certs) {
+    const int m = model ? model->m : 0, n = model ? model->n : 0, B = std::max(batch_size, 0);
+    try {
+        if (certs && !clear_batched_certificates(certs, B, m, n)) {
+            hprlp_free_batched_certificates(certs);
+            throw std::runtime_error("host allocation of the certificates failed");
+        }
+        if (!det) return solve_batched(model, batch_size, C, AL, AU, l, u, obj_constants, param);
+        Detection d;
+        detection_from(det, &d);
+        std::vector<Certificate> k;
+        HPRLP_batched_results r = solve_batched_impl(model, batch_size, C, AL, AU, l, u, obj_constants, param, &d, certs ? &k : nullptr);
+        if (certs && !export_batched_certificates(k, certs)) {
+            free_batched_results(&r);
+            hprlp_free_batched_certificates(certs);
+            throw std::runtime_error("host allocation of the certificates failed");
+        }
+        return r;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        std::cerr << "[error] hprlp_solve_batched_detect failed: " << e.what() << std::endl;
+        return make_batched_error("ERROR", m, n, B);
+    }
+}
+
+extern "C" void hprlp_free_batched_certificates(hprlp_batched_certificates *certs) {
+    if (!certs) return;
+    for (void *p : {static_cast<void *>(certs->kind), static_cast<void *>(certs->iter), static_cast<void *>(certs->objective),
+                    static_cast<void *>(certs->violation), static_cast<void *>(certs->y), static_cast<void *>(certs->z),
+                    static_cast<void *>(certs->d)})
+        std::free(p);
+    certs->kind = certs->iter = nullptr;
+    certs->objective = certs->violation = certs->y = certs->z = certs->d = nullptr;
+}
+
 // presolve as separate steps (host only; used by the CPU tests and by callers that want the maps)
 struct hprlp_presolve {
     Presolve p;

@@ -35,6 +35,9 @@ constexpr double kInfReplacement = 1.0e100;  // reference batched_solver.cu:17
 enum BSlot : int {  // per-problem scalar slots, SC[slot*Bp + k]
     B_CX = 0, B_YOBJ_Y, B_XZ, B_RD2, B_RP2, B_ADX_DY, B_DY2, B_DX2, B_MOVE_X2, B_MOVE_Y2, B_LU2, B_NSLOT
 };
+enum BRaySlot : int {  // infeasibility detection only, after the slots above: kb_ray_form's six, kb_ray_col's two, kb_ray_row's one
+    B_RAY_DY = B_NSLOT, B_RAY_CD, B_RAY_VY, B_RAY_WD, B_RAY_YN, B_RAY_DN, B_RAY_DZ, B_RAY_VZ, B_RAY_WQ, B_NSLOT_DETECT
+};
 
 struct BatchCtl {  // per-problem device scalars
     double *sigma;
@@ -74,23 +77,29 @@ __device__ __forceinline__ size_t pidx(const Geo &g, int chunk, int rows, int r,
 }
 
 // Sum `NACC` per-thread accumulators over all threads of the block that share a problem index and
-// store them to partials[(rb * NACC + i) * Bp + k] (rb: the workgroup's row block).  Fixed order => deterministic.
-template <int NACC>
+// store them to partials[(rb * NACC + i) * Bp + k] (rb: the workgroup's row block).  The last NMAX accumulators are
+// nonnegative maxima (the infeasibility detection's violations) and combine with fmax.  Fixed order => deterministic.
+template <int NACC, int NMAX = 0>
 __device__ __forceinline__ void block_store_per_problem(double (&acc)[NACC], const Geo &g, int rb, int k, bool kvalid,
                                                         double *partials) {
     __shared__ double red[4][NACC][64];
+    constexpr int kSums = NACC - NMAX;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
     for (int i = 0; i < NACC; ++i) {
         double v = acc[i];
-        for (int off = 32; off >= g.Bw; off >>= 1) v += __shfl_xor(v, off, 64);  // combine sub-rows of the wave
+        for (int off = 32; off >= g.Bw; off >>= 1) {  // combine sub-rows of the wave
+            const double o = __shfl_xor(v, off, 64);
+            v = i < kSums ? v + o : fmax(v, o);
+        }
         red[wave][i][lane] = v;
     }
     __syncthreads();
     if (wave == 0 && lane < g.Bw && kvalid) {
 #pragma unroll
         for (int i = 0; i < NACC; ++i) {
-            const double v = ((red[0][i][lane] + red[1][i][lane]) + red[2][i][lane]) + red[3][i][lane];
+            const double v = i < kSums ? ((red[0][i][lane] + red[1][i][lane]) + red[2][i][lane]) + red[3][i][lane]
+                                       : fmax(fmax(fmax(red[0][i][lane], red[1][i][lane]), red[2][i][lane]), red[3][i][lane]);
             partials[(static_cast<size_t>(rb) * NACC + i) * g.Bp + k] = v;
         }
     }
@@ -504,10 +513,150 @@ __global__ void __launch_bounds__(256) kb_restart(int n, int m, Geo g, double *X
     }
 }
 
-// SC[slot[i]*Bp + k] = sum over blocks of partials[(b*nacc + i)*Bp + k]
+// ---- infeasibility detection (hprlp_solve_batched_detect; DESIGN.md "Batched detection") ------------------------------
+// The Farkas ratio tests of Solver::ray_test, member by member in that member's units.  Scaled -> caller's units by the map of
+// the results: x = X / col_norm * b_scale[k], y = Y / row_norm * c_scale[k], z = Z * col_norm * c_scale[k]; the bound panels
+// hold AL / (row_norm b_scale[k]), l col_norm / b_scale[k] (positive factors: every bound stays on its side).
+//
+// A bound counts as finite iff its panel value is not +-kInfReplacement: the set-up writes that value where the caller passed
+// +-inf.  A caller's own bound that is +-1e100 after scaling cannot be told apart and counts as infinite too, which is how the
+// iteration already treats it (its projections see the same 1e100 either way).
+__device__ __forceinline__ bool finite_bound(double v) { return v != kInfReplacement && v != -kInfReplacement; }
+
+// kb_ray_form's accumulators are k_ray_form's (kernels.h kRayFormAccs): D of the rows, c'd (sums); V of the rows, W of the
+// columns, |y|_inf, |d|_inf (maxima)
+struct RayArgs {
+    const double *Xb, *Yb;
+    double *prevX, *prevY, *DS, *YS;  // previous evaluation's X_bar / Y_bar, and the rays (scaled units, gathered by kb_ray_col / kb_ray_row)
+    const double *L, *U, *C, *AL, *AU;
+    const double *col_norm, *row_norm;
+    const double *b_scale, *c_scale;  // per member (Bp)
+    const int *active;
+};
+
+// Active members only: DS = Xb - prevX, prevX <- Xb, YS = Yb - prevY, prevY <- Yb, and the elementwise terms of the tests in the
+// caller's units -> partials (kRayFormAccs per row block).  A frozen member's columns are left as they are: a verdict's
+// certificate is read from its DS / YS after the loop.
+__global__ void __launch_bounds__(256) kb_ray_form(int n, int m, Geo g, RayArgs a, double *partials) {
+    const Blk blk = decode_block(g);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int kl = lane % g.Bw, k = blk.chunk * g.Bw + kl;
+    const int sub = lane / g.Bw;
+    double acc[kRayFormAccs] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (a.active[k]) {
+        const double bs = a.b_scale[k], cs = a.c_scale[k];
+        const int r0 = blk.rb * g.rows_per_block + wave * g.rows_per_wave + sub, rs = blk.nrb * g.rows_per_block;
+        for (int r = r0; r < n; r += rs) {
+            const size_t t = pidx(g, blk.chunk, n, r, kl);
+            const double xb = a.Xb[t], ds = xb - a.prevX[t];
+            a.prevX[t] = xb;
+            a.DS[t] = ds;
+            const double cn = a.col_norm[r];
+            const double d = (ds / cn) * bs;
+            acc[1] += ((a.C[t] * cn) * cs) * d;
+            if (finite_bound(a.L[t])) acc[3] = fmax(acc[3], -d);
+            if (finite_bound(a.U[t])) acc[3] = fmax(acc[3], d);
+            acc[5] = fmax(acc[5], fabs(d));
+        }
+        for (int r = r0; r < m; r += rs) {
+            const size_t t = pidx(g, blk.chunk, m, r, kl);
+            const double yb = a.Yb[t], ys = yb - a.prevY[t];
+            a.prevY[t] = yb;
+            a.YS[t] = ys;
+            const double rn = a.row_norm[r];
+            const double y = (ys / rn) * cs;
+            if (y > 0.0) {  // pairs with AL
+                const double lo = a.AL[t];
+                if (finite_bound(lo)) acc[0] += ((lo * rn) * bs) * y;
+                else acc[2] = fmax(acc[2], y);
+            } else if (y < 0.0) {  // pairs with AU
+                const double hi = a.AU[t];
+                if (finite_bound(hi)) acc[0] += ((hi * rn) * bs) * y;
+                else acc[2] = fmax(acc[2], -y);
+            }
+            acc[4] = fmax(acc[4], fabs(y));
+        }
+    }
+    block_store_per_problem<kRayFormAccs, 4>(acc, g, blk.rb, k, true, partials);
+}
+
+// The SpMMs of the ray test, with kb_resid's panel geometry (a lane follows one member, rows summed in CSR order, four entries
+// in flight).  RAY_COL: rows of A^T gathering YS, z = -A^T y; D of the columns (z_j > 0 pairs with l_j, z_j < 0 with u_j; sum)
+// and V of the columns (max) -> out = partials (2 per row block).  RAY_ROW: rows of A gathering DS, q = A d; W of the rows (max)
+// -> partials.  RAY_PRODUCT: the plain product into the panel `out` for every member (the certificates' z, after the loop).
+// The kernels: kb_ray_col, kb_ray_row, kb_ray_product below.
+enum RaySpmm : int { RAY_COL = 0, RAY_ROW, RAY_PRODUCT };
+template <int MODE>
+__device__ __forceinline__ void ray_spmm(int rows, const int *__restrict__ rowptr, const int *__restrict__ col,
+                                         const double *__restrict__ val, const Geo &g, int vrows, const double *V, const double *lo,
+                                         const double *hi, const double *norm, const RayArgs &a, double *out) {
+    const Blk blk = decode_block(g);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int kl = lane % g.Bw, k = blk.chunk * g.Bw + kl;
+    const int sub = lane / g.Bw;
+    const size_t vbase = pidx(g, blk.chunk, vrows, 0, kl);
+    constexpr int NACC = MODE == RAY_COL ? 2 : 1;
+    double acc[NACC];
+#pragma unroll
+    for (int i = 0; i < NACC; ++i) acc[i] = 0.0;
+    if (MODE == RAY_PRODUCT || a.active[k]) {
+        const double bs = a.b_scale[k], cs = a.c_scale[k];
+        for (int r = blk.rb * g.rows_per_block + wave * g.rows_per_wave + sub; r < rows; r += blk.nrb * g.rows_per_block) {
+            double s = 0.0;
+            const int e = rowptr[r + 1];
+            for (int p = rowptr[r]; p < e; p += 4) {
+                double av[4], gv[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int q = min(p + u, e - 1);
+                    av[u] = val[q];
+                    gv[u] = V[vbase + static_cast<size_t>(col[q]) * g.Bw];
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+                    if (p + u < e) s += av[u] * gv[u];
+            }
+            const size_t t = pidx(g, blk.chunk, rows, r, kl);
+            if (MODE == RAY_PRODUCT) {
+                out[t] = s;
+            } else if (MODE == RAY_COL) {
+                const double cn = norm[r], z = -((s * cn) * cs);
+                if (z > 0.0) {
+                    const double l = lo[t];
+                    if (finite_bound(l)) acc[0] += ((l / cn) * bs) * z;
+                    else acc[NACC - 1] = fmax(acc[NACC - 1], z);
+                } else if (z < 0.0) {
+                    const double u = hi[t];
+                    if (finite_bound(u)) acc[0] += ((u / cn) * bs) * z;
+                    else acc[NACC - 1] = fmax(acc[NACC - 1], -z);
+                }
+            } else {
+                const double q = (s * norm[r]) * bs;
+                if (finite_bound(lo[t])) acc[0] = fmax(acc[0], -q);
+                if (finite_bound(hi[t])) acc[0] = fmax(acc[0], q);
+            }
+        }
+    }
+    if constexpr (MODE != RAY_PRODUCT) block_store_per_problem<NACC, 1>(acc, g, blk.rb, k, true, out);
+}
+
+#define HPRLP_RAY_SPMM_KERNEL(NAME, MODE)                                                                                        \
+    __global__ void __launch_bounds__(256) NAME(int rows, const int *__restrict__ rowptr, const int *__restrict__ col,        \
+                                                const double *__restrict__ val, Geo g, int vrows, const double *V,            \
+                                                const double *lo, const double *hi, const double *norm, RayArgs a, double *out) { \
+        ray_spmm<MODE>(rows, rowptr, col, val, g, vrows, V, lo, hi, norm, a, out);                                              \
+    }
+HPRLP_RAY_SPMM_KERNEL(kb_ray_col, RAY_COL)
+HPRLP_RAY_SPMM_KERNEL(kb_ray_row, RAY_ROW)
+HPRLP_RAY_SPMM_KERNEL(kb_ray_product, RAY_PRODUCT)
+#undef HPRLP_RAY_SPMM_KERNEL
+
+// SC[slot[i]*Bp + k] = sum over blocks of partials[(b*nacc + i)*Bp + k]; the maximum instead where bit i of max_mask is set
+// (partials of nonnegative maxima: kb_ray_form, kb_ray_col / kb_ray_row)
 struct BFin {
-    int slot[3];
+    int slot[6];
     int nacc;
+    unsigned max_mask;
 };
 // grid (ceil(Bp/64), nacc): a block sums one accumulator for 64 problems; its 4 waves stride over the
 // producer blocks (lane = problem: coalesced), then combine in a fixed order
@@ -516,25 +665,27 @@ __global__ void __launch_bounds__(1024) kb_finalize(const double *partials, int 
     __shared__ double red[16][64];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int k = blockIdx.x * 64 + lane, i = blockIdx.y;
+    const bool mx = (f.max_mask >> i) & 1u;  // (uniform per block)
+    auto comb = [mx](double a, double b) { return mx ? fmax(a, b) : a + b; };
     double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0;
     if (k < Bp) {
         const double *__restrict__ p = partials + static_cast<size_t>(i) * Bp + k;
         const size_t st = static_cast<size_t>(f.nacc) * Bp;
         int b = wave;
         for (; b + 48 < nblocks; b += 64) {
-            v0 += p[b * st];
-            v1 += p[(b + 16) * st];
-            v2 += p[(b + 32) * st];
-            v3 += p[(b + 48) * st];
+            v0 = comb(v0, p[b * st]);
+            v1 = comb(v1, p[(b + 16) * st]);
+            v2 = comb(v2, p[(b + 32) * st]);
+            v3 = comb(v3, p[(b + 48) * st]);
         }
-        for (; b < nblocks; b += 16) v0 += p[b * st];
+        for (; b < nblocks; b += 16) v0 = comb(v0, p[b * st]);
     }
-    red[wave][lane] = (v0 + v1) + (v2 + v3);
+    red[wave][lane] = comb(comb(v0, v1), comb(v2, v3));
     __syncthreads();
     if (wave == 0 && k < Bp) {
         double v = red[0][lane];
 #pragma unroll
-        for (int w = 1; w < 16; ++w) v += red[w][lane];
+        for (int w = 1; w < 16; ++w) v = comb(v, red[w][lane]);
         SC[static_cast<size_t>(f.slot[i]) * Bp + k] = v;
     }
 }
@@ -548,6 +699,9 @@ struct BatchWS {
     DBuf<double> sigma, SC, partials;
     DBuf<int> active, kx, ky, rflag;
     DBuf<int> order_x, order_y;  // launch order of the 4-row groups of A^T / A in kb_half64 (groups with long rows first)
+    // infeasibility detection (allocated only with it on): previous X_bar / Y_bar, the rays, the certificates' z, b/c scales
+    DBuf<double> prevX, DS, prevY, YS, Zray, bsc, csc;
+    int nslot = B_NSLOT;  // scalar slots per member (B_NSLOT_DETECT with detection on)
     HBuf<double> SC_h;
     BatchCtl ctl{};
     double lambda_max = 1.0;
@@ -574,9 +728,10 @@ int grid_for(int rows, const Geo &g) {
     return static_cast<int>(std::max(1L, std::min(need, 2048L)));
 }
 
-void finalize(BatchWS &w, int nblocks, std::initializer_list<int> slots) {
+void finalize(BatchWS &w, int nblocks, std::initializer_list<int> slots, unsigned max_mask = 0) {
     BFin f{};
     f.nacc = 0;
+    f.max_mask = max_mask;
     for (int s : slots) f.slot[f.nacc++] = s;
     hipLaunchKernelGGL(kb_finalize, dim3((w.Bp + 63) / 64, f.nacc), dim3(1024), 0, w.stream, w.partials.p, nblocks, w.Bp, f,
                        w.SC.p);
@@ -618,6 +773,10 @@ void launch_half_pair(BatchWS &w, bool check) {
 }
 
 void run_normal(BatchWS &w, int count) {
+    if (!w.shared->use_graph) {  // HPRLP_NO_GRAPH=1 (read by the shared solver's set-up): the same launches, eagerly
+        for (int i = 0; i < count; ++i) launch_half_pair(w, false);
+        return;
+    }
     while (count > 0) {
         const int len = std::min(count, 32);
         auto it = w.graphs.find(len);
@@ -639,10 +798,44 @@ void run_normal(BatchWS &w, int count) {
 }
 
 void fetch(BatchWS &w) {
-    HIP_CHECK(hipMemcpyAsync(w.SC_h.p, w.SC.p, sizeof(double) * B_NSLOT * w.Bp, hipMemcpyDeviceToHost, w.stream));
+    HIP_CHECK(hipMemcpyAsync(w.SC_h.p, w.SC.p, sizeof(double) * w.nslot * w.Bp, hipMemcpyDeviceToHost, w.stream));
     HIP_CHECK(hipStreamSynchronize(w.stream));
 }
 inline double sc(const BatchWS &w, int slot, int k) { return w.SC_h.p[static_cast<size_t>(slot) * w.Bp + k]; }
+
+RayArgs ray_args(const BatchWS &w) {
+    return RayArgs{w.Xb.p, w.Yb.p, w.prevX.p, w.prevY.p, w.DS.p, w.YS.p, w.L.p, w.U.p, w.C.p, w.AL.p, w.AU.p,
+                   w.shared->col_norm.p, w.shared->row_norm.p, w.bsc.p, w.csc.p, w.active.p};
+}
+
+// Infeasibility detection at a periodic evaluation: the active members' rays and, when `test` (every evaluation but the first,
+// which only stores X_bar / Y_bar), their ratio-test scalars into the slots B_RAY_*, fetched with the evaluation's own.
+void ray_step(BatchWS &w, bool test) {
+    const CsrDev &A = w.shared->A.view, &AT = w.shared->AT.view;
+    const Geo &g = w.geo;
+    const RayArgs a = ray_args(w);
+    const int gf = std::max(w.gx, w.gy);
+    hipLaunchKernelGGL(kb_ray_form, dim3(gf * g.nchunk), dim3(256), 0, w.stream, w.n, w.m, g, a, w.partials.p);
+    if (!test) return;
+    finalize(w, gf, {B_RAY_DY, B_RAY_CD, B_RAY_VY, B_RAY_WD, B_RAY_YN, B_RAY_DN}, 0x3cu);
+    hipLaunchKernelGGL(kb_ray_col, dim3(w.gx * g.nchunk), dim3(256), 0, w.stream, AT.rows, AT.rowptr, AT.col, AT.val, g,
+                       w.m, static_cast<const double *>(w.YS.p), static_cast<const double *>(w.L.p),
+                       static_cast<const double *>(w.U.p), static_cast<const double *>(w.shared->col_norm.p), a, w.partials.p);
+    finalize(w, w.gx, {B_RAY_DZ, B_RAY_VZ}, 0x2u);
+    hipLaunchKernelGGL(kb_ray_row, dim3(w.gy * g.nchunk), dim3(256), 0, w.stream, A.rows, A.rowptr, A.col, A.val, g,
+                       w.n, static_cast<const double *>(w.DS.p), static_cast<const double *>(w.AL.p),
+                       static_cast<const double *>(w.AU.p), static_cast<const double *>(w.shared->row_norm.p), a, w.partials.p);
+    finalize(w, w.gy, {B_RAY_WQ}, 0x1u);
+}
+
+// The verdict of member k from the fetched ray scalars: 1 primal infeasible, 2 dual infeasible, 0 neither (Solver::ray_verdict)
+int ray_verdict(const BatchWS &w, const Detection &det, int k) {
+    const double D = sc(w, B_RAY_DY, k) + sc(w, B_RAY_DZ, k), V = std::max(sc(w, B_RAY_VY, k), sc(w, B_RAY_VZ, k));
+    const double cd = sc(w, B_RAY_CD, k), W = std::max(sc(w, B_RAY_WD, k), sc(w, B_RAY_WQ, k));
+    if (D > 0.0 && V <= det.eps_primal * D) return 1;  // (NaN fails both tests)
+    if (cd < 0.0 && W <= det.eps_dual * -cd) return 2;
+    return 0;
+}
 
 // reference compute_weighted_norm :626-666.  DX/DY norms come from the slots the check step filled,
 // unless a movement pass has overwritten DX/DY since (then B_MOVE_* hold the matching norms).
@@ -711,6 +904,8 @@ int choose_chunk(int m, int n, int Bp) {
     return 64;
 }
 
+}  // namespace
+
 HPRLP_batched_results make_batched_error(const char *status, int m, int n, int B) {  // :356-368
     HPRLP_batched_results r;
     r.m = m;
@@ -724,7 +919,6 @@ HPRLP_batched_results make_batched_error(const char *status, int m, int n, int B
     return r;
 }
 
-}  // namespace
 // warm-up (abi.cpp: hprlp_warmup): an attribute query makes the runtime load this translation unit's code object now instead
 // of at the first launch of one of its kernels
 void warm_batched_tu() {
@@ -736,10 +930,12 @@ void warm_batched_tu() {
 
 using namespace hprlp;
 
-extern "C" HPRLP_batched_results solve_batched(const LP_info_cpu *model, int batch_size, const HPRLP_FLOAT *C_in,
-                                               const HPRLP_FLOAT *AL_in, const HPRLP_FLOAT *AU_in,
-                                               const HPRLP_FLOAT *l_in, const HPRLP_FLOAT *u_in,
-                                               const HPRLP_FLOAT *obj_constants, const HPRLP_parameters *param) {
+namespace hprlp {
+
+HPRLP_batched_results solve_batched_impl(const LP_info_cpu *model, int batch_size, const HPRLP_FLOAT *C_in, const HPRLP_FLOAT *AL_in,
+                                         const HPRLP_FLOAT *AU_in, const HPRLP_FLOAT *l_in, const HPRLP_FLOAT *u_in,
+                                         const HPRLP_FLOAT *obj_constants, const HPRLP_parameters *param, const Detection *det,
+                                         std::vector<Certificate> *certs) {
     if (!model || !model->A || batch_size <= 0 || !C_in || !AL_in || !AU_in || !l_in || !u_in)
         return make_batched_error("ERROR", model ? model->m : 0, model ? model->n : 0, std::max(batch_size, 0));
     const int m = model->m, n = model->n, B = batch_size;
@@ -861,9 +1057,11 @@ extern "C" HPRLP_batched_results solve_batched(const LP_info_cpu *model, int bat
         }
         for (DBuf<double> *p : {&w.X, &w.Xh, &w.Xb, &w.DX, &w.Zb, &w.lastX}) p->alloc_zero(nB);
         for (DBuf<double> *p : {&w.Y, &w.Yb, &w.DY, &w.Yobj, &w.lastY}) p->alloc_zero(mB);
-        w.SC.alloc_zero(static_cast<size_t>(B_NSLOT) * w.Bp);
-        w.SC_h.alloc(static_cast<size_t>(B_NSLOT) * w.Bp);
-        w.partials.alloc_zero(static_cast<size_t>(std::max(w.gx, w.gy)) * 3 * w.Bp);
+        const bool detect = det && det->on;
+        w.nslot = detect ? B_NSLOT_DETECT : B_NSLOT;
+        w.SC.alloc_zero(static_cast<size_t>(w.nslot) * w.Bp);
+        w.SC_h.alloc(static_cast<size_t>(w.nslot) * w.Bp);
+        w.partials.alloc_zero(static_cast<size_t>(std::max(w.gx, w.gy)) * (detect ? kRayFormAccs : 3) * w.Bp);
         w.sigma.alloc(w.Bp); w.active.alloc(w.Bp); w.kx.alloc_zero(w.Bp); w.ky.alloc_zero(w.Bp); w.rflag.alloc_zero(w.Bp);
         w.ctl = BatchCtl{w.sigma.p, w.active.p, w.kx.p, w.ky.p, w.rflag.p};
         std::vector<double> sigma(w.Bp, 1.0);
@@ -874,6 +1072,17 @@ extern "C" HPRLP_batched_results solve_batched(const LP_info_cpu *model, int bat
         }
         w.sigma.upload(sigma.data(), w.Bp);
         w.active.upload(active.data(), w.Bp);
+        if (detect) {
+            for (DBuf<double> *p : {&w.prevX, &w.DS}) p->alloc_zero(nB);
+            for (DBuf<double> *p : {&w.prevY, &w.YS}) p->alloc_zero(mB);
+            std::vector<double> bs(w.Bp, 1.0), cs(w.Bp, 1.0);
+            std::copy(b_scale.begin(), b_scale.end(), bs.begin());
+            std::copy(c_scale.begin(), c_scale.end(), cs.begin());
+            w.bsc.alloc(w.Bp);
+            w.bsc.upload(bs.data(), w.Bp);
+            w.csc.alloc(w.Bp);
+            w.csc.upload(cs.data(), w.Bp);
+        }
         HIP_CHECK(hipDeviceSynchronize());
         const double setup_time = time_since(setup_start);
 
@@ -888,6 +1097,10 @@ extern "C" HPRLP_batched_results solve_batched(const LP_info_cpu *model, int bat
         const int check_iter = std::max(actual.check_iter, 1);
         const CsrDev &A = shared.A.view, &AT = shared.AT.view;
         bool dxdy_from_movement = false;
+        // detection: a verdict's kind (1 primal, 2 dual infeasible), D resp. c'd, V resp. W, and the ray's infinity norm
+        bool ray_have_prev = false;
+        std::vector<int> verdict(B, 0);
+        std::vector<double> ray_obj(B, 0.0), ray_viol(B, 0.0), ray_norm(B, 1.0);
 
         int iter = 0;
         while (true) {  // one pass per event iteration (periodic check or iteration limit), :1017-1084
@@ -909,6 +1122,12 @@ extern "C" HPRLP_batched_results solve_batched(const LP_info_cpu *model, int bat
                                        shared.col_norm.p, w.DX.p, w.partials.p);
                     finalize(w, w.gx, {B_LU2});
                 }
+                bool ray_tested = false;
+                if (detect && iter > 0) {
+                    ray_tested = ray_have_prev;
+                    ray_step(w, ray_tested);
+                    ray_have_prev = true;
+                }
                 fetch(w);
                 for (int k = 0; k < B; ++k) {
                     // a frozen member's X_bar/Y_bar/Z_bar no longer change, so its residuals keep the
@@ -928,6 +1147,20 @@ extern "C" HPRLP_batched_results solve_batched(const LP_info_cpu *model, int bat
                         status[k] = "OPTIMAL";
                         final_iter[k] = iter;
                         active[k] = 0;
+                    }
+                if (ray_tested)
+                    for (int k = 0; k < B; ++k) {
+                        if (!active[k]) continue;  // (OPTIMAL at this evaluation takes precedence)
+                        const int v = ray_verdict(w, *det, k);
+                        if (!v) continue;
+                        status[k] = v == 1 ? "PRIMAL_INFEASIBLE" : "DUAL_INFEASIBLE";
+                        final_iter[k] = iter;
+                        active[k] = 0;
+                        verdict[k] = v;
+                        ray_obj[k] = v == 1 ? sc(w, B_RAY_DY, k) + sc(w, B_RAY_DZ, k) : sc(w, B_RAY_CD, k);
+                        ray_viol[k] = v == 1 ? std::max(sc(w, B_RAY_VY, k), sc(w, B_RAY_VZ, k))
+                                             : std::max(sc(w, B_RAY_WD, k), sc(w, B_RAY_WQ, k));
+                        ray_norm[k] = sc(w, v == 1 ? B_RAY_YN : B_RAY_DN, k);
                     }
                 w.active.upload(active.data(), w.Bp);
             }
@@ -1038,6 +1271,49 @@ extern "C" HPRLP_batched_results solve_batched(const LP_info_cpu *model, int bat
         w.Xb.download(hX.data(), nB);
         w.Yb.download(hY.data(), mB);
         w.Zb.download(hZ.data(), nB);
+        if (certs) {
+            // the certificates of the members with a verdict: their YS / DS columns have not changed since (Solver::collect_certificate)
+            certs->assign(B, Certificate());
+            bool any_y = false, any_d = false;
+            for (int k = 0; k < B; ++k) {
+                any_y = any_y || verdict[k] == 1;
+                any_d = any_d || verdict[k] == 2;
+            }
+            std::vector<double> hYS, hZS, hDS;
+            if (any_y) {  // z = -A^T y: the plain product on the device, into the scratch panel
+                w.Zray.alloc(nB);
+                hipLaunchKernelGGL(kb_ray_product, dim3(w.gx * geo.nchunk), dim3(256), 0, w.stream, AT.rows, AT.rowptr,
+                                   AT.col, AT.val, geo, m, static_cast<const double *>(w.YS.p), static_cast<const double *>(nullptr),
+                                   static_cast<const double *>(nullptr), static_cast<const double *>(nullptr), ray_args(w), w.Zray.p);
+                HIP_CHECK(hipStreamSynchronize(w.stream));
+                hYS.resize(mB);
+                hZS.resize(nB);
+                w.YS.download(hYS.data(), mB);
+                w.Zray.download(hZS.data(), nB);
+            }
+            if (any_d) {
+                hDS.resize(nB);
+                w.DS.download(hDS.data(), nB);
+            }
+            for (int k = 0; k < B; ++k) {
+                if (!verdict[k]) continue;
+                Certificate &c = (*certs)[k];
+                const double nrm = ray_norm[k];
+                c.kind = verdict[k];
+                c.iter = final_iter[k];
+                c.objective = ray_obj[k] / nrm;
+                c.violation = ray_viol[k] / nrm;
+                if (c.kind == 1) {
+                    c.y.resize(m);
+                    c.z.resize(n);
+                    for (int i = 0; i < m; ++i) c.y[i] = ((hYS[panel_index(geo, m, i, k)] / rn[i]) * c_scale[k]) / nrm;
+                    for (int j = 0; j < n; ++j) c.z[j] = -((hZS[panel_index(geo, n, j, k)] * cn[j]) * c_scale[k]) / nrm;
+                } else {
+                    c.d.resize(n);
+                    for (int j = 0; j < n; ++j) c.d[j] = ((hDS[panel_index(geo, n, j, k)] / cn[j]) * b_scale[k]) / nrm;
+                }
+            }
+        }
         HPRLP_batched_results out;
         out.m = m; out.n = n; out.batch_size = B;
         out.x = static_cast<double *>(std::malloc(sizeof(double) * static_cast<size_t>(n) * B));
@@ -1078,6 +1354,15 @@ extern "C" HPRLP_batched_results solve_batched(const LP_info_cpu *model, int bat
         std::cerr << "[error] solve_batched failed: " << e.what() << std::endl;
         return make_batched_error("ERROR", m, n, B);
     }
+}
+
+}  // namespace hprlp
+
+extern "C" HPRLP_batched_results solve_batched(const LP_info_cpu *model, int batch_size, const HPRLP_FLOAT *C_in,
+                                               const HPRLP_FLOAT *AL_in, const HPRLP_FLOAT *AU_in,
+                                               const HPRLP_FLOAT *l_in, const HPRLP_FLOAT *u_in,
+                                               const HPRLP_FLOAT *obj_constants, const HPRLP_parameters *param) {
+    return solve_batched_impl(model, batch_size, C_in, AL_in, AU_in, l_in, u_in, obj_constants, param, nullptr, nullptr);
 }
 
 extern "C" void free_batched_results(HPRLP_batched_results *results) {  // :1094-1105

@@ -86,6 +86,11 @@ class CCertificate(C.Structure):  # hprlp_certificate (include/hprlp_amd.h, 56 b
                 ("objective", C.c_double), ("violation", C.c_double), ("y", c_dbl_p), ("z", c_dbl_p), ("d", c_dbl_p)]
 
 
+class CBatchedCertificates(C.Structure):  # hprlp_batched_certificates (include/hprlp_amd.h, 72 bytes)
+    _fields_ = [("batch_size", C.c_int), ("m", C.c_int), ("n", C.c_int), ("kind", c_int_p), ("iter", c_int_p),
+                ("objective", c_dbl_p), ("violation", c_dbl_p), ("y", c_dbl_p), ("z", c_dbl_p), ("d", c_dbl_p)]
+
+
 _lib = None
 _libc = C.CDLL(None)
 _libc.free.argtypes = [C.c_void_p]
@@ -148,6 +153,10 @@ def lib():
     L.hprlp_free_certificate.argtypes = [C.POINTER(CCertificate)]
     L.hprlp_solver_set_detection.argtypes = [C.c_void_p, C.POINTER(CDetection)]
     L.hprlp_solver_get_certificate.argtypes = [C.c_void_p, C.POINTER(CCertificate)]
+    L.hprlp_solve_batched_detect.restype = CBatchedResults
+    L.hprlp_solve_batched_detect.argtypes = [C.POINTER(CLPInfo), C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p,
+                                             C.POINTER(CParameters), C.POINTER(CDetection), C.POINTER(CBatchedCertificates)]
+    L.hprlp_free_batched_certificates.argtypes = [C.POINTER(CBatchedCertificates)]
     _lib = L
     return L
 
@@ -384,6 +393,34 @@ def solve(A, AL, AU, l, u, c, param=None):
 
 def solve_batched(model, Cmat, AL, AU, l, u, obj_constants=None, param=None):
     """Cmat,l,u: (n,B) arrays; AL,AU: (m,B) arrays (any layout; passed column-major as the ABI asks)."""
+    return _batched_call(lambda B, args, cp: lib().solve_batched(model._ptr, B, *args, C.byref(cp)),
+                         model, Cmat, AL, AU, l, u, obj_constants, param)
+
+
+def solve_batched_detect(model, Cmat, AL, AU, l, u, obj_constants=None, param=None, eps_primal=1e-8, eps_dual=1e-8):
+    """solve_batched() with infeasibility detection per member (hprlp_solve_batched_detect): statuses PRIMAL_INFEASIBLE /
+    DUAL_INFEASIBLE, and "certificates": kind, iter, objective, violation (length B), y (m, B), z and d (n, B) or None; a
+    member's columns are zero where its kind does not use them.  eps_primal=None and eps_dual=None: detection off (exactly
+    solve_batched())."""
+    det = None if eps_primal is None and eps_dual is None else _detection(
+        1e-8 if eps_primal is None else eps_primal, 1e-8 if eps_dual is None else eps_dual)
+    cc = CBatchedCertificates()
+
+    def call(B, args, cp):
+        return lib().hprlp_solve_batched_detect(model._ptr, B, *args, C.byref(cp), C.byref(det) if det is not None else None,
+                                                C.byref(cc))
+    out = _batched_call(call, model, Cmat, AL, AU, l, u, obj_constants, param)
+    B, m, n = cc.batch_size, cc.m, cc.n
+    g = lambda q, k, dt=np.float64: None if not q else np.ctypeslib.as_array(q, shape=(k,)).astype(dt, copy=True)
+    panel = lambda q, rows: None if not q else g(q, rows * B).reshape(B, rows).T.copy()
+    out["certificates"] = dict(kind=g(cc.kind, B, np.int32), iter=g(cc.iter, B, np.int32), objective=g(cc.objective, B),
+                               violation=g(cc.violation, B), y=panel(cc.y, m), z=panel(cc.z, n), d=panel(cc.d, n))
+    lib().hprlp_free_batched_certificates(C.byref(cc))
+    return out
+
+
+def _batched_call(fn, model, Cmat, AL, AU, l, u, obj_constants, param):
+    """fn(B, (C, AL, AU, l, u, obj_constants) as pointers, CParameters) -> HPRLP_batched_results, as a dict of arrays."""
     Cmat = np.asfortranarray(Cmat, dtype=np.float64)
     B = Cmat.shape[1]
     F = lambda a: np.asfortranarray(a, dtype=np.float64)
@@ -391,8 +428,7 @@ def solve_batched(model, Cmat, AL, AU, l, u, obj_constants=None, param=None):
     P = lambda a: a.ctypes.data_as(c_dbl_p)
     oc = None if obj_constants is None else _as(obj_constants, np.float64)
     cp = (param or Parameters()).to_c()
-    res = lib().solve_batched(model._ptr, B, P(Cmat), P(AL), P(AU), P(l), P(u), None if oc is None else P(oc),
-                              C.byref(cp))
+    res = fn(B, (P(Cmat), P(AL), P(AU), P(l), P(u), None if oc is None else P(oc)), cp)
     m, n = model.m, model.n
     g = lambda q, k: None if not q else np.ctypeslib.as_array(q, shape=(k,)).copy()
     out = dict(batch_size=res.batch_size, time=res.time, setup_time=res.setup_time, solve_time=res.solve_time,

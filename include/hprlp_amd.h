@@ -106,6 +106,30 @@ int hprlp_solver_set_detection(hprlp_solver *s, const hprlp_detection *det);
 /* the certificate of the last hprlp_solver_run (kind 0 without a verdict) */
 int hprlp_solver_get_certificate(hprlp_solver *s, hprlp_certificate *cert);
 
+/* ---- the same detection for solve_batched (DESIGN.md "Batched detection") ----------------------------------------------------
+ * The tests above, member by member in that member's units, at the same evaluations.  A member with a verdict is frozen as an
+ * OPTIMAL one is: status "PRIMAL_INFEASIBLE" / "DUAL_INFEASIBLE", iter = the verdict's evaluation, x, y, z its last iterate; the
+ * batch ends when the last member has a status.  Per-member precedence: OPTIMAL, the two verdicts, then the limits.
+ * Arrays are malloc'd and column-major; a member's columns are zero wherever its kind does not use them.  kind, iter, objective
+ * and violation have batch_size entries; y (m x batch_size) and z (n x batch_size) are NULL unless some member has kind 1, d
+ * (n x batch_size) unless some member has kind 2.  Release with hprlp_free_batched_certificates. */
+typedef struct hprlp_batched_certificates {
+    int batch_size, m, n;
+    int *kind;         /* 0 none, 1 primal infeasible, 2 dual infeasible */
+    int *iter;         /* the evaluation that found it (0 for kind 0) */
+    double *objective; /* D(y) resp. c'd of the normalised ray */
+    double *violation; /* V(y) resp. W(d) */
+    double *y, *z;
+    double *d;
+} hprlp_batched_certificates;
+/* solve_batched() with detection.  det == NULL: exactly solve_batched() (same bits, same statuses).  certs (may be NULL) always
+ * gets batch_size, m, n and kind 0 for every member unless that member reached a verdict.  A negative eps is an error. */
+HPRLP_batched_results hprlp_solve_batched_detect(const LP_info_cpu *model, int batch_size, const double *C, const double *AL,
+                                                 const double *AU, const double *l, const double *u, const double *obj_constants,
+                                                 const HPRLP_parameters *param, const hprlp_detection *det,
+                                                 hprlp_batched_certificates *certs);
+void hprlp_free_batched_certificates(hprlp_batched_certificates *certs);
+
 /* Named device vectors: x y x_hat x_bar y_bar z_bar x_temp y_temp y_obj last_x last_y AL AU l u c
  * row_norm col_norm A_val AT_val.  get returns the length (or -1); cap is the capacity of out. */
 long hprlp_solver_get_vector(hprlp_solver *s, const char *name, double *out, long cap);
