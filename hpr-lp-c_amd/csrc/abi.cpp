@@ -170,8 +170,9 @@ extern "C" int hprlp_last_solve_phases(double out[8]) {
 }
 
 // reference src/HPRLP.cu:116-311.  det (may be null: off, as in the reference) switches the infeasibility detection on; a verdict's
-// certificate goes to *cert.
-static HPRLP_results main_solve(const LP_info_cpu *model, const HPRLP_parameters *param, const Detection *det, Certificate *cert) {
+// certificate goes to *cert.  x0 / y0 (both null: the reference's cold start from zero): warm start (Solver::set_start).
+static HPRLP_results main_solve(const LP_info_cpu *model, const HPRLP_parameters *param, const Detection *det, Certificate *cert,
+                                const double *x0 = nullptr, const double *y0 = nullptr) {
     if (!model || !param) {
         std::cerr << "[error] Null model or parameter pointer" << std::endl;
         return make_error_result("ERROR");
@@ -195,6 +196,7 @@ static HPRLP_results main_solve(const LP_info_cpu *model, const HPRLP_parameters
                   << " seconds" << std::endl << std::defaultfloat;
         s.init_iteration_state();
         if (det) s.detect = *det;
+        if (x0 || y0) s.set_start(x0, y0);
         const auto t_loop = time_now();
         s.solve_loop(&out);
         const double loop_s = time_since(t_loop);
@@ -203,6 +205,7 @@ static HPRLP_results main_solve(const LP_info_cpu *model, const HPRLP_parameters
         s.collect_solution(&out);
         g_phases[0] = s.setup_time; g_phases[1] = s.scaling_time; g_phases[2] = s.power_time; g_phases[3] = loop_s;
         g_phases[4] = time_since(t_col);
+        g_phases[7] = (x0 || y0) ? s.start_time : 0.0;
         t_down = time_now();
         }  // (the solver's device state goes here: part of the call's wall time)
         g_phases[5] = time_since(t_down);
@@ -248,15 +251,17 @@ static bool is_verdict(const HPRLP_results &r) {
     return std::strcmp(r.status, "PRIMAL_INFEASIBLE") == 0 || std::strcmp(r.status, "DUAL_INFEASIBLE") == 0;
 }
 
-// det / cert: infeasibility detection (hprlp_solve_detect), null for solve()
-static HPRLP_results solve_impl(const LP_info_cpu *model, const HPRLP_parameters *param, const Detection *det, Certificate *cert) {
+// det / cert: infeasibility detection (hprlp_solve_detect), null for solve().  x0 / y0: warm start of the model as given (hprlp_solve_warm),
+// both null for a cold start; the reduced solve starts from their image under the presolve's forward map.
+static HPRLP_results solve_impl(const LP_info_cpu *model, const HPRLP_parameters *param, const Detection *det, Certificate *cert,
+                                const double *x0 = nullptr, const double *y0 = nullptr) {
     if (!model) {
         std::cerr << "[error] Null model pointer" << std::endl;
         return make_error_result("ERROR");
     }
     HPRLP_parameters dflt;
     const HPRLP_parameters *p = param ? param : &dflt;
-    if (!p->use_presolve) return main_solve(model, p, det, cert);
+    if (!p->use_presolve) return main_solve(model, p, det, cert, x0, y0);
     const auto t_entry = time_now();  // (the fallback below charges everything since here against the caller's time limit)
 
     // The presolver indexes its work arrays by the model's column indices and trusts rowPtr: a hand-built
@@ -302,11 +307,11 @@ static HPRLP_results solve_impl(const LP_info_cpu *model, const HPRLP_parameters
         // (cannot happen with exact arithmetic; with rounding trouble fall back to the iteration)
         std::free(r.x); std::free(r.y); std::free(r.z);
         std::cout << "Postsolve-only solution failed the KKT check; solving original model" << std::endl;
-        return main_solve(model, p, det, cert);
+        return main_solve(model, p, det, cert, x0, y0);
     }
     if (!reduced) {
         std::cout << "Presolve left the model unchanged; solving original model" << std::endl;
-        return main_solve(model, p, det, cert);
+        return main_solve(model, p, det, cert, x0, y0);
     }
     const Presolve::Stats &st = pre.stats();
     std::cout << "Presolve reduced problem: (" << model->m << ", " << model->n << ") -> (" << pre.reduced()->m << ", "
@@ -339,7 +344,16 @@ static HPRLP_results solve_impl(const LP_info_cpu *model, const HPRLP_parameters
         std::cout << "Reduced-model tolerance " << pr.stop_tol << " (original norms |b| " << nb0 << ", |c| " << nc0 << "; reduced "
                   << nb1 << ", " << nc1 << ")" << std::endl;
     }
-    HPRLP_results r = main_solve(pre.reduced(), &pr, det, cert);
+    std::vector<double> xr, yr;  // the start carried into the reduced model
+    if (x0 || y0) {
+        std::vector<double> xf(x0 ? x0 : nullptr, x0 ? x0 + model->n : nullptr), yf(y0 ? y0 : nullptr, y0 ? y0 + model->m : nullptr);
+        xf.resize(static_cast<size_t>(model->n), 0.0);
+        yf.resize(static_cast<size_t>(model->m), 0.0);
+        xr.resize(static_cast<size_t>(pre.reduced()->n));
+        yr.resize(static_cast<size_t>(pre.reduced()->m));
+        pre.forward(xf.data(), yf.data(), xr.data(), yr.data());
+    }
+    HPRLP_results r = main_solve(pre.reduced(), &pr, det, cert, xr.empty() ? nullptr : xr.data(), yr.empty() ? nullptr : yr.data());
     if (det && is_verdict(r)) {
         // a certificate of the reduced model is no certificate of the caller's: solve the model as given, with detection, within
         // what is left of the time and iteration limits (reported times and counts include the reduced solve, as below)
@@ -352,7 +366,7 @@ static HPRLP_results solve_impl(const LP_info_cpu *model, const HPRLP_parameters
         p2.time_limit = std::max(p->time_limit - spent, 0.0);
         p2.max_iter = std::max(p->max_iter - it_first, 0);
         if (cert) *cert = Certificate();
-        HPRLP_results r2 = main_solve(model, &p2, det, cert);
+        HPRLP_results r2 = main_solve(model, &p2, det, cert, x0, y0);
         if (std::strcmp(r2.status, "ERROR") != 0) {
             r2.time += spent; r2.time4 += spent; r2.time6 += spent; r2.time8 += spent;
             r2.iter += it_first; r2.iter4 += it_first; r2.iter6 += it_first; r2.iter8 += it_first;
@@ -395,7 +409,7 @@ static HPRLP_results solve_impl(const LP_info_cpu *model, const HPRLP_parameters
                 HPRLP_parameters p2 = *p;
                 p2.time_limit = std::max(p->time_limit - spent, 0.0);
                 p2.max_iter = std::max(p->max_iter - it_first, 0);
-                HPRLP_results r2 = main_solve(model, &p2, det, cert);
+                HPRLP_results r2 = main_solve(model, &p2, det, cert, x0, y0);
                 if (std::strcmp(r2.status, "ERROR") != 0) {
                     // iter4/6/8 of a tolerance the second solve never reached are back-filled with its final count
                     // (reference src/HPRLP.cu:248-253): offset like `iter`, so they stay "<= iter"
@@ -475,6 +489,40 @@ extern "C" HPRLP_results hprlp_solve_detect(const LP_info_cpu *model, const HPRL
     } catch (const std::exception &e) {
         set_last_error(e.what());
         std::cerr << "[error] hprlp_solve_detect failed: " << e.what() << std::endl;
+        return make_error_result("ERROR");
+    }
+}
+
+// a warm start's entries must be finite (null: zeros)
+static void check_start(const double *v, long len, const char *what) {
+    if (!v) return;
+    for (long i = 0; i < len; ++i)
+        if (!std::isfinite(v[i]))
+            throw std::runtime_error(std::string("warm start: ") + what + "[" + std::to_string(i) + "] is not finite");
+}
+
+extern "C" HPRLP_results hprlp_solve_warm(const LP_info_cpu *model, const HPRLP_parameters *param, const double *x0, const double *y0,
+                                          const hprlp_detection *det, hprlp_certificate *cert) {
+    if (!x0 && !y0) return hprlp_solve_detect(model, param, det, cert);
+    const int m = model ? model->m : 0, n = model ? model->n : 0;
+    if (cert) clear_certificate(cert, m, n);
+    try {
+        if (!model) throw std::runtime_error("null model");
+        check_start(x0, n, "x0");
+        check_start(y0, m, "y0");
+        Detection d;
+        const bool with_det = detection_from(det, &d);
+        Certificate k;
+        HPRLP_results r = solve_impl(model, param, with_det ? &d : nullptr, with_det ? &k : nullptr, x0, y0);
+        if (std::strcmp(r.status, "ERROR") == 0 && !*last_error_cstr()) set_last_error("hprlp_solve_warm: the solve failed");
+        if (cert && with_det && !export_certificate(k, cert, m, n)) {
+            std::free(r.x); std::free(r.y); std::free(r.z);
+            throw std::runtime_error("host allocation of the certificate failed");
+        }
+        return r;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        std::cerr << "[error] hprlp_solve_warm failed: " << e.what() << std::endl;
         return make_error_result("ERROR");
     }
 }
@@ -559,6 +607,39 @@ extern "C" HPRLP_batched_results hprlp_solve_batched_detect(const LP_info_cpu *m
     }
 }
 
+extern "C" HPRLP_batched_results hprlp_solve_batched_warm(const LP_info_cpu *model, int batch_size, const double *C, const double *AL,
+                                                          const double *AU, const double *l, const double *u,
+                                                          const double *obj_constants, const HPRLP_parameters *param,
+                                                          const double *X0, const double *Y0, const hprlp_detection *det,
+                                                          hprlp_batched_certificates *certs) {
+    if (!X0 && !Y0) return hprlp_solve_batched_detect(model, batch_size, C, AL, AU, l, u, obj_constants, param, det, certs);
+    const int m = model ? model->m : 0, n = model ? model->n : 0, B = std::max(batch_size, 0);
+    try {
+        if (certs && !clear_batched_certificates(certs, B, m, n)) {
+            hprlp_free_batched_certificates(certs);
+            throw std::runtime_error("host allocation of the certificates failed");
+        }
+        if (!model) throw std::runtime_error("null model");
+        check_start(X0, static_cast<long>(n) * B, "X0");
+        check_start(Y0, static_cast<long>(m) * B, "Y0");
+        Detection d;
+        const bool with_det = detection_from(det, &d);
+        std::vector<Certificate> k;
+        HPRLP_batched_results r = solve_batched_impl(model, batch_size, C, AL, AU, l, u, obj_constants, param, with_det ? &d : nullptr,
+                                                     with_det && certs ? &k : nullptr, X0, Y0);
+        if (with_det && certs && !export_batched_certificates(k, certs)) {
+            free_batched_results(&r);
+            hprlp_free_batched_certificates(certs);
+            throw std::runtime_error("host allocation of the certificates failed");
+        }
+        return r;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        std::cerr << "[error] hprlp_solve_batched_warm failed: " << e.what() << std::endl;
+        return make_batched_error("ERROR", m, n, B);
+    }
+}
+
 extern "C" void hprlp_free_batched_certificates(hprlp_batched_certificates *certs) {
     if (!certs) return;
     for (void *p : {static_cast<void *>(certs->kind), static_cast<void *>(certs->iter), static_cast<void *>(certs->objective),
@@ -599,6 +680,11 @@ extern "C" int hprlp_presolve_postsolve(const hprlp_presolve *h, const double *x
                                         double *x, double *y, double *z) {
     if (!h || !xr || !yr || !zr || !x || !y || !z) return -1;
     h->p.postsolve(xr, yr, zr, x, y, z);
+    return 0;
+}
+extern "C" int hprlp_presolve_forward(const hprlp_presolve *h, const double *x, const double *y, double *xr, double *yr) {
+    if (!h || !x || !y || !xr || !yr) return -1;
+    h->p.forward(x, y, xr, yr);
     return 0;
 }
 extern "C" void hprlp_presolve_free(hprlp_presolve *h) { delete h; }
@@ -1135,6 +1221,19 @@ extern "C" int hprlp_solver_set_detection(hprlp_solver *h, const hprlp_detection
     Detection d;
     detection_from(det, &d);
     h->s.detect = d;
+    return 0;
+    GUARD_END(-1)
+}
+
+extern "C" int hprlp_solver_set_start(hprlp_solver *h, const double *x0, const double *y0) {
+    GUARD_BEGIN
+    if (!h) throw std::runtime_error("null solver");
+    if (h->sharded)
+        throw std::runtime_error("hprlp_solver_set_start: warm start runs on one GPU only; a sharded solver (hprlp_solver_create_dist* / "
+                                 "_local*) refuses it");
+    check_start(x0, h->s.n, "x0");
+    check_start(y0, h->s.m, "y0");
+    h->s.set_start(x0, y0);
     return 0;
     GUARD_END(-1)
 }

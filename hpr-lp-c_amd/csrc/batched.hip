@@ -651,6 +651,87 @@ HPRLP_RAY_SPMM_KERNEL(kb_ray_row, RAY_ROW)
 HPRLP_RAY_SPMM_KERNEL(kb_ray_product, RAY_PRODUCT)
 #undef HPRLP_RAY_SPMM_KERNEL
 
+// ---- warm start (hprlp_solve_batched_warm; DESIGN.md "Warm start") ------------------------------------------------------
+// X and Y hold the members' starts, scaled on the host: project them (X into [L, U]; Y onto the sign cone of the row's sides --
+// y > 0 means the row sits at AL) and seed every panel the first iteration reads: X, X_hat, X_bar, lastX (the Halpern anchor);
+// Y, Y_bar, lastY.  Every member, the padding included (its panels are zero and stay zero).
+__global__ void __launch_bounds__(256) kb_start_seed(int n, int m, Geo g, double *X, double *Xh, double *Xb, double *lastX,
+                                                     const double *L, const double *U, double *Y, double *Yb, double *lastY,
+                                                     const double *AL, const double *AU) {
+    const Blk blk = decode_block(g);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int kl = lane % g.Bw;
+    const int sub = lane / g.Bw;
+    const int r0 = blk.rb * g.rows_per_block + wave * g.rows_per_wave + sub, rs = blk.nrb * g.rows_per_block;
+    for (int r = r0; r < n; r += rs) {
+        const size_t t = pidx(g, blk.chunk, n, r, kl);
+        const double v = fmin(fmax(X[t], L[t]), U[t]);
+        X[t] = v;
+        Xh[t] = v;
+        Xb[t] = v;
+        lastX[t] = v;
+    }
+    for (int r = r0; r < m; r += rs) {
+        const size_t t = pidx(g, blk.chunk, m, r, kl);
+        double v = Y[t];
+        if (!finite_bound(AL[t])) v = fmin(v, 0.0);
+        if (!finite_bound(AU[t])) v = fmax(v, 0.0);
+        Y[t] = v;
+        Yb[t] = v;
+        lastY[t] = v;
+    }
+}
+
+// The iteration-0 evaluation of the starts, with kb_resid's geometry.  START_COL: rows of A^T gathering Y_bar; w = C - A^T y and
+// Z_bar = w where its sign has a finite bound to lean on (w > 0: L, w < 0: U), else 0 (the dual completion); partials of C.X_bar
+// (B_CX) and of the bound terms L z (z > 0), U z (z < 0) (B_XZ: what X_bar.Z_bar is at a check, Solver::set_start).  START_ROW: rows of A gathering X_bar; Y_obj = AL where y > 0, AU where y < 0, the activity
+// clamped into [AL, AU] where y = 0; partials of Y_obj.Y_bar (B_YOBJ_Y).
+template <bool COL>
+__global__ void __launch_bounds__(256) kb_start_spmm(int rows, const int *__restrict__ rowptr, const int *__restrict__ col,
+                                                     const double *__restrict__ val, Geo g, int vrows, const double *V,
+                                                     const double *p0, const double *lo, const double *hi, const double *bar,
+                                                     double *out, double *partials) {
+    const Blk blk = decode_block(g);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int kl = lane % g.Bw, k = blk.chunk * g.Bw + kl;
+    const int sub = lane / g.Bw;
+    const size_t vbase = pidx(g, blk.chunk, vrows, 0, kl);
+    constexpr int NACC = COL ? 2 : 1;
+    double acc[NACC];
+#pragma unroll
+    for (int i = 0; i < NACC; ++i) acc[i] = 0.0;
+    for (int r = blk.rb * g.rows_per_block + wave * g.rows_per_wave + sub; r < rows; r += blk.nrb * g.rows_per_block) {
+        double s = 0.0;
+        const int e = rowptr[r + 1];
+        for (int p = rowptr[r]; p < e; p += 4) {  // four entries in flight, summed in CSR order (kb_resid)
+            double av[4], gv[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int q = min(p + u, e - 1);
+                av[u] = val[q];
+                gv[u] = V[vbase + static_cast<size_t>(col[q]) * g.Bw];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (p + u < e) s += av[u] * gv[u];
+        }
+        const size_t t = pidx(g, blk.chunk, rows, r, kl);
+        const double b = bar[t];
+        if constexpr (COL) {
+            const double c = p0[t], d = c - s;
+            const double z = ((d > 0.0 && finite_bound(lo[t])) || (d < 0.0 && finite_bound(hi[t]))) ? d : 0.0;
+            out[t] = z;
+            acc[0] += c * b;
+            acc[NACC - 1] += (z > 0.0 ? lo[t] : (z < 0.0 ? hi[t] : 0.0)) * z;
+        } else {
+            const double yo = b > 0.0 ? lo[t] : (b < 0.0 ? hi[t] : fmin(fmax(s, lo[t]), hi[t]));
+            out[t] = yo;
+            acc[0] += yo * b;
+        }
+    }
+    block_store_per_problem<NACC>(acc, g, blk.rb, k, true, partials);
+}
+
 // SC[slot[i]*Bp + k] = sum over blocks of partials[(b*nacc + i)*Bp + k]; the maximum instead where bit i of max_mask is set
 // (partials of nonnegative maxima: kb_ray_form, kb_ray_col / kb_ray_row)
 struct BFin {
@@ -935,7 +1016,7 @@ namespace hprlp {
 HPRLP_batched_results solve_batched_impl(const LP_info_cpu *model, int batch_size, const HPRLP_FLOAT *C_in, const HPRLP_FLOAT *AL_in,
                                          const HPRLP_FLOAT *AU_in, const HPRLP_FLOAT *l_in, const HPRLP_FLOAT *u_in,
                                          const HPRLP_FLOAT *obj_constants, const HPRLP_parameters *param, const Detection *det,
-                                         std::vector<Certificate> *certs) {
+                                         std::vector<Certificate> *certs, const HPRLP_FLOAT *X0, const HPRLP_FLOAT *Y0) {
     if (!model || !model->A || batch_size <= 0 || !C_in || !AL_in || !AU_in || !l_in || !u_in)
         return make_batched_error("ERROR", model ? model->m : 0, model ? model->n : 0, std::max(batch_size, 0));
     const int m = model->m, n = model->n, B = batch_size;
@@ -1057,6 +1138,25 @@ HPRLP_batched_results solve_batched_impl(const LP_info_cpu *model, int batch_siz
         }
         for (DBuf<double> *p : {&w.X, &w.Xh, &w.Xb, &w.DX, &w.Zb, &w.lastX}) p->alloc_zero(nB);
         for (DBuf<double> *p : {&w.Y, &w.Yb, &w.DY, &w.Yobj, &w.lastY}) p->alloc_zero(mB);
+        const bool warm = X0 || Y0;
+        if (warm) {
+            // the starts in scaled units beside the other per-member vectors (the inverse of the results' map), into X / Y
+            std::vector<double> panel;
+            if (X0) {
+                std::vector<double> hX(X0, X0 + static_cast<size_t>(n) * B);
+                for (int k = 0; k < B; ++k)
+                    for (int i = 0; i < n; ++i) hX[static_cast<size_t>(k) * n + i] = (hX[static_cast<size_t>(k) * n + i] * cn[i]) / b_scale[k];
+                to_panel(hX, n, B, geo, 0.0, panel);
+                w.X.upload(panel.data(), nB);
+            }
+            if (Y0) {
+                std::vector<double> hY(Y0, Y0 + static_cast<size_t>(m) * B);
+                for (int k = 0; k < B; ++k)
+                    for (int i = 0; i < m; ++i) hY[static_cast<size_t>(k) * m + i] = (hY[static_cast<size_t>(k) * m + i] * rn[i]) / c_scale[k];
+                to_panel(hY, m, B, geo, 0.0, panel);
+                w.Y.upload(panel.data(), mB);
+            }
+        }
         const bool detect = det && det->on;
         w.nslot = detect ? B_NSLOT_DETECT : B_NSLOT;
         w.SC.alloc_zero(static_cast<size_t>(w.nslot) * w.Bp);
@@ -1082,6 +1182,18 @@ HPRLP_batched_results solve_batched_impl(const LP_info_cpu *model, int batch_siz
             w.bsc.upload(bs.data(), w.Bp);
             w.csc.alloc(w.Bp);
             w.csc.upload(cs.data(), w.Bp);
+        }
+        if (warm) {
+            const CsrDev &A0 = shared.A.view, &AT0 = shared.AT.view;
+            hipLaunchKernelGGL(kb_start_seed, dim3(std::max(w.gx, w.gy) * geo.nchunk), dim3(256), 0, w.stream, n, m, geo, w.X.p, w.Xh.p,
+                               w.Xb.p, w.lastX.p, w.L.p, w.U.p, w.Y.p, w.Yb.p, w.lastY.p, w.AL.p, w.AU.p);
+            hipLaunchKernelGGL(kb_start_spmm<true>, dim3(w.gx * geo.nchunk), dim3(256), 0, w.stream, AT0.rows, AT0.rowptr, AT0.col,
+                               AT0.val, geo, m, w.Yb.p, w.C.p, w.L.p, w.U.p, w.Xb.p, w.Zb.p, w.partials.p);
+            finalize(w, w.gx, {B_CX, B_XZ});
+            hipLaunchKernelGGL(kb_start_spmm<false>, dim3(w.gy * geo.nchunk), dim3(256), 0, w.stream, A0.rows, A0.rowptr, A0.col,
+                               A0.val, geo, n, w.Xb.p, static_cast<const double *>(nullptr), w.AL.p, w.AU.p, w.Yb.p, w.Yobj.p,
+                               w.partials.p);
+            finalize(w, w.gy, {B_YOBJ_Y});
         }
         HIP_CHECK(hipDeviceSynchronize());
         const double setup_time = time_since(setup_start);

@@ -203,6 +203,27 @@ void launch_ray_col(const CsrDev &AT, const double *ys_full, const double *l, co
 void launch_ray_row(const CsrDev &A, const double *ds_full, const double *AL, const double *AU, const double *row_norm, double b_scale,
                     double *partials, hipStream_t s);
 
+// ---- warm start (Solver::set_start, DESIGN.md "Warm start"): the caller's point into the iteration state ---------------------
+// k_start_in: x_s = clamp(x0[pc[j]] * col_norm[j] / b_scale, l_j, u_j) into x, last_x, x_hat, x_bar and y_s = y0[pr[i]] *
+// row_norm[i] / c_scale, projected onto the sign cone of row i's sides, into y, last_y, y_bar.  x0 / y0 null: zeros; pc / pr
+// null: no locality ordering (device index = caller's index).
+struct StartInArgs {
+    int n, m;
+    const double *x0, *y0;  // device copies of the caller's vectors (caller's numbering)
+    const int *pc, *pr;     // device index -> caller's index, or null
+    const double *l, *u, *col_norm, *AL, *AU, *row_norm;
+    double b_scale, c_scale;
+    double *x, *last_x, *x_hat, *x_bar, *y, *last_y, *y_bar;
+};
+void launch_start_in(const StartInArgs &a, hipStream_t s);
+// z_bar = dual completion of w = c - A^T y_bar (A^T, gathered y_bar); partials (2 x AT.grid()) of c.x_bar and of the bound terms
+// l.z+ + u.z- (what x_bar.z_bar is at a check)
+void launch_start_col(const CsrDev &AT, const double *ybar_full, const double *c, const double *l, const double *u,
+                      const double *x_bar, double *z_bar, double *partials, hipStream_t s);
+// y_obj = AL / AU / clamp(A x_bar) by the sign of y_bar (A, gathered x_bar); partials (A.grid()) of y_obj.y_bar
+void launch_start_row(const CsrDev &A, const double *xbar_full, const double *AL, const double *AU, const double *y_bar,
+                      double *y_obj, double *partials, hipStream_t s);
+
 // x_temp = x_bar - last_x, y_temp = y_bar - last_y, squared norms -> partials (2 x stride);
 // then last_x = x = x_bar, last_y = y = y_bar and the Halpern counter is reset
 // (reference update_sigma movement + do_restart, main_iterate.cu:312-322,369-375)

@@ -1487,6 +1487,55 @@ struct RayRowEpi {
     }
 };
 
+// Warm start (Solver::set_start, DESIGN.md "Warm start"): the iteration-0 evaluation of a caller's point, scaled units.  Column side
+// (rows of A^T, gathered y_bar): w = c - A^T y, and z_bar = w where the sign of w has a finite bound to lean on (w > 0: l_j,
+// w < 0: u_j), else 0 -- the dual completion; partials of c.x_bar (Slot S_CX) and of the bound terms l_j z_j (z_j > 0), u_j z_j
+// (z_j < 0) into S_XZ: the value x_bar.z_bar takes at a check, where z_bar is nonzero only at a bound.  (x_bar.z_bar itself would
+// hide the complementarity of the start: on a boxed LP every y completes to a feasible z, and x.z makes any feasible x look optimal.)
+struct StartColEpi {
+    static constexpr int NV = 1;
+    static constexpr int NACC = 2;
+    const double *gv[1];
+    const double *c, *l, *u, *x_bar;
+    double *z_bar;
+    double *partials;
+    int stride;
+    struct Row {
+        double ci, lo, hi, xb;
+    };
+    __device__ __forceinline__ void begin() {}
+    __device__ __forceinline__ Row load_row(int r) const { return Row{c[r], l[r], u[r], x_bar[r]}; }
+    __device__ __forceinline__ void apply(int r, const Row &w, const double (&s)[1], double (&acc)[2]) const {
+        const double d = w.ci - s[0];
+        const double z = ((d > 0.0 && isfinite(w.lo)) || (d < 0.0 && isfinite(w.hi))) ? d : 0.0;
+        z_bar[r] = z;
+        acc[0] += w.ci * w.xb;
+        acc[1] += (z > 0.0 ? w.lo : (z < 0.0 ? w.hi : 0.0)) * z;
+    }
+};
+
+// Row side (rows of A, gathered x_bar): y_obj = AL where y > 0, AU where y < 0, the activity clamped into [AL, AU] where y = 0
+// (what the check y-half stores for a converged point); partials of y_obj.y_bar (Slot S_YOBJ_Y).
+struct StartRowEpi {
+    static constexpr int NV = 1;
+    static constexpr int NACC = 1;
+    const double *gv[1];
+    const double *AL, *AU, *y_bar;
+    double *y_obj;
+    double *partials;
+    int stride;
+    struct Row {
+        double lo, hi, yb;
+    };
+    __device__ __forceinline__ void begin() {}
+    __device__ __forceinline__ Row load_row(int r) const { return Row{AL[r], AU[r], y_bar[r]}; }
+    __device__ __forceinline__ void apply(int r, const Row &w, const double (&s)[1], double (&acc)[1]) const {
+        const double yo = w.yb > 0.0 ? w.lo : (w.yb < 0.0 ? w.hi : fmin(fmax(s[0], w.lo), w.hi));
+        y_obj[r] = yo;
+        acc[0] += yo * w.yb;
+    }
+};
+
 // ------------------------------------------------------------------------------------------------
 // launch wrappers of the fused kernel
 // ------------------------------------------------------------------------------------------------
@@ -1741,6 +1790,18 @@ void launch_ray_col(const CsrDev &AT, const double *ys_full, const double *l, co
 void launch_ray_row(const CsrDev &A, const double *ds_full, const double *AL, const double *AU, const double *row_norm, double b_scale,
                     double *partials, hipStream_t s) {
     RayRowEpi e{{ds_full}, AL, AU, row_norm, b_scale, partials, A.grid()};
+    launch_fused(A, e, s);
+}
+
+void launch_start_col(const CsrDev &AT, const double *ybar_full, const double *c, const double *l, const double *u,
+                      const double *x_bar, double *z_bar, double *partials, hipStream_t s) {
+    StartColEpi e{{ybar_full}, c, l, u, x_bar, z_bar, partials, AT.grid()};
+    launch_fused(AT, e, s);
+}
+
+void launch_start_row(const CsrDev &A, const double *xbar_full, const double *AL, const double *AU, const double *y_bar,
+                      double *y_obj, double *partials, hipStream_t s) {
+    StartRowEpi e{{xbar_full}, AL, AU, y_bar, y_obj, partials, A.grid()};
     launch_fused(A, e, s);
 }
 
@@ -2539,6 +2600,32 @@ __global__ void __launch_bounds__(kThreads) k_ray_form(RayFormArgs a, double *pa
 }
 void launch_ray_form(const RayFormArgs &a, double *partials, int nblocks, hipStream_t s) {
     hipLaunchKernelGGL(k_ray_form, dim3(nblocks), dim3(kThreads), 0, s, a, partials);
+}
+
+// Warm start: the caller's point (caller's units and numbering) -> the scaled, permuted, projected iteration state.  The inverse
+// of k_unscale's map; positive scaling keeps every bound on its side, so the projection runs on the device's scaled bounds.
+__global__ void __launch_bounds__(kThreads) k_start_in(StartInArgs a) {
+    const int tid = blockIdx.x * kThreads + threadIdx.x, nth = gridDim.x * kThreads;
+    for (int j = tid; j < a.n; j += nth) {
+        const double v = a.x0 ? a.x0[a.pc ? a.pc[j] : j] : 0.0;
+        const double xs = fmin(fmax((v * a.col_norm[j]) / a.b_scale, a.l[j]), a.u[j]);
+        a.x[j] = xs;
+        a.last_x[j] = xs;
+        a.x_hat[j] = xs;
+        a.x_bar[j] = xs;
+    }
+    for (int i = tid; i < a.m; i += nth) {
+        const double v = a.y0 ? a.y0[a.pr ? a.pr[i] : i] : 0.0;
+        double ys = (v * a.row_norm[i]) / a.c_scale;
+        if (!isfinite(a.AL[i])) ys = fmin(ys, 0.0);  // no lower side: y <= 0 (y > 0 means the row sits at AL)
+        if (!isfinite(a.AU[i])) ys = fmax(ys, 0.0);  // no upper side: y >= 0; a free row: y = 0
+        a.y[i] = ys;
+        a.last_y[i] = ys;
+        a.y_bar[i] = ys;
+    }
+}
+void launch_start_in(const StartInArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(k_start_in, dim3(vec_grid(a.n > a.m ? a.n : a.m)), dim3(kThreads), 0, s, a);
 }
 
 __global__ void __launch_bounds__(kThreads) k_unscale(int n, int m, const double *x_bar, const double *y_bar,

@@ -681,6 +681,31 @@ void ReduceStage::postsolve(const double *xr, const double *yr, const double *zr
     }
 }
 
+// The forward map of the records, in the order they were applied (the inverse of postsolve's last-in first-out walk): a folded
+// parallel column's kept column stands for x_j1 + lambda x_j2, a slack substitution moved c_j / a out of the row's multiplier, a
+// folded parallel row's multiplier carries the removed row's (a_j y_j + a_i y_i = a_j (y_j + lambda y_i)).  Every other record
+// removes its row or column: restriction.
+void ReduceStage::forward(const double *x, const double *y, double *xr, double *yr) const {
+    std::vector<double> wx(x, x + n_), wy(y, y + m_);
+    for (const Record &r : stack_) {
+        switch (r.kind) {
+            case ParallelCol:  // r.j = j1 (kept), r.i = j2, r.a = lambda
+                wx[r.j] += r.a * wx[r.i];
+                break;
+            case SlackCol:
+                wy[r.i] -= r.cost / r.a;
+                break;
+            case ParallelRow:  // row r.i = r.a * row r.j, folded into r.j
+                wy[r.j] += r.a * wy[r.i];
+                break;
+            default:
+                break;
+        }
+    }
+    for (size_t q = 0; q < col_of_.size(); ++q) xr[q] = wx[col_of_[q]];
+    for (size_t r = 0; r < row_of_.size(); ++r) yr[r] = wy[row_of_[r]];
+}
+
 OriginalKkt original_kkt(const LP_info_cpu *model, const double *x, const double *y, const double *z) {
     // same definitions as the reference's check on the original model (src/pslp_integration.cpp:458-580):
     // duals are first projected onto the sign their finite bounds allow

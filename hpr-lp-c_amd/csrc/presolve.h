@@ -48,6 +48,9 @@ class PresolveLink {
     virtual int input_n() const = 0;
     // (xr, yr, zr) of reduced() -> (x, y, z) of the link's input model; all three null when the link left nothing
     virtual void postsolve(const double *xr, const double *yr, const double *zr, double *x, double *y, double *z) const = 0;
+    // (x, y) of the link's input model -> (xr, yr) of reduced() (warm start, DESIGN.md "Warm start"): the inverse of postsolve where
+    // it combines values, so that a primal-dual optimum of the input maps onto one of reduced(); elsewhere a restriction
+    virtual void forward(const double *x, const double *y, double *xr, double *yr) const = 0;
 };
 
 // The fixed-point loop over the reductions that leave the matrix entries alone (list at the top of this file).
@@ -68,6 +71,7 @@ class ReduceStage : public PresolveLink {
     int input_m() const override { return m_; }
     int input_n() const override { return n_; }
     void postsolve(const double *xr, const double *yr, const double *zr, double *x, double *y, double *z) const override;
+    void forward(const double *x, const double *y, double *xr, double *yr) const override;
 
    private:
     bool worth_it(const LP_info_cpu *model) const;  // large models: is there enough to remove?
@@ -108,6 +112,7 @@ class DoubletonStage : public PresolveLink {
     int input_n() const override { return n_; }
     int eliminated() const { return static_cast<int>(recs_.size()); }
     void postsolve(const double *xr, const double *yr, const double *zr, double *x, double *y, double *z) const override;
+    void forward(const double *x, const double *y, double *xr, double *yr) const override;  // restriction
 
    private:
     struct Rec {
@@ -141,6 +146,7 @@ class BoundStage : public PresolveLink {
     int input_n() const override { return n_; }
     int tightened() const { return static_cast<int>(recs_.size()); }
     void postsolve(const double *xr, const double *yr, const double *zr, double *x, double *y, double *z) const override;
+    void forward(const double *x, const double *y, double *xr, double *yr) const override;  // identity
 
    private:
     struct Rec {
@@ -173,6 +179,8 @@ class Presolve {
     int original_n() const { return n_; }
     // Maps a primal-dual solution of the reduced model back to the original dimensions.
     void postsolve(const double *xr, const double *yr, const double *zr, double *x, double *y, double *z) const;
+    // Maps a primal-dual point of the original model (x: n, y: m) into the reduced model (xr, yr: its n and m), link by link.
+    void forward(const double *x, const double *y, double *xr, double *yr) const;
 
    private:
     int m_ = 0, n_ = 0;

@@ -496,6 +496,37 @@ bool Presolve::run(const LP_info_cpu *model) {
     return true;
 }
 
+void DoubletonStage::forward(const double *x, const double *y, double *xr, double *yr) const {
+    // x_k keeps its meaning (x_j follows from the row); the row's multiplier leaves with it
+    for (size_t q = 0; q < col_of_.size(); ++q) xr[q] = x[col_of_[q]];
+    for (size_t r = 0; r < row_of_.size(); ++r) yr[r] = y[row_of_[r]];
+}
+
+void BoundStage::forward(const double *x, const double *y, double *xr, double *yr) const {
+    std::copy(x, x + n_, xr);
+    std::copy(y, y + m_, yr);
+}
+
+void Presolve::forward(const double *x, const double *y, double *xr, double *yr) const {
+    if (chain_.empty()) return;
+    std::vector<double> cx, cy, nx, ny;
+    const double *px = x, *py = y;
+    for (size_t s = 0; s < chain_.size(); ++s) {
+        const PresolveLink &lk = *chain_[s];
+        if (s + 1 == chain_.size()) {
+            lk.forward(px, py, xr, yr);
+        } else {
+            nx.assign(static_cast<size_t>(lk.reduced()->n), 0.0);
+            ny.assign(static_cast<size_t>(lk.reduced()->m), 0.0);
+            lk.forward(px, py, nx.data(), ny.data());
+            cx.swap(nx);
+            cy.swap(ny);
+            px = cx.data();
+            py = cy.data();
+        }
+    }
+}
+
 void Presolve::postsolve(const double *xr, const double *yr, const double *zr, double *x, double *y, double *z) const {
     if (chain_.empty()) return;
     std::vector<double> cx, cy, cz, nx, ny, nz;

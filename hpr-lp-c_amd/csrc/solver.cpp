@@ -2338,4 +2338,50 @@ void Solver::collect_certificate(int kind, int iter) {
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// warm start (DESIGN.md "Warm start"): the caller's point, projected, into the state the first iteration and compute_residuals(0)
+// read.  The Halpern anchor is the start itself (last_x, last_y) and the counter stays at 0 (init_iteration_state).
+// ------------------------------------------------------------------------------------------------
+void Solver::set_start(const double *x0, const double *y0) {
+    if (comm) throw std::runtime_error("warm start runs on one GPU only (sharded solver)");
+    if (y_exchange_pending) throw std::runtime_error("set_start: an exchange is still pending");
+    const auto t0 = time_now();
+    finish_tiling();
+    invalidate_far();  // y changes under the remainder buffer of A^T, and the SpMVs below refill both buffers
+    // the caller's vectors go to the device once, into scratch the kernels below do not write; a locality ordering's permutations
+    // travel for this call only (a host gather would be a pass over every entry on the host)
+    DBuf<double> dx, dy;
+    DBuf<int> dpc, dpr;
+    if (x0 && n_loc > 0) {
+        dx.alloc(static_cast<size_t>(n_loc));
+        HIP_CHECK(hipMemcpyAsync(dx.p, x0, sizeof(double) * n_loc, hipMemcpyHostToDevice, stream));
+    }
+    if (y0 && m_loc > 0) {
+        dy.alloc(static_cast<size_t>(m_loc));
+        HIP_CHECK(hipMemcpyAsync(dy.p, y0, sizeof(double) * m_loc, hipMemcpyHostToDevice, stream));
+    }
+    if (!perm_c.empty() && dx.p) {
+        dpc.alloc(perm_c.size());
+        HIP_CHECK(hipMemcpyAsync(dpc.p, perm_c.data(), sizeof(int) * perm_c.size(), hipMemcpyHostToDevice, stream));
+    }
+    if (!perm_r.empty() && dy.p) {
+        dpr.alloc(perm_r.size());
+        HIP_CHECK(hipMemcpyAsync(dpr.p, perm_r.data(), sizeof(int) * perm_r.size(), hipMemcpyHostToDevice, stream));
+    }
+    const StartInArgs a{n_loc, m_loc, dx.p, dy.p, dpc.p, dpr.p, l.p, u.p, col_norm.p, AL.p, AU.p, row_norm.p, b_scale, c_scale,
+                        x.p, last_x.p, x_hat, x_bar, y, last_y.p, y_bar};
+    launch_start_in(a, stream);
+    // (one GPU: x_hat, x_bar, y, y_bar are the gathered buffers themselves)
+    const int gx = AT.view.grid(), gyy = A.view.grid();
+    launch_start_col(AT.view, gyb.p, c.p, l.p, u.p, x_bar, z_bar.p, part_x.p, stream);
+    launch_start_row(A.view, gxb.p, AL.p, AU.p, y_bar, y_obj.p, part_r.p, stream);
+    FinalizeArgs f{};
+    f.item[f.n++] = {part_x.p, gx, S_CX};
+    f.item[f.n++] = {part_x.p + gx, gx, S_XZ};
+    f.item[f.n++] = {part_r.p, gyy, S_YOBJ_Y};
+    launch_finalize(f, scal.p, stream);
+    HIP_CHECK(hipStreamSynchronize(stream));  // (the uploads' buffers go out of scope here)
+    start_time = time_since(t0);
+}
+
 }  // namespace hprlp

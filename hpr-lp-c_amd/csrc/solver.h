@@ -49,10 +49,12 @@ struct Certificate {
 
 // batched.hip: solve_batched with the infeasibility detection, member by member (DESIGN.md "Batched detection").  det null or
 // off: exactly solve_batched.  certs (may be null) receives one Certificate per member, kind 0 where no verdict was reached.
+// X0 (n x B) / Y0 (m x B), column-major, caller's units: warm start per member (DESIGN.md "Warm start"); both null: cold.
 HPRLP_batched_results solve_batched_impl(const LP_info_cpu *model, int batch_size, const HPRLP_FLOAT *C, const HPRLP_FLOAT *AL,
                                          const HPRLP_FLOAT *AU, const HPRLP_FLOAT *l, const HPRLP_FLOAT *u,
                                          const HPRLP_FLOAT *obj_constants, const HPRLP_parameters *param, const Detection *det,
-                                         std::vector<Certificate> *certs);
+                                         std::vector<Certificate> *certs, const HPRLP_FLOAT *X0 = nullptr,
+                                         const HPRLP_FLOAT *Y0 = nullptr);
 // a batched result whose every member has status `status` and no arrays
 HPRLP_batched_results make_batched_error(const char *status, int m, int n, int B);
 
@@ -202,6 +204,13 @@ struct Solver {
     bool ray_test();               // enqueue the rays' kernels and reductions; false at the first evaluation (no previous iterate yet)
     int ray_verdict();             // after fetch_scalars: 1 primal infeasible, 2 dual infeasible, 0 neither
     void collect_certificate(int kind, int iter);
+
+    // Warm start (DESIGN.md "Warm start"): after init_iteration_state(), before solve_loop().  x0 (n) / y0 (m): the caller's point
+    // in the caller's units and numbering (host memory, either may be null: zeros), every entry finite.  Projects it, writes it
+    // into every vector the first iteration reads and evaluates it for iteration 0 (z_bar, y_obj, S_CX, S_XZ, S_YOBJ_Y).  Single
+    // GPU only.  start_time: seconds of the last call (upload, kernels, reductions).
+    void set_start(const double *x0, const double *y0);
+    double start_time = 0.0;
 
     std::map<int, hipGraphExec_t> graphs;
     TraceRow *trace = nullptr;

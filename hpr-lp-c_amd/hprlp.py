@@ -157,6 +157,15 @@ def lib():
     L.hprlp_solve_batched_detect.argtypes = [C.POINTER(CLPInfo), C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p,
                                              C.POINTER(CParameters), C.POINTER(CDetection), C.POINTER(CBatchedCertificates)]
     L.hprlp_free_batched_certificates.argtypes = [C.POINTER(CBatchedCertificates)]
+    L.hprlp_solve_warm.restype = CResults
+    L.hprlp_solve_warm.argtypes = [C.POINTER(CLPInfo), C.POINTER(CParameters), c_dbl_p, c_dbl_p, C.POINTER(CDetection),
+                                   C.POINTER(CCertificate)]
+    L.hprlp_solve_batched_warm.restype = CBatchedResults
+    L.hprlp_solve_batched_warm.argtypes = [C.POINTER(CLPInfo), C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p,
+                                           C.POINTER(CParameters), c_dbl_p, c_dbl_p, C.POINTER(CDetection),
+                                           C.POINTER(CBatchedCertificates)]
+    L.hprlp_solver_set_start.argtypes = [C.c_void_p, c_dbl_p, c_dbl_p]
+    L.hprlp_presolve_forward.argtypes = [C.c_void_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]
     _lib = L
     return L
 
@@ -245,6 +254,34 @@ def _detection(eps_primal, eps_dual):
     return CDetection(float(eps_primal), float(eps_dual))
 
 
+def _start_vector(v, length, name):
+    """A warm-start vector as a contiguous float64 array of the given length (None stays None: zeros)."""
+    if v is None:
+        return None
+    a = _as(v, np.float64)
+    if a.ndim != 1 or a.shape[0] != length:
+        raise ValueError(f"warm start: {name} must have length {length}, got shape {a.shape}")
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f"warm start: {name} has a non-finite entry")
+    return a
+
+
+def _start_panel(V, rows, B, name):
+    """A batched warm-start panel (rows x B) as a column-major float64 array (None stays None: zeros)."""
+    if V is None:
+        return None
+    a = np.asfortranarray(V, dtype=np.float64)
+    if a.shape != (rows, B):
+        raise ValueError(f"warm start: {name} must have shape ({rows}, {B}), got {a.shape}")
+    if not np.all(np.isfinite(a)):
+        raise ValueError(f"warm start: {name} has a non-finite entry")
+    return a
+
+
+def _dptr(a):
+    return None if a is None else a.ctypes.data_as(c_dbl_p)
+
+
 class Model:
     """LP model: min c'x s.t. AL <= Ax <= AU, l <= x <= u (wraps LP_info_cpu*)."""
 
@@ -327,6 +364,21 @@ class Model:
         r.certificate = Certificate(cc)
         return r
 
+    def solve_warm(self, x=None, y=None, param=None, eps_primal=None, eps_dual=None):
+        """solve() from the primal-dual point (x, y) in this model's units (hprlp_solve_warm; None: zeros, both None: exactly
+        solve()).  eps_primal / eps_dual not None: with infeasibility detection, the certificate in `.certificate`."""
+        xs, ys = _start_vector(x, self.n, "x"), _start_vector(y, self.m, "y")
+        cp = (param or Parameters()).to_c()
+        det = None if eps_primal is None and eps_dual is None else _detection(
+            1e-8 if eps_primal is None else eps_primal, 1e-8 if eps_dual is None else eps_dual)
+        cc = CCertificate()
+        res = lib().hprlp_solve_warm(self._ptr, C.byref(cp), _dptr(xs), _dptr(ys), C.byref(det) if det is not None else None,
+                                     C.byref(cc))
+        r = Results(res, self.m, self.n)
+        if det is not None:
+            r.certificate = Certificate(cc)
+        return r
+
     def free(self):
         if self._ptr:
             lib().free_model(self._ptr)
@@ -355,6 +407,14 @@ class Presolved:
         if lib().hprlp_presolve_postsolve(self.h, P(xr), P(yr), P(zr), P(x), P(y), P(z)) != 0:
             raise RuntimeError("postsolve failed")
         return x, y, z
+
+    def forward(self, x, y):
+        """(x, y) of the original model -> (xr, yr) of the reduced one (hprlp_presolve_forward)."""
+        x, y = _start_vector(x, self.model.n, "x"), _start_vector(y, self.model.m, "y")
+        xr, yr = np.zeros(self.reduced.n), np.zeros(self.reduced.m)
+        if lib().hprlp_presolve_forward(self.h, _dptr(x), _dptr(y), _dptr(xr), _dptr(yr)) != 0:
+            raise RuntimeError("presolve forward map failed")
+        return xr, yr
 
     def free(self):
         if self.h:
@@ -416,6 +476,31 @@ def solve_batched_detect(model, Cmat, AL, AU, l, u, obj_constants=None, param=No
     out["certificates"] = dict(kind=g(cc.kind, B, np.int32), iter=g(cc.iter, B, np.int32), objective=g(cc.objective, B),
                                violation=g(cc.violation, B), y=panel(cc.y, m), z=panel(cc.z, n), d=panel(cc.d, n))
     lib().hprlp_free_batched_certificates(C.byref(cc))
+    return out
+
+
+def solve_batched_warm(model, Cmat, AL, AU, l, u, X0=None, Y0=None, obj_constants=None, param=None, eps_primal=None,
+                       eps_dual=None):
+    """solve_batched() from per-member starts (hprlp_solve_batched_warm): X0 (n, B) and Y0 (m, B) in each member's units (None:
+    zeros; both None: exactly solve_batched()).  eps_primal / eps_dual not None: with detection, "certificates" as in
+    solve_batched_detect()."""
+    B = np.asarray(Cmat).shape[1]
+    X0, Y0 = _start_panel(X0, model.n, B, "X0"), _start_panel(Y0, model.m, B, "Y0")
+    det = None if eps_primal is None and eps_dual is None else _detection(
+        1e-8 if eps_primal is None else eps_primal, 1e-8 if eps_dual is None else eps_dual)
+    cc = CBatchedCertificates()
+
+    def call(B, args, cp):
+        return lib().hprlp_solve_batched_warm(model._ptr, B, *args, C.byref(cp), _dptr(X0), _dptr(Y0),
+                                              C.byref(det) if det is not None else None, C.byref(cc) if det is not None else None)
+    out = _batched_call(call, model, Cmat, AL, AU, l, u, obj_constants, param)
+    if det is not None:
+        Bc, m, n = cc.batch_size, cc.m, cc.n
+        g = lambda q, k, dt=np.float64: None if not q else np.ctypeslib.as_array(q, shape=(k,)).astype(dt, copy=True)
+        panel = lambda q, rows: None if not q else g(q, rows * Bc).reshape(Bc, rows).T.copy()
+        out["certificates"] = dict(kind=g(cc.kind, Bc, np.int32), iter=g(cc.iter, Bc, np.int32), objective=g(cc.objective, Bc),
+                                   violation=g(cc.violation, Bc), y=panel(cc.y, m), z=panel(cc.z, n), d=panel(cc.d, n))
+        lib().hprlp_free_batched_certificates(C.byref(cc))
     return out
 
 
@@ -664,6 +749,11 @@ class Solver:
         """Infeasibility detection for the following run() calls (hprlp_solver_set_detection); on=False switches it off."""
         det = _detection(eps_primal, eps_dual) if on else None
         self._chk(lib().hprlp_solver_set_detection(self.h, C.byref(det) if det is not None else None))
+
+    def set_start(self, x=None, y=None):
+        """Warm start of the next run() (hprlp_solver_set_start): after init(), in the model's units and numbering."""
+        xs, ys = _start_vector(x, self.model.n, "x"), _start_vector(y, self.model.m, "y")
+        self._chk(lib().hprlp_solver_set_start(self.h, _dptr(xs), _dptr(ys)))
 
     def certificate(self):
         """The certificate of the last run() (kind 0 without a verdict)."""

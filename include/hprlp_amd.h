@@ -130,6 +130,28 @@ HPRLP_batched_results hprlp_solve_batched_detect(const LP_info_cpu *model, int b
                                                  hprlp_batched_certificates *certs);
 void hprlp_free_batched_certificates(hprlp_batched_certificates *certs);
 
+/* ---- warm start (DESIGN.md "Warm start") ----------------------------------------------------------------------------------
+ * A start is x0 (length model->n) and / or y0 (length model->m) in the caller's units and numbering -- the dimensions of
+ * HPRLP_results.x / .y; NULL means zeros, a non-finite entry is an error.  It is projected (x0 clamped into [l, u]; y0 onto the
+ * sign its row's sides allow: y_i > 0 means the row sits at AL) and becomes the first iterate and the Halpern anchor.  The
+ * iteration-0 evaluation is the KKT error of the start itself, with z the dual completion of y0 (z_j = (c - A^T y0)_j where its
+ * sign has a finite bound of column j to lean on, else 0): a start that meets stop_tol ends OPTIMAL at iteration 0.  With
+ * use_presolve the start is carried into the reduced model by hprlp_presolve_forward.  Sharded solvers refuse a start. */
+/* hprlp_solve_detect from a start.  x0 == y0 == NULL: exactly hprlp_solve_detect (and so exactly solve() with det == NULL). */
+HPRLP_results hprlp_solve_warm(const LP_info_cpu *model, const HPRLP_parameters *param, const double *x0, const double *y0,
+                               const hprlp_detection *det, hprlp_certificate *cert);
+/* solve_batched() / hprlp_solve_batched_detect() from per-member starts: X0 is n x B and Y0 is m x B, column-major like C, each
+ * member's in its own units (either may be NULL: zeros).  Each member is projected, seeded and evaluated at iteration 0; a member
+ * that meets stop_tol there ends OPTIMAL with iter 0, the others iterate as before.  X0 == Y0 == NULL: exactly
+ * hprlp_solve_batched_detect (and so exactly solve_batched() with det == NULL). */
+HPRLP_batched_results hprlp_solve_batched_warm(const LP_info_cpu *model, int batch_size, const double *C, const double *AL,
+                                               const double *AU, const double *l, const double *u, const double *obj_constants,
+                                               const HPRLP_parameters *param, const double *X0, const double *Y0,
+                                               const hprlp_detection *det, hprlp_batched_certificates *certs);
+/* After hprlp_solver_init, before hprlp_solver_run: the start of the next run (caller's units; both NULL: the zero start,
+ * evaluated as a start).  -1 + hprlp_last_error() for a sharded solver or a non-finite entry. */
+int hprlp_solver_set_start(hprlp_solver *s, const double *x0, const double *y0);
+
 /* Named device vectors: x y x_hat x_bar y_bar z_bar x_temp y_temp y_obj last_x last_y AL AU l u c
  * row_norm col_norm A_val AT_val.  get returns the length (or -1); cap is the capacity of out. */
 long hprlp_solver_get_vector(hprlp_solver *s, const char *name, double *out, long cap);
@@ -143,7 +165,8 @@ int hprlp_solver_info(hprlp_solver *s, long out[8]);
 
 /* Wall-clock phases [s] of the calling thread's last HPRLP_main_solve (what solve() runs after presolve):
  * out = {device set-up (upload, transpose, tiled copies, ordering), scaling, power iteration, loop, solution's way back,
- *        teardown of the device state, whole call, 0}.  The reference's instrument covers power iteration + loop only
+ *        teardown of the device state, whole call, warm start (hprlp_solve_warm: upload, projection and the two SpMVs of
+ *        the iteration-0 evaluation; 0 for a cold start)}.  The reference's instrument covers power iteration + loop only
  * (HPRLP_results.time, src/HPRLP.cu:150,246). */
 int hprlp_last_solve_phases(double out[8]);
 
@@ -264,6 +287,10 @@ int hprlp_presolve_stats(const hprlp_presolve *p, int out[16]);
 /* (xr, yr, zr) of the reduced model -> (x, y, z) in the original dimensions */
 int hprlp_presolve_postsolve(const hprlp_presolve *p, const double *xr, const double *yr, const double *zr, double *x,
                              double *y, double *z);
+/* (x, y) in the original dimensions -> (xr, yr) of the reduced model, link by link: restriction, except where the postsolve
+ * combines values (a folded parallel column, a slack substitution, a folded parallel row), where it applies the inverse -- a
+ * primal-dual optimum of the original maps onto one of the reduced model.  Host only. */
+int hprlp_presolve_forward(const hprlp_presolve *p, const double *x, const double *y, double *xr, double *yr);
 void hprlp_presolve_free(hprlp_presolve *p);
 /* out = {primal infeasibility, dual infeasibility, gap (all relative), primal objective, dual objective} on the
  * model as given (reference compute_original_kkt_metrics, src/pslp_integration.cpp:499-580) */
