@@ -251,6 +251,25 @@ static bool is_verdict(const HPRLP_results &r) {
     return std::strcmp(r.status, "PRIMAL_INFEASIBLE") == 0 || std::strcmp(r.status, "DUAL_INFEASIBLE") == 0;
 }
 
+// solve_impl's fallback: the model as given, within what is left of the caller's time and iteration limits after `spent` seconds
+// (presolve and the reduced solve, wall clock since entry) and `it_first` iterations; so do the reported times and counts
+static HPRLP_results solve_original_rest(const LP_info_cpu *model, const HPRLP_parameters *p, const Detection *det, Certificate *cert,
+                                         const double *x0, const double *y0, double spent, int it_first) {
+    HPRLP_parameters p2 = *p;
+    p2.time_limit = std::max(p->time_limit - spent, 0.0);
+    p2.max_iter = std::max(p->max_iter - it_first, 0);
+    if (cert) *cert = Certificate();  // (only the original model's verdicts count)
+    HPRLP_results r2 = main_solve(model, &p2, det, cert, x0, y0);
+    if (std::strcmp(r2.status, "ERROR") != 0) {
+        // iter4/6/8 of a tolerance the second solve never reached are back-filled with its final count
+        // (reference src/HPRLP.cu:248-253): offset like `iter`, so they stay "<= iter"
+        r2.time += spent; r2.time4 += spent; r2.time6 += spent; r2.time8 += spent;
+        r2.iter += it_first; r2.iter4 += it_first; r2.iter6 += it_first; r2.iter8 += it_first;
+        if (cert && cert->kind) cert->iter += it_first;  // (detection: the verdict's iteration counts the same way)
+    }
+    return r2;
+}
+
 // det / cert: infeasibility detection (hprlp_solve_detect), null for solve().  x0 / y0: warm start of the model as given (hprlp_solve_warm),
 // both null for a cold start; the reduced solve starts from their image under the presolve's forward map.
 static HPRLP_results solve_impl(const LP_info_cpu *model, const HPRLP_parameters *param, const Detection *det, Certificate *cert,
@@ -355,24 +374,13 @@ static HPRLP_results solve_impl(const LP_info_cpu *model, const HPRLP_parameters
     }
     HPRLP_results r = main_solve(pre.reduced(), &pr, det, cert, xr.empty() ? nullptr : xr.data(), yr.empty() ? nullptr : yr.data());
     if (det && is_verdict(r)) {
-        // a certificate of the reduced model is no certificate of the caller's: solve the model as given, with detection, within
-        // what is left of the time and iteration limits (reported times and counts include the reduced solve, as below)
+        // a certificate of the reduced model is no certificate of the caller's: solve the model as given, with detection
         std::free(r.x); std::free(r.y); std::free(r.z);
         const double spent = time_since(t_entry);
         const int it_first = r.iter;
         std::cout << "Reduced model ended " << r.status << " at iteration " << r.iter << "; solving the original model for its certificate"
                   << std::endl;
-        HPRLP_parameters p2 = *p;
-        p2.time_limit = std::max(p->time_limit - spent, 0.0);
-        p2.max_iter = std::max(p->max_iter - it_first, 0);
-        if (cert) *cert = Certificate();
-        HPRLP_results r2 = main_solve(model, &p2, det, cert, x0, y0);
-        if (std::strcmp(r2.status, "ERROR") != 0) {
-            r2.time += spent; r2.time4 += spent; r2.time6 += spent; r2.time8 += spent;
-            r2.iter += it_first; r2.iter4 += it_first; r2.iter6 += it_first; r2.iter8 += it_first;
-            if (cert && cert->kind) cert->iter += it_first;
-        }
-        return r2;
+        return solve_original_rest(model, p, det, cert, x0, y0, spent, it_first);
     }
     if (det && cert) *cert = Certificate();  // (only the original model's verdicts count)
     if (!(r.x && r.y && r.z)) return r;
@@ -402,21 +410,9 @@ static HPRLP_results solve_impl(const LP_info_cpu *model, const HPRLP_parameters
             if (err > 100.0 * p->stop_tol && err > 1e-3) {
                 std::cout << "Postsolved solution is far from the original model's KKT conditions; solving the original model" << std::endl;
                 std::free(r.x); std::free(r.y); std::free(r.z);
-                // the caller's time limit and iteration limit cover presolve + the reduced solve (its set-up and scaling
-                // included: wall clock since entry) + this one; so do the reported times and counts
                 const double spent = time_since(t_entry);
                 const int it_first = r.iter;
-                HPRLP_parameters p2 = *p;
-                p2.time_limit = std::max(p->time_limit - spent, 0.0);
-                p2.max_iter = std::max(p->max_iter - it_first, 0);
-                HPRLP_results r2 = main_solve(model, &p2, det, cert, x0, y0);
-                if (std::strcmp(r2.status, "ERROR") != 0) {
-                    // iter4/6/8 of a tolerance the second solve never reached are back-filled with its final count
-                    // (reference src/HPRLP.cu:248-253): offset like `iter`, so they stay "<= iter"
-                    r2.time += spent; r2.time4 += spent; r2.time6 += spent; r2.time8 += spent;
-                    r2.iter += it_first; r2.iter4 += it_first; r2.iter6 += it_first; r2.iter8 += it_first;
-                    if (cert && cert->kind) cert->iter += it_first;  // (detection: the verdict's iteration counts the same way)
-                }
+                HPRLP_results r2 = solve_original_rest(model, p, det, cert, x0, y0, spent, it_first);
                 std::cout << "Fallback solve: reported time and iterations include presolve and the reduced solve (" << spent
                           << " s, " << it_first << " iterations)" << std::endl;
                 return r2;
@@ -470,29 +466,6 @@ static bool detection_from(const hprlp_detection *d, Detection *out) {
     return true;
 }
 
-extern "C" HPRLP_results hprlp_solve_detect(const LP_info_cpu *model, const HPRLP_parameters *param, const hprlp_detection *det,
-                                            hprlp_certificate *cert) {
-    const int m = model ? model->m : 0, n = model ? model->n : 0;
-    if (cert) clear_certificate(cert, m, n);
-    if (!det) return solve(model, param);
-    try {
-        Detection d;
-        detection_from(det, &d);
-        Certificate k;
-        HPRLP_results r = solve_impl(model, param, &d, &k);
-        if (std::strcmp(r.status, "ERROR") == 0 && !*last_error_cstr()) set_last_error("hprlp_solve_detect: the solve failed");
-        if (cert && !export_certificate(k, cert, m, n)) {
-            std::free(r.x); std::free(r.y); std::free(r.z);
-            throw std::runtime_error("host allocation of the certificate failed");
-        }
-        return r;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        std::cerr << "[error] hprlp_solve_detect failed: " << e.what() << std::endl;
-        return make_error_result("ERROR");
-    }
-}
-
 // a warm start's entries must be finite (null: zeros)
 static void check_start(const double *v, long len, const char *what) {
     if (!v) return;
@@ -501,20 +474,25 @@ static void check_start(const double *v, long len, const char *what) {
             throw std::runtime_error(std::string("warm start: ") + what + "[" + std::to_string(i) + "] is not finite");
 }
 
-extern "C" HPRLP_results hprlp_solve_warm(const LP_info_cpu *model, const HPRLP_parameters *param, const double *x0, const double *y0,
-                                          const hprlp_detection *det, hprlp_certificate *cert) {
-    if (!x0 && !y0) return hprlp_solve_detect(model, param, det, cert);
+// hprlp_solve_detect and hprlp_solve_warm (`who`, for the error messages).  No detection and no start: exactly solve().  The
+// certificate is cleared on entry and filled only when detection ran; a start is checked before any device work.
+static HPRLP_results solve_entry(const LP_info_cpu *model, const HPRLP_parameters *param, const double *x0, const double *y0,
+                                 const hprlp_detection *det, hprlp_certificate *cert, const char *who) {
     const int m = model ? model->m : 0, n = model ? model->n : 0;
+    const bool warm = x0 || y0;
     if (cert) clear_certificate(cert, m, n);
+    if (!det && !warm) return solve(model, param);
     try {
-        if (!model) throw std::runtime_error("null model");
-        check_start(x0, n, "x0");
-        check_start(y0, m, "y0");
+        if (warm) {
+            if (!model) throw std::runtime_error("null model");
+            check_start(x0, n, "x0");
+            check_start(y0, m, "y0");
+        }
         Detection d;
         const bool with_det = detection_from(det, &d);
         Certificate k;
         HPRLP_results r = solve_impl(model, param, with_det ? &d : nullptr, with_det ? &k : nullptr, x0, y0);
-        if (std::strcmp(r.status, "ERROR") == 0 && !*last_error_cstr()) set_last_error("hprlp_solve_warm: the solve failed");
+        if (std::strcmp(r.status, "ERROR") == 0 && !*last_error_cstr()) set_last_error(std::string(who) + ": the solve failed");
         if (cert && with_det && !export_certificate(k, cert, m, n)) {
             std::free(r.x); std::free(r.y); std::free(r.z);
             throw std::runtime_error("host allocation of the certificate failed");
@@ -522,9 +500,20 @@ extern "C" HPRLP_results hprlp_solve_warm(const LP_info_cpu *model, const HPRLP_
         return r;
     } catch (const std::exception &e) {
         set_last_error(e.what());
-        std::cerr << "[error] hprlp_solve_warm failed: " << e.what() << std::endl;
+        std::cerr << "[error] " << who << " failed: " << e.what() << std::endl;
         return make_error_result("ERROR");
     }
+}
+
+extern "C" HPRLP_results hprlp_solve_detect(const LP_info_cpu *model, const HPRLP_parameters *param, const hprlp_detection *det,
+                                            hprlp_certificate *cert) {
+    return solve_entry(model, param, nullptr, nullptr, det, cert, "hprlp_solve_detect");
+}
+
+extern "C" HPRLP_results hprlp_solve_warm(const LP_info_cpu *model, const HPRLP_parameters *param, const double *x0, const double *y0,
+                                          const hprlp_detection *det, hprlp_certificate *cert) {
+    if (!x0 && !y0) return hprlp_solve_detect(model, param, det, cert);
+    return solve_entry(model, param, x0, y0, det, cert, "hprlp_solve_warm");
 }
 
 extern "C" void hprlp_free_certificate(hprlp_certificate *cert) {
@@ -579,49 +568,25 @@ static bool export_batched_certificates(const std::vector<Certificate> &k, hprlp
     return true;
 }
 
-extern "C" HPRLP_batched_results hprlp_solve_batched_detect(const LP_info_cpu *model, int batch_size, const double *C,
-                                                            const double *AL, const double *AU, const double *l, const double *u,
-                                                            const double *obj_constants, const HPRLP_parameters *param,
-                                                            const hprlp_detection *det, hprlp_batched_certificates *certs) {
+// hprlp_solve_batched_detect and hprlp_solve_batched_warm (`who`, for the error messages), as solve_entry: no detection and no
+// starts are exactly solve_batched(); the certificates are cleared on entry and filled only when detection ran
+static HPRLP_batched_results solve_batched_entry(const LP_info_cpu *model, int batch_size, const double *C, const double *AL,
+                                                 const double *AU, const double *l, const double *u, const double *obj_constants,
+                                                 const HPRLP_parameters *param, const double *X0, const double *Y0,
+                                                 const hprlp_detection *det, hprlp_batched_certificates *certs, const char *who) {
     const int m = model ? model->m : 0, n = model ? model->n : 0, B = std::max(batch_size, 0);
+    const bool warm = X0 || Y0;
     try {
         if (certs && !clear_batched_certificates(certs, B, m, n)) {
             hprlp_free_batched_certificates(certs);
             throw std::runtime_error("host allocation of the certificates failed");
         }
-        if (!det) return solve_batched(model, batch_size, C, AL, AU, l, u, obj_constants, param);
-        Detection d;
-        detection_from(det, &d);
-        std::vector<Certificate> k;
-        HPRLP_batched_results r = solve_batched_impl(model, batch_size, C, AL, AU, l, u, obj_constants, param, &d, certs ? &k : nullptr);
-        if (certs && !export_batched_certificates(k, certs)) {
-            free_batched_results(&r);
-            hprlp_free_batched_certificates(certs);
-            throw std::runtime_error("host allocation of the certificates failed");
+        if (!det && !warm) return solve_batched(model, batch_size, C, AL, AU, l, u, obj_constants, param);
+        if (warm) {
+            if (!model) throw std::runtime_error("null model");
+            check_start(X0, static_cast<long>(n) * B, "X0");
+            check_start(Y0, static_cast<long>(m) * B, "Y0");
         }
-        return r;
-    } catch (const std::exception &e) {
-        set_last_error(e.what());
-        std::cerr << "[error] hprlp_solve_batched_detect failed: " << e.what() << std::endl;
-        return make_batched_error("ERROR", m, n, B);
-    }
-}
-
-extern "C" HPRLP_batched_results hprlp_solve_batched_warm(const LP_info_cpu *model, int batch_size, const double *C, const double *AL,
-                                                          const double *AU, const double *l, const double *u,
-                                                          const double *obj_constants, const HPRLP_parameters *param,
-                                                          const double *X0, const double *Y0, const hprlp_detection *det,
-                                                          hprlp_batched_certificates *certs) {
-    if (!X0 && !Y0) return hprlp_solve_batched_detect(model, batch_size, C, AL, AU, l, u, obj_constants, param, det, certs);
-    const int m = model ? model->m : 0, n = model ? model->n : 0, B = std::max(batch_size, 0);
-    try {
-        if (certs && !clear_batched_certificates(certs, B, m, n)) {
-            hprlp_free_batched_certificates(certs);
-            throw std::runtime_error("host allocation of the certificates failed");
-        }
-        if (!model) throw std::runtime_error("null model");
-        check_start(X0, static_cast<long>(n) * B, "X0");
-        check_start(Y0, static_cast<long>(m) * B, "Y0");
         Detection d;
         const bool with_det = detection_from(det, &d);
         std::vector<Certificate> k;
@@ -635,9 +600,27 @@ extern "C" HPRLP_batched_results hprlp_solve_batched_warm(const LP_info_cpu *mod
         return r;
     } catch (const std::exception &e) {
         set_last_error(e.what());
-        std::cerr << "[error] hprlp_solve_batched_warm failed: " << e.what() << std::endl;
+        std::cerr << "[error] " << who << " failed: " << e.what() << std::endl;
         return make_batched_error("ERROR", m, n, B);
     }
+}
+
+extern "C" HPRLP_batched_results hprlp_solve_batched_detect(const LP_info_cpu *model, int batch_size, const double *C,
+                                                            const double *AL, const double *AU, const double *l, const double *u,
+                                                            const double *obj_constants, const HPRLP_parameters *param,
+                                                            const hprlp_detection *det, hprlp_batched_certificates *certs) {
+    return solve_batched_entry(model, batch_size, C, AL, AU, l, u, obj_constants, param, nullptr, nullptr, det, certs,
+                               "hprlp_solve_batched_detect");
+}
+
+extern "C" HPRLP_batched_results hprlp_solve_batched_warm(const LP_info_cpu *model, int batch_size, const double *C, const double *AL,
+                                                          const double *AU, const double *l, const double *u,
+                                                          const double *obj_constants, const HPRLP_parameters *param,
+                                                          const double *X0, const double *Y0, const hprlp_detection *det,
+                                                          hprlp_batched_certificates *certs) {
+    if (!X0 && !Y0) return hprlp_solve_batched_detect(model, batch_size, C, AL, AU, l, u, obj_constants, param, det, certs);
+    return solve_batched_entry(model, batch_size, C, AL, AU, l, u, obj_constants, param, X0, Y0, det, certs,
+                               "hprlp_solve_batched_warm");
 }
 
 extern "C" void hprlp_free_batched_certificates(hprlp_batched_certificates *certs) {

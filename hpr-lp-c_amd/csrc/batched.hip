@@ -909,14 +909,21 @@ void ray_step(BatchWS &w, bool test) {
     finalize(w, w.gy, {B_RAY_WQ}, 0x1u);
 }
 
-// The verdict of member k from the fetched ray scalars: 1 primal infeasible, 2 dual infeasible, 0 neither (Solver::ray_verdict)
-int ray_verdict(const BatchWS &w, const Detection &det, int k) {
-    const double D = sc(w, B_RAY_DY, k) + sc(w, B_RAY_DZ, k), V = std::max(sc(w, B_RAY_VY, k), sc(w, B_RAY_VZ, k));
-    const double cd = sc(w, B_RAY_CD, k), W = std::max(sc(w, B_RAY_WD, k), sc(w, B_RAY_WQ, k));
-    if (D > 0.0 && V <= det.eps_primal * D) return 1;  // (NaN fails both tests)
-    if (cd < 0.0 && W <= det.eps_dual * -cd) return 2;
-    return 0;
+// member k's ratio-test sums from the fetched ray slots (Solver::ray_scalars)
+RayScalars ray_scalars(const BatchWS &w, int k) {
+    return RayScalars{sc(w, B_RAY_DY, k) + sc(w, B_RAY_DZ, k), std::max(sc(w, B_RAY_VY, k), sc(w, B_RAY_VZ, k)), sc(w, B_RAY_CD, k),
+                      std::max(sc(w, B_RAY_WD, k), sc(w, B_RAY_WQ, k)), sc(w, B_RAY_YN, k), sc(w, B_RAY_DN, k)};
 }
+
+// one LP of the batch: the host side of its iteration, and how it ended
+struct Member {
+    RestartState rs;
+    Residuals r;
+    std::string status = "CONTINUE";
+    int final_iter = 0;
+    int verdict = 0;  // detection: 1 primal, 2 dual infeasible
+    RayScalars ray;   // ... and the sums the verdict was reached with
+};
 
 // reference compute_weighted_norm :626-666.  DX/DY norms come from the slots the check step filled,
 // unless a movement pass has overwritten DX/DY since (then B_MOVE_* hold the matching norms).
@@ -1200,26 +1207,23 @@ HPRLP_batched_results solve_batched_impl(const LP_info_cpu *model, int batch_siz
 
         // restart state (:534-556)
         const auto solve_start = time_now();
-        const double INF = std::numeric_limits<double>::infinity();
-        std::vector<int> rflag(B, 0), inner(B, 0), final_iter(B, actual.max_iter);
-        std::vector<unsigned char> first(B, 1);
-        std::vector<double> last_gap(B, INF), cur_gap(B, INF), save_gap(B, INF), best_gap(B, INF), best_sigma(sigma.begin(), sigma.begin() + B);
-        std::vector<double> r_pobj(B, 0.0), r_dobj(B, 0.0), r_rp(B, 0.0), r_rd(B, 0.0), r_gap(B, 0.0), r_kkt(B, INF), tmp;
-        std::vector<std::string> status(B, "CONTINUE");
+        std::vector<Member> mem(B);  // (every way out of the loop below sets each member's status and final_iter)
+        for (int k = 0; k < B; ++k) mem[k].rs.best_sigma = sigma[k];
+        std::vector<double> gaps;
         const int check_iter = std::max(actual.check_iter, 1);
         const CsrDev &A = shared.A.view, &AT = shared.AT.view;
         bool dxdy_from_movement = false;
-        // detection: a verdict's kind (1 primal, 2 dual infeasible), D resp. c'd, V resp. W, and the ray's infinity norm
-        bool ray_have_prev = false;
-        std::vector<int> verdict(B, 0);
-        std::vector<double> ray_obj(B, 0.0), ray_viol(B, 0.0), ray_norm(B, 1.0);
+        bool ray_have_prev = false;  // detection
 
         int iter = 0;
         while (true) {  // one pass per event iteration (periodic check or iteration limit), :1017-1084
             const bool periodic = (iter % check_iter) == 0;
             const double elapsed = time_since(solve_start);
             if (periodic) {
-                if (iter > 0) weighted_norm(w, dxdy_from_movement, sigma, cur_gap);
+                if (iter > 0) {
+                    weighted_norm(w, dxdy_from_movement, sigma, gaps);
+                    for (int k = 0; k < B; ++k) mem[k].rs.current_gap = gaps[k];
+                }
                 // compute_residuals :578-624
                 hipLaunchKernelGGL((kb_resid<0>), dim3(w.gx * geo.nchunk), dim3(256), 0, w.stream, AT.rows, AT.rowptr, AT.col,
                                    AT.val, geo, m, w.Yb.p, static_cast<const double *>(nullptr), w.C.p, w.Zb.p,
@@ -1245,71 +1249,52 @@ HPRLP_batched_results solve_batched_impl(const LP_info_cpu *model, int batch_siz
                     // a frozen member's X_bar/Y_bar/Z_bar no longer change, so its residuals keep the
                     // values of the check that froze it (the fused dot slots only cover active members)
                     if (!active[k]) continue;
-                    const double obj_scale = b_scale[k] * c_scale[k];
-                    r_pobj[k] = obj_scale * sc(w, B_CX, k) + objc[k];
-                    r_dobj[k] = obj_scale * (sc(w, B_YOBJ_Y, k) + sc(w, B_XZ, k)) + objc[k];
-                    r_rd[k] = c_scale[k] * std::sqrt(sc(w, B_RD2, k)) / norm_c_org[k];
-                    r_rp[k] = b_scale[k] * std::sqrt(sc(w, B_RP2, k)) / norm_b_org[k];
-                    if (iter == 0) r_rp[k] = std::max(r_rp[k], b_scale[k] * std::sqrt(sc(w, B_LU2, k)));
-                    r_gap[k] = std::abs(r_pobj[k] - r_dobj[k]) / (1.0 + std::abs(r_pobj[k]) + std::abs(r_dobj[k]));
-                    r_kkt[k] = std::max(r_rp[k], std::max(r_rd[k], r_gap[k]));
+                    Residuals &r = mem[k].r;
+                    assemble_residuals(&r, {sc(w, B_CX, k), sc(w, B_YOBJ_Y, k), sc(w, B_XZ, k), sc(w, B_RD2, k), sc(w, B_RP2, k), sc(w, B_LU2, k)},
+                                       {b_scale[k], c_scale[k], norm_b_org[k], norm_c_org[k], objc[k]}, iter == 0);
+                    r.kkt = std::max(r.err_Rp, std::max(r.err_Rd, r.rel_gap));  // (solver.cpp nests the max() the other way, as the reference)
                 }
                 for (int k = 0; k < B; ++k)
-                    if (active[k] && r_kkt[k] <= actual.stop_tol) {
-                        status[k] = "OPTIMAL";
-                        final_iter[k] = iter;
+                    if (active[k] && mem[k].r.kkt <= actual.stop_tol) {  // (<= here, strict in solver.cpp, as in the reference)
+                        mem[k].status = "OPTIMAL";
+                        mem[k].final_iter = iter;
                         active[k] = 0;
                     }
                 if (ray_tested)
                     for (int k = 0; k < B; ++k) {
                         if (!active[k]) continue;  // (OPTIMAL at this evaluation takes precedence)
-                        const int v = ray_verdict(w, *det, k);
+                        const RayScalars s = ray_scalars(w, k);
+                        const int v = s.verdict(*det);
                         if (!v) continue;
-                        status[k] = v == 1 ? "PRIMAL_INFEASIBLE" : "DUAL_INFEASIBLE";
-                        final_iter[k] = iter;
+                        Member &mb = mem[k];
+                        mb.status = v == 1 ? "PRIMAL_INFEASIBLE" : "DUAL_INFEASIBLE";
+                        mb.final_iter = iter;
                         active[k] = 0;
-                        verdict[k] = v;
-                        ray_obj[k] = v == 1 ? sc(w, B_RAY_DY, k) + sc(w, B_RAY_DZ, k) : sc(w, B_RAY_CD, k);
-                        ray_viol[k] = v == 1 ? std::max(sc(w, B_RAY_VY, k), sc(w, B_RAY_VZ, k))
-                                             : std::max(sc(w, B_RAY_WD, k), sc(w, B_RAY_WQ, k));
-                        ray_norm[k] = sc(w, v == 1 ? B_RAY_YN : B_RAY_DN, k);
+                        mb.verdict = v;
+                        mb.ray = s;
                     }
                 w.active.upload(active.data(), w.Bp);
             }
             bool all_done = true;
-            for (const std::string &s : status) all_done = all_done && (s != "CONTINUE");
+            for (const Member &mb : mem) all_done = all_done && (mb.status != "CONTINUE");
             if (all_done) break;
-            if (iter >= actual.max_iter || elapsed >= actual.time_limit) {
+            if (iter >= actual.max_iter || elapsed >= actual.time_limit) {  // (>= here, strict in solver.cpp, as in the reference)
                 const char *fs = elapsed >= actual.time_limit ? "TIME_LIMIT" : "ITER_LIMIT";
                 for (int k = 0; k < B; ++k)
-                    if (status[k] == "CONTINUE") {
-                        status[k] = fs;
-                        final_iter[k] = iter;
+                    if (mem[k].status == "CONTINUE") {
+                        mem[k].status = fs;
+                        mem[k].final_iter = iter;
                         active[k] = 0;
                     }
                 break;
             }
-            std::fill(rflag.begin(), rflag.end(), 0);
-            if (periodic) {  // check_restart :667-700
-                for (int k = 0; k < B; ++k) {
-                    if (!active[k]) continue;
-                    if (first[k]) {
-                        if (iter == check_iter) {
-                            first[k] = 0; rflag[k] = 1;
-                            best_gap[k] = cur_gap[k]; best_sigma[k] = sigma[k];
-                        }
-                    } else {
-                        if (cur_gap[k] < 0.0) cur_gap[k] = 1.0e-6;
-                        if (cur_gap[k] <= 0.2 * last_gap[k]) rflag[k] = 1;
-                        if (cur_gap[k] <= 0.6 * last_gap[k] && cur_gap[k] > save_gap[k]) rflag[k] = 2;
-                        if (inner[k] >= 0.2 * iter) rflag[k] = 3;
-                        if (best_gap[k] > cur_gap[k]) { best_gap[k] = cur_gap[k]; best_sigma[k] = sigma[k]; }
-                        save_gap[k] = cur_gap[k];
-                    }
-                }
-            }
             bool restarted = false;
-            for (int k = 0; k < B; ++k) restarted = restarted || rflag[k] > 0;
+            for (int k = 0; k < B; ++k) {  // check_restart :667-700
+                RestartState &rs = mem[k].rs;
+                if (periodic && active[k]) check_restart(rs, iter, check_iter, sigma[k], false);
+                else rs.flag = 0;
+                restarted = restarted || rs.flag > 0;
+            }
             if (restarted) {
                 // update_sigma :702-745 (movement norms for every problem, formula for the flagged ones)
                 hipLaunchKernelGGL(kb_movement, dim3(std::max(w.gx, w.gy) * geo.nchunk), dim3(256), 0, w.stream, n, m, geo,
@@ -1317,38 +1302,25 @@ HPRLP_batched_results solve_batched_impl(const LP_info_cpu *model, int batch_siz
                 finalize(w, std::max(w.gx, w.gy), {B_MOVE_X2, B_MOVE_Y2});
                 fetch(w);
                 dxdy_from_movement = true;
-                const double sqrt_lambda = std::sqrt(w.lambda_max);
                 for (int k = 0; k < B; ++k) {
-                    if (!active[k] || rflag[k] < 1) continue;
-                    const double pm = std::sqrt(sc(w, B_MOVE_X2, k)), dm = std::sqrt(sc(w, B_MOVE_Y2, k));
-                    if (pm > 1.0e-16 && dm > 1.0e-16 && pm < 1.0e12 && dm < 1.0e12) {
-                        const double ratio = (pm / dm) / sqrt_lambda;
-                        const double fact = std::exp(-0.05 * (cur_gap[k] / best_gap[k]));
-                        const double temp1 = std::max(std::min(r_rd[k], r_rp[k]), std::min(r_gap[k], cur_gap[k]));
-                        const double sigma_cand = std::exp(fact * std::log(ratio) + (1.0 - fact) * std::log(best_sigma[k]));
-                        const double ratio_infeas = r_rd[k] / r_rp[k];
-                        double kappa = 1.0;
-                        if (temp1 > 9.0e-10) kappa = 1.0;
-                        else if (temp1 > 5.0e-10) kappa = std::max(std::min(std::sqrt(ratio_infeas), 100.0), 1.0e-2);
-                        else kappa = std::max(std::min(ratio_infeas, 100.0), 1.0e-2);
-                        sigma[k] = kappa * sigma_cand;
-                    } else {
-                        sigma[k] = 1.0;
-                    }
+                    const Member &mb = mem[k];
+                    if (!active[k] || mb.rs.flag < 1) continue;
+                    sigma[k] = restart_sigma(std::sqrt(sc(w, B_MOVE_X2, k)), std::sqrt(sc(w, B_MOVE_Y2, k)), w.lambda_max, mb.rs, mb.r);
                 }
                 w.sigma.upload(sigma.data(), w.Bp);
                 // do_restart :747-769
-                for (int k = 0; k < w.Bp; ++k) flags[k] = (k < B && rflag[k] > 0) ? 1 : 0;
+                for (int k = 0; k < w.Bp; ++k) flags[k] = (k < B && mem[k].rs.flag > 0) ? 1 : 0;
                 w.rflag.upload(flags.data(), w.Bp);
                 hipLaunchKernelGGL(kb_restart, dim3(std::max(w.gx, w.gy) * geo.nchunk), dim3(256), 0, w.stream, n, m, geo,
                                    w.X.p, w.lastX.p, w.Xb.p, w.Y.p, w.lastY.p, w.Yb.p, w.ctl);
                 for (int k = 0; k < B; ++k)
-                    if (active[k] && rflag[k] > 0) {
-                        inner[k] = 0;
-                        save_gap[k] = INF;
+                    if (active[k] && mem[k].rs.flag > 0) {
+                        mem[k].rs.inner = 0;
+                        mem[k].rs.save_gap = std::numeric_limits<double>::infinity();
                     }
             }
-            // iterations iter .. next-1; check variant where the reference's to_check holds (:1067-1068)
+            // iterations iter .. next-1; check variant where the reference's to_check holds (:1067-1068).  Unlike solver.cpp's
+            // next_event, the events are the periodic checks and the iteration limit only, not the log steps, as in the reference.
             int next = iter + 1;
             while (next % check_iter != 0 && next < actual.max_iter) ++next;
             int it = iter;
@@ -1365,14 +1337,14 @@ HPRLP_batched_results solve_batched_impl(const LP_info_cpu *model, int batch_siz
                     dxdy_from_movement = false;
                     ++it;
                     if (first_after_restart) {
-                        weighted_norm(w, false, sigma, tmp);
+                        weighted_norm(w, false, sigma, gaps);
                         for (int k = 0; k < B; ++k)
-                            if (rflag[k] > 0) last_gap[k] = tmp[k];
+                            if (mem[k].rs.flag > 0) mem[k].rs.last_gap = gaps[k];
                     }
                 }
             }
             for (int k = 0; k < B; ++k)
-                if (active[k]) inner[k] += next - iter;
+                if (active[k]) mem[k].rs.inner += next - iter;
             iter = next;
         }
         const double solve_time = time_since(solve_start);
@@ -1387,9 +1359,9 @@ HPRLP_batched_results solve_batched_impl(const LP_info_cpu *model, int batch_siz
             // the certificates of the members with a verdict: their YS / DS columns have not changed since (Solver::collect_certificate)
             certs->assign(B, Certificate());
             bool any_y = false, any_d = false;
-            for (int k = 0; k < B; ++k) {
-                any_y = any_y || verdict[k] == 1;
-                any_d = any_d || verdict[k] == 2;
+            for (const Member &mb : mem) {
+                any_y = any_y || mb.verdict == 1;
+                any_d = any_d || mb.verdict == 2;
             }
             std::vector<double> hYS, hZS, hDS;
             if (any_y) {  // z = -A^T y: the plain product on the device, into the scratch panel
@@ -1408,22 +1380,19 @@ HPRLP_batched_results solve_batched_impl(const LP_info_cpu *model, int batch_siz
                 w.DS.download(hDS.data(), nB);
             }
             for (int k = 0; k < B; ++k) {
-                if (!verdict[k]) continue;
+                const Member &mb = mem[k];
+                if (!mb.verdict) continue;
                 Certificate &c = (*certs)[k];
-                const double nrm = ray_norm[k];
-                c.kind = verdict[k];
-                c.iter = final_iter[k];
-                c.objective = ray_obj[k] / nrm;
-                c.violation = ray_viol[k] / nrm;
-                if (c.kind == 1) {
+                if (mb.verdict == 1) {
                     c.y.resize(m);
                     c.z.resize(n);
-                    for (int i = 0; i < m; ++i) c.y[i] = ((hYS[panel_index(geo, m, i, k)] / rn[i]) * c_scale[k]) / nrm;
-                    for (int j = 0; j < n; ++j) c.z[j] = -((hZS[panel_index(geo, n, j, k)] * cn[j]) * c_scale[k]) / nrm;
+                    for (int i = 0; i < m; ++i) c.y[i] = hYS[panel_index(geo, m, i, k)];
+                    for (int j = 0; j < n; ++j) c.z[j] = hZS[panel_index(geo, n, j, k)];
                 } else {
                     c.d.resize(n);
-                    for (int j = 0; j < n; ++j) c.d[j] = ((hDS[panel_index(geo, n, j, k)] / cn[j]) * b_scale[k]) / nrm;
+                    for (int j = 0; j < n; ++j) c.d[j] = hDS[panel_index(geo, n, j, k)];
                 }
+                finish_certificate(&c, mb.verdict, mb.final_iter, mb.ray, rn.data(), cn.data(), b_scale[k], c_scale[k]);
             }
         }
         HPRLP_batched_results out;
@@ -1450,11 +1419,11 @@ HPRLP_batched_results solve_batched_impl(const LP_info_cpu *model, int batch_siz
                 const size_t src = panel_index(geo, m, i, k), dst = static_cast<size_t>(k) * m + i;
                 out.y[dst] = (hY[src] / rn[i]) * c_scale[k];
             }
-            out.primal_obj[k] = r_pobj[k];
-            out.residuals[k] = r_kkt[k];
-            out.gap[k] = r_gap[k];
-            out.iter[k] = final_iter[k];
-            std::strncpy(out.status + 64 * k, status[k].c_str(), 63);
+            out.primal_obj[k] = mem[k].r.primal_obj;
+            out.residuals[k] = mem[k].r.kkt;
+            out.gap[k] = mem[k].r.rel_gap;
+            out.iter[k] = mem[k].final_iter;
+            std::strncpy(out.status + 64 * k, mem[k].status.c_str(), 63);
         }
         out.setup_time = setup_time;
         out.solve_time = solve_time;

@@ -2023,14 +2023,9 @@ void Solver::compute_residuals(int iter, bool compute_gap, Residuals *r, Restart
     if (ray) *ray = ray_test();  // (its scalars ride on the fetch below)
     fetch_scalars();
 
-    const double obj_scale = b_scale * c_scale;
-    r->primal_obj = obj_scale * scal_h[S_CX] + obj_constant;
-    r->dual_obj = obj_scale * (scal_h[S_YOBJ_Y] + scal_h[S_XZ]) + obj_constant;
-    r->rel_gap = std::abs(r->primal_obj - r->dual_obj) / (1.0 + std::abs(r->primal_obj) + std::abs(r->dual_obj));
-    r->err_Rd = c_scale * std::sqrt(scal_h[S_RD2]) / norm_c_org;
-    r->err_Rp = b_scale * std::sqrt(scal_h[S_RP2]) / norm_b_org;
-    if (iter == 0) r->err_Rp = std::max(r->err_Rp, b_scale * std::sqrt(scal_h[S_LU2]));
-    r->kkt = std::max(std::max(r->err_Rd, r->err_Rp), r->rel_gap);
+    assemble_residuals(r, {scal_h[S_CX], scal_h[S_YOBJ_Y], scal_h[S_XZ], scal_h[S_RD2], scal_h[S_RP2], scal_h[S_LU2]},
+                       {b_scale, c_scale, norm_b_org, norm_c_org, obj_constant}, iter == 0);
+    r->kkt = std::max(std::max(r->err_Rd, r->err_Rp), r->rel_gap);  // (batched.hip nests the max() the other way, as the reference)
     if (compute_gap && rs) rs->current_gap = weighted_norm_from(this, scal_h[S_ADX_DY], scal_h[S_DY2], scal_h[S_DX2]);
 }
 
@@ -2047,28 +2042,6 @@ double Solver::weighted_norm_after_restart() {
     return weighted_norm_from(this, scal_h[S_ADX_DY], scal_h[S_DY2], scal_h[S_DX2]);
 }
 
-static void check_restart(RestartState *rs, int iter, int check_iter, double sigma, bool verbose) {
-    rs->flag = 0;
-    if (rs->first) {
-        if (iter == check_iter) {
-            rs->first = false;
-            rs->flag = 1;
-            rs->best_gap = rs->current_gap;
-            rs->best_sigma = sigma;
-        }
-    } else if (iter % check_iter == 0) {
-        if (rs->current_gap < 0) {
-            rs->current_gap = 1e-6;
-            if (verbose) std::cout << "current_gap < 0" << std::endl;
-        }
-        if (rs->current_gap <= 0.2 * rs->last_gap) { rs->sufficient += 1; rs->flag = 1; }
-        if (rs->current_gap <= 0.6 * rs->last_gap && rs->current_gap > 1.00 * rs->save_gap) { rs->necessary += 1; rs->flag = 2; }
-        if (rs->inner >= 0.2 * iter) { rs->long_ += 1; rs->flag = 3; }
-        if (rs->best_gap > rs->current_gap) { rs->best_gap = rs->current_gap; rs->best_sigma = sigma; }
-        rs->save_gap = rs->current_gap;
-    }
-}
-
 void Solver::update_sigma_and_restart(RestartState *rs, const Residuals &r) {
     if (rs->flag <= 0) return;
     // movement x_bar - last_x, y_bar - last_y and their norms (update_sigma, main_iterate.cu:367-404)
@@ -2081,30 +2054,13 @@ void Solver::update_sigma_and_restart(RestartState *rs, const Residuals &r) {
     launch_finalize(f, scal.p, stream);
     allreduce_slots(this, S_MOVE_X2, 2);
     fetch_scalars();
-    const double primal_move = std::sqrt(scal_h[S_MOVE_X2]), dual_move = std::sqrt(scal_h[S_MOVE_Y2]);
-    double new_sigma = 1.0;
-    if (primal_move > 1e-16 && dual_move > 1e-16 && primal_move < 1e12 && dual_move < 1e12) {
-        const double ratio = (primal_move / dual_move) / std::sqrt(lambda_max);
-        const double fact = std::exp(-0.05 * (rs->current_gap / rs->best_gap));
-        const double temp1 = std::max(std::min(r.err_Rd, r.err_Rp), std::min(r.rel_gap, rs->current_gap));
-        const double sigma_cand = std::exp(fact * std::log(ratio) + (1 - fact) * std::log(rs->best_sigma));
-        double kappa;
-        if (temp1 > 9e-10) {
-            kappa = 1.0;
-        } else if (temp1 > 5e-10) {
-            kappa = std::max(std::min(std::sqrt(r.err_Rd / r.err_Rp), 100.0), 1e-2);
-        } else {
-            kappa = std::max(std::min(r.err_Rd / r.err_Rp, 100.0), 1e-2);
-        }
-        new_sigma = kappa * sigma_cand;
-    }
+    const double new_sigma = restart_sigma(std::sqrt(scal_h[S_MOVE_X2]), std::sqrt(scal_h[S_MOVE_Y2]), lambda_max, *rs, r);
     // do_restart (main_iterate.cu:312-322) + Halpern reset (:54-66)
     invalidate_far();  // y changes under the remainder buffer of A^T
     launch_restart_copy(n_loc, m_loc, x_bar, x.p, last_x.p, y_bar, y, last_y.p, ctrl.p, stream);
     gather(gy.p, true);
     set_sigma_lambda(new_sigma, lambda_max, true);
     rs->inner = 0;
-    rs->times += 1;
     rs->save_gap = std::numeric_limits<double>::infinity();
 }
 
@@ -2112,6 +2068,7 @@ void Solver::update_sigma_and_restart(RestartState *rs, const Residuals &r) {
 // the outer loop (reference src/HPRLP.cu:154-310).  `iter` only ever stops at event iterations
 // (periodic check, log line, iteration limit); everything between two events is enqueued at once.
 // ------------------------------------------------------------------------------------------------
+// (the batched loop stops at periodic checks and the iteration limit only, not at log steps: batched.hip)
 static int next_event(int iter, int check_iter, int max_iter) {
     int j = iter + 1;
     while (true) {
@@ -2143,9 +2100,9 @@ void Solver::solve_loop(HPRLP_results *out) {
         const bool periodic = (iter % check_iter == 0);
         bool ray = false;
         compute_residuals(iter, periodic && iter > 0, &r, &rs, detect.on && periodic && iter > 0 ? &ray : nullptr);
-        const int verdict = ray ? ray_verdict() : 0;
+        const int verdict = ray ? ray_scalars().verdict(detect) : 0;
         const double elapsed = t_before + time_since(t_loop);
-        bool timed_out = elapsed > prm.time_limit;
+        bool timed_out = elapsed > prm.time_limit;  // (strict here, >= in batched.hip, as in the reference)
         if (comm && comm->size > 1) {
             // the residuals are all-reduced, the clocks are not: every rank must take the same TIME_LIMIT decision, or
             // one leaves the loop while its peers enter the next exchange (a collective hang).  Any rank over its limit
@@ -2156,12 +2113,12 @@ void Solver::solve_loop(HPRLP_results *out) {
             fetch_scalars();
             timed_out = scal_h[S_TMP1] > 0.0;
         }
-        if (r.kkt < prm.stop_tol) status = "OPTIMAL";
+        if (r.kkt < prm.stop_tol) status = "OPTIMAL";  // (strict here, <= in batched.hip, as in the reference)
         else if (verdict == 1) status = "PRIMAL_INFEASIBLE";
         else if (verdict == 2) status = "DUAL_INFEASIBLE";
         else if (at_limit) status = "ITER_LIMIT";
         else if (timed_out) status = "TIME_LIMIT";
-        if (periodic && !at_limit) check_restart(&rs, iter, check_iter, sigma, verbose);
+        if (periodic && !at_limit) check_restart(rs, iter, check_iter, sigma, verbose);
         else rs.flag = 0;
         if (trace && trace_n < trace_cap)
             trace[trace_n++] = TraceRow{iter, rs.flag, r.err_Rp, r.err_Rd, r.primal_obj, r.dual_obj, r.rel_gap, r.kkt,
@@ -2289,53 +2246,38 @@ bool Solver::ray_test() {
     return true;
 }
 
-int Solver::ray_verdict() {
-    const double D = scal_h[S_RAY_DY] + scal_h[S_RAY_DZ], V = std::max(scal_h[S_RAY_VY], scal_h[S_RAY_VZ]);
-    const double cd = scal_h[S_RAY_CD], W = std::max(scal_h[S_RAY_WD], scal_h[S_RAY_WQ]);
-    if (D > 0.0 && V <= detect.eps_primal * D) return 1;  // (NaN fails both tests)
-    if (cd < 0.0 && W <= detect.eps_dual * -cd) return 2;
-    return 0;
+RayScalars Solver::ray_scalars() {
+    return RayScalars{scal_h[S_RAY_DY] + scal_h[S_RAY_DZ], std::max(scal_h[S_RAY_VY], scal_h[S_RAY_VZ]), scal_h[S_RAY_CD],
+                      std::max(scal_h[S_RAY_WD], scal_h[S_RAY_WQ]), scal_h[S_RAY_YN], scal_h[S_RAY_DN]};
 }
 
 void Solver::collect_certificate(int kind, int iter) {
     cert = Certificate();
-    cert.kind = kind;
-    cert.iter = iter;
     std::vector<double> rn(static_cast<size_t>(m_loc)), cn(static_cast<size_t>(n_loc));
     HIP_CHECK(hipMemcpyAsync(rn.data(), row_norm.p, sizeof(double) * m_loc, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipMemcpyAsync(cn.data(), col_norm.p, sizeof(double) * n_loc, hipMemcpyDeviceToHost, stream));
     auto unpermute = [](std::vector<double> &v, const std::vector<int> &perm) {
-        if (perm.empty()) return;
+        if (perm.empty() || v.empty()) return;  // (no ordering, or an array this kind does not use)
         const std::vector<double> tmp(v);
         for (size_t i = 0; i < perm.size(); ++i) v[perm[i]] = tmp[i];
     };
     if (kind == 1) {
-        // y and z = -A^T y of the ray, as k_unscale maps y_bar and z_bar; A^T y_s into scratch sn1 by the plain product
-        const double D = scal_h[S_RAY_DY] + scal_h[S_RAY_DZ], V = std::max(scal_h[S_RAY_VY], scal_h[S_RAY_VZ]);
-        const double yn = scal_h[S_RAY_YN];
+        // y and z = -A^T y of the ray; A^T y_s into scratch sn1 by the plain product
         invalidate_far();
         launch_spmv_plain(AT.view, ray_y.p, sn1.p, nullptr, false, nullptr, 0, stream);
         cert.y.resize(static_cast<size_t>(m_loc));
         cert.z.resize(static_cast<size_t>(n_loc));
         HIP_CHECK(hipMemcpyAsync(cert.y.data(), ray_y.p, sizeof(double) * m_loc, hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipMemcpyAsync(cert.z.data(), sn1.p, sizeof(double) * n_loc, hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
-        for (int i = 0; i < m_loc; ++i) cert.y[i] = ((cert.y[i] / rn[i]) * c_scale) / yn;
-        for (int j = 0; j < n_loc; ++j) cert.z[j] = -((cert.z[j] * cn[j]) * c_scale) / yn;
-        cert.objective = D / yn;
-        cert.violation = V / yn;
-        unpermute(cert.y, perm_r);
-        unpermute(cert.z, perm_c);
     } else {
-        const double cd = scal_h[S_RAY_CD], W = std::max(scal_h[S_RAY_WD], scal_h[S_RAY_WQ]), dn = scal_h[S_RAY_DN];
         cert.d.resize(static_cast<size_t>(n_loc));
         HIP_CHECK(hipMemcpyAsync(cert.d.data(), ray_d.p, sizeof(double) * n_loc, hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
-        for (int j = 0; j < n_loc; ++j) cert.d[j] = ((cert.d[j] / cn[j]) * b_scale) / dn;
-        cert.objective = cd / dn;
-        cert.violation = W / dn;
-        unpermute(cert.d, perm_c);
     }
+    HIP_CHECK(hipStreamSynchronize(stream));
+    finish_certificate(&cert, kind, iter, ray_scalars(), rn.data(), cn.data(), b_scale, c_scale);
+    unpermute(cert.y, perm_r);
+    unpermute(cert.z, perm_c);
+    unpermute(cert.d, perm_c);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -15,37 +15,9 @@
 #include "env.h"
 #include "dist.h"
 #include "kernels.h"
+#include "hpr_rules.h"
 
 namespace hprlp {
-
-struct Residuals {  // reference HPRLP_residuals, include/structs.h:255-263
-    double err_Rp = 0, err_Rd = 0, primal_obj = 0, dual_obj = 0, rel_gap = 0;
-    double kkt = std::numeric_limits<double>::infinity();
-};
-
-struct RestartState {  // reference HPRLP_restart, include/structs.h:215-228
-    int flag = 0;
-    bool first = true;
-    double last_gap = std::numeric_limits<double>::infinity();
-    double current_gap = std::numeric_limits<double>::infinity();
-    double save_gap = std::numeric_limits<double>::infinity();
-    double best_gap = std::numeric_limits<double>::infinity();
-    double best_sigma = 1.0;
-    int inner = 0, sufficient = 0, necessary = 0, long_ = 0, times = 0;
-};
-
-// Infeasibility detection (opt-in, one GPU; DESIGN.md "Infeasibility and unboundedness"): the Farkas ratio tests' tolerances ...
-struct Detection {
-    bool on = false;
-    double eps_primal = 1e-8, eps_dual = 1e-8;
-};
-// ... and what a verdict leaves: kind 1 (primal infeasible: y, z = -A^T y) or 2 (dual infeasible: d), the ray in the caller's
-// units and numbering, scaled to infinity norm 1; objective = D(y) resp. c'd, violation = V(y) resp. W(d) of that ray
-struct Certificate {
-    int kind = 0, iter = 0;
-    double objective = 0.0, violation = 0.0;
-    std::vector<double> y, z, d;
-};
 
 // batched.hip: solve_batched with the infeasibility detection, member by member (DESIGN.md "Batched detection").  det null or
 // off: exactly solve_batched.  certs (may be null) receives one Certificate per member, kind 0 where no verdict was reached.
@@ -194,15 +166,15 @@ struct Solver {
     DBuf<int> small_ij, small_posA;          // per A^T entry: i | j << 16, position in the CSR order of A
 
     // Infeasibility detection: at every periodic evaluation the rays d = x_bar - x_bar(previous evaluation), y = y_bar - y_bar(...)
-    // pass the ratio tests or not (ray_test enqueues, ray_verdict judges after the evaluation's scalar fetch).  The buffers exist
-    // only while detection is on; nothing the iteration reads is touched, so the iterates are the same bits either way.
+    // pass the ratio tests or not (ray_test enqueues, ray_scalars().verdict() judges after the evaluation's scalar fetch).  The
+    // buffers exist only while detection is on; nothing the iteration reads is touched, so the iterates are the same bits either way.
     Detection detect;
     DBuf<double> ray_prev_x, ray_prev_y, ray_d, ray_y, ray_part;
     bool ray_have_prev = false;
     Certificate cert;  // of the last solve_loop (kind 0: no verdict)
     void ray_begin();              // solve_loop: buffers allocated (first time) and the previous iterate forgotten
     bool ray_test();               // enqueue the rays' kernels and reductions; false at the first evaluation (no previous iterate yet)
-    int ray_verdict();             // after fetch_scalars: 1 primal infeasible, 2 dual infeasible, 0 neither
+    RayScalars ray_scalars();      // after fetch_scalars: the ratio tests' sums of the last ray_test
     void collect_certificate(int kind, int iter);
 
     // Warm start (DESIGN.md "Warm start"): after init_iteration_state(), before solve_loop().  x0 (n) / y0 (m): the caller's point

@@ -254,6 +254,24 @@ def _detection(eps_primal, eps_dual):
     return CDetection(float(eps_primal), float(eps_dual))
 
 
+def _detection_arg(eps_primal, eps_dual):
+    """The solve entries' eps arguments as a CDetection (either None: 1e-8), or None when both are None (detection off)."""
+    if eps_primal is None and eps_dual is None:
+        return None
+    return _detection(1e-8 if eps_primal is None else eps_primal, 1e-8 if eps_dual is None else eps_dual)
+
+
+def _batched_certificates(cc):
+    """A filled CBatchedCertificates as the "certificates" dict of solve_batched_detect(); frees the C arrays."""
+    B, m, n = cc.batch_size, cc.m, cc.n
+    g = lambda q, k, dt=np.float64: None if not q else np.ctypeslib.as_array(q, shape=(k,)).astype(dt, copy=True)
+    panel = lambda q, rows: None if not q else g(q, rows * B).reshape(B, rows).T.copy()
+    out = dict(kind=g(cc.kind, B, np.int32), iter=g(cc.iter, B, np.int32), objective=g(cc.objective, B),
+               violation=g(cc.violation, B), y=panel(cc.y, m), z=panel(cc.z, n), d=panel(cc.d, n))
+    lib().hprlp_free_batched_certificates(C.byref(cc))
+    return out
+
+
 def _start_vector(v, length, name):
     """A warm-start vector as a contiguous float64 array of the given length (None stays None: zeros)."""
     if v is None:
@@ -356,8 +374,7 @@ class Model:
         """solve() with infeasibility detection (hprlp_solve_detect): status PRIMAL_INFEASIBLE / DUAL_INFEASIBLE with the
         certificate in `.certificate`.  eps_primal=None and eps_dual=None: detection off (exactly solve())."""
         cp = (param or Parameters()).to_c()
-        det = None if eps_primal is None and eps_dual is None else _detection(
-            1e-8 if eps_primal is None else eps_primal, 1e-8 if eps_dual is None else eps_dual)
+        det = _detection_arg(eps_primal, eps_dual)
         cc = CCertificate()
         res = lib().hprlp_solve_detect(self._ptr, C.byref(cp), C.byref(det) if det is not None else None, C.byref(cc))
         r = Results(res, self.m, self.n)
@@ -369,8 +386,7 @@ class Model:
         solve()).  eps_primal / eps_dual not None: with infeasibility detection, the certificate in `.certificate`."""
         xs, ys = _start_vector(x, self.n, "x"), _start_vector(y, self.m, "y")
         cp = (param or Parameters()).to_c()
-        det = None if eps_primal is None and eps_dual is None else _detection(
-            1e-8 if eps_primal is None else eps_primal, 1e-8 if eps_dual is None else eps_dual)
+        det = _detection_arg(eps_primal, eps_dual)
         cc = CCertificate()
         res = lib().hprlp_solve_warm(self._ptr, C.byref(cp), _dptr(xs), _dptr(ys), C.byref(det) if det is not None else None,
                                      C.byref(cc))
@@ -462,20 +478,14 @@ def solve_batched_detect(model, Cmat, AL, AU, l, u, obj_constants=None, param=No
     DUAL_INFEASIBLE, and "certificates": kind, iter, objective, violation (length B), y (m, B), z and d (n, B) or None; a
     member's columns are zero where its kind does not use them.  eps_primal=None and eps_dual=None: detection off (exactly
     solve_batched())."""
-    det = None if eps_primal is None and eps_dual is None else _detection(
-        1e-8 if eps_primal is None else eps_primal, 1e-8 if eps_dual is None else eps_dual)
+    det = _detection_arg(eps_primal, eps_dual)
     cc = CBatchedCertificates()
 
     def call(B, args, cp):
         return lib().hprlp_solve_batched_detect(model._ptr, B, *args, C.byref(cp), C.byref(det) if det is not None else None,
                                                 C.byref(cc))
     out = _batched_call(call, model, Cmat, AL, AU, l, u, obj_constants, param)
-    B, m, n = cc.batch_size, cc.m, cc.n
-    g = lambda q, k, dt=np.float64: None if not q else np.ctypeslib.as_array(q, shape=(k,)).astype(dt, copy=True)
-    panel = lambda q, rows: None if not q else g(q, rows * B).reshape(B, rows).T.copy()
-    out["certificates"] = dict(kind=g(cc.kind, B, np.int32), iter=g(cc.iter, B, np.int32), objective=g(cc.objective, B),
-                               violation=g(cc.violation, B), y=panel(cc.y, m), z=panel(cc.z, n), d=panel(cc.d, n))
-    lib().hprlp_free_batched_certificates(C.byref(cc))
+    out["certificates"] = _batched_certificates(cc)
     return out
 
 
@@ -486,8 +496,7 @@ def solve_batched_warm(model, Cmat, AL, AU, l, u, X0=None, Y0=None, obj_constant
     solve_batched_detect()."""
     B = np.asarray(Cmat).shape[1]
     X0, Y0 = _start_panel(X0, model.n, B, "X0"), _start_panel(Y0, model.m, B, "Y0")
-    det = None if eps_primal is None and eps_dual is None else _detection(
-        1e-8 if eps_primal is None else eps_primal, 1e-8 if eps_dual is None else eps_dual)
+    det = _detection_arg(eps_primal, eps_dual)
     cc = CBatchedCertificates()
 
     def call(B, args, cp):
@@ -495,12 +504,7 @@ def solve_batched_warm(model, Cmat, AL, AU, l, u, X0=None, Y0=None, obj_constant
                                               C.byref(det) if det is not None else None, C.byref(cc) if det is not None else None)
     out = _batched_call(call, model, Cmat, AL, AU, l, u, obj_constants, param)
     if det is not None:
-        Bc, m, n = cc.batch_size, cc.m, cc.n
-        g = lambda q, k, dt=np.float64: None if not q else np.ctypeslib.as_array(q, shape=(k,)).astype(dt, copy=True)
-        panel = lambda q, rows: None if not q else g(q, rows * Bc).reshape(Bc, rows).T.copy()
-        out["certificates"] = dict(kind=g(cc.kind, Bc, np.int32), iter=g(cc.iter, Bc, np.int32), objective=g(cc.objective, Bc),
-                                   violation=g(cc.violation, Bc), y=panel(cc.y, m), z=panel(cc.z, n), d=panel(cc.d, n))
-        lib().hprlp_free_batched_certificates(C.byref(cc))
+        out["certificates"] = _batched_certificates(cc)
     return out
 
 
