@@ -9,7 +9,8 @@
 // one problem, 64 / Bc rows per wave.  A workgroup works on ONE chunk, chunk = blockIdx.x % (number of chunks):
 // workgroups go round-robin to the 8 XCDs, so with 8 chunks every XCD gathers from the same eighth of the
 // gathered panel (config 4: 2.2 MB of Y instead of 17 MB -- it stays in the XCD's 4 MiB L2).  Each problem's row sums are accumulated sequentially in CSR order, exactly like
-// the single-LP stream kernel, so the result is bit-identical to the oracle's batched restatement.
+// the single-LP stream kernel, so the result is bit-identical to the oracle's batched restatement (held to it iterate by
+// iterate up to the first restart, and within the oracle's own sensitivity after, by tests/test_gpu_batched_kernels.py).
 // The half-step update (projection, reflection, Halpern average, per-problem sigma / inner counter /
 // active mask) is fused into the SpMM epilogue: one launch per half-step, no per-iteration host sync
 // (the reference synchronises the stream and uploads 2B doubles every iteration, :1070-1073).
@@ -787,12 +788,16 @@ struct BatchWS {
     BatchCtl ctl{};
     double lambda_max = 1.0;
     int gx = 1, gy = 1;  // row blocks of the n- / m-row launches with partials (the grid is geo.nchunk times that)
+    int grid_cap = 0;    // HPRLP_BATCH_GRID of this call: most row blocks of a normal half-step launch (0: as many as the rows need)
     Geo geo{};
     hipStream_t stream = nullptr;
     std::map<int, hipGraphExec_t> graphs;
-    ~BatchWS() {
+    // The captured launches hold lambda_max BY VALUE (HalfArgs): whoever changes it drops them, and run_normal captures anew.
+    void drop_graphs() {
         for (auto &kv : graphs) (void)hipGraphExecDestroy(kv.second);
+        graphs.clear();
     }
+    ~BatchWS() { drop_graphs(); }
 };
 
 int padded_batch(int B) {
@@ -846,8 +851,7 @@ void launch_half_pair(BatchWS &w, bool check) {
     } else {
         // no reduction partials in the normal variant: one pass over the rows, as many workgroups as rows need
         const int rpb = g.Bw >= 8 ? 4 * kRowsPerWave * (64 / g.Bw) : g.rows_per_block;
-        static const int grid_cap = env_get("HPRLP_BATCH_GRID") ? std::atoi(env_get("HPRLP_BATCH_GRID")) : 0;  // experiment knob
-        auto cap = [&](int gr) { return grid_cap > 0 ? std::min(gr, grid_cap) : gr; };
+        auto cap = [&](int gr) { return w.grid_cap > 0 ? std::min(gr, w.grid_cap) : gr; };
         launch(T{}, F{}, dim3(cap((AT.rows + rpb - 1) / rpb) * g.nchunk), AT, xa);
         launch(F{}, F{}, dim3(cap((A.rows + rpb - 1) / rpb) * g.nchunk), A, ya);
     }
@@ -935,6 +939,7 @@ void weighted_norm(BatchWS &w, bool dxdy_from_movement, std::vector<double> &sig
     finalize(w, w.gy, {B_ADX_DY});
     fetch(w);
     out.assign(w.B, 0.0);
+    const double lambda_before = w.lambda_max;
     for (int k = 0; k < w.B; ++k) {
         const double dot_prod = 2.0 * sc(w, B_ADX_DY, k);
         // the reference squares cublasDnrm2 results (:653-654); sqrt-then-square keeps that rounding
@@ -949,6 +954,8 @@ void weighted_norm(BatchWS &w, bool dxdy_from_movement, std::vector<double> &sig
         }
         out[k] = std::sqrt(std::max(value, 0.0));
     }
+    // a bump: the graphs replay the old lambda (the stream is idle after fetch(): nothing of theirs is in flight)
+    if (w.lambda_max != lambda_before) w.drop_graphs();
 }
 
 double bound_norm_host(const double *AL, const double *AU, int m, size_t off) {  // :332-345
@@ -1085,7 +1092,10 @@ HPRLP_batched_results solve_batched_impl(const LP_info_cpu *model, int batch_siz
         }
 
         // lambda_max on the scaled shared matrix (:994-1001)
-        const double lambda0 = shared.power_iteration(5000, 1.0e-4, nullptr) * 1.01;
+        // (test hook HPRLP_BATCH_LAMBDA: the caller's value instead, so that a reference can run on the same bits)
+        const char *lambda_hook = env_get("HPRLP_BATCH_LAMBDA");
+        const double lambda0 = lambda_hook ? std::strtod(lambda_hook, nullptr) : shared.power_iteration(5000, 1.0e-4, nullptr) * 1.01;
+        if (!(lambda0 > 0.0) || !std::isfinite(lambda0)) throw std::runtime_error("HPRLP_BATCH_LAMBDA is not a positive finite number");
         const double power_time = shared.power_time;
 
         // workspace (:479-532): row-major padded panels
@@ -1096,6 +1106,7 @@ HPRLP_batched_results solve_batched_impl(const LP_info_cpu *model, int batch_siz
         w.lambda_max = lambda0;
         w.geo = make_geo(w.Bp, choose_chunk(m, n, w.Bp));
         const Geo &geo = w.geo;
+        if (const char *e = env_get("HPRLP_BATCH_GRID")) w.grid_cap = std::atoi(e);
         w.gx = grid_for(n, geo);
         w.gy = grid_for(m, geo);
         if (geo.Bw >= 8) {

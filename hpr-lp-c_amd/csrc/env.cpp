@@ -20,7 +20,8 @@ static const EnvEntry kTable[] = {
     {"HPRLP_NO_OVERLAP", EnvKind::Integrator, "multi-GPU: shards unsplit, exchange in line on the solver stream"},
     {"HPRLP_DIST_TIMEOUT_S", EnvKind::Integrator, "seconds a rank of the shared-memory transport waits for its peers before it fails (default 120)"},
     {"HPRLP_BATCH_CHUNK", EnvKind::Hook, "solve_batched with 64 or more problems: chunk width of the panels (default 64; narrower chunks map one chunk to each XCD -- measured slower, profiles/r03_tiled_decomposition.md section 6b)"},
-    {"HPRLP_BATCH_GRID", EnvKind::Hook, "solve_batched: workgroups of the half-step kernels"},
+    {"HPRLP_BATCH_GRID", EnvKind::Hook, "solve_batched: cap on the row blocks of the normal half-step kernels (read at every call; a small cap makes every workgroup's row loop wrap)"},
+    {"HPRLP_BATCH_LAMBDA", EnvKind::Hook, "solve_batched: the batch's lambda_max from the caller (strtod; hand it over as a C99 hex float to keep every bit) instead of 1.01 x the power iteration's estimate (read at every call)"},
     {"HPRLP_COPY_PAUSE_US", EnvKind::Hook, "piece size and pause of the threaded copies of set-up (64 MB, 100 us)"},
     {"HPRLP_COPY_PIECE_MB", EnvKind::Hook, "piece size and pause of the threaded copies of set-up (64 MB, 100 us)"},
     {"HPRLP_DEVICE_TRANSPOSE_MIN", EnvKind::Hook, "build Aᵀ on the host / nonzero threshold of the device transpose (default 4 M)"},
