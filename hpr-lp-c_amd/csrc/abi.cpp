@@ -1240,15 +1240,7 @@ extern "C" int hprlp_solver_describe(hprlp_solver *h, char *buf, int cap) {
         std::string d = std::string(name) + ": ";
         if (!t.valid) {
             d += "stream kernel (k_spmv_fused, " + std::to_string(M.view.nblk) + " row blocks, " + std::to_string(M.view.nlong) + " split rows)";
-            if (M.declined_skew) d += " [tiled form not attempted: too many entries in long rows]";
-            else if (M.declined_imbalance) d += " [tiled form not attempted: unbalanced row blocks]";
-            else if (M.declined_coalesced) d += " [tiled form not attempted: neighbouring rows gather from the same lines]";
-            else if (M.declined_l2) d += " [tiled form not attempted: the stream kernel's gathers stay in one L2]";
-            else if (M.declined_shape) d += " [tiled form not attempted: shape]";
-            else if (M.declined_sparse) d += " [tiled form declined: too few entries in dense tiles]";
-            else if (M.declined_thin) d += " [tiled piece form declined: thin rows]";
-            else if (M.declined_popular) d += " [tiled form declined: its remainder gathers from a few popular columns]";
-            else if (M.declined_few_rows) d += " [tiled form not attempted: too few rows]";
+            d += no_tiled_note(M.outcome.why);
             return d;
         }
         d += t.n_pieces > 0 ? "tiled, piece form (k_tiled_part + k_tiled_finish, " + std::to_string(t.n_pieces) + " pieces)"
@@ -1271,6 +1263,31 @@ extern "C" int hprlp_solver_describe(hprlp_solver *h, char *buf, int cap) {
     if (!s.env_ignored_at_setup.empty()) d += "; ignored without HPRLP_TEST_HOOKS=1: " + s.env_ignored_at_setup;
     std::snprintf(buf, static_cast<size_t>(cap), "%s", d.c_str());
     return static_cast<int>(d.size());
+    GUARD_END(-1)
+}
+
+// Host only: the staged decisions of the kernel-form selection (form_select.h) for a facts record
+extern "C" int hprlp_form_select(const hprlp_form_facts *facts, const hprlp_form_hooks *hooks, hprlp_form_decision *out) {
+    try {
+        if (!facts || !out) throw std::runtime_error("bad arguments");
+        const char *missing = "";
+        if (!form_select(*facts, hooks ? *hooks : FormHooks(), out, &missing))
+            throw std::runtime_error(std::string("the rules ask for a fact that the record marks as not measured: ") + missing);
+        return 0;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+extern "C" int hprlp_solver_form_facts(hprlp_solver *h, int which, hprlp_form_facts out[2]) {
+    GUARD_BEGIN
+    if (!h || !out || which < 0 || which > 1) throw std::runtime_error("null solver / buffer, or no such matrix");
+    h->s.finish_tiling();
+    const DeviceMatrix &M = which ? h->s.AT : h->s.A;
+    out[0] = M.facts;
+    out[1] = M.facts_pb;
+    return M.passes;
     GUARD_END(-1)
 }
 

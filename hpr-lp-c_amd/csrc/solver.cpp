@@ -239,26 +239,10 @@ static int workgroup_slots() {
     return cus * kTileResidentPerCu;
 }
 
-constexpr int kSkewRow = 256;              // build_tiled_copy: rows longer than this count as long ...
-constexpr double kMaxLongRowShare = 0.2;   // ... and a matrix with more than this share of its entries in them keeps the stream kernel
-constexpr double kMaxBlockLoad = 4.0;      // build_tiled_copy: heaviest block of sb_rows rows / mean, above which the fused tiled forms are declined
-constexpr double kPiecesMinDense = 0.75;   // build_tiled_copy: share of the entries in staged tiles below which the PIECE form is declined
-constexpr double kStreamLineDensity = 0.25;  // build_tiled_copy: at most this many 64-byte lines gathered per entry -> stream kernel
-constexpr double kStreamL2LineDensity = 0.6;  // ... and only while neighbouring rows still share lines: with a line per entry the L2 holds the window but every gather
-                                              // misses the L1 (1.5M x 1.5M, band 75 000, 0.93 lines per entry: stream 0.177 ms per half-step, pieces 0.128; the
-                                              // multicommodity-flow LP the rule was made for: 0.35 / 0.15)
-constexpr int kTiledMinCols = 7 << 16;        // build_tiled_copy: fewest columns of a matrix that is tried in a tiled form (458 752: 3.5 MiB of gathered vector)
-constexpr double kStreamLineDensityLong = 0.12;  // ... lines per entry up to which rows of ANY length keep the coalesced-rows preference
-constexpr double kCoalescedMaxRowEntries = 32.0;   // build_tiled_copy: the coalesced-rows preference for the stream kernel holds up to this many entries per row
-constexpr double kStreamL2LineDensityFused = 0.5;  // ... the same against a FUSED tiled form that needs its longest rows kept aside (build_tiled_copy)
-constexpr double kFewRowsTileShare = 1.8;    // build_tiled_copy: most tile bytes per entry byte at which a matrix of few rows is still tried in the piece form
-                                             // (threshold sweep, tools/form_regret.py --corpus boundaries: piece form ahead of the all-remainder form by 12-41 % at
-                                             // 0.8 / 1.2 / 1.5, level at 1.3, behind by 8-17 % at 2.2 / 2.8 and 2-3 x from 3.2 on)
-constexpr double kPopularFarShare = 0.8;     // build_tiled_copy: share of the remainder that 2 MB of the gathered vector serve, from which ...
-constexpr double kPopularFarMinRem = 0.1;    // ... a copy with at least this share of its entries in the remainder is dropped for the stream kernel (one-L2 window)
-constexpr double kPiecesThinRows = 10.0;     // build_tiled_copy: below this many entries per row a PIECE-form copy is dropped for the stream kernel
-constexpr double kPiecesMinRowEntries = 16.0;  // ... or while rows are thin (build_tiled_copy)
-constexpr double kStreamL2Bytes = 3.0e6;  // build_tiled_copy: an XCD's share of the gathered vector that one 4 MiB L2 keeps beside the matrix stream
+// form_select.h is host-only and cannot include tiled.h: the tile geometry its rules speak of must be the kernels'
+static_assert(kFormTileRows == kTileRows && kFormTileRowsMin == kTileRowsMin && kFormTileCols == kTileCols && kFormTileColsNarrow == kTileColsNarrow &&
+                  kFormMaxRow == kTileMaxRow && kFormPbRowsMax == kPbRowsMax,
+              "form_select.h and tiled.h disagree on the tile geometry");
 
 // HPRLP_TIMING=1: wall time of the set-up phases on stderr
 struct PhaseTimer {
@@ -399,7 +383,7 @@ void DeviceMatrix::describe_when(int rows, int cols, long nnz_l, std::shared_fut
     if (const char *e = env_get("HPRLP_NT")) view.nt = std::atoi(e) != 0;
     try {
         longest_row = 0;
-        long_row_share = 0.0;
+        double long_row_share = 0.0;  // share of the entries in rows of more than kSkewRow entries (0 for small matrices)
         if (rows > 100000) {  // (from the device copy: the host row pointers of A^T may still be on their way)
             long in_long = 0;
             longest_row = launch_longest_row(rowptr.p, rows, nullptr, kSkewRow, &in_long);
@@ -408,7 +392,7 @@ void DeviceMatrix::describe_when(int rows, int cols, long nnz_l, std::shared_fut
             const int *rp = host_rp();
             for (int i = 0; i < rows; ++i) longest_row = std::max(longest_row, rp[i + 1] - rp[i]);
         }
-        build_tiled_copy(rows, cols, nnz, host_rp, ci, std::move(keep), min_dense_override, join_values, pt);
+        build_tiled_copy(rows, cols, nnz, long_row_share, host_rp, ci, std::move(keep), min_dense_override, join_values, pt);
         join_values();
     } catch (...) {
         if (blocks_job.valid()) blocks_job.wait();
@@ -432,289 +416,151 @@ void DeviceMatrix::describe_when(int rows, int cols, long nnz_l, std::shared_fut
     view.nblk = static_cast<int>(b.size());
 }
 
-// The tiled copy of describe_when(): decision, device build (or the host builder's background job), values filled in.
-void DeviceMatrix::build_tiled_copy(int rows, int cols, int nnz, const std::function<const int *()> &host_rp, const int *ci, std::shared_ptr<void> keep,
-                                    double min_dense_override, const std::function<void()> &join_values, PhaseTimer &pt) {
-    // column-tiled copy: only for matrices with at least one 8192-row super-block per CU
-    // and with enough column locality (HPRLP_NO_TILED=1 disables; thresholds overridable for tests)
-    const char *no = env_get("HPRLP_NO_TILED");
+static FormBuilt built_figures(const DeviceTiled &t, bool ok) {
+    FormBuilt b = {ok ? 1L : 0L, t.view.n_pieces, static_cast<long>(t.dense_entries), static_cast<long>(t.n_rem), t.rem_top_share};
+    return b;
+}
+
+// The tiled copy of describe_when(): measure, ask the rules (form_select.h), build on the device (or start the host builder's
+// background job), ask again, keep the copy and fill in its values -- or drop it.
+void DeviceMatrix::build_tiled_copy(int rows, int cols, int nnz, double long_row_share, const std::function<const int *()> &host_rp, const int *ci,
+                                    std::shared_ptr<void> keep, double min_dense_override, const std::function<void()> &join_values, PhaseTimer &pt) {
+    const FormHooks hk = read_form_hooks();
+    if (hk.no_tiled) return;  // (outcome and facts stay as they are)
     // (a stream of its own for the build was measured: the stall beside the value upload is the runtime's lock, not a stream wait)
     const hipStream_t bs = nullptr;
-    if (!(no && no[0] == '1')) {
-        const char *mr = env_get("HPRLP_TILED_MIN_ROWS");
-        const char *md = env_get("HPRLP_TILED_MIN_DENSE");
-        // measured on shard-shaped matrices of the banded benchmark: 305 super-blocks 0.31 ms tiled vs
-        // 0.38 ms stream, 153 super-blocks 0.21 ms both -> one super-block per CU is the break-even
-        // (round 2: matrices with fewer super-blocks than CUs run the split form -- several workgroups per super-block)
-        const int rb = sb_rows, gb = far_group;  // (heights, not bit counts)
-        const bool short_form = rb < kTileRows;
-        // (lowered height: chosen by Solver::choose_sb_rows so that there is a super-block per workgroup slot)
-        // (a copy asked for WITHOUT a dense-tile requirement -- the all-remainder form, Solver::pb_fallback_wanted -- stages no tile:
-        // the row count that makes staging pay does not apply to it)
-        int min_rows = mr ? std::atoi(mr) : min_dense_override >= 0.0 ? 1 : (short_form ? 256 * rb : 32 * kTileRows);
-        const double min_dense = min_dense_override >= 0.0 ? min_dense_override : (md ? std::atof(md) : 0.5);
-        declined_sparse = false;
-        declined_thin = declined_popular = false;
-        declined_few_rows = false;
-        // Two more conditions on the shape (measured late in round 2, tools/longrow_ab.py):
-        //  * the gathered vector must be big enough for staging it to pay: a 300k x 100k matrix passes the dense-tile test but
-        //    its 0.8 MB vector lives in every L2 anyway -- stream kernel 11.5 us, tiled 30.7 us per launch.  Tiled from 2^20
-        //    columns on (8 MB: beyond an XCD's 4 MiB L2).  An explicit HPRLP_TILED_MIN_ROWS (tests) lifts the default.
-        //  * no long rows: a row's entries beyond four per tile go to the remainder list, where ONE lane adds a row's
-        //    consecutive products (two dependent LDS reads each): five rows of 3000 entries took that launch from 31 to 203
-        //    us.  Such matrices keep the stream kernel, which spreads a long row over a wave or several.
-        const char *mc = env_get("HPRLP_TILED_MIN_COLS");
-        // (2^19 columns = 4 MiB = one L2.  Until round 5 the full-height form waited for 800 k columns: a 600k x 600k band of 40 000
-        // columns, 40 per row, kept the stream kernel at 0.25 of 8 TB/s where the piece form runs 0.33 and the lowered fused form 0.36)
-        // (7 * 2^16 since the threshold sweep of round 5: 2 % band, 20 per row: 400 k columns stream 0.070 / lowered tiled 0.078 ms,
-        // 500 k columns 0.098 / 0.082 -- the vector shares its L2 with the matrix stream)
-        const int min_cols = mc ? std::atoi(mc) : (mr ? 0 : kTiledMinCols);
-        const int longest = longest_row;  // (describe_when)
-        // (an all-remainder copy -- min_dense_override >= 0 -- takes rows of any length: its steps add a row's products by a segmented
-        // reduction over the lanes, Solver::pb_fallback_wanted)
-        declined_shape = cols < min_cols || (longest > kTileMaxRow && min_dense_override < 0.0);
-        declined_long_rows = false;
-        // Round 4, late.  A matrix of fewer full-height super-blocks than workgroup slots whose height could not be lowered (its
-        // rows' column windows are too wide for short super-blocks) would run the piece form: partial sums through memory and a
-        // finish launch.  When the stream kernel's gathers stay inside one L2 anyway -- every XCD runs a contiguous eighth of the
-        // rows, whose columns (median row span + the eighth's own drift along the diagonal, Solver::choose_sb_rows) cover less
-        // than kStreamL2Bytes of the vector -- the stream kernel is the faster form: multicommodity-flow LP, 535 k x 2.03 M,
-        // 40 diagonal blocks: y-half 64.9 us (512 pieces of 66 super-blocks) against 22.4 us, 10.1 k -> 18.0 k iterations/s.
-        // Config 5's quarter shard (window 4.0 MB: pieces 0.31 ms, stream 0.38) keeps the pieces.
-        declined_l2 = false;
-        // bytes of the vector tiles a FULL-height super-block stages against the bytes of its entries (the row span back out of
-        // Solver::choose_sb_rows' estimate): above 1 the piece form moves more tile bytes than matrix bytes (staircase LP of 12 stages,
-        // 8 entries per row, span 2.4e5 columns: pieces 0.086 ms per half-step, stream kernel 0.068)
-        const double span_est = xcd_gather_bytes > 0.0 ? std::max(0.0, xcd_gather_bytes / 8.0 - cols / 8.0) : 0.0;
-        const double tile_share_full = rows > 0 && nnz > 0 ? (span_est + static_cast<double>(kTileRows) * cols / rows) * 8.0 / (static_cast<double>(nnz) / rows * kTileRows * 11.0) : 0.0;
-        // Second held-out set, round 5: FEW rows (under a super-block per CU) whose full-height tiles would still be dense -- the vector
-        // bytes a super-block stages stay under kFewRowsTileShare times its entries' bytes -- go through the tiled build after all and run the
-        // piece form: 50k x 2M with 400 random entries per row (the transpose of a 10-per-row matrix): 7 super-blocks in 512 pieces
-        // 0.101 ms per half-step, all-remainder form 0.162, stream kernel 0.291.  (100k x 5M with 150 per row: share 3.2 -- all-remainder
-        // form, Solver::pb_fallback_wanted.)
-        if (!mr && min_dense_override < 0.0 && rb == kTileRows && rows < min_rows && rows >= 4 * kTileRows && nnz >= 4000000 && xcd_gather_bytes > 0.0 &&
-            tile_share_full <= kFewRowsTileShare)
-            min_rows = rows;
-        // ... and thin rows: a piece's cost goes with the tiles it stages, the stream kernel's with the entries (1M x 1M band of 16 000
-        // columns, 6 per row: pieces 0.060 ms per half-step, stream 0.041; 12 per row + dense borders: 0.102 / 0.088; 20 per row: 0.128 / 0.177)
-        const double entries_per_row = rows > 0 ? static_cast<double>(nnz) / rows : 0.0;
-        line_density = (rows >= 8192 && nnz > 1000000) ? launch_line_density(rowptr.p, col.p, rows, nullptr) : 1.0;
-        if (pt.on) std::cerr << "[timing]   gathered 64-byte lines per entry (sampled 64-row windows): " << line_density << std::endl;
-        // Rows whose neighbours gather from the same 64-byte lines (stencil rows, incidence matrices, bands a few hundred columns
-        // wide) are what the stream kernel is good at: its gathers coalesce and hit the L1 / L2, and there is nothing for staged
-        // tiles to save.  Measured (tools/ab_forms.sh, 1M x 1M, 20 per row): band 500 (0.1 lines per entry) stream 0.071 ms per
-        // half-step, band 2000 (0.2) 0.107 -- the tiled build declines such bands (more than four entries of a row per tile) and the
-        // all-remainder form that used to follow took 0.138 / 0.149; grid PDE-control LP (0.11 / 0.20): stream 0.0245 against
-        // 0.0361 ms in the lowered fused form.  From 0.37 lines per entry on (band 4000) the fused tiled form wins (0.089 / 0.124).
-        // (these two hold for a matrix whose longest rows would be kept aside as well: evaluated whatever the longest row is -- with the
-        // layered tile lists of round 5 the copy of a block-angular LP WITHOUT its 400 linking rows passes the dense-tile test, and ran
-        // 0.48 / 0.42 of 8 TB/s where the stream kernel, whose rows share their lines, runs 0.58 / 0.47)
-        declined_coalesced = false;
-        const bool long_only = declined_shape && cols >= min_cols;  // declined so far for its longest row alone
-        // (rows of more than kCoalescedMaxRowEntries entries excepted: the stream kernel packs 512 entries per wave, so 60-entry rows leave
-        // it 8 busy lanes in its row-sum phase -- 600k x 600k, 60 per row in 6 000 columns, 0.2 lines per entry: stream 0.24 / 0.35 of
-        // 8 TB/s, lowered tiled form with three layers per tile 0.42 / 0.50)
-        // (... unless the rows share their lines almost completely: 1M x 1M, 40 / 48 per row inside 1 500 columns, 0.08 lines per entry:
-        // stream 0.243 / 0.298 ms per iteration, lowered tiled form 0.274 / 0.359 -- threshold sweep, round 5)
-        if ((!declined_shape || long_only) && line_density <= kStreamLineDensity && (entries_per_row <= kCoalescedMaxRowEntries || line_density <= kStreamLineDensityLong) &&
-            !mr && min_dense_override < 0.0 &&
-            env_get("HPRLP_TILED_ANYWAY") == nullptr)
-            declined_shape = declined_coalesced = true;
-        {
-            const bool pieces_expected = rb == kTileRows && (rows + rb - 1) / rb < workgroup_slots();
-            const bool in_one_l2 = xcd_gather_bytes > 0.0 && xcd_gather_bytes <= kStreamL2Bytes;
-            // pieces: round 4's rule with round 5's conditions.  A FUSED tiled form only where the copy would need its longest rows kept
-            // aside (two more launches per half-step for them) and the stream kernel's rows share their lines inside one L2:
-            // block-angular LP without its 400 linking rows (0.39 lines per entry, 2 MB per XCD): fused 1984-row form + side 0.48 / 0.42
-            // of 8 TB/s, stream kernel 0.58 / 0.47.  (A band of 4 000 columns has the same line density and window and no long rows:
-            // fused form 0.51, stream kernel 0.36.)
-            const bool stream_wins = pieces_expected ? (line_density <= kStreamL2LineDensity || tile_share_full > 1.0 || entries_per_row < kPiecesMinRowEntries)
-                                                     : (long_only && line_density <= kStreamL2LineDensityFused);
-            if ((!declined_shape || (long_only && !declined_coalesced)) && in_one_l2 && stream_wins && env_get("HPRLP_PIECES_ANYWAY") == nullptr &&
-                env_get("HPRLP_TILED_ANYWAY") == nullptr && !mr && min_dense_override < 0.0)
-                declined_shape = declined_l2 = true;
-        }
-        const char *ht = env_get("HPRLP_HOST_TILING");
-        const bool host_tiling = ht && ht[0] == '1';
-        // Round 5, from the form-regret corpus (tools/form_regret.py, profiles/r05_form_regret.txt) -- two properties of the ROW
-        // LENGTHS that the tiled forms do not survive, whatever the columns look like:
-        //  * skew: a matrix with a fifth of its entries in rows of more than kSkewRow entries (R-MAT / Kronecker graphs: 40 %).  A
-        //    long row's entries beyond four per tile all go through the remainder steps of ONE super-block; the stream kernel
-        //    gives such a row a wave of its own.  Kronecker 2^20 x 2^20, 7.5e6 entries, y-half: piece form 0.67 ms, lowered fused
-        //    0.54-0.58, all-remainder 0.71, stream kernel 0.076.
-        //  * imbalance: the heaviest block of sb_rows consecutive rows holds more than kMaxBlockLoad times the mean (a few hundred
-        //    coupling rows at the end of a block-diagonal model).  A fused launch ends when its heaviest super-block does:
-        //    block-diagonal 1M x 1.2M with 300 rows of 900 entries behind it, y-half 0.295 ms (1984-row super-blocks) against
-        //    0.066 with the stream kernel.  (The piece form cuts its work evenly and is exempt.)
-        declined_skew = declined_imbalance = false;
-        if (!mr && min_dense_override < 0.0 && env_get("HPRLP_TILED_ANYWAY") == nullptr) {
-            if (long_row_share > kMaxLongRowShare) {   // (also for a matrix whose longest rows would be kept aside, below)
-                declined_shape = declined_skew = true;
-            } else if (!declined_shape && rows > 100000) {
-                const int nsb = (rows + rb - 1) / rb;
-                const bool pieces_expected = rb == kTileRows && nsb <= workgroup_slots();
-                const int heaviest = pieces_expected ? 0 : launch_heaviest_block(rowptr.p, rows, rb, nullptr);
-                if (static_cast<double>(heaviest) > kMaxBlockLoad * static_cast<double>(nnz) / nsb) declined_shape = declined_imbalance = true;
+    const int rb = sb_rows, gb = far_group;  // (heights, not bit counts)
+    passes = min_dense_override >= 0.0 ? 2 : 1;
+    FormFacts &f = passes == 2 ? facts_pb : facts;
+    f = blank_form_facts();
+    f.rows = rows;
+    f.cols = cols;
+    f.nnz = nnz;
+    f.longest_row = longest_row;  // (describe_when)
+    f.long_row_share = long_row_share;
+    f.xcd_gather_bytes = xcd_gather_bytes;
+    f.sb_rows = rb;
+    f.slots = workgroup_slots();
+    f.min_dense_override = min_dense_override;
+    if (rows >= 8192 && nnz > 1000000) f.line_density = launch_line_density(rowptr.p, col.p, rows, nullptr);
+    if (pt.on) std::cerr << "[timing]   gathered 64-byte lines per entry (sampled 64-row windows): " << f.line_density << std::endl;
+    PreBuild p;
+    for (;;) {  // a pass that an earlier rule makes unnecessary does not run
+        p = before_build(f, hk);
+        if (p.need == FormNeed::HeaviestBlock) f.heaviest_block = launch_heaviest_block(rowptr.p, rows, rb, nullptr);
+        else if (p.need == FormNeed::TilingShare) f.tiling_share = device_tiling_dense_fraction(rows, cols, nnz, rowptr.p, col.p, nullptr, nullptr, bs);
+        else break;
+    }
+    if (pt.on && (p.skew || p.imbalance))
+        std::cerr << "[timing]   tiled forms declined for the row lengths: " << (p.skew ? "skew" : "imbalance") << " (share of the entries in rows over "
+                  << kSkewRow << ": " << long_row_share << ")" << std::endl;
+    if (pt.on && f.tiling_share >= 0.0)
+        std::cerr << "[timing]   thin rows (" << p.entries_per_row << " per row), tiling test: " << f.tiling_share << " of the entries in dense tiles" << std::endl;
+    if (p.thin_early) {
+        route_of(f, p, &outcome);
+        pt.tick("  tiling test (thin rows: the stream kernel without a build)");
+        return;
+    }
+    auto adopt = [&]() {
+        view.tiled = tiled.view;
+        join_values();
+        launch_tiled_refresh(tiled, val.p, bs);
+        HIP_CHECK(hipDeviceSynchronize());
+    };
+    if (p.side_open) {
+        const int *rp = host_rp();
+        std::vector<int> long_rows;
+        long long_nnz = 0;
+        for (int i = 0; i < rows; ++i)
+            if (rp[i + 1] - rp[i] > kTileMaxRow) {
+                long_rows.push_back(i);
+                long_nnz += rp[i + 1] - rp[i];
             }
-            if (pt.on && (declined_skew || declined_imbalance))
-                std::cerr << "[timing]   tiled forms declined for the row lengths: " << (declined_skew ? "skew" : "imbalance") << " (share of the entries in rows over "
-                          << kSkewRow << ": " << long_row_share << ")" << std::endl;
-        }
-        // Thin rows (rule below, after the build: a PIECE-form copy of a matrix with under kPiecesThinRows entries per row is dropped
-        // for the stream kernel) decided BEFORE the build where the cheap tiling test (a sort of the entries' tile keys, under a
-        // millisecond; the locality ordering's acceptance test) already says the copy would pass: the build and its drop were
-        // 20-65 ms per matrix of a 0.5 s solve (two-stage LP: 0.126 s of 0.57).
-        {
-            const bool pieces_expected = rb == kTileRows && (rows + rb - 1) / rb <= workgroup_slots();
-            if ((!declined_shape || long_only) && pieces_expected && rows >= min_rows && nnz > 0 && entries_per_row < kPiecesThinRows && !host_tiling && !mr && !md &&
-                min_dense_override < 0.0 && env_get("HPRLP_PIECES_ANYWAY") == nullptr && env_get("HPRLP_TILED_ANYWAY") == nullptr &&
-                env_get("HPRLP_TILING_CHECK") == nullptr) {
-                const double share = device_tiling_dense_fraction(rows, cols, nnz, rowptr.p, col.p, nullptr, nullptr, bs);
-                if (pt.on) std::cerr << "[timing]   thin rows (" << entries_per_row << " per row), tiling test: " << share << " of the entries in dense tiles" << std::endl;
-                if (share >= kPiecesMinDense) {
-                    declined_thin = true;
-                    pt.tick("  tiling test (thin rows: the stream kernel without a build)");
-                    return;
-                }
+        f.n_long_rows = static_cast<long>(long_rows.size());
+        f.long_rows_nnz = long_nnz;
+        if (long_rows_aside(f)) {
+            std::vector<int> rp_c(static_cast<size_t>(rows) + 1, 0);
+            for (int i = 0; i < rows; ++i) {
+                const int len = rp[i + 1] - rp[i];
+                rp_c[i + 1] = rp_c[i] + (len > kTileMaxRow ? 0 : len);
             }
-        }
-        // A FEW long rows (dense LP columns / rows) do not have to cost the matrix the tiled kernel: they are left out of the
-        // tiled copy and summed by the stream kernel's vector / split-row mode into a base vector that every tiled launch
-        // adds (tiled.h: TiledDev::side_*).  At most 0.1 % of the rows (and 64) and a fifth of the nonzeros.
-        const char *nside = env_get("HPRLP_NO_LONG_SIDE");
-        if (cols >= min_cols && longest > kTileMaxRow && rows >= min_rows && nnz > 0 && !host_tiling && !(nside && nside[0] == '1') && !declined_skew &&
-            !declined_coalesced && !declined_l2) {
-            const int *rp = host_rp();
-            std::vector<int> long_rows;
-            long long_nnz = 0;
-            for (int i = 0; i < rows; ++i)
-                if (rp[i + 1] - rp[i] > kTileMaxRow) {
-                    long_rows.push_back(i);
-                    long_nnz += rp[i + 1] - rp[i];
-                }
-            if (static_cast<long>(long_rows.size()) <= std::max<long>(64, rows / 1000) && long_nnz * 5 <= nnz) {
-                std::vector<int> rp_c(static_cast<size_t>(rows) + 1, 0);
-                for (int i = 0; i < rows; ++i) {
-                    const int len = rp[i + 1] - rp[i];
-                    rp_c[i + 1] = rp_c[i] + (len > kTileMaxRow ? 0 : len);
-                }
-                const long nnz_c = rp_c[rows];
-                DBuf<int> d_rp_c(rp_c.size()), col_c(static_cast<size_t>(std::max<long>(nnz_c, 1))), map_c(static_cast<size_t>(std::max<long>(nnz_c, 1)));
-                d_rp_c.upload(rp_c.data(), rp_c.size());
-                compact_without_rows(nnz, rows, rowptr.p, d_rp_c.p, col.p, col_c.p, map_c.p, bs);
-                const bool ok = tiled.build_on_device(rows, cols, nnz_c, d_rp_c.p, col_c.p, min_rows, min_dense, bs, rb, tile_cols, rem_cap);
-                if (pt.on)
-                    std::cerr << "[timing]   tiled copy without " << long_rows.size() << " long rows (" << long_nnz << " entries, longest " << longest
-                              << "): " << (ok ? "" : "declined; ") << tiled.view.nsb << " super-blocks, " << tiled.n_steps << " steps" << std::endl;
-                bool ok_kept = ok;
-                if (ok && tiled.view.n_pieces > 0 && !mr && !md && env_get("HPRLP_PIECES_ANYWAY") == nullptr) {   // (as below: kPiecesMinDense)
-                    const double staged = static_cast<double>(tiled.dense_entries) / std::max(1.0, static_cast<double>(tiled.dense_entries) + static_cast<double>(tiled.n_rem));
-                    if (staged < kPiecesMinDense) {
-                        tiled = DeviceTiled();
-                        ok_kept = false;
-                    } else if (entries_per_row < kPiecesThinRows) {   // (as below: thin rows)
-                        tiled = DeviceTiled();
-                        ok_kept = false;
-                        declined_thin = true;
-                    }
-                }
-                if (ok_kept) {
-                    tiled.build_far(cols, bs, gb);
-                    tiled.compose_perms(map_c.p, bs);
-                    tiled.set_side(rows, rp, long_rows);
-                    view.tiled = tiled.view;
-                    join_values();
-                    launch_tiled_refresh(tiled, val.p, bs);
-                    HIP_CHECK(hipDeviceSynchronize());
-                    declined_shape = false;
-                }
-                pt.tick("  build tiled copy (device, long rows aside)");
-                if (ok_kept) return;
+            const long nnz_c = rp_c[rows];
+            DBuf<int> d_rp_c(rp_c.size()), col_c(static_cast<size_t>(std::max<long>(nnz_c, 1))), map_c(static_cast<size_t>(std::max<long>(nnz_c, 1)));
+            d_rp_c.upload(rp_c.data(), rp_c.size());
+            compact_without_rows(nnz, rows, rowptr.p, d_rp_c.p, col.p, col_c.p, map_c.p, bs);
+            const bool ok = tiled.build_on_device(rows, cols, nnz_c, d_rp_c.p, col_c.p, p.min_rows, p.min_dense, bs, rb, tile_cols, rem_cap);
+            f.side = built_figures(tiled, ok);
+            if (pt.on)
+                std::cerr << "[timing]   tiled copy without " << long_rows.size() << " long rows (" << long_nnz << " entries, longest " << longest_row
+                          << "): " << (ok ? "" : "declined; ") << tiled.view.nsb << " super-blocks, " << tiled.n_steps << " steps" << std::endl;
+            const bool kept = after_build(f, hk, p, f.side, true, false) == NoTiled::None;
+            if (ok && !kept) tiled = DeviceTiled();
+            if (kept) {
+                tiled.build_far(cols, bs, gb);
+                tiled.compose_perms(map_c.p, bs);
+                tiled.set_side(rows, rp, long_rows);
+                adopt();
+                outcome = FormOutcome();
             }
+            pt.tick("  build tiled copy (device, long rows aside)");
+            if (kept) return;
         }
-        if (declined_shape) {
-            // declined for its row lengths alone (longest row, or too many entries in long rows) -- not because its rows share lines or
-            // gather from one L2's window: a candidate for the all-remainder form where the COLUMNS are not popular (pb_fallback_wanted)
-            declined_long_rows = cols >= min_cols && longest > kTileMaxRow && !declined_coalesced && !declined_l2 && !declined_imbalance && rows > 0 && nnz > 0;
-            if (pt.on) std::cerr << "[timing]   tiled copy not attempted: " << cols << " columns, longest row " << longest << std::endl;
-        } else if (rows < min_rows) {
-            declined_few_rows = rows > 0 && nnz > 0;  // (Solver::pb_fallback_wanted)
-            if (pt.on) std::cerr << "[timing]   tiled copy not attempted: " << rows << " rows (staged tiles from " << min_rows << " on)" << std::endl;
-        } else if (rows >= min_rows && rows > 0 && nnz > 0 && !host_tiling) {
+    }
+    switch (route_of(f, p, &outcome)) {
+        case FormRoute::NotAttempted:
+            if (pt.on) std::cerr << "[timing]   tiled copy not attempted: " << cols << " columns, longest row " << longest_row << std::endl;
+            break;
+        case FormRoute::FewRows:
+            if (pt.on) std::cerr << "[timing]   tiled copy not attempted: " << rows << " rows (staged tiles from " << p.min_rows << " on)" << std::endl;
+            break;
+        case FormRoute::DeviceBuild: {
             // built on the device from the device CSR arrays (tiled_build.hip); HPRLP_TILING_CHECK=1 also runs the
             // host builder and compares every array
-            const bool ok = tiled.build_on_device(rows, cols, nnz, rowptr.p, col.p, min_rows, min_dense, bs, rb, tile_cols, rem_cap);
-            declined_sparse = !ok;  // rows >= min_rows here: what was missing is dense tiles
+            const bool ok = tiled.build_on_device(rows, cols, nnz, rowptr.p, col.p, p.min_rows, p.min_dense, bs, rb, tile_cols, rem_cap);
+            f.whole = built_figures(tiled, ok);
             if (pt.on)
                 std::cerr << "[timing]   tiled copy (device build): " << (ok ? "" : "declined; ") << tiled.view.nsb << " super-blocks, "
                           << tiled.n_steps << " steps, " << tiled.dense_entries << " entries in tiles + " << tiled.padding
                           << " padding, " << tiled.n_rem << " in the remainder list" << std::endl;
-            const char *chk = env_get("HPRLP_TILING_CHECK");
-            if (chk && chk[0] == '1' && ci) {
+            if (hk.tiling_check == 1 && ci) {
                 TiledHost th;
-                const bool hok = build_tiled(rows, cols, host_rp(), ci, &th, min_rows, min_dense, rb, tile_cols, rem_cap);
+                const bool hok = build_tiled(rows, cols, host_rp(), ci, &th, p.min_rows, p.min_dense, rb, tile_cols, rem_cap);
                 if (hok != ok) throw std::runtime_error("tiling check: host and device builders disagree on acceptance");
                 if (ok) tiled.compare_with(th);
             }
-            // Round 5 (form-regret corpus): the PIECE form of a copy that stages only about half of its entries is the worst of both
-            // worlds -- every super-block's remainder steps stay with one piece, the partial sums go through memory.  Uniform random
-            // 1.2M x 1.2M, 16 per row (51 % in tiles): 0.55 ms per iteration against 0.27 in the all-remainder form; band + 30 % far
-            // entries (53 %): 0.39 against 0.28.  Such a copy is handed back as "too few entries in dense tiles": the
-            // all-remainder form follows where the matrix is large enough for it (Solver::pb_fallback_wanted), else the stream kernel.
-            declined_thin = false;
-            if (ok && tiled.view.n_pieces > 0 && !mr && !md && min_dense_override < 0.0 && env_get("HPRLP_PIECES_ANYWAY") == nullptr) {
-                const double staged = static_cast<double>(tiled.dense_entries) / std::max(1.0, static_cast<double>(tiled.dense_entries) + static_cast<double>(tiled.n_rem));
-                if (staged < kPiecesMinDense) {
-                    if (pt.on) std::cerr << "[timing]   piece form with " << staged << " of the entries in staged tiles: declined" << std::endl;
-                    tiled = DeviceTiled();
-                    declined_sparse = true;
-                } else if (entries_per_row < kPiecesThinRows) {
-                    // Held-out corpus, round 5: a copy that passes the dense-tile test has its rows' columns close together -- and
-                    // with fewer than ten entries per row the stream kernel then beats the PIECE form whether or not an XCD's window
-                    // fits its L2 (a piece's cost goes with the tiles it stages): node-arc incidence 1M x 4M after the locality
-                    // ordering, 8 / 2 per row: 0.070 / 0.093 ms per half-step in pieces, 0.055 / 0.085 on the stream kernel; 5-, 7-
-                    // and 9-point stencils in random order (after the ordering) 5-13 % per iteration; 3M x 3M band of 300 000 columns,
-                    // 8 per row: 0.357 -> 0.327 ms (12 per row: pieces stay ahead, 0.275 against 0.293).
-                    if (pt.on) std::cerr << "[timing]   piece form with " << entries_per_row << " entries per row: the stream kernel instead" << std::endl;
-                    tiled = DeviceTiled();
-                    declined_thin = true;
-                }
-            }
-            bool kept = ok && tiled.view.valid;
-            if (kept) {
+            NoTiled why = after_build(f, hk, p, f.whole, false, false);
+            if (why == NoTiled::None) {
                 tiled.build_far(cols, bs, gb);  // consumes the remainder lists the check above compares
-                // Second held-out set, round 5: what the tiles could not hold gathers from a FEW popular columns (the first-stage columns of
-                // a two-stage stochastic LP: 20 % of the entries, 160 KB of the vector) and the rest of a row from a window that an XCD's L2
-                // holds anyway: the stream kernel finds ALL of it in its L2, the tiled form sends the popular fifth through the remainder at
-                // 30 bytes per entry.  1M x 1.42M, 8 per row, 2 000 scenario blocks: lowered fused form 0.080 ms per half-step (28 % in
-                // the remainder), stream kernel 0.034.  (A band with 30 % uniformly far entries has the same share in the remainder and NO
-                // such concentration: the tiled form stays ahead, 0.237 against 0.288 ms per iteration.)
-                const bool in_one_l2 = xcd_gather_bytes > 0.0 && xcd_gather_bytes <= kStreamL2Bytes;
-                if (in_one_l2 && !mr && !md && min_dense_override < 0.0 && env_get("HPRLP_TILED_ANYWAY") == nullptr && env_get("HPRLP_PIECES_ANYWAY") == nullptr &&
-                    static_cast<double>(tiled.n_rem) >= kPopularFarMinRem * static_cast<double>(nnz) && tiled.rem_top_share >= kPopularFarShare) {
-                    if (pt.on) std::cerr << "[timing]   " << tiled.rem_top_share << " of the remainder on 2 MB of popular columns, window in one L2: the stream kernel instead" << std::endl;
-                    tiled = DeviceTiled();
-                    declined_popular = true;
-                    kept = false;
-                }
+                f.whole.rem_top_share = tiled.rem_top_share;
+                why = after_build(f, hk, p, f.whole, false, true);
             }
-            if (kept) {
-                view.tiled = tiled.view;
-                join_values();
-                launch_tiled_refresh(tiled, val.p, bs);
-                HIP_CHECK(hipDeviceSynchronize());
+            if (ok && why != NoTiled::None) {
+                if (pt.on && why == NoTiled::Sparse) std::cerr << "[timing]   piece form with " << staged_share(f.whole) << " of the entries in staged tiles: declined" << std::endl;
+                if (pt.on && why == NoTiled::Thin) std::cerr << "[timing]   piece form with " << p.entries_per_row << " entries per row: the stream kernel instead" << std::endl;
+                if (pt.on && why == NoTiled::Popular)
+                    std::cerr << "[timing]   " << tiled.rem_top_share << " of the remainder on 2 MB of popular columns, window in one L2: the stream kernel instead" << std::endl;
+                tiled = DeviceTiled();
             }
+            outcome.why = why;
+            if (why == NoTiled::None) adopt();
             pt.tick("  build tiled copy (device)");
-        } else if (rows >= min_rows && rows > 0 && nnz > 0 && ci) {  // the host builder needs the host column indices
-            planned_grid = std::max(((rows + rb - 1) / rb + 7) / 8 * 8, (rows + kThreads - 1) / kThreads);  // fused grid or the split form's finish grid
-            const int tc = tile_cols, rc = rem_cap;
-            const int *rp = host_rp();
-            tiling = std::async(std::launch::async, [=]() -> std::shared_ptr<TiledHost> {
-                (void)keep;  // keeps the host arrays alive for the duration of the build
-                auto th = std::make_shared<TiledHost>();
-                return build_tiled(rows, cols, rp, ci, th.get(), min_rows, min_dense, rb, tc, rc) ? th : nullptr;
-            });
+            break;
         }
+        case FormRoute::HostBuild:
+            if (ci) {  // the host builder needs the host column indices
+                planned_grid = std::max(((rows + rb - 1) / rb + 7) / 8 * 8, (rows + kThreads - 1) / kThreads);  // fused grid or the split form's finish grid
+                const int tc = tile_cols, rc = rem_cap, min_rows = p.min_rows;
+                const double min_dense = p.min_dense;
+                const int *rp = host_rp();
+                tiling = std::async(std::launch::async, [=]() -> std::shared_ptr<TiledHost> {
+                    (void)keep;  // keeps the host arrays alive for the duration of the build
+                    auto th = std::make_shared<TiledHost>();
+                    return build_tiled(rows, cols, rp, ci, th.get(), min_rows, min_dense, rb, tc, rc) ? th : nullptr;
+                });
+            }
+            break;
+        default:
+            break;
     }
 }
 
@@ -902,8 +748,8 @@ void Solver::setup(const LP_info_cpu *model, const HPRLP_parameters *param) {
                     return ht->trp.data();
                 }).share();
             // the column indices of A^T are only needed on the host by the host tiled builder (or its check)
-            const char *htile = env_get("HPRLP_HOST_TILING"), *chk = env_get("HPRLP_TILING_CHECK");
-            const bool need_tci = (htile && htile[0] == '1') || (chk && chk[0] == '1');
+            const FormHooks hk = read_form_hooks();
+            const bool need_tci = hk.host_tiling || hk.tiling_check == 1;
             if (need_tci) {
                 tci.resize(static_cast<size_t>(nnz));
                 AT.col.download(tci.data(), tci.size());
@@ -968,22 +814,6 @@ void Solver::setup(const LP_info_cpu *model, const HPRLP_parameters *param) {
     }
 }
 
-// Gather vector too long for the L2s (>= 4 M entries = 32 MB) and the tiled build declined for lack of dense tiles: the
-// stream kernel would pay a fabric line per gathered element (HPRLP_NO_PB_FALLBACK=1 keeps it anyway; one GPU only).
-// gathered vector from which the all-remainder tiled form beats the stream kernel on a pattern without locality (measured,
-// tools/unstructured_ab.py, uniformly random 10 per row: 1M columns 0.154 vs 0.125 ms per half-step, 2M 0.218 vs 0.318, 3M 0.316
-// vs 0.508, 4.2M 0.46 vs 0.75, 6M 0.59 vs 1.13)
-constexpr double kMaxTileShare = 0.6;  // choose_sb_rows: most tile bytes per entry byte a lowered super-block may stage (one round)
-constexpr double kMaxTileShareRounds = 0.9;  // ... when the height only trims a partial last round of a larger matrix
-constexpr long kPbMinCols = 800000;  // (round 4, tools/unstructured_ab.py with k_pb_fused, 10 per row: 0.5M columns 0.065 vs 0.041 ms stream, 1.0M 0.080 vs 0.123, 1.5M 0.119 vs 0.214: from where the vector outgrows a 4 MiB L2)
-constexpr int kPbFewRowsMin = 32768;   // pb_fallback_wanted: fewest rows of a matrix that takes the all-remainder form without having been through the tiled build
-constexpr long kPopularLines = 32768;      // pb_fallback_wanted: 2 MB of the gathered vector ...
-constexpr double kPopularShareMax = 0.3;   // ... that may not take more than this share of a few-row matrix' gathers
-constexpr double kPbHeaviestBlockShare = 48.0;  // pb_fallback_wanted: a matrix with long rows takes the all-remainder form only if its heaviest 4096-row block holds at most 1 / 48 of the entries
-constexpr int kPbFewRowsLow = 80000;    // ... half that height below this many rows
-constexpr int kPbFewRowsHeight = 512;  // choose_pb_rows: super-block height for such a matrix (below 32 full-height super-blocks' worth of rows)
-constexpr double kNarrowTilesFrom = 1.2;  // choose_sb_rows: entries of a row per 2048-column tile from which the copy gets 1024-column tiles
-
 // Share of a matrix' entries whose gathers go to the `lines` most popular 64-byte lines of the gathered vector (columns 8 l .. 8 l + 7;
 // `other` is the transpose: its row lengths are the column counts).  What the stream kernel's gathers find in an L2 however far apart
 // the rows reach.
@@ -1001,180 +831,93 @@ static double popular_lines_share(const int *d_rowptr, int cols, long nnz, long 
     return static_cast<double>(top) / static_cast<double>(nnz);
 }
 
-bool Solver::pb_fallback_wanted(const DeviceMatrix &M, const int *other_rowptr, int other_rows) const {
-    const char *no = env_get("HPRLP_NO_PB_FALLBACK");
-    if (no && no[0] == '1') return false;
-    const char *nt = env_get("HPRLP_NO_TILED");
-    if (nt && nt[0] == '1') return false;
-    const long min_cols = env_get("HPRLP_PB_MIN_COLS") ? std::atol(env_get("HPRLP_PB_MIN_COLS")) : kPbMinCols;
-    const long min_nnz = env_get("HPRLP_PB_MIN_NNZ") ? std::atol(env_get("HPRLP_PB_MIN_NNZ")) : 4000000L;  // (tests lower it)
-    // a pattern whose rows stay near a diagonal keeps the stream kernel: each XCD's eighth of the rows gathers from a window of the
-    // vector that its L2 holds (Solver::choose_sb_rows: xcd_gather_bytes; 0 = not estimated).  1M x 1M, band 2000, 20 per row (the
-    // tiled build declines it: too many entries of a row per tile): stream 0.107 ms per half-step, all-remainder form 0.149.
-    const bool in_l2 = M.xcd_gather_bytes > 0.0 && M.xcd_gather_bytes <= kStreamL2Bytes && env_get("HPRLP_PB_MIN_COLS") == nullptr;
-    // Round 5, held-out corpus (tools/form_regret.py --corpus held_out): a matrix with FEWER rows than the staged forms ask for
-    // (a super-block per CU) never reached the tiled build, so it never got here either -- and kept the stream kernel at 0.11 of
-    // 8 TB/s where its rows gather at random from millions of columns: 200k x 5M with 75 per row (the transpose of a 3-per-row
-    // matrix), x-half 0.262 ms against 0.125 here (pre-pass 0.073 + k_pb_fused 0.049, super-blocks of 512 rows); 100k x 5M with
-    // 150 per row: 0.262 against 0.140.  Taken where the rows do NOT share their lines (launch_line_density).
-    // ... and where a ROW's own column window is beyond an L2 (xcd_gather_bytes less the drift of the eighth along the diagonal =
-    // the median row span): 150k x 3M with 60 per row inside a window of 150 000 columns has every entry on a line of its own and
-    // still gathers out of 1.2 MB -- stream kernel 0.063 ms, all-remainder form 0.081.
-    const double row_window_bytes = M.xcd_gather_bytes > 0.0 ? M.xcd_gather_bytes - static_cast<double>(M.view.cols) : 0.0;
-    bool few_rows = M.declined_few_rows && M.view.rows >= kPbFewRowsMin && M.line_density >= kStreamL2LineDensity &&
-                    (M.xcd_gather_bytes <= 0.0 || row_window_bytes > kStreamL2Bytes);
-    const bool size_ok = !comm && !M.view.tiled.valid && !in_l2 && M.view.cols >= min_cols && M.view.nnz >= min_nnz;
-    // Validation set, end of round 5: a matrix kept off the tiled forms for its LONG rows (hubs of a b-matching LP: rows of up to 77 000
-    // entries, a quarter of the entries in rows over 1 024) whose columns are NOT popular gathers at random like any unstructured
-    // matrix -- stream kernel 0.12 of 8 TB/s.  k_pb_fused adds rows of any length; what it cannot take is a super-block far heavier
-    // than the chip's share (the launch ends with it).  (A Kronecker graph has popular columns: it keeps the stream kernel, rule 1.)
-    bool long_rows = false;
-    if (M.declined_long_rows && size_ok && !M.declined_sparse && !few_rows && M.line_density >= kStreamL2LineDensity && env_get("HPRLP_NO_PB_LONG_ROWS") == nullptr) {
-        const double share = popular_lines_share(other_rowptr, other_rows, M.view.nnz, kPopularLines);
-        const int heaviest = launch_heaviest_block(M.rowptr.p, M.view.rows, kPbRowsMax, stream);
-        if (env_get("HPRLP_TIMING"))
-            std::cerr << "[timing] long rows: share of the entries on the " << kPopularLines << " most popular lines " << share << ", heaviest block of " << kPbRowsMax
-                      << " rows " << heaviest << " entries of " << M.view.nnz << std::endl;
-        long_rows = share <= kPopularShareMax && static_cast<double>(heaviest) * kPbHeaviestBlockShare <= static_cast<double>(M.view.nnz);
+// The all-remainder decision (form_select.h: all_remainder_wanted, rules 7 and 13) on what M's last describe() left behind; the
+// popular-lines download and the heaviest-block pass run only when the rule gets as far as asking for them.
+bool Solver::pb_fallback_wanted(DeviceMatrix &M, const int *other_rowptr, int other_rows) {
+    const FormHooks hk = read_form_hooks();
+    FormFacts &f = M.facts;
+    f.sharded = comm != nullptr;
+    AllRemainder r;
+    for (;;) {
+        r = all_remainder_wanted(f, hk, M.outcome, M.view.tiled.valid);
+        if (r.need == FormNeed::PopularShare) f.popular_share = popular_lines_share(other_rowptr, other_rows, M.view.nnz, kPopularLines);
+        else if (r.need == FormNeed::HeaviestPbBlock) f.heaviest_pb_block = launch_heaviest_block(M.rowptr.p, M.view.rows, kPbRowsMax, stream);
+        else break;
     }
-    if (long_rows) return true;
-    if (few_rows && size_ok && !M.declined_sparse) {
-        // ... and where no small set of popular columns takes a large share of the gathers (they stay in the L2s whatever the rows'
-        // reach): set-covering pattern 200k x 2M, 50 per row, column popularity ~ c^-0.6 -- 44 % of the entries on the 32 768 most
-        // popular lines (2 MB): stream kernel 0.123 ms, all-remainder form 0.144 (uniform columns: 5 %).
-        const double share = popular_lines_share(other_rowptr, other_rows, M.view.nnz, kPopularLines);
-        if (env_get("HPRLP_TIMING")) std::cerr << "[timing] few rows: share of the entries on the " << kPopularLines << " most popular lines " << share << std::endl;
-        if (share > kPopularShareMax) few_rows = false;
+    if (env_get("HPRLP_TIMING")) {
+        if (f.heaviest_pb_block >= 0)
+            std::cerr << "[timing] long rows: share of the entries on the " << kPopularLines << " most popular lines " << f.popular_share << ", heaviest block of " << kPbRowsMax
+                      << " rows " << f.heaviest_pb_block << " entries of " << M.view.nnz << std::endl;
+        else if (f.popular_share >= 0.0)
+            std::cerr << "[timing] few rows: share of the entries on the " << kPopularLines << " most popular lines " << f.popular_share << std::endl;
     }
-    return size_ok && (M.declined_sparse || few_rows);
+    return r.wanted;
 }
 
-// Super-block heights of this LP's tiled copies (tiled.h).  A matrix with fewer than 512 full-height super-blocks cannot give
-// every workgroup slot of the chip a whole super-block: it ran the piece form (three launches, partial sums through memory) or,
-// below 2^20 columns, the stream kernel.  With R = rows / 512 every slot gets exactly one, the epilogue stays fused, a half-step
-// is one launch and there is no tail.  What a lower super-block costs is tile traffic -- a staged tile serves R rows -- so the
-// column window of a super-block must stay narrow against its entries: estimated from the column span of the middle three quarters of the
-// entries of 2048 sampled rows (the far entries of a band matrix do not count: they go through the remainder lists).  A
-// source group of one matrix' remainder lists is a super-block of the other (hand-off, kernels.h FarPush): far_group of A is
-// sb_rows of A^T and vice versa.  Same-box A/B (profiles/r03_ab_rows*.txt): 1M x 1M, band 1e4: 3658 it/s stream kernel, 3393
-// pieces, 5287 with 2048-row super-blocks; the 1.25M x 10M shard of config 5 (window of 2e5 columns): a loss, declined here.
-// The height that fills exactly k rounds of the chip's workgroup slots, k = the rounds the FULL height needs (k = 1: one
-// super-block per slot); the full height where its rounds are nearly full already.
-static int whole_rounds_height(int rows, int slots) {
-    const int nsb_full = (rows + kTileRows - 1) / kTileRows;
-    const int k = std::max(1, (nsb_full + slots - 1) / slots);
-    if (k > 1 && static_cast<double>(nsb_full) / (static_cast<double>(k) * slots) >= 0.8) return kTileRows;  // rounds nearly full already
-    const int per = (rows + k * slots - 1) / (k * slots);
-    return std::min(kTileRows, (per + 63) / 64 * 64);
-}
-
-// Heights for a matrix that runs the tiled form WITHOUT staged tiles (pb_fallback_wanted: every entry through the
-// propagation-blocking remainder).  No tile is staged, so a lower super-block costs nothing in tile traffic: take the height
-// that gives every workgroup slot whole super-blocks -- the half-step is then ONE fused launch whose epilogue hands the
-// products over to the other half (round 3 ran such matrices at full height: 245 super-blocks of a 2M x 2M matrix = the piece
-// form, three launches per half-step, partial sums through memory, no hand-off).  HPRLP_TILE_ROWS still overrides.
+// Heights for a matrix that runs the all-remainder form (form_select.h: pb_height).  Writes into BOTH matrices: a source group
+// of one matrix' remainder lists is a super-block of the other.
 void Solver::choose_pb_rows(DeviceMatrix &M, DeviceMatrix &other, int rows, int other_rows) {
     M.rem_cap = kTileRemCap;
     if (comm) return;
-    if (!env_get("HPRLP_TILE_ROWS")) {
+    const FormHooks hk = read_form_hooks();
+    if (!hk.tile_rows.set) {
         const int slots = workgroup_slots();
-        // at most kPbRowsMax rows (the all-remainder kernel's accumulators, kernels.hip: k_pb_fused): larger matrices take more rounds
-        auto height = [&](int nrows) {
-            // (few rows: 512-row super-blocks measured best -- 200k rows: 256 / 384 / 512 / 1024 rows 0.166 / 0.148 / 0.125 / 0.142 ms,
-            // 100k rows: 0.160 / 0.153 / 0.140 / 0.193)
-            // (50k rows: 256 / 512 rows 0.170 / 0.182; 33k rows: 0.155 / 0.190)
-            if (nrows < 32 * kTileRows) return nrows < kPbFewRowsLow ? kPbFewRowsHeight / 2 : kPbFewRowsHeight;
-            int r = std::max(kTileRowsMin, whole_rounds_height(nrows, slots));
-            for (int k = 2; r > kPbRowsMax; ++k) r = std::max(kTileRowsMin, ((nrows + k * slots - 1) / (k * slots) + 63) / 64 * 64);
-            return r;
-        };
-        M.sb_rows = other.far_group = height(rows);
+        M.sb_rows = other.far_group = pb_height(rows, slots);
         // the other matrix has the same graph: if it is not described yet, expect it to take the same form (its source groups are
         // this matrix' hand-off unit, kernels.h FarPush; a wrong guess only costs the hand-off)
-        if (!other.view.tiled.valid) other.sb_rows = M.far_group = height(other_rows);
+        if (!other.view.tiled.valid) other.sb_rows = M.far_group = pb_height(other_rows, slots);
     }
-    // (HPRLP_NO_PB_KERNEL, A/B runs: the all-remainder copy through k_tiled_fused's remainder steps, as in round 3)
-    if (M.sb_rows <= kPbRowsMax && !env_get("HPRLP_NO_PB_KERNEL")) M.rem_cap = kPbRemCap;
+    if (pb_kernel_fits(M.sb_rows, hk)) M.rem_cap = kPbRemCap;
     if (env_get("HPRLP_TIMING"))
         std::cerr << "[timing] no column locality: all-remainder form with super-blocks of " << M.sb_rows << " rows, remainder steps of " << M.rem_cap
                   << " entries" << std::endl;
 }
 
+// Super-block heights, tile widths and the XCD window estimate of this LP's tiled copies (form_select.h: tile_shapes) from the
+// median column span of a row, sampled here where the host arrays are.
 void Solver::choose_sb_rows(const LP_info_cpu *model) {
-    A.sb_rows = A.far_group = AT.sb_rows = AT.far_group = kTileRows;
-    A.tile_cols = AT.tile_cols = kTileCols;
-    A.xcd_gather_bytes = AT.xcd_gather_bytes = 0.0;
-    if (const char *force = env_get("HPRLP_TILE_COLS")) {  // tests / A/B runs: one tile width for both matrices
-        A.tile_cols = AT.tile_cols = std::atoi(force) <= kTileColsNarrow ? kTileColsNarrow : kTileCols;
-    }
-    if (const char *force = env_get("HPRLP_TILE_ROWS")) {  // tests / A/B runs: one height for both matrices
-        const int R = std::max(64, std::min(kTileRows, std::atoi(force) / 64 * 64));
-        A.sb_rows = A.far_group = AT.sb_rows = AT.far_group = R;
-        return;
-    }
-    if (comm) return;  // row shards: all columns of the LP against 1 / P of the rows -- full height
+    const FormHooks hk = read_form_hooks();
     const sparseMatrix *As = model->A;
     const long nnz = As->numElements;
-    if (nnz < 4000000) return;
-    const int slots = workgroup_slots();
-    // median column span of a row without its outermost entries
-    std::vector<long> span;
-    const int samples = 2048;
-    for (int q = 0; q < samples; ++q) {
-        const int i = static_cast<int>(static_cast<long>(q) * m / samples);
-        const int b = As->rowPtr[i], e = As->rowPtr[i + 1], len = e - b;
-        if (len < 4) continue;
-        // an eighth of the entries off either end (at least one: a 16-entry row of config 5's kind carries one far entry),
-        // the span of the rest scaled back to the whole row
-        // (rows need not be sorted by column: the span is |difference|, an unsorted row only makes the estimate coarser,
-        // never negative -- a negative span used to pass the `ratio <= most` test below)
-        const int cut = std::max(1, len / 8);
-        const long ia = std::min<long>(std::max<long>(static_cast<long>(e) - 1 - cut, b), nnz - 1), ib = std::min<long>(static_cast<long>(b) + cut, nnz - 1);
-        const long inner = std::labs(static_cast<long>(As->colIndex[ia]) - As->colIndex[ib]);
-        span.push_back(inner * (len - 1) / std::max(1, len - 1 - 2 * cut));
+    double w_a = 0.0;
+    if (row_spans_wanted(nnz, comm != nullptr, hk)) {
+        // median column span of a row without its outermost entries
+        std::vector<long> span;
+        const int samples = 2048;
+        for (int q = 0; q < samples; ++q) {
+            const int i = static_cast<int>(static_cast<long>(q) * m / samples);
+            const int b = As->rowPtr[i], e = As->rowPtr[i + 1], len = e - b;
+            if (len < 4) continue;
+            // an eighth of the entries off either end (at least one: a 16-entry row of config 5's kind carries one far entry),
+            // the span of the rest scaled back to the whole row
+            // (rows need not be sorted by column: the span is |difference|, an unsorted row only makes the estimate coarser,
+            // never negative -- a negative span used to pass the `ratio <= most` test below)
+            const int cut = std::max(1, len / 8);
+            const long ia = std::min<long>(std::max<long>(static_cast<long>(e) - 1 - cut, b), nnz - 1), ib = std::min<long>(static_cast<long>(b) + cut, nnz - 1);
+            const long inner = std::labs(static_cast<long>(As->colIndex[ia]) - As->colIndex[ib]);
+            span.push_back(inner * (len - 1) / std::max(1, len - 1 - 2 * cut));
+        }
+        if (span.size() >= 16) {
+            std::nth_element(span.begin(), span.begin() + span.size() / 2, span.end());
+            w_a = static_cast<double>(std::max<long>(span[span.size() / 2], 1));
+        }
     }
-    if (span.size() < 16) return;
-    std::nth_element(span.begin(), span.begin() + span.size() / 2, span.end());
-    const double w_a = static_cast<double>(std::max<long>(span[span.size() / 2], 1));
-    const double slope = static_cast<double>(n) / m;  // columns per row along the "diagonal"
-    // what one XCD's eighth of the rows gathers from (stream kernel; DeviceMatrix::build_tiled_copy weighs it against the piece form)
-    A.xcd_gather_bytes = (w_a + m / 8.0 * slope) * 8.0;
-    AT.xcd_gather_bytes = (w_a / slope + n / 8.0 / slope) * 8.0;
-    // Tile width (round 4).  A row segment of more than kTileChunk entries in one tile goes to the remainder lists WHOLE (34
-    // bytes of traffic per entry against 11 in a tile).  With d entries per row spread over a window of w columns a tile of T
-    // columns holds d T / w of them on average; from about 1.2 on, segments of five and more are common (1M x 1M, band 1e4,
-    // d = 19: 1.95 per 2048-column tile, 10.5 % of the entries in such segments; 1024 columns: 1.2 %).  Narrow tiles halve
-    // the staged bytes per step and leave the number of steps about the same (the wide tiles of such a matrix take two).
-    if (!env_get("HPRLP_TILE_COLS")) {
-        const double per_tile_a = static_cast<double>(nnz) / m * kTileCols / w_a;
-        const double per_tile_at = static_cast<double>(nnz) / n * kTileCols / std::max(w_a / slope, 1.0);
-        if (per_tile_a > kNarrowTilesFrom) A.tile_cols = kTileColsNarrow;
-        if (per_tile_at > kNarrowTilesFrom) AT.tile_cols = kTileColsNarrow;
-        if (env_get("HPRLP_TIMING"))
-            std::cerr << "[timing] entries of a row per 2048-column tile: " << per_tile_a << " (A), " << per_tile_at << " (A^T) -> tiles of "
+    const int slots = w_a > 0.0 ? workgroup_slots() : 0;
+    const TileShapes t = tile_shapes(m, n, nnz, slots, w_a, hk);
+    A.sb_rows = AT.far_group = t.sb_rows_a;
+    AT.sb_rows = A.far_group = t.sb_rows_at;
+    A.tile_cols = t.tile_cols_a;
+    AT.tile_cols = t.tile_cols_at;
+    A.xcd_gather_bytes = t.xcd_bytes_a;
+    AT.xcd_gather_bytes = t.xcd_bytes_at;
+    if (env_get("HPRLP_TIMING")) {
+        if (t.estimated && !hk.tile_cols.set)
+            std::cerr << "[timing] entries of a row per 2048-column tile: " << t.per_tile_a << " (A), " << t.per_tile_at << " (A^T) -> tiles of "
                       << A.tile_cols << " / " << AT.tile_cols << " columns" << std::endl;
+        if (t.weighed)
+            std::cerr << "[timing] super-block heights for whole rounds of " << slots << " slots: " << t.ra << " (A), " << t.rat << " (A^T); median row span " << w_a
+                      << " columns, tile bytes / entry bytes " << t.ratio_a << ", " << t.ratio_at << " -> " << (t.lowered ? "lowered" : "full height (8192)") << std::endl;
     }
-    // Heights considered for a matrix of `rows` rows: with k = the rounds the FULL height needs (ceil of its super-blocks over the
-    // slots), the height that fills exactly k rounds.  k = 1: one super-block per slot (mid-size matrices).  k >= 2: the same
-    // number of rounds as now without the partial last one -- only when the full height wastes more than a fifth of its rounds
-    // (6M x 6M, band 6e4: 733 super-blocks = 1.43 rounds run as 2; 1020 of 5888 rows: 1121 -> 1148 it/s; 5M x 5M: 1264 -> 1321;
-    // profiles/r03_ab_rows7.txt).  Nothing to gain below kTileRowsMin (launch-bound matrices: the stream kernel).
-    const int ra = whole_rounds_height(m, slots), rat = whole_rounds_height(n, slots);
-    if ((ra >= kTileRows && rat >= kTileRows) || ra < kTileRowsMin || rat < kTileRowsMin) return;
-    // bytes of the vector tiles a super-block stages against the bytes of its entries; a height that only trims a partial round
-    // may stage a little more (it saves a fifth of the rounds or more)
-    const double ratio_a = (w_a + ra * slope) * 8.0 / (static_cast<double>(nnz) / m * ra * 11.0);
-    const double ratio_at = (w_a / slope + rat / slope) * 8.0 / (static_cast<double>(nnz) / n * rat * 11.0);
-    const bool multi = static_cast<long>(ra) * slots < m || static_cast<long>(rat) * slots < n;  // more than one round
-    const double most = multi ? kMaxTileShareRounds : kMaxTileShare;
-    const bool ok = ratio_a <= most && ratio_at <= most;
-    if (ok) {
-        A.sb_rows = AT.far_group = ra;
-        AT.sb_rows = A.far_group = rat;
-    }
-    if (env_get("HPRLP_TIMING"))
-        std::cerr << "[timing] super-block heights for whole rounds of " << slots << " slots: " << ra << " (A), " << rat << " (A^T); median row span " << w_a
-                  << " columns, tile bytes / entry bytes " << ratio_a << ", " << ratio_at << " -> " << (ok ? "lowered" : "full height (8192)") << std::endl;
 }
 
 // Large matrix whose given order failed the tiling test: look for a locality ordering (reorder.cpp).  On entry A (device
@@ -1184,11 +927,10 @@ bool Solver::try_reorder(const LP_info_cpu *model) {
     if (!allow_reorder) return false;
     const char *no = env_get("HPRLP_NO_REORDER");
     if (no && no[0] == '1') return false;
-    const char *nt = env_get("HPRLP_NO_TILED");
-    if (nt && nt[0] == '1') return false;
-    const char *mr = env_get("HPRLP_TILED_MIN_ROWS");
-    const int min_rows = mr ? std::atoi(mr) : 32 * kTileRows;
-    if (comm || A.view.tiled.valid || A.declined_shape || m < min_rows || n < min_rows) return false;
+    const FormHooks hk = read_form_hooks();
+    if (hk.no_tiled) return false;
+    const int min_rows = hk.tiled_min_rows.set ? static_cast<int>(hk.tiled_min_rows.value) : 32 * kTileRows;
+    if (comm || A.view.tiled.valid || not_attempted_for_shape(A.outcome.why) || m < min_rows || n < min_rows) return false;
     const auto t0 = time_now();
     const sparseMatrix *As = model->A;
     const long nnz = As->numElements;

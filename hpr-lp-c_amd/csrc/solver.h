@@ -16,6 +16,7 @@
 #include "dist.h"
 #include "kernels.h"
 #include "hpr_rules.h"
+#include "form_select.h"
 
 namespace hprlp {
 
@@ -60,21 +61,15 @@ struct DeviceMatrix {
     // the same with the host row pointers delivered later and the values possibly still being uploaded (solver.cpp)
     void describe_when(int rows, int cols, long nnz, std::shared_future<const int *> rp_ready, const int *ci, std::shared_ptr<void> keep,
                        double min_dense_override, std::future<void> *values_ready);
-    void build_tiled_copy(int rows, int cols, int nnz, const std::function<const int *()> &host_rp, const int *ci, std::shared_ptr<void> keep,
-                          double min_dense_override, const std::function<void()> &join_values, struct PhaseTimer &pt);
+    void build_tiled_copy(int rows, int cols, int nnz, double long_row_share, const std::function<const int *()> &host_rp, const int *ci,
+                          std::shared_ptr<void> keep, double min_dense_override, const std::function<void()> &join_values, struct PhaseTimer &pt);
     int longest_row = 0;  // entries of the longest row (set by describe)
-    bool declined_sparse = false;  // the last tiled build was declined for lack of dense tiles (not for size)
-    bool declined_shape = false;   // ... not attempted: too few columns for staging to pay, or rows too long for the remainder list
-    bool declined_l2 = false;      // ... not attempted (a case of declined_shape): piece form against a stream kernel whose gathers stay in one L2
-    bool declined_coalesced = false;  // ... not attempted (a case of declined_shape): neighbouring rows gather from the same lines
-    bool declined_skew = false;       // ... not attempted (a case of declined_shape): too many of the entries in long rows
-    bool declined_imbalance = false;  // ... not attempted (a case of declined_shape): one block of sb_rows rows holds several times the mean
-    bool declined_thin = false;       // a PIECE-form copy was built and dropped: fewer than kPiecesThinRows entries per row (stream kernel instead)
-    bool declined_popular = false;    // a copy was built and dropped: its remainder gathers from a few popular columns and the rest from one L2's window
-    bool declined_long_rows = false;  // ... not attempted for the length of its rows alone (Solver::pb_fallback_wanted)
-    bool declined_few_rows = false;   // ... not attempted for the number of rows alone (fewer than a super-block per CU); Solver::pb_fallback_wanted
-    double long_row_share = 0.0;      // share of the entries in rows of more than kSkewRow entries (describe_when; 0 for small matrices)
-    double line_density = 1.0;     // distinct 64-byte lines of the gathered vector per entry (kernels.hip: launch_line_density)
+    // Why the last describe() left no tiled copy (form_select.h; hprlp_solver_describe prints its note).  Every pass starts it
+    // afresh -- except under HPRLP_NO_TILED=1, which leaves the matrix as it is.
+    FormOutcome outcome;
+    // What the rules were asked about: the last pass with the dense-tile requirement and the all-remainder pass (passes == 2)
+    FormFacts facts = blank_form_facts(), facts_pb = blank_form_facts();
+    int passes = 0;
     double xcd_gather_bytes = 0.0; // estimate by Solver::choose_sb_rows: bytes of the gathered vector an XCD's eighth of the rows reads (0: unknown)
     void finish_tiling(hipStream_t s);  // wait for the job, upload the copy, fill its values from the CSR values
     void refresh_tiled(hipStream_t s);  // re-gather the tiled values from the CSR values (after scaling)
@@ -128,7 +123,7 @@ struct Solver {
     void choose_sb_rows(const LP_info_cpu *model);  // super-block heights of this LP's tiled copies (tiled.h), before the matrices are described
     void choose_pb_rows(DeviceMatrix &M, DeviceMatrix &other, int rows, int other_rows);  // ... of a matrix without column locality (all-remainder form, tiled.h)
     // (other_rowptr: the device row pointers of M's transpose, other_rows + 1 of them -- its view need not be described yet)
-    bool pb_fallback_wanted(const DeviceMatrix &M, const int *other_rowptr, int other_rows) const;  // unstructured large matrix: tiled form without dense-tile requirement
+    bool pb_fallback_wanted(DeviceMatrix &M, const int *other_rowptr, int other_rows);  // unstructured large matrix: tiled form without dense-tile requirement
     // Hand-off of the remainder products between the two kernels of an iteration (kernels.h: FarPush).  far_A_ready: A's
     // remainder buffer holds the products of the current x_hat (written by the x-half's epilogue); far_AT_ready likewise
     // for y.  Every other launch on a tiled matrix refills its buffer for another vector: invalidate_far().

@@ -533,6 +533,75 @@ def _batched_call(fn, model, Cmat, AL, AU, l, u, obj_constants, param):
     return out
 
 
+class CFormBuilt(C.Structure):  # include/hprlp_amd.h: hprlp_form_built
+    _fields_ = [("ok", C.c_long), ("n_pieces", C.c_long), ("dense_entries", C.c_long), ("n_rem", C.c_long), ("rem_top_share", C.c_double)]
+
+
+class CFormFacts(C.Structure):  # hprlp_form_facts
+    _fields_ = [("rows", C.c_long), ("cols", C.c_long), ("nnz", C.c_long), ("longest_row", C.c_long), ("long_row_share", C.c_double),
+                ("line_density", C.c_double), ("xcd_gather_bytes", C.c_double), ("sb_rows", C.c_long), ("slots", C.c_long),
+                ("min_dense_override", C.c_double), ("sharded", C.c_long), ("heaviest_block", C.c_long), ("tiling_share", C.c_double),
+                ("n_long_rows", C.c_long), ("long_rows_nnz", C.c_long), ("side", CFormBuilt), ("whole", CFormBuilt),
+                ("popular_share", C.c_double), ("heaviest_pb_block", C.c_long)]
+
+
+class CFormHookValue(C.Structure):
+    _fields_ = [("set", C.c_int), ("value", C.c_double)]
+
+
+class CFormHooks(C.Structure):  # hprlp_form_hooks
+    _fields_ = [(k, C.c_int) for k in ("no_tiled", "tiled_anyway", "pieces_anyway", "host_tiling", "no_long_side", "no_pb_fallback",
+                                       "no_pb_long_rows", "no_pb_kernel", "tiling_check")] + \
+               [(k, CFormHookValue) for k in ("tiled_min_rows", "tiled_min_dense", "tiled_min_cols", "pb_min_cols", "pb_min_nnz",
+                                              "tile_rows", "tile_cols")]
+
+
+class CFormDecision(C.Structure):  # hprlp_form_decision
+    _fields_ = [("min_rows", C.c_int), ("min_cols", C.c_int), ("min_dense", C.c_double), ("route", C.c_int), ("side_tried", C.c_int),
+                ("kept", C.c_int), ("form", C.c_int), ("why", C.c_int), ("long_rows_alone", C.c_int), ("all_remainder_wanted", C.c_int),
+                ("note", C.c_char * 96)]
+
+
+FORM_NAMES = ("stream", "fused", "pieces", "all-remainder")
+BLANK_FORM_FACTS = dict(rows=0, cols=0, nnz=0, longest_row=0, long_row_share=0.0, line_density=1.0, xcd_gather_bytes=0.0, sb_rows=8192,
+                        slots=512, min_dense_override=-1.0, sharded=0, heaviest_block=-1, tiling_share=-1.0, n_long_rows=-1,
+                        long_rows_nnz=-1, side=dict(ok=-1, n_pieces=0, dense_entries=0, n_rem=0, rem_top_share=0.0),
+                        whole=dict(ok=-1, n_pieces=0, dense_entries=0, n_rem=0, rem_top_share=0.0), popular_share=-1.0,
+                        heaviest_pb_block=-1)
+
+
+def _struct_dict(s):
+    return {k: (_struct_dict(getattr(s, k)) if isinstance(getattr(s, k), C.Structure) else getattr(s, k)) for k, _ in s._fields_}
+
+
+def form_select(facts, hooks=None):
+    """Host only (hprlp_form_select): the staged decisions of the kernel-form selection for a facts record (a dict with the fields
+    of hprlp_form_facts; missing ones as in BLANK_FORM_FACTS) under test hooks {name: True or value}.  Returns a dict with
+    min_rows, min_cols, min_dense, route, side_tried, kept, form (a FORM_NAMES entry), why, long_rows_alone, all_remainder_wanted, note."""
+    f = CFormFacts()
+    for k, v in dict(BLANK_FORM_FACTS, **facts).items():
+        if isinstance(v, dict):
+            for kk, vv in v.items():
+                setattr(getattr(f, k), kk, vv)
+        else:
+            setattr(f, k, v)
+    h = CFormHooks()
+    for k, v in (hooks or {}).items():
+        if isinstance(getattr(h, k), CFormHookValue):
+            getattr(h, k).set, getattr(h, k).value = 1, float(v)
+        else:
+            setattr(h, k, int(v))
+    d = CFormDecision()
+    L = lib()
+    L.hprlp_form_select.argtypes = [C.POINTER(CFormFacts), C.POINTER(CFormHooks), C.POINTER(CFormDecision)]
+    if L.hprlp_form_select(C.byref(f), C.byref(h), C.byref(d)) != 0:
+        raise RuntimeError(L.hprlp_last_error().decode())
+    out = _struct_dict(d)
+    out["note"] = out["note"].decode()
+    out["form"] = FORM_NAMES[out["form"]]
+    return out
+
+
 class Solver:
     """Step-level handle (include/hprlp_amd.h) used by the parity tests and bench.py."""
 
@@ -739,6 +808,19 @@ class Solver:
         L.hprlp_solver_describe.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
         self._chk(L.hprlp_solver_describe(self.h, buf, 2048))
         return buf.value.decode()
+
+    def form_facts(self):
+        """The facts the kernel-form rules were asked about (hprlp_solver_form_facts): {"A": [pass, ...], "A^T": [...]}, each
+        pass a dict for form_select(); the second pass, where there is one, is the all-remainder request."""
+        L = lib()
+        L.hprlp_solver_form_facts.argtypes = [C.c_void_p, C.c_int, C.POINTER(CFormFacts)]
+        out = {}
+        for which, name in enumerate(("A", "A^T")):
+            buf = (CFormFacts * 2)()
+            n = L.hprlp_solver_form_facts(self.h, which, buf)
+            self._chk(min(n, 0))
+            out[name] = [_struct_dict(buf[i]) for i in range(n)]
+        return out
 
     def run(self, max_trace=4096):
         res = CResults()

@@ -313,6 +313,59 @@ int hprlp_row_block_plan(int m, int n, const int *rowptr, const int *col, int wi
  * -1 + hprlp_last_error() on the first violation or when the build declines the pattern. */
 int hprlp_tiled_host_check(int m, int n, const int *rowptr, const int *col, int R, int T, double min_dense, long out[6]);
 
+/* ---- which kernel form a matrix gets (hpr-lp-c_amd/csrc/form_select.h) as plain data ----------------
+ * The rules are host-only functions of the records below; a solver's set-up measures the facts and asks them. */
+typedef struct hprlp_form_built { /* a tiled copy as its builder left it */
+    long ok;                      /* -1: no such build ran; 0: the builder declined the pattern; 1: built */
+    long n_pieces, dense_entries, n_rem; /* pieces of the piece form (0: fused), entries in staged tiles / in the remainder lists */
+    double rem_top_share;         /* share of the remainder that gathers from the 2 MB of most popular columns */
+} hprlp_form_built;
+typedef struct hprlp_form_facts { /* what the rules look at, for one pass over one matrix */
+    long rows, cols, nnz, longest_row;
+    double long_row_share;        /* share of the entries in rows of more than 256 entries (0 below 100 000 rows) */
+    double line_density;          /* distinct 64-byte lines of the gathered vector per entry (1: not sampled) */
+    double xcd_gather_bytes;      /* bytes of the gathered vector an XCD's eighth of the rows reads (0: not estimated) */
+    long sb_rows, slots;          /* super-block height of the copy; workgroup slots of the device (CUs x resident workgroups) */
+    double min_dense_override;    /* >= 0: the all-remainder request (a copy without a dense-tile requirement); < 0: none */
+    long sharded;                 /* the matrix is a row shard of a multi-GPU solver */
+    /* measured only when the earlier rules have not decided; -1: not measured */
+    long heaviest_block;          /* entries of the heaviest block of sb_rows consecutive rows */
+    double tiling_share;          /* cheap tiling test: share of the entries that would sit in dense tiles */
+    long n_long_rows, long_rows_nnz; /* rows of more than 1024 entries and their entries */
+    hprlp_form_built side, whole; /* the copy built without its long rows / of the whole matrix */
+    double popular_share;         /* share of the entries on the 32 768 most popular 64-byte lines of the gathered vector */
+    long heaviest_pb_block;       /* entries of the heaviest block of 4096 consecutive rows */
+} hprlp_form_facts;
+typedef struct hprlp_form_hook_value {
+    int set;
+    double value;
+} hprlp_form_hook_value;
+typedef struct hprlp_form_hooks { /* the test hooks (HPRLP_<NAME>, csrc/env.h) that influence the selection; all zero: none set */
+    int no_tiled, tiled_anyway, pieces_anyway, host_tiling, no_long_side, no_pb_fallback, no_pb_long_rows, no_pb_kernel;
+    int tiling_check;             /* 0: unset, 1: "1", 2: set to anything else */
+    hprlp_form_hook_value tiled_min_rows, tiled_min_dense, tiled_min_cols, pb_min_cols, pb_min_nnz, tile_rows, tile_cols;
+} hprlp_form_hooks;
+typedef struct hprlp_form_decision { /* the staged decisions of one pass */
+    int min_rows, min_cols;       /* before the build: fewest rows / columns of a matrix that is tried in a tiled form ... */
+    double min_dense;             /* ... and the least share of the entries in staged tiles */
+    int route;                    /* 0: nothing to do, 1: stream kernel after the cheap tiling test (thin rows), 2: not attempted
+                                   * (shape), 3: too few rows, 4: build on the device, 5: the host builder, 6: built with the long
+                                   * rows aside and kept */
+    int side_tried;               /* the long-rows-aside build was attempted */
+    int kept;                     /* after the build: a tiled copy is in place */
+    int form;                     /* 0: stream kernel, 1: tiled fused, 2: tiled piece form, 3: tiled all-remainder form */
+    int why;                      /* why there is no tiled copy (0: there is one, or no reason to give; form_select.h: NoTiled) */
+    int long_rows_alone;          /* ... not attempted for the length of its rows alone (an input of rule 13) */
+    int all_remainder_wanted;     /* the all-remainder form follows (a second pass with min_dense_override = 0) */
+    char note[96];                /* the bracketed note of hprlp_solver_describe for `why` ("" or " [...]") */
+} hprlp_form_decision;
+/* host only: the decisions for a facts record (hooks NULL: none set).  -1 + hprlp_last_error() when a rule asks for a fact that
+ * the record marks as not measured. */
+int hprlp_form_select(const hprlp_form_facts *facts, const hprlp_form_hooks *hooks, hprlp_form_decision *out);
+/* The facts A (which = 0) or A^T (1) of a solver was decided on: out[0] the pass with the dense-tile requirement (on the final
+ * numbering, behind a locality ordering), out[1] the all-remainder pass where one followed.  Returns the number of passes. */
+int hprlp_solver_form_facts(hprlp_solver *s, int which, hprlp_form_facts out[2]);
+
 #ifdef __cplusplus
 }
 #endif
