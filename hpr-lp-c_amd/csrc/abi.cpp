@@ -1221,6 +1221,54 @@ extern "C" int hprlp_solver_set_start(hprlp_solver *h, const double *x0, const d
     GUARD_END(-1)
 }
 
+// Re-solve (DESIGN.md "Re-solve"): new data for the resident LP, then a further solve on the same solver
+extern "C" int hprlp_solver_set_data(hprlp_solver *h, const double *c, const double *obj_constant, const double *AL, const double *AU,
+                                     const double *l, const double *u) {
+    GUARD_BEGIN
+    if (!h) throw std::runtime_error("null solver");
+    if (h->sharded)
+        throw std::runtime_error("hprlp_solver_set_data: new data for a resident model runs on one GPU only; a sharded solver "
+                                 "(hprlp_solver_create_dist* / _local*) refuses it");
+    h->s.set_data(c, obj_constant, AL, AU, l, u);
+    return 0;
+    GUARD_END(-1)
+}
+
+extern "C" int hprlp_solver_resolve(hprlp_solver *h, double sigma, const double *x0, const double *y0, HPRLP_results *out,
+                                    hprlp_trace_row *trace, int max_trace, int *n_trace) {
+    GUARD_BEGIN
+    if (!h || !out) throw std::runtime_error("null solver / result");
+    if (h->sharded)
+        throw std::runtime_error("hprlp_solver_resolve: a re-solve runs on one GPU only; a sharded solver (hprlp_solver_create_dist* / "
+                                 "_local*) refuses it");
+    if (std::isnan(sigma)) throw std::runtime_error("hprlp_solver_resolve: sigma is NaN");
+    check_start(x0, h->s.n, "x0");
+    check_start(y0, h->s.m, "y0");
+    Solver &s = h->s;
+    s.trace = reinterpret_cast<TraceRow *>(trace);
+    s.trace_cap = trace ? max_trace : 0;
+    try {
+        s.resolve(sigma, x0, y0, out);
+    } catch (...) {
+        s.trace = nullptr;
+        s.trace_cap = 0;
+        throw;
+    }
+    if (n_trace) *n_trace = s.trace_n;
+    s.trace = nullptr;
+    s.trace_cap = 0;
+    return 0;
+    GUARD_END(-1)
+}
+
+extern "C" int hprlp_solver_data_seconds(hprlp_solver *h, double out[3]) {
+    GUARD_BEGIN
+    if (!h || !out) throw std::runtime_error("null solver / output");
+    for (int i = 0; i < 3; ++i) out[i] = h->s.data_time[i];
+    return 0;
+    GUARD_END(-1)
+}
+
 extern "C" int hprlp_solver_get_certificate(hprlp_solver *h, hprlp_certificate *cert) {
     GUARD_BEGIN
     if (!h || !cert) throw std::runtime_error("null solver / certificate");

@@ -53,6 +53,13 @@ enum Slot : int {
     S_RAY_DZ = 26,  // D: bound terms of the columns (z = -A^T y)
     S_RAY_VZ = 27,  // V: columns (max)
     S_RAY_WQ = 28,  // W: rows (q = A d, max)
+    // Solver::set_data (between two solves, when no ray test is in flight: the six slots of k_ray_form serve again)
+    S_DATA_B_ORG = 20,  // |b|^2 of the caller's AL / AU
+    S_DATA_C_ORG = 21,  // |c|^2 of the caller's c
+    S_DATA_B_PRE = 22,  // |b|^2 after row_norm, before the b scaling (b_scale = 1 + its root; k_data_bc reads it on the device)
+    S_DATA_C_PRE = 23,  // |c|^2 after col_norm, before the c scaling
+    S_DATA_NB = 24,     // norm_b^2 of the final vectors
+    S_DATA_NC = 25,     // norm_c^2
 };
 
 // Row-block descriptor: one per wave.  {first row, number of rows, first nonzero, nonzero count}.
@@ -264,6 +271,33 @@ void launch_pw_start(int m, unsigned long long seed, long long offset, double *z
 void launch_pw_normalize(const double *z, double *q, int m, const double *scalars, hipStream_t s);
 void launch_pw_err(const double *z, const double *q, int m, const double *scalars, double *partials, int nblocks,
                    hipStream_t s);
+
+// ---- re-solve (Solver::set_data, DESIGN.md "Re-solve"): new data of the caller into the resident model's scaled vectors --------
+// k_data_in: AL, AU = in[pr[i]] / row_norm[i]; c = in[pc[j]] / col_norm[j]; l, u = in[pc[j]] * col_norm[j]; partials (4 x stride)
+// of |b|^2, |c|^2 of the caller's data and of the scaled data.  m / nc / nb = 0: that part was not given.  pc / pr null: no
+// locality ordering.  Grid kReduceBlocks, the reduction of k_bnorm2 / k_norm2.
+struct DataInArgs {
+    int m, nc, nb;
+    const double *AL_in, *AU_in, *c_in, *l_in, *u_in;  // device copies of the caller's vectors (caller's numbering)
+    const int *pc, *pr;
+    const double *row_norm, *col_norm;
+    double *AL, *AU, *c, *l, *u;
+    double *partials;
+    int stride;
+};
+void launch_data_in(const DataInArgs &a, hipStream_t s);
+// k_data_bc: AL, AU, l, u *= 1 / (1 + sqrt(scalars[S_DATA_B_PRE])), c *= 1 / (1 + sqrt(scalars[S_DATA_C_PRE])) (use_bc; else as they
+// are), row_code / lu_code of the results (null: not kept), partials (2 x stride) of norm_b^2, norm_c^2
+struct DataBcArgs {
+    int m, nc, nb;
+    int use_bc;
+    const double *scalars;
+    double *AL, *AU, *c, *l, *u;
+    unsigned char *row_code, *lu_code;
+    double *partials;
+    int stride;
+};
+void launch_data_bc(const DataBcArgs &a, hipStream_t s);
 
 // x = b_scale * x_bar / col_norm etc. (reference collect_solution, utils.cu:143-200)
 void launch_unscale(int n, int m, const double *x_bar, const double *y_bar, const double *z_bar,

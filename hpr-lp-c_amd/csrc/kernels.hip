@@ -2628,6 +2628,119 @@ void launch_start_in(const StartInArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(k_start_in, dim3(vec_grid(a.n > a.m ? a.n : a.m)), dim3(kThreads), 0, s, a);
 }
 
+// Re-solve (Solver::set_data, DESIGN.md "Re-solve"): new c / AL, AU, l, u in the caller's units and numbering -> the scaled,
+// permuted vectors of the resident model.  First pass: gather, apply the cumulative row_norm / col_norm, write the vectors as they
+// are before the b / c scaling, and leave the partials of |b|^2, |c|^2 of the caller's data and of the scaled data.  Same grid,
+// same element-to-thread map and same block reduction as k_bnorm2 / k_norm2, so the sums over identical inputs are the bits
+// Solver::scale() gets.  nc / nb / m: 0 for a group the caller did not give.
+__global__ void __launch_bounds__(kThreads) k_data_in(DataInArgs a) {
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};  // b original, c original, b scaled, c scaled
+    const int tid = blockIdx.x * kThreads + threadIdx.x, nth = gridDim.x * kThreads;
+    for (int i = tid; i < a.m; i += nth) {
+        const int src = a.pr ? a.pr[i] : i;
+        const double lo = a.AL_in[src], hi = a.AU_in[src], rn = a.row_norm[i];
+        const double v = fmax(fabs(isinf(lo) ? 0.0 : lo), fabs(isinf(hi) ? 0.0 : hi));
+        acc[0] += v * v;
+        const double los = lo / rn, his = hi / rn;
+        a.AL[i] = los;
+        a.AU[i] = his;
+        const double w = fmax(fabs(isinf(los) ? 0.0 : los), fabs(isinf(his) ? 0.0 : his));
+        acc[2] += w * w;
+    }
+    for (int j = tid; j < a.nc; j += nth) {
+        const double v = a.c_in[a.pc ? a.pc[j] : j];
+        acc[1] += v * v;
+        const double vs = v / a.col_norm[j];
+        a.c[j] = vs;
+        acc[3] += vs * vs;
+    }
+    for (int j = tid; j < a.nb; j += nth) {
+        const int src = a.pc ? a.pc[j] : j;
+        const double cn = a.col_norm[j];
+        a.l[j] = a.l_in[src] * cn;
+        a.u[j] = a.u_in[src] * cn;
+    }
+    block_store_partials<4>(acc, a.partials, a.stride);
+}
+void launch_data_in(const DataInArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(k_data_in, dim3(kReduceBlocks), dim3(kThreads), 0, s, a);
+}
+
+// Second pass: 1 / b_scale and 1 / c_scale from the sums the finalize left on the device (no host round trip between the passes),
+// the scaled vectors in place, the bound codes of the final values (k_row_codes / k_bound_codes, same bytes) and the partials of
+// norm_b^2, norm_c^2.  Nothing is gathered here, so every array moves as 16-byte pairs (the buffers are allocation-aligned; an
+// odd length ends in one scalar element).
+__device__ __forceinline__ unsigned char row_code_of(double lo, double hi) {
+    const bool lo_minf = lo == -__builtin_huge_val(), hi_pinf = hi == __builtin_huge_val();
+    const bool eq = !hi_pinf && __double_as_longlong(lo) == __double_as_longlong(hi);
+    return static_cast<unsigned char>((lo_minf || eq ? 0u : kLoadLo) | (hi_pinf ? 0u : kLoadHi) | (eq ? kRowEq : 0u));
+}
+__device__ __forceinline__ unsigned char bound_code_of(double lj, double uj) {
+    const bool l_zero = __double_as_longlong(lj) == 0, l_minf = lj == -__builtin_huge_val(), u_pinf = uj == __builtin_huge_val();
+    return static_cast<unsigned char>((l_zero || l_minf ? 0u : kLoadL) | (u_pinf ? 0u : kLoadU) | (l_zero ? kZeroL : 0u));
+}
+__device__ __forceinline__ double bside_sq(double lo, double hi) {
+    const double v = fmax(fabs(isinf(lo) ? 0.0 : lo), fabs(isinf(hi) ? 0.0 : hi));
+    return v * v;
+}
+__global__ void __launch_bounds__(kThreads) k_data_bc(DataBcArgs a) {
+    const double bs = a.use_bc ? 1.0 / (1.0 + sqrt(a.scalars[S_DATA_B_PRE])) : 1.0;
+    const double cs = a.use_bc ? 1.0 / (1.0 + sqrt(a.scalars[S_DATA_C_PRE])) : 1.0;
+    double acc[2] = {0.0, 0.0};  // b, c
+    const int tid = blockIdx.x * kThreads + threadIdx.x, nth = gridDim.x * kThreads;
+    for (int p = tid; 2 * p < a.m; p += nth) {
+        const int i = 2 * p;
+        if (i + 1 < a.m) {
+            double2 lo = *reinterpret_cast<const double2 *>(a.AL + i), hi = *reinterpret_cast<const double2 *>(a.AU + i);
+            lo.x = lo.x * bs; lo.y = lo.y * bs; hi.x = hi.x * bs; hi.y = hi.y * bs;
+            *reinterpret_cast<double2 *>(a.AL + i) = lo;
+            *reinterpret_cast<double2 *>(a.AU + i) = hi;
+            if (a.row_code) *reinterpret_cast<uchar2 *>(a.row_code + i) = make_uchar2(row_code_of(lo.x, hi.x), row_code_of(lo.y, hi.y));
+            acc[0] += bside_sq(lo.x, hi.x);
+            acc[0] += bside_sq(lo.y, hi.y);
+        } else {
+            const double lo = a.AL[i] * bs, hi = a.AU[i] * bs;
+            a.AL[i] = lo;
+            a.AU[i] = hi;
+            if (a.row_code) a.row_code[i] = row_code_of(lo, hi);
+            acc[0] += bside_sq(lo, hi);
+        }
+    }
+    for (int p = tid; 2 * p < a.nb; p += nth) {
+        const int j = 2 * p;
+        if (j + 1 < a.nb) {
+            double2 lo = *reinterpret_cast<const double2 *>(a.l + j), hi = *reinterpret_cast<const double2 *>(a.u + j);
+            lo.x = lo.x * bs; lo.y = lo.y * bs; hi.x = hi.x * bs; hi.y = hi.y * bs;
+            *reinterpret_cast<double2 *>(a.l + j) = lo;
+            *reinterpret_cast<double2 *>(a.u + j) = hi;
+            if (a.lu_code) *reinterpret_cast<uchar2 *>(a.lu_code + j) = make_uchar2(bound_code_of(lo.x, hi.x), bound_code_of(lo.y, hi.y));
+        } else {
+            const double lo = a.l[j] * bs, hi = a.u[j] * bs;
+            a.l[j] = lo;
+            a.u[j] = hi;
+            if (a.lu_code) a.lu_code[j] = bound_code_of(lo, hi);
+        }
+    }
+    for (int p = tid; 2 * p < a.nc; p += nth) {
+        const int j = 2 * p;
+        if (j + 1 < a.nc) {
+            double2 v = *reinterpret_cast<const double2 *>(a.c + j);
+            v.x = v.x * cs; v.y = v.y * cs;
+            *reinterpret_cast<double2 *>(a.c + j) = v;
+            acc[1] += v.x * v.x;
+            acc[1] += v.y * v.y;
+        } else {
+            const double v = a.c[j] * cs;
+            a.c[j] = v;
+            acc[1] += v * v;
+        }
+    }
+    block_store_partials<2>(acc, a.partials, a.stride);
+}
+void launch_data_bc(const DataBcArgs &a, hipStream_t s) {
+    hipLaunchKernelGGL(k_data_bc, dim3(kReduceBlocks), dim3(kThreads), 0, s, a);
+}
+
 __global__ void __launch_bounds__(kThreads) k_unscale(int n, int m, const double *x_bar, const double *y_bar,
                                                      const double *z_bar, const double *col_norm,
                                                      const double *row_norm, double b_scale, double c_scale, double *xo,

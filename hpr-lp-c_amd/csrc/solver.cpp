@@ -1343,6 +1343,7 @@ void Solver::scale() {
     HIP_CHECK(hipMemsetAsync(gsn.p, 0, sizeof(double) * n_pad, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     scaling_time = time_since(t0);
+    scaled = true;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1821,7 +1822,9 @@ static int next_event(int iter, int check_iter, int max_iter) {
 
 void Solver::solve_loop(HPRLP_results *out) {
     const auto t_loop = time_now();
-    const double t_before = power_time;  // reported `time` includes the power iteration (HPRLP.cu:150)
+    // reported `time` includes the power iteration (HPRLP.cu:150); a re-solve ran none and counts its set_data instead
+    const double t_before = time_base >= 0.0 ? time_base : power_time;
+    data_since_run = 0.0;
     Residuals r;
     RestartState rs;
     rs.best_sigma = sigma;
@@ -2066,6 +2069,121 @@ void Solver::set_start(const double *x0, const double *y0) {
     launch_finalize(f, scal.p, stream);
     HIP_CHECK(hipStreamSynchronize(stream));  // (the uploads' buffers go out of scope here)
     start_time = time_since(t0);
+}
+
+// ------------------------------------------------------------------------------------------------
+// re-solve (DESIGN.md "Re-solve"): new c / row sides / bounds for the resident model.  Everything that depends on A alone stays
+// (scaled matrices, row_norm, col_norm, lambda_max, kernel forms, ordering); the vectors follow the reference's batched rule
+// (scale by the cumulative norms, then this data's own b_scale / c_scale and norms).
+// ------------------------------------------------------------------------------------------------
+void Solver::set_data(const double *c_, const double *obj_constant_, const double *AL_, const double *AU_, const double *l_, const double *u_) {
+    if (comm) throw std::runtime_error("new data for a resident model runs on one GPU only (sharded solver)");
+    if (!scaled) throw std::runtime_error("set_data: the solver has not been scaled yet (hprlp_solver_scale comes first)");
+    const bool bounds = AL_ || AU_ || l_ || u_;
+    if (bounds && !(AL_ && AU_ && l_ && u_))
+        throw std::runtime_error("set_data: AL, AU, l and u are given together or not at all (b_scale couples them)");
+    auto no_nan = [](const double *v, long len, const char *what) {
+        for (long i = 0; v && i < len; ++i)
+            if (std::isnan(v[i])) throw std::runtime_error(std::string("set_data: ") + what + "[" + std::to_string(i) + "] is NaN");
+    };
+    no_nan(c_, n, "c"); no_nan(AL_, m, "AL"); no_nan(AU_, m, "AU"); no_nan(l_, n, "l"); no_nan(u_, n, "u");
+    if (obj_constant_ && std::isnan(*obj_constant_)) throw std::runtime_error("set_data: obj_constant is NaN");
+    data_time[0] = data_time[1] = data_time[2] = 0.0;
+    if (obj_constant_) obj_constant = *obj_constant_;
+    if (!c_ && !bounds) return;
+    const auto t0 = time_now();
+    const int mb = bounds ? m_loc : 0, nb = bounds ? n_loc : 0, nc = c_ ? n_loc : 0;
+    // staging: [AL | AU | l | u | c]; below the allocator cache's block size the solver keeps it (a hipFree per call would
+    // synchronise the device), above it the cache does
+    const size_t total = 2 * static_cast<size_t>(mb) + 2 * static_cast<size_t>(nb) + static_cast<size_t>(nc);
+    if (data_stage.n < total) data_stage.alloc(total);
+    double *dAL = data_stage.p, *dAU = dAL + mb, *dl = dAU + mb, *du = dl + nb, *dc = du + nb;
+    const struct { const double *src; double *dst; int len; } parts[5] = {{AL_, dAL, mb}, {AU_, dAU, mb}, {l_, dl, nb}, {u_, du, nb}, {c_, dc, nc}};
+    if (total * sizeof(double) < kDeviceCacheMinBytes) {  // one copy instead of five
+        data_pack.resize(total);
+        for (const auto &q : parts)
+            if (q.len > 0) std::memcpy(data_pack.data() + (q.dst - data_stage.p), q.src, sizeof(double) * q.len);
+        HIP_CHECK(hipMemcpyAsync(data_stage.p, data_pack.data(), sizeof(double) * total, hipMemcpyHostToDevice, stream));
+    } else {
+        for (const auto &q : parts)
+            if (q.len > 0) HIP_CHECK(hipMemcpyAsync(q.dst, q.src, sizeof(double) * q.len, hipMemcpyHostToDevice, stream));
+    }
+    if (!perm_r.empty() && !perm_r_dev.p) {
+        perm_r_dev.alloc(perm_r.size());
+        perm_c_dev.alloc(perm_c.size());
+        HIP_CHECK(hipMemcpyAsync(perm_r_dev.p, perm_r.data(), sizeof(int) * perm_r.size(), hipMemcpyHostToDevice, stream));
+        HIP_CHECK(hipMemcpyAsync(perm_c_dev.p, perm_c.data(), sizeof(int) * perm_c.size(), hipMemcpyHostToDevice, stream));
+    }
+    if (!data_part.p) data_part.alloc_zero(static_cast<size_t>(4) * kReduceBlocks);
+    // The bound codes are written by the second pass into the arrays the iteration kernels (and the captured iteration graphs, by
+    // pointer) already read.  The graphs hold nothing else of the data: XHalfArgs / YHalfArgs carry pointers, strides and the
+    // hand-off flags, sigma and lambda live in ctrl.  Only a code array that has to be allocated here moves a captured pointer.
+    unsigned char *rc = nullptr, *lc = nullptr;
+    if (!hook_no_bound_codes && bounds) {
+        if (row_code.n != static_cast<size_t>(m_loc) || lu_code.n != static_cast<size_t>(n_loc)) {
+            for (auto &kv : graphs) (void)hipGraphExecDestroy(kv.second);
+            graphs.clear();
+            HIP_CHECK(hipStreamSynchronize(stream));
+            row_code.alloc(static_cast<size_t>(m_loc));
+            lu_code.alloc(static_cast<size_t>(n_loc));
+        }
+        rc = row_code.p;
+        lc = lu_code.p;
+    }
+    data_time[0] = time_since(t0);
+    const auto t1 = time_now();
+    const DataInArgs in{mb, nc, nb, dAL, dAU, dc, dl, du, perm_c_dev.p, perm_r_dev.p, row_norm.p, col_norm.p,
+                        AL.p, AU.p, c.p, l.p, u.p, data_part.p, kReduceBlocks};
+    launch_data_in(in, stream);
+    FinalizeArgs f{};
+    if (bounds) {
+        f.item[f.n++] = {data_part.p, kReduceBlocks, S_DATA_B_ORG};
+        f.item[f.n++] = {data_part.p + 2 * static_cast<size_t>(kReduceBlocks), kReduceBlocks, S_DATA_B_PRE};
+    }
+    if (c_) {
+        f.item[f.n++] = {data_part.p + kReduceBlocks, kReduceBlocks, S_DATA_C_ORG};
+        f.item[f.n++] = {data_part.p + 3 * static_cast<size_t>(kReduceBlocks), kReduceBlocks, S_DATA_C_PRE};
+    }
+    launch_finalize(f, scal.p, stream);
+    const DataBcArgs bc{mb, nc, nb, prm.use_bc_scaling ? 1 : 0, scal.p, AL.p, AU.p, c.p, l.p, u.p, rc, lc, data_part.p, kReduceBlocks};
+    launch_data_bc(bc, stream);
+    FinalizeArgs g{};
+    if (bounds) g.item[g.n++] = {data_part.p, kReduceBlocks, S_DATA_NB};
+    if (c_) g.item[g.n++] = {data_part.p + kReduceBlocks, kReduceBlocks, S_DATA_NC};
+    launch_finalize(g, scal.p, stream);
+    fetch_scalars();
+    if (bounds) {
+        norm_b_org = 1.0 + std::sqrt(scal_h[S_DATA_B_ORG]);
+        b_scale = prm.use_bc_scaling ? 1.0 + std::sqrt(scal_h[S_DATA_B_PRE]) : 1.0;
+        norm_b = std::sqrt(scal_h[S_DATA_NB]);
+    }
+    if (c_) {
+        norm_c_org = 1.0 + std::sqrt(scal_h[S_DATA_C_ORG]);
+        c_scale = prm.use_bc_scaling ? 1.0 + std::sqrt(scal_h[S_DATA_C_PRE]) : 1.0;
+        norm_c = std::sqrt(scal_h[S_DATA_NC]);
+    }
+    invalidate_far();
+    if (data_stage.cap_bytes >= kDeviceCacheMinBytes) data_stage.release();  // (back to the allocator cache)
+    data_time[1] = time_since(t1);
+    data_time[2] = time_since(t0);
+    data_since_run += data_time[2];
+}
+
+void Solver::resolve(double sigma_, const double *x0, const double *y0, HPRLP_results *out) {
+    if (comm) throw std::runtime_error("re-solve runs on one GPU only (sharded solver)");
+    reset_iterates();
+    init_iteration_state();
+    if (sigma_ > 0.0) set_sigma_lambda(sigma_, lambda_max, true);
+    if (x0 || y0) set_start(x0, y0);
+    time_base = data_since_run;
+    try {
+        solve_loop(out);
+    } catch (...) {
+        time_base = -1.0;
+        throw;
+    }
+    time_base = -1.0;
+    collect_solution(out);
 }
 
 }  // namespace hprlp

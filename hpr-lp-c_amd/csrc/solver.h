@@ -179,6 +179,22 @@ struct Solver {
     void set_start(const double *x0, const double *y0);
     double start_time = 0.0;
 
+    // Re-solve (DESIGN.md "Re-solve"): new data for the LP this solver holds, caller's units and numbering, host memory.  Objective
+    // group: c_ (n) and / or obj_constant_; bounds group: AL_, AU_ (m), l_, u_ (n), all four or none.  A null group keeps its
+    // vectors, scales, norms and bound codes bit for bit.  After scale(); single GPU only.  Throws before anything is written
+    // (a NaN, an incomplete bounds group).  Two kernels (k_data_in, k_data_bc), two finalizes, one scalar fetch.
+    void set_data(const double *c_, const double *obj_constant_, const double *AL_, const double *AU_, const double *l_, const double *u_);
+    // A further solve on this solver: iterates to zero, sigma from the current norm_b / norm_c (sigma_ > 0 overrides), lambda_max as
+    // it stands, optional start, loop, solution.  out->time = set_data seconds since the previous loop + this loop.
+    void resolve(double sigma_, const double *x0, const double *y0, HPRLP_results *out);
+    double data_time[3] = {0.0, 0.0, 0.0};  // the last set_data: upload, kernels + fetch, total
+    double data_since_run = 0.0;            // set_data seconds since the last solve_loop
+    double time_base = -1.0;                // solve_loop: what the reported time starts from (< 0: power_time, as the reference)
+    bool scaled = false;                    // scale() has run: row_norm / col_norm are the model's
+    DBuf<double> data_stage, data_part;     // set_data: the uploaded vectors (kept between calls while small), 4 x kReduceBlocks partials
+    DBuf<int> perm_r_dev, perm_c_dev;       // set_data: the locality ordering's permutations on the device (first use)
+    std::vector<double> data_pack;          // set_data: small vectors travel in one copy
+
     std::map<int, hipGraphExec_t> graphs;
     TraceRow *trace = nullptr;
     int trace_cap = 0, trace_n = 0;

@@ -165,6 +165,10 @@ def lib():
                                            C.POINTER(CParameters), c_dbl_p, c_dbl_p, C.POINTER(CDetection),
                                            C.POINTER(CBatchedCertificates)]
     L.hprlp_solver_set_start.argtypes = [C.c_void_p, c_dbl_p, c_dbl_p]
+    L.hprlp_solver_set_data.argtypes = [C.c_void_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]
+    L.hprlp_solver_resolve.argtypes = [C.c_void_p, C.c_double, c_dbl_p, c_dbl_p, C.POINTER(CResults), C.POINTER(CTraceRow),
+                                       C.c_int, c_int_p]
+    L.hprlp_solver_data_seconds.argtypes = [C.c_void_p, c_dbl_p]
     L.hprlp_presolve_forward.argtypes = [C.c_void_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]
     _lib = L
     return L
@@ -840,6 +844,48 @@ class Solver:
         """Warm start of the next run() (hprlp_solver_set_start): after init(), in the model's units and numbering."""
         xs, ys = _start_vector(x, self.model.n, "x"), _start_vector(y, self.model.m, "y")
         self._chk(lib().hprlp_solver_set_start(self.h, _dptr(xs), _dptr(ys)))
+
+    def prepare(self):
+        """scale(), power_iteration(), init(-1, 1.01 lambda): ready for run(), and later for set_data() / resolve()."""
+        self.scale()
+        lam, _ = self.power_iteration()
+        self.init(-1.0, 1.01 * lam)
+
+    def _data_vector(self, v, length, name):
+        if v is None:
+            return None
+        a = _as(v, np.float64)
+        if a.ndim != 1 or a.shape[0] != length:
+            raise ValueError(f"set_data: {name} must have length {length}, got shape {a.shape}")
+        return a
+
+    def set_data(self, c=None, obj_constant=None, AL=None, AU=None, l=None, u=None):
+        """New data for the LP this solver holds (hprlp_solver_set_data), in the model's units and numbering.  c and / or
+        obj_constant; AL, AU, l, u together or not at all.  What is not given stays bit for bit."""
+        m, n = self.model.m, self.model.n
+        cv, ALv, AUv = self._data_vector(c, n, "c"), self._data_vector(AL, m, "AL"), self._data_vector(AU, m, "AU")
+        lv, uv = self._data_vector(l, n, "l"), self._data_vector(u, n, "u")
+        oc = None if obj_constant is None else C.byref(C.c_double(float(obj_constant)))
+        self._chk(lib().hprlp_solver_set_data(self.h, _dptr(cv), oc, _dptr(ALv), _dptr(AUv), _dptr(lv), _dptr(uv)))
+
+    def resolve(self, x=None, y=None, sigma=-1.0, max_trace=4096):
+        """A further solve on this solver (hprlp_solver_resolve): from zero, or from (x, y); sigma > 0 overrides the
+        norm_b / norm_c rule.  Returns what run() returns."""
+        xs, ys = _start_vector(x, self.model.n, "x"), _start_vector(y, self.model.m, "y")
+        res = CResults()
+        trace = (CTraceRow * max_trace)()
+        nt = C.c_int(0)
+        self._chk(lib().hprlp_solver_resolve(self.h, float(sigma), _dptr(xs), _dptr(ys), C.byref(res), trace, max_trace,
+                                             C.byref(nt)))
+        r = Results(res, self.model.m, self.model.n)
+        r.trace = [{f: getattr(trace[i], f) for f, _ in CTraceRow._fields_} for i in range(nt.value)]
+        return r
+
+    def data_seconds(self):
+        """Seconds of the last set_data(): {upload, kernels, total}."""
+        out = np.zeros(3)
+        self._chk(lib().hprlp_solver_data_seconds(self.h, out.ctypes.data_as(c_dbl_p)))
+        return dict(zip(("upload", "kernels", "total"), out))
 
     def certificate(self):
         """The certificate of the last run() (kind 0 without a verdict)."""

@@ -152,6 +152,24 @@ HPRLP_batched_results hprlp_solve_batched_warm(const LP_info_cpu *model, int bat
  * evaluated as a start).  -1 + hprlp_last_error() for a sharded solver or a non-finite entry. */
 int hprlp_solver_set_start(hprlp_solver *s, const double *x0, const double *y0);
 
+/* ---- re-solve: a sequence of LPs over one matrix on one resident solver (one GPU; DESIGN.md "Re-solve") -----------------------
+ * Everything that depends on A alone -- device set-up, kernel forms, ordering, the scaling factors, lambda_max -- is kept; the
+ * vectors are scaled by the solver's cumulative row / column factors and get their own b_scale, c_scale and norms.
+ *   objective group: c (n) and / or obj_constant; NULL keeps the current one bit for bit.
+ *   bounds group:    AL, AU (m), l, u (n), all four or none (b_scale couples them); NULL keeps them, and the bound codes, bit for bit.
+ * Caller's units and numbering, host memory; infinite entries stay infinite.  After hprlp_solver_scale.  No presolve on this
+ * path: hprlp_solver_create never presolved, and a reduced model does not survive a change of c or of the bounds in general.
+ * 0, or -1 + hprlp_last_error() (solver unchanged): a sharded solver, a NaN, an incomplete bounds group. */
+int hprlp_solver_set_data(hprlp_solver *s, const double *c, const double *obj_constant,
+                          const double *AL, const double *AU, const double *l, const double *u);
+/* solve again from zero or from (x0, y0); sigma <= 0: the norm_b / norm_c rule.  lambda_max is the solver's current one.
+ * Detection as set by hprlp_solver_set_detection.  Same outputs as hprlp_solver_run; out->time counts the set_data calls since
+ * the previous run and this loop, and no power iteration. */
+int hprlp_solver_resolve(hprlp_solver *s, double sigma, const double *x0, const double *y0, HPRLP_results *out,
+                         hprlp_trace_row *trace, int max_trace, int *n_trace);
+/* seconds of the last set_data: {upload, kernels + fetch, total} */
+int hprlp_solver_data_seconds(hprlp_solver *s, double out[3]);
+
 /* Named device vectors: x y x_hat x_bar y_bar z_bar x_temp y_temp y_obj last_x last_y AL AU l u c
  * row_norm col_norm A_val AT_val.  get returns the length (or -1); cap is the capacity of out. */
 long hprlp_solver_get_vector(hprlp_solver *s, const char *name, double *out, long cap);
