@@ -15,6 +15,7 @@
 #include "presolve.h"
 #include "reorder.h"
 #include "solver.h"
+#include "many.h"
 #include "version.h"
 
 using namespace hprlp;
@@ -1044,6 +1045,137 @@ extern "C" int hprlp_solver_run(hprlp_solver *h, HPRLP_results *out, hprlp_trace
     if (n_trace) *n_trace = h->s.trace_n;
     h->s.trace = nullptr;
     h->s.trace_cap = 0;
+    return 0;
+    GUARD_END(-1)
+}
+
+// ------------------------------------------------------------------------------------------------
+// many small LPs at once (many.cpp; DESIGN.md "Many small LPs")
+// ------------------------------------------------------------------------------------------------
+// the members of a group call, checked before anything is launched (`who`, for the error messages)
+static std::vector<Solver *> group_members(hprlp_solver **h, int count, const char *who) {
+    const std::string w(who);
+    if (!h) throw std::runtime_error(w + ": null solver list");
+    if (count <= 0) throw std::runtime_error(w + ": count must be positive");
+    std::vector<Solver *> s(static_cast<size_t>(count));
+    for (int k = 0; k < count; ++k) {
+        if (!h[k]) throw std::runtime_error(w + ": member " + std::to_string(k) + " is null");
+        if (h[k]->sharded)
+            throw std::runtime_error(w + ": member " + std::to_string(k) + " is a sharded solver (hprlp_solver_create_dist* / _local*); a group runs on one GPU");
+        s[k] = &h[k]->s;
+    }
+    check_group(s.data(), count, who);
+    return s;
+}
+
+extern "C" int hprlp_solver_power_iteration_many(hprlp_solver **h, int count, int max_iter, double tol, double *lambda_out, int *iters_out) {
+    GUARD_BEGIN
+    std::vector<Solver *> s = group_members(h, count, "hprlp_solver_power_iteration_many");
+    if (!lambda_out) throw std::runtime_error("hprlp_solver_power_iteration_many: null lambda_out");
+    power_iteration_many(s.data(), count, max_iter, tol, lambda_out, iters_out);
+    return 0;
+    GUARD_END(-1)
+}
+
+extern "C" int hprlp_solver_iterate_many(hprlp_solver **h, int count, const int *normal, int then_check) {
+    GUARD_BEGIN
+    std::vector<Solver *> s = group_members(h, count, "hprlp_solver_iterate_many");
+    iterate_many(s.data(), count, normal, then_check != 0);
+    return 0;
+    GUARD_END(-1)
+}
+
+static void free_results_arrays(HPRLP_results *out, int count) {
+    for (int k = 0; k < count; ++k) {
+        std::free(out[k].x); std::free(out[k].y); std::free(out[k].z);
+        out[k].x = out[k].y = out[k].z = nullptr;
+    }
+}
+
+extern "C" int hprlp_solver_run_many(hprlp_solver **h, int count, HPRLP_results *out) {
+    GUARD_BEGIN
+    std::vector<Solver *> s = group_members(h, count, "hprlp_solver_run_many");
+    if (!out) throw std::runtime_error("hprlp_solver_run_many: null results");
+    for (int k = 0; k < count; ++k) out[k] = make_error_result("ERROR");
+    try {
+        run_many(s.data(), count, out);
+    } catch (...) {
+        free_results_arrays(out, count);
+        throw;
+    }
+    return 0;
+    GUARD_END(-1)
+}
+
+// phases of the calling thread's last hprlp_solve_many (hprlp_last_solve_many_phases)
+static thread_local double g_many_phases[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
+extern "C" int hprlp_last_solve_many_phases(double out[8]) {
+    if (!out) return -1;
+    for (int i = 0; i < 8; ++i) out[i] = g_many_phases[i];
+    return 0;
+}
+
+extern "C" int hprlp_solve_many(const LP_info_cpu *const *models, int count, const HPRLP_parameters *param, HPRLP_results *out) {
+    GUARD_BEGIN
+    if (!models) throw std::runtime_error("hprlp_solve_many: null model list");
+    if (count <= 0) throw std::runtime_error("hprlp_solve_many: count must be positive");
+    if (!out) throw std::runtime_error("hprlp_solve_many: null results");
+    for (int k = 0; k < count; ++k)
+        if (!models[k]) throw std::runtime_error("hprlp_solve_many: model " + std::to_string(k) + " is null");
+    HPRLP_parameters dflt;
+    const HPRLP_parameters *p = param ? param : &dflt;
+    const auto t_call = time_now();
+    for (int k = 0; k < count; ++k) out[k] = make_error_result("ERROR");
+    for (int i = 0; i < 8; ++i) g_many_phases[i] = 0.0;
+    // set-up and scaling, member by member; a model that fails here stays "ERROR" and the others go on
+    std::vector<std::unique_ptr<Solver>> owned(static_cast<size_t>(count));
+    std::vector<Solver *> s;
+    std::vector<int> who;
+    for (int k = 0; k < count; ++k) {
+        try {
+            owned[k].reset(new Solver());
+            owned[k]->verbose = false;
+            owned[k]->setup(models[k], p);
+            owned[k]->scale();
+            g_many_phases[0] += owned[k]->setup_time;
+            g_many_phases[1] += owned[k]->scaling_time;
+            s.push_back(owned[k].get());
+            who.push_back(k);
+        } catch (const std::exception &e) {
+            set_last_error("hprlp_solve_many: model " + std::to_string(k) + ": " + e.what());
+            std::cerr << "[error] hprlp_solve_many: model " << k << " failed its set-up: " << e.what() << std::endl;
+            owned[k].reset();
+        }
+    }
+    const int ng = static_cast<int>(s.size());
+    if (ng > 0) {
+        std::vector<HPRLP_results> res(static_cast<size_t>(ng));
+        for (auto &r : res) r = make_error_result("ERROR");
+        try {
+            const auto t_pw = time_now();
+            std::vector<double> lam(static_cast<size_t>(ng));
+            power_iteration_many(s.data(), ng, 5000, 1e-4, lam.data(), nullptr);  // src/HPRLP.cu:81-97
+            for (int g = 0; g < ng; ++g) {
+                s[g]->lambda_max = lam[g] * 1.01;
+                s[g]->init_iteration_state();
+            }
+            g_many_phases[2] = time_since(t_pw);
+            const auto t_loop = time_now();
+            GroupCounts gc;
+            run_many(s.data(), ng, res.data(), &gc);
+            g_many_phases[3] = time_since(t_loop);  // (the loop and the solutions' way back)
+            g_many_phases[5] = static_cast<double>(gc.rounds);
+            g_many_phases[6] = static_cast<double>(gc.waits);
+            g_many_phases[7] = static_cast<double>(gc.launches);
+        } catch (...) {
+            free_results_arrays(res.data(), ng);
+            throw;
+        }
+        for (int g = 0; g < ng; ++g) out[who[g]] = res[g];
+    }
+    owned.clear();  // (the members' device state goes here: part of the call's wall time)
+    g_many_phases[4] = time_since(t_call);
     return 0;
     GUARD_END(-1)
 }

@@ -324,6 +324,37 @@ void launch_small_iterations(const SmallArgs &a, int count, hipStream_t s);
 // the whole power iteration of a small LP in one launch (small.hip): z0 = start vector (m), out = {lambda, iterations done}
 void launch_small_power(const SmallArgs &a, const double *z0, int max_iter, double tol, double *out, hipStream_t s);
 
+// ---- many small LPs at once (small.hip, DESIGN.md "Many small LPs"): grid = number of tasks, workgroup b runs task b exactly as
+// the single-LP kernel runs its arguments.  K is filled in by the launch wrappers.
+struct SmallIterTask {
+    SmallArgs a;
+    int K, count;  // count <= 0: the workgroup (if one is launched at all) returns at once
+};
+struct SmallPowerTask {
+    SmallArgs a;
+    const double *z0;  // start vector (m)
+    double *out;       // {lambda, iterations done}
+    double tol;
+    int K, max_iter;
+};
+// Where the task lists travel: a pinned staging block and its device copy, both grown on demand.  One list is in flight per
+// stream; the staging block is rewritten only after the previous copy out of it has completed.
+struct SmallTaskBuf {
+    void *host = nullptr, *dev = nullptr;
+    size_t cap = 0;
+    hipEvent_t copied = nullptr;
+    SmallTaskBuf() = default;
+    SmallTaskBuf(const SmallTaskBuf &) = delete;
+    SmallTaskBuf &operator=(const SmallTaskBuf &) = delete;
+    ~SmallTaskBuf();
+    void *stage(size_t bytes);  // room for `bytes` in the staging block, free to be written
+    void send(size_t bytes, hipStream_t s);
+};
+// One launch per <KMAX, R> class present among the tasks (the classes of launch_small_iterations / launch_small_power); tasks
+// with count <= 0 are left out.  Returns the number of launches.
+int launch_small_iterations_many(const SmallIterTask *tasks, int ntasks, SmallTaskBuf &buf, hipStream_t s);
+int launch_small_power_many(const SmallPowerTask *tasks, int ntasks, SmallTaskBuf &buf, hipStream_t s);
+
 // device CSR -> device CSR of the transpose, stable in row order (transpose.hip); all pointers are device memory,
 // trp has cols+1 entries, tci / tv nnz
 void device_transpose(int rows, int cols, long nnz, const int *rowptr, const int *col, const double *val, int *trp,

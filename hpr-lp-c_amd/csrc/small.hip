@@ -20,7 +20,9 @@
 // advance_halpern_factors (src/main_iterate.cu:434-481,68-70) and the graph replay around them
 // (src/HPRLP.cu:99-114,290-303).
 #include <algorithm>
+#include <stdexcept>
 
+#include "common.h"
 #include "kernels.h"
 
 namespace hprlp {
@@ -68,8 +70,10 @@ __device__ __forceinline__ double wave_sum64(double v) {
     return v;
 }
 
-template <int KMAX, int R>
-__global__ void __launch_bounds__(NT) k_small_iterations(SmallArgs a, int K, int count) {
+// The body of k_small_iterations and of k_small_iterations_many: one workgroup, `count` iterations of the LP `a` names.
+// (Args: SmallArgs, or the same with its pointers typed as global memory -- see SmallArgsGlobal)
+template <int KMAX, int R, class Args>
+__device__ __forceinline__ void small_iterations_body(const Args &a, int K, int count) {
     static_assert(KMAX % 2 == 0, "positions are packed in pairs");
     __shared__ double prod[NT * KMAX + NT * KMAX / 32 + 1];
     __shared__ double ys[NT * R];
@@ -187,6 +191,46 @@ __global__ void __launch_bounds__(NT) k_small_iterations(SmallArgs a, int K, int
     }
 }
 
+template <int KMAX, int R>
+__global__ void __launch_bounds__(NT) k_small_iterations(SmallArgs a, int K, int count) {
+    small_iterations_body<KMAX, R>(a, K, count);
+}
+
+// A pointer read from a task list is a generic one to the compiler (a kernel argument it knows to be global memory): every access
+// through it would be a flat one with a 64-bit address register pair, and the <12, 2> instance would spill.  The group kernels
+// therefore hand the body the same arguments typed as global memory.
+#define HPRLP_GLOBAL __attribute__((address_space(1)))
+struct SmallArgsGlobal {
+    int m, n, nnz;
+    const HPRLP_GLOBAL int *A_rowptr, *AT_rowptr;
+    const HPRLP_GLOBAL double *AT_val;
+    const HPRLP_GLOBAL int *ent_ij, *ent_posA, *order_x, *order_y;
+    HPRLP_GLOBAL double *x, *x_hat, *y;
+    const HPRLP_GLOBAL double *l, *u, *c, *last_x, *AL, *AU, *last_y;
+    HPRLP_GLOBAL Ctrl *ctrl;
+};
+template <class T>
+__device__ __forceinline__ HPRLP_GLOBAL T *as_global(T *p) {
+    return (HPRLP_GLOBAL T *)p;
+}
+__device__ __forceinline__ SmallArgsGlobal global_args(const SmallArgs &a) {
+    return SmallArgsGlobal{a.m, a.n, a.nnz, as_global(a.A_rowptr), as_global(a.AT_rowptr), as_global(a.AT_val), as_global(a.ent_ij),
+                           as_global(a.ent_posA), as_global(a.order_x), as_global(a.order_y), as_global(a.x), as_global(a.x_hat),
+                           as_global(a.y), as_global(a.l), as_global(a.u), as_global(a.c), as_global(a.last_x), as_global(a.AL),
+                           as_global(a.AU), as_global(a.last_y), as_global(a.ctrl)};
+}
+
+// Many small LPs at once (DESIGN.md "Many small LPs"): workgroup b runs task b exactly as k_small_iterations would -- the same body
+// on the same arguments, so a member's iterates are the single launch's bits.  The task is uniform in the workgroup and is read
+// before anything is stored (scalar loads into a private copy).  No workgroup reads what another writes; a task without
+// iterations touches nothing.
+template <int KMAX, int R>
+__global__ void __launch_bounds__(NT) k_small_iterations_many(const SmallIterTask *__restrict__ tasks) {
+    const SmallIterTask task = tasks[blockIdx.x];
+    if (task.count <= 0) return;
+    small_iterations_body<KMAX, R>(global_args(task.a), task.K, task.count);
+}
+
 // ------------------------------------------------------------------------------------------------
 // The power iteration of a small LP (reference power_method_cusparse, src/power_iteration.cu:20-119) in ONE launch of the
 // same single workgroup: q = z / sqrt(z.z + eps), z = A (A^T q), every 10th iteration lambda = q.z and the stopping test
@@ -195,9 +239,9 @@ __global__ void __launch_bounds__(NT) k_small_iterations(SmallArgs a, int K, int
 // CSR order); the three dot products are added in a fixed tree order (thread, wave shuffle, 16 wave sums), i.e. they
 // agree with the oracle's sequential sums to rounding.  out = {lambda, iterations done}.
 // ------------------------------------------------------------------------------------------------
-template <int KMAX, int R>
-__global__ void __launch_bounds__(NT) k_small_power(SmallArgs a, int K, const double *__restrict__ z0, int max_iter, double tol,
-                                                   double *__restrict__ out) {
+template <int KMAX, int R, bool TIGHT, class Args, class In, class Out>
+__device__ __forceinline__ void small_power_body(const Args &a, int K, In z0, int max_iter, double tol, Out out) {
+    auto fr = [](unsigned int w) { return TIGHT ? fresh(w) : w; };
     __shared__ double prod[NT * KMAX + NT * KMAX / 32 + 1];
     __shared__ double qs[NT * R];   // q (length m), gathered by the products of A^T q
     __shared__ double gs[NT * R];   // A^T q (length n), gathered by the products of A (A^T q)
@@ -279,7 +323,7 @@ __global__ void __launch_bounds__(NT) k_small_power(SmallArgs a, int K, const do
         lds_sync();
 #pragma unroll
         for (int q = 0; q < R; ++q) {
-            const double sx = seq_sum(prod, static_cast<int>(xseg[q] & 0xffffu), static_cast<int>(xseg[q] >> 16));
+            const double sx = seq_sum(prod, static_cast<int>(fr(xseg[q]) & 0xffffu), static_cast<int>(fr(xseg[q]) >> 16));
             if ((own[q] & 0xffffu) != 0xffffu) gs[own[q] & 0xffffu] = sx;
         }
         lds_sync();
@@ -295,7 +339,7 @@ __global__ void __launch_bounds__(NT) k_small_power(SmallArgs a, int K, const do
         double pzz = 0.0, pqz = 0.0;
 #pragma unroll
         for (int q = 0; q < R; ++q) {
-            const double sy = seq_sum(prod, static_cast<int>(yseg[q] & 0xffffu), static_cast<int>(yseg[q] >> 16));
+            const double sy = seq_sum(prod, static_cast<int>(fr(yseg[q]) & 0xffffu), static_cast<int>(fr(yseg[q]) >> 16));
             z[q] = (own[q] >> 16) != 0xffffu ? sy : 0.0;
             pzz += z[q] * z[q];
             pqz += z[q] * qv[q];
@@ -322,6 +366,19 @@ __global__ void __launch_bounds__(NT) k_small_power(SmallArgs a, int K, const do
         out[0] = lambda;
         out[1] = static_cast<double>(done);
     }
+}
+
+template <int KMAX, int R>
+__global__ void __launch_bounds__(NT) k_small_power(SmallArgs a, int K, const double *__restrict__ z0, int max_iter, double tol,
+                                                   double *__restrict__ out) {
+    small_power_body<KMAX, R, false>(a, K, z0, max_iter, tol, out);
+}
+
+// workgroup b runs the power iteration of task b (its own start vector, limit, tolerance and output) as k_small_power would
+template <int KMAX, int R>
+__global__ void __launch_bounds__(NT) k_small_power_many(const SmallPowerTask *__restrict__ tasks) {
+    const SmallPowerTask task = tasks[blockIdx.x];
+    small_power_body<KMAX, R, true>(global_args(task.a), task.K, as_global(task.z0), task.max_iter, task.tol, as_global(task.out));
 }
 
 template <int KMAX, int R>
@@ -367,6 +424,120 @@ void launch_small_iterations(const SmallArgs &a, int count, hipStream_t s) {
     else if (K <= 8) launch_kr<8, 2>(a, count, s);
     else if (R <= 1) launch_kr<12, 1>(a, count, s);
     else launch_kr<12, 2>(a, count, s);
+}
+
+// ---- task lists of the group launches ------------------------------------------------------------------------------------
+SmallTaskBuf::~SmallTaskBuf() {
+    if (copied) (void)hipEventDestroy(copied);
+    if (host) (void)hipHostFree(host);
+    if (dev) (void)hipFree(dev);
+}
+
+void *SmallTaskBuf::stage(size_t bytes) {
+    if (!copied) HIP_CHECK(hipEventCreateWithFlags(&copied, hipEventDisableTiming));
+    else HIP_CHECK(hipEventSynchronize(copied));  // the previous list has left the staging block (long ago, as a rule)
+    if (bytes > cap) {
+        // (the device copy may still be read by the previous launch: hipFree waits for the device)
+        if (host) (void)hipHostFree(host);
+        if (dev) (void)hipFree(dev);
+        host = dev = nullptr;
+        cap = 0;
+        const size_t want = std::max(bytes, static_cast<size_t>(1) << 14);
+        HIP_CHECK(hipHostMalloc(&host, want, hipHostMallocDefault));
+        HIP_CHECK(hipMalloc(&dev, want));
+        cap = want;
+    }
+    return host;
+}
+
+void SmallTaskBuf::send(size_t bytes, hipStream_t s) {
+    HIP_CHECK(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, s));
+    HIP_CHECK(hipEventRecord(copied, s));
+}
+
+namespace {
+
+// the <KMAX, R> class of an LP, in the order of the if-chains of launch_small_iterations / launch_small_power
+int small_class(const SmallArgs &a) {
+    const int K = (a.nnz + NT - 1) / NT;
+    const int R = (std::max(a.m, a.n) + NT - 1) / NT;
+    if (K <= 4 && R <= 1) return 0;
+    if (K <= 4) return 1;
+    if (K <= 8 && R <= 1) return 2;
+    if (K <= 8) return 3;
+    if (R <= 1) return 4;
+    return 5;
+}
+
+void check_small_task(const SmallArgs &a) {
+    // the kernels index LDS by these: a task outside the small path's limits must never reach them
+    if (a.m < 1 || a.n < 1 || a.m > NT * kSmallMaxR || a.n > NT * kSmallMaxR || a.nnz < 1 || a.nnz >= NT * kSmallMaxK)
+        throw std::runtime_error("a task of a group launch is outside the small path's limits");
+}
+
+// tasks -> staging block, grouped by class (stable), K filled in; first[c] .. first[c + 1] is class c's range
+template <class Task, class Keep>
+int stage_tasks(const Task *tasks, int ntasks, SmallTaskBuf &buf, int first[7], Keep keep) {
+    int per[6] = {0, 0, 0, 0, 0, 0}, total = 0;
+    for (int k = 0; k < ntasks; ++k)
+        if (keep(tasks[k])) {
+            check_small_task(tasks[k].a);
+            ++per[small_class(tasks[k].a)];
+            ++total;
+        }
+    first[0] = 0;
+    for (int c = 0; c < 6; ++c) first[c + 1] = first[c] + per[c];
+    if (total == 0) return 0;
+    Task *st = static_cast<Task *>(buf.stage(sizeof(Task) * static_cast<size_t>(total)));
+    int at[6];
+    for (int c = 0; c < 6; ++c) at[c] = first[c];
+    for (int k = 0; k < ntasks; ++k)
+        if (keep(tasks[k])) {
+            Task t = tasks[k];
+            t.K = (t.a.nnz + NT - 1) / NT;
+            st[at[small_class(t.a)]++] = t;
+        }
+    return total;
+}
+
+template <int KMAX, int R>
+int launch_iterations_many_kr(const SmallIterTask *dev, int first, int count, hipStream_t s) {
+    if (count <= 0) return 0;
+    hipLaunchKernelGGL((k_small_iterations_many<KMAX, R>), dim3(count), dim3(NT), 0, s, dev + first);
+    HIP_CHECK(hipGetLastError());  // (as launch_kr: a refused launch must not pass silently)
+    return 1;
+}
+
+template <int KMAX, int R>
+int launch_power_many_kr(const SmallPowerTask *dev, int first, int count, hipStream_t s) {
+    if (count <= 0) return 0;
+    hipLaunchKernelGGL((k_small_power_many<KMAX, R>), dim3(count), dim3(NT), 0, s, dev + first);
+    HIP_CHECK(hipGetLastError());
+    return 1;
+}
+
+}  // namespace
+
+int launch_small_iterations_many(const SmallIterTask *tasks, int ntasks, SmallTaskBuf &buf, hipStream_t s) {
+    int first[7];
+    const int total = stage_tasks(tasks, ntasks, buf, first, [](const SmallIterTask &t) { return t.count > 0; });
+    if (total == 0) return 0;
+    buf.send(sizeof(SmallIterTask) * static_cast<size_t>(total), s);
+    const SmallIterTask *d = static_cast<const SmallIterTask *>(buf.dev);
+    return launch_iterations_many_kr<4, 1>(d, first[0], first[1] - first[0], s) + launch_iterations_many_kr<4, 2>(d, first[1], first[2] - first[1], s) +
+           launch_iterations_many_kr<8, 1>(d, first[2], first[3] - first[2], s) + launch_iterations_many_kr<8, 2>(d, first[3], first[4] - first[3], s) +
+           launch_iterations_many_kr<12, 1>(d, first[4], first[5] - first[4], s) + launch_iterations_many_kr<12, 2>(d, first[5], first[6] - first[5], s);
+}
+
+int launch_small_power_many(const SmallPowerTask *tasks, int ntasks, SmallTaskBuf &buf, hipStream_t s) {
+    int first[7];
+    const int total = stage_tasks(tasks, ntasks, buf, first, [](const SmallPowerTask &) { return true; });
+    if (total == 0) return 0;
+    buf.send(sizeof(SmallPowerTask) * static_cast<size_t>(total), s);
+    const SmallPowerTask *d = static_cast<const SmallPowerTask *>(buf.dev);
+    return launch_power_many_kr<4, 1>(d, first[0], first[1] - first[0], s) + launch_power_many_kr<4, 2>(d, first[1], first[2] - first[1], s) +
+           launch_power_many_kr<8, 1>(d, first[2], first[3] - first[2], s) + launch_power_many_kr<8, 2>(d, first[3], first[4] - first[3], s) +
+           launch_power_many_kr<12, 1>(d, first[4], first[5] - first[4], s) + launch_power_many_kr<12, 2>(d, first[5], first[6] - first[5], s);
 }
 
 // warm-up (abi.cpp: hprlp_warmup): an attribute query makes the runtime load this translation unit's code object now instead

@@ -1185,14 +1185,22 @@ void Solver::verify_exchange() {
     }
 }
 
-void Solver::fetch_scalars() {
+void Solver::fetch_enqueue() {
     const auto t0 = time_now();
     HIP_CHECK(hipMemcpyAsync(scal_h.p, scal.p, kNumScalars * sizeof(double), hipMemcpyDeviceToHost, stream));
+    fetch_enqueue_s += time_since(t0);
+}
+
+void Solver::fetch_wait() {
     const auto t1 = time_now();
     HIP_CHECK(hipStreamSynchronize(stream));
-    fetch_enqueue_s += std::chrono::duration<double>(t1 - t0).count();
     fetch_wait_s += time_since(t1);
     ++fetches;
+}
+
+void Solver::fetch_scalars() {
+    fetch_enqueue();
+    fetch_wait();
 }
 
 static void allreduce_slots(Solver *s, int first, int count) {
@@ -1351,11 +1359,17 @@ void Solver::scale() {
 // A^T q in gsn, z in sm1; the dots ride on the second SpMV's epilogue and stay on the device; the
 // host reads back only at the every-10th-iteration convergence check.
 // ------------------------------------------------------------------------------------------------
-double Solver::power_iteration(int max_iter, double tol, int *iters) {
-    finish_tiling();
-    invalidate_far();
-    const auto t0 = time_now();
-    double *q = gsm.p + row_off, *ATq = gsn.p + col_off, *z = sm1.p;
+SmallArgs Solver::small_args() const {
+    return SmallArgs{m, n, A.view.nnz, A.view.rowptr, AT.view.rowptr, AT.view.val, small_ij.p, small_posA.p,
+                     small_order_x.p, small_order_y.p, x.p, x_hat, y, l.p, u.p, c.p, last_x.p, AL.p, AU.p, last_y.p, ctrl.p};
+}
+
+bool Solver::small_power_wanted() const {
+    const bool no_small_power = env_get("HPRLP_NO_SMALL_POWER") != nullptr;  // tests: the regular kernels instead
+    return use_small && !comm && !no_small_power;
+}
+
+void Solver::power_start(double *z) {
     // large vectors in the caller's numbering are filled on the device (last-place differences from the host's libm are
     // possible there; below the threshold the start vector is the oracle's bit for bit)
     const bool host_start = env_get("HPRLP_HOST_POWER_START") != nullptr;  // (tests)
@@ -1372,12 +1386,18 @@ double Solver::power_iteration(int max_iter, double tol, int *iters) {
         HIP_CHECK(hipMemcpyAsync(z, z0.data(), sizeof(double) * m_loc, hipMemcpyHostToDevice, stream));
         HIP_CHECK(hipStreamSynchronize(stream));
     }
-    const bool no_small_power = env_get("HPRLP_NO_SMALL_POWER") != nullptr;  // tests: the regular kernels instead
-    if (use_small && !comm && !no_small_power) {
+}
+
+double Solver::power_iteration(int max_iter, double tol, int *iters) {
+    finish_tiling();
+    invalidate_far();
+    const auto t0 = time_now();
+    double *q = gsm.p + row_off, *ATq = gsn.p + col_off, *z = sm1.p;
+    power_start(z);
+    if (small_power_wanted()) {
         // Netlib-scale LP: the whole power iteration in one launch of the single-workgroup kernel (small.hip), stopping test on
         // the device; the host waits once
-        const SmallArgs a{m, n, A.view.nnz, A.view.rowptr, AT.view.rowptr, AT.view.val, small_ij.p, small_posA.p,
-                          small_order_x.p, small_order_y.p, x.p, x_hat, y, l.p, u.p, c.p, last_x.p, AL.p, AU.p, last_y.p, ctrl.p};
+        const SmallArgs a = small_args();
         HIP_CHECK(hipMemsetAsync(scal.p + S_SMALL_PW_LAMBDA, 0, 2 * sizeof(double), stream));
         launch_small_power(a, z, max_iter, tol, scal.p + S_SMALL_PW_LAMBDA, stream);
         fetch_scalars();
@@ -1697,9 +1717,7 @@ void Solver::run_normal(int count) {
     finish_tiling();
     if (use_small && !comm) {
         // Netlib-scale LP: all `count` iterations in one single-workgroup launch, matrices in registers (small.hip)
-        const SmallArgs a{m, n, A.view.nnz, A.view.rowptr, AT.view.rowptr, AT.view.val, small_ij.p, small_posA.p,
-                          small_order_x.p, small_order_y.p, x.p, x_hat, y, l.p, u.p, c.p, last_x.p, AL.p, AU.p, last_y.p, ctrl.p};
-        launch_small_iterations(a, count, stream);
+        launch_small_iterations(small_args(), count, stream);
         return;
     }
     if (!use_graph) {
@@ -1743,6 +1761,12 @@ static double weighted_norm_from(Solver *s, double dot_adx_dy, double dy2, doubl
 }
 
 void Solver::compute_residuals(int iter, bool compute_gap, Residuals *r, RestartState *rs, bool *ray) {
+    residuals_enqueue(iter, compute_gap, ray);
+    fetch_wait();
+    residuals_consume(iter, compute_gap, r, rs);
+}
+
+void Solver::residuals_enqueue(int iter, bool compute_gap, bool *ray) {
     invalidate_far();  // the residual SpMVs refill the remainder buffers for x_bar / y_bar
     finish_tiling();
     const int gx = AT.view.grid(), gyy = A.view.grid();
@@ -1764,8 +1788,10 @@ void Solver::compute_residuals(int iter, bool compute_gap, Residuals *r, Restart
     allreduce_slots(this, S_CX, 8);
     if (iter == 0) allreduce_slots(this, S_LU2, 1);
     if (ray) *ray = ray_test();  // (its scalars ride on the fetch below)
-    fetch_scalars();
+    fetch_enqueue();
+}
 
+void Solver::residuals_consume(int iter, bool compute_gap, Residuals *r, RestartState *rs) {
     assemble_residuals(r, {scal_h[S_CX], scal_h[S_YOBJ_Y], scal_h[S_XZ], scal_h[S_RD2], scal_h[S_RP2], scal_h[S_LU2]},
                        {b_scale, c_scale, norm_b_org, norm_c_org, obj_constant}, iter == 0);
     r->kkt = std::max(std::max(r->err_Rd, r->err_Rp), r->rel_gap);  // (batched.hip nests the max() the other way, as the reference)
@@ -1820,106 +1846,139 @@ static int next_event(int iter, int check_iter, int max_iter) {
     }
 }
 
-void Solver::solve_loop(HPRLP_results *out) {
-    const auto t_loop = time_now();
+void Solver::loop_begin(LoopState *ls, HPRLP_results *out) {
+    *ls = LoopState();
+    ls->t_loop = time_now();
     // reported `time` includes the power iteration (HPRLP.cu:150); a re-solve ran none and counts its set_data instead
-    const double t_before = time_base >= 0.0 ? time_base : power_time;
+    ls->t_before = time_base >= 0.0 ? time_base : power_time;
     data_since_run = 0.0;
-    Residuals r;
-    RestartState rs;
-    rs.best_sigma = sigma;
-    bool first4 = true, first6 = true, first8 = true;
-    const int check_iter = std::max(prm.check_iter, 1);
-    const int max_iter = std::max(prm.max_iter, 0);
+    ls->rs.best_sigma = sigma;
+    ls->check_iter = std::max(prm.check_iter, 1);
+    ls->max_iter = std::max(prm.max_iter, 0);
+    ls->out = out;
     *out = HPRLP_results();
-    std::string status = "CONTINUE";
     trace_n = 0;
     cert = Certificate();
     if (detect.on) ray_begin();
-    if (verbose)
-        std::cout << " iter     errRp        errRd         p_obj            d_obj          gap         sigma       time\n"
-                  << std::flush;
-    int iter = 0;
-    while (true) {
-        const bool at_limit = iter >= max_iter;
-        const bool periodic = (iter % check_iter == 0);
-        bool ray = false;
-        compute_residuals(iter, periodic && iter > 0, &r, &rs, detect.on && periodic && iter > 0 ? &ray : nullptr);
-        const int verdict = ray ? ray_scalars().verdict(detect) : 0;
-        const double elapsed = t_before + time_since(t_loop);
-        bool timed_out = elapsed > prm.time_limit;  // (strict here, >= in batched.hip, as in the reference)
-        if (comm && comm->size > 1) {
-            // the residuals are all-reduced, the clocks are not: every rank must take the same TIME_LIMIT decision, or
-            // one leaves the loop while its peers enter the next exchange (a collective hang).  Any rank over its limit
-            // stops the whole group at this event.
-            const double flag = timed_out ? 1.0 : 0.0;
-            HIP_CHECK(hipMemcpyAsync(scal.p + S_TMP1, &flag, sizeof(double), hipMemcpyHostToDevice, stream));
-            allreduce_slots(this, S_TMP1, 1);
-            fetch_scalars();
-            timed_out = scal_h[S_TMP1] > 0.0;
-        }
-        if (r.kkt < prm.stop_tol) status = "OPTIMAL";  // (strict here, <= in batched.hip, as in the reference)
-        else if (verdict == 1) status = "PRIMAL_INFEASIBLE";
-        else if (verdict == 2) status = "DUAL_INFEASIBLE";
-        else if (at_limit) status = "ITER_LIMIT";
-        else if (timed_out) status = "TIME_LIMIT";
-        if (periodic && !at_limit) check_restart(rs, iter, check_iter, sigma, verbose);
-        else rs.flag = 0;
-        if (trace && trace_n < trace_cap)
-            trace[trace_n++] = TraceRow{iter, rs.flag, r.err_Rp, r.err_Rd, r.primal_obj, r.dual_obj, r.rel_gap, r.kkt,
-                                        sigma, rs.current_gap, lambda_max};
-        if (verbose) {
-            std::cout << std::setw(5) << iter << "    " << std::scientific << std::setprecision(2) << r.err_Rp << "    "
-                      << r.err_Rd << "    " << std::setprecision(6) << std::showpos << r.primal_obj << "    "
-                      << r.dual_obj << "    " << std::setprecision(2) << std::noshowpos << r.rel_gap << "    " << sigma
-                      << "      " << std::fixed << std::setprecision(2) << elapsed << "\n" << std::defaultfloat
-                      << std::flush;
-        }
-        auto mark = [&](bool &first, double thr, int &it_out, double &t_out, const char *label) {
-            if (first && r.kkt < thr) {
-                it_out = iter;
-                t_out = elapsed;
-                first = false;
-                if (verbose) std::cout << "Residual < " << label << " at iter = " << iter << "\n" << std::flush;
-            }
-        };
-        mark(first4, 1e-4, out->iter4, out->time4, "1e-4");
-        mark(first6, 1e-6, out->iter6, out->time6, "1e-6");
-        mark(first8, 1e-8, out->iter8, out->time8, "1e-8");
-        if (status != "CONTINUE") {
-            if (verdict && status != "OPTIMAL") collect_certificate(verdict, iter);
-            break;
-        }
+}
 
-        const int flag = rs.flag;
-        update_sigma_and_restart(&rs, r);
-        const int next = next_event(iter, check_iter, max_iter);
-        int it = iter;
-        if (flag > 0) {
-            step(true);
-            rs.last_gap = weighted_norm_after_restart();
-            ++it;
-        }
-        if (it < next) run_normal_then_check(next - 1 - it);
-        rs.inner += next - iter;
-        iter = next;
+void Solver::loop_enqueue_evaluation(LoopState *ls) {
+    ls->at_limit = ls->iter >= ls->max_iter;
+    ls->periodic = (ls->iter % ls->check_iter == 0);
+    ls->ray = false;
+    residuals_enqueue(ls->iter, ls->periodic && ls->iter > 0, detect.on && ls->periodic && ls->iter > 0 ? &ls->ray : nullptr);
+}
+
+bool Solver::loop_decide(LoopState *ls) {
+    const int iter = ls->iter, check_iter = ls->check_iter, max_iter = ls->max_iter;
+    const bool at_limit = ls->at_limit, periodic = ls->periodic;
+    Residuals &r = ls->r;
+    RestartState &rs = ls->rs;
+    HPRLP_results *out = ls->out;
+    std::string &status = ls->status;
+    residuals_consume(iter, periodic && iter > 0, &r, &rs);
+    const int verdict = ls->ray ? ray_scalars().verdict(detect) : 0;
+    const double elapsed = ls->t_before + time_since(ls->t_loop);
+    bool timed_out = elapsed > prm.time_limit;  // (strict here, >= in batched.hip, as in the reference)
+    if (comm && comm->size > 1) {
+        // the residuals are all-reduced, the clocks are not: every rank must take the same TIME_LIMIT decision, or
+        // one leaves the loop while its peers enter the next exchange (a collective hang).  Any rank over its limit
+        // stops the whole group at this event.
+        const double flag = timed_out ? 1.0 : 0.0;
+        HIP_CHECK(hipMemcpyAsync(scal.p + S_TMP1, &flag, sizeof(double), hipMemcpyHostToDevice, stream));
+        allreduce_slots(this, S_TMP1, 1);
+        fetch_scalars();
+        timed_out = scal_h[S_TMP1] > 0.0;
     }
-    if (env_get("HPRLP_TIMING"))
-        std::cerr << "[timing] loop: " << time_since(t_loop) << " s, " << iter << " iterations; " << fetches << " scalar fetches: enqueue "
-                  << fetch_enqueue_s << " s, wait " << fetch_wait_s << " s" << std::endl;
-    std::strncpy(out->status, status.c_str(), sizeof(out->status) - 1);
+    if (r.kkt < prm.stop_tol) status = "OPTIMAL";  // (strict here, <= in batched.hip, as in the reference)
+    else if (verdict == 1) status = "PRIMAL_INFEASIBLE";
+    else if (verdict == 2) status = "DUAL_INFEASIBLE";
+    else if (at_limit) status = "ITER_LIMIT";
+    else if (timed_out) status = "TIME_LIMIT";
+    if (periodic && !at_limit) check_restart(rs, iter, check_iter, sigma, verbose);
+    else rs.flag = 0;
+    if (trace && trace_n < trace_cap)
+        trace[trace_n++] = TraceRow{iter, rs.flag, r.err_Rp, r.err_Rd, r.primal_obj, r.dual_obj, r.rel_gap, r.kkt,
+                                    sigma, rs.current_gap, lambda_max};
+    if (verbose) {
+        std::cout << std::setw(5) << iter << "    " << std::scientific << std::setprecision(2) << r.err_Rp << "    "
+                  << r.err_Rd << "    " << std::setprecision(6) << std::showpos << r.primal_obj << "    "
+                  << r.dual_obj << "    " << std::setprecision(2) << std::noshowpos << r.rel_gap << "    " << sigma
+                  << "      " << std::fixed << std::setprecision(2) << elapsed << "\n" << std::defaultfloat
+                  << std::flush;
+    }
+    auto mark = [&](bool &first, double thr, int &it_out, double &t_out, const char *label) {
+        if (first && r.kkt < thr) {
+            it_out = iter;
+            t_out = elapsed;
+            first = false;
+            if (verbose) std::cout << "Residual < " << label << " at iter = " << iter << "\n" << std::flush;
+        }
+    };
+    mark(ls->first4, 1e-4, out->iter4, out->time4, "1e-4");
+    mark(ls->first6, 1e-6, out->iter6, out->time6, "1e-6");
+    mark(ls->first8, 1e-8, out->iter8, out->time8, "1e-8");
+    if (status != "CONTINUE") {
+        if (verdict && status != "OPTIMAL") collect_certificate(verdict, iter);
+        return false;
+    }
+
+    const int flag = rs.flag;
+    update_sigma_and_restart(&rs, r);
+    const int next = next_event(iter, check_iter, max_iter);
+    int it = iter;
+    ls->restarted = flag > 0;
+    if (flag > 0) {
+        step(true);
+        rs.last_gap = weighted_norm_after_restart();
+        ++it;
+    }
+    ls->pending = it < next ? next - 1 - it : -1;
+    rs.inner += next - iter;
+    ls->iter = next;
+    return true;
+}
+
+bool Solver::loop_event(LoopState *ls) {
+    loop_enqueue_evaluation(ls);
+    fetch_wait();
+    return loop_decide(ls);
+}
+
+void Solver::loop_advance(LoopState *ls, bool normal_done) {
+    if (ls->pending < 0) return;
+    if (normal_done) step(true);
+    else run_normal_then_check(ls->pending);
+}
+
+void Solver::loop_finish(LoopState *ls) {
+    HPRLP_results *out = ls->out;
+    std::strncpy(out->status, ls->status.c_str(), sizeof(out->status) - 1);
     out->status[sizeof(out->status) - 1] = '\0';
-    out->iter = iter;
-    out->gap = r.rel_gap;
-    out->residuals = r.kkt;
-    out->primal_obj = r.primal_obj;
-    out->time = t_before + time_since(t_loop);
+    out->iter = ls->iter;
+    out->gap = ls->r.rel_gap;
+    out->residuals = ls->r.kkt;
+    out->primal_obj = ls->r.primal_obj;
+    out->time = ls->t_before + time_since(ls->t_loop);
     if (out->time4 == 0.0) out->time4 = out->time;
     if (out->time6 == 0.0) out->time6 = out->time;
     if (out->time8 == 0.0) out->time8 = out->time;
     if (out->iter4 == 0) out->iter4 = out->iter;
     if (out->iter6 == 0) out->iter6 = out->iter;
     if (out->iter8 == 0) out->iter8 = out->iter;
+}
+
+void Solver::solve_loop(HPRLP_results *out) {
+    LoopState ls;
+    loop_begin(&ls, out);
+    if (verbose)
+        std::cout << " iter     errRp        errRd         p_obj            d_obj          gap         sigma       time\n"
+                  << std::flush;
+    while (loop_event(&ls)) loop_advance(&ls);
+    if (env_get("HPRLP_TIMING"))
+        std::cerr << "[timing] loop: " << time_since(ls.t_loop) << " s, " << ls.iter << " iterations; " << fetches << " scalar fetches: enqueue "
+                  << fetch_enqueue_s << " s, wait " << fetch_wait_s << " s" << std::endl;
+    loop_finish(&ls);
 }
 
 void Solver::collect_solution(HPRLP_results *out) {

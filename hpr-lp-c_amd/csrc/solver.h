@@ -95,6 +95,24 @@ struct HaloPlan {
     void build(Comm *comm, const int *cols, long nnz, int total, int chunk, hipStream_t s);
 };
 
+// What Solver::solve_loop keeps between two events (an event: evaluation, decision, restart).  The loop is
+//   loop_begin; while (loop_event) loop_advance; loop_finish
+// and a group of solvers advanced in lock-step (many.cpp) runs the same pieces member by member around shared launches and waits.
+struct LoopState {
+    int iter = 0;
+    Residuals r;
+    RestartState rs;
+    bool first4 = true, first6 = true, first8 = true;
+    std::string status = "CONTINUE";
+    int pending = -1;        // normal iterations before the next check step (loop_advance); < 0: no check step either
+    bool restarted = false;  // the last event restarted (its check step and weighted norm have run)
+    bool periodic = false, at_limit = false, ray = false;  // of the evaluation in flight
+    int check_iter = 1, max_iter = 0;
+    double t_before = 0.0;   // what the reported times start from
+    clock_type::time_point t_loop;
+    HPRLP_results *out = nullptr;
+};
+
 struct Solver {
     HPRLP_parameters prm;
     int m = 0, n = 0;          // global sizes
@@ -218,12 +236,30 @@ struct Solver {
     void step(bool check);                                          // one HPR iteration
     void run_normal(int count);                                     // count normal iterations (graph replay)
     void run_normal_then_check(int count);                          // count normal iterations, then one check-variant iteration
-    void fetch_scalars();
+    void fetch_scalars();                                           // fetch_enqueue + fetch_wait
+    void fetch_enqueue();                                           // the asynchronous copy of the scalars, no wait
+    void fetch_wait();                                              // the wait for the stream
     // main_iterate.cu:229-309; ray: also the infeasibility detection's ray test (detect.on only), read by ray_verdict()
     void compute_residuals(int iter, bool compute_gap, Residuals *r, RestartState *rs, bool *ray = nullptr);
+    // its two halves: everything up to and including the asynchronous copy of the scalars / what follows the wait for the stream
+    void residuals_enqueue(int iter, bool compute_gap, bool *ray);
+    void residuals_consume(int iter, bool compute_gap, Residuals *r, RestartState *rs);
     double weighted_norm_after_restart();                           // main_iterate.cu:486-515
     void update_sigma_and_restart(RestartState *rs, const Residuals &r);  // main_iterate.cu:312-322,367-404
     void solve_loop(HPRLP_results *out);                            // src/HPRLP.cu:154-310
+    // the pieces of solve_loop (LoopState)
+    void loop_begin(LoopState *ls, HPRLP_results *out);
+    void loop_enqueue_evaluation(LoopState *ls);  // first half of an event: the evaluation of the current iterate, not waited for
+    // second half, after the wait: status, marks, restart decision, sigma update, a restart's own check step and weighted norm.
+    // false: finished (ls->status says how); true: ls->restarted and ls->pending say what runs next
+    bool loop_decide(LoopState *ls);
+    bool loop_event(LoopState *ls);               // loop_enqueue_evaluation, wait, loop_decide
+    // what run_normal_then_check does for ls->pending; normal_done: the normal iterations have been run by a group launch
+    void loop_advance(LoopState *ls, bool normal_done = false);
+    void loop_finish(LoopState *ls);              // the results' scalars
+    SmallArgs small_args() const;                 // the single-workgroup kernels' view of this LP (use_small)
+    bool small_power_wanted() const;              // the power iteration runs in the single-workgroup kernel
+    void power_start(double *z);                  // the power iteration's start vector (m_loc), in place on return
     void collect_solution(HPRLP_results *out);                      // src/utils.cu:143-200
     double reduce_sum_sq(const double *v, int n_local);             // allreduced ||v||^2
     void verify_exchange();                                         // set-up self-test of the exchange (multi-GPU only)

@@ -170,6 +170,11 @@ def lib():
                                        C.c_int, c_int_p]
     L.hprlp_solver_data_seconds.argtypes = [C.c_void_p, c_dbl_p]
     L.hprlp_presolve_forward.argtypes = [C.c_void_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]
+    L.hprlp_solver_power_iteration_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_double, c_dbl_p, c_int_p]
+    L.hprlp_solver_iterate_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, c_int_p, C.c_int]
+    L.hprlp_solver_run_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(CResults)]
+    L.hprlp_solve_many.argtypes = [C.POINTER(C.POINTER(CLPInfo)), C.c_int, C.POINTER(CParameters), C.POINTER(CResults)]
+    L.hprlp_last_solve_many_phases.argtypes = [c_dbl_p]
     _lib = L
     return L
 
@@ -469,6 +474,29 @@ def solve(A, AL, AU, l, u, c, param=None):
         return model.solve(param)
     finally:
         model.free()
+
+
+def solve_many(models, param=None):
+    """Many independent LPs at once (hprlp_solve_many): what Model.solve does without presolve (use_presolve is ignored), with
+    the power iterations and the loops of all models advanced together -- Netlib-scale models share their launches, one
+    workgroup each.  Returns a list of Results; a model that failed its set-up has status "ERROR"."""
+    models = list(models)
+    if not models:
+        raise ValueError("solve_many: no models")
+    cp = (param or Parameters()).to_c()
+    ptrs = (C.POINTER(CLPInfo) * len(models))(*[mod._ptr for mod in models])
+    res = (CResults * len(models))()
+    if lib().hprlp_solve_many(ptrs, len(models), C.byref(cp), res) < 0:
+        raise RuntimeError(last_error())
+    return [Results(res[k], mod.m, mod.n) for k, mod in enumerate(models)]
+
+
+def last_solve_many_phases():
+    """Phases of this thread's last solve_many (hprlp_last_solve_many_phases): seconds, then the loop's counts."""
+    out = np.zeros(8)
+    lib().hprlp_last_solve_many_phases(out.ctypes.data_as(c_dbl_p))
+    keys = ("setup", "scaling", "power", "loop", "call", "rounds", "waits", "launches")
+    return dict(zip(keys, [float(v) for v in out]))
 
 
 def solve_batched(model, Cmat, AL, AU, l, u, obj_constants=None, param=None):
@@ -834,6 +862,44 @@ class Solver:
         r = Results(res, getattr(self, "m_loc", self.model.m), getattr(self, "n_loc", self.model.n))
         r.trace = [{f: getattr(trace[i], f) for f, _ in CTraceRow._fields_} for i in range(nt.value)]
         return r
+
+    @staticmethod
+    def _handles(solvers):
+        solvers = list(solvers)
+        return solvers, (C.c_void_p * max(len(solvers), 1))(*[sv.h for sv in solvers])
+
+    @staticmethod
+    def power_iteration_many(solvers, max_iter=5000, tol=1e-4):
+        """power_iteration() of every solver, small-path members in one launch per kernel class
+        (hprlp_solver_power_iteration_many).  Returns [(lambda, iterations), ...]."""
+        solvers, hs = Solver._handles(solvers)
+        lam = np.zeros(max(len(solvers), 1))
+        its = np.zeros(max(len(solvers), 1), dtype=np.int32)
+        if lib().hprlp_solver_power_iteration_many(hs, len(solvers), int(max_iter), float(tol), lam.ctypes.data_as(c_dbl_p),
+                                                   its.ctypes.data_as(c_int_p)) < 0:
+            raise RuntimeError(last_error())
+        return [(float(lam[k]), int(its[k])) for k in range(len(solvers))]
+
+    @staticmethod
+    def iterate_many(solvers, normals, then_check=False):
+        """iterate(normals[k], then_check) of every solver, the normal iterations of small-path members in one launch per
+        kernel class (hprlp_solver_iterate_many)."""
+        solvers, hs = Solver._handles(solvers)
+        cnt = _as(normals, np.int32)
+        if cnt.ndim != 1 or cnt.shape[0] != len(solvers):
+            raise ValueError("iterate_many: one iteration count per solver")
+        if lib().hprlp_solver_iterate_many(hs, len(solvers), cnt.ctypes.data_as(c_int_p), int(bool(then_check))) < 0:
+            raise RuntimeError(last_error())
+
+    @staticmethod
+    def run_many(solvers):
+        """run() of every solver in lock-step, from its current state (hprlp_solver_run_many).  Returns a list of Results (no
+        trace); certificates come from certificate() of each solver."""
+        solvers, hs = Solver._handles(solvers)
+        res = (CResults * max(len(solvers), 1))()
+        if lib().hprlp_solver_run_many(hs, len(solvers), res) < 0:
+            raise RuntimeError(last_error())
+        return [Results(res[k], sv.model.m, sv.model.n) for k, sv in enumerate(solvers)]
 
     def set_detection(self, eps_primal=1e-8, eps_dual=1e-8, on=True):
         """Infeasibility detection for the following run() calls (hprlp_solver_set_detection); on=False switches it off."""

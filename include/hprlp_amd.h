@@ -170,6 +170,33 @@ int hprlp_solver_resolve(hprlp_solver *s, double sigma, const double *x0, const 
 /* seconds of the last set_data: {upload, kernels + fetch, total} */
 int hprlp_solver_data_seconds(hprlp_solver *s, double out[3]);
 
+/* ---- many small LPs at once (one GPU; DESIGN.md "Many small LPs") --------------------------------------------------------------
+ * A Netlib-scale LP (nnz < 12288, m, n <= 2048, rows and columns of at most 256 entries) runs as ONE workgroup and occupies one
+ * compute unit of 256.  These entry points advance a group of independent solvers -- each with its own matrix -- in lock-step:
+ * the normal iterations and the power iterations of all small-path members go in one launch per kernel class (workgroup b =
+ * member b), and one host wait serves the evaluations of all members.  Check step, evaluation, stopping test, restart rule, sigma
+ * update and detection stay the member's own, so every member gets the bits it gets alone.  Members off the small path are legal
+ * (they run their own kernels inside the same lock-step).  The group runs quietly (hprlp_solver_set_verbose is ignored).
+ * All four return 0, or -1 + hprlp_last_error(); nothing is launched when the arguments are wrong: a NULL pointer, count <= 0,
+ * the same handle twice, a sharded solver (hprlp_solver_create_dist* / _local*), a solver that was never scaled, members on
+ * different devices, a negative normal[k]. */
+/* hprlp_solver_power_iteration for every member: lambda_out[k] (lambda, not lambda x 1.01), iters_out[k] (may be NULL) */
+int hprlp_solver_power_iteration_many(hprlp_solver **s, int count, int max_iter, double tol, double *lambda_out, int *iters_out);
+/* hprlp_solver_iterate for every member: normal[k] normal iterations of member k, then one check step each if then_check */
+int hprlp_solver_iterate_many(hprlp_solver **s, int count, const int *normal, int then_check);
+/* hprlp_solver_run for every member, from its current state (detection, a start, changed data are honoured): out[k] as
+ * hprlp_solver_run fills it (x, y, z malloc'd), no trace; certificates from hprlp_solver_get_certificate member by member.  A
+ * finished member drops out, the call returns with the last one.  out[k].time = the member's power-iteration (or set_data) time
+ * + the group loop's wall time up to the member's last event; time_limit applies to that value. */
+int hprlp_solver_run_many(hprlp_solver **s, int count, HPRLP_results *out);
+/* What HPRLP_main_solve does, for `count` models at once: set-up and scaling member by member, the power iterations together
+ * (lambda x 1.01), the loop together, solutions, teardown.  NO presolve on this path: param->use_presolve is ignored, as in
+ * solve_batched.  A model that fails its set-up gets status "ERROR" (and hprlp_last_error() names it); the others are solved. */
+int hprlp_solve_many(const LP_info_cpu *const *models, int count, const HPRLP_parameters *param, HPRLP_results *out);
+/* Wall-clock phases [s] of the calling thread's last hprlp_solve_many: out = {set-up (sum over the members), scaling (sum), power
+ * iterations + init, loop + solutions' way back, whole call (teardown included), evaluation rounds, host waits, group launches} */
+int hprlp_last_solve_many_phases(double out[8]);
+
 /* Named device vectors: x y x_hat x_bar y_bar z_bar x_temp y_temp y_obj last_x last_y AL AU l u c
  * row_norm col_norm A_val AT_val.  get returns the length (or -1); cap is the capacity of out. */
 long hprlp_solver_get_vector(hprlp_solver *s, const char *name, double *out, long cap);
