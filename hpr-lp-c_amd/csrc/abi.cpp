@@ -10,6 +10,8 @@
 #include <iostream>
 
 #include "hprlp_amd.h"
+#include "batch_prep.h"
+#include "batched.h"
 #include "env.h"
 #include "dist.h"
 #include "presolve.h"
@@ -1292,6 +1294,52 @@ extern "C" int hprlp_row_block_plan(int m, int n, const int *rowptr, const int *
     try {
         if (m <= 0 || n <= 0 || !rowptr || !col || !out) throw std::runtime_error("bad arguments");
         row_block_plan_host(m, n, rowptr, col, with_cuts != 0, out);
+        return 0;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+// Host only: what solve_batched does to a batch's vectors before anything is uploaded (batch_prep.h), on plain arrays
+extern "C" int hprlp_batched_prepare_host(int m, int n, int B, const double *rn, const double *cn, const double *C, const double *AL,
+                                          const double *AU, const double *l, const double *u, const double *X0, const double *Y0,
+                                          int use_bc_scaling, hprlp_batched_prepared *out) {
+    try {
+        if (m <= 0 || n <= 0 || B <= 0 || !rn || !cn || !C || !AL || !AU || !l || !u || !out) throw std::runtime_error("bad arguments");
+        const BatchData d = prepare_batch(m, n, B, C, AL, AU, l, u, nullptr, 0.0, rn, cn, use_bc_scaling != 0);
+        const size_t nB = static_cast<size_t>(n) * B, mB = static_cast<size_t>(m) * B;
+        auto give = [](const std::vector<double> &v, double *dst) {
+            if (dst) std::copy(v.begin(), v.end(), dst);
+        };
+        give(d.C, out->C); give(d.AL, out->AL); give(d.AU, out->AU); give(d.L, out->l); give(d.U, out->u);
+        const std::vector<double> *scalars[7] = {&d.b_scale, &d.c_scale, &d.norm_b, &d.norm_c, &d.norm_b_org, &d.norm_c_org, &d.sigma};
+        for (int i = 0; i < 7 && out->scalars; ++i) give(*scalars[i], out->scalars + static_cast<size_t>(i) * B);
+        // a start into scaled units, and from there back as a solution goes
+        auto there_and_back = [B](const double *v0, size_t len, int rows, const double *norm, const std::vector<double> &scale,
+                                  double *scaled, double *back) {
+            if (!v0) return;
+            std::vector<double> v(v0, v0 + len);
+            start_to_scaled(v.data(), rows, B, norm, scale);
+            if (scaled) std::copy(v.begin(), v.end(), scaled);
+            point_to_caller(v.data(), rows, B, norm, scale);
+            if (back) std::copy(v.begin(), v.end(), back);
+        };
+        there_and_back(X0, nB, n, cn, d.b_scale, out->X0, out->X_back);
+        there_and_back(Y0, mB, m, rn, d.c_scale, out->Y0, out->Y_back);
+        if (out->z_back) {  // z = (Z * cn) * c_scale of the scaled C
+            give(d.C, out->z_back);
+            reduced_cost_to_caller(out->z_back, n, B, cn, d.c_scale);
+        }
+        out->Bp = padded_batch(B);
+        out->Bc = choose_chunk(m, n, out->Bp);
+        const Geo geo = make_geo(out->Bp, out->Bc);
+        std::vector<double> panel;
+        to_panel(d.C, n, B, geo, out->pad, panel);
+        give(panel, out->panel);
+        if (out->panel_back) from_panel(panel, n, B, geo, out->panel_back);
+        for (int k = 0; k < B && out->panel_index; ++k)
+            for (int i = 0; i < n; ++i) out->panel_index[static_cast<size_t>(k) * n + i] = static_cast<long>(panel_index(geo, n, i, k));
         return 0;
     } catch (const std::exception &e) {
         set_last_error(e.what());

@@ -1,0 +1,157 @@
+// batch_prep.cpp -- see batch_prep.h.  Host only.  The order of the multiplications and divisions below is part of the result:
+// (v * cn) / b_scale is not v * (cn / b_scale), and tests/test_batch_prep.py holds every one of them to its bits.
+#include "batch_prep.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+#include <stdexcept>
+
+#include "HPRLP.h"
+#include "env.h"
+
+namespace hprlp {
+
+HPRLP_batched_results make_batched_error(const char *status, int m, int n, int B) {
+    HPRLP_batched_results r;
+    r.m = m;
+    r.n = n;
+    r.batch_size = B;
+    if (B > 0) {
+        r.status = static_cast<char *>(std::calloc(static_cast<size_t>(B) * 64, sizeof(char)));
+        if (r.status)
+            for (int k = 0; k < B; ++k) std::strncpy(r.status + 64 * k, status, 63);
+    }
+    return r;
+}
+
+HPRLP_batched_results alloc_batched_results(int m, int n, int B) {
+    HPRLP_batched_results out;
+    out.m = m; out.n = n; out.batch_size = B;
+    out.x = static_cast<double *>(std::malloc(sizeof(double) * static_cast<size_t>(n) * B));
+    out.y = static_cast<double *>(std::malloc(sizeof(double) * static_cast<size_t>(m) * B));
+    out.z = static_cast<double *>(std::malloc(sizeof(double) * static_cast<size_t>(n) * B));
+    out.primal_obj = static_cast<double *>(std::malloc(sizeof(double) * B));
+    out.residuals = static_cast<double *>(std::malloc(sizeof(double) * B));
+    out.gap = static_cast<double *>(std::malloc(sizeof(double) * B));
+    out.iter = static_cast<int *>(std::malloc(sizeof(int) * B));
+    out.status = static_cast<char *>(std::calloc(static_cast<size_t>(B) * 64, sizeof(char)));
+    if (!out.x || !out.y || !out.z || !out.primal_obj || !out.residuals || !out.gap || !out.iter || !out.status) {
+        free_batched_results(&out);
+        throw std::runtime_error("host allocation of the batched results failed");
+    }
+    return out;
+}
+
+int padded_batch(int B) {
+    if (B <= 64) {
+        int p = 1;
+        while (p < B) p <<= 1;
+        return p;
+    }
+    return (B + 63) / 64 * 64;
+}
+
+int choose_chunk(int m, int n, int Bp) {
+    if (Bp < 64) return Bp;
+    if (const char *e = env_get("HPRLP_BATCH_CHUNK")) {
+        const int c = std::atoi(e);
+        if (c == 8 || c == 16 || c == 32 || c == 64) return c;
+    }
+    (void)m; (void)n;
+    return 64;
+}
+
+void to_panel(const std::vector<double> &cm, int rows, int B, const Geo &g, double pad, std::vector<double> &out) {
+    out.assign(static_cast<size_t>(rows) * g.Bp, pad);
+    for (int k = 0; k < B; ++k)
+        for (int i = 0; i < rows; ++i) out[panel_index(g, rows, i, k)] = cm[static_cast<size_t>(k) * rows + i];
+}
+
+void from_panel(const std::vector<double> &panel, int rows, int B, const Geo &g, double *cm) {
+    for (int k = 0; k < B; ++k)
+        for (int i = 0; i < rows; ++i) cm[static_cast<size_t>(k) * rows + i] = panel[panel_index(g, rows, i, k)];
+}
+
+namespace {
+
+double bound_norm_host(const double *AL, const double *AU, int m, size_t off) {  // :332-345
+    long double sum = 0.0;
+    for (int i = 0; i < m; ++i) {
+        const double lo = AL[off + i], hi = AU[off + i];
+        const double a = (std::isinf(lo) && lo < 0) ? 0.0 : std::abs(lo);
+        const double b = (std::isinf(hi) && hi > 0) ? 0.0 : std::abs(hi);
+        const double v = std::max(a, b);
+        sum += static_cast<long double>(v) * v;
+    }
+    return std::sqrt(static_cast<double>(sum));
+}
+double column_norm_host(const double *X, int n, size_t off) {  // :347-354
+    long double sum = 0.0;
+    for (int i = 0; i < n; ++i) sum += static_cast<long double>(X[off + i]) * X[off + i];
+    return std::sqrt(static_cast<double>(sum));
+}
+
+}  // namespace
+
+BatchData prepare_batch(int m, int n, int B, const double *C, const double *AL, const double *AU, const double *l, const double *u,
+                        const double *obj_constants, double model_obj_constant, const double *rn, const double *cn,
+                        bool use_bc_scaling) {
+    BatchData d;
+    d.m = m; d.n = n; d.B = B;
+    const size_t nB = static_cast<size_t>(n) * B, mB = static_cast<size_t>(m) * B;
+    d.C.assign(C, C + nB); d.AL.assign(AL, AL + mB); d.AU.assign(AU, AU + mB); d.L.assign(l, l + nB); d.U.assign(u, u + nB);
+    std::vector<double> &hC = d.C, &hAL = d.AL, &hAU = d.AU, &hL = d.L, &hU = d.U;
+    d.b_scale.assign(B, 1.0); d.c_scale.assign(B, 1.0); d.sigma.assign(B, 1.0);
+    for (std::vector<double> *p : {&d.norm_b, &d.norm_c, &d.norm_b_org, &d.norm_c_org, &d.objc}) p->assign(B, 0.0);
+    for (int k = 0; k < B; ++k) {
+        const size_t om = static_cast<size_t>(k) * m, on = static_cast<size_t>(k) * n;
+        d.norm_b_org[k] = 1.0 + bound_norm_host(hAL.data(), hAU.data(), m, om);
+        d.norm_c_org[k] = 1.0 + column_norm_host(hC.data(), n, on);
+        for (int i = 0; i < m; ++i) { hAL[om + i] /= rn[i]; hAU[om + i] /= rn[i]; }
+        for (int i = 0; i < n; ++i) { hC[on + i] /= cn[i]; hL[on + i] *= cn[i]; hU[on + i] *= cn[i]; }
+    }
+    if (use_bc_scaling) {
+        for (int k = 0; k < B; ++k) {
+            const size_t om = static_cast<size_t>(k) * m, on = static_cast<size_t>(k) * n;
+            d.b_scale[k] = 1.0 + bound_norm_host(hAL.data(), hAU.data(), m, om);
+            d.c_scale[k] = 1.0 + column_norm_host(hC.data(), n, on);
+            for (int i = 0; i < m; ++i) { hAL[om + i] /= d.b_scale[k]; hAU[om + i] /= d.b_scale[k]; }
+            for (int i = 0; i < n; ++i) { hC[on + i] /= d.c_scale[k]; hL[on + i] /= d.b_scale[k]; hU[on + i] /= d.b_scale[k]; }
+        }
+    }
+    for (int k = 0; k < B; ++k) {
+        const size_t om = static_cast<size_t>(k) * m, on = static_cast<size_t>(k) * n;
+        d.norm_b[k] = bound_norm_host(hAL.data(), hAU.data(), m, om);
+        d.norm_c[k] = column_norm_host(hC.data(), n, on);
+        for (int i = 0; i < m; ++i) {
+            if (std::isinf(hAL[om + i]) && hAL[om + i] < 0) hAL[om + i] = -kInfReplacement;
+            if (std::isinf(hAU[om + i]) && hAU[om + i] > 0) hAU[om + i] = kInfReplacement;
+        }
+        for (int i = 0; i < n; ++i) {
+            if (std::isinf(hL[on + i]) && hL[on + i] < 0) hL[on + i] = -kInfReplacement;
+            if (std::isinf(hU[on + i]) && hU[on + i] > 0) hU[on + i] = kInfReplacement;
+        }
+        d.objc[k] = obj_constants ? obj_constants[k] : model_obj_constant;
+        if (d.norm_b[k] > 1.0e-8 && d.norm_c[k] > 1.0e-8) d.sigma[k] = d.norm_b[k] / d.norm_c[k];
+    }
+    return d;
+}
+
+void start_to_scaled(double *v, int rows, int B, const double *norm, const std::vector<double> &scale) {
+    for (int k = 0; k < B; ++k)
+        for (int i = 0; i < rows; ++i) v[static_cast<size_t>(k) * rows + i] = (v[static_cast<size_t>(k) * rows + i] * norm[i]) / scale[k];
+}
+
+void point_to_caller(double *v, int rows, int B, const double *norm, const std::vector<double> &scale) {
+    for (int k = 0; k < B; ++k)
+        for (int i = 0; i < rows; ++i) v[static_cast<size_t>(k) * rows + i] = (v[static_cast<size_t>(k) * rows + i] / norm[i]) * scale[k];
+}
+
+void reduced_cost_to_caller(double *z, int n, int B, const double *cn, const std::vector<double> &c_scale) {
+    for (int k = 0; k < B; ++k)
+        for (int i = 0; i < n; ++i) z[static_cast<size_t>(k) * n + i] = (z[static_cast<size_t>(k) * n + i] * cn[i]) * c_scale[k];
+}
+
+}  // namespace hprlp

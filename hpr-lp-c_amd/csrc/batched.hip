@@ -25,13 +25,13 @@
 #include <type_traits>
 
 #include "HPRLP.h"
+#include "batch_prep.h"
+#include "batched.h"
 #include "env.h"
 #include "solver.h"
 
 namespace hprlp {
 namespace {
-
-constexpr double kInfReplacement = 1.0e100;  // reference batched_solver.cu:17
 
 enum BSlot : int {  // per-problem scalar slots, SC[slot*Bp + k]
     B_CX = 0, B_YOBJ_Y, B_XZ, B_RD2, B_RP2, B_ADX_DY, B_DY2, B_DX2, B_MOVE_X2, B_MOVE_Y2, B_LU2, B_NSLOT
@@ -47,20 +47,6 @@ struct BatchCtl {  // per-problem device scalars
     int *restart_flag;
 };
 
-// thread -> (row slot, problem): lane l of a wave handles sub-row l / Bw and problem chunk*Bw + l % Bw, Bw = Bc = the
-// chunk width; a 256-thread block covers 4 * (64/Bw) rows of one chunk.
-struct Geo {
-    int Bp, Bw, nchunk, rows_per_wave, rows_per_block;
-};
-inline Geo make_geo(int Bp, int Bc) {
-    Geo g;
-    g.Bp = Bp;
-    g.Bw = Bc;
-    g.nchunk = Bp / Bc;
-    g.rows_per_wave = 64 / g.Bw;
-    g.rows_per_block = 4 * g.rows_per_wave;
-    return g;
-}
 // which chunk / which block of rows a workgroup works on (1-D grids of nchunk * row blocks, chunk fastest)
 struct Blk {
     int chunk, rb, nrb;
@@ -773,24 +759,30 @@ __global__ void __launch_bounds__(1024) kb_finalize(const double *partials, int 
 }
 
 // ---- host side ----------------------------------------------------------------------------------
+// solve_batched_impl at the end of the file is the order of things; every kernel is launched by a named launcher.
 struct BatchWS {
-    int m = 0, n = 0, B = 0, Bp = 0;
+    // -- depends on the matrix only (and on the chunk geometry): ws_matrix_part
+    int m = 0, n = 0;
     Solver *shared = nullptr;  // scaled A, A^T, row_norm, col_norm
+    std::vector<double> rn, cn;  // ... and the host's copies of the two (fetched by solve_batched_impl)
+    hipStream_t stream = nullptr;
+    Geo geo{};
+    int gx = 1, gy = 1;  // row blocks of the n- / m-row launches with partials (the grid is geo.nchunk times that)
+    int grid_cap = 0;    // HPRLP_BATCH_GRID of this call: most row blocks of a normal half-step launch (0: as many as the rows need)
+    DBuf<int> order_x, order_y;  // launch order of the 4-row groups of A^T / A in kb_half64 (groups with long rows first)
+    // -- depends on this batch: ws_batch_part
+    int B = 0, Bp = 0;
+    const BatchData *data = nullptr;
     DBuf<double> C, AL, AU, L, U;
     DBuf<double> X, Xh, Xb, DX, Zb, lastX, Y, Yb, DY, Yobj, lastY;
     DBuf<double> sigma, SC, partials;
     DBuf<int> active, kx, ky, rflag;
-    DBuf<int> order_x, order_y;  // launch order of the 4-row groups of A^T / A in kb_half64 (groups with long rows first)
     // infeasibility detection (allocated only with it on): previous X_bar / Y_bar, the rays, the certificates' z, b/c scales
     DBuf<double> prevX, DS, prevY, YS, Zray, bsc, csc;
     int nslot = B_NSLOT;  // scalar slots per member (B_NSLOT_DETECT with detection on)
     HBuf<double> SC_h;
     BatchCtl ctl{};
     double lambda_max = 1.0;
-    int gx = 1, gy = 1;  // row blocks of the n- / m-row launches with partials (the grid is geo.nchunk times that)
-    int grid_cap = 0;    // HPRLP_BATCH_GRID of this call: most row blocks of a normal half-step launch (0: as many as the rows need)
-    Geo geo{};
-    hipStream_t stream = nullptr;
     std::map<int, hipGraphExec_t> graphs;
     // The captured launches hold lambda_max BY VALUE (HalfArgs): whoever changes it drops them, and run_normal captures anew.
     void drop_graphs() {
@@ -799,15 +791,6 @@ struct BatchWS {
     }
     ~BatchWS() { drop_graphs(); }
 };
-
-int padded_batch(int B) {
-    if (B <= 64) {
-        int p = 1;
-        while (p < B) p <<= 1;
-        return p;
-    }
-    return (B + 63) / 64 * 64;
-}
 
 int grid_for(int rows, const Geo &g) {
     long need = (static_cast<long>(rows) + g.rows_per_block - 1) / g.rows_per_block;
@@ -882,6 +865,67 @@ void run_normal(BatchWS &w, int count) {
     }
 }
 
+// The launches with kb_resid's geometry: x-side ones run over the n rows of A^T (w.gx row blocks), y-side ones over the m rows of
+// A (w.gy), elementwise ones over both (the larger of the two); each is followed by the finalize of the slots it fills.
+constexpr const double *kUnread = nullptr;  // an operand that the launched variant of a kernel does not read
+inline dim3 grid_of(const BatchWS &w, int row_blocks) { return dim3(row_blocks * w.geo.nchunk); }
+inline int both_grids(const BatchWS &w) { return std::max(w.gx, w.gy); }
+
+// compute_residuals :578-624, dual part: |(C - A^T Ybar - Zbar) .* col_norm|^2
+void launch_dual_residual(BatchWS &w) {
+    const CsrDev &AT = w.shared->AT.view;
+    hipLaunchKernelGGL((kb_resid<0>), grid_of(w, w.gx), dim3(256), 0, w.stream, AT.rows, AT.rowptr, AT.col, AT.val, w.geo, w.m,
+                       /*V*/ w.Yb.p, /*V2*/ kUnread, /*p0*/ w.C.p, /*p1*/ w.Zb.p, /*norm*/ w.shared->col_norm.p, /*dvec*/ kUnread,
+                       w.partials.p);
+    finalize(w, w.gx, {B_RD2});
+}
+// ... primal part: |row_norm .* (A Xbar out of [AL, AU])|^2
+void launch_primal_residual(BatchWS &w) {
+    const CsrDev &A = w.shared->A.view;
+    hipLaunchKernelGGL((kb_resid<1>), grid_of(w, w.gy), dim3(256), 0, w.stream, A.rows, A.rowptr, A.col, A.val, w.geo, w.n,
+                       /*V*/ w.Xb.p, /*V2*/ kUnread, /*p0*/ w.AL.p, /*p1*/ w.AU.p, /*norm*/ w.shared->row_norm.p, /*dvec*/ kUnread,
+                       w.partials.p);
+    finalize(w, w.gy, {B_RP2});
+}
+// the weighted norm's <A DX, DY>
+void launch_cross_term(BatchWS &w) {
+    const CsrDev &A = w.shared->A.view;
+    hipLaunchKernelGGL((kb_resid<3>), grid_of(w, w.gy), dim3(256), 0, w.stream, A.rows, A.rowptr, A.col, A.val, w.geo, w.n,
+                       /*V*/ kUnread, /*V2*/ w.DX.p, /*p0*/ kUnread, /*p1*/ kUnread, /*norm*/ kUnread, /*dvec*/ w.DY.p, w.partials.p);
+    finalize(w, w.gy, {B_ADX_DY});
+}
+void launch_bound_violation(BatchWS &w) {  // iteration 0 only
+    hipLaunchKernelGGL(kb_lu, grid_of(w, w.gx), dim3(256), 0, w.stream, w.n, w.geo, w.Xb.p, w.L.p, w.U.p, w.shared->col_norm.p,
+                       w.DX.p, w.partials.p);
+    finalize(w, w.gx, {B_LU2});
+}
+// update_sigma :702-745, device part: movement norms for every problem
+void launch_movement(BatchWS &w) {
+    hipLaunchKernelGGL(kb_movement, grid_of(w, both_grids(w)), dim3(256), 0, w.stream, w.n, w.m, w.geo, w.Xb.p, w.lastX.p, w.DX.p,
+                       w.Yb.p, w.lastY.p, w.DY.p, w.partials.p);
+    finalize(w, both_grids(w), {B_MOVE_X2, B_MOVE_Y2});
+}
+void launch_restart_copy(BatchWS &w) {  // do_restart :747-769
+    hipLaunchKernelGGL(kb_restart, grid_of(w, both_grids(w)), dim3(256), 0, w.stream, w.n, w.m, w.geo, w.X.p, w.lastX.p, w.Xb.p,
+                       w.Y.p, w.lastY.p, w.Yb.p, w.ctl);
+}
+void launch_start_seed(BatchWS &w) {
+    hipLaunchKernelGGL(kb_start_seed, grid_of(w, both_grids(w)), dim3(256), 0, w.stream, w.n, w.m, w.geo, w.X.p, w.Xh.p, w.Xb.p,
+                       w.lastX.p, w.L.p, w.U.p, w.Y.p, w.Yb.p, w.lastY.p, w.AL.p, w.AU.p);
+}
+void launch_start_col(BatchWS &w) {  // Z_bar, C.X_bar and the bound terms of the start
+    const CsrDev &AT = w.shared->AT.view;
+    hipLaunchKernelGGL(kb_start_spmm<true>, grid_of(w, w.gx), dim3(256), 0, w.stream, AT.rows, AT.rowptr, AT.col, AT.val, w.geo, w.m,
+                       /*V*/ w.Yb.p, /*p0*/ w.C.p, /*lo*/ w.L.p, /*hi*/ w.U.p, /*bar*/ w.Xb.p, /*out*/ w.Zb.p, w.partials.p);
+    finalize(w, w.gx, {B_CX, B_XZ});
+}
+void launch_start_row(BatchWS &w) {  // Y_obj and Y_obj.Y_bar of the start
+    const CsrDev &A = w.shared->A.view;
+    hipLaunchKernelGGL(kb_start_spmm<false>, grid_of(w, w.gy), dim3(256), 0, w.stream, A.rows, A.rowptr, A.col, A.val, w.geo, w.n,
+                       /*V*/ w.Xb.p, /*p0*/ kUnread, /*lo*/ w.AL.p, /*hi*/ w.AU.p, /*bar*/ w.Yb.p, /*out*/ w.Yobj.p, w.partials.p);
+    finalize(w, w.gy, {B_YOBJ_Y});
+}
+
 void fetch(BatchWS &w) {
     HIP_CHECK(hipMemcpyAsync(w.SC_h.p, w.SC.p, sizeof(double) * w.nslot * w.Bp, hipMemcpyDeviceToHost, w.stream));
     HIP_CHECK(hipStreamSynchronize(w.stream));
@@ -912,6 +956,13 @@ void ray_step(BatchWS &w, bool test) {
                        static_cast<const double *>(w.AU.p), static_cast<const double *>(w.shared->row_norm.p), a, w.partials.p);
     finalize(w, w.gy, {B_RAY_WQ}, 0x1u);
 }
+// the certificates' z = -A^T y: the plain product A^T YS for every member, into the scratch panel (no partials, no finalize)
+void launch_ray_product(BatchWS &w) {
+    const CsrDev &AT = w.shared->AT.view;
+    hipLaunchKernelGGL(kb_ray_product, grid_of(w, w.gx), dim3(256), 0, w.stream, AT.rows, AT.rowptr, AT.col, AT.val, w.geo, w.m,
+                       /*V*/ static_cast<const double *>(w.YS.p), /*lo*/ kUnread, /*hi*/ kUnread, /*norm*/ kUnread, ray_args(w),
+                       w.Zray.p);
+}
 
 // member k's ratio-test sums from the fetched ray slots (Solver::ray_scalars)
 RayScalars ray_scalars(const BatchWS &w, int k) {
@@ -919,24 +970,10 @@ RayScalars ray_scalars(const BatchWS &w, int k) {
                       std::max(sc(w, B_RAY_WD, k), sc(w, B_RAY_WQ, k)), sc(w, B_RAY_YN, k), sc(w, B_RAY_DN, k)};
 }
 
-// one LP of the batch: the host side of its iteration, and how it ended
-struct Member {
-    RestartState rs;
-    Residuals r;
-    std::string status = "CONTINUE";
-    int final_iter = 0;
-    int verdict = 0;  // detection: 1 primal, 2 dual infeasible
-    RayScalars ray;   // ... and the sums the verdict was reached with
-};
-
 // reference compute_weighted_norm :626-666.  DX/DY norms come from the slots the check step filled,
 // unless a movement pass has overwritten DX/DY since (then B_MOVE_* hold the matching norms).
 void weighted_norm(BatchWS &w, bool dxdy_from_movement, std::vector<double> &sigma, std::vector<double> &out) {
-    const CsrDev &A = w.shared->A.view;
-    hipLaunchKernelGGL((kb_resid<3>), dim3(w.gy * w.geo.nchunk), dim3(256), 0, w.stream, A.rows, A.rowptr, A.col, A.val, w.geo,
-                       w.n, static_cast<const double *>(nullptr), w.DX.p, static_cast<const double *>(nullptr),
-                       static_cast<const double *>(nullptr), static_cast<const double *>(nullptr), w.DY.p, w.partials.p);
-    finalize(w, w.gy, {B_ADX_DY});
+    launch_cross_term(w);
     fetch(w);
     out.assign(w.B, 0.0);
     const double lambda_before = w.lambda_max;
@@ -958,61 +995,343 @@ void weighted_norm(BatchWS &w, bool dxdy_from_movement, std::vector<double> &sig
     if (w.lambda_max != lambda_before) w.drop_graphs();
 }
 
-double bound_norm_host(const double *AL, const double *AU, int m, size_t off) {  // :332-345
-    long double sum = 0.0;
-    for (int i = 0; i < m; ++i) {
-        const double lo = AL[off + i], hi = AU[off + i];
-        const double a = (std::isinf(lo) && lo < 0) ? 0.0 : std::abs(lo);
-        const double b = (std::isinf(hi) && hi > 0) ? 0.0 : std::abs(hi);
-        const double v = std::max(a, b);
-        sum += static_cast<long double>(v) * v;
-    }
-    return std::sqrt(static_cast<double>(sum));
-}
-double column_norm_host(const double *X, int n, size_t off) {  // :347-354
-    long double sum = 0.0;
-    for (int i = 0; i < n; ++i) sum += static_cast<long double>(X[off + i]) * X[off + i];
-    return std::sqrt(static_cast<double>(sum));
+// ---- the workspace ---------------------------------------------------------------------------------------------------------
+// Launch order of the row groups of one matrix (kb_half64 / kb_halfN): groups of kRowsPerWave rows with more than kLongGroup
+// nonzeros go first, longest first; the rest keep their order.  A wave's group: subs = 64 / Bw lane groups of kRowsPerWave rows
+// each; its length = the longest lane group's entry count.  `out` stays empty (identity: no table) without a long group.
+void build_order(const DBuf<int> &rowptr_dev, int rows, int subs, DBuf<int> &out) {
+    constexpr int kLongGroup = 32;
+    const int gr = kRowsPerWave * subs;
+    std::vector<int> rp(static_cast<size_t>(rows) + 1);
+    rowptr_dev.download(rp.data(), rp.size());
+    const int ng = (rows + gr - 1) / gr;
+    std::vector<int> longg, order;
+    order.reserve(static_cast<size_t>(ng));
+    auto len = [&](int g) {
+        int longest = 0;
+        for (int sb = 0; sb < subs; ++sb) {  // lane group sb: rows g * gr + i * subs + sb (kb_halfN; kb_half64: subs = 1)
+            int cnt = 0;
+            for (int i = 0; i < kRowsPerWave; ++i) {
+                const int r = g * gr + i * subs + sb;
+                if (r < rows) cnt += rp[r + 1] - rp[r];
+            }
+            longest = std::max(longest, cnt);
+        }
+        return longest;
+    };
+    for (int g = 0; g < ng; ++g)
+        if (len(g) > kLongGroup) longg.push_back(g);
+    if (longg.empty()) return;
+    std::stable_sort(longg.begin(), longg.end(), [&](int x, int y) { return len(x) > len(y); });
+    order = longg;
+    for (int g = 0; g < ng; ++g)
+        if (len(g) <= kLongGroup) order.push_back(g);
+    out.alloc(order.size());
+    out.upload(order.data(), order.size());
 }
 
-// element (row i, problem k) of a device panel with `rows` rows (the host's copy of pidx)
-inline size_t panel_index(const Geo &g, int rows, int i, int k) {
-    return (static_cast<size_t>(k / g.Bw) * rows + i) * g.Bw + k % g.Bw;
+// What depends on the (scaled) shared matrix and the chunk geometry alone: grids and order tables (and w.rn / w.cn, which
+// solve_batched_impl fetches first: the batch's vectors are scaled with them).
+void ws_matrix_part(BatchWS &w, Solver &shared, const Geo &geo) {
+    w.m = shared.m; w.n = shared.n;
+    w.shared = &shared;
+    w.stream = shared.stream;
+    w.geo = geo;
+    if (const char *e = env_get("HPRLP_BATCH_GRID")) w.grid_cap = std::atoi(e);
+    w.gx = grid_for(w.n, geo);
+    w.gy = grid_for(w.m, geo);
+    if (geo.Bw >= 8) {
+        build_order(shared.AT.rowptr, w.n, 64 / geo.Bw, w.order_x);
+        build_order(shared.A.rowptr, w.m, 64 / geo.Bw, w.order_y);
+    }
 }
-// column-major (ABI) rows x B -> padded device panel
-void to_panel(const std::vector<double> &cm, int rows, int B, const Geo &g, double pad, std::vector<double> &out) {
-    out.assign(static_cast<size_t>(rows) * g.Bp, pad);
+
+std::vector<double> padded(const std::vector<double> &v, int Bp, double pad) {  // per-member values, padding members included
+    std::vector<double> out(Bp, pad);
+    std::copy(v.begin(), v.end(), out.begin());
+    return out;
+}
+
+// What depends on this batch (:479-532): row-major padded panels of its vectors, work vectors, scalar slots, control arrays and,
+// with `detect`, the detection's buffers.  sigma / active: the loop's per-member values (Bp of each), as it starts.
+void ws_batch_part(BatchWS &w, const BatchData &d, const std::vector<double> &sigma, const std::vector<int> &active, bool detect) {
+    const int m = w.m, n = w.n, B = d.B;
+    w.B = B; w.Bp = w.geo.Bp;
+    w.data = &d;
+    const size_t nB = static_cast<size_t>(n) * w.Bp, mB = static_cast<size_t>(m) * w.Bp;
+    {
+        std::vector<double> panel;
+        to_panel(d.C, n, B, w.geo, 0.0, panel); w.C.alloc(nB); w.C.upload(panel.data(), nB);
+        to_panel(d.L, n, B, w.geo, 0.0, panel); w.L.alloc(nB); w.L.upload(panel.data(), nB);
+        to_panel(d.U, n, B, w.geo, 0.0, panel); w.U.alloc(nB); w.U.upload(panel.data(), nB);
+        to_panel(d.AL, m, B, w.geo, 0.0, panel); w.AL.alloc(mB); w.AL.upload(panel.data(), mB);
+        to_panel(d.AU, m, B, w.geo, 0.0, panel); w.AU.alloc(mB); w.AU.upload(panel.data(), mB);
+    }
+    for (DBuf<double> *p : {&w.X, &w.Xh, &w.Xb, &w.DX, &w.Zb, &w.lastX}) p->alloc_zero(nB);
+    for (DBuf<double> *p : {&w.Y, &w.Yb, &w.DY, &w.Yobj, &w.lastY}) p->alloc_zero(mB);
+    w.nslot = detect ? B_NSLOT_DETECT : B_NSLOT;
+    w.SC.alloc_zero(static_cast<size_t>(w.nslot) * w.Bp);
+    w.SC_h.alloc(static_cast<size_t>(w.nslot) * w.Bp);
+    w.partials.alloc_zero(static_cast<size_t>(std::max(w.gx, w.gy)) * (detect ? kRayFormAccs : 3) * w.Bp);
+    w.sigma.alloc(w.Bp); w.active.alloc(w.Bp); w.kx.alloc_zero(w.Bp); w.ky.alloc_zero(w.Bp); w.rflag.alloc_zero(w.Bp);
+    w.ctl = BatchCtl{w.sigma.p, w.active.p, w.kx.p, w.ky.p, w.rflag.p};
+    w.sigma.upload(sigma.data(), w.Bp);
+    w.active.upload(active.data(), w.Bp);
+    if (detect) {
+        for (DBuf<double> *p : {&w.prevX, &w.DS}) p->alloc_zero(nB);
+        for (DBuf<double> *p : {&w.prevY, &w.YS}) p->alloc_zero(mB);
+        w.bsc.alloc(w.Bp);
+        w.bsc.upload(padded(d.b_scale, w.Bp, 1.0).data(), w.Bp);
+        w.csc.alloc(w.Bp);
+        w.csc.upload(padded(d.c_scale, w.Bp, 1.0).data(), w.Bp);
+    }
+}
+
+// Warm start: the starts in scaled units beside the other per-member vectors (the inverse of the results' map) into X / Y, then
+// their projection, the seeding of every panel the first iteration reads, and the iteration-0 evaluation's sums.
+void ws_start(BatchWS &w, const double *X0, const double *Y0) {
+    auto upload = [&w](const double *v0, int rows, const std::vector<double> &norm, const std::vector<double> &scale, DBuf<double> &P) {
+        if (!v0) return;
+        std::vector<double> v(v0, v0 + static_cast<size_t>(rows) * w.B), panel;
+        start_to_scaled(v.data(), rows, w.B, norm.data(), scale);
+        to_panel(v, rows, w.B, w.geo, 0.0, panel);
+        P.upload(panel.data(), panel.size());
+    };
+    upload(X0, w.n, w.cn, w.data->b_scale, w.X);
+    upload(Y0, w.m, w.rn, w.data->c_scale, w.Y);
+    launch_start_seed(w);
+    launch_start_col(w);
+    launch_start_row(w);
+}
+
+// ---- the loop --------------------------------------------------------------------------------------------------------------
+// one LP of the batch: the host side of its iteration, and how it ended
+struct Member {
+    RestartState rs;
+    Residuals r;
+    std::string status = "CONTINUE";
+    int final_iter = 0;
+    int verdict = 0;  // detection: 1 primal, 2 dual infeasible
+    RayScalars ray;   // ... and the sums the verdict was reached with
+};
+
+struct BatchLoop {
+    const HPRLP_parameters &prm;
+    const Detection *det;  // null: detection off
+    const int check_iter;
+    clock_type::time_point solve_start;
+    int iter = 0;
+    std::vector<Member> mem;  // (every way out of the loop sets each member's status and final_iter)
+    std::vector<double> sigma, gaps;
+    std::vector<int> active, flags;
+    bool dxdy_from_movement = false;
+    bool ray_have_prev = false;  // detection
+    // restart state (:534-556)
+    BatchLoop(const BatchData &d, int Bp, const HPRLP_parameters &p, const Detection *dt)
+        : prm(p), det(dt), check_iter(std::max(p.check_iter, 1)), mem(d.B), sigma(padded(d.sigma, Bp, 1.0)), active(Bp, 0), flags(Bp, 0) {
+        std::fill_n(active.begin(), d.B, 1);
+        for (int k = 0; k < d.B; ++k) mem[k].rs.best_sigma = sigma[k];
+    }
+};
+
+// The evaluation at a periodic event: residuals, stopping test and the detection's verdicts of the active members.
+void loop_evaluate(BatchWS &w, BatchLoop &L) {
+    const BatchData &d = *w.data;
+    const int B = w.B, iter = L.iter;
+    if (iter > 0) {
+        weighted_norm(w, L.dxdy_from_movement, L.sigma, L.gaps);
+        for (int k = 0; k < B; ++k) L.mem[k].rs.current_gap = L.gaps[k];
+    }
+    launch_dual_residual(w);
+    launch_primal_residual(w);
+    if (iter == 0) launch_bound_violation(w);
+    bool ray_tested = false;
+    if (L.det && iter > 0) {
+        ray_tested = L.ray_have_prev;
+        ray_step(w, ray_tested);
+        L.ray_have_prev = true;
+    }
+    fetch(w);
+    for (int k = 0; k < B; ++k) {
+        // a frozen member's X_bar/Y_bar/Z_bar no longer change, so its residuals keep the
+        // values of the check that froze it (the fused dot slots only cover active members)
+        if (!L.active[k]) continue;
+        Residuals &r = L.mem[k].r;
+        assemble_residuals(&r, {sc(w, B_CX, k), sc(w, B_YOBJ_Y, k), sc(w, B_XZ, k), sc(w, B_RD2, k), sc(w, B_RP2, k), sc(w, B_LU2, k)},
+                           {d.b_scale[k], d.c_scale[k], d.norm_b_org[k], d.norm_c_org[k], d.objc[k]}, iter == 0);
+        r.kkt = std::max(r.err_Rp, std::max(r.err_Rd, r.rel_gap));  // (solver.cpp nests the max() the other way, as the reference)
+    }
     for (int k = 0; k < B; ++k)
-        for (int i = 0; i < rows; ++i) out[panel_index(g, rows, i, k)] = cm[static_cast<size_t>(k) * rows + i];
+        if (L.active[k] && L.mem[k].r.kkt <= L.prm.stop_tol) {  // (<= here, strict in solver.cpp, as in the reference)
+            L.mem[k].status = "OPTIMAL";
+            L.mem[k].final_iter = iter;
+            L.active[k] = 0;
+        }
+    if (ray_tested)
+        for (int k = 0; k < B; ++k) {
+            if (!L.active[k]) continue;  // (OPTIMAL at this evaluation takes precedence)
+            const RayScalars s = ray_scalars(w, k);
+            const int v = s.verdict(*L.det);
+            if (!v) continue;
+            Member &mb = L.mem[k];
+            mb.status = v == 1 ? "PRIMAL_INFEASIBLE" : "DUAL_INFEASIBLE";
+            mb.final_iter = iter;
+            L.active[k] = 0;
+            mb.verdict = v;
+            mb.ray = s;
+        }
+    w.active.upload(L.active.data(), w.Bp);
 }
 
-// Chunk width.  Below 64 problems: one chunk.  From 64 up: 8 problems per chunk when the gathered panels are too large for
-// an XCD's L2 as a whole but an eighth (a sixteenth, ..) of them is not -- every XCD then works on its own chunks and
-// gathers from 1 / nchunk-th of the panel -- else 64 (a wave = one row, scalar CSR loads).  HPRLP_BATCH_CHUNK overrides.
-int choose_chunk(int m, int n, int Bp) {
-    if (Bp < 64) return Bp;
-    if (const char *e = env_get("HPRLP_BATCH_CHUNK")) {
-        const int c = std::atoi(e);
-        if (c == 8 || c == 16 || c == 32 || c == 64) return c;
+// True when the loop is over: every member has a status, or the iteration / time limit gives the rest theirs.
+bool loop_ended(BatchLoop &L, double elapsed) {
+    bool all_done = true;
+    for (const Member &mb : L.mem) all_done = all_done && (mb.status != "CONTINUE");
+    if (all_done) return true;
+    if (L.iter >= L.prm.max_iter || elapsed >= L.prm.time_limit) {  // (>= here, strict in solver.cpp, as in the reference)
+        const char *fs = elapsed >= L.prm.time_limit ? "TIME_LIMIT" : "ITER_LIMIT";
+        for (size_t k = 0; k < L.mem.size(); ++k)
+            if (L.mem[k].status == "CONTINUE") {
+                L.mem[k].status = fs;
+                L.mem[k].final_iter = L.iter;
+                L.active[k] = 0;
+            }
+        return true;
     }
-    (void)m; (void)n;
-    return 64;
+    return false;
+}
+
+// The restart decision of every member and, where one restarts (the return value), the sigma update and the restart copy.
+bool loop_restart(BatchWS &w, BatchLoop &L, bool periodic) {
+    const int B = w.B;
+    bool restarted = false;
+    for (int k = 0; k < B; ++k) {  // check_restart :667-700
+        RestartState &rs = L.mem[k].rs;
+        if (periodic && L.active[k]) check_restart(rs, L.iter, L.check_iter, L.sigma[k], false);
+        else rs.flag = 0;
+        restarted = restarted || rs.flag > 0;
+    }
+    if (!restarted) return false;
+    // update_sigma :702-745 (movement norms for every problem, formula for the flagged ones)
+    launch_movement(w);
+    fetch(w);
+    L.dxdy_from_movement = true;
+    for (int k = 0; k < B; ++k) {
+        const Member &mb = L.mem[k];
+        if (!L.active[k] || mb.rs.flag < 1) continue;
+        L.sigma[k] = restart_sigma(std::sqrt(sc(w, B_MOVE_X2, k)), std::sqrt(sc(w, B_MOVE_Y2, k)), w.lambda_max, mb.rs, mb.r);
+    }
+    w.sigma.upload(L.sigma.data(), w.Bp);
+    // do_restart :747-769
+    for (int k = 0; k < w.Bp; ++k) L.flags[k] = (k < B && L.mem[k].rs.flag > 0) ? 1 : 0;
+    w.rflag.upload(L.flags.data(), w.Bp);
+    launch_restart_copy(w);
+    for (int k = 0; k < B; ++k)
+        if (L.active[k] && L.mem[k].rs.flag > 0) {
+            L.mem[k].rs.inner = 0;
+            L.mem[k].rs.save_gap = std::numeric_limits<double>::infinity();
+        }
+    return true;
+}
+
+// Iterations iter .. next-1; check variant where the reference's to_check holds (:1067-1068).  Unlike solver.cpp's
+// next_event, the events are the periodic checks and the iteration limit only, not the log steps, as in the reference.
+void loop_advance(BatchWS &w, BatchLoop &L, bool restarted) {
+    const int iter = L.iter, check_iter = L.check_iter;
+    int next = iter + 1;
+    while (next % check_iter != 0 && next < L.prm.max_iter) ++next;
+    int it = iter;
+    while (it < next) {
+        const bool first_after_restart = (it == iter) && restarted;
+        int run = 0;  // normal iterations before the next check-variant one
+        while (it + run < next && !(((it + run + 1) % check_iter) == 0 || ((it + run + 1) % log_step(it + run + 1)) == 0 ||
+                                    (first_after_restart && run == 0)))
+            ++run;
+        run_normal(w, run);
+        it += run;
+        if (it < next) {
+            launch_half_pair(w, true);
+            L.dxdy_from_movement = false;
+            ++it;
+            if (first_after_restart) {
+                weighted_norm(w, false, L.sigma, L.gaps);
+                for (int k = 0; k < w.B; ++k)
+                    if (L.mem[k].rs.flag > 0) L.mem[k].rs.last_gap = L.gaps[k];
+            }
+        }
+    }
+    for (int k = 0; k < w.B; ++k)
+        if (L.active[k]) L.mem[k].rs.inner += next - iter;
+    L.iter = next;
+}
+
+// ---- after the loop --------------------------------------------------------------------------------------------------------
+// the first B members of a device panel, column-major on the host
+std::vector<double> download_panel(const BatchWS &w, const DBuf<double> &P, int rows) {
+    std::vector<double> panel(static_cast<size_t>(rows) * w.Bp), cm(static_cast<size_t>(rows) * w.B);
+    P.download(panel.data(), panel.size());
+    from_panel(panel, rows, w.B, w.geo, cm.data());
+    return cm;
+}
+
+// the certificates of the members with a verdict: their YS / DS columns have not changed since (Solver::collect_certificate)
+void collect_certificates(BatchWS &w, const BatchLoop &L, std::vector<Certificate> *certs) {
+    const int m = w.m, n = w.n;
+    certs->assign(w.B, Certificate());
+    bool any_y = false, any_d = false;
+    for (const Member &mb : L.mem) {
+        any_y = any_y || mb.verdict == 1;
+        any_d = any_d || mb.verdict == 2;
+    }
+    std::vector<double> hYS, hZS, hDS;
+    if (any_y) {  // z = -A^T y: the plain product on the device, into the scratch panel
+        w.Zray.alloc(static_cast<size_t>(n) * w.Bp);
+        launch_ray_product(w);
+        HIP_CHECK(hipStreamSynchronize(w.stream));
+        hYS = download_panel(w, w.YS, m);
+        hZS = download_panel(w, w.Zray, n);
+    }
+    if (any_d) hDS = download_panel(w, w.DS, n);
+    for (int k = 0; k < w.B; ++k) {
+        const Member &mb = L.mem[k];
+        if (!mb.verdict) continue;
+        Certificate &c = (*certs)[k];
+        const size_t om = static_cast<size_t>(k) * m, on = static_cast<size_t>(k) * n;
+        if (mb.verdict == 1) {
+            c.y.assign(hYS.begin() + om, hYS.begin() + om + m);
+            c.z.assign(hZS.begin() + on, hZS.begin() + on + n);
+        } else {
+            c.d.assign(hDS.begin() + on, hDS.begin() + on + n);
+        }
+        finish_certificate(&c, mb.verdict, mb.final_iter, mb.ray, w.rn.data(), w.cn.data(), w.data->b_scale[k], w.data->c_scale[k]);
+    }
+}
+
+// collect_results :887-935: the bars in the caller's units, and every member's evaluation, iteration and status
+HPRLP_batched_results collect_results(BatchWS &w, const BatchLoop &L, std::vector<Certificate> *certs) {
+    const BatchData &d = *w.data;
+    const int m = w.m, n = w.n, B = w.B;
+    HIP_CHECK(hipStreamSynchronize(w.stream));
+    const std::vector<double> hX = download_panel(w, w.Xb, n), hY = download_panel(w, w.Yb, m), hZ = download_panel(w, w.Zb, n);
+    if (certs) collect_certificates(w, L, certs);
+    HPRLP_batched_results out = alloc_batched_results(m, n, B);
+    std::copy(hX.begin(), hX.end(), out.x);
+    std::copy(hY.begin(), hY.end(), out.y);
+    std::copy(hZ.begin(), hZ.end(), out.z);
+    point_to_caller(out.x, n, B, w.cn.data(), d.b_scale);
+    point_to_caller(out.y, m, B, w.rn.data(), d.c_scale);
+    reduced_cost_to_caller(out.z, n, B, w.cn.data(), d.c_scale);
+    for (int k = 0; k < B; ++k) {
+        out.primal_obj[k] = L.mem[k].r.primal_obj;
+        out.residuals[k] = L.mem[k].r.kkt;
+        out.gap[k] = L.mem[k].r.rel_gap;
+        out.iter[k] = L.mem[k].final_iter;
+        std::strncpy(out.status + 64 * k, L.mem[k].status.c_str(), 63);
+    }
+    return out;
 }
 
 }  // namespace
-
-HPRLP_batched_results make_batched_error(const char *status, int m, int n, int B) {  // :356-368
-    HPRLP_batched_results r;
-    r.m = m;
-    r.n = n;
-    r.batch_size = B;
-    if (B > 0) {
-        r.status = static_cast<char *>(std::calloc(static_cast<size_t>(B) * 64, sizeof(char)));
-        if (r.status)
-            for (int k = 0; k < B; ++k) std::strncpy(r.status + 64 * k, status, 63);
-    }
-    return r;
-}
 
 // warm-up (abi.cpp: hprlp_warmup): an attribute query makes the runtime load this translation unit's code object now instead
 // of at the first launch of one of its kernels
@@ -1020,12 +1339,6 @@ void warm_batched_tu() {
     hipFuncAttributes a;
     (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&kb_finalize));
 }
-
-}  // namespace hprlp
-
-using namespace hprlp;
-
-namespace hprlp {
 
 HPRLP_batched_results solve_batched_impl(const LP_info_cpu *model, int batch_size, const HPRLP_FLOAT *C_in, const HPRLP_FLOAT *AL_in,
                                          const HPRLP_FLOAT *AU_in, const HPRLP_FLOAT *l_in, const HPRLP_FLOAT *u_in,
@@ -1051,394 +1364,45 @@ HPRLP_batched_results solve_batched_impl(const LP_info_cpu *model, int batch_siz
         shared.allow_reorder = false;  // the panels and the returned X / Y / Z are in the caller's numbering
         shared.setup(&mat, &mp);
         shared.scale();
-        std::vector<double> rn(m), cn(n);
-        shared.row_norm.download(rn.data(), m);
-        shared.col_norm.download(cn.data(), n);
+        BatchWS w;
+        w.rn.resize(m); w.cn.resize(n);
+        shared.row_norm.download(w.rn.data(), m);
+        shared.col_norm.download(w.cn.data(), n);
 
         // per-column vector scaling on the host (:792-885)
-        std::vector<double> hC(C_in, C_in + static_cast<size_t>(n) * B), hAL(AL_in, AL_in + static_cast<size_t>(m) * B),
-            hAU(AU_in, AU_in + static_cast<size_t>(m) * B), hL(l_in, l_in + static_cast<size_t>(n) * B),
-            hU(u_in, u_in + static_cast<size_t>(n) * B);
-        std::vector<double> b_scale(B, 1.0), c_scale(B, 1.0), norm_b(B), norm_c(B), norm_b_org(B), norm_c_org(B), objc(B);
-        for (int k = 0; k < B; ++k) {
-            const size_t om = static_cast<size_t>(k) * m, on = static_cast<size_t>(k) * n;
-            norm_b_org[k] = 1.0 + bound_norm_host(hAL.data(), hAU.data(), m, om);
-            norm_c_org[k] = 1.0 + column_norm_host(hC.data(), n, on);
-            for (int i = 0; i < m; ++i) { hAL[om + i] /= rn[i]; hAU[om + i] /= rn[i]; }
-            for (int i = 0; i < n; ++i) { hC[on + i] /= cn[i]; hL[on + i] *= cn[i]; hU[on + i] *= cn[i]; }
-        }
-        if (actual.use_bc_scaling) {
-            for (int k = 0; k < B; ++k) {
-                const size_t om = static_cast<size_t>(k) * m, on = static_cast<size_t>(k) * n;
-                b_scale[k] = 1.0 + bound_norm_host(hAL.data(), hAU.data(), m, om);
-                c_scale[k] = 1.0 + column_norm_host(hC.data(), n, on);
-                for (int i = 0; i < m; ++i) { hAL[om + i] /= b_scale[k]; hAU[om + i] /= b_scale[k]; }
-                for (int i = 0; i < n; ++i) { hC[on + i] /= c_scale[k]; hL[on + i] /= b_scale[k]; hU[on + i] /= b_scale[k]; }
-            }
-        }
-        for (int k = 0; k < B; ++k) {
-            const size_t om = static_cast<size_t>(k) * m, on = static_cast<size_t>(k) * n;
-            norm_b[k] = bound_norm_host(hAL.data(), hAU.data(), m, om);
-            norm_c[k] = column_norm_host(hC.data(), n, on);
-            for (int i = 0; i < m; ++i) {
-                if (std::isinf(hAL[om + i]) && hAL[om + i] < 0) hAL[om + i] = -kInfReplacement;
-                if (std::isinf(hAU[om + i]) && hAU[om + i] > 0) hAU[om + i] = kInfReplacement;
-            }
-            for (int i = 0; i < n; ++i) {
-                if (std::isinf(hL[on + i]) && hL[on + i] < 0) hL[on + i] = -kInfReplacement;
-                if (std::isinf(hU[on + i]) && hU[on + i] > 0) hU[on + i] = kInfReplacement;
-            }
-            objc[k] = obj_constants ? obj_constants[k] : model->obj_constant;
-        }
+        const BatchData data = prepare_batch(m, n, B, C_in, AL_in, AU_in, l_in, u_in, obj_constants, model->obj_constant, w.rn.data(),
+                                             w.cn.data(), actual.use_bc_scaling);
 
         // lambda_max on the scaled shared matrix (:994-1001)
         // (test hook HPRLP_BATCH_LAMBDA: the caller's value instead, so that a reference can run on the same bits)
         const char *lambda_hook = env_get("HPRLP_BATCH_LAMBDA");
-        const double lambda0 = lambda_hook ? std::strtod(lambda_hook, nullptr) : shared.power_iteration(5000, 1.0e-4, nullptr) * 1.01;
-        if (!(lambda0 > 0.0) || !std::isfinite(lambda0)) throw std::runtime_error("HPRLP_BATCH_LAMBDA is not a positive finite number");
-        const double power_time = shared.power_time;
+        w.lambda_max = lambda_hook ? std::strtod(lambda_hook, nullptr) : shared.power_iteration(5000, 1.0e-4, nullptr) * 1.01;
+        if (!(w.lambda_max > 0.0) || !std::isfinite(w.lambda_max)) throw std::runtime_error("HPRLP_BATCH_LAMBDA is not a positive finite number");
 
-        // workspace (:479-532): row-major padded panels
-        BatchWS w;
-        w.m = m; w.n = n; w.B = B; w.Bp = padded_batch(B);
-        w.shared = &shared;
-        w.stream = shared.stream;
-        w.lambda_max = lambda0;
-        w.geo = make_geo(w.Bp, choose_chunk(m, n, w.Bp));
-        const Geo &geo = w.geo;
-        if (const char *e = env_get("HPRLP_BATCH_GRID")) w.grid_cap = std::atoi(e);
-        w.gx = grid_for(n, geo);
-        w.gy = grid_for(m, geo);
-        if (geo.Bw >= 8) {
-            // groups of kRowsPerWave rows with more than kLongGroup nonzeros go first, longest first; the rest keep their order
-            // a wave's group: 64 / Bw lane groups of kRowsPerWave rows each; its length = the longest lane group's entry count
-            const int subs = 64 / geo.Bw, gr = kRowsPerWave * subs;
-            auto build_order = [gr, subs](const DBuf<int> &rowptr_dev, int rows, DBuf<int> &out) {
-                constexpr int kLongGroup = 32;
-                std::vector<int> rp(static_cast<size_t>(rows) + 1);
-                rowptr_dev.download(rp.data(), rp.size());
-                const int ng = (rows + gr - 1) / gr;
-                std::vector<int> longg, order;
-                order.reserve(static_cast<size_t>(ng));
-                auto len = [&](int g) {
-                    int longest = 0;
-                    for (int sb = 0; sb < subs; ++sb) {  // lane group sb: rows g * gr + i * subs + sb (kb_halfN; kb_half64: subs = 1)
-                        int cnt = 0;
-                        for (int i = 0; i < kRowsPerWave; ++i) {
-                            const int r = g * gr + i * subs + sb;
-                            if (r < rows) cnt += rp[r + 1] - rp[r];
-                        }
-                        longest = std::max(longest, cnt);
-                    }
-                    return longest;
-                };
-                for (int g = 0; g < ng; ++g)
-                    if (len(g) > kLongGroup) longg.push_back(g);
-                if (longg.empty()) return;  // identity: no table
-                std::stable_sort(longg.begin(), longg.end(), [&](int x, int y) { return len(x) > len(y); });
-                order = longg;
-                for (int g = 0; g < ng; ++g)
-                    if (len(g) <= kLongGroup) order.push_back(g);
-                out.alloc(order.size());
-                out.upload(order.data(), order.size());
-            };
-            build_order(shared.AT.rowptr, n, w.order_x);
-            build_order(shared.A.rowptr, m, w.order_y);
-        }
-        const size_t nB = static_cast<size_t>(n) * w.Bp, mB = static_cast<size_t>(m) * w.Bp;
-        {
-            std::vector<double> panel;
-            to_panel(hC, n, B, geo, 0.0, panel); w.C.alloc(nB); w.C.upload(panel.data(), nB);
-            to_panel(hL, n, B, geo, 0.0, panel); w.L.alloc(nB); w.L.upload(panel.data(), nB);
-            to_panel(hU, n, B, geo, 0.0, panel); w.U.alloc(nB); w.U.upload(panel.data(), nB);
-            to_panel(hAL, m, B, geo, 0.0, panel); w.AL.alloc(mB); w.AL.upload(panel.data(), mB);
-            to_panel(hAU, m, B, geo, 0.0, panel); w.AU.alloc(mB); w.AU.upload(panel.data(), mB);
-        }
-        for (DBuf<double> *p : {&w.X, &w.Xh, &w.Xb, &w.DX, &w.Zb, &w.lastX}) p->alloc_zero(nB);
-        for (DBuf<double> *p : {&w.Y, &w.Yb, &w.DY, &w.Yobj, &w.lastY}) p->alloc_zero(mB);
-        const bool warm = X0 || Y0;
-        if (warm) {
-            // the starts in scaled units beside the other per-member vectors (the inverse of the results' map), into X / Y
-            std::vector<double> panel;
-            if (X0) {
-                std::vector<double> hX(X0, X0 + static_cast<size_t>(n) * B);
-                for (int k = 0; k < B; ++k)
-                    for (int i = 0; i < n; ++i) hX[static_cast<size_t>(k) * n + i] = (hX[static_cast<size_t>(k) * n + i] * cn[i]) / b_scale[k];
-                to_panel(hX, n, B, geo, 0.0, panel);
-                w.X.upload(panel.data(), nB);
-            }
-            if (Y0) {
-                std::vector<double> hY(Y0, Y0 + static_cast<size_t>(m) * B);
-                for (int k = 0; k < B; ++k)
-                    for (int i = 0; i < m; ++i) hY[static_cast<size_t>(k) * m + i] = (hY[static_cast<size_t>(k) * m + i] * rn[i]) / c_scale[k];
-                to_panel(hY, m, B, geo, 0.0, panel);
-                w.Y.upload(panel.data(), mB);
-            }
-        }
         const bool detect = det && det->on;
-        w.nslot = detect ? B_NSLOT_DETECT : B_NSLOT;
-        w.SC.alloc_zero(static_cast<size_t>(w.nslot) * w.Bp);
-        w.SC_h.alloc(static_cast<size_t>(w.nslot) * w.Bp);
-        w.partials.alloc_zero(static_cast<size_t>(std::max(w.gx, w.gy)) * (detect ? kRayFormAccs : 3) * w.Bp);
-        w.sigma.alloc(w.Bp); w.active.alloc(w.Bp); w.kx.alloc_zero(w.Bp); w.ky.alloc_zero(w.Bp); w.rflag.alloc_zero(w.Bp);
-        w.ctl = BatchCtl{w.sigma.p, w.active.p, w.kx.p, w.ky.p, w.rflag.p};
-        std::vector<double> sigma(w.Bp, 1.0);
-        std::vector<int> active(w.Bp, 0), flags(w.Bp, 0);
-        for (int k = 0; k < B; ++k) {
-            if (norm_b[k] > 1.0e-8 && norm_c[k] > 1.0e-8) sigma[k] = norm_b[k] / norm_c[k];
-            active[k] = 1;
-        }
-        w.sigma.upload(sigma.data(), w.Bp);
-        w.active.upload(active.data(), w.Bp);
-        if (detect) {
-            for (DBuf<double> *p : {&w.prevX, &w.DS}) p->alloc_zero(nB);
-            for (DBuf<double> *p : {&w.prevY, &w.YS}) p->alloc_zero(mB);
-            std::vector<double> bs(w.Bp, 1.0), cs(w.Bp, 1.0);
-            std::copy(b_scale.begin(), b_scale.end(), bs.begin());
-            std::copy(c_scale.begin(), c_scale.end(), cs.begin());
-            w.bsc.alloc(w.Bp);
-            w.bsc.upload(bs.data(), w.Bp);
-            w.csc.alloc(w.Bp);
-            w.csc.upload(cs.data(), w.Bp);
-        }
-        if (warm) {
-            const CsrDev &A0 = shared.A.view, &AT0 = shared.AT.view;
-            hipLaunchKernelGGL(kb_start_seed, dim3(std::max(w.gx, w.gy) * geo.nchunk), dim3(256), 0, w.stream, n, m, geo, w.X.p, w.Xh.p,
-                               w.Xb.p, w.lastX.p, w.L.p, w.U.p, w.Y.p, w.Yb.p, w.lastY.p, w.AL.p, w.AU.p);
-            hipLaunchKernelGGL(kb_start_spmm<true>, dim3(w.gx * geo.nchunk), dim3(256), 0, w.stream, AT0.rows, AT0.rowptr, AT0.col,
-                               AT0.val, geo, m, w.Yb.p, w.C.p, w.L.p, w.U.p, w.Xb.p, w.Zb.p, w.partials.p);
-            finalize(w, w.gx, {B_CX, B_XZ});
-            hipLaunchKernelGGL(kb_start_spmm<false>, dim3(w.gy * geo.nchunk), dim3(256), 0, w.stream, A0.rows, A0.rowptr, A0.col,
-                               A0.val, geo, n, w.Xb.p, static_cast<const double *>(nullptr), w.AL.p, w.AU.p, w.Yb.p, w.Yobj.p,
-                               w.partials.p);
-            finalize(w, w.gy, {B_YOBJ_Y});
-        }
+        const int Bp = padded_batch(B);
+        BatchLoop L(data, Bp, actual, detect ? det : nullptr);
+        ws_matrix_part(w, shared, make_geo(Bp, choose_chunk(m, n, Bp)));
+        ws_batch_part(w, data, L.sigma, L.active, detect);
+        if (X0 || Y0) ws_start(w, X0, Y0);
         HIP_CHECK(hipDeviceSynchronize());
         const double setup_time = time_since(setup_start);
 
-        // restart state (:534-556)
-        const auto solve_start = time_now();
-        std::vector<Member> mem(B);  // (every way out of the loop below sets each member's status and final_iter)
-        for (int k = 0; k < B; ++k) mem[k].rs.best_sigma = sigma[k];
-        std::vector<double> gaps;
-        const int check_iter = std::max(actual.check_iter, 1);
-        const CsrDev &A = shared.A.view, &AT = shared.AT.view;
-        bool dxdy_from_movement = false;
-        bool ray_have_prev = false;  // detection
-
-        int iter = 0;
+        L.solve_start = time_now();
         while (true) {  // one pass per event iteration (periodic check or iteration limit), :1017-1084
-            const bool periodic = (iter % check_iter) == 0;
-            const double elapsed = time_since(solve_start);
-            if (periodic) {
-                if (iter > 0) {
-                    weighted_norm(w, dxdy_from_movement, sigma, gaps);
-                    for (int k = 0; k < B; ++k) mem[k].rs.current_gap = gaps[k];
-                }
-                // compute_residuals :578-624
-                hipLaunchKernelGGL((kb_resid<0>), dim3(w.gx * geo.nchunk), dim3(256), 0, w.stream, AT.rows, AT.rowptr, AT.col,
-                                   AT.val, geo, m, w.Yb.p, static_cast<const double *>(nullptr), w.C.p, w.Zb.p,
-                                   shared.col_norm.p, static_cast<const double *>(nullptr), w.partials.p);
-                finalize(w, w.gx, {B_RD2});
-                hipLaunchKernelGGL((kb_resid<1>), dim3(w.gy * geo.nchunk), dim3(256), 0, w.stream, A.rows, A.rowptr, A.col,
-                                   A.val, geo, n, w.Xb.p, static_cast<const double *>(nullptr), w.AL.p, w.AU.p,
-                                   shared.row_norm.p, static_cast<const double *>(nullptr), w.partials.p);
-                finalize(w, w.gy, {B_RP2});
-                if (iter == 0) {
-                    hipLaunchKernelGGL(kb_lu, dim3(w.gx * geo.nchunk), dim3(256), 0, w.stream, n, geo, w.Xb.p, w.L.p, w.U.p,
-                                       shared.col_norm.p, w.DX.p, w.partials.p);
-                    finalize(w, w.gx, {B_LU2});
-                }
-                bool ray_tested = false;
-                if (detect && iter > 0) {
-                    ray_tested = ray_have_prev;
-                    ray_step(w, ray_tested);
-                    ray_have_prev = true;
-                }
-                fetch(w);
-                for (int k = 0; k < B; ++k) {
-                    // a frozen member's X_bar/Y_bar/Z_bar no longer change, so its residuals keep the
-                    // values of the check that froze it (the fused dot slots only cover active members)
-                    if (!active[k]) continue;
-                    Residuals &r = mem[k].r;
-                    assemble_residuals(&r, {sc(w, B_CX, k), sc(w, B_YOBJ_Y, k), sc(w, B_XZ, k), sc(w, B_RD2, k), sc(w, B_RP2, k), sc(w, B_LU2, k)},
-                                       {b_scale[k], c_scale[k], norm_b_org[k], norm_c_org[k], objc[k]}, iter == 0);
-                    r.kkt = std::max(r.err_Rp, std::max(r.err_Rd, r.rel_gap));  // (solver.cpp nests the max() the other way, as the reference)
-                }
-                for (int k = 0; k < B; ++k)
-                    if (active[k] && mem[k].r.kkt <= actual.stop_tol) {  // (<= here, strict in solver.cpp, as in the reference)
-                        mem[k].status = "OPTIMAL";
-                        mem[k].final_iter = iter;
-                        active[k] = 0;
-                    }
-                if (ray_tested)
-                    for (int k = 0; k < B; ++k) {
-                        if (!active[k]) continue;  // (OPTIMAL at this evaluation takes precedence)
-                        const RayScalars s = ray_scalars(w, k);
-                        const int v = s.verdict(*det);
-                        if (!v) continue;
-                        Member &mb = mem[k];
-                        mb.status = v == 1 ? "PRIMAL_INFEASIBLE" : "DUAL_INFEASIBLE";
-                        mb.final_iter = iter;
-                        active[k] = 0;
-                        mb.verdict = v;
-                        mb.ray = s;
-                    }
-                w.active.upload(active.data(), w.Bp);
-            }
-            bool all_done = true;
-            for (const Member &mb : mem) all_done = all_done && (mb.status != "CONTINUE");
-            if (all_done) break;
-            if (iter >= actual.max_iter || elapsed >= actual.time_limit) {  // (>= here, strict in solver.cpp, as in the reference)
-                const char *fs = elapsed >= actual.time_limit ? "TIME_LIMIT" : "ITER_LIMIT";
-                for (int k = 0; k < B; ++k)
-                    if (mem[k].status == "CONTINUE") {
-                        mem[k].status = fs;
-                        mem[k].final_iter = iter;
-                        active[k] = 0;
-                    }
-                break;
-            }
-            bool restarted = false;
-            for (int k = 0; k < B; ++k) {  // check_restart :667-700
-                RestartState &rs = mem[k].rs;
-                if (periodic && active[k]) check_restart(rs, iter, check_iter, sigma[k], false);
-                else rs.flag = 0;
-                restarted = restarted || rs.flag > 0;
-            }
-            if (restarted) {
-                // update_sigma :702-745 (movement norms for every problem, formula for the flagged ones)
-                hipLaunchKernelGGL(kb_movement, dim3(std::max(w.gx, w.gy) * geo.nchunk), dim3(256), 0, w.stream, n, m, geo,
-                                   w.Xb.p, w.lastX.p, w.DX.p, w.Yb.p, w.lastY.p, w.DY.p, w.partials.p);
-                finalize(w, std::max(w.gx, w.gy), {B_MOVE_X2, B_MOVE_Y2});
-                fetch(w);
-                dxdy_from_movement = true;
-                for (int k = 0; k < B; ++k) {
-                    const Member &mb = mem[k];
-                    if (!active[k] || mb.rs.flag < 1) continue;
-                    sigma[k] = restart_sigma(std::sqrt(sc(w, B_MOVE_X2, k)), std::sqrt(sc(w, B_MOVE_Y2, k)), w.lambda_max, mb.rs, mb.r);
-                }
-                w.sigma.upload(sigma.data(), w.Bp);
-                // do_restart :747-769
-                for (int k = 0; k < w.Bp; ++k) flags[k] = (k < B && mem[k].rs.flag > 0) ? 1 : 0;
-                w.rflag.upload(flags.data(), w.Bp);
-                hipLaunchKernelGGL(kb_restart, dim3(std::max(w.gx, w.gy) * geo.nchunk), dim3(256), 0, w.stream, n, m, geo,
-                                   w.X.p, w.lastX.p, w.Xb.p, w.Y.p, w.lastY.p, w.Yb.p, w.ctl);
-                for (int k = 0; k < B; ++k)
-                    if (active[k] && mem[k].rs.flag > 0) {
-                        mem[k].rs.inner = 0;
-                        mem[k].rs.save_gap = std::numeric_limits<double>::infinity();
-                    }
-            }
-            // iterations iter .. next-1; check variant where the reference's to_check holds (:1067-1068).  Unlike solver.cpp's
-            // next_event, the events are the periodic checks and the iteration limit only, not the log steps, as in the reference.
-            int next = iter + 1;
-            while (next % check_iter != 0 && next < actual.max_iter) ++next;
-            int it = iter;
-            while (it < next) {
-                const bool first_after_restart = (it == iter) && restarted;
-                int run = 0;  // normal iterations before the next check-variant one
-                while (it + run < next && !(((it + run + 1) % check_iter) == 0 || ((it + run + 1) % log_step(it + run + 1)) == 0 ||
-                                            (first_after_restart && run == 0)))
-                    ++run;
-                run_normal(w, run);
-                it += run;
-                if (it < next) {
-                    launch_half_pair(w, true);
-                    dxdy_from_movement = false;
-                    ++it;
-                    if (first_after_restart) {
-                        weighted_norm(w, false, sigma, gaps);
-                        for (int k = 0; k < B; ++k)
-                            if (mem[k].rs.flag > 0) mem[k].rs.last_gap = gaps[k];
-                    }
-                }
-            }
-            for (int k = 0; k < B; ++k)
-                if (active[k]) mem[k].rs.inner += next - iter;
-            iter = next;
+            const bool periodic = (L.iter % L.check_iter) == 0;
+            const double elapsed = time_since(L.solve_start);
+            if (periodic) loop_evaluate(w, L);
+            if (loop_ended(L, elapsed)) break;
+            const bool restarted = loop_restart(w, L, periodic);
+            loop_advance(w, L, restarted);
         }
-        const double solve_time = time_since(solve_start);
+        const double solve_time = time_since(L.solve_start);
 
-        // collect_results :887-935
-        std::vector<double> hX(nB), hY(mB), hZ(nB);
-        HIP_CHECK(hipStreamSynchronize(w.stream));
-        w.Xb.download(hX.data(), nB);
-        w.Yb.download(hY.data(), mB);
-        w.Zb.download(hZ.data(), nB);
-        if (certs) {
-            // the certificates of the members with a verdict: their YS / DS columns have not changed since (Solver::collect_certificate)
-            certs->assign(B, Certificate());
-            bool any_y = false, any_d = false;
-            for (const Member &mb : mem) {
-                any_y = any_y || mb.verdict == 1;
-                any_d = any_d || mb.verdict == 2;
-            }
-            std::vector<double> hYS, hZS, hDS;
-            if (any_y) {  // z = -A^T y: the plain product on the device, into the scratch panel
-                w.Zray.alloc(nB);
-                hipLaunchKernelGGL(kb_ray_product, dim3(w.gx * geo.nchunk), dim3(256), 0, w.stream, AT.rows, AT.rowptr,
-                                   AT.col, AT.val, geo, m, static_cast<const double *>(w.YS.p), static_cast<const double *>(nullptr),
-                                   static_cast<const double *>(nullptr), static_cast<const double *>(nullptr), ray_args(w), w.Zray.p);
-                HIP_CHECK(hipStreamSynchronize(w.stream));
-                hYS.resize(mB);
-                hZS.resize(nB);
-                w.YS.download(hYS.data(), mB);
-                w.Zray.download(hZS.data(), nB);
-            }
-            if (any_d) {
-                hDS.resize(nB);
-                w.DS.download(hDS.data(), nB);
-            }
-            for (int k = 0; k < B; ++k) {
-                const Member &mb = mem[k];
-                if (!mb.verdict) continue;
-                Certificate &c = (*certs)[k];
-                if (mb.verdict == 1) {
-                    c.y.resize(m);
-                    c.z.resize(n);
-                    for (int i = 0; i < m; ++i) c.y[i] = hYS[panel_index(geo, m, i, k)];
-                    for (int j = 0; j < n; ++j) c.z[j] = hZS[panel_index(geo, n, j, k)];
-                } else {
-                    c.d.resize(n);
-                    for (int j = 0; j < n; ++j) c.d[j] = hDS[panel_index(geo, n, j, k)];
-                }
-                finish_certificate(&c, mb.verdict, mb.final_iter, mb.ray, rn.data(), cn.data(), b_scale[k], c_scale[k]);
-            }
-        }
-        HPRLP_batched_results out;
-        out.m = m; out.n = n; out.batch_size = B;
-        out.x = static_cast<double *>(std::malloc(sizeof(double) * static_cast<size_t>(n) * B));
-        out.y = static_cast<double *>(std::malloc(sizeof(double) * static_cast<size_t>(m) * B));
-        out.z = static_cast<double *>(std::malloc(sizeof(double) * static_cast<size_t>(n) * B));
-        out.primal_obj = static_cast<double *>(std::malloc(sizeof(double) * B));
-        out.residuals = static_cast<double *>(std::malloc(sizeof(double) * B));
-        out.gap = static_cast<double *>(std::malloc(sizeof(double) * B));
-        out.iter = static_cast<int *>(std::malloc(sizeof(int) * B));
-        out.status = static_cast<char *>(std::calloc(static_cast<size_t>(B) * 64, sizeof(char)));
-        if (!out.x || !out.y || !out.z || !out.primal_obj || !out.residuals || !out.gap || !out.iter || !out.status) {
-            free_batched_results(&out);
-            throw std::runtime_error("host allocation of the batched results failed");
-        }
-        for (int k = 0; k < B; ++k) {
-            for (int i = 0; i < n; ++i) {
-                const size_t src = panel_index(geo, n, i, k), dst = static_cast<size_t>(k) * n + i;
-                out.x[dst] = (hX[src] / cn[i]) * b_scale[k];
-                out.z[dst] = (hZ[src] * cn[i]) * c_scale[k];
-            }
-            for (int i = 0; i < m; ++i) {
-                const size_t src = panel_index(geo, m, i, k), dst = static_cast<size_t>(k) * m + i;
-                out.y[dst] = (hY[src] / rn[i]) * c_scale[k];
-            }
-            out.primal_obj[k] = mem[k].r.primal_obj;
-            out.residuals[k] = mem[k].r.kkt;
-            out.gap[k] = mem[k].r.rel_gap;
-            out.iter[k] = mem[k].final_iter;
-            std::strncpy(out.status + 64 * k, mem[k].status.c_str(), 63);
-        }
+        HPRLP_batched_results out = collect_results(w, L, certs);
         out.setup_time = setup_time;
         out.solve_time = solve_time;
-        out.power_time = power_time;
+        out.power_time = shared.power_time;
         out.time = setup_time + solve_time;
         return out;
     } catch (const std::exception &e) {
@@ -1449,6 +1413,8 @@ HPRLP_batched_results solve_batched_impl(const LP_info_cpu *model, int batch_siz
 }
 
 }  // namespace hprlp
+
+using namespace hprlp;
 
 extern "C" HPRLP_batched_results solve_batched(const LP_info_cpu *model, int batch_size, const HPRLP_FLOAT *C_in,
                                                const HPRLP_FLOAT *AL_in, const HPRLP_FLOAT *AU_in,

@@ -634,6 +634,45 @@ def form_select(facts, hooks=None):
     return out
 
 
+class CBatchedPrepared(C.Structure):  # include/hprlp_amd.h: hprlp_batched_prepared
+    _fields_ = [(k, c_dbl_p) for k in ("C", "AL", "AU", "l", "u", "scalars", "X0", "Y0", "X_back", "Y_back", "z_back")] + \
+               [("Bp", C.c_int), ("Bc", C.c_int), ("pad", C.c_double), ("panel", c_dbl_p), ("panel_back", c_dbl_p),
+                ("panel_index", C.POINTER(C.c_long))]
+
+
+BATCH_SCALARS = ("b_scale", "c_scale", "norm_b", "norm_c", "norm_b_org", "norm_c_org", "sigma")
+
+
+def batched_prepare_host(rn, cn, Cmat, AL, AU, l, u, X0=None, Y0=None, use_bc_scaling=True, pad=0.0):
+    """Host only (hprlp_batched_prepare_host): what solve_batched does to a batch's vectors before anything is uploaded.  rn (m) /
+    cn (n): the shared matrix' row / column scaling; Cmat, l, u, X0: (n, B); AL, AU, Y0: (m, B).  Returns a dict: the scaled C, AL,
+    AU, l, u; the BATCH_SCALARS (B each); X0, Y0 scaled and X_back, Y_back mapped back as a solution is (None without a start);
+    z_back (the scaled C mapped as a solution's z); Bp, Bc; panel (the scaled C as a device panel, flat, padding = pad),
+    panel_back (n, B) and panel_index (n, B)."""
+    F = lambda a: None if a is None else np.asfortranarray(a, dtype=np.float64)
+    rn, cn = _as(rn, np.float64), _as(cn, np.float64)
+    m, n, B = len(rn), len(cn), np.asarray(Cmat).shape[1]
+    ins = [F(a) for a in (Cmat, AL, AU, l, u, X0, Y0)]
+    for a, rows in zip(ins, (n, m, m, n, n, n, m)):
+        if a is not None and a.shape != (rows, B):
+            raise ValueError("batched_prepare_host: an array of shape %s where (%d, %d) is expected" % (a.shape, rows, B))
+    Bp = (B + 63) // 64 * 64  # room for any padding: the library's Bp is at most the next multiple of 64
+    new = lambda rows, cols=B: np.zeros((rows, cols), order="F")
+    out = dict(C=new(n), AL=new(m), AU=new(m), l=new(n), u=new(n), scalars=np.zeros((7, B)),
+               X0=None if X0 is None else new(n), Y0=None if Y0 is None else new(m),
+               X_back=None if X0 is None else new(n), Y_back=None if Y0 is None else new(m), z_back=new(n),
+               panel=np.zeros(n * Bp), panel_back=new(n), panel_index=np.zeros((n, B), dtype=np.int64, order="F"))
+    P = lambda a: None if a is None else a.ctypes.data_as(c_dbl_p)
+    o = CBatchedPrepared(pad=pad, **{k: (v.ctypes.data_as(C.POINTER(C.c_long)) if k == "panel_index" else P(v)) for k, v in out.items()})
+    L = lib()
+    L.hprlp_batched_prepare_host.argtypes = [C.c_int] * 3 + [c_dbl_p] * 9 + [C.c_int, C.POINTER(CBatchedPrepared)]
+    if L.hprlp_batched_prepare_host(m, n, B, P(rn), P(cn), *[P(a) for a in ins], int(use_bc_scaling), C.byref(o)) != 0:
+        raise RuntimeError(L.hprlp_last_error().decode())
+    out.update(Bp=o.Bp, Bc=o.Bc, panel=out["panel"][:n * o.Bp])
+    out.update(zip(BATCH_SCALARS, out.pop("scalars")))
+    return out
+
+
 class Solver:
     """Step-level handle (include/hprlp_amd.h) used by the parity tests and bench.py."""
 

@@ -358,6 +358,25 @@ int hprlp_row_block_plan(int m, int n, const int *rowptr, const int *col, int wi
  * -1 + hprlp_last_error() on the first violation or when the build declines the pattern. */
 int hprlp_tiled_host_check(int m, int n, const int *rowptr, const int *col, int R, int T, double min_dense, long out[6]);
 
+/* host only: what solve_batched does to a batch's vectors before anything is uploaded (hpr-lp-c_amd/csrc/batch_prep.h).  rn (m) /
+ * cn (n): the row / column scaling of the shared matrix; C, l, u (n x B), AL, AU (m x B), X0 (n x B) / Y0 (m x B; either may be
+ * NULL) column-major as solve_batched takes them.  The arrays of `out` are the caller's (NULL: not wanted). */
+typedef struct hprlp_batched_prepared {
+    double *C, *AL, *AU, *l, *u; /* the vectors in scaled units, infinite sides and bounds replaced by +-1e100 */
+    double *scalars;             /* 7 x B, one after the other: b_scale, c_scale, norm_b, norm_c, norm_b_org, norm_c_org, first sigma */
+    double *X0, *Y0;             /* the starts in scaled units ... */
+    double *X_back, *Y_back;     /* ... and those mapped back as a solution's x and y are */
+    double *z_back;              /* the scaled C mapped as a solution's z is (n x B) */
+    int Bp, Bc;                  /* out: the padded batch and the chunk width of the device panels (HPRLP_BATCH_CHUNK is honoured) */
+    double pad;                  /* in: the value of `panel`'s padding */
+    double *panel;               /* n x Bp: the scaled C as a device panel */
+    double *panel_back;          /* n x B: that panel's first B members, column-major again */
+    long *panel_index;           /* n x B: [k * n + i] = where (row i, member k) sits in an n-row panel */
+} hprlp_batched_prepared;
+int hprlp_batched_prepare_host(int m, int n, int B, const double *rn, const double *cn, const double *C, const double *AL,
+                               const double *AU, const double *l, const double *u, const double *X0, const double *Y0,
+                               int use_bc_scaling, hprlp_batched_prepared *out);
+
 /* ---- which kernel form a matrix gets (hpr-lp-c_amd/csrc/form_select.h) as plain data ----------------
  * The rules are host-only functions of the records below; a solver's set-up measures the facts and asks them. */
 typedef struct hprlp_form_built { /* a tiled copy as its builder left it */

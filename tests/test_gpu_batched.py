@@ -40,6 +40,27 @@ def test_example_batch_matches_golden(gpu):
     model.free()
 
 
+def test_two_calls_in_one_process_give_the_same_bits(gpu):
+    """Nothing of a call survives it (graphs, scalar slots, control arrays, the warm-start panels): the same inputs twice, on the
+    2 x 2 matrix of the example with B = 5 (padded to 8), give x, y, z, iter and status bit for bit."""
+    g = json.load(open(os.path.join(HERE, "golden", "known_lps.json")))
+    model = hprlp.Model.from_csr(2, 2, g[0]["rowptr"], g[0]["colind"], [float(v) for v in g[0]["values"]],
+                                 [-INF, -INF], [10, 12], [0, 0], [INF, INF], [-3, -5])
+    B = 5
+    rng = np.random.default_rng(5)
+    Cm = np.array([[-3.0, -5.0]] * B).T * (1 + 0.1 * rng.random((2, B)))
+    AU = np.array([[10.0, 12.0]] * B).T + rng.random((2, B))
+    AL = np.full((2, B), -INF); L = np.zeros((2, B)); U = np.full((2, B), INF)
+    prm = hprlp.Parameters(stop_tol=1e-8, max_iter=200000, use_presolve=False)
+    a = hprlp.solve_batched(model, Cm, AL, AU, L, U, None, prm)
+    b = hprlp.solve_batched(model, Cm, AL, AU, L, U, None, prm)
+    assert a["status"] == b["status"] == ["OPTIMAL"] * B
+    for key in ("x", "y", "z", "iter"):
+        assert np.array_equal(a[key], b[key]), key
+    assert not np.array_equal(a["x"][:, 0], a["x"][:, 1])  # (the members are not copies of one another)
+    model.free()
+
+
 def make_batch(lp, B, seed):
     """Perturbed copies of one planted LP (BASELINE config 4 recipe): c_k = c(1+0.1 N), AU_k = AU + |N(0,0.1)|."""
     rng = np.random.default_rng(seed)
