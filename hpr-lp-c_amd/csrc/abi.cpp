@@ -626,6 +626,93 @@ extern "C" HPRLP_batched_results hprlp_solve_batched_warm(const LP_info_cpu *mod
                                "hprlp_solve_batched_warm");
 }
 
+// ---- resident batches (DESIGN.md "Resident batches"): a sequence of batches over one matrix ------------------------------------
+struct hprlp_batched_solver {
+    BatchedSolver *s = nullptr;
+};
+
+extern "C" hprlp_batched_solver *hprlp_batched_solver_create(const LP_info_cpu *model, const HPRLP_parameters *param) {
+    hprlp_batched_solver *h = nullptr;
+    try {
+        if (!model || !model->A) throw std::runtime_error("hprlp_batched_solver_create: null model");
+        int count = 0;
+        if (hipInit(0) != hipSuccess || hipGetDeviceCount(&count) != hipSuccess || count <= 0) {
+            (void)hipGetLastError();
+            throw std::runtime_error("hprlp_batched_solver_create: no usable GPU");
+        }
+        h = new hprlp_batched_solver();
+        h->s = batched_solver_create(model, param);
+        return h;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        delete h;
+        return nullptr;
+    }
+}
+
+extern "C" void hprlp_batched_solver_destroy(hprlp_batched_solver *h) {
+    if (!h) return;
+    batched_solver_destroy(h->s);
+    delete h;
+}
+
+extern "C" int hprlp_batched_solver_solve(hprlp_batched_solver *h, int batch_size, const double *C, const double *AL, const double *AU,
+                                          const double *l, const double *u, const double *obj_constants, const HPRLP_parameters *param,
+                                          const double *X0, const double *Y0, int carry, const hprlp_detection *det,
+                                          hprlp_batched_certificates *certs, HPRLP_batched_results *out) {
+    try {
+        if (!h || !h->s) throw std::runtime_error("hprlp_batched_solver_solve: null solver");
+        if (!out) throw std::runtime_error("hprlp_batched_solver_solve: null results");
+        long mn[8];
+        batched_solver_info(h->s, mn);
+        const int m = static_cast<int>(mn[0]), n = static_cast<int>(mn[1]), B = std::max(batch_size, 0);
+        if (certs && !clear_batched_certificates(certs, B, m, n)) {
+            hprlp_free_batched_certificates(certs);
+            throw std::runtime_error("host allocation of the certificates failed");
+        }
+        check_start(X0, static_cast<long>(n) * B, "X0");
+        check_start(Y0, static_cast<long>(m) * B, "Y0");
+        Detection d;
+        const bool with_det = detection_from(det, &d);
+        std::vector<Certificate> k;
+        HPRLP_batched_results r;
+        batched_solver_solve(h->s, batch_size, C, AL, AU, l, u, obj_constants, param, X0, Y0, carry != 0, with_det ? &d : nullptr,
+                             with_det && certs ? &k : nullptr, &r);
+        if (with_det && certs && !export_batched_certificates(k, certs)) {
+            free_batched_results(&r);
+            hprlp_free_batched_certificates(certs);
+            throw std::runtime_error("host allocation of the certificates failed");
+        }
+        *out = r;
+        return 0;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+extern "C" int hprlp_batched_solver_info(hprlp_batched_solver *h, long out[8]) {
+    try {
+        if (!h || !h->s || !out) throw std::runtime_error("hprlp_batched_solver_info: null solver / output");
+        batched_solver_info(h->s, out);
+        return 0;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+extern "C" int hprlp_batched_solver_seconds(hprlp_batched_solver *h, double out[6]) {
+    try {
+        if (!h || !h->s || !out) throw std::runtime_error("hprlp_batched_solver_seconds: null solver / output");
+        batched_solver_seconds(h->s, out);
+        return 0;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
 extern "C" void hprlp_free_batched_certificates(hprlp_batched_certificates *certs) {
     if (!certs) return;
     for (void *p : {static_cast<void *>(certs->kind), static_cast<void *>(certs->iter), static_cast<void *>(certs->objective),

@@ -17,4 +17,19 @@ HPRLP_batched_results solve_batched_impl(const LP_info_cpu *model, int batch_siz
                                          std::vector<Certificate> *certs, const HPRLP_FLOAT *X0 = nullptr,
                                          const HPRLP_FLOAT *Y0 = nullptr);
 
+// The resident solver behind hprlp_batched_solver_* (DESIGN.md "Resident batches"): the scaled shared matrix, the workspace of
+// the last batch geometry and its captured graphs stay on the device from one batch to the next.  Every function throws on
+// failure; a solve that refuses its arguments leaves the handle as it was.  param of a solve (null: the create's) supplies
+// max_iter, stop_tol, time_limit, check_iter and use_bc_scaling only.  carry: start every member from the previous batch's
+// solution of the same member, taken from the panels on the device (kb_carry_start).
+struct BatchedSolver;
+BatchedSolver *batched_solver_create(const LP_info_cpu *model, const HPRLP_parameters *param);
+void batched_solver_destroy(BatchedSolver *h);
+void batched_solver_solve(BatchedSolver *h, int batch_size, const HPRLP_FLOAT *C, const HPRLP_FLOAT *AL, const HPRLP_FLOAT *AU,
+                          const HPRLP_FLOAT *l, const HPRLP_FLOAT *u, const HPRLP_FLOAT *obj_constants, const HPRLP_parameters *param,
+                          const HPRLP_FLOAT *X0, const HPRLP_FLOAT *Y0, bool carry, const Detection *det,
+                          std::vector<Certificate> *certs, HPRLP_batched_results *out);
+void batched_solver_info(const BatchedSolver *h, long out[8]);       // hprlp_batched_solver_info
+void batched_solver_seconds(const BatchedSolver *h, double out[6]);  // hprlp_batched_solver_seconds
+
 }  // namespace hprlp

@@ -758,8 +758,123 @@ __global__ void __launch_bounds__(1024) kb_finalize(const double *partials, int 
     }
 }
 
+// ---- a batch's way in and out (DESIGN.md "Resident batches") --------------------------------------------------------------
+// Column-major staging (rows x B: member k's vector at k * rows, as the ABI has it) <-> padded panels.  The staging side runs
+// along the rows and the panel side along the members, so a 256-thread workgroup moves a tile of kPanelTile rows x kPanelTile
+// members through LDS (one column of padding: the transposed access walks the banks) and both sides move whole lines: 256
+// contiguous bytes per row of the tile on the staging side; on the panel side min(Bw, 32) members of a row are contiguous,
+// and with Bw < 32 the rows of a chunk follow each other, so the tile's part of a chunk is one run.  Elementwise: the bits
+// are the host path's (to_panel / from_panel, point_to_caller, reduced_cost_to_caller, start_to_scaled).
+constexpr int kPanelTile = 32;
+constexpr int kPanelVectors = 7;  // C, L, U, AL, AU and the starts X0, Y0
+
+// (row, member) of the tile that thread `e` (of 1024 / 4 per thread) touches on the panel side: consecutive e = consecutive addresses
+struct TileElem {
+    int il, kl;  // row and member inside the tile
+};
+__device__ __forceinline__ TileElem panel_side(int e, int W) {
+    const int sub = e / (kPanelTile * W), r = e % (kPanelTile * W);  // the tile's members lie in 32 / W chunks
+    return TileElem{r / W, sub * W + r % W};
+}
+
+struct PanelIn {
+    const double *src[kPanelVectors];  // column-major rows x B
+    double *dst[kPanelVectors];        // padded panels
+    int rows[kPanelVectors];
+};
+// grid (row tiles of the longest vector, member tiles of Bp, vectors): padding members and dead columns become 0.0
+__global__ void __launch_bounds__(256) kb_panel_in(PanelIn a, int B, Geo g) {
+    __shared__ double tile[kPanelTile][kPanelTile + 1];  // [member][row]
+    const int v = blockIdx.z, rows = a.rows[v];
+    const int i0 = blockIdx.x * kPanelTile, k0 = blockIdx.y * kPanelTile;
+    if (i0 >= rows) return;  // (uniform per workgroup)
+    const double *__restrict__ src = a.src[v];
+    double *__restrict__ dst = a.dst[v];
+    const int tx = threadIdx.x % kPanelTile, ty = threadIdx.x / kPanelTile;
+#pragma unroll
+    for (int j = 0; j < kPanelTile; j += 8) {
+        const int k = k0 + ty + j, i = i0 + tx;
+        tile[ty + j][tx] = (k < B && i < rows) ? src[static_cast<size_t>(k) * rows + i] : 0.0;
+    }
+    __syncthreads();
+    const int W = min(g.Bw, kPanelTile);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const TileElem t = panel_side(threadIdx.x + 256 * j, W);
+        const int k = k0 + t.kl, i = i0 + t.il;
+        if (k < g.Bp && i < rows) dst[pidx(g, k / g.Bw, rows, i, k % g.Bw)] = tile[t.kl][t.il];
+    }
+}
+
+struct PanelOut {
+    const double *src[3];    // Xb, Yb, Zb
+    double *dst[3];          // column-major rows x B
+    const double *norm[3];   // cn, rn, cn
+    const double *scale[3];  // b_scale, c_scale, c_scale (per member)
+    int rows[3];
+};
+// The first B members of X_bar / Y_bar / Z_bar in the caller's units, column-major: x = (X / cn) * b_scale[k],
+// y = (Y / rn) * c_scale[k] (point_to_caller) and z = (Z * cn) * c_scale[k] (reduced_cost_to_caller), in that operation order.
+__global__ void __launch_bounds__(256) kb_panel_out(PanelOut a, int B, Geo g) {
+    __shared__ double tile[kPanelTile][kPanelTile + 1];  // [member][row]
+    const int v = blockIdx.z, rows = a.rows[v];
+    const int i0 = blockIdx.x * kPanelTile, k0 = blockIdx.y * kPanelTile;
+    if (i0 >= rows) return;
+    const double *__restrict__ src = a.src[v];
+    const double *__restrict__ norm = a.norm[v];
+    const double *__restrict__ scale = a.scale[v];
+    double *__restrict__ dst = a.dst[v];
+    const int W = min(g.Bw, kPanelTile);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const TileElem t = panel_side(threadIdx.x + 256 * j, W);
+        const int k = k0 + t.kl, i = i0 + t.il;
+        double r = 0.0;
+        if (k < B && i < rows) {
+            const double p = src[pidx(g, k / g.Bw, rows, i, k % g.Bw)];
+            r = (v == 2 ? p * norm[i] : p / norm[i]) * scale[k];
+        }
+        tile[t.kl][t.il] = r;
+    }
+    __syncthreads();
+    const int tx = threadIdx.x % kPanelTile, ty = threadIdx.x / kPanelTile;
+#pragma unroll
+    for (int j = 0; j < kPanelTile; j += 8) {
+        const int k = k0 + ty + j, i = i0 + tx;
+        if (k < B && i < rows) dst[static_cast<size_t>(k) * rows + i] = tile[ty + j][tx];
+    }
+}
+
+// carry: every member starts from the previous batch's solution of the same member.  Per element the composition of the results'
+// map with the previous batch's scales and start_to_scaled with this batch's, each rounding kept: x = (Xb / cn) * b_old[k], then
+// X = (x * cn) / b_new[k]; the same for Y with rn and the c scales.  Reads X_bar / Y_bar in place (before they are zeroed), writes
+// X / Y; padding members get 0.0.
+__global__ void __launch_bounds__(256) kb_carry_start(int n, int m, int B, Geo g, const double *Xb, const double *Yb, double *X, double *Y,
+                                                      const double *col_norm, const double *row_norm, const double *b_old,
+                                                      const double *b_new, const double *c_old, const double *c_new) {
+    const Blk blk = decode_block(g);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int kl = lane % g.Bw, k = blk.chunk * g.Bw + kl;
+    const int sub = lane / g.Bw;
+    const bool live = k < B;
+    const double bo = b_old[k], bn = b_new[k], co = c_old[k], cw = c_new[k];
+    const int r0 = blk.rb * g.rows_per_block + wave * g.rows_per_wave + sub, rs = blk.nrb * g.rows_per_block;
+    for (int r = r0; r < n; r += rs) {
+        const size_t t = pidx(g, blk.chunk, n, r, kl);
+        const double cn = col_norm[r];
+        const double x = (Xb[t] / cn) * bo;
+        X[t] = live ? (x * cn) / bn : 0.0;
+    }
+    for (int r = r0; r < m; r += rs) {
+        const size_t t = pidx(g, blk.chunk, m, r, kl);
+        const double rn = row_norm[r];
+        const double y = (Yb[t] / rn) * co;
+        Y[t] = live ? (y * rn) / cw : 0.0;
+    }
+}
+
 // ---- host side ----------------------------------------------------------------------------------
-// solve_batched_impl at the end of the file is the order of things; every kernel is launched by a named launcher.
+// BatchedSolver::solve at the end of the file is the order of things; every kernel is launched by a named launcher.
 struct BatchWS {
     // -- depends on the matrix only (and on the chunk geometry): ws_matrix_part
     int m = 0, n = 0;
@@ -770,21 +885,28 @@ struct BatchWS {
     int gx = 1, gy = 1;  // row blocks of the n- / m-row launches with partials (the grid is geo.nchunk times that)
     int grid_cap = 0;    // HPRLP_BATCH_GRID of this call: most row blocks of a normal half-step launch (0: as many as the rows need)
     DBuf<int> order_x, order_y;  // launch order of the 4-row groups of A^T / A in kb_half64 (groups with long rows first)
-    // -- depends on this batch: ws_batch_part
+    // -- sized by the padded batch and the chunk geometry, kept while those stay (ws_panels); filled per batch (ws_fill)
     int B = 0, Bp = 0;
     const BatchData *data = nullptr;
     DBuf<double> C, AL, AU, L, U;
     DBuf<double> X, Xh, Xb, DX, Zb, lastX, Y, Yb, DY, Yobj, lastY;
     DBuf<double> sigma, SC, partials;
     DBuf<int> active, kx, ky, rflag;
-    // infeasibility detection (allocated only with it on): previous X_bar / Y_bar, the rays, the certificates' z, b/c scales
-    DBuf<double> prevX, DS, prevY, YS, Zray, bsc, csc;
-    int nslot = B_NSLOT;  // scalar slots per member (B_NSLOT_DETECT with detection on)
+    DBuf<double> bsc, csc, bsc_prev, csc_prev;  // b / c scales per member of this batch and of the one before (kb_carry_start)
+    // infeasibility detection (allocated at its first use): previous X_bar / Y_bar, the rays, the certificates' z
+    DBuf<double> prevX, DS, prevY, YS, Zray;
+    int nslot = B_NSLOT;  // scalar slots per member that fetch() brings back (B_NSLOT_DETECT with detection on; SC holds those always)
     HBuf<double> SC_h;
+    // a batch's way in and out: device block and its pinned twin, column-major regions (BatchedSolver::solve lays them out)
+    DBuf<double> stage_d;
+    HBuf<double> stage_h;
     BatchCtl ctl{};
     double lambda_max = 1.0;
     std::map<int, hipGraphExec_t> graphs;
-    // The captured launches hold lambda_max BY VALUE (HalfArgs): whoever changes it drops them, and run_normal captures anew.
+    double graph_lambda = 0.0;  // the lambda_max the graphs alive were captured with
+    long captures = 0, panel_allocs = 0;
+    // The captured launches hold lambda_max BY VALUE (HalfArgs), and every panel's address: whoever changes one of them drops
+    // them, and run_normal captures anew.
     void drop_graphs() {
         for (auto &kv : graphs) (void)hipGraphExecDestroy(kv.second);
         graphs.clear();
@@ -856,7 +978,9 @@ void run_normal(BatchWS &w, int count) {
             HIP_CHECK(hipStreamEndCapture(w.stream, &g));
             HIP_CHECK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
             HIP_CHECK(hipGraphDestroy(g));
+            if (w.graphs.empty()) w.graph_lambda = w.lambda_max;
             w.graphs[len] = ge;
+            ++w.captures;
         } else {
             ge = it->second;
         }
@@ -1002,6 +1126,7 @@ void weighted_norm(BatchWS &w, bool dxdy_from_movement, std::vector<double> &sig
 void build_order(const DBuf<int> &rowptr_dev, int rows, int subs, DBuf<int> &out) {
     constexpr int kLongGroup = 32;
     const int gr = kRowsPerWave * subs;
+    out.release();
     std::vector<int> rp(static_cast<size_t>(rows) + 1);
     rowptr_dev.download(rp.data(), rp.size());
     const int ng = (rows + gr - 1) / gr;
@@ -1031,15 +1156,16 @@ void build_order(const DBuf<int> &rowptr_dev, int rows, int subs, DBuf<int> &out
 }
 
 // What depends on the (scaled) shared matrix and the chunk geometry alone: grids and order tables (and w.rn / w.cn, which
-// solve_batched_impl fetches first: the batch's vectors are scaled with them).
+// BatchedSolver's constructor fetches: the batch's vectors are scaled with them).
 void ws_matrix_part(BatchWS &w, Solver &shared, const Geo &geo) {
     w.m = shared.m; w.n = shared.n;
     w.shared = &shared;
     w.stream = shared.stream;
     w.geo = geo;
-    if (const char *e = env_get("HPRLP_BATCH_GRID")) w.grid_cap = std::atoi(e);
     w.gx = grid_for(w.n, geo);
     w.gy = grid_for(w.m, geo);
+    w.order_x.release();
+    w.order_y.release();
     if (geo.Bw >= 8) {
         build_order(shared.AT.rowptr, w.n, 64 / geo.Bw, w.order_x);
         build_order(shared.A.rowptr, w.m, 64 / geo.Bw, w.order_y);
@@ -1052,53 +1178,68 @@ std::vector<double> padded(const std::vector<double> &v, int Bp, double pad) {  
     return out;
 }
 
-// What depends on this batch (:479-532): row-major padded panels of its vectors, work vectors, scalar slots, control arrays and,
-// with `detect`, the detection's buffers.  sigma / active: the loop's per-member values (Bp of each), as it starts.
-void ws_batch_part(BatchWS &w, const BatchData &d, const std::vector<double> &sigma, const std::vector<int> &active, bool detect) {
-    const int m = w.m, n = w.n, B = d.B;
-    w.B = B; w.Bp = w.geo.Bp;
-    w.data = &d;
-    const size_t nB = static_cast<size_t>(n) * w.Bp, mB = static_cast<size_t>(m) * w.Bp;
-    {
-        std::vector<double> panel;
-        to_panel(d.C, n, B, w.geo, 0.0, panel); w.C.alloc(nB); w.C.upload(panel.data(), nB);
-        to_panel(d.L, n, B, w.geo, 0.0, panel); w.L.alloc(nB); w.L.upload(panel.data(), nB);
-        to_panel(d.U, n, B, w.geo, 0.0, panel); w.U.alloc(nB); w.U.upload(panel.data(), nB);
-        to_panel(d.AL, m, B, w.geo, 0.0, panel); w.AL.alloc(mB); w.AL.upload(panel.data(), mB);
-        to_panel(d.AU, m, B, w.geo, 0.0, panel); w.AU.alloc(mB); w.AU.upload(panel.data(), mB);
-    }
-    for (DBuf<double> *p : {&w.X, &w.Xh, &w.Xb, &w.DX, &w.Zb, &w.lastX}) p->alloc_zero(nB);
-    for (DBuf<double> *p : {&w.Y, &w.Yb, &w.DY, &w.Yobj, &w.lastY}) p->alloc_zero(mB);
-    w.nslot = detect ? B_NSLOT_DETECT : B_NSLOT;
-    w.SC.alloc_zero(static_cast<size_t>(w.nslot) * w.Bp);
-    w.SC_h.alloc(static_cast<size_t>(w.nslot) * w.Bp);
-    w.partials.alloc_zero(static_cast<size_t>(std::max(w.gx, w.gy)) * (detect ? kRayFormAccs : 3) * w.Bp);
-    w.sigma.alloc(w.Bp); w.active.alloc(w.Bp); w.kx.alloc_zero(w.Bp); w.ky.alloc_zero(w.Bp); w.rflag.alloc_zero(w.Bp);
+// The buffers of a padded batch in w.geo (:479-532): row-major padded panels of the batch's vectors, work vectors, scalar slots
+// (with the detection's: whether a call detects does not move a buffer), control arrays.  Allocation only; ws_fill fills them.
+void ws_panels(BatchWS &w) {
+    const size_t Bp = static_cast<size_t>(w.geo.Bp), nB = w.n * Bp, mB = w.m * Bp;
+    w.Bp = w.geo.Bp;
+    for (DBuf<double> *p : {&w.C, &w.L, &w.U, &w.X, &w.Xh, &w.Xb, &w.DX, &w.Zb, &w.lastX}) p->alloc(nB);
+    for (DBuf<double> *p : {&w.AL, &w.AU, &w.Y, &w.Yb, &w.DY, &w.Yobj, &w.lastY}) p->alloc(mB);
+    for (DBuf<double> *p : {&w.prevX, &w.DS, &w.prevY, &w.YS, &w.Zray}) p->release();
+    w.SC.alloc(B_NSLOT_DETECT * Bp);
+    w.SC_h.alloc(B_NSLOT_DETECT * Bp);
+    w.partials.alloc(static_cast<size_t>(std::max(w.gx, w.gy)) * kRayFormAccs * Bp);
+    for (DBuf<double> *p : {&w.sigma, &w.bsc, &w.csc, &w.bsc_prev, &w.csc_prev}) p->alloc(Bp);
+    for (DBuf<int> *p : {&w.active, &w.kx, &w.ky, &w.rflag}) p->alloc(Bp);
     w.ctl = BatchCtl{w.sigma.p, w.active.p, w.kx.p, w.ky.p, w.rflag.p};
-    w.sigma.upload(sigma.data(), w.Bp);
-    w.active.upload(active.data(), w.Bp);
-    if (detect) {
-        for (DBuf<double> *p : {&w.prevX, &w.DS}) p->alloc_zero(nB);
-        for (DBuf<double> *p : {&w.prevY, &w.YS}) p->alloc_zero(mB);
-        w.bsc.alloc(w.Bp);
-        w.bsc.upload(padded(d.b_scale, w.Bp, 1.0).data(), w.Bp);
-        w.csc.alloc(w.Bp);
-        w.csc.upload(padded(d.c_scale, w.Bp, 1.0).data(), w.Bp);
-    }
+    ++w.panel_allocs;
 }
 
-// Warm start: the starts in scaled units beside the other per-member vectors (the inverse of the results' map) into X / Y, then
-// their projection, the seeding of every panel the first iteration reads, and the iteration-0 evaluation's sums.
-void ws_start(BatchWS &w, const double *X0, const double *Y0) {
-    auto upload = [&w](const double *v0, int rows, const std::vector<double> &norm, const std::vector<double> &scale, DBuf<double> &P) {
-        if (!v0) return;
-        std::vector<double> v(v0, v0 + static_cast<size_t>(rows) * w.B), panel;
-        start_to_scaled(v.data(), rows, w.B, norm.data(), scale);
-        to_panel(v, rows, w.B, w.geo, 0.0, panel);
-        P.upload(panel.data(), panel.size());
-    };
-    upload(X0, w.n, w.cn, w.data->b_scale, w.X);
-    upload(Y0, w.m, w.rn, w.data->c_scale, w.Y);
+template <class T>
+void zero_async(BatchWS &w, DBuf<T> &b) {
+    HIP_CHECK(hipMemsetAsync(b.p, 0, (b.n ? b.n : 1) * sizeof(T), w.stream));
+}
+
+// One batch into the resident buffers, all of it on the stream.  The pinned block holds, in this order: sigma, b_scale, c_scale
+// (Bp doubles each), active (Bp ints in the room of Bp doubles), then the column-major regions of `in` (BatchedSolver::solve
+// wrote all of them there).  carry: X / Y from the panels of the batch before (kb_carry_start, before anything is zeroed;
+// bsc_prev / csc_prev hold that batch's scales).  Zeroed: what a fresh workspace has zeroed -- the work panels, counters, flags, slots and partials.
+void ws_fill(BatchWS &w, const BatchData &d, size_t stage_count, const PanelIn &in, int nvec, bool has_x, bool has_y, bool carry,
+             bool detect) {
+    const int m = w.m, n = w.n;
+    const size_t Bp = static_cast<size_t>(w.Bp);
+    w.B = d.B;
+    w.data = &d;
+    w.nslot = detect ? B_NSLOT_DETECT : B_NSLOT;
+    HIP_CHECK(hipMemcpyAsync(w.stage_d.p, w.stage_h.p, stage_count * sizeof(double), hipMemcpyHostToDevice, w.stream));
+    const double *hd = w.stage_d.p;
+    HIP_CHECK(hipMemcpyAsync(w.sigma.p, hd, Bp * sizeof(double), hipMemcpyDeviceToDevice, w.stream));
+    HIP_CHECK(hipMemcpyAsync(w.bsc.p, hd + Bp, Bp * sizeof(double), hipMemcpyDeviceToDevice, w.stream));
+    HIP_CHECK(hipMemcpyAsync(w.csc.p, hd + 2 * Bp, Bp * sizeof(double), hipMemcpyDeviceToDevice, w.stream));
+    HIP_CHECK(hipMemcpyAsync(w.active.p, hd + 3 * Bp, Bp * sizeof(int), hipMemcpyDeviceToDevice, w.stream));
+    if (carry)
+        hipLaunchKernelGGL(kb_carry_start, grid_of(w, both_grids(w)), dim3(256), 0, w.stream, n, m, w.B, w.geo, w.Xb.p, w.Yb.p, w.X.p,
+                           w.Y.p, w.shared->col_norm.p, w.shared->row_norm.p, w.bsc_prev.p, w.bsc.p, w.csc_prev.p, w.csc.p);
+    for (DBuf<double> *p : {&w.Xh, &w.Xb, &w.DX, &w.Zb, &w.lastX, &w.Yb, &w.DY, &w.Yobj, &w.lastY, &w.SC, &w.partials}) zero_async(w, *p);
+    if (!has_x && !carry) zero_async(w, w.X);
+    if (!has_y && !carry) zero_async(w, w.Y);
+    for (DBuf<int> *p : {&w.kx, &w.ky, &w.rflag}) zero_async(w, *p);
+    if (detect) {
+        if (!w.prevX.p) {
+            for (DBuf<double> *p : {&w.prevX, &w.DS}) p->alloc(n * Bp);
+            for (DBuf<double> *p : {&w.prevY, &w.YS}) p->alloc(m * Bp);
+            ++w.panel_allocs;
+        }
+        for (DBuf<double> *p : {&w.prevX, &w.DS, &w.prevY, &w.YS}) zero_async(w, *p);
+    }
+    const int longest = std::max(n, m);
+    hipLaunchKernelGGL(kb_panel_in, dim3((longest + kPanelTile - 1) / kPanelTile, (w.Bp + kPanelTile - 1) / kPanelTile, nvec), dim3(256), 0,
+                       w.stream, in, w.B, w.geo);
+}
+
+// Warm start: X / Y hold the starts in scaled units (the inverse of the results' map; kb_panel_in or kb_carry_start put them
+// there): their projection, the seeding of every panel the first iteration reads, and the iteration-0 evaluation's sums.
+void ws_start(BatchWS &w) {
     launch_start_seed(w);
     launch_start_col(w);
     launch_start_row(w);
@@ -1307,20 +1448,28 @@ void collect_certificates(BatchWS &w, const BatchLoop &L, std::vector<Certificat
     }
 }
 
-// collect_results :887-935: the bars in the caller's units, and every member's evaluation, iteration and status
+// collect_results :887-935: the bars in the caller's units (kb_panel_out into the staging block, one download), and every
+// member's evaluation, iteration and status
 HPRLP_batched_results collect_results(BatchWS &w, const BatchLoop &L, std::vector<Certificate> *certs) {
-    const BatchData &d = *w.data;
     const int m = w.m, n = w.n, B = w.B;
-    HIP_CHECK(hipStreamSynchronize(w.stream));
-    const std::vector<double> hX = download_panel(w, w.Xb, n), hY = download_panel(w, w.Yb, m), hZ = download_panel(w, w.Zb, n);
-    if (certs) collect_certificates(w, L, certs);
+    const size_t nB = static_cast<size_t>(n) * B, mB = static_cast<size_t>(m) * B;
     HPRLP_batched_results out = alloc_batched_results(m, n, B);
-    std::copy(hX.begin(), hX.end(), out.x);
-    std::copy(hY.begin(), hY.end(), out.y);
-    std::copy(hZ.begin(), hZ.end(), out.z);
-    point_to_caller(out.x, n, B, w.cn.data(), d.b_scale);
-    point_to_caller(out.y, m, B, w.rn.data(), d.c_scale);
-    reduced_cost_to_caller(out.z, n, B, w.cn.data(), d.c_scale);
+    try {
+        double *sd = w.stage_d.p;
+        const PanelOut po{{w.Xb.p, w.Yb.p, w.Zb.p}, {sd, sd + nB, sd + nB + mB}, {w.shared->col_norm.p, w.shared->row_norm.p, w.shared->col_norm.p},
+                          {w.bsc.p, w.csc.p, w.csc.p}, {n, m, n}};
+        hipLaunchKernelGGL(kb_panel_out, dim3((std::max(n, m) + kPanelTile - 1) / kPanelTile, (w.Bp + kPanelTile - 1) / kPanelTile, 3), dim3(256),
+                           0, w.stream, po, B, w.geo);
+        HIP_CHECK(hipMemcpyAsync(w.stage_h.p, sd, (2 * nB + mB) * sizeof(double), hipMemcpyDeviceToHost, w.stream));
+        HIP_CHECK(hipStreamSynchronize(w.stream));
+        std::memcpy(out.x, w.stage_h.p, nB * sizeof(double));
+        std::memcpy(out.y, w.stage_h.p + nB, mB * sizeof(double));
+        std::memcpy(out.z, w.stage_h.p + nB + mB, nB * sizeof(double));
+        if (certs) collect_certificates(w, L, certs);
+    } catch (...) {
+        free_batched_results(&out);
+        throw;
+    }
     for (int k = 0; k < B; ++k) {
         out.primal_obj[k] = L.mem[k].r.primal_obj;
         out.residuals[k] = L.mem[k].r.kkt;
@@ -1340,53 +1489,160 @@ void warm_batched_tu() {
     (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&kb_finalize));
 }
 
-HPRLP_batched_results solve_batched_impl(const LP_info_cpu *model, int batch_size, const HPRLP_FLOAT *C_in, const HPRLP_FLOAT *AL_in,
-                                         const HPRLP_FLOAT *AU_in, const HPRLP_FLOAT *l_in, const HPRLP_FLOAT *u_in,
-                                         const HPRLP_FLOAT *obj_constants, const HPRLP_parameters *param, const Detection *det,
-                                         std::vector<Certificate> *certs, const HPRLP_FLOAT *X0, const HPRLP_FLOAT *Y0) {
-    if (!model || !model->A || batch_size <= 0 || !C_in || !AL_in || !AU_in || !l_in || !u_in)
-        return make_batched_error("ERROR", model ? model->m : 0, model ? model->n : 0, std::max(batch_size, 0));
-    const int m = model->m, n = model->n, B = batch_size;
+// ---- the resident solver (DESIGN.md "Resident batches") -------------------------------------------------------------------
+// Over the handle's life: the scaled shared matrix, its norms on the host, the created lambda_max, the staging blocks (they only
+// grow).  While Bp and Bc stay: order tables, every panel and control buffer at its address, and (also while the grid cap
+// and the lambda a call starts with stay) the captured graphs.  Per call: prepare_batch, ws_fill, the loop, the results.
+struct BatchedSolver {
+    int m = 0, n = 0;
+    double obj_constant = 0.0;
+    HPRLP_parameters param;
+    Solver shared;  // (before w: the workspace goes first)
+    BatchWS w;
+    double lambda_created = 1.0;
+    bool have_geo = false;   // w holds a workspace
+    bool have_prev = false;  // the last call succeeded: X_bar / Y_bar of prev_B members and their scales are on the device,
+    int prev_B = 0;          // ... and their caller's-units copy is at the front of w.stage_h (x, then y)
+    long solves = 0;
+    double seconds[6] = {0, 0, 0, 0, 0, 0};
+
+    BatchedSolver(const LP_info_cpu *model, const HPRLP_parameters *p);
+    void solve(int B, const double *C, const double *AL, const double *AU, const double *l, const double *u, const double *obj_constants,
+               const HPRLP_parameters *p, const double *X0, const double *Y0, bool carry, const Detection *det,
+               std::vector<Certificate> *certs, HPRLP_batched_results *out);
+};
+
+BatchedSolver::BatchedSolver(const LP_info_cpu *model, const HPRLP_parameters *p) {
+    if (!model || !model->A) throw std::runtime_error("batched solver: null model");
+    m = model->m; n = model->n;
+    obj_constant = model->obj_constant;
+    param = p ? *p : HPRLP_parameters();
+    param.use_presolve = false;
+    const auto t0 = time_now();
+    // shared-A scaling with zero vectors and b/c scaling off (:959-981)
+    std::vector<double> zero_m(m, 0.0), zero_n(n, 0.0);
+    LP_info_cpu mat{};
+    mat.m = m; mat.n = n; mat.A = model->A;
+    mat.AL = zero_m.data(); mat.AU = zero_m.data(); mat.c = zero_n.data(); mat.l = zero_n.data(); mat.u = zero_n.data();
+    HPRLP_parameters mp = param;
+    mp.use_bc_scaling = false;
+    shared.verbose = false;
+    shared.allow_reorder = false;  // the panels and the returned X / Y / Z are in the caller's numbering
+    shared.setup(&mat, &mp);
+    shared.scale();
+    w.rn.resize(m); w.cn.resize(n);
+    shared.row_norm.download(w.rn.data(), m);
+    shared.col_norm.download(w.cn.data(), n);
+    w.m = m; w.n = n;
+    w.shared = &shared;
+    w.stream = shared.stream;
+    seconds[0] = time_since(t0);
+    // lambda_max on the scaled shared matrix (:994-1001)
+    // (test hook HPRLP_BATCH_LAMBDA: the caller's value instead, so that a reference can run on the same bits)
+    const auto t1 = time_now();
+    const char *lambda_hook = env_get("HPRLP_BATCH_LAMBDA");
+    lambda_created = lambda_hook ? std::strtod(lambda_hook, nullptr) : shared.power_iteration(5000, 1.0e-4, nullptr) * 1.01;
+    if (!(lambda_created > 0.0) || !std::isfinite(lambda_created)) throw std::runtime_error("HPRLP_BATCH_LAMBDA is not a positive finite number");
+    seconds[1] = time_since(t1);
+}
+
+void BatchedSolver::solve(int B, const double *C_in, const double *AL_in, const double *AU_in, const double *l_in, const double *u_in,
+                          const double *obj_constants, const HPRLP_parameters *p, const double *X0, const double *Y0, bool carry,
+                          const Detection *det, std::vector<Certificate> *certs, HPRLP_batched_results *out) {
+    // -- everything that can refuse the call, before the handle changes
+    if (!out) throw std::runtime_error("batched solver: null results");
+    if (B <= 0) throw std::runtime_error("batched solver: batch_size must be positive");
+    if (!C_in || !AL_in || !AU_in || !l_in || !u_in) throw std::runtime_error("batched solver: null C / AL / AU / l / u");
+    const size_t nB = static_cast<size_t>(n) * B, mB = static_cast<size_t>(m) * B;
+    if (carry) {
+        if (X0 || Y0) throw std::runtime_error("batched solver: carry takes its starts from the previous batch; X0 and Y0 must be null");
+        if (!have_prev) throw std::runtime_error("batched solver: carry needs a previous successful solve on this handle");
+        if (B != prev_B)
+            throw std::runtime_error("batched solver: carry needs the previous batch_size (" + std::to_string(prev_B) + "), got " +
+                                     std::to_string(B));
+    }
+    const int Bp = padded_batch(B), Bc = choose_chunk(m, n, Bp);  // (HPRLP_BATCH_CHUNK: per call)
+    const char *grid_hook = env_get("HPRLP_BATCH_GRID");
+    const int grid_cap = grid_hook ? std::atoi(grid_hook) : 0;
+    const bool new_geo = !have_geo || Bp != w.geo.Bp || Bc != w.geo.Bw;
+    if (carry) {
+        if (new_geo) throw std::runtime_error("batched solver: carry needs the previous call's chunk width (HPRLP_BATCH_CHUNK changed)");
+        const double *prev = w.stage_h.p;  // x (n x B) and y (m x B) as the previous call returned them
+        for (size_t i = 0; i < nB + mB; ++i)
+            if (!std::isfinite(prev[i])) throw std::runtime_error("batched solver: carry refused, the previous batch's solution holds a non-finite value");
+    }
+    HPRLP_parameters actual = param;
+    if (p) {
+        actual.max_iter = p->max_iter; actual.stop_tol = p->stop_tol; actual.time_limit = p->time_limit;
+        actual.check_iter = p->check_iter; actual.use_bc_scaling = p->use_bc_scaling;
+    }
+    const bool detect = det && det->on;
+    const bool warm = X0 || Y0 || carry;
+
+    have_prev = false;  // (until this call has succeeded)
     try {
-        HPRLP_parameters actual = param ? *param : HPRLP_parameters();
-        actual.use_presolve = false;
-        const auto setup_start = time_now();
-
-        // shared-A scaling with zero vectors and b/c scaling off (:959-981)
-        std::vector<double> zero_m(m, 0.0), zero_n(n, 0.0);
-        LP_info_cpu mat{};
-        mat.m = m; mat.n = n; mat.A = model->A;
-        mat.AL = zero_m.data(); mat.AU = zero_m.data(); mat.c = zero_n.data(); mat.l = zero_n.data(); mat.u = zero_n.data();
-        HPRLP_parameters mp = actual;
-        mp.use_bc_scaling = false;
-        Solver shared;
-        shared.verbose = false;
-        shared.allow_reorder = false;  // the panels and the returned X / Y / Z are in the caller's numbering
-        shared.setup(&mat, &mp);
-        shared.scale();
-        BatchWS w;
-        w.rn.resize(m); w.cn.resize(n);
-        shared.row_norm.download(w.rn.data(), m);
-        shared.col_norm.download(w.cn.data(), n);
-
-        // per-column vector scaling on the host (:792-885)
-        const BatchData data = prepare_batch(m, n, B, C_in, AL_in, AU_in, l_in, u_in, obj_constants, model->obj_constant, w.rn.data(),
-                                             w.cn.data(), actual.use_bc_scaling);
-
-        // lambda_max on the scaled shared matrix (:994-1001)
-        // (test hook HPRLP_BATCH_LAMBDA: the caller's value instead, so that a reference can run on the same bits)
-        const char *lambda_hook = env_get("HPRLP_BATCH_LAMBDA");
-        w.lambda_max = lambda_hook ? std::strtod(lambda_hook, nullptr) : shared.power_iteration(5000, 1.0e-4, nullptr) * 1.01;
-        if (!(w.lambda_max > 0.0) || !std::isfinite(w.lambda_max)) throw std::runtime_error("HPRLP_BATCH_LAMBDA is not a positive finite number");
-
-        const bool detect = det && det->on;
-        const int Bp = padded_batch(B);
+        // -- host: per-column vector scaling (:792-885), and everything into the pinned block
+        const auto t_prep = time_now();
+        const BatchData data = prepare_batch(m, n, B, C_in, AL_in, AU_in, l_in, u_in, obj_constants, obj_constant, w.rn.data(), w.cn.data(),
+                                             actual.use_bc_scaling);
         BatchLoop L(data, Bp, actual, detect ? det : nullptr);
-        ws_matrix_part(w, shared, make_geo(Bp, choose_chunk(m, n, Bp)));
-        ws_batch_part(w, data, L.sigma, L.active, detect);
-        if (X0 || Y0) ws_start(w, X0, Y0);
-        HIP_CHECK(hipDeviceSynchronize());
-        const double setup_time = time_since(setup_start);
+        const size_t hdr = 4 * static_cast<size_t>(Bp);
+        const size_t stage_count = hdr + 3 * nB + 2 * mB + (X0 ? nB : 0) + (Y0 ? mB : 0);
+        if (w.stage_h.n < stage_count) {
+            w.stage_h.alloc(stage_count, /*zero=*/false);
+            w.stage_d.alloc(stage_count);
+        }
+        double *sh = w.stage_h.p;
+        const std::vector<double> bs = padded(data.b_scale, Bp, 1.0), cs = padded(data.c_scale, Bp, 1.0);
+        std::copy(L.sigma.begin(), L.sigma.end(), sh);
+        std::copy(bs.begin(), bs.end(), sh + Bp);
+        std::copy(cs.begin(), cs.end(), sh + 2 * Bp);
+        std::memcpy(sh + 3 * Bp, L.active.data(), sizeof(int) * Bp);
+        PanelIn in{};
+        int nvec = 0;
+        size_t off = hdr;
+        auto region = [&](const double *src, size_t count, int rows, double *panel) {
+            if (src) std::memcpy(sh + off, src, count * sizeof(double));
+            in.src[nvec] = w.stage_d.p + off;  // (the panel's address: below, once the workspace is there)
+            in.rows[nvec] = rows;
+            in.dst[nvec] = panel;
+            off += count;
+            return nvec++;
+        };
+        const int iC = region(data.C.data(), nB, n, nullptr), iL = region(data.L.data(), nB, n, nullptr), iU = region(data.U.data(), nB, n, nullptr);
+        const int iAL = region(data.AL.data(), mB, m, nullptr), iAU = region(data.AU.data(), mB, m, nullptr);
+        int iX = -1, iY = -1;
+        if (X0) {
+            iX = region(X0, nB, n, nullptr);
+            start_to_scaled(sh + off - nB, n, B, w.cn.data(), data.b_scale);
+        }
+        if (Y0) {
+            iY = region(Y0, mB, m, nullptr);
+            start_to_scaled(sh + off - mB, m, B, w.rn.data(), data.c_scale);
+        }
+        seconds[2] = time_since(t_prep);
+
+        // -- device: the workspace where the geometry is new, this batch into it, the start
+        const auto t_fill = time_now();
+        w.lambda_max = lambda_created;  // not what an earlier call bumped it to: a call does not depend on the handle's history
+        if (new_geo) {
+            w.drop_graphs();
+            have_geo = false;
+            ws_matrix_part(w, shared, make_geo(Bp, Bc));
+            ws_panels(w);
+            have_geo = true;
+        }
+        if (grid_cap != w.grid_cap || (!w.graphs.empty() && w.graph_lambda != w.lambda_max)) w.drop_graphs();
+        w.grid_cap = grid_cap;
+        in.dst[iC] = w.C.p; in.dst[iL] = w.L.p; in.dst[iU] = w.U.p; in.dst[iAL] = w.AL.p; in.dst[iAU] = w.AU.p;
+        if (iX >= 0) in.dst[iX] = w.X.p;
+        if (iY >= 0) in.dst[iY] = w.Y.p;
+        std::swap(w.bsc, w.bsc_prev);
+        std::swap(w.csc, w.csc_prev);
+        ws_fill(w, data, stage_count, in, nvec, X0 != nullptr, Y0 != nullptr, carry, detect);
+        if (warm) ws_start(w);
+        HIP_CHECK(hipStreamSynchronize(w.stream));
+        seconds[3] = time_since(t_fill);
 
         L.solve_start = time_now();
         while (true) {  // one pass per event iteration (periodic check or iteration limit), :1017-1084
@@ -1397,18 +1653,68 @@ HPRLP_batched_results solve_batched_impl(const LP_info_cpu *model, int batch_siz
             const bool restarted = loop_restart(w, L, periodic);
             loop_advance(w, L, restarted);
         }
-        const double solve_time = time_since(L.solve_start);
+        seconds[4] = time_since(L.solve_start);
 
-        HPRLP_batched_results out = collect_results(w, L, certs);
-        out.setup_time = setup_time;
-        out.solve_time = solve_time;
-        out.power_time = shared.power_time;
-        out.time = setup_time + solve_time;
+        const auto t_res = time_now();
+        *out = collect_results(w, L, certs);
+        seconds[5] = time_since(t_res);
+        out->setup_time = seconds[2] + seconds[3];
+        out->solve_time = seconds[4];
+        out->power_time = 0.0;
+        out->time = out->setup_time + out->solve_time;
+        w.data = nullptr;
+        have_prev = true;
+        prev_B = B;
+        ++solves;
+    } catch (...) {
+        // a call that failed half-way: nothing of it is carried, and the next call builds its workspace anew
+        (void)hipStreamSynchronize(w.stream);
+        (void)hipGetLastError();
+        w.drop_graphs();
+        w.data = nullptr;
+        have_geo = false;
+        throw;
+    }
+}
+
+BatchedSolver *batched_solver_create(const LP_info_cpu *model, const HPRLP_parameters *param) { return new BatchedSolver(model, param); }
+void batched_solver_destroy(BatchedSolver *h) { delete h; }
+void batched_solver_solve(BatchedSolver *h, int batch_size, const double *C, const double *AL, const double *AU, const double *l,
+                          const double *u, const double *obj_constants, const HPRLP_parameters *param, const double *X0, const double *Y0,
+                          bool carry, const Detection *det, std::vector<Certificate> *certs, HPRLP_batched_results *out) {
+    if (!h) throw std::runtime_error("batched solver: null handle");
+    h->solve(batch_size, C, AL, AU, l, u, obj_constants, param, X0, Y0, carry, det, certs, out);
+}
+void batched_solver_info(const BatchedSolver *h, long out[8]) {
+    if (!h || !out) throw std::runtime_error("batched solver: null handle / output");
+    const long v[8] = {h->m, h->n, h->solves, h->have_geo ? h->w.geo.Bp : 0, h->have_geo ? h->w.geo.Bw : 0, h->w.captures,
+                       static_cast<long>(h->w.graphs.size()), h->w.panel_allocs};
+    std::copy(v, v + 8, out);
+}
+void batched_solver_seconds(const BatchedSolver *h, double out[6]) {
+    if (!h || !out) throw std::runtime_error("batched solver: null handle / output");
+    std::copy(h->seconds, h->seconds + 6, out);
+}
+
+// One batch and no more: a resident solver that lives for one call.  Its set-up, scaling and power iteration count as this call's set-up.
+HPRLP_batched_results solve_batched_impl(const LP_info_cpu *model, int batch_size, const HPRLP_FLOAT *C_in, const HPRLP_FLOAT *AL_in,
+                                         const HPRLP_FLOAT *AU_in, const HPRLP_FLOAT *l_in, const HPRLP_FLOAT *u_in,
+                                         const HPRLP_FLOAT *obj_constants, const HPRLP_parameters *param, const Detection *det,
+                                         std::vector<Certificate> *certs, const HPRLP_FLOAT *X0, const HPRLP_FLOAT *Y0) {
+    if (!model || !model->A || batch_size <= 0 || !C_in || !AL_in || !AU_in || !l_in || !u_in)
+        return make_batched_error("ERROR", model ? model->m : 0, model ? model->n : 0, std::max(batch_size, 0));
+    try {
+        BatchedSolver h(model, param);
+        HPRLP_batched_results out;
+        h.solve(batch_size, C_in, AL_in, AU_in, l_in, u_in, obj_constants, nullptr, X0, Y0, false, det, certs, &out);
+        out.setup_time += h.seconds[0] + h.seconds[1];
+        out.power_time = h.shared.power_time;
+        out.time = out.setup_time + out.solve_time;
         return out;
     } catch (const std::exception &e) {
         set_last_error(e.what());
         std::cerr << "[error] solve_batched failed: " << e.what() << std::endl;
-        return make_batched_error("ERROR", m, n, B);
+        return make_batched_error("ERROR", model->m, model->n, batch_size);
     }
 }
 

@@ -127,10 +127,13 @@ struct HBuf {
     HBuf(const HBuf &) = delete;
     HBuf &operator=(const HBuf &) = delete;
     ~HBuf() { if (p) (void)hipHostFree(p); }
-    void alloc(size_t count) {
-        n = count;
+    void alloc(size_t count, bool zero = true) {  // (again: the block before is freed)
+        if (p) (void)hipHostFree(p);
+        p = nullptr;
+        n = 0;
         HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&p), (count ? count : 1) * sizeof(T), hipHostMallocDefault));
-        std::memset(p, 0, (count ? count : 1) * sizeof(T));
+        n = count;
+        if (zero) std::memset(p, 0, (count ? count : 1) * sizeof(T));
     }
     T &operator[](size_t i) { return p[i]; }
 };

@@ -164,6 +164,14 @@ def lib():
     L.hprlp_solve_batched_warm.argtypes = [C.POINTER(CLPInfo), C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p,
                                            C.POINTER(CParameters), c_dbl_p, c_dbl_p, C.POINTER(CDetection),
                                            C.POINTER(CBatchedCertificates)]
+    L.hprlp_batched_solver_create.restype = C.c_void_p
+    L.hprlp_batched_solver_create.argtypes = [C.POINTER(CLPInfo), C.POINTER(CParameters)]
+    L.hprlp_batched_solver_destroy.argtypes = [C.c_void_p]
+    L.hprlp_batched_solver_solve.argtypes = [C.c_void_p, C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p,
+                                             C.POINTER(CParameters), c_dbl_p, c_dbl_p, C.c_int, C.POINTER(CDetection),
+                                             C.POINTER(CBatchedCertificates), C.POINTER(CBatchedResults)]
+    L.hprlp_batched_solver_info.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
+    L.hprlp_batched_solver_seconds.argtypes = [C.c_void_p, c_dbl_p]
     L.hprlp_solver_set_start.argtypes = [C.c_void_p, c_dbl_p, c_dbl_p]
     L.hprlp_solver_set_data.argtypes = [C.c_void_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]
     L.hprlp_solver_resolve.argtypes = [C.c_void_p, C.c_double, c_dbl_p, c_dbl_p, C.POINTER(CResults), C.POINTER(CTraceRow),
@@ -538,6 +546,74 @@ def solve_batched_warm(model, Cmat, AL, AU, l, u, X0=None, Y0=None, obj_constant
     if det is not None:
         out["certificates"] = _batched_certificates(cc)
     return out
+
+
+class BatchedSolver:
+    """A sequence of batches over one matrix (hprlp_batched_solver_*, DESIGN.md "Resident batches"): the scaled matrix, its
+    lambda_max, the panels and the captured graphs stay on the GPU between solve() calls.  Raises RuntimeError with the library's
+    message where the C call fails (creation without a GPU, a refused solve); a refused solve leaves the solver usable."""
+
+    _INFO = ("m", "n", "solves", "Bp", "Bc", "graph_captures", "graphs_alive", "panel_allocations")
+    _SECONDS = ("create_setup", "create_power", "prep", "upload", "loop", "results")
+
+    def __init__(self, model, param=None):
+        self.model = model
+        self._h = lib().hprlp_batched_solver_create(model._ptr, C.byref((param or Parameters(use_presolve=False)).to_c()))
+        if not self._h:
+            raise RuntimeError("hprlp_batched_solver_create failed: " + last_error())
+
+    def solve(self, Cmat, AL, AU, l, u, obj_constants=None, X0=None, Y0=None, carry=False, param=None, eps_primal=None,
+              eps_dual=None):
+        """One batch, arguments and result as solve_batched_warm() (param None: the constructor's).  carry=True: every member
+        starts from the previous solve()'s solution of the same member, taken from the panels on the GPU (no X0 / Y0, same
+        batch size).  X0 / Y0 are checked for shape here and for finite entries by the library."""
+        if not self._h:
+            raise RuntimeError("BatchedSolver: closed")
+        B = np.asarray(Cmat).shape[1]
+
+        def panel(V, rows, name):
+            if V is None:
+                return None
+            a = np.asfortranarray(V, dtype=np.float64)
+            if a.shape != (rows, B):
+                raise ValueError(f"warm start: {name} must have shape ({rows}, {B}), got {a.shape}")
+            return a
+        X0, Y0 = panel(X0, self.model.n, "X0"), panel(Y0, self.model.m, "Y0")
+        det = _detection_arg(eps_primal, eps_dual)
+        cc = CBatchedCertificates()
+        cprm = None if param is None else param.to_c()
+
+        def call(B, args, cp):
+            res = CBatchedResults()
+            rc = lib().hprlp_batched_solver_solve(self._h, B, *args, None if cprm is None else C.byref(cprm), _dptr(X0), _dptr(Y0),
+                                                  int(bool(carry)), C.byref(det) if det is not None else None,
+                                                  C.byref(cc) if det is not None else None, C.byref(res))
+            if rc != 0:
+                if det is not None:
+                    lib().hprlp_free_batched_certificates(C.byref(cc))
+                raise RuntimeError("hprlp_batched_solver_solve failed: " + last_error())
+            return res
+        out = _batched_call(call, self.model, Cmat, AL, AU, l, u, obj_constants, param)
+        if det is not None:
+            out["certificates"] = _batched_certificates(cc)
+        return out
+
+    def info(self):
+        out = (C.c_long * 8)()
+        if lib().hprlp_batched_solver_info(self._h, out) != 0:
+            raise RuntimeError(last_error())
+        return dict(zip(self._INFO, [int(v) for v in out]))
+
+    def seconds(self):
+        out = (C.c_double * 6)()
+        if lib().hprlp_batched_solver_seconds(self._h, out) != 0:
+            raise RuntimeError(last_error())
+        return dict(zip(self._SECONDS, [float(v) for v in out]))
+
+    def close(self):
+        if self._h:
+            lib().hprlp_batched_solver_destroy(self._h)
+            self._h = None
 
 
 def _batched_call(fn, model, Cmat, AL, AU, l, u, obj_constants, param):

@@ -148,6 +148,37 @@ HPRLP_batched_results hprlp_solve_batched_warm(const LP_info_cpu *model, int bat
                                                const double *AU, const double *l, const double *u, const double *obj_constants,
                                                const HPRLP_parameters *param, const double *X0, const double *Y0,
                                                const hprlp_detection *det, hprlp_batched_certificates *certs);
+
+/* ---- resident batches: a sequence of batches over one matrix (DESIGN.md "Resident batches") ---------------------------------
+ * What solve_batched() redoes at every call although only the batch has changed -- the shared matrix' set-up and scaling, the
+ * power iteration, the launch-order tables, the panels' allocation, the graph captures -- stays with the handle. */
+typedef struct hprlp_batched_solver hprlp_batched_solver; /* opaque */
+
+/* set-up of the shared matrix exactly as solve_batched does it (zero vectors, b/c scaling off, no reordering, no presolve),
+ * scale(), row_norm / col_norm to the host, lambda_max = 1.01 x power iteration (test hook HPRLP_BATCH_LAMBDA is read HERE).
+ * NULL + hprlp_last_error() on failure (no GPU included). */
+hprlp_batched_solver *hprlp_batched_solver_create(const LP_info_cpu *model, const HPRLP_parameters *param);
+void hprlp_batched_solver_destroy(hprlp_batched_solver *h);
+
+/* One batch.  Arguments as hprlp_solve_batched_warm.  param (NULL: create's) supplies max_iter, stop_tol, time_limit, check_iter
+ * and use_bc_scaling only.  carry != 0: every member starts from the PREVIOUS batch's solution of the same member, taken from
+ * the panels still on the device (needs X0 == Y0 == NULL, a previous successful solve on this handle, and the same batch_size;
+ * refused when that solution holds a non-finite value).  The results equal those of a fresh hprlp_solve_batched_warm call with
+ * the same arguments (carry: with X0 / Y0 = the previous results' x / y) bit for bit, whatever the handle has solved before.
+ * out->setup_time is this call's preparation, out->solve_time its loop, out->power_time 0, out->time their sum.
+ * 0, or -1 + hprlp_last_error() with the handle unchanged and still usable. */
+int hprlp_batched_solver_solve(hprlp_batched_solver *h, int batch_size, const double *C, const double *AL, const double *AU,
+                               const double *l, const double *u, const double *obj_constants, const HPRLP_parameters *param,
+                               const double *X0, const double *Y0, int carry, const hprlp_detection *det,
+                               hprlp_batched_certificates *certs, HPRLP_batched_results *out);
+
+/* out = {m, n, solves so far, Bp, Bc of the last solve, graph captures in total, graphs alive,
+ *        panel (re)allocations in total} */
+int hprlp_batched_solver_info(hprlp_batched_solver *h, long out[8]);
+
+/* seconds: {create: set-up + scaling, create: power iteration,
+ *           last solve: host prep, staging upload + panel kernels + start, loop, results' way back} */
+int hprlp_batched_solver_seconds(hprlp_batched_solver *h, double out[6]);
 /* After hprlp_solver_init, before hprlp_solver_run: the start of the next run (caller's units; both NULL: the zero start,
  * evaluated as a start).  -1 + hprlp_last_error() for a sharded solver or a non-finite entry. */
 int hprlp_solver_set_start(hprlp_solver *s, const double *x0, const double *y0);
