@@ -691,6 +691,75 @@ extern "C" int hprlp_batched_solver_solve(hprlp_batched_solver *h, int batch_siz
     }
 }
 
+extern "C" int hprlp_batched_solver_solve_device(hprlp_batched_solver *h, int batch_size, const double *dC, const double *dAL,
+                                                 const double *dAU, const double *dl, const double *du, const double *obj_constants,
+                                                 const HPRLP_parameters *param, const double *dX0, const double *dY0, int carry,
+                                                 const hprlp_detection *det, hprlp_batched_certificates *certs, void *stream,
+                                                 double *dx, double *dy, double *dz, hprlp_batched_scalars *out) {
+    try {
+        if (!h || !h->s) throw std::runtime_error("hprlp_batched_solver_solve_device: null solver");
+        if (!out) throw std::runtime_error("hprlp_batched_solver_solve_device: null scalars");
+        long mn[8];
+        batched_solver_info(h->s, mn);
+        const int m = static_cast<int>(mn[0]), n = static_cast<int>(mn[1]), B = std::max(batch_size, 0);
+        if (certs && !clear_batched_certificates(certs, B, m, n)) {
+            hprlp_free_batched_certificates(certs);
+            throw std::runtime_error("host allocation of the certificates failed");
+        }
+        Detection d;
+        const bool with_det = detection_from(det, &d);
+        std::vector<Certificate> k;
+        DeviceBatch db;
+        db.stream = stream;
+        db.x = dx; db.y = dy; db.z = dz;
+        db.primal_obj = out->primal_obj; db.residuals = out->residuals; db.gap = out->gap; db.iter = out->iter; db.status = out->status;
+        if (out->status && B > 0) std::memset(out->status, 0, static_cast<size_t>(B) * 64);
+        batched_solver_solve_device(h->s, batch_size, dC, dAL, dAU, dl, du, obj_constants, param, dX0, dY0, carry != 0,
+                                    with_det ? &d : nullptr, with_det && certs ? &k : nullptr, &db);
+        if (with_det && certs && !export_batched_certificates(k, certs)) {
+            hprlp_free_batched_certificates(certs);
+            throw std::runtime_error("host allocation of the certificates failed");
+        }
+        out->time = db.time; out->setup_time = db.setup_time; out->solve_time = db.solve_time; out->power_time = db.power_time;
+        return 0;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+extern "C" int hprlp_batched_solver_set_norms(hprlp_batched_solver *h, int rule) {
+    try {
+        if (!h || !h->s) throw std::runtime_error("hprlp_batched_solver_set_norms: null solver");
+        batched_solver_set_norms(h->s, rule);
+        return 0;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+extern "C" int hprlp_batched_solver_scalars(hprlp_batched_solver *h, double *out) {
+    try {
+        if (!h || !h->s || !out) throw std::runtime_error("hprlp_batched_solver_scalars: null solver / output");
+        return batched_solver_scalars(h->s, out);
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+extern "C" int hprlp_batched_solver_transfer(hprlp_batched_solver *h, long out[4]) {
+    try {
+        if (!h || !h->s || !out) throw std::runtime_error("hprlp_batched_solver_transfer: null solver / output");
+        batched_solver_transfer(h->s, out);
+        return 0;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
 extern "C" int hprlp_batched_solver_info(hprlp_batched_solver *h, long out[8]) {
     try {
         if (!h || !h->s || !out) throw std::runtime_error("hprlp_batched_solver_info: null solver / output");
@@ -1392,9 +1461,15 @@ extern "C" int hprlp_row_block_plan(int m, int n, const int *rowptr, const int *
 extern "C" int hprlp_batched_prepare_host(int m, int n, int B, const double *rn, const double *cn, const double *C, const double *AL,
                                           const double *AU, const double *l, const double *u, const double *X0, const double *Y0,
                                           int use_bc_scaling, hprlp_batched_prepared *out) {
+    return hprlp_batched_prepare_host_rule(m, n, B, rn, cn, C, AL, AU, l, u, X0, Y0, use_bc_scaling, kNormRuleReference, out);
+}
+
+extern "C" int hprlp_batched_prepare_host_rule(int m, int n, int B, const double *rn, const double *cn, const double *C,
+                                               const double *AL, const double *AU, const double *l, const double *u, const double *X0,
+                                               const double *Y0, int use_bc_scaling, int norm_rule, hprlp_batched_prepared *out) {
     try {
         if (m <= 0 || n <= 0 || B <= 0 || !rn || !cn || !C || !AL || !AU || !l || !u || !out) throw std::runtime_error("bad arguments");
-        const BatchData d = prepare_batch(m, n, B, C, AL, AU, l, u, nullptr, 0.0, rn, cn, use_bc_scaling != 0);
+        const BatchData d = prepare_batch(m, n, B, C, AL, AU, l, u, nullptr, 0.0, rn, cn, use_bc_scaling != 0, norm_rule);
         const size_t nB = static_cast<size_t>(n) * B, mB = static_cast<size_t>(m) * B;
         auto give = [](const std::vector<double> &v, double *dst) {
             if (dst) std::copy(v.begin(), v.end(), dst);

@@ -76,18 +76,44 @@ void from_panel(const std::vector<double> &panel, int rows, int B, const Geo &g,
 
 namespace {
 
-double bound_norm_host(const double *AL, const double *AU, int m, size_t off) {  // :332-345
+// b_i = max(|AL_i|, |AU_i|), an infinite side counting 0
+inline double bound_value(double lo, double hi) {
+    const double a = (std::isinf(lo) && lo < 0) ? 0.0 : std::abs(lo);
+    const double b = (std::isinf(hi) && hi > 0) ? 0.0 : std::abs(hi);
+    return std::max(a, b);
+}
+
+// the tree rule (batch_prep.h) for the values value(0) .. value(rows - 1)
+template <class F>
+double tree_sum_of_squares(int rows, F value) {
+    double total = 0.0;
+    for (int s = 0; s < norm_segments(rows); ++s) {
+        double a[kNormLanes];
+        std::fill(a, a + kNormLanes, 0.0);
+        const int i0 = s * kNormSeg, end = std::min(rows, i0 + kNormSeg);
+        for (int i = i0; i < end; ++i) {
+            const double v = value(i);
+            const double t = v * v;
+            a[(i - i0) % kNormLanes] += t;
+        }
+        for (int stride = kNormLanes / 2; stride >= 1; stride /= 2)
+            for (int j = 0; j < stride; ++j) a[j] += a[j + stride];
+        total += a[0];
+    }
+    return total;
+}
+
+double bound_norm_host(const double *AL, const double *AU, int m, size_t off, int rule) {  // :332-345
+    if (rule == kNormRuleTree) return std::sqrt(tree_sum_of_squares(m, [&](int i) { return bound_value(AL[off + i], AU[off + i]); }));
     long double sum = 0.0;
     for (int i = 0; i < m; ++i) {
-        const double lo = AL[off + i], hi = AU[off + i];
-        const double a = (std::isinf(lo) && lo < 0) ? 0.0 : std::abs(lo);
-        const double b = (std::isinf(hi) && hi > 0) ? 0.0 : std::abs(hi);
-        const double v = std::max(a, b);
+        const double v = bound_value(AL[off + i], AU[off + i]);
         sum += static_cast<long double>(v) * v;
     }
     return std::sqrt(static_cast<double>(sum));
 }
-double column_norm_host(const double *X, int n, size_t off) {  // :347-354
+double column_norm_host(const double *X, int n, size_t off, int rule) {  // :347-354
+    if (rule == kNormRuleTree) return std::sqrt(tree_sum_of_squares(n, [&](int i) { return X[off + i]; }));
     long double sum = 0.0;
     for (int i = 0; i < n; ++i) sum += static_cast<long double>(X[off + i]) * X[off + i];
     return std::sqrt(static_cast<double>(sum));
@@ -97,7 +123,8 @@ double column_norm_host(const double *X, int n, size_t off) {  // :347-354
 
 BatchData prepare_batch(int m, int n, int B, const double *C, const double *AL, const double *AU, const double *l, const double *u,
                         const double *obj_constants, double model_obj_constant, const double *rn, const double *cn,
-                        bool use_bc_scaling) {
+                        bool use_bc_scaling, int norm_rule) {
+    if (norm_rule != kNormRuleReference && norm_rule != kNormRuleTree) throw std::runtime_error("prepare_batch: norm rule must be 0 (reference) or 1 (tree)");
     BatchData d;
     d.m = m; d.n = n; d.B = B;
     const size_t nB = static_cast<size_t>(n) * B, mB = static_cast<size_t>(m) * B;
@@ -107,24 +134,24 @@ BatchData prepare_batch(int m, int n, int B, const double *C, const double *AL, 
     for (std::vector<double> *p : {&d.norm_b, &d.norm_c, &d.norm_b_org, &d.norm_c_org, &d.objc}) p->assign(B, 0.0);
     for (int k = 0; k < B; ++k) {
         const size_t om = static_cast<size_t>(k) * m, on = static_cast<size_t>(k) * n;
-        d.norm_b_org[k] = 1.0 + bound_norm_host(hAL.data(), hAU.data(), m, om);
-        d.norm_c_org[k] = 1.0 + column_norm_host(hC.data(), n, on);
+        d.norm_b_org[k] = 1.0 + bound_norm_host(hAL.data(), hAU.data(), m, om, norm_rule);
+        d.norm_c_org[k] = 1.0 + column_norm_host(hC.data(), n, on, norm_rule);
         for (int i = 0; i < m; ++i) { hAL[om + i] /= rn[i]; hAU[om + i] /= rn[i]; }
         for (int i = 0; i < n; ++i) { hC[on + i] /= cn[i]; hL[on + i] *= cn[i]; hU[on + i] *= cn[i]; }
     }
     if (use_bc_scaling) {
         for (int k = 0; k < B; ++k) {
             const size_t om = static_cast<size_t>(k) * m, on = static_cast<size_t>(k) * n;
-            d.b_scale[k] = 1.0 + bound_norm_host(hAL.data(), hAU.data(), m, om);
-            d.c_scale[k] = 1.0 + column_norm_host(hC.data(), n, on);
+            d.b_scale[k] = 1.0 + bound_norm_host(hAL.data(), hAU.data(), m, om, norm_rule);
+            d.c_scale[k] = 1.0 + column_norm_host(hC.data(), n, on, norm_rule);
             for (int i = 0; i < m; ++i) { hAL[om + i] /= d.b_scale[k]; hAU[om + i] /= d.b_scale[k]; }
             for (int i = 0; i < n; ++i) { hC[on + i] /= d.c_scale[k]; hL[on + i] /= d.b_scale[k]; hU[on + i] /= d.b_scale[k]; }
         }
     }
     for (int k = 0; k < B; ++k) {
         const size_t om = static_cast<size_t>(k) * m, on = static_cast<size_t>(k) * n;
-        d.norm_b[k] = bound_norm_host(hAL.data(), hAU.data(), m, om);
-        d.norm_c[k] = column_norm_host(hC.data(), n, on);
+        d.norm_b[k] = bound_norm_host(hAL.data(), hAU.data(), m, om, norm_rule);
+        d.norm_c[k] = column_norm_host(hC.data(), n, on, norm_rule);
         for (int i = 0; i < m; ++i) {
             if (std::isinf(hAL[om + i]) && hAL[om + i] < 0) hAL[om + i] = -kInfReplacement;
             if (std::isinf(hAU[om + i]) && hAU[om + i] > 0) hAU[om + i] = kInfReplacement;

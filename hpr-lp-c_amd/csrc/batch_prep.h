@@ -53,10 +53,22 @@ struct BatchData {
     std::vector<double> b_scale, c_scale, norm_b, norm_c, norm_b_org, norm_c_org, objc;  // per member
     std::vector<double> sigma;            // the first sigma: norm_b / norm_c where both exceed 1e-8, else 1
 };
+// The order in which a norm's sum of squares is added up is part of its bits.  Rule 0 is the reference's: long double,
+// sequentially.  Rule 1, the "tree" rule, is one a GPU can follow, fixed by the vector's length alone (DESIGN.md "Device-resident
+// batches"; kb_data_in / kb_data_bc of batched.hip are its device side, tree_sum_of_squares below its host twin).  The terms
+// t_i = v_i * v_i are rounded to double and never fused with the add.  Rows are cut into segments of kNormSeg consecutive rows;
+// within a segment, lane j of kNormLanes adds the terms with (i - s * kNormSeg) % kNormLanes == j in increasing i, from 0.0; the
+// lane sums are folded by halving strides (a[j] += a[j + stride], stride kNormLanes / 2 ... 1); the segment sums are added in
+// increasing s, from 0.0.
+constexpr int kNormRuleReference = 0, kNormRuleTree = 1;
+constexpr int kNormSeg = 16384, kNormLanes = 256;
+static_assert(kNormSeg % kNormLanes == 0 && (kNormLanes & (kNormLanes - 1)) == 0, "whole rounds of a power of two of lanes");
+constexpr int norm_segments(int rows) { return (rows + kNormSeg - 1) / kNormSeg; }
 // rn (m) / cn (n): the shared matrix' row / column scaling.  obj_constants null: model_obj_constant for every member.
+// norm_rule: kNormRuleReference (the default: the bits of every call before the rule existed) or kNormRuleTree.
 BatchData prepare_batch(int m, int n, int B, const double *C, const double *AL, const double *AU, const double *l, const double *u,
                         const double *obj_constants, double model_obj_constant, const double *rn, const double *cn,
-                        bool use_bc_scaling);
+                        bool use_bc_scaling, int norm_rule = kNormRuleReference);
 
 // ---- caller's units <-> scaled units, column-major rows x B in place ------------------------------------------------------------
 // a start: X0 -> (x * cn) / b_scale[k], Y0 -> (y * rn) / c_scale[k]

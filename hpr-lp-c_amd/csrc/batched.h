@@ -29,6 +29,25 @@ void batched_solver_solve(BatchedSolver *h, int batch_size, const HPRLP_FLOAT *C
                           const HPRLP_FLOAT *l, const HPRLP_FLOAT *u, const HPRLP_FLOAT *obj_constants, const HPRLP_parameters *param,
                           const HPRLP_FLOAT *X0, const HPRLP_FLOAT *Y0, bool carry, const Detection *det,
                           std::vector<Certificate> *certs, HPRLP_batched_results *out);
+// The device entry (DESIGN.md "Device-resident batches"): C .. Y0 are DEVICE arrays, column-major like the host entry's, ordered on
+// `stream` (a hipStream_t); x / y / z are device buffers of n x B / m x B / n x B doubles that receive the solution in the
+// caller's units; the members' scalars go to the host arrays below (B each, status 64 bytes per member; null: not wanted).
+// Every pointer is checked against the runtime's records before anything is launched.
+struct DeviceBatch {
+    void *stream = nullptr;
+    double *x = nullptr, *y = nullptr, *z = nullptr;
+    double *primal_obj = nullptr, *residuals = nullptr, *gap = nullptr;
+    int *iter = nullptr;
+    char *status = nullptr;
+    double time = 0.0, setup_time = 0.0, solve_time = 0.0, power_time = 0.0;
+};
+void batched_solver_solve_device(BatchedSolver *h, int batch_size, const HPRLP_FLOAT *C, const HPRLP_FLOAT *AL, const HPRLP_FLOAT *AU,
+                                 const HPRLP_FLOAT *l, const HPRLP_FLOAT *u, const HPRLP_FLOAT *obj_constants /* host */,
+                                 const HPRLP_parameters *param, const HPRLP_FLOAT *X0, const HPRLP_FLOAT *Y0, bool carry,
+                                 const Detection *det, std::vector<Certificate> *certs, DeviceBatch *dev);
+void batched_solver_set_norms(BatchedSolver *h, int rule);           // the HOST entry's norm rule (batch_prep.h): 0 reference, 1 tree
+int batched_solver_scalars(const BatchedSolver *h, double *out);     // 7 x B of the last successful call; returns B
+void batched_solver_transfer(const BatchedSolver *h, long out[4]);   // hprlp_batched_solver_transfer
 void batched_solver_info(const BatchedSolver *h, long out[8]);       // hprlp_batched_solver_info
 void batched_solver_seconds(const BatchedSolver *h, double out[6]);  // hprlp_batched_solver_seconds
 

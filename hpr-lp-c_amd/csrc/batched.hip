@@ -18,11 +18,13 @@
 // A-tile to feed it and the kernel is bound by panel traffic, not by FMA rate.
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include <iostream>
 #include <limits>
 #include <string>
 #include <type_traits>
+#include <utility>
 
 #include "HPRLP.h"
 #include "batch_prep.h"
@@ -873,6 +875,211 @@ __global__ void __launch_bounds__(256) kb_carry_start(int n, int m, int B, Geo g
     }
 }
 
+// ---- a batch from device memory (DESIGN.md "Device-resident batches") ------------------------------------------------------------
+// prepare_batch (batch_prep.cpp) on the device, operation by operation, the norms by the tree rule of batch_prep.h.  The caller's
+// vectors are column-major rows x B, so a segment of one member is one contiguous run: a 256-thread workgroup per (segment,
+// member, vector group) reads it coalesced, thread j is lane j of the rule, and the workgroup leaves one partial per sum.  Group 0:
+// the n-row vectors C, l, u; group 1: the m-row vectors AL, AU.  Partial (group g, sum a, member k, segment s) sits at
+// part[((g * 2 + a) * B + k) * nseg + s], nseg = the segments of the longer vector.  The per-member scalars live in `scal`,
+// 7 x B in BATCH_SCALARS' order (b_scale, c_scale, norm_b, norm_c, norm_b_org, norm_c_org, sigma), followed by two flag words.
+enum DataScalar : int { DS_B_SCALE = 0, DS_C_SCALE, DS_NORM_B, DS_NORM_C, DS_NORM_B_ORG, DS_NORM_C_ORG, DS_SIGMA, DS_COUNT };
+enum DataFlag : int { DF_START = 0, DF_RESULT, DF_COUNT };  // a non-finite entry in X0 / Y0; in the x / y of the results
+
+__device__ __forceinline__ double bound_value_dev(double lo, double hi) {  // batch_prep.cpp: bound_value
+    const double a = (isinf(lo) && lo < 0) ? 0.0 : fabs(lo);
+    const double b = (isinf(hi) && hi > 0) ? 0.0 : fabs(hi);
+    return fmax(a, b);
+}
+
+// The fold of the tree rule for NSUM sums at once: acc[i] of thread j is lane j's sum.  Strides 128 and 64 cross the waves
+// through LDS; strides 32 .. 1 stay inside wave 0 (lane j takes lane j + stride's value: for j < stride that is a[j] += a[j + stride]).
+// Thread 0 returns with the segment sums in acc.
+template <int NSUM>
+__device__ __forceinline__ void tree_fold(double (&acc)[NSUM]) {
+    static_assert(kNormLanes == 256, "the fold below is written for 256 lanes = 4 waves");
+    __shared__ double red[NSUM][kNormLanes];
+    const int j = threadIdx.x;
+#pragma unroll
+    for (int i = 0; i < NSUM; ++i) red[i][j] = acc[i];
+    __syncthreads();
+    if (j < 128) {
+#pragma unroll
+        for (int i = 0; i < NSUM; ++i) red[i][j] += red[i][j + 128];
+    }
+    __syncthreads();
+    if (j < 64) {
+#pragma unroll
+        for (int i = 0; i < NSUM; ++i) {
+            double v = red[i][j] + red[i][j + 64];
+#pragma unroll
+            for (int stride = 32; stride >= 1; stride >>= 1) v += __shfl_down(v, stride, 64);
+            acc[i] = v;
+        }
+    }
+}
+
+struct DataIn {
+    const double *C, *L, *U, *AL, *AU;  // the caller's, column-major
+    double *oC, *oL, *oU, *oAL, *oAU;   // the staging block's regions
+    const double *cn, *rn;
+    double *part;
+    int n, m, nseg;
+};
+// grid (nseg, B, 2).  AL, AU /= rn; C /= cn; l, u *= cn; sum 0: the caller's values' sum of squares, sum 1: the scaled values'.
+__global__ void __launch_bounds__(kNormLanes) kb_data_in(DataIn a, int B) {
+    const int s = blockIdx.x, k = blockIdx.y, g = blockIdx.z;
+    const int rows = g ? a.m : a.n;
+    const int i0 = s * kNormSeg;
+    if (i0 >= rows) return;  // (uniform per workgroup)
+    const int end = min(rows, i0 + kNormSeg);
+    const size_t base = static_cast<size_t>(k) * rows;
+    double acc[2] = {0.0, 0.0};
+    if (g == 0) {
+        for (int i = i0 + threadIdx.x; i < end; i += kNormLanes) {
+            const double nrm = a.cn[i];
+            const double c = a.C[base + i];
+            const double t0 = c * c;
+            acc[0] += t0;
+            const double cs = c / nrm;
+            const double t1 = cs * cs;
+            acc[1] += t1;
+            a.oC[base + i] = cs;
+            a.oL[base + i] = a.L[base + i] * nrm;
+            a.oU[base + i] = a.U[base + i] * nrm;
+        }
+    } else {
+        for (int i = i0 + threadIdx.x; i < end; i += kNormLanes) {
+            const double nrm = a.rn[i];
+            double lo = a.AL[base + i], hi = a.AU[base + i];
+            const double v0 = bound_value_dev(lo, hi);
+            const double t0 = v0 * v0;
+            acc[0] += t0;
+            lo /= nrm;
+            hi /= nrm;
+            const double v1 = bound_value_dev(lo, hi);
+            const double t1 = v1 * v1;
+            acc[1] += t1;
+            a.oAL[base + i] = lo;
+            a.oAU[base + i] = hi;
+        }
+    }
+    tree_fold<2>(acc);
+    if (threadIdx.x == 0) {
+        a.part[(static_cast<size_t>(g * 2 + 0) * B + k) * a.nseg + s] = acc[0];
+        a.part[(static_cast<size_t>(g * 2 + 1) * B + k) * a.nseg + s] = acc[1];
+    }
+}
+
+// the segment partials of (group g, sum a, member k), added in increasing s from 0.0
+__device__ __forceinline__ double segment_total(const double *part, int g, int a, int B, int k, int nseg, int rows) {
+    const double *p = part + (static_cast<size_t>(g * 2 + a) * B + k) * nseg;
+    double total = 0.0;
+    for (int s = 0; s < norm_segments(rows); ++s) total += p[s];
+    return total;
+}
+
+// one thread per member: norm_b_org, norm_c_org of the caller's data; b_scale, c_scale (1.0 without use_bc_scaling)
+__global__ void __launch_bounds__(256) kb_data_scales(const double *part, int B, int n, int m, int nseg, int use_bc, double *scal) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= B) return;
+    scal[DS_NORM_C_ORG * B + k] = 1.0 + sqrt(segment_total(part, 0, 0, B, k, nseg, n));
+    scal[DS_NORM_B_ORG * B + k] = 1.0 + sqrt(segment_total(part, 1, 0, B, k, nseg, m));
+    scal[DS_C_SCALE * B + k] = use_bc ? 1.0 + sqrt(segment_total(part, 0, 1, B, k, nseg, n)) : 1.0;
+    scal[DS_B_SCALE * B + k] = use_bc ? 1.0 + sqrt(segment_total(part, 1, 1, B, k, nseg, m)) : 1.0;
+}
+
+struct DataBc {
+    double *C, *L, *U, *AL, *AU;  // the staging block's regions, in place
+    const double *X0, *Y0;        // the caller's starts (null: none) ...
+    double *oX0, *oY0;            // ... and their regions
+    const double *cn, *rn;
+    const double *scal;
+    double *part;
+    int *flags;
+    int n, m, nseg;
+};
+// grid (nseg, B, 2).  The divisions by the scales kb_data_scales left (by 1.0 without use_bc_scaling: exact), sum 0: the final
+// values' sum of squares, and only then +-kInfReplacement for infinite sides and bounds.  The starts as start_to_scaled has them:
+// X0 -> (x * cn) / b_scale[k], Y0 -> (y * rn) / c_scale[k]; a non-finite entry of the caller's raises flags[DF_START].
+__global__ void __launch_bounds__(kNormLanes) kb_data_bc(DataBc a, int B) {
+    const int s = blockIdx.x, k = blockIdx.y, g = blockIdx.z;
+    const int rows = g ? a.m : a.n;
+    const int i0 = s * kNormSeg;
+    if (i0 >= rows) return;
+    const int end = min(rows, i0 + kNormSeg);
+    const size_t base = static_cast<size_t>(k) * rows;
+    const double bs = a.scal[DS_B_SCALE * B + k], cs = a.scal[DS_C_SCALE * B + k];
+    double acc[1] = {0.0};
+    bool bad = false;
+    if (g == 0) {
+        for (int i = i0 + threadIdx.x; i < end; i += kNormLanes) {
+            const double c = a.C[base + i] / cs;
+            const double t = c * c;
+            acc[0] += t;
+            a.C[base + i] = c;
+            double lo = a.L[base + i] / bs, hi = a.U[base + i] / bs;
+            if (isinf(lo) && lo < 0) lo = -kInfReplacement;
+            if (isinf(hi) && hi > 0) hi = kInfReplacement;
+            a.L[base + i] = lo;
+            a.U[base + i] = hi;
+            if (a.X0) {
+                const double x = a.X0[base + i];
+                bad = bad || !isfinite(x);
+                a.oX0[base + i] = (x * a.cn[i]) / bs;
+            }
+        }
+    } else {
+        for (int i = i0 + threadIdx.x; i < end; i += kNormLanes) {
+            double lo = a.AL[base + i] / bs, hi = a.AU[base + i] / bs;
+            const double v = bound_value_dev(lo, hi);
+            const double t = v * v;
+            acc[0] += t;
+            if (isinf(lo) && lo < 0) lo = -kInfReplacement;
+            if (isinf(hi) && hi > 0) hi = kInfReplacement;
+            a.AL[base + i] = lo;
+            a.AU[base + i] = hi;
+            if (a.Y0) {
+                const double y = a.Y0[base + i];
+                bad = bad || !isfinite(y);
+                a.oY0[base + i] = (y * a.rn[i]) / cs;
+            }
+        }
+    }
+    if (bad) a.flags[DF_START] = 1;  // (every writer writes the same word)
+    tree_fold<1>(acc);
+    if (threadIdx.x == 0) a.part[(static_cast<size_t>(g * 2) * B + k) * a.nseg + s] = acc[0];
+}
+
+// one thread per member of the PADDED batch: norm_b, norm_c of the final vectors, the first sigma, and the header of the staging
+// block as ws_fill reads it: sigma | b_scale | c_scale (padding members 1.0) | active (ints: 1 for a member, 0 for padding)
+__global__ void __launch_bounds__(256) kb_data_header(const double *part, int B, int Bp, int n, int m, int nseg, double *scal, double *hdr) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= Bp) return;
+    double sigma = 1.0, bs = 1.0, cs = 1.0;
+    if (k < B) {
+        const double nc = sqrt(segment_total(part, 0, 0, B, k, nseg, n)), nb = sqrt(segment_total(part, 1, 0, B, k, nseg, m));
+        if (nb > 1.0e-8 && nc > 1.0e-8) sigma = nb / nc;
+        scal[DS_NORM_B * B + k] = nb;
+        scal[DS_NORM_C * B + k] = nc;
+        scal[DS_SIGMA * B + k] = sigma;
+        bs = scal[DS_B_SCALE * B + k];
+        cs = scal[DS_C_SCALE * B + k];
+    }
+    hdr[k] = sigma;
+    hdr[Bp + k] = bs;
+    hdr[2 * Bp + k] = cs;
+    reinterpret_cast<int *>(hdr + 3 * static_cast<size_t>(Bp))[k] = k < B ? 1 : 0;
+}
+
+// raises *flag where one of the first `count` values of v is not finite (the x / y a device-entry call has just written)
+__global__ void __launch_bounds__(256) kb_flag_nonfinite(const double *x, size_t nx, const double *y, size_t ny, int *flag) {
+    bool bad = false;
+    const size_t stride = static_cast<size_t>(gridDim.x) * blockDim.x;
+    for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < nx + ny; i += stride)
+        bad = bad || !isfinite(i < nx ? x[i] : y[i - nx]);
+    if (bad) *flag = 1;
+}
+
 // ---- host side ----------------------------------------------------------------------------------
 // BatchedSolver::solve at the end of the file is the order of things; every kernel is launched by a named launcher.
 struct BatchWS {
@@ -900,6 +1107,10 @@ struct BatchWS {
     // a batch's way in and out: device block and its pinned twin, column-major regions (BatchedSolver::solve lays them out)
     DBuf<double> stage_d;
     HBuf<double> stage_h;
+    // a device-entry call (DESIGN.md "Device-resident batches"): the segment partials of its norms; the per-member scalars
+    // (DS_COUNT x B) with the DF_COUNT flag words behind them, and their pinned twin
+    DBuf<double> data_part, data_scal;
+    HBuf<double> data_scal_h;
     BatchCtl ctl{};
     double lambda_max = 1.0;
     std::map<int, hipGraphExec_t> graphs;
@@ -1204,6 +1415,7 @@ void zero_async(BatchWS &w, DBuf<T> &b) {
 // (Bp doubles each), active (Bp ints in the room of Bp doubles), then the column-major regions of `in` (BatchedSolver::solve
 // wrote all of them there).  carry: X / Y from the panels of the batch before (kb_carry_start, before anything is zeroed;
 // bsc_prev / csc_prev hold that batch's scales).  Zeroed: what a fresh workspace has zeroed -- the work panels, counters, flags, slots and partials.
+// stage_count 0: a device-entry call, whose kernels have left the header and the regions in the staging block already.
 void ws_fill(BatchWS &w, const BatchData &d, size_t stage_count, const PanelIn &in, int nvec, bool has_x, bool has_y, bool carry,
              bool detect) {
     const int m = w.m, n = w.n;
@@ -1211,7 +1423,7 @@ void ws_fill(BatchWS &w, const BatchData &d, size_t stage_count, const PanelIn &
     w.B = d.B;
     w.data = &d;
     w.nslot = detect ? B_NSLOT_DETECT : B_NSLOT;
-    HIP_CHECK(hipMemcpyAsync(w.stage_d.p, w.stage_h.p, stage_count * sizeof(double), hipMemcpyHostToDevice, w.stream));
+    if (stage_count) HIP_CHECK(hipMemcpyAsync(w.stage_d.p, w.stage_h.p, stage_count * sizeof(double), hipMemcpyHostToDevice, w.stream));
     const double *hd = w.stage_d.p;
     HIP_CHECK(hipMemcpyAsync(w.sigma.p, hd, Bp * sizeof(double), hipMemcpyDeviceToDevice, w.stream));
     HIP_CHECK(hipMemcpyAsync(w.bsc.p, hd + Bp, Bp * sizeof(double), hipMemcpyDeviceToDevice, w.stream));
@@ -1448,6 +1660,26 @@ void collect_certificates(BatchWS &w, const BatchLoop &L, std::vector<Certificat
     }
 }
 
+// the bars in the caller's units, column-major rows x B, to device addresses x, y, z (kb_panel_out)
+void launch_panel_out(BatchWS &w, double *x, double *y, double *z) {
+    const int m = w.m, n = w.n;
+    const PanelOut po{{w.Xb.p, w.Yb.p, w.Zb.p}, {x, y, z}, {w.shared->col_norm.p, w.shared->row_norm.p, w.shared->col_norm.p},
+                      {w.bsc.p, w.csc.p, w.csc.p}, {n, m, n}};
+    hipLaunchKernelGGL(kb_panel_out, dim3((std::max(n, m) + kPanelTile - 1) / kPanelTile, (w.Bp + kPanelTile - 1) / kPanelTile, 3), dim3(256),
+                       0, w.stream, po, w.B, w.geo);
+}
+
+// every member's evaluation, iteration and status (arrays of B; status 64 bytes per member; a null array is not wanted)
+void member_results(const BatchLoop &L, int B, double *primal_obj, double *residuals, double *gap, int *iter, char *status) {
+    for (int k = 0; k < B; ++k) {
+        if (primal_obj) primal_obj[k] = L.mem[k].r.primal_obj;
+        if (residuals) residuals[k] = L.mem[k].r.kkt;
+        if (gap) gap[k] = L.mem[k].r.rel_gap;
+        if (iter) iter[k] = L.mem[k].final_iter;
+        if (status) std::strncpy(status + 64 * k, L.mem[k].status.c_str(), 63);
+    }
+}
+
 // collect_results :887-935: the bars in the caller's units (kb_panel_out into the staging block, one download), and every
 // member's evaluation, iteration and status
 HPRLP_batched_results collect_results(BatchWS &w, const BatchLoop &L, std::vector<Certificate> *certs) {
@@ -1456,10 +1688,7 @@ HPRLP_batched_results collect_results(BatchWS &w, const BatchLoop &L, std::vecto
     HPRLP_batched_results out = alloc_batched_results(m, n, B);
     try {
         double *sd = w.stage_d.p;
-        const PanelOut po{{w.Xb.p, w.Yb.p, w.Zb.p}, {sd, sd + nB, sd + nB + mB}, {w.shared->col_norm.p, w.shared->row_norm.p, w.shared->col_norm.p},
-                          {w.bsc.p, w.csc.p, w.csc.p}, {n, m, n}};
-        hipLaunchKernelGGL(kb_panel_out, dim3((std::max(n, m) + kPanelTile - 1) / kPanelTile, (w.Bp + kPanelTile - 1) / kPanelTile, 3), dim3(256),
-                           0, w.stream, po, B, w.geo);
+        launch_panel_out(w, sd, sd + nB, sd + nB + mB);
         HIP_CHECK(hipMemcpyAsync(w.stage_h.p, sd, (2 * nB + mB) * sizeof(double), hipMemcpyDeviceToHost, w.stream));
         HIP_CHECK(hipStreamSynchronize(w.stream));
         std::memcpy(out.x, w.stage_h.p, nB * sizeof(double));
@@ -1470,14 +1699,94 @@ HPRLP_batched_results collect_results(BatchWS &w, const BatchLoop &L, std::vecto
         free_batched_results(&out);
         throw;
     }
-    for (int k = 0; k < B; ++k) {
-        out.primal_obj[k] = L.mem[k].r.primal_obj;
-        out.residuals[k] = L.mem[k].r.kkt;
-        out.gap[k] = L.mem[k].r.rel_gap;
-        out.iter[k] = L.mem[k].final_iter;
-        std::strncpy(out.status + 64 * k, L.mem[k].status.c_str(), 63);
-    }
+    member_results(L, B, out.primal_obj, out.residuals, out.gap, out.iter, out.status);
     return out;
+}
+
+// ---- the device entry's own steps (DESIGN.md "Device-resident batches") ---------------------------------------------------------
+inline int *data_flags(const BatchWS &w, int B) { return reinterpret_cast<int *>(w.data_scal.p + static_cast<size_t>(DS_COUNT) * B); }
+inline const int *data_flags_host(const BatchWS &w, int B) {
+    return reinterpret_cast<const int *>(w.data_scal_h.p + static_cast<size_t>(DS_COUNT) * B);
+}
+
+// A pointer of the caller's passes only as device memory of `device` that the runtime knows, with room for `count` doubles where
+// the runtime reports the allocation's range.  Nothing is launched before every pointer of a call has passed.
+void check_device_pointer(const void *p, size_t count, int device, const char *name) {
+    const std::string who = std::string("batched solver: ") + name;
+    if (!p) throw std::runtime_error(who + " is null");
+    if (reinterpret_cast<uintptr_t>(p) % sizeof(double)) throw std::runtime_error(who + " is not aligned to 8 bytes");
+    hipPointerAttribute_t attr{};
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+        (void)hipGetLastError();
+        throw std::runtime_error(who + " is not a pointer the HIP runtime knows (a host address?)");
+    }
+    if (attr.type != hipMemoryTypeDevice) throw std::runtime_error(who + " is not device memory");
+    if (attr.device != device)
+        throw std::runtime_error(who + " is memory of device " + std::to_string(attr.device) + ", the solver's is " + std::to_string(device));
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(p)) != hipSuccess || !base) {
+        (void)hipGetLastError();
+        return;  // (no range reported)
+    }
+    const char *end = static_cast<const char *>(base) + size;
+    if (static_cast<const char *>(p) + count * sizeof(double) > end)
+        throw std::runtime_error(who + " is too short: " + std::to_string(count) + " doubles wanted, " +
+                                 std::to_string((end - static_cast<const char *>(p)) / sizeof(double)) + " left in its allocation");
+}
+
+// prepare_batch on the device: the caller's vectors (ordered on `stream`) into the staging block in scaled units, its header, and
+// the per-member scalars on the host -- the BatchData a loop needs (it reads none of the vectors).  `in` gets the regions.
+BatchData device_prep(BatchWS &w, int B, int Bp, const double *C, const double *AL, const double *AU, const double *l, const double *u,
+                      const double *X0, const double *Y0, const double *obj_constants, double model_obj_constant, bool use_bc,
+                      hipStream_t stream, hipEvent_t ready, PanelIn &in, int &nvec) {
+    const int m = w.m, n = w.n, nseg = norm_segments(std::max(n, m));
+    const size_t nB = static_cast<size_t>(n) * B, mB = static_cast<size_t>(m) * B, hdr = 4 * static_cast<size_t>(Bp);
+    const size_t stage_count = hdr + 3 * nB + 2 * mB + (X0 ? nB : 0) + (Y0 ? mB : 0);
+    if (w.stage_d.n < stage_count) w.stage_d.alloc(stage_count);
+    const size_t part_count = static_cast<size_t>(4) * B * nseg, scal_count = static_cast<size_t>(DS_COUNT) * B + DF_COUNT;
+    if (w.data_part.n < part_count) w.data_part.alloc(part_count);
+    if (w.data_scal.n != scal_count) {  // (the flag words sit behind the scalars of exactly B members)
+        w.data_scal.alloc(scal_count);
+        w.data_scal_h.alloc(scal_count);
+    }
+    HIP_CHECK(hipEventRecord(ready, stream));
+    HIP_CHECK(hipStreamWaitEvent(w.stream, ready, 0));
+    double *sd = w.stage_d.p;
+    nvec = 0;
+    size_t off = hdr;
+    auto region = [&](size_t count, int rows) {
+        in.src[nvec] = sd + off;
+        in.rows[nvec] = rows;
+        in.dst[nvec] = nullptr;  // (the panel's address: once the workspace is there)
+        off += count;
+        return const_cast<double *>(in.src[nvec++]);
+    };
+    double *rC = region(nB, n), *rL = region(nB, n), *rU = region(nB, n), *rAL = region(mB, m), *rAU = region(mB, m);
+    double *rX = X0 ? region(nB, n) : nullptr, *rY = Y0 ? region(mB, m) : nullptr;
+    int *flags = data_flags(w, B);
+    HIP_CHECK(hipMemsetAsync(flags, 0, DF_COUNT * sizeof(int), w.stream));
+    const double *cn = w.shared->col_norm.p, *rn = w.shared->row_norm.p;
+    const dim3 grid(nseg, B, 2);
+    hipLaunchKernelGGL(kb_data_in, grid, dim3(kNormLanes), 0, w.stream, DataIn{C, l, u, AL, AU, rC, rL, rU, rAL, rAU, cn, rn, w.data_part.p, n, m, nseg}, B);
+    hipLaunchKernelGGL(kb_data_scales, dim3((B + 255) / 256), dim3(256), 0, w.stream, static_cast<const double *>(w.data_part.p), B, n, m, nseg,
+                       use_bc ? 1 : 0, w.data_scal.p);
+    hipLaunchKernelGGL(kb_data_bc, grid, dim3(kNormLanes), 0, w.stream,
+                       DataBc{rC, rL, rU, rAL, rAU, X0, Y0, rX, rY, cn, rn, w.data_scal.p, w.data_part.p, flags, n, m, nseg}, B);
+    hipLaunchKernelGGL(kb_data_header, dim3((Bp + 255) / 256), dim3(256), 0, w.stream, static_cast<const double *>(w.data_part.p), B, Bp, n, m,
+                       nseg, w.data_scal.p, sd);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(w.data_scal_h.p, w.data_scal.p, static_cast<size_t>(DS_COUNT) * B * sizeof(double) + DF_COUNT * sizeof(int),
+                             hipMemcpyDeviceToHost, w.stream));
+    HIP_CHECK(hipStreamSynchronize(w.stream));
+    BatchData d;
+    d.m = m; d.n = n; d.B = B;
+    const double *h = w.data_scal_h.p;
+    std::vector<double> *dst[DS_COUNT] = {&d.b_scale, &d.c_scale, &d.norm_b, &d.norm_c, &d.norm_b_org, &d.norm_c_org, &d.sigma};
+    for (int i = 0; i < DS_COUNT; ++i) dst[i]->assign(h + static_cast<size_t>(i) * B, h + static_cast<size_t>(i + 1) * B);
+    d.objc.assign(B, model_obj_constant);
+    if (obj_constants) d.objc.assign(obj_constants, obj_constants + B);
+    return d;
 }
 
 }  // namespace
@@ -1492,7 +1801,9 @@ void warm_batched_tu() {
 // ---- the resident solver (DESIGN.md "Resident batches") -------------------------------------------------------------------
 // Over the handle's life: the scaled shared matrix, its norms on the host, the created lambda_max, the staging blocks (they only
 // grow).  While Bp and Bc stay: order tables, every panel and control buffer at its address, and (also while the grid cap
-// and the lambda a call starts with stay) the captured graphs.  Per call: prepare_batch, ws_fill, the loop, the results.
+// and the lambda a call starts with stay) the captured graphs.  Per call: prepare_batch, ws_fill, the loop, the results -- or, for
+// a batch that is in device memory already (DESIGN.md "Device-resident batches"), device_prep in prepare_batch's place, ws_fill
+// without its upload, and kb_panel_out straight into the caller's device buffers.
 struct BatchedSolver {
     int m = 0, n = 0;
     double obj_constant = 0.0;
@@ -1502,14 +1813,25 @@ struct BatchedSolver {
     double lambda_created = 1.0;
     bool have_geo = false;   // w holds a workspace
     bool have_prev = false;  // the last call succeeded: X_bar / Y_bar of prev_B members and their scales are on the device,
-    int prev_B = 0;          // ... and their caller's-units copy is at the front of w.stage_h (x, then y)
-    long solves = 0;
+    int prev_B = 0;          // ... and their caller's-units copy is at the front of w.stage_h (x, then y) -- or, after a
+    bool prev_on_device = false, prev_nonfinite = false;  // device-entry call, went to the caller's buffers and left this flag
+    long solves = 0, device_solves = 0;
     double seconds[6] = {0, 0, 0, 0, 0, 0};
+    int device = 0;                       // the device the matrix lives on
+    int norm_rule = kNormRuleReference;   // of the HOST entry (batched_solver_set_norms); the device entry's is the tree rule
+    hipEvent_t inputs_ready = nullptr;    // device entry: recorded on the caller's stream, waited for by w.stream
+    std::vector<double> last_scalars;     // DS_COUNT x B of the last successful call
+    long staged[2] = {0, 0};              // ... and its staging bytes host -> device, device -> host
 
     BatchedSolver(const LP_info_cpu *model, const HPRLP_parameters *p);
+    ~BatchedSolver() {
+        if (inputs_ready) (void)hipEventDestroy(inputs_ready);
+    }
+    // dev null: the host entry, C .. Y0 host arrays, the results into `out`.  dev set: the device entry, C .. Y0 device arrays
+    // ordered on dev->stream, x / y / z into dev's device buffers and the members' scalars into its host arrays.
     void solve(int B, const double *C, const double *AL, const double *AU, const double *l, const double *u, const double *obj_constants,
                const HPRLP_parameters *p, const double *X0, const double *Y0, bool carry, const Detection *det,
-               std::vector<Certificate> *certs, HPRLP_batched_results *out);
+               std::vector<Certificate> *certs, HPRLP_batched_results *out, DeviceBatch *dev = nullptr);
 };
 
 BatchedSolver::BatchedSolver(const LP_info_cpu *model, const HPRLP_parameters *p) {
@@ -1536,6 +1858,7 @@ BatchedSolver::BatchedSolver(const LP_info_cpu *model, const HPRLP_parameters *p
     w.m = m; w.n = n;
     w.shared = &shared;
     w.stream = shared.stream;
+    HIP_CHECK(hipGetDevice(&device));
     seconds[0] = time_since(t0);
     // lambda_max on the scaled shared matrix (:994-1001)
     // (test hook HPRLP_BATCH_LAMBDA: the caller's value instead, so that a reference can run on the same bits)
@@ -1548,9 +1871,9 @@ BatchedSolver::BatchedSolver(const LP_info_cpu *model, const HPRLP_parameters *p
 
 void BatchedSolver::solve(int B, const double *C_in, const double *AL_in, const double *AU_in, const double *l_in, const double *u_in,
                           const double *obj_constants, const HPRLP_parameters *p, const double *X0, const double *Y0, bool carry,
-                          const Detection *det, std::vector<Certificate> *certs, HPRLP_batched_results *out) {
+                          const Detection *det, std::vector<Certificate> *certs, HPRLP_batched_results *out, DeviceBatch *dev) {
     // -- everything that can refuse the call, before the handle changes
-    if (!out) throw std::runtime_error("batched solver: null results");
+    if (!out && !dev) throw std::runtime_error("batched solver: null results");
     if (B <= 0) throw std::runtime_error("batched solver: batch_size must be positive");
     if (!C_in || !AL_in || !AU_in || !l_in || !u_in) throw std::runtime_error("batched solver: null C / AL / AU / l / u");
     const size_t nB = static_cast<size_t>(n) * B, mB = static_cast<size_t>(m) * B;
@@ -1568,8 +1891,21 @@ void BatchedSolver::solve(int B, const double *C_in, const double *AL_in, const 
     if (carry) {
         if (new_geo) throw std::runtime_error("batched solver: carry needs the previous call's chunk width (HPRLP_BATCH_CHUNK changed)");
         const double *prev = w.stage_h.p;  // x (n x B) and y (m x B) as the previous call returned them
-        for (size_t i = 0; i < nB + mB; ++i)
-            if (!std::isfinite(prev[i])) throw std::runtime_error("batched solver: carry refused, the previous batch's solution holds a non-finite value");
+        bool bad = prev_on_device && prev_nonfinite;
+        for (size_t i = 0; !prev_on_device && !bad && i < nB + mB; ++i) bad = !std::isfinite(prev[i]);
+        if (bad) throw std::runtime_error("batched solver: carry refused, the previous batch's solution holds a non-finite value");
+    }
+    if (dev) {  // no pointer reaches a kernel before all of them have passed
+        if (B > 65535) throw std::runtime_error("batched solver: the device entry takes at most 65535 members");
+        const std::pair<const double *, size_t> in_ptrs[5] = {{C_in, nB}, {AL_in, mB}, {AU_in, mB}, {l_in, nB}, {u_in, nB}};
+        const char *in_names[5] = {"C", "AL", "AU", "l", "u"};
+        for (int i = 0; i < 5; ++i) check_device_pointer(in_ptrs[i].first, in_ptrs[i].second, device, in_names[i]);
+        if (X0) check_device_pointer(X0, nB, device, "X0");
+        if (Y0) check_device_pointer(Y0, mB, device, "Y0");
+        check_device_pointer(dev->x, nB, device, "x");
+        check_device_pointer(dev->y, mB, device, "y");
+        check_device_pointer(dev->z, nB, device, "z");
+        if (!inputs_ready) HIP_CHECK(hipEventCreateWithFlags(&inputs_ready, hipEventDisableTiming));
     }
     HPRLP_parameters actual = param;
     if (p) {
@@ -1579,46 +1915,58 @@ void BatchedSolver::solve(int B, const double *C_in, const double *AL_in, const 
     const bool detect = det && det->on;
     const bool warm = X0 || Y0 || carry;
 
-    have_prev = false;  // (until this call has succeeded)
+    const bool had_prev = have_prev;
+    bool refused = false;  // the call is turned away before the workspace has changed
+    have_prev = false;     // (until this call has succeeded)
     try {
-        // -- host: per-column vector scaling (:792-885), and everything into the pinned block
+        // -- the batch in scaled units (:792-885) in the staging block.  Host entry: scaled on the host and copied into the pinned
+        // block, to be uploaded by ws_fill.  Device entry: scaled by kb_data_in / kb_data_bc where it is; only the scalars come back.
         const auto t_prep = time_now();
-        const BatchData data = prepare_batch(m, n, B, C_in, AL_in, AU_in, l_in, u_in, obj_constants, obj_constant, w.rn.data(), w.cn.data(),
-                                             actual.use_bc_scaling);
-        BatchLoop L(data, Bp, actual, detect ? det : nullptr);
         const size_t hdr = 4 * static_cast<size_t>(Bp);
-        const size_t stage_count = hdr + 3 * nB + 2 * mB + (X0 ? nB : 0) + (Y0 ? mB : 0);
-        if (w.stage_h.n < stage_count) {
-            w.stage_h.alloc(stage_count, /*zero=*/false);
-            w.stage_d.alloc(stage_count);
-        }
-        double *sh = w.stage_h.p;
-        const std::vector<double> bs = padded(data.b_scale, Bp, 1.0), cs = padded(data.c_scale, Bp, 1.0);
-        std::copy(L.sigma.begin(), L.sigma.end(), sh);
-        std::copy(bs.begin(), bs.end(), sh + Bp);
-        std::copy(cs.begin(), cs.end(), sh + 2 * Bp);
-        std::memcpy(sh + 3 * Bp, L.active.data(), sizeof(int) * Bp);
+        const size_t stage_count = dev ? 0 : hdr + 3 * nB + 2 * mB + (X0 ? nB : 0) + (Y0 ? mB : 0);
         PanelIn in{};
         int nvec = 0;
-        size_t off = hdr;
-        auto region = [&](const double *src, size_t count, int rows, double *panel) {
-            if (src) std::memcpy(sh + off, src, count * sizeof(double));
-            in.src[nvec] = w.stage_d.p + off;  // (the panel's address: below, once the workspace is there)
-            in.rows[nvec] = rows;
-            in.dst[nvec] = panel;
-            off += count;
-            return nvec++;
-        };
-        const int iC = region(data.C.data(), nB, n, nullptr), iL = region(data.L.data(), nB, n, nullptr), iU = region(data.U.data(), nB, n, nullptr);
-        const int iAL = region(data.AL.data(), mB, m, nullptr), iAU = region(data.AU.data(), mB, m, nullptr);
-        int iX = -1, iY = -1;
-        if (X0) {
-            iX = region(X0, nB, n, nullptr);
-            start_to_scaled(sh + off - nB, n, B, w.cn.data(), data.b_scale);
+        const BatchData data =
+            dev ? device_prep(w, B, Bp, C_in, AL_in, AU_in, l_in, u_in, X0, Y0, obj_constants, obj_constant, actual.use_bc_scaling,
+                              static_cast<hipStream_t>(dev->stream), inputs_ready, in, nvec)
+                : prepare_batch(m, n, B, C_in, AL_in, AU_in, l_in, u_in, obj_constants, obj_constant, w.rn.data(), w.cn.data(),
+                                actual.use_bc_scaling, norm_rule);
+        if (dev && data_flags_host(w, B)[DF_START]) {
+            refused = true;
+            throw std::runtime_error("batched solver: warm start: X0 or Y0 holds a non-finite entry");
         }
-        if (Y0) {
-            iY = region(Y0, mB, m, nullptr);
-            start_to_scaled(sh + off - mB, m, B, w.rn.data(), data.c_scale);
+        BatchLoop L(data, Bp, actual, detect ? det : nullptr);
+        int iC = 0, iL = 1, iU = 2, iAL = 3, iAU = 4, iX = X0 ? 5 : -1, iY = Y0 ? (X0 ? 6 : 5) : -1;  // (the regions' order, both entries)
+        if (!dev) {
+            if (w.stage_h.n < stage_count) {
+                w.stage_h.alloc(stage_count, /*zero=*/false);
+                w.stage_d.alloc(stage_count);
+            }
+            double *sh = w.stage_h.p;
+            const std::vector<double> bs = padded(data.b_scale, Bp, 1.0), cs = padded(data.c_scale, Bp, 1.0);
+            std::copy(L.sigma.begin(), L.sigma.end(), sh);
+            std::copy(bs.begin(), bs.end(), sh + Bp);
+            std::copy(cs.begin(), cs.end(), sh + 2 * Bp);
+            std::memcpy(sh + 3 * Bp, L.active.data(), sizeof(int) * Bp);
+            size_t off = hdr;
+            auto region = [&](const double *src, size_t count, int rows, double *panel) {
+                if (src) std::memcpy(sh + off, src, count * sizeof(double));
+                in.src[nvec] = w.stage_d.p + off;  // (the panel's address: below, once the workspace is there)
+                in.rows[nvec] = rows;
+                in.dst[nvec] = panel;
+                off += count;
+                return nvec++;
+            };
+            iC = region(data.C.data(), nB, n, nullptr); iL = region(data.L.data(), nB, n, nullptr); iU = region(data.U.data(), nB, n, nullptr);
+            iAL = region(data.AL.data(), mB, m, nullptr); iAU = region(data.AU.data(), mB, m, nullptr);
+            if (X0) {
+                iX = region(X0, nB, n, nullptr);
+                start_to_scaled(sh + off - nB, n, B, w.cn.data(), data.b_scale);
+            }
+            if (Y0) {
+                iY = region(Y0, mB, m, nullptr);
+                start_to_scaled(sh + off - mB, m, B, w.rn.data(), data.c_scale);
+            }
         }
         seconds[2] = time_since(t_prep);
 
@@ -1656,17 +2004,45 @@ void BatchedSolver::solve(int B, const double *C_in, const double *AL_in, const 
         seconds[4] = time_since(L.solve_start);
 
         const auto t_res = time_now();
-        *out = collect_results(w, L, certs);
+        if (dev) {  // x, y, z straight into the caller's buffers; one flag word comes back
+            launch_panel_out(w, dev->x, dev->y, dev->z);
+            hipLaunchKernelGGL(kb_flag_nonfinite, dim3(static_cast<unsigned>(std::min<size_t>((nB + mB + 255) / 256, 1024))), dim3(256), 0,
+                               w.stream, static_cast<const double *>(dev->x), nB, static_cast<const double *>(dev->y), mB,
+                               data_flags(w, B) + DF_RESULT);
+            HIP_CHECK(hipGetLastError());
+            HIP_CHECK(hipMemcpyAsync(const_cast<int *>(data_flags_host(w, B)) + DF_RESULT, data_flags(w, B) + DF_RESULT, sizeof(int),
+                                     hipMemcpyDeviceToHost, w.stream));
+            HIP_CHECK(hipStreamSynchronize(w.stream));
+            if (certs) collect_certificates(w, L, certs);
+            member_results(L, B, dev->primal_obj, dev->residuals, dev->gap, dev->iter, dev->status);
+            prev_nonfinite = data_flags_host(w, B)[DF_RESULT] != 0;
+        } else {
+            *out = collect_results(w, L, certs);
+        }
         seconds[5] = time_since(t_res);
-        out->setup_time = seconds[2] + seconds[3];
-        out->solve_time = seconds[4];
-        out->power_time = 0.0;
-        out->time = out->setup_time + out->solve_time;
+        const double setup_time = seconds[2] + seconds[3];
+        if (dev) {
+            dev->setup_time = setup_time; dev->solve_time = seconds[4]; dev->power_time = 0.0; dev->time = setup_time + seconds[4];
+        } else {
+            out->setup_time = setup_time; out->solve_time = seconds[4]; out->power_time = 0.0; out->time = setup_time + seconds[4];
+        }
+        last_scalars.clear();
+        for (const std::vector<double> *v : {&data.b_scale, &data.c_scale, &data.norm_b, &data.norm_c, &data.norm_b_org, &data.norm_c_org, &data.sigma})
+            last_scalars.insert(last_scalars.end(), v->begin(), v->end());
+        staged[0] = static_cast<long>(stage_count * sizeof(double));
+        staged[1] = dev ? static_cast<long>(static_cast<size_t>(DS_COUNT) * B * sizeof(double) + (DF_COUNT + 1) * sizeof(int))
+                        : static_cast<long>((2 * nB + mB) * sizeof(double));
         w.data = nullptr;
         have_prev = true;
         prev_B = B;
+        prev_on_device = dev != nullptr;
         ++solves;
+        if (dev) ++device_solves;
     } catch (...) {
+        if (refused) {  // nothing the previous call left has been touched
+            have_prev = had_prev;
+            throw;
+        }
         // a call that failed half-way: nothing of it is carried, and the next call builds its workspace anew
         (void)hipStreamSynchronize(w.stream);
         (void)hipGetLastError();
@@ -1684,6 +2060,28 @@ void batched_solver_solve(BatchedSolver *h, int batch_size, const double *C, con
                           bool carry, const Detection *det, std::vector<Certificate> *certs, HPRLP_batched_results *out) {
     if (!h) throw std::runtime_error("batched solver: null handle");
     h->solve(batch_size, C, AL, AU, l, u, obj_constants, param, X0, Y0, carry, det, certs, out);
+}
+void batched_solver_solve_device(BatchedSolver *h, int batch_size, const double *C, const double *AL, const double *AU, const double *l,
+                                 const double *u, const double *obj_constants, const HPRLP_parameters *param, const double *X0,
+                                 const double *Y0, bool carry, const Detection *det, std::vector<Certificate> *certs, DeviceBatch *dev) {
+    if (!h || !dev) throw std::runtime_error("batched solver: null handle / device batch");
+    h->solve(batch_size, C, AL, AU, l, u, obj_constants, param, X0, Y0, carry, det, certs, nullptr, dev);
+}
+void batched_solver_set_norms(BatchedSolver *h, int rule) {
+    if (!h) throw std::runtime_error("batched solver: null handle");
+    if (rule != kNormRuleReference && rule != kNormRuleTree) throw std::runtime_error("batched solver: the norm rule is 0 (reference) or 1 (tree)");
+    h->norm_rule = rule;
+}
+int batched_solver_scalars(const BatchedSolver *h, double *out) {
+    if (!h || !out) throw std::runtime_error("batched solver: null handle / output");
+    if (!h->have_prev) throw std::runtime_error("batched solver: no successful solve to report the scalars of");
+    std::copy(h->last_scalars.begin(), h->last_scalars.end(), out);
+    return h->prev_B;
+}
+void batched_solver_transfer(const BatchedSolver *h, long out[4]) {
+    if (!h || !out) throw std::runtime_error("batched solver: null handle / output");
+    const long v[4] = {h->staged[0], h->staged[1], h->prev_on_device ? 1 : 0, h->device_solves};
+    std::copy(v, v + 4, out);
 }
 void batched_solver_info(const BatchedSolver *h, long out[8]) {
     if (!h || !out) throw std::runtime_error("batched solver: null handle / output");

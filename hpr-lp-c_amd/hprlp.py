@@ -91,9 +91,28 @@ class CBatchedCertificates(C.Structure):  # hprlp_batched_certificates (include/
                 ("objective", c_dbl_p), ("violation", c_dbl_p), ("y", c_dbl_p), ("z", c_dbl_p), ("d", c_dbl_p)]
 
 
+class CBatchedScalars(C.Structure):  # hprlp_batched_scalars (include/hprlp_amd.h): host arrays of the caller's, B each
+    _fields_ = [("primal_obj", c_dbl_p), ("residuals", c_dbl_p), ("gap", c_dbl_p), ("iter", c_int_p), ("status", C.POINTER(C.c_char)),
+                ("time", C.c_double), ("setup_time", C.c_double), ("solve_time", C.c_double), ("power_time", C.c_double)]
+
+
 _lib = None
 _libc = C.CDLL(None)
 _libc.free.argtypes = [C.c_void_p]
+
+
+def _share_hip_runtime():
+    """One HIP runtime per process whichever of this library and torch is loaded first.  torch's wheel brings its own copies of
+    the runtime's libraries with the system's SONAMEs but asks for them by their UNVERSIONED file names.  Loaded first, torch's
+    copies serve this library too (its versioned names match their SONAMEs).  Loaded second, torch would not find the unversioned
+    names among the objects this library brought in, load its own copies beside them, and the second HSA runtime of the process
+    sees no GPU.  So the unversioned names are added to the objects already loaded: RTLD_NOLOAD opens nothing new -- where a name
+    resolves to another file than the one loaded, or to none, nothing happens."""
+    for name in ("librocprofiler-register.so", "libhsa-runtime64.so", "libamdhip64.so"):
+        try:
+            C.CDLL(name, mode=os.RTLD_NOLOAD)
+        except OSError:
+            pass
 
 
 def lib():
@@ -104,6 +123,7 @@ def lib():
     if not os.path.exists(LIB_PATH):
         raise RuntimeError(f"{LIB_PATH} not found: build it with `make` (no CPU fallback exists)")
     L = C.CDLL(LIB_PATH)
+    _share_hip_runtime()
     L.create_model_from_arrays.restype = C.POINTER(CLPInfo)
     L.create_model_from_arrays.argtypes = [C.c_int, C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p, c_dbl_p, c_dbl_p,
                                            c_dbl_p, c_dbl_p, c_dbl_p, C.c_bool]
@@ -172,6 +192,13 @@ def lib():
                                              C.POINTER(CBatchedCertificates), C.POINTER(CBatchedResults)]
     L.hprlp_batched_solver_info.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
     L.hprlp_batched_solver_seconds.argtypes = [C.c_void_p, c_dbl_p]
+    L.hprlp_batched_solver_solve_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [c_dbl_p, C.POINTER(CParameters)] + \
+        [C.c_void_p] * 2 + [C.c_int, C.POINTER(CDetection), C.POINTER(CBatchedCertificates)] + [C.c_void_p] * 4 + \
+        [C.POINTER(CBatchedScalars)]
+    L.hprlp_batched_solver_set_norms.argtypes = [C.c_void_p, C.c_int]
+    L.hprlp_batched_solver_scalars.argtypes = [C.c_void_p, c_dbl_p]
+    L.hprlp_batched_solver_transfer.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
+    L.hprlp_batched_prepare_host_rule.argtypes = [C.c_int] * 3 + [c_dbl_p] * 9 + [C.c_int, C.c_int, C.POINTER(CBatchedPrepared)]
     L.hprlp_solver_set_start.argtypes = [C.c_void_p, c_dbl_p, c_dbl_p]
     L.hprlp_solver_set_data.argtypes = [C.c_void_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]
     L.hprlp_solver_resolve.argtypes = [C.c_void_p, C.c_double, c_dbl_p, c_dbl_p, C.POINTER(CResults), C.POINTER(CTraceRow),
@@ -556,9 +583,14 @@ class BatchedSolver:
     _INFO = ("m", "n", "solves", "Bp", "Bc", "graph_captures", "graphs_alive", "panel_allocations")
     _SECONDS = ("create_setup", "create_power", "prep", "upload", "loop", "results")
 
+    _TRANSFER = ("staged_h2d_bytes", "staged_d2h_bytes", "device_entry", "device_solves")
+
     def __init__(self, model, param=None):
         self.model = model
-        self._h = lib().hprlp_batched_solver_create(model._ptr, C.byref((param or Parameters(use_presolve=False)).to_c()))
+        cp = (param or Parameters(use_presolve=False)).to_c()
+        self.device_number = int(cp.device_number)
+        self._last_B = 0
+        self._h = lib().hprlp_batched_solver_create(model._ptr, C.byref(cp))
         if not self._h:
             raise RuntimeError("hprlp_batched_solver_create failed: " + last_error())
 
@@ -596,7 +628,97 @@ class BatchedSolver:
         out = _batched_call(call, self.model, Cmat, AL, AU, l, u, obj_constants, param)
         if det is not None:
             out["certificates"] = _batched_certificates(cc)
+        self._last_B = B
         return out
+
+    def solve_tensors(self, Cmat, AL, AU, l, u, obj_constants=None, X0=None, Y0=None, carry=False, param=None, eps_primal=None,
+                      eps_dual=None):
+        """solve() for a batch that is on the GPU already (hprlp_batched_solver_solve_device, DESIGN.md "Device-resident batches"):
+        Cmat, l, u, X0 (n, B) and AL, AU, Y0 (m, B) are float64 torch tensors on the solver's device.  A tensor whose transpose is
+        contiguous (strides (1, rows)) is passed as it is; any other layout costs one copy on the device.  Returns the dict of
+        solve() with x, y, z as torch tensors (rows, B) on the device -- views of fresh (B, rows) buffers -- and the per-member
+        scalars and statuses on the host as before.  The inputs are taken as ordered on the current torch stream.  ValueError for a
+        wrong type, dtype, device or shape, before the library is called; RuntimeError with the library's message for a call it
+        refuses, which leaves the solver usable.  The norms of the scaling follow the tree rule (see set_norms)."""
+        import torch
+        if not self._h:
+            raise RuntimeError("BatchedSolver: closed")
+        m, n = self.model.m, self.model.n
+        if not isinstance(Cmat, torch.Tensor) or Cmat.dim() != 2:
+            raise ValueError("solve_tensors: Cmat must be a 2-D torch tensor")
+        B = int(Cmat.shape[1])
+        if B <= 0:
+            raise ValueError("solve_tensors: an empty batch")
+
+        def dev(t, rows, name):
+            """The tensor as column-major rows x B device memory: (what keeps it alive, its address)."""
+            if t is None:
+                return None, None
+            if not isinstance(t, torch.Tensor):
+                raise ValueError(f"solve_tensors: {name} must be a torch tensor, got {type(t).__name__}")
+            if t.dtype != torch.float64:
+                raise ValueError(f"solve_tensors: {name} must be float64, got {t.dtype}")
+            if t.device.type != "cuda" or t.device.index != self.device_number:
+                raise ValueError(f"solve_tensors: {name} must be on the solver's device cuda:{self.device_number}, got {t.device}")
+            if tuple(t.shape) != (rows, B):
+                raise ValueError(f"solve_tensors: {name} must have shape ({rows}, {B}), got {tuple(t.shape)}")
+            tt = t.T
+            if not tt.is_contiguous():
+                tt = tt.contiguous()
+            return tt, tt.data_ptr()
+        keep = [dev(t, rows, name) for t, rows, name in ((Cmat, n, "Cmat"), (AL, m, "AL"), (AU, m, "AU"), (l, n, "l"), (u, n, "u"),
+                                                         (X0, n, "X0"), (Y0, m, "Y0"))]
+        oc = None if obj_constants is None else _as(obj_constants, np.float64)
+        if oc is not None and oc.shape != (B,):
+            raise ValueError(f"solve_tensors: obj_constants must have {B} entries")
+        det = _detection_arg(eps_primal, eps_dual)
+        cc = CBatchedCertificates()
+        cprm = None if param is None else param.to_c()
+        device = torch.device("cuda", self.device_number)
+        xb, yb, zb = (torch.empty((B, rows), dtype=torch.float64, device=device) for rows in (n, m, n))
+        res = dict(primal_obj=np.zeros(B), residuals=np.zeros(B), gap=np.zeros(B), iter=np.zeros(B, dtype=np.intc))
+        status = C.create_string_buffer(64 * B)
+        sc = CBatchedScalars(primal_obj=_dptr(res["primal_obj"]), residuals=_dptr(res["residuals"]), gap=_dptr(res["gap"]),
+                             iter=res["iter"].ctypes.data_as(c_int_p), status=C.cast(status, C.POINTER(C.c_char)))
+        stream = torch.cuda.current_stream(device).cuda_stream
+        ptrs = [p for _, p in keep]
+        rc = lib().hprlp_batched_solver_solve_device(self._h, B, *ptrs[:5], _dptr(oc), None if cprm is None else C.byref(cprm), ptrs[5],
+                                                     ptrs[6], int(bool(carry)), C.byref(det) if det is not None else None,
+                                                     C.byref(cc) if det is not None else None, stream, xb.data_ptr(), yb.data_ptr(),
+                                                     zb.data_ptr(), C.byref(sc))
+        if rc != 0:
+            if det is not None:
+                lib().hprlp_free_batched_certificates(C.byref(cc))
+            raise RuntimeError("hprlp_batched_solver_solve_device failed: " + last_error())
+        out = dict(batch_size=B, time=sc.time, setup_time=sc.setup_time, solve_time=sc.solve_time, power_time=sc.power_time,
+                   x=xb.T, y=yb.T, z=zb.T, **res)
+        out["status"] = [status.raw[64 * k:64 * (k + 1)].split(b"\0")[0].decode() for k in range(B)]
+        if det is not None:
+            out["certificates"] = _batched_certificates(cc)
+        self._last_B = B
+        return out
+
+    def set_norms(self, rule):
+        """The norm rule of solve() -- the host entry -- on this solver: 0 = the reference's long double sums (the default), 1 = the
+        tree rule that solve_tensors() always follows; with 1 the two agree bit for bit."""
+        if lib().hprlp_batched_solver_set_norms(self._h, int(rule)) != 0:
+            raise RuntimeError(last_error())
+
+    def scalars(self):
+        """The BATCH_SCALARS of the last successful solve() / solve_tensors(): a dict of arrays of B."""
+        out = np.zeros((len(BATCH_SCALARS), max(self._last_B, 1)))
+        B = lib().hprlp_batched_solver_scalars(self._h, _dptr(out))
+        if B < 0:
+            raise RuntimeError(last_error())
+        return dict(zip(BATCH_SCALARS, out.reshape(-1)[:len(BATCH_SCALARS) * B].reshape(len(BATCH_SCALARS), B).copy()))
+
+    def transfer(self):
+        """The last successful call's staging traffic in bytes, host to device and back (the batch's way in and the solution's way
+        out; not the loop's scalar fetches), whether it was a solve_tensors() call, and how many of those there have been."""
+        out = (C.c_long * 4)()
+        if lib().hprlp_batched_solver_transfer(self._h, out) != 0:
+            raise RuntimeError(last_error())
+        return dict(zip(self._TRANSFER, [int(v) for v in out]))
 
     def info(self):
         out = (C.c_long * 8)()
@@ -717,14 +839,16 @@ class CBatchedPrepared(C.Structure):  # include/hprlp_amd.h: hprlp_batched_prepa
 
 
 BATCH_SCALARS = ("b_scale", "c_scale", "norm_b", "norm_c", "norm_b_org", "norm_c_org", "sigma")
+NORM_SEG, NORM_LANES = 16384, 256  # the tree rule's constants (csrc/batch_prep.h: kNormSeg, kNormLanes)
 
 
-def batched_prepare_host(rn, cn, Cmat, AL, AU, l, u, X0=None, Y0=None, use_bc_scaling=True, pad=0.0):
+def batched_prepare_host(rn, cn, Cmat, AL, AU, l, u, X0=None, Y0=None, use_bc_scaling=True, pad=0.0, norm_rule=0):
     """Host only (hprlp_batched_prepare_host): what solve_batched does to a batch's vectors before anything is uploaded.  rn (m) /
     cn (n): the shared matrix' row / column scaling; Cmat, l, u, X0: (n, B); AL, AU, Y0: (m, B).  Returns a dict: the scaled C, AL,
     AU, l, u; the BATCH_SCALARS (B each); X0, Y0 scaled and X_back, Y_back mapped back as a solution is (None without a start);
     z_back (the scaled C mapped as a solution's z); Bp, Bc; panel (the scaled C as a device panel, flat, padding = pad),
-    panel_back (n, B) and panel_index (n, B)."""
+    panel_back (n, B) and panel_index (n, B).  norm_rule: 0 = the reference's long double sums, non-zero = that rule of
+    hprlp_batched_prepare_host_rule (1: the tree rule of the device entry, NORM_SEG / NORM_LANES)."""
     F = lambda a: None if a is None else np.asfortranarray(a, dtype=np.float64)
     rn, cn = _as(rn, np.float64), _as(cn, np.float64)
     m, n, B = len(rn), len(cn), np.asarray(Cmat).shape[1]
@@ -742,7 +866,11 @@ def batched_prepare_host(rn, cn, Cmat, AL, AU, l, u, X0=None, Y0=None, use_bc_sc
     o = CBatchedPrepared(pad=pad, **{k: (v.ctypes.data_as(C.POINTER(C.c_long)) if k == "panel_index" else P(v)) for k, v in out.items()})
     L = lib()
     L.hprlp_batched_prepare_host.argtypes = [C.c_int] * 3 + [c_dbl_p] * 9 + [C.c_int, C.POINTER(CBatchedPrepared)]
-    if L.hprlp_batched_prepare_host(m, n, B, P(rn), P(cn), *[P(a) for a in ins], int(use_bc_scaling), C.byref(o)) != 0:
+    if norm_rule:
+        rc = L.hprlp_batched_prepare_host_rule(m, n, B, P(rn), P(cn), *[P(a) for a in ins], int(use_bc_scaling), int(norm_rule), C.byref(o))
+    else:
+        rc = L.hprlp_batched_prepare_host(m, n, B, P(rn), P(cn), *[P(a) for a in ins], int(use_bc_scaling), C.byref(o))
+    if rc != 0:
         raise RuntimeError(L.hprlp_last_error().decode())
     out.update(Bp=o.Bp, Bc=o.Bc, panel=out["panel"][:n * o.Bp])
     out.update(zip(BATCH_SCALARS, out.pop("scalars")))

@@ -179,6 +179,44 @@ int hprlp_batched_solver_info(hprlp_batched_solver *h, long out[8]);
 /* seconds: {create: set-up + scaling, create: power iteration,
  *           last solve: host prep, staging upload + panel kernels + start, loop, results' way back} */
 int hprlp_batched_solver_seconds(hprlp_batched_solver *h, double out[6]);
+
+/* ---- device-resident batches: tensors in, tensors out (DESIGN.md "Device-resident batches") ------------------------------------
+ * hprlp_batched_solver_solve with the batch's vectors already in device memory and the solution wanted there.  dC, dl, du
+ * (n x B), dAL, dAU (m x B), dX0 (n x B) / dY0 (m x B; either may be NULL) are DEVICE arrays, column-major like the host entry's;
+ * dx, dz (n x B) and dy (m x B) are device buffers that receive the solution in the caller's units.  obj_constants (B or NULL),
+ * param, det, certs and `out` are host memory.  The per-member scaling and its norms run in kernels, the results are written
+ * straight into dx / dy / dz, and only the per-member scalars cross the bus.
+ *   Pointers: before anything is launched every device pointer is looked up with hipPointerGetAttributes.  It passes only as
+ * device memory of the handle's device and, where the runtime reports the allocation's range, with room for rows * B doubles;
+ * a host address, another device's memory, a short buffer or an address the runtime does not know is refused.
+ *   Ordering: `stream` is the hipStream_t (NULL: the default stream) on which the inputs were produced; the solver's own stream
+ * waits for an event recorded on it before its first read, and the call returns after its own stream has drained: the outputs
+ * are complete on return.
+ *   Bits: the norms follow the "tree" rule (norm rule 1), whose order of additions is fixed by the vector's length alone; with
+ * hprlp_batched_solver_set_norms(h, 1) the host entry follows it too, and the two entries then agree bit for bit.  carry,
+ * detection and param behave as in hprlp_batched_solver_solve, and the two entries may alternate on one handle, carry included.
+ * A non-finite entry of dX0 / dY0 is refused after the scaling kernels, before the loop.
+ * 0, or -1 + hprlp_last_error() with the handle as it was and still usable. */
+typedef struct hprlp_batched_scalars { /* host; the arrays are the caller's (NULL: not wanted) */
+    double *primal_obj, *residuals, *gap; /* B each */
+    int *iter;                            /* B */
+    char *status;                         /* 64 x B */
+    double time, setup_time, solve_time, power_time; /* out, as in HPRLP_batched_results */
+} hprlp_batched_scalars;
+int hprlp_batched_solver_solve_device(hprlp_batched_solver *h, int batch_size, const double *dC, const double *dAL, const double *dAU,
+                                      const double *dl, const double *du, const double *obj_constants, const HPRLP_parameters *param,
+                                      const double *dX0, const double *dY0, int carry, const hprlp_detection *det,
+                                      hprlp_batched_certificates *certs, void *stream, double *dx, double *dy, double *dz,
+                                      hprlp_batched_scalars *out);
+/* The norm rule of the HOST entry of this handle: 0 = the reference's long double sums (the default), 1 = the tree rule. */
+int hprlp_batched_solver_set_norms(hprlp_batched_solver *h, int rule);
+/* out (7 x B): b_scale, c_scale, norm_b, norm_c, norm_b_org, norm_c_org, first sigma of the last successful solve, either entry.
+ * Returns that call's B, or -1. */
+int hprlp_batched_solver_scalars(hprlp_batched_solver *h, double *out);
+/* out = {staging bytes host -> device, staging bytes device -> host of the last successful solve (the batch's way in and its
+ *        solution's way out; the loop's scalar fetches are not counted), 1 if that solve was a device-entry call,
+ *        device-entry solves so far} */
+int hprlp_batched_solver_transfer(hprlp_batched_solver *h, long out[4]);
 /* After hprlp_solver_init, before hprlp_solver_run: the start of the next run (caller's units; both NULL: the zero start,
  * evaluated as a start).  -1 + hprlp_last_error() for a sharded solver or a non-finite entry. */
 int hprlp_solver_set_start(hprlp_solver *s, const double *x0, const double *y0);
@@ -407,6 +445,10 @@ typedef struct hprlp_batched_prepared {
 int hprlp_batched_prepare_host(int m, int n, int B, const double *rn, const double *cn, const double *C, const double *AL,
                                const double *AU, const double *l, const double *u, const double *X0, const double *Y0,
                                int use_bc_scaling, hprlp_batched_prepared *out);
+/* ... with the norm rule named: 0 = exactly hprlp_batched_prepare_host, 1 = the tree rule of the device entry (csrc/batch_prep.h) */
+int hprlp_batched_prepare_host_rule(int m, int n, int B, const double *rn, const double *cn, const double *C, const double *AL,
+                                    const double *AU, const double *l, const double *u, const double *X0, const double *Y0,
+                                    int use_bc_scaling, int norm_rule, hprlp_batched_prepared *out);
 
 /* ---- which kernel form a matrix gets (hpr-lp-c_amd/csrc/form_select.h) as plain data ----------------
  * The rules are host-only functions of the records below; a solver's set-up measures the facts and asks them. */
