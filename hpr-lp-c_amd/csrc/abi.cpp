@@ -18,6 +18,7 @@
 #include "reorder.h"
 #include "solver.h"
 #include "many.h"
+#include "values.h"
 #include "version.h"
 
 using namespace hprlp;
@@ -1609,6 +1610,85 @@ extern "C" int hprlp_solver_data_seconds(hprlp_solver *h, double out[3]) {
     for (int i = 0; i < 3; ++i) out[i] = h->s.data_time[i];
     return 0;
     GUARD_END(-1)
+}
+
+// Matrix values (DESIGN.md "Matrix values"): new values on the resident pattern, then hprlp_solver_power_iteration / _init / _resolve
+extern "C" int hprlp_solver_set_matrix_values(hprlp_solver *h, const double *val, long nnz, const double *c, const double *obj_constant,
+                                              const double *AL, const double *AU, const double *l, const double *u) {
+    GUARD_BEGIN
+    if (!h) throw std::runtime_error("hprlp_solver_set_matrix_values: null solver");
+    if (h->sharded)
+        throw std::runtime_error("hprlp_solver_set_matrix_values: new matrix values for a resident model run on one GPU only; a sharded "
+                                 "solver (hprlp_solver_create_dist* / _local*) refuses them");
+    h->s.set_matrix_values(val, nnz, c, obj_constant, AL, AU, l, u);
+    return 0;
+    GUARD_END(-1)
+}
+
+extern "C" int hprlp_solver_matrix_seconds(hprlp_solver *h, double out[6]) {
+    GUARD_BEGIN
+    if (!h || !out) throw std::runtime_error("hprlp_solver_matrix_seconds: null solver / output");
+    for (int i = 0; i < 5; ++i) out[i] = h->s.matrix_time[i];
+    out[5] = static_cast<double>(h->s.matrix_calls);
+    return 0;
+    GUARD_END(-1)
+}
+
+// The value maps as the solver built them (built here if no hprlp_solver_set_matrix_values call has done it yet); mapA / mapAT
+// receive nnz ints each.  Returns nnz.
+extern "C" long hprlp_solver_value_maps(hprlp_solver *h, int *mapA, int *mapAT, long cap) {
+    GUARD_BEGIN
+    if (!h || !mapA || !mapAT) throw std::runtime_error("hprlp_solver_value_maps: null solver / output");
+    if (h->sharded) throw std::runtime_error("hprlp_solver_value_maps: one GPU only; a sharded solver has no value maps");
+    Solver &s = h->s;
+    const long nnz = s.A.view.nnz;
+    if (cap < nnz) throw std::runtime_error("hprlp_solver_value_maps: output buffers too small");
+    s.build_value_maps();
+    HIP_CHECK(hipStreamSynchronize(s.stream));
+    if (nnz > 0) {
+        if (s.map_A.p) HIP_CHECK(hipMemcpy(mapA, s.map_A.p, sizeof(int) * nnz, hipMemcpyDeviceToHost));
+        else
+            for (long e = 0; e < nnz; ++e) mapA[e] = static_cast<int>(e);
+        HIP_CHECK(hipMemcpy(mapAT, s.map_AT.p, sizeof(int) * nnz, hipMemcpyDeviceToHost));
+    }
+    return nnz;
+    GUARD_END(-1)
+}
+
+// Host only: the rule of the value maps restated (values_host.cpp); row_new2old / col_new2old null: no ordering
+extern "C" int hprlp_value_maps_host(int m, int n, const int *rowptr, const int *col, const int *row_new2old, const int *col_new2old,
+                                     int *mapA, int *mapAT) {
+    try {
+        value_maps_host(m, n, rowptr, col, row_new2old, col_new2old, mapA, mapAT);
+        return 0;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+// The locality ordering a solver applied: row_new2old (m) / col_new2old (n) as perm_r / perm_c hold them.  Returns 1 with the
+// arrays filled, 0 without an ordering (arrays untouched).
+extern "C" int hprlp_solver_ordering(hprlp_solver *h, int *row_new2old, int *col_new2old) {
+    GUARD_BEGIN
+    if (!h || !row_new2old || !col_new2old) throw std::runtime_error("hprlp_solver_ordering: null solver / output");
+    const Solver &s = h->s;
+    if (s.perm_r.empty()) return 0;
+    std::copy(s.perm_r.begin(), s.perm_r.end(), row_new2old);
+    std::copy(s.perm_c.begin(), s.perm_c.end(), col_new2old);
+    return 1;
+    GUARD_END(-1)
+}
+
+extern "C" int hprlp_batched_solver_set_matrix_values(hprlp_batched_solver *h, const double *val, long nnz) {
+    try {
+        if (!h || !h->s) throw std::runtime_error("hprlp_batched_solver_set_matrix_values: null solver");
+        batched_solver_set_matrix_values(h->s, val, nnz);
+        return 0;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return -1;
+    }
 }
 
 extern "C" int hprlp_solver_get_certificate(hprlp_solver *h, hprlp_certificate *cert) {

@@ -45,6 +45,10 @@ void batched_solver_solve_device(BatchedSolver *h, int batch_size, const HPRLP_F
                                  const HPRLP_FLOAT *l, const HPRLP_FLOAT *u, const HPRLP_FLOAT *obj_constants /* host */,
                                  const HPRLP_parameters *param, const HPRLP_FLOAT *X0, const HPRLP_FLOAT *Y0, bool carry,
                                  const Detection *det, std::vector<Certificate> *certs, DeviceBatch *dev);
+// New values on the shared matrix' pattern (DESIGN.md "Matrix values"): val = the nnz values of the model's CSR in the caller's order.
+// The shared solver takes them with zero vectors and is scaled again, the host's row / column norms and the created lambda_max
+// follow; panels, staging blocks, order tables and workspace stay.  carry is refused until the next successful solve.
+void batched_solver_set_matrix_values(BatchedSolver *h, const double *val, long nnz);
 void batched_solver_set_norms(BatchedSolver *h, int rule);           // the HOST entry's norm rule (batch_prep.h): 0 reference, 1 tree
 int batched_solver_scalars(const BatchedSolver *h, double *out);     // 7 x B of the last successful call; returns B
 void batched_solver_transfer(const BatchedSolver *h, long out[4]);   // hprlp_batched_solver_transfer

@@ -2067,6 +2067,28 @@ void batched_solver_solve_device(BatchedSolver *h, int batch_size, const double 
     if (!h || !dev) throw std::runtime_error("batched solver: null handle / device batch");
     h->solve(batch_size, C, AL, AU, l, u, obj_constants, param, X0, Y0, carry, det, certs, nullptr, dev);
 }
+// New values on the shared pattern (DESIGN.md "Matrix values"): what the constructor does after setup(), on the resident solver.
+// Panels, staging blocks, order tables and the workspace stay; the graphs hold lambda by value and follow graph_lambda at the
+// next call.  The previous solution was mapped with the old factors: nothing is carried across.
+void batched_solver_set_matrix_values(BatchedSolver *h, const double *val, long nnz) {
+    if (!h) throw std::runtime_error("batched solver: null handle");
+    if (!val) throw std::runtime_error("batched solver: null matrix values");
+    const char *lambda_hook = env_get("HPRLP_BATCH_LAMBDA");
+    const double lambda_given = lambda_hook ? std::strtod(lambda_hook, nullptr) : 1.0;
+    if (!(lambda_given > 0.0) || !std::isfinite(lambda_given)) throw std::runtime_error("HPRLP_BATCH_LAMBDA is not a positive finite number");
+    HIP_CHECK(hipStreamSynchronize(h->w.stream));
+    const auto t0 = time_now();
+    const std::vector<double> zero_m(static_cast<size_t>(std::max(h->m, 1)), 0.0), zero_n(static_cast<size_t>(std::max(h->n, 1)), 0.0);
+    // (refuses a wrong nnz and a non-finite value before the shared solver has changed)
+    h->shared.set_matrix_values(val, nnz, zero_n.data(), nullptr, zero_m.data(), zero_m.data(), zero_n.data(), zero_n.data());
+    h->have_prev = false;
+    h->shared.row_norm.download(h->w.rn.data(), h->m);
+    h->shared.col_norm.download(h->w.cn.data(), h->n);
+    h->seconds[0] += time_since(t0);
+    const auto t1 = time_now();
+    h->lambda_created = lambda_hook ? lambda_given : h->shared.power_iteration(5000, 1.0e-4, nullptr) * 1.01;
+    h->seconds[1] += time_since(t1);
+}
 void batched_solver_set_norms(BatchedSolver *h, int rule) {
     if (!h) throw std::runtime_error("batched solver: null handle");
     if (rule != kNormRuleReference && rule != kNormRuleTree) throw std::runtime_error("batched solver: the norm rule is 0 (reference) or 1 (tree)");

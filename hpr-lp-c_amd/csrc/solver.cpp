@@ -704,6 +704,7 @@ void Solver::setup(const LP_info_cpu *model, const HPRLP_parameters *param) {
             AT.rowptr.alloc(static_cast<size_t>(n) + 1);
             AT.col.alloc(static_cast<size_t>(nnz));
             AT.val.alloc(static_cast<size_t>(nnz));
+            device_transposed = true;
             device_transpose(m, n, nnz, A.rowptr.p, A.col.p, A.val.p, AT.rowptr.p, AT.col.p, AT.val.p, stream);
             pt.tick("device transpose");
             const bool reordered = try_reorder(model);
@@ -982,6 +983,8 @@ bool Solver::try_reorder(const LP_info_cpu *model) {
     DBuf<int> nrp(static_cast<size_t>(m) + 1), nci(static_cast<size_t>(nnz));
     DBuf<double> nval(static_cast<size_t>(nnz));
     device_permute_csr(m, n, nnz, A.rowptr.p, A.col.p, A.val.p, d_r.p, d_c.p, nrp.p, nci.p, nval.p, stream);
+    src_rowptr = std::move(A.rowptr);  // the caller's pattern: what the value maps of set_matrix_values are built from
+    src_col = std::move(A.col);
     A.rowptr = std::move(nrp);
     A.col = std::move(nci);
     A.val = std::move(nval);

@@ -202,6 +202,26 @@ struct Solver {
     DBuf<int> perm_r_dev, perm_c_dev;       // set_data: the locality ordering's permutations on the device (first use)
     std::vector<double> data_pack;          // set_data: small vectors travel in one copy
 
+    // Matrix values (DESIGN.md "Matrix values"): new values on the resident pattern.  val: the nnz values of the model's CSR in the
+    // caller's order; the five vectors and obj_constant_ (null: kept) in the caller's units and numbering, host memory.  Afterwards
+    // the solver is bit for bit a fresh setup() on the changed model followed by scale(): values scattered through the value maps,
+    // vectors written unscaled in the solver's numbering, iterates zeroed, scale() as it is.  The power iteration is the caller's
+    // next step.  After scale(); single GPU only.  Throws before anything the solver reads is written (a NaN in a vector, a
+    // non-finite value -- found on the device in the staging block).
+    void set_matrix_values(const double *val, long nnz, const double *c_, const double *obj_constant_, const double *AL_, const double *AU_,
+                           const double *l_, const double *u_);
+    // The value maps, built at the first use and kept (4 bytes per entry each): map_A[e] / map_AT[k] = the caller's CSR position of
+    // entry e of A / k of A^T as the device holds them.  map_A stays empty where it is the identity (no locality ordering).
+    void build_value_maps();
+    DBuf<int> map_A, map_AT;
+    bool have_maps = false;
+    bool device_transposed = false;      // setup() built A^T with device_transpose (else csr_transpose_host)
+    DBuf<int> src_rowptr, src_col;       // locality ordering in place: the caller's pattern on the device, until the maps are built
+    DBuf<double> matrix_stage;           // [val | AL | AU | l | u | c], kept between calls while small (as data_stage)
+    DBuf<unsigned long long> values_flag;
+    double matrix_time[5] = {0.0, 0.0, 0.0, 0.0, 0.0};  // the last call: maps (first call only), upload, kernels, scale(), total
+    long matrix_calls = 0;
+
     std::map<int, hipGraphExec_t> graphs;
     TraceRow *trace = nullptr;
     int trace_cap = 0, trace_n = 0;

@@ -204,6 +204,13 @@ def lib():
     L.hprlp_solver_resolve.argtypes = [C.c_void_p, C.c_double, c_dbl_p, c_dbl_p, C.POINTER(CResults), C.POINTER(CTraceRow),
                                        C.c_int, c_int_p]
     L.hprlp_solver_data_seconds.argtypes = [C.c_void_p, c_dbl_p]
+    L.hprlp_solver_set_matrix_values.argtypes = [C.c_void_p, c_dbl_p, C.c_long] + [c_dbl_p] * 6
+    L.hprlp_solver_matrix_seconds.argtypes = [C.c_void_p, c_dbl_p]
+    L.hprlp_solver_value_maps.restype = C.c_long
+    L.hprlp_solver_value_maps.argtypes = [C.c_void_p, c_int_p, c_int_p, C.c_long]
+    L.hprlp_solver_ordering.argtypes = [C.c_void_p, c_int_p, c_int_p]
+    L.hprlp_value_maps_host.argtypes = [C.c_int, C.c_int] + [c_int_p] * 6
+    L.hprlp_batched_solver_set_matrix_values.argtypes = [C.c_void_p, c_dbl_p, C.c_long]
     L.hprlp_presolve_forward.argtypes = [C.c_void_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]
     L.hprlp_solver_power_iteration_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_double, c_dbl_p, c_int_p]
     L.hprlp_solver_iterate_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, c_int_p, C.c_int]
@@ -698,6 +705,18 @@ class BatchedSolver:
         self._last_B = B
         return out
 
+    def set_matrix(self, values):
+        """New values on the shared matrix' pattern (hprlp_batched_solver_set_matrix_values), in the order of the model's CSR.
+        Every later solve() / solve_tensors() gives what a fresh BatchedSolver on the changed model gives; carry is refused
+        until the next successful solve.  ValueError for a wrong length, RuntimeError for a call the library refuses."""
+        if not self._h:
+            raise RuntimeError("BatchedSolver: closed")
+        v = _as(values, np.float64)
+        if v.ndim != 1 or v.shape[0] != self.model.nnz:
+            raise ValueError(f"set_matrix: values must have length {self.model.nnz}, got shape {v.shape}")
+        if lib().hprlp_batched_solver_set_matrix_values(self._h, _dptr(v), v.shape[0]) != 0:
+            raise RuntimeError("hprlp_batched_solver_set_matrix_values failed: " + last_error())
+
     def set_norms(self, rule):
         """The norm rule of solve() -- the host entry -- on this solver: 0 = the reference's long double sums (the default), 1 = the
         tree rule that solve_tensors() always follows; with 1 the two agree bit for bit."""
@@ -875,6 +894,29 @@ def batched_prepare_host(rn, cn, Cmat, AL, AU, l, u, X0=None, Y0=None, use_bc_sc
     out.update(Bp=o.Bp, Bc=o.Bc, panel=out["panel"][:n * o.Bp])
     out.update(zip(BATCH_SCALARS, out.pop("scalars")))
     return out
+
+
+def value_maps_host(m, n, rowptr, colind, row_new2old=None, col_new2old=None):
+    """Host only (hprlp_value_maps_host): (mapA, mapAT) of a CSR pattern under a locality ordering, or under none -- the rule
+    of Solver.value_maps() restated without a GPU."""
+    rp, ci = _as(rowptr, np.int32), _as(colind, np.int32)
+    if rp.ndim != 1 or rp.shape[0] != m + 1:
+        raise ValueError(f"value_maps_host: rowptr must have length {m + 1}, got shape {rp.shape}")
+    nnz = int(rp[m])
+    if ci.ndim != 1 or ci.shape[0] != nnz:
+        raise ValueError(f"value_maps_host: colind must have length {nnz}, got shape {ci.shape}")
+    if (row_new2old is None) != (col_new2old is None):
+        raise ValueError("value_maps_host: both permutations or neither")
+    pr = pc = None
+    if row_new2old is not None:
+        pr, pc = _as(row_new2old, np.int32), _as(col_new2old, np.int32)
+        if pr.shape != (m,) or pc.shape != (n,):
+            raise ValueError(f"value_maps_host: the permutations must have length {m} and {n}")
+    ip = lambda a: None if a is None else a.ctypes.data_as(c_int_p)
+    a, t = np.zeros(max(nnz, 1), np.int32), np.zeros(max(nnz, 1), np.int32)
+    if lib().hprlp_value_maps_host(m, n, ip(rp), ip(ci), ip(pr), ip(pc), ip(a), ip(t)) != 0:
+        raise RuntimeError(last_error())
+    return a[:nnz].copy(), t[:nnz].copy()
 
 
 class Solver:
@@ -1195,6 +1237,55 @@ class Solver:
         out = np.zeros(3)
         self._chk(lib().hprlp_solver_data_seconds(self.h, out.ctypes.data_as(c_dbl_p)))
         return dict(zip(("upload", "kernels", "total"), out))
+
+    def set_matrix(self, values, c, AL, AU, l, u, obj_constant=None):
+        """New matrix values on the resident pattern (hprlp_solver_set_matrix_values), then what prepare() does after scale():
+        power_iteration() and init(-1, 1.01 lambda).  values: the nnz values in the order of the model's CSR; all five vectors are
+        required, in the model's units and numbering.  Afterwards the solver is bit for bit a fresh Solver on the changed model
+        after prepare(); resolve() runs it.  Returns (lambda, power iterations)."""
+        m, n = self.model.m, self.model.n
+        nnz = self.model.nnz if hasattr(self.model, "nnz") else self.info()["nnz"]
+        v = _as(values, np.float64)
+        if v.ndim != 1 or v.shape[0] != nnz:
+            raise ValueError(f"set_matrix: values must have length {nnz}, got shape {v.shape}")
+        vecs = []
+        for arr, length, name in ((c, n, "c"), (AL, m, "AL"), (AU, m, "AU"), (l, n, "l"), (u, n, "u")):
+            if arr is None:
+                raise ValueError(f"set_matrix: {name} is required (length {length})")
+            a = _as(arr, np.float64)
+            if a.ndim != 1 or a.shape[0] != length:
+                raise ValueError(f"set_matrix: {name} must have length {length}, got shape {a.shape}")
+            vecs.append(a)
+        oc = None if obj_constant is None else C.byref(C.c_double(float(obj_constant)))
+        self._chk(lib().hprlp_solver_set_matrix_values(self.h, _dptr(v), nnz, _dptr(vecs[0]), oc, *[_dptr(a) for a in vecs[1:]]))
+        lam, its = self.power_iteration()
+        self.init(-1.0, 1.01 * lam)
+        return lam, its
+
+    def matrix_seconds(self):
+        """Seconds of the last set_matrix() (without its power iteration): {maps (first call only), upload, kernels, scale, total}
+        and the calls so far."""
+        out = np.zeros(6)
+        self._chk(lib().hprlp_solver_matrix_seconds(self.h, out.ctypes.data_as(c_dbl_p)))
+        d = dict(zip(("maps", "upload", "kernels", "scale", "total"), out[:5]))
+        d["calls"] = int(out[5])
+        return d
+
+    def value_maps(self):
+        """(mapA, mapAT) as the solver built them (hprlp_solver_value_maps): the model's CSR position of every entry of A and of
+        A^T in the solver's internal numbering."""
+        nnz = self.info()["nnz"]
+        a, t = np.zeros(max(nnz, 1), np.int32), np.zeros(max(nnz, 1), np.int32)
+        k = lib().hprlp_solver_value_maps(self.h, a.ctypes.data_as(c_int_p), t.ctypes.data_as(c_int_p), nnz)
+        if k < 0:
+            raise RuntimeError(last_error())
+        return a[:k].copy(), t[:k].copy()
+
+    def ordering(self):
+        """The locality ordering in place as (row_new2old, col_new2old), or None without one (hprlp_solver_ordering)."""
+        r, c = np.zeros(max(self.model.m, 1), np.int32), np.zeros(max(self.model.n, 1), np.int32)
+        rc = self._chk(lib().hprlp_solver_ordering(self.h, r.ctypes.data_as(c_int_p), c.ctypes.data_as(c_int_p)))
+        return (r[:self.model.m], c[:self.model.n]) if rc == 1 else None
 
     def certificate(self):
         """The certificate of the last run() (kind 0 without a verdict)."""

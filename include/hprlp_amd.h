@@ -239,6 +239,43 @@ int hprlp_solver_resolve(hprlp_solver *s, double sigma, const double *x0, const 
 /* seconds of the last set_data: {upload, kernels + fetch, total} */
 int hprlp_solver_data_seconds(hprlp_solver *s, double out[3]);
 
+/* ---- matrix values: new coefficients on the resident sparsity pattern (DESIGN.md "Matrix values") -------------------------------
+ * val: the nnz values of the model's CSR in the caller's order, i.e. at the positions of the rowPtr / colIndex the solver was
+ * created from; the pattern is not passed and cannot change (a stored zero switches an entry off).  All five vectors are
+ * required -- every scaled vector depends on the row and column factors, which change with A, and the solver keeps no copy in
+ * the caller's units; obj_constant NULL keeps the current one.  Caller's units and numbering, host memory; infinite sides and
+ * bounds are legal.  After the call the solver is, bit for bit, a fresh hprlp_solver_create on the changed model followed by
+ * hprlp_solver_scale: index arrays, ordering, kernel forms, tiled layouts and captured graphs stay, the iterates are zero.  The
+ * caller's next steps are those after hprlp_solver_scale: hprlp_solver_power_iteration, hprlp_solver_init, then
+ * hprlp_solver_resolve, whose out->time counts this call's seconds as it counts set_data's.
+ * The first call builds the solver's two value maps (internal entry -> caller's position, for A and for A^T) and keeps them: 4
+ * bytes per entry each.  A solver with a locality ordering also holds the caller's index arrays on the device (4 bytes per entry)
+ * from its creation until that first call.
+ * 0, or -1 + hprlp_last_error() with the solver unchanged bit for bit and still usable: a NULL argument, nnz other than the
+ * model's, a sharded solver (one GPU only), a solver never scaled, a NaN in a vector, a non-finite value (found on the device in
+ * the staging block before anything the solver reads is written). */
+int hprlp_solver_set_matrix_values(hprlp_solver *s, const double *val, long nnz, const double *c, const double *obj_constant,
+                                   const double *AL, const double *AU, const double *l, const double *u);
+/* the last successful call: {map construction (first call only, else 0), upload + check, value + vector kernels, scale(), total,
+ *                            calls so far} */
+int hprlp_solver_matrix_seconds(hprlp_solver *s, double out[6]);
+/* the value maps as the solver built them (built now if no set_matrix_values call has): mapA[e] / mapAT[k] = the caller's CSR
+ * position of entry e of A / entry k of A^T in the solver's internal numbering; cap >= nnz ints each.  Returns nnz, or -1. */
+long hprlp_solver_value_maps(hprlp_solver *s, int *mapA, int *mapAT, long cap);
+/* the locality ordering in place: row_new2old (m), col_new2old (n).  1: filled; 0: no ordering, arrays untouched; -1: error */
+int hprlp_solver_ordering(hprlp_solver *s, int *row_new2old, int *col_new2old);
+/* Host only, no GPU: the rule of the maps restated.  Without an ordering (both NULL) mapA is the identity and mapAT the
+ * row-stable transpose's entry permutation; with one, mapA is the entry permutation of P A Q with every row's columns ascending
+ * (ties in the caller's order) and mapAT that of its row-stable transpose. */
+int hprlp_value_maps_host(int m, int n, const int *rowptr, const int *col, const int *row_new2old, const int *col_new2old,
+                          int *mapA, int *mapAT);
+/* The same for the resident batched solver: the shared matrix takes the values and is scaled again (zero vectors, b/c scaling
+ * off), the norms and the created lambda_max follow (HPRLP_BATCH_LAMBDA is read here as at create); panels, staging blocks,
+ * order tables and workspace stay.  The seconds are added to the create's two.  Every later call gives the bits of a fresh
+ * hprlp_batched_solver_create on the changed model followed by the same call; carry is refused until the next successful solve.
+ * 0, or -1 + hprlp_last_error() with the handle unchanged: NULL, a wrong nnz, a non-finite value. */
+int hprlp_batched_solver_set_matrix_values(hprlp_batched_solver *h, const double *val, long nnz);
+
 /* ---- many small LPs at once (one GPU; DESIGN.md "Many small LPs") --------------------------------------------------------------
  * A Netlib-scale LP (nnz < 12288, m, n <= 2048, rows and columns of at most 256 entries) runs as ONE workgroup and occupies one
  * compute unit of 256.  These entry points advance a group of independent solvers -- each with its own matrix -- in lock-step:
