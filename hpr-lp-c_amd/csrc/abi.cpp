@@ -1244,6 +1244,42 @@ extern "C" int hprlp_solver_iterate_many(hprlp_solver **h, int count, const int 
     GUARD_END(-1)
 }
 
+extern "C" int hprlp_solver_residuals_many(hprlp_solver **h, int count, const int *iter, const int *compute_gap, double *out) {
+    GUARD_BEGIN
+    // (the plain arguments first, so that a wrong call is refused whatever the handles are)
+    if (!iter) throw std::runtime_error("hprlp_solver_residuals_many: null iter");
+    if (!compute_gap) throw std::runtime_error("hprlp_solver_residuals_many: null compute_gap");
+    if (!out) throw std::runtime_error("hprlp_solver_residuals_many: null out");
+    for (int k = 0; k < count; ++k)
+        if (iter[k] < 0) throw std::runtime_error("hprlp_solver_residuals_many: iter[" + std::to_string(k) + "] is negative");
+    std::vector<Solver *> s = group_members(h, count, "hprlp_solver_residuals_many");
+    residuals_many(s.data(), count, iter, compute_gap, out);
+    return 0;
+    GUARD_END(-1)
+}
+
+extern "C" int hprlp_solver_restart_many(hprlp_solver **h, int count, const double *in, double *sigma_out) {
+    GUARD_BEGIN
+    if (!in) throw std::runtime_error("hprlp_solver_restart_many: null in");
+    std::vector<Solver *> s = group_members(h, count, "hprlp_solver_restart_many");
+    restart_many(s.data(), count, in, sigma_out);
+    return 0;
+    GUARD_END(-1)
+}
+
+// counts of the calling thread's last hprlp_solver_run_many / hprlp_solve_many (hprlp_last_run_many_counts)
+static thread_local long g_many_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+static void keep_many_counts(const GroupCounts &gc) {
+    const long v[8] = {gc.rounds, gc.waits, gc.group_launches, gc.copies, gc.own, gc.served, 0, 0};
+    for (int i = 0; i < 8; ++i) g_many_counts[i] = v[i];
+}
+
+extern "C" int hprlp_last_run_many_counts(long out[8]) {
+    if (!out) return -1;
+    for (int i = 0; i < 8; ++i) out[i] = g_many_counts[i];
+    return 0;
+}
+
 static void free_results_arrays(HPRLP_results *out, int count) {
     for (int k = 0; k < count; ++k) {
         std::free(out[k].x); std::free(out[k].y); std::free(out[k].z);
@@ -1256,8 +1292,11 @@ extern "C" int hprlp_solver_run_many(hprlp_solver **h, int count, HPRLP_results 
     std::vector<Solver *> s = group_members(h, count, "hprlp_solver_run_many");
     if (!out) throw std::runtime_error("hprlp_solver_run_many: null results");
     for (int k = 0; k < count; ++k) out[k] = make_error_result("ERROR");
+    keep_many_counts(GroupCounts());
     try {
-        run_many(s.data(), count, out);
+        GroupCounts gc;
+        run_many(s.data(), count, out, &gc);
+        keep_many_counts(gc);
     } catch (...) {
         free_results_arrays(out, count);
         throw;
@@ -1287,6 +1326,7 @@ extern "C" int hprlp_solve_many(const LP_info_cpu *const *models, int count, con
     const auto t_call = time_now();
     for (int k = 0; k < count; ++k) out[k] = make_error_result("ERROR");
     for (int i = 0; i < 8; ++i) g_many_phases[i] = 0.0;
+    keep_many_counts(GroupCounts());
     // set-up and scaling, member by member; a model that fails here stays "ERROR" and the others go on
     std::vector<std::unique_ptr<Solver>> owned(static_cast<size_t>(count));
     std::vector<Solver *> s;
@@ -1327,6 +1367,7 @@ extern "C" int hprlp_solve_many(const LP_info_cpu *const *models, int count, con
             g_many_phases[5] = static_cast<double>(gc.rounds);
             g_many_phases[6] = static_cast<double>(gc.waits);
             g_many_phases[7] = static_cast<double>(gc.launches);
+            keep_many_counts(gc);
         } catch (...) {
             free_results_arrays(res.data(), ng);
             throw;

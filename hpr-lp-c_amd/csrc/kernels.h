@@ -4,6 +4,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <memory>
+
 #include "tiled.h"
 
 namespace hprlp {
@@ -354,6 +356,56 @@ struct SmallTaskBuf {
 // with count <= 0 are left out.  Returns the number of launches.
 int launch_small_iterations_many(const SmallIterTask *tasks, int ntasks, SmallTaskBuf &buf, hipStream_t s);
 int launch_small_power_many(const SmallPowerTask *tasks, int ntasks, SmallTaskBuf &buf, hipStream_t s);
+
+// ---- group forms of the regular kernels (kernels.hip, DESIGN.md "Many small LPs"): check step, evaluation and restart of every
+// member of a group in one launch per kernel.  A workgroup runs the single kernel's body as workgroup lb of lg of its member, so a
+// member's partials and scalars are the bits of its own launches.
+// What the stream kernel reads of a matrix that has neither a tiled copy nor split rows.
+struct CsrStream {
+    int nblk, nt;
+    const int *rowptr, *col;
+    const double *val;
+    const int4 *blk;
+    double *long_partial;  // (null, never reached: no block of such a matrix is a chunk of a split row)
+    __host__ __device__ int csr_grid() const { return (nblk + kWavesPerBlock - 1) / kWavesPerBlock; }
+};
+bool group_form_fits(const CsrDev &M);  // every fused launch on M is one k_spmv_fused launch: no tiled copy, no split rows
+// The calls mirror the single launch_* wrappers and only record; run() sends the tables of all records in one copy and issues ONE
+// launch per kind present and stage (next_stage), in the order of a member's own calls (restart copy, ctrl, check x, check y, Rd,
+// Rp, Rp + gap, gap, movement, all finalize items); fetch() packs the scalar blocks recorded by pack() and enqueues one copy to the
+// host; deliver(), after the caller's wait, hands each member its kNumScalars doubles.  Whatever a member enqueues itself between
+// run() and fetch() rides on that copy.  A kind that holds ONE task is issued as that member's own launch (arguments in the
+// launch, no table), and one member's scalars come by its own copy: a group of one issues what the member issues alone.  One
+// run's tables are in flight at a time: the caller waits for the stream between two runs of one object (the staging block is
+// rewritten only after the copy out of it has completed, as for SmallTaskBuf).
+class GroupLaunches {
+  public:
+    GroupLaunches();
+    ~GroupLaunches();
+    GroupLaunches(const GroupLaunches &) = delete;
+    void x_half_check(const CsrDev &AT, const XHalfArgs &a);
+    void y_half_check(const CsrDev &A, const YHalfArgs &a);
+    void resid_d(const CsrDev &AT, const double *ybar_full, const double *c, const double *z_bar, const double *col_norm, double *partials);
+    void resid_p(const CsrDev &A, const double *xbar_full, const double *xtemp_full, const double *AL, const double *AU, const double *row_norm,
+                 const double *y_temp, bool with_gap, double *partials, int stride);
+    void gap(const CsrDev &A, const double *xtemp_full, const double *y_temp, double *partials);
+    void finalize(const FinalizeArgs &f, double *scalars);
+    void movement(int n, int m, const double *x_bar, const double *last_x, double *x_temp, const double *y_bar, const double *last_y, double *y_temp,
+                  double *partials, int stride);
+    void restart_copy(int n, int m, const double *x_bar, double *x, double *last_x, const double *y_bar, double *y, double *last_y, Ctrl *ctrl);
+    void set_ctrl(Ctrl *ctrl, double sigma, double lambda_max, int reset_k);
+    void pack(const double *scalars, double *host);  // a member's device scalars and the host block they go to
+    // What is recorded from here on runs after everything recorded so far, finalize included (one run, one copy of the tables
+    // all the same).  Needed where a later kernel overwrites partials an earlier finalize reads: an evaluation's Rd writes part_x,
+    // where the check step before it left the partials of c.x -- alone, the member finalises the check step in between.
+    void next_stage();
+    int run(hipStream_t s);    // returns the number of launches
+    int fetch(hipStream_t s);  // returns the number of copies to the host (0: nothing was recorded by pack())
+    void deliver();
+  private:
+    struct Impl;
+    std::unique_ptr<Impl> impl;
+};
 
 // device CSR -> device CSR of the transpose, stable in row order (transpose.hip); all pointers are device memory,
 // trp has cols+1 entries, tci / tv nnz

@@ -15,6 +15,8 @@
 #include "kernels.h"
 
 #include <algorithm>
+#include <cstring>
+#include <stdexcept>
 #include <vector>
 #include <cmath>
 #include <type_traits>
@@ -36,11 +38,12 @@ __device__ __forceinline__ double wave_max(double v) {
     return v;
 }
 
-// Sum NACC per-thread accumulators over the block; thread 0 stores partials[i*stride + blockIdx.x].
+// Sum NACC per-thread accumulators over the block; thread 0 stores partials[i*stride + bid] (bid: blockIdx.x, or the workgroup's
+// place in its member's launch when a group kernel runs the body -- DESIGN.md "Many small LPs").
 // The last NMAX of them are maxima instead of sums (the ray test's violations, RayRowEpi / RayColEpi).
 // `red`: NW * NACC doubles of LDS that no lane still uses.
 template <int NACC, int NW, int NMAX = 0>
-__device__ __forceinline__ void block_store_partials_in(double (&acc)[NACC], double *partials, int stride, double (*red)[NACC > 0 ? NACC : 1]) {
+__device__ __forceinline__ void block_store_partials_in(double (&acc)[NACC], double *partials, int stride, double (*red)[NACC > 0 ? NACC : 1], int bid) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
     for (int i = 0; i < NACC; ++i) {
@@ -54,15 +57,23 @@ __device__ __forceinline__ void block_store_partials_in(double (&acc)[NACC], dou
             double v = red[0][i];
 #pragma unroll
             for (int w = 1; w < NW; ++w) v = i < NACC - NMAX ? v + red[w][i] : fmax(v, red[w][i]);
-            partials[(size_t)i * stride + blockIdx.x] = v;
+            partials[(size_t)i * stride + bid] = v;
         }
     }
 }
+template <int NACC, int NW, int NMAX = 0>
+__device__ __forceinline__ void block_store_partials_in(double (&acc)[NACC], double *partials, int stride, double (*red)[NACC > 0 ? NACC : 1]) {
+    block_store_partials_in<NACC, NW, NMAX>(acc, partials, stride, red, blockIdx.x);
+}
 
 template <int NACC, int NW = kWavesPerBlock, int NMAX = 0>
-__device__ __forceinline__ void block_store_partials(double (&acc)[NACC], double *partials, int stride) {
+__device__ __forceinline__ void block_store_partials_at(double (&acc)[NACC], double *partials, int stride, int bid) {
     __shared__ double red[NW][NACC > 0 ? NACC : 1];
-    block_store_partials_in<NACC, NW, NMAX>(acc, partials, stride, red);
+    block_store_partials_in<NACC, NW, NMAX>(acc, partials, stride, red, bid);
+}
+template <int NACC, int NW = kWavesPerBlock, int NMAX = 0>
+__device__ __forceinline__ void block_store_partials(double (&acc)[NACC], double *partials, int stride) {
+    block_store_partials_at<NACC, NW, NMAX>(acc, partials, stride, blockIdx.x);
 }
 
 // Epilogues whose last kMaxAccs accumulators are maxima (default: none)
@@ -102,8 +113,22 @@ struct LogTerm : std::false_type {};
 template <class Epi>
 struct LogTerm<Epi, std::void_t<decltype(Epi::kLogTerm)>> : std::true_type {};
 
+// An epilogue whose begin() has one workgroup of the launch write something (the half-steps' counter hand-off) names that workgroup
+// through begin_at(bid); everybody else has a plain begin().
+template <class Epi, class = void>
+struct BeginOf {
+    static __device__ __forceinline__ void f(Epi &e, int) { e.begin(); }
+};
 template <class Epi>
-__global__ void __launch_bounds__(kThreads) k_spmv_fused(CsrDev A, Epi epi) {
+struct BeginOf<Epi, std::void_t<decltype(&Epi::begin_at)>> {
+    static __device__ __forceinline__ void f(Epi &e, int bid) { e.begin_at(bid); }
+};
+
+// The body of k_spmv_fused and of k_spmv_fused_many: workgroup `bid` of a launch of `grid` workgroups on the matrix A (Mat: CsrDev,
+// or the stream kernel's part of it, CsrStream).  bid and grid enter in two places only: the XCD-contiguous remap and the index of
+// the reduction partials (and, for the half-steps, which workgroup hands the counter over).
+template <class Epi, class Mat>
+__device__ __forceinline__ void spmv_fused_body(const Mat &A, Epi &epi, const int bid, const int grid) {
     constexpr int NV = Epi::NV;
     constexpr int NACC = Epi::NACC;
     __shared__ double lds[kWavesPerBlock][NV][kStreamW];
@@ -114,14 +139,14 @@ __global__ void __launch_bounds__(kThreads) k_spmv_fused(CsrDev A, Epi epi) {
     // gather through ONE 4 MiB L2 instead of pulling the same lines of the vector into up to eight of them (block-angular
     // ladder point, y-half: 1.65 x the algorithmic bytes left the L2s with the plain blockIdx order).  A bijection of
     // [0, gridDim.x): share x owns start_x = x * (grid / 8) + min(x, grid % 8) and the next grid / 8 (+ 1) workgroups.
-    const int xcd = blockIdx.x & 7, per_lo = gridDim.x >> 3, rem = gridDim.x & 7;
-    const int wg = xcd * per_lo + min(xcd, rem) + (blockIdx.x >> 3);
+    const int xcd = bid & 7, per_lo = grid >> 3, rem = grid & 7;
+    const int wg = xcd * per_lo + min(xcd, rem) + (bid >> 3);
     const int b = wg * kWavesPerBlock + wave;
     double acc[NACC > 0 ? NACC : 1];
 #pragma unroll
     for (int i = 0; i < (NACC > 0 ? NACC : 1); ++i) acc[i] = 0.0;
 
-    epi.begin();
+    BeginOf<Epi>::f(epi, bid);
 
     if (b < A.nblk) {
         const int4 d = A.blk[b];
@@ -280,9 +305,13 @@ __global__ void __launch_bounds__(kThreads) k_spmv_fused(CsrDev A, Epi epi) {
             }
         }
     }
-    if constexpr (NACC > 0) block_store_partials<NACC, kWavesPerBlock, MaxAccs<Epi>::value>(acc, epi.partials, epi.stride);
+    if constexpr (NACC > 0) block_store_partials_at<NACC, kWavesPerBlock, MaxAccs<Epi>::value>(acc, epi.partials, epi.stride, bid);
 }
 
+template <class Epi>
+__global__ void __launch_bounds__(kThreads) k_spmv_fused(CsrDev A, Epi epi) {
+    spmv_fused_body<Epi>(A, epi, blockIdx.x, gridDim.x);
+}
 
 // ------------------------------------------------------------------------------------------------
 // the column-tiled fused kernel (format and rationale: tiled.h).  One workgroup = one super-block of
@@ -1205,14 +1234,15 @@ struct XEpi {
     struct Row {
         double xi, ci, li, ui, lx;
     };
-    __device__ __forceinline__ void begin() {
+    __device__ __forceinline__ void begin() { begin_at(blockIdx.x); }
+    __device__ __forceinline__ void begin_at(int bid) {
         const int k = ctrl->kx;
         sigma = ctrl->sigma;
         f1 = 1.0 / (static_cast<double>(k) + 2.0);
         f2 = 1.0 - f1;
         f1p = 1.0 / (static_cast<double>(k - 1) + 2.0);  // (as the previous x-half formed its f1, f2)
         f2p = 1.0 - f1p;
-        if (blockIdx.x == 0 && threadIdx.x == 0) ctrl->ky = k;
+        if (bid == 0 && threadIdx.x == 0) ctrl->ky = k;
     }
     __device__ __forceinline__ Row load_row(int r) const {
         constexpr bool NT = STREAMED && HPRLP_EPI_NT >= 1;
@@ -1282,13 +1312,14 @@ struct YEpi {
     struct Row {
         double yi, lo, hi, ly;
     };
-    __device__ __forceinline__ void begin() {
+    __device__ __forceinline__ void begin() { begin_at(blockIdx.x); }
+    __device__ __forceinline__ void begin_at(int bid) {
         const int k = ctrl->ky;
         fact1 = ctrl->lam_sigma;
         fact2 = ctrl->inv_lam_sigma;
         hf1 = 1.0 / (static_cast<double>(k) + 2.0);
         hf2 = 1.0 - hf1;
-        if (blockIdx.x == 0 && threadIdx.x == 0) ctrl->kx = k + 1;
+        if (bid == 0 && threadIdx.x == 0) ctrl->kx = k + 1;
     }
     __device__ __forceinline__ Row load_row(int r) const {
         constexpr bool NT = STREAMED && HPRLP_EPI_NT >= 1;
@@ -1809,8 +1840,8 @@ void launch_start_row(const CsrDev &A, const double *xbar_full, const double *AL
 // scalar finalisation: out[slot] = sum of a partial array, one block per item, fixed order
 // ------------------------------------------------------------------------------------------------
 static_assert(kWavesPerBlock == 4, "k_finalize's sum adds the four waves' partials in a fixed order");
-__global__ void __launch_bounds__(kThreads) k_finalize(FinalizeArgs f, double *scalars) {
-    const FinalizeItem it = f.item[blockIdx.x];
+// (the body of k_finalize and of k_finalize_many: one workgroup, one item)
+__device__ __forceinline__ void finalize_body(const FinalizeItem &it, double *scalars) {
     __shared__ double red[kWavesPerBlock];
     if (it.max) {  // (uniform per block) partials of nonnegative maxima
         double v = 0.0;
@@ -1833,6 +1864,10 @@ __global__ void __launch_bounds__(kThreads) k_finalize(FinalizeArgs f, double *s
     if (threadIdx.x == 0) scalars[it.slot] = ((red[0] + red[1]) + red[2]) + red[3];
 }
 
+__global__ void __launch_bounds__(kThreads) k_finalize(FinalizeArgs f, double *scalars) {
+    finalize_body(f.item[blockIdx.x], scalars);
+}
+
 void launch_finalize(const FinalizeArgs &f, double *scalars, hipStream_t s) {
     if (f.n <= 0) return;
     hipLaunchKernelGGL(k_finalize, dim3(f.n), dim3(kThreads), 0, s, f, scalars);
@@ -1841,11 +1876,11 @@ void launch_finalize(const FinalizeArgs &f, double *scalars, hipStream_t s) {
 // ------------------------------------------------------------------------------------------------
 // plain vector kernels (grid-stride, fixed grids so partial counts are static)
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(kThreads) k_movement(int n, int m, const double *x_bar, const double *last_x,
-                                                      double *x_temp, const double *y_bar, const double *last_y,
-                                                      double *y_temp, double *partials, int stride) {
+// (the body of k_movement and of k_movement_many: workgroup `bid` of `grid`)
+__device__ __forceinline__ void movement_body(int n, int m, const double *x_bar, const double *last_x, double *x_temp, const double *y_bar,
+                                              const double *last_y, double *y_temp, double *partials, int stride, int bid, int grid) {
     double acc[2] = {0.0, 0.0};
-    const int tid = blockIdx.x * kThreads + threadIdx.x, nth = gridDim.x * kThreads;
+    const int tid = bid * kThreads + threadIdx.x, nth = grid * kThreads;
     for (int i = tid; i < n; i += nth) {
         const double d = 1.0 * x_bar[i] + (-1.0) * last_x[i];
         x_temp[i] = d;
@@ -1856,7 +1891,13 @@ __global__ void __launch_bounds__(kThreads) k_movement(int n, int m, const doubl
         y_temp[i] = d;
         acc[1] += d * d;
     }
-    block_store_partials<2>(acc, partials, stride);
+    block_store_partials_at<2>(acc, partials, stride, bid);
+}
+
+__global__ void __launch_bounds__(kThreads) k_movement(int n, int m, const double *x_bar, const double *last_x,
+                                                      double *x_temp, const double *y_bar, const double *last_y,
+                                                      double *y_temp, double *partials, int stride) {
+    movement_body(n, m, x_bar, last_x, x_temp, y_bar, last_y, y_temp, partials, stride, blockIdx.x, gridDim.x);
 }
 
 void launch_movement(int n, int m, const double *x_bar, const double *last_x, double *x_temp, const double *y_bar,
@@ -1865,9 +1906,10 @@ void launch_movement(int n, int m, const double *x_bar, const double *last_x, do
                        y_temp, partials, stride);
 }
 
-__global__ void __launch_bounds__(kThreads) k_restart_copy(int n, int m, const double *x_bar, double *x, double *last_x,
-                                                          const double *y_bar, double *y, double *last_y, Ctrl *ctrl) {
-    const int tid = blockIdx.x * kThreads + threadIdx.x, nth = gridDim.x * kThreads;
+// (the body of k_restart_copy and of k_restart_copy_many: workgroup `bid` of `grid`)
+__device__ __forceinline__ void restart_copy_body(int n, int m, const double *x_bar, double *x, double *last_x, const double *y_bar, double *y,
+                                                  double *last_y, Ctrl *ctrl, int bid, int grid) {
+    const int tid = bid * kThreads + threadIdx.x, nth = grid * kThreads;
     for (int i = tid; i < n; i += nth) {
         const double v = x_bar[i];
         x[i] = v;
@@ -1882,6 +1924,11 @@ __global__ void __launch_bounds__(kThreads) k_restart_copy(int n, int m, const d
         ctrl->kx = 0;
         ctrl->ky = 0;
     }
+}
+
+__global__ void __launch_bounds__(kThreads) k_restart_copy(int n, int m, const double *x_bar, double *x, double *last_x,
+                                                          const double *y_bar, double *y, double *last_y, Ctrl *ctrl) {
+    restart_copy_body(n, m, x_bar, x, last_x, y_bar, y, last_y, ctrl, blockIdx.x, gridDim.x);
 }
 
 static int vec_grid(long n) {
@@ -1916,18 +1963,21 @@ void launch_lu(int n, const double *x_bar, const double *l, const double *u, con
     hipLaunchKernelGGL(k_lu, dim3(nblocks), dim3(kThreads), 0, s, n, x_bar, l, u, col_norm, x_temp, partials);
 }
 
-__global__ void k_set_ctrl(Ctrl *ctrl, double sigma, double lambda_max, int reset_k) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        const double f = lambda_max * sigma;
-        ctrl->sigma = sigma;
-        ctrl->lam_sigma = f;
-        ctrl->inv_lam_sigma = 1.0 / f;
-        ctrl->inv_sigma = 1.0 / sigma;
-        if (reset_k) {
-            ctrl->kx = 0;
-            ctrl->ky = 0;
-        }
+// (the body of k_set_ctrl and of k_set_ctrl_many: one thread)
+__device__ __forceinline__ void set_ctrl_body(Ctrl *ctrl, double sigma, double lambda_max, int reset_k) {
+    const double f = lambda_max * sigma;
+    ctrl->sigma = sigma;
+    ctrl->lam_sigma = f;
+    ctrl->inv_lam_sigma = 1.0 / f;
+    ctrl->inv_sigma = 1.0 / sigma;
+    if (reset_k) {
+        ctrl->kx = 0;
+        ctrl->ky = 0;
     }
+}
+
+__global__ void k_set_ctrl(Ctrl *ctrl, double sigma, double lambda_max, int reset_k) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) set_ctrl_body(ctrl, sigma, lambda_max, reset_k);
 }
 
 void launch_set_ctrl(Ctrl *ctrl, double sigma, double lambda_max, int reset_k, hipStream_t s) {
@@ -2776,6 +2826,344 @@ void launch_pack(const double *src, const int *idx, double *dst, int n, hipStrea
 }
 void launch_scatter(double *dst, const int *idx, const double *src, int n, hipStream_t s) {
     if (n > 0) hipLaunchKernelGGL(k_scatter, dim3(vec_grid(n)), dim3(kThreads), 0, s, dst, idx, src, n);
+}
+
+// ------------------------------------------------------------------------------------------------
+// group forms of the regular kernels (DESIGN.md "Many small LPs"): one launch serves every member of a group of small LPs.
+// A workgroup looks up {task, its place lb in the member's own launch} and runs the single kernel's body for workgroup lb of
+// lg = the member's own grid -- the same instructions on the same operands in the same order, so every partial and every
+// finalised scalar is the bits the member computes alone.  No workgroup reads what a workgroup of another member writes.
+// ------------------------------------------------------------------------------------------------
+template <class Epi>
+struct GroupTask {
+    CsrStream A;
+    Epi epi;
+};
+struct FinalizeOne {
+    FinalizeItem it;
+    double *scalars;
+};
+struct MovementTask {
+    int n, m;
+    const double *x_bar, *last_x;
+    double *x_temp;
+    const double *y_bar, *last_y;
+    double *y_temp, *partials;
+    int stride;
+};
+struct RestartCopyTask {
+    int n, m;
+    const double *x_bar;
+    double *x, *last_x;
+    const double *y_bar;
+    double *y, *last_y;
+    Ctrl *ctrl;
+    int grid;  // of the member's own launch (vec_grid)
+};
+struct SetCtrlTask {
+    Ctrl *ctrl;
+    double sigma, lambda_max;
+    int reset_k;
+};
+
+// (the task read is uniform in the workgroup: scalar loads into a private copy, before anything is stored)
+template <class Epi>
+__global__ void __launch_bounds__(kThreads) k_spmv_fused_many(const GroupTask<Epi> *__restrict__ tasks, const int2 *__restrict__ wgmap) {
+    const int2 w = wgmap[blockIdx.x];
+    const CsrStream A = tasks[w.x].A;
+    Epi epi = tasks[w.x].epi;
+    spmv_fused_body<Epi>(A, epi, w.y, A.csr_grid());
+}
+
+__global__ void __launch_bounds__(kThreads) k_finalize_many(const FinalizeOne *__restrict__ items) {
+    const FinalizeOne o = items[blockIdx.x];
+    finalize_body(o.it, o.scalars);
+}
+
+// kReduceBlocks workgroups per member, as the member's own launch
+__global__ void __launch_bounds__(kThreads) k_movement_many(const MovementTask *__restrict__ tasks) {
+    const MovementTask t = tasks[blockIdx.x / kReduceBlocks];
+    movement_body(t.n, t.m, t.x_bar, t.last_x, t.x_temp, t.y_bar, t.last_y, t.y_temp, t.partials, t.stride, blockIdx.x % kReduceBlocks,
+                  kReduceBlocks);
+}
+
+__global__ void __launch_bounds__(kThreads) k_restart_copy_many(const RestartCopyTask *__restrict__ tasks, const int2 *__restrict__ wgmap) {
+    const int2 w = wgmap[blockIdx.x];
+    const RestartCopyTask t = tasks[w.x];
+    restart_copy_body(t.n, t.m, t.x_bar, t.x, t.last_x, t.y_bar, t.y, t.last_y, t.ctrl, w.y, t.grid);
+}
+
+__global__ void __launch_bounds__(kThreads) k_set_ctrl_many(const SetCtrlTask *__restrict__ tasks, int ntasks) {
+    const int i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= ntasks) return;
+    const SetCtrlTask t = tasks[i];
+    set_ctrl_body(t.ctrl, t.sigma, t.lambda_max, t.reset_k);
+}
+
+// the members' kNumScalars-slot blocks side by side (one copy to the host serves the group)
+__global__ void __launch_bounds__(kWave) k_pack_scalars(const double *const *__restrict__ src, double *__restrict__ dst) {
+    if (threadIdx.x < kNumScalars) dst[blockIdx.x * kNumScalars + threadIdx.x] = src[blockIdx.x][threadIdx.x];
+}
+
+bool group_form_fits(const CsrDev &M) { return !M.tiled.valid && M.nlong == 0 && M.nblk > 0; }
+
+namespace {
+// the finalize items of a stage are one member's and fit one k_finalize launch
+bool one_members_items(const std::vector<FinalizeOne> &fin) {
+    if (fin.empty() || fin.size() > 8) return false;
+    for (const FinalizeOne &o : fin)
+        if (o.scalars != fin[0].scalars) return false;
+    return true;
+}
+CsrStream stream_part(const CsrDev &M) {
+    if (!group_form_fits(M)) throw std::runtime_error("a matrix of a group launch does not run the stream kernel alone");
+    return CsrStream{M.nblk, M.nt, M.rowptr, M.col, M.val, M.blk, nullptr};
+}
+}  // namespace
+
+// The records of one stage: kinds that may share a run in the fixed order below without one reading or overwriting what another
+// still needs (a check step's partials in part_x are overwritten by the next evaluation's Rd: the two are different stages).
+struct GroupStage {
+    std::vector<GroupTask<XEpi<true>>> xs;
+    std::vector<GroupTask<YEpi<true>>> ys;
+    std::vector<GroupTask<RdEpi>> rd;
+    std::vector<GroupTask<RpEpi<false>>> rp;
+    std::vector<GroupTask<RpEpi<true>>> rpg;
+    std::vector<GroupTask<GapEpi>> gap;
+    std::vector<FinalizeOne> fin;
+    std::vector<MovementTask> mov;
+    std::vector<RestartCopyTask> rc;
+    std::vector<SetCtrlTask> sc;
+    bool empty() const {
+        return xs.empty() && ys.empty() && rd.empty() && rp.empty() && rpg.empty() && gap.empty() && fin.empty() && mov.empty() && rc.empty() &&
+               sc.empty();
+    }
+};
+
+struct GroupLaunches::Impl {
+    std::vector<GroupStage> stages = std::vector<GroupStage>(1);
+    GroupStage &st() { return stages.back(); }
+    std::vector<const double *> pack_src;
+    std::vector<double *> pack_dst;  // the members' host blocks
+    size_t pack_at = 0;              // where the last run's block holds the members' scalar pointers
+    const double *pack_one = nullptr;  // ... or the one member's scalars
+    int pack_n = 0, deliver_n = 0;   // members to pack (fetch) / to hand their scalars (deliver)
+    SmallTaskBuf buf;
+    DBuf<double> packed_d;
+    HBuf<double> packed_h;
+    std::vector<double *> deliver_to;
+    std::vector<char> bytes;  // the tables of a run, as they travel
+    std::vector<int2> map;
+
+    size_t put(const void *p, size_t n) {
+        const size_t at = (bytes.size() + 15) / 16 * 16;
+        bytes.resize(at + n);
+        std::memcpy(bytes.data() + at, p, n);
+        return at;
+    }
+    template <class Task, class GridOf>
+    size_t put_map(const std::vector<Task> &tasks, GridOf grid_of, int *nwg) {
+        map.clear();
+        for (size_t t = 0; t < tasks.size(); ++t)
+            for (int lb = 0, lg = grid_of(tasks[t]); lb < lg; ++lb) map.push_back(int2{static_cast<int>(t), lb});
+        *nwg = static_cast<int>(map.size());
+        return put(map.data(), map.size() * sizeof(int2));
+    }
+};
+
+GroupLaunches::GroupLaunches() : impl(new Impl()) {}
+GroupLaunches::~GroupLaunches() = default;
+
+void GroupLaunches::next_stage() {
+    if (!impl->st().empty()) impl->stages.emplace_back();
+}
+void GroupLaunches::x_half_check(const CsrDev &AT, const XHalfArgs &a) {
+    XEpi<true> e{{a.y_full}, a.x, a.x_hat, a.l, a.u, a.c, a.last_x, a.x_bar, a.z_bar, a.x_temp, a.ctrl, a.partials, a.stride, 0, 0, 0, FarPush{}, a.lu_code};
+    impl->st().xs.push_back({stream_part(AT), e});
+}
+void GroupLaunches::y_half_check(const CsrDev &A, const YHalfArgs &a) {
+    YEpi<true> e{{a.xhat_full}, a.y, a.AL, a.AU, a.last_y, a.y_bar, a.y_obj, a.y_temp, a.ctrl, a.partials, a.stride, 0, 0, 0, 0, FarPush{}, a.row_code};
+    impl->st().ys.push_back({stream_part(A), e});
+}
+void GroupLaunches::resid_d(const CsrDev &AT, const double *ybar_full, const double *c, const double *z_bar, const double *col_norm,
+                            double *partials) {
+    impl->st().rd.push_back({stream_part(AT), RdEpi{{ybar_full}, c, z_bar, col_norm, partials, AT.grid()}});
+}
+void GroupLaunches::resid_p(const CsrDev &A, const double *xbar_full, const double *xtemp_full, const double *AL, const double *AU,
+                            const double *row_norm, const double *y_temp, bool with_gap, double *partials, int stride) {
+    if (with_gap) impl->st().rpg.push_back({stream_part(A), RpEpi<true>{{xbar_full, xtemp_full}, AL, AU, row_norm, y_temp, partials, stride}});
+    else impl->st().rp.push_back({stream_part(A), RpEpi<false>{{xbar_full}, AL, AU, row_norm, nullptr, partials, stride}});
+}
+void GroupLaunches::gap(const CsrDev &A, const double *xtemp_full, const double *y_temp, double *partials) {
+    impl->st().gap.push_back({stream_part(A), GapEpi{{xtemp_full}, y_temp, partials, A.grid()}});
+}
+void GroupLaunches::finalize(const FinalizeArgs &f, double *scalars) {
+    for (int i = 0; i < f.n; ++i) impl->st().fin.push_back({f.item[i], scalars});
+}
+void GroupLaunches::movement(int n, int m, const double *x_bar, const double *last_x, double *x_temp, const double *y_bar, const double *last_y,
+                             double *y_temp, double *partials, int stride) {
+    impl->st().mov.push_back({n, m, x_bar, last_x, x_temp, y_bar, last_y, y_temp, partials, stride});
+}
+void GroupLaunches::restart_copy(int n, int m, const double *x_bar, double *x, double *last_x, const double *y_bar, double *y, double *last_y,
+                                 Ctrl *ctrl) {
+    impl->st().rc.push_back({n, m, x_bar, x, last_x, y_bar, y, last_y, ctrl, vec_grid(n > m ? n : m)});
+}
+void GroupLaunches::set_ctrl(Ctrl *ctrl, double sigma, double lambda_max, int reset_k) { impl->st().sc.push_back({ctrl, sigma, lambda_max, reset_k}); }
+void GroupLaunches::pack(const double *scalars, double *host) {
+    impl->pack_src.push_back(scalars);
+    impl->pack_dst.push_back(host);
+}
+
+int GroupLaunches::run(hipStream_t s) {
+    Impl &g = *impl;
+    g.bytes.clear();
+    // ---- the tables of every kind present in every stage, in one block
+    struct Spot {
+        size_t tasks = 0, map = 0;
+        int nwg = 0;
+    };
+    struct Spots {
+        Spot x, y, rd, rp, rpg, gap, fin, mov, rc, sc;
+    };
+    std::vector<Spots> spots(g.stages.size());
+    // A kind with ONE task is that member's own launch, arguments in the launch and no table: a group of one (or the last member
+    // still running) issues what it issues alone.
+    auto spmv_tables = [&](auto &tasks, Spot &sp) {
+        if (tasks.size() < 2) return;
+        sp.tasks = g.put(tasks.data(), tasks.size() * sizeof(tasks[0]));
+        sp.map = g.put_map(tasks, [](const auto &t) { return t.A.csr_grid(); }, &sp.nwg);
+    };
+    for (size_t i = 0; i < g.stages.size(); ++i) {
+        GroupStage &t = g.stages[i];
+        Spots &p = spots[i];
+        if (t.rc.size() > 1) {
+            p.rc.tasks = g.put(t.rc.data(), t.rc.size() * sizeof(RestartCopyTask));
+            p.rc.map = g.put_map(t.rc, [](const RestartCopyTask &r) { return r.grid; }, &p.rc.nwg);
+        }
+        if (t.sc.size() > 1) p.sc.tasks = g.put(t.sc.data(), t.sc.size() * sizeof(SetCtrlTask));
+        spmv_tables(t.xs, p.x);
+        spmv_tables(t.ys, p.y);
+        spmv_tables(t.rd, p.rd);
+        spmv_tables(t.rp, p.rp);
+        spmv_tables(t.rpg, p.rpg);
+        spmv_tables(t.gap, p.gap);
+        if (t.mov.size() > 1) p.mov.tasks = g.put(t.mov.data(), t.mov.size() * sizeof(MovementTask));
+        if (!one_members_items(t.fin)) p.fin.tasks = g.put(t.fin.data(), t.fin.size() * sizeof(FinalizeOne));
+    }
+    size_t pack_at = 0;
+    if (g.pack_src.size() > 1) pack_at = g.put(g.pack_src.data(), g.pack_src.size() * sizeof(const double *));
+    int launches = 0;
+    if (!g.bytes.empty()) {
+        std::memcpy(g.buf.stage(g.bytes.size()), g.bytes.data(), g.bytes.size());
+        g.buf.send(g.bytes.size(), s);
+    }
+    const char *dev = static_cast<const char *>(g.buf.dev);
+    auto launched = [&]() {
+        HIP_CHECK(hipGetLastError());  // (a refused launch must not pass silently)
+        ++launches;
+    };
+    auto spmv_launch = [&](auto &tasks, const Spot &sp) {
+        using Task = std::decay_t<decltype(tasks[0])>;
+        using Epi = decltype(Task::epi);
+        if (tasks.size() == 1) {
+            const CsrStream &a = tasks[0].A;
+            CsrDev M;  // (what k_spmv_fused reads of it)
+            M.nblk = a.nblk, M.nt = a.nt, M.rowptr = a.rowptr, M.col = a.col, M.val = const_cast<double *>(a.val), M.blk = a.blk;
+            hipLaunchKernelGGL(k_spmv_fused<Epi>, dim3(a.csr_grid()), dim3(kThreads), 0, s, M, tasks[0].epi);
+            launched();
+            return;
+        }
+        if (sp.nwg <= 0) return;
+        hipLaunchKernelGGL(k_spmv_fused_many<Epi>, dim3(sp.nwg), dim3(kThreads), 0, s, reinterpret_cast<const Task *>(dev + sp.tasks),
+                           reinterpret_cast<const int2 *>(dev + sp.map));
+        launched();
+    };
+    // ---- stage by stage one launch per kind present, in the order of a member's own calls: restart copy, ctrl, check x / y,
+    // residuals, gap, movement, then every finalize item of the stage
+    for (size_t i = 0; i < g.stages.size(); ++i) {
+        GroupStage &t = g.stages[i];
+        const Spots &p = spots[i];
+        if (t.rc.size() == 1) {
+            const RestartCopyTask &r = t.rc[0];
+            launch_restart_copy(r.n, r.m, r.x_bar, r.x, r.last_x, r.y_bar, r.y, r.last_y, r.ctrl, s);
+            launched();
+        } else if (p.rc.nwg > 0) {
+            hipLaunchKernelGGL(k_restart_copy_many, dim3(p.rc.nwg), dim3(kThreads), 0, s, reinterpret_cast<const RestartCopyTask *>(dev + p.rc.tasks),
+                               reinterpret_cast<const int2 *>(dev + p.rc.map));
+            launched();
+        }
+        if (t.sc.size() == 1) {
+            launch_set_ctrl(t.sc[0].ctrl, t.sc[0].sigma, t.sc[0].lambda_max, t.sc[0].reset_k, s);
+            launched();
+        } else if (!t.sc.empty()) {
+            const int n = static_cast<int>(t.sc.size());
+            hipLaunchKernelGGL(k_set_ctrl_many, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, s,
+                               reinterpret_cast<const SetCtrlTask *>(dev + p.sc.tasks), n);
+            launched();
+        }
+        spmv_launch(t.xs, p.x);
+        spmv_launch(t.ys, p.y);
+        spmv_launch(t.rd, p.rd);
+        spmv_launch(t.rp, p.rp);
+        spmv_launch(t.rpg, p.rpg);
+        spmv_launch(t.gap, p.gap);
+        if (t.mov.size() == 1) {
+            const MovementTask &v = t.mov[0];
+            launch_movement(v.n, v.m, v.x_bar, v.last_x, v.x_temp, v.y_bar, v.last_y, v.y_temp, v.partials, v.stride, kReduceBlocks, s);
+            launched();
+        } else if (!t.mov.empty()) {
+            hipLaunchKernelGGL(k_movement_many, dim3(static_cast<unsigned>(t.mov.size()) * kReduceBlocks), dim3(kThreads), 0, s,
+                               reinterpret_cast<const MovementTask *>(dev + p.mov.tasks));
+            launched();
+        }
+        if (one_members_items(t.fin)) {
+            FinalizeArgs f{};
+            for (const FinalizeOne &o : t.fin) f.item[f.n++] = o.it;
+            launch_finalize(f, t.fin[0].scalars, s);
+            launched();
+        } else if (!t.fin.empty()) {
+            hipLaunchKernelGGL(k_finalize_many, dim3(static_cast<unsigned>(t.fin.size())), dim3(kThreads), 0, s,
+                               reinterpret_cast<const FinalizeOne *>(dev + p.fin.tasks));
+            launched();
+        }
+    }
+    g.stages.assign(1, GroupStage());
+    g.pack_at = pack_at;
+    g.pack_n = static_cast<int>(g.pack_src.size());
+    g.pack_one = g.pack_src.empty() ? nullptr : g.pack_src[0];
+    g.deliver_to.swap(g.pack_dst);
+    g.pack_src.clear();
+    g.pack_dst.clear();
+    return launches;
+}
+
+int GroupLaunches::fetch(hipStream_t s) {
+    Impl &g = *impl;
+    const int n = g.pack_n;
+    if (n <= 0) return 0;
+    if (n == 1) {  // (one member: its own copy, as Solver::fetch_enqueue)
+        HIP_CHECK(hipMemcpyAsync(g.deliver_to[0], g.pack_one, kNumScalars * sizeof(double), hipMemcpyDeviceToHost, s));
+        g.pack_n = 0;
+        return 1;
+    }
+    const size_t want = static_cast<size_t>(n) * kNumScalars;
+    if (g.packed_d.n < want) {  // (nothing of an earlier fetch is in flight: the caller has waited and delivered)
+        g.packed_d.alloc(2 * want);
+        g.packed_h.alloc(2 * want, false);
+    }
+    hipLaunchKernelGGL(k_pack_scalars, dim3(n), dim3(kWave), 0, s, reinterpret_cast<const double *const *>(static_cast<const char *>(g.buf.dev) + g.pack_at),
+                       g.packed_d.p);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(g.packed_h.p, g.packed_d.p, want * sizeof(double), hipMemcpyDeviceToHost, s));
+    g.pack_n = 0;
+    g.deliver_n = n;
+    return 1;
+}
+
+void GroupLaunches::deliver() {
+    Impl &g = *impl;
+    for (int k = 0; k < g.deliver_n; ++k) std::memcpy(g.deliver_to[k], g.packed_h.p + static_cast<size_t>(k) * kNumScalars, kNumScalars * sizeof(double));
+    g.deliver_n = 0;
 }
 
 // warm-up (abi.cpp: hprlp_warmup): an attribute query makes the runtime load this translation unit's code object now instead

@@ -2,9 +2,13 @@
 //
 // A Netlib-scale LP runs as one workgroup (small.hip) and keeps one CU of 256 busy.  K such LPs, each with its own matrix, are
 // advanced together here: one k_small_iterations_many launch per <KMAX, R> class carries the normal iterations of every member
-// (workgroup b = member b, the single-LP kernel's arithmetic on the member's own arguments), and one host wait serves the
-// evaluations of all members.  Everything else -- check step, evaluation, stopping test, restart rule, sigma update, detection --
-// is the member's own code (the pieces of Solver::solve_loop), so a member's iterates and results are the bits it gets alone.
+// (workgroup b = member b, the single-LP kernel's arithmetic on the member's own arguments).  Check step, evaluation and restart
+// run in the group forms of the regular kernels (kernels.h: GroupLaunches -- one launch per kernel for all members, a workgroup
+// running the single kernel's body as workgroup lb of lg of its member), and one copy and one host wait serve the scalars of all
+// members.  The host side -- stopping test, restart rule, sigma update, detection -- is the member's own code (the pieces of
+// Solver::solve_loop), so a member's iterates and results are the bits it gets alone.  A member that cannot join the group launches
+// (Solver::joins_group) issues its own launches inside the same lock-step; so does every member for its iteration-0 evaluation and
+// its ray tests.
 //
 // Ordering is by stream: for the duration of a call every member works on ONE stream (the first member's), after its own stream
 // has been waited for once; the members' streams come back at exit, after one wait for the group's.
@@ -45,6 +49,22 @@ struct GroupScope {
 };
 
 bool on_small_path(const Solver *s) { return s->use_small && !s->comm; }
+
+std::vector<char> who_joins(Solver **s, int count) {
+    std::vector<char> j(static_cast<size_t>(count));
+    for (int k = 0; k < count; ++k) j[k] = s[k]->joins_group() ? 1 : 0;
+    return j;
+}
+
+// what has been recorded and enqueued, then the one copy of the scalars, the wait and each member's scalars into its host block
+void run_fetch_wait(GroupLaunches &gl, hipStream_t group, GroupCounts &gc) {
+    const int copies = gl.fetch(group);
+    gc.group_launches += copies;  // (the packing kernel)
+    gc.copies += copies;
+    HIP_CHECK(hipStreamSynchronize(group));
+    ++gc.waits;
+    gl.deliver();
+}
 
 }  // namespace
 
@@ -124,9 +144,69 @@ void iterate_many(Solver **s, int count, const int *normal, bool then_check) {
     launch_small_iterations_many(tasks.data(), static_cast<int>(tasks.size()), buf, scope.group);
     for (int k = 0; k < count; ++k)
         if (!on_small_path(s[k])) s[k]->run_normal(normal[k]);
-    if (then_check)
-        for (int k = 0; k < count; ++k) s[k]->step(true);
+    if (then_check) {
+        const std::vector<char> joins = who_joins(s, count);
+        GroupLaunches gl;
+        for (int k = 0; k < count; ++k) s[k]->step(true, joins[k] ? &gl : nullptr);
+        gl.run(scope.group);
+    }
     HIP_CHECK(hipStreamSynchronize(scope.group));
+}
+
+void residuals_many(Solver **s, int count, const int *iter, const int *compute_gap, double *out) {
+    check_group(s, count, "residuals_many");
+    if (!iter || !compute_gap || !out) throw std::runtime_error("residuals_many: null iter, compute_gap or out");
+    for (int k = 0; k < count; ++k)
+        if (iter[k] < 0) throw std::runtime_error("residuals_many: iter[" + std::to_string(k) + "] is negative");
+    GroupScope scope(s, count);
+    const std::vector<char> joins = who_joins(s, count);
+    GroupLaunches gl;
+    GroupCounts gc;
+    for (int k = 0; k < count; ++k) {
+        s[k]->residuals_launch(iter[k], compute_gap[k] != 0, joins[k] && iter[k] > 0 ? &gl : nullptr);
+        gl.pack(s[k]->scal.p, s[k]->scal_h.p);
+    }
+    gl.run(scope.group);
+    run_fetch_wait(gl, scope.group, gc);
+    for (int k = 0; k < count; ++k) {
+        Residuals r;
+        RestartState rs;
+        ++s[k]->fetches;
+        s[k]->residuals_consume(iter[k], compute_gap[k] != 0, &r, &rs);
+        double *o = out + 8 * static_cast<size_t>(k);
+        o[0] = r.err_Rp; o[1] = r.err_Rd; o[2] = r.primal_obj; o[3] = r.dual_obj;
+        o[4] = r.rel_gap; o[5] = r.kkt; o[6] = rs.current_gap; o[7] = s[k]->lambda_max;
+    }
+}
+
+void restart_many(Solver **s, int count, const double *in, double *sigma_out) {
+    check_group(s, count, "restart_many");
+    if (!in) throw std::runtime_error("restart_many: null input");
+    GroupScope scope(s, count);
+    const std::vector<char> joins = who_joins(s, count);
+    GroupLaunches gl;
+    GroupCounts gc;
+    for (int k = 0; k < count; ++k) {
+        s[k]->movement_launch(joins[k] ? &gl : nullptr);
+        gl.pack(s[k]->scal.p, s[k]->scal_h.p);
+    }
+    gl.run(scope.group);
+    run_fetch_wait(gl, scope.group, gc);
+    for (int k = 0; k < count; ++k) {
+        const double *v = in + 6 * static_cast<size_t>(k);
+        RestartState rs;  // (as hprlp_solver_restart)
+        rs.flag = 1;
+        rs.first = false;
+        rs.current_gap = v[0]; rs.best_gap = v[1]; rs.best_sigma = v[2];
+        Residuals r;
+        r.err_Rd = v[3]; r.err_Rp = v[4]; r.rel_gap = v[5];
+        ++s[k]->fetches;
+        s[k]->restart_launch(&rs, r, joins[k] ? &gl : nullptr);
+    }
+    gl.run(scope.group);
+    HIP_CHECK(hipStreamSynchronize(scope.group));
+    if (sigma_out)
+        for (int k = 0; k < count; ++k) sigma_out[k] = s[k]->sigma;
 }
 
 void run_many(Solver **s, int count, HPRLP_results *out, GroupCounts *counts) {
@@ -135,39 +215,89 @@ void run_many(Solver **s, int count, HPRLP_results *out, GroupCounts *counts) {
     GroupCounts gc;
     {
         GroupScope scope(s, count);
+        const std::vector<char> joins = who_joins(s, count);
         std::vector<LoopState> ls(static_cast<size_t>(count));
         std::vector<char> active(static_cast<size_t>(count), 1);
         for (int k = 0; k < count; ++k) s[k]->loop_begin(&ls[k], &out[k]);
         SmallTaskBuf buf;
         std::vector<SmallIterTask> tasks;
+        std::vector<int> flagged;
+        GroupLaunches gl;  // (between two rounds it holds the check steps recorded in step 11: they run with the next evaluation, a stage ahead)
         int left = count;
         while (left > 0) {
-            // 1-3: every active member's evaluation enqueued, one wait, then member by member what follows the wait
-            for (int k = 0; k < count; ++k)
-                if (active[k]) s[k]->loop_enqueue_evaluation(&ls[k]);
-            HIP_CHECK(hipStreamSynchronize(scope.group));
+            // 1-3: the evaluation of every active member, one copy of the scalars, one wait.  Iteration 0 (launch_lu, a start's
+            // evaluation) is a member's own, and so is everything of a member outside the group launches.
+            for (int k = 0; k < count; ++k) {
+                if (!active[k]) continue;
+                if (joins[k] && ls[k].iter > 0) {
+                    s[k]->loop_enqueue_evaluation(&ls[k], &gl);
+                    ++gc.served;
+                }
+                gl.pack(s[k]->scal.p, s[k]->scal_h.p);
+            }
+            gc.group_launches += gl.run(scope.group);
+            for (int k = 0; k < count; ++k) {
+                if (!active[k]) continue;
+                if (joins[k] && ls[k].iter > 0) {
+                    if (s[k]->loop_enqueue_ray(&ls[k])) ++gc.own;  // (between the group's kernels and the group's copy)
+                } else {
+                    s[k]->loop_enqueue_evaluation(&ls[k], nullptr, false);
+                    ++gc.own;
+                }
+            }
+            run_fetch_wait(gl, scope.group, gc);
             ++gc.rounds;
-            ++gc.waits;
-            tasks.clear();
+            // 4: every member's status and restart flag; finished members drop out
+            flagged.clear();
             for (int k = 0; k < count; ++k) {
                 if (!active[k]) continue;
                 ++s[k]->fetches;
-                // 4-5: the member's own decision; a restart runs its movement, copy, check step and weighted norm here (two
-                // waits of its own: the exception to "one wait per round")
-                if (!s[k]->loop_decide(&ls[k])) {
+                if (!s[k]->loop_status(&ls[k])) {
                     s[k]->loop_finish(&ls[k]);
                     active[k] = 0;
                     --left;
                     continue;
                 }
-                if (ls[k].restarted) gc.waits += 2;
+                if (ls[k].restarted) flagged.push_back(k);
+            }
+            if (!flagged.empty()) {
+                // 5-6: movement of the flagged members
+                for (int k : flagged) {
+                    s[k]->loop_movement(&ls[k], joins[k] ? &gl : nullptr);
+                    if (!joins[k]) ++gc.own;
+                    gl.pack(s[k]->scal.p, s[k]->scal_h.p);
+                }
+                gc.group_launches += gl.run(scope.group);
+                run_fetch_wait(gl, scope.group, gc);
+                // 7-9: each one's sigma rule on the host; restart copy, ctrl, check step and gap
+                for (int k : flagged) {
+                    ++s[k]->fetches;
+                    s[k]->loop_restart(&ls[k], joins[k] ? &gl : nullptr);
+                    if (!joins[k]) ++gc.own;
+                    gl.pack(s[k]->scal.p, s[k]->scal_h.p);
+                }
+                gc.group_launches += gl.run(scope.group);
+                run_fetch_wait(gl, scope.group, gc);
+                for (int k : flagged) ++s[k]->fetches;
+            }
+            // 10: the normal iterations of all small-path members, one launch per class
+            tasks.clear();
+            for (int k = 0; k < count; ++k) {
+                if (!active[k]) continue;
+                s[k]->loop_plan(&ls[k]);  // (a restart's weighted norm consumed: the rare lambda bump inside is the member's own launch)
                 if (on_small_path(s[k]) && ls[k].pending > 0) tasks.push_back(SmallIterTask{s[k]->small_args(), 0, ls[k].pending});
             }
-            // 6: the normal iterations of all small-path members, one launch per class
-            gc.launches += launch_small_iterations_many(tasks.data(), static_cast<int>(tasks.size()), buf, scope.group);
-            // 7: every member's own check step (members off the small path run their normal iterations first)
-            for (int k = 0; k < count; ++k)
-                if (active[k]) s[k]->loop_advance(&ls[k], on_small_path(s[k]));
+            const int it_launches = launch_small_iterations_many(tasks.data(), static_cast<int>(tasks.size()), buf, scope.group);
+            gc.launches += it_launches;
+            gc.group_launches += it_launches;
+            // 11: the check step: recorded for the members of the group launches (it runs in front of the next round's evaluation,
+            // same stream); members off the small path run their normal iterations first
+            for (int k = 0; k < count; ++k) {
+                if (!active[k]) continue;
+                s[k]->loop_advance(&ls[k], on_small_path(s[k]), joins[k] ? &gl : nullptr);
+                if (!joins[k] && ls[k].pending >= 0) ++gc.own;
+            }
+            gl.next_stage();  // (the evaluation's Rd overwrites the partials the check step's finalize reads)
         }
         for (int k = 0; k < count; ++k) s[k]->collect_solution(&out[k]);
     }

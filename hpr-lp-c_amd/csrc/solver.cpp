@@ -1500,10 +1500,17 @@ double Solver::power_iteration(int max_iter, double tol, int *iters) {
 }
 
 // ------------------------------------------------------------------------------------------------
-void Solver::set_sigma_lambda(double sigma_, double lambda_, bool reset_k) {
+void Solver::set_sigma_lambda(double sigma_, double lambda_, bool reset_k, GroupLaunches *g) {
     sigma = sigma_;
     lambda_max = lambda_;
-    launch_set_ctrl(ctrl.p, sigma, lambda_max, reset_k ? 1 : 0, stream);
+    if (g) g->set_ctrl(ctrl.p, sigma, lambda_max, reset_k ? 1 : 0);
+    else launch_set_ctrl(ctrl.p, sigma, lambda_max, reset_k ? 1 : 0, stream);
+}
+
+bool Solver::joins_group() {
+    if (!use_small || comm) return false;
+    finish_tiling();
+    return group_form_fits(A.view) && group_form_fits(AT.view);
 }
 
 // hooks that the iteration path consults: read when the solver is set up (a later change of the environment does not reach it)
@@ -1666,7 +1673,7 @@ void Solver::launch_normal_pair(bool more_follow, hipEvent_t *ev, int x_mode) {
     else HIP_CHECK(hipStreamWaitEvent(stream, ev_done_y, 0));
 }
 
-void Solver::step(bool check) {
+void Solver::step(bool check, GroupLaunches *g) {
     finish_tiling();
     if (!check) {
         launch_normal_pair();
@@ -1676,13 +1683,15 @@ void Solver::step(bool check) {
     xa.lu_code = lu_code.p;
     xa.push = push_into(A, AT);
     xa.far_ready = far_AT_ready;
-    far_A_ready = launch_x_half(AT.view, xa, true, stream);
+    if (g) g->x_half_check(AT.view, xa);  // (a member of the group launches has neither tiled copies nor an exchange)
+    else far_A_ready = launch_x_half(AT.view, xa, true, stream);
     gather(gxh.p, false);
     YHalfArgs ya{gxh.p, y, AL.p, AU.p, last_y.p, y_bar, y_obj.p, y_temp.p, ctrl.p, part_y.p, stride_y};
     ya.row_code = row_code.p;
     ya.push = push_into(AT, A);
     ya.far_ready = far_A_ready;
-    far_AT_ready = launch_y_half(A.view, ya, true, stream);
+    if (g) g->y_half_check(A.view, ya);
+    else far_AT_ready = launch_y_half(A.view, ya, true, stream);
     gather(gy.p, true);
     FinalizeArgs f{};
     const int gx = AT.view.grid(), gyy = A.view.grid();
@@ -1692,7 +1701,8 @@ void Solver::step(bool check) {
     f.item[2] = {part_x.p + 2 * static_cast<size_t>(stride_x), gx, S_DX2};
     f.item[3] = {part_y.p, gyy, S_YOBJ_Y};
     f.item[4] = {part_y.p + stride_y, gyy, S_DY2};
-    launch_finalize(f, scal.p, stream);
+    if (g) g->finalize(f, scal.p);
+    else launch_finalize(f, scal.p, stream);
 }
 
 hipGraphExec_t Solver::graph_for(int len) {
@@ -1770,6 +1780,12 @@ void Solver::compute_residuals(int iter, bool compute_gap, Residuals *r, Restart
 }
 
 void Solver::residuals_enqueue(int iter, bool compute_gap, bool *ray) {
+    residuals_launch(iter, compute_gap, nullptr);
+    if (ray) *ray = ray_test();  // (its scalars ride on the fetch below)
+    fetch_enqueue();
+}
+
+void Solver::residuals_launch(int iter, bool compute_gap, GroupLaunches *g) {
     invalidate_far();  // the residual SpMVs refill the remainder buffers for x_bar / y_bar
     finish_tiling();
     const int gx = AT.view.grid(), gyy = A.view.grid();
@@ -1778,20 +1794,22 @@ void Solver::residuals_enqueue(int iter, bool compute_gap, bool *ray) {
     gather(gxb.p, false);
     if (compute_gap) gather(gxt.p, false);
     FinalizeArgs f{};
-    launch_resid_d(AT.view, gyb.p, c.p, z_bar.p, col_norm.p, part_x.p, stream);
+    if (g) g->resid_d(AT.view, gyb.p, c.p, z_bar.p, col_norm.p, part_x.p);
+    else launch_resid_d(AT.view, gyb.p, c.p, z_bar.p, col_norm.p, part_x.p, stream);
     f.item[f.n++] = {part_x.p, gx, S_RD2};
-    launch_resid_p(A.view, gxb.p, gxt.p, AL.p, AU.p, row_norm.p, y_temp.p, compute_gap, part_r.p, rstride, stream);
+    if (g) g->resid_p(A.view, gxb.p, gxt.p, AL.p, AU.p, row_norm.p, y_temp.p, compute_gap, part_r.p, rstride);
+    else launch_resid_p(A.view, gxb.p, gxt.p, AL.p, AU.p, row_norm.p, y_temp.p, compute_gap, part_r.p, rstride, stream);
     f.item[f.n++] = {part_r.p, gyy, S_RP2};
     if (compute_gap) f.item[f.n++] = {part_r.p + rstride, gyy, S_ADX_DY};
     if (iter == 0) {
+        if (g) throw std::runtime_error("the evaluation of iteration 0 is a member's own");
         launch_lu(n_loc, x_bar, l.p, u.p, col_norm.p, x_temp, part_v.p, kReduceBlocks, stream);
         f.item[f.n++] = {part_v.p, kReduceBlocks, S_LU2};
     }
-    launch_finalize(f, scal.p, stream);
+    if (g) g->finalize(f, scal.p);
+    else launch_finalize(f, scal.p, stream);
     allreduce_slots(this, S_CX, 8);
     if (iter == 0) allreduce_slots(this, S_LU2, 1);
-    if (ray) *ray = ray_test();  // (its scalars ride on the fetch below)
-    fetch_enqueue();
 }
 
 void Solver::residuals_consume(int iter, bool compute_gap, Residuals *r, RestartState *rs) {
@@ -1802,36 +1820,54 @@ void Solver::residuals_consume(int iter, bool compute_gap, Residuals *r, Restart
 }
 
 double Solver::weighted_norm_after_restart() {
+    gap_launch(nullptr);
+    fetch_scalars();
+    return weighted_norm_consume();
+}
+
+void Solver::gap_launch(GroupLaunches *g) {
     invalidate_far();
     gather(gxt.p, false);
-    launch_gap(A.view, gxt.p, y_temp.p, part_r.p, stream);
+    if (g) g->gap(A.view, gxt.p, y_temp.p, part_r.p);
+    else launch_gap(A.view, gxt.p, y_temp.p, part_r.p, stream);
     FinalizeArgs f{};
     f.n = 1;
     f.item[0] = {part_r.p, A.view.grid(), S_ADX_DY};
-    launch_finalize(f, scal.p, stream);
+    if (g) g->finalize(f, scal.p);
+    else launch_finalize(f, scal.p, stream);
     allreduce_slots(this, S_ADX_DY, 3);  // S_ADX_DY, S_DY2, S_DX2 are adjacent
-    fetch_scalars();
-    return weighted_norm_from(this, scal_h[S_ADX_DY], scal_h[S_DY2], scal_h[S_DX2]);
 }
+
+double Solver::weighted_norm_consume() { return weighted_norm_from(this, scal_h[S_ADX_DY], scal_h[S_DY2], scal_h[S_DX2]); }
 
 void Solver::update_sigma_and_restart(RestartState *rs, const Residuals &r) {
     if (rs->flag <= 0) return;
+    movement_launch(nullptr);
+    fetch_scalars();
+    restart_launch(rs, r, nullptr);
+}
+
+void Solver::movement_launch(GroupLaunches *g) {
     // movement x_bar - last_x, y_bar - last_y and their norms (update_sigma, main_iterate.cu:367-404)
-    launch_movement(n_loc, m_loc, x_bar, last_x.p, x_temp, y_bar, last_y.p, y_temp.p, part_v.p, kReduceBlocks,
-                    kReduceBlocks, stream);
+    if (g) g->movement(n_loc, m_loc, x_bar, last_x.p, x_temp, y_bar, last_y.p, y_temp.p, part_v.p, kReduceBlocks);
+    else launch_movement(n_loc, m_loc, x_bar, last_x.p, x_temp, y_bar, last_y.p, y_temp.p, part_v.p, kReduceBlocks, kReduceBlocks, stream);
     FinalizeArgs f{};
     f.n = 2;
     f.item[0] = {part_v.p, kReduceBlocks, S_MOVE_X2};
     f.item[1] = {part_v.p + kReduceBlocks, kReduceBlocks, S_MOVE_Y2};
-    launch_finalize(f, scal.p, stream);
+    if (g) g->finalize(f, scal.p);
+    else launch_finalize(f, scal.p, stream);
     allreduce_slots(this, S_MOVE_X2, 2);
-    fetch_scalars();
+}
+
+void Solver::restart_launch(RestartState *rs, const Residuals &r, GroupLaunches *g) {
     const double new_sigma = restart_sigma(std::sqrt(scal_h[S_MOVE_X2]), std::sqrt(scal_h[S_MOVE_Y2]), lambda_max, *rs, r);
     // do_restart (main_iterate.cu:312-322) + Halpern reset (:54-66)
     invalidate_far();  // y changes under the remainder buffer of A^T
-    launch_restart_copy(n_loc, m_loc, x_bar, x.p, last_x.p, y_bar, y, last_y.p, ctrl.p, stream);
+    if (g) g->restart_copy(n_loc, m_loc, x_bar, x.p, last_x.p, y_bar, y, last_y.p, ctrl.p);
+    else launch_restart_copy(n_loc, m_loc, x_bar, x.p, last_x.p, y_bar, y, last_y.p, ctrl.p, stream);
     gather(gy.p, true);
-    set_sigma_lambda(new_sigma, lambda_max, true);
+    set_sigma_lambda(new_sigma, lambda_max, true, g);
     rs->inner = 0;
     rs->save_gap = std::numeric_limits<double>::infinity();
 }
@@ -1865,15 +1901,24 @@ void Solver::loop_begin(LoopState *ls, HPRLP_results *out) {
     if (detect.on) ray_begin();
 }
 
-void Solver::loop_enqueue_evaluation(LoopState *ls) {
+void Solver::loop_enqueue_evaluation(LoopState *ls, GroupLaunches *g, bool fetch) {
     ls->at_limit = ls->iter >= ls->max_iter;
     ls->periodic = (ls->iter % ls->check_iter == 0);
     ls->ray = false;
-    residuals_enqueue(ls->iter, ls->periodic && ls->iter > 0, detect.on && ls->periodic && ls->iter > 0 ? &ls->ray : nullptr);
+    residuals_launch(ls->iter, ls->periodic && ls->iter > 0, g);
+    if (g) return;  // (the ray test follows the group's kernels: loop_enqueue_ray)
+    loop_enqueue_ray(ls);
+    if (fetch) fetch_enqueue();
 }
 
-bool Solver::loop_decide(LoopState *ls) {
-    const int iter = ls->iter, check_iter = ls->check_iter, max_iter = ls->max_iter;
+bool Solver::loop_enqueue_ray(LoopState *ls) {
+    if (!(detect.on && ls->periodic && ls->iter > 0)) return false;
+    ls->ray = ray_test();  // (its scalars ride on the copy that follows)
+    return true;
+}
+
+bool Solver::loop_status(LoopState *ls) {
+    const int iter = ls->iter, check_iter = ls->check_iter;
     const bool at_limit = ls->at_limit, periodic = ls->periodic;
     Residuals &r = ls->r;
     RestartState &rs = ls->rs;
@@ -1925,32 +1970,49 @@ bool Solver::loop_decide(LoopState *ls) {
         if (verdict && status != "OPTIMAL") collect_certificate(verdict, iter);
         return false;
     }
+    ls->restarted = rs.flag > 0;
+    return true;
+}
 
-    const int flag = rs.flag;
-    update_sigma_and_restart(&rs, r);
-    const int next = next_event(iter, check_iter, max_iter);
+void Solver::loop_movement(LoopState *, GroupLaunches *g) { movement_launch(g); }
+
+void Solver::loop_restart(LoopState *ls, GroupLaunches *g) {
+    restart_launch(&ls->rs, ls->r, g);
+    step(true, g);
+    gap_launch(g);
+}
+
+void Solver::loop_plan(LoopState *ls) {
+    const int iter = ls->iter;
+    RestartState &rs = ls->rs;
+    const int next = next_event(iter, ls->check_iter, ls->max_iter);
     int it = iter;
-    ls->restarted = flag > 0;
-    if (flag > 0) {
-        step(true);
-        rs.last_gap = weighted_norm_after_restart();
+    if (ls->restarted) {
+        rs.last_gap = weighted_norm_consume();
         ++it;
     }
     ls->pending = it < next ? next - 1 - it : -1;
     rs.inner += next - iter;
     ls->iter = next;
-    return true;
 }
 
 bool Solver::loop_event(LoopState *ls) {
     loop_enqueue_evaluation(ls);
     fetch_wait();
-    return loop_decide(ls);
+    if (!loop_status(ls)) return false;
+    if (ls->restarted) {
+        loop_movement(ls);
+        fetch_scalars();
+        loop_restart(ls);
+        fetch_scalars();
+    }
+    loop_plan(ls);
+    return true;
 }
 
-void Solver::loop_advance(LoopState *ls, bool normal_done) {
+void Solver::loop_advance(LoopState *ls, bool normal_done, GroupLaunches *g) {
     if (ls->pending < 0) return;
-    if (normal_done) step(true);
+    if (normal_done) step(true, g);
     else run_normal_then_check(ls->pending);
 }
 

@@ -240,9 +240,10 @@ struct Solver {
     void scale();                                                   // src/scaling.cu:88-216
     double power_iteration(int max_iter, double tol, int *iters);   // src/power_iteration.cu:20-119
     void init_iteration_state();                                    // src/HPRLP.cu:154-167
-    void set_sigma_lambda(double sigma_, double lambda_, bool reset_k);
+    // (g, here and below: record the launch for a group run instead of issuing it -- kernels.h: GroupLaunches, many.cpp)
+    void set_sigma_lambda(double sigma_, double lambda_, bool reset_k, GroupLaunches *g = nullptr);
     void reset_iterates();                                          // all iterates back to zero (as after create + scale + power iteration)
-    void step(bool check);                                          // one HPR iteration
+    void step(bool check, GroupLaunches *g = nullptr);              // one HPR iteration
     void run_normal(int count);                                     // count normal iterations (graph replay)
     void run_normal_then_check(int count);                          // count normal iterations, then one check-variant iteration
     void fetch_scalars();                                           // fetch_enqueue + fetch_wait
@@ -252,19 +253,38 @@ struct Solver {
     void compute_residuals(int iter, bool compute_gap, Residuals *r, RestartState *rs, bool *ray = nullptr);
     // its two halves: everything up to and including the asynchronous copy of the scalars / what follows the wait for the stream
     void residuals_enqueue(int iter, bool compute_gap, bool *ray);
+    void residuals_launch(int iter, bool compute_gap, GroupLaunches *g);  // its kernels and finalize: no ray test, no copy (g: iter > 0 only)
     void residuals_consume(int iter, bool compute_gap, Residuals *r, RestartState *rs);
-    double weighted_norm_after_restart();                           // main_iterate.cu:486-515
-    void update_sigma_and_restart(RestartState *rs, const Residuals &r);  // main_iterate.cu:312-322,367-404
+    double weighted_norm_after_restart();                           // main_iterate.cu:486-515: gap_launch, fetch, weighted_norm_consume
+    void gap_launch(GroupLaunches *g);
+    double weighted_norm_consume();                                 // (the rare lambda bump inside is always the solver's own launch)
+    // main_iterate.cu:312-322,367-404: movement_launch, fetch, restart_launch
+    void update_sigma_and_restart(RestartState *rs, const Residuals &r);
+    void movement_launch(GroupLaunches *g);                         // the movement and its two norms, not fetched
+    void restart_launch(RestartState *rs, const Residuals &r, GroupLaunches *g);  // movement fetched: the sigma rule, restart copy, ctrl
+    // Check step, evaluation and restart run in the group launches (many.cpp): small path, and both matrices run the stream kernel
+    // alone (no tiled copy, no split rows).  Adopts a pending tiled copy first.
+    bool joins_group();
     void solve_loop(HPRLP_results *out);                            // src/HPRLP.cu:154-310
     // the pieces of solve_loop (LoopState)
     void loop_begin(LoopState *ls, HPRLP_results *out);
-    void loop_enqueue_evaluation(LoopState *ls);  // first half of an event: the evaluation of the current iterate, not waited for
-    // second half, after the wait: status, marks, restart decision, sigma update, a restart's own check step and weighted norm.
-    // false: finished (ls->status says how); true: ls->restarted and ls->pending say what runs next
-    bool loop_decide(LoopState *ls);
-    bool loop_event(LoopState *ls);               // loop_enqueue_evaluation, wait, loop_decide
+    // first half of an event: the evaluation of the current iterate, not waited for.  g: kernels and finalize recorded, nothing
+    // else; fetch = false: without the copy of the scalars (a group's copy carries them)
+    void loop_enqueue_evaluation(LoopState *ls, GroupLaunches *g = nullptr, bool fetch = true);
+    bool loop_enqueue_ray(LoopState *ls);         // the ray test of that evaluation where detection asks for one (true: enqueued)
+    // second half, after the wait, in pieces that end where the host has to wait for scalars:
+    //   loop_status    status, marks, restart decision.  false: finished (ls->status says how); true: ls->restarted says whether the
+    //                  two pieces below run
+    //   loop_movement  the movement and its norms enqueued                                  [wait]
+    //   loop_restart   the sigma rule, restart copy, ctrl, check step, gap enqueued         [wait]
+    //   loop_plan      a restart's weighted norm consumed; ls->pending and ls->iter say what runs next
+    bool loop_status(LoopState *ls);
+    void loop_movement(LoopState *ls, GroupLaunches *g = nullptr);
+    void loop_restart(LoopState *ls, GroupLaunches *g = nullptr);
+    void loop_plan(LoopState *ls);
+    bool loop_event(LoopState *ls);               // loop_enqueue_evaluation, wait, the four pieces with their waits
     // what run_normal_then_check does for ls->pending; normal_done: the normal iterations have been run by a group launch
-    void loop_advance(LoopState *ls, bool normal_done = false);
+    void loop_advance(LoopState *ls, bool normal_done = false, GroupLaunches *g = nullptr);
     void loop_finish(LoopState *ls);              // the results' scalars
     SmallArgs small_args() const;                 // the single-workgroup kernels' view of this LP (use_small)
     bool small_power_wanted() const;              // the power iteration runs in the single-workgroup kernel

@@ -217,6 +217,10 @@ def lib():
     L.hprlp_solver_run_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(CResults)]
     L.hprlp_solve_many.argtypes = [C.POINTER(C.POINTER(CLPInfo)), C.c_int, C.POINTER(CParameters), C.POINTER(CResults)]
     L.hprlp_last_solve_many_phases.argtypes = [c_dbl_p]
+    if hasattr(L, "hprlp_last_run_many_counts"):  # (HPRLP_LIB may name a build of an earlier commit: the A side of tools/many_ab.py)
+        L.hprlp_solver_residuals_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, c_int_p, c_int_p, c_dbl_p]
+        L.hprlp_solver_restart_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, c_dbl_p, c_dbl_p]
+        L.hprlp_last_run_many_counts.argtypes = [C.POINTER(C.c_long)]
     _lib = L
     return L
 
@@ -539,6 +543,14 @@ def last_solve_many_phases():
     lib().hprlp_last_solve_many_phases(out.ctypes.data_as(c_dbl_p))
     keys = ("setup", "scaling", "power", "loop", "call", "rounds", "waits", "launches")
     return dict(zip(keys, [float(v) for v in out]))
+
+
+def last_run_many_counts():
+    """Counts of this thread's last Solver.run_many / solve_many (hprlp_last_run_many_counts)."""
+    out = (C.c_long * 8)()
+    lib().hprlp_last_run_many_counts(out)
+    keys = ("rounds", "waits", "group_launches", "copies", "own", "served")
+    return dict(zip(keys, [int(v) for v in out]))
 
 
 def solve_batched(model, Cmat, AL, AU, l, u, obj_constants=None, param=None):
@@ -1175,6 +1187,34 @@ class Solver:
             raise ValueError("iterate_many: one iteration count per solver")
         if lib().hprlp_solver_iterate_many(hs, len(solvers), cnt.ctypes.data_as(c_int_p), int(bool(then_check))) < 0:
             raise RuntimeError(last_error())
+
+    @staticmethod
+    def residuals_many(solvers, iters, compute_gap):
+        """residuals(iters[k], compute_gap[k]) of every solver, one launch per kernel for the members of the group launches
+        (hprlp_solver_residuals_many).  Returns a list of dicts."""
+        solvers, hs = Solver._handles(solvers)
+        it, cg = _as(iters, np.int32), _as([int(bool(v)) for v in compute_gap], np.int32)
+        if it.ndim != 1 or it.shape[0] != len(solvers) or cg.shape[0] != len(solvers):
+            raise ValueError("residuals_many: one iteration and one flag per solver")
+        out = np.zeros(8 * max(len(solvers), 1))
+        if lib().hprlp_solver_residuals_many(hs, len(solvers), it.ctypes.data_as(c_int_p), cg.ctypes.data_as(c_int_p),
+                                             out.ctypes.data_as(c_dbl_p)) < 0:
+            raise RuntimeError(last_error())
+        keys = ("err_Rp", "err_Rd", "primal_obj", "dual_obj", "gap", "kkt", "weighted_norm", "lambda_max")
+        return [dict(zip(keys, out[8 * k:8 * k + 8])) for k in range(len(solvers))]
+
+    @staticmethod
+    def restart_many(solvers, inputs):
+        """restart(*inputs[k]) of every solver (hprlp_solver_restart_many); inputs[k] = (current_gap, best_gap, best_sigma,
+        err_Rd, err_Rp, rel_gap).  Returns the new sigmas."""
+        solvers, hs = Solver._handles(solvers)
+        a = np.ascontiguousarray(np.asarray(inputs, dtype=np.float64).reshape(-1))
+        if a.shape[0] != 6 * len(solvers):
+            raise ValueError("restart_many: six inputs per solver")
+        sig = np.zeros(max(len(solvers), 1))
+        if lib().hprlp_solver_restart_many(hs, len(solvers), a.ctypes.data_as(c_dbl_p), sig.ctypes.data_as(c_dbl_p)) < 0:
+            raise RuntimeError(last_error())
+        return [float(v) for v in sig[:len(solvers)]]
 
     @staticmethod
     def run_many(solvers):

@@ -280,16 +280,24 @@ int hprlp_batched_solver_set_matrix_values(hprlp_batched_solver *h, const double
  * A Netlib-scale LP (nnz < 12288, m, n <= 2048, rows and columns of at most 256 entries) runs as ONE workgroup and occupies one
  * compute unit of 256.  These entry points advance a group of independent solvers -- each with its own matrix -- in lock-step:
  * the normal iterations and the power iterations of all small-path members go in one launch per kernel class (workgroup b =
- * member b), and one host wait serves the evaluations of all members.  Check step, evaluation, stopping test, restart rule, sigma
- * update and detection stay the member's own, so every member gets the bits it gets alone.  Members off the small path are legal
- * (they run their own kernels inside the same lock-step).  The group runs quietly (hprlp_solver_set_verbose is ignored).
- * All four return 0, or -1 + hprlp_last_error(); nothing is launched when the arguments are wrong: a NULL pointer, count <= 0,
+ * member b).  Check step, evaluation and restart go in one launch per kernel for the whole group (a workgroup runs the single
+ * kernel's code as workgroup lb of lg of its member), and one copy and one host wait serve the scalars of all members: a round of
+ * hprlp_solver_run_many has one wait, three if some member restarts in it, and a number of launches that does not depend on the
+ * count.  The stopping test, restart rule, sigma update and detection stay the member's own host code, so every member gets the
+ * bits it gets alone.  Members off the small path are legal (they issue their own launches inside the same lock-step), and a
+ * member's iteration-0 evaluation and ray tests are always its own.  The group runs quietly (hprlp_solver_set_verbose is ignored).
+ * All of them return 0, or -1 + hprlp_last_error(); nothing is launched when the arguments are wrong: a NULL pointer, count <= 0,
  * the same handle twice, a sharded solver (hprlp_solver_create_dist* / _local*), a solver that was never scaled, members on
- * different devices, a negative normal[k]. */
+ * different devices, a negative normal[k] or iter[k]. */
 /* hprlp_solver_power_iteration for every member: lambda_out[k] (lambda, not lambda x 1.01), iters_out[k] (may be NULL) */
 int hprlp_solver_power_iteration_many(hprlp_solver **s, int count, int max_iter, double tol, double *lambda_out, int *iters_out);
 /* hprlp_solver_iterate for every member: normal[k] normal iterations of member k, then one check step each if then_check */
 int hprlp_solver_iterate_many(hprlp_solver **s, int count, const int *normal, int then_check);
+/* hprlp_solver_residuals for every member: iter[k], compute_gap[k] as its arguments, out[8 * k .. 8 * k + 8) as its out.  A member
+ * with iter[k] = 0 (the bound violation of iteration 0) is evaluated by its own launches. */
+int hprlp_solver_residuals_many(hprlp_solver **s, int count, const int *iter, const int *compute_gap, double *out /* 8 x count */);
+/* hprlp_solver_restart for every member: in[6 * k .. 6 * k + 6) as its in, sigma_out[k] (may be NULL) the member's new sigma */
+int hprlp_solver_restart_many(hprlp_solver **s, int count, const double *in /* 6 x count */, double *sigma_out /* count */);
 /* hprlp_solver_run for every member, from its current state (detection, a start, changed data are honoured): out[k] as
  * hprlp_solver_run fills it (x, y, z malloc'd), no trace; certificates from hprlp_solver_get_certificate member by member.  A
  * finished member drops out, the call returns with the last one.  out[k].time = the member's power-iteration (or set_data) time
@@ -300,8 +308,14 @@ int hprlp_solver_run_many(hprlp_solver **s, int count, HPRLP_results *out);
  * solve_batched.  A model that fails its set-up gets status "ERROR" (and hprlp_last_error() names it); the others are solved. */
 int hprlp_solve_many(const LP_info_cpu *const *models, int count, const HPRLP_parameters *param, HPRLP_results *out);
 /* Wall-clock phases [s] of the calling thread's last hprlp_solve_many: out = {set-up (sum over the members), scaling (sum), power
- * iterations + init, loop + solutions' way back, whole call (teardown included), evaluation rounds, host waits, group launches} */
+ * iterations + init, loop + solutions' way back, whole call (teardown included), evaluation rounds, host waits, group launches of
+ * the normal iterations (every kind: hprlp_last_run_many_counts)} */
 int hprlp_last_solve_many_phases(double out[8]);
+/* Counts of the calling thread's last hprlp_solver_run_many / hprlp_solve_many: out = {evaluation rounds, host waits, group
+ * launches of every kind (normal iterations, check, evaluation, restart, packing of the scalars), copies of the scalars to the host,
+ * operations issued for ONE member (an own evaluation, ray test, check step or restart piece), member-evaluations served by group
+ * launches, 0, 0} */
+int hprlp_last_run_many_counts(long out[8]);
 
 /* Named device vectors: x y x_hat x_bar y_bar z_bar x_temp y_temp y_obj last_x last_y AL AU l u c
  * row_norm col_norm A_val AT_val.  get returns the length (or -1); cap is the capacity of out. */
