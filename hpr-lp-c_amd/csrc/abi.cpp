@@ -1212,7 +1212,7 @@ extern "C" int hprlp_solver_run(hprlp_solver *h, HPRLP_results *out, hprlp_trace
 // many small LPs at once (many.cpp; DESIGN.md "Many small LPs")
 // ------------------------------------------------------------------------------------------------
 // the members of a group call, checked before anything is launched (`who`, for the error messages)
-static std::vector<Solver *> group_members(hprlp_solver **h, int count, const char *who) {
+static std::vector<Solver *> group_members(hprlp_solver **h, int count, const char *who, bool need_scaled = true) {
     const std::string w(who);
     if (!h) throw std::runtime_error(w + ": null solver list");
     if (count <= 0) throw std::runtime_error(w + ": count must be positive");
@@ -1223,8 +1223,123 @@ static std::vector<Solver *> group_members(hprlp_solver **h, int count, const ch
             throw std::runtime_error(w + ": member " + std::to_string(k) + " is a sharded solver (hprlp_solver_create_dist* / _local*); a group runs on one GPU");
         s[k] = &h[k]->s;
     }
-    check_group(s.data(), count, who);
+    check_group(s.data(), count, who, need_scaled);
     return s;
+}
+
+// ---- group set-up, scaling and teardown (DESIGN.md "Many small LPs", group set-up) -------------------------------------------
+// counts of the calling thread's last hprlp_solver_create_many / _scale_many / _destroy_many; each call zeroes and fills its own
+static thread_local long g_setup_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
+extern "C" int hprlp_last_setup_many_counts(long out[8]) {
+    if (!out) return -1;
+    for (int i = 0; i < 8; ++i) out[i] = g_setup_counts[i];
+    return 0;
+}
+
+// hprlp_solver_create for every model.  together: the members whose set-up only allocates, zeroes and uploads
+// (Solver::group_setup_fits) are created inside one arena -- a few device blocks, one pinned block, one stream, one copy per
+// block and one wait for all of them; every other member, and everybody when !together, is set up as hprlp_solver_create does.
+// A model that fails leaves out[k] = NULL and its message in hprlp_last_error(); the others are created.  Returns the number
+// created.
+static int create_group(const LP_info_cpu *const *models, int count, const HPRLP_parameters *p, hprlp_solver **out, const char *who, bool together) {
+    for (int k = 0; k < count; ++k) out[k] = nullptr;
+    const AllocCounts before = alloc_counts();
+    Arena *arena = nullptr;
+    if (together) {
+        try {
+            arena = arena_create(p->device_number);
+        } catch (const std::exception &) {
+            // (no device, a wrong device number: every member says so itself below, as in a set-up member by member)
+        }
+    }
+    struct CreatorsReference {  // (the members hold their own: the arena goes with the last of them, or here if nobody joined it)
+        Arena *a;
+        ~CreatorsReference() { arena_release(a); }
+    } creators{arena};
+    int made = 0;
+    try {
+        for (int k = 0; k < count; ++k) {
+            hprlp_solver *h = nullptr;
+            try {
+                if (!models[k]) throw std::runtime_error("null model");
+                h = new hprlp_solver();
+                h->s.verbose = false;
+                if (arena && Solver::group_setup_fits(models[k])) {
+                    ArenaScope scope(arena);
+                    h->s.setup(models[k], p);
+                } else {
+                    h->s.setup(models[k], p);
+                }
+                out[k] = h;
+                ++made;
+            } catch (const std::exception &e) {
+                set_last_error(std::string(who) + ": model " + std::to_string(k) + ": " + e.what());
+                std::cerr << "[error] " << who << ": model " << k << " failed its set-up: " << e.what() << std::endl;
+                delete h;
+            }
+        }
+        if (arena) arena_flush(arena);
+        if (made > 0) HIP_CHECK(hipDeviceSynchronize());
+    } catch (...) {
+        for (int k = 0; k < count; ++k) {
+            delete out[k];
+            out[k] = nullptr;
+        }
+        throw;
+    }
+    const AllocCounts after = alloc_counts();
+    g_setup_counts[0] = after.device_allocs - before.device_allocs;
+    g_setup_counts[1] = after.pinned_allocs - before.pinned_allocs;
+    g_setup_counts[2] = after.h2d_copies - before.h2d_copies;
+    return made;
+}
+
+static void destroy_group(hprlp_solver **h, int count) {
+    const long before = alloc_counts().device_frees;
+    for (int k = 0; k < count; ++k) {
+        try {
+            destroy_handle(h[k]);
+        } catch (...) {
+        }
+        h[k] = nullptr;
+    }
+    g_setup_counts[7] = alloc_counts().device_frees - before;
+}
+
+static void keep_scale_counts(const SetupCounts &sc) {
+    g_setup_counts[3] = sc.scale_launches;
+    g_setup_counts[4] = sc.scale_waits;
+    g_setup_counts[5] = sc.served;
+    g_setup_counts[6] = sc.own;
+}
+
+extern "C" int hprlp_solver_create_many(const LP_info_cpu *const *models, int count, const HPRLP_parameters *param, hprlp_solver **out) {
+    GUARD_BEGIN
+    for (int i = 0; i < 3; ++i) g_setup_counts[i] = 0;
+    if (!models) throw std::runtime_error("hprlp_solver_create_many: null model list");
+    if (count <= 0) throw std::runtime_error("hprlp_solver_create_many: count must be positive");
+    if (!out) throw std::runtime_error("hprlp_solver_create_many: null handle list");
+    HPRLP_parameters dflt;
+    return create_group(models, count, param ? param : &dflt, out, "hprlp_solver_create_many", true);
+    GUARD_END(-1)
+}
+
+extern "C" int hprlp_solver_scale_many(hprlp_solver **h, int count) {
+    GUARD_BEGIN
+    keep_scale_counts(SetupCounts());
+    std::vector<Solver *> s = group_members(h, count, "hprlp_solver_scale_many", false);
+    SetupCounts sc;
+    scale_many(s.data(), count, &sc);
+    keep_scale_counts(sc);
+    return 0;
+    GUARD_END(-1)
+}
+
+extern "C" void hprlp_solver_destroy_many(hprlp_solver **h, int count) {
+    g_setup_counts[7] = 0;
+    if (!h || count <= 0) return;
+    destroy_group(h, count);
 }
 
 extern "C" int hprlp_solver_power_iteration_many(hprlp_solver **h, int count, int max_iter, double tol, double *lambda_out, int *iters_out) {
@@ -1327,28 +1442,50 @@ extern "C" int hprlp_solve_many(const LP_info_cpu *const *models, int count, con
     for (int k = 0; k < count; ++k) out[k] = make_error_result("ERROR");
     for (int i = 0; i < 8; ++i) g_many_phases[i] = 0.0;
     keep_many_counts(GroupCounts());
-    // set-up and scaling, member by member; a model that fails here stays "ERROR" and the others go on
-    std::vector<std::unique_ptr<Solver>> owned(static_cast<size_t>(count));
+    for (int i = 0; i < 8; ++i) g_setup_counts[i] = 0;
+    // set-up and scaling of the whole group (create_group, scale_many); a model that fails its set-up stays "ERROR" and the others
+    // go on.  HPRLP_NO_GROUP_SETUP=1 (test hook, A/B runs): member by member, as hprlp_solver_create + hprlp_solver_scale.
+    const char *ngs = env_get("HPRLP_NO_GROUP_SETUP");
+    const bool together = !(ngs && ngs[0] == '1');
+    std::vector<hprlp_solver *> owned(static_cast<size_t>(count), nullptr);
+    struct Teardown {  // (the members' device state goes when the call ends, however it ends)
+        std::vector<hprlp_solver *> &h;
+        ~Teardown() {
+            for (hprlp_solver *m : h)
+                if (m) {
+                    destroy_group(h.data(), static_cast<int>(h.size()));
+                    return;
+                }
+        }
+    } teardown{owned};
     std::vector<Solver *> s;
     std::vector<int> who;
-    for (int k = 0; k < count; ++k) {
-        try {
-            owned[k].reset(new Solver());
-            owned[k]->verbose = false;
-            owned[k]->setup(models[k], p);
-            owned[k]->scale();
-            g_many_phases[0] += owned[k]->setup_time;
-            g_many_phases[1] += owned[k]->scaling_time;
-            s.push_back(owned[k].get());
+    const auto t_setup = time_now();
+    create_group(models, count, p, owned.data(), "hprlp_solve_many", together);
+    g_many_phases[0] = time_since(t_setup);
+    for (int k = 0; k < count; ++k)
+        if (owned[k]) {
+            s.push_back(&owned[k]->s);
             who.push_back(k);
-        } catch (const std::exception &e) {
-            set_last_error("hprlp_solve_many: model " + std::to_string(k) + ": " + e.what());
-            std::cerr << "[error] hprlp_solve_many: model " << k << " failed its set-up: " << e.what() << std::endl;
-            owned[k].reset();
         }
-    }
     const int ng = static_cast<int>(s.size());
     if (ng > 0) {
+        const auto t_scale = time_now();
+        SetupCounts sc;
+        if (together) {
+            scale_many(s.data(), ng, &sc);
+        } else {
+            const long l0 = scaling_launch_count();
+            for (int g = 0; g < ng; ++g) {
+                const long f0 = s[g]->fetches;
+                s[g]->scale();
+                sc.scale_waits += s[g]->fetches - f0 + 1;
+                ++sc.own;
+            }
+            sc.scale_launches = scaling_launch_count() - l0;
+        }
+        keep_scale_counts(sc);
+        g_many_phases[1] = time_since(t_scale);
         std::vector<HPRLP_results> res(static_cast<size_t>(ng));
         for (auto &r : res) r = make_error_result("ERROR");
         try {
@@ -1374,7 +1511,7 @@ extern "C" int hprlp_solve_many(const LP_info_cpu *const *models, int count, con
         }
         for (int g = 0; g < ng; ++g) out[who[g]] = res[g];
     }
-    owned.clear();  // (the members' device state goes here: part of the call's wall time)
+    destroy_group(owned.data(), count);  // (the members' device state goes here: part of the call's wall time)
     g_many_phases[4] = time_since(t_call);
     return 0;
     GUARD_END(-1)

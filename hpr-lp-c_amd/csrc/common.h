@@ -59,6 +59,37 @@ bool device_cache_put(void *p, size_t capacity);        // false: not cached (ca
 void device_cache_trim();
 void *device_malloc_or_trim(size_t bytes);              // hipMalloc; on out-of-memory: trim the cache, retry once, then throw
 
+// Arena of a group of solvers created together (alloc.cpp; DESIGN.md "Many small LPs", group set-up).  While an ArenaScope is
+// active on the calling thread, DBuf::alloc bump-allocates every request below kDeviceCacheMinBytes out of a few large device
+// blocks (256-byte aligned; release() of such a buffer is a no-op) and HBuf::alloc takes its pinned memory out of one pinned
+// block.  Every device block has a pinned mirror of the same layout while the scope is open: the mirror starts as zeros,
+// DBuf::upload writes into it, and the scope's flush() sends the used part of every block in ONE asynchronous copy -- so the
+// zero-filled buffers and the uploaded arrays of all members cost one copy per block.  Nothing on the device may READ an arena
+// buffer before flush(): the scope is for set-up code that only allocates, zeroes and uploads (abi.cpp: group_setup_fits).
+// The blocks go back when the last solver created in the arena is gone (retain / release).
+struct Arena;
+Arena *arena_create(int device);
+void arena_retain(Arena *a);
+void arena_release(Arena *a);                          // the last one frees the blocks (hipFree waits for the device) and the stream
+hipStream_t arena_stream(Arena *a);                    // the one stream of the solvers created in it
+void arena_flush(Arena *a);                            // the mirrors' used parts to the device (asynchronous, on arena_stream), one wait, mirrors freed
+struct ArenaScope {                                    // RAII: `a` serves the calling thread's small allocations
+    Arena *prev;
+    explicit ArenaScope(Arena *a);
+    ~ArenaScope();
+};
+Arena *arena_in_scope();                               // nullptr: no scope on this thread
+void *arena_alloc(Arena *a, size_t bytes);             // device memory (never null: throws)
+void *arena_alloc_pinned(Arena *a, size_t bytes);      // pinned host memory, zeroed
+bool arena_upload(Arena *a, void *dst, const void *src, size_t bytes);  // true: written into dst's mirror (dst is arena memory not yet flushed)
+bool arena_mirrored(Arena *a, const void *p);          // p lies in a block whose mirror (zeros where nothing was uploaded) is still to be sent
+
+// What the calling thread's allocations and uploads cost (hprlp_last_setup_many_counts): calls to the driver, not buffers.
+struct AllocCounts {
+    long device_allocs = 0, pinned_allocs = 0, h2d_copies = 0, device_frees = 0;
+};
+AllocCounts &alloc_counts();
+
 // Device buffer with RAII; sized in elements.
 template <class T>
 struct DBuf {
@@ -68,17 +99,30 @@ struct DBuf {
     explicit DBuf(size_t count) { alloc(count); }
     DBuf(const DBuf &) = delete;
     DBuf &operator=(const DBuf &) = delete;
-    DBuf(DBuf &&o) noexcept : p(o.p), n(o.n), cap_bytes(o.cap_bytes) { o.p = nullptr; o.n = 0; o.cap_bytes = 0; }
+    DBuf(DBuf &&o) noexcept : p(o.p), n(o.n), cap_bytes(o.cap_bytes), in_arena(o.in_arena) { o.p = nullptr; o.n = 0; o.cap_bytes = 0; o.in_arena = false; }
     DBuf &operator=(DBuf &&o) noexcept {
-        if (this != &o) { release(); p = o.p; n = o.n; cap_bytes = o.cap_bytes; o.p = nullptr; o.n = 0; o.cap_bytes = 0; }
+        if (this != &o) {
+            release();
+            p = o.p; n = o.n; cap_bytes = o.cap_bytes; in_arena = o.in_arena;
+            o.p = nullptr; o.n = 0; o.cap_bytes = 0; o.in_arena = false;
+        }
         return *this;
     }
     ~DBuf() { release(); }
     size_t cap_bytes = 0;  // size of the underlying block (>= n * sizeof(T); blocks from the cache are rounded up)
+    bool in_arena = false;  // p is a piece of an arena block: it goes back with the arena, not here
     void alloc(size_t count) {
         release();
         n = count;
         size_t bytes = (count ? count : 1) * sizeof(T);
+        if (bytes < kDeviceCacheMinBytes) {
+            if (Arena *a = arena_in_scope()) {
+                p = static_cast<T *>(arena_alloc(a, bytes));
+                cap_bytes = bytes;
+                in_arena = true;
+                return;
+            }
+        }
         if (bytes >= kDeviceCacheMinBytes) {
             bytes = (bytes + (size_t(2) << 20) - 1) / (size_t(2) << 20) * (size_t(2) << 20);
             if (void *q = device_cache_get(bytes, &cap_bytes)) {
@@ -91,26 +135,33 @@ struct DBuf {
         cap_bytes = bytes;
         AllocStats::get().malloc_s += time_since(t0);
         ++AllocStats::get().mallocs;
+        ++alloc_counts().device_allocs;
     }
     void alloc_zero(size_t count) {
         alloc(count);
+        if (in_arena && arena_mirrored(arena_in_scope(), p)) return;  // (the block's mirror is zeros there)
         HIP_CHECK(hipMemset(p, 0, (count ? count : 1) * sizeof(T)));
     }
     void release() {
-        if (p) {
+        if (p && !in_arena) {
             if (!(cap_bytes >= kDeviceCacheMinBytes && device_cache_put(p, cap_bytes))) {
                 const auto t0 = time_now();
                 (void)hipFree(p);
                 AllocStats::get().free_s += time_since(t0);
                 ++AllocStats::get().frees;
+                ++alloc_counts().device_frees;
             }
         }
         p = nullptr;
         n = 0;
         cap_bytes = 0;
+        in_arena = false;
     }
     void upload(const T *src, size_t count) {
-        if (count) HIP_CHECK(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
+        if (!count) return;
+        if (in_arena && arena_upload(arena_in_scope(), p, src, count * sizeof(T))) return;
+        HIP_CHECK(hipMemcpy(p, src, count * sizeof(T), hipMemcpyHostToDevice));
+        ++alloc_counts().h2d_copies;
     }
     void download(T *dst, size_t count) const {
         if (count) HIP_CHECK(hipMemcpy(dst, p, count * sizeof(T), hipMemcpyDeviceToHost));
@@ -126,12 +177,21 @@ struct HBuf {
     HBuf() = default;
     HBuf(const HBuf &) = delete;
     HBuf &operator=(const HBuf &) = delete;
-    ~HBuf() { if (p) (void)hipHostFree(p); }
+    bool in_arena = false;  // p is a piece of an arena's pinned block
+    ~HBuf() { if (p && !in_arena) (void)hipHostFree(p); }
     void alloc(size_t count, bool zero = true) {  // (again: the block before is freed)
-        if (p) (void)hipHostFree(p);
+        if (p && !in_arena) (void)hipHostFree(p);
         p = nullptr;
         n = 0;
+        in_arena = false;
+        if (Arena *a = arena_in_scope()) {
+            p = static_cast<T *>(arena_alloc_pinned(a, (count ? count : 1) * sizeof(T)));
+            n = count;
+            in_arena = true;
+            return;
+        }
         HIP_CHECK(hipHostMalloc(reinterpret_cast<void **>(&p), (count ? count : 1) * sizeof(T), hipHostMallocDefault));
+        ++alloc_counts().pinned_allocs;
         n = count;
         if (zero) std::memset(p, 0, (count ? count : 1) * sizeof(T));
     }

@@ -36,6 +36,7 @@ static const EnvEntry kTable[] = {
     {"HPRLP_NO_FAR_PUSH", EnvKind::Hook, "always run the remainder pre-pass (k_far_products) instead of the hand-off from the producing half-step's epilogue"},
     {"HPRLP_NO_FAR_WORK", EnvKind::Hook, "the remainder pre-pass with one workgroup per source group also where one group holds several times the mean (default: a work list cuts heavy groups into chunks, tiled.h f_work)"},
     {"HPRLP_NO_PB_LONG_ROWS", EnvKind::Hook, "a matrix kept off the tiled forms for its long rows keeps the stream kernel also where its columns are not popular (default: all-remainder form, Solver::pb_fallback_wanted)"},
+    {"HPRLP_NO_GROUP_SETUP", EnvKind::Hook, "hprlp_solve_many sets up, scales and frees its members one by one (default: together -- one arena, one copy per arena block, group scaling launches)"},
     {"HPRLP_NO_FUSED_NORMS", EnvKind::Hook, "the Ruiz row norms by their own passes instead of as a by-product of the preceding scaling pass (same bits)"},
     {"HPRLP_NO_LONG_SIDE", EnvKind::Hook, "a matrix with rows over 1024 entries keeps the stream kernel instead of being tiled with those rows kept aside"},
     {"HPRLP_NO_PB_FALLBACK", EnvKind::Hook, "unstructured large matrices keep the stream kernel instead of the tiled form without dense-tile requirement"},

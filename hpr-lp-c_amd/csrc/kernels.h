@@ -407,6 +407,40 @@ class GroupLaunches {
     std::unique_ptr<Impl> impl;
 };
 
+// ---- group scaling (kernels.hip, DESIGN.md "Many small LPs"; many.cpp: scale_many): Solver::scale() of every member of a group in
+// one launch per kernel kind and step.  The calls mirror the single launch_* wrappers and only record.  mark() ends a segment:
+// what is recorded afterwards is launched after everything before it.  Inside a segment one launch per kind present, in this
+// order: row max norms, row sum norms, Curtis-Reid update, the elementwise kernels (fill, vector scaling, scalar scaling, exp /
+// clamp: one launch), the matrix scalings (one launch per <ROW_FIRST, DIVIDE, NEXT> instance present), the two reductions, their
+// finalize items, bound codes, row codes.  repeat_last(n, times): the last n segments are issued `times` times in a row (the
+// twenty Curtis-Reid sweeps share two tables).  run() sends the tables of all segments in one copy and issues the launches; one
+// run's tables are in flight at a time (the caller waits for the stream between two runs, as for GroupLaunches).
+class ScaleLaunches {
+  public:
+    ScaleLaunches();
+    ~ScaleLaunches();
+    ScaleLaunches(const ScaleLaunches &) = delete;
+    void fill(double *x, double a, int n);
+    void vec_scale(double *x, const double *s, int n, bool divide);
+    void vec_scal(double *x, double a, int n);
+    void exp_clamp(double *v, int n);
+    void bnorm2(const double *AL, const double *AU, int m, double *partials);  // kReduceBlocks partials
+    void norm2(const double *x, int n, double *partials);
+    void finalize(const double *partials, int count, double *scalars, int slot);
+    void row_norm(const CsrDev &M, double *result, int norm);  // 99 or 1
+    void scale_matrix(const CsrDev &M, const double *rowvec, const double *colvec_full, bool row_first, bool divide, double *next_max_norm);
+    void cr_log_update(const CsrDev &M, const double *other_full, double *result);
+    void bound_codes(int n, const double *l, const double *u, unsigned char *code);
+    void row_codes(int m, const double *AL, const double *AU, unsigned char *code);
+    void mark();
+    void repeat_last(int nseg, int times);
+    int run(hipStream_t s);  // returns the number of launches
+  private:
+    struct Impl;
+    std::unique_ptr<Impl> impl;
+};
+long &scaling_launch_count();  // kernel launches of the scaling wrappers above on the calling thread (callers take differences)
+
 // device CSR -> device CSR of the transpose, stable in row order (transpose.hip); all pointers are device memory,
 // trp has cols+1 entries, tci / tv nnz
 void device_transpose(int rows, int cols, long nnz, const int *rowptr, const int *col, const double *val, int *trp,

@@ -1868,8 +1868,10 @@ __global__ void __launch_bounds__(kThreads) k_finalize(FinalizeArgs f, double *s
     finalize_body(f.item[blockIdx.x], scalars);
 }
 
+long &scaling_launch_count();
 void launch_finalize(const FinalizeArgs &f, double *scalars, hipStream_t s) {
     if (f.n <= 0) return;
+    ++scaling_launch_count();  // (every finalize counts; the callers take differences around a scaling)
     hipLaunchKernelGGL(k_finalize, dim3(f.n), dim3(kThreads), 0, s, f, scalars);
 }
 
@@ -1987,6 +1989,14 @@ void launch_set_ctrl(Ctrl *ctrl, double sigma, double lambda_max, int reset_k, h
 // ------------------------------------------------------------------------------------------------
 // scaling kernels (reference src/scaling.cu:5-38, HPR_cuda_kernels.cu:34-43,91-157)
 // ------------------------------------------------------------------------------------------------
+// Every kernel below is a __device__ body that takes its workgroup's place `bid` (and, where it matters, the launch's size `grid`)
+// and a __global__ wrapper that passes blockIdx.x / gridDim.x; the group forms at the end of this file run the same bodies as
+// workgroup lb of a member's own grid (DESIGN.md "Many small LPs", group scaling).
+// (kernel launches of Solver::scale and of the group scaling on the calling thread: hprlp_last_setup_many_counts)
+long &scaling_launch_count() {
+    thread_local long n = 0;
+    return n;
+}
 // Curtis-Reid update (reference scaling.cu:5-38): result[r] = mean over the row's entries of (-log|a| - other[col]).
 // Runs as an epilogue of the stream kernel (coalesced matrix reads; per row the terms are added in CSR order like
 // the thread-per-row loop it replaces, which took 6.4 ms per pass on the 2e8-nnz matrix against 1.4 ms).  Through the
@@ -2028,20 +2038,24 @@ void launch_cr_log_update(const CsrDev &M, const double *other_full, double *res
         else if (L.tiled.T == kTileColsNarrow) hipLaunchKernelGGL((k_tiled_fused<CrEpi, false, false, true>), dim3(L.tiled.grid), dim3(kTileThreads), 0, s, L, e);
         else if (L.tiled.repeats) hipLaunchKernelGGL((k_tiled_fused<CrEpi, true>), dim3(L.tiled.grid), dim3(kTileThreads), 0, s, L, e);
         else hipLaunchKernelGGL((k_tiled_fused<CrEpi, false>), dim3(L.tiled.grid), dim3(kTileThreads), 0, s, L, e);
+        ++scaling_launch_count();
         return;
     }
     hipLaunchKernelGGL(k_spmv_fused<CrEpi>, dim3(M.csr_grid()), dim3(kThreads), 0, s, M, e);
+    ++scaling_launch_count();
     if (M.nlong > 0)
         hipLaunchKernelGGL(k_long_finish<CrEpi>, dim3(M.finish_grid()), dim3(kThreads), 0, s, M, e, M.csr_grid());
 }
 
-__global__ void __launch_bounds__(kThreads) k_exp_clamp(double *v, int n) {
-    const int i = blockIdx.x * kThreads + threadIdx.x;
+__device__ __forceinline__ void exp_clamp_body(double *v, int n, int bid) {
+    const int i = bid * kThreads + threadIdx.x;
     if (i < n) v[i] = fmin(fmax(exp(v[i]), 1e-30), 1e30);
 }
+__global__ void __launch_bounds__(kThreads) k_exp_clamp(double *v, int n) { exp_clamp_body(v, n, blockIdx.x); }
 
 void launch_exp_clamp(double *v, int n, hipStream_t s) {
     if (n <= 0) return;
+    ++scaling_launch_count();
     hipLaunchKernelGGL(k_exp_clamp, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, s, v, n);
 }
 
@@ -2072,10 +2086,12 @@ __device__ __forceinline__ double norm_result(double acc) {
     return acc < 1e-15 ? 1.0 : acc;
 }
 
-__global__ void __launch_bounds__(kThreads) k_row_max_blocks(CsrDev M, double *result) {
+// (Mat: CsrDev, or CsrStream in the group form)
+template <class Mat>
+__device__ __forceinline__ void row_max_blocks_body(const Mat &M, double *result, int bid) {
     __shared__ double lds[kWavesPerBlock][kStreamW];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int b = blockIdx.x * kWavesPerBlock + wave;
+    const int b = bid * kWavesPerBlock + wave;
     if (b >= M.nblk) return;
     const int4 d = M.blk[b];
     const int r0 = d.x, nr = d.y, k0 = d.z, nz = d.w;
@@ -2111,6 +2127,7 @@ __global__ void __launch_bounds__(kThreads) k_row_max_blocks(CsrDev M, double *r
         result[r0 + lane] = norm_result(acc);
     }
 }
+__global__ void __launch_bounds__(kThreads) k_row_max_blocks(CsrDev M, double *result) { row_max_blocks_body(M, result, blockIdx.x); }
 
 __global__ void __launch_bounds__(kThreads) k_row_max_long(CsrDev M, double *result) {
     __shared__ double red[kWavesPerBlock];
@@ -2137,10 +2154,11 @@ __global__ void __launch_bounds__(kThreads) k_row_max_long(CsrDev M, double *res
 // The sum norm (Pock-Chambolle, one pass per matrix) over the same row blocks: |a| through LDS (coalesced reads), one lane per
 // row adds its segment in CSR order -- the order of the thread-per-row loop and of the oracle, so the sums are the same bit for
 // bit (2.3 -> 0.5 ms per pass on 2e8 nonzeros).  Rows in vector mode or split into chunks: one lane, in order, from memory.
-__global__ void __launch_bounds__(kThreads) k_row_sum_blocks(CsrDev M, double *result) {
+template <class Mat>
+__device__ __forceinline__ void row_sum_blocks_body(const Mat &M, double *result, int bid) {
     __shared__ double lds[kWavesPerBlock][kStreamW];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int b = blockIdx.x * kWavesPerBlock + wave;
+    const int b = bid * kWavesPerBlock + wave;
     if (b >= M.nblk) return;
     const int4 d = M.blk[b];
     const int r0 = d.x, nr = d.y, k0 = d.z, nz = d.w;
@@ -2167,6 +2185,7 @@ __global__ void __launch_bounds__(kThreads) k_row_sum_blocks(CsrDev M, double *r
         result[r0 + lane] = norm_result(acc);
     }
 }
+__global__ void __launch_bounds__(kThreads) k_row_sum_blocks(CsrDev M, double *result) { row_sum_blocks_body(M, result, blockIdx.x); }
 
 __global__ void __launch_bounds__(kWave) k_row_sum_long(CsrDev M, double *result) {
     const int i = blockIdx.x * kWave + threadIdx.x;
@@ -2303,6 +2322,7 @@ int launch_heaviest_block(const int *rowptr, int rows, int height, hipStream_t s
 
 void launch_row_norm(const CsrDev &M, double *result, int norm, hipStream_t s) {
     if (M.rows <= 0) return;
+    ++scaling_launch_count();
     if (norm == 99 && M.nblk > 0) {
         hipLaunchKernelGGL(k_row_max_blocks, dim3(M.csr_grid()), dim3(kThreads), 0, s, M, result);
         if (M.nlong > 0) hipLaunchKernelGGL(k_row_max_long, dim3(M.nlong), dim3(kThreads), 0, s, M, result);
@@ -2336,17 +2356,19 @@ __device__ __forceinline__ double scale_entry(double v, double rv, double cv) {
 // LDS stores, no dependent chain -- the binary search in the row offsets this replaces was six dependent LDS reads per entry and
 // held the pass at 2.0 ms on 2e8 nonzeros), and with NEXT the pass also leaves norm_result(max |new value|) of every row in
 // next_norm: the following Ruiz pass's row norm, which otherwise re-read the matrix.  The maximum does not depend on the order.
+// (m_*: the fields of the matrix view the pass reads -- of a CsrDev, or of a CsrStream in the group form)
 template <bool ROW_FIRST, bool DIVIDE, bool NEXT>
-__global__ void __launch_bounds__(kThreads) k_scale_matrix(CsrDev M, const double *rowvec, const double *colvec, double *next_norm) {
-    __shared__ double rsv[kWavesPerBlock][kStreamW];
+__device__ __forceinline__ void scale_matrix_body(const int m_nblk, const int4 *m_blk, const int *m_rowptr, const int *m_col, double *m_val,
+                                                  const double *rowvec, const double *colvec, double *next_norm, const int bid,
+                                                  double (*rsv)[kStreamW]) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int b = blockIdx.x * kWavesPerBlock + wave;
-    if (b >= M.nblk) return;
-    const int4 d = M.blk[b];
+    const int b = bid * kWavesPerBlock + wave;
+    if (b >= m_nblk) return;
+    const int4 d = m_blk[b];
     const int r0 = d.x, nr = d.y, k0 = d.z, nz = d.w;
     if (nr == 0) return;  // chunk of a split row: k_scale_long_rows
-    const int *__restrict__ col = M.col + k0;
-    double *__restrict__ val = M.val + k0;
+    const int *__restrict__ col = m_col + k0;
+    double *__restrict__ val = m_val + k0;
     if (nr == 1 && nz > kLongRow) {
         const double rv = rowvec[r0];
         double acc = 0.0;
@@ -2380,8 +2402,8 @@ __global__ void __launch_bounds__(kThreads) k_scale_matrix(CsrDev M, const doubl
     }
     int rs = 0, re = 0;
     if (lane < nr) {
-        rs = M.rowptr[r0 + lane] - k0;
-        re = M.rowptr[r0 + lane + 1] - k0;
+        rs = m_rowptr[r0 + lane] - k0;
+        re = m_rowptr[r0 + lane + 1] - k0;
     }
 #pragma unroll
     for (int t = 0; t < PER; ++t)
@@ -2411,6 +2433,11 @@ __global__ void __launch_bounds__(kThreads) k_scale_matrix(CsrDev M, const doubl
             next_norm[r0 + lane] = norm_result(acc);
         }
     }
+}
+template <bool ROW_FIRST, bool DIVIDE, bool NEXT>
+__global__ void __launch_bounds__(kThreads) k_scale_matrix(CsrDev M, const double *rowvec, const double *colvec, double *next_norm) {
+    __shared__ double rsv[kWavesPerBlock][kStreamW];
+    scale_matrix_body<ROW_FIRST, DIVIDE, NEXT>(M.nblk, M.blk, M.rowptr, M.col, M.val, rowvec, colvec, next_norm, blockIdx.x, rsv);
 }
 
 // rows longer than kSplitRow (their blocks carry chunk slots, not row numbers): one workgroup per row
@@ -2443,6 +2470,7 @@ __global__ void __launch_bounds__(kThreads) k_scale_long_rows(CsrDev M, const do
 
 template <bool ROW_FIRST, bool DIVIDE, bool NEXT>
 static void launch_scale_matrix_t(const CsrDev &M, const double *rowvec, const double *colvec_full, double *next_norm, hipStream_t s) {
+    ++scaling_launch_count();
     hipLaunchKernelGGL((k_scale_matrix<ROW_FIRST, DIVIDE, NEXT>), dim3(M.csr_grid()), dim3(kThreads), 0, s, M, rowvec, colvec_full, next_norm);
     if (M.nlong > 0)
         hipLaunchKernelGGL((k_scale_long_rows<ROW_FIRST, DIVIDE, NEXT>), dim3(M.nlong), dim3(kThreads), 0, s, M, rowvec, colvec_full, next_norm);
@@ -2465,36 +2493,42 @@ void launch_scale_matrix(const CsrDev &M, const double *rowvec, const double *co
     else launch_scale_matrix_t<false, false, false>(M, rowvec, colvec_full, nullptr, s);
 }
 
-__global__ void __launch_bounds__(kThreads) k_vec_scale(double *x, const double *s, int n, int divide) {
-    const int i = blockIdx.x * kThreads + threadIdx.x;
+__device__ __forceinline__ void vec_scale_body(double *x, const double *s, int n, int divide, int bid) {
+    const int i = bid * kThreads + threadIdx.x;
     if (i < n) x[i] = divide ? x[i] / s[i] : x[i] * s[i];
 }
+__global__ void __launch_bounds__(kThreads) k_vec_scale(double *x, const double *s, int n, int divide) { vec_scale_body(x, s, n, divide, blockIdx.x); }
 void launch_vec_scale(double *x, const double *sv, int n, bool divide, hipStream_t s) {
     if (n <= 0) return;
+    ++scaling_launch_count();
     hipLaunchKernelGGL(k_vec_scale, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, s, x, sv, n, divide ? 1 : 0);
 }
 
-__global__ void __launch_bounds__(kThreads) k_vec_scal(double *x, double a, int n) {
-    const int i = blockIdx.x * kThreads + threadIdx.x;
+__device__ __forceinline__ void vec_scal_body(double *x, double a, int n, int bid) {
+    const int i = bid * kThreads + threadIdx.x;
     if (i < n) x[i] = x[i] * a;
 }
+__global__ void __launch_bounds__(kThreads) k_vec_scal(double *x, double a, int n) { vec_scal_body(x, a, n, blockIdx.x); }
 void launch_vec_scal(double *x, double a, int n, hipStream_t s) {
     if (n <= 0) return;
+    ++scaling_launch_count();
     hipLaunchKernelGGL(k_vec_scal, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, s, x, a, n);
 }
 
-__global__ void __launch_bounds__(kThreads) k_fill(double *x, double a, int n) {
-    const int i = blockIdx.x * kThreads + threadIdx.x;
+__device__ __forceinline__ void fill_body(double *x, double a, int n, int bid) {
+    const int i = bid * kThreads + threadIdx.x;
     if (i < n) x[i] = a;
 }
+__global__ void __launch_bounds__(kThreads) k_fill(double *x, double a, int n) { fill_body(x, a, n, blockIdx.x); }
 void launch_fill(double *x, double a, int n, hipStream_t s) {
     if (n <= 0) return;
+    ++scaling_launch_count();
     hipLaunchKernelGGL(k_fill, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, s, x, a, n);
 }
 
-__global__ void __launch_bounds__(kThreads) k_bnorm2(const double *AL, const double *AU, int m, double *partials) {
+__device__ __forceinline__ void bnorm2_body(const double *AL, const double *AU, int m, double *partials, int bid, int grid) {
     double acc[1] = {0.0};
-    const int tid = blockIdx.x * kThreads + threadIdx.x, nth = gridDim.x * kThreads;
+    const int tid = bid * kThreads + threadIdx.x, nth = grid * kThreads;
     for (int i = tid; i < m; i += nth) {
         double a = AL[i], b = AU[i];
         a = isinf(a) ? 0.0 : a;
@@ -2502,38 +2536,48 @@ __global__ void __launch_bounds__(kThreads) k_bnorm2(const double *AL, const dou
         const double v = fmax(fabs(a), fabs(b));
         acc[0] += v * v;
     }
-    block_store_partials<1>(acc, partials, gridDim.x);
+    block_store_partials_at<1>(acc, partials, grid, bid);
+}
+__global__ void __launch_bounds__(kThreads) k_bnorm2(const double *AL, const double *AU, int m, double *partials) {
+    bnorm2_body(AL, AU, m, partials, blockIdx.x, gridDim.x);
 }
 void launch_bnorm2(const double *AL, const double *AU, int m, double *partials, int nblocks, hipStream_t s) {
+    ++scaling_launch_count();
     hipLaunchKernelGGL(k_bnorm2, dim3(nblocks), dim3(kThreads), 0, s, AL, AU, m, partials);
 }
 
-__global__ void __launch_bounds__(kThreads) k_norm2(const double *x, int n, double *partials) {
+__device__ __forceinline__ void norm2_body(const double *x, int n, double *partials, int bid, int grid) {
     double acc[1] = {0.0};
-    const int tid = blockIdx.x * kThreads + threadIdx.x, nth = gridDim.x * kThreads;
+    const int tid = bid * kThreads + threadIdx.x, nth = grid * kThreads;
     for (int i = tid; i < n; i += nth) acc[0] += x[i] * x[i];
-    block_store_partials<1>(acc, partials, gridDim.x);
+    block_store_partials_at<1>(acc, partials, grid, bid);
 }
+__global__ void __launch_bounds__(kThreads) k_norm2(const double *x, int n, double *partials) { norm2_body(x, n, partials, blockIdx.x, gridDim.x); }
 void launch_norm2(const double *x, int n, double *partials, int nblocks, hipStream_t s) {
+    ++scaling_launch_count();
     hipLaunchKernelGGL(k_norm2, dim3(nblocks), dim3(kThreads), 0, s, x, n, partials);
 }
 
 // which of l[j], u[j] the x-half has to read (kernels.h: XHalfArgs::lu_code); derived from the arrays as they are on the
 // device (after scaling: zero stays zero, infinite stays infinite), so a coded bound is bit for bit the stored one
-__global__ void __launch_bounds__(kThreads) k_bound_codes(int n, const double *l, const double *u, unsigned char *code) {
-    const int j = blockIdx.x * kThreads + threadIdx.x;
+__device__ __forceinline__ void bound_codes_body(int n, const double *l, const double *u, unsigned char *code, int bid) {
+    const int j = bid * kThreads + threadIdx.x;
     if (j >= n) return;
     const double lj = l[j], uj = u[j];
     const bool l_zero = __double_as_longlong(lj) == 0, l_minf = lj == -__builtin_huge_val(), u_pinf = uj == __builtin_huge_val();
     code[j] = static_cast<unsigned char>((l_zero || l_minf ? 0u : kLoadL) | (u_pinf ? 0u : kLoadU) | (l_zero ? kZeroL : 0u));
 }
+__global__ void __launch_bounds__(kThreads) k_bound_codes(int n, const double *l, const double *u, unsigned char *code) {
+    bound_codes_body(n, l, u, code, blockIdx.x);
+}
 void launch_bound_codes(int n, const double *l, const double *u, unsigned char *code, hipStream_t s) {
+    if (n > 0) ++scaling_launch_count();
     if (n > 0) hipLaunchKernelGGL(k_bound_codes, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, s, n, l, u, code);
 }
 
 // which of AL[i], AU[i] the y-half has to read (kernels.h: YHalfArgs::row_code); derived from the arrays as they are on the device
-__global__ void __launch_bounds__(kThreads) k_row_codes(int m, const double *AL, const double *AU, unsigned char *code) {
-    const int i = blockIdx.x * kThreads + threadIdx.x;
+__device__ __forceinline__ void row_codes_body(int m, const double *AL, const double *AU, unsigned char *code, int bid) {
+    const int i = bid * kThreads + threadIdx.x;
     if (i >= m) return;
     const double lo = AL[i], hi = AU[i];
     const bool lo_minf = lo == -__builtin_huge_val(), hi_pinf = hi == __builtin_huge_val();
@@ -2541,7 +2585,11 @@ __global__ void __launch_bounds__(kThreads) k_row_codes(int m, const double *AL,
     const bool eq = !hi_pinf && __double_as_longlong(lo) == __double_as_longlong(hi);
     code[i] = static_cast<unsigned char>((lo_minf || eq ? 0u : kLoadLo) | (hi_pinf ? 0u : kLoadHi) | (eq ? kRowEq : 0u));
 }
+__global__ void __launch_bounds__(kThreads) k_row_codes(int m, const double *AL, const double *AU, unsigned char *code) {
+    row_codes_body(m, AL, AU, code, blockIdx.x);
+}
 void launch_row_codes(int m, const double *AL, const double *AU, unsigned char *code, hipStream_t s) {
+    if (m > 0) ++scaling_launch_count();
     if (m > 0) hipLaunchKernelGGL(k_row_codes, dim3((m + kThreads - 1) / kThreads), dim3(kThreads), 0, s, m, AL, AU, code);
 }
 
@@ -3164,6 +3212,257 @@ void GroupLaunches::deliver() {
     Impl &g = *impl;
     for (int k = 0; k < g.deliver_n; ++k) std::memcpy(g.deliver_to[k], g.packed_h.p + static_cast<size_t>(k) * kNumScalars, kNumScalars * sizeof(double));
     g.deliver_n = 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// group forms of the scaling kernels (DESIGN.md "Many small LPs", group scaling; many.cpp: scale_many).  The rule of the group
+// launches above: a workgroup reads {task, lb} (uniform: scalar loads) and runs the single kernel's body as workgroup lb of the
+// member's own grid -- ceil(len / kThreads) for the elementwise kernels, csr_grid() for the matrix passes, kReduceBlocks for the
+// two reductions (task = blockIdx.x / kReduceBlocks, no table) -- so every value, partial and finalised sum is the member's own.
+// ------------------------------------------------------------------------------------------------
+enum VecOp : int { kVecFill = 0, kVecMul = 1, kVecDiv = 2, kVecScal = 3, kVecExpClamp = 4 };
+struct VecTask {  // k_fill, k_vec_scale (multiply / divide), k_vec_scal, k_exp_clamp
+    double *x;
+    const double *s;
+    double a;
+    int n, op;
+};
+struct ReduceTask {  // k_bnorm2 (a = AL, b = AU) / k_norm2 (a = x)
+    const double *a, *b;
+    int n;
+    double *partials;
+};
+struct RowNormTask {
+    CsrStream A;
+    double *result;
+};
+struct ScaleMatTask {
+    CsrStream A;
+    const double *rowvec, *colvec;
+    double *next_norm;
+};
+struct CodesTask {  // k_bound_codes (a = l, b = u) / k_row_codes (a = AL, b = AU)
+    int n;
+    const double *a, *b;
+    unsigned char *code;
+};
+
+__global__ void __launch_bounds__(kThreads) k_vec_many(const VecTask *__restrict__ tasks, const int2 *__restrict__ wgmap) {
+    const int2 w = wgmap[blockIdx.x];
+    const VecTask t = tasks[w.x];
+    switch (t.op) {  // (uniform in the workgroup)
+        case kVecFill: fill_body(t.x, t.a, t.n, w.y); break;
+        case kVecMul: vec_scale_body(t.x, t.s, t.n, 0, w.y); break;
+        case kVecDiv: vec_scale_body(t.x, t.s, t.n, 1, w.y); break;
+        case kVecScal: vec_scal_body(t.x, t.a, t.n, w.y); break;
+        default: exp_clamp_body(t.x, t.n, w.y); break;
+    }
+}
+__global__ void __launch_bounds__(kThreads) k_bnorm2_many(const ReduceTask *__restrict__ tasks) {
+    const ReduceTask t = tasks[blockIdx.x / kReduceBlocks];
+    bnorm2_body(t.a, t.b, t.n, t.partials, blockIdx.x % kReduceBlocks, kReduceBlocks);
+}
+__global__ void __launch_bounds__(kThreads) k_norm2_many(const ReduceTask *__restrict__ tasks) {
+    const ReduceTask t = tasks[blockIdx.x / kReduceBlocks];
+    norm2_body(t.a, t.n, t.partials, blockIdx.x % kReduceBlocks, kReduceBlocks);
+}
+__global__ void __launch_bounds__(kThreads) k_row_max_blocks_many(const RowNormTask *__restrict__ tasks, const int2 *__restrict__ wgmap) {
+    const int2 w = wgmap[blockIdx.x];
+    const CsrStream A = tasks[w.x].A;
+    row_max_blocks_body(A, tasks[w.x].result, w.y);
+}
+__global__ void __launch_bounds__(kThreads) k_row_sum_blocks_many(const RowNormTask *__restrict__ tasks, const int2 *__restrict__ wgmap) {
+    const int2 w = wgmap[blockIdx.x];
+    const CsrStream A = tasks[w.x].A;
+    row_sum_blocks_body(A, tasks[w.x].result, w.y);
+}
+template <bool ROW_FIRST, bool DIVIDE, bool NEXT>
+__global__ void __launch_bounds__(kThreads) k_scale_matrix_many(const ScaleMatTask *__restrict__ tasks, const int2 *__restrict__ wgmap) {
+    const int2 w = wgmap[blockIdx.x];
+    const ScaleMatTask t = tasks[w.x];
+    __shared__ double rsv[kWavesPerBlock][kStreamW];
+    scale_matrix_body<ROW_FIRST, DIVIDE, NEXT>(t.A.nblk, t.A.blk, t.A.rowptr, t.A.col, const_cast<double *>(t.A.val), t.rowvec, t.colvec, t.next_norm, w.y, rsv);
+}
+__global__ void __launch_bounds__(kThreads) k_bound_codes_many(const CodesTask *__restrict__ tasks, const int2 *__restrict__ wgmap) {
+    const int2 w = wgmap[blockIdx.x];
+    const CodesTask t = tasks[w.x];
+    bound_codes_body(t.n, t.a, t.b, t.code, w.y);
+}
+__global__ void __launch_bounds__(kThreads) k_row_codes_many(const CodesTask *__restrict__ tasks, const int2 *__restrict__ wgmap) {
+    const int2 w = wgmap[blockIdx.x];
+    const CodesTask t = tasks[w.x];
+    row_codes_body(t.n, t.a, t.b, t.code, w.y);
+}
+
+// One segment of a recording: tasks that do not depend on each other except in the fixed order of the kinds below, which is the
+// order of a member's own calls wherever two kinds of one segment touch the same memory (many.cpp places the marks accordingly).
+struct ScaleSegment {
+    std::vector<RowNormTask> rmax, rsum;
+    std::vector<GroupTask<CrEpi>> cr;
+    std::vector<VecTask> vec;
+    std::vector<ScaleMatTask> mat[8];  // index: ROW_FIRST << 2 | DIVIDE << 1 | NEXT
+    std::vector<ReduceTask> bn, n2;
+    std::vector<FinalizeOne> fin;
+    std::vector<CodesTask> lu, rc;
+};
+
+struct ScaleLaunches::Impl {
+    std::vector<ScaleSegment> segs = std::vector<ScaleSegment>(1);
+    std::vector<int> order;  // the closed segments in the order they are issued (a repeated one appears more than once)
+    SmallTaskBuf buf;
+    std::vector<char> bytes;
+    std::vector<int2> map;
+    ScaleSegment &st() { return segs.back(); }
+    size_t put(const void *p, size_t n) {
+        const size_t at = (bytes.size() + 15) / 16 * 16;
+        bytes.resize(at + n);
+        std::memcpy(bytes.data() + at, p, n);
+        return at;
+    }
+};
+
+ScaleLaunches::ScaleLaunches() : impl(new Impl()) {}
+ScaleLaunches::~ScaleLaunches() = default;
+
+static int elem_grid(int n) { return (n + kThreads - 1) / kThreads; }
+
+void ScaleLaunches::fill(double *x, double a, int n) {
+    if (n > 0) impl->st().vec.push_back({x, nullptr, a, n, kVecFill});
+}
+void ScaleLaunches::vec_scale(double *x, const double *sv, int n, bool divide) {
+    if (n > 0) impl->st().vec.push_back({x, sv, 0.0, n, divide ? kVecDiv : kVecMul});
+}
+void ScaleLaunches::vec_scal(double *x, double a, int n) {
+    if (n > 0) impl->st().vec.push_back({x, nullptr, a, n, kVecScal});
+}
+void ScaleLaunches::exp_clamp(double *v, int n) {
+    if (n > 0) impl->st().vec.push_back({v, nullptr, 0.0, n, kVecExpClamp});
+}
+void ScaleLaunches::bnorm2(const double *AL, const double *AU, int m, double *partials) { impl->st().bn.push_back({AL, AU, m, partials}); }
+void ScaleLaunches::norm2(const double *x, int n, double *partials) { impl->st().n2.push_back({x, nullptr, n, partials}); }
+void ScaleLaunches::finalize(const double *partials, int count, double *scalars, int slot) {
+    impl->st().fin.push_back({FinalizeItem{partials, count, slot, 0}, scalars});
+}
+void ScaleLaunches::row_norm(const CsrDev &M, double *result, int norm) {
+    if (norm != 99 && norm != 1) throw std::runtime_error("group scaling: a row norm other than the max norm and the sum norm");
+    (norm == 99 ? impl->st().rmax : impl->st().rsum).push_back({stream_part(M), result});
+}
+void ScaleLaunches::scale_matrix(const CsrDev &M, const double *rowvec, const double *colvec_full, bool row_first, bool divide, double *next_max_norm) {
+    const int inst = (row_first ? 4 : 0) | (divide ? 2 : 0) | (next_max_norm ? 1 : 0);
+    impl->st().mat[inst].push_back({stream_part(M), rowvec, colvec_full, next_max_norm});
+}
+void ScaleLaunches::cr_log_update(const CsrDev &M, const double *other_full, double *result) {
+    impl->st().cr.push_back({stream_part(M), CrEpi{{other_full}, M.rowptr, result, nullptr, 0}});
+}
+void ScaleLaunches::bound_codes(int n, const double *l, const double *u, unsigned char *code) {
+    if (n > 0) impl->st().lu.push_back({n, l, u, code});
+}
+void ScaleLaunches::row_codes(int m, const double *AL, const double *AU, unsigned char *code) {
+    if (m > 0) impl->st().rc.push_back({m, AL, AU, code});
+}
+void ScaleLaunches::mark() {
+    impl->order.push_back(static_cast<int>(impl->segs.size()) - 1);
+    impl->segs.emplace_back();
+}
+void ScaleLaunches::repeat_last(int nseg, int times) {
+    Impl &g = *impl;
+    if (nseg <= 0 || static_cast<size_t>(nseg) > g.order.size()) throw std::runtime_error("group scaling: repeat of segments that were not recorded");
+    const std::vector<int> tail(g.order.end() - nseg, g.order.end());
+    for (int t = 1; t < times; ++t) g.order.insert(g.order.end(), tail.begin(), tail.end());
+}
+
+int ScaleLaunches::run(hipStream_t s) {
+    Impl &g = *impl;
+    mark();  // (what is open is part of this run)
+    g.bytes.clear();
+    struct Spot {
+        size_t tasks = 0, map = 0;
+        int nwg = 0;
+    };
+    struct Spots {
+        Spot rmax, rsum, cr, vec, mat[8], bn, n2, fin, lu, rc;
+    };
+    std::vector<Spots> spots(g.segs.size());
+    auto table = [&](const auto &tasks, Spot &sp) {
+        if (!tasks.empty()) sp.tasks = g.put(tasks.data(), tasks.size() * sizeof(tasks[0]));
+    };
+    auto table_map = [&](const auto &tasks, Spot &sp, auto grid_of) {
+        if (tasks.empty()) return;
+        sp.tasks = g.put(tasks.data(), tasks.size() * sizeof(tasks[0]));
+        g.map.clear();
+        for (size_t t = 0; t < tasks.size(); ++t)
+            for (int lb = 0, lg = grid_of(tasks[t]); lb < lg; ++lb) g.map.push_back(int2{static_cast<int>(t), lb});
+        sp.nwg = static_cast<int>(g.map.size());
+        sp.map = g.put(g.map.data(), g.map.size() * sizeof(int2));
+    };
+    auto csr_grid_of = [](const auto &t) { return t.A.csr_grid(); };
+    for (size_t i = 0; i + 1 < g.segs.size(); ++i) {  // (the last one is the empty segment mark() opened)
+        const ScaleSegment &t = g.segs[i];
+        Spots &p = spots[i];
+        table_map(t.rmax, p.rmax, csr_grid_of);
+        table_map(t.rsum, p.rsum, csr_grid_of);
+        table_map(t.cr, p.cr, csr_grid_of);
+        table_map(t.vec, p.vec, [](const VecTask &v) { return elem_grid(v.n); });
+        for (int k = 0; k < 8; ++k) table_map(t.mat[k], p.mat[k], csr_grid_of);
+        table(t.bn, p.bn);
+        table(t.n2, p.n2);
+        table(t.fin, p.fin);
+        table_map(t.lu, p.lu, [](const CodesTask &c) { return elem_grid(c.n); });
+        table_map(t.rc, p.rc, [](const CodesTask &c) { return elem_grid(c.n); });
+    }
+    int launches = 0;
+    if (!g.bytes.empty()) {
+        std::memcpy(g.buf.stage(g.bytes.size()), g.bytes.data(), g.bytes.size());
+        g.buf.send(g.bytes.size(), s);
+    }
+    const char *dev = static_cast<const char *>(g.buf.dev);
+    auto launched = [&]() {
+        HIP_CHECK(hipGetLastError());
+        ++launches;
+    };
+#define HPRLP_MAPPED(kernel, Task, sp)                                                                                                       \
+    if ((sp).nwg > 0) {                                                                                                                      \
+        hipLaunchKernelGGL(kernel, dim3((sp).nwg), dim3(kThreads), 0, s, reinterpret_cast<const Task *>(dev + (sp).tasks),                   \
+                           reinterpret_cast<const int2 *>(dev + (sp).map));                                                                  \
+        launched();                                                                                                                          \
+    }
+    for (int i : g.order) {
+        const ScaleSegment &t = g.segs[i];
+        const Spots &p = spots[i];
+        HPRLP_MAPPED(k_row_max_blocks_many, RowNormTask, p.rmax)
+        HPRLP_MAPPED(k_row_sum_blocks_many, RowNormTask, p.rsum)
+        HPRLP_MAPPED(k_spmv_fused_many<CrEpi>, GroupTask<CrEpi>, p.cr)
+        HPRLP_MAPPED(k_vec_many, VecTask, p.vec)
+        HPRLP_MAPPED((k_scale_matrix_many<false, false, false>), ScaleMatTask, p.mat[0])
+        HPRLP_MAPPED((k_scale_matrix_many<false, false, true>), ScaleMatTask, p.mat[1])
+        HPRLP_MAPPED((k_scale_matrix_many<false, true, false>), ScaleMatTask, p.mat[2])
+        HPRLP_MAPPED((k_scale_matrix_many<false, true, true>), ScaleMatTask, p.mat[3])
+        HPRLP_MAPPED((k_scale_matrix_many<true, false, false>), ScaleMatTask, p.mat[4])
+        HPRLP_MAPPED((k_scale_matrix_many<true, false, true>), ScaleMatTask, p.mat[5])
+        HPRLP_MAPPED((k_scale_matrix_many<true, true, false>), ScaleMatTask, p.mat[6])
+        HPRLP_MAPPED((k_scale_matrix_many<true, true, true>), ScaleMatTask, p.mat[7])
+        if (!t.bn.empty()) {
+            hipLaunchKernelGGL(k_bnorm2_many, dim3(static_cast<unsigned>(t.bn.size()) * kReduceBlocks), dim3(kThreads), 0, s,
+                               reinterpret_cast<const ReduceTask *>(dev + p.bn.tasks));
+            launched();
+        }
+        if (!t.n2.empty()) {
+            hipLaunchKernelGGL(k_norm2_many, dim3(static_cast<unsigned>(t.n2.size()) * kReduceBlocks), dim3(kThreads), 0, s,
+                               reinterpret_cast<const ReduceTask *>(dev + p.n2.tasks));
+            launched();
+        }
+        if (!t.fin.empty()) {
+            hipLaunchKernelGGL(k_finalize_many, dim3(static_cast<unsigned>(t.fin.size())), dim3(kThreads), 0, s,
+                               reinterpret_cast<const FinalizeOne *>(dev + p.fin.tasks));
+            launched();
+        }
+        HPRLP_MAPPED(k_bound_codes_many, CodesTask, p.lu)
+        HPRLP_MAPPED(k_row_codes_many, CodesTask, p.rc)
+    }
+#undef HPRLP_MAPPED
+    g.segs.assign(1, ScaleSegment());
+    g.order.clear();
+    return launches;
 }
 
 // warm-up (abi.cpp: hprlp_warmup): an attribute query makes the runtime load this translation unit's code object now instead

@@ -600,7 +600,21 @@ Solver::~Solver() {
     if (ev_done_x) (void)hipEventDestroy(ev_done_x);
     if (ev_done_y) (void)hipEventDestroy(ev_done_y);
     if (comm_stream) (void)hipStreamDestroy(comm_stream);
-    if (stream) (void)hipStreamDestroy(stream);
+    if (stream && !arena) (void)hipStreamDestroy(stream);
+    // (the buffers taken from the arena are not given back one by one: DBuf::release leaves them alone; the last member frees the blocks)
+    if (arena) arena_release(arena);
+}
+
+bool Solver::group_setup_fits(const LP_info_cpu *model) {
+    if (!model || !model->A || model->m <= 0 || model->n <= 0) return false;
+    const long nnz = model->A->numElements;
+    if (!small_path_fits(model->m, model->n, nnz, 0, 0)) return false;
+    const char *hostt = env_get("HPRLP_HOST_TRANSPOSE");
+    const char *dmin = env_get("HPRLP_DEVICE_TRANSPOSE_MIN");
+    if (nnz > (dmin ? std::atol(dmin) : 4000000L) && !(hostt && hostt[0] == '1')) return false;  // (setup(): the device transpose)
+    const FormHooks hk = read_form_hooks();
+    // (form_select.cpp: before_build -- so few columns are "not attempted" unless a hook lowers the thresholds)
+    return hk.no_tiled || (!hk.tiled_min_rows.set && !hk.tiled_min_cols.set && !hk.tiled_anyway);
 }
 
 void Solver::alloc_work() {
@@ -621,6 +635,10 @@ void Solver::alloc_work() {
     part_y.alloc_zero(static_cast<size_t>(2) * stride_y);
     part_r.alloc_zero(static_cast<size_t>(2) * std::max(stride_x, stride_y));
     part_v.alloc_zero(static_cast<size_t>(2) * kReduceBlocks);
+    if (arena && !hook_no_bound_codes) {  // (refresh_bound_codes would allocate them after the scope: two hipMallocs and two hipFrees per member)
+        if (n_loc > 0) lu_code.alloc(static_cast<size_t>(n_loc));
+        if (m_loc > 0) row_code.alloc(static_cast<size_t>(m_loc));
+    }
     const char *ng = env_get("HPRLP_NO_GRAPH");
     use_graph = !(ng && ng[0] == '1') && comm == nullptr;
     const char *no = env_get("HPRLP_NO_OVERLAP");
@@ -635,7 +653,13 @@ void Solver::setup(const LP_info_cpu *model, const HPRLP_parameters *param) {
     env_at_setup = env_in_effect(&env_ignored_at_setup);
     read_hooks();
     HIP_CHECK(hipSetDevice(prm.device_number));
-    HIP_CHECK(hipStreamCreate(&stream));
+    if (Arena *a = arena_in_scope()) {
+        arena = a;
+        arena_retain(a);
+        stream = arena_stream(a);
+    } else {
+        HIP_CHECK(hipStreamCreate(&stream));
+    }
     m = m_loc = model->m;
     n = n_loc = model->n;
     m_pad = m; n_pad = n;
@@ -806,7 +830,7 @@ void Solver::setup(const LP_info_cpu *model, const HPRLP_parameters *param) {
     // job of A^T owns its arrays and keeps running under scale()
     A.finish_tiling(stream);
     pt.tick("vectors, work space, tiled copy of A");
-    HIP_CHECK(hipDeviceSynchronize());
+    if (!arena) HIP_CHECK(hipDeviceSynchronize());  // (a group waits once, after the arena's flush)
     setup_time = time_since(t0);
     if (pt.on) {
         const AllocStats &as = AllocStats::get();

@@ -111,6 +111,13 @@ struct Solver {
     double obj_constant = 0.0;
     bool verbose = true;
     hipStream_t stream = nullptr;
+    // Created inside an ArenaScope (common.h; abi.cpp: hprlp_solver_create_many): the small device buffers and the pinned scalar
+    // block of setup() are pieces of the group's arena, `stream` is the group's and goes with the arena, not with this solver.
+    Arena *arena = nullptr;
+    // setup() inside an ArenaScope is sound only where it allocates, zeroes and uploads and launches nothing (the uploads reach
+    // the device at arena_flush): a model within the small path's sizes that no hook sends through a device transpose or a tiled
+    // build.  Host-only test.
+    static bool group_setup_fits(const LP_info_cpu *model);
     Comm *comm = nullptr;
     // Second communicator (its own unique id) for the exchanges enqueued on comm_stream beside the local part of a
     // half-step: a communicator is only ever driven from ONE stream.  Null: the in-process group (host-blocking, no

@@ -221,6 +221,12 @@ def lib():
         L.hprlp_solver_residuals_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, c_int_p, c_int_p, c_dbl_p]
         L.hprlp_solver_restart_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, c_dbl_p, c_dbl_p]
         L.hprlp_last_run_many_counts.argtypes = [C.POINTER(C.c_long)]
+    if hasattr(L, "hprlp_solver_create_many"):  # (likewise)
+        L.hprlp_solver_create_many.argtypes = [C.POINTER(C.POINTER(CLPInfo)), C.c_int, C.POINTER(CParameters), C.POINTER(C.c_void_p)]
+        L.hprlp_solver_scale_many.argtypes = [C.POINTER(C.c_void_p), C.c_int]
+        L.hprlp_solver_destroy_many.argtypes = [C.POINTER(C.c_void_p), C.c_int]
+        L.hprlp_solver_destroy_many.restype = None
+        L.hprlp_last_setup_many_counts.argtypes = [C.POINTER(C.c_long)]
     _lib = L
     return L
 
@@ -551,6 +557,18 @@ def last_run_many_counts():
     lib().hprlp_last_run_many_counts(out)
     keys = ("rounds", "waits", "group_launches", "copies", "own", "served")
     return dict(zip(keys, [int(v) for v in out]))
+
+
+SETUP_MANY_KEYS = ("device allocations", "pinned allocations", "host-to-device copies", "scaling launches", "scaling host waits",
+                   "members served by group scaling launches", "members that scaled on their own", "device frees")
+
+
+def last_setup_many_counts():
+    """Counts of this thread's last Solver.create_many / scale_many / close_many (hprlp_last_setup_many_counts): each call fills
+    its own slots; solve_many fills all of them."""
+    out = (C.c_long * 8)()
+    lib().hprlp_last_setup_many_counts(out)
+    return dict(zip(SETUP_MANY_KEYS, [int(v) for v in out]))
 
 
 def solve_batched(model, Cmat, AL, AU, l, u, obj_constants=None, param=None):
@@ -940,6 +958,46 @@ class Solver:
         self.h = lib().hprlp_solver_create(model._ptr, C.byref(cp))
         if not self.h:
             raise RuntimeError("hprlp_solver_create failed: " + last_error())
+
+    @classmethod
+    def create_many(cls, models, param=None):
+        """Solver(model, param) for every model, set up together (hprlp_solver_create_many): one arena, one stream and one copy per
+        arena block for the Netlib-scale members.  Returns a list with None where a model failed (last_error() names it)."""
+        models = list(models)
+        cp = (param or Parameters()).to_c()
+        ptrs = (C.POINTER(CLPInfo) * max(len(models), 1))(*[mod._ptr for mod in models])
+        hs = (C.c_void_p * max(len(models), 1))()
+        if lib().hprlp_solver_create_many(ptrs, len(models), C.byref(cp), hs) < 0:
+            raise RuntimeError(last_error())
+        out = []
+        for k, mod in enumerate(models):
+            if not hs[k]:
+                out.append(None)
+                continue
+            sv = cls.__new__(cls)
+            sv.model = mod
+            sv.h = hs[k]
+            out.append(sv)
+        return out
+
+    @staticmethod
+    def scale_many(solvers):
+        """scale() of every solver, one launch per kernel kind and scaling step for the small-path members
+        (hprlp_solver_scale_many)."""
+        solvers, hs = Solver._handles(solvers)
+        if lib().hprlp_solver_scale_many(hs, len(solvers)) < 0:
+            raise RuntimeError(last_error())
+
+    @staticmethod
+    def close_many(solvers):
+        """close() of every solver that is not None (hprlp_solver_destroy_many)."""
+        solvers = [sv for sv in solvers if sv is not None and sv.h]
+        if not solvers:
+            return
+        _, hs = Solver._handles(solvers)
+        lib().hprlp_solver_destroy_many(hs, len(solvers))
+        for sv in solvers:
+            sv.h = None
 
     @classmethod
     def create_dist(cls, model, param, rank, size, unique_id=None):

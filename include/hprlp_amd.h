@@ -303,11 +303,30 @@ int hprlp_solver_restart_many(hprlp_solver **s, int count, const double *in /* 6
  * finished member drops out, the call returns with the last one.  out[k].time = the member's power-iteration (or set_data) time
  * + the group loop's wall time up to the member's last event; time_limit applies to that value. */
 int hprlp_solver_run_many(hprlp_solver **s, int count, HPRLP_results *out);
-/* What HPRLP_main_solve does, for `count` models at once: set-up and scaling member by member, the power iterations together
- * (lambda x 1.01), the loop together, solutions, teardown.  NO presolve on this path: param->use_presolve is ignored, as in
+/* What HPRLP_main_solve does, for `count` models at once: hprlp_solver_create_many, hprlp_solver_scale_many, the power iterations
+ * together (lambda x 1.01), the loop together, solutions, hprlp_solver_destroy_many.  NO presolve on this path: param->use_presolve is ignored, as in
  * solve_batched.  A model that fails its set-up gets status "ERROR" (and hprlp_last_error() names it); the others are solved. */
 int hprlp_solve_many(const LP_info_cpu *const *models, int count, const HPRLP_parameters *param, HPRLP_results *out);
-/* Wall-clock phases [s] of the calling thread's last hprlp_solve_many: out = {set-up (sum over the members), scaling (sum), power
+/* Group form of creation, scaling and destruction: every member ends bit for bit the solver that hprlp_solver_create +
+ * hprlp_solver_scale give it alone.  The members of a _create_many call whose set-up only allocates and uploads (Netlib-scale
+ * models) share one arena -- a few device blocks, one pinned block, one stream, one copy per block -- which goes when the last
+ * of them is destroyed, in any order, by either destroy call; _scale_many issues one launch per kernel kind and scaling step for
+ * the members on the small path and three host waits for the whole group, every other member scales on its own inside the call.
+ * Refused before anything is launched or allocated: a NULL list, count <= 0, a handle given twice, a sharded solver, members on
+ * different devices. */
+/* hprlp_solver_create for every model, on param->device_number; out[k] = NULL where model k failed.  Returns the number created, -1 on bad arguments. */
+int  hprlp_solver_create_many(const LP_info_cpu *const *models, int count, const HPRLP_parameters *param, hprlp_solver **out);
+/* hprlp_solver_scale for every member; handles from hprlp_solver_create are as welcome as those from _create_many */
+int  hprlp_solver_scale_many(hprlp_solver **s, int count);
+/* hprlp_solver_destroy for every non-NULL entry */
+void hprlp_solver_destroy_many(hprlp_solver **s, int count);
+/* calling thread's last create_many / scale_many / destroy_many (each fills its own slots):
+ * {device allocations, pinned allocations, host-to-device copies, scaling launches, scaling host waits,
+ *  members served by group scaling launches, members that scaled on their own, device frees} */
+int  hprlp_last_setup_many_counts(long out[8]);
+/* bookkeeping self-test of the arena, no GPU needed: 0, or the number of the failed check */
+int  hprlp_arena_selftest(void);
+/* Wall-clock phases [s] of the calling thread's last hprlp_solve_many: out = {set-up of the group, scaling of the group, power
  * iterations + init, loop + solutions' way back, whole call (teardown included), evaluation rounds, host waits, group launches of
  * the normal iterations (every kind: hprlp_last_run_many_counts)} */
 int hprlp_last_solve_many_phases(double out[8]);
