@@ -1812,6 +1812,66 @@ extern "C" int hprlp_solver_matrix_seconds(hprlp_solver *h, double out[6]) {
     GUARD_END(-1)
 }
 
+// Device-resident re-solve (DESIGN.md "Device-resident re-solve"): the three entries above with the vectors in device memory
+extern "C" int hprlp_solver_set_data_device(hprlp_solver *h, const double *dc, const double *obj_constant, const double *dAL,
+                                            const double *dAU, const double *dl, const double *du, void *stream) {
+    GUARD_BEGIN
+    if (!h) throw std::runtime_error("hprlp_solver_set_data_device: null solver");
+    if (h->sharded)
+        throw std::runtime_error("hprlp_solver_set_data_device: new data for a resident model runs on one GPU only; a sharded solver "
+                                 "(hprlp_solver_create_dist* / _local*) refuses it");
+    h->s.set_data_device(dc, obj_constant, dAL, dAU, dl, du, static_cast<hipStream_t>(stream));
+    return 0;
+    GUARD_END(-1)
+}
+
+extern "C" int hprlp_solver_resolve_device(hprlp_solver *h, double sigma, const double *dx0, const double *dy0, void *stream, double *dx,
+                                           double *dy, double *dz, HPRLP_results *out, hprlp_trace_row *trace, int max_trace,
+                                           int *n_trace) {
+    GUARD_BEGIN
+    if (!h || !out) throw std::runtime_error("hprlp_solver_resolve_device: null solver / result");
+    if (h->sharded)
+        throw std::runtime_error("hprlp_solver_resolve_device: a re-solve runs on one GPU only; a sharded solver (hprlp_solver_create_dist* / "
+                                 "_local*) refuses it");
+    if (std::isnan(sigma)) throw std::runtime_error("hprlp_solver_resolve_device: sigma is NaN");
+    Solver &s = h->s;
+    s.trace = reinterpret_cast<TraceRow *>(trace);
+    s.trace_cap = trace ? max_trace : 0;
+    try {
+        s.resolve_device(sigma, dx0, dy0, static_cast<hipStream_t>(stream), dx, dy, dz, out);
+    } catch (...) {
+        s.trace = nullptr;
+        s.trace_cap = 0;
+        throw;
+    }
+    if (n_trace) *n_trace = s.trace_n;
+    s.trace = nullptr;
+    s.trace_cap = 0;
+    return 0;
+    GUARD_END(-1)
+}
+
+extern "C" int hprlp_solver_set_matrix_values_device(hprlp_solver *h, const double *dval, long nnz, const double *dc,
+                                                     const double *obj_constant, const double *dAL, const double *dAU, const double *dl,
+                                                     const double *du, void *stream) {
+    GUARD_BEGIN
+    if (!h) throw std::runtime_error("hprlp_solver_set_matrix_values_device: null solver");
+    if (h->sharded)
+        throw std::runtime_error("hprlp_solver_set_matrix_values_device: new matrix values for a resident model run on one GPU only; a "
+                                 "sharded solver (hprlp_solver_create_dist* / _local*) refuses them");
+    h->s.set_matrix_values_device(dval, nnz, dc, obj_constant, dAL, dAU, dl, du, static_cast<hipStream_t>(stream));
+    return 0;
+    GUARD_END(-1)
+}
+
+extern "C" int hprlp_solver_transfer(hprlp_solver *h, long out[4]) {
+    GUARD_BEGIN
+    if (!h || !out) throw std::runtime_error("hprlp_solver_transfer: null solver / output");
+    for (int i = 0; i < 4; ++i) out[i] = h->s.transfer[i];
+    return 0;
+    GUARD_END(-1)
+}
+
 // The value maps as the solver built them (built here if no hprlp_solver_set_matrix_values call has done it yet); mapA / mapAT
 // receive nnz ints each.  Returns nnz.
 extern "C" long hprlp_solver_value_maps(hprlp_solver *h, int *mapA, int *mapAT, long cap) {

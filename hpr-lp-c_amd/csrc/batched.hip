@@ -1709,32 +1709,6 @@ inline const int *data_flags_host(const BatchWS &w, int B) {
     return reinterpret_cast<const int *>(w.data_scal_h.p + static_cast<size_t>(DS_COUNT) * B);
 }
 
-// A pointer of the caller's passes only as device memory of `device` that the runtime knows, with room for `count` doubles where
-// the runtime reports the allocation's range.  Nothing is launched before every pointer of a call has passed.
-void check_device_pointer(const void *p, size_t count, int device, const char *name) {
-    const std::string who = std::string("batched solver: ") + name;
-    if (!p) throw std::runtime_error(who + " is null");
-    if (reinterpret_cast<uintptr_t>(p) % sizeof(double)) throw std::runtime_error(who + " is not aligned to 8 bytes");
-    hipPointerAttribute_t attr{};
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError();
-        throw std::runtime_error(who + " is not a pointer the HIP runtime knows (a host address?)");
-    }
-    if (attr.type != hipMemoryTypeDevice) throw std::runtime_error(who + " is not device memory");
-    if (attr.device != device)
-        throw std::runtime_error(who + " is memory of device " + std::to_string(attr.device) + ", the solver's is " + std::to_string(device));
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(p)) != hipSuccess || !base) {
-        (void)hipGetLastError();
-        return;  // (no range reported)
-    }
-    const char *end = static_cast<const char *>(base) + size;
-    if (static_cast<const char *>(p) + count * sizeof(double) > end)
-        throw std::runtime_error(who + " is too short: " + std::to_string(count) + " doubles wanted, " +
-                                 std::to_string((end - static_cast<const char *>(p)) / sizeof(double)) + " left in its allocation");
-}
-
 // prepare_batch on the device: the caller's vectors (ordered on `stream`) into the staging block in scaled units, its header, and
 // the per-member scalars on the host -- the BatchData a loop needs (it reads none of the vectors).  `in` gets the regions.
 BatchData device_prep(BatchWS &w, int B, int Bp, const double *C, const double *AL, const double *AU, const double *l, const double *u,
@@ -1790,6 +1764,33 @@ BatchData device_prep(BatchWS &w, int B, int Bp, const double *C, const double *
 }
 
 }  // namespace
+
+// A pointer of the caller's passes only as device memory of `device` that the runtime knows, with room for `count` doubles where
+// the runtime reports the allocation's range.  Nothing is launched before every pointer of a call has passed.
+// (declared in common.h: the resident solver's device entries check their pointers with it too)
+void check_device_pointer(const void *p, size_t count, int device, const char *name, const char *entry) {
+    const std::string who = std::string(entry) + ": " + name;
+    if (!p) throw std::runtime_error(who + " is null");
+    if (reinterpret_cast<uintptr_t>(p) % sizeof(double)) throw std::runtime_error(who + " is not aligned to 8 bytes");
+    hipPointerAttribute_t attr{};
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+        (void)hipGetLastError();
+        throw std::runtime_error(who + " is not a pointer the HIP runtime knows (a host address?)");
+    }
+    if (attr.type != hipMemoryTypeDevice) throw std::runtime_error(who + " is not device memory");
+    if (attr.device != device)
+        throw std::runtime_error(who + " is memory of device " + std::to_string(attr.device) + ", the solver's is " + std::to_string(device));
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(p)) != hipSuccess || !base) {
+        (void)hipGetLastError();
+        return;  // (no range reported)
+    }
+    const char *end = static_cast<const char *>(base) + size;
+    if (static_cast<const char *>(p) + count * sizeof(double) > end)
+        throw std::runtime_error(who + " is too short: " + std::to_string(count) + " doubles wanted, " +
+                                 std::to_string((end - static_cast<const char *>(p)) / sizeof(double)) + " left in its allocation");
+}
 
 // warm-up (abi.cpp: hprlp_warmup): an attribute query makes the runtime load this translation unit's code object now instead
 // of at the first launch of one of its kernels

@@ -198,6 +198,11 @@ struct HBuf {
     T &operator[](size_t i) { return p[i]; }
 };
 
+// A caller's device pointer (batched.hip; the device entries of the batched and of the resident solver): passes only as device
+// memory of `device` that the runtime knows, 8-byte aligned, with room for `count` doubles where the runtime reports the
+// allocation's range; throws otherwise, naming `entry: name`.  Launches nothing and moves no state.
+void check_device_pointer(const void *p, size_t count, int device, const char *name, const char *entry = "batched solver");
+
 // Host-side CSR transpose, stable in row order (reference src/utils.cu:203-232).
 void csr_transpose_host(int rows, int cols, long nnz, const int *rp, const int *ci, const double *v,
                         std::vector<int> &trp, std::vector<int> &tci, std::vector<double> &tv);

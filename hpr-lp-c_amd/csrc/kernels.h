@@ -306,6 +306,26 @@ void launch_unscale(int n, int m, const double *x_bar, const double *y_bar, cons
                     const double *col_norm, const double *row_norm, double b_scale, double c_scale, double *xo,
                     double *yo, double *zo, hipStream_t s);
 
+// ---- device-resident re-solve (DESIGN.md "Device-resident re-solve"): the caller's device buffers in, the caller's buffers out ----
+// k_unscale_out: k_unscale's three operations in its order, on its grid and element-to-thread map, stored into the caller's
+// buffers in the caller's numbering: xo[pc[j]], zo[pc[j]], yo[pr[i]] (pc / pr: device index -> caller's index, null: no locality
+// ordering).  A null output is skipped.
+void launch_unscale_out(int n, int m, const double *x_bar, const double *y_bar, const double *z_bar, const double *col_norm,
+                        const double *row_norm, double b_scale, double c_scale, const int *pc, const int *pr, double *xo, double *yo,
+                        double *zo, hipStream_t s);
+// k_data_check: one grid-stride pass over up to kDataCheckVecs caller vectors (null / length 0: skipped).  *first_bad, which the
+// caller sets to kDataCheckClean before the launch, receives the smallest (vector << kDataCheckShift) | index whose entry is NaN
+// (non_finite = 0) or not finite (non_finite = 1: the warm start's rule).
+constexpr int kDataCheckVecs = 5;
+constexpr int kDataCheckShift = 56;
+constexpr unsigned long long kDataCheckClean = ~0ULL;
+struct DataCheckArgs {
+    const double *v[kDataCheckVecs];
+    int len[kDataCheckVecs];
+    int non_finite;
+};
+void launch_data_check(const DataCheckArgs &a, unsigned long long *first_bad, hipStream_t s);
+
 // ---- small-LP path (small.hip): `count` normal iterations in one single-workgroup launch -----------
 constexpr int kSmallMaxK = 12;     // matrix entries per thread (1024 threads) -> nnz <= 12288
 constexpr int kSmallMaxR = 2;      // rows per thread -> m, n <= 2048

@@ -2857,6 +2857,62 @@ void launch_unscale(int n, int m, const double *x_bar, const double *y_bar, cons
                        col_norm, row_norm, b_scale, c_scale, xo, yo, zo);
 }
 
+// Device-resident re-solve (DESIGN.md "Device-resident re-solve").  k_unscale with the caller's buffers as its outputs: the same
+// grid, the same element-to-thread map and the same three operations in the same order, so every stored number is the one
+// k_unscale leaves in scratch for the host entry.  The loads of the solver's arrays (and of pc / pr) are coalesced; the store
+// goes to the caller's index, which under a locality ordering is a scatter -- what the host entry does one element at a time
+// after its download.  xo / yo / zo null: that output is not wanted.
+__global__ void __launch_bounds__(kThreads) k_unscale_out(int n, int m, const double *__restrict__ x_bar, const double *__restrict__ y_bar,
+                                                         const double *__restrict__ z_bar, const double *__restrict__ col_norm,
+                                                         const double *__restrict__ row_norm, double b_scale, double c_scale,
+                                                         const int *__restrict__ pc, const int *__restrict__ pr, double *xo, double *yo,
+                                                         double *zo) {
+    const int tid = blockIdx.x * kThreads + threadIdx.x, nth = gridDim.x * kThreads;
+    if (xo || zo) {
+        for (int i = tid; i < n; i += nth) {
+            const int dst = pc ? pc[i] : i;
+            const double cn = col_norm[i];
+            if (xo) xo[dst] = (x_bar[i] / cn) * b_scale;
+            if (zo) zo[dst] = (z_bar[i] * cn) * c_scale;
+        }
+    }
+    if (yo) {
+        for (int i = tid; i < m; i += nth) yo[pr ? pr[i] : i] = (y_bar[i] / row_norm[i]) * c_scale;
+    }
+}
+void launch_unscale_out(int n, int m, const double *x_bar, const double *y_bar, const double *z_bar, const double *col_norm,
+                        const double *row_norm, double b_scale, double c_scale, const int *pc, const int *pr, double *xo, double *yo,
+                        double *zo, hipStream_t s) {
+    hipLaunchKernelGGL(k_unscale_out, dim3(vec_grid(n > m ? n : m)), dim3(kThreads), 0, s, n, m, x_bar, y_bar, z_bar, col_norm,
+                       row_norm, b_scale, c_scale, pc, pr, xo, yo, zo);
+}
+
+// The caller's vectors are checked where they lie, before any kernel that writes what the solver reads: the smallest
+// (vector, index) of a NaN -- or, for a warm start, of any non-finite entry -- by atomicMin on a word that starts at all ones
+// (k_values_check's rule).  A lane walks each vector in ascending positions and the vectors in order, so its first hit is its
+// smallest; it then stops.
+__global__ void __launch_bounds__(kThreads) k_data_check(DataCheckArgs a, unsigned long long *__restrict__ first_bad) {
+    const int tid = blockIdx.x * kThreads + threadIdx.x, nth = gridDim.x * kThreads;
+    unsigned long long mine = kDataCheckClean;
+#pragma unroll
+    for (int k = 0; k < kDataCheckVecs; ++k) {
+        const double *__restrict__ v = a.v[k];
+        const int len = v ? a.len[k] : 0;
+        for (int i = tid; i < len && mine == kDataCheckClean; i += nth) {
+            const double e = v[i];
+            if (a.non_finite ? !isfinite(e) : isnan(e)) mine = (static_cast<unsigned long long>(k) << kDataCheckShift) | static_cast<unsigned long long>(i);
+        }
+    }
+    if (mine != kDataCheckClean) atomicMin(first_bad, mine);
+}
+void launch_data_check(const DataCheckArgs &a, unsigned long long *first_bad, hipStream_t s) {
+    int longest = 0;
+    for (int k = 0; k < kDataCheckVecs; ++k)
+        if (a.v[k] && a.len[k] > longest) longest = a.len[k];
+    if (longest <= 0) return;
+    hipLaunchKernelGGL(k_data_check, dim3(vec_grid(longest)), dim3(kThreads), 0, s, a, first_bad);
+}
+
 // ------------------------------------------------------------------------------------------------
 // multi-GPU neighbour exchange (HaloPlan, solver.h): the index lists are sorted, so both kernels walk
 // the big vector monotonically

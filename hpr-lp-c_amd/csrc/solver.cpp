@@ -599,6 +599,7 @@ Solver::~Solver() {
     if (ev_ready) (void)hipEventDestroy(ev_ready);
     if (ev_done_x) (void)hipEventDestroy(ev_done_x);
     if (ev_done_y) (void)hipEventDestroy(ev_done_y);
+    if (inputs_ready) (void)hipEventDestroy(inputs_ready);
     if (comm_stream) (void)hipStreamDestroy(comm_stream);
     if (stream && !arena) (void)hipStreamDestroy(stream);
     // (the buffers taken from the arena are not given back one by one: DBuf::release leaves them alone; the last member frees the blocks)
@@ -2203,7 +2204,14 @@ void Solver::set_start(const double *x0, const double *y0) {
         dpr.alloc(perm_r.size());
         HIP_CHECK(hipMemcpyAsync(dpr.p, perm_r.data(), sizeof(int) * perm_r.size(), hipMemcpyHostToDevice, stream));
     }
-    const StartInArgs a{n_loc, m_loc, dx.p, dy.p, dpc.p, dpr.p, l.p, u.p, col_norm.p, AL.p, AU.p, row_norm.p, b_scale, c_scale,
+    start_apply(dx.p, dy.p, dpc.p, dpr.p);  // (waits for the stream: the uploads' buffers go out of scope here)
+    start_time = time_since(t0);
+}
+
+// The kernels of a warm start, on device copies of the caller's vectors (caller's numbering; dpc / dpr: device index -> caller's
+// index, null without a locality ordering).  Returns after the stream has drained: dx / dy are not read afterwards.
+void Solver::start_apply(const double *dx, const double *dy, const int *dpc, const int *dpr) {
+    const StartInArgs a{n_loc, m_loc, dx, dy, dpc, dpr, l.p, u.p, col_norm.p, AL.p, AU.p, row_norm.p, b_scale, c_scale,
                         x.p, last_x.p, x_hat, x_bar, y, last_y.p, y_bar};
     launch_start_in(a, stream);
     // (one GPU: x_hat, x_bar, y, y_bar are the gathered buffers themselves)
@@ -2215,8 +2223,7 @@ void Solver::set_start(const double *x0, const double *y0) {
     f.item[f.n++] = {part_x.p + gx, gx, S_XZ};
     f.item[f.n++] = {part_r.p, gyy, S_YOBJ_Y};
     launch_finalize(f, scal.p, stream);
-    HIP_CHECK(hipStreamSynchronize(stream));  // (the uploads' buffers go out of scope here)
-    start_time = time_since(t0);
+    HIP_CHECK(hipStreamSynchronize(stream));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2238,7 +2245,10 @@ void Solver::set_data(const double *c_, const double *obj_constant_, const doubl
     if (obj_constant_ && std::isnan(*obj_constant_)) throw std::runtime_error("set_data: obj_constant is NaN");
     data_time[0] = data_time[1] = data_time[2] = 0.0;
     if (obj_constant_) obj_constant = *obj_constant_;
-    if (!c_ && !bounds) return;
+    if (!c_ && !bounds) {
+        set_transfer(0, 0, false);
+        return;
+    }
     const auto t0 = time_now();
     const int mb = bounds ? m_loc : 0, nb = bounds ? n_loc : 0, nc = c_ ? n_loc : 0;
     // staging: [AL | AU | l | u | c]; below the allocator cache's block size the solver keeps it (a hipFree per call would
@@ -2256,12 +2266,17 @@ void Solver::set_data(const double *c_, const double *obj_constant_, const doubl
         for (const auto &q : parts)
             if (q.len > 0) HIP_CHECK(hipMemcpyAsync(q.dst, q.src, sizeof(double) * q.len, hipMemcpyHostToDevice, stream));
     }
-    if (!perm_r.empty() && !perm_r_dev.p) {
-        perm_r_dev.alloc(perm_r.size());
-        perm_c_dev.alloc(perm_c.size());
-        HIP_CHECK(hipMemcpyAsync(perm_r_dev.p, perm_r.data(), sizeof(int) * perm_r.size(), hipMemcpyHostToDevice, stream));
-        HIP_CHECK(hipMemcpyAsync(perm_c_dev.p, perm_c.data(), sizeof(int) * perm_c.size(), hipMemcpyHostToDevice, stream));
-    }
+    data_apply(dAL, dAU, dl, du, c_ ? dc : nullptr, bounds, t0);
+    set_transfer(total, 0, false);
+}
+
+// set_data from the point where the caller's vectors can be read on the device (the staging block, or the caller's own device
+// buffers): k_data_in, k_data_bc, the finalizes, one scalar fetch.  dc null: c not given; bounds false: dAL .. du not read.
+void Solver::data_apply(const double *dAL, const double *dAU, const double *dl, const double *du, const double *dc, bool bounds,
+                        clock_type::time_point t0) {
+    const bool c_ = dc != nullptr;
+    const int mb = bounds ? m_loc : 0, nb = bounds ? n_loc : 0, nc = c_ ? n_loc : 0;
+    perms_to_device();
     if (!data_part.p) data_part.alloc_zero(static_cast<size_t>(4) * kReduceBlocks);
     // The bound codes are written by the second pass into the arrays the iteration kernels (and the captured iteration graphs, by
     // pointer) already read.  The graphs hold nothing else of the data: XHalfArgs / YHalfArgs carry pointers, strides and the
@@ -2332,6 +2347,142 @@ void Solver::resolve(double sigma_, const double *x0, const double *y0, HPRLP_re
     }
     time_base = -1.0;
     collect_solution(out);
+    set_transfer((x0 ? n_loc : 0) + static_cast<size_t>(y0 ? m_loc : 0), 2 * static_cast<size_t>(n_loc) + m_loc, false);
+}
+
+// ------------------------------------------------------------------------------------------------
+// device-resident re-solve (DESIGN.md "Device-resident re-solve"): the entries above with the caller's vectors in device memory.
+// The kernels are the host entries'; their sources are the caller's pointers where the host entries pass the staging block.
+// ------------------------------------------------------------------------------------------------
+void Solver::perms_to_device() {
+    if (perm_r.empty() || perm_r_dev.p) return;
+    perm_r_dev.alloc(perm_r.size());
+    perm_c_dev.alloc(perm_c.size());
+    HIP_CHECK(hipMemcpyAsync(perm_r_dev.p, perm_r.data(), sizeof(int) * perm_r.size(), hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemcpyAsync(perm_c_dev.p, perm_c.data(), sizeof(int) * perm_c.size(), hipMemcpyHostToDevice, stream));
+}
+
+void Solver::wait_for_caller(hipStream_t caller) {
+    if (!inputs_ready) HIP_CHECK(hipEventCreateWithFlags(&inputs_ready, hipEventDisableTiming));
+    HIP_CHECK(hipEventRecord(inputs_ready, caller));
+    HIP_CHECK(hipStreamWaitEvent(stream, inputs_ready, 0));
+}
+
+unsigned long long *Solver::cleared_check_flags() {
+    if (!check_flags.p) check_flags.alloc(2);
+    HIP_CHECK(hipMemsetAsync(check_flags.p, 0xff, 2 * sizeof(unsigned long long), stream));
+    return check_flags.p;
+}
+
+void Solver::set_transfer(size_t h2d_words, size_t d2h_words, bool device_entry) {
+    transfer[0] = static_cast<long>(h2d_words * sizeof(double));
+    transfer[1] = static_cast<long>(d2h_words * sizeof(double));
+    transfer[2] = device_entry ? 1 : 0;
+    if (device_entry) ++transfer[3];
+}
+
+namespace {
+// k_data_check's word as the host entries' message: "<who>: <vector>[<index>] <what>"
+void throw_if_flagged(unsigned long long word, const char *const names[kDataCheckVecs], const char *who, const char *what) {
+    if (word == kDataCheckClean) return;
+    const int k = static_cast<int>(word >> kDataCheckShift);
+    const unsigned long long i = word & ((1ULL << kDataCheckShift) - 1);
+    throw std::runtime_error(std::string(who) + ": " + (k < kDataCheckVecs ? names[k] : "?") + "[" + std::to_string(i) + "] " + what);
+}
+const char *const kDataNames[kDataCheckVecs] = {"c", "AL", "AU", "l", "u"};
+const char *const kStartNames[kDataCheckVecs] = {"x0", "y0", "", "", ""};
+}  // namespace
+
+void Solver::set_data_device(const double *dc, const double *obj_constant_, const double *dAL, const double *dAU, const double *dl,
+                             const double *du, hipStream_t caller) {
+    if (comm) throw std::runtime_error("new data for a resident model runs on one GPU only (sharded solver)");
+    if (!scaled) throw std::runtime_error("set_data: the solver has not been scaled yet (hprlp_solver_scale comes first)");
+    const bool bounds = dAL || dAU || dl || du;
+    if (bounds && !(dAL && dAU && dl && du))
+        throw std::runtime_error("set_data: AL, AU, l and u are given together or not at all (b_scale couples them)");
+    if (obj_constant_ && std::isnan(*obj_constant_)) throw std::runtime_error("set_data: obj_constant is NaN");
+    const auto t0 = time_now();
+    // -- no pointer reaches a kernel before all of them have passed
+    const char *who = "set_data_device";
+    if (dc) check_device_pointer(dc, static_cast<size_t>(n_loc), prm.device_number, "c", who);
+    if (bounds) {
+        check_device_pointer(dAL, static_cast<size_t>(m_loc), prm.device_number, "AL", who);
+        check_device_pointer(dAU, static_cast<size_t>(m_loc), prm.device_number, "AU", who);
+        check_device_pointer(dl, static_cast<size_t>(n_loc), prm.device_number, "l", who);
+        check_device_pointer(du, static_cast<size_t>(n_loc), prm.device_number, "u", who);
+    }
+    if (dc || bounds) {
+        const double t_ptr = time_since(t0);
+        wait_for_caller(caller);
+        const double t_ev = time_since(t0);
+        unsigned long long *flag = cleared_check_flags();
+        const DataCheckArgs chk{{dc, dAL, dAU, dl, du}, {n_loc, m_loc, m_loc, n_loc, n_loc}, 0};
+        launch_data_check(chk, flag, stream);
+        unsigned long long first_bad = kDataCheckClean;
+        HIP_CHECK(hipMemcpyAsync(&first_bad, flag, sizeof(first_bad), hipMemcpyDeviceToHost, stream));
+        const double t_enq = time_since(t0);
+        HIP_CHECK(hipStreamSynchronize(stream));
+        if (env_get("HPRLP_TIMING"))
+            std::cerr << "[timing] set_data_device: pointer checks " << t_ptr << " s, event " << t_ev - t_ptr << " s, check enqueued "
+                      << t_enq - t_ev << " s, wait " << time_since(t0) - t_enq << " s" << std::endl;
+        throw_if_flagged(first_bad, kDataNames, "set_data", "is NaN");
+    }
+    // -- from here on the call goes through
+    data_time[0] = data_time[1] = data_time[2] = 0.0;
+    if (obj_constant_) obj_constant = *obj_constant_;
+    if (dc || bounds) {
+        data_apply(dAL, dAU, dl, du, dc, bounds, t0);  // (ends with the scalar fetch: the stream has drained)
+    }
+    set_transfer(0, 0, true);
+}
+
+void Solver::resolve_device(double sigma_, const double *dx0, const double *dy0, hipStream_t caller, double *dx, double *dy, double *dz,
+                            HPRLP_results *out) {
+    if (comm) throw std::runtime_error("re-solve runs on one GPU only (sharded solver)");
+    const char *who = "resolve_device";
+    if (dx0) check_device_pointer(dx0, static_cast<size_t>(n_loc), prm.device_number, "x0", who);
+    if (dy0) check_device_pointer(dy0, static_cast<size_t>(m_loc), prm.device_number, "y0", who);
+    if (dx) check_device_pointer(dx, static_cast<size_t>(n_loc), prm.device_number, "x", who);
+    if (dy) check_device_pointer(dy, static_cast<size_t>(m_loc), prm.device_number, "y", who);
+    if (dz) check_device_pointer(dz, static_cast<size_t>(n_loc), prm.device_number, "z", who);
+    wait_for_caller(caller);  // (the outputs too: what the caller's stream still does with them comes first)
+    if (dx0 || dy0) {
+        unsigned long long *flag = cleared_check_flags();
+        const DataCheckArgs chk{{dx0, dy0, nullptr, nullptr, nullptr}, {n_loc, m_loc, 0, 0, 0}, 1};
+        launch_data_check(chk, flag, stream);
+        unsigned long long first_bad = kDataCheckClean;
+        HIP_CHECK(hipMemcpyAsync(&first_bad, flag, sizeof(first_bad), hipMemcpyDeviceToHost, stream));
+        HIP_CHECK(hipStreamSynchronize(stream));
+        throw_if_flagged(first_bad, kStartNames, "warm start", "is not finite");
+    }
+    reset_iterates();
+    init_iteration_state();
+    if (sigma_ > 0.0) set_sigma_lambda(sigma_, lambda_max, true);
+    if (dx0 || dy0) {  // set_start with the caller's buffers where it uploads copies; consumed here, so dx / dy may be the same buffers
+        if (y_exchange_pending) throw std::runtime_error("set_start: an exchange is still pending");
+        const auto t0 = time_now();
+        finish_tiling();
+        invalidate_far();
+        perms_to_device();
+        start_apply(dx0, dy0, dx0 ? perm_c_dev.p : nullptr, dy0 ? perm_r_dev.p : nullptr);
+        start_time = time_since(t0);
+    }
+    time_base = data_since_run;
+    try {
+        solve_loop(out);
+    } catch (...) {
+        time_base = -1.0;
+        throw;
+    }
+    time_base = -1.0;
+    out->x = out->y = out->z = nullptr;
+    if (dx || dy || dz) {
+        perms_to_device();
+        launch_unscale_out(n_loc, m_loc, x_bar, y_bar, z_bar.p, col_norm.p, row_norm.p, b_scale, c_scale, perm_c_dev.p, perm_r_dev.p, dx, dy,
+                           dz, stream);
+    }
+    HIP_CHECK(hipStreamSynchronize(stream));
+    set_transfer(0, 0, true);
 }
 
 }  // namespace hprlp

@@ -229,6 +229,25 @@ struct Solver {
     double matrix_time[5] = {0.0, 0.0, 0.0, 0.0, 0.0};  // the last call: maps (first call only), upload, kernels, scale(), total
     long matrix_calls = 0;
 
+    // Device-resident re-solve (DESIGN.md "Device-resident re-solve"): set_data, resolve and set_matrix_values with the caller's
+    // vectors in DEVICE memory (caller's units and numbering) and the solution written into the caller's device buffers.  The
+    // kernels of the host entries read the caller's pointers in the staging block's place, so the bits are the host entries'.
+    // Every device pointer passes check_device_pointer before anything is launched; `caller` is the stream the inputs were
+    // produced on (the solver's stream waits for an event recorded on it), and the solver's stream has drained on return.  A NaN
+    // (a non-finite entry of a start) is found by k_data_check before anything the solver reads is written.
+    void set_data_device(const double *dc, const double *obj_constant_, const double *dAL, const double *dAU, const double *dl,
+                         const double *du, hipStream_t caller);
+    // dx0 / dy0 null: cold; dx, dz (n) / dy (m) null: not wanted; dx may be dx0 and dy may be dy0.  out->x / y / z stay null.
+    void resolve_device(double sigma_, const double *dx0, const double *dy0, hipStream_t caller, double *dx, double *dy, double *dz,
+                        HPRLP_results *out);
+    void set_matrix_values_device(const double *dval, long nnz, const double *dc, const double *obj_constant_, const double *dAL,
+                                  const double *dAU, const double *dl, const double *du, hipStream_t caller);
+    // The last successful set_data* / set_matrix_values* / resolve*: bytes of model data and solution host -> device, device ->
+    // host, 1 for a device entry, device-entry calls so far.
+    long transfer[4] = {0, 0, 0, 0};
+    hipEvent_t inputs_ready = nullptr;       // recorded on the caller's stream, waited for by `stream`
+    DBuf<unsigned long long> check_flags;    // k_data_check's word and k_values_check's, fetched together
+
     std::map<int, hipGraphExec_t> graphs;
     TraceRow *trace = nullptr;
     int trace_cap = 0, trace_n = 0;
@@ -333,6 +352,16 @@ struct Solver {
     int x_mode_of(int i, int count) const;
 
    private:
+    // What the host and the device entries share: everything after the caller's vectors are readable on the device.
+    void data_apply(const double *dAL, const double *dAU, const double *dl, const double *du, const double *dc, bool bounds,
+                    clock_type::time_point t0);
+    void start_apply(const double *dx, const double *dy, const int *dpc, const int *dpr);
+    void values_apply(const double *dval, long nnz, const double *dAL, const double *dAU, const double *dl, const double *du,
+                      const double *dc, const double *obj_constant_, clock_type::time_point t0, double times[5]);
+    void perms_to_device();                                                   // perm_r_dev / perm_c_dev, first use
+    void wait_for_caller(hipStream_t caller);                                 // event on `caller`, `stream` waits for it
+    unsigned long long *cleared_check_flags();                                // two words of all ones
+    void set_transfer(size_t h2d_words, size_t d2h_words, bool device_entry);
     void alloc_work();
     hipGraphExec_t graph_for(int len);
 };

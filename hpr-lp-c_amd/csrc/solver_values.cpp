@@ -125,6 +125,14 @@ void Solver::set_matrix_values(const double *val, long nnz, const double *c_, co
     if (first_bad != kValuesAllFinite)
         throw std::runtime_error("set_matrix_values: val[" + std::to_string(first_bad) + "] is not finite");
     // -- from here on the call goes through
+    values_apply(dval, nnz, dAL, dAU, dl, du, dc, obj_constant_, t0, times);
+    set_transfer(total, 0, false);
+}
+
+// set_matrix_values from the point where the values and the vectors have been checked where they lie on the device (the staging
+// block, or the caller's own buffers): the scatter through the value maps, the gather of the vectors, iterates to zero, scale().
+void Solver::values_apply(const double *dval, long nnz, const double *dAL, const double *dAU, const double *dl, const double *du,
+                          const double *dc, const double *obj_constant_, clock_type::time_point t0, double times[5]) {
     const auto t_k = time_now();
     launch_values_in(nnz, dval, map_A.p, map_AT.p, A.val.p, AT.val.p, stream);
     const VectorsInArgs vin{m_loc, n_loc, dAL, dAU, dl, du, dc, perm_r_dev.p, perm_c_dev.p, AL.p, AU.p, l.p, u.p, c.p};
@@ -141,6 +149,59 @@ void Solver::set_matrix_values(const double *val, long nnz, const double *c_, co
     for (int i = 0; i < 5; ++i) matrix_time[i] = times[i];
     ++matrix_calls;
     data_since_run += times[4];
+}
+
+// The device entry (DESIGN.md "Device-resident re-solve"): the caller's device buffers take the staging block's place.
+void Solver::set_matrix_values_device(const double *dval, long nnz, const double *dc, const double *obj_constant_, const double *dAL,
+                                      const double *dAU, const double *dl, const double *du, hipStream_t caller) {
+    if (comm) throw std::runtime_error("set_matrix_values: new matrix values for a resident model run on one GPU only (sharded solver)");
+    if (!scaled) throw std::runtime_error("set_matrix_values: the solver has not been scaled yet (hprlp_solver_scale comes first)");
+    if (!dval || !dc || !dAL || !dAU || !dl || !du)
+        throw std::runtime_error("set_matrix_values: val, c, AL, AU, l and u are all required (every scaled vector depends on the values)");
+    if (nnz != static_cast<long>(A.view.nnz))
+        throw std::runtime_error("set_matrix_values: nnz is " + std::to_string(nnz) + ", the model has " + std::to_string(A.view.nnz) +
+                                 " entries (the pattern cannot change)");
+    if (obj_constant_ && std::isnan(*obj_constant_)) throw std::runtime_error("set_matrix_values: obj_constant is NaN");
+    // -- no pointer reaches a kernel before all of them have passed
+    const auto t_ptr = time_now();
+    const char *who = "set_matrix_values_device";
+    check_device_pointer(dval, static_cast<size_t>(nnz), prm.device_number, "val", who);
+    check_device_pointer(dc, static_cast<size_t>(n), prm.device_number, "c", who);
+    check_device_pointer(dAL, static_cast<size_t>(m), prm.device_number, "AL", who);
+    check_device_pointer(dAU, static_cast<size_t>(m), prm.device_number, "AU", who);
+    check_device_pointer(dl, static_cast<size_t>(n), prm.device_number, "l", who);
+    check_device_pointer(du, static_cast<size_t>(n), prm.device_number, "u", who);
+    const double ptr_seconds = time_since(t_ptr);
+    const auto t0 = time_now();
+    double times[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    if (!have_maps) {
+        build_value_maps();
+        times[0] = time_since(t0);
+    }
+    const auto t_up = time_now();
+    wait_for_caller(caller);
+    perms_to_device();
+    // nothing the solver reads has been written yet: values and vectors are checked where they are, both words in one fetch
+    unsigned long long *flags = cleared_check_flags();
+    const DataCheckArgs chk{{dc, dAL, dAU, dl, du}, {n, m, m, n, n}, 0};
+    launch_data_check(chk, flags, stream);
+    launch_values_check(dval, nnz, flags + 1, stream);
+    unsigned long long first_bad[2] = {kDataCheckClean, kValuesAllFinite};
+    HIP_CHECK(hipMemcpyAsync(first_bad, flags, sizeof(first_bad), hipMemcpyDeviceToHost, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    times[1] = ptr_seconds + time_since(t_up);
+    if (first_bad[0] != kDataCheckClean) {
+        const char *const names[kDataCheckVecs] = {"c", "AL", "AU", "l", "u"};
+        const int k = static_cast<int>(first_bad[0] >> kDataCheckShift);
+        throw std::runtime_error(std::string("set_matrix_values: ") + (k < kDataCheckVecs ? names[k] : "?") + "[" +
+                                 std::to_string(first_bad[0] & ((1ULL << kDataCheckShift) - 1)) + "] is NaN");
+    }
+    if (first_bad[1] != kValuesAllFinite)
+        throw std::runtime_error("set_matrix_values: val[" + std::to_string(first_bad[1]) + "] is not finite");
+    // -- from here on the call goes through
+    values_apply(dval, nnz, dAL, dAU, dl, du, dc, obj_constant_, t0, times);
+    HIP_CHECK(hipStreamSynchronize(stream));  // (the caller's buffers are not read after the return)
+    set_transfer(0, 0, true);
 }
 
 }  // namespace hprlp

@@ -206,6 +206,13 @@ def lib():
     L.hprlp_solver_data_seconds.argtypes = [C.c_void_p, c_dbl_p]
     L.hprlp_solver_set_matrix_values.argtypes = [C.c_void_p, c_dbl_p, C.c_long] + [c_dbl_p] * 6
     L.hprlp_solver_matrix_seconds.argtypes = [C.c_void_p, c_dbl_p]
+    if hasattr(L, "hprlp_solver_transfer"):  # (HPRLP_LIB may name a build of an earlier commit)
+        # device arrays travel as addresses (c_void_p), host arrays as before
+        L.hprlp_solver_set_data_device.argtypes = [C.c_void_p, C.c_void_p, c_dbl_p] + [C.c_void_p] * 5
+        L.hprlp_solver_resolve_device.argtypes = [C.c_void_p, C.c_double] + [C.c_void_p] * 6 + \
+            [C.POINTER(CResults), C.POINTER(CTraceRow), C.c_int, c_int_p]
+        L.hprlp_solver_set_matrix_values_device.argtypes = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, c_dbl_p] + [C.c_void_p] * 5
+        L.hprlp_solver_transfer.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
     L.hprlp_solver_value_maps.restype = C.c_long
     L.hprlp_solver_value_maps.argtypes = [C.c_void_p, c_int_p, c_int_p, C.c_long]
     L.hprlp_solver_ordering.argtypes = [C.c_void_p, c_int_p, c_int_p]
@@ -955,6 +962,7 @@ class Solver:
     def __init__(self, model, param=None):
         cp = (param or Parameters()).to_c()
         self.model = model
+        self.device_number = int(cp.device_number)
         self.h = lib().hprlp_solver_create(model._ptr, C.byref(cp))
         if not self.h:
             raise RuntimeError("hprlp_solver_create failed: " + last_error())
@@ -976,6 +984,7 @@ class Solver:
                 continue
             sv = cls.__new__(cls)
             sv.model = mod
+            sv.device_number = int(cp.device_number)
             sv.h = hs[k]
             out.append(sv)
         return out
@@ -1368,6 +1377,83 @@ class Solver:
         d = dict(zip(("maps", "upload", "kernels", "scale", "total"), out[:5]))
         d["calls"] = int(out[5])
         return d
+
+    # ---- device-resident re-solve (DESIGN.md "Device-resident re-solve"): torch tensors in, torch tensors out ----------------------
+    def _tensor(self, t, length, name, who):
+        """A caller's tensor as contiguous device memory of `length` doubles: (what keeps it alive, its address)."""
+        import torch
+        if t is None:
+            return None, None
+        dev = getattr(self, "device_number", 0)
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{who}: {name} must be a torch tensor, got {type(t).__name__}")
+        if t.dtype != torch.float64:
+            raise ValueError(f"{who}: {name} must be float64, got {t.dtype}")
+        if t.device.type != "cuda" or t.device.index != dev:
+            raise ValueError(f"{who}: {name} must be on the solver's device cuda:{dev}, got {t.device}")
+        if t.dim() != 1 or t.shape[0] != length:
+            raise ValueError(f"{who}: {name} must have length {length}, got shape {tuple(t.shape)}")
+        if not t.is_contiguous():
+            t = t.contiguous()
+        return t, t.data_ptr()
+
+    def _torch_stream(self):
+        import torch
+        return torch.cuda.current_stream(torch.device("cuda", getattr(self, "device_number", 0))).cuda_stream
+
+    def set_data_tensors(self, c=None, obj_constant=None, AL=None, AU=None, l=None, u=None):
+        """set_data() for vectors that are on the GPU already (hprlp_solver_set_data_device): float64 torch tensors on the solver's
+        device, 1-D, taken as ordered on the current torch stream.  A contiguous tensor is passed as it is, any other layout costs
+        one copy on the device.  ValueError for a wrong type, dtype, device or length, before the library is called; RuntimeError
+        with the library's message for a call it refuses, which leaves the solver as it was.  Same bits as set_data()."""
+        m, n = self.model.m, self.model.n
+        keep = [self._tensor(t, length, name, "set_data_tensors")
+                for t, length, name in ((c, n, "c"), (AL, m, "AL"), (AU, m, "AU"), (l, n, "l"), (u, n, "u"))]
+        oc = None if obj_constant is None else C.byref(C.c_double(float(obj_constant)))
+        p = [a for _, a in keep]
+        self._chk(lib().hprlp_solver_set_data_device(self.h, p[0], oc, p[1], p[2], p[3], p[4], self._torch_stream()))
+
+    def resolve_tensors(self, x=None, y=None, sigma=-1.0, max_trace=4096):
+        """resolve() from a start on the GPU, or cold, with the solution left on the GPU (hprlp_solver_resolve_device).  Returns
+        the Results of resolve() with x, y, z as fresh float64 tensors on the solver's device; scalars and trace as from resolve()."""
+        import torch
+        m, n = self.model.m, self.model.n
+        xs, ys = self._tensor(x, n, "x", "resolve_tensors"), self._tensor(y, m, "y", "resolve_tensors")
+        device = torch.device("cuda", getattr(self, "device_number", 0))
+        xo, yo, zo = (torch.empty(k, dtype=torch.float64, device=device) for k in (n, m, n))
+        res = CResults()
+        trace = (CTraceRow * max_trace)()
+        nt = C.c_int(0)
+        self._chk(lib().hprlp_solver_resolve_device(self.h, float(sigma), xs[1], ys[1], self._torch_stream(), xo.data_ptr(), yo.data_ptr(),
+                                                    zo.data_ptr(), C.byref(res), trace, max_trace, C.byref(nt)))
+        r = Results(res, m, n)  # (x, y, z of the C struct are NULL)
+        r.x, r.y, r.z = xo, yo, zo
+        r.trace = [{f: getattr(trace[i], f) for f, _ in CTraceRow._fields_} for i in range(nt.value)]
+        return r
+
+    def set_matrix_tensors(self, values, c, AL, AU, l, u, obj_constant=None):
+        """set_matrix() for values and vectors that are on the GPU already (hprlp_solver_set_matrix_values_device), then
+        power_iteration() and init(-1, 1.01 lambda) as there.  Returns (lambda, power iterations).  Same bits as set_matrix()."""
+        m, n = self.model.m, self.model.n
+        nnz = self.model.nnz if hasattr(self.model, "nnz") else self.info()["nnz"]
+        keep = []
+        for t, length, name in ((values, nnz, "values"), (c, n, "c"), (AL, m, "AL"), (AU, m, "AU"), (l, n, "l"), (u, n, "u")):
+            if t is None:
+                raise ValueError(f"set_matrix_tensors: {name} is required (length {length})")
+            keep.append(self._tensor(t, length, name, "set_matrix_tensors"))
+        oc = None if obj_constant is None else C.byref(C.c_double(float(obj_constant)))
+        p = [a for _, a in keep]
+        self._chk(lib().hprlp_solver_set_matrix_values_device(self.h, p[0], nnz, p[1], oc, p[2], p[3], p[4], p[5], self._torch_stream()))
+        lam, its = self.power_iteration()
+        self.init(-1.0, 1.01 * lam)
+        return lam, its
+
+    def transfer(self):
+        """The last successful set_data* / set_matrix* / resolve* call's traffic of model data and solution in bytes, host to
+        device and back (not the loop's scalar fetches), whether it was a *_tensors call, and how many of those there have been."""
+        out = (C.c_long * 4)()
+        self._chk(lib().hprlp_solver_transfer(self.h, out))
+        return dict(zip(("h2d_bytes", "d2h_bytes", "device_entry", "device_calls"), [int(v) for v in out]))
 
     def value_maps(self):
         """(mapA, mapAT) as the solver built them (hprlp_solver_value_maps): the model's CSR position of every entry of A and of

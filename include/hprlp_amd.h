@@ -259,6 +259,42 @@ int hprlp_solver_set_matrix_values(hprlp_solver *s, const double *val, long nnz,
 /* the last successful call: {map construction (first call only, else 0), upload + check, value + vector kernels, scale(), total,
  *                            calls so far} */
 int hprlp_solver_matrix_seconds(hprlp_solver *s, double out[6]);
+
+/* ---- device-resident re-solve: tensors in, tensors out (one GPU; DESIGN.md "Device-resident re-solve") --------------------------
+ * hprlp_solver_set_data, hprlp_solver_resolve and hprlp_solver_set_matrix_values with the vectors already in device memory and
+ * the solution wanted there.  The d* arguments are DEVICE arrays in the caller's units and numbering (dc, dl, du, dx0, dx, dz: n;
+ * dAL, dAU, dy0, dy: m; dval: nnz); obj_constant, out, trace and n_trace are host memory.  Semantics are those of the host
+ * entries, argument for argument: the groups of set_data (dc and / or obj_constant; dAL, dAU, dl, du together or not at all), all
+ * six arrays for the matrix values, sigma <= 0 for the norm rule, NULL starts for a cold re-solve; detection, trace, out->time and
+ * hprlp_solver_data_seconds / hprlp_solver_matrix_seconds as there ("upload" holds the pointer checks and the device check).
+ *   Results: dx, dz and dy receive the solution in the caller's units and numbering; any of the three may be NULL (not wanted).
+ * out->x, out->y, out->z are NULL (hprlp_free_results stays legal), every scalar field of out is filled as by hprlp_solver_resolve.
+ * dx may be the same buffer as dx0 and dy the same as dy0: the start is consumed before the loop and the results are written
+ * after it -- what a loop that carries one solve's x and y into the next wants.
+ *   Pointers: before anything is launched every non-NULL device pointer is looked up.  It passes only as device memory of the
+ * solver's device, 8-byte aligned and, where the runtime reports the allocation's range, with room for its length; a host
+ * address, another device's or managed memory, a short buffer or an address the runtime does not know is refused.
+ *   Ordering: `stream` is the hipStream_t (NULL: the default stream) on which the inputs were produced; the solver's own stream
+ * waits for an event recorded on it before its first read, and the call returns after its own stream has drained: the outputs
+ * are complete on return.
+ *   Bits: the kernels of the host entries read the caller's buffers where they read the staging block, and the results kernel
+ * does the host entry's three operations in its order: a device-entry call gives the bits of the host-entry call with the same
+ * numbers, and the entries may alternate on one handle.  A NaN in a vector, a non-finite value or a non-finite entry of a start
+ * is found by a kernel before anything the solver reads is written.
+ * 0, or -1 + hprlp_last_error() with the solver as it was, bit for bit, and still usable: what the host entries refuse (a sharded
+ * solver, a solver never scaled, an incomplete bounds group, a wrong nnz, a NaN) and a pointer that does not pass. */
+int hprlp_solver_set_data_device(hprlp_solver *s, const double *dc, const double *obj_constant, const double *dAL,
+                                 const double *dAU, const double *dl, const double *du, void *stream);
+int hprlp_solver_resolve_device(hprlp_solver *s, double sigma, const double *dx0, const double *dy0, void *stream, double *dx,
+                                double *dy, double *dz, HPRLP_results *out, hprlp_trace_row *trace, int max_trace, int *n_trace);
+int hprlp_solver_set_matrix_values_device(hprlp_solver *s, const double *dval, long nnz, const double *dc,
+                                          const double *obj_constant, const double *dAL, const double *dAU, const double *dl,
+                                          const double *du, void *stream);
+/* The last successful set_data*, set_matrix_values* or resolve* call, either entry: out = {bytes of model data and solution host
+ * -> device, the same device -> host, 1 if that call was a device entry, device-entry calls so far}.  Counted are the vectors,
+ * the values, the starts and the solution; not counted are the loop's scalar fetches, the 8-byte check flag and the one-time
+ * upload of a locality ordering's permutations.  A device entry therefore reports 0 / 0. */
+int hprlp_solver_transfer(hprlp_solver *s, long out[4]);
 /* the value maps as the solver built them (built now if no set_matrix_values call has): mapA[e] / mapAT[k] = the caller's CSR
  * position of entry e of A / entry k of A^T in the solver's internal numbering; cap >= nnz ints each.  Returns nnz, or -1. */
 long hprlp_solver_value_maps(hprlp_solver *s, int *mapA, int *mapAT, long cap);
