@@ -1544,6 +1544,12 @@ VecRef find_vector(Solver &s, const std::string &name) {
     if (name == "col_norm") return {s.col_norm.p, s.n_loc, 'c'};
     if (name == "A_val") return {s.A.val.p, s.A.view.nnz, '-'};
     if (name == "AT_val") return {s.AT.val.p, s.AT.view.nnz, '-'};
+    if (s.ray_prev_x.p) {  // the ray test's vectors, once Solver::ray_begin has allocated them (scaled units)
+        if (name == "ray_d") return {s.ray_d.p, s.n_loc, 'c'};
+        if (name == "ray_prev_x") return {s.ray_prev_x.p, s.n_loc, 'c'};
+        if (name == "ray_y") return {s.ray_y.p, s.m_loc, 'r'};
+        if (name == "ray_prev_y") return {s.ray_prev_y.p, s.m_loc, 'r'};
+    }
     return {nullptr, -1, '-'};
 }
 // the permutation (device index -> caller's index) that applies to a vector, or null
@@ -1726,6 +1732,28 @@ extern "C" int hprlp_solver_set_detection(hprlp_solver *h, const hprlp_detection
     detection_from(det, &d);
     h->s.detect = d;
     return 0;
+    GUARD_END(-1)
+}
+
+// One ray test outside the loop: the evaluation a periodic check of solve_loop runs (residuals with the gap, then the ray test,
+// one fetch), so the nine slots come the way the loop reads them.  Solver::detect is not touched.
+extern "C" int hprlp_solver_ray_step(hprlp_solver *h, int restart, double out[9]) {
+    GUARD_BEGIN
+    if (!h || !out) throw std::runtime_error("null solver / output");
+    if (h->sharded)
+        throw std::runtime_error("hprlp_solver_ray_step: infeasibility detection runs on one GPU only; a sharded solver "
+                                 "(hprlp_solver_create_dist* / _local*) refuses it");
+    Solver &s = h->s;
+    if (restart) s.ray_begin();
+    else if (!s.ray_prev_x.p) throw std::runtime_error("hprlp_solver_ray_step: the first step of a solver needs restart != 0");
+    Residuals r;
+    RestartState rs;
+    bool ray = false;
+    s.compute_residuals(1, true, &r, &rs, &ray);
+    if (!ray) return 0;
+    const int slots[9] = {S_RAY_DY, S_RAY_CD, S_RAY_VY, S_RAY_WD, S_RAY_YN, S_RAY_DN, S_RAY_DZ, S_RAY_VZ, S_RAY_WQ};
+    for (int k = 0; k < 9; ++k) out[k] = s.scal_h[slots[k]];
+    return 1;
     GUARD_END(-1)
 }
 

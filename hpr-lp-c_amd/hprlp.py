@@ -173,6 +173,7 @@ def lib():
     L.hprlp_free_certificate.argtypes = [C.POINTER(CCertificate)]
     L.hprlp_solver_set_detection.argtypes = [C.c_void_p, C.POINTER(CDetection)]
     L.hprlp_solver_get_certificate.argtypes = [C.c_void_p, C.POINTER(CCertificate)]
+    L.hprlp_solver_ray_step.argtypes = [C.c_void_p, C.c_int, c_dbl_p]
     L.hprlp_solve_batched_detect.restype = CBatchedResults
     L.hprlp_solve_batched_detect.argtypes = [C.POINTER(CLPInfo), C.c_int, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p,
                                              C.POINTER(CParameters), C.POINTER(CDetection), C.POINTER(CBatchedCertificates)]
@@ -1297,6 +1298,19 @@ class Solver:
         """Infeasibility detection for the following run() calls (hprlp_solver_set_detection); on=False switches it off."""
         det = _detection(eps_primal, eps_dual) if on else None
         self._chk(lib().hprlp_solver_set_detection(self.h, C.byref(det) if det is not None else None))
+
+    RAY_SLOTS = ("DY", "CD", "VY", "WD", "YN", "DN", "DZ", "VZ", "WQ")
+
+    def ray_step(self, restart=False):
+        """One ray test of the detection on the current x_bar / y_bar (hprlp_solver_ray_step).  None where only the iterate was
+        stored (the first step after restart=True), else the nine raw slots (RAY_SLOTS) and the sums the verdict reads, as
+        Solver::ray_scalars forms them: D, V, cd, W, yn, dn."""
+        out = np.zeros(9)
+        if self._chk(lib().hprlp_solver_ray_step(self.h, int(bool(restart)), out.ctypes.data_as(c_dbl_p))) == 0:
+            return None
+        r = dict(zip(self.RAY_SLOTS, (float(v) for v in out)))
+        r.update(D=r["DY"] + r["DZ"], V=max(r["VY"], r["VZ"]), cd=r["CD"], W=max(r["WD"], r["WQ"]), yn=r["YN"], dn=r["DN"])
+        return r
 
     def set_start(self, x=None, y=None):
         """Warm start of the next run() (hprlp_solver_set_start): after init(), in the model's units and numbering."""

@@ -105,6 +105,14 @@ void hprlp_free_certificate(hprlp_certificate *cert);
 int hprlp_solver_set_detection(hprlp_solver *s, const hprlp_detection *det);
 /* the certificate of the last hprlp_solver_run (kind 0 without a verdict) */
 int hprlp_solver_get_certificate(hprlp_solver *s, hprlp_certificate *cert);
+/* One ray test on the current x_bar / y_bar, as a periodic evaluation of hprlp_solver_run enqueues it (after the residual
+ * kernels, its scalars on the same fetch).  restart != 0 forgets the stored iterate first.  Returns 1: tested, out = the raw
+ * sums and maxima {D rows, c'd, V rows, W columns, |y|_inf, |d|_inf, D columns, V columns, W rows} (D = out[0] + out[6],
+ * V = max(out[2], out[7]), W = max(out[3], out[8])); 0: only the iterate was stored (the first call after a restart), out
+ * untouched; -1 + hprlp_last_error(), a sharded solver among the errors.  The detection setting of later hprlp_solver_run calls
+ * stays as it was.  After the first call the vectors "ray_d", "ray_prev_x" (n) and "ray_y", "ray_prev_y" (m) can be read with
+ * hprlp_solver_get_vector (scaled units). */
+int hprlp_solver_ray_step(hprlp_solver *s, int restart, double out[9]);
 
 /* ---- the same detection for solve_batched (DESIGN.md "Batched detection") ----------------------------------------------------
  * The tests above, member by member in that member's units, at the same evaluations.  A member with a verdict is frozen as an

@@ -48,6 +48,40 @@ assumption on the order of any sum:
         Where W < 0 the solver raises lambda_max instead; that branch is bounded the same way beside its code below.
   movement: d = a - b carries u |d|; (Q), (S), (W).
   lu_term: t_j carries u |t_j|, the quotient another u |r_j|: e(r_j) = 2 u |r_j|; (Q), (S) over n, (W), one (M).
+
+THE RAY TEST of the infeasibility detection (evaluate_rays; kernels.hip: k_ray_form, RayColEpi, RayRowEpi; solver.cpp:
+Solver::ray_test, Solver::ray_scalars).  The scaled rays ds (columns) and ys (rows) are INPUTS, in FP64 as read back (one
+subtraction each on the device: the same bits anywhere).  Nine slots, caller's units:
+
+    d_j = (ds_j / cn_j) b_scale                       y_i = (ys_i / rn_i) c_scale
+    CD = sum_j ((c_j cn_j) c_scale) d_j               DN = max_j |d_j|              YN = max_i |y_i|
+    WD = max(0, max_{l_j finite} -d_j, max_{u_j finite} d_j)
+    DY = sum_{y_i > 0, AL_i finite} ((AL_i rn_i) b_scale) y_i + sum_{y_i < 0, AU_i finite} ((AU_i rn_i) b_scale) y_i
+    VY = max(0, max_{y_i > 0, AL_i infinite} y_i, max_{y_i < 0, AU_i infinite} -y_i)
+    s = A^T ys,  z_j = -((s_j cn_j) c_scale),  lo'_j = (l_j / cn_j) b_scale,  hi'_j = (u_j / cn_j) b_scale
+    DZ = sum_{z_j > 0, l_j finite} lo'_j z_j + sum_{z_j < 0, u_j finite} hi'_j z_j
+    VZ = max(0, max_{z_j > 0, l_j infinite} z_j, max_{z_j < 0, u_j infinite} -z_j)
+    g = A ds,  q_i = (g_i rn_i) b_scale,  WQ = max(0, max_{AL_i finite} -q_i, max_{AU_i finite} q_i)
+    D = DY + DZ,  V = max(VY, VZ),  cd = CD,  W = max(WD, WQ),  yn = YN,  dn = DN
+
+  elementwise values: d_j and y_i are a quotient and a product with exactly known factors: 2 u |d_j|, 2 u |y_i|  (M).
+  sign branches of y: rn_i > 0 and c_scale > 0, and a correctly rounded quotient or product of a nonzero value by a positive
+        factor keeps its sign (and 0 stays 0), so the device takes the branch of y_i that the exact value takes: the branch is exact.
+  sums: a term of CD is coefficient x d_j: the coefficient's two products (2 u), the product (u) and the 2 u of d_j: 5 u |t_j|;
+        a term of DY the like with y_i: 5 u |t_i|; then (S) over n resp. m.
+  products: z_j = -((s_j cn_j) c_scale): e(z_j) = cn_j c_scale e_row_j + 2 u |z_j| by (R), (M); q_i: rn_i b_scale e_row_i + 2 u |q_i|.
+  a maximum is 1-Lipschitz in the sup norm: max_k f_k moves by at most max_k |f_k - f_k'|, so the bound of VY, WD, YN, DN, VZ, WQ
+        is the LARGEST bound of the elements that may enter it (every column with a finite side for WD, ...); the floor 0 is exact.
+  the sign of z_j can flip within e(z_j), so the device may take another branch than the reference.  As functions of z both
+        terms of a column are CONTINUOUS at 0 and piecewise linear:
+            D-term  f_j(z) = lo'_j z for z > 0 with l_j finite, hi'_j z for z < 0 with u_j finite, else 0:
+                    slopes at most L_j = max(|lo'_j|, |hi'_j|) over the finite sides;
+            V-term  v_j(z) = z for z > 0 with l_j infinite, -z for z < 0 with u_j infinite, else 0: slopes at most 1.
+        Hence |f_j(z) - f_j(z')| <= L_j |z - z'| and |v_j(z) - v_j(z')| <= |z - z'| WHICHEVER branches z and z' take:
+            e(D-term_j) = L_j e(z_j) + 3 u |term_j|   (lo'_j or hi'_j: 2 u, the product: u),     e(V-term_j) = e(z_j),
+        and every column with an infinite side may enter VZ.  This is what makes a bound possible without knowing the device's
+        branch.  DZ: (S) over n.  (q_i enters WQ through the fixed finite sides of its row: no branch on its sign.)
+  combinations: D = DY + DZ: e_DY + e_DZ + u |D|; V and W: the larger of the two bounds (a maximum again); cd, yn, dn: the slots'.
 """
 import math
 
@@ -230,6 +264,108 @@ def evaluate_f64(A, AT, data, scalars, st, sigma, lambda_max, drop_A=None, drop_
     return dict(err_Rp=rp, err_Rd=rd, primal_obj=pobj, dual_obj=dobj, gap=gap, kkt=max(max(rd, rp), gap), weighted_norm=wn)
 
 
+# ---- the ray test of the infeasibility detection ---------------------------------------------------------------------------------
+RAY_SLOTS = ("DY", "CD", "VY", "WD", "YN", "DN", "DZ", "VZ", "WQ")   # (the order of hprlp_solver_ray_step's out[9])
+RAY_SUMS = ("D", "V", "cd", "W", "yn", "dn")                          # (Solver::ray_scalars)
+RAY_NAMES = RAY_SLOTS + RAY_SUMS
+RAY_MAXIMA = ("VY", "WD", "YN", "DN", "VZ", "WQ")
+
+
+def _ray_elements(dt, data, scalars, s, g, ds, ys, swap_sides):
+    """The elementwise parts of the ray test in the arithmetic of the dtype dt, from the row sums s = A^T ys and g = A ds:
+    (d, y, z, q, the terms of CD, DY, DZ, and per maximum the element values (0 where the element does not enter) with the mask
+    of the elements that MAY enter).  swap_sides: the dual ray's signs paired with the wrong bound (y_i > 0 and z_j > 0 with the
+    upper side): a deliberately wrong evaluation."""
+    a = lambda k: np.asarray(data[k], dtype=dt)
+    c, AL, AU, l, u, rn, cn = (a(k) for k in ("c", "AL", "AU", "l", "u", "row_norm", "col_norm"))
+    bs, cs = dt(scalars["b_scale"]), dt(scalars["c_scale"])
+    d = (np.asarray(ds, dtype=dt) / cn) * bs
+    y = (np.asarray(ys, dtype=dt) / rn) * cs
+    z = -((s * cn) * cs)
+    q = (g * rn) * bs
+    rlo, rhi, clo, chi = (AU, AL, u, l) if swap_sides else (AL, AU, l, u)
+    fin, zero = np.isfinite, dt(0)
+    with np.errstate(invalid="ignore"):
+        t_cd = ((c * cn) * cs) * d
+        t_dy = np.where((y > 0) & fin(rlo), ((rlo * rn) * bs) * y, np.where((y < 0) & fin(rhi), ((rhi * rn) * bs) * y, zero))
+        lo_, hi_ = (clo / cn) * bs, (chi / cn) * bs
+        t_dz = np.where((z > 0) & fin(clo), lo_ * z, np.where((z < 0) & fin(chi), hi_ * z, zero))
+    slope = np.maximum(np.where(fin(clo), np.abs(lo_), zero), np.where(fin(chi), np.abs(hi_), zero))
+    in_vy = ((y > 0) & ~fin(rlo)) | ((y < 0) & ~fin(rhi))
+    el = {"VY": (np.where(in_vy, np.abs(y), zero), in_vy),
+          "WD": (np.maximum(np.where(fin(l), -d, zero), np.where(fin(u), d, zero)), fin(l) | fin(u)),
+          "YN": (np.abs(y), np.ones(len(y), dtype=bool)),
+          "DN": (np.abs(d), np.ones(len(d), dtype=bool)),
+          "VZ": (np.where((z > 0) & ~fin(clo), z, np.where((z < 0) & ~fin(chi), -z, zero)), ~fin(clo) | ~fin(chi)),
+          "WQ": (np.maximum(np.where(fin(AL), -q, zero), np.where(fin(AU), q, zero)), fin(AL) | fin(AU))}
+    return d, y, z, q, t_cd, t_dy, t_dz, slope, el
+
+
+def _ray_sums(out):
+    """the six combinations of Solver::ray_scalars from the nine slots (plain values)"""
+    return {"D": out["DY"] + out["DZ"], "V": max(out["VY"], out["VZ"]), "cd": out["CD"], "W": max(out["WD"], out["WQ"]),
+            "yn": out["YN"], "dn": out["DN"]}
+
+
+def evaluate_rays(A, AT, data, scalars, ds, ys, drop_A=None, drop_AT=None, leave_out=None, swap_sides=False):
+    """The nine slots (RAY_SLOTS) and six combinations (RAY_SUMS) of the ray test, each as (value, bound) in np.longdouble (the
+    module docstring: THE RAY TEST).  A, AT, data, scalars as evaluate(); ds, ys: the scaled rays in FP64.  drop_A / drop_AT: one
+    stored entry left out; leave_out: {maximum's name: index of an element left out of it}; swap_sides: see _ray_elements -- three
+    deliberately wrong evaluations.  out["elements"]: per maximum the FP64 element values (0 where an element does not enter)."""
+    s, s_abs, s_len = _row_sums(AT, ys, drop_AT)
+    g, g_abs, g_len = _row_sums(A, ds, drop_A)
+    d, y, z, q, t_cd, t_dy, t_dz, slope, el = _ray_elements(LD, data, scalars, s, g, ds, ys, swap_sides)
+    rn, cn = np.asarray(data["row_norm"], dtype=LD), np.asarray(data["col_norm"], dtype=LD)
+    bs, cs = LD(scalars["b_scale"]), LD(scalars["c_scale"])
+    e_z = cn * cs * ((s_len + 1) * U * s_abs) + 2 * U * np.abs(z)
+    e_q = rn * bs * ((g_len + 1) * U * g_abs) + 2 * U * np.abs(q)
+    e_el = {"VY": 2 * U * np.abs(y), "WD": 2 * U * np.abs(d), "YN": 2 * U * np.abs(y), "DN": 2 * U * np.abs(d), "VZ": e_z, "WQ": e_q}
+    out = {"CD": _sum(t_cd, 5 * U * np.abs(t_cd)), "DY": _sum(t_dy, 5 * U * np.abs(t_dy)),
+           "DZ": _sum(t_dz, slope * e_z + 3 * U * np.abs(t_dz)), "elements": {}}
+    for k in RAY_MAXIMA:
+        v, may = el[k]
+        may = may.copy()
+        if leave_out and k in leave_out:
+            may[leave_out[k]] = False
+        out["elements"][k] = np.where(may, v, LD(0)).astype(np.float64)
+        out[k] = (max(LD(0), v[may].max()), e_el[k][may].max()) if may.any() else (LD(0), LD(0))
+    D = out["DY"][0] + out["DZ"][0]
+    out["D"] = (D, out["DY"][1] + out["DZ"][1] + U * abs(D))
+    out["V"] = (max(out["VY"][0], out["VZ"][0]), max(out["VY"][1], out["VZ"][1]))
+    out["W"] = (max(out["WD"][0], out["WQ"][0]), max(out["WD"][1], out["WQ"][1]))
+    out["cd"], out["yn"], out["dn"] = out["CD"], out["YN"], out["DN"]
+    return out
+
+
+def evaluate_rays_f64(A, AT, data, scalars, ds, ys, drop_A=None, drop_AT=None, leave_out=None, swap_sides=False, row_sums=None,
+                      total=None):
+    """The same fifteen numbers in plain FP64 numpy, as the device forms them.  row_sums(csr, v, drop) and total(terms) replace
+    numpy's summation orders by another FP64 order; leave_out / swap_sides / drop_*: as evaluate_rays."""
+    if row_sums is None:
+        row_sums = lambda csr, v, drop: _row_sums(csr, v, drop, np.float64)[0]
+    if total is None:
+        total = np.sum
+    s, g = row_sums(AT, ys, drop_AT), row_sums(A, ds, drop_A)
+    _, _, _, _, t_cd, t_dy, t_dz, _, el = _ray_elements(np.float64, data, scalars, s, g, ds, ys, swap_sides)
+    out = {"CD": float(total(t_cd)), "DY": float(total(t_dy)), "DZ": float(total(t_dz))}
+    for k in RAY_MAXIMA:
+        v, may = el[k]
+        may = may.copy()
+        if leave_out and k in leave_out:
+            may[leave_out[k]] = False
+        out[k] = max(0.0, float(v[may].max())) if may.any() else 0.0
+    out.update(_ray_sums(out))
+    return out
+
+
+def top_two(elements):
+    """(arg-max, maximum, runner-up) of a maximum's element values"""
+    e = np.asarray(elements, dtype=np.float64)
+    j = int(np.argmax(e))
+    rest = np.delete(e, j)
+    return j, float(e[j]), float(rest.max()) if len(rest) else 0.0
+
+
 def ratio(got, ref):
     """|got - value| / bound of one quantity (0 where both vanish); inf where `got`, the value or the bound is not finite, so that
     a NaN can never compare as within bounds (and never hides in a max())."""
@@ -307,3 +443,118 @@ def check_solver(s, patterns, got, sigma, lambda_max, names=QUANTITIES, label=""
     assert all(np.isfinite(got[k]) for k in names), (label, {k: got[k] for k in names})
     assert all_within(r), (label, r, {k: (got[k], want[k]) for k in names if not r[k] <= TOL_FACTOR})
     return inp, st, want, r
+
+
+def check_rays(s, patterns, got, label=""):
+    """The nine slots and six combinations `got` of s.ray_step() against evaluate_rays on the solver's OWN read-back scaled data
+    and read-back rays (ray_d, ray_y): every one within TOL_FACTOR x its bound; a value that is not finite fails.  Prints the
+    observed-difference / bound ratios; returns (inputs, (ds, ys), reference, ratios)."""
+    inp, ds, ys = solver_inputs(s, *patterns), s.get("ray_d"), s.get("ray_y")
+    want = evaluate_rays(*inp, ds, ys)
+    r = ratios(got, want, RAY_NAMES)
+    print("rays", label, " ".join("%s %.3g" % kv for kv in r.items()))
+    assert all(np.isfinite(float(want[k][0])) for k in RAY_NAMES), {k: want[k] for k in RAY_NAMES}
+    assert all(np.isfinite(got[k]) for k in RAY_NAMES), (label, {k: got[k] for k in RAY_NAMES})
+    assert all_within(r), (label, r, {k: (got[k], want[k]) for k in RAY_NAMES if not r[k] <= TOL_FACTOR})
+    return inp, (ds, ys), want, r
+
+
+# ---- the ray test in the caller's units ------------------------------------------------------------------------------------------
+# The roundings a number of the model goes through in scale() with use_CR_scaling off (oracle/hpr_oracle.c: orc_scaling; the
+# device runs the same passes): 10 Ruiz passes and one Pock-Chambolle pass, then the b / c scaling.
+#   a matrix entry: one division by the row factor and one by the column factor per pass: 2 x 11 = 22;
+#   row_norm_i and col_norm_j: one multiplication per pass: 11 each;
+#   AL_i, AU_i (c_j; l_j, u_j): one division (division; multiplication) per pass: 11, the reciprocal of b_scale (c_scale;
+#   b_scale): 1, the multiplication by it: 1: 13.
+# Mapped back, a_s rn_i cn_j = a (1 + 44 u) and side_s rn_i b_scale = side (1 + 24 u) (the like for c, l, u); the unscaled ray
+# entry y_i = (ys_i / rn_i) c_scale or d_j = (ds_j / cn_j) b_scale that the caller's-units side is given in FP64 carries 2 u.
+SCALE_PASSES = 11
+K_ENTRY = 2 * SCALE_PASSES + 2 * SCALE_PASSES + 2   # 46: per product a_ij y_i resp. a_ij d_j
+K_SIDE = (SCALE_PASSES + 2) + SCALE_PASSES + 2      # 26: per product side_i y_i, bound_j z_j, c_j d_j
+
+
+def unit_inputs(lp, AT):
+    """(A, AT, data, scalars) of evaluate_rays for a model in the caller's own units: no scaling.  AT = (rowptr, colind, values)."""
+    data = dict(c=lp["c"], AL=lp["AL"], AU=lp["AU"], l=lp["l"], u=lp["u"], row_norm=np.ones(lp["m"]), col_norm=np.ones(lp["n"]))
+    return (lp["rowptr"], lp["colind"], lp["values"]), AT, data, dict(b_scale=1.0, c_scale=1.0)
+
+
+def caller_units_allowance(A, AT, data, d, y, k_entry=K_ENTRY, k_side=K_SIDE):
+    """What D, V, c'd, W of the rays d, y ON THE CALLER'S MODEL (A, AT, data unscaled) may differ by from the same sums formed on
+    the scaled model, from the roundings of scale() alone: k_entry u per product with a matrix entry, k_side u per product with a
+    side, a bound or a cost; through the maxima and the sign branches of z as the module docstring derives."""
+    fin = np.isfinite
+    a = lambda k: np.asarray(data[k], dtype=LD)
+    c, AL, AU, l, u = (a(k) for k in ("c", "AL", "AU", "l", "u"))
+    y, d = np.asarray(y, dtype=LD), np.asarray(d, dtype=LD)
+    s, s_abs, _ = _row_sums(AT, y)
+    _, g_abs, _ = _row_sums(A, d)
+    z = -s
+    a_z, a_q = k_entry * U * s_abs, k_entry * U * g_abs
+    with np.errstate(invalid="ignore"):
+        t_y = np.where((y > 0) & fin(AL), AL * y, np.where((y < 0) & fin(AU), AU * y, LD(0)))
+        t_z = np.where((z > 0) & fin(l), l * z, np.where((z < 0) & fin(u), u * z, LD(0)))
+    slope = np.maximum(np.where(fin(l), np.abs(l), LD(0)), np.where(fin(u), np.abs(u), LD(0)))
+    open_col, shut_row = ~fin(l) | ~fin(u), fin(AL) | fin(AU)
+    return {"D": k_side * U * np.sum(np.abs(t_y)) + np.sum(slope * a_z) + k_side * U * np.sum(np.abs(t_z)),
+            "V": max(k_side * U * np.abs(y).max(), a_z[open_col].max() if open_col.any() else LD(0)),
+            "cd": k_side * U * np.sum(np.abs(c * d)),
+            "W": max(k_side * U * np.abs(d).max(), a_q[shut_row].max() if shut_row.any() else LD(0))}
+
+
+# ---- rays for the tests ----------------------------------------------------------------------------------------------------------
+def random_rays(m, n, seed):
+    """(ds, ys): standard normal in scaled units, about one entry in eight exactly 0"""
+    rng = np.random.default_rng(seed)
+    ds, ys = rng.normal(size=n), rng.normal(size=m)
+    ds[rng.random(n) < 0.125] = 0.0
+    ys[rng.random(m) < 0.125] = 0.0
+    return ds, ys
+
+
+def line_of(csr, k, length, sign=1.0):
+    """sign x (stored line k of csr) as a dense vector of `length`: ys = -(column j of A) from A^T gives z_j = cn_j c_scale sum a^2,
+    ds = +-(row i of A) gives q_i = +- rn_i b_scale sum a^2"""
+    rp, ci, val = csr
+    v = np.zeros(length)
+    v[np.asarray(ci[rp[k]:rp[k + 1]], dtype=np.int64)] = sign * np.asarray(val[rp[k]:rp[k + 1]], dtype=np.float64)
+    return v
+
+
+def largest_entry(csr, k):
+    """index of the stored entry of largest magnitude in line k"""
+    rp, _, val = csr
+    return int(rp[k] + np.argmax(np.abs(np.asarray(val[rp[k]:rp[k + 1]]))))
+
+
+def boosted(v, norm, k, sign, factor=4.0):
+    """v with entry k set so that sign x v_k / norm_k is `factor` x the largest |v / norm| of the others"""
+    v = np.array(v, dtype=np.float64)
+    others = np.abs(np.delete(v / norm, k)).max()
+    v[k] = sign * factor * others * norm[k]
+    return v
+
+
+def check_certificate_values(lp, kind, ray, objective, violation, label=""):
+    """A certificate's objective and violation against D, V (kind 1, ray = y) resp. c'd, W (kind 2, ray = d) of the RETURNED,
+    normalised ray, by value and from both sides: evaluate_rays on the caller's model in the caller's units (no scaling: unit norms
+    and scales), within TOL_FACTOR x its bound plus the allowance for the roundings of scale() with use_CR_scaling off
+    (caller_units_allowance; two more u per product for the division of the ray and of the sums by its infinity norm).  The
+    violation of a verdict is what is left of sums that cancel, so its tolerance is large relative to it: the ratios are printed."""
+    from scipy import sparse
+    A = sparse.csr_matrix((lp["values"], lp["colind"], lp["rowptr"]), shape=(lp["m"], lp["n"]))
+    AT = sparse.csr_matrix(A.T)
+    AT.sort_indices()
+    inp = unit_inputs(lp, (AT.indptr, AT.indices, AT.data))
+    ds, ys = (np.zeros(lp["n"]), np.asarray(ray, np.float64)) if kind == 1 else (np.asarray(ray, np.float64), np.zeros(lp["m"]))
+    want = evaluate_rays(*inp, ds, ys)
+    allow = caller_units_allowance(inp[0], inp[1], inp[2], ds, ys, K_ENTRY + 2, K_SIDE + 2)
+    out = {}
+    for field, got, name in (("objective", objective, "D" if kind == 1 else "cd"), ("violation", violation, "V" if kind == 1 else "W")):
+        v, b = want[name]
+        tol = TOL_FACTOR * b + allow[name]
+        out[field] = ratio(got, (v, tol))
+        print("certificate", label, field, "%.17g" % got, "reference %.17g" % float(v), "difference / tolerance %.3g" % out[field],
+              "(tolerance %.3g: bound %.3g, allowance %.3g)" % (float(tol), float(b), float(allow[name])))
+    assert all(r <= 1.0 for r in out.values()), (label, out)
+    return out

@@ -136,7 +136,8 @@ def test_struct_layouts_equal_the_ctypes_mirrors(cc, std, tmp_path):
 def test_new_symbols_are_exported():
     out = subprocess.run(["nm", "-D", "--defined-only", hprlp.LIB_PATH], capture_output=True, text=True, check=True).stdout
     names = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
-    for s in ("hprlp_solve_detect", "hprlp_free_certificate", "hprlp_solver_set_detection", "hprlp_solver_get_certificate"):
+    for s in ("hprlp_solve_detect", "hprlp_free_certificate", "hprlp_solver_set_detection", "hprlp_solver_get_certificate",
+              "hprlp_solver_ray_step"):
         assert s in names, s
 
 

@@ -1,6 +1,12 @@
 """Infeasibility detection in solve_batched (include/hprlp_amd.h hprlp_solve_batched_detect, DESIGN.md "Batched detection") on the
 GPU: per-member verdicts against HiGHS, certificates judged by the numpy restatement of the ratio tests in each member's units,
-every panel form, the limits' precedence, and no perturbation of the feasible members."""
+every panel form, the limits' precedence, and no perturbation of the feasible members.
+
+Every certificate's objective and violation are also held BY VALUE, from both sides, to D and V resp. c'd and W of the returned
+ray (tests/evalref.py: check_certificate_values, in the member's units; the solves run with use_CR_scaling off, whose device
+`exp` rounds by more than one u).  For the batched ray kernels (kb_ray_form, kb_ray_col, kb_ray_row) this is the value-level
+check there is; it covers the panel forms of test_mixed_batch_verdicts_and_certificates: B = 5 (one chunk of 8), B = 64, and
+B = 70 with chunks of 8 and of 32.  (A step-level entry to the batched ray test does not exist.)"""
 import functools
 import json
 import os
@@ -9,6 +15,7 @@ import numpy as np
 import pytest
 from scipy import sparse
 
+import evalref
 from conftest import hprlp, lpgen
 from test_detect import dual_ray_test, highs_status, primal_ray_test
 from test_gpu_batched import make_batch
@@ -29,7 +36,8 @@ def _member_equal(a, b, k):
 
 
 def _check_certificate(lp, r, k):
-    """Member k's verdict and certificate, in its units, by the numpy ratio tests (10 x eps, as tests/test_gpu_detect.py)."""
+    """Member k's verdict and certificate, in its units, by the numpy ratio tests (10 x eps, as tests/test_gpu_detect.py), and
+    its objective and violation by value from both sides (tests/evalref.py: check_certificate_values; use_CR_scaling off)."""
     cert = r["certificates"]
     kind, st = int(cert["kind"][k]), r["status"][k]
     assert st == {1: "PRIMAL_INFEASIBLE", 2: "DUAL_INFEASIBLE"}[kind], (k, st, kind)
@@ -42,6 +50,7 @@ def _check_certificate(lp, r, k):
         A = sparse.csr_matrix((lp["values"], lp["colind"], lp["rowptr"]), shape=(lp["m"], lp["n"]))
         np.testing.assert_allclose(z, -(A.T @ y), rtol=1e-9, atol=1e-12)
         assert abs(cert["objective"][k] - D) <= 1e-6 * abs(D) and cert["violation"][k] <= 10 * EPS * D
+        evalref.check_certificate_values(lp, 1, y, float(cert["objective"][k]), float(cert["violation"][k]), "member %d" % k)
         assert cert["d"] is None or not cert["d"][:, k].any()
     else:
         d = cert["d"][:, k]
@@ -49,6 +58,7 @@ def _check_certificate(lp, r, k):
         cd, W = dual_ray_test(lp, d)
         assert cd < 0 and W <= 10 * EPS * -cd, (k, cd, W)
         assert abs(cert["objective"][k] - cd) <= 1e-6 * abs(cd) and cert["violation"][k] <= 10 * EPS * -cd
+        evalref.check_certificate_values(lp, 2, d, float(cert["objective"][k]), float(cert["violation"][k]), "member %d" % k)
         assert cert["y"] is None or (not cert["y"][:, k].any() and not cert["z"][:, k].any())
 
 
@@ -64,7 +74,7 @@ def test_three_member_batch_with_an_infeasible_member(gpu):
     L = np.zeros((2, B)); U = np.full((2, B), INF)
     AL[0, 1] = 11.0
     U[:, 1] = 1.0
-    prm = hprlp.Parameters(stop_tol=1e-6, max_iter=3000, use_presolve=False)
+    prm = hprlp.Parameters(stop_tol=1e-6, max_iter=3000, use_presolve=False, use_CR_scaling=False)
     off = hprlp.solve_batched(model, Cm, AL, AU, L, U, [0.0, 0.0, 7.0], prm)
     on = hprlp.solve_batched_detect(model, Cm, AL, AU, L, U, [0.0, 0.0, 7.0], prm)
     assert off["status"] == ["OPTIMAL", "ITER_LIMIT", "OPTIMAL"]
@@ -131,7 +141,7 @@ def _with_chunk(chunk, fn):
             os.environ["HPRLP_BATCH_CHUNK"] = old
 
 
-MIXED_PRM = dict(stop_tol=1e-6, max_iter=30000, time_limit=60.0, use_presolve=False)
+MIXED_PRM = dict(stop_tol=1e-6, max_iter=30000, time_limit=60.0, use_presolve=False, use_CR_scaling=False)
 
 
 @pytest.mark.parametrize("B,chunk", [(5, 0), (64, 0), (70, 8), (70, 32)])

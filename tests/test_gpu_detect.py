@@ -38,8 +38,11 @@ def model_of(lp):
     return hprlp.Model.from_csr(lp["m"], lp["n"], lp["rowptr"], lp["colind"], lp["values"], lp["AL"], lp["AU"], lp["l"], lp["u"], lp["c"])
 
 
-def check_certificate(lp, r, want):
-    """The verdict `want` and its certificate in the caller's units and numbering, by the numpy ratio tests (10 x eps)."""
+def check_certificate(lp, r, want, by_value=False):
+    """The verdict `want` and its certificate in the caller's units and numbering, by the numpy ratio tests (10 x eps); by_value
+    (solves with use_CR_scaling off): objective and violation equal D and V resp. c'd and W of the returned ray, from both sides,
+    within the derived tolerance of tests/evalref.py: check_certificate_values."""
+    import evalref
     k = r.certificate
     assert r.status == want and k.verdict == want, (r.status, k.kind)
     assert (k.m, k.n) == (lp["m"], lp["n"]) and k.iter == r.iter and k.iter > 0
@@ -52,12 +55,16 @@ def check_certificate(lp, r, want):
         A = sparse.csr_matrix((lp["values"], lp["colind"], lp["rowptr"]), shape=(lp["m"], lp["n"]))
         np.testing.assert_allclose(k.z, -(A.T @ k.y), rtol=1e-9, atol=1e-12)
         assert abs(k.objective - D) <= 1e-6 * abs(D) and k.violation <= 10 * EPS * D
+        if by_value:
+            evalref.check_certificate_values(lp, 1, k.y, k.objective, k.violation, want)
     else:
         assert k.y is None and k.z is None and len(k.d) == lp["n"]
         assert abs(np.abs(k.d).max() - 1.0) <= 1e-12
         cd, W = dual_ray_test(lp, k.d)
         assert cd < 0 and W <= 10 * EPS * -cd, (cd, W)
         assert abs(k.objective - cd) <= 1e-6 * abs(cd) and k.violation <= 10 * EPS * -cd
+        if by_value:
+            evalref.check_certificate_values(lp, 2, k.d, k.objective, k.violation, want)
     return k
 
 
@@ -65,8 +72,8 @@ def check_certificate(lp, r, want):
 def test_edge_cases_end_in_a_verdict(gpu, name, want):
     lp = as_lp(EDGE[name])
     model = model_of(lp)
-    r = model.solve_detect(hprlp.Parameters(stop_tol=1e-8, max_iter=3000, use_presolve=False))
-    check_certificate(lp, r, want)
+    r = model.solve_detect(hprlp.Parameters(stop_tol=1e-8, max_iter=3000, use_presolve=False, use_CR_scaling=False))
+    check_certificate(lp, r, want, by_value=True)
     assert r.iter <= 1500, r.iter
     model.free()
 
@@ -95,13 +102,13 @@ def test_presolve_on_gives_a_certificate_of_the_original_model(gpu, capfd):
     assert pre.stats["fixed_cols"] == 3 and (pre.stats["m"], pre.stats["n"]) == (lp["m"], lp["n"] - 3), pre.stats
     pre.free()
     capfd.readouterr()
-    r = model.solve_detect(hprlp.Parameters(max_iter=6000, use_presolve=True))
+    r = model.solve_detect(hprlp.Parameters(max_iter=6000, use_presolve=True, use_CR_scaling=False))
     out = capfd.readouterr().out
     hit = re.search(r"Reduced model ended PRIMAL_INFEASIBLE at iteration (\d+); solving the original model", out)
     assert hit, out[-2000:]
     it_reduced = int(hit.group(1))
     assert it_reduced > 0 and r.iter >= it_reduced + 300, (it_reduced, r.iter)   # (a verdict needs two evaluations)
-    check_certificate(lp, r, "PRIMAL_INFEASIBLE")   # (k.iter == r.iter: offset by the reduced solve's count too)
+    check_certificate(lp, r, "PRIMAL_INFEASIBLE", by_value=True)   # (k.iter == r.iter: offset by the reduced solve's count too)
     model.free()
 
 
@@ -160,7 +167,8 @@ else:   # tiled forms: a banded matrix
     A = sparse.csr_matrix((v, ci, rp), shape=(m, n)); A.sum_duplicates(); A.sort_indices()
     lp = gen(m, n, 0, 23, A=A)
 model = model_of(lp)
-prm = hprlp.Parameters(max_iter=50000, use_presolve=False)
+by_value = form != "reordered"   # (1.6 M rows: the certificate's numbers by value are left to the other forms)
+prm = hprlp.Parameters(max_iter=50000, use_presolve=False, use_CR_scaling=not by_value)
 s = hprlp.Solver(model, prm)
 d, info = s.describe(), s.info()
 expect = {"small": "single-workgroup kernel", "stream": "A: stream kernel", "tiled": "tiled, fused (k_tiled_fused",
@@ -173,10 +181,10 @@ s.scale(); lam, _ = s.power_iteration(); s.init(-1.0, lam * 1.01)
 rs = s.run(max_trace=1)
 ks = s.certificate()
 s.close()
-r1 = model.solve_detect(prm); k1 = check_certificate(lp, r1, want)
+r1 = model.solve_detect(prm); k1 = check_certificate(lp, r1, want, by_value)
 assert rs.status == want and ks.kind == k1.kind and ks.iter == r1.iter, (rs.status, ks.iter, r1.iter)
 if form != "reordered":  # (there the step-level run above is the second run)
-    r2 = model.solve_detect(prm); k2 = check_certificate(lp, r2, want)
+    r2 = model.solve_detect(prm); k2 = check_certificate(lp, r2, want, False)
     assert r1.iter == r2.iter and np.array_equal(k1.y if k1.y is not None else k1.d, k2.y if k2.y is not None else k2.d)
 print("OK", form, kind, r1.status, r1.iter, r1.time, d)
 ''' % ROOT

@@ -56,6 +56,9 @@ def test_reordered_iterates_match_oracle(gpu, lp):
     lam, it = s.power_iteration()
     lam_ref, it_ref = ref.power_iteration()
     assert it == it_ref and abs(lam - lam_ref) <= 1e-10 * lam_ref
+    # the ray test's vectors go through the ordering's permutation like every other one (tests/test_gpu_ray_values.py)
+    assert s.ray_step(restart=True) is None
+    assert np.array_equal(s.get("ray_prev_x"), s.get("x_bar")) and np.array_equal(s.get("ray_prev_y"), s.get("y_bar"))
     s.close(); model.free()
 
 
