@@ -1420,6 +1420,63 @@ extern "C" int hprlp_solver_run_many(hprlp_solver **h, int count, HPRLP_results 
     GUARD_END(-1)
 }
 
+// ---- group re-solve (DESIGN.md "Many small LPs", group re-solve) -------------------------------------------------------------
+// counts of the calling thread's last hprlp_solver_set_data_many / hprlp_solver_resolve_many (hprlp_last_resolve_many_counts)
+static thread_local long g_resolve_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+static void keep_resolve_counts(const ResolveCounts &rc) {
+    const long v[8] = {rc.h2d, rc.d2h, rc.waits, rc.launches, rc.memsets, rc.served, rc.own, rc.loop_own};
+    for (int i = 0; i < 8; ++i) g_resolve_counts[i] = v[i];
+}
+
+extern "C" int hprlp_last_resolve_many_counts(long out[8]) {
+    if (!out) return -1;
+    for (int i = 0; i < 8; ++i) out[i] = g_resolve_counts[i];
+    return 0;
+}
+
+extern "C" int hprlp_solver_set_data_many(hprlp_solver **h, int count, const hprlp_member_data *data) {
+    GUARD_BEGIN
+    // (list, count, data, then the members: the order of the refusals)
+    if (!h) throw std::runtime_error("hprlp_solver_set_data_many: null solver list");
+    if (count <= 0) throw std::runtime_error("hprlp_solver_set_data_many: count must be positive");
+    if (!data) throw std::runtime_error("hprlp_solver_set_data_many: null data");
+    std::vector<Solver *> s = group_members(h, count, "hprlp_solver_set_data_many");
+    std::vector<MemberData> d(static_cast<size_t>(count));
+    for (int k = 0; k < count; ++k) {
+        d[k].c = data[k].c, d[k].obj_constant = data[k].obj_constant;
+        d[k].AL = data[k].AL, d[k].AU = data[k].AU, d[k].l = data[k].l, d[k].u = data[k].u;
+    }
+    keep_resolve_counts(ResolveCounts());
+    ResolveCounts rc;
+    set_data_many(s.data(), count, d.data(), &rc);
+    keep_resolve_counts(rc);
+    return 0;
+    GUARD_END(-1)
+}
+
+extern "C" int hprlp_solver_resolve_many(hprlp_solver **h, int count, const hprlp_member_start *start, HPRLP_results *out) {
+    GUARD_BEGIN
+    if (!h) throw std::runtime_error("hprlp_solver_resolve_many: null solver list");
+    if (count <= 0) throw std::runtime_error("hprlp_solver_resolve_many: count must be positive");
+    if (!out) throw std::runtime_error("hprlp_solver_resolve_many: null results");
+    std::vector<Solver *> s = group_members(h, count, "hprlp_solver_resolve_many");
+    std::vector<MemberStart> b(static_cast<size_t>(count));
+    for (int k = 0; start && k < count; ++k) b[k].x0 = start[k].x0, b[k].y0 = start[k].y0, b[k].sigma = start[k].sigma;
+    check_starts(s.data(), count, b.data());  // (before the results are touched: a refusal leaves the output arrays as they were)
+    for (int k = 0; k < count; ++k) out[k] = make_error_result("ERROR");
+    keep_resolve_counts(ResolveCounts());
+    try {
+        ResolveCounts rc;
+        resolve_many(s.data(), count, b.data(), out, &rc);
+        keep_resolve_counts(rc);
+    } catch (...) {
+        free_results_arrays(out, count);
+        throw;
+    }
+    return 0;
+    GUARD_END(-1)
+}
+
 // phases of the calling thread's last hprlp_solve_many (hprlp_last_solve_many_phases)
 static thread_local double g_many_phases[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 

@@ -415,6 +415,23 @@ class GroupLaunches {
     void restart_copy(int n, int m, const double *x_bar, double *x, double *last_x, const double *y_bar, double *y, double *last_y, Ctrl *ctrl);
     void set_ctrl(Ctrl *ctrl, double sigma, double lambda_max, int reset_k);
     void pack(const double *scalars, double *host);  // a member's device scalars and the host block they go to
+    // The kernels on either side of the loop (DESIGN.md "Many small LPs", group re-solve; many.cpp: set_data_many, resolve_many).
+    // Order inside a stage: fill, bound codes, row codes, [restart copy, ctrl], start_in, start_col, start_row, [check x ... gap],
+    // lu, [movement], data_in, data_bc, unscale, [all finalize items].  fill(x, +0.0, n) leaves the bits of a memset.
+    void fill(double *x, double a, int n);
+    void bound_codes(int n, const double *l, const double *u, unsigned char *code);
+    void row_codes(int m, const double *AL, const double *AU, unsigned char *code);
+    void start_in(const StartInArgs &a);
+    void start_col(const CsrDev &AT, const double *ybar_full, const double *c, const double *l, const double *u, const double *x_bar, double *z_bar,
+                   double *partials);
+    void start_row(const CsrDev &A, const double *xbar_full, const double *AL, const double *AU, const double *y_bar, double *y_obj, double *partials);
+    void lu(int n, const double *x_bar, const double *l, const double *u, const double *col_norm, double *x_temp, double *partials);  // kReduceBlocks partials
+    void data_in(const DataInArgs &a);  // stride kReduceBlocks, as the member's own launch
+    void data_bc(const DataBcArgs &a);
+    void unscale(int n, int m, const double *x_bar, const double *y_bar, const double *z_bar, const double *col_norm, const double *row_norm,
+                 double b_scale, double c_scale, double *xo, double *yo, double *zo);
+    long tables_sent() const;  // host-to-device copies of the tables so far (one per run() that had a table to send)
+    int recorded_launches() const;  // what run() would issue for the records held now
     // What is recorded from here on runs after everything recorded so far, finalize included (one run, one copy of the tables
     // all the same).  Needed where a later kernel overwrites partials an earlier finalize reads: an evaluation's Rd writes part_x,
     // where the check step before it left the partials of c.x -- alone, the member finalises the check step in between.

@@ -1946,10 +1946,11 @@ void launch_restart_copy(int n, int m, const double *x_bar, double *x, double *l
                        y_bar, y, last_y, ctrl);
 }
 
-__global__ void __launch_bounds__(kThreads) k_lu(int n, const double *x_bar, const double *l, const double *u,
-                                                const double *col_norm, double *x_temp, double *partials) {
+// (the body of k_lu and of k_lu_many: workgroup `bid` of `grid`)
+__device__ __forceinline__ void lu_body(int n, const double *x_bar, const double *l, const double *u, const double *col_norm, double *x_temp,
+                                        double *partials, int bid, int grid) {
     double acc[1] = {0.0};
-    const int tid = blockIdx.x * kThreads + threadIdx.x, nth = gridDim.x * kThreads;
+    const int tid = bid * kThreads + threadIdx.x, nth = grid * kThreads;
     for (int i = tid; i < n; i += nth) {
         const double xb = x_bar[i], li = l[i], ui = u[i];
         const double t = (xb < li) ? (li - xb) : ((xb > ui) ? (xb - ui) : 0.0);
@@ -1957,7 +1958,12 @@ __global__ void __launch_bounds__(kThreads) k_lu(int n, const double *x_bar, con
         x_temp[i] = r;
         acc[0] += r * r;
     }
-    block_store_partials<1>(acc, partials, gridDim.x);
+    block_store_partials_at<1>(acc, partials, grid, bid);
+}
+
+__global__ void __launch_bounds__(kThreads) k_lu(int n, const double *x_bar, const double *l, const double *u,
+                                                const double *col_norm, double *x_temp, double *partials) {
+    lu_body(n, x_bar, l, u, col_norm, x_temp, partials, blockIdx.x, gridDim.x);
 }
 
 void launch_lu(int n, const double *x_bar, const double *l, const double *u, const double *col_norm, double *x_temp,
@@ -2702,8 +2708,9 @@ void launch_ray_form(const RayFormArgs &a, double *partials, int nblocks, hipStr
 
 // Warm start: the caller's point (caller's units and numbering) -> the scaled, permuted, projected iteration state.  The inverse
 // of k_unscale's map; positive scaling keeps every bound on its side, so the projection runs on the device's scaled bounds.
-__global__ void __launch_bounds__(kThreads) k_start_in(StartInArgs a) {
-    const int tid = blockIdx.x * kThreads + threadIdx.x, nth = gridDim.x * kThreads;
+// (the body of k_start_in and of k_start_in_many: workgroup `bid` of `grid`)
+__device__ __forceinline__ void start_in_body(const StartInArgs &a, int bid, int grid) {
+    const int tid = bid * kThreads + threadIdx.x, nth = grid * kThreads;
     for (int j = tid; j < a.n; j += nth) {
         const double v = a.x0 ? a.x0[a.pc ? a.pc[j] : j] : 0.0;
         const double xs = fmin(fmax((v * a.col_norm[j]) / a.b_scale, a.l[j]), a.u[j]);
@@ -2722,6 +2729,7 @@ __global__ void __launch_bounds__(kThreads) k_start_in(StartInArgs a) {
         a.y_bar[i] = ys;
     }
 }
+__global__ void __launch_bounds__(kThreads) k_start_in(StartInArgs a) { start_in_body(a, blockIdx.x, gridDim.x); }
 void launch_start_in(const StartInArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(k_start_in, dim3(vec_grid(a.n > a.m ? a.n : a.m)), dim3(kThreads), 0, s, a);
 }
@@ -2731,9 +2739,10 @@ void launch_start_in(const StartInArgs &a, hipStream_t s) {
 // are before the b / c scaling, and leave the partials of |b|^2, |c|^2 of the caller's data and of the scaled data.  Same grid,
 // same element-to-thread map and same block reduction as k_bnorm2 / k_norm2, so the sums over identical inputs are the bits
 // Solver::scale() gets.  nc / nb / m: 0 for a group the caller did not give.
-__global__ void __launch_bounds__(kThreads) k_data_in(DataInArgs a) {
+// (the body of k_data_in and of k_data_in_many: workgroup `bid` of `grid`)
+__device__ __forceinline__ void data_in_body(const DataInArgs &a, int bid, int grid) {
     double acc[4] = {0.0, 0.0, 0.0, 0.0};  // b original, c original, b scaled, c scaled
-    const int tid = blockIdx.x * kThreads + threadIdx.x, nth = gridDim.x * kThreads;
+    const int tid = bid * kThreads + threadIdx.x, nth = grid * kThreads;
     for (int i = tid; i < a.m; i += nth) {
         const int src = a.pr ? a.pr[i] : i;
         const double lo = a.AL_in[src], hi = a.AU_in[src], rn = a.row_norm[i];
@@ -2758,8 +2767,9 @@ __global__ void __launch_bounds__(kThreads) k_data_in(DataInArgs a) {
         a.l[j] = a.l_in[src] * cn;
         a.u[j] = a.u_in[src] * cn;
     }
-    block_store_partials<4>(acc, a.partials, a.stride);
+    block_store_partials_at<4>(acc, a.partials, a.stride, bid);
 }
+__global__ void __launch_bounds__(kThreads) k_data_in(DataInArgs a) { data_in_body(a, blockIdx.x, gridDim.x); }
 void launch_data_in(const DataInArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(k_data_in, dim3(kReduceBlocks), dim3(kThreads), 0, s, a);
 }
@@ -2781,11 +2791,12 @@ __device__ __forceinline__ double bside_sq(double lo, double hi) {
     const double v = fmax(fabs(isinf(lo) ? 0.0 : lo), fabs(isinf(hi) ? 0.0 : hi));
     return v * v;
 }
-__global__ void __launch_bounds__(kThreads) k_data_bc(DataBcArgs a) {
+// (the body of k_data_bc and of k_data_bc_many: workgroup `bid` of `grid`)
+__device__ __forceinline__ void data_bc_body(const DataBcArgs &a, int bid, int grid) {
     const double bs = a.use_bc ? 1.0 / (1.0 + sqrt(a.scalars[S_DATA_B_PRE])) : 1.0;
     const double cs = a.use_bc ? 1.0 / (1.0 + sqrt(a.scalars[S_DATA_C_PRE])) : 1.0;
     double acc[2] = {0.0, 0.0};  // b, c
-    const int tid = blockIdx.x * kThreads + threadIdx.x, nth = gridDim.x * kThreads;
+    const int tid = bid * kThreads + threadIdx.x, nth = grid * kThreads;
     for (int p = tid; 2 * p < a.m; p += nth) {
         const int i = 2 * p;
         if (i + 1 < a.m) {
@@ -2833,22 +2844,29 @@ __global__ void __launch_bounds__(kThreads) k_data_bc(DataBcArgs a) {
             acc[1] += v * v;
         }
     }
-    block_store_partials<2>(acc, a.partials, a.stride);
+    block_store_partials_at<2>(acc, a.partials, a.stride, bid);
 }
+__global__ void __launch_bounds__(kThreads) k_data_bc(DataBcArgs a) { data_bc_body(a, blockIdx.x, gridDim.x); }
 void launch_data_bc(const DataBcArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(k_data_bc, dim3(kReduceBlocks), dim3(kThreads), 0, s, a);
 }
 
-__global__ void __launch_bounds__(kThreads) k_unscale(int n, int m, const double *x_bar, const double *y_bar,
-                                                     const double *z_bar, const double *col_norm,
-                                                     const double *row_norm, double b_scale, double c_scale, double *xo,
-                                                     double *yo, double *zo) {
-    const int tid = blockIdx.x * kThreads + threadIdx.x, nth = gridDim.x * kThreads;
+// (the body of k_unscale and of k_unscale_many: workgroup `bid` of `grid`)
+__device__ __forceinline__ void unscale_body(int n, int m, const double *x_bar, const double *y_bar, const double *z_bar, const double *col_norm,
+                                             const double *row_norm, double b_scale, double c_scale, double *xo, double *yo, double *zo, int bid,
+                                             int grid) {
+    const int tid = bid * kThreads + threadIdx.x, nth = grid * kThreads;
     for (int i = tid; i < n; i += nth) {
         xo[i] = (x_bar[i] / col_norm[i]) * b_scale;
         zo[i] = (z_bar[i] * col_norm[i]) * c_scale;
     }
     for (int i = tid; i < m; i += nth) yo[i] = (y_bar[i] / row_norm[i]) * c_scale;
+}
+__global__ void __launch_bounds__(kThreads) k_unscale(int n, int m, const double *x_bar, const double *y_bar,
+                                                     const double *z_bar, const double *col_norm,
+                                                     const double *row_norm, double b_scale, double c_scale, double *xo,
+                                                     double *yo, double *zo) {
+    unscale_body(n, m, x_bar, y_bar, z_bar, col_norm, row_norm, b_scale, c_scale, xo, yo, zo, blockIdx.x, gridDim.x);
 }
 void launch_unscale(int n, int m, const double *x_bar, const double *y_bar, const double *z_bar,
                     const double *col_norm, const double *row_norm, double b_scale, double c_scale, double *xo,
@@ -3009,6 +3027,86 @@ __global__ void __launch_bounds__(kWave) k_pack_scalars(const double *const *__r
     if (threadIdx.x < kNumScalars) dst[blockIdx.x * kNumScalars + threadIdx.x] = src[blockIdx.x][threadIdx.x];
 }
 
+// ---- the elementwise kernels and the bound codes (the group scaling further down records them too)
+enum VecOp : int { kVecFill = 0, kVecMul = 1, kVecDiv = 2, kVecScal = 3, kVecExpClamp = 4 };
+struct VecTask {  // k_fill, k_vec_scale (multiply / divide), k_vec_scal, k_exp_clamp
+    double *x;
+    const double *s;
+    double a;
+    int n, op;
+};
+struct CodesTask {  // k_bound_codes (a = l, b = u) / k_row_codes (a = AL, b = AU)
+    int n;
+    const double *a, *b;
+    unsigned char *code;
+};
+static int elem_grid(int n) { return (n + kThreads - 1) / kThreads; }
+
+__global__ void __launch_bounds__(kThreads) k_vec_many(const VecTask *__restrict__ tasks, const int2 *__restrict__ wgmap) {
+    const int2 w = wgmap[blockIdx.x];
+    const VecTask t = tasks[w.x];
+    switch (t.op) {  // (uniform in the workgroup)
+        case kVecFill: fill_body(t.x, t.a, t.n, w.y); break;
+        case kVecMul: vec_scale_body(t.x, t.s, t.n, 0, w.y); break;
+        case kVecDiv: vec_scale_body(t.x, t.s, t.n, 1, w.y); break;
+        case kVecScal: vec_scal_body(t.x, t.a, t.n, w.y); break;
+        default: exp_clamp_body(t.x, t.n, w.y); break;
+    }
+}
+__global__ void __launch_bounds__(kThreads) k_bound_codes_many(const CodesTask *__restrict__ tasks, const int2 *__restrict__ wgmap) {
+    const int2 w = wgmap[blockIdx.x];
+    const CodesTask t = tasks[w.x];
+    bound_codes_body(t.n, t.a, t.b, t.code, w.y);
+}
+__global__ void __launch_bounds__(kThreads) k_row_codes_many(const CodesTask *__restrict__ tasks, const int2 *__restrict__ wgmap) {
+    const int2 w = wgmap[blockIdx.x];
+    const CodesTask t = tasks[w.x];
+    row_codes_body(t.n, t.a, t.b, t.code, w.y);
+}
+
+// ---- group re-solve (DESIGN.md "Many small LPs", group re-solve): the kernels on either side of the loop.  The two data passes
+// and k_lu keep the member's own shape, kReduceBlocks workgroups (task = blockIdx.x / kReduceBlocks, no table), so all 512
+// partials of every sum are stored and k_finalize_many adds the same operands in the same order; the start and the solution run
+// on the member's vec_grid through the {task, lb} map.
+struct StartInTask {
+    StartInArgs a;
+    int grid;  // of the member's own launch (vec_grid)
+};
+struct LuTask {
+    int n;
+    const double *x_bar, *l, *u, *col_norm;
+    double *x_temp, *partials;
+};
+struct UnscaleTask {
+    int n, m;
+    const double *x_bar, *y_bar, *z_bar, *col_norm, *row_norm;
+    double b_scale, c_scale;
+    double *xo, *yo, *zo;
+    int grid;  // of the member's own launch (vec_grid)
+};
+__global__ void __launch_bounds__(kThreads) k_data_in_many(const DataInArgs *__restrict__ tasks) {
+    const DataInArgs t = tasks[blockIdx.x / kReduceBlocks];
+    data_in_body(t, blockIdx.x % kReduceBlocks, kReduceBlocks);
+}
+__global__ void __launch_bounds__(kThreads) k_data_bc_many(const DataBcArgs *__restrict__ tasks) {
+    const DataBcArgs t = tasks[blockIdx.x / kReduceBlocks];
+    data_bc_body(t, blockIdx.x % kReduceBlocks, kReduceBlocks);
+}
+__global__ void __launch_bounds__(kThreads) k_start_in_many(const StartInTask *__restrict__ tasks, const int2 *__restrict__ wgmap) {
+    const int2 w = wgmap[blockIdx.x];
+    const StartInTask t = tasks[w.x];
+    start_in_body(t.a, w.y, t.grid);
+}
+__global__ void __launch_bounds__(kThreads) k_lu_many(const LuTask *__restrict__ tasks) {
+    const LuTask t = tasks[blockIdx.x / kReduceBlocks];
+    lu_body(t.n, t.x_bar, t.l, t.u, t.col_norm, t.x_temp, t.partials, blockIdx.x % kReduceBlocks, kReduceBlocks);
+}
+__global__ void __launch_bounds__(kThreads) k_unscale_many(const UnscaleTask *__restrict__ tasks, const int2 *__restrict__ wgmap) {
+    const int2 w = wgmap[blockIdx.x];
+    const UnscaleTask t = tasks[w.x];
+    unscale_body(t.n, t.m, t.x_bar, t.y_bar, t.z_bar, t.col_norm, t.row_norm, t.b_scale, t.c_scale, t.xo, t.yo, t.zo, w.y, t.grid);
+}
+
 bool group_form_fits(const CsrDev &M) { return !M.tiled.valid && M.nlong == 0 && M.nblk > 0; }
 
 namespace {
@@ -3038,9 +3136,20 @@ struct GroupStage {
     std::vector<MovementTask> mov;
     std::vector<RestartCopyTask> rc;
     std::vector<SetCtrlTask> sc;
+    // the group re-solve's kinds (set_data_many / resolve_many only)
+    std::vector<VecTask> fill;
+    std::vector<CodesTask> lu_codes, row_codes;
+    std::vector<StartInTask> start_in;
+    std::vector<GroupTask<StartColEpi>> start_col;
+    std::vector<GroupTask<StartRowEpi>> start_row;
+    std::vector<LuTask> lu;
+    std::vector<DataInArgs> data_in;
+    std::vector<DataBcArgs> data_bc;
+    std::vector<UnscaleTask> unscale;
     bool empty() const {
         return xs.empty() && ys.empty() && rd.empty() && rp.empty() && rpg.empty() && gap.empty() && fin.empty() && mov.empty() && rc.empty() &&
-               sc.empty();
+               sc.empty() && fill.empty() && lu_codes.empty() && row_codes.empty() && start_in.empty() && start_col.empty() && start_row.empty() &&
+               lu.empty() && data_in.empty() && data_bc.empty() && unscale.empty();
     }
 };
 
@@ -3053,6 +3162,7 @@ struct GroupLaunches::Impl {
     const double *pack_one = nullptr;  // ... or the one member's scalars
     int pack_n = 0, deliver_n = 0;   // members to pack (fetch) / to hand their scalars (deliver)
     SmallTaskBuf buf;
+    long tables_sent = 0;  // copies of the tables so far
     DBuf<double> packed_d;
     HBuf<double> packed_h;
     std::vector<double *> deliver_to;
@@ -3117,6 +3227,48 @@ void GroupLaunches::pack(const double *scalars, double *host) {
     impl->pack_src.push_back(scalars);
     impl->pack_dst.push_back(host);
 }
+void GroupLaunches::fill(double *x, double a, int n) {
+    if (n > 0) impl->st().fill.push_back({x, nullptr, a, n, kVecFill});
+}
+void GroupLaunches::bound_codes(int n, const double *l, const double *u, unsigned char *code) {
+    if (n > 0) impl->st().lu_codes.push_back({n, l, u, code});
+}
+void GroupLaunches::row_codes(int m, const double *AL, const double *AU, unsigned char *code) {
+    if (m > 0) impl->st().row_codes.push_back({m, AL, AU, code});
+}
+void GroupLaunches::start_in(const StartInArgs &a) { impl->st().start_in.push_back({a, vec_grid(a.n > a.m ? a.n : a.m)}); }
+void GroupLaunches::start_col(const CsrDev &AT, const double *ybar_full, const double *c, const double *l, const double *u, const double *x_bar,
+                              double *z_bar, double *partials) {
+    impl->st().start_col.push_back({stream_part(AT), StartColEpi{{ybar_full}, c, l, u, x_bar, z_bar, partials, AT.grid()}});
+}
+void GroupLaunches::start_row(const CsrDev &A, const double *xbar_full, const double *AL, const double *AU, const double *y_bar, double *y_obj,
+                              double *partials) {
+    impl->st().start_row.push_back({stream_part(A), StartRowEpi{{xbar_full}, AL, AU, y_bar, y_obj, partials, A.grid()}});
+}
+void GroupLaunches::lu(int n, const double *x_bar, const double *l, const double *u, const double *col_norm, double *x_temp, double *partials) {
+    impl->st().lu.push_back({n, x_bar, l, u, col_norm, x_temp, partials});
+}
+void GroupLaunches::data_in(const DataInArgs &a) {
+    if (a.stride != kReduceBlocks) throw std::runtime_error("group data pass: the partials' stride is the member's own grid");
+    impl->st().data_in.push_back(a);
+}
+void GroupLaunches::data_bc(const DataBcArgs &a) {
+    if (a.stride != kReduceBlocks) throw std::runtime_error("group data pass: the partials' stride is the member's own grid");
+    impl->st().data_bc.push_back(a);
+}
+void GroupLaunches::unscale(int n, int m, const double *x_bar, const double *y_bar, const double *z_bar, const double *col_norm,
+                            const double *row_norm, double b_scale, double c_scale, double *xo, double *yo, double *zo) {
+    impl->st().unscale.push_back({n, m, x_bar, y_bar, z_bar, col_norm, row_norm, b_scale, c_scale, xo, yo, zo, vec_grid(n > m ? n : m)});
+}
+long GroupLaunches::tables_sent() const { return impl->tables_sent; }
+int GroupLaunches::recorded_launches() const {  // (every kind present in a stage is one launch, the stage's finalize items one more)
+    int n = 0;
+    for (const GroupStage &t : impl->stages)
+        n += !t.xs.empty() + !t.ys.empty() + !t.rd.empty() + !t.rp.empty() + !t.rpg.empty() + !t.gap.empty() + !t.fin.empty() + !t.mov.empty() +
+             !t.rc.empty() + !t.sc.empty() + !t.fill.empty() + !t.lu_codes.empty() + !t.row_codes.empty() + !t.start_in.empty() +
+             !t.start_col.empty() + !t.start_row.empty() + !t.lu.empty() + !t.data_in.empty() + !t.data_bc.empty() + !t.unscale.empty();
+    return n;
+}
 
 int GroupLaunches::run(hipStream_t s) {
     Impl &g = *impl;
@@ -3127,7 +3279,16 @@ int GroupLaunches::run(hipStream_t s) {
         int nwg = 0;
     };
     struct Spots {
-        Spot x, y, rd, rp, rpg, gap, fin, mov, rc, sc;
+        Spot x, y, rd, rp, rpg, gap, fin, mov, rc, sc, fill, lu_codes, row_codes, start_in, start_col, start_row, lu, data_in, data_bc, unscale;
+    };
+    // (the kinds of the group re-solve: a table for two tasks and more, with a {task, lb} map where the member's grid is its own)
+    auto plain_table = [&](const auto &tasks, Spot &sp) {
+        if (tasks.size() > 1) sp.tasks = g.put(tasks.data(), tasks.size() * sizeof(tasks[0]));
+    };
+    auto mapped_table = [&](const auto &tasks, Spot &sp, auto grid_of) {
+        if (tasks.size() < 2) return;
+        sp.tasks = g.put(tasks.data(), tasks.size() * sizeof(tasks[0]));
+        sp.map = g.put_map(tasks, grid_of, &sp.nwg);
     };
     std::vector<Spots> spots(g.stages.size());
     // A kind with ONE task is that member's own launch, arguments in the launch and no table: a group of one (or the last member
@@ -3145,6 +3306,16 @@ int GroupLaunches::run(hipStream_t s) {
             p.rc.map = g.put_map(t.rc, [](const RestartCopyTask &r) { return r.grid; }, &p.rc.nwg);
         }
         if (t.sc.size() > 1) p.sc.tasks = g.put(t.sc.data(), t.sc.size() * sizeof(SetCtrlTask));
+        mapped_table(t.fill, p.fill, [](const VecTask &v) { return elem_grid(v.n); });
+        mapped_table(t.lu_codes, p.lu_codes, [](const CodesTask &c) { return elem_grid(c.n); });
+        mapped_table(t.row_codes, p.row_codes, [](const CodesTask &c) { return elem_grid(c.n); });
+        mapped_table(t.start_in, p.start_in, [](const StartInTask &v) { return v.grid; });
+        spmv_tables(t.start_col, p.start_col);
+        spmv_tables(t.start_row, p.start_row);
+        plain_table(t.lu, p.lu);
+        plain_table(t.data_in, p.data_in);
+        plain_table(t.data_bc, p.data_bc);
+        mapped_table(t.unscale, p.unscale, [](const UnscaleTask &v) { return v.grid; });
         spmv_tables(t.xs, p.x);
         spmv_tables(t.ys, p.y);
         spmv_tables(t.rd, p.rd);
@@ -3160,6 +3331,7 @@ int GroupLaunches::run(hipStream_t s) {
     if (!g.bytes.empty()) {
         std::memcpy(g.buf.stage(g.bytes.size()), g.bytes.data(), g.bytes.size());
         g.buf.send(g.bytes.size(), s);
+        ++g.tables_sent;
     }
     const char *dev = static_cast<const char *>(g.buf.dev);
     auto launched = [&]() {
@@ -3182,11 +3354,39 @@ int GroupLaunches::run(hipStream_t s) {
                            reinterpret_cast<const int2 *>(dev + sp.map));
         launched();
     };
-    // ---- stage by stage one launch per kind present, in the order of a member's own calls: restart copy, ctrl, check x / y,
-    // residuals, gap, movement, then every finalize item of the stage
+    // (the kinds of the group re-solve: ONE task is the member's own launch -- `own` issues it --, two and more go through the
+    // table: with a {task, lb} map on the members' own grids, or kReduceBlocks workgroups per task and no map)
+    auto mapped_launch = [&](auto kernel, const auto &tasks, const Spot &sp, auto own) {
+        using Task = std::decay_t<decltype(tasks[0])>;
+        if (tasks.size() == 1) {
+            own(tasks[0]);
+            launched();
+        } else if (sp.nwg > 0) {
+            hipLaunchKernelGGL(kernel, dim3(sp.nwg), dim3(kThreads), 0, s, reinterpret_cast<const Task *>(dev + sp.tasks),
+                               reinterpret_cast<const int2 *>(dev + sp.map));
+            launched();
+        }
+    };
+    auto reduce_launch = [&](auto kernel, const auto &tasks, const Spot &sp, auto own) {
+        using Task = std::decay_t<decltype(tasks[0])>;
+        if (tasks.size() == 1) {
+            own(tasks[0]);
+            launched();
+        } else if (tasks.size() > 1) {
+            hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(tasks.size()) * kReduceBlocks), dim3(kThreads), 0, s,
+                               reinterpret_cast<const Task *>(dev + sp.tasks));
+            launched();
+        }
+    };
+    // ---- stage by stage one launch per kind present, in the order of a member's own calls: zeroing, bound codes, restart copy,
+    // ctrl, the start, check x / y, residuals, gap, iteration-0 bound violation, movement, the two data passes, the solution, then
+    // every finalize item of the stage
     for (size_t i = 0; i < g.stages.size(); ++i) {
         GroupStage &t = g.stages[i];
         const Spots &p = spots[i];
+        mapped_launch(k_vec_many, t.fill, p.fill, [&](const VecTask &v) { launch_fill(v.x, v.a, v.n, s); });
+        mapped_launch(k_bound_codes_many, t.lu_codes, p.lu_codes, [&](const CodesTask &v) { launch_bound_codes(v.n, v.a, v.b, v.code, s); });
+        mapped_launch(k_row_codes_many, t.row_codes, p.row_codes, [&](const CodesTask &v) { launch_row_codes(v.n, v.a, v.b, v.code, s); });
         if (t.rc.size() == 1) {
             const RestartCopyTask &r = t.rc[0];
             launch_restart_copy(r.n, r.m, r.x_bar, r.x, r.last_x, r.y_bar, r.y, r.last_y, r.ctrl, s);
@@ -3205,12 +3405,17 @@ int GroupLaunches::run(hipStream_t s) {
                                reinterpret_cast<const SetCtrlTask *>(dev + p.sc.tasks), n);
             launched();
         }
+        mapped_launch(k_start_in_many, t.start_in, p.start_in, [&](const StartInTask &v) { launch_start_in(v.a, s); });
+        spmv_launch(t.start_col, p.start_col);
+        spmv_launch(t.start_row, p.start_row);
         spmv_launch(t.xs, p.x);
         spmv_launch(t.ys, p.y);
         spmv_launch(t.rd, p.rd);
         spmv_launch(t.rp, p.rp);
         spmv_launch(t.rpg, p.rpg);
         spmv_launch(t.gap, p.gap);
+        reduce_launch(k_lu_many, t.lu, p.lu,
+                      [&](const LuTask &v) { launch_lu(v.n, v.x_bar, v.l, v.u, v.col_norm, v.x_temp, v.partials, kReduceBlocks, s); });
         if (t.mov.size() == 1) {
             const MovementTask &v = t.mov[0];
             launch_movement(v.n, v.m, v.x_bar, v.last_x, v.x_temp, v.y_bar, v.last_y, v.y_temp, v.partials, v.stride, kReduceBlocks, s);
@@ -3220,6 +3425,11 @@ int GroupLaunches::run(hipStream_t s) {
                                reinterpret_cast<const MovementTask *>(dev + p.mov.tasks));
             launched();
         }
+        reduce_launch(k_data_in_many, t.data_in, p.data_in, [&](const DataInArgs &v) { launch_data_in(v, s); });
+        reduce_launch(k_data_bc_many, t.data_bc, p.data_bc, [&](const DataBcArgs &v) { launch_data_bc(v, s); });
+        mapped_launch(k_unscale_many, t.unscale, p.unscale, [&](const UnscaleTask &v) {
+            launch_unscale(v.n, v.m, v.x_bar, v.y_bar, v.z_bar, v.col_norm, v.row_norm, v.b_scale, v.c_scale, v.xo, v.yo, v.zo, s);
+        });
         if (one_members_items(t.fin)) {
             FinalizeArgs f{};
             for (const FinalizeOne &o : t.fin) f.item[f.n++] = o.it;
@@ -3276,13 +3486,7 @@ void GroupLaunches::deliver() {
 // member's own grid -- ceil(len / kThreads) for the elementwise kernels, csr_grid() for the matrix passes, kReduceBlocks for the
 // two reductions (task = blockIdx.x / kReduceBlocks, no table) -- so every value, partial and finalised sum is the member's own.
 // ------------------------------------------------------------------------------------------------
-enum VecOp : int { kVecFill = 0, kVecMul = 1, kVecDiv = 2, kVecScal = 3, kVecExpClamp = 4 };
-struct VecTask {  // k_fill, k_vec_scale (multiply / divide), k_vec_scal, k_exp_clamp
-    double *x;
-    const double *s;
-    double a;
-    int n, op;
-};
+// (VecTask / k_vec_many and CodesTask / k_bound_codes_many / k_row_codes_many stand further up: the group re-solve records them too)
 struct ReduceTask {  // k_bnorm2 (a = AL, b = AU) / k_norm2 (a = x)
     const double *a, *b;
     int n;
@@ -3297,23 +3501,7 @@ struct ScaleMatTask {
     const double *rowvec, *colvec;
     double *next_norm;
 };
-struct CodesTask {  // k_bound_codes (a = l, b = u) / k_row_codes (a = AL, b = AU)
-    int n;
-    const double *a, *b;
-    unsigned char *code;
-};
 
-__global__ void __launch_bounds__(kThreads) k_vec_many(const VecTask *__restrict__ tasks, const int2 *__restrict__ wgmap) {
-    const int2 w = wgmap[blockIdx.x];
-    const VecTask t = tasks[w.x];
-    switch (t.op) {  // (uniform in the workgroup)
-        case kVecFill: fill_body(t.x, t.a, t.n, w.y); break;
-        case kVecMul: vec_scale_body(t.x, t.s, t.n, 0, w.y); break;
-        case kVecDiv: vec_scale_body(t.x, t.s, t.n, 1, w.y); break;
-        case kVecScal: vec_scal_body(t.x, t.a, t.n, w.y); break;
-        default: exp_clamp_body(t.x, t.n, w.y); break;
-    }
-}
 __global__ void __launch_bounds__(kThreads) k_bnorm2_many(const ReduceTask *__restrict__ tasks) {
     const ReduceTask t = tasks[blockIdx.x / kReduceBlocks];
     bnorm2_body(t.a, t.b, t.n, t.partials, blockIdx.x % kReduceBlocks, kReduceBlocks);
@@ -3338,16 +3526,6 @@ __global__ void __launch_bounds__(kThreads) k_scale_matrix_many(const ScaleMatTa
     const ScaleMatTask t = tasks[w.x];
     __shared__ double rsv[kWavesPerBlock][kStreamW];
     scale_matrix_body<ROW_FIRST, DIVIDE, NEXT>(t.A.nblk, t.A.blk, t.A.rowptr, t.A.col, const_cast<double *>(t.A.val), t.rowvec, t.colvec, t.next_norm, w.y, rsv);
-}
-__global__ void __launch_bounds__(kThreads) k_bound_codes_many(const CodesTask *__restrict__ tasks, const int2 *__restrict__ wgmap) {
-    const int2 w = wgmap[blockIdx.x];
-    const CodesTask t = tasks[w.x];
-    bound_codes_body(t.n, t.a, t.b, t.code, w.y);
-}
-__global__ void __launch_bounds__(kThreads) k_row_codes_many(const CodesTask *__restrict__ tasks, const int2 *__restrict__ wgmap) {
-    const int2 w = wgmap[blockIdx.x];
-    const CodesTask t = tasks[w.x];
-    row_codes_body(t.n, t.a, t.b, t.code, w.y);
 }
 
 // One segment of a recording: tasks that do not depend on each other except in the fixed order of the kinds below, which is the
@@ -3379,8 +3557,6 @@ struct ScaleLaunches::Impl {
 
 ScaleLaunches::ScaleLaunches() : impl(new Impl()) {}
 ScaleLaunches::~ScaleLaunches() = default;
-
-static int elem_grid(int n) { return (n + kThreads - 1) / kThreads; }
 
 void ScaleLaunches::fill(double *x, double a, int n) {
     if (n > 0) impl->st().vec.push_back({x, nullptr, a, n, kVecFill});

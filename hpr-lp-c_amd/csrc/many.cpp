@@ -7,15 +7,17 @@
 // running the single kernel's body as workgroup lb of lg of its member), and one copy and one host wait serve the scalars of all
 // members.  The host side -- stopping test, restart rule, sigma update, detection -- is the member's own code (the pieces of
 // Solver::solve_loop), so a member's iterates and results are the bits it gets alone.  A member that cannot join the group launches
-// (Solver::joins_group) issues its own launches inside the same lock-step; so does every member for its iteration-0 evaluation and
-// its ray tests.
+// (Solver::joins_group) issues its own launches inside the same lock-step; so does every member for its iteration-0 evaluation
+// (resolve_many apart: the group re-solve at the end of this file) and its ray tests.
 //
 // Ordering is by stream: for the duration of a call every member works on ONE stream (the first member's), after its own stream
 // has been waited for once; the members' streams come back at exit, after one wait for the group's.
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 
 #include "many.h"
+#include "group_pack.h"
 
 namespace hprlp {
 
@@ -428,6 +430,102 @@ void restart_many(Solver **s, int count, const double *in, double *sigma_out) {
         for (int k = 0; k < count; ++k) sigma_out[k] = s[k]->sigma;
 }
 
+namespace {
+
+// The lock-step loop of run_many from every member's current state, up to loop_finish (the solutions are the caller's).  gl may
+// hold records already (resolve_many: zeroing, ctrl, starts): they run in front of the first evaluation, in the same copy of the
+// tables.  iter0 (null: nobody): the members whose iteration-0 evaluation is recorded into the group as well -- only resolve_many
+// sets it; for everybody else iteration 0 is a member's own, as it always was.
+void loop_many(Solver **s, int count, HPRLP_results *out, GroupCounts &gc, GroupScope &scope, const std::vector<char> &joins, GroupLaunches &gl,
+               const char *iter0) {
+    std::vector<LoopState> ls(static_cast<size_t>(count));
+    std::vector<char> active(static_cast<size_t>(count), 1);
+    for (int k = 0; k < count; ++k) s[k]->loop_begin(&ls[k], &out[k]);
+    SmallTaskBuf buf;
+    std::vector<SmallIterTask> tasks;
+    std::vector<int> flagged;
+    // (between two rounds gl holds the check steps recorded in step 11: they run with the next evaluation, a stage ahead)
+    auto in_group = [&](int k) { return joins[k] && (ls[k].iter > 0 || (iter0 && iter0[k])); };
+    int left = count;
+    while (left > 0) {
+        // 1-3: the evaluation of every active member, one copy of the scalars, one wait.  Iteration 0 (launch_lu, a start's
+        // evaluation) is a member's own, and so is everything of a member outside the group launches.
+        for (int k = 0; k < count; ++k) {
+            if (!active[k]) continue;
+            if (in_group(k)) {
+                s[k]->loop_enqueue_evaluation(&ls[k], &gl);
+                ++gc.served;
+            }
+            gl.pack(s[k]->scal.p, s[k]->scal_h.p);
+        }
+        gc.group_launches += gl.run(scope.group);
+        for (int k = 0; k < count; ++k) {
+            if (!active[k]) continue;
+            if (in_group(k)) {
+                if (s[k]->loop_enqueue_ray(&ls[k])) ++gc.own;  // (between the group's kernels and the group's copy)
+            } else {
+                s[k]->loop_enqueue_evaluation(&ls[k], nullptr, false);
+                ++gc.own;
+            }
+        }
+        run_fetch_wait(gl, scope.group, gc);
+        ++gc.rounds;
+        // 4: every member's status and restart flag; finished members drop out
+        flagged.clear();
+        for (int k = 0; k < count; ++k) {
+            if (!active[k]) continue;
+            ++s[k]->fetches;
+            if (!s[k]->loop_status(&ls[k])) {
+                s[k]->loop_finish(&ls[k]);
+                active[k] = 0;
+                --left;
+                continue;
+            }
+            if (ls[k].restarted) flagged.push_back(k);
+        }
+        if (!flagged.empty()) {
+            // 5-6: movement of the flagged members
+            for (int k : flagged) {
+                s[k]->loop_movement(&ls[k], joins[k] ? &gl : nullptr);
+                if (!joins[k]) ++gc.own;
+                gl.pack(s[k]->scal.p, s[k]->scal_h.p);
+            }
+            gc.group_launches += gl.run(scope.group);
+            run_fetch_wait(gl, scope.group, gc);
+            // 7-9: each one's sigma rule on the host; restart copy, ctrl, check step and gap
+            for (int k : flagged) {
+                ++s[k]->fetches;
+                s[k]->loop_restart(&ls[k], joins[k] ? &gl : nullptr);
+                if (!joins[k]) ++gc.own;
+                gl.pack(s[k]->scal.p, s[k]->scal_h.p);
+            }
+            gc.group_launches += gl.run(scope.group);
+            run_fetch_wait(gl, scope.group, gc);
+            for (int k : flagged) ++s[k]->fetches;
+        }
+        // 10: the normal iterations of all small-path members, one launch per class
+        tasks.clear();
+        for (int k = 0; k < count; ++k) {
+            if (!active[k]) continue;
+            s[k]->loop_plan(&ls[k]);  // (a restart's weighted norm consumed: the rare lambda bump inside is the member's own launch)
+            if (on_small_path(s[k]) && ls[k].pending > 0) tasks.push_back(SmallIterTask{s[k]->small_args(), 0, ls[k].pending});
+        }
+        const int it_launches = launch_small_iterations_many(tasks.data(), static_cast<int>(tasks.size()), buf, scope.group);
+        gc.launches += it_launches;
+        gc.group_launches += it_launches;
+        // 11: the check step: recorded for the members of the group launches (it runs in front of the next round's evaluation,
+        // same stream); members off the small path run their normal iterations first
+        for (int k = 0; k < count; ++k) {
+            if (!active[k]) continue;
+            s[k]->loop_advance(&ls[k], on_small_path(s[k]), joins[k] ? &gl : nullptr);
+            if (!joins[k] && ls[k].pending >= 0) ++gc.own;
+        }
+        gl.next_stage();  // (the evaluation's Rd overwrites the partials the check step's finalize reads)
+    }
+}
+
+}  // namespace
+
 void run_many(Solver **s, int count, HPRLP_results *out, GroupCounts *counts) {
     check_group(s, count, "run_many");
     if (!out) throw std::runtime_error("run_many: null results");
@@ -435,92 +533,276 @@ void run_many(Solver **s, int count, HPRLP_results *out, GroupCounts *counts) {
     {
         GroupScope scope(s, count);
         const std::vector<char> joins = who_joins(s, count);
-        std::vector<LoopState> ls(static_cast<size_t>(count));
-        std::vector<char> active(static_cast<size_t>(count), 1);
-        for (int k = 0; k < count; ++k) s[k]->loop_begin(&ls[k], &out[k]);
-        SmallTaskBuf buf;
-        std::vector<SmallIterTask> tasks;
-        std::vector<int> flagged;
-        GroupLaunches gl;  // (between two rounds it holds the check steps recorded in step 11: they run with the next evaluation, a stage ahead)
-        int left = count;
-        while (left > 0) {
-            // 1-3: the evaluation of every active member, one copy of the scalars, one wait.  Iteration 0 (launch_lu, a start's
-            // evaluation) is a member's own, and so is everything of a member outside the group launches.
-            for (int k = 0; k < count; ++k) {
-                if (!active[k]) continue;
-                if (joins[k] && ls[k].iter > 0) {
-                    s[k]->loop_enqueue_evaluation(&ls[k], &gl);
-                    ++gc.served;
-                }
-                gl.pack(s[k]->scal.p, s[k]->scal_h.p);
-            }
-            gc.group_launches += gl.run(scope.group);
-            for (int k = 0; k < count; ++k) {
-                if (!active[k]) continue;
-                if (joins[k] && ls[k].iter > 0) {
-                    if (s[k]->loop_enqueue_ray(&ls[k])) ++gc.own;  // (between the group's kernels and the group's copy)
-                } else {
-                    s[k]->loop_enqueue_evaluation(&ls[k], nullptr, false);
-                    ++gc.own;
-                }
-            }
-            run_fetch_wait(gl, scope.group, gc);
-            ++gc.rounds;
-            // 4: every member's status and restart flag; finished members drop out
-            flagged.clear();
-            for (int k = 0; k < count; ++k) {
-                if (!active[k]) continue;
-                ++s[k]->fetches;
-                if (!s[k]->loop_status(&ls[k])) {
-                    s[k]->loop_finish(&ls[k]);
-                    active[k] = 0;
-                    --left;
-                    continue;
-                }
-                if (ls[k].restarted) flagged.push_back(k);
-            }
-            if (!flagged.empty()) {
-                // 5-6: movement of the flagged members
-                for (int k : flagged) {
-                    s[k]->loop_movement(&ls[k], joins[k] ? &gl : nullptr);
-                    if (!joins[k]) ++gc.own;
-                    gl.pack(s[k]->scal.p, s[k]->scal_h.p);
-                }
-                gc.group_launches += gl.run(scope.group);
-                run_fetch_wait(gl, scope.group, gc);
-                // 7-9: each one's sigma rule on the host; restart copy, ctrl, check step and gap
-                for (int k : flagged) {
-                    ++s[k]->fetches;
-                    s[k]->loop_restart(&ls[k], joins[k] ? &gl : nullptr);
-                    if (!joins[k]) ++gc.own;
-                    gl.pack(s[k]->scal.p, s[k]->scal_h.p);
-                }
-                gc.group_launches += gl.run(scope.group);
-                run_fetch_wait(gl, scope.group, gc);
-                for (int k : flagged) ++s[k]->fetches;
-            }
-            // 10: the normal iterations of all small-path members, one launch per class
-            tasks.clear();
-            for (int k = 0; k < count; ++k) {
-                if (!active[k]) continue;
-                s[k]->loop_plan(&ls[k]);  // (a restart's weighted norm consumed: the rare lambda bump inside is the member's own launch)
-                if (on_small_path(s[k]) && ls[k].pending > 0) tasks.push_back(SmallIterTask{s[k]->small_args(), 0, ls[k].pending});
-            }
-            const int it_launches = launch_small_iterations_many(tasks.data(), static_cast<int>(tasks.size()), buf, scope.group);
-            gc.launches += it_launches;
-            gc.group_launches += it_launches;
-            // 11: the check step: recorded for the members of the group launches (it runs in front of the next round's evaluation,
-            // same stream); members off the small path run their normal iterations first
-            for (int k = 0; k < count; ++k) {
-                if (!active[k]) continue;
-                s[k]->loop_advance(&ls[k], on_small_path(s[k]), joins[k] ? &gl : nullptr);
-                if (!joins[k] && ls[k].pending >= 0) ++gc.own;
-            }
-            gl.next_stage();  // (the evaluation's Rd overwrites the partials the check step's finalize reads)
-        }
+        GroupLaunches gl;
+        loop_many(s, count, out, gc, scope, joins, gl, nullptr);
         for (int k = 0; k < count; ++k) s[k]->collect_solution(&out[k]);
     }
     if (counts) *counts = gc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// group re-solve (DESIGN.md "Many small LPs", group re-solve): set_data and resolve of every member of a group.  The rule is the
+// group launches': a workgroup runs the single kernel's body as workgroup lb of its member's own grid, so every stored number is
+// the member's own; what changes is who issues the launches, how the caller's vectors travel (one pinned block, one copy) and how
+// often the host waits (once per call outside the loop, never once per member).
+// ------------------------------------------------------------------------------------------------
+// The blocks of a group call, kept with member 0 (the owner of the group's stream) and grown on demand: staging of the data / the
+// starts (pinned, and its device copy), the data passes' partials, the solutions (device, and pinned), the launch tables.
+struct GroupBlocks {
+    SmallTaskBuf in;
+    DBuf<double> parts, out_d;
+    HBuf<double> out_h;
+    GroupLaunches gl;
+};
+
+namespace {
+
+GroupBlocks &blocks_of(Solver *owner) {
+    if (!owner->group_blocks) owner->group_blocks = std::make_shared<GroupBlocks>();
+    return *owner->group_blocks;
+}
+
+std::string member(const char *who, int k) { return std::string(who) + ": member " + std::to_string(k); }
+
+}  // namespace
+
+void set_data_many(Solver **s, int count, const MemberData *data, ResolveCounts *counts) {
+    const char *who = "hprlp_solver_set_data_many";
+    // (the list, the count, data and the members have been checked by the caller: abi.cpp owns those refusals, group_members)
+    // ---- the host checks of all members, before the first upload (Solver::set_data's rules)
+    for (int k = 0; k < count; ++k) {
+        const MemberData &d = data[k];
+        const bool bounds = d.AL || d.AU || d.l || d.u;
+        if (bounds && !(d.AL && d.AU && d.l && d.u))
+            throw std::runtime_error(member(who, k) + ": AL, AU, l and u are given together or not at all (b_scale couples them)");
+        auto no_nan = [&](const double *v, long len, const char *what) {
+            for (long i = 0; v && i < len; ++i)
+                if (std::isnan(v[i])) throw std::runtime_error(member(who, k) + ": " + what + "[" + std::to_string(i) + "] is NaN");
+        };
+        no_nan(d.c, s[k]->n, "c"); no_nan(d.AL, s[k]->m, "AL"); no_nan(d.AU, s[k]->m, "AU"); no_nan(d.l, s[k]->n, "l"); no_nan(d.u, s[k]->n, "u");
+        if (d.obj_constant && std::isnan(*d.obj_constant)) throw std::runtime_error(member(who, k) + ": obj_constant is NaN");
+    }
+    ResolveCounts rc;
+    const auto t0 = time_now();
+    GroupScope scope(s, count);
+    const hipStream_t st = scope.group;
+    std::vector<int> in;  // the members of the group launches
+    std::vector<PackMember> pm(static_cast<size_t>(count));
+    for (int k = 0; k < count; ++k) {
+        const MemberData &d = data[k];
+        pm[k].m = s[k]->m_loc, pm[k].n = s[k]->n_loc;
+        pm[k].c = d.c != nullptr, pm[k].bounds = d.AL != nullptr;
+        if ((pm[k].c || pm[k].bounds) && s[k]->joins_group_resolve()) in.push_back(k);
+    }
+    if (in.size() < 2) in.clear();  // (a group of one issues the member's own launches)
+    std::vector<char> joins(static_cast<size_t>(count), 0);
+    for (int k : in) joins[k] = 1;
+    for (int k = 0; k < count; ++k) {
+        const MemberData &d = data[k];
+        if (joins[k]) continue;
+        pm[k].c = pm[k].bounds = false;  // (no room in the group's block)
+        if (!(d.c || d.obj_constant || d.AL)) continue;  // nothing given: the member keeps its bits
+        s[k]->set_data(d.c, d.obj_constant, d.AL, d.AU, d.l, d.u);
+        if (!(d.c || d.AL)) continue;  // (obj_constant alone is a host assignment)
+        ++rc.own;
+        // Solver::set_data, nominal (many.h: ResolveCounts): the staging in one copy, or one per vector from the allocator cache's
+        // block size on; two passes and two finalizes; the scalars' copy and its wait
+        const size_t words = (d.AL ? 2 * static_cast<size_t>(s[k]->m_loc) + 2 * static_cast<size_t>(s[k]->n_loc) : 0) + (d.c ? s[k]->n_loc : 0);
+        rc.h2d += words * sizeof(double) < kDeviceCacheMinBytes ? 1 : (d.AL ? 4 : 0) + (d.c ? 1 : 0);
+        rc.launches += 4, rc.d2h += 1, rc.waits += 1;
+    }
+    const int nj = static_cast<int>(in.size());
+    if (nj > 0) {
+        GroupBlocks &gb = blocks_of(s[0]);
+        try {
+            const GroupPackLayout L = group_pack_layout(pm.data(), count);
+            double *host = static_cast<double *>(gb.in.stage(sizeof(double) * L.data_doubles));
+            for (int k : in) group_pack_data(L, k, pm[k], data[k].AL, data[k].AU, data[k].l, data[k].u, data[k].c, host);
+            gb.in.send(sizeof(double) * L.data_doubles, st);
+            ++rc.h2d;
+            const double *dev = static_cast<const double *>(gb.in.dev);
+            const size_t per = static_cast<size_t>(4) * kReduceBlocks;
+            if (gb.parts.n < per * nj) gb.parts.alloc(per * nj);
+            GroupLaunches &gl = gb.gl;
+            const long tables0 = gl.tables_sent();
+            auto at = [&](size_t off) { return off == kPackAbsent ? nullptr : dev + off; };
+            for (int j = 0; j < nj; ++j) {
+                const int k = in[j];
+                Solver &m = *s[k];
+                m.data_time[0] = m.data_time[1] = m.data_time[2] = 0.0;
+                if (data[k].obj_constant) m.obj_constant = *data[k].obj_constant;
+                const PackSlot &p = L.slot[k];
+                m.data_first_pass(at(p.AL), at(p.AU), at(p.l), at(p.u), at(p.c), pm[k].bounds, gb.parts.p + per * j, &gl);
+            }
+            gl.next_stage();  // (the second pass reads the sums the first pass' finalize leaves in the member's scalars)
+            for (int j = 0; j < nj; ++j) {
+                const int k = in[j];
+                s[k]->data_second_pass(pm[k].bounds, pm[k].c, gb.parts.p + per * j, &gl);
+                gl.pack(s[k]->scal.p, s[k]->scal_h.p);
+            }
+            rc.launches += gl.run(st);
+            const int copies = gl.fetch(st);
+            rc.launches += copies;  // (the packing kernel)
+            rc.d2h += copies;
+            rc.h2d += gl.tables_sent() - tables0;
+            HIP_CHECK(hipStreamSynchronize(st));
+            ++rc.waits;
+            gl.deliver();
+            const double wall = time_since(t0);  // the group call's wall time is every member's
+            for (int k : in) {
+                Solver &m = *s[k];
+                ++m.fetches;
+                m.data_consume(pm[k].bounds, pm[k].c);
+                m.invalidate_far();
+                m.data_time[1] = m.data_time[2] = wall;
+                m.data_since_run += wall;
+                m.set_transfer((pm[k].bounds ? 2 * static_cast<size_t>(m.m_loc) + 2 * static_cast<size_t>(m.n_loc) : 0) + (pm[k].c ? m.n_loc : 0), 0,
+                               false);
+                ++rc.served;
+            }
+        } catch (...) {
+            s[0]->group_blocks.reset();  // (whatever was recorded goes with it)
+            throw;
+        }
+    }
+    if (counts) *counts = rc;
+}
+
+void check_starts(Solver *const *s, int count, const MemberStart *start) {
+    const char *who = "hprlp_solver_resolve_many";
+    for (int k = 0; start && k < count; ++k) {
+        if (std::isnan(start[k].sigma)) throw std::runtime_error(member(who, k) + ": sigma is NaN");
+        auto finite = [&](const double *v, long len, const char *what) {
+            for (long i = 0; v && i < len; ++i)
+                if (!std::isfinite(v[i])) throw std::runtime_error(member(who, k) + ": warm start: " + what + "[" + std::to_string(i) + "] is not finite");
+        };
+        finite(start[k].x0, s[k]->n, "x0");
+        finite(start[k].y0, s[k]->m, "y0");
+    }
+}
+
+void resolve_many(Solver **s, int count, const MemberStart *start, HPRLP_results *out, ResolveCounts *counts) {
+    std::vector<MemberStart> cold;
+    if (!start) {
+        cold.resize(static_cast<size_t>(count));
+        start = cold.data();
+    }
+    ResolveCounts rc;
+    GroupCounts gc;
+    struct TimeBase {  // (Solver::resolve: the reported time starts from the set_data seconds since the previous loop)
+        Solver **s;
+        int count;
+        ~TimeBase() {
+            for (int k = 0; k < count; ++k) s[k]->time_base = -1.0;
+        }
+    };
+    {
+        GroupScope scope(s, count);
+        const hipStream_t st = scope.group;
+        const std::vector<char> joins = who_joins(s, count);
+        std::vector<int> in;
+        for (int k = 0; k < count; ++k)
+            if (joins[k] && s[k]->joins_group_resolve()) in.push_back(k);
+        if (in.size() < 2) in.clear();  // (a group of one issues the member's own launches)
+        std::vector<char> grouped(static_cast<size_t>(count), 0);
+        for (int k : in) grouped[k] = 1;
+        const int nj = static_cast<int>(in.size());
+        // ---- the members that go their own way: Solver::resolve up to its loop
+        for (int k = 0; k < count; ++k) {
+            if (grouped[k]) continue;
+            Solver &m = *s[k];
+            const MemberStart &b = start[k];
+            m.reset_iterates();
+            m.init_iteration_state();
+            if (b.sigma > 0.0) m.set_sigma_lambda(b.sigma, m.lambda_max, true);
+            if (b.x0 || b.y0) m.set_start(b.x0, b.y0);
+            ++rc.own;
+            // (nominal, many.h: ResolveCounts -- what Solver::resolve issues for a member without a locality ordering)
+            rc.memsets += 17, rc.waits += 1;                                        // reset_iterates
+            rc.launches += (m.hook_no_bound_codes ? 0 : 2) + 1 + (b.sigma > 0.0 ? 1 : 0);  // bound codes, ctrl, the override
+            if (b.x0 || b.y0) rc.h2d += (b.x0 ? 1 : 0) + (b.y0 ? 1 : 0), rc.launches += 4, rc.waits += 1;  // set_start
+            rc.launches += 1, rc.d2h += 3, rc.waits += 1;                            // collect_solution (below)
+        }
+        GroupLaunches own_gl;  // (nobody in the group: the loop of run_many with tables of its own)
+        GroupBlocks *gb = nj > 0 ? &blocks_of(s[0]) : nullptr;
+        GroupLaunches &gl = gb ? gb->gl : own_gl;
+        try {
+            std::vector<PackMember> pm(static_cast<size_t>(count));
+            for (int k : in) {
+                pm[k].m = s[k]->m_loc, pm[k].n = s[k]->n_loc;
+                pm[k].x0 = start[k].x0 != nullptr, pm[k].y0 = start[k].y0 != nullptr, pm[k].result = true;
+            }
+            const GroupPackLayout L = group_pack_layout(pm.data(), count);
+            if (nj > 0) {
+                // ---- zeroing, bound codes, ctrl and the starts of the group, recorded: they run in front of the first evaluation
+                const double *dev = nullptr;
+                if (L.start_doubles > 0) {
+                    double *host = static_cast<double *>(gb->in.stage(sizeof(double) * L.start_doubles));
+                    for (int k : in) group_pack_start(L, k, pm[k], start[k].x0, start[k].y0, host);
+                    gb->in.send(sizeof(double) * L.start_doubles, st);
+                    ++rc.h2d;
+                    dev = static_cast<const double *>(gb->in.dev);  // (it outlives the start kernels: no wait between them and the loop)
+                }
+                for (int k : in) {
+                    Solver &m = *s[k];
+                    m.reset_iterates(&gl);
+                    m.init_iteration_state(&gl, start[k].sigma);
+                    if (pm[k].x0 || pm[k].y0) {
+                        m.invalidate_far();
+                        const PackSlot &p = L.slot[k];
+                        m.start_launch(pm[k].x0 && p.x0 != kPackAbsent ? dev + p.x0 : nullptr, pm[k].y0 && p.y0 != kPackAbsent ? dev + p.y0 : nullptr,
+                                       nullptr, nullptr, &gl);
+                    }
+                }
+                rc.launches += gl.recorded_launches();
+                gl.next_stage();  // (the evaluation's Rd / Rp overwrite the partials the start's finalize reads)
+            }
+            {
+                TimeBase tb{s, count};
+                for (int k = 0; k < count; ++k) s[k]->time_base = s[k]->data_since_run;
+                loop_many(s, count, out, gc, scope, joins, gl, grouped.data());
+            }
+            rc.loop_own = gc.own;
+            // ---- the solutions: the group's through one block, one copy and one wait
+            for (int k = 0; k < count; ++k)
+                if (!grouped[k]) s[k]->collect_solution(&out[k]);
+            if (nj > 0) {
+                if (gb->out_d.n < L.result_doubles) {
+                    gb->out_d.alloc(L.result_doubles);
+                    gb->out_h.alloc(L.result_doubles, false);
+                }
+                for (int k : in) {
+                    const PackSlot &p = L.slot[k];
+                    auto at = [&](size_t off) { return off == kPackAbsent ? nullptr : gb->out_d.p + off; };
+                    s[k]->solution_launch(at(p.x), at(p.y), at(p.z), &gl);
+                }
+                const long tables0 = gl.tables_sent();
+                rc.launches += gl.run(st);
+                rc.h2d += gl.tables_sent() - tables0;  // (the tables of what runs in front of the loop ride on the loop's first copy)
+                HIP_CHECK(hipMemcpyAsync(gb->out_h.p, gb->out_d.p, sizeof(double) * L.result_doubles, hipMemcpyDeviceToHost, st));
+                ++rc.d2h;
+                HIP_CHECK(hipStreamSynchronize(st));
+                ++rc.waits;
+                for (int k : in) {
+                    Solver &m = *s[k];
+                    HPRLP_results *o = &out[k];
+                    o->x = static_cast<double *>(std::malloc(sizeof(double) * std::max(m.n_loc, 1)));
+                    o->y = static_cast<double *>(std::malloc(sizeof(double) * std::max(m.m_loc, 1)));
+                    o->z = static_cast<double *>(std::malloc(sizeof(double) * std::max(m.n_loc, 1)));
+                    if (!o->x || !o->y || !o->z) throw std::runtime_error("host allocation of the solution failed");
+                    group_unpack_result(L, k, pm[k], gb->out_h.p, o->x, o->y, o->z);
+                    ++rc.served;
+                }
+            }
+            for (int k = 0; k < count; ++k)
+                s[k]->set_transfer((start[k].x0 ? s[k]->n_loc : 0) + static_cast<size_t>(start[k].y0 ? s[k]->m_loc : 0),
+                                   2 * static_cast<size_t>(s[k]->n_loc) + s[k]->m_loc, false);
+        } catch (...) {
+            if (gb) s[0]->group_blocks.reset();  // (whatever was recorded goes with it)
+            throw;
+        }
+    }
+    if (counts) *counts = rc;
 }
 
 }  // namespace hprlp

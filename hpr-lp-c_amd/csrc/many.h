@@ -42,4 +42,35 @@ void restart_many(Solver **s, int count, const double *in, double *sigma_out);
 // Solver::solve_loop + collect_solution for every member, from its current state
 void run_many(Solver **s, int count, HPRLP_results *out, GroupCounts *counts = nullptr);
 
+// ---- group re-solve (DESIGN.md "Many small LPs", group re-solve) ------------------------------------------------------------
+struct MemberData {   // Solver::set_data's arguments for one member (hprlp_member_data); all null: nothing changes
+    const double *c = nullptr, *obj_constant = nullptr, *AL = nullptr, *AU = nullptr, *l = nullptr, *u = nullptr;
+};
+struct MemberStart {  // Solver::resolve's arguments for one member (hprlp_member_start)
+    const double *x0 = nullptr, *y0 = nullptr;
+    double sigma = -1.0;
+};
+// what a set_data_many / resolve_many call did (hprlp_last_resolve_many_counts): copies host -> device (staging blocks and task
+// tables) and device -> host, host waits, kernel launches and memsets, all OUTSIDE the loop and with the operations of the members
+// that went their own way included; members served by the group launches / that went their own way (a member that gave nothing,
+// or obj_constant only, is neither); resolve_many: the loop's operations issued for one member (GroupCounts::own).  What the
+// group issues is counted where it is issued; what a member on its own issues is NOMINAL: the operations its single entries issue
+// in the common case (staging below the allocator cache's block size: one upload; no locality ordering; code arrays in place)
+struct ResolveCounts {
+    long h2d = 0, d2h = 0, waits = 0, launches = 0, memsets = 0, served = 0, own = 0, loop_own = 0;
+};
+// Solver::set_data for every member.  The members that join (Solver::joins_group_resolve, two at least): all given vectors in one
+// pinned block and one copy, k_data_in_many, finalize, k_data_bc_many, finalize, the scalars packed, one copy back, ONE wait, then
+// each member's host formulas.  Every other member runs its own set_data inside the same call.  The members have passed
+// check_group and data is not null (abi.cpp owns those refusals); throws before anything is written or launched: an incomplete
+// bounds group, a NaN.
+void set_data_many(Solver **s, int count, const MemberData *data, ResolveCounts *counts = nullptr);
+// Solver::resolve for every member: zeroing, bound codes, ctrl (a sigma override included) and the starts of the joining members
+// recorded into the group's launches, the lock-step loop of run_many with their iteration-0 evaluations recorded as well, the
+// solutions through one device block, one copy and one wait.  start null: all cold.  The members have passed check_group, out
+// is not null (abi.cpp owns those refusals) and the starts have passed check_starts.
+// check_starts: throws, naming `member k`, for a NaN sigma or a non-finite start entry; touches nothing.
+void check_starts(Solver *const *s, int count, const MemberStart *start);
+void resolve_many(Solver **s, int count, const MemberStart *start, HPRLP_results *out, ResolveCounts *counts = nullptr);
+
 }  // namespace hprlp

@@ -1545,26 +1545,40 @@ void Solver::read_hooks() {
     hook_store_x = env_get("HPRLP_STORE_X") != nullptr;                // A/B runs: every x-half reads and stores x
 }
 
-void Solver::refresh_bound_codes() {
+void Solver::refresh_bound_codes(GroupLaunches *g) {
     if (hook_no_bound_codes) return;
     if (n_loc > 0) {
         if (lu_code.n != static_cast<size_t>(n_loc)) lu_code.alloc(static_cast<size_t>(n_loc));
-        launch_bound_codes(n_loc, l.p, u.p, lu_code.p, stream);
+        if (g) g->bound_codes(n_loc, l.p, u.p, lu_code.p);
+        else launch_bound_codes(n_loc, l.p, u.p, lu_code.p, stream);
     }
     if (m_loc > 0) {
         if (row_code.n != static_cast<size_t>(m_loc)) row_code.alloc(static_cast<size_t>(m_loc));
-        launch_row_codes(m_loc, AL.p, AU.p, row_code.p, stream);
+        if (g) g->row_codes(m_loc, AL.p, AU.p, row_code.p);
+        else launch_row_codes(m_loc, AL.p, AU.p, row_code.p, stream);
     }
+}
+
+bool Solver::bound_codes_in_place() const {
+    return hook_no_bound_codes || (row_code.n == static_cast<size_t>(m_loc) && lu_code.n == static_cast<size_t>(n_loc));
+}
+
+bool Solver::joins_group_resolve() {
+    return joins_group() && perm_r.empty() && perm_c.empty() && bound_codes_in_place() && !y_exchange_pending && !overlap_enabled;
 }
 
 // Back to the state of a fresh solver after scale() and power_iteration(): every iterate and work vector zero, nothing handed over.
 // (bench.py: the timed iterations and the solve to tolerance of a multi-GPU run use ONE solver -- a second one would need a
 // second set of communicators.)  Call init_iteration_state() / set_sigma_lambda() afterwards, as after create.
-void Solver::reset_iterates() {
+void Solver::reset_iterates(GroupLaunches *g) {
     if (y_exchange_pending) throw std::runtime_error("reset_iterates: an exchange is still pending");
     invalidate_far();
+    static_assert(sizeof(Ctrl) % sizeof(double) == 0, "the group's zeroing fills Ctrl as doubles (+0.0: all bits zero)");
+    // (g: fill tasks of +0.0, the bits of the memsets; the group's launch and wait are the caller's)
     auto zero = [&](double *p, size_t n) {
-        if (p && n > 0) HIP_CHECK(hipMemsetAsync(p, 0, sizeof(double) * n, stream));
+        if (!(p && n > 0)) return;
+        if (g) g->fill(p, 0.0, static_cast<int>(n));
+        else HIP_CHECK(hipMemsetAsync(p, 0, sizeof(double) * n, stream));
     };
     zero(x.p, x.n); zero(last_x.p, last_x.n); zero(z_bar.p, z_bar.n);
     zero(last_y.p, last_y.n); zero(y_obj.p, y_obj.n); zero(y_temp.p, y_temp.n);
@@ -1572,17 +1586,23 @@ void Solver::reset_iterates() {
     zero(gxh.p, gxh.n); zero(gxb.p, gxb.n); zero(gxt.p, gxt.n); zero(gsn.p, gsn.n);
     zero(sm1.p, sm1.n); zero(sn1.p, sn1.n);
     zero(scal.p, scal.n);
+    if (g) {
+        g->fill(reinterpret_cast<double *>(ctrl.p), 0.0, static_cast<int>(sizeof(Ctrl) / sizeof(double)));
+        return;
+    }
     HIP_CHECK(hipMemsetAsync(ctrl.p, 0, sizeof(Ctrl), stream));
     HIP_CHECK(hipStreamSynchronize(stream));
 }
 
-void Solver::init_iteration_state() {  // reference src/HPRLP.cu:154-167
+// g: the bound codes and ctrl recorded; sigma_ > 0 (g only) takes the place of the rule's sigma -- alone the override is a second
+// k_set_ctrl that overwrites every word the first one wrote, so one task with the final sigma leaves the same bits
+void Solver::init_iteration_state(GroupLaunches *g, double sigma_) {  // reference src/HPRLP.cu:154-167
     finish_tiling();
     invalidate_far();
-    refresh_bound_codes();
+    refresh_bound_codes(g);
     if (overlap_enabled && !overlap_ready) prepare_overlap();  // set-up work, not part of the first iteration
     const double s0 = (norm_b > 1e-8 && norm_c > 1e-8) ? norm_b / norm_c : 1.0;
-    set_sigma_lambda(s0, lambda_max, true);
+    set_sigma_lambda(g && sigma_ > 0.0 ? sigma_ : s0, lambda_max, true, g);
 }
 
 // Column split of one shard on the device: local = entries whose column lies in [lo, hi).
@@ -1827,8 +1847,8 @@ void Solver::residuals_launch(int iter, bool compute_gap, GroupLaunches *g) {
     f.item[f.n++] = {part_r.p, gyy, S_RP2};
     if (compute_gap) f.item[f.n++] = {part_r.p + rstride, gyy, S_ADX_DY};
     if (iter == 0) {
-        if (g) throw std::runtime_error("the evaluation of iteration 0 is a member's own");
-        launch_lu(n_loc, x_bar, l.p, u.p, col_norm.p, x_temp, part_v.p, kReduceBlocks, stream);
+        if (g) g->lu(n_loc, x_bar, l.p, u.p, col_norm.p, x_temp, part_v.p);  // (resolve_many only: many.cpp)
+        else launch_lu(n_loc, x_bar, l.p, u.p, col_norm.p, x_temp, part_v.p, kReduceBlocks, stream);
         f.item[f.n++] = {part_v.p, kReduceBlocks, S_LU2};
     }
     if (g) g->finalize(f, scal.p);
@@ -2074,8 +2094,7 @@ void Solver::solve_loop(HPRLP_results *out) {
 void Solver::collect_solution(HPRLP_results *out) {
     // scratch: sn1 (x), sm1 (y), gsn local slice (z)
     double *zo = gsn.p + col_off;
-    launch_unscale(n_loc, m_loc, x_bar, y_bar, z_bar.p, col_norm.p, row_norm.p, b_scale, c_scale, sn1.p, sm1.p, zo,
-                   stream);
+    solution_launch(sn1.p, sm1.p, zo, nullptr);
     out->x = static_cast<double *>(std::malloc(sizeof(double) * std::max(n_loc, 1)));
     out->y = static_cast<double *>(std::malloc(sizeof(double) * std::max(m_loc, 1)));
     out->z = static_cast<double *>(std::malloc(sizeof(double) * std::max(n_loc, 1)));
@@ -2095,6 +2114,12 @@ void Solver::collect_solution(HPRLP_results *out) {
         unpermute(out->z, perm_c);
         unpermute(out->y, perm_r);
     }
+}
+
+// k_unscale into xo (n_loc), yo (m_loc), zo (n_loc), in the solver's numbering (g: recorded)
+void Solver::solution_launch(double *xo, double *yo, double *zo, GroupLaunches *g) {
+    if (g) g->unscale(n_loc, m_loc, x_bar, y_bar, z_bar.p, col_norm.p, row_norm.p, b_scale, c_scale, xo, yo, zo);
+    else launch_unscale(n_loc, m_loc, x_bar, y_bar, z_bar.p, col_norm.p, row_norm.p, b_scale, c_scale, xo, yo, zo, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2211,19 +2236,28 @@ void Solver::set_start(const double *x0, const double *y0) {
 // The kernels of a warm start, on device copies of the caller's vectors (caller's numbering; dpc / dpr: device index -> caller's
 // index, null without a locality ordering).  Returns after the stream has drained: dx / dy are not read afterwards.
 void Solver::start_apply(const double *dx, const double *dy, const int *dpc, const int *dpr) {
+    start_launch(dx, dy, dpc, dpr, nullptr);
+    HIP_CHECK(hipStreamSynchronize(stream));
+}
+
+// start_apply up to its wait (g: recorded; dx / dy must then outlive the group's run)
+void Solver::start_launch(const double *dx, const double *dy, const int *dpc, const int *dpr, GroupLaunches *g) {
     const StartInArgs a{n_loc, m_loc, dx, dy, dpc, dpr, l.p, u.p, col_norm.p, AL.p, AU.p, row_norm.p, b_scale, c_scale,
                         x.p, last_x.p, x_hat, x_bar, y, last_y.p, y_bar};
-    launch_start_in(a, stream);
+    if (g) g->start_in(a);
+    else launch_start_in(a, stream);
     // (one GPU: x_hat, x_bar, y, y_bar are the gathered buffers themselves)
     const int gx = AT.view.grid(), gyy = A.view.grid();
-    launch_start_col(AT.view, gyb.p, c.p, l.p, u.p, x_bar, z_bar.p, part_x.p, stream);
-    launch_start_row(A.view, gxb.p, AL.p, AU.p, y_bar, y_obj.p, part_r.p, stream);
+    if (g) g->start_col(AT.view, gyb.p, c.p, l.p, u.p, x_bar, z_bar.p, part_x.p);
+    else launch_start_col(AT.view, gyb.p, c.p, l.p, u.p, x_bar, z_bar.p, part_x.p, stream);
+    if (g) g->start_row(A.view, gxb.p, AL.p, AU.p, y_bar, y_obj.p, part_r.p);
+    else launch_start_row(A.view, gxb.p, AL.p, AU.p, y_bar, y_obj.p, part_r.p, stream);
     FinalizeArgs f{};
     f.item[f.n++] = {part_x.p, gx, S_CX};
     f.item[f.n++] = {part_x.p + gx, gx, S_XZ};
     f.item[f.n++] = {part_r.p, gyy, S_YOBJ_Y};
-    launch_finalize(f, scal.p, stream);
-    HIP_CHECK(hipStreamSynchronize(stream));
+    if (g) g->finalize(f, scal.p);
+    else launch_finalize(f, scal.p, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2275,13 +2309,11 @@ void Solver::set_data(const double *c_, const double *obj_constant_, const doubl
 void Solver::data_apply(const double *dAL, const double *dAU, const double *dl, const double *du, const double *dc, bool bounds,
                         clock_type::time_point t0) {
     const bool c_ = dc != nullptr;
-    const int mb = bounds ? m_loc : 0, nb = bounds ? n_loc : 0, nc = c_ ? n_loc : 0;
     perms_to_device();
     if (!data_part.p) data_part.alloc_zero(static_cast<size_t>(4) * kReduceBlocks);
     // The bound codes are written by the second pass into the arrays the iteration kernels (and the captured iteration graphs, by
     // pointer) already read.  The graphs hold nothing else of the data: XHalfArgs / YHalfArgs carry pointers, strides and the
     // hand-off flags, sigma and lambda live in ctrl.  Only a code array that has to be allocated here moves a captured pointer.
-    unsigned char *rc = nullptr, *lc = nullptr;
     if (!hook_no_bound_codes && bounds) {
         if (row_code.n != static_cast<size_t>(m_loc) || lu_code.n != static_cast<size_t>(n_loc)) {
             for (auto &kv : graphs) (void)hipGraphExecDestroy(kv.second);
@@ -2290,31 +2322,60 @@ void Solver::data_apply(const double *dAL, const double *dAU, const double *dl, 
             row_code.alloc(static_cast<size_t>(m_loc));
             lu_code.alloc(static_cast<size_t>(n_loc));
         }
-        rc = row_code.p;
-        lc = lu_code.p;
     }
     data_time[0] = time_since(t0);
     const auto t1 = time_now();
+    data_first_pass(dAL, dAU, dl, du, dc, bounds, data_part.p, nullptr);
+    data_second_pass(bounds, c_, data_part.p, nullptr);
+    fetch_scalars();
+    data_consume(bounds, c_);
+    invalidate_far();
+    if (data_stage.cap_bytes >= kDeviceCacheMinBytes) data_stage.release();  // (back to the allocator cache)
+    data_time[1] = time_since(t1);
+    data_time[2] = time_since(t0);
+    data_since_run += data_time[2];
+}
+
+// The pieces of data_apply (g: recorded instead of launched; many.cpp: set_data_many).  part: 4 x kReduceBlocks partials -- the
+// solver's data_part, or a piece of the group's block (where a partial is stored does not change its value).  The second pass
+// reads what the first pass' finalize left in scal: a group records it a stage later.
+void Solver::data_first_pass(const double *dAL, const double *dAU, const double *dl, const double *du, const double *dc, bool bounds,
+                             double *part, GroupLaunches *g) {
+    const bool c_ = dc != nullptr;
+    const int mb = bounds ? m_loc : 0, nb = bounds ? n_loc : 0, nc = c_ ? n_loc : 0;
     const DataInArgs in{mb, nc, nb, dAL, dAU, dc, dl, du, perm_c_dev.p, perm_r_dev.p, row_norm.p, col_norm.p,
-                        AL.p, AU.p, c.p, l.p, u.p, data_part.p, kReduceBlocks};
-    launch_data_in(in, stream);
+                        AL.p, AU.p, c.p, l.p, u.p, part, kReduceBlocks};
+    if (g) g->data_in(in);
+    else launch_data_in(in, stream);
     FinalizeArgs f{};
     if (bounds) {
-        f.item[f.n++] = {data_part.p, kReduceBlocks, S_DATA_B_ORG};
-        f.item[f.n++] = {data_part.p + 2 * static_cast<size_t>(kReduceBlocks), kReduceBlocks, S_DATA_B_PRE};
+        f.item[f.n++] = {part, kReduceBlocks, S_DATA_B_ORG};
+        f.item[f.n++] = {part + 2 * static_cast<size_t>(kReduceBlocks), kReduceBlocks, S_DATA_B_PRE};
     }
     if (c_) {
-        f.item[f.n++] = {data_part.p + kReduceBlocks, kReduceBlocks, S_DATA_C_ORG};
-        f.item[f.n++] = {data_part.p + 3 * static_cast<size_t>(kReduceBlocks), kReduceBlocks, S_DATA_C_PRE};
+        f.item[f.n++] = {part + kReduceBlocks, kReduceBlocks, S_DATA_C_ORG};
+        f.item[f.n++] = {part + 3 * static_cast<size_t>(kReduceBlocks), kReduceBlocks, S_DATA_C_PRE};
     }
-    launch_finalize(f, scal.p, stream);
-    const DataBcArgs bc{mb, nc, nb, prm.use_bc_scaling ? 1 : 0, scal.p, AL.p, AU.p, c.p, l.p, u.p, rc, lc, data_part.p, kReduceBlocks};
-    launch_data_bc(bc, stream);
-    FinalizeArgs g{};
-    if (bounds) g.item[g.n++] = {data_part.p, kReduceBlocks, S_DATA_NB};
-    if (c_) g.item[g.n++] = {data_part.p + kReduceBlocks, kReduceBlocks, S_DATA_NC};
-    launch_finalize(g, scal.p, stream);
-    fetch_scalars();
+    if (g) g->finalize(f, scal.p);
+    else launch_finalize(f, scal.p, stream);
+}
+
+void Solver::data_second_pass(bool bounds, bool c_, double *part, GroupLaunches *g) {
+    const int mb = bounds ? m_loc : 0, nb = bounds ? n_loc : 0, nc = c_ ? n_loc : 0;
+    const bool codes = !hook_no_bound_codes && bounds;
+    const DataBcArgs bc{mb, nc, nb, prm.use_bc_scaling ? 1 : 0, scal.p, AL.p, AU.p, c.p, l.p, u.p, codes ? row_code.p : nullptr,
+                        codes ? lu_code.p : nullptr, part, kReduceBlocks};
+    if (g) g->data_bc(bc);
+    else launch_data_bc(bc, stream);
+    FinalizeArgs f{};
+    if (bounds) f.item[f.n++] = {part, kReduceBlocks, S_DATA_NB};
+    if (c_) f.item[f.n++] = {part + kReduceBlocks, kReduceBlocks, S_DATA_NC};
+    if (g) g->finalize(f, scal.p);
+    else launch_finalize(f, scal.p, stream);
+}
+
+// after the scalars have reached scal_h
+void Solver::data_consume(bool bounds, bool c_) {
     if (bounds) {
         norm_b_org = 1.0 + std::sqrt(scal_h[S_DATA_B_ORG]);
         b_scale = prm.use_bc_scaling ? 1.0 + std::sqrt(scal_h[S_DATA_B_PRE]) : 1.0;
@@ -2325,11 +2386,6 @@ void Solver::data_apply(const double *dAL, const double *dAU, const double *dl, 
         c_scale = prm.use_bc_scaling ? 1.0 + std::sqrt(scal_h[S_DATA_C_PRE]) : 1.0;
         norm_c = std::sqrt(scal_h[S_DATA_NC]);
     }
-    invalidate_far();
-    if (data_stage.cap_bytes >= kDeviceCacheMinBytes) data_stage.release();  // (back to the allocator cache)
-    data_time[1] = time_since(t1);
-    data_time[2] = time_since(t0);
-    data_since_run += data_time[2];
 }
 
 void Solver::resolve(double sigma_, const double *x0, const double *y0, HPRLP_results *out) {

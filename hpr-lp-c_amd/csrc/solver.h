@@ -102,6 +102,8 @@ struct LoopState {
     HPRLP_results *out = nullptr;
 };
 
+struct GroupBlocks;  // many.cpp
+
 struct Solver {
     HPRLP_parameters prm;
     int m = 0, n = 0;          // global sizes
@@ -149,7 +151,7 @@ struct Solver {
     DBuf<double> AL, AU, l, u, c, row_norm, col_norm;
     DBuf<unsigned char> row_code;  // per row: which of AL, AU the y-half reads (kernels.h); follows AL / AU (refresh_bound_codes)
     DBuf<unsigned char> lu_code;  // per column: which of l, u the x-half reads (kernels.h); follows l / u (refresh_bound_codes)
-    void refresh_bound_codes();
+    void refresh_bound_codes(GroupLaunches *g = nullptr);
     // local work vectors
     DBuf<double> x, last_x, z_bar, last_y, y_obj, y_temp;
     // gathered vectors (length *_pad); the local slice starts at *_off
@@ -208,6 +210,9 @@ struct Solver {
     DBuf<double> data_stage, data_part;     // set_data: the uploaded vectors (kept between calls while small), 4 x kReduceBlocks partials
     DBuf<int> perm_r_dev, perm_c_dev;       // set_data: the locality ordering's permutations on the device (first use)
     std::vector<double> data_pack;          // set_data: small vectors travel in one copy
+    // set_data_many / resolve_many with this solver as member 0 (the owner of the group's stream): the group's staging, partials
+    // and result blocks, grown on demand and kept between calls (many.cpp)
+    std::shared_ptr<GroupBlocks> group_blocks;
 
     // Matrix values (DESIGN.md "Matrix values"): new values on the resident pattern.  val: the nnz values of the model's CSR in the
     // caller's order; the five vectors and obj_constant_ (null: kept) in the caller's units and numbering, host memory.  Afterwards
@@ -265,10 +270,10 @@ struct Solver {
                      double obj_constant_, const HPRLP_parameters *param, Comm *comm_);
     void scale();                                                   // src/scaling.cu:88-216
     double power_iteration(int max_iter, double tol, int *iters);   // src/power_iteration.cu:20-119
-    void init_iteration_state();                                    // src/HPRLP.cu:154-167
+    void init_iteration_state(GroupLaunches *g = nullptr, double sigma_ = -1.0);  // src/HPRLP.cu:154-167 (sigma_ > 0 with g: the override)
     // (g, here and below: record the launch for a group run instead of issuing it -- kernels.h: GroupLaunches, many.cpp)
     void set_sigma_lambda(double sigma_, double lambda_, bool reset_k, GroupLaunches *g = nullptr);
-    void reset_iterates();                                          // all iterates back to zero (as after create + scale + power iteration)
+    void reset_iterates(GroupLaunches *g = nullptr);                // all iterates back to zero (as after create + scale + power iteration)
     void step(bool check, GroupLaunches *g = nullptr);              // one HPR iteration
     void run_normal(int count);                                     // count normal iterations (graph replay)
     void run_normal_then_check(int count);                          // count normal iterations, then one check-variant iteration
@@ -351,6 +356,21 @@ struct Solver {
     // x-half's epilogue has no such mode: no tiled copy, split shards)
     int x_mode_of(int i, int count) const;
 
+    // The pieces of set_data / resolve that a group call records instead of launching (DESIGN.md "Many small LPs", group re-solve;
+    // many.cpp: set_data_many, resolve_many).  Each ends where the host must wait; the single entries call them with g = nullptr
+    // and issue today's launches in today's order.
+    void data_first_pass(const double *dAL, const double *dAU, const double *dl, const double *du, const double *dc, bool bounds, double *part,
+                         GroupLaunches *g);                                      // k_data_in, finalize
+    void data_second_pass(bool bounds, bool c_, double *part, GroupLaunches *g);  // k_data_bc, finalize
+    void data_consume(bool bounds, bool c_);                                      // the host formulas, scalars fetched
+    void start_launch(const double *dx, const double *dy, const int *dpc, const int *dpr, GroupLaunches *g);  // start_apply without its wait
+    void solution_launch(double *xo, double *yo, double *zo, GroupLaunches *g);   // k_unscale
+    bool bound_codes_in_place() const;  // row_code / lu_code need no allocation (or the hook keeps them out)
+    // joins_group(), and nothing of this member's set_data / resolve needs a launch or an allocation of its own: no locality
+    // ordering, code arrays in place (allocating them drops the captured graphs)
+    bool joins_group_resolve();
+    void set_transfer(size_t h2d_words, size_t d2h_words, bool device_entry);
+
    private:
     // What the host and the device entries share: everything after the caller's vectors are readable on the device.
     void data_apply(const double *dAL, const double *dAU, const double *dl, const double *du, const double *dc, bool bounds,
@@ -361,7 +381,6 @@ struct Solver {
     void perms_to_device();                                                   // perm_r_dev / perm_c_dev, first use
     void wait_for_caller(hipStream_t caller);                                 // event on `caller`, `stream` waits for it
     unsigned long long *cleared_check_flags();                                // two words of all ones
-    void set_transfer(size_t h2d_words, size_t d2h_words, bool device_entry);
     void alloc_work();
     hipGraphExec_t graph_for(int len);
 };

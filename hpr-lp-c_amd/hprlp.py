@@ -77,6 +77,14 @@ class CTraceRow(C.Structure):
     ]
 
 
+class CMemberData(C.Structure):  # hprlp_member_data (include/hprlp_amd.h)
+    _fields_ = [(k, c_dbl_p) for k in ("c", "obj_constant", "AL", "AU", "l", "u")]
+
+
+class CMemberStart(C.Structure):  # hprlp_member_start
+    _fields_ = [("x0", c_dbl_p), ("y0", c_dbl_p), ("sigma", C.c_double)]
+
+
 class CDetection(C.Structure):  # hprlp_detection (include/hprlp_amd.h, 16 bytes)
     _fields_ = [("eps_primal_infeasible", C.c_double), ("eps_dual_infeasible", C.c_double)]
 
@@ -235,6 +243,11 @@ def lib():
         L.hprlp_solver_destroy_many.argtypes = [C.POINTER(C.c_void_p), C.c_int]
         L.hprlp_solver_destroy_many.restype = None
         L.hprlp_last_setup_many_counts.argtypes = [C.POINTER(C.c_long)]
+    if hasattr(L, "hprlp_solver_resolve_many"):  # (likewise: the A side of tools/many_resolve_ab.py)
+        L.hprlp_solver_set_data_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(CMemberData)]
+        L.hprlp_solver_resolve_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(CMemberStart), C.POINTER(CResults)]
+        L.hprlp_last_resolve_many_counts.argtypes = [C.POINTER(C.c_long)]
+        L.hprlp_group_pack_selftest.argtypes = []
     _lib = L
     return L
 
@@ -577,6 +590,19 @@ def last_setup_many_counts():
     out = (C.c_long * 8)()
     lib().hprlp_last_setup_many_counts(out)
     return dict(zip(SETUP_MANY_KEYS, [int(v) for v in out]))
+
+
+RESOLVE_MANY_KEYS = ("host-to-device copies", "device-to-host copies", "host waits outside the loop", "launches outside the loop",
+                     "memsets", "members served by group launches", "members that went their own way",
+                     "loop operations issued for one member")
+
+
+def last_resolve_many_counts():
+    """Counts of this thread's last Solver.set_data_many / resolve_many, whichever came last
+    (hprlp_last_resolve_many_counts); the last slot is resolve_many's alone."""
+    out = (C.c_long * 8)()
+    lib().hprlp_last_resolve_many_counts(out)
+    return dict(zip(RESOLVE_MANY_KEYS, [int(v) for v in out]))
 
 
 def solve_batched(model, Cmat, AL, AU, l, u, obj_constants=None, param=None):
@@ -1352,6 +1378,58 @@ class Solver:
         r = Results(res, self.model.m, self.model.n)
         r.trace = [{f: getattr(trace[i], f) for f, _ in CTraceRow._fields_} for i in range(nt.value)]
         return r
+
+    @staticmethod
+    def set_data_many(solvers, data):
+        """set_data(**data[k]) of every solver with one copy, one launch per kernel and one host wait for the members that join
+        (hprlp_solver_set_data_many).  data: one dict per solver with the keys of set_data; None or {} changes nothing."""
+        solvers, hs = Solver._handles(solvers)
+        data = list(data)
+        if len(data) != len(solvers):
+            raise ValueError("set_data_many: one dict (or None) per solver")
+        arr = (CMemberData * max(len(solvers), 1))()
+        keep = []  # (the arrays the pointers name live until the call returns)
+        for k, (sv, d) in enumerate(zip(solvers, data)):
+            d = dict(d or {})
+            unknown = set(d) - {"c", "obj_constant", "AL", "AU", "l", "u"}
+            if unknown:
+                raise ValueError(f"set_data_many: member {k}: unknown keys {sorted(unknown)}")
+            m, n = sv.model.m, sv.model.n
+            for key, length in (("c", n), ("AL", m), ("AU", m), ("l", n), ("u", n)):
+                v = sv._data_vector(d.get(key), length, key)
+                keep.append(v)
+                setattr(arr[k], key, _dptr(v))
+            if d.get("obj_constant") is not None:
+                oc = C.c_double(float(d["obj_constant"]))
+                keep.append(oc)
+                arr[k].obj_constant = C.pointer(oc)
+        if lib().hprlp_solver_set_data_many(hs, len(solvers), arr) < 0:
+            raise RuntimeError(last_error())
+
+    @staticmethod
+    def resolve_many(solvers, x=None, y=None, sigma=None):
+        """resolve(x[k], y[k], sigma[k]) of every solver in lock-step (hprlp_solver_resolve_many).  x, y, sigma: lists (None
+        entries allowed), or None for all.  Returns a list of Results (no trace)."""
+        solvers, hs = Solver._handles(solvers)
+        K = len(solvers)
+        lists = []
+        for name, v in (("x", x), ("y", y), ("sigma", sigma)):
+            v = [None] * K if v is None else list(v)
+            if len(v) != K:
+                raise ValueError(f"resolve_many: {name} needs one entry (or None) per solver")
+            lists.append(v)
+        arr = (CMemberStart * max(K, 1))()
+        keep = []
+        for k, sv in enumerate(solvers):
+            # (lengths are checked here; a non-finite entry is the library's to refuse, naming the member)
+            xs, ys = sv._data_vector(lists[0][k], sv.model.n, "x"), sv._data_vector(lists[1][k], sv.model.m, "y")
+            keep += [xs, ys]
+            arr[k].x0, arr[k].y0 = _dptr(xs), _dptr(ys)
+            arr[k].sigma = -1.0 if lists[2][k] is None else float(lists[2][k])
+        res = (CResults * max(K, 1))()
+        if lib().hprlp_solver_resolve_many(hs, K, arr, res) < 0:
+            raise RuntimeError(last_error())
+        return [Results(res[k], sv.model.m, sv.model.n) for k, sv in enumerate(solvers)]
 
     def data_seconds(self):
         """Seconds of the last set_data(): {upload, kernels, total}."""

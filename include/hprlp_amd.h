@@ -329,7 +329,7 @@ int hprlp_batched_solver_set_matrix_values(hprlp_batched_solver *h, const double
  * hprlp_solver_run_many has one wait, three if some member restarts in it, and a number of launches that does not depend on the
  * count.  The stopping test, restart rule, sigma update and detection stay the member's own host code, so every member gets the
  * bits it gets alone.  Members off the small path are legal (they issue their own launches inside the same lock-step), and a
- * member's iteration-0 evaluation and ray tests are always its own.  The group runs quietly (hprlp_solver_set_verbose is ignored).
+ * member's iteration-0 evaluation (hprlp_solver_resolve_many apart) and ray tests are always its own.  The group runs quietly (hprlp_solver_set_verbose is ignored).
  * All of them return 0, or -1 + hprlp_last_error(); nothing is launched when the arguments are wrong: a NULL pointer, count <= 0,
  * the same handle twice, a sharded solver (hprlp_solver_create_dist* / _local*), a solver that was never scaled, members on
  * different devices, a negative normal[k] or iter[k]. */
@@ -379,6 +379,46 @@ int hprlp_last_solve_many_phases(double out[8]);
  * operations issued for ONE member (an own evaluation, ray test, check step or restart piece), member-evaluations served by group
  * launches, 0, 0} */
 int hprlp_last_run_many_counts(long out[8]);
+
+/* ---- group re-solve: new data, starts and solutions for the whole group (DESIGN.md "Many small LPs", group re-solve) ----------
+ * The callers of a group -- scenario sets, MPC horizons, search-tree nodes -- change c and the bounds of K resident solvers and
+ * solve again, over and over.  The two entries below are hprlp_solver_set_data and hprlp_solver_resolve for every member, with
+ * the work on either side of the loop issued for the group: all given vectors travel in ONE pinned block and one copy, the data
+ * passes, the zeroing, the bound codes, ctrl, the starts, the iteration-0 evaluations and the solutions run in one launch per
+ * kernel for all members that join (small path, stream kernel alone, no locality ordering, bound-code arrays in place; two at
+ * least), and the host waits once per call outside the loop -- none of it grows with the count.  Every member ends bit for bit
+ * where its own call leaves it (the rule of the group launches: a workgroup runs the single kernel's code as workgroup lb of its
+ * member's own grid).  A member that cannot join runs its own set_data / resolve pieces inside the same call; ray tests stay a
+ * member's own.  Refusals (-1 + hprlp_last_error(), naming the entry point and `member k`) come before anything is written or
+ * launched for any member: the group rules above, NULL data / out, an incomplete bounds group, a NaN in a data vector or
+ * obj_constant, a NaN sigma, a non-finite start entry. */
+typedef struct hprlp_member_data {   /* hprlp_solver_set_data's arguments for one member; all NULL: nothing changes */
+    const double *c, *obj_constant, *AL, *AU, *l, *u;
+} hprlp_member_data;
+typedef struct hprlp_member_start {  /* hprlp_solver_resolve's arguments for one member */
+    const double *x0, *y0;           /* NULL: zeros; both NULL: a cold re-solve */
+    double sigma;                    /* > 0 overrides the norm_b / norm_c rule */
+} hprlp_member_start;
+/* hprlp_solver_set_data for every member: scaled vectors, bound codes, scales and norms as its own call leaves them, the group
+ * that was not given untouched, the captured graphs kept.  A member whose entry is all NULL is skipped.  The seconds a member
+ * reports for it (hprlp_solver_data_seconds, and the start of its next out.time) are the group call's wall time. */
+int hprlp_solver_set_data_many(hprlp_solver **s, int count, const hprlp_member_data *data);
+/* hprlp_solver_resolve for every member (start NULL: all cold): out[k] as hprlp_solver_run_many fills it (x, y, z malloc'd), no
+ * trace; certificates from hprlp_solver_get_certificate.  out[k].time = the member's set_data time since its previous loop + the
+ * group loop's wall time up to the member's last event.  For a member served by the group launches that wall time includes the
+ * zeroing, bound-code, ctrl and start kernels: they run in front of the loop's first evaluation, after the loop's clock has
+ * started, where hprlp_solver_resolve runs them before it starts its clock.  Results are not affected. */
+int hprlp_solver_resolve_many(hprlp_solver **s, int count, const hprlp_member_start *start, HPRLP_results *out);
+/* Counts of the calling thread's last hprlp_solver_set_data_many / hprlp_solver_resolve_many (whichever came last; each zeroes
+ * and fills the slots), everything OUTSIDE the loop and with the operations of members that went their own way included:
+ * out = {host-to-device copies (staging blocks and task tables), device-to-host copies, host waits, kernel launches, memsets,
+ * members served by group launches, members that went their own way, resolve_many only: the loop's operations issued for ONE
+ * member (hprlp_last_run_many_counts)}.  A member that gave nothing, or obj_constant only, is neither served nor on its own.
+ * What the group issues is counted where it is issued; the operations of a member on its own are NOMINAL: what its single
+ * entries issue in the common case (no locality ordering, bound-code arrays in place). */
+int hprlp_last_resolve_many_counts(long out[8]);
+/* self-test of the packing layout of the group's staging and result blocks, no GPU needed: 0, or the number of the failed check */
+int hprlp_group_pack_selftest(void);
 
 /* Named device vectors: x y x_hat x_bar y_bar z_bar x_temp y_temp y_obj last_x last_y AL AU l u c
  * row_norm col_norm A_val AT_val.  get returns the length (or -1); cap is the capacity of out. */
