@@ -1,0 +1,197 @@
+// group_table.cpp -- stage order, table block and launch list of a group recording, and its self-test (group_table.h).  Host only.
+#include "group_table.h"
+
+#include <algorithm>
+#include <cstring>
+#include <stdexcept>
+
+namespace hprlp {
+
+GroupTable::GroupTable(bool own_launches, int reduce_blocks, int threads) : own_(own_launches), reduce_blocks_(reduce_blocks), threads_(threads) {}
+
+void GroupTable::note(int kind) { present_.back() |= uint64_t(1) << kind; }
+
+void GroupTable::next_stage() {
+    if (present_.back() == 0) return;
+    order_.push_back(open_stage());
+    present_.push_back(0);
+}
+
+void GroupTable::repeat_last(int nseg, int times) {
+    if (nseg <= 0 || static_cast<size_t>(nseg) > order_.size()) throw std::invalid_argument("group launches: repeat of stages that were not recorded");
+    const std::vector<int> tail(order_.end() - nseg, order_.end());
+    for (int t = 1; t < times; ++t) order_.insert(order_.end(), tail.begin(), tail.end());
+}
+
+static int bits(uint64_t v) {
+    int n = 0;
+    for (; v; v &= v - 1) ++n;
+    return n;
+}
+
+int GroupTable::recorded_launches() const {
+    int n = bits(present_.back());
+    for (int i : order_) n += bits(present_[i]);
+    return n;
+}
+
+void GroupTable::begin() {
+    next_stage();  // (what is open is part of this run)
+    bytes_.clear();
+    made_.clear();
+    first_.assign(present_.size() + 1, 0);
+}
+
+size_t GroupTable::put(const void *p, size_t n) {
+    const size_t at = (bytes_.size() + kTableAlign - 1) / kTableAlign * kTableAlign;
+    bytes_.resize(at + n);
+    if (n > 0) std::memcpy(bytes_.data() + at, p, n);
+    return at;
+}
+
+size_t GroupTable::put_map(const int *grids, int ntasks, int *nwg) {
+    int total = 0;
+    for (int t = 0; t < ntasks; ++t) total += std::max(grids[t], 0);
+    *nwg = total;
+    const size_t at = (bytes_.size() + kTableAlign - 1) / kTableAlign * kTableAlign;
+    bytes_.resize(at + static_cast<size_t>(total) * 2 * sizeof(int));
+    int *pair = reinterpret_cast<int *>(bytes_.data() + at);  // (written in place: the block's storage is aligned for any scalar)
+    for (int t = 0; t < ntasks; ++t)
+        for (int lb = 0; lb < grids[t]; ++lb) {
+            *pair++ = t;
+            *pair++ = lb;
+        }
+    return at;
+}
+
+void GroupTable::add(int stage, int kind, GridRule rule, const void *tasks, size_t task_bytes, int ntasks, const int *grids, bool own) {
+    if (ntasks <= 0) return;
+    GroupLaunch l{kind, stage, ntasks, 0, 0, 0, own_ && own};
+    if (!l.own) {
+        l.tasks = put(tasks, task_bytes * static_cast<size_t>(ntasks));
+        switch (rule) {
+            case kGridMapped: l.map = put_map(grids, ntasks, &l.nwg); break;
+            case kGridReduce: l.nwg = ntasks * reduce_blocks_; break;
+            case kGridPerTask: l.nwg = ntasks; break;
+            case kGridPerThread: l.nwg = (ntasks + threads_ - 1) / threads_; break;
+        }
+        if (l.nwg <= 0) return;  // (members' grids that are all empty: nothing to launch)
+    }
+    // (stages come in ascending order: a stage's launches are one range of made_, ending where the next one's begin)
+    made_.push_back(l);
+    for (size_t i = static_cast<size_t>(stage) + 1; i < first_.size(); ++i) first_[i] = made_.size();
+}
+
+const std::vector<GroupLaunch> &GroupTable::finish() {
+    list_.clear();  // (the vectors of a run keep their capacity: no allocation per run once they have grown)
+    for (int i : order_) list_.insert(list_.end(), made_.begin() + first_[i], made_.begin() + first_[i + 1]);
+    present_.assign(1, 0);
+    order_.clear();
+    return list_;
+}
+
+}  // namespace hprlp
+
+// Checks, numbered: 1 every table and map offset is a multiple of 16; 2 tables and maps do not overlap and lie inside the block;
+// 3 grids {3, 0, 2} give the map (0,0) (0,1) (0,2) (2,0) (2,1) and 5 workgroups; 4 a kind with one task takes no table under the
+// own-launch rule and one without it; 5 repeat_last(2, 20) over stages s, t issues s t s t ... (40 launches) from one table each;
+// 6 the launch list is as long as recorded_launches() says, for two stages that hold the same kind; 7 an empty trailing stage adds
+// nothing; 8 the grid rules' workgroup counts; 9 a repeat of stages that were not recorded is refused.
+extern "C" int hprlp_group_table_selftest(void) {
+    using namespace hprlp;
+    struct Task {
+        double a;
+        int n;
+    };  // (16 bytes; the odd table lengths below come from the 12-byte one)
+    struct Odd {
+        int a, b, c;
+    };
+    const Task t3[3] = {{1.0, 3}, {2.0, 0}, {3.0, 2}};
+    const Odd o5[5] = {{1, 2, 3}, {4, 5, 6}, {7, 8, 9}, {10, 11, 12}, {13, 14, 15}};
+    const int grids[3] = {3, 0, 2};
+    enum { kA = 0, kB = 1, kC = 2, kD = 3 };
+    {   // ---- 1, 2, 3, 6, 7, 8: two stages, kind kA in both
+        GroupTable g(true, 512, 256);
+        g.note(kA), g.note(kB), g.note(kC);
+        g.next_stage();
+        g.note(kA), g.note(kD);
+        g.next_stage();
+        g.next_stage();  // (nothing open: no new stage)
+        if (g.open_stage() != 2) return 7;
+        const int want = g.recorded_launches();
+        if (want != 5) return 6;
+        g.begin();
+        g.add(0, kA, kGridMapped, t3, sizeof(Task), 3, grids, false);
+        g.add(0, kB, kGridReduce, o5, sizeof(Odd), 5, nullptr, false);
+        g.add(0, kC, kGridPerThread, o5, sizeof(Odd), 5, nullptr, false);
+        g.add(1, kA, kGridMapped, t3, sizeof(Task), 3, grids, false);
+        g.add(1, kD, kGridPerTask, o5, sizeof(Odd), 3, nullptr, false);
+        const size_t block = g.bytes().size();
+        const std::vector<char> bytes = g.bytes();
+        const std::vector<GroupLaunch> list = g.finish();
+        if (static_cast<int>(list.size()) != want) return 6;
+        if (g.recorded_launches() != 0 || g.open_stage() != 0) return 7;
+        struct Range {
+            size_t at, len;
+        };
+        std::vector<Range> r;
+        for (const GroupLaunch &l : list) {
+            if (l.own) return 4;
+            if (l.tasks % kTableAlign != 0 || l.map % kTableAlign != 0) return 1;
+            r.push_back({l.tasks, static_cast<size_t>(l.ntasks) * (l.kind == kA ? sizeof(Task) : sizeof(Odd))});
+            if (l.kind == kA) r.push_back({l.map, static_cast<size_t>(l.nwg) * 2 * sizeof(int)});
+        }
+        for (const Range &e : r)
+            if (e.at + e.len > block) return 2;
+        std::sort(r.begin(), r.end(), [](const Range &a, const Range &c) { return a.at < c.at; });
+        for (size_t i = 1; i < r.size(); ++i)
+            if (r[i - 1].at + r[i - 1].len > r[i].at) return 2;
+        const int want_map[10] = {0, 0, 0, 1, 0, 2, 2, 0, 2, 1};
+        for (const GroupLaunch &l : list) {
+            if (l.kind != kA) continue;
+            if (l.nwg != 5 || std::memcmp(bytes.data() + l.map, want_map, sizeof(want_map)) != 0) return 3;
+            if (std::memcmp(bytes.data() + l.tasks, t3, sizeof(t3)) != 0) return 3;
+        }
+        if (list[0].kind != kA || list[0].stage != 0 || list[3].kind != kA || list[3].stage != 1) return 6;
+        if (list[1].nwg != 5 * 512 || list[2].nwg != 1 || list[4].nwg != 3) return 8;
+    }
+    for (int own_rule = 0; own_rule < 2; ++own_rule) {  // ---- 4: one task, with a launch of the member's own
+        GroupTable g(own_rule != 0, 512, 256);
+        g.note(kA);
+        g.begin();
+        g.add(0, kA, kGridMapped, t3, sizeof(Task), 1, grids, true);
+        g.add(0, kB, kGridReduce, o5, sizeof(Odd), 1, nullptr, false);  // (no launch of its own: a table under either rule)
+        const size_t block = g.bytes().size();
+        const std::vector<GroupLaunch> list = g.finish();
+        if (list.size() != 2 || list[0].own != (own_rule != 0) || list[1].own) return 4;
+        if (own_rule ? block != sizeof(Odd) : block != 16 + 3 * 2 * sizeof(int) + 8 + sizeof(Odd)) return 4;
+        if (!own_rule && list[0].nwg != 3) return 4;
+    }
+    {   // ---- 5, 9: the Curtis-Reid sweeps' shape
+        GroupTable g(false, 512, 256);
+        bool refused = false;
+        try {
+            g.repeat_last(1, 2);
+        } catch (const std::invalid_argument &) {
+            refused = true;
+        }
+        if (!refused) return 9;
+        g.note(kA);
+        g.next_stage();
+        g.note(kA);
+        g.next_stage();
+        g.repeat_last(2, 20);
+        g.note(kB);
+        if (g.recorded_launches() != 41) return 5;
+        g.begin();
+        g.add(0, kA, kGridMapped, t3, sizeof(Task), 3, grids, false);
+        g.add(1, kA, kGridMapped, t3, sizeof(Task), 1, grids, false);
+        g.add(2, kB, kGridPerTask, o5, sizeof(Odd), 5, nullptr, false);
+        const std::vector<GroupLaunch> list = g.finish();
+        if (list.size() != 41) return 5;
+        for (int i = 0; i < 40; ++i)
+            if (list[i].stage != i % 2 || list[i].tasks != list[i % 2].tasks || list[i].map != list[i % 2].map) return 5;
+        if (list[0].tasks == list[1].tasks || list[40].stage != 2) return 5;
+    }
+    return 0;
+}

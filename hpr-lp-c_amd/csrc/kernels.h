@@ -391,16 +391,18 @@ struct CsrStream {
 };
 bool group_form_fits(const CsrDev &M);  // every fused launch on M is one k_spmv_fused launch: no tiled copy, no split rows
 // The calls mirror the single launch_* wrappers and only record; run() sends the tables of all records in one copy and issues ONE
-// launch per kind present and stage (next_stage), in the order of a member's own calls (restart copy, ctrl, check x, check y, Rd,
-// Rp, Rp + gap, gap, movement, all finalize items); fetch() packs the scalar blocks recorded by pack() and enqueues one copy to the
-// host; deliver(), after the caller's wait, hands each member its kNumScalars doubles.  Whatever a member enqueues itself between
-// run() and fetch() rides on that copy.  A kind that holds ONE task is issued as that member's own launch (arguments in the
-// launch, no table), and one member's scalars come by its own copy: a group of one issues what the member issues alone.  One
-// run's tables are in flight at a time: the caller waits for the stream between two runs of one object (the staging block is
-// rewritten only after the copy out of it has completed, as for SmallTaskBuf).
+// launch per kind present and stage, the kinds in one fixed order (kernels.hip: GroupKinds -- the order of a member's own calls
+// wherever two kinds of a stage touch the same memory; the table part is host only: group_table.h); fetch() packs the scalar
+// blocks recorded by pack() and enqueues one copy to the host; deliver(), after the caller's wait, hands each member its
+// kNumScalars doubles.  Whatever a member enqueues itself between run() and fetch() rides on that copy.  The loop, the re-solve
+// and the data passes record with own_launches: a kind that holds ONE task is issued as that member's own launch (arguments in the
+// launch, no table), a stage's finalize items that are one member's and at most 8 go through launch_finalize, and one member's
+// scalars come by its own copy -- a group of one issues what the member issues alone.  scale_many records without it: every kind
+// present gets its table.  One run's tables are in flight at a time: the caller waits for the stream between two runs of one
+// object (the staging block is rewritten only after the copy out of it has completed, as for SmallTaskBuf).
 class GroupLaunches {
   public:
-    GroupLaunches();
+    explicit GroupLaunches(bool own_launches = true);
     ~GroupLaunches();
     GroupLaunches(const GroupLaunches &) = delete;
     void x_half_check(const CsrDev &AT, const XHalfArgs &a);
@@ -416,8 +418,7 @@ class GroupLaunches {
     void set_ctrl(Ctrl *ctrl, double sigma, double lambda_max, int reset_k);
     void pack(const double *scalars, double *host);  // a member's device scalars and the host block they go to
     // The kernels on either side of the loop (DESIGN.md "Many small LPs", group re-solve; many.cpp: set_data_many, resolve_many).
-    // Order inside a stage: fill, bound codes, row codes, [restart copy, ctrl], start_in, start_col, start_row, [check x ... gap],
-    // lu, [movement], data_in, data_bc, unscale, [all finalize items].  fill(x, +0.0, n) leaves the bits of a memset.
+    // fill(x, +0.0, n) leaves the bits of a memset.
     void fill(double *x, double a, int n);
     void bound_codes(int n, const double *l, const double *u, unsigned char *code);
     void row_codes(int m, const double *AL, const double *AU, unsigned char *code);
@@ -430,48 +431,28 @@ class GroupLaunches {
     void data_bc(const DataBcArgs &a);
     void unscale(int n, int m, const double *x_bar, const double *y_bar, const double *z_bar, const double *col_norm, const double *row_norm,
                  double b_scale, double c_scale, double *xo, double *yo, double *zo);
-    long tables_sent() const;  // host-to-device copies of the tables so far (one per run() that had a table to send)
-    int recorded_launches() const;  // what run() would issue for the records held now
-    // What is recorded from here on runs after everything recorded so far, finalize included (one run, one copy of the tables
-    // all the same).  Needed where a later kernel overwrites partials an earlier finalize reads: an evaluation's Rd writes part_x,
-    // where the check step before it left the partials of c.x -- alone, the member finalises the check step in between.
-    void next_stage();
-    int run(hipStream_t s);    // returns the number of launches
-    int fetch(hipStream_t s);  // returns the number of copies to the host (0: nothing was recorded by pack())
-    void deliver();
-  private:
-    struct Impl;
-    std::unique_ptr<Impl> impl;
-};
-
-// ---- group scaling (kernels.hip, DESIGN.md "Many small LPs"; many.cpp: scale_many): Solver::scale() of every member of a group in
-// one launch per kernel kind and step.  The calls mirror the single launch_* wrappers and only record.  mark() ends a segment:
-// what is recorded afterwards is launched after everything before it.  Inside a segment one launch per kind present, in this
-// order: row max norms, row sum norms, Curtis-Reid update, the elementwise kernels (fill, vector scaling, scalar scaling, exp /
-// clamp: one launch), the matrix scalings (one launch per <ROW_FIRST, DIVIDE, NEXT> instance present), the two reductions, their
-// finalize items, bound codes, row codes.  repeat_last(n, times): the last n segments are issued `times` times in a row (the
-// twenty Curtis-Reid sweeps share two tables).  run() sends the tables of all segments in one copy and issues the launches; one
-// run's tables are in flight at a time (the caller waits for the stream between two runs, as for GroupLaunches).
-class ScaleLaunches {
-  public:
-    ScaleLaunches();
-    ~ScaleLaunches();
-    ScaleLaunches(const ScaleLaunches &) = delete;
-    void fill(double *x, double a, int n);
+    // The scaling kernels (DESIGN.md "Many small LPs", group scaling; the pieces of Solver::scale()).  fill, the two vector scalings
+    // and exp / clamp share one launch; a matrix scaling is one launch per <ROW_FIRST, DIVIDE, NEXT> instance present.
     void vec_scale(double *x, const double *s, int n, bool divide);
     void vec_scal(double *x, double a, int n);
     void exp_clamp(double *v, int n);
     void bnorm2(const double *AL, const double *AU, int m, double *partials);  // kReduceBlocks partials
     void norm2(const double *x, int n, double *partials);
-    void finalize(const double *partials, int count, double *scalars, int slot);
     void row_norm(const CsrDev &M, double *result, int norm);  // 99 or 1
     void scale_matrix(const CsrDev &M, const double *rowvec, const double *colvec_full, bool row_first, bool divide, double *next_max_norm);
     void cr_log_update(const CsrDev &M, const double *other_full, double *result);
-    void bound_codes(int n, const double *l, const double *u, unsigned char *code);
-    void row_codes(int m, const double *AL, const double *AU, unsigned char *code);
-    void mark();
-    void repeat_last(int nseg, int times);
-    int run(hipStream_t s);  // returns the number of launches
+    long tables_sent() const;  // host-to-device copies of the tables so far (one per run() that had a table to send)
+    int recorded_launches() const;  // what run() would issue for the records held now
+    // What is recorded from here on runs after everything recorded so far, finalize included (one run, one copy of the tables
+    // all the same; nothing happens while the open stage holds no record).  Needed where a later kernel overwrites partials an
+    // earlier finalize reads: an evaluation's Rd writes part_x, where the check step before it left the partials of c.x -- alone,
+    // the member finalises the check step in between.
+    void next_stage();
+    // The last n closed stages are issued `times` times in a row (the twenty Curtis-Reid sweeps share two tables).
+    void repeat_last(int nstages, int times);
+    int run(hipStream_t s);    // returns the number of launches
+    int fetch(hipStream_t s);  // returns the number of copies to the host (0: nothing was recorded by pack())
+    void deliver();
   private:
     struct Impl;
     std::unique_ptr<Impl> impl;

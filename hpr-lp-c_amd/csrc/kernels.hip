@@ -13,9 +13,12 @@
 // Reference formulas: src/cuda_kernels/HPR_cuda_kernels.cu:203-295 (updates), :160-189 (residuals),
 // :91-157 (scaling), src/scaling.cu:5-38, src/power_iteration.cu:60-100.
 #include "kernels.h"
+#include "group_table.h"
 
 #include <algorithm>
+#include <array>
 #include <cstring>
+#include <tuple>
 #include <stdexcept>
 #include <vector>
 #include <cmath>
@@ -1840,7 +1843,7 @@ void launch_start_row(const CsrDev &A, const double *xbar_full, const double *AL
 // scalar finalisation: out[slot] = sum of a partial array, one block per item, fixed order
 // ------------------------------------------------------------------------------------------------
 static_assert(kWavesPerBlock == 4, "k_finalize's sum adds the four waves' partials in a fixed order");
-// (the body of k_finalize and of k_finalize_many: one workgroup, one item)
+// (the body of k_finalize and of its group form: one workgroup, one item)
 __device__ __forceinline__ void finalize_body(const FinalizeItem &it, double *scalars) {
     __shared__ double red[kWavesPerBlock];
     if (it.max) {  // (uniform per block) partials of nonnegative maxima
@@ -1878,7 +1881,7 @@ void launch_finalize(const FinalizeArgs &f, double *scalars, hipStream_t s) {
 // ------------------------------------------------------------------------------------------------
 // plain vector kernels (grid-stride, fixed grids so partial counts are static)
 // ------------------------------------------------------------------------------------------------
-// (the body of k_movement and of k_movement_many: workgroup `bid` of `grid`)
+// (the body of k_movement and of its group form: workgroup `bid` of `grid`)
 __device__ __forceinline__ void movement_body(int n, int m, const double *x_bar, const double *last_x, double *x_temp, const double *y_bar,
                                               const double *last_y, double *y_temp, double *partials, int stride, int bid, int grid) {
     double acc[2] = {0.0, 0.0};
@@ -1908,7 +1911,7 @@ void launch_movement(int n, int m, const double *x_bar, const double *last_x, do
                        y_temp, partials, stride);
 }
 
-// (the body of k_restart_copy and of k_restart_copy_many: workgroup `bid` of `grid`)
+// (the body of k_restart_copy and of its group form: workgroup `bid` of `grid`)
 __device__ __forceinline__ void restart_copy_body(int n, int m, const double *x_bar, double *x, double *last_x, const double *y_bar, double *y,
                                                   double *last_y, Ctrl *ctrl, int bid, int grid) {
     const int tid = bid * kThreads + threadIdx.x, nth = grid * kThreads;
@@ -1946,7 +1949,7 @@ void launch_restart_copy(int n, int m, const double *x_bar, double *x, double *l
                        y_bar, y, last_y, ctrl);
 }
 
-// (the body of k_lu and of k_lu_many: workgroup `bid` of `grid`)
+// (the body of k_lu and of its group form: workgroup `bid` of `grid`)
 __device__ __forceinline__ void lu_body(int n, const double *x_bar, const double *l, const double *u, const double *col_norm, double *x_temp,
                                         double *partials, int bid, int grid) {
     double acc[1] = {0.0};
@@ -1971,7 +1974,7 @@ void launch_lu(int n, const double *x_bar, const double *l, const double *u, con
     hipLaunchKernelGGL(k_lu, dim3(nblocks), dim3(kThreads), 0, s, n, x_bar, l, u, col_norm, x_temp, partials);
 }
 
-// (the body of k_set_ctrl and of k_set_ctrl_many: one thread)
+// (the body of k_set_ctrl and of its group form: one thread)
 __device__ __forceinline__ void set_ctrl_body(Ctrl *ctrl, double sigma, double lambda_max, int reset_k) {
     const double f = lambda_max * sigma;
     ctrl->sigma = sigma;
@@ -2708,7 +2711,7 @@ void launch_ray_form(const RayFormArgs &a, double *partials, int nblocks, hipStr
 
 // Warm start: the caller's point (caller's units and numbering) -> the scaled, permuted, projected iteration state.  The inverse
 // of k_unscale's map; positive scaling keeps every bound on its side, so the projection runs on the device's scaled bounds.
-// (the body of k_start_in and of k_start_in_many: workgroup `bid` of `grid`)
+// (the body of k_start_in and of its group form: workgroup `bid` of `grid`)
 __device__ __forceinline__ void start_in_body(const StartInArgs &a, int bid, int grid) {
     const int tid = bid * kThreads + threadIdx.x, nth = grid * kThreads;
     for (int j = tid; j < a.n; j += nth) {
@@ -2739,7 +2742,7 @@ void launch_start_in(const StartInArgs &a, hipStream_t s) {
 // are before the b / c scaling, and leave the partials of |b|^2, |c|^2 of the caller's data and of the scaled data.  Same grid,
 // same element-to-thread map and same block reduction as k_bnorm2 / k_norm2, so the sums over identical inputs are the bits
 // Solver::scale() gets.  nc / nb / m: 0 for a group the caller did not give.
-// (the body of k_data_in and of k_data_in_many: workgroup `bid` of `grid`)
+// (the body of k_data_in and of its group form: workgroup `bid` of `grid`)
 __device__ __forceinline__ void data_in_body(const DataInArgs &a, int bid, int grid) {
     double acc[4] = {0.0, 0.0, 0.0, 0.0};  // b original, c original, b scaled, c scaled
     const int tid = bid * kThreads + threadIdx.x, nth = grid * kThreads;
@@ -2791,7 +2794,7 @@ __device__ __forceinline__ double bside_sq(double lo, double hi) {
     const double v = fmax(fabs(isinf(lo) ? 0.0 : lo), fabs(isinf(hi) ? 0.0 : hi));
     return v * v;
 }
-// (the body of k_data_bc and of k_data_bc_many: workgroup `bid` of `grid`)
+// (the body of k_data_bc and of its group form: workgroup `bid` of `grid`)
 __device__ __forceinline__ void data_bc_body(const DataBcArgs &a, int bid, int grid) {
     const double bs = a.use_bc ? 1.0 / (1.0 + sqrt(a.scalars[S_DATA_B_PRE])) : 1.0;
     const double cs = a.use_bc ? 1.0 / (1.0 + sqrt(a.scalars[S_DATA_C_PRE])) : 1.0;
@@ -2851,7 +2854,7 @@ void launch_data_bc(const DataBcArgs &a, hipStream_t s) {
     hipLaunchKernelGGL(k_data_bc, dim3(kReduceBlocks), dim3(kThreads), 0, s, a);
 }
 
-// (the body of k_unscale and of k_unscale_many: workgroup `bid` of `grid`)
+// (the body of k_unscale and of its group form: workgroup `bid` of `grid`)
 __device__ __forceinline__ void unscale_body(int n, int m, const double *x_bar, const double *y_bar, const double *z_bar, const double *col_norm,
                                              const double *row_norm, double b_scale, double c_scale, double *xo, double *yo, double *zo, int bid,
                                              int grid) {
@@ -2952,43 +2955,62 @@ void launch_scatter(double *dst, const int *idx, const double *src, int n, hipSt
 
 // ------------------------------------------------------------------------------------------------
 // group forms of the regular kernels (DESIGN.md "Many small LPs"): one launch serves every member of a group of small LPs.
-// A workgroup looks up {task, its place lb in the member's own launch} and runs the single kernel's body for workgroup lb of
-// lg = the member's own grid -- the same instructions on the same operands in the same order, so every partial and every
-// finalised scalar is the bits the member computes alone.  No workgroup reads what a workgroup of another member writes.
+// A workgroup finds its task by the kind's grid rule (group_table.h: a {task, lb} map on the members' own grids -- vec_grid,
+// ceil(len / kThreads) or csr_grid() --, kReduceBlocks workgroups per task, one workgroup or one thread per task) and runs the
+// single kernel's body for workgroup lb of the member's own grid -- the same instructions on the same operands in the same
+// order, so every value, partial and finalised scalar is the bits the member computes alone.  No workgroup reads what a
+// workgroup of another member writes.
+//
+// A KIND is a task type: its fields, `rule`, run() -- the single kernel's body on the fields --, own_grid() for a mapped kind
+// and, where the member has a launch of its own for one task, own().  GroupKinds further down lists the kinds once, in issue
+// order; storage, counting, tables and launches walk that list.
 // ------------------------------------------------------------------------------------------------
+// (the task read is uniform in the workgroup: scalar loads into a private copy, before anything is stored)
+template <class Task>
+__global__ void __launch_bounds__(kThreads) k_mapped_many(const Task *__restrict__ tasks, const int2 *__restrict__ wgmap) {
+    const int2 w = wgmap[blockIdx.x];
+    const Task t = tasks[w.x];
+    t.run(w.y);
+}
+// kReduceBlocks workgroups per member, as the member's own launch: all 512 partials of every sum are stored and the finalize
+// items add the same operands in the same order
+template <class Task>
+__global__ void __launch_bounds__(kThreads) k_reduce_many(const Task *__restrict__ tasks) {
+    const Task t = tasks[blockIdx.x / kReduceBlocks];
+    t.run(blockIdx.x % kReduceBlocks);
+}
+template <class Task>
+__global__ void __launch_bounds__(kThreads) k_each_many(const Task *__restrict__ tasks, int ntasks) {
+    if constexpr (Task::rule == kGridPerThread) {
+        const int i = blockIdx.x * kThreads + threadIdx.x;
+        if (i >= ntasks) return;
+        const Task t = tasks[i];
+        t.run();
+    } else {
+        const Task t = tasks[blockIdx.x];
+        t.run();
+    }
+}
+
+bool group_form_fits(const CsrDev &M) { return !M.tiled.valid && M.nlong == 0 && M.nblk > 0; }
+static CsrStream stream_part(const CsrDev &M) {
+    if (!group_form_fits(M)) throw std::runtime_error("a matrix of a group launch does not run the stream kernel alone");
+    return CsrStream{M.nblk, M.nt, M.rowptr, M.col, M.val, M.blk, nullptr};
+}
+static int elem_grid(int n) { return (n + kThreads - 1) / kThreads; }
+
 template <class Epi>
-struct GroupTask {
+struct GroupTask {  // k_spmv_fused<Epi> (its group kernel is its own: k_spmv_fused_many)
+    static constexpr GridRule rule = kGridMapped;
     CsrStream A;
     Epi epi;
+    int own_grid() const { return A.csr_grid(); }
+    void own(hipStream_t s) const {
+        CsrDev M;  // (what k_spmv_fused reads of it)
+        M.nblk = A.nblk, M.nt = A.nt, M.rowptr = A.rowptr, M.col = A.col, M.val = const_cast<double *>(A.val), M.blk = A.blk;
+        hipLaunchKernelGGL(k_spmv_fused<Epi>, dim3(A.csr_grid()), dim3(kThreads), 0, s, M, epi);
+    }
 };
-struct FinalizeOne {
-    FinalizeItem it;
-    double *scalars;
-};
-struct MovementTask {
-    int n, m;
-    const double *x_bar, *last_x;
-    double *x_temp;
-    const double *y_bar, *last_y;
-    double *y_temp, *partials;
-    int stride;
-};
-struct RestartCopyTask {
-    int n, m;
-    const double *x_bar;
-    double *x, *last_x;
-    const double *y_bar;
-    double *y, *last_y;
-    Ctrl *ctrl;
-    int grid;  // of the member's own launch (vec_grid)
-};
-struct SetCtrlTask {
-    Ctrl *ctrl;
-    double sigma, lambda_max;
-    int reset_k;
-};
-
-// (the task read is uniform in the workgroup: scalar loads into a private copy, before anything is stored)
 template <class Epi>
 __global__ void __launch_bounds__(kThreads) k_spmv_fused_many(const GroupTask<Epi> *__restrict__ tasks, const int2 *__restrict__ wgmap) {
     const int2 w = wgmap[blockIdx.x];
@@ -2997,29 +3019,169 @@ __global__ void __launch_bounds__(kThreads) k_spmv_fused_many(const GroupTask<Ep
     spmv_fused_body<Epi>(A, epi, w.y, A.csr_grid());
 }
 
-__global__ void __launch_bounds__(kThreads) k_finalize_many(const FinalizeOne *__restrict__ items) {
-    const FinalizeOne o = items[blockIdx.x];
-    finalize_body(o.it, o.scalars);
-}
-
-// kReduceBlocks workgroups per member, as the member's own launch
-__global__ void __launch_bounds__(kThreads) k_movement_many(const MovementTask *__restrict__ tasks) {
-    const MovementTask t = tasks[blockIdx.x / kReduceBlocks];
-    movement_body(t.n, t.m, t.x_bar, t.last_x, t.x_temp, t.y_bar, t.last_y, t.y_temp, t.partials, t.stride, blockIdx.x % kReduceBlocks,
-                  kReduceBlocks);
-}
-
-__global__ void __launch_bounds__(kThreads) k_restart_copy_many(const RestartCopyTask *__restrict__ tasks, const int2 *__restrict__ wgmap) {
+struct FinalizeOne {  // one item of k_finalize; a stage's items that are one member's and at most 8 are its own launch_finalize
+    static constexpr GridRule rule = kGridPerTask;
+    FinalizeItem it;
+    double *scalars;
+    __device__ void run() const { finalize_body(it, scalars); }
+};
+struct MovementTask {
+    static constexpr GridRule rule = kGridReduce;
+    int n, m;
+    const double *x_bar, *last_x;
+    double *x_temp;
+    const double *y_bar, *last_y;
+    double *y_temp, *partials;
+    int stride;
+    __device__ void run(int lb) const { movement_body(n, m, x_bar, last_x, x_temp, y_bar, last_y, y_temp, partials, stride, lb, kReduceBlocks); }
+    void own(hipStream_t s) const { launch_movement(n, m, x_bar, last_x, x_temp, y_bar, last_y, y_temp, partials, stride, kReduceBlocks, s); }
+};
+struct RestartCopyTask {
+    static constexpr GridRule rule = kGridMapped;
+    int n, m;
+    const double *x_bar;
+    double *x, *last_x;
+    const double *y_bar;
+    double *y, *last_y;
+    Ctrl *ctrl;
+    int grid;  // of the member's own launch (vec_grid)
+    __device__ void run(int lb) const { restart_copy_body(n, m, x_bar, x, last_x, y_bar, y, last_y, ctrl, lb, grid); }
+    int own_grid() const { return grid; }
+    void own(hipStream_t s) const { launch_restart_copy(n, m, x_bar, x, last_x, y_bar, y, last_y, ctrl, s); }
+};
+struct SetCtrlTask {
+    static constexpr GridRule rule = kGridPerThread;
+    Ctrl *ctrl;
+    double sigma, lambda_max;
+    int reset_k;
+    __device__ void run() const { set_ctrl_body(ctrl, sigma, lambda_max, reset_k); }
+    void own(hipStream_t s) const { launch_set_ctrl(ctrl, sigma, lambda_max, reset_k, s); }
+};
+enum VecOp : int { kVecFill = 0, kVecMul = 1, kVecDiv = 2, kVecScal = 3, kVecExpClamp = 4 };
+struct VecTask {  // k_fill, k_vec_scale (multiply / divide), k_vec_scal, k_exp_clamp: one launch for all of them
+    static constexpr GridRule rule = kGridMapped;
+    double *x;
+    const double *s;
+    double a;
+    int n, op;
+    __device__ void run(int lb) const {
+        switch (op) {  // (uniform in the workgroup)
+            case kVecFill: fill_body(x, a, n, lb); break;
+            case kVecMul: vec_scale_body(x, s, n, 0, lb); break;
+            case kVecDiv: vec_scale_body(x, s, n, 1, lb); break;
+            case kVecScal: vec_scal_body(x, a, n, lb); break;
+            default: exp_clamp_body(x, n, lb); break;
+        }
+    }
+    int own_grid() const { return elem_grid(n); }
+    void own(hipStream_t st) const {
+        switch (op) {
+            case kVecFill: launch_fill(x, a, n, st); break;
+            case kVecMul: launch_vec_scale(x, s, n, false, st); break;
+            case kVecDiv: launch_vec_scale(x, s, n, true, st); break;
+            case kVecScal: launch_vec_scal(x, a, n, st); break;
+            default: launch_exp_clamp(x, n, st); break;
+        }
+    }
+};
+template <bool ROWS>
+struct CodesTask {  // k_bound_codes (a = l, b = u) / ROWS: k_row_codes (a = AL, b = AU)
+    static constexpr GridRule rule = kGridMapped;
+    int n;
+    const double *a, *b;
+    unsigned char *code;
+    __device__ void run(int lb) const {
+        if constexpr (ROWS) row_codes_body(n, a, b, code, lb);
+        else bound_codes_body(n, a, b, code, lb);
+    }
+    int own_grid() const { return elem_grid(n); }
+    void own(hipStream_t s) const {
+        if constexpr (ROWS) launch_row_codes(n, a, b, code, s);
+        else launch_bound_codes(n, a, b, code, s);
+    }
+};
+// The kernels on either side of the loop (DESIGN.md "Many small LPs", group re-solve): the two data passes and k_lu keep the
+// member's own shape of kReduceBlocks workgroups, the start and the solution run on the member's vec_grid.
+struct StartInTask {
+    static constexpr GridRule rule = kGridMapped;
+    StartInArgs a;
+    int grid;  // of the member's own launch (vec_grid)
+    __device__ void run(int lb) const { start_in_body(a, lb, grid); }
+    int own_grid() const { return grid; }
+    void own(hipStream_t s) const { launch_start_in(a, s); }
+};
+struct LuTask {
+    static constexpr GridRule rule = kGridReduce;
+    int n;
+    const double *x_bar, *l, *u, *col_norm;
+    double *x_temp, *partials;
+    __device__ void run(int lb) const { lu_body(n, x_bar, l, u, col_norm, x_temp, partials, lb, kReduceBlocks); }
+    void own(hipStream_t s) const { launch_lu(n, x_bar, l, u, col_norm, x_temp, partials, kReduceBlocks, s); }
+};
+struct DataInTask {
+    static constexpr GridRule rule = kGridReduce;
+    DataInArgs a;
+    __device__ void run(int lb) const { data_in_body(a, lb, kReduceBlocks); }
+    void own(hipStream_t s) const { launch_data_in(a, s); }
+};
+struct DataBcTask {
+    static constexpr GridRule rule = kGridReduce;
+    DataBcArgs a;
+    __device__ void run(int lb) const { data_bc_body(a, lb, kReduceBlocks); }
+    void own(hipStream_t s) const { launch_data_bc(a, s); }
+};
+struct UnscaleTask {
+    static constexpr GridRule rule = kGridMapped;
+    int n, m;
+    const double *x_bar, *y_bar, *z_bar, *col_norm, *row_norm;
+    double b_scale, c_scale;
+    double *xo, *yo, *zo;
+    int grid;  // of the member's own launch (vec_grid)
+    __device__ void run(int lb) const { unscale_body(n, m, x_bar, y_bar, z_bar, col_norm, row_norm, b_scale, c_scale, xo, yo, zo, lb, grid); }
+    int own_grid() const { return grid; }
+    void own(hipStream_t s) const { launch_unscale(n, m, x_bar, y_bar, z_bar, col_norm, row_norm, b_scale, c_scale, xo, yo, zo, s); }
+};
+// The scaling kernels (DESIGN.md "Many small LPs", group scaling).  scale_many records them with a table for every kind, so they
+// name no launch of the member's own.
+template <bool BOUNDS>
+struct ReduceTask {  // BOUNDS: k_bnorm2 (a = AL, b = AU) / k_norm2 (a = x)
+    static constexpr GridRule rule = kGridReduce;
+    const double *a, *b;
+    int n;
+    double *partials;
+    __device__ void run(int lb) const {
+        if constexpr (BOUNDS) bnorm2_body(a, b, n, partials, lb, kReduceBlocks);
+        else norm2_body(a, n, partials, lb, kReduceBlocks);
+    }
+};
+template <bool SUM>
+struct RowNormTask {  // k_row_max_blocks / SUM: k_row_sum_blocks
+    static constexpr GridRule rule = kGridMapped;
+    CsrStream A;
+    double *result;
+    __device__ void run(int lb) const {
+        if constexpr (SUM) row_sum_blocks_body(A, result, lb);
+        else row_max_blocks_body(A, result, lb);
+    }
+    int own_grid() const { return A.csr_grid(); }
+};
+template <bool ROW_FIRST, bool DIVIDE, bool NEXT>
+struct ScaleMatTask {  // k_scale_matrix<ROW_FIRST, DIVIDE, NEXT> (its group kernel is its own: it holds the __shared__ array)
+    static constexpr GridRule rule = kGridMapped;
+    CsrStream A;
+    const double *rowvec, *colvec;
+    double *next_norm;
+    int own_grid() const { return A.csr_grid(); }
+};
+template <int I>
+using ScaleMat = ScaleMatTask<(I & 4) != 0, (I & 2) != 0, (I & 1) != 0>;
+template <bool ROW_FIRST, bool DIVIDE, bool NEXT>
+__global__ void __launch_bounds__(kThreads) k_scale_matrix_many(const ScaleMatTask<ROW_FIRST, DIVIDE, NEXT> *__restrict__ tasks,
+                                                               const int2 *__restrict__ wgmap) {
     const int2 w = wgmap[blockIdx.x];
-    const RestartCopyTask t = tasks[w.x];
-    restart_copy_body(t.n, t.m, t.x_bar, t.x, t.last_x, t.y_bar, t.y, t.last_y, t.ctrl, w.y, t.grid);
-}
-
-__global__ void __launch_bounds__(kThreads) k_set_ctrl_many(const SetCtrlTask *__restrict__ tasks, int ntasks) {
-    const int i = blockIdx.x * kThreads + threadIdx.x;
-    if (i >= ntasks) return;
-    const SetCtrlTask t = tasks[i];
-    set_ctrl_body(t.ctrl, t.sigma, t.lambda_max, t.reset_k);
+    const ScaleMatTask<ROW_FIRST, DIVIDE, NEXT> t = tasks[w.x];
+    __shared__ double rsv[kWavesPerBlock][kStreamW];
+    scale_matrix_body<ROW_FIRST, DIVIDE, NEXT>(t.A.nblk, t.A.blk, t.A.rowptr, t.A.col, const_cast<double *>(t.A.val), t.rowvec, t.colvec, t.next_norm, w.y, rsv);
 }
 
 // the members' kNumScalars-slot blocks side by side (one copy to the host serves the group)
@@ -3027,135 +3189,89 @@ __global__ void __launch_bounds__(kWave) k_pack_scalars(const double *const *__r
     if (threadIdx.x < kNumScalars) dst[blockIdx.x * kNumScalars + threadIdx.x] = src[blockIdx.x][threadIdx.x];
 }
 
-// ---- the elementwise kernels and the bound codes (the group scaling further down records them too)
-enum VecOp : int { kVecFill = 0, kVecMul = 1, kVecDiv = 2, kVecScal = 3, kVecExpClamp = 4 };
-struct VecTask {  // k_fill, k_vec_scale (multiply / divide), k_vec_scal, k_exp_clamp
-    double *x;
-    const double *s;
-    double a;
-    int n, op;
-};
-struct CodesTask {  // k_bound_codes (a = l, b = u) / k_row_codes (a = AL, b = AU)
-    int n;
-    const double *a, *b;
-    unsigned char *code;
-};
-static int elem_grid(int n) { return (n + kThreads - 1) / kThreads; }
-
-__global__ void __launch_bounds__(kThreads) k_vec_many(const VecTask *__restrict__ tasks, const int2 *__restrict__ wgmap) {
-    const int2 w = wgmap[blockIdx.x];
-    const VecTask t = tasks[w.x];
-    switch (t.op) {  // (uniform in the workgroup)
-        case kVecFill: fill_body(t.x, t.a, t.n, w.y); break;
-        case kVecMul: vec_scale_body(t.x, t.s, t.n, 0, w.y); break;
-        case kVecDiv: vec_scale_body(t.x, t.s, t.n, 1, w.y); break;
-        case kVecScal: vec_scal_body(t.x, t.a, t.n, w.y); break;
-        default: exp_clamp_body(t.x, t.n, w.y); break;
-    }
-}
-__global__ void __launch_bounds__(kThreads) k_bound_codes_many(const CodesTask *__restrict__ tasks, const int2 *__restrict__ wgmap) {
-    const int2 w = wgmap[blockIdx.x];
-    const CodesTask t = tasks[w.x];
-    bound_codes_body(t.n, t.a, t.b, t.code, w.y);
-}
-__global__ void __launch_bounds__(kThreads) k_row_codes_many(const CodesTask *__restrict__ tasks, const int2 *__restrict__ wgmap) {
-    const int2 w = wgmap[blockIdx.x];
-    const CodesTask t = tasks[w.x];
-    row_codes_body(t.n, t.a, t.b, t.code, w.y);
-}
-
-// ---- group re-solve (DESIGN.md "Many small LPs", group re-solve): the kernels on either side of the loop.  The two data passes
-// and k_lu keep the member's own shape, kReduceBlocks workgroups (task = blockIdx.x / kReduceBlocks, no table), so all 512
-// partials of every sum are stored and k_finalize_many adds the same operands in the same order; the start and the solution run
-// on the member's vec_grid through the {task, lb} map.
-struct StartInTask {
-    StartInArgs a;
-    int grid;  // of the member's own launch (vec_grid)
-};
-struct LuTask {
-    int n;
-    const double *x_bar, *l, *u, *col_norm;
-    double *x_temp, *partials;
-};
-struct UnscaleTask {
-    int n, m;
-    const double *x_bar, *y_bar, *z_bar, *col_norm, *row_norm;
-    double b_scale, c_scale;
-    double *xo, *yo, *zo;
-    int grid;  // of the member's own launch (vec_grid)
-};
-__global__ void __launch_bounds__(kThreads) k_data_in_many(const DataInArgs *__restrict__ tasks) {
-    const DataInArgs t = tasks[blockIdx.x / kReduceBlocks];
-    data_in_body(t, blockIdx.x % kReduceBlocks, kReduceBlocks);
-}
-__global__ void __launch_bounds__(kThreads) k_data_bc_many(const DataBcArgs *__restrict__ tasks) {
-    const DataBcArgs t = tasks[blockIdx.x / kReduceBlocks];
-    data_bc_body(t, blockIdx.x % kReduceBlocks, kReduceBlocks);
-}
-__global__ void __launch_bounds__(kThreads) k_start_in_many(const StartInTask *__restrict__ tasks, const int2 *__restrict__ wgmap) {
-    const int2 w = wgmap[blockIdx.x];
-    const StartInTask t = tasks[w.x];
-    start_in_body(t.a, w.y, t.grid);
-}
-__global__ void __launch_bounds__(kThreads) k_lu_many(const LuTask *__restrict__ tasks) {
-    const LuTask t = tasks[blockIdx.x / kReduceBlocks];
-    lu_body(t.n, t.x_bar, t.l, t.u, t.col_norm, t.x_temp, t.partials, blockIdx.x % kReduceBlocks, kReduceBlocks);
-}
-__global__ void __launch_bounds__(kThreads) k_unscale_many(const UnscaleTask *__restrict__ tasks, const int2 *__restrict__ wgmap) {
-    const int2 w = wgmap[blockIdx.x];
-    const UnscaleTask t = tasks[w.x];
-    unscale_body(t.n, t.m, t.x_bar, t.y_bar, t.z_bar, t.col_norm, t.row_norm, t.b_scale, t.c_scale, t.xo, t.yo, t.zo, w.y, t.grid);
-}
-
-bool group_form_fits(const CsrDev &M) { return !M.tiled.valid && M.nlong == 0 && M.nblk > 0; }
-
 namespace {
-// the finalize items of a stage are one member's and fit one k_finalize launch
-bool one_members_items(const std::vector<FinalizeOne> &fin) {
+// ---- the group kernel of a kind: its grid rule's template, or the kind's own
+template <class Task>
+struct GroupKernel {
+    static constexpr auto pick() {
+        if constexpr (Task::rule == kGridMapped) return &k_mapped_many<Task>;
+        else if constexpr (Task::rule == kGridReduce) return &k_reduce_many<Task>;
+        else return &k_each_many<Task>;
+    }
+};
+template <class Epi>
+struct GroupKernel<GroupTask<Epi>> {
+    static constexpr auto pick() { return &k_spmv_fused_many<Epi>; }
+};
+template <bool R, bool D, bool N>
+struct GroupKernel<ScaleMatTask<R, D, N>> {
+    static constexpr auto pick() { return &k_scale_matrix_many<R, D, N>; }
+};
+
+// ---- the member's own launch for the tasks of a kind in one stage, where there is one
+template <class Task, class = void>
+struct HasOwn : std::false_type {};
+template <class Task>
+struct HasOwn<Task, std::void_t<decltype(&Task::own)>> : std::true_type {};
+template <class Task>
+bool issues_own(const std::vector<Task> &tasks) {
+    return HasOwn<Task>::value && tasks.size() == 1;
+}
+template <class Task>
+void issue_own(const std::vector<Task> &tasks, hipStream_t s) {
+    if constexpr (HasOwn<Task>::value) tasks[0].own(s);
+}
+// (the finalize items of a stage are one member's and fit one k_finalize launch)
+bool issues_own(const std::vector<FinalizeOne> &fin) {
     if (fin.empty() || fin.size() > 8) return false;
     for (const FinalizeOne &o : fin)
         if (o.scalars != fin[0].scalars) return false;
     return true;
 }
-CsrStream stream_part(const CsrDev &M) {
-    if (!group_form_fits(M)) throw std::runtime_error("a matrix of a group launch does not run the stream kernel alone");
-    return CsrStream{M.nblk, M.nt, M.rowptr, M.col, M.val, M.blk, nullptr};
+void issue_own(const std::vector<FinalizeOne> &fin, hipStream_t s) {
+    FinalizeArgs f{};
+    for (const FinalizeOne &o : fin) f.item[f.n++] = o.it;
+    launch_finalize(f, fin[0].scalars, s);
 }
-}  // namespace
 
-// The records of one stage: kinds that may share a run in the fixed order below without one reading or overwriting what another
-// still needs (a check step's partials in part_x are overwritten by the next evaluation's Rd: the two are different stages).
-struct GroupStage {
-    std::vector<GroupTask<XEpi<true>>> xs;
-    std::vector<GroupTask<YEpi<true>>> ys;
-    std::vector<GroupTask<RdEpi>> rd;
-    std::vector<GroupTask<RpEpi<false>>> rp;
-    std::vector<GroupTask<RpEpi<true>>> rpg;
-    std::vector<GroupTask<GapEpi>> gap;
-    std::vector<FinalizeOne> fin;
-    std::vector<MovementTask> mov;
-    std::vector<RestartCopyTask> rc;
-    std::vector<SetCtrlTask> sc;
-    // the group re-solve's kinds (set_data_many / resolve_many only)
-    std::vector<VecTask> fill;
-    std::vector<CodesTask> lu_codes, row_codes;
-    std::vector<StartInTask> start_in;
-    std::vector<GroupTask<StartColEpi>> start_col;
-    std::vector<GroupTask<StartRowEpi>> start_row;
-    std::vector<LuTask> lu;
-    std::vector<DataInArgs> data_in;
-    std::vector<DataBcArgs> data_bc;
-    std::vector<UnscaleTask> unscale;
-    bool empty() const {
-        return xs.empty() && ys.empty() && rd.empty() && rp.empty() && rpg.empty() && gap.empty() && fin.empty() && mov.empty() && rc.empty() &&
-               sc.empty() && fill.empty() && lu_codes.empty() && row_codes.empty() && start_in.empty() && start_col.empty() && start_row.empty() &&
-               lu.empty() && data_in.empty() && data_bc.empty() && unscale.empty();
+template <class... Task>
+struct KindList {
+    using Stage = std::tuple<std::vector<Task>...>;  // the records of one stage
+    static_assert(sizeof...(Task) <= 64, "GroupTable keeps the kinds present in a stage as bits of one word");
+    template <class T>
+    static constexpr int index() {
+        constexpr bool same[] = {std::is_same_v<T, Task>...};
+        for (int i = 0; i < static_cast<int>(sizeof...(Task)); ++i)
+            if (same[i]) return i;
+        return -1;
     }
 };
+}  // namespace
+
+// THE LIST OF KINDS, in the one order in which a stage issues them (one launch per kind present).  A stage holds kinds that may
+// share a run in this order without one reading or overwriting what another still needs; the callers place next_stage() where
+// that does not hold (a check step's partials in part_x are overwritten by the next evaluation's Rd: two stages).  The order is
+// that of a member's own calls wherever two kinds of one stage touch the same memory:
+//   scaling:  row max norms, row sum norms, Curtis-Reid update, the elementwise kernels, [bound codes, row codes], the matrix
+//             scalings, the two reductions, ..., all finalize items;
+//   the loop and the re-solve:  zeroing (the elementwise kind), bound codes, row codes, restart copy, ctrl, the start, check x / y,
+//             residuals, gap, iteration-0 bound violation, movement, the two data passes, the solution, all finalize items.
+// The kinds of the first line other than the elementwise one, the codes and the finalize items are recorded by scale_many alone,
+// those from the restart copy to the solution never by it, so their mutual order is no statement.  ONE pair order differs from
+// what the scaling recorder had before it became this one: the two codes kernels now come BEFORE the two reductions and the
+// finalize items instead of after them (and before the matrix scalings, with which they never share a stage).  many.cpp records
+// them together in one stage only, the end of a scaling (Solver::scale_finish): there the reductions read AL, AU and c and write
+// part_v, the finalize items read part_v and write the sums block and scal, and the codes kernels read l, u, AL, AU and write
+// lu_code and row_code -- nobody writes what another of them reads or writes, apart from part_v, whose order is kept.
+using GroupKinds = KindList<RowNormTask<false>, RowNormTask<true>, GroupTask<CrEpi>, VecTask, CodesTask<false>, CodesTask<true>, RestartCopyTask, SetCtrlTask,
+                            StartInTask, GroupTask<StartColEpi>, GroupTask<StartRowEpi>, GroupTask<XEpi<true>>, GroupTask<YEpi<true>>,
+                            GroupTask<RdEpi>, GroupTask<RpEpi<false>>, GroupTask<RpEpi<true>>, GroupTask<GapEpi>, LuTask, MovementTask, DataInTask,
+                            DataBcTask, UnscaleTask, ScaleMat<0>, ScaleMat<1>, ScaleMat<2>, ScaleMat<3>, ScaleMat<4>, ScaleMat<5>, ScaleMat<6>,
+                            ScaleMat<7>, ReduceTask<true>, ReduceTask<false>, FinalizeOne>;
 
 struct GroupLaunches::Impl {
-    std::vector<GroupStage> stages = std::vector<GroupStage>(1);
-    GroupStage &st() { return stages.back(); }
+    GroupTable plan;
+    std::vector<GroupKinds::Stage> stages;
     std::vector<const double *> pack_src;
     std::vector<double *> pack_dst;  // the members' host blocks
     size_t pack_at = 0;              // where the last run's block holds the members' scalar pointers
@@ -3166,282 +3282,172 @@ struct GroupLaunches::Impl {
     DBuf<double> packed_d;
     HBuf<double> packed_h;
     std::vector<double *> deliver_to;
-    std::vector<char> bytes;  // the tables of a run, as they travel
-    std::vector<int2> map;
+    std::vector<int> grids;
 
-    size_t put(const void *p, size_t n) {
-        const size_t at = (bytes.size() + 15) / 16 * 16;
-        bytes.resize(at + n);
-        std::memcpy(bytes.data() + at, p, n);
-        return at;
+    explicit Impl(bool own_launches) : plan(own_launches, kReduceBlocks, kThreads) {}
+    template <class Task>
+    std::vector<Task> &rec() {  // the open stage's records of a kind
+        plan.note(GroupKinds::index<Task>());
+        if (stages.size() <= static_cast<size_t>(plan.open_stage())) stages.resize(static_cast<size_t>(plan.open_stage()) + 1);
+        return std::get<std::vector<Task>>(stages[plan.open_stage()]);
     }
-    template <class Task, class GridOf>
-    size_t put_map(const std::vector<Task> &tasks, GridOf grid_of, int *nwg) {
-        map.clear();
-        for (size_t t = 0; t < tasks.size(); ++t)
-            for (int lb = 0, lg = grid_of(tasks[t]); lb < lg; ++lb) map.push_back(int2{static_cast<int>(t), lb});
-        *nwg = static_cast<int>(map.size());
-        return put(map.data(), map.size() * sizeof(int2));
+    template <class Task>
+    void add(int stage) {  // a kind's tasks of one stage into the plan of a run
+        const std::vector<Task> &tasks = std::get<std::vector<Task>>(stages[stage]);
+        grids.clear();
+        if constexpr (Task::rule == kGridMapped)
+            for (const Task &t : tasks) grids.push_back(t.own_grid());
+        plan.add(stage, GroupKinds::index<Task>(), Task::rule, tasks.data(), sizeof(Task), static_cast<int>(tasks.size()), grids.data(), issues_own(tasks));
+    }
+    template <class Task>
+    void issue(const GroupLaunch &l, hipStream_t s) {
+        if (l.own) return issue_own(std::get<std::vector<Task>>(stages[l.stage]), s);
+        const char *dev = static_cast<const char *>(buf.dev);
+        const Task *tasks = reinterpret_cast<const Task *>(dev + l.tasks);
+        constexpr auto kernel = GroupKernel<Task>::pick();
+        if constexpr (Task::rule == kGridMapped) hipLaunchKernelGGL(kernel, dim3(l.nwg), dim3(kThreads), 0, s, tasks, reinterpret_cast<const int2 *>(dev + l.map));
+        else if constexpr (Task::rule == kGridReduce) hipLaunchKernelGGL(kernel, dim3(l.nwg), dim3(kThreads), 0, s, tasks);
+        else hipLaunchKernelGGL(kernel, dim3(l.nwg), dim3(kThreads), 0, s, tasks, l.ntasks);
+    }
+    template <int... I>
+    void rec_scale_matrix(int inst, const CsrStream &A, const double *rowvec, const double *colvec, double *next, std::integer_sequence<int, I...>) {
+        ((inst == I ? rec<ScaleMat<I>>().push_back({A, rowvec, colvec, next}) : void()), ...);
+    }
+    template <class... Task>
+    void add_all(int stage, KindList<Task...>) {
+        (add<Task>(stage), ...);
+    }
+    template <class... Task>
+    void issue_kind(const GroupLaunch &l, hipStream_t s, KindList<Task...>) {
+        using Fn = void (Impl::*)(const GroupLaunch &, hipStream_t);
+        static constexpr Fn fn[] = {&Impl::issue<Task>...};
+        (this->*fn[l.kind])(l, s);
     }
 };
 
-GroupLaunches::GroupLaunches() : impl(new Impl()) {}
+GroupLaunches::GroupLaunches(bool own_launches) : impl(new Impl(own_launches)) {}
 GroupLaunches::~GroupLaunches() = default;
 
-void GroupLaunches::next_stage() {
-    if (!impl->st().empty()) impl->stages.emplace_back();
-}
+void GroupLaunches::next_stage() { impl->plan.next_stage(); }
+void GroupLaunches::repeat_last(int nstages, int times) { impl->plan.repeat_last(nstages, times); }
 void GroupLaunches::x_half_check(const CsrDev &AT, const XHalfArgs &a) {
     XEpi<true> e{{a.y_full}, a.x, a.x_hat, a.l, a.u, a.c, a.last_x, a.x_bar, a.z_bar, a.x_temp, a.ctrl, a.partials, a.stride, 0, 0, 0, FarPush{}, a.lu_code};
-    impl->st().xs.push_back({stream_part(AT), e});
+    impl->rec<GroupTask<XEpi<true>>>().push_back({stream_part(AT), e});
 }
 void GroupLaunches::y_half_check(const CsrDev &A, const YHalfArgs &a) {
     YEpi<true> e{{a.xhat_full}, a.y, a.AL, a.AU, a.last_y, a.y_bar, a.y_obj, a.y_temp, a.ctrl, a.partials, a.stride, 0, 0, 0, 0, FarPush{}, a.row_code};
-    impl->st().ys.push_back({stream_part(A), e});
+    impl->rec<GroupTask<YEpi<true>>>().push_back({stream_part(A), e});
 }
 void GroupLaunches::resid_d(const CsrDev &AT, const double *ybar_full, const double *c, const double *z_bar, const double *col_norm,
                             double *partials) {
-    impl->st().rd.push_back({stream_part(AT), RdEpi{{ybar_full}, c, z_bar, col_norm, partials, AT.grid()}});
+    impl->rec<GroupTask<RdEpi>>().push_back({stream_part(AT), RdEpi{{ybar_full}, c, z_bar, col_norm, partials, AT.grid()}});
 }
 void GroupLaunches::resid_p(const CsrDev &A, const double *xbar_full, const double *xtemp_full, const double *AL, const double *AU,
                             const double *row_norm, const double *y_temp, bool with_gap, double *partials, int stride) {
-    if (with_gap) impl->st().rpg.push_back({stream_part(A), RpEpi<true>{{xbar_full, xtemp_full}, AL, AU, row_norm, y_temp, partials, stride}});
-    else impl->st().rp.push_back({stream_part(A), RpEpi<false>{{xbar_full}, AL, AU, row_norm, nullptr, partials, stride}});
+    if (with_gap) impl->rec<GroupTask<RpEpi<true>>>().push_back({stream_part(A), RpEpi<true>{{xbar_full, xtemp_full}, AL, AU, row_norm, y_temp, partials, stride}});
+    else impl->rec<GroupTask<RpEpi<false>>>().push_back({stream_part(A), RpEpi<false>{{xbar_full}, AL, AU, row_norm, nullptr, partials, stride}});
 }
 void GroupLaunches::gap(const CsrDev &A, const double *xtemp_full, const double *y_temp, double *partials) {
-    impl->st().gap.push_back({stream_part(A), GapEpi{{xtemp_full}, y_temp, partials, A.grid()}});
+    impl->rec<GroupTask<GapEpi>>().push_back({stream_part(A), GapEpi{{xtemp_full}, y_temp, partials, A.grid()}});
 }
 void GroupLaunches::finalize(const FinalizeArgs &f, double *scalars) {
-    for (int i = 0; i < f.n; ++i) impl->st().fin.push_back({f.item[i], scalars});
+    for (int i = 0; i < f.n; ++i) impl->rec<FinalizeOne>().push_back({f.item[i], scalars});
 }
 void GroupLaunches::movement(int n, int m, const double *x_bar, const double *last_x, double *x_temp, const double *y_bar, const double *last_y,
                              double *y_temp, double *partials, int stride) {
-    impl->st().mov.push_back({n, m, x_bar, last_x, x_temp, y_bar, last_y, y_temp, partials, stride});
+    impl->rec<MovementTask>().push_back({n, m, x_bar, last_x, x_temp, y_bar, last_y, y_temp, partials, stride});
 }
 void GroupLaunches::restart_copy(int n, int m, const double *x_bar, double *x, double *last_x, const double *y_bar, double *y, double *last_y,
                                  Ctrl *ctrl) {
-    impl->st().rc.push_back({n, m, x_bar, x, last_x, y_bar, y, last_y, ctrl, vec_grid(n > m ? n : m)});
+    impl->rec<RestartCopyTask>().push_back({n, m, x_bar, x, last_x, y_bar, y, last_y, ctrl, vec_grid(n > m ? n : m)});
 }
-void GroupLaunches::set_ctrl(Ctrl *ctrl, double sigma, double lambda_max, int reset_k) { impl->st().sc.push_back({ctrl, sigma, lambda_max, reset_k}); }
+void GroupLaunches::set_ctrl(Ctrl *ctrl, double sigma, double lambda_max, int reset_k) { impl->rec<SetCtrlTask>().push_back({ctrl, sigma, lambda_max, reset_k}); }
 void GroupLaunches::pack(const double *scalars, double *host) {
     impl->pack_src.push_back(scalars);
     impl->pack_dst.push_back(host);
 }
 void GroupLaunches::fill(double *x, double a, int n) {
-    if (n > 0) impl->st().fill.push_back({x, nullptr, a, n, kVecFill});
+    if (n > 0) impl->rec<VecTask>().push_back({x, nullptr, a, n, kVecFill});
+}
+void GroupLaunches::vec_scale(double *x, const double *sv, int n, bool divide) {
+    if (n > 0) impl->rec<VecTask>().push_back({x, sv, 0.0, n, divide ? kVecDiv : kVecMul});
+}
+void GroupLaunches::vec_scal(double *x, double a, int n) {
+    if (n > 0) impl->rec<VecTask>().push_back({x, nullptr, a, n, kVecScal});
+}
+void GroupLaunches::exp_clamp(double *v, int n) {
+    if (n > 0) impl->rec<VecTask>().push_back({v, nullptr, 0.0, n, kVecExpClamp});
 }
 void GroupLaunches::bound_codes(int n, const double *l, const double *u, unsigned char *code) {
-    if (n > 0) impl->st().lu_codes.push_back({n, l, u, code});
+    if (n > 0) impl->rec<CodesTask<false>>().push_back({n, l, u, code});
 }
 void GroupLaunches::row_codes(int m, const double *AL, const double *AU, unsigned char *code) {
-    if (m > 0) impl->st().row_codes.push_back({m, AL, AU, code});
+    if (m > 0) impl->rec<CodesTask<true>>().push_back({m, AL, AU, code});
 }
-void GroupLaunches::start_in(const StartInArgs &a) { impl->st().start_in.push_back({a, vec_grid(a.n > a.m ? a.n : a.m)}); }
+void GroupLaunches::start_in(const StartInArgs &a) { impl->rec<StartInTask>().push_back({a, vec_grid(a.n > a.m ? a.n : a.m)}); }
 void GroupLaunches::start_col(const CsrDev &AT, const double *ybar_full, const double *c, const double *l, const double *u, const double *x_bar,
                               double *z_bar, double *partials) {
-    impl->st().start_col.push_back({stream_part(AT), StartColEpi{{ybar_full}, c, l, u, x_bar, z_bar, partials, AT.grid()}});
+    impl->rec<GroupTask<StartColEpi>>().push_back({stream_part(AT), StartColEpi{{ybar_full}, c, l, u, x_bar, z_bar, partials, AT.grid()}});
 }
 void GroupLaunches::start_row(const CsrDev &A, const double *xbar_full, const double *AL, const double *AU, const double *y_bar, double *y_obj,
                               double *partials) {
-    impl->st().start_row.push_back({stream_part(A), StartRowEpi{{xbar_full}, AL, AU, y_bar, y_obj, partials, A.grid()}});
+    impl->rec<GroupTask<StartRowEpi>>().push_back({stream_part(A), StartRowEpi{{xbar_full}, AL, AU, y_bar, y_obj, partials, A.grid()}});
 }
 void GroupLaunches::lu(int n, const double *x_bar, const double *l, const double *u, const double *col_norm, double *x_temp, double *partials) {
-    impl->st().lu.push_back({n, x_bar, l, u, col_norm, x_temp, partials});
+    impl->rec<LuTask>().push_back({n, x_bar, l, u, col_norm, x_temp, partials});
 }
 void GroupLaunches::data_in(const DataInArgs &a) {
     if (a.stride != kReduceBlocks) throw std::runtime_error("group data pass: the partials' stride is the member's own grid");
-    impl->st().data_in.push_back(a);
+    impl->rec<DataInTask>().push_back({a});
 }
 void GroupLaunches::data_bc(const DataBcArgs &a) {
     if (a.stride != kReduceBlocks) throw std::runtime_error("group data pass: the partials' stride is the member's own grid");
-    impl->st().data_bc.push_back(a);
+    impl->rec<DataBcTask>().push_back({a});
 }
 void GroupLaunches::unscale(int n, int m, const double *x_bar, const double *y_bar, const double *z_bar, const double *col_norm,
                             const double *row_norm, double b_scale, double c_scale, double *xo, double *yo, double *zo) {
-    impl->st().unscale.push_back({n, m, x_bar, y_bar, z_bar, col_norm, row_norm, b_scale, c_scale, xo, yo, zo, vec_grid(n > m ? n : m)});
+    impl->rec<UnscaleTask>().push_back({n, m, x_bar, y_bar, z_bar, col_norm, row_norm, b_scale, c_scale, xo, yo, zo, vec_grid(n > m ? n : m)});
+}
+void GroupLaunches::bnorm2(const double *AL, const double *AU, int m, double *partials) { impl->rec<ReduceTask<true>>().push_back({AL, AU, m, partials}); }
+void GroupLaunches::norm2(const double *x, int n, double *partials) { impl->rec<ReduceTask<false>>().push_back({x, nullptr, n, partials}); }
+void GroupLaunches::row_norm(const CsrDev &M, double *result, int norm) {
+    if (norm != 99 && norm != 1) throw std::runtime_error("group scaling: a row norm other than the max norm and the sum norm");
+    if (norm == 99) impl->rec<RowNormTask<false>>().push_back({stream_part(M), result});
+    else impl->rec<RowNormTask<true>>().push_back({stream_part(M), result});
+}
+void GroupLaunches::scale_matrix(const CsrDev &M, const double *rowvec, const double *colvec_full, bool row_first, bool divide, double *next_max_norm) {
+    const int inst = (row_first ? 4 : 0) | (divide ? 2 : 0) | (next_max_norm ? 1 : 0);
+    impl->rec_scale_matrix(inst, stream_part(M), rowvec, colvec_full, next_max_norm, std::make_integer_sequence<int, 8>());
+}
+void GroupLaunches::cr_log_update(const CsrDev &M, const double *other_full, double *result) {
+    impl->rec<GroupTask<CrEpi>>().push_back({stream_part(M), CrEpi{{other_full}, M.rowptr, result, nullptr, 0}});
 }
 long GroupLaunches::tables_sent() const { return impl->tables_sent; }
-int GroupLaunches::recorded_launches() const {  // (every kind present in a stage is one launch, the stage's finalize items one more)
-    int n = 0;
-    for (const GroupStage &t : impl->stages)
-        n += !t.xs.empty() + !t.ys.empty() + !t.rd.empty() + !t.rp.empty() + !t.rpg.empty() + !t.gap.empty() + !t.fin.empty() + !t.mov.empty() +
-             !t.rc.empty() + !t.sc.empty() + !t.fill.empty() + !t.lu_codes.empty() + !t.row_codes.empty() + !t.start_in.empty() +
-             !t.start_col.empty() + !t.start_row.empty() + !t.lu.empty() + !t.data_in.empty() + !t.data_bc.empty() + !t.unscale.empty();
-    return n;
-}
+int GroupLaunches::recorded_launches() const { return impl->plan.recorded_launches(); }
 
 int GroupLaunches::run(hipStream_t s) {
     Impl &g = *impl;
-    g.bytes.clear();
     // ---- the tables of every kind present in every stage, in one block
-    struct Spot {
-        size_t tasks = 0, map = 0;
-        int nwg = 0;
-    };
-    struct Spots {
-        Spot x, y, rd, rp, rpg, gap, fin, mov, rc, sc, fill, lu_codes, row_codes, start_in, start_col, start_row, lu, data_in, data_bc, unscale;
-    };
-    // (the kinds of the group re-solve: a table for two tasks and more, with a {task, lb} map where the member's grid is its own)
-    auto plain_table = [&](const auto &tasks, Spot &sp) {
-        if (tasks.size() > 1) sp.tasks = g.put(tasks.data(), tasks.size() * sizeof(tasks[0]));
-    };
-    auto mapped_table = [&](const auto &tasks, Spot &sp, auto grid_of) {
-        if (tasks.size() < 2) return;
-        sp.tasks = g.put(tasks.data(), tasks.size() * sizeof(tasks[0]));
-        sp.map = g.put_map(tasks, grid_of, &sp.nwg);
-    };
-    std::vector<Spots> spots(g.stages.size());
-    // A kind with ONE task is that member's own launch, arguments in the launch and no table: a group of one (or the last member
-    // still running) issues what it issues alone.
-    auto spmv_tables = [&](auto &tasks, Spot &sp) {
-        if (tasks.size() < 2) return;
-        sp.tasks = g.put(tasks.data(), tasks.size() * sizeof(tasks[0]));
-        sp.map = g.put_map(tasks, [](const auto &t) { return t.A.csr_grid(); }, &sp.nwg);
-    };
-    for (size_t i = 0; i < g.stages.size(); ++i) {
-        GroupStage &t = g.stages[i];
-        Spots &p = spots[i];
-        if (t.rc.size() > 1) {
-            p.rc.tasks = g.put(t.rc.data(), t.rc.size() * sizeof(RestartCopyTask));
-            p.rc.map = g.put_map(t.rc, [](const RestartCopyTask &r) { return r.grid; }, &p.rc.nwg);
-        }
-        if (t.sc.size() > 1) p.sc.tasks = g.put(t.sc.data(), t.sc.size() * sizeof(SetCtrlTask));
-        mapped_table(t.fill, p.fill, [](const VecTask &v) { return elem_grid(v.n); });
-        mapped_table(t.lu_codes, p.lu_codes, [](const CodesTask &c) { return elem_grid(c.n); });
-        mapped_table(t.row_codes, p.row_codes, [](const CodesTask &c) { return elem_grid(c.n); });
-        mapped_table(t.start_in, p.start_in, [](const StartInTask &v) { return v.grid; });
-        spmv_tables(t.start_col, p.start_col);
-        spmv_tables(t.start_row, p.start_row);
-        plain_table(t.lu, p.lu);
-        plain_table(t.data_in, p.data_in);
-        plain_table(t.data_bc, p.data_bc);
-        mapped_table(t.unscale, p.unscale, [](const UnscaleTask &v) { return v.grid; });
-        spmv_tables(t.xs, p.x);
-        spmv_tables(t.ys, p.y);
-        spmv_tables(t.rd, p.rd);
-        spmv_tables(t.rp, p.rp);
-        spmv_tables(t.rpg, p.rpg);
-        spmv_tables(t.gap, p.gap);
-        if (t.mov.size() > 1) p.mov.tasks = g.put(t.mov.data(), t.mov.size() * sizeof(MovementTask));
-        if (!one_members_items(t.fin)) p.fin.tasks = g.put(t.fin.data(), t.fin.size() * sizeof(FinalizeOne));
-    }
+    g.plan.begin();
+    if (g.stages.size() <= static_cast<size_t>(g.plan.open_stage())) g.stages.resize(static_cast<size_t>(g.plan.open_stage()) + 1);
+    for (int i = 0; i < g.plan.open_stage(); ++i) g.add_all(i, GroupKinds());
     size_t pack_at = 0;
-    if (g.pack_src.size() > 1) pack_at = g.put(g.pack_src.data(), g.pack_src.size() * sizeof(const double *));
-    int launches = 0;
-    if (!g.bytes.empty()) {
-        std::memcpy(g.buf.stage(g.bytes.size()), g.bytes.data(), g.bytes.size());
-        g.buf.send(g.bytes.size(), s);
+    if (g.pack_src.size() > 1) pack_at = g.plan.put(g.pack_src.data(), g.pack_src.size() * sizeof(const double *));
+    const std::vector<char> &bytes = g.plan.bytes();
+    if (!bytes.empty()) {
+        std::memcpy(g.buf.stage(bytes.size()), bytes.data(), bytes.size());
+        g.buf.send(bytes.size(), s);
         ++g.tables_sent;
     }
-    const char *dev = static_cast<const char *>(g.buf.dev);
-    auto launched = [&]() {
+    // ---- stage by stage (a repeated one again) one launch per kind present
+    int launches = 0;
+    for (const GroupLaunch &l : g.plan.finish()) {
+        g.issue_kind(l, s, GroupKinds());
         HIP_CHECK(hipGetLastError());  // (a refused launch must not pass silently)
         ++launches;
-    };
-    auto spmv_launch = [&](auto &tasks, const Spot &sp) {
-        using Task = std::decay_t<decltype(tasks[0])>;
-        using Epi = decltype(Task::epi);
-        if (tasks.size() == 1) {
-            const CsrStream &a = tasks[0].A;
-            CsrDev M;  // (what k_spmv_fused reads of it)
-            M.nblk = a.nblk, M.nt = a.nt, M.rowptr = a.rowptr, M.col = a.col, M.val = const_cast<double *>(a.val), M.blk = a.blk;
-            hipLaunchKernelGGL(k_spmv_fused<Epi>, dim3(a.csr_grid()), dim3(kThreads), 0, s, M, tasks[0].epi);
-            launched();
-            return;
-        }
-        if (sp.nwg <= 0) return;
-        hipLaunchKernelGGL(k_spmv_fused_many<Epi>, dim3(sp.nwg), dim3(kThreads), 0, s, reinterpret_cast<const Task *>(dev + sp.tasks),
-                           reinterpret_cast<const int2 *>(dev + sp.map));
-        launched();
-    };
-    // (the kinds of the group re-solve: ONE task is the member's own launch -- `own` issues it --, two and more go through the
-    // table: with a {task, lb} map on the members' own grids, or kReduceBlocks workgroups per task and no map)
-    auto mapped_launch = [&](auto kernel, const auto &tasks, const Spot &sp, auto own) {
-        using Task = std::decay_t<decltype(tasks[0])>;
-        if (tasks.size() == 1) {
-            own(tasks[0]);
-            launched();
-        } else if (sp.nwg > 0) {
-            hipLaunchKernelGGL(kernel, dim3(sp.nwg), dim3(kThreads), 0, s, reinterpret_cast<const Task *>(dev + sp.tasks),
-                               reinterpret_cast<const int2 *>(dev + sp.map));
-            launched();
-        }
-    };
-    auto reduce_launch = [&](auto kernel, const auto &tasks, const Spot &sp, auto own) {
-        using Task = std::decay_t<decltype(tasks[0])>;
-        if (tasks.size() == 1) {
-            own(tasks[0]);
-            launched();
-        } else if (tasks.size() > 1) {
-            hipLaunchKernelGGL(kernel, dim3(static_cast<unsigned>(tasks.size()) * kReduceBlocks), dim3(kThreads), 0, s,
-                               reinterpret_cast<const Task *>(dev + sp.tasks));
-            launched();
-        }
-    };
-    // ---- stage by stage one launch per kind present, in the order of a member's own calls: zeroing, bound codes, restart copy,
-    // ctrl, the start, check x / y, residuals, gap, iteration-0 bound violation, movement, the two data passes, the solution, then
-    // every finalize item of the stage
-    for (size_t i = 0; i < g.stages.size(); ++i) {
-        GroupStage &t = g.stages[i];
-        const Spots &p = spots[i];
-        mapped_launch(k_vec_many, t.fill, p.fill, [&](const VecTask &v) { launch_fill(v.x, v.a, v.n, s); });
-        mapped_launch(k_bound_codes_many, t.lu_codes, p.lu_codes, [&](const CodesTask &v) { launch_bound_codes(v.n, v.a, v.b, v.code, s); });
-        mapped_launch(k_row_codes_many, t.row_codes, p.row_codes, [&](const CodesTask &v) { launch_row_codes(v.n, v.a, v.b, v.code, s); });
-        if (t.rc.size() == 1) {
-            const RestartCopyTask &r = t.rc[0];
-            launch_restart_copy(r.n, r.m, r.x_bar, r.x, r.last_x, r.y_bar, r.y, r.last_y, r.ctrl, s);
-            launched();
-        } else if (p.rc.nwg > 0) {
-            hipLaunchKernelGGL(k_restart_copy_many, dim3(p.rc.nwg), dim3(kThreads), 0, s, reinterpret_cast<const RestartCopyTask *>(dev + p.rc.tasks),
-                               reinterpret_cast<const int2 *>(dev + p.rc.map));
-            launched();
-        }
-        if (t.sc.size() == 1) {
-            launch_set_ctrl(t.sc[0].ctrl, t.sc[0].sigma, t.sc[0].lambda_max, t.sc[0].reset_k, s);
-            launched();
-        } else if (!t.sc.empty()) {
-            const int n = static_cast<int>(t.sc.size());
-            hipLaunchKernelGGL(k_set_ctrl_many, dim3((n + kThreads - 1) / kThreads), dim3(kThreads), 0, s,
-                               reinterpret_cast<const SetCtrlTask *>(dev + p.sc.tasks), n);
-            launched();
-        }
-        mapped_launch(k_start_in_many, t.start_in, p.start_in, [&](const StartInTask &v) { launch_start_in(v.a, s); });
-        spmv_launch(t.start_col, p.start_col);
-        spmv_launch(t.start_row, p.start_row);
-        spmv_launch(t.xs, p.x);
-        spmv_launch(t.ys, p.y);
-        spmv_launch(t.rd, p.rd);
-        spmv_launch(t.rp, p.rp);
-        spmv_launch(t.rpg, p.rpg);
-        spmv_launch(t.gap, p.gap);
-        reduce_launch(k_lu_many, t.lu, p.lu,
-                      [&](const LuTask &v) { launch_lu(v.n, v.x_bar, v.l, v.u, v.col_norm, v.x_temp, v.partials, kReduceBlocks, s); });
-        if (t.mov.size() == 1) {
-            const MovementTask &v = t.mov[0];
-            launch_movement(v.n, v.m, v.x_bar, v.last_x, v.x_temp, v.y_bar, v.last_y, v.y_temp, v.partials, v.stride, kReduceBlocks, s);
-            launched();
-        } else if (!t.mov.empty()) {
-            hipLaunchKernelGGL(k_movement_many, dim3(static_cast<unsigned>(t.mov.size()) * kReduceBlocks), dim3(kThreads), 0, s,
-                               reinterpret_cast<const MovementTask *>(dev + p.mov.tasks));
-            launched();
-        }
-        reduce_launch(k_data_in_many, t.data_in, p.data_in, [&](const DataInArgs &v) { launch_data_in(v, s); });
-        reduce_launch(k_data_bc_many, t.data_bc, p.data_bc, [&](const DataBcArgs &v) { launch_data_bc(v, s); });
-        mapped_launch(k_unscale_many, t.unscale, p.unscale, [&](const UnscaleTask &v) {
-            launch_unscale(v.n, v.m, v.x_bar, v.y_bar, v.z_bar, v.col_norm, v.row_norm, v.b_scale, v.c_scale, v.xo, v.yo, v.zo, s);
-        });
-        if (one_members_items(t.fin)) {
-            FinalizeArgs f{};
-            for (const FinalizeOne &o : t.fin) f.item[f.n++] = o.it;
-            launch_finalize(f, t.fin[0].scalars, s);
-            launched();
-        } else if (!t.fin.empty()) {
-            hipLaunchKernelGGL(k_finalize_many, dim3(static_cast<unsigned>(t.fin.size())), dim3(kThreads), 0, s,
-                               reinterpret_cast<const FinalizeOne *>(dev + p.fin.tasks));
-            launched();
-        }
     }
-    g.stages.assign(1, GroupStage());
+    for (GroupKinds::Stage &t : g.stages)  // (emptied, capacity kept: a loop's rounds record into the same storage)
+        std::apply([](auto &...tasks) { (tasks.clear(), ...); }, t);
     g.pack_at = pack_at;
     g.pack_n = static_cast<int>(g.pack_src.size());
     g.pack_one = g.pack_src.empty() ? nullptr : g.pack_src[0];
@@ -3478,223 +3484,6 @@ void GroupLaunches::deliver() {
     Impl &g = *impl;
     for (int k = 0; k < g.deliver_n; ++k) std::memcpy(g.deliver_to[k], g.packed_h.p + static_cast<size_t>(k) * kNumScalars, kNumScalars * sizeof(double));
     g.deliver_n = 0;
-}
-
-// ------------------------------------------------------------------------------------------------
-// group forms of the scaling kernels (DESIGN.md "Many small LPs", group scaling; many.cpp: scale_many).  The rule of the group
-// launches above: a workgroup reads {task, lb} (uniform: scalar loads) and runs the single kernel's body as workgroup lb of the
-// member's own grid -- ceil(len / kThreads) for the elementwise kernels, csr_grid() for the matrix passes, kReduceBlocks for the
-// two reductions (task = blockIdx.x / kReduceBlocks, no table) -- so every value, partial and finalised sum is the member's own.
-// ------------------------------------------------------------------------------------------------
-// (VecTask / k_vec_many and CodesTask / k_bound_codes_many / k_row_codes_many stand further up: the group re-solve records them too)
-struct ReduceTask {  // k_bnorm2 (a = AL, b = AU) / k_norm2 (a = x)
-    const double *a, *b;
-    int n;
-    double *partials;
-};
-struct RowNormTask {
-    CsrStream A;
-    double *result;
-};
-struct ScaleMatTask {
-    CsrStream A;
-    const double *rowvec, *colvec;
-    double *next_norm;
-};
-
-__global__ void __launch_bounds__(kThreads) k_bnorm2_many(const ReduceTask *__restrict__ tasks) {
-    const ReduceTask t = tasks[blockIdx.x / kReduceBlocks];
-    bnorm2_body(t.a, t.b, t.n, t.partials, blockIdx.x % kReduceBlocks, kReduceBlocks);
-}
-__global__ void __launch_bounds__(kThreads) k_norm2_many(const ReduceTask *__restrict__ tasks) {
-    const ReduceTask t = tasks[blockIdx.x / kReduceBlocks];
-    norm2_body(t.a, t.n, t.partials, blockIdx.x % kReduceBlocks, kReduceBlocks);
-}
-__global__ void __launch_bounds__(kThreads) k_row_max_blocks_many(const RowNormTask *__restrict__ tasks, const int2 *__restrict__ wgmap) {
-    const int2 w = wgmap[blockIdx.x];
-    const CsrStream A = tasks[w.x].A;
-    row_max_blocks_body(A, tasks[w.x].result, w.y);
-}
-__global__ void __launch_bounds__(kThreads) k_row_sum_blocks_many(const RowNormTask *__restrict__ tasks, const int2 *__restrict__ wgmap) {
-    const int2 w = wgmap[blockIdx.x];
-    const CsrStream A = tasks[w.x].A;
-    row_sum_blocks_body(A, tasks[w.x].result, w.y);
-}
-template <bool ROW_FIRST, bool DIVIDE, bool NEXT>
-__global__ void __launch_bounds__(kThreads) k_scale_matrix_many(const ScaleMatTask *__restrict__ tasks, const int2 *__restrict__ wgmap) {
-    const int2 w = wgmap[blockIdx.x];
-    const ScaleMatTask t = tasks[w.x];
-    __shared__ double rsv[kWavesPerBlock][kStreamW];
-    scale_matrix_body<ROW_FIRST, DIVIDE, NEXT>(t.A.nblk, t.A.blk, t.A.rowptr, t.A.col, const_cast<double *>(t.A.val), t.rowvec, t.colvec, t.next_norm, w.y, rsv);
-}
-
-// One segment of a recording: tasks that do not depend on each other except in the fixed order of the kinds below, which is the
-// order of a member's own calls wherever two kinds of one segment touch the same memory (many.cpp places the marks accordingly).
-struct ScaleSegment {
-    std::vector<RowNormTask> rmax, rsum;
-    std::vector<GroupTask<CrEpi>> cr;
-    std::vector<VecTask> vec;
-    std::vector<ScaleMatTask> mat[8];  // index: ROW_FIRST << 2 | DIVIDE << 1 | NEXT
-    std::vector<ReduceTask> bn, n2;
-    std::vector<FinalizeOne> fin;
-    std::vector<CodesTask> lu, rc;
-};
-
-struct ScaleLaunches::Impl {
-    std::vector<ScaleSegment> segs = std::vector<ScaleSegment>(1);
-    std::vector<int> order;  // the closed segments in the order they are issued (a repeated one appears more than once)
-    SmallTaskBuf buf;
-    std::vector<char> bytes;
-    std::vector<int2> map;
-    ScaleSegment &st() { return segs.back(); }
-    size_t put(const void *p, size_t n) {
-        const size_t at = (bytes.size() + 15) / 16 * 16;
-        bytes.resize(at + n);
-        std::memcpy(bytes.data() + at, p, n);
-        return at;
-    }
-};
-
-ScaleLaunches::ScaleLaunches() : impl(new Impl()) {}
-ScaleLaunches::~ScaleLaunches() = default;
-
-void ScaleLaunches::fill(double *x, double a, int n) {
-    if (n > 0) impl->st().vec.push_back({x, nullptr, a, n, kVecFill});
-}
-void ScaleLaunches::vec_scale(double *x, const double *sv, int n, bool divide) {
-    if (n > 0) impl->st().vec.push_back({x, sv, 0.0, n, divide ? kVecDiv : kVecMul});
-}
-void ScaleLaunches::vec_scal(double *x, double a, int n) {
-    if (n > 0) impl->st().vec.push_back({x, nullptr, a, n, kVecScal});
-}
-void ScaleLaunches::exp_clamp(double *v, int n) {
-    if (n > 0) impl->st().vec.push_back({v, nullptr, 0.0, n, kVecExpClamp});
-}
-void ScaleLaunches::bnorm2(const double *AL, const double *AU, int m, double *partials) { impl->st().bn.push_back({AL, AU, m, partials}); }
-void ScaleLaunches::norm2(const double *x, int n, double *partials) { impl->st().n2.push_back({x, nullptr, n, partials}); }
-void ScaleLaunches::finalize(const double *partials, int count, double *scalars, int slot) {
-    impl->st().fin.push_back({FinalizeItem{partials, count, slot, 0}, scalars});
-}
-void ScaleLaunches::row_norm(const CsrDev &M, double *result, int norm) {
-    if (norm != 99 && norm != 1) throw std::runtime_error("group scaling: a row norm other than the max norm and the sum norm");
-    (norm == 99 ? impl->st().rmax : impl->st().rsum).push_back({stream_part(M), result});
-}
-void ScaleLaunches::scale_matrix(const CsrDev &M, const double *rowvec, const double *colvec_full, bool row_first, bool divide, double *next_max_norm) {
-    const int inst = (row_first ? 4 : 0) | (divide ? 2 : 0) | (next_max_norm ? 1 : 0);
-    impl->st().mat[inst].push_back({stream_part(M), rowvec, colvec_full, next_max_norm});
-}
-void ScaleLaunches::cr_log_update(const CsrDev &M, const double *other_full, double *result) {
-    impl->st().cr.push_back({stream_part(M), CrEpi{{other_full}, M.rowptr, result, nullptr, 0}});
-}
-void ScaleLaunches::bound_codes(int n, const double *l, const double *u, unsigned char *code) {
-    if (n > 0) impl->st().lu.push_back({n, l, u, code});
-}
-void ScaleLaunches::row_codes(int m, const double *AL, const double *AU, unsigned char *code) {
-    if (m > 0) impl->st().rc.push_back({m, AL, AU, code});
-}
-void ScaleLaunches::mark() {
-    impl->order.push_back(static_cast<int>(impl->segs.size()) - 1);
-    impl->segs.emplace_back();
-}
-void ScaleLaunches::repeat_last(int nseg, int times) {
-    Impl &g = *impl;
-    if (nseg <= 0 || static_cast<size_t>(nseg) > g.order.size()) throw std::runtime_error("group scaling: repeat of segments that were not recorded");
-    const std::vector<int> tail(g.order.end() - nseg, g.order.end());
-    for (int t = 1; t < times; ++t) g.order.insert(g.order.end(), tail.begin(), tail.end());
-}
-
-int ScaleLaunches::run(hipStream_t s) {
-    Impl &g = *impl;
-    mark();  // (what is open is part of this run)
-    g.bytes.clear();
-    struct Spot {
-        size_t tasks = 0, map = 0;
-        int nwg = 0;
-    };
-    struct Spots {
-        Spot rmax, rsum, cr, vec, mat[8], bn, n2, fin, lu, rc;
-    };
-    std::vector<Spots> spots(g.segs.size());
-    auto table = [&](const auto &tasks, Spot &sp) {
-        if (!tasks.empty()) sp.tasks = g.put(tasks.data(), tasks.size() * sizeof(tasks[0]));
-    };
-    auto table_map = [&](const auto &tasks, Spot &sp, auto grid_of) {
-        if (tasks.empty()) return;
-        sp.tasks = g.put(tasks.data(), tasks.size() * sizeof(tasks[0]));
-        g.map.clear();
-        for (size_t t = 0; t < tasks.size(); ++t)
-            for (int lb = 0, lg = grid_of(tasks[t]); lb < lg; ++lb) g.map.push_back(int2{static_cast<int>(t), lb});
-        sp.nwg = static_cast<int>(g.map.size());
-        sp.map = g.put(g.map.data(), g.map.size() * sizeof(int2));
-    };
-    auto csr_grid_of = [](const auto &t) { return t.A.csr_grid(); };
-    for (size_t i = 0; i + 1 < g.segs.size(); ++i) {  // (the last one is the empty segment mark() opened)
-        const ScaleSegment &t = g.segs[i];
-        Spots &p = spots[i];
-        table_map(t.rmax, p.rmax, csr_grid_of);
-        table_map(t.rsum, p.rsum, csr_grid_of);
-        table_map(t.cr, p.cr, csr_grid_of);
-        table_map(t.vec, p.vec, [](const VecTask &v) { return elem_grid(v.n); });
-        for (int k = 0; k < 8; ++k) table_map(t.mat[k], p.mat[k], csr_grid_of);
-        table(t.bn, p.bn);
-        table(t.n2, p.n2);
-        table(t.fin, p.fin);
-        table_map(t.lu, p.lu, [](const CodesTask &c) { return elem_grid(c.n); });
-        table_map(t.rc, p.rc, [](const CodesTask &c) { return elem_grid(c.n); });
-    }
-    int launches = 0;
-    if (!g.bytes.empty()) {
-        std::memcpy(g.buf.stage(g.bytes.size()), g.bytes.data(), g.bytes.size());
-        g.buf.send(g.bytes.size(), s);
-    }
-    const char *dev = static_cast<const char *>(g.buf.dev);
-    auto launched = [&]() {
-        HIP_CHECK(hipGetLastError());
-        ++launches;
-    };
-#define HPRLP_MAPPED(kernel, Task, sp)                                                                                                       \
-    if ((sp).nwg > 0) {                                                                                                                      \
-        hipLaunchKernelGGL(kernel, dim3((sp).nwg), dim3(kThreads), 0, s, reinterpret_cast<const Task *>(dev + (sp).tasks),                   \
-                           reinterpret_cast<const int2 *>(dev + (sp).map));                                                                  \
-        launched();                                                                                                                          \
-    }
-    for (int i : g.order) {
-        const ScaleSegment &t = g.segs[i];
-        const Spots &p = spots[i];
-        HPRLP_MAPPED(k_row_max_blocks_many, RowNormTask, p.rmax)
-        HPRLP_MAPPED(k_row_sum_blocks_many, RowNormTask, p.rsum)
-        HPRLP_MAPPED(k_spmv_fused_many<CrEpi>, GroupTask<CrEpi>, p.cr)
-        HPRLP_MAPPED(k_vec_many, VecTask, p.vec)
-        HPRLP_MAPPED((k_scale_matrix_many<false, false, false>), ScaleMatTask, p.mat[0])
-        HPRLP_MAPPED((k_scale_matrix_many<false, false, true>), ScaleMatTask, p.mat[1])
-        HPRLP_MAPPED((k_scale_matrix_many<false, true, false>), ScaleMatTask, p.mat[2])
-        HPRLP_MAPPED((k_scale_matrix_many<false, true, true>), ScaleMatTask, p.mat[3])
-        HPRLP_MAPPED((k_scale_matrix_many<true, false, false>), ScaleMatTask, p.mat[4])
-        HPRLP_MAPPED((k_scale_matrix_many<true, false, true>), ScaleMatTask, p.mat[5])
-        HPRLP_MAPPED((k_scale_matrix_many<true, true, false>), ScaleMatTask, p.mat[6])
-        HPRLP_MAPPED((k_scale_matrix_many<true, true, true>), ScaleMatTask, p.mat[7])
-        if (!t.bn.empty()) {
-            hipLaunchKernelGGL(k_bnorm2_many, dim3(static_cast<unsigned>(t.bn.size()) * kReduceBlocks), dim3(kThreads), 0, s,
-                               reinterpret_cast<const ReduceTask *>(dev + p.bn.tasks));
-            launched();
-        }
-        if (!t.n2.empty()) {
-            hipLaunchKernelGGL(k_norm2_many, dim3(static_cast<unsigned>(t.n2.size()) * kReduceBlocks), dim3(kThreads), 0, s,
-                               reinterpret_cast<const ReduceTask *>(dev + p.n2.tasks));
-            launched();
-        }
-        if (!t.fin.empty()) {
-            hipLaunchKernelGGL(k_finalize_many, dim3(static_cast<unsigned>(t.fin.size())), dim3(kThreads), 0, s,
-                               reinterpret_cast<const FinalizeOne *>(dev + p.fin.tasks));
-            launched();
-        }
-        HPRLP_MAPPED(k_bound_codes_many, CodesTask, p.lu)
-        HPRLP_MAPPED(k_row_codes_many, CodesTask, p.rc)
-    }
-#undef HPRLP_MAPPED
-    g.segs.assign(1, ScaleSegment());
-    g.order.clear();
-    return launches;
 }
 
 // warm-up (abi.cpp: hprlp_warmup): an attribute query makes the runtime load this translation unit's code object now instead

@@ -85,12 +85,6 @@ void check_group(Solver *const *s, int count, const char *who, bool need_scaled)
     }
 }
 
-// Solver::scale() (solver.cpp) walked for all joining members at once.  The stages are scale()'s own, in its order; what differs is
-// who issues a launch (ScaleLaunches: one per kernel kind for everybody in the stage) and where the six sums of squares travel:
-// bnorm_sq and reduce_sum_sq share part_v and S_TMP0 when a member runs alone, with a host round trip between them; here the second
-// reduction has the upper half of part_v for its partials (2 x kReduceBlocks were always allocated) and both sums are finalised
-// into a block of the group's, two slots per member, that one copy brings to the host.  Where a partial or a sum is stored does not
-// change its value; the host forms 1 + sqrt(.) and 1 / b_scale as scale() does and hands the factors over by value.
 void scale_many(Solver **s, int count, SetupCounts *counts) {
     check_group(s, count, "scale_many", false);
     SetupCounts sc;
@@ -113,187 +107,84 @@ void scale_many(Solver **s, int count, SetupCounts *counts) {
     sc.scale_launches += scaling_launch_count() - launches_before;
     const int nj = static_cast<int>(who.size());
     if (nj > 0) {
+        // Solver::scale() walked for all joining members at once: the pieces are scale()'s own (solver.cpp), in its order, recorded
+        // into one GroupLaunches with a table for every kind (inside a stage a kind may hold one member's task).  The group's own:
+        // the stages, one block for the second pairs of gathered vectors, and the sums block -- two slots per member, where the
+        // pieces finalise |b|^2 and |c|^2 and from where one copy brings them to the host, three times.
         const auto t0 = time_now();
         const hipStream_t st = scope.group;
-        struct Walk {
-            Solver *s;
-            double *gm, *gn, *gm_next, *gn_next;
-            bool fuse, have_norms;
-            int passes;
-        };
-        std::vector<Walk> w(static_cast<size_t>(nj));
-        // the second pair of gathered vectors of every member with Ruiz passes (scale(): gsm2 / gsn2), pieces of one block
+        std::vector<Solver::ScaleWalk> w(static_cast<size_t>(nj));
+        auto member = [&](int j) -> Solver & { return *s[who[j]]; };
+        // the second pair of gathered vectors of every member with Ruiz passes, pieces of one block
         auto aligned = [](size_t doubles) { return (doubles + 31) / 32 * 32; };
         size_t pair_doubles = 0;
-        for (int j = 0; j < nj; ++j) {
-            Solver &m = *s[who[j]];
-            if (m.prm.use_Ruiz_scaling) pair_doubles += aligned(static_cast<size_t>(m.m_pad)) + aligned(static_cast<size_t>(m.n_pad));
-        }
+        for (int j = 0; j < nj; ++j)
+            if (member(j).prm.use_Ruiz_scaling) pair_doubles += aligned(static_cast<size_t>(member(j).m_pad)) + aligned(static_cast<size_t>(member(j).n_pad));
         DBuf<double> pairs(std::max<size_t>(pair_doubles, 1)), sums(static_cast<size_t>(2) * nj);
         HBuf<double> sums_h;
         sums_h.alloc(static_cast<size_t>(2) * nj);
-        ScaleLaunches sl;
+        GroupLaunches gl(/*own_launches=*/false);
         auto run_fetch_wait = [&]() {
-            sc.scale_launches += sl.run(st);
+            sc.scale_launches += gl.run(st);
             HIP_CHECK(hipMemcpyAsync(sums_h.p, sums.p, sizeof(double) * 2 * nj, hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipStreamSynchronize(st));
             ++sc.scale_waits;
         };
-        auto both_norms = [&](int j, double *c_scalars, int c_slot) {  // bnorm_sq and reduce_sum_sq(c) of member j into its two slots
-            Solver &m = *w[j].s;
-            sl.bnorm2(m.AL.p, m.AU.p, m.m_loc, m.part_v.p);
-            sl.norm2(m.c.p, m.n_loc, m.part_v.p + kReduceBlocks);
-            sl.finalize(m.part_v.p, kReduceBlocks, sums.p, 2 * j);
-            sl.finalize(m.part_v.p + kReduceBlocks, kReduceBlocks, sums.p, 2 * j + 1);
-            if (c_scalars) sl.finalize(m.part_v.p + kReduceBlocks, kReduceBlocks, c_scalars, c_slot);
-        };
         // ---- the start of scale(): norms of the unscaled b and c
         size_t at = 0;
         for (int j = 0; j < nj; ++j) {
-            Solver &m = *s[who[j]];
-            Walk &v = w[j];
-            v.s = &m;
-            m.invalidate_far();
-            m.overlap_ready = false;
-            m.ovA.reset();
-            m.ovAT.reset();
-            v.fuse = m.prm.use_Ruiz_scaling;
-            v.gm = m.gsm.p, v.gn = m.gsn.p, v.gm_next = v.gn_next = nullptr;
-            if (v.fuse) {
-                v.gm_next = pairs.p + at;
+            Solver &m = member(j);
+            w[j].sums = sums.p + 2 * j;
+            if (m.prm.use_Ruiz_scaling) {
+                w[j].gm_next = pairs.p + at;
                 at += aligned(static_cast<size_t>(m.m_pad));
-                v.gn_next = pairs.p + at;
+                w[j].gn_next = pairs.p + at;
                 at += aligned(static_cast<size_t>(m.n_pad));
-                sl.fill(v.gm_next, 0.0, m.m_pad);
-                sl.fill(v.gn_next, 0.0, m.n_pad);
             }
-            v.have_norms = false;
-            v.passes = (m.prm.use_Ruiz_scaling ? 10 : 0) + (m.prm.use_Pock_Chambolle_scaling ? 1 : 0);
-            sl.fill(m.row_norm.p, 1.0, m.m_loc);
-            sl.fill(m.col_norm.p, 1.0, m.n_loc);
-            both_norms(j, nullptr, 0);
-            if (m.prm.use_CR_scaling) {
-                sl.fill(m.gsm.p, 0.0, m.m_pad);
-                sl.fill(m.gsn.p, 0.0, m.n_pad);
-            }
+            m.scale_begin(&w[j], &gl);
         }
         run_fetch_wait();
-        for (int j = 0; j < nj; ++j) {
-            w[j].s->norm_b_org = 1.0 + std::sqrt(sums_h[2 * j]);
-            w[j].s->norm_c_org = 1.0 + std::sqrt(sums_h[2 * j + 1]);
-        }
+        for (int j = 0; j < nj; ++j) member(j).scale_norms_org(sums_h.p + 2 * j);
         // ---- Curtis-Reid: twenty sweeps over A and A^T (two tables, issued twenty times), exp / clamp, the scaling pass
+        auto each_cr = [&](auto piece) {
+            for (int j = 0; j < nj; ++j)
+                if (member(j).prm.use_CR_scaling) piece(member(j), &w[j]);
+            gl.next_stage();
+        };
         bool any_cr = false;
-        for (const Walk &v : w) any_cr = any_cr || v.s->prm.use_CR_scaling;
+        for (int j = 0; j < nj; ++j) any_cr = any_cr || member(j).prm.use_CR_scaling;
         if (any_cr) {
-            for (const Walk &v : w)
-                if (v.s->prm.use_CR_scaling) sl.cr_log_update(v.s->A.view, v.gn, v.gm);
-            sl.mark();
-            for (const Walk &v : w)
-                if (v.s->prm.use_CR_scaling) sl.cr_log_update(v.s->AT.view, v.gm, v.gn);
-            sl.mark();
-            sl.repeat_last(2, 20);
-            for (const Walk &v : w)
-                if (v.s->prm.use_CR_scaling) {
-                    sl.exp_clamp(v.gm, v.s->m_loc);
-                    sl.exp_clamp(v.gn, v.s->n_loc);
-                }
-            sl.mark();
-            for (Walk &v : w) {
-                Solver &m = *v.s;
-                if (!m.prm.use_CR_scaling) continue;
-                double *t1 = v.gm, *t2 = v.gn;
-                sl.vec_scale(m.row_norm.p, t1, m.m_loc, true);
-                sl.vec_scale(m.col_norm.p, t2, m.n_loc, true);
-                sl.scale_matrix(m.A.view, t1, v.gn, true, false, v.fuse ? v.gm_next : nullptr);
-                sl.scale_matrix(m.AT.view, t2, v.gm, false, false, v.fuse ? v.gn_next : nullptr);
-                v.have_norms = v.fuse;
-                sl.vec_scale(m.AL.p, t1, m.m_loc, false);
-                sl.vec_scale(m.AU.p, t1, m.m_loc, false);
-                sl.vec_scale(m.c.p, t2, m.n_loc, false);
-                sl.vec_scale(m.l.p, t2, m.n_loc, true);
-                sl.vec_scale(m.u.p, t2, m.n_loc, true);
-            }
-            sl.mark();
+            each_cr([&](Solver &m, Solver::ScaleWalk *v) { m.scale_cr_sweep(v, false, &gl); });
+            each_cr([&](Solver &m, Solver::ScaleWalk *v) { m.scale_cr_sweep(v, true, &gl); });
+            gl.repeat_last(2, 20);
+            each_cr([&](Solver &m, Solver::ScaleWalk *v) { m.scale_cr_exp(v, &gl); });
+            each_cr([&](Solver &m, Solver::ScaleWalk *v) { m.scale_cr_apply(v, &gl); });
         }
         // ---- Ruiz (ten passes) and Pock-Chambolle (one); a member's pass `it` is its own whatever the others' switches are
         int most = 0;
-        for (const Walk &v : w) most = std::max(most, v.passes);
+        for (const Solver::ScaleWalk &v : w) most = std::max(most, v.passes);
         for (int it = 0; it < most; ++it) {
-            for (Walk &v : w) {
-                Solver &m = *v.s;
-                if (it >= v.passes) continue;
-                const int norm = (m.prm.use_Ruiz_scaling && it < 10) ? 99 : 1;
-                if (v.have_norms) {
-                    std::swap(v.gm, v.gm_next);
-                    std::swap(v.gn, v.gn_next);
-                } else {
-                    sl.row_norm(m.A.view, v.gm, norm);
-                    sl.row_norm(m.AT.view, v.gn, norm);
-                }
-                double *t1 = v.gm, *t2 = v.gn;
-                sl.vec_scale(m.row_norm.p, t1, m.m_loc, false);
-                sl.vec_scale(m.AL.p, t1, m.m_loc, true);
-                sl.vec_scale(m.AU.p, t1, m.m_loc, true);
-                sl.vec_scale(m.col_norm.p, t2, m.n_loc, false);
-                const bool next = v.fuse && it + 1 < v.passes && it + 1 < 10;
-                sl.scale_matrix(m.A.view, t1, v.gn, true, true, next ? v.gm_next : nullptr);
-                sl.scale_matrix(m.AT.view, t2, v.gm, false, true, next ? v.gn_next : nullptr);
-                v.have_norms = next;
-                sl.vec_scale(m.c.p, t2, m.n_loc, true);
-                sl.vec_scale(m.l.p, t2, m.n_loc, false);
-                sl.vec_scale(m.u.p, t2, m.n_loc, false);
-            }
-            sl.mark();
+            for (int j = 0; j < nj; ++j) member(j).scale_pass(&w[j], it, &gl);
+            gl.next_stage();
         }
         // ---- b / c scaling: the second round trip, for the members that have it
         bool any_bc = false;
         for (int j = 0; j < nj; ++j) {
-            if (!w[j].s->prm.use_bc_scaling) continue;
+            if (!member(j).prm.use_bc_scaling) continue;
             any_bc = true;
-            both_norms(j, nullptr, 0);
+            member(j).scale_sums(&w[j], &gl, nullptr);
         }
         if (any_bc) run_fetch_wait();
-        for (int j = 0; j < nj; ++j) {
-            Solver &m = *w[j].s;
-            if (!m.prm.use_bc_scaling) {
-                m.b_scale = 1.0;
-                m.c_scale = 1.0;
-                continue;
-            }
-            m.b_scale = 1.0 + std::sqrt(sums_h[2 * j]);
-            m.c_scale = 1.0 + std::sqrt(sums_h[2 * j + 1]);
-            const double bs = 1.0 / m.b_scale, cs = 1.0 / m.c_scale;
-            sl.vec_scal(m.AU.p, bs, m.m_loc);
-            sl.vec_scal(m.AL.p, bs, m.m_loc);
-            sl.vec_scal(m.l.p, bs, m.n_loc);
-            sl.vec_scal(m.u.p, bs, m.n_loc);
-            sl.vec_scal(m.c.p, cs, m.n_loc);
-        }
-        sl.mark();
-        // ---- the norms of the scaled b and c (|c|^2 also where the member's own last reduction leaves it: S_TMP0), the bound codes,
-        // the two gathered vectors back to zero
-        for (int j = 0; j < nj; ++j) {
-            Solver &m = *w[j].s;
-            both_norms(j, m.scal.p, S_TMP0);
-            if (!m.hook_no_bound_codes) {
-                if (m.lu_code.n != static_cast<size_t>(m.n_loc)) m.lu_code.alloc(static_cast<size_t>(m.n_loc));
-                if (m.row_code.n != static_cast<size_t>(m.m_loc)) m.row_code.alloc(static_cast<size_t>(m.m_loc));
-                sl.bound_codes(m.n_loc, m.l.p, m.u.p, m.lu_code.p);
-                sl.row_codes(m.m_loc, m.AL.p, m.AU.p, m.row_code.p);
-            }
-        }
-        sl.mark();  // (the gathered vectors were a pass's scale vectors: zeroed after everything that read them)
-        for (int j = 0; j < nj; ++j) {
-            Solver &m = *w[j].s;
-            sl.fill(m.gsm.p, 0.0, m.m_pad);
-            sl.fill(m.gsn.p, 0.0, m.n_pad);
-        }
+        for (int j = 0; j < nj; ++j) member(j).scale_bc_apply(sums_h.p + 2 * j, &gl);
+        gl.next_stage();
+        // ---- the norms of the scaled b and c, the bound codes, then the two gathered vectors back to zero
+        for (int j = 0; j < nj; ++j) member(j).scale_finish(&w[j], &gl, nullptr);
+        gl.next_stage();
+        for (int j = 0; j < nj; ++j) member(j).scale_end(&gl);
         run_fetch_wait();
         for (int j = 0; j < nj; ++j) {
-            Solver &m = *w[j].s;
-            m.norm_b = std::sqrt(sums_h[2 * j]);
-            m.norm_c = std::sqrt(sums_h[2 * j + 1]);
+            Solver &m = member(j);
+            m.scale_norms(sums_h.p + 2 * j);
             m.scal_h[S_TMP0] = sums_h[2 * j + 1];         // (what the member's own last fetch leaves in its host block)
             m.fetches += m.prm.use_bc_scaling ? 6 : 4;    // (the scalar fetches of its own scale())
             m.scaling_time = time_since(t0);              // the group's wall time

@@ -24,8 +24,9 @@ struct SetupCounts {
 // Throws (before anything is launched) unless s[0..count) are distinct, non-null, scaled, unsharded solvers on one device.
 // need_scaled = false: a solver never scaled is welcome (scale_many).
 void check_group(Solver *const *s, int count, const char *who, bool need_scaled = true);
-// Solver::scale() for every member, in lock-step: one launch per kernel kind and step for the members that join (Solver::joins_group,
-// fused Ruiz norms) -- kernels.h: ScaleLaunches --, three host waits for the whole group; every other member runs its own scale()
+// Solver::scale() for every member, in lock-step: the pieces of scale() recorded into one GroupLaunches for the members that join
+// (Solver::joins_group, fused Ruiz norms) -- one launch per kernel kind and stage, three host waits for the whole group; every other
+// member runs its own scale()
 // inside the same call, and so does a group with fewer than two joining members.  Every member ends bit for bit where its own
 // scale() leaves it.
 void scale_many(Solver **s, int count, SetupCounts *counts = nullptr);
@@ -60,7 +61,7 @@ struct ResolveCounts {
     long h2d = 0, d2h = 0, waits = 0, launches = 0, memsets = 0, served = 0, own = 0, loop_own = 0;
 };
 // Solver::set_data for every member.  The members that join (Solver::joins_group_resolve, two at least): all given vectors in one
-// pinned block and one copy, k_data_in_many, finalize, k_data_bc_many, finalize, the scalars packed, one copy back, ONE wait, then
+// pinned block and one copy, k_reduce_many<DataInTask>, finalize, k_reduce_many<DataBcTask>, finalize, the scalars packed, one copy back, ONE wait, then
 // each member's host formulas.  Every other member runs its own set_data inside the same call.  The members have passed
 // check_group and data is not null (abi.cpp owns those refusals); throws before anything is written or launched: an incomplete
 // bounds group, a NaN.

@@ -1261,122 +1261,216 @@ static double bnorm_sq(Solver *s) {
 // ------------------------------------------------------------------------------------------------
 // scaling (reference src/scaling.cu:88-216).  t1 lives in the gathered m-vector gsm, t2 in gsn, so
 // that the column-side scaling of each stored matrix can index the full vector.
+// scale() is the sequence of the pieces below; scale_many (many.cpp) walks the same pieces for a group, recording into g.
 // ------------------------------------------------------------------------------------------------
-void Solver::scale() {
+namespace {
+// a scaling piece's launch: recorded for a group run, or issued on the member's stream
+struct ScaleIssue {
+    GroupLaunches *g;
+    hipStream_t s;
+    void zero(double *x, int n) const {  // (recorded: a fill of +0.0, the bits of the memset)
+        if (g) g->fill(x, 0.0, n);
+        else HIP_CHECK(hipMemsetAsync(x, 0, sizeof(double) * n, s));
+    }
+    void fill(double *x, double a, int n) const { g ? g->fill(x, a, n) : launch_fill(x, a, n, s); }
+    void vec_scale(double *x, const double *v, int n, bool divide) const { g ? g->vec_scale(x, v, n, divide) : launch_vec_scale(x, v, n, divide, s); }
+    void vec_scal(double *x, double a, int n) const { g ? g->vec_scal(x, a, n) : launch_vec_scal(x, a, n, s); }
+    void exp_clamp(double *v, int n) const { g ? g->exp_clamp(v, n) : launch_exp_clamp(v, n, s); }
+    void row_norm(const CsrDev &M, double *result, int norm) const { g ? g->row_norm(M, result, norm) : launch_row_norm(M, result, norm, s); }
+    void scale_matrix(const CsrDev &M, const double *rowvec, const double *colvec_full, bool row_first, bool divide, double *next) const {
+        g ? g->scale_matrix(M, rowvec, colvec_full, row_first, divide, next) : launch_scale_matrix(M, rowvec, colvec_full, row_first, divide, s, next);
+    }
+};
+}  // namespace
+
+// Alone the two sums share part_v and S_TMP0, with a host round trip between them.  Recorded, the second reduction has the upper
+// half of part_v for its partials (2 x kReduceBlocks are allocated) and both sums are finalised into the caller's two slots --
+// where a partial or a sum is stored does not change its value; also_tmp0: |c|^2 into S_TMP0 too, where the member's own last
+// reduction leaves it.
+void Solver::scale_sums(ScaleWalk *w, GroupLaunches *g, double out[2], bool also_tmp0) {
+    if (!g) {
+        out[0] = bnorm_sq(this);
+        out[1] = reduce_sum_sq(c.p, n_loc);
+        return;
+    }
+    g->bnorm2(AL.p, AU.p, m_loc, part_v.p);
+    g->norm2(c.p, n_loc, part_v.p + kReduceBlocks);
+    FinalizeArgs f{};
+    f.n = 2;
+    f.item[0] = {part_v.p, kReduceBlocks, 0};
+    f.item[1] = {part_v.p + kReduceBlocks, kReduceBlocks, 1};
+    g->finalize(f, w->sums);
+    f.n = 1;
+    f.item[0] = {part_v.p + kReduceBlocks, kReduceBlocks, S_TMP0};
+    if (also_tmp0) g->finalize(f, scal.p);
+}
+void Solver::scale_norms_org(const double sums[2]) {
+    norm_b_org = 1.0 + std::sqrt(sums[0]);
+    norm_c_org = 1.0 + std::sqrt(sums[1]);
+}
+void Solver::scale_norms(const double sums[2]) {
+    norm_b = std::sqrt(sums[0]);
+    norm_c = std::sqrt(sums[1]);
+}
+
+void Solver::scale_begin(ScaleWalk *w, GroupLaunches *g) {
+    const ScaleIssue on{g, stream};
     invalidate_far();
-    const auto t0 = time_now();
     overlap_ready = false;  // the split copies of the shards carry matrix values
     ovA.reset();
     ovAT.reset();
     // Every matrix-scaling pass that a Ruiz pass follows also leaves that pass's row norms (max |a| of the scaled rows, kernels.hip:
     // k_scale_matrix<.., NEXT>) in a second pair of gathered vectors, so the norm passes over the matrices are not run; the pairs
     // change roles pass by pass.  HPRLP_NO_FUSED_NORMS=1: separate norm passes (A/B runs, tests).
-    const bool fuse_norms = prm.use_Ruiz_scaling && env_get("HPRLP_NO_FUSED_NORMS") == nullptr;
-    DBuf<double> gsm2, gsn2;
-    if (fuse_norms) {
-        gsm2.alloc(static_cast<size_t>(m_pad));
-        gsn2.alloc(static_cast<size_t>(n_pad));
-        HIP_CHECK(hipMemsetAsync(gsm2.p, 0, sizeof(double) * m_pad, stream));
-        HIP_CHECK(hipMemsetAsync(gsn2.p, 0, sizeof(double) * n_pad, stream));
-    }
-    double *gm = gsm.p, *gn = gsn.p, *gm_next = gsm2.p, *gn_next = gsn2.p;
-    double *t1 = gm + row_off, *t2 = gn + col_off;
-    double *t1n = fuse_norms ? gm_next + row_off : nullptr, *t2n = fuse_norms ? gn_next + col_off : nullptr;
-    bool have_norms = false;  // t1n / t2n hold the next pass's row norms
-    const bool max_next = fuse_norms;  // (a CR scaling pass is followed by Ruiz pass 0)
-    launch_fill(row_norm.p, 1.0, m_loc, stream);
-    launch_fill(col_norm.p, 1.0, n_loc, stream);
-    norm_b_org = 1.0 + std::sqrt(bnorm_sq(this));
-    norm_c_org = 1.0 + std::sqrt(reduce_sum_sq(c.p, n_loc));
-
-    if (prm.use_CR_scaling) {  // :40-83
-        HIP_CHECK(hipMemsetAsync(gsm.p, 0, sizeof(double) * m_pad, stream));
-        HIP_CHECK(hipMemsetAsync(gsn.p, 0, sizeof(double) * n_pad, stream));
-        // Matrices with a tiled copy run the 40 passes through the tiled kernel on a second value array of the copy that
-        // holds -log|a| (formed once; released when the passes are done).  HPRLP_NO_TILED_CR=1: stream kernel (A/B runs).
-        finish_tiling();
-        struct LogValues {
-            DBuf<double> tile, far;
-        } logA, logAT;
-        const bool tiled_cr = env_get("HPRLP_NO_TILED_CR") == nullptr;
-        auto log_values = [&](DeviceMatrix &M, LogValues &lv) {
-            if (!tiled_cr || !cr_runs_tiled(M.view)) return;
-            lv.tile.alloc(static_cast<size_t>(std::max<long>(M.tiled.n_tile, 1)));
-            lv.far.alloc(static_cast<size_t>(std::max<long>(M.tiled.n_rem, 1)));
-            launch_tiled_refresh_log(M.tiled, M.val.p, lv.tile.p, lv.far.p, stream);
-        };
-        log_values(A, logA);
-        log_values(AT, logAT);
-        for (int it = 0; it < 20; ++it) {
-            launch_cr_log_update(A.view, gsn.p, t1, stream, logA.tile.p, logA.far.p);
-            gather(gsm.p, true);
-            launch_cr_log_update(AT.view, gsm.p, t2, stream, logAT.tile.p, logAT.far.p);
-            gather(gsn.p, false);
+    w->fuse = prm.use_Ruiz_scaling && env_get("HPRLP_NO_FUSED_NORMS") == nullptr;
+    if (w->fuse) {
+        if (!g) {
+            w->gsm2.alloc(static_cast<size_t>(m_pad));
+            w->gsn2.alloc(static_cast<size_t>(n_pad));
+            w->gm_next = w->gsm2.p, w->gn_next = w->gsn2.p;
         }
-        if (logA.tile.p || logAT.tile.p) HIP_CHECK(hipStreamSynchronize(stream));  // the log values are released below
-        launch_exp_clamp(t1, m_loc, stream);
-        launch_exp_clamp(t2, n_loc, stream);
-        gather(gsm.p, true);
-        gather(gsn.p, false);
-        launch_vec_scale(row_norm.p, t1, m_loc, true, stream);
-        launch_vec_scale(col_norm.p, t2, n_loc, true, stream);
-        launch_scale_matrix(A.view, t1, gsn.p, /*row_first=*/true, /*divide=*/false, stream, max_next ? t1n : nullptr);
-        launch_scale_matrix(AT.view, t2, gsm.p, /*row_first=*/false, /*divide=*/false, stream, max_next ? t2n : nullptr);
-        have_norms = max_next;
-        launch_vec_scale(AL.p, t1, m_loc, false, stream);
-        launch_vec_scale(AU.p, t1, m_loc, false, stream);
-        launch_vec_scale(c.p, t2, n_loc, false, stream);
-        launch_vec_scale(l.p, t2, n_loc, true, stream);
-        launch_vec_scale(u.p, t2, n_loc, true, stream);
+        on.zero(w->gm_next, m_pad);
+        on.zero(w->gn_next, n_pad);
     }
+    w->gm = gsm.p, w->gn = gsn.p;
+    w->have_norms = false;
+    w->passes = (prm.use_Ruiz_scaling ? 10 : 0) + (prm.use_Pock_Chambolle_scaling ? 1 : 0);
+    on.fill(row_norm.p, 1.0, m_loc);
+    on.fill(col_norm.p, 1.0, n_loc);
+    double sums[2];
+    scale_sums(w, g, sums);
+    if (!g) scale_norms_org(sums);
+    if (!prm.use_CR_scaling) return;  // :40-83
+    on.zero(gsm.p, m_pad);
+    on.zero(gsn.p, n_pad);
+    if (g) return;  // (the matrices of a group launch have no tiled copy)
+    // Matrices with a tiled copy run the 40 passes through the tiled kernel on a second value array of the copy that
+    // holds -log|a| (formed once; released when the passes are done).  HPRLP_NO_TILED_CR=1: stream kernel (A/B runs).
+    finish_tiling();
+    const bool tiled_cr = env_get("HPRLP_NO_TILED_CR") == nullptr;
+    auto log_values = [&](DeviceMatrix &M, DBuf<double> &tile, DBuf<double> &far) {
+        if (!tiled_cr || !cr_runs_tiled(M.view)) return;
+        tile.alloc(static_cast<size_t>(std::max<long>(M.tiled.n_tile, 1)));
+        far.alloc(static_cast<size_t>(std::max<long>(M.tiled.n_rem, 1)));
+        launch_tiled_refresh_log(M.tiled, M.val.p, tile.p, far.p, stream);
+    };
+    log_values(A, w->logA_tile, w->logA_far);
+    log_values(AT, w->logAT_tile, w->logAT_far);
+}
 
-    const int passes = (prm.use_Ruiz_scaling ? 10 : 0) + (prm.use_Pock_Chambolle_scaling ? 1 : 0);
-    for (int it = 0; it < passes; ++it) {  // Ruiz :123-153 then Pock-Chambolle :157-183
-        const int norm = (prm.use_Ruiz_scaling && it < 10) ? 99 : 1;
-        if (have_norms) {  // left by the previous scaling pass in the other pair of vectors
-            std::swap(gm, gm_next);
-            std::swap(gn, gn_next);
-            t1 = gm + row_off, t2 = gn + col_off, t1n = gm_next + row_off, t2n = gn_next + col_off;
-        } else {
-            launch_row_norm(A.view, t1, norm, stream);
-            launch_row_norm(AT.view, t2, norm, stream);
-        }
-        gather(gm, true);
-        gather(gn, false);
-        launch_vec_scale(row_norm.p, t1, m_loc, false, stream);
-        launch_vec_scale(AL.p, t1, m_loc, true, stream);
-        launch_vec_scale(AU.p, t1, m_loc, true, stream);
-        launch_vec_scale(col_norm.p, t2, n_loc, false, stream);
-        const bool next = fuse_norms && it + 1 < passes && it + 1 < 10;  // a max-norm (Ruiz) pass follows
-        launch_scale_matrix(A.view, t1, gn, true, true, stream, next ? t1n : nullptr);
-        launch_scale_matrix(AT.view, t2, gm, false, true, stream, next ? t2n : nullptr);
-        have_norms = next;
-        launch_vec_scale(c.p, t2, n_loc, true, stream);
-        launch_vec_scale(l.p, t2, n_loc, false, stream);
-        launch_vec_scale(u.p, t2, n_loc, false, stream);
+void Solver::scale_cr_sweep(ScaleWalk *w, bool transposed, GroupLaunches *g) {
+    DeviceMatrix &M = transposed ? AT : A;
+    const double *other = transposed ? gsm.p : gsn.p;
+    double *result = transposed ? gsn.p + col_off : gsm.p + row_off;
+    if (g) return g->cr_log_update(M.view, other, result);
+    launch_cr_log_update(M.view, other, result, stream, transposed ? w->logAT_tile.p : w->logA_tile.p, transposed ? w->logAT_far.p : w->logA_far.p);
+    gather(transposed ? gsn.p : gsm.p, !transposed);
+}
+
+void Solver::scale_cr_exp(ScaleWalk *w, GroupLaunches *g) {
+    const ScaleIssue on{g, stream};
+    if (w->logA_tile.p || w->logAT_tile.p) HIP_CHECK(hipStreamSynchronize(stream));  // the log values are released after the scaling pass
+    on.exp_clamp(gsm.p + row_off, m_loc);
+    on.exp_clamp(gsn.p + col_off, n_loc);
+    gather(gsm.p, true);
+    gather(gsn.p, false);
+}
+
+void Solver::scale_cr_apply(ScaleWalk *w, GroupLaunches *g) {
+    const ScaleIssue on{g, stream};
+    double *t1 = gsm.p + row_off, *t2 = gsn.p + col_off;
+    const bool max_next = w->fuse;  // (a CR scaling pass is followed by Ruiz pass 0)
+    on.vec_scale(row_norm.p, t1, m_loc, true);
+    on.vec_scale(col_norm.p, t2, n_loc, true);
+    on.scale_matrix(A.view, t1, gsn.p, /*row_first=*/true, /*divide=*/false, max_next ? w->gm_next + row_off : nullptr);
+    on.scale_matrix(AT.view, t2, gsm.p, /*row_first=*/false, /*divide=*/false, max_next ? w->gn_next + col_off : nullptr);
+    w->have_norms = max_next;
+    on.vec_scale(AL.p, t1, m_loc, false);
+    on.vec_scale(AU.p, t1, m_loc, false);
+    on.vec_scale(c.p, t2, n_loc, false);
+    on.vec_scale(l.p, t2, n_loc, true);
+    on.vec_scale(u.p, t2, n_loc, true);
+    w->logAT_far.release(), w->logAT_tile.release(), w->logA_far.release(), w->logA_tile.release();
+}
+
+void Solver::scale_pass(ScaleWalk *w, int it, GroupLaunches *g) {  // Ruiz :123-153 then Pock-Chambolle :157-183
+    if (it >= w->passes) return;
+    const ScaleIssue on{g, stream};
+    const int norm = (prm.use_Ruiz_scaling && it < 10) ? 99 : 1;
+    if (w->have_norms) {  // left by the previous scaling pass in the other pair of vectors
+        std::swap(w->gm, w->gm_next);
+        std::swap(w->gn, w->gn_next);
     }
+    double *t1 = w->gm + row_off, *t2 = w->gn + col_off;
+    if (!w->have_norms) {
+        on.row_norm(A.view, t1, norm);
+        on.row_norm(AT.view, t2, norm);
+    }
+    gather(w->gm, true);
+    gather(w->gn, false);
+    on.vec_scale(row_norm.p, t1, m_loc, false);
+    on.vec_scale(AL.p, t1, m_loc, true);
+    on.vec_scale(AU.p, t1, m_loc, true);
+    on.vec_scale(col_norm.p, t2, n_loc, false);
+    const bool next = w->fuse && it + 1 < w->passes && it + 1 < 10;  // a max-norm (Ruiz) pass follows
+    on.scale_matrix(A.view, t1, w->gn, true, true, next ? w->gm_next + row_off : nullptr);
+    on.scale_matrix(AT.view, t2, w->gm, false, true, next ? w->gn_next + col_off : nullptr);
+    w->have_norms = next;
+    on.vec_scale(c.p, t2, n_loc, true);
+    on.vec_scale(l.p, t2, n_loc, false);
+    on.vec_scale(u.p, t2, n_loc, false);
+}
 
-    if (prm.use_bc_scaling) {  // :185-202
-        b_scale = 1.0 + std::sqrt(bnorm_sq(this));
-        c_scale = 1.0 + std::sqrt(reduce_sum_sq(c.p, n_loc));
-        const double bs = 1.0 / b_scale, cs = 1.0 / c_scale;
-        launch_vec_scal(AU.p, bs, m_loc, stream);
-        launch_vec_scal(AL.p, bs, m_loc, stream);
-        launch_vec_scal(l.p, bs, n_loc, stream);
-        launch_vec_scal(u.p, bs, n_loc, stream);
-        launch_vec_scal(c.p, cs, n_loc, stream);
-    } else {
+void Solver::scale_bc_apply(const double sums[2], GroupLaunches *g) {  // :185-202
+    if (!prm.use_bc_scaling) {
         b_scale = 1.0;
         c_scale = 1.0;
+        return;
     }
-    norm_b = std::sqrt(bnorm_sq(this));
-    norm_c = std::sqrt(reduce_sum_sq(c.p, n_loc));
+    const ScaleIssue on{g, stream};
+    b_scale = 1.0 + std::sqrt(sums[0]);
+    c_scale = 1.0 + std::sqrt(sums[1]);
+    const double bs = 1.0 / b_scale, cs = 1.0 / c_scale;
+    on.vec_scal(AU.p, bs, m_loc);
+    on.vec_scal(AL.p, bs, m_loc);
+    on.vec_scal(l.p, bs, n_loc);
+    on.vec_scal(u.p, bs, n_loc);
+    on.vec_scal(c.p, cs, n_loc);
+}
+
+void Solver::scale_finish(ScaleWalk *w, GroupLaunches *g, double out[2]) {
+    scale_sums(w, g, out, /*also_tmp0=*/true);
+    if (!g) scale_norms(out);
     finish_tiling();  // tiled copies still being built pick up the scaled values here ...
     A.refresh_tiled(stream);  // ... finished ones are refreshed
     AT.refresh_tiled(stream);
-    refresh_bound_codes();
-    HIP_CHECK(hipMemsetAsync(gsm.p, 0, sizeof(double) * m_pad, stream));
-    HIP_CHECK(hipMemsetAsync(gsn.p, 0, sizeof(double) * n_pad, stream));
+    refresh_bound_codes(g);
+}
+
+void Solver::scale_end(GroupLaunches *g) {  // (the gathered vectors were a pass's scale vectors: zeroed after everything that read them)
+    const ScaleIssue on{g, stream};
+    on.zero(gsm.p, m_pad);
+    on.zero(gsn.p, n_pad);
+}
+
+void Solver::scale() {
+    const auto t0 = time_now();
+    ScaleWalk w;
+    double sums[2];
+    scale_begin(&w);
+    if (prm.use_CR_scaling) {
+        for (int it = 0; it < 20; ++it) {
+            scale_cr_sweep(&w, false);
+            scale_cr_sweep(&w, true);
+        }
+        scale_cr_exp(&w);
+        scale_cr_apply(&w);
+    }
+    for (int it = 0; it < w.passes; ++it) scale_pass(&w, it);
+    if (prm.use_bc_scaling) scale_sums(&w, nullptr, sums);
+    scale_bc_apply(sums);
+    scale_finish(&w, nullptr, sums);
+    scale_end();
     HIP_CHECK(hipStreamSynchronize(stream));
     scaling_time = time_since(t0);
     scaled = true;

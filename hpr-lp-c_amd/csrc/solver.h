@@ -269,6 +269,29 @@ struct Solver {
                      const double *AL_, const double *AU_, const double *l_, const double *u_, const double *c_,
                      double obj_constant_, const HPRLP_parameters *param, Comm *comm_);
     void scale();                                                   // src/scaling.cu:88-216
+    // scale() in pieces (many.cpp: scale_many walks them for a group, with a stage change or a host round trip between two).  g:
+    // record instead of issuing; then a zeroing is a fill of +0.0, the second pair of gathered vectors and the two slots for the
+    // pair of sums (w->sums) are the caller's, and nothing is fetched: the caller brings the sums to the host.
+    struct ScaleWalk {
+        double *gm = nullptr, *gn = nullptr;            // the gathered scale vectors of this pass ...
+        double *gm_next = nullptr, *gn_next = nullptr;  // ... and where a scaling pass leaves the next pass's row norms (fuse)
+        bool fuse = false, have_norms = false;          // have_norms: gm_next / gn_next hold the next pass's row norms
+        int passes = 0;                                 // Ruiz (ten) + Pock-Chambolle (one)
+        double *sums = nullptr;                         // g: |b|^2 and |c|^2 are finalised into sums[0], sums[1]
+        DBuf<double> gsm2, gsn2;                        // alone: the second pair
+        DBuf<double> logA_tile, logA_far, logAT_tile, logAT_far;  // alone: -log|a| of the tiled copies, for the Curtis-Reid sweeps
+    };
+    void scale_begin(ScaleWalk *w, GroupLaunches *g = nullptr);          // fills, norms of the unscaled b and c, Curtis-Reid set-up
+    void scale_sums(ScaleWalk *w, GroupLaunches *g, double out[2], bool also_tmp0 = false);  // |b|^2, |c|^2 (alone: fetched into out)
+    void scale_norms_org(const double sums[2]);                          // ... of the unscaled problem: norm_b_org, norm_c_org
+    void scale_cr_sweep(ScaleWalk *w, bool transposed, GroupLaunches *g = nullptr);  // one Curtis-Reid update on A or on A^T
+    void scale_cr_exp(ScaleWalk *w, GroupLaunches *g = nullptr);         // after the sweeps: exp / clamp ...
+    void scale_cr_apply(ScaleWalk *w, GroupLaunches *g = nullptr);       // ... and the Curtis-Reid scaling pass (reads what exp / clamp wrote)
+    void scale_pass(ScaleWalk *w, int it, GroupLaunches *g = nullptr);   // Ruiz / Pock-Chambolle pass `it` (nothing past w->passes)
+    void scale_bc_apply(const double sums[2], GroupLaunches *g = nullptr);  // b_scale, c_scale and their passes (1 without b / c scaling)
+    void scale_finish(ScaleWalk *w, GroupLaunches *g, double out[2]);    // norms of the scaled b and c, tiled copies, bound codes
+    void scale_norms(const double sums[2]);                              // ... norm_b, norm_c
+    void scale_end(GroupLaunches *g = nullptr);                          // the gathered vectors back to zero
     double power_iteration(int max_iter, double tol, int *iters);   // src/power_iteration.cu:20-119
     void init_iteration_state(GroupLaunches *g = nullptr, double sigma_ = -1.0);  // src/HPRLP.cu:154-167 (sigma_ > 0 with g: the override)
     // (g, here and below: record the launch for a group run instead of issuing it -- kernels.h: GroupLaunches, many.cpp)

@@ -248,6 +248,8 @@ def lib():
         L.hprlp_solver_resolve_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(CMemberStart), C.POINTER(CResults)]
         L.hprlp_last_resolve_many_counts.argtypes = [C.POINTER(C.c_long)]
         L.hprlp_group_pack_selftest.argtypes = []
+    if hasattr(L, "hprlp_group_table_selftest"):  # (likewise)
+        L.hprlp_group_table_selftest.argtypes = []
     _lib = L
     return L
 

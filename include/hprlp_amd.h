@@ -419,6 +419,9 @@ int hprlp_solver_resolve_many(hprlp_solver **s, int count, const hprlp_member_st
 int hprlp_last_resolve_many_counts(long out[8]);
 /* self-test of the packing layout of the group's staging and result blocks, no GPU needed: 0, or the number of the failed check */
 int hprlp_group_pack_selftest(void);
+/* self-test of the table builder of the group launches (stage order, table block, launch list), no GPU needed: 0, or the number
+ * of the failed check */
+int hprlp_group_table_selftest(void);
 
 /* Named device vectors: x y x_hat x_bar y_bar z_bar x_temp y_temp y_obj last_x last_y AL AU l u c
  * row_norm col_norm A_val AT_val.  get returns the length (or -1); cap is the capacity of out. */

@@ -1,7 +1,7 @@
 """Group set-up, scaling and teardown of many small LPs (hprlp_solver_create_many / _scale_many / _destroy_many; csrc/many.cpp:
-scale_many, csrc/alloc.cpp: the arena, the *_many scaling kernels in csrc/kernels.hip; DESIGN.md "Many small LPs").  The group path
-changes neither arithmetic nor order: every member must be bit for bit the solver that Solver(model, param) + scale() give it
-alone.  So everything below is == or np.array_equal; nothing has a tolerance.  (Of scalars() the three wall times are left out:
+scale_many, csrc/alloc.cpp: the arena, the group forms of the scaling kernels in csrc/kernels.hip; DESIGN.md "Many small LPs").
+The group path changes neither arithmetic nor order: every member must be bit for bit the solver that Solver(model, param) +
+scale() give it alone.  So everything below is == or np.array_equal; nothing has a tolerance.  (Of scalars() the three wall times are left out:
 they are clock readings, not results.)"""
 import numpy as np
 import pytest
@@ -125,6 +125,58 @@ def test_members_with_different_switches_in_one_group(gpu):
     for k, (g, c) in enumerate(zip(group, ctrl)):
         same_scaled_solver(g, c, list(SWITCHES)[k])
     same_first_iterations(group, ctrl, "mixed")
+    close(group + ctrl, models)
+
+
+def tiny_lps():
+    """The smallest shapes that take every path of the group scaling: 40 x 70 and 70 x 40 (m > n) with 300 entries each, and
+    5 x 130 with one row of 100 entries (the vector-mode branch of the matrix passes: more than kLongRow = 64) and one empty
+    row.  No size is a multiple of 256."""
+    if "tiny" not in _lps:
+        from scipy import sparse
+        rng = np.random.default_rng(23)
+
+        def values(k):
+            return rng.normal(size=k) * 0.3 + np.sign(rng.normal(size=k))
+
+        def scattered(m, n, nnz):
+            at = rng.choice(m * n, size=nnz, replace=False)
+            return sparse.csr_matrix((values(nnz), (at // n, at % n)), shape=(m, n))
+
+        wide = sparse.lil_matrix((5, 130))
+        wide[0, np.sort(rng.choice(130, size=100, replace=False))] = values(100)
+        for i in (2, 3, 4):  # (row 1 stays empty)
+            wide[i, np.sort(rng.choice(130, size=12, replace=False))] = values(12)
+        wide = sparse.csr_matrix(wide)
+        assert np.diff(wide.indptr).tolist() == [100, 0, 12, 12, 12]
+        _lps["tiny"] = [evalcases.all_bounds_lp(scattered(40, 70, 300), 24), evalcases.all_bounds_lp(wide, 25),
+                        evalcases.all_bounds_lp(scattered(70, 40, 300), 26)]
+    return _lps["tiny"]
+
+
+def test_one_curtis_reid_member_among_three_tiny_ones(gpu):
+    """A kind that holds ONE task inside a repeated stage (only the 5 x 130 member has Curtis-Reid on: its forty sweeps, exp / clamp
+    and the Curtis-Reid scaling pass are tables of one task), a member with Ruiz off and Pock-Chambolle on (one sum-norm pass, no
+    fused norms, the <*, *, false> matrix instances only) and without b / c scaling, a member with m > n.  Bits as everywhere in
+    this file; the launches are one per kind present and stage, counted from Solver::scale()'s walk for these three switch sets:
+    4 (fills, the two reductions, finalize) + 40 (sweeps) + 1 (exp / clamp) + 3 (vectors, two matrix instances) + 7 (pass 0: max
+    norms of the first member, sum norms of the third, vectors, four matrix instances) + 8 x 3 (passes 1-8) + 3 (pass 9) + 4
+    (pass 10: sum norms, vectors, two instances) + 3 (b / c reductions, finalize) + 1 (b / c passes) + 5 (reductions, finalize, two
+    codes kernels) + 1 (zeroing) = 96, with three host waits."""
+    lps = tiny_lps()
+    models = [make(lp) for lp in lps]
+    prms = [prm("no-cr"), prm("default"), prm("pc-only")]
+    group = [hprlp.Solver(mod, p) for mod, p in zip(models, prms)]
+    assert all(s.info()["tiled"] & 4 for s in group)  # (all on the small path)
+    hprlp.Solver.scale_many(group)
+    cnt = hprlp.last_setup_many_counts()
+    print(cnt)
+    assert cnt["members served by group scaling launches"] == 3 and cnt["members that scaled on their own"] == 0
+    assert (cnt["scaling launches"], cnt["scaling host waits"]) == (96, 3), cnt
+    ctrl = controls(models, prms)
+    for k, (g, c) in enumerate(zip(group, ctrl)):
+        same_scaled_solver(g, c, ("tiny", k))
+    same_first_iterations(group, ctrl, "tiny")
     close(group + ctrl, models)
 
 

@@ -113,3 +113,10 @@ def test_packing_layout_selftest():
     """Ranges disjoint and inside their block, absent vectors take no room, a pack / unpack round trip on host memory returns
     what went in (csrc/group_pack.cpp lists the numbered checks)."""
     assert hprlp.lib().hprlp_group_pack_selftest() == 0
+
+
+def test_group_table_selftest():
+    """The host side of a group recording: table and map offsets aligned and disjoint, the {task, lb} map of grids {3, 0, 2}, a
+    one-task kind with and without the own-launch rule, repeat_last(2, 20), the launch list against recorded_launches(), an empty
+    trailing stage (csrc/group_table.cpp lists the numbered checks)."""
+    assert hprlp.lib().hprlp_group_table_selftest() == 0
