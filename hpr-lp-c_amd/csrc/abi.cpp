@@ -2046,6 +2046,7 @@ extern "C" int hprlp_solver_describe(hprlp_solver *h, char *buf, int cap) {
         if (t.f_rk) d += ", source-side run tables";
         if (t.f_work) d += ", pre-pass work list of " + std::to_string(t.n_work) + " workgroups for " + std::to_string(t.n_groups) + " source groups";
         if (t.side_nblk > 0) d += ", long rows aside (" + std::to_string(t.side_nblk) + " blocks through the stream kernel)";
+        if (t.repeats) d += ", repeats";  // (some tile has several steps: the <.., REP = true> instantiations run)
         return d;
     };
     std::string d = one("A", s.A) + "; " + one("A^T", s.AT);
