@@ -783,6 +783,38 @@ extern "C" int hprlp_batched_solver_seconds(hprlp_batched_solver *h, double out[
     }
 }
 
+// One ray test outside the loop on the resident batched solver, and its panels by name (batched.hip: batched_solver_ray_step)
+extern "C" int hprlp_batched_solver_ray_step(hprlp_batched_solver *h, const int *active, int restart, double *out, int *tested) {
+    try {
+        if (!h || !h->s) throw std::runtime_error("hprlp_batched_solver_ray_step: null solver");
+        return batched_solver_ray_step(h->s, active, restart != 0, out, tested);
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+extern "C" long hprlp_batched_solver_get_panel(hprlp_batched_solver *h, const char *name, double *out, long len) {
+    try {
+        if (!h || !h->s) throw std::runtime_error("hprlp_batched_solver_get_panel: null solver");
+        return batched_solver_get_panel(h->s, name, out, len);
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+extern "C" int hprlp_batched_solver_set_panel(hprlp_batched_solver *h, const char *name, const double *in, long len) {
+    try {
+        if (!h || !h->s) throw std::runtime_error("hprlp_batched_solver_set_panel: null solver");
+        batched_solver_set_panel(h->s, name, in, len);
+        return 0;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
 extern "C" void hprlp_free_batched_certificates(hprlp_batched_certificates *certs) {
     if (!certs) return;
     for (void *p : {static_cast<void *>(certs->kind), static_cast<void *>(certs->iter), static_cast<void *>(certs->objective),

@@ -54,5 +54,12 @@ int batched_solver_scalars(const BatchedSolver *h, double *out);     // 7 x B of
 void batched_solver_transfer(const BatchedSolver *h, long out[4]);   // hprlp_batched_solver_transfer
 void batched_solver_info(const BatchedSolver *h, long out[8]);       // hprlp_batched_solver_info
 void batched_solver_seconds(const BatchedSolver *h, double out[6]);  // hprlp_batched_solver_seconds
+// One ray test of the detection outside the loop, on the panels of the last successful solve (hprlp_batched_solver_ray_step):
+// active (B ints), out (9 x B slots, slot-major), tested (B); 1 after a test, 0 where the iterate was only stored (restart).
+int batched_solver_ray_step(BatchedSolver *h, const int *active, bool restart, double *out, int *tested);
+// A panel of the last successful solve by name, column-major rows x B (hprlp_batched_solver_get_panel / _set_panel); X_bar and
+// Y_bar alone can be written.
+long batched_solver_get_panel(BatchedSolver *h, const char *name, double *out, long len);
+void batched_solver_set_panel(BatchedSolver *h, const char *name, const double *in, long len);
 
 }  // namespace hprlp

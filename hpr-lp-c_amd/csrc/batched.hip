@@ -1411,6 +1411,18 @@ void zero_async(BatchWS &w, DBuf<T> &b) {
     HIP_CHECK(hipMemsetAsync(b.p, 0, (b.n ? b.n : 1) * sizeof(T), w.stream));
 }
 
+// The detection's panels, allocated at their first use in this geometry, and zeroed: no stored iterate, no rays.  (A detecting
+// solve's ws_fill, and the ray step outside the loop where it starts over: batched_solver_ray_step.)
+void ws_ray_panels(BatchWS &w) {
+    const size_t Bp = static_cast<size_t>(w.Bp);
+    if (!w.prevX.p) {
+        for (DBuf<double> *p : {&w.prevX, &w.DS}) p->alloc(w.n * Bp);
+        for (DBuf<double> *p : {&w.prevY, &w.YS}) p->alloc(w.m * Bp);
+        ++w.panel_allocs;
+    }
+    for (DBuf<double> *p : {&w.prevX, &w.DS, &w.prevY, &w.YS}) zero_async(w, *p);
+}
+
 // One batch into the resident buffers, all of it on the stream.  The pinned block holds, in this order: sigma, b_scale, c_scale
 // (Bp doubles each), active (Bp ints in the room of Bp doubles), then the column-major regions of `in` (BatchedSolver::solve
 // wrote all of them there).  carry: X / Y from the panels of the batch before (kb_carry_start, before anything is zeroed;
@@ -1436,14 +1448,7 @@ void ws_fill(BatchWS &w, const BatchData &d, size_t stage_count, const PanelIn &
     if (!has_x && !carry) zero_async(w, w.X);
     if (!has_y && !carry) zero_async(w, w.Y);
     for (DBuf<int> *p : {&w.kx, &w.ky, &w.rflag}) zero_async(w, *p);
-    if (detect) {
-        if (!w.prevX.p) {
-            for (DBuf<double> *p : {&w.prevX, &w.DS}) p->alloc(n * Bp);
-            for (DBuf<double> *p : {&w.prevY, &w.YS}) p->alloc(m * Bp);
-            ++w.panel_allocs;
-        }
-        for (DBuf<double> *p : {&w.prevX, &w.DS, &w.prevY, &w.YS}) zero_async(w, *p);
-    }
+    if (detect) ws_ray_panels(w);
     const int longest = std::max(n, m);
     hipLaunchKernelGGL(kb_panel_in, dim3((longest + kPanelTile - 1) / kPanelTile, (w.Bp + kPanelTile - 1) / kPanelTile, nvec), dim3(256), 0,
                        w.stream, in, w.B, w.geo);
@@ -1823,6 +1828,9 @@ struct BatchedSolver {
     hipEvent_t inputs_ready = nullptr;    // device entry: recorded on the caller's stream, waited for by w.stream
     std::vector<double> last_scalars;     // DS_COUNT x B of the last successful call
     long staged[2] = {0, 0};              // ... and its staging bytes host -> device, device -> host
+    // the ray test outside the loop (batched_solver_ray_step): a step since the last solve has stored an iterate; X_bar / Y_bar
+    // have been written by name since the last solve (they are no longer that solve's solution: carry is refused)
+    bool ray_have_prev = false, bars_written = false;
 
     BatchedSolver(const LP_info_cpu *model, const HPRLP_parameters *p);
     ~BatchedSolver() {
@@ -1884,6 +1892,9 @@ void BatchedSolver::solve(int B, const double *C_in, const double *AL_in, const 
         if (B != prev_B)
             throw std::runtime_error("batched solver: carry needs the previous batch_size (" + std::to_string(prev_B) + "), got " +
                                      std::to_string(B));
+        if (bars_written)
+            throw std::runtime_error("batched solver: carry refused, X_bar / Y_bar were written by name since the previous solve "
+                                     "(they are no longer its solution)");
     }
     const int Bp = padded_batch(B), Bc = choose_chunk(m, n, Bp);  // (HPRLP_BATCH_CHUNK: per call)
     const char *grid_hook = env_get("HPRLP_BATCH_GRID");
@@ -2037,6 +2048,8 @@ void BatchedSolver::solve(int B, const double *C_in, const double *AL_in, const 
         have_prev = true;
         prev_B = B;
         prev_on_device = dev != nullptr;
+        ray_have_prev = false;
+        bars_written = false;
         ++solves;
         if (dev) ++device_solves;
     } catch (...) {
@@ -2115,6 +2128,125 @@ void batched_solver_info(const BatchedSolver *h, long out[8]) {
 void batched_solver_seconds(const BatchedSolver *h, double out[6]) {
     if (!h || !out) throw std::runtime_error("batched solver: null handle / output");
     std::copy(h->seconds, h->seconds + 6, out);
+}
+
+
+// ---- the ray test outside the loop (DESIGN.md "Batched detection": the ray test by value) -----------------------------------------
+// One ray test on the panels the last successful solve left: its B, its geometry, its scales on the device.  The launches, the
+// fetch and the slot reads are the loop's own (ray_step, fetch, sc); nothing of the finished solve's host BatchData is read.
+// active (B ints): the members that take part, as the loop's active mask; padding members never do.  restart: the stored iterate
+// and the rays are forgotten (zeroed, as a detecting solve starts) and the step only stores X_bar / Y_bar of the active members --
+// a member that sat out a restart step has a zero stored iterate at its first test.  out: 9 x B raw slots, slot-major, in the
+// order of BRaySlot (DY, CD, VY, WD, YN, DN, DZ, VZ, WQ); tested[k]: 1 where member k was tested.  Returns 1 after a test, 0
+// where the iterate was only stored.  The next solve on the handle fills every buffer a step touches (active, slots, partials, the
+// detection's panels) as on a handle that never stepped.
+int batched_solver_ray_step(BatchedSolver *h, const int *active, bool restart, double *out, int *tested) {
+    if (!h || !active || !out || !tested) throw std::runtime_error("batched ray step: null handle / active / output");
+    if (!h->have_prev || !h->have_geo) throw std::runtime_error("batched ray step: needs a successful solve on this handle");
+    if (!restart && !h->ray_have_prev)
+        throw std::runtime_error("batched ray step: no stored iterate, the first step after a solve needs restart != 0");
+    BatchWS &w = h->w;
+    const int B = w.B;
+    std::vector<int> act(static_cast<size_t>(w.Bp), 0);
+    for (int k = 0; k < B; ++k) act[k] = active[k] != 0 ? 1 : 0;
+    if (restart) ws_ray_panels(w);
+    w.active.upload(act.data(), act.size());
+    w.nslot = B_NSLOT_DETECT;
+    const bool test = !restart;
+    ray_step(w, test);
+    HIP_CHECK(hipGetLastError());
+    fetch(w);
+    h->ray_have_prev = true;
+    for (int k = 0; k < B; ++k) {
+        tested[k] = test ? act[k] : 0;
+        for (int s = 0; s < B_NSLOT_DETECT - B_NSLOT; ++s) out[static_cast<size_t>(s) * B + k] = tested[k] ? sc(w, B_RAY_DY + s, k) : 0.0;
+    }
+    return test ? 1 : 0;
+}
+
+namespace {
+// a panel by name: its buffer, its rows, and whether a caller may write it
+struct NamedPanel {
+    const char *name;
+    DBuf<double> BatchWS::*buf;
+    bool x_side;  // n rows (else m)
+    bool ray;     // one of the detection's panels: unknown until a detecting solve or a ray step has allocated them
+    bool writable;
+};
+constexpr NamedPanel kNamedPanels[] = {
+    {"C", &BatchWS::C, true, false, false},          {"AL", &BatchWS::AL, false, false, false},
+    {"AU", &BatchWS::AU, false, false, false},       {"L", &BatchWS::L, true, false, false},
+    {"U", &BatchWS::U, true, false, false},          {"X_bar", &BatchWS::Xb, true, false, true},
+    {"Y_bar", &BatchWS::Yb, false, false, true},     {"ray_d", &BatchWS::DS, true, true, false},
+    {"ray_y", &BatchWS::YS, false, true, false},     {"ray_prev_x", &BatchWS::prevX, true, true, false},
+    {"ray_prev_y", &BatchWS::prevY, false, true, false}, {"ray_z", &BatchWS::Zray, true, true, false},
+};
+const NamedPanel &named_panel(const BatchWS &w, const std::string &name, const char *who) {
+    for (const NamedPanel &p : kNamedPanels)
+        if (name == p.name) {
+            if (p.ray && !w.prevX.p) throw std::runtime_error(std::string(who) + ": '" + name + "' does not exist before a detecting solve or a ray step");
+            return p;
+        }
+    throw std::runtime_error(std::string(who) + ": unknown panel '" + name + "'");
+}
+}  // namespace
+
+// The first B members of a panel of the last successful solve by name, column-major rows x B (download_panel): C, AL, AU, L, U,
+// X_bar, Y_bar, ray_d, ray_y, ray_prev_x, ray_prev_y; ray_z runs launch_ray_product and returns its product A^T ray_y; row_norm /
+// col_norm: the shared matrix' norms (m / n values).  "raw:" in front of a panel's name: the whole padded panel in the device's
+// layout, rows x Bp (panel_index).  out null: only the count.  Returns the count of values; throws where `len` is another.
+long batched_solver_get_panel(BatchedSolver *h, const char *name, double *out, long len) {
+    if (!h || !name) throw std::runtime_error("batched get_panel: null handle / name");
+    if (!h->have_prev || !h->have_geo) throw std::runtime_error("batched get_panel: needs a successful solve on this handle");
+    BatchWS &w = h->w;
+    std::string nm(name);
+    const bool norm = nm == "row_norm" || nm == "col_norm";
+    const bool raw = nm.rfind("raw:", 0) == 0;
+    if (raw) nm = nm.substr(4);
+    const NamedPanel *p = norm ? nullptr : &named_panel(w, nm, "batched get_panel");
+    const int rows = norm ? (nm == "row_norm" ? w.m : w.n) : (p->x_side ? w.n : w.m);
+    const long count = norm ? rows : static_cast<long>(rows) * (raw ? w.Bp : w.B);
+    if (!out) return count;
+    if (len != count) throw std::runtime_error("batched get_panel: '" + nm + "' has " + std::to_string(count) + " values, room for " + std::to_string(len));
+    std::vector<double> v;
+    if (norm) {
+        v = nm == "row_norm" ? w.rn : w.cn;
+    } else {
+        if (nm == "ray_z") {
+            w.Zray.alloc(static_cast<size_t>(w.n) * w.Bp);
+            launch_ray_product(w);
+            HIP_CHECK(hipGetLastError());
+        }
+        HIP_CHECK(hipStreamSynchronize(w.stream));
+        const DBuf<double> &buf = w.*(p->buf);
+        if (raw) {
+            v.resize(static_cast<size_t>(count));
+            buf.download(v.data(), v.size());
+        } else {
+            v = download_panel(w, buf, rows);
+        }
+    }
+    std::copy(v.begin(), v.end(), out);
+    return count;
+}
+
+// X_bar / Y_bar of the first B members from column-major rows x B (to_panel; the padding members' columns become 0.0, which is
+// what they hold).  No other panel can be written.  carry is refused until the next successful solve.
+void batched_solver_set_panel(BatchedSolver *h, const char *name, const double *in, long len) {
+    if (!h || !name || !in) throw std::runtime_error("batched set_panel: null handle / name / values");
+    if (!h->have_prev || !h->have_geo) throw std::runtime_error("batched set_panel: needs a successful solve on this handle");
+    BatchWS &w = h->w;
+    const NamedPanel &p = named_panel(w, name, "batched set_panel");
+    if (!p.writable) throw std::runtime_error(std::string("batched set_panel: '") + name + "' cannot be written (X_bar and Y_bar can)");
+    const int rows = p.x_side ? w.n : w.m;
+    const long count = static_cast<long>(rows) * w.B;
+    if (len != count) throw std::runtime_error(std::string("batched set_panel: '") + name + "' takes " + std::to_string(count) + " values, got " + std::to_string(len));
+    const std::vector<double> cm(in, in + count);
+    std::vector<double> panel;
+    to_panel(cm, rows, w.B, w.geo, 0.0, panel);
+    HIP_CHECK(hipStreamSynchronize(w.stream));
+    (w.*(p.buf)).upload(panel.data(), panel.size());
+    h->bars_written = true;
 }
 
 // One batch and no more: a resident solver that lives for one call.  Its set-up, scaling and power iteration count as this call's set-up.

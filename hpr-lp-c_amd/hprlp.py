@@ -207,7 +207,11 @@ def lib():
     L.hprlp_batched_solver_set_norms.argtypes = [C.c_void_p, C.c_int]
     L.hprlp_batched_solver_scalars.argtypes = [C.c_void_p, c_dbl_p]
     L.hprlp_batched_solver_transfer.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
-    L.hprlp_batched_prepare_host_rule.argtypes = [C.c_int] * 3 + [c_dbl_p] * 9 + [C.c_int, C.c_int, C.POINTER(CBatchedPrepared)]
+    L.hprlp_batched_solver_ray_step.argtypes = [C.c_void_p, c_int_p, C.c_int, c_dbl_p, c_int_p]
+    L.hprlp_batched_solver_get_panel.restype = C.c_long
+    L.hprlp_batched_solver_get_panel.argtypes = [C.c_void_p, C.c_char_p, c_dbl_p, C.c_long]
+    L.hprlp_batched_solver_set_panel.argtypes = [C.c_void_p, C.c_char_p, c_dbl_p, C.c_long]
+    L.hprlp_batched_prepare_host_rule.argtypes =[C.c_int] * 3 + [c_dbl_p] * 9 + [C.c_int, C.c_int, C.POINTER(CBatchedPrepared)]
     L.hprlp_solver_set_start.argtypes = [C.c_void_p, c_dbl_p, c_dbl_p]
     L.hprlp_solver_set_data.argtypes = [C.c_void_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]
     L.hprlp_solver_resolve.argtypes = [C.c_void_p, C.c_double, c_dbl_p, c_dbl_p, C.POINTER(CResults), C.POINTER(CTraceRow),
@@ -796,6 +800,65 @@ class BatchedSolver:
         if B < 0:
             raise RuntimeError(last_error())
         return dict(zip(BATCH_SCALARS, out.reshape(-1)[:len(BATCH_SCALARS) * B].reshape(len(BATCH_SCALARS), B).copy()))
+
+    RAY_SLOTS = ("DY", "CD", "VY", "WD", "YN", "DN", "DZ", "VZ", "WQ")
+
+    def ray_step(self, active=None, restart=False):
+        """One ray test of the detection on the X_bar / Y_bar panels of the last successful solve (hprlp_batched_solver_ray_step),
+        for the members with active[k] != 0 (None: all).  restart=True: forgets the stored iterate and only stores the active
+        members' X_bar / Y_bar: returns None.  Otherwise a list of B entries: None for a member that was not tested, else the nine
+        device scalars by name and the six sums the verdicts are taken from (Solver.ray_step's dict)."""
+        if not self._h:
+            raise RuntimeError("BatchedSolver: closed")
+        B = self._last_B
+        act = np.ones(B, dtype=np.intc) if active is None else np.ascontiguousarray(active, dtype=np.intc)
+        if act.shape != (B,):
+            raise ValueError(f"ray_step: active must have {B} entries, got shape {act.shape}")
+        out, tested = np.zeros((9, max(B, 1))), np.zeros(max(B, 1), dtype=np.intc)
+        rc = lib().hprlp_batched_solver_ray_step(self._h, act.ctypes.data_as(c_int_p), int(bool(restart)), _dptr(out),
+                                                 tested.ctypes.data_as(c_int_p))
+        if rc < 0:
+            raise RuntimeError("hprlp_batched_solver_ray_step failed: " + last_error())
+        if rc == 0:
+            return None
+        res = []
+        for k in range(B):
+            if not tested[k]:
+                res.append(None)
+                continue
+            s = dict(zip(self.RAY_SLOTS, (float(v) for v in out[:, k])))
+            s.update(D=s["DY"] + s["DZ"], V=max(s["VY"], s["VZ"]), cd=s["CD"], W=max(s["WD"], s["WQ"]), yn=s["YN"], dn=s["DN"])
+            res.append(s)
+        return res
+
+    def get_panel(self, name):
+        """A panel of the last successful solve by name (hprlp_batched_solver_get_panel), scaled units: (rows, B) for C, AL, AU, L,
+        U, X_bar, Y_bar, ray_d, ray_y, ray_prev_x, ray_prev_y, ray_z; a vector for row_norm / col_norm; "raw:" + name: the padded
+        panel as the device holds it, flat (element (i, k) at ((k // Bc) * rows + i) * Bc + k % Bc, see info())."""
+        if not self._h:
+            raise RuntimeError("BatchedSolver: closed")
+        nm = name.encode()
+        count = lib().hprlp_batched_solver_get_panel(self._h, nm, None, 0)
+        if count < 0:
+            raise RuntimeError("hprlp_batched_solver_get_panel failed: " + last_error())
+        out = np.zeros(max(count, 1))
+        if lib().hprlp_batched_solver_get_panel(self._h, nm, _dptr(out), count) != count:
+            raise RuntimeError("hprlp_batched_solver_get_panel failed: " + last_error())
+        out = out[:count]
+        if name in ("row_norm", "col_norm") or name.startswith("raw:"):
+            return out
+        return out.reshape(self._last_B, -1).T
+
+    def set_panel(self, name, values):
+        """X_bar or Y_bar of the last successful solve from a (rows, B) array in scaled units (hprlp_batched_solver_set_panel);
+        carry=True is refused afterwards until the next successful solve."""
+        if not self._h:
+            raise RuntimeError("BatchedSolver: closed")
+        a = np.asfortranarray(values, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != self._last_B:
+            raise ValueError(f"set_panel: values must have shape (rows, {self._last_B}), got {a.shape}")
+        if lib().hprlp_batched_solver_set_panel(self._h, name.encode(), a.ctypes.data_as(c_dbl_p), a.size) != 0:
+            raise RuntimeError("hprlp_batched_solver_set_panel failed: " + last_error())
 
     def transfer(self):
         """The last successful call's staging traffic in bytes, host to device and back (the batch's way in and the solution's way

@@ -225,6 +225,24 @@ int hprlp_batched_solver_scalars(hprlp_batched_solver *h, double *out);
  *        solution's way out; the loop's scalar fetches are not counted), 1 if that solve was a device-entry call,
  *        device-entry solves so far} */
 int hprlp_batched_solver_transfer(hprlp_batched_solver *h, long out[4]);
+/* One ray test of the detection OUTSIDE the loop (the step-level entry the value tests use; DESIGN.md "Batched detection"), on
+ * the panels the last successful solve left on the device: its B members, its panel geometry, its scales.  active (B ints):
+ * the members that take part, as the loop's active mask.  restart != 0: the stored iterate and the rays are forgotten and the
+ * step only stores X_bar / Y_bar of the active members (returns 0); the first step after a solve needs it.  Otherwise (returns 1):
+ * rays = X_bar / Y_bar minus the stored iterate, the iterate is stored, and out receives the nine device scalars per member,
+ * slot-major (out[s * B + k]) in the order DY, CD, VY, WD, YN, DN, DZ, VZ, WQ; tested[k] = 1 where member k was active (0: its
+ * slots are not meaningful).  A later solve on the handle gives the bits of a handle that never stepped.
+ * -1 + hprlp_last_error(): no successful solve on the handle, or no stored iterate and restart == 0. */
+int hprlp_batched_solver_ray_step(hprlp_batched_solver *h, const int *active, int restart, double *out, int *tested);
+/* A panel of the last successful solve by name, the first B members column-major rows x B in SCALED units: C, L, U, X_bar, ray_d,
+ * ray_prev_x (n rows), AL, AU, Y_bar, ray_y, ray_prev_y (m rows) -- infinite sides and bounds read +-1e100 -- and ray_z
+ * (n rows: the product A^T ray_y of the certificates, computed by the call); row_norm (m values) / col_norm (n values).  "raw:"
+ * before a panel's name: the whole padded panel in the device's layout, rows x Bp.  out NULL: only the count.  Returns the count
+ * of values (len must equal it), or -1 + hprlp_last_error() (an unknown name; a ray_* name before a detecting solve or a step). */
+long hprlp_batched_solver_get_panel(hprlp_batched_solver *h, const char *name, double *out, long len);
+/* X_bar or Y_bar of the first B members from column-major rows x B (scaled units); no other name can be written.  carry is
+ * refused until the next successful solve.  0, or -1 + hprlp_last_error(). */
+int hprlp_batched_solver_set_panel(hprlp_batched_solver *h, const char *name, const double *in, long len);
 /* After hprlp_solver_init, before hprlp_solver_run: the start of the next run (caller's units; both NULL: the zero start,
  * evaluated as a start).  -1 + hprlp_last_error() for a sharded solver or a non-finite entry. */
 int hprlp_solver_set_start(hprlp_solver *s, const double *x0, const double *y0);

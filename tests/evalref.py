@@ -459,6 +459,83 @@ def check_rays(s, patterns, got, label=""):
     return inp, (ds, ys), want, r
 
 
+# ---- the batched ray test (batched.hip: kb_ray_form, kb_ray_col, kb_ray_row, kb_ray_product) ---------------------------------------
+# Its device formulas are term by term those of _ray_elements -- (ds / cn) bs, ((c cn) cs) d, ((lo rn) bs) y, -((s cn) cs),
+# ((l / cn) bs) z, (s rn) bs -- so evaluate_rays serves per member: that member's column of every read-back panel, the shared
+# norms, its b_scale / c_scale.  The one difference is the finiteness rule: a panel holds +-K_INF where the caller passed +-inf.
+K_INF = 1.0e100     # csrc/batch_prep.h: kInfReplacement
+BOUND_PANELS = ("AL", "AU", "L", "U")
+
+
+def panel_bounds_to_inf(panel, caller, name=""):
+    """A read-back bound panel with +-K_INF mapped to +-inf, after asserting that it holds exactly +K_INF (-K_INF) where, and only
+    where, the caller passed +inf (-inf)."""
+    panel, caller = np.asarray(panel, np.float64), np.asarray(caller, np.float64)
+    assert panel.shape == caller.shape, (name, panel.shape, caller.shape)
+    for sign in (1.0, -1.0):
+        rep, inf = panel == sign * K_INF, caller == sign * np.inf
+        bad = np.argwhere(rep != inf)
+        assert not len(bad), (name, "%+g" % (sign * K_INF), "first (line, member):", bad[0].tolist(), "of", len(bad),
+                              float(panel[tuple(bad[0])]), float(caller[tuple(bad[0])]))
+    assert np.isfinite(panel).all(), name
+    return np.where(panel == K_INF, np.inf, np.where(panel == -K_INF, -np.inf, panel))
+
+
+def batched_member_inputs(A, AT, panels, norms, scalars, k):
+    """(A, AT, data, scalars) of evaluate_rays for member k: panels = {C, AL, AU, L, U: (rows, B), bounds with +-inf};
+    norms = (row_norm, col_norm); scalars = {b_scale, c_scale: B}."""
+    data = dict(c=panels["C"][:, k], AL=panels["AL"][:, k], AU=panels["AU"][:, k], l=panels["L"][:, k], u=panels["U"][:, k],
+                row_norm=norms[0], col_norm=norms[1])
+    return A, AT, data, dict(b_scale=float(scalars["b_scale"][k]), c_scale=float(scalars["c_scale"][k]))
+
+
+def check_batched_rays(A, AT, panels, norms, scalars, caller, got, label=""):
+    """The nine slots and six combinations per member, `got` (BatchedSolver.ray_step(): a list of dicts, None = not tested), against
+    evaluate_rays on the solver's OWN read-back panels (scaled units): C, AL, AU, L, U, ray_d, ray_y, each (rows, B).  A, AT: the
+    scaled shared matrix; caller = {AL, AU, L, U} as the caller passed them (+-inf where infinite): the bound panels must hold
+    +-K_INF there and nowhere else.  Every number within TOL_FACTOR x its bound; one that is not finite fails.  Returns
+    (per member None or (inputs, ds, ys, reference, ratios), the largest ratio per name)."""
+    panels = dict(panels)
+    for name in BOUND_PANELS:
+        panels[name] = panel_bounds_to_inf(panels[name], caller[name], name)
+    out, worst = [], {}
+    for k, g in enumerate(got):
+        if g is None:
+            out.append(None)
+            continue
+        inp = batched_member_inputs(A, AT, panels, norms, scalars, k)
+        ds, ys = panels["ray_d"][:, k], panels["ray_y"][:, k]
+        want = evaluate_rays(*inp, ds, ys)
+        r = ratios(g, want, RAY_NAMES)
+        for name, v in r.items():
+            worst[name] = max(worst.get(name, 0.0), v)
+        assert all(np.isfinite(float(want[n][0])) for n in RAY_NAMES), (label, k, {n: want[n] for n in RAY_NAMES})
+        assert all(np.isfinite(g[n]) for n in RAY_NAMES), (label, k, {n: g[n] for n in RAY_NAMES})
+        assert all_within(r), (label, "member %d" % k, r, {n: (g[n], want[n]) for n in RAY_NAMES if not r[n] <= TOL_FACTOR})
+        out.append((inp, ds, ys, want, r))
+    print("batched rays", label, " ".join("%s %.3g" % kv for kv in worst.items()))
+    return out, worst
+
+
+def ray_product(AT, ys):
+    """(z, bound) per column of the certificates' product A^T ys in scaled units (kb_ray_product): rule (R), the row-sum term of
+    e_z: (len + 1) u sum|a_ij ys_i|."""
+    s, s_abs, s_len = _row_sums(AT, ys)
+    return s, (s_len + 1) * U * s_abs
+
+
+def dominated(want, got, inp, ds, ys, slot, line, label="", **drop):
+    """The reference shows `line` as the arg-max of `slot` with the runner-up at most half of it, and the evaluator without that
+    line (and, with drop_A / drop_AT, without one stored entry of it) is farther than the tolerance from the number `got[slot]`."""
+    k, top, second = top_two(want["elements"][slot])
+    assert k == line and top > 0 and second <= 0.5 * top, (label, slot, line, k, top, second)
+    bad = evaluate_rays(*inp, ds, ys, leave_out={slot: line})
+    assert ratio(got[slot], bad[slot]) > TOL_FACTOR, (label, slot, "left out", got[slot], bad[slot])
+    if drop:
+        bad = evaluate_rays(*inp, ds, ys, **drop)
+        assert ratio(got[slot], bad[slot]) > TOL_FACTOR, (label, slot, drop, got[slot], bad[slot])
+
+
 # ---- the ray test in the caller's units ------------------------------------------------------------------------------------------
 # The roundings a number of the model goes through in scale() with use_CR_scaling off (oracle/hpr_oracle.c: orc_scaling; the
 # device runs the same passes): 10 Ruiz passes and one Pock-Chambolle pass, then the b / c scaling.

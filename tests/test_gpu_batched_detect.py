@@ -4,9 +4,10 @@ every panel form, the limits' precedence, and no perturbation of the feasible me
 
 Every certificate's objective and violation are also held BY VALUE, from both sides, to D and V resp. c'd and W of the returned
 ray (tests/evalref.py: check_certificate_values, in the member's units; the solves run with use_CR_scaling off, whose device
-`exp` rounds by more than one u).  For the batched ray kernels (kb_ray_form, kb_ray_col, kb_ray_row) this is the value-level
-check there is; it covers the panel forms of test_mixed_batch_verdicts_and_certificates: B = 5 (one chunk of 8), B = 64, and
-B = 70 with chunks of 8 and of 32.  (A step-level entry to the batched ray test does not exist.)"""
+`exp` rounds by more than one u), on the panel forms of test_mixed_batch_verdicts_and_certificates: B = 5 (one chunk of 8),
+B = 64, and B = 70 with chunks of 8 and of 32.  The nine device scalars of the batched ray kernels (kb_ray_form, kb_ray_col,
+kb_ray_row) themselves are checked by value, step by step and in every panel geometry, by
+tests/test_gpu_batched_ray_values.py through hprlp_batched_solver_ray_step."""
 import functools
 import json
 import os
