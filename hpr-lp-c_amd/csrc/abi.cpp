@@ -1509,6 +1509,40 @@ extern "C" int hprlp_solver_resolve_many(hprlp_solver **h, int count, const hprl
     GUARD_END(-1)
 }
 
+// ---- group matrix values (DESIGN.md "Many small LPs", group matrix values) ----------------------------------------------------
+// counts of the calling thread's last hprlp_solver_set_matrix_values_many (hprlp_last_values_many_counts)
+static thread_local long g_values_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+static void keep_values_counts(const ValuesCounts &vc) {
+    const long v[8] = {vc.h2d, vc.d2h, vc.waits, vc.launches, vc.memsets, vc.served, vc.own, vc.maps};
+    for (int i = 0; i < 8; ++i) g_values_counts[i] = v[i];
+}
+
+extern "C" int hprlp_last_values_many_counts(long out[8]) {
+    if (!out) return -1;
+    for (int i = 0; i < 8; ++i) out[i] = g_values_counts[i];
+    return 0;
+}
+
+extern "C" int hprlp_solver_set_matrix_values_many(hprlp_solver **h, int count, const hprlp_member_values *data) {
+    GUARD_BEGIN
+    keep_values_counts(ValuesCounts());
+    // (list, count, data, then the members: the order of the refusals)
+    if (!h) throw std::runtime_error("hprlp_solver_set_matrix_values_many: null solver list");
+    if (count <= 0) throw std::runtime_error("hprlp_solver_set_matrix_values_many: count must be positive");
+    if (!data) throw std::runtime_error("hprlp_solver_set_matrix_values_many: null data");
+    std::vector<Solver *> s = group_members(h, count, "hprlp_solver_set_matrix_values_many");
+    std::vector<MemberValues> d(static_cast<size_t>(count));
+    for (int k = 0; k < count; ++k) {
+        d[k].val = data[k].val, d[k].nnz = data[k].nnz, d[k].c = data[k].c, d[k].obj_constant = data[k].obj_constant;
+        d[k].AL = data[k].AL, d[k].AU = data[k].AU, d[k].l = data[k].l, d[k].u = data[k].u;
+    }
+    ValuesCounts vc;
+    set_matrix_values_many(s.data(), count, d.data(), &vc);
+    keep_values_counts(vc);
+    return 0;
+    GUARD_END(-1)
+}
+
 // phases of the calling thread's last hprlp_solve_many (hprlp_last_solve_many_phases)
 static thread_local double g_many_phases[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 

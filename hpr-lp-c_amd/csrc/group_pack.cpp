@@ -26,7 +26,9 @@ GroupPackLayout group_pack_layout(const PackMember *members, int count) {
         const PackMember &mb = members[k];
         PackSlot &s = L.slot[k];
         const size_t m = static_cast<size_t>(std::max(mb.m, 0)), n = static_cast<size_t>(std::max(mb.n, 0));
-        if (mb.bounds) {  // the order of Solver::set_data's staging: [AL | AU | l | u | c]
+        // the order of Solver::set_matrix_values' staging, [val | AL | AU | l | u | c]; without values Solver::set_data's
+        if (mb.nnz > 0) s.val = take(L.data_doubles, static_cast<size_t>(mb.nnz));
+        if (mb.bounds) {
             s.AL = take(L.data_doubles, m);
             s.AU = take(L.data_doubles, m);
             s.l = take(L.data_doubles, n);
@@ -55,6 +57,10 @@ void group_pack_data(const GroupPackLayout &L, int k, const PackMember &mb, cons
     put(block, s.c, c, n);
 }
 
+void group_pack_values(const GroupPackLayout &L, int k, const PackMember &mb, const double *val, double *block) {
+    put(block, L.slot[static_cast<size_t>(k)].val, val, static_cast<size_t>(std::max<long>(mb.nnz, 0)));
+}
+
 void group_pack_start(const GroupPackLayout &L, int k, const PackMember &mb, const double *x0, const double *y0, double *block) {
     const PackSlot &s = L.slot[static_cast<size_t>(k)];
     put(block, s.x0, x0, static_cast<size_t>(std::max(mb.n, 0)));
@@ -73,7 +79,9 @@ void group_unpack_result(const GroupPackLayout &L, int k, const PackMember &mb, 
 
 // Checks, numbered: 1 absent vectors take no room and have no offset; 2 every range lies inside its block; 3 the ranges of a block
 // are disjoint; 4 offsets are aligned; 5 a pack / unpack round trip of the data and start blocks returns what went in and leaves
-// the padding alone; 6 the result round trip; 7 an empty group and members of size zero.
+// the padding alone; 6 the result round trip; 7 an empty group and members of size zero; 8 matrix values (set_matrix_values_many):
+// a member's values lie in front of its vectors in the order [val | AL | AU | l | u | c], aligned, disjoint from everything else
+// and inside the block, odd, even and single counts, a member with values and no vectors; the round trip leaves the padding alone.
 extern "C" int hprlp_group_pack_selftest(void) {
     using namespace hprlp;
     // odd sizes, sizes below and at the alignment, every combination of given / absent
@@ -186,5 +194,59 @@ extern "C" int hprlp_group_pack_selftest(void) {
     none.m = 5, none.n = 9;
     const GroupPackLayout N = group_pack_layout(&none, 1);
     if (N.data_doubles || N.start_doubles || N.result_doubles || N.slot[0].c != kPackAbsent || N.slot[0].x != kPackAbsent) return 7;
+    if (N.slot[0].val != kPackAbsent) return 7;
+    for (const PackSlot &s : L.slot)
+        if (s.val != kPackAbsent) return 8;  // (nobody above gave values)
+    // matrix values: nnz 1, odd, even, at and around the alignment; with all vectors, with none (a member on its own way)
+    {
+        const long counts[] = {1, 7, 31, 32, 33, 64, 2501, 2500, 0};
+        std::vector<PackMember> vm;
+        for (size_t i = 0; i < sizeof(counts) / sizeof(counts[0]); ++i) {
+            PackMember p;
+            p.m = 3 + static_cast<int>(i) * 5, p.n = 4 + static_cast<int>(i) * 7, p.nnz = counts[i];
+            p.c = p.bounds = (i % 3) != 2;
+            vm.push_back(p);
+        }
+        const int VK = static_cast<int>(vm.size());
+        const GroupPackLayout V = group_pack_layout(vm.data(), VK);
+        if (V.start_doubles || V.result_doubles) return 8;
+        std::vector<double> vblock(V.data_doubles + 1, pad);
+        std::vector<Range> vr;
+        size_t want = 0, written = 0;
+        for (int k = 0; k < VK; ++k) {
+            const PackMember &p = vm[k];
+            const PackSlot &s = V.slot[k];
+            const size_t m = static_cast<size_t>(p.m), n = static_cast<size_t>(p.n), nz = static_cast<size_t>(p.nnz);
+            if ((nz > 0) != (s.val != kPackAbsent)) return 8;
+            if (p.bounds != (s.AL != kPackAbsent) || p.c != (s.c != kPackAbsent)) return 8;
+            const size_t at[6] = {s.val, s.AL, s.AU, s.l, s.u, s.c};
+            const size_t len[6] = {nz, m, m, n, n, n};
+            size_t prev = kPackAbsent;
+            std::vector<std::vector<double>> srcv(6);
+            for (int v = 0; v < 6; ++v) {
+                if (at[v] == kPackAbsent) continue;
+                if (at[v] % kPackAlign != 0) return 8;
+                if (at[v] != want) return 8;  // (the order of the staging, nothing in between but the padding)
+                if (prev != kPackAbsent && at[v] <= prev) return 8;
+                prev = at[v];
+                want += padded(len[v]);
+                vr.push_back({at[v], len[v]});
+                srcv[v].resize(len[v]);
+                for (size_t i = 0; i < len[v]; ++i) srcv[v][i] = value(k, v, i);
+                written += len[v];
+            }
+            group_pack_values(V, k, p, nz > 0 ? srcv[0].data() : nullptr, vblock.data());
+            group_pack_data(V, k, p, p.bounds ? srcv[1].data() : nullptr, p.bounds ? srcv[2].data() : nullptr, p.bounds ? srcv[3].data() : nullptr,
+                            p.bounds ? srcv[4].data() : nullptr, p.c ? srcv[5].data() : nullptr, vblock.data());
+            for (int v = 0; v < 6; ++v)
+                if (at[v] != kPackAbsent && std::memcmp(vblock.data() + at[v], srcv[v].data(), sizeof(double) * len[v]) != 0) return 8;
+        }
+        if (want != V.data_doubles) return 8;
+        for (const Range &e : vr)
+            if (e.at + e.len > V.data_doubles) return 8;
+        for (size_t i = 1; i < vr.size(); ++i)
+            if (vr[i - 1].at + vr[i - 1].len > vr[i].at) return 8;
+        if (static_cast<size_t>(std::count(vblock.begin(), vblock.end(), pad)) != vblock.size() - written) return 8;
+    }
     return 0;
 }

@@ -400,6 +400,7 @@ bool group_form_fits(const CsrDev &M);  // every fused launch on M is one k_spmv
 // scalars come by its own copy -- a group of one issues what the member issues alone.  scale_many records without it: every kind
 // present gets its table.  One run's tables are in flight at a time: the caller waits for the stream between two runs of one
 // object (the staging block is rewritten only after the copy out of it has completed, as for SmallTaskBuf).
+struct VectorsInArgs;  // values.h
 class GroupLaunches {
   public:
     explicit GroupLaunches(bool own_launches = true);
@@ -441,6 +442,11 @@ class GroupLaunches {
     void row_norm(const CsrDev &M, double *result, int norm);  // 99 or 1
     void scale_matrix(const CsrDev &M, const double *rowvec, const double *colvec_full, bool row_first, bool divide, double *next_max_norm);
     void cr_log_update(const CsrDev &M, const double *other_full, double *result);
+    // New matrix values (DESIGN.md "Many small LPs", group matrix values; values.h has the single launches): the check of one
+    // member's staged values into its own flag word, the scatter through the value maps, the gather of the five vectors.
+    void values_check(const double *v, long n, unsigned long long *first_bad);
+    void values_in(long nnz, const double *stage, const int *mapA, const int *mapAT, double *A_val, double *AT_val);
+    void vectors_in(const VectorsInArgs &a);
     long tables_sent() const;  // host-to-device copies of the tables so far (one per run() that had a table to send)
     int recorded_launches() const;  // what run() would issue for the records held now
     // What is recorded from here on runs after everything recorded so far, finalize included (one run, one copy of the tables

@@ -14,6 +14,7 @@
 // :91-157 (scaling), src/scaling.cu:5-38, src/power_iteration.cu:60-100.
 #include "kernels.h"
 #include "group_table.h"
+#include "values_body.h"
 
 #include <algorithm>
 #include <array>
@@ -3141,6 +3142,38 @@ struct UnscaleTask {
     int own_grid() const { return grid; }
     void own(hipStream_t s) const { launch_unscale(n, m, x_bar, y_bar, z_bar, col_norm, row_norm, b_scale, c_scale, xo, yo, zo, s); }
 };
+// New matrix values for a group (DESIGN.md "Many small LPs", group matrix values; many.cpp: set_matrix_values_many): the bodies of
+// values.hip's three kernels (values_body.h) on the member's own grid.  The task's pointers come from memory, so the compiler
+// takes them as generic; the resource remarks show no scratch and no spill for the three instances (DESIGN.md has the rows), so
+// they are not retyped as SmallArgsGlobal's are.
+struct ValuesCheckTask {  // k_values_check on one member's staged values; first_bad: the member's own flag word
+    static constexpr GridRule rule = kGridMapped;
+    const double *v;
+    long n;
+    unsigned long long *first_bad;
+    int grid;  // of the member's own launch (grid_stride_blocks(n))
+    __device__ void run(int lb) const { values_check_body(v, n, first_bad, static_cast<unsigned>(lb), static_cast<unsigned>(grid)); }
+    int own_grid() const { return grid; }
+    void own(hipStream_t s) const { launch_values_check(v, n, first_bad, s); }
+};
+struct ValuesInTask {  // k_values_in
+    static constexpr GridRule rule = kGridMapped;
+    long nnz;
+    const double *stage;
+    const int *mapA, *mapAT;
+    double *A_val, *AT_val;
+    int grid;  // of the member's own launch (grid_stride_blocks((nnz + 1) / 2))
+    __device__ void run(int lb) const { values_in_body(nnz, stage, mapA, mapAT, A_val, AT_val, static_cast<unsigned>(lb), static_cast<unsigned>(grid)); }
+    int own_grid() const { return grid; }
+    void own(hipStream_t s) const { launch_values_in(nnz, stage, mapA, mapAT, A_val, AT_val, s); }
+};
+struct VectorsInTask {  // k_vectors_in
+    static constexpr GridRule rule = kGridMapped;
+    VectorsInArgs a;
+    __device__ void run(int lb) const { vectors_in_body(a, static_cast<unsigned>(lb)); }
+    int own_grid() const { return elem_grid(a.m > a.n ? a.m : a.n); }
+    void own(hipStream_t s) const { launch_vectors_in(a, s); }
+};
 // The scaling kernels (DESIGN.md "Many small LPs", group scaling).  scale_many records them with a table for every kind, so they
 // name no launch of the member's own.
 template <bool BOUNDS>
@@ -3263,7 +3296,14 @@ struct KindList {
 // them together in one stage only, the end of a scaling (Solver::scale_finish): there the reductions read AL, AU and c and write
 // part_v, the finalize items read part_v and write the sums block and scal, and the codes kernels read l, u, AL, AU and write
 // lu_code and row_code -- nobody writes what another of them reads or writes, apart from part_v, whose order is kept.
-using GroupKinds = KindList<RowNormTask<false>, RowNormTask<true>, GroupTask<CrEpi>, VecTask, CodesTask<false>, CodesTask<true>, RestartCopyTask, SetCtrlTask,
+//   new matrix values:  the check of the staged values (a run of its own: the host reads the flags before anything is written),
+//             the scatter of the values, the gather of the vectors, zeroing (the elementwise kind).
+// The three kinds of that line stand in front of everything.  set_matrix_values_many records the scatter, the gather and the
+// zeroing fills of Solver::reset_iterates in ONE stage: the scatter reads the staging block and the maps and writes A_val and
+// AT_val, the gather reads the staging block and writes AL, AU, l, u and c, the fills write the iterates, the work vectors, the
+// scalars and ctrl -- three disjoint sets of arrays, none of which another of the three reads, so their order is no statement
+// either; scaling, which reads all of them, begins a stage later.
+using GroupKinds = KindList<ValuesCheckTask, ValuesInTask, VectorsInTask, RowNormTask<false>, RowNormTask<true>, GroupTask<CrEpi>, VecTask, CodesTask<false>, CodesTask<true>, RestartCopyTask, SetCtrlTask,
                             StartInTask, GroupTask<StartColEpi>, GroupTask<StartRowEpi>, GroupTask<XEpi<true>>, GroupTask<YEpi<true>>,
                             GroupTask<RdEpi>, GroupTask<RpEpi<false>>, GroupTask<RpEpi<true>>, GroupTask<GapEpi>, LuTask, MovementTask, DataInTask,
                             DataBcTask, UnscaleTask, ScaleMat<0>, ScaleMat<1>, ScaleMat<2>, ScaleMat<3>, ScaleMat<4>, ScaleMat<5>, ScaleMat<6>,
@@ -3421,6 +3461,15 @@ void GroupLaunches::scale_matrix(const CsrDev &M, const double *rowvec, const do
 }
 void GroupLaunches::cr_log_update(const CsrDev &M, const double *other_full, double *result) {
     impl->rec<GroupTask<CrEpi>>().push_back({stream_part(M), CrEpi{{other_full}, M.rowptr, result, nullptr, 0}});
+}
+void GroupLaunches::values_check(const double *v, long n, unsigned long long *first_bad) {
+    if (n > 0) impl->rec<ValuesCheckTask>().push_back({v, n, first_bad, static_cast<int>(grid_stride_blocks(n))});
+}
+void GroupLaunches::values_in(long nnz, const double *stage, const int *mapA, const int *mapAT, double *A_val, double *AT_val) {
+    if (nnz > 0) impl->rec<ValuesInTask>().push_back({nnz, stage, mapA, mapAT, A_val, AT_val, static_cast<int>(grid_stride_blocks((nnz + 1) / 2))});
+}
+void GroupLaunches::vectors_in(const VectorsInArgs &a) {
+    if (a.m > 0 || a.n > 0) impl->rec<VectorsInTask>().push_back({a});
 }
 long GroupLaunches::tables_sent() const { return impl->tables_sent; }
 int GroupLaunches::recorded_launches() const { return impl->plan.recorded_launches(); }

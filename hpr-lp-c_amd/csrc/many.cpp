@@ -8,7 +8,8 @@
 // members.  The host side -- stopping test, restart rule, sigma update, detection -- is the member's own code (the pieces of
 // Solver::solve_loop), so a member's iterates and results are the bits it gets alone.  A member that cannot join the group launches
 // (Solver::joins_group) issues its own launches inside the same lock-step; so does every member for its iteration-0 evaluation
-// (resolve_many apart: the group re-solve at the end of this file) and its ray tests.
+// (resolve_many apart: the group re-solve further down) and its ray tests.  New matrix values for the whole group
+// (set_matrix_values_many) are at the end of this file; they share scale_many's walk of Solver::scale() (scale_walk).
 //
 // Ordering is by stream: for the duration of a call every member works on ONE stream (the first member's), after its own stream
 // has been waited for once; the members' streams come back at exit, after one wait for the group's.
@@ -18,6 +19,7 @@
 
 #include "many.h"
 #include "group_pack.h"
+#include "values.h"
 
 namespace hprlp {
 
@@ -68,6 +70,95 @@ void run_fetch_wait(GroupLaunches &gl, hipStream_t group, GroupCounts &gc) {
     gl.deliver();
 }
 
+// Solver::scale() walked for the members who[0 ..) at once (scale_many, set_matrix_values_many).  gl records with a table for every
+// kind (own_launches = false) and may hold closed stages already: they run in front of the scaling, in the first copy of the
+// tables.  Launches, waits and served members are added to sc; st is the group's stream.
+void scale_walk(Solver **s, const std::vector<int> &who, GroupLaunches &gl, hipStream_t st, SetupCounts &sc) {
+    const int nj = static_cast<int>(who.size());
+    // The pieces are scale()'s own (solver.cpp), in its order, recorded into one GroupLaunches with a table for every kind
+    // (inside a stage a kind may hold one member's task).  The group's own:
+    // the stages, one block for the second pairs of gathered vectors, and the sums block -- two slots per member, where the
+    // pieces finalise |b|^2 and |c|^2 and from where one copy brings them to the host, three times.
+    const auto t0 = time_now();
+    std::vector<Solver::ScaleWalk> w(static_cast<size_t>(nj));
+    auto member = [&](int j) -> Solver & { return *s[who[j]]; };
+    // the second pair of gathered vectors of every member with Ruiz passes, pieces of one block
+    auto aligned = [](size_t doubles) { return (doubles + 31) / 32 * 32; };
+    size_t pair_doubles = 0;
+    for (int j = 0; j < nj; ++j)
+        if (member(j).prm.use_Ruiz_scaling) pair_doubles += aligned(static_cast<size_t>(member(j).m_pad)) + aligned(static_cast<size_t>(member(j).n_pad));
+    DBuf<double> pairs(std::max<size_t>(pair_doubles, 1)), sums(static_cast<size_t>(2) * nj);
+    HBuf<double> sums_h;
+    sums_h.alloc(static_cast<size_t>(2) * nj);
+    auto run_fetch_wait = [&]() {
+        sc.scale_launches += gl.run(st);
+        HIP_CHECK(hipMemcpyAsync(sums_h.p, sums.p, sizeof(double) * 2 * nj, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        ++sc.scale_waits;
+    };
+    // ---- the start of scale(): norms of the unscaled b and c
+    size_t at = 0;
+    for (int j = 0; j < nj; ++j) {
+        Solver &m = member(j);
+        w[j].sums = sums.p + 2 * j;
+        if (m.prm.use_Ruiz_scaling) {
+            w[j].gm_next = pairs.p + at;
+            at += aligned(static_cast<size_t>(m.m_pad));
+            w[j].gn_next = pairs.p + at;
+            at += aligned(static_cast<size_t>(m.n_pad));
+        }
+        m.scale_begin(&w[j], &gl);
+    }
+    run_fetch_wait();
+    for (int j = 0; j < nj; ++j) member(j).scale_norms_org(sums_h.p + 2 * j);
+    // ---- Curtis-Reid: twenty sweeps over A and A^T (two tables, issued twenty times), exp / clamp, the scaling pass
+    auto each_cr = [&](auto piece) {
+        for (int j = 0; j < nj; ++j)
+            if (member(j).prm.use_CR_scaling) piece(member(j), &w[j]);
+        gl.next_stage();
+    };
+    bool any_cr = false;
+    for (int j = 0; j < nj; ++j) any_cr = any_cr || member(j).prm.use_CR_scaling;
+    if (any_cr) {
+        each_cr([&](Solver &m, Solver::ScaleWalk *v) { m.scale_cr_sweep(v, false, &gl); });
+        each_cr([&](Solver &m, Solver::ScaleWalk *v) { m.scale_cr_sweep(v, true, &gl); });
+        gl.repeat_last(2, 20);
+        each_cr([&](Solver &m, Solver::ScaleWalk *v) { m.scale_cr_exp(v, &gl); });
+        each_cr([&](Solver &m, Solver::ScaleWalk *v) { m.scale_cr_apply(v, &gl); });
+    }
+    // ---- Ruiz (ten passes) and Pock-Chambolle (one); a member's pass `it` is its own whatever the others' switches are
+    int most = 0;
+    for (const Solver::ScaleWalk &v : w) most = std::max(most, v.passes);
+    for (int it = 0; it < most; ++it) {
+        for (int j = 0; j < nj; ++j) member(j).scale_pass(&w[j], it, &gl);
+        gl.next_stage();
+    }
+    // ---- b / c scaling: the second round trip, for the members that have it
+    bool any_bc = false;
+    for (int j = 0; j < nj; ++j) {
+        if (!member(j).prm.use_bc_scaling) continue;
+        any_bc = true;
+        member(j).scale_sums(&w[j], &gl, nullptr);
+    }
+    if (any_bc) run_fetch_wait();
+    for (int j = 0; j < nj; ++j) member(j).scale_bc_apply(sums_h.p + 2 * j, &gl);
+    gl.next_stage();
+    // ---- the norms of the scaled b and c, the bound codes, then the two gathered vectors back to zero
+    for (int j = 0; j < nj; ++j) member(j).scale_finish(&w[j], &gl, nullptr);
+    gl.next_stage();
+    for (int j = 0; j < nj; ++j) member(j).scale_end(&gl);
+    run_fetch_wait();
+    for (int j = 0; j < nj; ++j) {
+        Solver &m = member(j);
+        m.scale_norms(sums_h.p + 2 * j);
+        m.scal_h[S_TMP0] = sums_h[2 * j + 1];         // (what the member's own last fetch leaves in its host block)
+        m.fetches += m.prm.use_bc_scaling ? 6 : 4;    // (the scalar fetches of its own scale())
+        m.scaling_time = time_since(t0);              // the group's wall time
+        m.scaled = true;
+        ++sc.served;
+    }
+}
+
 }  // namespace
 
 void check_group(Solver *const *s, int count, const char *who, bool need_scaled) {
@@ -105,92 +196,9 @@ void scale_many(Solver **s, int count, SetupCounts *counts) {
         ++sc.own;
     }
     sc.scale_launches += scaling_launch_count() - launches_before;
-    const int nj = static_cast<int>(who.size());
-    if (nj > 0) {
-        // Solver::scale() walked for all joining members at once: the pieces are scale()'s own (solver.cpp), in its order, recorded
-        // into one GroupLaunches with a table for every kind (inside a stage a kind may hold one member's task).  The group's own:
-        // the stages, one block for the second pairs of gathered vectors, and the sums block -- two slots per member, where the
-        // pieces finalise |b|^2 and |c|^2 and from where one copy brings them to the host, three times.
-        const auto t0 = time_now();
-        const hipStream_t st = scope.group;
-        std::vector<Solver::ScaleWalk> w(static_cast<size_t>(nj));
-        auto member = [&](int j) -> Solver & { return *s[who[j]]; };
-        // the second pair of gathered vectors of every member with Ruiz passes, pieces of one block
-        auto aligned = [](size_t doubles) { return (doubles + 31) / 32 * 32; };
-        size_t pair_doubles = 0;
-        for (int j = 0; j < nj; ++j)
-            if (member(j).prm.use_Ruiz_scaling) pair_doubles += aligned(static_cast<size_t>(member(j).m_pad)) + aligned(static_cast<size_t>(member(j).n_pad));
-        DBuf<double> pairs(std::max<size_t>(pair_doubles, 1)), sums(static_cast<size_t>(2) * nj);
-        HBuf<double> sums_h;
-        sums_h.alloc(static_cast<size_t>(2) * nj);
+    if (!who.empty()) {
         GroupLaunches gl(/*own_launches=*/false);
-        auto run_fetch_wait = [&]() {
-            sc.scale_launches += gl.run(st);
-            HIP_CHECK(hipMemcpyAsync(sums_h.p, sums.p, sizeof(double) * 2 * nj, hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            ++sc.scale_waits;
-        };
-        // ---- the start of scale(): norms of the unscaled b and c
-        size_t at = 0;
-        for (int j = 0; j < nj; ++j) {
-            Solver &m = member(j);
-            w[j].sums = sums.p + 2 * j;
-            if (m.prm.use_Ruiz_scaling) {
-                w[j].gm_next = pairs.p + at;
-                at += aligned(static_cast<size_t>(m.m_pad));
-                w[j].gn_next = pairs.p + at;
-                at += aligned(static_cast<size_t>(m.n_pad));
-            }
-            m.scale_begin(&w[j], &gl);
-        }
-        run_fetch_wait();
-        for (int j = 0; j < nj; ++j) member(j).scale_norms_org(sums_h.p + 2 * j);
-        // ---- Curtis-Reid: twenty sweeps over A and A^T (two tables, issued twenty times), exp / clamp, the scaling pass
-        auto each_cr = [&](auto piece) {
-            for (int j = 0; j < nj; ++j)
-                if (member(j).prm.use_CR_scaling) piece(member(j), &w[j]);
-            gl.next_stage();
-        };
-        bool any_cr = false;
-        for (int j = 0; j < nj; ++j) any_cr = any_cr || member(j).prm.use_CR_scaling;
-        if (any_cr) {
-            each_cr([&](Solver &m, Solver::ScaleWalk *v) { m.scale_cr_sweep(v, false, &gl); });
-            each_cr([&](Solver &m, Solver::ScaleWalk *v) { m.scale_cr_sweep(v, true, &gl); });
-            gl.repeat_last(2, 20);
-            each_cr([&](Solver &m, Solver::ScaleWalk *v) { m.scale_cr_exp(v, &gl); });
-            each_cr([&](Solver &m, Solver::ScaleWalk *v) { m.scale_cr_apply(v, &gl); });
-        }
-        // ---- Ruiz (ten passes) and Pock-Chambolle (one); a member's pass `it` is its own whatever the others' switches are
-        int most = 0;
-        for (const Solver::ScaleWalk &v : w) most = std::max(most, v.passes);
-        for (int it = 0; it < most; ++it) {
-            for (int j = 0; j < nj; ++j) member(j).scale_pass(&w[j], it, &gl);
-            gl.next_stage();
-        }
-        // ---- b / c scaling: the second round trip, for the members that have it
-        bool any_bc = false;
-        for (int j = 0; j < nj; ++j) {
-            if (!member(j).prm.use_bc_scaling) continue;
-            any_bc = true;
-            member(j).scale_sums(&w[j], &gl, nullptr);
-        }
-        if (any_bc) run_fetch_wait();
-        for (int j = 0; j < nj; ++j) member(j).scale_bc_apply(sums_h.p + 2 * j, &gl);
-        gl.next_stage();
-        // ---- the norms of the scaled b and c, the bound codes, then the two gathered vectors back to zero
-        for (int j = 0; j < nj; ++j) member(j).scale_finish(&w[j], &gl, nullptr);
-        gl.next_stage();
-        for (int j = 0; j < nj; ++j) member(j).scale_end(&gl);
-        run_fetch_wait();
-        for (int j = 0; j < nj; ++j) {
-            Solver &m = member(j);
-            m.scale_norms(sums_h.p + 2 * j);
-            m.scal_h[S_TMP0] = sums_h[2 * j + 1];         // (what the member's own last fetch leaves in its host block)
-            m.fetches += m.prm.use_bc_scaling ? 6 : 4;    // (the scalar fetches of its own scale())
-            m.scaling_time = time_since(t0);              // the group's wall time
-            m.scaled = true;
-            ++sc.served;
-        }
+        scale_walk(s, who, gl, scope.group, sc);
     }
     if (counts) *counts = sc;
 }
@@ -444,6 +452,10 @@ struct GroupBlocks {
     DBuf<double> parts, out_d;
     HBuf<double> out_h;
     GroupLaunches gl;
+    // set_matrix_values_many: the recorder with a table for every kind (what scale_walk asks for), one flag word per member
+    GroupLaunches tables{/*own_launches=*/false};
+    DBuf<unsigned long long> flags;
+    HBuf<unsigned long long> flags_h;
 };
 
 namespace {
@@ -694,6 +706,177 @@ void resolve_many(Solver **s, int count, const MemberStart *start, HPRLP_results
         }
     }
     if (counts) *counts = rc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// group matrix values (DESIGN.md "Many small LPs", group matrix values): Solver::set_matrix_values of every member of a group.
+// The rule is the group launches': the bodies of values.hip's kernels run as workgroup lb of the member's own grid, the zeroing
+// is reset_iterates' fills, the scaling is scale_many's walk, so every stored number is the member's own.
+// ------------------------------------------------------------------------------------------------
+void set_matrix_values_many(Solver **s, int count, const MemberValues *data, ValuesCounts *counts) {
+    const char *who = "hprlp_solver_set_matrix_values_many";
+    // ---- the host checks of all members, before the first upload (Solver::set_matrix_values' rules and messages)
+    std::vector<char> gave(static_cast<size_t>(count), 0);
+    int ngave = 0;
+    for (int k = 0; k < count; ++k) {
+        const MemberValues &d = data[k];
+        if (!(d.val || d.c || d.obj_constant || d.AL || d.AU || d.l || d.u)) continue;  // skipped: the member keeps every bit
+        if (!d.val || !d.c || !d.AL || !d.AU || !d.l || !d.u)
+            throw std::runtime_error(member(who, k) + ": val, c, AL, AU, l and u are all required (every scaled vector depends on the values)");
+        if (d.nnz != static_cast<long>(s[k]->A.view.nnz))
+            throw std::runtime_error(member(who, k) + ": nnz is " + std::to_string(d.nnz) + ", the model has " + std::to_string(s[k]->A.view.nnz) +
+                                     " entries (the pattern cannot change)");
+        auto no_nan = [&](const double *v, long len, const char *what) {
+            for (long i = 0; i < len; ++i)
+                if (std::isnan(v[i])) throw std::runtime_error(member(who, k) + ": " + what + "[" + std::to_string(i) + "] is NaN");
+        };
+        no_nan(d.c, s[k]->n, "c"); no_nan(d.AL, s[k]->m, "AL"); no_nan(d.AU, s[k]->m, "AU"); no_nan(d.l, s[k]->n, "l"); no_nan(d.u, s[k]->n, "u");
+        if (d.obj_constant && std::isnan(*d.obj_constant)) throw std::runtime_error(member(who, k) + ": obj_constant is NaN");
+        gave[k] = 1;
+        ++ngave;
+    }
+    ValuesCounts vc;
+    const auto t0 = time_now();
+    GroupScope scope(s, count);
+    const hipStream_t st = scope.group;
+    const bool fused_norms = env_get("HPRLP_NO_FUSED_NORMS") == nullptr;  // (scale_many's condition)
+    std::vector<int> in;  // the members of the group launches
+    for (int k = 0; k < count; ++k)
+        if (gave[k] && fused_norms && s[k]->joins_group_resolve() && s[k]->m_loc > 0 && s[k]->n_loc > 0) in.push_back(k);
+    if (in.size() < 2) in.clear();  // (a group of one issues the member's own launches)
+    std::vector<char> joins(static_cast<size_t>(count), 0);
+    for (int k : in) joins[k] = 1;
+    const int nj = static_cast<int>(in.size());
+    // One member alone is checked by its own call before it writes anything, and nobody else is written: no block.
+    GroupBlocks *gb = ngave >= 2 ? &blocks_of(s[0]) : nullptr;
+    try {
+        // ---- value maps: a member's own construction, once (joining members have no ordering: map_A stays null, map_AT comes
+        // from the host transpose); the members on their own way build theirs inside their own call
+        const auto t_maps = time_now();
+        std::vector<char> built(static_cast<size_t>(count), 0);
+        for (int k : in) {
+            if (s[k]->have_maps) continue;
+            s[k]->build_value_maps();
+            built[k] = 1;
+            ++vc.maps;
+        }
+        const double maps_seconds = time_since(t_maps);
+        // ---- staging: [val | AL | AU | l | u | c] of the joining members and the values of the others in ONE pinned block, one copy
+        const auto t_up = time_now();
+        std::vector<PackMember> pm(static_cast<size_t>(count));
+        GroupPackLayout L;
+        const double *dev = nullptr;
+        if (gb) {
+            for (int k = 0; k < count; ++k) {
+                if (!gave[k]) continue;
+                pm[k].m = s[k]->m_loc, pm[k].n = s[k]->n_loc, pm[k].nnz = data[k].nnz;
+                pm[k].c = pm[k].bounds = joins[k] != 0;
+            }
+            L = group_pack_layout(pm.data(), count);
+            double *host = static_cast<double *>(gb->in.stage(sizeof(double) * std::max<size_t>(L.data_doubles, 1)));
+            for (int k = 0; k < count; ++k) {
+                if (!gave[k]) continue;
+                group_pack_values(L, k, pm[k], data[k].val, host);
+                group_pack_data(L, k, pm[k], data[k].AL, data[k].AU, data[k].l, data[k].u, data[k].c, host);
+            }
+            if (L.data_doubles > 0) {
+                gb->in.send(sizeof(double) * L.data_doubles, st);
+                ++vc.h2d;
+            }
+            dev = static_cast<const double *>(gb->in.dev);
+            // ---- the check: one flag word per member (all bits set: clean), one launch over everybody's values, one copy, one wait
+            if (gb->flags.n < static_cast<size_t>(count)) {
+                gb->flags.alloc(static_cast<size_t>(count));
+                gb->flags_h.alloc(static_cast<size_t>(count));
+            }
+            HIP_CHECK(hipMemsetAsync(gb->flags.p, 0xff, sizeof(unsigned long long) * count, st));
+            ++vc.memsets;
+            GroupLaunches &chk = gb->gl;
+            const long tables0 = chk.tables_sent();
+            for (int k = 0; k < count; ++k)
+                if (gave[k] && L.slot[k].val != kPackAbsent) chk.values_check(dev + L.slot[k].val, data[k].nnz, gb->flags.p + k);
+            vc.launches += chk.run(st);
+            vc.h2d += chk.tables_sent() - tables0;
+            HIP_CHECK(hipMemcpyAsync(gb->flags_h.p, gb->flags.p, sizeof(unsigned long long) * count, hipMemcpyDeviceToHost, st));
+            ++vc.d2h;
+            HIP_CHECK(hipStreamSynchronize(st));
+            ++vc.waits;
+            for (int k = 0; k < count; ++k)  // (the lowest member, its smallest position)
+                if (gave[k] && gb->flags_h[k] != kValuesAllFinite)
+                    throw std::runtime_error(member(who, k) + ": val[" + std::to_string(gb->flags_h[k]) + "] is not finite");
+        }
+        const double upload_seconds = time_since(t_up);
+        // -- from here on the call goes through
+        // ---- the members that go their own way: Solver::set_matrix_values (its own upload and check included)
+        for (int k = 0; k < count; ++k) {
+            if (!gave[k] || joins[k]) continue;
+            Solver &m = *s[k];
+            const MemberValues &d = data[k];
+            const bool had_maps = m.have_maps;
+            const long f0 = m.fetches, l0 = scaling_launch_count();
+            try {
+                m.set_matrix_values(d.val, d.nnz, d.c, d.obj_constant, d.AL, d.AU, d.l, d.u);
+            } catch (const std::exception &e) {  // (a member alone in the call: its own check's refusal, named as the group's)
+                const std::string msg = e.what(), own = "set_matrix_values: ";
+                throw std::runtime_error(member(who, k) + ": " + (msg.compare(0, own.size(), own) == 0 ? msg.substr(own.size()) : msg));
+            }
+            ++vc.own;
+            if (!had_maps) ++vc.maps;
+            // its staging in one copy (six from the allocator cache's block size on), the flag's memset, check, scatter, gather, the
+            // flag's copy and wait; reset_iterates' seventeen memsets and wait; scale(): its launches, its scalar fetches, its final wait
+            const size_t words = static_cast<size_t>(d.nnz) + 2 * static_cast<size_t>(m.m) + 3 * static_cast<size_t>(m.n);
+            vc.h2d += words * sizeof(double) < kDeviceCacheMinBytes ? 1 : 6;
+            vc.memsets += 1 + 17;
+            vc.launches += 3 + (scaling_launch_count() - l0);
+            vc.d2h += 1 + (m.fetches - f0);
+            vc.waits += 1 + 1 + (m.fetches - f0) + 1;
+        }
+        if (nj > 0) {
+            // ---- apply: scatter, gather and zeroing in one stage, Solver::scale()'s pieces behind them, one recorder
+            const auto t_k = time_now();
+            GroupLaunches &gl = gb->tables;
+            const long tables0 = gl.tables_sent();
+            for (int k : in) {
+                Solver &m = *s[k];
+                const PackSlot &p = L.slot[k];
+                auto at = [&](size_t off) { return off == kPackAbsent ? nullptr : dev + off; };
+                // The scatter stores 16 bytes at A_val + 2 t and AT_val + 2 t, and with map_A null it loads 16 bytes at the
+                // staged values + 2 t: the value arrays are hipMalloc's or pieces of the group's arena (256-byte aligned both),
+                // and every vector of the staging block starts on a multiple of kPackAlign = 32 doubles of a pinned block's copy.
+                gl.values_in(data[k].nnz, at(p.val), m.map_A.p, m.map_AT.p, m.A.val.p, m.AT.val.p);
+                gl.vectors_in(VectorsInArgs{m.m_loc, m.n_loc, at(p.AL), at(p.AU), at(p.l), at(p.u), at(p.c), m.perm_r_dev.p, m.perm_c_dev.p, m.AL.p,
+                                            m.AU.p, m.l.p, m.u.p, m.c.p});
+                if (data[k].obj_constant) m.obj_constant = *data[k].obj_constant;
+                m.reset_iterates(&gl);
+            }
+            gl.next_stage();  // (the scaling reads what the three kinds of this stage write)
+            const double kernels_seconds = time_since(t_k);
+            SetupCounts sc;
+            scale_walk(s, in, gl, st, sc);
+            vc.launches += sc.scale_launches;
+            vc.waits += sc.scale_waits;
+            vc.d2h += sc.scale_waits;  // (the sums block comes back once per wait)
+            vc.h2d += gl.tables_sent() - tables0;
+            vc.served += sc.served;
+            // ---- bookkeeping: what Solver::values_apply and set_matrix_values leave, with the group call's wall times
+            const double wall = time_since(t0);
+            for (int k : in) {
+                Solver &m = *s[k];
+                m.matrix_time[0] = built[k] ? maps_seconds : 0.0;
+                m.matrix_time[1] = upload_seconds;
+                m.matrix_time[2] = kernels_seconds;
+                m.matrix_time[3] = m.scaling_time;
+                m.matrix_time[4] = wall;
+                ++m.matrix_calls;
+                m.data_since_run += wall;
+                m.set_transfer(static_cast<size_t>(data[k].nnz) + 2 * static_cast<size_t>(m.m) + 3 * static_cast<size_t>(m.n), 0, false);
+            }
+        }
+    } catch (...) {
+        if (gb) s[0]->group_blocks.reset();  // (whatever was recorded goes with it)
+        throw;
+    }
+    if (counts) *counts = vc;
 }
 
 }  // namespace hprlp

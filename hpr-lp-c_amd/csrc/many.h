@@ -74,4 +74,26 @@ void set_data_many(Solver **s, int count, const MemberData *data, ResolveCounts 
 void check_starts(Solver *const *s, int count, const MemberStart *start);
 void resolve_many(Solver **s, int count, const MemberStart *start, HPRLP_results *out, ResolveCounts *counts = nullptr);
 
+// ---- group matrix values (DESIGN.md "Many small LPs", group matrix values) ------------------------------------------------------
+struct MemberValues {  // Solver::set_matrix_values' arguments for one member (hprlp_member_values); all null: the member is skipped
+    const double *val = nullptr;
+    long nnz = 0;
+    const double *c = nullptr, *obj_constant = nullptr, *AL = nullptr, *AU = nullptr, *l = nullptr, *u = nullptr;
+};
+// what a set_matrix_values_many call did (hprlp_last_values_many_counts): copies host -> device (the staging block and the task
+// tables) and device -> host, host waits, kernel launches, memsets; members served by the group launches / that went their own way
+// (for those the operations their own Solver::set_matrix_values issues are added: counted where the solver counts them -- scaling
+// launches, scalar fetches --, nominal otherwise, as ResolveCounts); members whose value maps were built in this call
+struct ValuesCounts {
+    long h2d = 0, d2h = 0, waits = 0, launches = 0, memsets = 0, served = 0, own = 0, maps = 0;
+};
+// Solver::set_matrix_values for every member that gave values.  All host checks of all members first; the values of ALL of them
+// in one pinned block and one copy, checked by ONE launch into one flag word per member, one copy of the flags, one wait -- up to
+// there nothing a solver reads has been written, so a refusal leaves every member as it was.  Then the members that join
+// (values given, Solver::joins_group_resolve, scale_many's conditions, two at least): scatter, gather and the zeroing of
+// reset_iterates recorded in one stage, and Solver::scale()'s pieces walked behind them (scale_many's walk); every other member
+// runs its own set_matrix_values inside the same call.  The members have passed check_group and data is not null (abi.cpp owns
+// those refusals).
+void set_matrix_values_many(Solver **s, int count, const MemberValues *data, ValuesCounts *counts = nullptr);
+
 }  // namespace hprlp

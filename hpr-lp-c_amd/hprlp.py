@@ -81,6 +81,10 @@ class CMemberData(C.Structure):  # hprlp_member_data (include/hprlp_amd.h)
     _fields_ = [(k, c_dbl_p) for k in ("c", "obj_constant", "AL", "AU", "l", "u")]
 
 
+class CMemberValues(C.Structure):  # hprlp_member_values
+    _fields_ = [("val", c_dbl_p), ("nnz", C.c_long)] + [(k, c_dbl_p) for k in ("c", "obj_constant", "AL", "AU", "l", "u")]
+
+
 class CMemberStart(C.Structure):  # hprlp_member_start
     _fields_ = [("x0", c_dbl_p), ("y0", c_dbl_p), ("sigma", C.c_double)]
 
@@ -254,6 +258,9 @@ def lib():
         L.hprlp_group_pack_selftest.argtypes = []
     if hasattr(L, "hprlp_group_table_selftest"):  # (likewise)
         L.hprlp_group_table_selftest.argtypes = []
+    if hasattr(L, "hprlp_solver_set_matrix_values_many"):  # (likewise)
+        L.hprlp_solver_set_matrix_values_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(CMemberValues)]
+        L.hprlp_last_values_many_counts.argtypes = [C.POINTER(C.c_long)]
     _lib = L
     return L
 
@@ -609,6 +616,17 @@ def last_resolve_many_counts():
     out = (C.c_long * 8)()
     lib().hprlp_last_resolve_many_counts(out)
     return dict(zip(RESOLVE_MANY_KEYS, [int(v) for v in out]))
+
+
+VALUES_MANY_KEYS = ("host-to-device copies", "device-to-host copies", "host waits", "kernel launches", "memsets",
+                    "members served by group launches", "members that went their own way", "members whose value maps were built")
+
+
+def last_values_many_counts():
+    """Counts of this thread's last Solver.set_matrix_many (hprlp_last_values_many_counts)."""
+    out = (C.c_long * 8)()
+    lib().hprlp_last_values_many_counts(out)
+    return dict(zip(VALUES_MANY_KEYS, [int(v) for v in out]))
 
 
 def solve_batched(model, Cmat, AL, AU, l, u, obj_constants=None, param=None):
@@ -1525,6 +1543,44 @@ class Solver:
         lam, its = self.power_iteration()
         self.init(-1.0, 1.01 * lam)
         return lam, its
+
+    @staticmethod
+    def set_matrix_many(solvers, data):
+        """New matrix values for every solver of a group (hprlp_solver_set_matrix_values_many): one copy, one check and one launch
+        per kernel and stage for the members that join; every member ends bit for bit where hprlp_solver_set_matrix_values leaves
+        it.  data: per solver None (skipped), or a dict of set_matrix's keyword arguments (values, c, AL, AU, l, u and, optionally,
+        obj_constant).  Unlike set_matrix() this is the C call alone: power_iteration_many(), init() and resolve_many() come next,
+        as after scale_many()."""
+        solvers, hs = Solver._handles(solvers)
+        data = list(data)
+        if len(data) != len(solvers):
+            raise ValueError("set_matrix_many: one dict (or None) per solver")
+        arr = (CMemberValues * max(len(solvers), 1))()
+        keep = []  # (the arrays the pointers name live until the call returns)
+        for k, (sv, d) in enumerate(zip(solvers, data)):
+            if d is None:
+                continue
+            d = dict(d)
+            unknown = set(d) - {"values", "c", "obj_constant", "AL", "AU", "l", "u"}
+            if unknown:
+                raise ValueError(f"set_matrix_many: member {k}: unknown keys {sorted(unknown)}")
+            m, n = sv.model.m, sv.model.n
+            if d.get("values") is not None:
+                v = _as(d["values"], np.float64)
+                if v.ndim != 1:
+                    raise ValueError(f"set_matrix_many: member {k}: values must be one-dimensional, got shape {v.shape}")
+                keep.append(v)
+                arr[k].val, arr[k].nnz = _dptr(v), v.shape[0]  # (a wrong count is the library's to refuse, naming the member)
+            for key, length in (("c", n), ("AL", m), ("AU", m), ("l", n), ("u", n)):
+                a = sv._data_vector(d.get(key), length, key)
+                keep.append(a)
+                setattr(arr[k], key, _dptr(a))
+            if d.get("obj_constant") is not None:
+                oc = C.c_double(float(d["obj_constant"]))
+                keep.append(oc)
+                arr[k].obj_constant = C.pointer(oc)
+        if lib().hprlp_solver_set_matrix_values_many(hs, len(solvers), arr) < 0:
+            raise RuntimeError(last_error())
 
     def matrix_seconds(self):
         """Seconds of the last set_matrix() (without its power iteration): {maps (first call only), upload, kernels, scale, total}

@@ -441,6 +441,36 @@ int hprlp_group_pack_selftest(void);
  * of the failed check */
 int hprlp_group_table_selftest(void);
 
+/* ---- group matrix values: new coefficients on the resident patterns of the whole group (DESIGN.md "Many small LPs", group
+ * matrix values) ------------------------------------------------------------------------------------------------------------
+ * hprlp_solver_set_matrix_values for every member: an MPC horizon that re-linearises its dynamics, a scenario set that redraws
+ * its coefficients.  Every member that gave values ends bit for bit where its own hprlp_solver_set_matrix_values leaves it -- a
+ * fresh hprlp_solver_create on the changed model followed by hprlp_solver_scale: iterates zero; index arrays, kernel forms and
+ * captured graphs kept.  The next steps are those after hprlp_solver_scale_many: hprlp_solver_power_iteration_many, init,
+ * hprlp_solver_resolve_many.  The values and vectors of all members travel in ONE pinned block and one copy; the values of all
+ * of them are checked on the device by one launch, one copy of one flag word per member and one wait; the members that join
+ * (values given, the group re-solve's conditions, hprlp_solver_scale_many's; two at least) get scatter, gather, zeroing and the
+ * whole scaling in one launch per kernel and stage, three more waits -- none of it grows with the count (the value maps apart: a
+ * member builds its own at its first call).  A member that cannot join runs its own set_matrix_values inside the same call,
+ * after the common check.  A member's hprlp_solver_matrix_seconds and the start of its next out.time are the group call's wall
+ * times; hprlp_solver_transfer reports the member's own words.
+ * Refusals (-1 + hprlp_last_error(), naming the entry point and `member k`): the group rules (NULL list or data, count <= 0, a
+ * handle twice, a sharded member, a member never scaled, different devices); per member the single entry's rules with its
+ * messages (some but not all of val, c, AL, AU, l, u; nnz other than the member's; a NaN in a vector or obj_constant), all before
+ * the first upload; a non-finite value, found on the device in the staging block: `val[i]` with the smallest such i of the
+ * lowest such member.  After ANY refusal EVERY member of the call is unchanged bit for bit and still usable. */
+typedef struct hprlp_member_values {  /* hprlp_solver_set_matrix_values' arguments for one member; val NULL and all others NULL: skipped */
+    const double *val; long nnz;
+    const double *c, *obj_constant, *AL, *AU, *l, *u;
+} hprlp_member_values;
+int hprlp_solver_set_matrix_values_many(hprlp_solver **s, int count, const hprlp_member_values *data);
+/* Counts of the calling thread's last hprlp_solver_set_matrix_values_many: out = {host-to-device copies (staging block and task
+ * tables), device-to-host copies, host waits, kernel launches, memsets, members served by group launches, members that went
+ * their own way (their operations are included: scaling launches and scalar fetches as the solver counts them, the rest nominal,
+ * as hprlp_last_resolve_many_counts does), members whose value maps were built in this call (the map construction's own
+ * operations are not counted)}. */
+int hprlp_last_values_many_counts(long out[8]);
+
 /* Named device vectors: x y x_hat x_bar y_bar z_bar x_temp y_temp y_obj last_x last_y AL AU l u c
  * row_norm col_norm A_val AT_val.  get returns the length (or -1); cap is the capacity of out. */
 long hprlp_solver_get_vector(hprlp_solver *s, const char *name, double *out, long cap);
