@@ -1417,7 +1417,7 @@ extern "C" int hprlp_solver_restart_many(hprlp_solver **h, int count, const doub
 // counts of the calling thread's last hprlp_solver_run_many / hprlp_solve_many (hprlp_last_run_many_counts)
 static thread_local long g_many_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 static void keep_many_counts(const GroupCounts &gc) {
-    const long v[8] = {gc.rounds, gc.waits, gc.group_launches, gc.copies, gc.own, gc.served, 0, 0};
+    const long v[8] = {gc.rounds, gc.waits, gc.group_launches, gc.copies, gc.own, gc.served, gc.ray_served, gc.certs_served};
     for (int i = 0; i < 8; ++i) g_many_counts[i] = v[i];
 }
 
@@ -1552,13 +1552,26 @@ extern "C" int hprlp_last_solve_many_phases(double out[8]) {
     return 0;
 }
 
-extern "C" int hprlp_solve_many(const LP_info_cpu *const *models, int count, const HPRLP_parameters *param, HPRLP_results *out) {
+// hprlp_solve_many and hprlp_solve_many_detect (`who`, for the error messages).  det null: no detection.  certs (may be null):
+// count entries, each cleared to its member's m and n on entry (hprlp_solve_detect's contract) and filled where detection ran.
+static int solve_many_entry(const LP_info_cpu *const *models, int count, const HPRLP_parameters *param, const hprlp_detection *det,
+                            HPRLP_results *out, hprlp_certificate *certs, const char *who_) {
     GUARD_BEGIN
-    if (!models) throw std::runtime_error("hprlp_solve_many: null model list");
-    if (count <= 0) throw std::runtime_error("hprlp_solve_many: count must be positive");
-    if (!out) throw std::runtime_error("hprlp_solve_many: null results");
+    const std::string w(who_);
+    if (!models) throw std::runtime_error(w + ": null model list");
+    if (count <= 0) throw std::runtime_error(w + ": count must be positive");
+    if (!out) throw std::runtime_error(w + ": null results");
     for (int k = 0; k < count; ++k)
-        if (!models[k]) throw std::runtime_error("hprlp_solve_many: model " + std::to_string(k) + " is null");
+        if (!models[k]) throw std::runtime_error(w + ": model " + std::to_string(k) + " is null");
+    Detection dsel;
+    bool with_det = false;
+    try {
+        with_det = detection_from(det, &dsel);  // (a negative eps: refused before anything is created)
+    } catch (const std::exception &e) {
+        throw std::runtime_error(w + ": " + e.what());
+    }
+    if (certs)
+        for (int k = 0; k < count; ++k) clear_certificate(&certs[k], models[k]->m, models[k]->n);
     HPRLP_parameters dflt;
     const HPRLP_parameters *p = param ? param : &dflt;
     const auto t_call = time_now();
@@ -1584,7 +1597,7 @@ extern "C" int hprlp_solve_many(const LP_info_cpu *const *models, int count, con
     std::vector<Solver *> s;
     std::vector<int> who;
     const auto t_setup = time_now();
-    create_group(models, count, p, owned.data(), "hprlp_solve_many", together);
+    create_group(models, count, p, owned.data(), who_, together);
     g_many_phases[0] = time_since(t_setup);
     for (int k = 0; k < count; ++k)
         if (owned[k]) {
@@ -1618,6 +1631,7 @@ extern "C" int hprlp_solve_many(const LP_info_cpu *const *models, int count, con
             for (int g = 0; g < ng; ++g) {
                 s[g]->lambda_max = lam[g] * 1.01;
                 s[g]->init_iteration_state();
+                if (with_det) s[g]->detect = dsel;
             }
             g_many_phases[2] = time_since(t_pw);
             const auto t_loop = time_now();
@@ -1628,6 +1642,12 @@ extern "C" int hprlp_solve_many(const LP_info_cpu *const *models, int count, con
             g_many_phases[6] = static_cast<double>(gc.waits);
             g_many_phases[7] = static_cast<double>(gc.launches);
             keep_many_counts(gc);
+            if (with_det && certs)
+                for (int g = 0; g < ng; ++g)
+                    if (!export_certificate(s[g]->cert, &certs[who[g]], models[who[g]]->m, models[who[g]]->n)) {
+                        for (int k = 0; k < count; ++k) hprlp_free_certificate(&certs[k]);
+                        throw std::runtime_error(w + ": host allocation of a certificate failed");
+                    }
         } catch (...) {
             free_results_arrays(res.data(), ng);
             throw;
@@ -1638,6 +1658,15 @@ extern "C" int hprlp_solve_many(const LP_info_cpu *const *models, int count, con
     g_many_phases[4] = time_since(t_call);
     return 0;
     GUARD_END(-1)
+}
+
+extern "C" int hprlp_solve_many(const LP_info_cpu *const *models, int count, const HPRLP_parameters *param, HPRLP_results *out) {
+    return solve_many_entry(models, count, param, nullptr, out, nullptr, "hprlp_solve_many");
+}
+
+extern "C" int hprlp_solve_many_detect(const LP_info_cpu *const *models, int count, const HPRLP_parameters *param, const hprlp_detection *det,
+                                       HPRLP_results *out, hprlp_certificate *certs) {
+    return solve_many_entry(models, count, param, det, out, certs, "hprlp_solve_many_detect");
 }
 
 namespace {
@@ -1877,6 +1906,19 @@ extern "C" int hprlp_solver_ray_step(hprlp_solver *h, int restart, double out[9]
     const int slots[9] = {S_RAY_DY, S_RAY_CD, S_RAY_VY, S_RAY_WD, S_RAY_YN, S_RAY_DN, S_RAY_DZ, S_RAY_VZ, S_RAY_WQ};
     for (int k = 0; k < 9; ++k) out[k] = s.scal_h[slots[k]];
     return 1;
+    GUARD_END(-1)
+}
+
+// hprlp_solver_ray_step for every member of a group (many.cpp: ray_step_many)
+extern "C" int hprlp_solver_ray_step_many(hprlp_solver **h, int count, const int *restart, double *out, int *tested) {
+    GUARD_BEGIN
+    // (the plain arguments first, so that a wrong call is refused whatever the handles are)
+    if (!restart) throw std::runtime_error("hprlp_solver_ray_step_many: null restart");
+    if (!out) throw std::runtime_error("hprlp_solver_ray_step_many: null out");
+    if (!tested) throw std::runtime_error("hprlp_solver_ray_step_many: null tested");
+    std::vector<Solver *> s = group_members(h, count, "hprlp_solver_ray_step_many");
+    ray_step_many(s.data(), count, restart, out, tested);
+    return 0;
     GUARD_END(-1)
 }
 

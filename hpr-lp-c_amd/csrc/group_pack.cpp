@@ -42,6 +42,15 @@ GroupPackLayout group_pack_layout(const PackMember *members, int count) {
             s.y = take(L.result_doubles, m);
             s.z = take(L.result_doubles, n);
         }
+        if (mb.cert == 1) {
+            s.cert_rn = take(L.cert_doubles, m);
+            s.cert_cn = take(L.cert_doubles, n);
+            s.cert_ray = take(L.cert_doubles, m);
+            s.cert_aty = take(L.cert_doubles, n);
+        } else if (mb.cert == 2) {
+            s.cert_cn = take(L.cert_doubles, n);
+            s.cert_ray = take(L.cert_doubles, n);
+        }
     }
     return L;
 }
@@ -81,7 +90,9 @@ void group_unpack_result(const GroupPackLayout &L, int k, const PackMember &mb, 
 // are disjoint; 4 offsets are aligned; 5 a pack / unpack round trip of the data and start blocks returns what went in and leaves
 // the padding alone; 6 the result round trip; 7 an empty group and members of size zero; 8 matrix values (set_matrix_values_many):
 // a member's values lie in front of its vectors in the order [val | AL | AU | l | u | c], aligned, disjoint from everything else
-// and inside the block, odd, even and single counts, a member with values and no vectors; the round trip leaves the padding alone.
+// and inside the block, odd, even and single counts, a member with values and no vectors; the round trip leaves the padding alone;
+// 9 certificates (loop_many): kind 1 takes [row_norm (m) | col_norm (n) | ray (m) | A^T y (n)], kind 2 [col_norm (n) | ray (n)],
+// kind 0 nothing, in member order without gaps but the padding, aligned, disjoint, inside the block, and in no other block.
 extern "C" int hprlp_group_pack_selftest(void) {
     using namespace hprlp;
     // odd sizes, sizes below and at the alignment, every combination of given / absent
@@ -247,6 +258,38 @@ extern "C" int hprlp_group_pack_selftest(void) {
         for (size_t i = 1; i < vr.size(); ++i)
             if (vr[i - 1].at + vr[i - 1].len > vr[i].at) return 8;
         if (static_cast<size_t>(std::count(vblock.begin(), vblock.end(), pad)) != vblock.size() - written) return 8;
+    }
+    {
+        const int shapes[][3] = {{1, 2, 1}, {2, 1, 2}, {30, 50, 0}, {33, 31, 1}, {400, 600, 2}, {64, 32, 1}, {5, 9, 0}, {1, 1, 2}};
+        std::vector<PackMember> cmv;
+        for (const auto &sh : shapes) {
+            PackMember p;
+            p.m = sh[0], p.n = sh[1], p.cert = sh[2];
+            cmv.push_back(p);
+        }
+        const GroupPackLayout Cl = group_pack_layout(cmv.data(), static_cast<int>(cmv.size()));
+        if (Cl.data_doubles || Cl.start_doubles || Cl.result_doubles) return 9;
+        size_t want = 0;
+        for (size_t k = 0; k < cmv.size(); ++k) {
+            const PackMember &p = cmv[k];
+            const PackSlot &s = Cl.slot[k];
+            const size_t m = static_cast<size_t>(p.m), n = static_cast<size_t>(p.n);
+            const size_t at[4] = {s.cert_rn, s.cert_cn, s.cert_ray, s.cert_aty};
+            const size_t len[4] = {m, n, p.cert == 1 ? m : n, n};
+            const bool there[4] = {p.cert == 1, p.cert != 0, p.cert != 0, p.cert == 1};
+            for (int v = 0; v < 4; ++v) {
+                if (there[v] != (at[v] != kPackAbsent)) return 9;
+                if (!there[v]) continue;
+                if (at[v] != want || at[v] % kPackAlign != 0) return 9;  // (in order, nothing in between but the padding: disjoint)
+                want += padded(len[v]);
+                if (at[v] + len[v] > Cl.cert_doubles) return 9;
+            }
+            if (s.x != kPackAbsent || s.AL != kPackAbsent || s.val != kPackAbsent || s.x0 != kPackAbsent) return 9;
+        }
+        if (want != Cl.cert_doubles) return 9;
+        for (const PackSlot &s : L.slot)
+            if (s.cert_rn != kPackAbsent || s.cert_cn != kPackAbsent || s.cert_ray != kPackAbsent || s.cert_aty != kPackAbsent) return 9;
+        if (L.cert_doubles) return 9;
     }
     return 0;
 }

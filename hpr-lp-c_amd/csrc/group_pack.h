@@ -19,19 +19,23 @@ struct PackMember {
     bool c = false, bounds = false;  // bounds: AL, AU (m) and l, u (n) together
     bool x0 = false, y0 = false;
     bool result = false;             // the member's solution [x (n) | y (m) | z (n)] comes back through the group's block
+    // a verdict's raw arrays come back through the group's certificate block (loop_many): 1 primal infeasible [row_norm (m) |
+    // col_norm (n) | ray_y (m) | A^T y_s (n)], 2 dual infeasible [col_norm (n) | ray_d (n)], 0 none
+    int cert = 0;
 };
 
-// Offsets in doubles (kPackAbsent: not there).  Three blocks: the data of set_data_many, the starts of resolve_many (both travel
-// host -> device in one copy each) and the results (device -> host in one copy).
+// Offsets in doubles (kPackAbsent: not there).  Four blocks: the data of set_data_many, the starts of resolve_many (both travel
+// host -> device in one copy each), the results and the certificates of a round's verdicts (device -> host in one copy each).
 struct PackSlot {
     size_t val = kPackAbsent;
     size_t AL = kPackAbsent, AU = kPackAbsent, l = kPackAbsent, u = kPackAbsent, c = kPackAbsent;
     size_t x0 = kPackAbsent, y0 = kPackAbsent;
     size_t x = kPackAbsent, y = kPackAbsent, z = kPackAbsent;
+    size_t cert_rn = kPackAbsent, cert_cn = kPackAbsent, cert_ray = kPackAbsent, cert_aty = kPackAbsent;
 };
 struct GroupPackLayout {
     std::vector<PackSlot> slot;
-    size_t data_doubles = 0, start_doubles = 0, result_doubles = 0;
+    size_t data_doubles = 0, start_doubles = 0, result_doubles = 0, cert_doubles = 0;
 };
 
 GroupPackLayout group_pack_layout(const PackMember *members, int count);

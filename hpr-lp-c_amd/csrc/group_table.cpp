@@ -96,7 +96,10 @@ const std::vector<GroupLaunch> &GroupTable::finish() {
 // 3 grids {3, 0, 2} give the map (0,0) (0,1) (0,2) (2,0) (2,1) and 5 workgroups; 4 a kind with one task takes no table under the
 // own-launch rule and one without it; 5 repeat_last(2, 20) over stages s, t issues s t s t ... (40 launches) from one table each;
 // 6 the launch list is as long as recorded_launches() says, for two stages that hold the same kind; 7 an empty trailing stage adds
-// nothing; 8 the grid rules' workgroup counts; 9 a repeat of stages that were not recorded is refused.
+// nothing; 8 the grid rules' workgroup counts; 9 a repeat of stages that were not recorded is refused; 10 the shape of a periodic
+// round with detection (a check step's stage, then the evaluation's stage with the three ray kinds, one of them a lone member's):
+// the launches of the second stage do not depend on the number of tasks, a lone task goes its own way only where its kind says so,
+// and the kinds of a stage are issued in ascending order (the form ahead of the two products that gather what it writes).
 extern "C" int hprlp_group_table_selftest(void) {
     using namespace hprlp;
     struct Task {
@@ -192,6 +195,30 @@ extern "C" int hprlp_group_table_selftest(void) {
         for (int i = 0; i < 40; ++i)
             if (list[i].stage != i % 2 || list[i].tasks != list[i % 2].tasks || list[i].map != list[i % 2].map) return 5;
         if (list[0].tasks == list[1].tasks || list[40].stage != 2) return 5;
+    }
+    for (int members = 1; members <= 5; members += 4) {  // ---- 10
+        enum { kX = 0, kRd = 1, kForm = 2, kCol = 3, kRow = 4, kFin = 5 };
+        GroupTable g(true, 512, 256);
+        g.note(kX), g.note(kFin);
+        g.next_stage();
+        g.note(kRd), g.note(kForm), g.note(kCol), g.note(kRow), g.note(kFin);
+        if (g.recorded_launches() != 7) return 10;
+        g.begin();
+        const int gr[5] = {1, 3, 2, 1, 5};
+        const bool lone = members == 1;  // (what the recorder says of a kind with a launch of the member's own: one task)
+        g.add(0, kX, kGridMapped, o5, sizeof(Odd), members, gr, lone);
+        g.add(0, kFin, kGridPerTask, o5, sizeof(Odd), members, nullptr, false);
+        g.add(1, kRd, kGridMapped, o5, sizeof(Odd), members, gr, lone);
+        g.add(1, kForm, kGridReduce, o5, sizeof(Odd), members, nullptr, lone);
+        g.add(1, kCol, kGridMapped, o5, sizeof(Odd), 1, gr, true);   // (one member has a previous iterate: a lone task)
+        g.add(1, kRow, kGridMapped, o5, sizeof(Odd), 1, gr, false);  // (a kind without a launch of the member's own)
+        g.add(1, kFin, kGridPerTask, o5, sizeof(Odd), members, nullptr, false);
+        const std::vector<GroupLaunch> list = g.finish();
+        if (list.size() != 7) return 10;
+        for (size_t i = 1; i < list.size(); ++i)
+            if (list[i].stage < list[i - 1].stage || (list[i].stage == list[i - 1].stage && list[i].kind <= list[i - 1].kind)) return 10;
+        if (list[3].kind != kForm || list[3].own != (members == 1) || (!list[3].own && list[3].nwg != members * 512)) return 10;
+        if (!list[4].own || list[5].own || list[5].nwg != 1) return 10;
     }
     return 0;
 }

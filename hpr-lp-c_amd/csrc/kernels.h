@@ -447,6 +447,15 @@ class GroupLaunches {
     void values_check(const double *v, long n, unsigned long long *first_bad);
     void values_in(long nnz, const double *stage, const int *mapA, const int *mapAT, double *A_val, double *AT_val);
     void vectors_in(const VectorsInArgs &a);
+    // Infeasibility detection (DESIGN.md "Many small LPs", group detection): the ray test's three kernels, mirroring launch_ray_*
+    // (the form on its kReduceBlocks workgroups), and a verdict's raw arrays into the group's certificate block -- elementwise
+    // copies and the plain product M v (launch_spmv_plain without dots) writing straight into it.
+    void ray_form(const RayFormArgs &a, double *partials);
+    void ray_col(const CsrDev &AT, const double *ys_full, const double *l, const double *u, const double *col_norm, double b_scale, double c_scale,
+                 double *partials);
+    void ray_row(const CsrDev &A, const double *ds_full, const double *AL, const double *AU, const double *row_norm, double b_scale, double *partials);
+    void copy(double *dst, const double *src, int n);
+    void spmv_plain(const CsrDev &M, const double *v_full, double *out);
     long tables_sent() const;  // host-to-device copies of the tables so far (one per run() that had a table to send)
     int recorded_launches() const;  // what run() would issue for the records held now
     // What is recorded from here on runs after everything recorded so far, finalize included (one run, one copy of the tables

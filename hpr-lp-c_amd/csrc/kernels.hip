@@ -2671,9 +2671,10 @@ void launch_pw_err(const double *z, const double *q, int m, const double *scalar
 // the ray SpMVs read), prev_* <- *_bar, and the elementwise parts of the ray test in original units (k_unscale's map):
 // partials of {D over the rows, c'd} (sums) and {V over the rows, W over the columns, |y|_inf, |d|_inf} (maxima), kRayFormAccs x
 // gridDim.x.  A row with y_i > 0 pairs with AL_i, y_i < 0 with AU_i; a column's step d_j must stay inside the finite bounds' cone.
-__global__ void __launch_bounds__(kThreads) k_ray_form(RayFormArgs a, double *partials) {
+// (the body of k_ray_form and of its group form: workgroup `bid` of `grid`)
+__device__ __forceinline__ void ray_form_body(const RayFormArgs &a, double *partials, int bid, int grid) {
     double acc[kRayFormAccs] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    const int tid = blockIdx.x * kThreads + threadIdx.x, nth = gridDim.x * kThreads;
+    const int tid = bid * kThreads + threadIdx.x, nth = grid * kThreads;
     for (int j = tid; j < a.n; j += nth) {
         const double xb = a.x_bar[j];
         const double ds = xb - a.prev_x[j];
@@ -2704,8 +2705,9 @@ __global__ void __launch_bounds__(kThreads) k_ray_form(RayFormArgs a, double *pa
         }
         acc[4] = fmax(acc[4], fabs(y));
     }
-    block_store_partials<kRayFormAccs, kWavesPerBlock, 4>(acc, partials, gridDim.x);
+    block_store_partials_at<kRayFormAccs, kWavesPerBlock, 4>(acc, partials, grid, bid);
 }
+__global__ void __launch_bounds__(kThreads) k_ray_form(RayFormArgs a, double *partials) { ray_form_body(a, partials, blockIdx.x, gridDim.x); }
 void launch_ray_form(const RayFormArgs &a, double *partials, int nblocks, hipStream_t s) {
     hipLaunchKernelGGL(k_ray_form, dim3(nblocks), dim3(kThreads), 0, s, a, partials);
 }
@@ -3119,6 +3121,28 @@ struct LuTask {
     __device__ void run(int lb) const { lu_body(n, x_bar, l, u, col_norm, x_temp, partials, lb, kReduceBlocks); }
     void own(hipStream_t s) const { launch_lu(n, x_bar, l, u, col_norm, x_temp, partials, kReduceBlocks, s); }
 };
+// The ray test of the infeasibility detection (DESIGN.md "Many small LPs", group detection): k_ray_form keeps the member's own
+// shape of kReduceBlocks workgroups; its two SpMVs are GroupTask<RayColEpi> and GroupTask<RayRowEpi>.
+struct RayFormTask {
+    static constexpr GridRule rule = kGridReduce;
+    RayFormArgs a;
+    double *partials;
+    __device__ void run(int lb) const { ray_form_body(a, partials, lb, kReduceBlocks); }
+    void own(hipStream_t s) const { launch_ray_form(a, partials, kReduceBlocks, s); }
+};
+// A verdict's raw arrays into the group's certificate block (many.cpp: loop_many): dst[i] = src[i], one thread per element.
+// Recorded by the certificate collection alone, which has no launch of a member's own for it.
+struct CopyTask {
+    static constexpr GridRule rule = kGridMapped;
+    double *dst;
+    const double *src;
+    int n;
+    __device__ void run(int lb) const {
+        const int i = lb * kThreads + threadIdx.x;
+        if (i < n) dst[i] = src[i];
+    }
+    int own_grid() const { return elem_grid(n); }
+};
 struct DataInTask {
     static constexpr GridRule rule = kGridReduce;
     DataInArgs a;
@@ -3298,15 +3322,26 @@ struct KindList {
 // lu_code and row_code -- nobody writes what another of them reads or writes, apart from part_v, whose order is kept.
 //   new matrix values:  the check of the staged values (a run of its own: the host reads the flags before anything is written),
 //             the scatter of the values, the gather of the vectors, zeroing (the elementwise kind).
-// The three kinds of that line stand in front of everything.  set_matrix_values_many records the scatter, the gather and the
+//   group detection:  the ray test's form, its column and its row product -- behind the gap, in a member's own order (the two
+//             products gather the ray_d and ray_y the form writes) --, then the certificate's copies and its plain product.
+// The three ray kinds share the evaluation's stage (Solver::ray_test recorded behind Solver::residuals_launch).  They read x_bar,
+// y_bar, the bounds, c, the two norms and the matrix, which nothing of that stage writes (the check step that wrote x_bar and y_bar
+// stands a stage earlier), and write ray_prev_x / ray_prev_y, ray_d, ray_y, their three disjoint regions of ray_part and, through
+// their nine finalize items, the slots S_RAY_* -- none of which the residual kinds, the gap, k_lu or their finalize items (slots
+// S_RD2, S_RP2, S_ADX_DY, S_LU2; part_x, part_r, part_v) read or write; a joining member has no remainder buffers.  The zeroing
+// of a member's ray vectors at its first detection run (Solver::ray_begin) is the elementwise kind of the same or of an earlier
+// stage: in front of the form either way.  A verdict's certificate is a run of its own (the loop has consumed the round's scalars):
+// the copies read row_norm, col_norm, ray_y and ray_d, the plain product reads the matrix and ray_y, and both write only the
+// group's certificate block, every task its own range.
+// The three kinds of the values line stand in front of everything.  set_matrix_values_many records the scatter, the gather and the
 // zeroing fills of Solver::reset_iterates in ONE stage: the scatter reads the staging block and the maps and writes A_val and
 // AT_val, the gather reads the staging block and writes AL, AU, l, u and c, the fills write the iterates, the work vectors, the
 // scalars and ctrl -- three disjoint sets of arrays, none of which another of the three reads, so their order is no statement
 // either; scaling, which reads all of them, begins a stage later.
 using GroupKinds = KindList<ValuesCheckTask, ValuesInTask, VectorsInTask, RowNormTask<false>, RowNormTask<true>, GroupTask<CrEpi>, VecTask, CodesTask<false>, CodesTask<true>, RestartCopyTask, SetCtrlTask,
                             StartInTask, GroupTask<StartColEpi>, GroupTask<StartRowEpi>, GroupTask<XEpi<true>>, GroupTask<YEpi<true>>,
-                            GroupTask<RdEpi>, GroupTask<RpEpi<false>>, GroupTask<RpEpi<true>>, GroupTask<GapEpi>, LuTask, MovementTask, DataInTask,
-                            DataBcTask, UnscaleTask, ScaleMat<0>, ScaleMat<1>, ScaleMat<2>, ScaleMat<3>, ScaleMat<4>, ScaleMat<5>, ScaleMat<6>,
+                            GroupTask<RdEpi>, GroupTask<RpEpi<false>>, GroupTask<RpEpi<true>>, GroupTask<GapEpi>, RayFormTask, GroupTask<RayColEpi>,
+                            GroupTask<RayRowEpi>, CopyTask, GroupTask<PlainEpi<false>>, LuTask, MovementTask, DataInTask, DataBcTask, UnscaleTask, ScaleMat<0>, ScaleMat<1>, ScaleMat<2>, ScaleMat<3>, ScaleMat<4>, ScaleMat<5>, ScaleMat<6>,
                             ScaleMat<7>, ReduceTask<true>, ReduceTask<false>, FinalizeOne>;
 
 struct GroupLaunches::Impl {
@@ -3470,6 +3505,21 @@ void GroupLaunches::values_in(long nnz, const double *stage, const int *mapA, co
 }
 void GroupLaunches::vectors_in(const VectorsInArgs &a) {
     if (a.m > 0 || a.n > 0) impl->rec<VectorsInTask>().push_back({a});
+}
+void GroupLaunches::ray_form(const RayFormArgs &a, double *partials) { impl->rec<RayFormTask>().push_back({a, partials}); }
+void GroupLaunches::ray_col(const CsrDev &AT, const double *ys_full, const double *l, const double *u, const double *col_norm, double b_scale,
+                            double c_scale, double *partials) {
+    impl->rec<GroupTask<RayColEpi>>().push_back({stream_part(AT), RayColEpi{{ys_full}, l, u, col_norm, b_scale, c_scale, partials, AT.grid()}});
+}
+void GroupLaunches::ray_row(const CsrDev &A, const double *ds_full, const double *AL, const double *AU, const double *row_norm, double b_scale,
+                            double *partials) {
+    impl->rec<GroupTask<RayRowEpi>>().push_back({stream_part(A), RayRowEpi{{ds_full}, AL, AU, row_norm, b_scale, partials, A.grid()}});
+}
+void GroupLaunches::copy(double *dst, const double *src, int n) {
+    if (n > 0) impl->rec<CopyTask>().push_back({dst, src, n});
+}
+void GroupLaunches::spmv_plain(const CsrDev &M, const double *v_full, double *out) {
+    impl->rec<GroupTask<PlainEpi<false>>>().push_back({stream_part(M), PlainEpi<false>{{v_full}, out, nullptr, nullptr, 0}});
 }
 long GroupLaunches::tables_sent() const { return impl->tables_sent; }
 int GroupLaunches::recorded_launches() const { return impl->plan.recorded_launches(); }

@@ -8,7 +8,8 @@
 // members.  The host side -- stopping test, restart rule, sigma update, detection -- is the member's own code (the pieces of
 // Solver::solve_loop), so a member's iterates and results are the bits it gets alone.  A member that cannot join the group launches
 // (Solver::joins_group) issues its own launches inside the same lock-step; so does every member for its iteration-0 evaluation
-// (resolve_many apart: the group re-solve further down) and its ray tests.  New matrix values for the whole group
+// (resolve_many apart: the group re-solve further down).  The ray tests of the infeasibility detection and the certificates of the
+// members that join are the group's as well (DESIGN.md "Many small LPs", group detection).  New matrix values for the whole group
 // (set_matrix_values_many) are at the end of this file; they share scale_many's walk of Solver::scale() (scale_walk).
 //
 // Ordering is by stream: for the duration of a call every member works on ONE stream (the first member's), after its own stream
@@ -329,6 +330,36 @@ void restart_many(Solver **s, int count, const double *in, double *sigma_out) {
         for (int k = 0; k < count; ++k) sigma_out[k] = s[k]->sigma;
 }
 
+void ray_step_many(Solver **s, int count, const int *restart, double *out, int *tested) {
+    const char *who = "hprlp_solver_ray_step_many";
+    // (the list, the count, the arrays and the members have been checked by the caller: abi.cpp owns those refusals)
+    for (int k = 0; k < count; ++k)
+        if (!restart[k] && !s[k]->ray_prev_x.p)
+            throw std::runtime_error(std::string(who) + ": member " + std::to_string(k) + ": the first step of a solver needs restart != 0");
+    GroupScope scope(s, count);
+    const std::vector<char> joins = who_joins(s, count);
+    GroupLaunches gl;
+    GroupCounts gc;
+    for (int k = 0; k < count; ++k) {
+        GroupLaunches *g = joins[k] ? &gl : nullptr;
+        if (restart[k]) s[k]->ray_begin(g);
+        s[k]->residuals_launch(1, true, g);
+        tested[k] = s[k]->ray_test(g) ? 1 : 0;  // (a member outside the group: its own launches, behind its own evaluation)
+        gl.pack(s[k]->scal.p, s[k]->scal_h.p);
+    }
+    gl.run(scope.group);
+    run_fetch_wait(gl, scope.group, gc);
+    const int slots[9] = {S_RAY_DY, S_RAY_CD, S_RAY_VY, S_RAY_WD, S_RAY_YN, S_RAY_DN, S_RAY_DZ, S_RAY_VZ, S_RAY_WQ};
+    for (int k = 0; k < count; ++k) {
+        Residuals r;
+        RestartState rs;
+        ++s[k]->fetches;
+        s[k]->residuals_consume(1, true, &r, &rs);  // (as hprlp_solver_ray_step: the evaluation a periodic check runs)
+        if (!tested[k]) continue;
+        for (int i = 0; i < 9; ++i) out[9 * static_cast<size_t>(k) + i] = s[k]->scal_h[slots[i]];
+    }
+}
+
 namespace {
 
 // The lock-step loop of run_many from every member's current state, up to loop_finish (the solutions are the caller's).  gl may
@@ -339,48 +370,86 @@ void loop_many(Solver **s, int count, HPRLP_results *out, GroupCounts &gc, Group
                const char *iter0) {
     std::vector<LoopState> ls(static_cast<size_t>(count));
     std::vector<char> active(static_cast<size_t>(count), 1);
-    for (int k = 0; k < count; ++k) s[k]->loop_begin(&ls[k], &out[k]);
+    // (a joining member's first detection run: its ray vectors zeroed by recorded fills, ahead of the first evaluation)
+    for (int k = 0; k < count; ++k) s[k]->loop_begin(&ls[k], &out[k], joins[k] ? &gl : nullptr);
     SmallTaskBuf buf;
     std::vector<SmallIterTask> tasks;
-    std::vector<int> flagged;
+    std::vector<int> flagged, verdicts;
+    std::vector<PackMember> cm;  // the certificate block of a round with verdicts: device, and pinned
+    DBuf<double> cert_d;
+    HBuf<double> cert_h;
     // (between two rounds gl holds the check steps recorded in step 11: they run with the next evaluation, a stage ahead)
     auto in_group = [&](int k) { return joins[k] && (ls[k].iter > 0 || (iter0 && iter0[k])); };
     int left = count;
     while (left > 0) {
-        // 1-3: the evaluation of every active member, one copy of the scalars, one wait.  Iteration 0 (launch_lu, a start's
-        // evaluation) is a member's own, and so is everything of a member outside the group launches.
+        // 1-3: the evaluation of every active member and, where detection asks for one, its ray test in the same stage
+        // (kernels.hip: GroupKinds); one copy of the scalars, one wait.  Iteration 0 (launch_lu, a start's evaluation) is a
+        // member's own, and so is everything of a member outside the group launches, its ray test included.
         for (int k = 0; k < count; ++k) {
             if (!active[k]) continue;
             if (in_group(k)) {
                 s[k]->loop_enqueue_evaluation(&ls[k], &gl);
                 ++gc.served;
+                if (s[k]->loop_enqueue_ray(&ls[k], &gl)) ++gc.ray_served;
             }
             gl.pack(s[k]->scal.p, s[k]->scal_h.p);
         }
         gc.group_launches += gl.run(scope.group);
         for (int k = 0; k < count; ++k) {
-            if (!active[k]) continue;
-            if (in_group(k)) {
-                if (s[k]->loop_enqueue_ray(&ls[k])) ++gc.own;  // (between the group's kernels and the group's copy)
-            } else {
-                s[k]->loop_enqueue_evaluation(&ls[k], nullptr, false);
-                ++gc.own;
-            }
+            if (!active[k] || in_group(k)) continue;
+            s[k]->loop_enqueue_evaluation(&ls[k], nullptr, false);  // (between the group's kernels and the group's copy)
+            ++gc.own;
         }
         run_fetch_wait(gl, scope.group, gc);
         ++gc.rounds;
         // 4: every member's status and restart flag; finished members drop out
         flagged.clear();
+        verdicts.clear();
         for (int k = 0; k < count; ++k) {
             if (!active[k]) continue;
             ++s[k]->fetches;
             if (!s[k]->loop_status(&ls[k])) {
-                s[k]->loop_finish(&ls[k]);
                 active[k] = 0;
                 --left;
+                if (ls[k].verdict && joins[k]) {
+                    verdicts.push_back(k);  // (finished below, once the group's block is back)
+                    continue;
+                }
+                if (ls[k].verdict) ++gc.own;
+                s[k]->loop_certificate(&ls[k]);
+                s[k]->loop_finish(&ls[k]);
                 continue;
             }
             if (ls[k].restarted) flagged.push_back(k);
+        }
+        if (!verdicts.empty()) {
+            // 4b: the certificates of this round's verdicts among the joining members: the raw arrays of all of them into one
+            // device block (copies, and A^T y_s by the plain product straight into it), one copy, one wait, then each member's own
+            // finish_certificate and un-permutation
+            cm.assign(static_cast<size_t>(count), PackMember());
+            for (int k : verdicts) cm[k].m = s[k]->m_loc, cm[k].n = s[k]->n_loc, cm[k].cert = ls[k].verdict;
+            const GroupPackLayout L = group_pack_layout(cm.data(), count);
+            if (cert_d.n < L.cert_doubles) {
+                cert_d.alloc(2 * L.cert_doubles);
+                cert_h.alloc(2 * L.cert_doubles, false);
+            }
+            auto dev = [&](size_t off) { return off == kPackAbsent ? nullptr : cert_d.p + off; };
+            auto host = [&](size_t off) { return off == kPackAbsent ? nullptr : cert_h.p + off; };
+            for (int k : verdicts) {
+                const PackSlot &p = L.slot[k];
+                s[k]->certificate_launch(ls[k].verdict, dev(p.cert_rn), dev(p.cert_cn), dev(p.cert_ray), dev(p.cert_aty), &gl);
+            }
+            gc.group_launches += gl.run(scope.group);
+            HIP_CHECK(hipMemcpyAsync(cert_h.p, cert_d.p, sizeof(double) * L.cert_doubles, hipMemcpyDeviceToHost, scope.group));
+            ++gc.copies;
+            HIP_CHECK(hipStreamSynchronize(scope.group));
+            ++gc.waits;
+            for (int k : verdicts) {
+                const PackSlot &p = L.slot[k];
+                s[k]->certificate_consume(ls[k].verdict, ls[k].verdict_iter, host(p.cert_rn), host(p.cert_cn), host(p.cert_ray), host(p.cert_aty));
+                ++gc.certs_served;
+                s[k]->loop_finish(&ls[k]);
+            }
         }
         if (!flagged.empty()) {
             // 5-6: movement of the flagged members

@@ -8,9 +8,11 @@ namespace hprlp {
 // what a run_many call did: evaluation rounds; host waits (one per round + two per round with a restart); launches of the normal
 // iterations; group launches of every kind (those, the group forms of the regular kernels, the packing of the scalars); copies of
 // the scalars to the host; operations issued for ONE member (an own evaluation -- iteration 0, a member outside the group launches
-// --, ray test, check step or restart piece); member-evaluations served by group launches
+// --, check step, restart piece, the ray test or the certificate of a member outside the group launches); member-evaluations
+// served by group launches; member ray tests served by group launches; certificates collected through the group's block (each
+// round with such a verdict adds one wait and one copy to the counts above)
 struct GroupCounts {
-    long rounds = 0, waits = 0, launches = 0, group_launches = 0, copies = 0, own = 0, served = 0;
+    long rounds = 0, waits = 0, launches = 0, group_launches = 0, copies = 0, own = 0, served = 0, ray_served = 0, certs_served = 0;
 };
 
 // what a group set-up, scaling or teardown did (hprlp_last_setup_many_counts; each call fills its own slots): calls to the driver
@@ -40,7 +42,13 @@ void iterate_many(Solver **s, int count, const int *normal, bool then_check);
 void residuals_many(Solver **s, int count, const int *iter, const int *compute_gap, double *out);
 // Solver::update_sigma_and_restart for every member from in[6 * k ..] as hprlp_solver_restart; sigma_out (optional): the new sigmas
 void restart_many(Solver **s, int count, const double *in, double *sigma_out);
-// Solver::solve_loop + collect_solution for every member, from its current state
+// hprlp_solver_ray_step for every member: the evaluation with the gap, then the ray test, one copy of the scalars and one wait,
+// through the group launches for the members that join.  tested[k]: 1 or 0 as that entry's return value; out + 9 k is untouched
+// where it is 0.  The members have passed check_group and the arrays are not null (abi.cpp owns those refusals); throws before
+// anything is launched for a first step without restart[k].
+void ray_step_many(Solver **s, int count, const int *restart, double *out, int *tested);
+// Solver::solve_loop + collect_solution for every member, from its current state.  With detection on, the ray tests and the
+// certificates of the members that join are the group's (DESIGN.md "Many small LPs", group detection).
 void run_many(Solver **s, int count, HPRLP_results *out, GroupCounts *counts = nullptr);
 
 // ---- group re-solve (DESIGN.md "Many small LPs", group re-solve) ------------------------------------------------------------

@@ -2024,7 +2024,7 @@ static int next_event(int iter, int check_iter, int max_iter) {
     }
 }
 
-void Solver::loop_begin(LoopState *ls, HPRLP_results *out) {
+void Solver::loop_begin(LoopState *ls, HPRLP_results *out, GroupLaunches *g) {
     *ls = LoopState();
     ls->t_loop = time_now();
     // reported `time` includes the power iteration (HPRLP.cu:150); a re-solve ran none and counts its set_data instead
@@ -2037,7 +2037,7 @@ void Solver::loop_begin(LoopState *ls, HPRLP_results *out) {
     *out = HPRLP_results();
     trace_n = 0;
     cert = Certificate();
-    if (detect.on) ray_begin();
+    if (detect.on) ray_begin(g);
 }
 
 void Solver::loop_enqueue_evaluation(LoopState *ls, GroupLaunches *g, bool fetch) {
@@ -2050,9 +2050,9 @@ void Solver::loop_enqueue_evaluation(LoopState *ls, GroupLaunches *g, bool fetch
     if (fetch) fetch_enqueue();
 }
 
-bool Solver::loop_enqueue_ray(LoopState *ls) {
+bool Solver::loop_enqueue_ray(LoopState *ls, GroupLaunches *g) {
     if (!(detect.on && ls->periodic && ls->iter > 0)) return false;
-    ls->ray = ray_test();  // (its scalars ride on the copy that follows)
+    ls->ray = ray_test(g);  // (its scalars ride on the copy that follows)
     return true;
 }
 
@@ -2106,11 +2106,15 @@ bool Solver::loop_status(LoopState *ls) {
     mark(ls->first6, 1e-6, out->iter6, out->time6, "1e-6");
     mark(ls->first8, 1e-8, out->iter8, out->time8, "1e-8");
     if (status != "CONTINUE") {
-        if (verdict && status != "OPTIMAL") collect_certificate(verdict, iter);
+        if (verdict && status != "OPTIMAL") ls->verdict = verdict, ls->verdict_iter = iter;  // (collected by loop_certificate)
         return false;
     }
     ls->restarted = rs.flag > 0;
     return true;
+}
+
+void Solver::loop_certificate(LoopState *ls) {
+    if (ls->verdict) collect_certificate(ls->verdict, ls->verdict_iter);
 }
 
 void Solver::loop_movement(LoopState *, GroupLaunches *g) { movement_launch(g); }
@@ -2138,7 +2142,10 @@ void Solver::loop_plan(LoopState *ls) {
 bool Solver::loop_event(LoopState *ls) {
     loop_enqueue_evaluation(ls);
     fetch_wait();
-    if (!loop_status(ls)) return false;
+    if (!loop_status(ls)) {
+        loop_certificate(ls);
+        return false;
+    }
     if (ls->restarted) {
         loop_movement(ls);
         fetch_scalars();
@@ -2220,18 +2227,24 @@ void Solver::solution_launch(double *xo, double *yo, double *zo, GroupLaunches *
 // infeasibility detection (DESIGN.md "Infeasibility and unboundedness"): Farkas ratio tests on the difference of the projected
 // iterates between two periodic evaluations, in the caller's units.  Single GPU only (abi.cpp refuses sharded solvers).
 // ------------------------------------------------------------------------------------------------
-void Solver::ray_begin() {
+void Solver::ray_begin(GroupLaunches *g) {
     if (comm) throw std::runtime_error("infeasibility detection runs on one GPU only (sharded solver)");
     if (!ray_prev_x.p) {
-        ray_prev_x.alloc_zero(static_cast<size_t>(n_loc));
-        ray_prev_y.alloc_zero(static_cast<size_t>(m_loc));
-        ray_d.alloc_zero(static_cast<size_t>(n_pad));  // gathered by the ray SpMVs: full padded length
-        ray_y.alloc_zero(static_cast<size_t>(m_pad));
+        // (g: fills of +0.0, the bits of the memsets, run by the group's launch ahead of the first evaluation)
+        auto zeroed = [&](DBuf<double> &b, int len) {
+            if (!g) return b.alloc_zero(static_cast<size_t>(len));
+            b.alloc(static_cast<size_t>(len));
+            g->fill(b.p, 0.0, len);
+        };
+        zeroed(ray_prev_x, n_loc);
+        zeroed(ray_prev_y, m_loc);
+        zeroed(ray_d, n_pad);  // gathered by the ray SpMVs: full padded length
+        zeroed(ray_y, m_pad);
     }
     ray_have_prev = false;
 }
 
-bool Solver::ray_test() {
+bool Solver::ray_test(GroupLaunches *rec) {
     finish_tiling();
     const int gx = AT.view.grid(), gyy = A.view.grid();
     const size_t need = static_cast<size_t>(kRayFormAccs) * kReduceBlocks + 2 * static_cast<size_t>(gx) + gyy;
@@ -2239,7 +2252,8 @@ bool Solver::ray_test() {
     double *pf = ray_part.p, *pc = pf + static_cast<size_t>(kRayFormAccs) * kReduceBlocks, *pr = pc + 2 * static_cast<size_t>(gx);
     const RayFormArgs a{n_loc, m_loc, x_bar, y_bar, ray_prev_x.p, ray_prev_y.p, ray_d.p, ray_y.p, l.p, u.p, c.p, col_norm.p,
                         AL.p, AU.p, row_norm.p, b_scale, c_scale};
-    launch_ray_form(a, pf, kReduceBlocks, stream);
+    if (rec) rec->ray_form(a, pf);
+    else launch_ray_form(a, pf, kReduceBlocks, stream);
     if (!ray_have_prev) {  // first periodic evaluation: only the stored iterate
         ray_have_prev = true;
         return false;
@@ -2247,15 +2261,22 @@ bool Solver::ray_test() {
     FinalizeArgs f{};
     const int form_slots[kRayFormAccs] = {S_RAY_DY, S_RAY_CD, S_RAY_VY, S_RAY_WD, S_RAY_YN, S_RAY_DN};
     for (int k = 0; k < kRayFormAccs; ++k) f.item[f.n++] = {pf + static_cast<size_t>(k) * kReduceBlocks, kReduceBlocks, form_slots[k], k >= 2};
-    launch_finalize(f, scal.p, stream);
+    if (rec) rec->finalize(f, scal.p);
+    else launch_finalize(f, scal.p, stream);
     invalidate_far();  // the ray SpMVs refill the remainder buffers
-    launch_ray_col(AT.view, ray_y.p, l.p, u.p, col_norm.p, b_scale, c_scale, pc, stream);
-    launch_ray_row(A.view, ray_d.p, AL.p, AU.p, row_norm.p, b_scale, pr, stream);
+    if (rec) {
+        rec->ray_col(AT.view, ray_y.p, l.p, u.p, col_norm.p, b_scale, c_scale, pc);
+        rec->ray_row(A.view, ray_d.p, AL.p, AU.p, row_norm.p, b_scale, pr);
+    } else {
+        launch_ray_col(AT.view, ray_y.p, l.p, u.p, col_norm.p, b_scale, c_scale, pc, stream);
+        launch_ray_row(A.view, ray_d.p, AL.p, AU.p, row_norm.p, b_scale, pr, stream);
+    }
     FinalizeArgs g{};
     g.item[g.n++] = {pc, gx, S_RAY_DZ, 0};
     g.item[g.n++] = {pc + gx, gx, S_RAY_VZ, 1};
     g.item[g.n++] = {pr, gyy, S_RAY_WQ, 1};
-    launch_finalize(g, scal.p, stream);
+    if (rec) rec->finalize(g, scal.p);
+    else launch_finalize(g, scal.p, stream);
     return true;
 }
 
@@ -2288,6 +2309,37 @@ void Solver::collect_certificate(int kind, int iter) {
     }
     HIP_CHECK(hipStreamSynchronize(stream));
     finish_certificate(&cert, kind, iter, ray_scalars(), rn.data(), cn.data(), b_scale, c_scale);
+    unpermute(cert.y, perm_r);
+    unpermute(cert.z, perm_c);
+    unpermute(cert.d, perm_c);
+}
+
+void Solver::certificate_launch(int kind, double *rn, double *cn, double *ray, double *aty, GroupLaunches *g) {
+    g->copy(cn, col_norm.p, n_loc);
+    if (kind == 1) {
+        invalidate_far();
+        g->copy(rn, row_norm.p, m_loc);
+        g->copy(ray, ray_y.p, m_loc);
+        g->spmv_plain(AT.view, ray_y.p, aty);  // A^T y_s straight into the block
+    } else {
+        g->copy(ray, ray_d.p, n_loc);
+    }
+}
+
+void Solver::certificate_consume(int kind, int iter, const double *rn, const double *cn, const double *ray, const double *aty) {
+    cert = Certificate();
+    auto unpermute = [](std::vector<double> &v, const std::vector<int> &perm) {  // (collect_certificate's)
+        if (perm.empty() || v.empty()) return;
+        const std::vector<double> tmp(v);
+        for (size_t i = 0; i < perm.size(); ++i) v[perm[i]] = tmp[i];
+    };
+    if (kind == 1) {
+        cert.y.assign(ray, ray + m_loc);
+        cert.z.assign(aty, aty + n_loc);
+    } else {
+        cert.d.assign(ray, ray + n_loc);
+    }
+    finish_certificate(&cert, kind, iter, ray_scalars(), rn, cn, b_scale, c_scale);
     unpermute(cert.y, perm_r);
     unpermute(cert.z, perm_c);
     unpermute(cert.d, perm_c);

@@ -96,6 +96,7 @@ struct LoopState {
     int pending = -1;        // normal iterations before the next check step (loop_advance); < 0: no check step either
     bool restarted = false;  // the last event restarted (its check step and weighted norm have run)
     bool periodic = false, at_limit = false, ray = false;  // of the evaluation in flight
+    int verdict = 0, verdict_iter = 0;  // loop_status: the verdict that ended the loop (0: none), for loop_certificate
     int check_iter = 1, max_iter = 0;
     double t_before = 0.0;   // what the reported times start from
     clock_type::time_point t_loop;
@@ -183,10 +184,19 @@ struct Solver {
     DBuf<double> ray_prev_x, ray_prev_y, ray_d, ray_y, ray_part;
     bool ray_have_prev = false;
     Certificate cert;  // of the last solve_loop (kind 0: no verdict)
-    void ray_begin();              // solve_loop: buffers allocated (first time) and the previous iterate forgotten
-    bool ray_test();               // enqueue the rays' kernels and reductions; false at the first evaluation (no previous iterate yet)
+    // solve_loop: buffers allocated (first time) and the previous iterate forgotten.  g: the first-time zeroing is recorded as
+    // fills of +0.0 (the bits of the memset) instead of four synchronous memsets
+    void ray_begin(GroupLaunches *g = nullptr);
+    // enqueue the rays' kernels and reductions; false at the first evaluation (no previous iterate yet).  g: the form, the two
+    // SpMVs and the nine finalize items recorded (a first test records the form only)
+    bool ray_test(GroupLaunches *g = nullptr);
     RayScalars ray_scalars();      // after fetch_scalars: the ratio tests' sums of the last ray_test
     void collect_certificate(int kind, int iter);
+    // collect_certificate in the pieces a group call walks (many.cpp: loop_many): the raw arrays recorded into the member's ranges
+    // of the group's block (kind 1: row_norm, col_norm, ray_y and A^T y_s by the plain product; kind 2: col_norm, ray_d; the
+    // pointers a kind does not use are null), then, once the block is on the host, finish_certificate and the un-permutation
+    void certificate_launch(int kind, double *rn, double *cn, double *ray, double *aty, GroupLaunches *g);
+    void certificate_consume(int kind, int iter, const double *rn, const double *cn, const double *ray, const double *aty);
 
     // Warm start (DESIGN.md "Warm start"): after init_iteration_state(), before solve_loop().  x0 (n) / y0 (m): the caller's point
     // in the caller's units and numbering (host memory, either may be null: zeros), every entry finite.  Projects it, writes it
@@ -321,18 +331,21 @@ struct Solver {
     bool joins_group();
     void solve_loop(HPRLP_results *out);                            // src/HPRLP.cu:154-310
     // the pieces of solve_loop (LoopState)
-    void loop_begin(LoopState *ls, HPRLP_results *out);
+    void loop_begin(LoopState *ls, HPRLP_results *out, GroupLaunches *g = nullptr);  // (g: ray_begin's zeroing recorded)
     // first half of an event: the evaluation of the current iterate, not waited for.  g: kernels and finalize recorded, nothing
     // else; fetch = false: without the copy of the scalars (a group's copy carries them)
     void loop_enqueue_evaluation(LoopState *ls, GroupLaunches *g = nullptr, bool fetch = true);
-    bool loop_enqueue_ray(LoopState *ls);         // the ray test of that evaluation where detection asks for one (true: enqueued)
+    // the ray test of that evaluation where detection asks for one (true: enqueued, or recorded into g)
+    bool loop_enqueue_ray(LoopState *ls, GroupLaunches *g = nullptr);
     // second half, after the wait, in pieces that end where the host has to wait for scalars:
-    //   loop_status    status, marks, restart decision.  false: finished (ls->status says how); true: ls->restarted says whether the
-    //                  two pieces below run
+    //   loop_status    status, marks, restart decision.  false: finished (ls->status says how; a verdict is noted in
+    //                  ls->verdict and collected by loop_certificate); true: ls->restarted says whether the two pieces below run
+    //   loop_certificate  a noted verdict's certificate: collect_certificate (its copies and its wait)
     //   loop_movement  the movement and its norms enqueued                                  [wait]
     //   loop_restart   the sigma rule, restart copy, ctrl, check step, gap enqueued         [wait]
     //   loop_plan      a restart's weighted norm consumed; ls->pending and ls->iter say what runs next
     bool loop_status(LoopState *ls);
+    void loop_certificate(LoopState *ls);
     void loop_movement(LoopState *ls, GroupLaunches *g = nullptr);
     void loop_restart(LoopState *ls, GroupLaunches *g = nullptr);
     void loop_plan(LoopState *ls);

@@ -245,6 +245,10 @@ def lib():
         L.hprlp_solver_residuals_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, c_int_p, c_int_p, c_dbl_p]
         L.hprlp_solver_restart_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, c_dbl_p, c_dbl_p]
         L.hprlp_last_run_many_counts.argtypes = [C.POINTER(C.c_long)]
+    if hasattr(L, "hprlp_solve_many_detect"):  # (likewise: the A side of tools/many_detect_ab.py)
+        L.hprlp_solve_many_detect.argtypes = [C.POINTER(C.POINTER(CLPInfo)), C.c_int, C.POINTER(CParameters), C.POINTER(CDetection),
+                                              C.POINTER(CResults), C.POINTER(CCertificate)]
+        L.hprlp_solver_ray_step_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, c_int_p, c_dbl_p, c_int_p]
     if hasattr(L, "hprlp_solver_create_many"):  # (likewise)
         L.hprlp_solver_create_many.argtypes = [C.POINTER(C.POINTER(CLPInfo)), C.c_int, C.POINTER(CParameters), C.POINTER(C.c_void_p)]
         L.hprlp_solver_scale_many.argtypes = [C.POINTER(C.c_void_p), C.c_int]
@@ -577,6 +581,27 @@ def solve_many(models, param=None):
     return [Results(res[k], mod.m, mod.n) for k, mod in enumerate(models)]
 
 
+def solve_many_detect(models, param=None, eps_primal=1e-8, eps_dual=1e-8):
+    """solve_many with infeasibility detection on for every member (hprlp_solve_many_detect).  Returns (results, certificates):
+    one Results and one Certificate per model; kind 0 where the member reached no verdict.  eps_primal=None and eps_dual=None:
+    detection off (exactly solve_many)."""
+    models = list(models)
+    if not models:
+        raise ValueError("solve_many_detect: no models")
+    cp = (param or Parameters()).to_c()
+    det = _detection_arg(eps_primal, eps_dual)
+    ptrs = (C.POINTER(CLPInfo) * len(models))(*[mod._ptr for mod in models])
+    res = (CResults * len(models))()
+    ccs = (CCertificate * len(models))()
+    if lib().hprlp_solve_many_detect(ptrs, len(models), C.byref(cp), C.byref(det) if det is not None else None, res, ccs) < 0:
+        raise RuntimeError(last_error())
+    results = [Results(res[k], mod.m, mod.n) for k, mod in enumerate(models)]
+    certificates = [Certificate(ccs[k]) for k in range(len(models))]
+    for r, k in zip(results, certificates):
+        r.certificate = k
+    return results, certificates
+
+
 def last_solve_many_phases():
     """Phases of this thread's last solve_many (hprlp_last_solve_many_phases): seconds, then the loop's counts."""
     out = np.zeros(8)
@@ -586,10 +611,21 @@ def last_solve_many_phases():
 
 
 def last_run_many_counts():
-    """Counts of this thread's last Solver.run_many / solve_many (hprlp_last_run_many_counts)."""
+    """Counts of this thread's last Solver.run_many / solve_many (hprlp_last_run_many_counts); the two counts of the group
+    detection are in last_run_many_detect_counts()."""
     out = (C.c_long * 8)()
     lib().hprlp_last_run_many_counts(out)
     keys = ("rounds", "waits", "group_launches", "copies", "own", "served")
+    return dict(zip(keys, [int(v) for v in out]))
+
+
+def last_run_many_detect_counts():
+    """All eight slots of hprlp_last_run_many_counts after Solver.run_many / solve_many / solve_many_detect: the six of
+    last_run_many_counts(), then the member ray tests served by group launches and the certificates collected through the
+    group's block (a library of an earlier commit reports 0 for both)."""
+    out = (C.c_long * 8)()
+    lib().hprlp_last_run_many_counts(out)
+    keys = ("rounds", "waits", "group_launches", "copies", "own", "served", "ray_served", "certs_served")
     return dict(zip(keys, [int(v) for v in out]))
 
 
@@ -1420,6 +1456,28 @@ class Solver:
         r = dict(zip(self.RAY_SLOTS, (float(v) for v in out)))
         r.update(D=r["DY"] + r["DZ"], V=max(r["VY"], r["VZ"]), cd=r["CD"], W=max(r["WD"], r["WQ"]), yn=r["YN"], dn=r["DN"])
         return r
+
+    @staticmethod
+    def ray_step_many(solvers, restart):
+        """ray_step(restart[k]) of every solver with one fetch for the group (hprlp_solver_ray_step_many).  Returns one entry per
+        solver: None where only the iterate was stored, else ray_step's dict."""
+        solvers, hs = Solver._handles(solvers)
+        K = len(solvers)
+        flags = np.ascontiguousarray([1 if f else 0 for f in restart], dtype=np.int32)
+        if flags.shape[0] != K:
+            raise ValueError("ray_step_many: one restart flag per solver")
+        out, tested = np.zeros(9 * max(K, 1)), np.zeros(max(K, 1), np.int32)
+        if lib().hprlp_solver_ray_step_many(hs, K, flags.ctypes.data_as(c_int_p), out.ctypes.data_as(c_dbl_p), tested.ctypes.data_as(c_int_p)) < 0:
+            raise RuntimeError(last_error())
+        res = []
+        for k in range(K):
+            if not tested[k]:
+                res.append(None)
+                continue
+            r = dict(zip(Solver.RAY_SLOTS, (float(v) for v in out[9 * k:9 * k + 9])))
+            r.update(D=r["DY"] + r["DZ"], V=max(r["VY"], r["VZ"]), cd=r["CD"], W=max(r["WD"], r["WQ"]), yn=r["YN"], dn=r["DN"])
+            res.append(r)
+        return res
 
     def set_start(self, x=None, y=None):
         """Warm start of the next run() (hprlp_solver_set_start): after init(), in the model's units and numbering."""

@@ -347,7 +347,10 @@ int hprlp_batched_solver_set_matrix_values(hprlp_batched_solver *h, const double
  * hprlp_solver_run_many has one wait, three if some member restarts in it, and a number of launches that does not depend on the
  * count.  The stopping test, restart rule, sigma update and detection stay the member's own host code, so every member gets the
  * bits it gets alone.  Members off the small path are legal (they issue their own launches inside the same lock-step), and a
- * member's iteration-0 evaluation (hprlp_solver_resolve_many apart) and ray tests are always its own.  The group runs quietly (hprlp_solver_set_verbose is ignored).
+ * member's iteration-0 evaluation (hprlp_solver_resolve_many apart) is always its own.  With detection on, the ray tests of the
+ * members that join ride in the evaluation's launches (three kernels more per periodic round, whatever the count, and no wait),
+ * and the certificates of a round's verdicts come back through one device block, one copy and one wait; a member outside the
+ * group launches keeps its own ray test and certificate.  The group runs quietly (hprlp_solver_set_verbose is ignored).
  * All of them return 0, or -1 + hprlp_last_error(); nothing is launched when the arguments are wrong: a NULL pointer, count <= 0,
  * the same handle twice, a sharded solver (hprlp_solver_create_dist* / _local*), a solver that was never scaled, members on
  * different devices, a negative normal[k] or iter[k]. */
@@ -369,6 +372,19 @@ int hprlp_solver_run_many(hprlp_solver **s, int count, HPRLP_results *out);
  * together (lambda x 1.01), the loop together, solutions, hprlp_solver_destroy_many.  NO presolve on this path: param->use_presolve is ignored, as in
  * solve_batched.  A model that fails its set-up gets status "ERROR" (and hprlp_last_error() names it); the others are solved. */
 int hprlp_solve_many(const LP_info_cpu *const *models, int count, const HPRLP_parameters *param, HPRLP_results *out);
+/* hprlp_solve_many with infeasibility detection on for every member (hprlp_solve_detect's twin; no presolve, as on the whole
+ * path).  det == NULL: exactly hprlp_solve_many.  certs (count entries, may be NULL): certs[k] always gets the member's m and n,
+ * and kind 0 unless the member reached a verdict (status PRIMAL_INFEASIBLE / DUAL_INFEASIBLE); each entry is released with
+ * hprlp_free_certificate.  A member whose set-up fails keeps status "ERROR" and kind 0.  A negative eps is refused before
+ * anything is created. */
+int hprlp_solve_many_detect(const LP_info_cpu *const *models, int count, const HPRLP_parameters *param, const hprlp_detection *det,
+                            HPRLP_results *out, hprlp_certificate *certs);
+/* hprlp_solver_ray_step for every member: the evaluation with the gap, then the ray test, one fetch for the whole group, through
+ * the group launches for the members that join.  restart[k] as that entry's restart; tested[k] = 1 or 0 as its return value;
+ * out[9 * k .. 9 * k + 9) as its out, untouched where tested[k] is 0.  The members' detection settings are not touched.  Refused
+ * before anything is launched, naming the entry point and `member k`: the group rules above, NULL arrays, a first step of a
+ * member without restart[k]. */
+int hprlp_solver_ray_step_many(hprlp_solver **s, int count, const int *restart, double *out /* 9 x count */, int *tested /* count */);
 /* Group form of creation, scaling and destruction: every member ends bit for bit the solver that hprlp_solver_create +
  * hprlp_solver_scale give it alone.  The members of a _create_many call whose set-up only allocates and uploads (Netlib-scale
  * models) share one arena -- a few device blocks, one pinned block, one stream, one copy per block -- which goes when the last
@@ -394,8 +410,9 @@ int  hprlp_arena_selftest(void);
 int hprlp_last_solve_many_phases(double out[8]);
 /* Counts of the calling thread's last hprlp_solver_run_many / hprlp_solve_many: out = {evaluation rounds, host waits, group
  * launches of every kind (normal iterations, check, evaluation, restart, packing of the scalars), copies of the scalars to the host,
- * operations issued for ONE member (an own evaluation, ray test, check step or restart piece), member-evaluations served by group
- * launches, 0, 0} */
+ * operations issued for ONE member (an own evaluation, check step or restart piece; the ray test or the certificate of a member
+ * outside the group launches), member-evaluations served by group launches, member ray tests served by group launches,
+ * certificates collected through the group's block (a round with such a verdict adds one wait and one copy)} */
 int hprlp_last_run_many_counts(long out[8]);
 
 /* ---- group re-solve: new data, starts and solutions for the whole group (DESIGN.md "Many small LPs", group re-solve) ----------
@@ -406,8 +423,8 @@ int hprlp_last_run_many_counts(long out[8]);
  * kernel for all members that join (small path, stream kernel alone, no locality ordering, bound-code arrays in place; two at
  * least), and the host waits once per call outside the loop -- none of it grows with the count.  Every member ends bit for bit
  * where its own call leaves it (the rule of the group launches: a workgroup runs the single kernel's code as workgroup lb of its
- * member's own grid).  A member that cannot join runs its own set_data / resolve pieces inside the same call; ray tests stay a
- * member's own.  Refusals (-1 + hprlp_last_error(), naming the entry point and `member k`) come before anything is written or
+ * member's own grid).  A member that cannot join runs its own set_data / resolve pieces inside the same call; the ray tests
+ * and certificates of the loop are the group's as in hprlp_solver_run_many.  Refusals (-1 + hprlp_last_error(), naming the entry point and `member k`) come before anything is written or
  * launched for any member: the group rules above, NULL data / out, an incomplete bounds group, a NaN in a data vector or
  * obj_constant, a NaN sigma, a non-finite start entry. */
 typedef struct hprlp_member_data {   /* hprlp_solver_set_data's arguments for one member; all NULL: nothing changes */
