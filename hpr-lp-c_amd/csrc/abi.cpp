@@ -1543,6 +1543,83 @@ extern "C" int hprlp_solver_set_matrix_values_many(hprlp_solver **h, int count, 
     GUARD_END(-1)
 }
 
+// ---- group device re-solve (DESIGN.md "Many small LPs", group device re-solve): the three group entries with the vectors in device
+// memory.  ResolveCounts / ValuesCounts go where the host entries put theirs; what only a device call has is kept here.
+static thread_local DeviceCounts g_device_counts;
+
+extern "C" int hprlp_last_many_device_counts(long out[8]) {
+    if (!out) return -1;
+    const DeviceCounts &d = g_device_counts;
+    const long v[8] = {d.pointers, d.lookups, d.check_launches, d.flags, d.served, d.own, d.waits_before_write, 0};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return 0;
+}
+
+extern "C" int hprlp_solver_set_data_many_device(hprlp_solver **h, int count, const hprlp_member_data *data, void *stream) {
+    GUARD_BEGIN
+    g_device_counts = DeviceCounts();
+    keep_resolve_counts(ResolveCounts());
+    // (list, count, data, then the members: the order of the refusals)
+    if (!h) throw std::runtime_error("hprlp_solver_set_data_many_device: null solver list");
+    if (count <= 0) throw std::runtime_error("hprlp_solver_set_data_many_device: count must be positive");
+    if (!data) throw std::runtime_error("hprlp_solver_set_data_many_device: null data");
+    std::vector<Solver *> s = group_members(h, count, "hprlp_solver_set_data_many_device");
+    std::vector<MemberData> d(static_cast<size_t>(count));
+    for (int k = 0; k < count; ++k) {
+        d[k].c = data[k].c, d[k].obj_constant = data[k].obj_constant;
+        d[k].AL = data[k].AL, d[k].AU = data[k].AU, d[k].l = data[k].l, d[k].u = data[k].u;
+    }
+    ResolveCounts rc;
+    set_data_many_device(s.data(), count, d.data(), static_cast<hipStream_t>(stream), &rc, &g_device_counts);
+    keep_resolve_counts(rc);
+    return 0;
+    GUARD_END(-1)
+}
+
+extern "C" int hprlp_solver_resolve_many_device(hprlp_solver **h, int count, const hprlp_member_start *start, const hprlp_member_out *dst,
+                                                void *stream, HPRLP_results *out) {
+    GUARD_BEGIN
+    g_device_counts = DeviceCounts();
+    keep_resolve_counts(ResolveCounts());
+    if (!h) throw std::runtime_error("hprlp_solver_resolve_many_device: null solver list");
+    if (count <= 0) throw std::runtime_error("hprlp_solver_resolve_many_device: count must be positive");
+    if (!out) throw std::runtime_error("hprlp_solver_resolve_many_device: null results");
+    std::vector<Solver *> s = group_members(h, count, "hprlp_solver_resolve_many_device");
+    std::vector<MemberStart> b(static_cast<size_t>(count));
+    for (int k = 0; start && k < count; ++k) b[k].x0 = start[k].x0, b[k].y0 = start[k].y0, b[k].sigma = start[k].sigma;
+    std::vector<MemberOut> o(static_cast<size_t>(count));
+    for (int k = 0; dst && k < count; ++k) o[k].x = dst[k].x, o[k].y = dst[k].y, o[k].z = dst[k].z;
+    // (a refusal leaves the output array as it was: the results are touched once the call goes through)
+    std::vector<HPRLP_results> res(static_cast<size_t>(count), make_error_result("ERROR"));
+    ResolveCounts rc;
+    resolve_many_device(s.data(), count, b.data(), o.data(), static_cast<hipStream_t>(stream), res.data(), &rc, &g_device_counts);
+    keep_resolve_counts(rc);
+    for (int k = 0; k < count; ++k) out[k] = res[k];  // (x, y, z are NULL: nothing for hprlp_free_results to free)
+    return 0;
+    GUARD_END(-1)
+}
+
+extern "C" int hprlp_solver_set_matrix_values_many_device(hprlp_solver **h, int count, const hprlp_member_values *data, void *stream) {
+    GUARD_BEGIN
+    g_device_counts = DeviceCounts();
+    keep_values_counts(ValuesCounts());
+    // (list, count, data, then the members: the order of the refusals)
+    if (!h) throw std::runtime_error("hprlp_solver_set_matrix_values_many_device: null solver list");
+    if (count <= 0) throw std::runtime_error("hprlp_solver_set_matrix_values_many_device: count must be positive");
+    if (!data) throw std::runtime_error("hprlp_solver_set_matrix_values_many_device: null data");
+    std::vector<Solver *> s = group_members(h, count, "hprlp_solver_set_matrix_values_many_device");
+    std::vector<MemberValues> d(static_cast<size_t>(count));
+    for (int k = 0; k < count; ++k) {
+        d[k].val = data[k].val, d[k].nnz = data[k].nnz, d[k].c = data[k].c, d[k].obj_constant = data[k].obj_constant;
+        d[k].AL = data[k].AL, d[k].AU = data[k].AU, d[k].l = data[k].l, d[k].u = data[k].u;
+    }
+    ValuesCounts vc;
+    set_matrix_values_many_device(s.data(), count, d.data(), static_cast<hipStream_t>(stream), &vc, &g_device_counts);
+    keep_values_counts(vc);
+    return 0;
+    GUARD_END(-1)
+}
+
 // phases of the calling thread's last hprlp_solve_many (hprlp_last_solve_many_phases)
 static thread_local double g_many_phases[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 

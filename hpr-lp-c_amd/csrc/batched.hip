@@ -1773,7 +1773,8 @@ BatchData device_prep(BatchWS &w, int B, int Bp, const double *C, const double *
 // A pointer of the caller's passes only as device memory of `device` that the runtime knows, with room for `count` doubles where
 // the runtime reports the allocation's range.  Nothing is launched before every pointer of a call has passed.
 // (declared in common.h: the resident solver's device entries check their pointers with it too)
-void check_device_pointer(const void *p, size_t count, int device, const char *name, const char *entry) {
+void check_device_pointer(const void *p, size_t count, int device, const char *name, const char *entry, DeviceRange *range) {
+    if (range) *range = DeviceRange();
     const std::string who = std::string(entry) + ": " + name;
     if (!p) throw std::runtime_error(who + " is null");
     if (reinterpret_cast<uintptr_t>(p) % sizeof(double)) throw std::runtime_error(who + " is not aligned to 8 bytes");
@@ -1795,6 +1796,7 @@ void check_device_pointer(const void *p, size_t count, int device, const char *n
     if (static_cast<const char *>(p) + count * sizeof(double) > end)
         throw std::runtime_error(who + " is too short: " + std::to_string(count) + " doubles wanted, " +
                                  std::to_string((end - static_cast<const char *>(p)) / sizeof(double)) + " left in its allocation");
+    if (range) *range = DeviceRange{static_cast<const char *>(base), size};
 }
 
 // warm-up (abi.cpp: hprlp_warmup): an attribute query makes the runtime load this translation unit's code object now instead

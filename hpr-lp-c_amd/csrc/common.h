@@ -201,7 +201,14 @@ struct HBuf {
 // A caller's device pointer (batched.hip; the device entries of the batched and of the resident solver): passes only as device
 // memory of `device` that the runtime knows, 8-byte aligned, with room for `count` doubles where the runtime reports the
 // allocation's range; throws otherwise, naming `entry: name`.  Launches nothing and moves no state.
-void check_device_pointer(const void *p, size_t count, int device, const char *name, const char *entry = "batched solver");
+// range (optional): the allocation the runtime reported for p -- device memory of `device` from base on, `bytes` long; bytes = 0
+// where it reported none.  A later pointer that lies with its length inside such a range needs no lookup of its own (many.cpp).
+struct DeviceRange {
+    const char *base = nullptr;
+    size_t bytes = 0;
+};
+void check_device_pointer(const void *p, size_t count, int device, const char *name, const char *entry = "batched solver",
+                          DeviceRange *range = nullptr);
 
 // Host-side CSR transpose, stable in row order (reference src/utils.cu:203-232).
 void csr_transpose_host(int rows, int cols, long nnz, const int *rp, const int *ci, const double *v,

@@ -99,7 +99,10 @@ const std::vector<GroupLaunch> &GroupTable::finish() {
 // nothing; 8 the grid rules' workgroup counts; 9 a repeat of stages that were not recorded is refused; 10 the shape of a periodic
 // round with detection (a check step's stage, then the evaluation's stage with the three ray kinds, one of them a lone member's):
 // the launches of the second stage do not depend on the number of tasks, a lone task goes its own way only where its kind says so,
-// and the kinds of a stage are issued in ascending order (the form ahead of the two products that gather what it writes).
+// and the kinds of a stage are issued in ascending order (the form ahead of the two products that gather what it writes); 11 the
+// check stage of a group's device entries (the check of the members' vectors and, for new matrix values, the check of the values:
+// two mapped kinds with one task per member in ONE stage): two launches whatever the number of members, on the sum of the
+// members' own grids, and a group of one issues the member's own two launches and sends no table.
 extern "C" int hprlp_group_table_selftest(void) {
     using namespace hprlp;
     struct Task {
@@ -219,6 +222,22 @@ extern "C" int hprlp_group_table_selftest(void) {
             if (list[i].stage < list[i - 1].stage || (list[i].stage == list[i - 1].stage && list[i].kind <= list[i - 1].kind)) return 10;
         if (list[3].kind != kForm || list[3].own != (members == 1) || (!list[3].own && list[3].nwg != members * 512)) return 10;
         if (!list[4].own || list[5].own || list[5].nwg != 1) return 10;
+    }
+    for (int members = 1; members <= 5; members += 4) {  // ---- 11
+        enum { kDataCheck = 0, kValuesCheck = 1 };
+        GroupTable g(true, 512, 256);
+        g.note(kDataCheck), g.note(kValuesCheck);
+        if (g.recorded_launches() != 2) return 11;
+        g.begin();
+        const int gr[5] = {1, 1, 2, 1, 3};
+        const bool lone = members == 1;
+        g.add(0, kDataCheck, kGridMapped, o5, sizeof(Odd), members, gr, lone);
+        g.add(0, kValuesCheck, kGridMapped, o5, sizeof(Odd), members, gr, lone);
+        const size_t block = g.bytes().size();
+        const std::vector<GroupLaunch> list = g.finish();
+        if (list.size() != 2 || list[0].kind != kDataCheck || list[1].kind != kValuesCheck || list[0].stage != 0 || list[1].stage != 0) return 11;
+        if (list[0].own != lone || list[1].own != lone || (lone ? block != 0 : block == 0)) return 11;
+        if (!lone && (list[0].nwg != 8 || list[1].nwg != 8 || list[0].ntasks != 5 || list[0].tasks == list[1].tasks)) return 11;
     }
     return 0;
 }

@@ -446,6 +446,9 @@ class GroupLaunches {
     // member's staged values into its own flag word, the scatter through the value maps, the gather of the five vectors.
     void values_check(const double *v, long n, unsigned long long *first_bad);
     void values_in(long nnz, const double *stage, const int *mapA, const int *mapAT, double *A_val, double *AT_val);
+    // The group's device entries (DESIGN.md "Many small LPs", group device re-solve): k_data_check on one member's caller vectors
+    // into its own flag word, which the caller has set to kDataCheckClean.  Nothing is recorded where no vector is given.
+    void data_check(const DataCheckArgs &a, unsigned long long *first_bad);
     void vectors_in(const VectorsInArgs &a);
     // Infeasibility detection (DESIGN.md "Many small LPs", group detection): the ray test's three kernels, mirroring launch_ray_*
     // (the form on its kReduceBlocks workgroups), and a verdict's raw arrays into the group's certificate block -- elementwise

@@ -2915,8 +2915,9 @@ void launch_unscale_out(int n, int m, const double *x_bar, const double *y_bar, 
 // (vector, index) of a NaN -- or, for a warm start, of any non-finite entry -- by atomicMin on a word that starts at all ones
 // (k_values_check's rule).  A lane walks each vector in ascending positions and the vectors in order, so its first hit is its
 // smallest; it then stops.
-__global__ void __launch_bounds__(kThreads) k_data_check(DataCheckArgs a, unsigned long long *__restrict__ first_bad) {
-    const int tid = blockIdx.x * kThreads + threadIdx.x, nth = gridDim.x * kThreads;
+// (the body of k_data_check and of its group form: workgroup `bid` of `grid`)
+__device__ __forceinline__ void data_check_body(const DataCheckArgs &a, unsigned long long *__restrict__ first_bad, int bid, int grid) {
+    const int tid = bid * kThreads + threadIdx.x, nth = grid * kThreads;
     unsigned long long mine = kDataCheckClean;
 #pragma unroll
     for (int k = 0; k < kDataCheckVecs; ++k) {
@@ -2929,10 +2930,17 @@ __global__ void __launch_bounds__(kThreads) k_data_check(DataCheckArgs a, unsign
     }
     if (mine != kDataCheckClean) atomicMin(first_bad, mine);
 }
-void launch_data_check(const DataCheckArgs &a, unsigned long long *first_bad, hipStream_t s) {
+__global__ void __launch_bounds__(kThreads) k_data_check(DataCheckArgs a, unsigned long long *__restrict__ first_bad) {
+    data_check_body(a, first_bad, blockIdx.x, gridDim.x);
+}
+static int data_check_longest(const DataCheckArgs &a) {
     int longest = 0;
     for (int k = 0; k < kDataCheckVecs; ++k)
         if (a.v[k] && a.len[k] > longest) longest = a.len[k];
+    return longest;
+}
+void launch_data_check(const DataCheckArgs &a, unsigned long long *first_bad, hipStream_t s) {
+    const int longest = data_check_longest(a);
     if (longest <= 0) return;
     hipLaunchKernelGGL(k_data_check, dim3(vec_grid(longest)), dim3(kThreads), 0, s, a, first_bad);
 }
@@ -3180,6 +3188,17 @@ struct ValuesCheckTask {  // k_values_check on one member's staged values; first
     int own_grid() const { return grid; }
     void own(hipStream_t s) const { launch_values_check(v, n, first_bad, s); }
 };
+// The device check of a group's device entries (DESIGN.md "Many small LPs", group device re-solve; many.cpp): k_data_check on one
+// member's caller vectors, where they lie; first_bad: the member's own flag word in the group's block.
+struct DataCheckTask {
+    static constexpr GridRule rule = kGridMapped;
+    DataCheckArgs a;
+    unsigned long long *first_bad;
+    int grid;  // of the member's own launch (vec_grid of the longest vector)
+    __device__ void run(int lb) const { data_check_body(a, first_bad, lb, grid); }
+    int own_grid() const { return grid; }
+    void own(hipStream_t s) const { launch_data_check(a, first_bad, s); }
+};
 struct ValuesInTask {  // k_values_in
     static constexpr GridRule rule = kGridMapped;
     long nnz;
@@ -3333,12 +3352,15 @@ struct KindList {
 // stage: in front of the form either way.  A verdict's certificate is a run of its own (the loop has consumed the round's scalars):
 // the copies read row_norm, col_norm, ray_y and ray_d, the plain product reads the matrix and ray_y, and both write only the
 // group's certificate block, every task its own range.
-// The three kinds of the values line stand in front of everything.  set_matrix_values_many records the scatter, the gather and the
+//   group device entries:  the check of the callers' vectors where they lie (a run of its own, as the check of the staged values and,
+//             for new matrix values from device memory, in one stage with it: both read the caller's buffers and write only their
+//             own member's flag word, so their order is no statement).
+// The three kinds of the values line stand in front of everything but that check.  set_matrix_values_many records the scatter, the gather and the
 // zeroing fills of Solver::reset_iterates in ONE stage: the scatter reads the staging block and the maps and writes A_val and
 // AT_val, the gather reads the staging block and writes AL, AU, l, u and c, the fills write the iterates, the work vectors, the
 // scalars and ctrl -- three disjoint sets of arrays, none of which another of the three reads, so their order is no statement
 // either; scaling, which reads all of them, begins a stage later.
-using GroupKinds = KindList<ValuesCheckTask, ValuesInTask, VectorsInTask, RowNormTask<false>, RowNormTask<true>, GroupTask<CrEpi>, VecTask, CodesTask<false>, CodesTask<true>, RestartCopyTask, SetCtrlTask,
+using GroupKinds = KindList<DataCheckTask, ValuesCheckTask, ValuesInTask, VectorsInTask, RowNormTask<false>, RowNormTask<true>, GroupTask<CrEpi>, VecTask, CodesTask<false>, CodesTask<true>, RestartCopyTask, SetCtrlTask,
                             StartInTask, GroupTask<StartColEpi>, GroupTask<StartRowEpi>, GroupTask<XEpi<true>>, GroupTask<YEpi<true>>,
                             GroupTask<RdEpi>, GroupTask<RpEpi<false>>, GroupTask<RpEpi<true>>, GroupTask<GapEpi>, RayFormTask, GroupTask<RayColEpi>,
                             GroupTask<RayRowEpi>, CopyTask, GroupTask<PlainEpi<false>>, LuTask, MovementTask, DataInTask, DataBcTask, UnscaleTask, ScaleMat<0>, ScaleMat<1>, ScaleMat<2>, ScaleMat<3>, ScaleMat<4>, ScaleMat<5>, ScaleMat<6>,
@@ -3499,6 +3521,10 @@ void GroupLaunches::cr_log_update(const CsrDev &M, const double *other_full, dou
 }
 void GroupLaunches::values_check(const double *v, long n, unsigned long long *first_bad) {
     if (n > 0) impl->rec<ValuesCheckTask>().push_back({v, n, first_bad, static_cast<int>(grid_stride_blocks(n))});
+}
+void GroupLaunches::data_check(const DataCheckArgs &a, unsigned long long *first_bad) {
+    const int longest = data_check_longest(a);
+    if (longest > 0) impl->rec<DataCheckTask>().push_back({a, first_bad, vec_grid(longest)});
 }
 void GroupLaunches::values_in(long nnz, const double *stage, const int *mapA, const int *mapAT, double *A_val, double *AT_val) {
     if (nnz > 0) impl->rec<ValuesInTask>().push_back({nnz, stage, mapA, mapAT, A_val, AT_val, static_cast<int>(grid_stride_blocks((nnz + 1) / 2))});

@@ -10,13 +10,15 @@
 // (Solver::joins_group) issues its own launches inside the same lock-step; so does every member for its iteration-0 evaluation
 // (resolve_many apart: the group re-solve further down).  The ray tests of the infeasibility detection and the certificates of the
 // members that join are the group's as well (DESIGN.md "Many small LPs", group detection).  New matrix values for the whole group
-// (set_matrix_values_many) are at the end of this file; they share scale_many's walk of Solver::scale() (scale_walk).
+// (set_matrix_values_many) share scale_many's walk of Solver::scale() (scale_walk).  The three group entries with the vectors in the
+// caller's device memory (DESIGN.md "Many small LPs", group device re-solve) are at the end of this file.
 //
 // Ordering is by stream: for the duration of a call every member works on ONE stream (the first member's), after its own stream
 // has been waited for once; the members' streams come back at exit, after one wait for the group's.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 
 #include "many.h"
 #include "group_pack.h"
@@ -525,6 +527,14 @@ struct GroupBlocks {
     GroupLaunches tables{/*own_launches=*/false};
     DBuf<unsigned long long> flags;
     HBuf<unsigned long long> flags_h;
+    // the device entries (DESIGN.md "Many small LPs", group device re-solve): the event recorded on the caller's stream
+    hipEvent_t inputs_ready = nullptr;
+    GroupBlocks() = default;
+    GroupBlocks(const GroupBlocks &) = delete;
+    GroupBlocks &operator=(const GroupBlocks &) = delete;
+    ~GroupBlocks() {
+        if (inputs_ready) (void)hipEventDestroy(inputs_ready);
+    }
 };
 
 namespace {
@@ -535,6 +545,53 @@ GroupBlocks &blocks_of(Solver *owner) {
 }
 
 std::string member(const char *who, int k) { return std::string(who) + ": member " + std::to_string(k); }
+
+// The two data passes of the members `in`: recorded, run, the scalars packed and fetched, ONE wait, then each member's host
+// formulas.  src[k]: where member k's given vectors are read on the device -- pieces of the staging block, or the caller's own
+// buffers (the device entries); data[k].obj_constant is host memory either way.
+void data_passes(Solver **s, const std::vector<int> &in, const std::vector<PackMember> &pm, const MemberData *data, const MemberData *src,
+                 GroupBlocks &gb, hipStream_t st, ResolveCounts &rc, clock_type::time_point t0, bool device_entry) {
+    const int nj = static_cast<int>(in.size());
+    const size_t per = static_cast<size_t>(4) * kReduceBlocks;
+    if (gb.parts.n < per * nj) gb.parts.alloc(per * nj);
+    GroupLaunches &gl = gb.gl;
+    const long tables0 = gl.tables_sent();
+    for (int j = 0; j < nj; ++j) {
+        const int k = in[j];
+        Solver &m = *s[k];
+        m.data_time[0] = m.data_time[1] = m.data_time[2] = 0.0;
+        if (data[k].obj_constant) m.obj_constant = *data[k].obj_constant;
+        m.data_first_pass(src[k].AL, src[k].AU, src[k].l, src[k].u, src[k].c, pm[k].bounds, gb.parts.p + per * j, &gl);
+    }
+    gl.next_stage();  // (the second pass reads the sums the first pass' finalize leaves in the member's scalars)
+    for (int j = 0; j < nj; ++j) {
+        const int k = in[j];
+        s[k]->data_second_pass(pm[k].bounds, pm[k].c, gb.parts.p + per * j, &gl);
+        gl.pack(s[k]->scal.p, s[k]->scal_h.p);
+    }
+    rc.launches += gl.run(st);
+    const int copies = gl.fetch(st);
+    rc.launches += copies;  // (the packing kernel)
+    rc.d2h += copies;
+    rc.h2d += gl.tables_sent() - tables0;
+    HIP_CHECK(hipStreamSynchronize(st));
+    ++rc.waits;
+    gl.deliver();
+    const double wall = time_since(t0);  // the group call's wall time is every member's
+    for (int k : in) {
+        Solver &m = *s[k];
+        ++m.fetches;
+        m.data_consume(pm[k].bounds, pm[k].c);
+        m.invalidate_far();
+        m.data_time[1] = m.data_time[2] = wall;
+        m.data_since_run += wall;
+        if (device_entry) m.set_transfer(0, 0, true);
+        else
+            m.set_transfer((pm[k].bounds ? 2 * static_cast<size_t>(m.m_loc) + 2 * static_cast<size_t>(m.n_loc) : 0) + (pm[k].c ? m.n_loc : 0), 0,
+                           false);
+        ++rc.served;
+    }
+}
 
 }  // namespace
 
@@ -593,45 +650,13 @@ void set_data_many(Solver **s, int count, const MemberData *data, ResolveCounts 
             gb.in.send(sizeof(double) * L.data_doubles, st);
             ++rc.h2d;
             const double *dev = static_cast<const double *>(gb.in.dev);
-            const size_t per = static_cast<size_t>(4) * kReduceBlocks;
-            if (gb.parts.n < per * nj) gb.parts.alloc(per * nj);
-            GroupLaunches &gl = gb.gl;
-            const long tables0 = gl.tables_sent();
             auto at = [&](size_t off) { return off == kPackAbsent ? nullptr : dev + off; };
-            for (int j = 0; j < nj; ++j) {
-                const int k = in[j];
-                Solver &m = *s[k];
-                m.data_time[0] = m.data_time[1] = m.data_time[2] = 0.0;
-                if (data[k].obj_constant) m.obj_constant = *data[k].obj_constant;
-                const PackSlot &p = L.slot[k];
-                m.data_first_pass(at(p.AL), at(p.AU), at(p.l), at(p.u), at(p.c), pm[k].bounds, gb.parts.p + per * j, &gl);
-            }
-            gl.next_stage();  // (the second pass reads the sums the first pass' finalize leaves in the member's scalars)
-            for (int j = 0; j < nj; ++j) {
-                const int k = in[j];
-                s[k]->data_second_pass(pm[k].bounds, pm[k].c, gb.parts.p + per * j, &gl);
-                gl.pack(s[k]->scal.p, s[k]->scal_h.p);
-            }
-            rc.launches += gl.run(st);
-            const int copies = gl.fetch(st);
-            rc.launches += copies;  // (the packing kernel)
-            rc.d2h += copies;
-            rc.h2d += gl.tables_sent() - tables0;
-            HIP_CHECK(hipStreamSynchronize(st));
-            ++rc.waits;
-            gl.deliver();
-            const double wall = time_since(t0);  // the group call's wall time is every member's
+            std::vector<MemberData> src(static_cast<size_t>(count));
             for (int k : in) {
-                Solver &m = *s[k];
-                ++m.fetches;
-                m.data_consume(pm[k].bounds, pm[k].c);
-                m.invalidate_far();
-                m.data_time[1] = m.data_time[2] = wall;
-                m.data_since_run += wall;
-                m.set_transfer((pm[k].bounds ? 2 * static_cast<size_t>(m.m_loc) + 2 * static_cast<size_t>(m.n_loc) : 0) + (pm[k].c ? m.n_loc : 0), 0,
-                               false);
-                ++rc.served;
+                const PackSlot &p = L.slot[k];
+                src[k].c = at(p.c), src[k].AL = at(p.AL), src[k].AU = at(p.AU), src[k].l = at(p.l), src[k].u = at(p.u);
             }
+            data_passes(s, in, pm, data, src.data(), gb, st, rc, t0, false);
         } catch (...) {
             s[0]->group_blocks.reset();  // (whatever was recorded goes with it)
             throw;
@@ -653,6 +678,16 @@ void check_starts(Solver *const *s, int count, const MemberStart *start) {
     }
 }
 
+namespace {
+struct TimeBase {  // (Solver::resolve: the reported time starts from the set_data seconds since the previous loop)
+    Solver **s;
+    int count;
+    ~TimeBase() {
+        for (int k = 0; k < count; ++k) s[k]->time_base = -1.0;
+    }
+};
+}  // namespace
+
 void resolve_many(Solver **s, int count, const MemberStart *start, HPRLP_results *out, ResolveCounts *counts) {
     std::vector<MemberStart> cold;
     if (!start) {
@@ -661,13 +696,6 @@ void resolve_many(Solver **s, int count, const MemberStart *start, HPRLP_results
     }
     ResolveCounts rc;
     GroupCounts gc;
-    struct TimeBase {  // (Solver::resolve: the reported time starts from the set_data seconds since the previous loop)
-        Solver **s;
-        int count;
-        ~TimeBase() {
-            for (int k = 0; k < count; ++k) s[k]->time_base = -1.0;
-        }
-    };
     {
         GroupScope scope(s, count);
         const hipStream_t st = scope.group;
@@ -782,6 +810,52 @@ void resolve_many(Solver **s, int count, const MemberStart *start, HPRLP_results
 // The rule is the group launches': the bodies of values.hip's kernels run as workgroup lb of the member's own grid, the zeroing
 // is reset_iterates' fills, the scaling is scale_many's walk, so every stored number is the member's own.
 // ------------------------------------------------------------------------------------------------
+namespace {
+
+// The apply of set_matrix_values_many for the members `in`: scatter, gather and zeroing in one stage, Solver::scale()'s pieces
+// behind them, one recorder; then what Solver::values_apply and set_matrix_values leave, with the group call's wall times.
+// src[k]: where member k's values and vectors are read on the device -- pieces of the staging block, or the caller's own buffers
+// (the device entries); data[k]: nnz and the host pointer obj_constant.
+void values_apply_group(Solver **s, const std::vector<int> &in, const MemberValues *data, const MemberValues *src, const std::vector<char> &built,
+                        double maps_seconds, double upload_seconds, GroupBlocks &gb, hipStream_t st, ValuesCounts &vc, clock_type::time_point t0,
+                        bool device_entry) {
+    const auto t_k = time_now();
+    GroupLaunches &gl = gb.tables;
+    const long tables0 = gl.tables_sent();
+    for (int k : in) {
+        Solver &m = *s[k];
+        gl.values_in(data[k].nnz, src[k].val, m.map_A.p, m.map_AT.p, m.A.val.p, m.AT.val.p);
+        gl.vectors_in(VectorsInArgs{m.m_loc, m.n_loc, src[k].AL, src[k].AU, src[k].l, src[k].u, src[k].c, m.perm_r_dev.p, m.perm_c_dev.p, m.AL.p,
+                                    m.AU.p, m.l.p, m.u.p, m.c.p});
+        if (data[k].obj_constant) m.obj_constant = *data[k].obj_constant;
+        m.reset_iterates(&gl);
+    }
+    gl.next_stage();  // (the scaling reads what the three kinds of this stage write)
+    const double kernels_seconds = time_since(t_k);
+    SetupCounts sc;
+    scale_walk(s, in, gl, st, sc);
+    vc.launches += sc.scale_launches;
+    vc.waits += sc.scale_waits;
+    vc.d2h += sc.scale_waits;  // (the sums block comes back once per wait)
+    vc.h2d += gl.tables_sent() - tables0;
+    vc.served += sc.served;
+    const double wall = time_since(t0);
+    for (int k : in) {
+        Solver &m = *s[k];
+        m.matrix_time[0] = built[k] ? maps_seconds : 0.0;
+        m.matrix_time[1] = upload_seconds;
+        m.matrix_time[2] = kernels_seconds;
+        m.matrix_time[3] = m.scaling_time;
+        m.matrix_time[4] = wall;
+        ++m.matrix_calls;
+        m.data_since_run += wall;
+        if (device_entry) m.set_transfer(0, 0, true);
+        else m.set_transfer(static_cast<size_t>(data[k].nnz) + 2 * static_cast<size_t>(m.m) + 3 * static_cast<size_t>(m.n), 0, false);
+    }
+}
+
+}  // namespace
+
 void set_matrix_values_many(Solver **s, int count, const MemberValues *data, ValuesCounts *counts) {
     const char *who = "hprlp_solver_set_matrix_values_many";
     // ---- the host checks of all members, before the first upload (Solver::set_matrix_values' rules and messages)
@@ -901,45 +975,406 @@ void set_matrix_values_many(Solver **s, int count, const MemberValues *data, Val
             vc.waits += 1 + 1 + (m.fetches - f0) + 1;
         }
         if (nj > 0) {
-            // ---- apply: scatter, gather and zeroing in one stage, Solver::scale()'s pieces behind them, one recorder
-            const auto t_k = time_now();
-            GroupLaunches &gl = gb->tables;
-            const long tables0 = gl.tables_sent();
+            std::vector<MemberValues> src(static_cast<size_t>(count));
+            auto at = [&](size_t off) { return off == kPackAbsent ? nullptr : dev + off; };
             for (int k : in) {
-                Solver &m = *s[k];
                 const PackSlot &p = L.slot[k];
-                auto at = [&](size_t off) { return off == kPackAbsent ? nullptr : dev + off; };
-                // The scatter stores 16 bytes at A_val + 2 t and AT_val + 2 t, and with map_A null it loads 16 bytes at the
-                // staged values + 2 t: the value arrays are hipMalloc's or pieces of the group's arena (256-byte aligned both),
-                // and every vector of the staging block starts on a multiple of kPackAlign = 32 doubles of a pinned block's copy.
-                gl.values_in(data[k].nnz, at(p.val), m.map_A.p, m.map_AT.p, m.A.val.p, m.AT.val.p);
-                gl.vectors_in(VectorsInArgs{m.m_loc, m.n_loc, at(p.AL), at(p.AU), at(p.l), at(p.u), at(p.c), m.perm_r_dev.p, m.perm_c_dev.p, m.AL.p,
-                                            m.AU.p, m.l.p, m.u.p, m.c.p});
-                if (data[k].obj_constant) m.obj_constant = *data[k].obj_constant;
-                m.reset_iterates(&gl);
+                src[k].val = at(p.val), src[k].c = at(p.c), src[k].AL = at(p.AL), src[k].AU = at(p.AU), src[k].l = at(p.l), src[k].u = at(p.u);
             }
-            gl.next_stage();  // (the scaling reads what the three kinds of this stage write)
-            const double kernels_seconds = time_since(t_k);
-            SetupCounts sc;
-            scale_walk(s, in, gl, st, sc);
-            vc.launches += sc.scale_launches;
-            vc.waits += sc.scale_waits;
-            vc.d2h += sc.scale_waits;  // (the sums block comes back once per wait)
-            vc.h2d += gl.tables_sent() - tables0;
-            vc.served += sc.served;
-            // ---- bookkeeping: what Solver::values_apply and set_matrix_values leave, with the group call's wall times
-            const double wall = time_since(t0);
-            for (int k : in) {
-                Solver &m = *s[k];
-                m.matrix_time[0] = built[k] ? maps_seconds : 0.0;
-                m.matrix_time[1] = upload_seconds;
-                m.matrix_time[2] = kernels_seconds;
-                m.matrix_time[3] = m.scaling_time;
-                m.matrix_time[4] = wall;
-                ++m.matrix_calls;
-                m.data_since_run += wall;
-                m.set_transfer(static_cast<size_t>(data[k].nnz) + 2 * static_cast<size_t>(m.m) + 3 * static_cast<size_t>(m.n), 0, false);
+            // The scatter stores 16 bytes at A_val + 2 t and AT_val + 2 t, and with map_A null it loads 16 bytes at the
+            // staged values + 2 t: the value arrays are hipMalloc's or pieces of the group's arena (256-byte aligned both),
+            // and every vector of the staging block starts on a multiple of kPackAlign = 32 doubles of a pinned block's copy.
+            values_apply_group(s, in, data, src.data(), built, maps_seconds, upload_seconds, *gb, st, vc, t0, false);
+        }
+    } catch (...) {
+        if (gb) s[0]->group_blocks.reset();  // (whatever was recorded goes with it)
+        throw;
+    }
+    if (counts) *counts = vc;
+}
+
+// ------------------------------------------------------------------------------------------------
+// group device re-solve (DESIGN.md "Many small LPs", group device re-solve): the three group entries above with every vector in
+// the caller's device memory and the solutions wanted there.  The mechanism is the single device entries': a group task's source
+// is the caller's buffer where the host entries pass a piece of the staging block, and the solution kernel stores into the
+// caller's buffers (a joining member has no locality ordering: nothing to scatter).  What is new is the check: all pointers of
+// all members are looked up before anything is launched, and ONE launch (GroupLaunches::data_check) checks the vectors of all
+// members where they lie, one flag word per member, one copy, one wait -- before anything a solver reads is written.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+// The pointer checks of one call.  A pointer that lies, with its length, inside a range the runtime has already reported in this
+// call is device memory of the group's device with room for it: no second lookup (a group cut from a few packed tensors costs a
+// few lookups whatever its size).  Everything else goes through check_device_pointer, whose words the refusal carries.
+class PointerChecks {
+  public:
+    PointerChecks(int device, const char *who, DeviceCounts &dc) : device_(device), who_(who), dc_(dc) {}
+    void operator()(int k, const void *p, size_t count, const char *name) {
+        if (!p) return;  // (not given / not wanted)
+        ++dc_.pointers;
+        const char *b = static_cast<const char *>(p), *e = b + count * sizeof(double);
+        if (reinterpret_cast<uintptr_t>(p) % sizeof(double) == 0)
+            for (const DeviceRange &r : seen_)
+                if (b >= r.base && e <= r.base + r.bytes) return;
+        ++dc_.lookups;
+        DeviceRange r;
+        check_device_pointer(p, count, device_, name, member(who_, k).c_str(), &r);
+        if (r.bytes > 0) seen_.push_back(r);
+    }
+
+  private:
+    int device_;
+    const char *who_;
+    DeviceCounts &dc_;
+    std::vector<DeviceRange> seen_;
+};
+
+// The group's stream waits for what the caller's stream has been given so far (one event per call).
+void wait_for_caller(GroupBlocks &gb, hipStream_t caller, hipStream_t st) {
+    if (!gb.inputs_ready) HIP_CHECK(hipEventCreateWithFlags(&gb.inputs_ready, hipEventDisableTiming));
+    HIP_CHECK(hipEventRecord(gb.inputs_ready, caller));
+    HIP_CHECK(hipStreamWaitEvent(st, gb.inputs_ready, 0));
+}
+
+// `words` flag words of all ones (kDataCheckClean, kValuesAllFinite) by ONE memset; fetch_flags: one copy, one wait
+unsigned long long *cleared_flags(GroupBlocks &gb, size_t words, hipStream_t st) {
+    if (gb.flags.n < words) {
+        gb.flags.alloc(words);
+        gb.flags_h.alloc(words);
+    }
+    HIP_CHECK(hipMemsetAsync(gb.flags.p, 0xff, sizeof(unsigned long long) * words, st));
+    return gb.flags.p;
+}
+void fetch_flags(GroupBlocks &gb, size_t words, hipStream_t st, DeviceCounts &dc) {
+    HIP_CHECK(hipMemcpyAsync(gb.flags_h.p, gb.flags.p, sizeof(unsigned long long) * words, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    dc.flags += static_cast<long>(words);
+    ++dc.waits_before_write;
+}
+// k_data_check's word of member k as the host group entries' message
+void throw_if_flagged(unsigned long long word, const char *const names[kDataCheckVecs], const std::string &who, const char *what) {
+    if (word == kDataCheckClean) return;
+    const int v = static_cast<int>(word >> kDataCheckShift);
+    const unsigned long long i = word & ((1ULL << kDataCheckShift) - 1);
+    throw std::runtime_error(who + ": " + (v < kDataCheckVecs ? names[v] : "?") + "[" + std::to_string(i) + "] " + what);
+}
+const char *const kDataNames[kDataCheckVecs] = {"c", "AL", "AU", "l", "u"};  // (the host entries' order of vectors)
+const char *const kStartNames[kDataCheckVecs] = {"x0", "y0", "", "", ""};
+
+}  // namespace
+
+void set_data_many_device(Solver **s, int count, const MemberData *data, hipStream_t caller, ResolveCounts *counts, DeviceCounts *dcounts) {
+    const char *who = "hprlp_solver_set_data_many_device";
+    DeviceCounts unused;
+    DeviceCounts &dc = dcounts ? *dcounts : unused;
+    // ---- the host rules of all members, then every pointer of every member: nothing has been launched or written
+    bool any = false;
+    for (int k = 0; k < count; ++k) {
+        const MemberData &d = data[k];
+        const bool bounds = d.AL || d.AU || d.l || d.u;
+        if (bounds && !(d.AL && d.AU && d.l && d.u))
+            throw std::runtime_error(member(who, k) + ": AL, AU, l and u are given together or not at all (b_scale couples them)");
+        if (d.obj_constant && std::isnan(*d.obj_constant)) throw std::runtime_error(member(who, k) + ": obj_constant is NaN");
+        any = any || d.c || bounds;
+    }
+    PointerChecks pass(s[0]->prm.device_number, who, dc);
+    for (int k = 0; k < count; ++k) {
+        const MemberData &d = data[k];
+        const size_t m = static_cast<size_t>(s[k]->m_loc), n = static_cast<size_t>(s[k]->n_loc);
+        pass(k, d.c, n, "c"); pass(k, d.AL, m, "AL"); pass(k, d.AU, m, "AU"); pass(k, d.l, n, "l"); pass(k, d.u, n, "u");
+    }
+    ResolveCounts rc;
+    const auto t0 = time_now();
+    GroupScope scope(s, count);
+    const hipStream_t st = scope.group;
+    std::vector<int> in;  // the members of the group launches
+    std::vector<PackMember> pm(static_cast<size_t>(count));
+    for (int k = 0; k < count; ++k) {
+        pm[k].c = data[k].c != nullptr, pm[k].bounds = data[k].AL != nullptr;
+        if ((pm[k].c || pm[k].bounds) && s[k]->joins_group_resolve()) in.push_back(k);
+    }
+    if (in.size() < 2) in.clear();  // (a group of one issues the member's own launches)
+    std::vector<char> joins(static_cast<size_t>(count), 0);
+    for (int k : in) joins[k] = 1;
+    GroupBlocks &gb = blocks_of(s[0]);
+    try {
+        if (any) {
+            // ---- the check: the vectors of ALL members where they lie, one launch, one copy of the flag words, one wait
+            wait_for_caller(gb, caller, st);
+            unsigned long long *flags = cleared_flags(gb, static_cast<size_t>(count), st);
+            ++rc.memsets;
+            GroupLaunches &chk = gb.gl;
+            const long tables0 = chk.tables_sent();
+            for (int k = 0; k < count; ++k) {
+                const MemberData &d = data[k];
+                const int m = s[k]->m_loc, n = s[k]->n_loc;
+                chk.data_check(DataCheckArgs{{d.c, d.AL, d.AU, d.l, d.u}, {n, m, m, n, n}, 0}, flags + k);
             }
+            const int launches = chk.run(st);
+            rc.launches += launches, dc.check_launches += launches;
+            rc.h2d += chk.tables_sent() - tables0;
+            fetch_flags(gb, static_cast<size_t>(count), st, dc);
+            ++rc.d2h, ++rc.waits;
+            for (int k = 0; k < count; ++k) throw_if_flagged(gb.flags_h[k], kDataNames, member(who, k), "is NaN");  // (the lowest member first)
+        }
+        // -- from here on the call goes through
+        for (int k = 0; k < count; ++k) {
+            const MemberData &d = data[k];
+            if (joins[k] || !(d.c || d.obj_constant || d.AL)) continue;  // (nothing given: the member keeps its bits)
+            s[k]->set_data_device(d.c, d.obj_constant, d.AL, d.AU, d.l, d.u, caller);
+            if (!(d.c || d.AL)) continue;  // (obj_constant alone is a host assignment)
+            ++rc.own, ++dc.own;
+            // Solver::set_data_device, nominal (many.h: ResolveCounts): the flag's memset, its check, two passes and two finalizes;
+            // the flag's copy and the scalars', a wait each
+            rc.memsets += 1, rc.launches += 5, rc.d2h += 2, rc.waits += 2;
+        }
+        if (!in.empty()) {
+            data_passes(s, in, pm, data, data, gb, st, rc, t0, true);
+            dc.served += static_cast<long>(in.size());
+        }
+    } catch (...) {
+        s[0]->group_blocks.reset();  // (whatever was recorded goes with it)
+        throw;
+    }
+    if (counts) *counts = rc;
+}
+
+void resolve_many_device(Solver **s, int count, const MemberStart *start, const MemberOut *dst, hipStream_t caller, HPRLP_results *out,
+                         ResolveCounts *counts, DeviceCounts *dcounts) {
+    const char *who = "hprlp_solver_resolve_many_device";
+    DeviceCounts unused;
+    DeviceCounts &dc = dcounts ? *dcounts : unused;
+    std::vector<MemberStart> cold;
+    if (!start) {
+        cold.resize(static_cast<size_t>(count));
+        start = cold.data();
+    }
+    std::vector<MemberOut> none;
+    if (!dst) {
+        none.resize(static_cast<size_t>(count));
+        dst = none.data();
+    }
+    bool warm = false;
+    for (int k = 0; k < count; ++k) {
+        if (std::isnan(start[k].sigma)) throw std::runtime_error(member(who, k) + ": sigma is NaN");
+        warm = warm || start[k].x0 || start[k].y0;
+    }
+    PointerChecks pass(s[0]->prm.device_number, who, dc);
+    for (int k = 0; k < count; ++k) {
+        const size_t m = static_cast<size_t>(s[k]->m_loc), n = static_cast<size_t>(s[k]->n_loc);
+        pass(k, start[k].x0, n, "x0"); pass(k, start[k].y0, m, "y0");
+        pass(k, dst[k].x, n, "x"); pass(k, dst[k].y, m, "y"); pass(k, dst[k].z, n, "z");
+    }
+    ResolveCounts rc;
+    GroupCounts gc;
+    {
+        GroupScope scope(s, count);
+        const hipStream_t st = scope.group;
+        std::vector<int> in;
+        for (int k = 0; k < count; ++k)
+            if (s[k]->joins_group_resolve()) in.push_back(k);
+        if (in.size() < 2) in.clear();  // (a group of one issues the member's own launches)
+        std::vector<char> grouped(static_cast<size_t>(count), 0);
+        for (int k : in) grouped[k] = 1;
+        const int nj = static_cast<int>(in.size());
+        GroupBlocks &gb = blocks_of(s[0]);
+        GroupLaunches &gl = gb.gl;
+        try {
+            wait_for_caller(gb, caller, st);  // (the outputs too: what the caller's stream still does with them comes first)
+            if (warm) {
+                // ---- the check: the starts of ALL members where they lie, one launch, one copy of the flag words, one wait
+                unsigned long long *flags = cleared_flags(gb, static_cast<size_t>(count), st);
+                ++rc.memsets;
+                const long tables0 = gl.tables_sent();
+                for (int k = 0; k < count; ++k)
+                    gl.data_check(DataCheckArgs{{start[k].x0, start[k].y0, nullptr, nullptr, nullptr}, {s[k]->n_loc, s[k]->m_loc, 0, 0, 0}, 1}, flags + k);
+                const int launches = gl.run(st);
+                rc.launches += launches, dc.check_launches += launches;
+                rc.h2d += gl.tables_sent() - tables0;
+                fetch_flags(gb, static_cast<size_t>(count), st, dc);
+                ++rc.d2h, ++rc.waits;
+                for (int k = 0; k < count; ++k) throw_if_flagged(gb.flags_h[k], kStartNames, member(who, k) + ": warm start", "is not finite");
+            }
+            // -- from here on the call goes through
+            // ---- the members that go their own way: Solver::resolve_device, start to solution
+            for (int k = 0; k < count; ++k) {
+                if (grouped[k]) continue;
+                const MemberStart &b = start[k];
+                s[k]->resolve_device(b.sigma, b.x0, b.y0, caller, dst[k].x, dst[k].y, dst[k].z, &out[k]);
+                ++rc.own, ++dc.own;
+                // (nominal, many.h: ResolveCounts -- what Solver::resolve_device issues for a member without a locality ordering)
+                rc.memsets += 17, rc.waits += 1;                                                         // reset_iterates
+                rc.launches += (s[k]->hook_no_bound_codes ? 0 : 2) + 1 + (b.sigma > 0.0 ? 1 : 0);         // bound codes, ctrl, the override
+                if (b.x0 || b.y0) rc.memsets += 1, rc.launches += 1 + 4, rc.d2h += 1, rc.waits += 2;    // the check, the start
+                rc.launches += dst[k].x || dst[k].y || dst[k].z ? 1 : 0, rc.waits += 1;                  // the solution, the final wait
+            }
+            if (nj > 0) {
+                // ---- zeroing, bound codes, ctrl and the starts of the group, recorded: they run in front of the first evaluation
+                for (int k : in) {
+                    Solver &m = *s[k];
+                    m.reset_iterates(&gl);
+                    m.init_iteration_state(&gl, start[k].sigma);
+                    if (start[k].x0 || start[k].y0) {
+                        m.invalidate_far();
+                        m.start_launch(start[k].x0, start[k].y0, nullptr, nullptr, &gl);
+                    }
+                }
+                rc.launches += gl.recorded_launches();
+                gl.next_stage();  // (the evaluation's Rd / Rp overwrite the partials the start's finalize reads)
+                // ---- the lock-step loop over the group's members
+                std::vector<Solver *> js(static_cast<size_t>(nj));
+                std::vector<HPRLP_results> jout(static_cast<size_t>(nj));
+                for (int j = 0; j < nj; ++j) js[j] = s[in[j]], jout[j] = out[in[j]];
+                const std::vector<char> all(static_cast<size_t>(nj), 1);
+                {
+                    TimeBase tb{js.data(), nj};
+                    for (Solver *m : js) m->time_base = m->data_since_run;
+                    loop_many(js.data(), nj, jout.data(), gc, scope, all, gl, all.data());
+                }
+                rc.loop_own = gc.own;
+                // ---- the solutions: straight into the callers' buffers (an output that is not wanted: the member's own scratch,
+                // where its collect_solution puts it), one launch, one wait, no copy
+                for (int j = 0; j < nj; ++j) {
+                    const int k = in[j];
+                    Solver &m = *s[k];
+                    out[k] = jout[j];
+                    out[k].x = out[k].y = out[k].z = nullptr;
+                    const MemberOut &o = dst[k];
+                    if (o.x || o.y || o.z) m.solution_launch(o.x ? o.x : m.sn1.p, o.y ? o.y : m.sm1.p, o.z ? o.z : m.gsn.p + m.col_off, &gl);
+                }
+                const long tables0 = gl.tables_sent();
+                rc.launches += gl.run(st);
+                rc.h2d += gl.tables_sent() - tables0;  // (the tables of what runs in front of the loop ride on the loop's first copy)
+                HIP_CHECK(hipStreamSynchronize(st));
+                ++rc.waits;
+                for (int k : in) {
+                    s[k]->set_transfer(0, 0, true);
+                    ++rc.served, ++dc.served;
+                }
+            }
+        } catch (...) {
+            s[0]->group_blocks.reset();  // (whatever was recorded goes with it)
+            throw;
+        }
+    }
+    if (counts) *counts = rc;
+}
+
+void set_matrix_values_many_device(Solver **s, int count, const MemberValues *data, hipStream_t caller, ValuesCounts *counts,
+                                   DeviceCounts *dcounts) {
+    const char *who = "hprlp_solver_set_matrix_values_many_device";
+    DeviceCounts unused;
+    DeviceCounts &dc = dcounts ? *dcounts : unused;
+    // ---- the host rules of all members (Solver::set_matrix_values_device's, with its messages), then every pointer
+    std::vector<char> gave(static_cast<size_t>(count), 0);
+    int ngave = 0;
+    for (int k = 0; k < count; ++k) {
+        const MemberValues &d = data[k];
+        if (!(d.val || d.c || d.obj_constant || d.AL || d.AU || d.l || d.u)) continue;  // skipped: the member keeps every bit
+        if (!d.val || !d.c || !d.AL || !d.AU || !d.l || !d.u)
+            throw std::runtime_error(member(who, k) + ": val, c, AL, AU, l and u are all required (every scaled vector depends on the values)");
+        if (d.nnz != static_cast<long>(s[k]->A.view.nnz))
+            throw std::runtime_error(member(who, k) + ": nnz is " + std::to_string(d.nnz) + ", the model has " + std::to_string(s[k]->A.view.nnz) +
+                                     " entries (the pattern cannot change)");
+        if (d.obj_constant && std::isnan(*d.obj_constant)) throw std::runtime_error(member(who, k) + ": obj_constant is NaN");
+        gave[k] = 1;
+        ++ngave;
+    }
+    const auto t_ptr = time_now();
+    PointerChecks pass(s[0]->prm.device_number, who, dc);
+    for (int k = 0; k < count; ++k) {
+        if (!gave[k]) continue;
+        const MemberValues &d = data[k];
+        const size_t m = static_cast<size_t>(s[k]->m), n = static_cast<size_t>(s[k]->n);
+        pass(k, d.val, static_cast<size_t>(d.nnz), "val");
+        pass(k, d.c, n, "c"); pass(k, d.AL, m, "AL"); pass(k, d.AU, m, "AU"); pass(k, d.l, n, "l"); pass(k, d.u, n, "u");
+    }
+    const double ptr_seconds = time_since(t_ptr);
+    ValuesCounts vc;
+    const auto t0 = time_now();
+    GroupScope scope(s, count);
+    const hipStream_t st = scope.group;
+    const bool fused_norms = env_get("HPRLP_NO_FUSED_NORMS") == nullptr;  // (scale_many's condition)
+    std::vector<int> in;  // the members of the group launches
+    for (int k = 0; k < count; ++k)
+        if (gave[k] && fused_norms && s[k]->joins_group_resolve() && s[k]->m_loc > 0 && s[k]->n_loc > 0) in.push_back(k);
+    if (in.size() < 2) in.clear();  // (a group of one issues the member's own launches)
+    std::vector<char> joins(static_cast<size_t>(count), 0);
+    for (int k : in) joins[k] = 1;
+    // The scatter of a joining member (no value map for A) loads the values as 16-byte pairs: from the staging block in the host
+    // entry, from the caller's buffer here.  An 8-byte aligned `val` is the single entries' rule; the pairs need 16.
+    for (int k : in)
+        if (reinterpret_cast<uintptr_t>(data[k].val) % 16)
+            throw std::runtime_error(member(who, k) + ": val is not aligned to 16 bytes (the group's scatter loads the values in pairs)");
+    // One member alone is checked by its own call before it writes anything, and nobody else is written: no block.
+    GroupBlocks *gb = ngave >= 2 ? &blocks_of(s[0]) : nullptr;
+    try {
+        const auto t_maps = time_now();
+        std::vector<char> built(static_cast<size_t>(count), 0);
+        for (int k : in) {
+            if (s[k]->have_maps) continue;
+            s[k]->build_value_maps();
+            built[k] = 1;
+            ++vc.maps;
+        }
+        const double maps_seconds = time_since(t_maps);
+        const auto t_up = time_now();
+        if (gb) {
+            // ---- the check: vectors and values of ALL members where they lie, in ONE stage: two flag words per member (the
+            // vectors' at k, the values' at count + k), one memset, one copy, one wait
+            wait_for_caller(*gb, caller, st);
+            const size_t words = 2 * static_cast<size_t>(count);
+            unsigned long long *flags = cleared_flags(*gb, words, st);
+            ++vc.memsets;
+            GroupLaunches &chk = gb->gl;
+            const long tables0 = chk.tables_sent();
+            for (int k = 0; k < count; ++k) {
+                if (!gave[k]) continue;
+                const MemberValues &d = data[k];
+                chk.data_check(DataCheckArgs{{d.c, d.AL, d.AU, d.l, d.u}, {s[k]->n, s[k]->m, s[k]->m, s[k]->n, s[k]->n}, 0}, flags + k);
+                chk.values_check(d.val, d.nnz, flags + count + k);
+            }
+            const int launches = chk.run(st);
+            vc.launches += launches, dc.check_launches += launches;
+            vc.h2d += chk.tables_sent() - tables0;
+            fetch_flags(*gb, words, st, dc);
+            ++vc.d2h, ++vc.waits;
+            // (as the host entry, where the host checks of the vectors come first: a vector's NaN of any member wins)
+            for (int k = 0; k < count; ++k)
+                if (gave[k]) throw_if_flagged(gb->flags_h[k], kDataNames, member(who, k), "is NaN");
+            for (int k = 0; k < count; ++k)
+                if (gave[k] && gb->flags_h[count + k] != kValuesAllFinite)
+                    throw std::runtime_error(member(who, k) + ": val[" + std::to_string(gb->flags_h[count + k]) + "] is not finite");
+        }
+        const double upload_seconds = ptr_seconds + time_since(t_up);
+        // -- from here on the call goes through
+        // ---- the members that go their own way: Solver::set_matrix_values_device (its own checks included)
+        for (int k = 0; k < count; ++k) {
+            if (!gave[k] || joins[k]) continue;
+            Solver &m = *s[k];
+            const MemberValues &d = data[k];
+            const bool had_maps = m.have_maps;
+            const long f0 = m.fetches, l0 = scaling_launch_count();
+            try {
+                m.set_matrix_values_device(d.val, d.nnz, d.c, d.obj_constant, d.AL, d.AU, d.l, d.u, caller);
+            } catch (const std::exception &e) {  // (a member alone in the call: its own check's refusal, named as the group's)
+                std::string msg = e.what();
+                for (const char *own : {"set_matrix_values: ", "set_matrix_values_device: "})
+                    if (msg.compare(0, std::strlen(own), own) == 0) msg = msg.substr(std::strlen(own));
+                throw std::runtime_error(member(who, k) + ": " + msg);
+            }
+            ++vc.own, ++dc.own;
+            if (!had_maps) ++vc.maps;
+            // the flags' memset, the two checks, scatter, gather, the flags' copy and wait; reset_iterates' seventeen memsets and
+            // wait; scale(): its launches, its scalar fetches, its final wait; the wait that ends the call
+            vc.memsets += 1 + 17;
+            vc.launches += 4 + (scaling_launch_count() - l0);
+            vc.d2h += 1 + (m.fetches - f0);
+            vc.waits += 1 + 1 + (m.fetches - f0) + 1 + 1;
+        }
+        if (!in.empty()) {
+            values_apply_group(s, in, data, data, built, maps_seconds, upload_seconds, *gb, st, vc, t0, true);
+            dc.served += static_cast<long>(in.size());
         }
     } catch (...) {
         if (gb) s[0]->group_blocks.reset();  // (whatever was recorded goes with it)

@@ -104,4 +104,32 @@ struct ValuesCounts {
 // those refusals).
 void set_matrix_values_many(Solver **s, int count, const MemberValues *data, ValuesCounts *counts = nullptr);
 
+// ---- group device re-solve (DESIGN.md "Many small LPs", group device re-solve) ---------------------------------------------------
+struct MemberOut {  // where one member's solution goes (hprlp_member_out): device buffers of the caller's, null: not wanted
+    double *x = nullptr, *y = nullptr, *z = nullptr;
+};
+// what a device group call did beyond ResolveCounts / ValuesCounts (hprlp_last_many_device_counts): non-null device pointers
+// checked; lookups issued to the runtime for them (a pointer inside a range already reported in the call needs none); launches of
+// the device check; flag words copied back; members served by the group launches / that ran their own device entry; host waits
+// before the first write of anything a solver reads (the check's: 0 where nothing had to be checked)
+struct DeviceCounts {
+    long pointers = 0, lookups = 0, check_launches = 0, flags = 0, served = 0, own = 0, waits_before_write = 0;
+};
+// set_data_many, resolve_many and set_matrix_values_many with the members' vectors in DEVICE memory of the caller's (obj_constant
+// and sigma stay host values) and the solutions stored into dst[k] (null: none wanted); out[k].x / y / z stay null.  `caller` is
+// the stream the inputs were produced on: one event on it, the group's stream waits for it before its first read, and the call
+// returns after the group's stream has drained.  Every non-null pointer of every member passes check_device_pointer first (one
+// lookup per distinct range); then ONE launch checks the vectors of all members where they lie (NaN in a data vector, a
+// non-finite start entry; the values in the same stage), one copy of the flag words, one wait -- a refusal of any kind leaves
+// every member as it was.  The members that join read the caller's buffers where the host entries read the staging block, same
+// kernels, same bits; every other member runs its own Solver::set_data_device / resolve_device / set_matrix_values_device inside
+// the same call.  The members have passed check_group and data / out are not null (abi.cpp owns those refusals).  dcounts is
+// filled as the call proceeds, so it also tells what a refused call did.
+void set_data_many_device(Solver **s, int count, const MemberData *data, hipStream_t caller, ResolveCounts *counts = nullptr,
+                          DeviceCounts *dcounts = nullptr);
+void resolve_many_device(Solver **s, int count, const MemberStart *start, const MemberOut *dst, hipStream_t caller, HPRLP_results *out,
+                         ResolveCounts *counts = nullptr, DeviceCounts *dcounts = nullptr);
+void set_matrix_values_many_device(Solver **s, int count, const MemberValues *data, hipStream_t caller, ValuesCounts *counts = nullptr,
+                                   DeviceCounts *dcounts = nullptr);
+
 }  // namespace hprlp

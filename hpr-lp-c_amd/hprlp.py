@@ -89,6 +89,10 @@ class CMemberStart(C.Structure):  # hprlp_member_start
     _fields_ = [("x0", c_dbl_p), ("y0", c_dbl_p), ("sigma", C.c_double)]
 
 
+class CMemberOut(C.Structure):  # hprlp_member_out: device buffers for one member's solution (None: not wanted)
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("z", C.c_void_p)]
+
+
 class CDetection(C.Structure):  # hprlp_detection (include/hprlp_amd.h, 16 bytes)
     _fields_ = [("eps_primal_infeasible", C.c_double), ("eps_dual_infeasible", C.c_double)]
 
@@ -265,6 +269,12 @@ def lib():
     if hasattr(L, "hprlp_solver_set_matrix_values_many"):  # (likewise)
         L.hprlp_solver_set_matrix_values_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(CMemberValues)]
         L.hprlp_last_values_many_counts.argtypes = [C.POINTER(C.c_long)]
+    if hasattr(L, "hprlp_solver_resolve_many_device"):  # (likewise)
+        L.hprlp_solver_set_data_many_device.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(CMemberData), C.c_void_p]
+        L.hprlp_solver_resolve_many_device.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(CMemberStart), C.POINTER(CMemberOut),
+                                                       C.c_void_p, C.POINTER(CResults)]
+        L.hprlp_solver_set_matrix_values_many_device.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(CMemberValues), C.c_void_p]
+        L.hprlp_last_many_device_counts.argtypes = [C.POINTER(C.c_long)]
     _lib = L
     return L
 
@@ -663,6 +673,23 @@ def last_values_many_counts():
     out = (C.c_long * 8)()
     lib().hprlp_last_values_many_counts(out)
     return dict(zip(VALUES_MANY_KEYS, [int(v) for v in out]))
+
+
+MANY_DEVICE_KEYS = ("device pointers checked", "lookups issued to the runtime", "check-kernel launches", "flag words copied back",
+                    "members served by group launches", "members on their own", "waits before the first write")
+
+
+def last_many_device_counts():
+    """Counts of this thread's last Solver.set_data_many_tensors / resolve_many_tensors / set_matrix_many_tensors
+    (hprlp_last_many_device_counts); a refused call reports what it did up to its refusal."""
+    out = (C.c_long * 8)()
+    lib().hprlp_last_many_device_counts(out)
+    return dict(zip(MANY_DEVICE_KEYS, [int(v) for v in out]))
+
+
+def _dev_dbl(addr):
+    """A device address as the const double * of the member structs (None stays NULL)."""
+    return None if addr is None else C.cast(C.c_void_p(addr), c_dbl_p)
 
 
 def solve_batched(model, Cmat, AL, AU, l, u, obj_constants=None, param=None):
@@ -1718,6 +1745,132 @@ class Solver:
         lam, its = self.power_iteration()
         self.init(-1.0, 1.01 * lam)
         return lam, its
+
+    # ---- group device re-solve (DESIGN.md "Many small LPs", group device re-solve): the *_many methods with torch tensors ------------
+    @staticmethod
+    def set_data_many_tensors(solvers, data):
+        """set_data_many() for vectors that are on the GPU already (hprlp_solver_set_data_many_device).  data: one dict per solver
+        with the keys of set_data_tensors -- float64 torch tensors on the solvers' device, 1-D and contiguous (rows of a 2-D tensor
+        and slices of a packed one are welcome: they are views), taken as ordered on the current torch stream; obj_constant is a
+        host number; None or {} changes nothing.  No vector is copied.  Same bits as set_data_many()."""
+        solvers, hs = Solver._handles(solvers)
+        data = list(data)
+        if len(data) != len(solvers):
+            raise ValueError("set_data_many_tensors: one dict (or None) per solver")
+        arr = (CMemberData * max(len(solvers), 1))()
+        keep = []  # (what the pointers name lives until the call returns)
+        for k, (sv, d) in enumerate(zip(solvers, data)):
+            d = dict(d or {})
+            unknown = set(d) - {"c", "obj_constant", "AL", "AU", "l", "u"}
+            if unknown:
+                raise ValueError(f"set_data_many_tensors: member {k}: unknown keys {sorted(unknown)}")
+            m, n = sv.model.m, sv.model.n
+            for key, length in (("c", n), ("AL", m), ("AU", m), ("l", n), ("u", n)):
+                t, addr = sv._tensor(d.get(key), length, key, f"set_data_many_tensors: member {k}")
+                keep.append(t)
+                setattr(arr[k], key, _dev_dbl(addr))
+            if d.get("obj_constant") is not None:
+                oc = C.c_double(float(d["obj_constant"]))
+                keep.append(oc)
+                arr[k].obj_constant = C.pointer(oc)
+        stream = solvers[0]._torch_stream() if solvers else None
+        if lib().hprlp_solver_set_data_many_device(hs, len(solvers), arr, stream) < 0:
+            raise RuntimeError(last_error())
+
+    @staticmethod
+    def resolve_many_tensors(solvers, x=None, y=None, sigma=None, out=None):
+        """resolve_many() from starts on the GPU, or cold, with the solutions left on the GPU (hprlp_solver_resolve_many_device).
+        x, y: lists of float64 tensors (None entries allowed) or None for all; sigma: as resolve_many.  out: a list with one
+        (x, y, z) triple of tensors to write into per solver -- any of the three, or the whole entry, may be None: not wanted; a
+        triple's x and y may be the tensors given as that member's start.  Without out the method allocates ONE tensor per kind
+        for the whole group and the members' x, y, z are views of them.  Returns a list of Results (no trace) that carry the
+        tensors as x, y, z (None where none was wanted).  No start and no solution is copied.  Same bits as resolve_many()."""
+        import torch
+        solvers, hs = Solver._handles(solvers)
+        K = len(solvers)
+        lists = []
+        for name, v in (("x", x), ("y", y), ("sigma", sigma), ("out", out)):
+            v = [None] * K if v is None else list(v)
+            if len(v) != K:
+                raise ValueError(f"resolve_many_tensors: {name} needs one entry (or None) per solver")
+            lists.append(v)
+        if out is None and K > 0:
+            device = torch.device("cuda", getattr(solvers[0], "device_number", 0))
+            ns, ms = [sv.model.n for sv in solvers], [sv.model.m for sv in solvers]
+            xs_all, zs_all = (torch.empty(sum(ns), dtype=torch.float64, device=device) for _ in range(2))
+            ys_all = torch.empty(sum(ms), dtype=torch.float64, device=device)
+            an = am = 0
+            for k in range(K):
+                lists[3][k] = (xs_all[an:an + ns[k]], ys_all[am:am + ms[k]], zs_all[an:an + ns[k]])
+                an, am = an + ns[k], am + ms[k]
+        starts = (CMemberStart * max(K, 1))()
+        dst = (CMemberOut * max(K, 1))()
+        keep, outs = [], []
+        for k, sv in enumerate(solvers):
+            who = f"resolve_many_tensors: member {k}"
+            m, n = sv.model.m, sv.model.n
+            xs, ys = sv._tensor(lists[0][k], n, "x", who), sv._tensor(lists[1][k], m, "y", who)
+            keep += [xs[0], ys[0]]
+            starts[k].x0, starts[k].y0 = _dev_dbl(xs[1]), _dev_dbl(ys[1])
+            starts[k].sigma = -1.0 if lists[2][k] is None else float(lists[2][k])
+            triple = tuple(lists[3][k]) if lists[3][k] is not None else (None, None, None)
+            if len(triple) != 3:
+                raise ValueError(f"{who}: out is an (x, y, z) triple of tensors or Nones")
+            for t, length, name in zip(triple, (n, m, n), ("x", "y", "z")):
+                if t is not None and (not isinstance(t, torch.Tensor) or not t.is_contiguous()):
+                    raise ValueError(f"{who}: out {name} must be a contiguous torch tensor (it is written in place)")
+                setattr(dst[k], name, sv._tensor(t, length, "out " + name, who)[1])
+            outs.append(triple)
+        res = (CResults * max(K, 1))()
+        stream = solvers[0]._torch_stream() if solvers else None
+        if lib().hprlp_solver_resolve_many_device(hs, K, starts, dst, stream, res) < 0:
+            raise RuntimeError(last_error())
+        results = []
+        for k, sv in enumerate(solvers):
+            r = Results(res[k], sv.model.m, sv.model.n)  # (x, y, z of the C struct are NULL)
+            r.x, r.y, r.z = outs[k]
+            results.append(r)
+        return results
+
+    @staticmethod
+    def set_matrix_many_tensors(solvers, data):
+        """set_matrix_many() for values and vectors that are on the GPU already (hprlp_solver_set_matrix_values_many_device).
+        data: per solver None (skipped) or a dict of set_matrix_tensors' keyword arguments (values, c, AL, AU, l, u as float64
+        tensors; optionally obj_constant, a host number).  As set_matrix_many() this is the C call alone:
+        power_iteration_many(), init() and a re-solve come next.  Same bits as set_matrix_many()."""
+        solvers, hs = Solver._handles(solvers)
+        data = list(data)
+        if len(data) != len(solvers):
+            raise ValueError("set_matrix_many_tensors: one dict (or None) per solver")
+        arr = (CMemberValues * max(len(solvers), 1))()
+        keep = []  # (what the pointers name lives until the call returns)
+        for k, (sv, d) in enumerate(zip(solvers, data)):
+            if d is None:
+                continue
+            d = dict(d)
+            unknown = set(d) - {"values", "c", "obj_constant", "AL", "AU", "l", "u"}
+            if unknown:
+                raise ValueError(f"set_matrix_many_tensors: member {k}: unknown keys {sorted(unknown)}")
+            who = f"set_matrix_many_tensors: member {k}"
+            m, n = sv.model.m, sv.model.n
+            v = d.get("values")
+            if v is not None:
+                if getattr(v, "ndim", 0) != 1:
+                    raise ValueError(f"{who}: values must be a one-dimensional tensor")
+                t, addr = sv._tensor(v, v.shape[0], "values", who)  # (a wrong count is the library's to refuse, naming the member)
+                keep.append(t)
+                arr[k].val, arr[k].nnz = _dev_dbl(addr), v.shape[0]
+            for key, length in (("c", n), ("AL", m), ("AU", m), ("l", n), ("u", n)):
+                t, addr = sv._tensor(d.get(key), length, key, who)
+                keep.append(t)
+                setattr(arr[k], key, _dev_dbl(addr))
+            if d.get("obj_constant") is not None:
+                oc = C.c_double(float(d["obj_constant"]))
+                keep.append(oc)
+                arr[k].obj_constant = C.pointer(oc)
+        stream = solvers[0]._torch_stream() if solvers else None
+        if lib().hprlp_solver_set_matrix_values_many_device(hs, len(solvers), arr, stream) < 0:
+            raise RuntimeError(last_error())
 
     def transfer(self):
         """The last successful set_data* / set_matrix* / resolve* call's traffic of model data and solution in bytes, host to

@@ -488,6 +488,52 @@ int hprlp_solver_set_matrix_values_many(hprlp_solver **s, int count, const hprlp
  * operations are not counted)}. */
 int hprlp_last_values_many_counts(long out[8]);
 
+/* ---- group device re-solve: the three group entries from device memory, tensors in and out (DESIGN.md "Many small LPs", group
+ * device re-solve) ------------------------------------------------------------------------------------------------------------
+ * The callers of a group produce c, the bounds and the re-linearised coefficients on the GPU, consume x and y there and carry one
+ * solve's x, y into the next as its start.  The three entries below are hprlp_solver_set_data_many, hprlp_solver_resolve_many and
+ * hprlp_solver_set_matrix_values_many with every VECTOR pointer of the member structs a DEVICE array in the caller's units and
+ * numbering (c, l, u, x0: n; AL, AU, y0: m; val: nnz); obj_constant stays a host pointer and sigma a host value, as in the single
+ * device entries.  Semantics are those of the host group entries, argument for argument: an all-NULL member is skipped, the bounds
+ * come together or not at all, start == NULL means all cold.  Nothing crosses the bus but scalars: no vector, start or solution is
+ * copied; what travels is the task tables, one flag word per member and the packed scalars.
+ *   Results: dst[k].x, .z (n) and .y (m) receive member k's solution; any may be NULL, dst == NULL or an all-NULL dst[k] means the
+ * solution is not wanted and nothing is launched for it.  out[k].x, .y, .z are NULL (hprlp_free_results stays legal); every scalar
+ * field of out[k] is as hprlp_solver_resolve_many fills it.  dst[k].x may be start[k].x0 and dst[k].y may be start[k].y0: the
+ * group's start kernels run in front of the loop, the solution kernel behind it.  Buffers of DIFFERENT members must not overlap
+ * (not checked).  hprlp_solver_transfer of every member reports 0 / 0 / 1.
+ *   Pointers: before anything is launched or written every non-NULL device pointer of every member passes the single device
+ * entries' rule (device memory of the group's device, 8-byte aligned, room for its length where the runtime reports the range).
+ * A pointer that lies with its length inside a range the runtime has already reported in this call costs no second lookup, so a
+ * group cut from a few packed tensors costs a few lookups whatever the count.  One exception to the 8 bytes: `val` of a member
+ * that joins the group launches must be 16-byte aligned (its scatter loads the values in pairs).
+ *   Ordering: one event is recorded on `stream` (the hipStream_t the inputs were produced on; NULL: the default stream), the
+ * group's stream waits for it before its first read, and the call returns after the group's stream has drained.
+ *   The device check: ONE launch checks the vectors of all members where they lie -- a NaN in c, AL, AU, l, u (set_data, matrix
+ * values; the values themselves in the same stage), a non-finite entry of x0 / y0 (resolve; none launched when all are cold) --
+ * into one flag word per member, one copy and one wait bring the verdicts back, and nothing a solver reads is written before
+ * that wait.  The message is the host group entry's for the same numbers (`<entry>: member k: c[i] is NaN`: the lowest member,
+ * then the order c, AL, AU, l, u, then the smallest index; a vector's NaN of any member wins over a non-finite value).  A NaN
+ * obj_constant or sigma is refused on the host.
+ *   Bits: every member ends bit for bit where the host group entry with the same numbers leaves it, hence where its own single
+ * call leaves it; host and device entries may alternate on one group.  A member that cannot join the group launches (off the
+ * small path, a locality ordering, bound-code arrays not in place; a group of fewer than two) runs its own
+ * hprlp_solver_set_data_device / _resolve_device / _set_matrix_values_device inside the same call, on the same caller stream,
+ * after the common checks.
+ * 0, or -1 + hprlp_last_error() naming the entry point and `member k`: the group rules, NULL data / out, a pointer that does not
+ * pass, an incomplete group, a wrong nnz, the device check.  After ANY refusal every member is unchanged bit for bit and usable.
+ * hprlp_last_resolve_many_counts / hprlp_last_values_many_counts are filled with their meanings (host-to-device copies are then
+ * task tables only; a member on its own adds its device entry's nominal operations). */
+typedef struct hprlp_member_out { double *x, *y, *z; } hprlp_member_out;   /* device; any may be NULL: not wanted */
+int hprlp_solver_set_data_many_device(hprlp_solver **s, int count, const hprlp_member_data *data, void *stream);
+int hprlp_solver_resolve_many_device(hprlp_solver **s, int count, const hprlp_member_start *start, const hprlp_member_out *dst,
+                                     void *stream, HPRLP_results *out);
+int hprlp_solver_set_matrix_values_many_device(hprlp_solver **s, int count, const hprlp_member_values *data, void *stream);
+/* The calling thread's last device group call (a refused one: up to its refusal): out = {device pointers checked, lookups issued
+ * to the runtime, check-kernel launches, flag words copied back, members served by group launches, members on their own, waits
+ * before the first write, 0} */
+int hprlp_last_many_device_counts(long out[8]);
+
 /* Named device vectors: x y x_hat x_bar y_bar z_bar x_temp y_temp y_obj last_x last_y AL AU l u c
  * row_norm col_norm A_val AT_val.  get returns the length (or -1); cap is the capacity of out. */
 long hprlp_solver_get_vector(hprlp_solver *s, const char *name, double *out, long cap);
