@@ -17,6 +17,7 @@
 #include "presolve.h"
 #include "reorder.h"
 #include "solver.h"
+#include "stream_schedule.h"
 #include "many.h"
 #include "values.h"
 #include "version.h"
@@ -686,6 +687,99 @@ extern "C" int hprlp_batched_solver_solve(hprlp_batched_solver *h, int batch_siz
         }
         *out = r;
         return 0;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+// ---- streamed batches (DESIGN.md "Streamed batches") ---------------------------------------------------------------------------
+// What can be told from the arguments alone is refused first, so that those refusals need no solver (and no GPU).
+extern "C" int hprlp_batched_solver_solve_stream(hprlp_batched_solver *h, int count, int width, const double *C, const double *AL,
+                                                 const double *AU, const double *l, const double *u, const double *obj_constants,
+                                                 const HPRLP_parameters *param, const double *X0, const double *Y0,
+                                                 const hprlp_detection *det, hprlp_batched_certificates *certs,
+                                                 HPRLP_batched_results *out) {
+    bool certs_cleared = false;  // (a call that fails after this leaves no allocation behind in certs)
+    try {
+        // (with param NULL the solver's own parameters decide, and the solver asks again)
+        stream_check_call(out != nullptr, count, width, C && AL && AU && l && u, param ? param->max_iter : 0, param ? param->check_iter : 1);
+        if (!h || !h->s) throw std::runtime_error("hprlp_batched_solver_solve_stream: null solver");
+        long mn[8];
+        batched_solver_info(h->s, mn);
+        const int m = static_cast<int>(mn[0]), n = static_cast<int>(mn[1]);
+        Detection d;  // (the starts' finite entries: the solver checks them, before it changes)
+        const bool with_det = detection_from(det, &d);
+        certs_cleared = certs != nullptr;
+        if (certs && !clear_batched_certificates(certs, count, m, n)) {
+            hprlp_free_batched_certificates(certs);
+            throw std::runtime_error("host allocation of the certificates failed");
+        }
+        std::vector<Certificate> k;
+        HPRLP_batched_results r;
+        batched_solver_solve_stream(h->s, count, width, C, AL, AU, l, u, obj_constants, param, X0, Y0, with_det ? &d : nullptr,
+                                    with_det && certs ? &k : nullptr, &r);
+        if (with_det && certs && !export_batched_certificates(k, certs)) {
+            free_batched_results(&r);
+            hprlp_free_batched_certificates(certs);
+            throw std::runtime_error("host allocation of the certificates failed");
+        }
+        *out = r;
+        return 0;
+    } catch (const std::exception &e) {
+        if (certs_cleared) hprlp_free_batched_certificates(certs);
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+extern "C" int hprlp_batched_solver_stream_record(hprlp_batched_solver *h, int *slot, int *event_in, int *event_out) {
+    try {
+        if (!h || !h->s) throw std::runtime_error("hprlp_batched_solver_stream_record: null solver");
+        return batched_solver_stream_record(h->s, slot, event_in, event_out);
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+extern "C" int hprlp_batched_solver_stream_info(hprlp_batched_solver *h, long out[8]) {
+    try {
+        if (!h || !h->s || !out) throw std::runtime_error("hprlp_batched_solver_stream_info: null solver / output");
+        batched_solver_stream_info(h->s, out, nullptr);
+        return 0;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+extern "C" int hprlp_batched_solver_stream_seconds(hprlp_batched_solver *h, double out[2]) {
+    try {
+        if (!h || !h->s || !out) throw std::runtime_error("hprlp_batched_solver_stream_seconds: null solver / output");
+        long counts[8];
+        batched_solver_stream_info(h->s, counts, out);
+        return 0;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+extern "C" int hprlp_batched_solver_lambda(hprlp_batched_solver *h, double out[2]) {
+    try {
+        if (!h || !h->s || !out) throw std::runtime_error("hprlp_batched_solver_lambda: null solver / output");
+        batched_solver_lambda(h->s, out);
+        return 0;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+extern "C" int hprlp_stream_schedule_host(int count, int width, const int *events, int *slot, int *event_in, int *event_out) {
+    try {
+        return stream_schedule(count, width, events, slot, event_in, event_out);
     } catch (const std::exception &e) {
         set_last_error(e.what());
         return -1;

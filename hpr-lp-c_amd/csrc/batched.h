@@ -29,6 +29,15 @@ void batched_solver_solve(BatchedSolver *h, int batch_size, const HPRLP_FLOAT *C
                           const HPRLP_FLOAT *l, const HPRLP_FLOAT *u, const HPRLP_FLOAT *obj_constants, const HPRLP_parameters *param,
                           const HPRLP_FLOAT *X0, const HPRLP_FLOAT *Y0, bool carry, const Detection *det,
                           std::vector<Certificate> *certs, HPRLP_batched_results *out);
+// Streamed batches (DESIGN.md "Streamed batches"; hprlp_batched_solver_solve_stream): count problems through min(width, count) slots, a
+// finished member's slot taking the next queued problem at the same evaluation.  Host arrays, column-major rows x count.
+void batched_solver_solve_stream(BatchedSolver *h, int count, int width, const HPRLP_FLOAT *C, const HPRLP_FLOAT *AL, const HPRLP_FLOAT *AU,
+                                 const HPRLP_FLOAT *l, const HPRLP_FLOAT *u, const HPRLP_FLOAT *obj_constants, const HPRLP_parameters *param,
+                                 const HPRLP_FLOAT *X0, const HPRLP_FLOAT *Y0, const Detection *det, std::vector<Certificate> *certs,
+                                 HPRLP_batched_results *out);
+int batched_solver_stream_record(const BatchedSolver *h, int *slot, int *event_in, int *event_out);  // returns count
+void batched_solver_stream_info(const BatchedSolver *h, long out[8], double seconds[2]);              // either may be what is wanted (seconds null: not)
+void batched_solver_lambda(const BatchedSolver *h, double out[2]);                                    // hprlp_batched_solver_lambda
 // The device entry (DESIGN.md "Device-resident batches"): C .. Y0 are DEVICE arrays, column-major like the host entry's, ordered on
 // `stream` (a hipStream_t); x / y / z are device buffers of n x B / m x B / n x B doubles that receive the solution in the
 // caller's units; the members' scalars go to the host arrays below (B each, status 64 bytes per member; null: not wanted).

@@ -31,6 +31,7 @@
 #include "batched.h"
 #include "env.h"
 #include "solver.h"
+#include "stream_schedule.h"
 
 namespace hprlp {
 namespace {
@@ -643,14 +644,16 @@ HPRLP_RAY_SPMM_KERNEL(kb_ray_product, RAY_PRODUCT)
 // ---- warm start (hprlp_solve_batched_warm; DESIGN.md "Warm start") ------------------------------------------------------
 // X and Y hold the members' starts, scaled on the host: project them (X into [L, U]; Y onto the sign cone of the row's sides --
 // y > 0 means the row sits at AL) and seed every panel the first iteration reads: X, X_hat, X_bar, lastX (the Halpern anchor);
-// Y, Y_bar, lastY.  Every member, the padding included (its panels are zero and stay zero).
+// Y, Y_bar, lastY.  mask null: every member, the padding included (its panels are zero and stay zero); else the members with
+// mask[k] != 0 (a streamed batch's refill seeds the members that have just entered, and no other).
 __global__ void __launch_bounds__(256) kb_start_seed(int n, int m, Geo g, double *X, double *Xh, double *Xb, double *lastX,
                                                      const double *L, const double *U, double *Y, double *Yb, double *lastY,
-                                                     const double *AL, const double *AU) {
+                                                     const double *AL, const double *AU, const int *mask) {
     const Blk blk = decode_block(g);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int kl = lane % g.Bw;
     const int sub = lane / g.Bw;
+    if (mask && !mask[blk.chunk * g.Bw + kl]) return;
     const int r0 = blk.rb * g.rows_per_block + wave * g.rows_per_wave + sub, rs = blk.nrb * g.rows_per_block;
     for (int r = r0; r < n; r += rs) {
         const size_t t = pidx(g, blk.chunk, n, r, kl);
@@ -674,12 +677,13 @@ __global__ void __launch_bounds__(256) kb_start_seed(int n, int m, Geo g, double
 // The iteration-0 evaluation of the starts, with kb_resid's geometry.  START_COL: rows of A^T gathering Y_bar; w = C - A^T y and
 // Z_bar = w where its sign has a finite bound to lean on (w > 0: L, w < 0: U), else 0 (the dual completion); partials of C.X_bar
 // (B_CX) and of the bound terms L z (z > 0), U z (z < 0) (B_XZ: what X_bar.Z_bar is at a check, Solver::set_start).  START_ROW: rows of A gathering X_bar; Y_obj = AL where y > 0, AU where y < 0, the activity
-// clamped into [AL, AU] where y = 0; partials of Y_obj.Y_bar (B_YOBJ_Y).
+// clamped into [AL, AU] where y = 0; partials of Y_obj.Y_bar (B_YOBJ_Y).  mask as kb_start_seed's: a member left out keeps its
+// `out` column and contributes 0.0 partials.
 template <bool COL>
 __global__ void __launch_bounds__(256) kb_start_spmm(int rows, const int *__restrict__ rowptr, const int *__restrict__ col,
                                                      const double *__restrict__ val, Geo g, int vrows, const double *V,
                                                      const double *p0, const double *lo, const double *hi, const double *bar,
-                                                     double *out, double *partials) {
+                                                     double *out, double *partials, const int *mask) {
     const Blk blk = decode_block(g);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int kl = lane % g.Bw, k = blk.chunk * g.Bw + kl;
@@ -689,7 +693,8 @@ __global__ void __launch_bounds__(256) kb_start_spmm(int rows, const int *__rest
     double acc[NACC];
 #pragma unroll
     for (int i = 0; i < NACC; ++i) acc[i] = 0.0;
-    for (int r = blk.rb * g.rows_per_block + wave * g.rows_per_wave + sub; r < rows; r += blk.nrb * g.rows_per_block) {
+    const bool live = !mask || mask[k] != 0;
+    for (int r = blk.rb * g.rows_per_block + wave * g.rows_per_wave + sub; live && r < rows; r += blk.nrb * g.rows_per_block) {
         double s = 0.0;
         const int e = rowptr[r + 1];
         for (int p = rowptr[r]; p < e; p += 4) {  // four entries in flight, summed in CSR order (kb_resid)
@@ -873,6 +878,97 @@ __global__ void __launch_bounds__(256) kb_carry_start(int n, int m, int B, Geo g
         const double y = (Yb[t] / rn) * co;
         Y[t] = live ? (y * rn) / cw : 0.0;
     }
+}
+
+// ---- one member into and out of a running workspace (DESIGN.md "Streamed batches") -------------------------------------------------
+// A refill pass of a streamed batch is driven by one table of {slot, problem} pairs, ordered by slot.  One thread per element,
+// element e = (row e / np, pair e % np): consecutive lanes take consecutive listed slots of ONE row before the next row.  On the
+// panel side a row of a chunk is Bw consecutive doubles, so the slots of one chunk that refill together share its lines; the
+// queue / result side is column-major per problem (problem p's vector at p * rows) and is strided by the vector's length.
+// No thread writes an element another thread touches: no atomics.
+struct SlotPair {
+    int slot, problem;
+};
+__device__ __forceinline__ size_t slot_elem(const Geo &g, int rows, int i, int slot) {
+    return pidx(g, slot / g.Bw, rows, i, slot % g.Bw);
+}
+
+constexpr int kSlotPanels = 8;  // most panels of one height a refill zeroes
+struct SlotClear {
+    double *pn[kSlotPanels], *pm[kSlotPanels];  // the n-row and the m-row panels whose listed columns become 0.0
+    int npn, npm, n, m;
+    double *SC;  // B_NSLOT_DETECT scalar slots per member
+    BatchCtl ctl;
+    double *bsc, *csc;
+    const double *q_sigma, *q_bs, *q_cs;  // per problem of the staged queue
+};
+// What a fresh workspace holds for a member, for the listed slots: zero work panels (with detection: the four ray panels), zero
+// counters, restart flag and scalar slots; sigma, b_scale, c_scale of the slot's problem and active = 1.
+// grid (ceil(max(n, m) * np / 256), npn + npm + 1): y < npn + npm one panel each, the last y the control values.
+__global__ void __launch_bounds__(256) kb_slot_clear(SlotClear a, const SlotPair *pairs, int np, Geo g) {
+    const int v = blockIdx.y;
+    const long e = static_cast<long>(blockIdx.x) * 256 + threadIdx.x;
+    if (v == a.npn + a.npm) {
+        if (e >= np) return;
+        const SlotPair pr = pairs[e];
+        const int k = pr.slot;
+        for (int s = 0; s < B_NSLOT_DETECT; ++s) a.SC[static_cast<size_t>(s) * g.Bp + k] = 0.0;
+        a.ctl.sigma[k] = a.q_sigma[pr.problem];
+        a.bsc[k] = a.q_bs[pr.problem];
+        a.csc[k] = a.q_cs[pr.problem];
+        a.ctl.kx[k] = 0;
+        a.ctl.ky[k] = 0;
+        a.ctl.restart_flag[k] = 0;
+        a.ctl.active[k] = 1;
+        return;
+    }
+    const int rows = v < a.npn ? a.n : a.m;
+    double *__restrict__ P = v < a.npn ? a.pn[v] : a.pm[v - a.npn];
+    const long i = e / np;
+    if (i >= rows) return;
+    P[slot_elem(g, rows, static_cast<int>(i), pairs[e % np].slot)] = 0.0;
+}
+
+struct SlotIn {
+    const double *src[kPanelVectors];  // the staged queue's regions, column-major rows x count
+    double *dst[kPanelVectors];        // padded panels
+    int rows[kPanelVectors];
+};
+// The listed problems' scaled vectors from the staged queue into their slots' columns: a copy, element for element what
+// kb_panel_in writes for a member.  grid (ceil(max rows * np / 256), vectors).
+__global__ void __launch_bounds__(256) kb_slot_in(SlotIn a, const SlotPair *pairs, int np, Geo g) {
+    const int v = blockIdx.y, rows = a.rows[v];
+    const long e = static_cast<long>(blockIdx.x) * 256 + threadIdx.x;
+    const long i = e / np;
+    if (i >= rows) return;
+    const SlotPair pr = pairs[e % np];
+    a.dst[v][slot_elem(g, rows, static_cast<int>(i), pr.slot)] = a.src[v][static_cast<size_t>(pr.problem) * rows + i];
+}
+
+constexpr int kSlotOutVectors = 6;  // x, y, z and, with detection, the rays d, y, A^T y, in that order ...
+constexpr int kSlotOutPlain = 3, kSlotOutDual = 4;  // ... so that a pass copies as many as its verdicts need: none, a dual one, a primal one
+enum SlotOutMap : int { SLOT_OUT_POINT = 0, SLOT_OUT_REDUCED_COST, SLOT_OUT_RAW };
+struct SlotOut {
+    const double *src[kSlotOutVectors];    // padded panels
+    double *dst[kSlotOutVectors];          // the result block's regions, column-major rows x count
+    const double *norm[kSlotOutVectors];   // cn / rn (unread for SLOT_OUT_RAW)
+    const double *scale[kSlotOutVectors];  // per SLOT: b_scale / c_scale
+    int rows[kSlotOutVectors], map[kSlotOutVectors];
+};
+// The listed slots' columns into column `problem` of the result block.  x, y, z in the caller's units by kb_panel_out's map:
+// (X / cn) * b_scale, (Y / rn) * c_scale, (Z * cn) * c_scale, in that operation order; the rays as they are (finish_certificate
+// maps them on the host).  grid (ceil(max rows * np / 256), vectors).
+__global__ void __launch_bounds__(256) kb_slot_out(SlotOut a, const SlotPair *pairs, int np, Geo g) {
+    const int v = blockIdx.y, rows = a.rows[v];
+    const long e = static_cast<long>(blockIdx.x) * 256 + threadIdx.x;
+    const long i = e / np;
+    if (i >= rows) return;
+    const SlotPair pr = pairs[e % np];
+    const double p = a.src[v][slot_elem(g, rows, static_cast<int>(i), pr.slot)];
+    double r = p;
+    if (a.map[v] == SLOT_OUT_POINT) r = (p / a.norm[v][i]) * a.scale[v][pr.slot];
+    else if (a.map[v] == SLOT_OUT_REDUCED_COST) r = (p * a.norm[v][i]) * a.scale[v][pr.slot];
+    a.dst[v][static_cast<size_t>(pr.problem) * rows + i] = r;
 }
 
 // ---- a batch from device memory (DESIGN.md "Device-resident batches") ------------------------------------------------------------
@@ -1111,8 +1207,14 @@ struct BatchWS {
     // (DS_COUNT x B) with the DF_COUNT flag words behind them, and their pinned twin
     DBuf<double> data_part, data_scal;
     HBuf<double> data_scal_h;
+    // a streamed call (DESIGN.md "Streamed batches"): the result block (x, y, z and, with detection, the rays: column p = problem
+    // p); the refill pass's tables and start mask on the device, and their pinned twin
+    DBuf<double> res_d;
+    DBuf<int> tab_d;
+    HBuf<int> tab_h;
     BatchCtl ctl{};
     double lambda_max = 1.0;
+    long bumps = 0;  // evaluations of the weighted norm that raised lambda_max, over the handle's life
     std::map<int, hipGraphExec_t> graphs;
     double graph_lambda = 0.0;  // the lambda_max the graphs alive were captured with
     long captures = 0, panel_allocs = 0;
@@ -1244,20 +1346,21 @@ void launch_restart_copy(BatchWS &w) {  // do_restart :747-769
     hipLaunchKernelGGL(kb_restart, grid_of(w, both_grids(w)), dim3(256), 0, w.stream, w.n, w.m, w.geo, w.X.p, w.lastX.p, w.Xb.p,
                        w.Y.p, w.lastY.p, w.Yb.p, w.ctl);
 }
-void launch_start_seed(BatchWS &w) {
+constexpr const int *kAllMembers = nullptr;  // the start kernels' mask of a plain solve
+void launch_start_seed(BatchWS &w, const int *mask) {
     hipLaunchKernelGGL(kb_start_seed, grid_of(w, both_grids(w)), dim3(256), 0, w.stream, w.n, w.m, w.geo, w.X.p, w.Xh.p, w.Xb.p,
-                       w.lastX.p, w.L.p, w.U.p, w.Y.p, w.Yb.p, w.lastY.p, w.AL.p, w.AU.p);
+                       w.lastX.p, w.L.p, w.U.p, w.Y.p, w.Yb.p, w.lastY.p, w.AL.p, w.AU.p, mask);
 }
-void launch_start_col(BatchWS &w) {  // Z_bar, C.X_bar and the bound terms of the start
+void launch_start_col(BatchWS &w, const int *mask) {  // Z_bar, C.X_bar and the bound terms of the start
     const CsrDev &AT = w.shared->AT.view;
     hipLaunchKernelGGL(kb_start_spmm<true>, grid_of(w, w.gx), dim3(256), 0, w.stream, AT.rows, AT.rowptr, AT.col, AT.val, w.geo, w.m,
-                       /*V*/ w.Yb.p, /*p0*/ w.C.p, /*lo*/ w.L.p, /*hi*/ w.U.p, /*bar*/ w.Xb.p, /*out*/ w.Zb.p, w.partials.p);
+                       /*V*/ w.Yb.p, /*p0*/ w.C.p, /*lo*/ w.L.p, /*hi*/ w.U.p, /*bar*/ w.Xb.p, /*out*/ w.Zb.p, w.partials.p, mask);
     finalize(w, w.gx, {B_CX, B_XZ});
 }
-void launch_start_row(BatchWS &w) {  // Y_obj and Y_obj.Y_bar of the start
+void launch_start_row(BatchWS &w, const int *mask) {  // Y_obj and Y_obj.Y_bar of the start
     const CsrDev &A = w.shared->A.view;
     hipLaunchKernelGGL(kb_start_spmm<false>, grid_of(w, w.gy), dim3(256), 0, w.stream, A.rows, A.rowptr, A.col, A.val, w.geo, w.n,
-                       /*V*/ w.Xb.p, /*p0*/ kUnread, /*lo*/ w.AL.p, /*hi*/ w.AU.p, /*bar*/ w.Yb.p, /*out*/ w.Yobj.p, w.partials.p);
+                       /*V*/ w.Xb.p, /*p0*/ kUnread, /*lo*/ w.AL.p, /*hi*/ w.AU.p, /*bar*/ w.Yb.p, /*out*/ w.Yobj.p, w.partials.p, mask);
     finalize(w, w.gy, {B_YOBJ_Y});
 }
 
@@ -1327,7 +1430,10 @@ void weighted_norm(BatchWS &w, bool dxdy_from_movement, std::vector<double> &sig
         out[k] = std::sqrt(std::max(value, 0.0));
     }
     // a bump: the graphs replay the old lambda (the stream is idle after fetch(): nothing of theirs is in flight)
-    if (w.lambda_max != lambda_before) w.drop_graphs();
+    if (w.lambda_max != lambda_before) {
+        w.drop_graphs();
+        ++w.bumps;
+    }
 }
 
 // ---- the workspace ---------------------------------------------------------------------------------------------------------
@@ -1456,10 +1562,10 @@ void ws_fill(BatchWS &w, const BatchData &d, size_t stage_count, const PanelIn &
 
 // Warm start: X / Y hold the starts in scaled units (the inverse of the results' map; kb_panel_in or kb_carry_start put them
 // there): their projection, the seeding of every panel the first iteration reads, and the iteration-0 evaluation's sums.
-void ws_start(BatchWS &w) {
-    launch_start_seed(w);
-    launch_start_col(w);
-    launch_start_row(w);
+void ws_start(BatchWS &w, const int *mask = kAllMembers) {
+    launch_start_seed(w, mask);
+    launch_start_col(w, mask);
+    launch_start_row(w, mask);
 }
 
 // ---- the loop --------------------------------------------------------------------------------------------------------------
@@ -1483,57 +1589,70 @@ struct BatchLoop {
     std::vector<double> sigma, gaps;
     std::vector<int> active, flags;
     bool dxdy_from_movement = false;
-    bool ray_have_prev = false;  // detection
+    // Per member, for a streamed batch (DESIGN.md "Streamed batches"): the loop iteration at which the member entered its slot --
+    // every rule that reads the iteration number reads iter - base[k], the member's LOCAL one -- and whether the detection has
+    // stored an iterate of it.  A plain solve: base 0 throughout, and the members active at an evaluation have all stored theirs
+    // at the same one.
+    std::vector<int> base;
+    std::vector<char> ray_prev, ray_tested;
     // restart state (:534-556)
     BatchLoop(const BatchData &d, int Bp, const HPRLP_parameters &p, const Detection *dt)
-        : prm(p), det(dt), check_iter(std::max(p.check_iter, 1)), mem(d.B), sigma(padded(d.sigma, Bp, 1.0)), active(Bp, 0), flags(Bp, 0) {
+        : prm(p), det(dt), check_iter(std::max(p.check_iter, 1)), mem(d.B), sigma(padded(d.sigma, Bp, 1.0)), active(Bp, 0), flags(Bp, 0),
+          base(d.B, 0), ray_prev(d.B, 0), ray_tested(d.B, 0) {
         std::fill_n(active.begin(), d.B, 1);
         for (int k = 0; k < d.B; ++k) mem[k].rs.best_sigma = sigma[k];
     }
 };
 
-// The evaluation at a periodic event: residuals, stopping test and the detection's verdicts of the active members.
-void loop_evaluate(BatchWS &w, BatchLoop &L) {
+// The evaluation at a periodic event: residuals, stopping test and the detection's verdicts of the active members.  first: the
+// iteration-0 evaluation (the bound term; no weighted norm, no ray test) -- of a plain solve the one at iteration 0; a streamed
+// batch gives it to the members that have just entered, only[k] != 0 (null: every member), at whatever iteration the loop is.
+void loop_evaluate(BatchWS &w, BatchLoop &L, bool first, const char *only = nullptr) {
     const BatchData &d = *w.data;
     const int B = w.B, iter = L.iter;
-    if (iter > 0) {
+    if (!first) {
         weighted_norm(w, L.dxdy_from_movement, L.sigma, L.gaps);
         for (int k = 0; k < B; ++k) L.mem[k].rs.current_gap = L.gaps[k];
     }
     launch_dual_residual(w);
     launch_primal_residual(w);
-    if (iter == 0) launch_bound_violation(w);
+    if (first) launch_bound_violation(w);
     bool ray_tested = false;
-    if (L.det && iter > 0) {
-        ray_tested = L.ray_have_prev;
+    if (L.det && !first) {  // a member's first periodic evaluation only stores its iterate
+        for (int k = 0; k < B; ++k) {
+            L.ray_tested[k] = L.active[k] && L.ray_prev[k];
+            ray_tested = ray_tested || L.ray_tested[k];
+        }
         ray_step(w, ray_tested);
-        L.ray_have_prev = true;
+        for (int k = 0; k < B; ++k)
+            if (L.active[k]) L.ray_prev[k] = 1;
     }
     fetch(w);
+    auto taken = [&](int k) { return L.active[k] && (!only || only[k]); };
     for (int k = 0; k < B; ++k) {
         // a frozen member's X_bar/Y_bar/Z_bar no longer change, so its residuals keep the
         // values of the check that froze it (the fused dot slots only cover active members)
-        if (!L.active[k]) continue;
+        if (!taken(k)) continue;
         Residuals &r = L.mem[k].r;
         assemble_residuals(&r, {sc(w, B_CX, k), sc(w, B_YOBJ_Y, k), sc(w, B_XZ, k), sc(w, B_RD2, k), sc(w, B_RP2, k), sc(w, B_LU2, k)},
-                           {d.b_scale[k], d.c_scale[k], d.norm_b_org[k], d.norm_c_org[k], d.objc[k]}, iter == 0);
+                           {d.b_scale[k], d.c_scale[k], d.norm_b_org[k], d.norm_c_org[k], d.objc[k]}, first);
         r.kkt = std::max(r.err_Rp, std::max(r.err_Rd, r.rel_gap));  // (solver.cpp nests the max() the other way, as the reference)
     }
     for (int k = 0; k < B; ++k)
-        if (L.active[k] && L.mem[k].r.kkt <= L.prm.stop_tol) {  // (<= here, strict in solver.cpp, as in the reference)
+        if (taken(k) && L.mem[k].r.kkt <= L.prm.stop_tol) {  // (<= here, strict in solver.cpp, as in the reference)
             L.mem[k].status = "OPTIMAL";
-            L.mem[k].final_iter = iter;
+            L.mem[k].final_iter = iter - L.base[k];
             L.active[k] = 0;
         }
     if (ray_tested)
         for (int k = 0; k < B; ++k) {
-            if (!L.active[k]) continue;  // (OPTIMAL at this evaluation takes precedence)
+            if (!L.active[k] || !L.ray_tested[k]) continue;  // (OPTIMAL at this evaluation takes precedence)
             const RayScalars s = ray_scalars(w, k);
             const int v = s.verdict(*L.det);
             if (!v) continue;
             Member &mb = L.mem[k];
             mb.status = v == 1 ? "PRIMAL_INFEASIBLE" : "DUAL_INFEASIBLE";
-            mb.final_iter = iter;
+            mb.final_iter = iter - L.base[k];
             L.active[k] = 0;
             mb.verdict = v;
             mb.ray = s;
@@ -1565,7 +1684,7 @@ bool loop_restart(BatchWS &w, BatchLoop &L, bool periodic) {
     bool restarted = false;
     for (int k = 0; k < B; ++k) {  // check_restart :667-700
         RestartState &rs = L.mem[k].rs;
-        if (periodic && L.active[k]) check_restart(rs, L.iter, L.check_iter, L.sigma[k], false);
+        if (periodic && L.active[k]) check_restart(rs, L.iter - L.base[k], L.check_iter, L.sigma[k], false);
         else rs.flag = 0;
         restarted = restarted || rs.flag > 0;
     }
@@ -1675,13 +1794,13 @@ void launch_panel_out(BatchWS &w, double *x, double *y, double *z) {
 }
 
 // every member's evaluation, iteration and status (arrays of B; status 64 bytes per member; a null array is not wanted)
-void member_results(const BatchLoop &L, int B, double *primal_obj, double *residuals, double *gap, int *iter, char *status) {
+void member_results(const std::vector<Member> &mem, int B, double *primal_obj, double *residuals, double *gap, int *iter, char *status) {
     for (int k = 0; k < B; ++k) {
-        if (primal_obj) primal_obj[k] = L.mem[k].r.primal_obj;
-        if (residuals) residuals[k] = L.mem[k].r.kkt;
-        if (gap) gap[k] = L.mem[k].r.rel_gap;
-        if (iter) iter[k] = L.mem[k].final_iter;
-        if (status) std::strncpy(status + 64 * k, L.mem[k].status.c_str(), 63);
+        if (primal_obj) primal_obj[k] = mem[k].r.primal_obj;
+        if (residuals) residuals[k] = mem[k].r.kkt;
+        if (gap) gap[k] = mem[k].r.rel_gap;
+        if (iter) iter[k] = mem[k].final_iter;
+        if (status) std::strncpy(status + 64 * k, mem[k].status.c_str(), 63);
     }
 }
 
@@ -1704,7 +1823,7 @@ HPRLP_batched_results collect_results(BatchWS &w, const BatchLoop &L, std::vecto
         free_batched_results(&out);
         throw;
     }
-    member_results(L, B, out.primal_obj, out.residuals, out.gap, out.iter, out.status);
+    member_results(L.mem, B, out.primal_obj, out.residuals, out.gap, out.iter, out.status);
     return out;
 }
 
@@ -1833,6 +1952,13 @@ struct BatchedSolver {
     // the ray test outside the loop (batched_solver_ray_step): a step since the last solve has stored an iterate; X_bar / Y_bar
     // have been written by name since the last solve (they are no longer that solve's solution: carry is refused)
     bool ray_have_prev = false, bars_written = false;
+    // a streamed call (DESIGN.md "Streamed batches"): the last call was one (its panels hold members of many problems: carry, the
+    // ray step and the panels by name are refused until the next plain solve); the record and the counts of the last one
+    bool streamed = false, have_stream = false;
+    std::vector<int> rec_slot, rec_in, rec_out;
+    long stream_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double stream_seconds[2] = {0, 0};  // of the last streamed call: its refill passes (harvest, refill, iteration-0 evaluation); the rest of its loop
+    double lambda_last = 0.0;           // lambda_max at the end of the last successful call of either kind (0: none yet)
 
     BatchedSolver(const LP_info_cpu *model, const HPRLP_parameters *p);
     ~BatchedSolver() {
@@ -1843,6 +1969,10 @@ struct BatchedSolver {
     void solve(int B, const double *C, const double *AL, const double *AU, const double *l, const double *u, const double *obj_constants,
                const HPRLP_parameters *p, const double *X0, const double *Y0, bool carry, const Detection *det,
                std::vector<Certificate> *certs, HPRLP_batched_results *out, DeviceBatch *dev = nullptr);
+    // count problems through min(width, count) slots, a freed slot taking the next queued problem at once (host arrays only)
+    void solve_stream(int count, int width, const double *C, const double *AL, const double *AU, const double *l, const double *u,
+                      const double *obj_constants, const HPRLP_parameters *p, const double *X0, const double *Y0, const Detection *det,
+                      std::vector<Certificate> *certs, HPRLP_batched_results *out);
 };
 
 BatchedSolver::BatchedSolver(const LP_info_cpu *model, const HPRLP_parameters *p) {
@@ -1890,6 +2020,7 @@ void BatchedSolver::solve(int B, const double *C_in, const double *AL_in, const 
     const size_t nB = static_cast<size_t>(n) * B, mB = static_cast<size_t>(m) * B;
     if (carry) {
         if (X0 || Y0) throw std::runtime_error("batched solver: carry takes its starts from the previous batch; X0 and Y0 must be null");
+        if (streamed) throw std::runtime_error("batched solver: carry refused after a streamed call (its slots held several problems each); a plain solve comes first");
         if (!have_prev) throw std::runtime_error("batched solver: carry needs a previous successful solve on this handle");
         if (B != prev_B)
             throw std::runtime_error("batched solver: carry needs the previous batch_size (" + std::to_string(prev_B) + "), got " +
@@ -1952,10 +2083,8 @@ void BatchedSolver::solve(int B, const double *C_in, const double *AL_in, const 
         BatchLoop L(data, Bp, actual, detect ? det : nullptr);
         int iC = 0, iL = 1, iU = 2, iAL = 3, iAU = 4, iX = X0 ? 5 : -1, iY = Y0 ? (X0 ? 6 : 5) : -1;  // (the regions' order, both entries)
         if (!dev) {
-            if (w.stage_h.n < stage_count) {
-                w.stage_h.alloc(stage_count, /*zero=*/false);
-                w.stage_d.alloc(stage_count);
-            }
+            if (w.stage_h.n < stage_count) w.stage_h.alloc(stage_count, /*zero=*/false);
+            if (w.stage_d.n < stage_count) w.stage_d.alloc(stage_count);  // (each by its own size: a streamed call grows the pinned one further)
             double *sh = w.stage_h.p;
             const std::vector<double> bs = padded(data.b_scale, Bp, 1.0), cs = padded(data.c_scale, Bp, 1.0);
             std::copy(L.sigma.begin(), L.sigma.end(), sh);
@@ -2010,7 +2139,7 @@ void BatchedSolver::solve(int B, const double *C_in, const double *AL_in, const 
         while (true) {  // one pass per event iteration (periodic check or iteration limit), :1017-1084
             const bool periodic = (L.iter % L.check_iter) == 0;
             const double elapsed = time_since(L.solve_start);
-            if (periodic) loop_evaluate(w, L);
+            if (periodic) loop_evaluate(w, L, L.iter == 0);
             if (loop_ended(L, elapsed)) break;
             const bool restarted = loop_restart(w, L, periodic);
             loop_advance(w, L, restarted);
@@ -2028,7 +2157,7 @@ void BatchedSolver::solve(int B, const double *C_in, const double *AL_in, const 
                                      hipMemcpyDeviceToHost, w.stream));
             HIP_CHECK(hipStreamSynchronize(w.stream));
             if (certs) collect_certificates(w, L, certs);
-            member_results(L, B, dev->primal_obj, dev->residuals, dev->gap, dev->iter, dev->status);
+            member_results(L.mem, B, dev->primal_obj, dev->residuals, dev->gap, dev->iter, dev->status);
             prev_nonfinite = data_flags_host(w, B)[DF_RESULT] != 0;
         } else {
             *out = collect_results(w, L, certs);
@@ -2052,6 +2181,8 @@ void BatchedSolver::solve(int B, const double *C_in, const double *AL_in, const 
         prev_on_device = dev != nullptr;
         ray_have_prev = false;
         bars_written = false;
+        streamed = false;
+        lambda_last = w.lambda_max;
         ++solves;
         if (dev) ++device_solves;
     } catch (...) {
@@ -2069,7 +2200,374 @@ void BatchedSolver::solve(int B, const double *C_in, const double *AL_in, const 
     }
 }
 
+// ---- streamed batches (DESIGN.md "Streamed batches") -------------------------------------------------------------------------
+// `count` problems over the shared matrix through W = min(width, count) slots of a workspace whose geometry is a plain solve's
+// of W members.  The loop is solve()'s: an evaluation at every multiple of check_iter, restart decisions, check_iter iterations.
+// A member that receives a status at an evaluation is harvested at once (kb_slot_out: its x, y, z into column p of the result
+// block) and its slot takes the next queued problem (kb_slot_clear, kb_slot_in, the start kernels masked to the new members),
+// which gets its own iteration-0 evaluation within the same event; every rule that reads the iteration number reads the member's
+// local one (BatchLoop::base).  The slot decisions are stream_assign's (stream_schedule.h).  No panel moves: the graphs survive.
+//
+// Memory of a call, beside the workspace of W members: the whole queue staged in scaled units, (3 n + 2 m) * count doubles (plus
+// (n + m) * count or part of it with starts) and 3 * count scalars; the result block, (2 n + m) * count doubles, twice that with
+// detection (the rays of the verdicts); and ONE pinned host block of the larger of the two for the upload at entry and the download
+// at the end.  Per refill pass 4 W + Bp ints go up through a second, small pinned block.  On the host, beside the pinned block:
+// prepare_batch's BatchData holds the scaled queue once more while the call runs ((3 n + 2 m) * count doubles), and the results
+// returned to the caller are (2 n + m) * count doubles (with detection the certificates' vectors of the members with a verdict).
+void BatchedSolver::solve_stream(int count, int width, const double *C_in, const double *AL_in, const double *AU_in, const double *l_in,
+                                 const double *u_in, const double *obj_constants, const HPRLP_parameters *p, const double *X0,
+                                 const double *Y0, const Detection *det, std::vector<Certificate> *certs, HPRLP_batched_results *out) {
+    // -- everything that can refuse the call, before the handle changes
+    HPRLP_parameters actual = param;
+    if (p) {
+        actual.max_iter = p->max_iter; actual.stop_tol = p->stop_tol; actual.time_limit = p->time_limit;
+        actual.check_iter = p->check_iter; actual.use_bc_scaling = p->use_bc_scaling;
+    }
+    stream_check_call(out != nullptr, count, width, C_in && AL_in && AU_in && l_in && u_in, actual.max_iter, actual.check_iter);
+    const int check_iter = std::max(actual.check_iter, 1);
+    const size_t nN = static_cast<size_t>(n) * count, mN = static_cast<size_t>(m) * count;
+    for (size_t i = 0; X0 && i < nN; ++i)
+        if (!std::isfinite(X0[i])) throw std::runtime_error("batched stream: warm start: X0[" + std::to_string(i) + "] is not finite");
+    for (size_t i = 0; Y0 && i < mN; ++i)
+        if (!std::isfinite(Y0[i])) throw std::runtime_error("batched stream: warm start: Y0[" + std::to_string(i) + "] is not finite");
+    const int W = std::min(width, count);
+    const int Bp = padded_batch(W), Bc = choose_chunk(m, n, Bp);  // (HPRLP_BATCH_CHUNK: per call)
+    const char *grid_hook = env_get("HPRLP_BATCH_GRID");
+    const int grid_cap = grid_hook ? std::atoi(grid_hook) : 0;
+    const bool new_geo = !have_geo || Bp != w.geo.Bp || Bc != w.geo.Bw;
+    const bool detect = det && det->on;
+    const bool warm = X0 || Y0;
+
+    have_prev = false;  // the panels will hold members of many problems: nothing of this call is carried
+    try {
+        // -- the whole queue in scaled units, into the pinned block behind the header of the first W members
+        const auto t_prep = time_now();
+        const BatchData q = prepare_batch(m, n, count, C_in, AL_in, AU_in, l_in, u_in, obj_constants, obj_constant, w.rn.data(), w.cn.data(),
+                                          actual.use_bc_scaling, norm_rule);
+        BatchData sd;  // the scalars of the problems in the slots: what the loop reads as "the batch" (it reads none of the vectors)
+        sd.m = m; sd.n = n; sd.B = W;
+        auto first_w = [W](const std::vector<double> &v) { return std::vector<double>(v.begin(), v.begin() + W); };
+        sd.b_scale = first_w(q.b_scale); sd.c_scale = first_w(q.c_scale); sd.norm_b = first_w(q.norm_b); sd.norm_c = first_w(q.norm_c);
+        sd.norm_b_org = first_w(q.norm_b_org); sd.norm_c_org = first_w(q.norm_c_org); sd.objc = first_w(q.objc); sd.sigma = first_w(q.sigma);
+        HPRLP_parameters loop_prm = actual;
+        loop_prm.max_iter = std::numeric_limits<int>::max();  // (the limit is each member's own: below)
+        BatchLoop L(sd, Bp, loop_prm, detect ? det : nullptr);
+        const size_t hdr = 4 * static_cast<size_t>(Bp);
+        const size_t stage_count = hdr + 3 * nN + 2 * mN + (X0 ? nN : 0) + (Y0 ? mN : 0) + 3 * static_cast<size_t>(count);
+        const size_t res_count = (2 * nN + mN) * (detect ? 2 : 1);
+        // (the pinned block serves the upload of the queue and the download of the results; its device twin only the queue)
+        if (w.stage_h.n < std::max(stage_count, res_count)) w.stage_h.alloc(std::max(stage_count, res_count), /*zero=*/false);
+        if (w.stage_d.n < stage_count) w.stage_d.alloc(stage_count);
+        if (w.res_d.n < res_count) w.res_d.alloc(res_count);
+        double *sh = w.stage_h.p;
+        const std::vector<double> bs = padded(sd.b_scale, Bp, 1.0), cs = padded(sd.c_scale, Bp, 1.0);
+        std::copy(L.sigma.begin(), L.sigma.end(), sh);
+        std::copy(bs.begin(), bs.end(), sh + Bp);
+        std::copy(cs.begin(), cs.end(), sh + 2 * Bp);
+        std::memcpy(sh + 3 * Bp, L.active.data(), sizeof(int) * Bp);
+        PanelIn in{};  // the initial fill: the first W columns of every region
+        SlotIn sin{};  // ... and a refill's way in from the same regions
+        int nvec = 0;
+        size_t off = hdr;
+        auto region = [&](const double *src, size_t cnt, int rows) {
+            std::memcpy(sh + off, src, cnt * sizeof(double));
+            in.src[nvec] = sin.src[nvec] = w.stage_d.p + off;
+            in.rows[nvec] = sin.rows[nvec] = rows;
+            off += cnt;
+            return nvec++;
+        };
+        const int iC = region(q.C.data(), nN, n), iL = region(q.L.data(), nN, n), iU = region(q.U.data(), nN, n);
+        const int iAL = region(q.AL.data(), mN, m), iAU = region(q.AU.data(), mN, m);
+        int iX = -1, iY = -1;
+        if (X0) {
+            iX = region(X0, nN, n);
+            start_to_scaled(sh + off - nN, n, count, w.cn.data(), q.b_scale);
+        }
+        if (Y0) {
+            iY = region(Y0, mN, m);
+            start_to_scaled(sh + off - mN, m, count, w.rn.data(), q.c_scale);
+        }
+        const size_t q_off = off;  // sigma | b_scale | c_scale of every problem of the queue
+        std::copy(q.sigma.begin(), q.sigma.end(), sh + q_off);
+        std::copy(q.b_scale.begin(), q.b_scale.end(), sh + q_off + count);
+        std::copy(q.c_scale.begin(), q.c_scale.end(), sh + q_off + 2 * static_cast<size_t>(count));
+        seconds[2] = time_since(t_prep);
+
+        // -- device: the workspace where the geometry is new, the first W problems into it as a plain solve's batch, their start
+        const auto t_fill = time_now();
+        w.lambda_max = lambda_created;
+        if (new_geo) {
+            w.drop_graphs();
+            have_geo = false;
+            ws_matrix_part(w, shared, make_geo(Bp, Bc));
+            ws_panels(w);
+            have_geo = true;
+        }
+        if (grid_cap != w.grid_cap || (!w.graphs.empty() && w.graph_lambda != w.lambda_max)) w.drop_graphs();
+        w.grid_cap = grid_cap;
+        double *panels[kPanelVectors] = {};
+        panels[iC] = w.C.p; panels[iL] = w.L.p; panels[iU] = w.U.p; panels[iAL] = w.AL.p; panels[iAU] = w.AU.p;
+        if (iX >= 0) panels[iX] = w.X.p;
+        if (iY >= 0) panels[iY] = w.Y.p;
+        for (int v = 0; v < nvec; ++v) in.dst[v] = sin.dst[v] = panels[v];
+        const size_t tab_count = 4 * static_cast<size_t>(W) + Bp;  // out pairs | in pairs | the start mask
+        if (w.tab_h.n < tab_count) {
+            w.tab_h.alloc(tab_count);
+            w.tab_d.alloc(tab_count);
+        }
+        HIP_CHECK(hipMemsetAsync(w.res_d.p, 0, res_count * sizeof(double), w.stream));  // (a problem that never started: zero vectors)
+        ws_fill(w, sd, stage_count, in, nvec, X0 != nullptr, Y0 != nullptr, /*carry=*/false, detect);
+        if (warm) ws_start(w);
+        if (detect && w.Zray.n != static_cast<size_t>(n) * Bp) w.Zray.alloc(static_cast<size_t>(n) * Bp);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipStreamSynchronize(w.stream));
+        seconds[3] = time_since(t_fill);
+
+        // -- the refill pass's launches: their number does not depend on how many slots a pass hands on
+        const double *qd = w.stage_d.p + q_off;
+        SlotClear sclr{};
+        sclr.n = n; sclr.m = m;
+        for (double *pn : {w.Xh.p, w.Xb.p, w.DX.p, w.Zb.p, w.lastX.p}) sclr.pn[sclr.npn++] = pn;
+        for (double *pm : {w.Yb.p, w.DY.p, w.Yobj.p, w.lastY.p}) sclr.pm[sclr.npm++] = pm;
+        if (!X0) sclr.pn[sclr.npn++] = w.X.p;
+        if (!Y0) sclr.pm[sclr.npm++] = w.Y.p;
+        if (detect) {
+            sclr.pn[sclr.npn++] = w.prevX.p; sclr.pn[sclr.npn++] = w.DS.p;
+            sclr.pm[sclr.npm++] = w.prevY.p; sclr.pm[sclr.npm++] = w.YS.p;
+        }
+        sclr.SC = w.SC.p; sclr.ctl = w.ctl; sclr.bsc = w.bsc.p; sclr.csc = w.csc.p;
+        sclr.q_sigma = qd; sclr.q_bs = qd + count; sclr.q_cs = qd + 2 * static_cast<size_t>(count);
+        double *rd = w.res_d.p;
+        const double *cnd = shared.col_norm.p, *rnd = shared.row_norm.p;
+        SlotOut sout{};
+        {
+            // (the ray d before the rays y, A^T y: a pass without a primal verdict stops short of them -- nobody has written Zray then)
+            const double *src[kSlotOutVectors] = {w.Xb.p, w.Yb.p, w.Zb.p, w.DS.p, w.YS.p, w.Zray.p};
+            double *dst[kSlotOutVectors] = {rd, rd + nN, rd + nN + mN, rd + 3 * nN + 2 * mN, rd + 2 * nN + mN, rd + 2 * nN + 2 * mN};
+            const double *norm[kSlotOutVectors] = {cnd, rnd, cnd, nullptr, nullptr, nullptr};
+            const double *scale[kSlotOutVectors] = {w.bsc.p, w.csc.p, w.csc.p, nullptr, nullptr, nullptr};
+            const int rows[kSlotOutVectors] = {n, m, n, n, m, n};
+            const int map[kSlotOutVectors] = {SLOT_OUT_POINT, SLOT_OUT_POINT, SLOT_OUT_REDUCED_COST, SLOT_OUT_RAW, SLOT_OUT_RAW, SLOT_OUT_RAW};
+            for (int v = 0; v < kSlotOutVectors; ++v) {
+                sout.src[v] = src[v]; sout.dst[v] = dst[v]; sout.norm[v] = norm[v]; sout.scale[v] = scale[v];
+                sout.rows[v] = rows[v]; sout.map[v] = map[v];
+            }
+        }
+        const SlotPair *out_pairs = reinterpret_cast<const SlotPair *>(w.tab_d.p);
+        const SlotPair *in_pairs = reinterpret_cast<const SlotPair *>(w.tab_d.p + 2 * static_cast<size_t>(W));
+        const int *new_mask = w.tab_d.p + 4 * static_cast<size_t>(W);
+        const long longest = std::max(n, m);
+        auto elem_grid = [&](int np, int ny) { return dim3(static_cast<unsigned>((longest * np + 255) / 256), ny); };
+
+        // -- the loop
+        std::vector<Member> done(count);
+        std::vector<int> occ(W), freed(W), ps(W), pp(W);  // the problem in each slot (-1: empty)
+        std::vector<char> is_new(W, 0);
+        std::vector<int> r_slot(count, -1), r_in(count, -1), r_out(count, -1);  // the record: the handle takes it when the call has succeeded
+        for (int k = 0; k < W; ++k) {
+            occ[k] = k;
+            r_slot[k] = k;
+            r_in[k] = 0;
+        }
+        StreamQueue queue;
+        queue.count = count;
+        queue.next = W;
+        long evals = 0, refill_events = 0, refills = 0, passes = 0;
+        const long bumps0 = w.bumps;
+        double refill_seconds = 0.0;
+        L.solve_start = time_now();
+        while (true) {  // one pass per periodic event
+            const double elapsed = time_since(L.solve_start);
+            const int event = L.iter / check_iter;
+            loop_evaluate(w, L, L.iter == 0);  // 1. every occupied slot, by its local iteration
+            ++evals;
+            const bool time_up = elapsed >= actual.time_limit;
+            const auto t_pass = time_now();
+            bool refilled = false, active_stale = false;
+            while (true) {  // the passes of this event: 2. harvest, 3. refill, 4. the new members' iteration-0 evaluation
+                int nout = 0;
+                bool ray_y = false, any_verdict = false;
+                for (int k = 0; k < W; ++k) {
+                    if (occ[k] < 0) continue;
+                    Member &mb = L.mem[k];
+                    const int local = L.iter - L.base[k];
+                    if (mb.status == "CONTINUE" && (time_up || local >= actual.max_iter)) {  // (the time limit first, as loop_ended)
+                        mb.status = time_up ? "TIME_LIMIT" : "ITER_LIMIT";
+                        mb.final_iter = local;
+                        L.active[k] = 0;
+                        active_stale = true;
+                    }
+                    if (mb.status == "CONTINUE") continue;
+                    freed[nout++] = k;
+                    ray_y = ray_y || mb.verdict == 1;
+                    any_verdict = any_verdict || mb.verdict != 0;
+                }
+                if (!nout) break;
+                const int nin = time_up ? 0 : stream_assign(queue, freed.data(), nout, ps.data(), pp.data());
+                int *th = w.tab_h.p;
+                for (int i = 0; i < nout; ++i) {
+                    th[2 * i] = freed[i];
+                    th[2 * i + 1] = occ[freed[i]];
+                }
+                std::fill(th + 4 * static_cast<size_t>(W), th + tab_count, 0);
+                for (int i = 0; i < nin; ++i) {
+                    th[2 * (W + i)] = ps[i];
+                    th[2 * (W + i) + 1] = pp[i];
+                    th[4 * static_cast<size_t>(W) + ps[i]] = 1;
+                }
+                HIP_CHECK(hipMemcpyAsync(w.tab_d.p, th, tab_count * sizeof(int), hipMemcpyHostToDevice, w.stream));
+                if (ray_y) {  // z = -A^T y of a primal verdict: the plain product of every column, as collect_certificates has it
+                    launch_ray_product(w);
+                    HIP_CHECK(hipGetLastError());
+                }
+                hipLaunchKernelGGL(kb_slot_out, elem_grid(nout, ray_y ? kSlotOutVectors : (any_verdict ? kSlotOutDual : kSlotOutPlain)), dim3(256), 0, w.stream, sout, out_pairs, nout,
+                                   w.geo);
+                HIP_CHECK(hipGetLastError());
+                for (int i = 0; i < nout; ++i) {
+                    const int k = freed[i], pr = occ[k];
+                    done[pr] = L.mem[k];
+                    r_out[pr] = event;
+                    occ[k] = -1;
+                }
+                if (!nin) {
+                    HIP_CHECK(hipStreamSynchronize(w.stream));  // (the pinned table is free again)
+                    break;
+                }
+                hipLaunchKernelGGL(kb_slot_clear, elem_grid(nin, sclr.npn + sclr.npm + 1), dim3(256), 0, w.stream, sclr, in_pairs, nin, w.geo);
+                HIP_CHECK(hipGetLastError());
+                hipLaunchKernelGGL(kb_slot_in, elem_grid(nin, nvec), dim3(256), 0, w.stream, sin, in_pairs, nin, w.geo);
+                HIP_CHECK(hipGetLastError());
+                if (warm) {
+                    ws_start(w, new_mask);
+                    HIP_CHECK(hipGetLastError());
+                }
+                std::fill(is_new.begin(), is_new.end(), 0);
+                for (int i = 0; i < nin; ++i) {
+                    const int k = ps[i], pr = pp[i];
+                    occ[k] = pr;
+                    r_slot[pr] = k;
+                    r_in[pr] = event;
+                    L.mem[k] = Member();
+                    L.mem[k].rs.best_sigma = q.sigma[pr];
+                    L.sigma[k] = q.sigma[pr];
+                    L.active[k] = 1;
+                    L.base[k] = L.iter;
+                    L.ray_prev[k] = 0;
+                    L.ray_tested[k] = 0;
+                    is_new[k] = 1;
+                    sd.b_scale[k] = q.b_scale[pr]; sd.c_scale[k] = q.c_scale[pr]; sd.norm_b[k] = q.norm_b[pr]; sd.norm_c[k] = q.norm_c[pr];
+                    sd.norm_b_org[k] = q.norm_b_org[pr]; sd.norm_c_org[k] = q.norm_c_org[pr]; sd.objc[k] = q.objc[pr]; sd.sigma[k] = q.sigma[pr];
+                }
+                refills += nin;
+                ++passes;
+                refilled = true;
+                loop_evaluate(w, L, /*first=*/true, is_new.data());  // (its fetch ends the pass; it uploads the active mask)
+                active_stale = false;
+            }
+            if (active_stale) w.active.upload(L.active.data(), w.Bp);
+            if (refilled) ++refill_events;
+            refill_seconds += time_since(t_pass);
+            bool any = false;
+            for (int k = 0; k < W; ++k) any = any || occ[k] >= 0;
+            if (!any) break;
+            const bool restarted = loop_restart(w, L, true);  // 5. an empty slot is an inactive one
+            loop_advance(w, L, restarted);
+        }
+        seconds[4] = time_since(L.solve_start);
+        for (int pr = queue.next; pr < count; ++pr) {  // (only the time limit leaves a problem queued)
+            done[pr].status = "TIME_LIMIT";
+            done[pr].final_iter = 0;
+            done[pr].r = Residuals();
+        }
+
+        // -- the results: one download
+        const auto t_res = time_now();
+        HPRLP_batched_results res = alloc_batched_results(m, n, count);
+        try {
+            HIP_CHECK(hipMemcpyAsync(w.stage_h.p, w.res_d.p, res_count * sizeof(double), hipMemcpyDeviceToHost, w.stream));
+            HIP_CHECK(hipStreamSynchronize(w.stream));
+            const double *rh = w.stage_h.p;
+            std::memcpy(res.x, rh, nN * sizeof(double));
+            std::memcpy(res.y, rh + nN, mN * sizeof(double));
+            std::memcpy(res.z, rh + nN + mN, nN * sizeof(double));
+            if (certs) {
+                certs->assign(count, Certificate());
+                const double *cy = rh + 2 * nN + mN, *cz = cy + mN, *cd = cz + nN;
+                for (int pr = 0; pr < count && detect; ++pr) {
+                    const Member &mb = done[pr];
+                    if (!mb.verdict) continue;
+                    Certificate &c = (*certs)[pr];
+                    const size_t om = static_cast<size_t>(pr) * m, on = static_cast<size_t>(pr) * n;
+                    if (mb.verdict == 1) {
+                        c.y.assign(cy + om, cy + om + m);
+                        c.z.assign(cz + on, cz + on + n);
+                    } else {
+                        c.d.assign(cd + on, cd + on + n);
+                    }
+                    finish_certificate(&c, mb.verdict, mb.final_iter, mb.ray, w.rn.data(), w.cn.data(), q.b_scale[pr], q.c_scale[pr]);
+                }
+            }
+        } catch (...) {
+            free_batched_results(&res);
+            throw;
+        }
+        member_results(done, count, res.primal_obj, res.residuals, res.gap, res.iter, res.status);
+        seconds[5] = time_since(t_res);
+        res.setup_time = seconds[2] + seconds[3]; res.solve_time = seconds[4]; res.power_time = 0.0; res.time = res.setup_time + res.solve_time;
+        *out = res;
+        const long stats[8] = {count, width, L.iter, evals, refill_events, refills, passes, w.bumps - bumps0};
+        std::copy(stats, stats + 8, stream_stats);
+        rec_slot = std::move(r_slot); rec_in = std::move(r_in); rec_out = std::move(r_out);
+        stream_seconds[0] = refill_seconds;
+        stream_seconds[1] = seconds[4] - refill_seconds;
+        staged[0] = static_cast<long>(stage_count * sizeof(double));
+        staged[1] = static_cast<long>(res_count * sizeof(double));
+        w.data = nullptr;
+        streamed = true;
+        have_stream = true;
+        prev_on_device = false;
+        ray_have_prev = false;
+        bars_written = false;
+        lambda_last = w.lambda_max;
+        ++solves;
+    } catch (...) {
+        // a call that failed half-way: the next call builds its workspace anew
+        (void)hipStreamSynchronize(w.stream);
+        (void)hipGetLastError();
+        w.drop_graphs();
+        w.data = nullptr;
+        have_geo = false;
+        streamed = true;
+        throw;
+    }
+}
+
 BatchedSolver *batched_solver_create(const LP_info_cpu *model, const HPRLP_parameters *param) { return new BatchedSolver(model, param); }
+void batched_solver_solve_stream(BatchedSolver *h, int count, int width, const double *C, const double *AL, const double *AU, const double *l,
+                                 const double *u, const double *obj_constants, const HPRLP_parameters *param, const double *X0,
+                                 const double *Y0, const Detection *det, std::vector<Certificate> *certs, HPRLP_batched_results *out) {
+    if (!h) throw std::runtime_error("batched stream: null handle");
+    h->solve_stream(count, width, C, AL, AU, l, u, obj_constants, param, X0, Y0, det, certs, out);
+}
+int batched_solver_stream_record(const BatchedSolver *h, int *slot, int *event_in, int *event_out) {
+    if (!h || !slot || !event_in || !event_out) throw std::runtime_error("batched stream record: null handle / output");
+    if (!h->have_stream) throw std::runtime_error("batched stream record: no successful stream call on this handle");
+    std::copy(h->rec_slot.begin(), h->rec_slot.end(), slot);
+    std::copy(h->rec_in.begin(), h->rec_in.end(), event_in);
+    std::copy(h->rec_out.begin(), h->rec_out.end(), event_out);
+    return static_cast<int>(h->rec_slot.size());
+}
+void batched_solver_stream_info(const BatchedSolver *h, long out[8], double seconds[2]) {
+    if (!h || !out) throw std::runtime_error("batched stream info: null handle / output");
+    if (!h->have_stream) throw std::runtime_error("batched stream info: no successful stream call on this handle");
+    std::copy(h->stream_stats, h->stream_stats + 8, out);
+    if (seconds) std::copy(h->stream_seconds, h->stream_seconds + 2, seconds);
+}
+void batched_solver_lambda(const BatchedSolver *h, double out[2]) {
+    if (!h || !out) throw std::runtime_error("batched solver lambda: null handle / output");
+    out[0] = h->lambda_created;
+    out[1] = h->lambda_last > 0.0 ? h->lambda_last : h->lambda_created;
+}
 void batched_solver_destroy(BatchedSolver *h) { delete h; }
 void batched_solver_solve(BatchedSolver *h, int batch_size, const double *C, const double *AL, const double *AU, const double *l,
                           const double *u, const double *obj_constants, const HPRLP_parameters *param, const double *X0, const double *Y0,
@@ -2144,6 +2642,7 @@ void batched_solver_seconds(const BatchedSolver *h, double out[6]) {
 // detection's panels) as on a handle that never stepped.
 int batched_solver_ray_step(BatchedSolver *h, const int *active, bool restart, double *out, int *tested) {
     if (!h || !active || !out || !tested) throw std::runtime_error("batched ray step: null handle / active / output");
+    if (h->streamed) throw std::runtime_error("batched ray step: refused after a streamed call (its slots held several problems each); a plain solve comes first");
     if (!h->have_prev || !h->have_geo) throw std::runtime_error("batched ray step: needs a successful solve on this handle");
     if (!restart && !h->ray_have_prev)
         throw std::runtime_error("batched ray step: no stored iterate, the first step after a solve needs restart != 0");
@@ -2199,6 +2698,7 @@ const NamedPanel &named_panel(const BatchWS &w, const std::string &name, const c
 // layout, rows x Bp (panel_index).  out null: only the count.  Returns the count of values; throws where `len` is another.
 long batched_solver_get_panel(BatchedSolver *h, const char *name, double *out, long len) {
     if (!h || !name) throw std::runtime_error("batched get_panel: null handle / name");
+    if (h->streamed) throw std::runtime_error("batched get_panel: refused after a streamed call (its slots held several problems each); a plain solve comes first");
     if (!h->have_prev || !h->have_geo) throw std::runtime_error("batched get_panel: needs a successful solve on this handle");
     BatchWS &w = h->w;
     std::string nm(name);
@@ -2236,6 +2736,7 @@ long batched_solver_get_panel(BatchedSolver *h, const char *name, double *out, l
 // what they hold).  No other panel can be written.  carry is refused until the next successful solve.
 void batched_solver_set_panel(BatchedSolver *h, const char *name, const double *in, long len) {
     if (!h || !name || !in) throw std::runtime_error("batched set_panel: null handle / name / values");
+    if (h->streamed) throw std::runtime_error("batched set_panel: refused after a streamed call (its slots held several problems each); a plain solve comes first");
     if (!h->have_prev || !h->have_geo) throw std::runtime_error("batched set_panel: needs a successful solve on this handle");
     BatchWS &w = h->w;
     const NamedPanel &p = named_panel(w, name, "batched set_panel");

@@ -219,6 +219,14 @@ def lib():
     L.hprlp_batched_solver_get_panel.restype = C.c_long
     L.hprlp_batched_solver_get_panel.argtypes = [C.c_void_p, C.c_char_p, c_dbl_p, C.c_long]
     L.hprlp_batched_solver_set_panel.argtypes = [C.c_void_p, C.c_char_p, c_dbl_p, C.c_long]
+    if hasattr(L, "hprlp_batched_solver_solve_stream"):  # (HPRLP_LIB may name a build of an earlier commit: _need_stream() says so)
+        L.hprlp_batched_solver_solve_stream.argtypes = [C.c_void_p, C.c_int, C.c_int] + [c_dbl_p] * 6 + \
+            [C.POINTER(CParameters), c_dbl_p, c_dbl_p, C.POINTER(CDetection), C.POINTER(CBatchedCertificates), C.POINTER(CBatchedResults)]
+        L.hprlp_batched_solver_stream_record.argtypes = [C.c_void_p, c_int_p, c_int_p, c_int_p]
+        L.hprlp_batched_solver_stream_info.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
+        L.hprlp_batched_solver_stream_seconds.argtypes = [C.c_void_p, c_dbl_p]
+        L.hprlp_batched_solver_lambda.argtypes = [C.c_void_p, c_dbl_p]
+        L.hprlp_stream_schedule_host.argtypes = [C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p]
     L.hprlp_batched_prepare_host_rule.argtypes =[C.c_int] * 3 + [c_dbl_p] * 9 + [C.c_int, C.c_int, C.POINTER(CBatchedPrepared)]
     L.hprlp_solver_set_start.argtypes = [C.c_void_p, c_dbl_p, c_dbl_p]
     L.hprlp_solver_set_data.argtypes = [C.c_void_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]
@@ -281,6 +289,12 @@ def lib():
 
 def last_error():
     return lib().hprlp_last_error().decode()
+
+
+def _need_stream():
+    """The streamed-batch entries are in every build of this tree; a library named by HPRLP_LIB may be older."""
+    if not hasattr(lib(), "hprlp_batched_solver_solve_stream"):
+        raise RuntimeError(f"{LIB_PATH} has no hprlp_batched_solver_solve_stream: a build of an earlier commit (HPRLP_LIB?)")
 
 
 class Parameters:
@@ -789,6 +803,80 @@ class BatchedSolver:
         self._last_B = B
         return out
 
+    _STREAM_INFO = ("count", "width", "loop_iterations", "evaluations", "refill_evaluations", "refills", "refill_passes",
+                    "lambda_bumps")
+
+    def solve_stream(self, Cmat, AL, AU, l, u, obj_constants=None, width=64, X0=None, Y0=None, eps_primal=None, eps_dual=None,
+                     prm=None):
+        """N problems through `width` slots (hprlp_batched_solver_solve_stream, DESIGN.md "Streamed batches"): Cmat, l, u (n, N),
+        AL, AU (m, N), X0 (n, N) / Y0 (m, N) or None.  A member that ends hands its slot to the next queued problem at the same
+        evaluation.  Returns solve()'s dict for the N problems plus "slot", "event_in", "event_out" (the evaluation, loop iteration
+        / check_iter, at which each problem entered and left its slot; event_in -1: never started) and, with detection,
+        "certificates".  prm None: the constructor's parameters; max_iter, each member's own limit, must be a multiple of
+        check_iter.  carry, ray_step() and get_panel() are refused afterwards until the next solve()."""
+        if not self._h:
+            raise RuntimeError("BatchedSolver: closed")
+        _need_stream()
+        N = np.asarray(Cmat).shape[1]
+
+        def panel(V, rows, name):   # (shape here, finite entries by the library, as solve())
+            if V is None:
+                return None
+            a = np.asfortranarray(V, dtype=np.float64)
+            if a.shape != (rows, N):
+                raise ValueError(f"warm start: {name} must have shape ({rows}, {N}), got {a.shape}")
+            return a
+        X0, Y0 = panel(X0, self.model.n, "X0"), panel(Y0, self.model.m, "Y0")
+        det = _detection_arg(eps_primal, eps_dual)
+        cc = CBatchedCertificates()
+        cprm = None if prm is None else prm.to_c()
+
+        def call(B, args, cp):
+            res = CBatchedResults()
+            rc = lib().hprlp_batched_solver_solve_stream(self._h, B, int(width), *args, None if cprm is None else C.byref(cprm),
+                                                         _dptr(X0), _dptr(Y0), C.byref(det) if det is not None else None,
+                                                         C.byref(cc) if det is not None else None, C.byref(res))
+            if rc != 0:
+                if det is not None:
+                    lib().hprlp_free_batched_certificates(C.byref(cc))
+                raise RuntimeError("hprlp_batched_solver_solve_stream failed: " + last_error())
+            return res
+        out = _batched_call(call, self.model, Cmat, AL, AU, l, u, obj_constants, prm)
+        if det is not None:
+            out["certificates"] = _batched_certificates(cc)
+        rec = [np.zeros(N, dtype=np.intc) for _ in range(3)]
+        if lib().hprlp_batched_solver_stream_record(self._h, *(r.ctypes.data_as(c_int_p) for r in rec)) != N:
+            raise RuntimeError("hprlp_batched_solver_stream_record failed: " + last_error())
+        out["slot"], out["event_in"], out["event_out"] = rec
+        return out
+
+    def stream_info(self):
+        """The counts of the last solve_stream(): count, width, loop_iterations (of the call), evaluations, refill_evaluations (those
+        at which a slot was refilled), refills (entries after the initial fill), refill_passes (iteration-0 evaluation passes added
+        for refills, cascades included), lambda_bumps."""
+        _need_stream()
+        out = (C.c_long * 8)()
+        if lib().hprlp_batched_solver_stream_info(self._h, out) != 0:
+            raise RuntimeError(last_error())
+        return dict(zip(self._STREAM_INFO, [int(v) for v in out]))
+
+    def stream_seconds(self):
+        """Wall seconds of the last solve_stream()'s loop: its refill passes (harvest, refill, the new members' evaluation), the rest."""
+        _need_stream()
+        out = (C.c_double * 2)()
+        if lib().hprlp_batched_solver_stream_seconds(self._h, out) != 0:
+            raise RuntimeError(last_error())
+        return dict(refill_passes=float(out[0]), rest=float(out[1]))
+
+    def lambda_max(self):
+        """(lambda_max as created, lambda_max at the end of the last successful solve() / solve_tensors() / solve_stream()): they
+        differ where the call raised it (weighted norm)."""
+        _need_stream()
+        out = (C.c_double * 2)()
+        if lib().hprlp_batched_solver_lambda(self._h, out) != 0:
+            raise RuntimeError(last_error())
+        return float(out[0]), float(out[1])
+
     def solve_tensors(self, Cmat, AL, AU, l, u, obj_constants=None, X0=None, Y0=None, carry=False, param=None, eps_primal=None,
                       eps_dual=None):
         """solve() for a batch that is on the GPU already (hprlp_batched_solver_solve_device, DESIGN.md "Device-resident batches"):
@@ -965,6 +1053,21 @@ class BatchedSolver:
         if self._h:
             lib().hprlp_batched_solver_destroy(self._h)
             self._h = None
+
+
+def stream_schedule(events, width):
+    """The schedule BatchedSolver.solve_stream() follows (hprlp_stream_schedule_host; host only, no GPU), from each problem's
+    length in evaluations (iter // check_iter; 0: it ends at its iteration-0 evaluation): (slot, event_in, event_out), arrays of
+    len(events).  The makespan in evaluations is event_out.max().  ValueError for what the library refuses."""
+    _need_stream()
+    ev = np.ascontiguousarray(events, dtype=np.intc)
+    if ev.ndim != 1:
+        raise ValueError("stream_schedule: events must be one-dimensional")
+    out = [np.zeros(max(ev.shape[0], 1), dtype=np.intc) for _ in range(3)]
+    rc = lib().hprlp_stream_schedule_host(ev.shape[0], int(width), ev.ctypes.data_as(c_int_p), *(o.ctypes.data_as(c_int_p) for o in out))
+    if rc < 0:
+        raise ValueError("hprlp_stream_schedule_host: " + last_error())
+    return tuple(o[:ev.shape[0]] for o in out)
 
 
 def _batched_call(fn, model, Cmat, AL, AU, l, u, obj_constants, param):

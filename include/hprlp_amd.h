@@ -188,6 +188,51 @@ int hprlp_batched_solver_info(hprlp_batched_solver *h, long out[8]);
  *           last solve: host prep, staging upload + panel kernels + start, loop, results' way back} */
 int hprlp_batched_solver_seconds(hprlp_batched_solver *h, double out[6]);
 
+/* ---- streamed batches: refill finished slots from a queue of LPs (DESIGN.md "Streamed batches") --------------------------------
+ * count problems over the handle's matrix through `width` slots.  C, l, u: n x count; AL, AU: m x count; X0 / Y0 as in
+ * hprlp_batched_solver_solve (either NULL), all column-major, host memory.  out: an HPRLP_batched_results of `count` members
+ * (free_batched_results), certs as hprlp_solve_batched_detect's with batch_size = count.
+ *
+ * The panel geometry is that of a plain solve of min(width, count) members; slots 0 .. min(width, count)-1 take problems 0, 1, ...
+ * At every multiple of check_iter every occupied slot is evaluated by its member's LOCAL iteration (the loop's iteration minus
+ * check_iter x event_in); a member that received a status is taken out before its slot is touched; the freed slots, ascending,
+ * take the queued problems, ascending, and the new members get their iteration-0 evaluation within the same event (one that
+ * ends there hands its slot on at once).  For a problem that sat in slot k, status, iter, x, y, z, primal_obj, residuals, gap and
+ * certificate are bit for bit those of a plain hprlp_batched_solver_solve of min(width, count) members whose slot k holds it,
+ * provided neither call raised lambda_max (hprlp_batched_solver_stream_info, hprlp_batched_solver_lambda); with count <= width
+ * the call is exactly the plain solve.  lambda_max is shared: a raise applies to every member in flight and to every later one of
+ * the call; the next call starts from the created value.
+ *
+ * max_iter is each member's own; time_limit is the call's: at the limit the running members get TIME_LIMIT with their local iter,
+ * the queued ones TIME_LIMIT, iter 0, zero vectors and event_in -1.  Refused with -1 + hprlp_last_error() before anything
+ * changes: a non-positive count or width, NULL vectors, a non-finite start, and a max_iter that is not a multiple of check_iter
+ * (every member's last event has to be a periodic event of the loop).  There is no carry and no device entry.  After a stream
+ * call, carry, hprlp_batched_solver_ray_step and the panels by name are refused until the next plain solve, which gives the bits
+ * of a handle that never streamed.
+ *
+ * Device memory of a call beside the workspace of min(width, count) members: the staged queue, (3 n + 2 m) x count doubles (plus
+ * n x count / m x count for X0 / Y0) and 3 x count scalars, and the result block, (2 n + m) x count doubles (twice that with
+ * detection); one pinned host block of the larger of the two.  Host memory beside it: the scaled queue once more while the call
+ * runs, and the returned results. */
+int hprlp_batched_solver_solve_stream(hprlp_batched_solver *h, int count, int width, const double *C, const double *AL,
+                                      const double *AU, const double *l, const double *u, const double *obj_constants,
+                                      const HPRLP_parameters *param, const double *X0, const double *Y0, const hprlp_detection *det,
+                                      hprlp_batched_certificates *certs, HPRLP_batched_results *out);
+/* per problem of the last stream call (count entries each): slot, the evaluation at which it entered and left (global loop
+ * iteration / check_iter; event_in -1: never started, then slot and event_out are -1 too).  Returns count, or -1. */
+int hprlp_batched_solver_stream_record(hprlp_batched_solver *h, int *slot, int *event_in, int *event_out);
+/* {count, width, loop iterations of the call, evaluations, evaluations at which a slot was refilled, refills (entries after the
+ *  initial fill), iteration-0 evaluation passes added for refills (cascades included), lambda bumps} */
+int hprlp_batched_solver_stream_info(hprlp_batched_solver *h, long out[8]);
+/* wall seconds of the last stream call's loop: {its refill passes (harvest, refill, the new members' evaluation), the rest} */
+int hprlp_batched_solver_stream_seconds(hprlp_batched_solver *h, double out[2]);
+/* {lambda_max as created, lambda_max at the end of the last successful call of either kind (the created one before any)} */
+int hprlp_batched_solver_lambda(hprlp_batched_solver *h, double out[2]);
+/* host only, no GPU: the schedule the loop follows, from each problem's length in evaluations (iter / check_iter; 0: it ends at
+ * its iteration-0 evaluation).  slot / event_in / event_out: count entries each.  Returns the makespan in evaluations (the
+ * largest event_out), or -1 + hprlp_last_error() (a non-positive count or width, a NULL array, a negative length). */
+int hprlp_stream_schedule_host(int count, int width, const int *events, int *slot, int *event_in, int *event_out);
+
 /* ---- device-resident batches: tensors in, tensors out (DESIGN.md "Device-resident batches") ------------------------------------
  * hprlp_batched_solver_solve with the batch's vectors already in device memory and the solution wanted there.  dC, dl, du
  * (n x B), dAL, dAU (m x B), dX0 (n x B) / dY0 (m x B; either may be NULL) are DEVICE arrays, column-major like the host entry's;
