@@ -712,27 +712,122 @@ __device__ __forceinline__ void remainder_steps(const TiledDev &t, int smid, int
 
 // Epilogue of a super-block (k_tiled_fused, k_pb_fused): row i of the block has its sum in acc[i]; the half-step / residual /
 // dot epilogue runs on it, and with PUSH the value the half-step publishes replaces the sum (the hand-off reads it from there).
-// Four rows per lane at a time, all their loads before the first update: one trip to memory per four rows instead of one
-// per row (the update's stores may alias the next row's loads as far as the compiler knows, so it kept them in order:
-// a 1984-row super-block of a mid-size matrix spent 8 us of its 96 in four such trips).
+// Four rows per lane at a time (a batch), all their loads before the first update: the update's stores may alias the next
+// row's loads as far as the compiler knows, so it keeps them in order (a 1984-row super-block of a mid-size matrix spent 8 us of
+// its 96 in four trips to memory, one per row).
+//
+// The half-steps (XEpi, YEpi) give their loads in stages, because a plain load_row per row no longer is one trip per batch:
+//   - the bounds / row sides are read only where a loaded code byte says so.  Written as conditional loads, every row of the
+//     batch became "code, s_waitcnt vmcnt(0), data": the full wait for row u+1's code also drained row u's data, four dependent
+//     trips per batch;
+//   - XEpi's rebuild of x (kXRebuild) is arithmetic on loaded values: in the middle of load_row it cost a second full wait per
+//     row, before c was even requested;
+//   - stores count in vmcnt on this ISA: the first full wait of a batch also waited for the acknowledgement of the batch
+//     before's (nontemporal) stores.
+// Issue order of batch b, the groups kept apart by scheduling barriers as in tiled_sweep (the compiler would interleave them
+// back):
+//   1. its stage-A loads -- addresses that depend on the row alone;
+//   2. its stage-B loads -- the ones the codes select, branch-free (Epi::load_b: a branch around a load costs the counted
+//      waits).  The codes are in registers already, see 3.;
+//   3. the B code bytes of batch b+1 (past the last batch: the last row's again, so that every batch looks the same);
+//   4. ONE wait for all of that, then finish (the arithmetic on loaded values), apply, stores.
+// That is one trip to memory per batch, plus one per super-block for the first batch's codes.  The wait of step 4 stands in front
+// of the guarded updates (needed_here), not inside them: see there.  It is a full one: the stores of batch b-1 are older than the
+// loads of batch b, so any wait for those loads covers their acknowledgement too -- but they have been under way since before
+// the loads were issued.  Loading stage A a batch ahead as well (two register sets) does not change that -- stage B still
+// follows the stores -- and does not fit 128 registers (built: 8-140 bytes of scratch).
+// Two sets of codes, the loop unrolled over them: a copy from "next" to "current" would wait for the loads it copies.
+// Values, operations and their order are those of load_row + apply: results do not change by a bit.
+template <class Epi, class = void>
+struct StagedLoads : std::false_type {};
+template <class Epi>
+struct StagedLoads<Epi, std::void_t<decltype(std::declval<const Epi &>().load_code(0))>> : std::true_type {};
+// every double of a struct of loaded doubles is wanted in its register at this point (the compiler waits for it here)
+template <class T>
+__device__ __forceinline__ void needed_here(const T &v) {
+    static_assert(sizeof(T) % sizeof(double) == 0 && alignof(T) == alignof(double), "a struct of doubles");
+    double d[sizeof(T) / sizeof(double)];
+    __builtin_memcpy(d, &v, sizeof(T));
+#pragma unroll
+    for (unsigned k = 0; k < sizeof(T) / sizeof(double); ++k) asm volatile("" ::"v"(d[k]));
+}
+
 template <class Epi, bool PUSH>
 __device__ __forceinline__ void epilogue_rows(const Epi &epi, double *acc, double (&racc)[Epi::NACC > 0 ? Epi::NACC : 1], int r0, int nr, int tid) {
     constexpr int NT = kTileThreads, B = 4;
-    for (int i0 = tid; i0 < nr; i0 += B * NT) {
-        typename Epi::Row rw[B];
-        double sv[B][1];
+    if constexpr (StagedLoads<Epi>::value) {
+        using Raw = decltype(epi.load_a(0));
+        using Sel = decltype(epi.load_b(0, 0, 0u));
+        // (rows past the end are clamped to the last one: branch-free loads in range, surplus lanes skip the update)
+        auto issue_codes = [&](int b0, unsigned (&cd)[B]) {
 #pragma unroll
-        for (int u = 0; u < B; ++u) {
-            const int i = min(i0 + u * NT, nr - 1);  // clamped: branch-free loads, surplus lanes skip the update
-            rw[u] = epi.load_row(r0 + i);
-            sv[u][0] = acc[i];
+            for (int u = 0; u < B; ++u) cd[u] = epi.load_code(r0 + min(b0 + tid + u * NT, nr - 1));
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        auto batch = [&](int b0, const unsigned (&cd)[B], unsigned (&cdn)[B]) {
+            Raw ra[B];
+            Sel rs[B];
+            double sv[B][1];
+#pragma unroll
+            for (int u = 0; u < B; ++u) ra[u] = epi.load_a(r0 + min(b0 + tid + u * NT, nr - 1));
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < B; ++u) rs[u] = epi.load_b(r0 + min(b0 + tid + u * NT, nr - 1), r0, cd[u]);
+            __builtin_amdgcn_sched_barrier(0);
+            issue_codes(b0 + B * NT, cdn);
+#pragma unroll
+            for (int u = 0; u < B; ++u) sv[u][0] = acc[min(b0 + tid + u * NT, nr - 1)];
+            // the batch's one wait, in front of the guarded updates and not inside them: a load whose first use sits behind
+            // `if (i < nr)` stays pending on the path around it as far as the compiler knows, and the next batch's first
+            // reuse of its register then waits for everything issued before -- this batch's stores included
+#pragma unroll
+            for (int u = 0; u < B; ++u) {
+                needed_here(ra[u]);
+                needed_here(rs[u]);
+                asm volatile("" ::"v"(cdn[u]));  // (issued right behind them; the next batch then starts without a wait)
+            }
+            typename Epi::Row rw[B];
+#pragma unroll
+            for (int u = 0; u < B; ++u) rw[u] = epi.finish(cd[u], ra[u], rs[u]);
+#pragma unroll
+            for (int u = 0; u < B; ++u) {
+                const int i = b0 + tid + u * NT;
+                if (i < nr) {
+                    if constexpr (PUSH) acc[i] = epi.apply(r0 + i, rw[u], sv[u], racc);  // the published value replaces the row sum
+                    else epi.apply(r0 + i, rw[u], sv[u], racc);
+                }
+            }
+        };
+        if (nr <= 0) return;  // (uniform; the clamp needs a last row)
+        unsigned cd0[B], cd1[B];
+        __builtin_amdgcn_sched_barrier(0);
+        issue_codes(0, cd0);
+#pragma unroll
+        for (int u = 0; u < B; ++u) asm volatile("" ::"v"(cd0[u]));  // (every batch finds its codes in registers: one state at the loop's head)
+        for (int b0 = 0;;) {  // (uniform trip count)
+            batch(b0, cd0, cd1);
+            if ((b0 += B * NT) >= nr) break;
+            batch(b0, cd1, cd0);
+            if ((b0 += B * NT) >= nr) break;
         }
+    } else {
+        // every other epilogue: a row's loads are independent of each other, one step
+        for (int i0 = tid; i0 < nr; i0 += B * NT) {
+            typename Epi::Row rw[B];
+            double sv[B][1];
 #pragma unroll
-        for (int u = 0; u < B; ++u) {
-            const int i = i0 + u * NT;
-            if (i < nr) {
-                if constexpr (PUSH) acc[i] = epi.apply(r0 + i, rw[u], sv[u], racc);  // the published value replaces the row sum
-                else epi.apply(r0 + i, rw[u], sv[u], racc);
+            for (int u = 0; u < B; ++u) {
+                const int i = min(i0 + u * NT, nr - 1);  // clamped: branch-free loads, surplus lanes skip the update
+                rw[u] = epi.load_row(r0 + i);
+                sv[u][0] = acc[i];
+            }
+#pragma unroll
+            for (int u = 0; u < B; ++u) {
+                const int i = i0 + u * NT;
+                if (i < nr) {
+                    if constexpr (PUSH) acc[i] = epi.apply(r0 + i, rw[u], sv[u], racc);  // the published value replaces the row sum
+                    else epi.apply(r0 + i, rw[u], sv[u], racc);
+                }
             }
         }
     }
@@ -1267,6 +1362,43 @@ struct XEpi {
         }
         return Row{ld(x + r), ld(c + r), li, ui, lx};
     }
+    // load_row in the stages epilogue_rows issues for a whole batch of rows (see there): the code byte; the loads whose address
+    // depends on r alone; the loads the code selects -- branch-free: a lane without a bound to read reads row `rs` instead (in
+    // range, one address for the wave) and drops the value; then the arithmetic.  Same values as load_row, bit for bit.
+    struct Raw {
+        double lx, xv, ci;
+    };
+    struct Sel {
+        double lv, uv;
+    };
+    static constexpr bool kNT = STREAMED && HPRLP_EPI_NT >= 1;
+    static __device__ __forceinline__ double ld_s(const double *p) { return kNT ? __builtin_nontemporal_load(p) : *p; }
+    __device__ __forceinline__ unsigned load_code(int r) const {
+        // no codes: "load both".  Without a branch around the load -- the counted waits of epilogue_rows do not survive one: some
+        // byte of l stands in, and code_bits() forces the bits where the byte is used (arithmetic on it here would be a wait)
+        const unsigned char *p = lu_code ? lu_code : reinterpret_cast<const unsigned char *>(l);
+        return kNT ? __builtin_nontemporal_load(p + r) : p[r];
+    }
+    __device__ __forceinline__ unsigned code_bits(unsigned loaded) const { return lu_code ? loaded : (loaded | kLoadL | kLoadU); }
+    __device__ __forceinline__ Raw load_a(int r) const {
+        const double *px = x;
+        if constexpr (kSkipsX) px = (x_mode & kXRebuild) ? x_hat : x;
+        return Raw{ld_s(last_x + r), ld_s(px + r), ld_s(c + r)};
+    }
+    __device__ __forceinline__ Sel load_b(int r, int rs, unsigned loaded) const {
+        const unsigned cd = code_bits(loaded);
+        return Sel{ld_s(l + ((cd & kLoadL) ? r : rs)), ld_s(u + ((cd & kLoadU) ? r : rs))};
+    }
+    __device__ __forceinline__ Row finish(unsigned loaded, const Raw &a, const Sel &s) const {
+        const unsigned cd = code_bits(loaded);
+        const double li = (cd & kLoadL) ? s.lv : ((cd & kZeroL) ? 0.0 : -__builtin_huge_val());
+        const double ui = (cd & kLoadU) ? s.uv : __builtin_huge_val();
+        double xi = a.xv;
+        if constexpr (kSkipsX) {
+            if (x_mode & kXRebuild) xi = f2p * a.xv + f1p * a.lx;  // = the x the previous launch did not store
+        }
+        return Row{xi, a.ci, li, ui, a.lx};
+    }
     // returns the value the half-step publishes for the other half's gather (x_hat)
     __device__ __forceinline__ double apply(int r, const Row &w, const double (&s)[1], double (&acc)[CHECK ? 3 : 1]) const {
         const double gc = s[0] - w.ci;
@@ -1339,6 +1471,31 @@ struct YEpi {
             hi = ld(AU + r);
         }
         return Row{ld(y + r), lo, hi, ld(last_y + r)};
+    }
+    // load_row in the stages epilogue_rows issues for a whole batch of rows (as XEpi's)
+    struct Raw {
+        double yi, ly;
+    };
+    struct Sel {
+        double lov, hiv;
+    };
+    static constexpr bool kNT = STREAMED && HPRLP_EPI_NT >= 1;
+    static __device__ __forceinline__ double ld_s(const double *p) { return kNT ? __builtin_nontemporal_load(p) : *p; }
+    __device__ __forceinline__ unsigned load_code(int r) const {
+        const unsigned char *p = row_code ? row_code : reinterpret_cast<const unsigned char *>(AL);  // (as XEpi's)
+        return kNT ? __builtin_nontemporal_load(p + r) : p[r];
+    }
+    __device__ __forceinline__ unsigned code_bits(unsigned loaded) const { return row_code ? loaded : (loaded | kLoadLo | kLoadHi); }
+    __device__ __forceinline__ Raw load_a(int r) const { return Raw{ld_s(y + r), ld_s(last_y + r)}; }
+    __device__ __forceinline__ Sel load_b(int r, int rs, unsigned loaded) const {
+        const unsigned cd = code_bits(loaded);
+        return Sel{ld_s(AL + ((cd & kLoadLo) ? r : rs)), ld_s(AU + ((cd & kLoadHi) ? r : rs))};
+    }
+    __device__ __forceinline__ Row finish(unsigned loaded, const Raw &a, const Sel &s) const {
+        const unsigned cd = code_bits(loaded);
+        const double hi = (cd & kLoadHi) ? s.hiv : __builtin_huge_val();
+        const double lo = (cd & kLoadLo) ? s.lov : ((cd & kRowEq) ? hi : -__builtin_huge_val());
+        return Row{a.yi, lo, hi, a.ly};
     }
     // returns the value the half-step publishes for the other half's gather (y)
     __device__ __forceinline__ double apply(int r, const Row &w, const double (&s)[1], double (&acc)[CHECK ? 2 : 1]) const {
@@ -1622,6 +1779,21 @@ struct WithBase : Epi {
         double b;
     };
     __device__ __forceinline__ Row load_row(int r) const { return Row{Epi::load_row(r), base[r]}; }
+    // Epi's staged loads (epilogue_rows), where it has them (member templates: a one-step Epi instantiates none of them);
+    // base[r] travels with the stage whose addresses depend on r alone
+    template <class A>
+    struct RawB {
+        A w;
+        double b;
+    };
+    template <class E = Epi>
+    __device__ __forceinline__ auto load_code(int r) const -> decltype(this->E::load_code(r)) { return Epi::load_code(r); }
+    template <class E = Epi>
+    __device__ __forceinline__ auto load_a(int r) const -> RawB<decltype(this->E::load_a(r))> { return {Epi::load_a(r), base[r]}; }
+    template <class E = Epi>
+    __device__ __forceinline__ auto load_b(int r, int rs, unsigned cd) const -> decltype(this->E::load_b(r, rs, cd)) { return Epi::load_b(r, rs, cd); }
+    template <class A, class S>
+    __device__ __forceinline__ Row finish(unsigned cd, const RawB<A> &a, const S &s) const { return Row{Epi::finish(cd, a.w, s), a.b}; }
     __device__ __forceinline__ auto apply(int r, const Row &w, const double (&s)[1], double (&acc)[Epi::NACC > 0 ? Epi::NACC : 1]) const {
         const double t[1] = {w.b + s[0]};
         return Epi::apply(r, w.w, t, acc);
