@@ -4,6 +4,7 @@
 // plain arrays, so that its arithmetic can be held to a restatement bit for bit without a GPU (tests/test_batch_prep.py).
 #pragma once
 
+#include <array>
 #include <cstddef>
 #include <vector>
 
@@ -53,6 +54,23 @@ struct BatchData {
     std::vector<double> b_scale, c_scale, norm_b, norm_c, norm_b_org, norm_c_org, objc;  // per member
     std::vector<double> sigma;            // the first sigma: norm_b / norm_c where both exceed 1e-8, else 1
 };
+// The per-member scalar vectors of a BatchData, enumerated once: the seven that a device-entry call computes where the batch lies,
+// in the order in which it stores them (batched.hip: DataScalar), then objc.
+constexpr int kMemberScalars = 8;
+template <class Data>  // BatchData or const BatchData
+inline auto member_scalars(Data &d) -> std::array<decltype(&d.sigma), kMemberScalars> {
+    return {{&d.b_scale, &d.c_scale, &d.norm_b, &d.norm_c, &d.norm_b_org, &d.norm_c_org, &d.sigma, &d.objc}};
+}
+// ... and the scalars of the first W members of q alone: no vectors (a streamed batch's slots at its start)
+inline BatchData first_members(const BatchData &q, int W) {
+    BatchData d;
+    d.m = q.m; d.n = q.n; d.B = W;
+    const auto to = member_scalars(d);
+    const auto from = member_scalars(q);
+    for (int s = 0; s < kMemberScalars; ++s) to[s]->assign(from[s]->begin(), from[s]->begin() + W);
+    return d;
+}
+
 // The order in which a norm's sum of squares is added up is part of its bits.  Rule 0 is the reference's: long double,
 // sequentially.  Rule 1, the "tree" rule, is one a GPU can follow, fixed by the vector's length alone (DESIGN.md "Device-resident
 // batches"; kb_data_in / kb_data_bc of batched.hip are its device side, tree_sum_of_squares below its host twin).  The terms

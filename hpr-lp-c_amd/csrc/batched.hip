@@ -1364,6 +1364,14 @@ void launch_start_row(BatchWS &w, const int *mask) {  // Y_obj and Y_obj.Y_bar o
     finalize(w, w.gy, {B_YOBJ_Y});
 }
 
+// one of a streamed call's slot kernels: a thread per element of the longest vector for each of np listed (slot, problem) pairs, ny vectors
+template <class Kernel, class Args>
+void launch_slot(BatchWS &w, Kernel kernel, const Args &a, const SlotPair *pairs, int np, int ny) {
+    const dim3 grid(static_cast<unsigned>((static_cast<long>(std::max(w.n, w.m)) * np + 255) / 256), ny);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, w.stream, a, pairs, np, w.geo);
+    HIP_CHECK(hipGetLastError());
+}
+
 void fetch(BatchWS &w) {
     HIP_CHECK(hipMemcpyAsync(w.SC_h.p, w.SC.p, sizeof(double) * w.nslot * w.Bp, hipMemcpyDeviceToHost, w.stream));
     HIP_CHECK(hipStreamSynchronize(w.stream));
@@ -1751,6 +1759,19 @@ std::vector<double> download_panel(const BatchWS &w, const DBuf<double> &P, int 
     return cm;
 }
 
+// one member's certificate from column `col` of the rays y, A^T y (primal) or d (dual): host arrays, scaled units, column-major
+void member_certificate(const BatchWS &w, Certificate &c, const Member &mb, size_t col, const double *y, const double *z, const double *d,
+                        double b_scale, double c_scale) {
+    const size_t m = w.m, n = w.n;
+    if (mb.verdict == 1) {
+        c.y.assign(y + col * m, y + col * m + m);
+        c.z.assign(z + col * n, z + col * n + n);
+    } else {
+        c.d.assign(d + col * n, d + col * n + n);
+    }
+    finish_certificate(&c, mb.verdict, mb.final_iter, mb.ray, w.rn.data(), w.cn.data(), b_scale, c_scale);
+}
+
 // the certificates of the members with a verdict: their YS / DS columns have not changed since (Solver::collect_certificate)
 void collect_certificates(BatchWS &w, const BatchLoop &L, std::vector<Certificate> *certs) {
     const int m = w.m, n = w.n;
@@ -1769,19 +1790,9 @@ void collect_certificates(BatchWS &w, const BatchLoop &L, std::vector<Certificat
         hZS = download_panel(w, w.Zray, n);
     }
     if (any_d) hDS = download_panel(w, w.DS, n);
-    for (int k = 0; k < w.B; ++k) {
-        const Member &mb = L.mem[k];
-        if (!mb.verdict) continue;
-        Certificate &c = (*certs)[k];
-        const size_t om = static_cast<size_t>(k) * m, on = static_cast<size_t>(k) * n;
-        if (mb.verdict == 1) {
-            c.y.assign(hYS.begin() + om, hYS.begin() + om + m);
-            c.z.assign(hZS.begin() + on, hZS.begin() + on + n);
-        } else {
-            c.d.assign(hDS.begin() + on, hDS.begin() + on + n);
-        }
-        finish_certificate(&c, mb.verdict, mb.final_iter, mb.ray, w.rn.data(), w.cn.data(), w.data->b_scale[k], w.data->c_scale[k]);
-    }
+    for (int k = 0; k < w.B; ++k)
+        if (L.mem[k].verdict)
+            member_certificate(w, (*certs)[k], L.mem[k], k, hYS.data(), hZS.data(), hDS.data(), w.data->b_scale[k], w.data->c_scale[k]);
 }
 
 // the bars in the caller's units, column-major rows x B, to device addresses x, y, z (kb_panel_out)
@@ -1827,21 +1838,71 @@ HPRLP_batched_results collect_results(BatchWS &w, const BatchLoop &L, std::vecto
     return out;
 }
 
+// ---- a call's way into the staging block (all three entries) ------------------------------------------------------------------------
+// The block: the header, sigma | b_scale | c_scale (Bp doubles each) | active (Bp ints in the room of Bp doubles), then the
+// column-major regions C, L, U, AL, AU and, where the call has them, X0 and Y0, of `members` members (a stream: the whole queue).
+struct Regions {
+    int nvec = 0, iX = -1, iY = -1;  // the starts' places among the regions (-1: none)
+    int rows[kPanelVectors];
+    size_t start[kPanelVectors], count[kPanelVectors], end;  // in doubles from the block's start; end: its length
+    Regions(int Bp, int n, int m, int members, bool has_x, bool has_y) : end(4 * static_cast<size_t>(Bp)) {
+        auto region = [&](int r) {
+            rows[nvec] = r;
+            start[nvec] = end;
+            end += count[nvec] = static_cast<size_t>(r) * members;
+            return nvec++;
+        };
+        for (int r : {n, n, n, m, m}) region(r);
+        if (has_x) iX = region(n);
+        if (has_y) iY = region(m);
+    }
+};
+
+// Host entries: the staging blocks grow, each by its own size (the pinned one also serves a streamed call's download); into the pinned
+// one go the header of the Bp members the loop starts with, `first`, and d's scaled vectors and the caller's starts, in scaled units.
+void stage_host(BatchWS &w, const BatchLoop &L, const BatchData &first, const Regions &r, const BatchData &d, const double *X0,
+                const double *Y0, size_t pinned, size_t device) {
+    if (w.stage_h.n < pinned) w.stage_h.alloc(pinned, /*zero=*/false);
+    if (w.stage_d.n < device) w.stage_d.alloc(device);
+    const size_t Bp = L.sigma.size();
+    double *sh = w.stage_h.p;
+    const std::vector<double> bs = padded(first.b_scale, Bp, 1.0), cs = padded(first.c_scale, Bp, 1.0);
+    std::copy(L.sigma.begin(), L.sigma.end(), sh);
+    std::copy(bs.begin(), bs.end(), sh + Bp);
+    std::copy(cs.begin(), cs.end(), sh + 2 * Bp);
+    std::memcpy(sh + 3 * Bp, L.active.data(), sizeof(int) * Bp);
+    const double *src[kPanelVectors] = {d.C.data(), d.L.data(), d.U.data(), d.AL.data(), d.AU.data(), X0 ? X0 : Y0, Y0};
+    for (int v = 0; v < r.nvec; ++v) std::memcpy(sh + r.start[v], src[v], r.count[v] * sizeof(double));
+    if (X0) start_to_scaled(sh + r.start[r.iX], w.n, d.B, w.cn.data(), d.b_scale);
+    if (Y0) start_to_scaled(sh + r.start[r.iY], w.m, d.B, w.rn.data(), d.c_scale);
+}
+
+// the regions as kb_panel_in's argument: from the device block into the workspace's panels, once both are at their addresses
+PanelIn bind_panels(const BatchWS &w, const Regions &r) {
+    PanelIn in{};
+    double *const panels[5] = {w.C.p, w.L.p, w.U.p, w.AL.p, w.AU.p};
+    for (int v = 0; v < r.nvec; ++v) {
+        in.src[v] = w.stage_d.p + r.start[v];
+        in.rows[v] = r.rows[v];
+        in.dst[v] = v < 5 ? panels[v] : (v == r.iX ? w.X.p : w.Y.p);
+    }
+    return in;
+}
+
 // ---- the device entry's own steps (DESIGN.md "Device-resident batches") ---------------------------------------------------------
+static_assert(DS_COUNT == kMemberScalars - 1, "member_scalars() lists the device entry's scalars in DataScalar's order, then objc");
 inline int *data_flags(const BatchWS &w, int B) { return reinterpret_cast<int *>(w.data_scal.p + static_cast<size_t>(DS_COUNT) * B); }
 inline const int *data_flags_host(const BatchWS &w, int B) {
     return reinterpret_cast<const int *>(w.data_scal_h.p + static_cast<size_t>(DS_COUNT) * B);
 }
 
-// prepare_batch on the device: the caller's vectors (ordered on `stream`) into the staging block in scaled units, its header, and
-// the per-member scalars on the host -- the BatchData a loop needs (it reads none of the vectors).  `in` gets the regions.
-BatchData device_prep(BatchWS &w, int B, int Bp, const double *C, const double *AL, const double *AU, const double *l, const double *u,
-                      const double *X0, const double *Y0, const double *obj_constants, double model_obj_constant, bool use_bc,
-                      hipStream_t stream, hipEvent_t ready, PanelIn &in, int &nvec) {
+// prepare_batch on the device: the caller's vectors (ordered on `stream`) into the regions r of the staging block in scaled units,
+// its header, and the per-member scalars on the host -- the BatchData a loop needs (it reads none of the vectors).
+BatchData device_prep(BatchWS &w, int B, int Bp, const Regions &r, const double *C, const double *AL, const double *AU, const double *l,
+                      const double *u, const double *X0, const double *Y0, const double *obj_constants, double model_obj_constant,
+                      bool use_bc, hipStream_t stream, hipEvent_t ready) {
     const int m = w.m, n = w.n, nseg = norm_segments(std::max(n, m));
-    const size_t nB = static_cast<size_t>(n) * B, mB = static_cast<size_t>(m) * B, hdr = 4 * static_cast<size_t>(Bp);
-    const size_t stage_count = hdr + 3 * nB + 2 * mB + (X0 ? nB : 0) + (Y0 ? mB : 0);
-    if (w.stage_d.n < stage_count) w.stage_d.alloc(stage_count);
+    if (w.stage_d.n < r.end) w.stage_d.alloc(r.end);
     const size_t part_count = static_cast<size_t>(4) * B * nseg, scal_count = static_cast<size_t>(DS_COUNT) * B + DF_COUNT;
     if (w.data_part.n < part_count) w.data_part.alloc(part_count);
     if (w.data_scal.n != scal_count) {  // (the flag words sit behind the scalars of exactly B members)
@@ -1851,17 +1912,8 @@ BatchData device_prep(BatchWS &w, int B, int Bp, const double *C, const double *
     HIP_CHECK(hipEventRecord(ready, stream));
     HIP_CHECK(hipStreamWaitEvent(w.stream, ready, 0));
     double *sd = w.stage_d.p;
-    nvec = 0;
-    size_t off = hdr;
-    auto region = [&](size_t count, int rows) {
-        in.src[nvec] = sd + off;
-        in.rows[nvec] = rows;
-        in.dst[nvec] = nullptr;  // (the panel's address: once the workspace is there)
-        off += count;
-        return const_cast<double *>(in.src[nvec++]);
-    };
-    double *rC = region(nB, n), *rL = region(nB, n), *rU = region(nB, n), *rAL = region(mB, m), *rAU = region(mB, m);
-    double *rX = X0 ? region(nB, n) : nullptr, *rY = Y0 ? region(mB, m) : nullptr;
+    double *rC = sd + r.start[0], *rL = sd + r.start[1], *rU = sd + r.start[2], *rAL = sd + r.start[3], *rAU = sd + r.start[4];
+    double *rX = X0 ? sd + r.start[r.iX] : nullptr, *rY = Y0 ? sd + r.start[r.iY] : nullptr;
     int *flags = data_flags(w, B);
     HIP_CHECK(hipMemsetAsync(flags, 0, DF_COUNT * sizeof(int), w.stream));
     const double *cn = w.shared->col_norm.p, *rn = w.shared->row_norm.p;
@@ -1880,12 +1932,235 @@ BatchData device_prep(BatchWS &w, int B, int Bp, const double *C, const double *
     BatchData d;
     d.m = m; d.n = n; d.B = B;
     const double *h = w.data_scal_h.p;
-    std::vector<double> *dst[DS_COUNT] = {&d.b_scale, &d.c_scale, &d.norm_b, &d.norm_c, &d.norm_b_org, &d.norm_c_org, &d.sigma};
+    const auto dst = member_scalars(d);
     for (int i = 0; i < DS_COUNT; ++i) dst[i]->assign(h + static_cast<size_t>(i) * B, h + static_cast<size_t>(i + 1) * B);
     d.objc.assign(B, model_obj_constant);
     if (obj_constants) d.objc.assign(obj_constants, obj_constants + B);
     return d;
 }
+
+// the device entry's results, straight into the caller's buffers; the flag word that comes back: x or y holds a non-finite entry
+bool device_results(BatchWS &w, const BatchLoop &L, DeviceBatch &dev, std::vector<Certificate> *certs) {
+    const int B = w.B;
+    const size_t nB = static_cast<size_t>(w.n) * B, mB = static_cast<size_t>(w.m) * B;
+    launch_panel_out(w, dev.x, dev.y, dev.z);
+    hipLaunchKernelGGL(kb_flag_nonfinite, dim3(static_cast<unsigned>(std::min<size_t>((nB + mB + 255) / 256, 1024))), dim3(256), 0, w.stream,
+                       static_cast<const double *>(dev.x), nB, static_cast<const double *>(dev.y), mB, data_flags(w, B) + DF_RESULT);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpyAsync(const_cast<int *>(data_flags_host(w, B)) + DF_RESULT, data_flags(w, B) + DF_RESULT, sizeof(int),
+                             hipMemcpyDeviceToHost, w.stream));
+    HIP_CHECK(hipStreamSynchronize(w.stream));
+    if (certs) collect_certificates(w, L, certs);
+    member_results(L.mem, B, dev.primal_obj, dev.residuals, dev.gap, dev.iter, dev.status);
+    return data_flags_host(w, B)[DF_RESULT] != 0;
+}
+
+// ---- a streamed call's state: the slots' side of the loop, which problem sits in which slot and the record of it, the members that
+// have ended, the queue, the counters, and the refill pass's argument blocks and tables -------------------------------------------
+struct StreamRun {
+    BatchWS &w;
+    const BatchData &q;  // the whole queue in scaled units
+    const int count, W, max_iter;  // max_iter: each member's own limit (the loop's own is unlimited)
+    const bool warm, detect;
+    BatchData sd;  // the scalars of the problems in the slots: what the loop reads as "the batch" (it reads none of the vectors)
+    HPRLP_parameters loop_prm;  // the call's, but for max_iter: unlimited
+    BatchLoop L;
+    const Regions regions;  // of the whole queue; behind them, at regions.end, sigma | b_scale | c_scale of every problem
+    // res_count: x, y, z and, with detection, the rays y, A^T y, d of every problem; tab_count: out pairs | in pairs | the start mask
+    const size_t nN, mN, stage_count, res_count, tab_count;
+    SlotClear sclr{};
+    SlotIn sin{};
+    SlotOut sout{};
+    std::vector<Member> done;
+    std::vector<int> occ, freed, ps, pp;   // the problem in each slot (-1: empty); a pass's freed slots and its (slot, problem) pairs
+    std::vector<char> is_new;
+    std::vector<int> r_slot, r_in, r_out;  // the record: the handle takes it when the call has succeeded
+    StreamQueue queue;
+    long evals = 0, refill_events = 0, refills = 0, passes = 0;
+    const long bumps0;
+    bool ray_y = false, any_verdict = false;      // of a pass's freed members: which rays their harvest copies
+
+    StreamRun(BatchWS &w_, const BatchData &q_, int W_, int Bp, const HPRLP_parameters &prm, const Detection *det, bool has_x, bool has_y)
+        : w(w_), q(q_), count(q_.B), W(W_), max_iter(prm.max_iter), warm(has_x || has_y), detect(det != nullptr), sd(first_members(q_, W_)),
+          loop_prm(prm), L(sd, Bp, loop_prm, det), regions(Bp, q_.n, q_.m, q_.B, has_x, has_y), nN(static_cast<size_t>(q_.n) * count),
+          mN(static_cast<size_t>(q_.m) * count), stage_count(regions.end + 3 * static_cast<size_t>(count)),
+          res_count((2 * nN + mN) * (detect ? 2 : 1)), tab_count(4 * static_cast<size_t>(W_) + Bp), done(count), occ(W), freed(W), ps(W),
+          pp(W), is_new(W, 0), r_slot(count, -1), r_in(count, -1), r_out(count, -1), bumps0(w_.bumps) {
+        loop_prm.max_iter = std::numeric_limits<int>::max();
+        for (int k = 0; k < W; ++k) occ[k] = r_slot[k] = k;  // (where the initial fill puts the first W problems)
+        std::fill_n(r_in.begin(), W, 0);
+        queue = StreamQueue{count, W};
+    }
+
+    // the whole queue into the pinned block, behind the header of the first W members; behind it the scalars a refill reads
+    void stage(const double *X0, const double *Y0) {
+        stage_host(w, L, sd, regions, q, X0, Y0, std::max(stage_count, res_count), stage_count);
+        if (w.res_d.n < res_count) w.res_d.alloc(res_count);
+        double *qh = w.stage_h.p + regions.end;
+        std::copy(q.sigma.begin(), q.sigma.end(), qh);
+        std::copy(q.b_scale.begin(), q.b_scale.end(), qh + count);
+        std::copy(q.c_scale.begin(), q.c_scale.end(), qh + 2 * static_cast<size_t>(count));
+    }
+
+    // Behind the initial fill, when every panel is at its address: the harvest's scratch panel, the tables (they only grow), and the
+    // refill pass's argument blocks.  in: the initial fill's way in, which a refill shares.
+    void bind(const PanelIn &in) {
+        const int n = w.n, m = w.m;
+        if (detect && w.Zray.n != static_cast<size_t>(n) * w.Bp) w.Zray.alloc(static_cast<size_t>(n) * w.Bp);
+        if (w.tab_h.n < tab_count) {
+            w.tab_h.alloc(tab_count);
+            w.tab_d.alloc(tab_count);
+        }
+        std::copy(in.src, in.src + kPanelVectors, sin.src);
+        std::copy(in.dst, in.dst + kPanelVectors, sin.dst);
+        std::copy(in.rows, in.rows + kPanelVectors, sin.rows);
+        const double *qd = w.stage_d.p + regions.end;
+        sclr.n = n; sclr.m = m;
+        for (double *pn : {w.Xh.p, w.Xb.p, w.DX.p, w.Zb.p, w.lastX.p}) sclr.pn[sclr.npn++] = pn;
+        for (double *pm : {w.Yb.p, w.DY.p, w.Yobj.p, w.lastY.p}) sclr.pm[sclr.npm++] = pm;
+        if (regions.iX < 0) sclr.pn[sclr.npn++] = w.X.p;
+        if (regions.iY < 0) sclr.pm[sclr.npm++] = w.Y.p;
+        if (detect) {
+            sclr.pn[sclr.npn++] = w.prevX.p; sclr.pn[sclr.npn++] = w.DS.p;
+            sclr.pm[sclr.npm++] = w.prevY.p; sclr.pm[sclr.npm++] = w.YS.p;
+        }
+        sclr.SC = w.SC.p; sclr.ctl = w.ctl; sclr.bsc = w.bsc.p; sclr.csc = w.csc.p;
+        sclr.q_sigma = qd; sclr.q_bs = qd + count; sclr.q_cs = qd + 2 * static_cast<size_t>(count);
+        double *rd = w.res_d.p;
+        const double *cnd = w.shared->col_norm.p, *rnd = w.shared->row_norm.p;
+        // (the ray d before the rays y, A^T y: a pass without a primal verdict stops short of them -- nobody has written Zray then)
+        sout = SlotOut{{w.Xb.p, w.Yb.p, w.Zb.p, w.DS.p, w.YS.p, w.Zray.p},
+                       {rd, rd + nN, rd + nN + mN, rd + 3 * nN + 2 * mN, rd + 2 * nN + mN, rd + 2 * nN + 2 * mN},
+                       {cnd, rnd, cnd, nullptr, nullptr, nullptr},
+                       {w.bsc.p, w.csc.p, w.csc.p, nullptr, nullptr, nullptr},
+                       {n, m, n, n, m, n},
+                       {SLOT_OUT_POINT, SLOT_OUT_POINT, SLOT_OUT_REDUCED_COST, SLOT_OUT_RAW, SLOT_OUT_RAW, SLOT_OUT_RAW}};
+    }
+    const SlotPair *out_pairs() const { return reinterpret_cast<const SlotPair *>(w.tab_d.p); }
+    const SlotPair *in_pairs() const { return reinterpret_cast<const SlotPair *>(w.tab_d.p + 2 * static_cast<size_t>(W)); }
+    const int *new_mask() const { return w.tab_d.p + 4 * static_cast<size_t>(W); }
+
+    // the limit rule (time first, as loop_ended; then the member's own max_iter), then the slots whose member has a status: freed[0 .. return)
+    int expire_and_collect(bool time_up, bool &active_stale) {
+        int nout = 0;
+        ray_y = any_verdict = false;
+        for (int k = 0; k < W; ++k) {
+            if (occ[k] < 0) continue;
+            Member &mb = L.mem[k];
+            const int local = L.iter - L.base[k];
+            if (mb.status == "CONTINUE" && (time_up || local >= max_iter)) {
+                mb.status = time_up ? "TIME_LIMIT" : "ITER_LIMIT";
+                mb.final_iter = local;
+                L.active[k] = 0;
+                active_stale = true;
+            }
+            if (mb.status == "CONTINUE") continue;
+            freed[nout++] = k;
+            ray_y = ray_y || mb.verdict == 1;
+            any_verdict = any_verdict || mb.verdict != 0;
+        }
+        return nout;
+    }
+
+    // the pass's table up (freed slots; the refill's pairs and start mask), then the freed members' x, y, z and rays into the result block
+    void harvest(int nout, int nin) {
+        const int event = L.iter / L.check_iter;
+        int *th = w.tab_h.p;
+        for (int i = 0; i < nout; ++i) {  // (and the host's side of the hand-over: the member is kept, its slot is empty)
+            const int k = freed[i], pr = occ[k];
+            th[2 * i] = k;
+            th[2 * i + 1] = pr;
+            done[pr] = L.mem[k];
+            r_out[pr] = event;
+            occ[k] = -1;
+        }
+        std::fill(th + 4 * static_cast<size_t>(W), th + tab_count, 0);
+        for (int i = 0; i < nin; ++i) {
+            th[2 * (W + i)] = ps[i];
+            th[2 * (W + i) + 1] = pp[i];
+            th[4 * static_cast<size_t>(W) + ps[i]] = 1;
+        }
+        HIP_CHECK(hipMemcpyAsync(w.tab_d.p, th, tab_count * sizeof(int), hipMemcpyHostToDevice, w.stream));
+        if (ray_y) {  // z = -A^T y of a primal verdict: the plain product of every column, as collect_certificates has it
+            launch_ray_product(w);
+            HIP_CHECK(hipGetLastError());
+        }
+        launch_slot(w, kb_slot_out, sout, out_pairs(), nout, ray_y ? kSlotOutVectors : (any_verdict ? kSlotOutDual : kSlotOutPlain));
+    }
+
+    // the queued problems into their slots (cleared, filled, started), the slots' host side re-seated, the new members' iteration-0 evaluation
+    void refill(int nin) {
+        const int event = L.iter / L.check_iter;
+        launch_slot(w, kb_slot_clear, sclr, in_pairs(), nin, sclr.npn + sclr.npm + 1);
+        launch_slot(w, kb_slot_in, sin, in_pairs(), nin, regions.nvec);
+        if (warm) {
+            ws_start(w, new_mask());
+            HIP_CHECK(hipGetLastError());
+        }
+        const auto slot = member_scalars(sd);
+        const auto queued = member_scalars(q);
+        std::fill(is_new.begin(), is_new.end(), 0);
+        for (int i = 0; i < nin; ++i) {
+            const int k = ps[i], pr = pp[i];
+            occ[k] = pr;
+            r_slot[pr] = k;
+            r_in[pr] = event;
+            L.mem[k] = Member();
+            L.mem[k].rs.best_sigma = q.sigma[pr];
+            L.sigma[k] = q.sigma[pr];
+            L.active[k] = 1;
+            L.base[k] = L.iter;
+            L.ray_prev[k] = 0;
+            L.ray_tested[k] = 0;
+            is_new[k] = 1;
+            for (int s = 0; s < kMemberScalars; ++s) (*slot[s])[k] = (*queued[s])[pr];
+        }
+        refills += nin;
+        ++passes;
+        loop_evaluate(w, L, /*first=*/true, is_new.data());
+    }
+
+    // one pass of an event; false when it handed no slot on (nobody ended, the queue is empty, the time is up): the event is over
+    bool pass(bool time_up, bool &active_stale) {
+        const int nout = expire_and_collect(time_up, active_stale);
+        if (!nout) return false;
+        const int nin = time_up ? 0 : stream_assign(queue, freed.data(), nout, ps.data(), pp.data());
+        harvest(nout, nin);
+        if (!nin) {
+            HIP_CHECK(hipStreamSynchronize(w.stream));  // (the pinned table is free again)
+            return false;
+        }
+        refill(nin);
+        active_stale = false;
+        return true;
+    }
+    bool occupied() const { return std::any_of(occ.begin(), occ.end(), [](int pr) { return pr >= 0; }); }
+
+    // all `count` problems: one download of the result block, the members' evaluations, the certificates from the rays beside the solutions
+    HPRLP_batched_results results(std::vector<Certificate> *certs) {
+        for (int pr = queue.next; pr < count; ++pr) done[pr].status = "TIME_LIMIT";  // (only the time limit leaves a problem queued: iteration 0, no residuals)
+        HPRLP_batched_results res = alloc_batched_results(w.m, w.n, count);
+        try {
+            HIP_CHECK(hipMemcpyAsync(w.stage_h.p, w.res_d.p, res_count * sizeof(double), hipMemcpyDeviceToHost, w.stream));
+            HIP_CHECK(hipStreamSynchronize(w.stream));
+            const double *rh = w.stage_h.p;
+            std::memcpy(res.x, rh, nN * sizeof(double));
+            std::memcpy(res.y, rh + nN, mN * sizeof(double));
+            std::memcpy(res.z, rh + nN + mN, nN * sizeof(double));
+            if (certs) {
+                certs->assign(count, Certificate());
+                const double *cy = rh + 2 * nN + mN, *cz = cy + mN, *cd = cz + nN;
+                for (int pr = 0; pr < count && detect; ++pr)
+                    if (done[pr].verdict) member_certificate(w, (*certs)[pr], done[pr], pr, cy, cz, cd, q.b_scale[pr], q.c_scale[pr]);
+            }
+        } catch (...) {
+            free_batched_results(&res);
+            throw;
+        }
+        member_results(done, count, res.primal_obj, res.residuals, res.gap, res.iter, res.status);
+        return res;
+    }
+};
 
 }  // namespace
 
@@ -1925,12 +2200,10 @@ void warm_batched_tu() {
     (void)hipFuncGetAttributes(&a, reinterpret_cast<const void *>(&kb_finalize));
 }
 
-// ---- the resident solver (DESIGN.md "Resident batches") -------------------------------------------------------------------
-// Over the handle's life: the scaled shared matrix, its norms on the host, the created lambda_max, the staging blocks (they only
-// grow).  While Bp and Bc stay: order tables, every panel and control buffer at its address, and (also while the grid cap
-// and the lambda a call starts with stay) the captured graphs.  Per call: prepare_batch, ws_fill, the loop, the results -- or, for
-// a batch that is in device memory already (DESIGN.md "Device-resident batches"), device_prep in prepare_batch's place, ws_fill
-// without its upload, and kb_panel_out straight into the caller's device buffers.
+// ---- the resident solver (DESIGN.md "Resident batches": what is kept over the handle's life, and what while Bp and Bc stay) -------
+// Every call, of whichever entry, is one sequence of steps: refuse (before the handle changes); call_parameters; plan_geometry; the
+// batch in scaled units into the staging block (prepare_batch and stage_host, or device_prep where it lies); ensure_workspace;
+// bind_panels, ws_fill, ws_start; the loop (a streamed call's StreamRun hands slots on inside it); the results; call_succeeded or call_failed.
 struct BatchedSolver {
     int m = 0, n = 0;
     double obj_constant = 0.0;
@@ -1973,7 +2246,119 @@ struct BatchedSolver {
     void solve_stream(int count, int width, const double *C, const double *AL, const double *AU, const double *l, const double *u,
                       const double *obj_constants, const HPRLP_parameters *p, const double *X0, const double *Y0, const Detection *det,
                       std::vector<Certificate> *certs, HPRLP_batched_results *out);
+
+    // the handle's parameters with the caller's max_iter, stop_tol, time_limit, check_iter and use_bc_scaling (p null: the handle's)
+    HPRLP_parameters call_parameters(const HPRLP_parameters *p) const {
+        HPRLP_parameters actual = param;
+        if (p) {
+            actual.max_iter = p->max_iter; actual.stop_tol = p->stop_tol; actual.time_limit = p->time_limit;
+            actual.check_iter = p->check_iter; actual.use_bc_scaling = p->use_bc_scaling;
+        }
+        return actual;
+    }
+    // the panel geometry of `members` members (HPRLP_BATCH_CHUNK: per call), and whether the workspace has another
+    Geo plan_geometry(int members) const {
+        const int Bp = padded_batch(members);
+        return make_geo(Bp, choose_chunk(m, n, Bp));
+    }
+    bool new_geometry(const Geo &g) const { return !have_geo || g.Bp != w.geo.Bp || g.Bw != w.geo.Bw; }
+    // what a streamed call has left -- slots that held several problems each -- serves no carry, ray step or panel by name
+    void refuse_after_stream(const char *who) const {
+        if (streamed)
+            throw std::runtime_error(std::string(who) + " refused after a streamed call (its slots held several problems each); a plain solve comes first");
+    }
+    // a carry's refusals, in this order: what the call asks for, what the handle holds, the geometry, the previous solution's values
+    void refuse_carry(int B, const double *X0, const double *Y0, bool new_geo) const {
+        if (X0 || Y0) throw std::runtime_error("batched solver: carry takes its starts from the previous batch; X0 and Y0 must be null");
+        refuse_after_stream("batched solver: carry");
+        if (!have_prev) throw std::runtime_error("batched solver: carry needs a previous successful solve on this handle");
+        if (B != prev_B)
+            throw std::runtime_error("batched solver: carry needs the previous batch_size (" + std::to_string(prev_B) + "), got " +
+                                     std::to_string(B));
+        if (bars_written)
+            throw std::runtime_error("batched solver: carry refused, X_bar / Y_bar were written by name since the previous solve "
+                                     "(they are no longer its solution)");
+        if (new_geo) throw std::runtime_error("batched solver: carry needs the previous call's chunk width (HPRLP_BATCH_CHUNK changed)");
+        const double *prev = w.stage_h.p;  // x (n x B) and y (m x B) as the previous call returned them
+        bool bad = prev_on_device && prev_nonfinite;
+        for (size_t i = 0; !prev_on_device && !bad && i < (static_cast<size_t>(n) + m) * B; ++i) bad = !std::isfinite(prev[i]);
+        if (bad) throw std::runtime_error("batched solver: carry refused, the previous batch's solution holds a non-finite value");
+    }
+    // the device entry: no pointer reaches a kernel before all of them have passed
+    void check_device_call(const DeviceBatch &dev, int B, const double *C, const double *AL, const double *AU, const double *l,
+                           const double *u, const double *X0, const double *Y0) {
+        const size_t nB = static_cast<size_t>(n) * B, mB = static_cast<size_t>(m) * B;
+        if (B > 65535) throw std::runtime_error("batched solver: the device entry takes at most 65535 members");
+        const std::pair<const double *, size_t> in_ptrs[5] = {{C, nB}, {AL, mB}, {AU, mB}, {l, nB}, {u, nB}};
+        const char *in_names[5] = {"C", "AL", "AU", "l", "u"};
+        for (int i = 0; i < 5; ++i) check_device_pointer(in_ptrs[i].first, in_ptrs[i].second, device, in_names[i]);
+        if (X0) check_device_pointer(X0, nB, device, "X0");
+        if (Y0) check_device_pointer(Y0, mB, device, "Y0");
+        check_device_pointer(dev.x, nB, device, "x");
+        check_device_pointer(dev.y, mB, device, "y");
+        check_device_pointer(dev.z, nB, device, "z");
+        if (!inputs_ready) HIP_CHECK(hipEventCreateWithFlags(&inputs_ready, hipEventDisableTiming));
+    }
+    // the workspace of geometry g and lambda_max as created, whatever the handle solved before; the graphs go with a panel, the grid cap or their lambda
+    void ensure_workspace(const Geo &g) {
+        const char *grid_hook = env_get("HPRLP_BATCH_GRID");
+        const int grid_cap = grid_hook ? std::atoi(grid_hook) : 0;
+        w.lambda_max = lambda_created;
+        if (new_geometry(g)) {
+            w.drop_graphs();
+            have_geo = false;
+            ws_matrix_part(w, shared, g);
+            ws_panels(w);
+            have_geo = true;
+        }
+        if (grid_cap != w.grid_cap || (!w.graphs.empty() && w.graph_lambda != w.lambda_max)) w.drop_graphs();
+        w.grid_cap = grid_cap;
+    }
+    template <class Result>  // HPRLP_batched_results, DeviceBatch
+    void set_times(Result &r) const {
+        r.setup_time = seconds[2] + seconds[3]; r.solve_time = seconds[4]; r.power_time = 0.0;
+        r.time = r.setup_time + r.solve_time;
+    }
+    // what every successful call leaves; data: the batch a later call may carry -- null after a streamed call, which leaves none
+    void call_succeeded(size_t h2d_bytes, size_t d2h_bytes, const BatchData *data, bool device_entry) {
+        staged[0] = static_cast<long>(h2d_bytes);
+        staged[1] = static_cast<long>(d2h_bytes);
+        w.data = nullptr;
+        if (data) {
+            last_scalars.clear();
+            const auto scalars = member_scalars(*data);
+            for (int i = 0; i < DS_COUNT; ++i) last_scalars.insert(last_scalars.end(), scalars[i]->begin(), scalars[i]->end());
+            have_prev = true;
+            prev_B = data->B;
+        }
+        prev_on_device = device_entry;
+        ray_have_prev = bars_written = false;
+        streamed = !data;
+        have_stream = have_stream || streamed;
+        lambda_last = w.lambda_max;
+        ++solves;
+        if (device_entry) ++device_solves;
+    }
+    // a call that failed half-way: nothing of it is carried, and the next call builds its workspace anew
+    void call_failed(bool streamed_call) {
+        (void)hipStreamSynchronize(w.stream);
+        (void)hipGetLastError();
+        w.drop_graphs();
+        w.data = nullptr;
+        have_geo = false;
+        if (streamed_call) streamed = true;
+    }
 };
+
+// Test hook HPRLP_BATCH_LAMBDA (0: not set): the caller's lambda_max for the power iteration's; of a computed one only the constructor checks
+double checked_lambda(double v) {
+    if (!(v > 0.0) || !std::isfinite(v)) throw std::runtime_error("HPRLP_BATCH_LAMBDA is not a positive finite number");
+    return v;
+}
+double lambda_hook() {
+    const char *hook = env_get("HPRLP_BATCH_LAMBDA");
+    return hook ? checked_lambda(std::strtod(hook, nullptr)) : 0.0;
+}
 
 BatchedSolver::BatchedSolver(const LP_info_cpu *model, const HPRLP_parameters *p) {
     if (!model || !model->A) throw std::runtime_error("batched solver: null model");
@@ -2001,12 +2386,9 @@ BatchedSolver::BatchedSolver(const LP_info_cpu *model, const HPRLP_parameters *p
     w.stream = shared.stream;
     HIP_CHECK(hipGetDevice(&device));
     seconds[0] = time_since(t0);
-    // lambda_max on the scaled shared matrix (:994-1001)
-    // (test hook HPRLP_BATCH_LAMBDA: the caller's value instead, so that a reference can run on the same bits)
     const auto t1 = time_now();
-    const char *lambda_hook = env_get("HPRLP_BATCH_LAMBDA");
-    lambda_created = lambda_hook ? std::strtod(lambda_hook, nullptr) : shared.power_iteration(5000, 1.0e-4, nullptr) * 1.01;
-    if (!(lambda_created > 0.0) || !std::isfinite(lambda_created)) throw std::runtime_error("HPRLP_BATCH_LAMBDA is not a positive finite number");
+    const double hook = lambda_hook();  // lambda_max on the scaled shared matrix (:994-1001), or the hook's
+    lambda_created = checked_lambda(hook > 0.0 ? hook : shared.power_iteration(5000, 1.0e-4, nullptr) * 1.01);
     seconds[1] = time_since(t1);
 }
 
@@ -2017,121 +2399,40 @@ void BatchedSolver::solve(int B, const double *C_in, const double *AL_in, const 
     if (!out && !dev) throw std::runtime_error("batched solver: null results");
     if (B <= 0) throw std::runtime_error("batched solver: batch_size must be positive");
     if (!C_in || !AL_in || !AU_in || !l_in || !u_in) throw std::runtime_error("batched solver: null C / AL / AU / l / u");
-    const size_t nB = static_cast<size_t>(n) * B, mB = static_cast<size_t>(m) * B;
-    if (carry) {
-        if (X0 || Y0) throw std::runtime_error("batched solver: carry takes its starts from the previous batch; X0 and Y0 must be null");
-        if (streamed) throw std::runtime_error("batched solver: carry refused after a streamed call (its slots held several problems each); a plain solve comes first");
-        if (!have_prev) throw std::runtime_error("batched solver: carry needs a previous successful solve on this handle");
-        if (B != prev_B)
-            throw std::runtime_error("batched solver: carry needs the previous batch_size (" + std::to_string(prev_B) + "), got " +
-                                     std::to_string(B));
-        if (bars_written)
-            throw std::runtime_error("batched solver: carry refused, X_bar / Y_bar were written by name since the previous solve "
-                                     "(they are no longer its solution)");
-    }
-    const int Bp = padded_batch(B), Bc = choose_chunk(m, n, Bp);  // (HPRLP_BATCH_CHUNK: per call)
-    const char *grid_hook = env_get("HPRLP_BATCH_GRID");
-    const int grid_cap = grid_hook ? std::atoi(grid_hook) : 0;
-    const bool new_geo = !have_geo || Bp != w.geo.Bp || Bc != w.geo.Bw;
-    if (carry) {
-        if (new_geo) throw std::runtime_error("batched solver: carry needs the previous call's chunk width (HPRLP_BATCH_CHUNK changed)");
-        const double *prev = w.stage_h.p;  // x (n x B) and y (m x B) as the previous call returned them
-        bool bad = prev_on_device && prev_nonfinite;
-        for (size_t i = 0; !prev_on_device && !bad && i < nB + mB; ++i) bad = !std::isfinite(prev[i]);
-        if (bad) throw std::runtime_error("batched solver: carry refused, the previous batch's solution holds a non-finite value");
-    }
-    if (dev) {  // no pointer reaches a kernel before all of them have passed
-        if (B > 65535) throw std::runtime_error("batched solver: the device entry takes at most 65535 members");
-        const std::pair<const double *, size_t> in_ptrs[5] = {{C_in, nB}, {AL_in, mB}, {AU_in, mB}, {l_in, nB}, {u_in, nB}};
-        const char *in_names[5] = {"C", "AL", "AU", "l", "u"};
-        for (int i = 0; i < 5; ++i) check_device_pointer(in_ptrs[i].first, in_ptrs[i].second, device, in_names[i]);
-        if (X0) check_device_pointer(X0, nB, device, "X0");
-        if (Y0) check_device_pointer(Y0, mB, device, "Y0");
-        check_device_pointer(dev->x, nB, device, "x");
-        check_device_pointer(dev->y, mB, device, "y");
-        check_device_pointer(dev->z, nB, device, "z");
-        if (!inputs_ready) HIP_CHECK(hipEventCreateWithFlags(&inputs_ready, hipEventDisableTiming));
-    }
-    HPRLP_parameters actual = param;
-    if (p) {
-        actual.max_iter = p->max_iter; actual.stop_tol = p->stop_tol; actual.time_limit = p->time_limit;
-        actual.check_iter = p->check_iter; actual.use_bc_scaling = p->use_bc_scaling;
-    }
+    const Geo plan = plan_geometry(B);
+    if (carry) refuse_carry(B, X0, Y0, new_geometry(plan));
+    if (dev) check_device_call(*dev, B, C_in, AL_in, AU_in, l_in, u_in, X0, Y0);
+    const HPRLP_parameters actual = call_parameters(p);
     const bool detect = det && det->on;
-    const bool warm = X0 || Y0 || carry;
 
     const bool had_prev = have_prev;
     bool refused = false;  // the call is turned away before the workspace has changed
     have_prev = false;     // (until this call has succeeded)
     try {
-        // -- the batch in scaled units (:792-885) in the staging block.  Host entry: scaled on the host and copied into the pinned
-        // block, to be uploaded by ws_fill.  Device entry: scaled by kb_data_in / kb_data_bc where it is; only the scalars come back.
+        // -- the batch in scaled units (:792-885) in the staging block: scaled on the host, or by the device entry's kernels where it is
         const auto t_prep = time_now();
-        const size_t hdr = 4 * static_cast<size_t>(Bp);
-        const size_t stage_count = dev ? 0 : hdr + 3 * nB + 2 * mB + (X0 ? nB : 0) + (Y0 ? mB : 0);
-        PanelIn in{};
-        int nvec = 0;
+        const Regions regions(plan.Bp, n, m, B, X0 != nullptr, Y0 != nullptr);
+        const size_t stage_count = dev ? 0 : regions.end;
         const BatchData data =
-            dev ? device_prep(w, B, Bp, C_in, AL_in, AU_in, l_in, u_in, X0, Y0, obj_constants, obj_constant, actual.use_bc_scaling,
-                              static_cast<hipStream_t>(dev->stream), inputs_ready, in, nvec)
+            dev ? device_prep(w, B, plan.Bp, regions, C_in, AL_in, AU_in, l_in, u_in, X0, Y0, obj_constants, obj_constant,
+                              actual.use_bc_scaling, static_cast<hipStream_t>(dev->stream), inputs_ready)
                 : prepare_batch(m, n, B, C_in, AL_in, AU_in, l_in, u_in, obj_constants, obj_constant, w.rn.data(), w.cn.data(),
                                 actual.use_bc_scaling, norm_rule);
         if (dev && data_flags_host(w, B)[DF_START]) {
             refused = true;
             throw std::runtime_error("batched solver: warm start: X0 or Y0 holds a non-finite entry");
         }
-        BatchLoop L(data, Bp, actual, detect ? det : nullptr);
-        int iC = 0, iL = 1, iU = 2, iAL = 3, iAU = 4, iX = X0 ? 5 : -1, iY = Y0 ? (X0 ? 6 : 5) : -1;  // (the regions' order, both entries)
-        if (!dev) {
-            if (w.stage_h.n < stage_count) w.stage_h.alloc(stage_count, /*zero=*/false);
-            if (w.stage_d.n < stage_count) w.stage_d.alloc(stage_count);  // (each by its own size: a streamed call grows the pinned one further)
-            double *sh = w.stage_h.p;
-            const std::vector<double> bs = padded(data.b_scale, Bp, 1.0), cs = padded(data.c_scale, Bp, 1.0);
-            std::copy(L.sigma.begin(), L.sigma.end(), sh);
-            std::copy(bs.begin(), bs.end(), sh + Bp);
-            std::copy(cs.begin(), cs.end(), sh + 2 * Bp);
-            std::memcpy(sh + 3 * Bp, L.active.data(), sizeof(int) * Bp);
-            size_t off = hdr;
-            auto region = [&](const double *src, size_t count, int rows, double *panel) {
-                if (src) std::memcpy(sh + off, src, count * sizeof(double));
-                in.src[nvec] = w.stage_d.p + off;  // (the panel's address: below, once the workspace is there)
-                in.rows[nvec] = rows;
-                in.dst[nvec] = panel;
-                off += count;
-                return nvec++;
-            };
-            iC = region(data.C.data(), nB, n, nullptr); iL = region(data.L.data(), nB, n, nullptr); iU = region(data.U.data(), nB, n, nullptr);
-            iAL = region(data.AL.data(), mB, m, nullptr); iAU = region(data.AU.data(), mB, m, nullptr);
-            if (X0) {
-                iX = region(X0, nB, n, nullptr);
-                start_to_scaled(sh + off - nB, n, B, w.cn.data(), data.b_scale);
-            }
-            if (Y0) {
-                iY = region(Y0, mB, m, nullptr);
-                start_to_scaled(sh + off - mB, m, B, w.rn.data(), data.c_scale);
-            }
-        }
+        BatchLoop L(data, plan.Bp, actual, detect ? det : nullptr);
+        if (!dev) stage_host(w, L, data, regions, data, X0, Y0, stage_count, stage_count);
         seconds[2] = time_since(t_prep);
 
         // -- device: the workspace where the geometry is new, this batch into it, the start
         const auto t_fill = time_now();
-        w.lambda_max = lambda_created;  // not what an earlier call bumped it to: a call does not depend on the handle's history
-        if (new_geo) {
-            w.drop_graphs();
-            have_geo = false;
-            ws_matrix_part(w, shared, make_geo(Bp, Bc));
-            ws_panels(w);
-            have_geo = true;
-        }
-        if (grid_cap != w.grid_cap || (!w.graphs.empty() && w.graph_lambda != w.lambda_max)) w.drop_graphs();
-        w.grid_cap = grid_cap;
-        in.dst[iC] = w.C.p; in.dst[iL] = w.L.p; in.dst[iU] = w.U.p; in.dst[iAL] = w.AL.p; in.dst[iAU] = w.AU.p;
-        if (iX >= 0) in.dst[iX] = w.X.p;
-        if (iY >= 0) in.dst[iY] = w.Y.p;
-        std::swap(w.bsc, w.bsc_prev);
-        std::swap(w.csc, w.csc_prev);
-        ws_fill(w, data, stage_count, in, nvec, X0 != nullptr, Y0 != nullptr, carry, detect);
-        if (warm) ws_start(w);
+        ensure_workspace(plan);
+        std::swap(w.bsc, w.bsc_prev);  // (this batch's scales beside those of the batch before: the swap serves carry, so a
+        std::swap(w.csc, w.csc_prev);  // streamed call, which carries nothing, does without it)
+        ws_fill(w, data, stage_count, bind_panels(w, regions), regions.nvec, X0 != nullptr, Y0 != nullptr, carry, detect);
+        if (X0 || Y0 || carry) ws_start(w);
         HIP_CHECK(hipStreamSynchronize(w.stream));
         seconds[3] = time_since(t_fill);
 
@@ -2147,96 +2448,41 @@ void BatchedSolver::solve(int B, const double *C_in, const double *AL_in, const 
         seconds[4] = time_since(L.solve_start);
 
         const auto t_res = time_now();
-        if (dev) {  // x, y, z straight into the caller's buffers; one flag word comes back
-            launch_panel_out(w, dev->x, dev->y, dev->z);
-            hipLaunchKernelGGL(kb_flag_nonfinite, dim3(static_cast<unsigned>(std::min<size_t>((nB + mB + 255) / 256, 1024))), dim3(256), 0,
-                               w.stream, static_cast<const double *>(dev->x), nB, static_cast<const double *>(dev->y), mB,
-                               data_flags(w, B) + DF_RESULT);
-            HIP_CHECK(hipGetLastError());
-            HIP_CHECK(hipMemcpyAsync(const_cast<int *>(data_flags_host(w, B)) + DF_RESULT, data_flags(w, B) + DF_RESULT, sizeof(int),
-                                     hipMemcpyDeviceToHost, w.stream));
-            HIP_CHECK(hipStreamSynchronize(w.stream));
-            if (certs) collect_certificates(w, L, certs);
-            member_results(L.mem, B, dev->primal_obj, dev->residuals, dev->gap, dev->iter, dev->status);
-            prev_nonfinite = data_flags_host(w, B)[DF_RESULT] != 0;
-        } else {
-            *out = collect_results(w, L, certs);
-        }
+        if (dev) prev_nonfinite = device_results(w, L, *dev, certs);
+        else *out = collect_results(w, L, certs);
         seconds[5] = time_since(t_res);
-        const double setup_time = seconds[2] + seconds[3];
-        if (dev) {
-            dev->setup_time = setup_time; dev->solve_time = seconds[4]; dev->power_time = 0.0; dev->time = setup_time + seconds[4];
-        } else {
-            out->setup_time = setup_time; out->solve_time = seconds[4]; out->power_time = 0.0; out->time = setup_time + seconds[4];
-        }
-        last_scalars.clear();
-        for (const std::vector<double> *v : {&data.b_scale, &data.c_scale, &data.norm_b, &data.norm_c, &data.norm_b_org, &data.norm_c_org, &data.sigma})
-            last_scalars.insert(last_scalars.end(), v->begin(), v->end());
-        staged[0] = static_cast<long>(stage_count * sizeof(double));
-        staged[1] = dev ? static_cast<long>(static_cast<size_t>(DS_COUNT) * B * sizeof(double) + (DF_COUNT + 1) * sizeof(int))
-                        : static_cast<long>((2 * nB + mB) * sizeof(double));
-        w.data = nullptr;
-        have_prev = true;
-        prev_B = B;
-        prev_on_device = dev != nullptr;
-        ray_have_prev = false;
-        bars_written = false;
-        streamed = false;
-        lambda_last = w.lambda_max;
-        ++solves;
-        if (dev) ++device_solves;
+        if (dev) set_times(*dev);
+        else set_times(*out);
+        const size_t back = dev ? static_cast<size_t>(DS_COUNT) * B * sizeof(double) + (DF_COUNT + 1) * sizeof(int)  // the scalars and flag words
+                                : (2 * static_cast<size_t>(n) + m) * B * sizeof(double);                            // x, y, z
+        call_succeeded(stage_count * sizeof(double), back, &data, dev != nullptr);
     } catch (...) {
         if (refused) {  // nothing the previous call left has been touched
             have_prev = had_prev;
             throw;
         }
-        // a call that failed half-way: nothing of it is carried, and the next call builds its workspace anew
-        (void)hipStreamSynchronize(w.stream);
-        (void)hipGetLastError();
-        w.drop_graphs();
-        w.data = nullptr;
-        have_geo = false;
+        call_failed(/*streamed_call=*/false);
         throw;
     }
 }
 
-// ---- streamed batches (DESIGN.md "Streamed batches") -------------------------------------------------------------------------
-// `count` problems over the shared matrix through W = min(width, count) slots of a workspace whose geometry is a plain solve's
-// of W members.  The loop is solve()'s: an evaluation at every multiple of check_iter, restart decisions, check_iter iterations.
-// A member that receives a status at an evaluation is harvested at once (kb_slot_out: its x, y, z into column p of the result
-// block) and its slot takes the next queued problem (kb_slot_clear, kb_slot_in, the start kernels masked to the new members),
-// which gets its own iteration-0 evaluation within the same event; every rule that reads the iteration number reads the member's
-// local one (BatchLoop::base).  The slot decisions are stream_assign's (stream_schedule.h).  No panel moves: the graphs survive.
-//
-// Memory of a call, beside the workspace of W members: the whole queue staged in scaled units, (3 n + 2 m) * count doubles (plus
-// (n + m) * count or part of it with starts) and 3 * count scalars; the result block, (2 n + m) * count doubles, twice that with
-// detection (the rays of the verdicts); and ONE pinned host block of the larger of the two for the upload at entry and the download
-// at the end.  Per refill pass 4 W + Bp ints go up through a second, small pinned block.  On the host, beside the pinned block:
-// prepare_batch's BatchData holds the scaled queue once more while the call runs ((3 n + 2 m) * count doubles), and the results
-// returned to the caller are (2 n + m) * count doubles (with detection the certificates' vectors of the members with a verdict).
+// ---- streamed batches (DESIGN.md "Streamed batches": the rule, the local iteration numbers, the memory of a call) ----------------
+// `count` problems through W = min(width, count) slots of a workspace whose geometry is a plain solve's of W members.  The loop is
+// solve()'s; a member that ends at an evaluation hands its slot on within that event (StreamRun).  No panel moves: the graphs survive.
 void BatchedSolver::solve_stream(int count, int width, const double *C_in, const double *AL_in, const double *AU_in, const double *l_in,
                                  const double *u_in, const double *obj_constants, const HPRLP_parameters *p, const double *X0,
                                  const double *Y0, const Detection *det, std::vector<Certificate> *certs, HPRLP_batched_results *out) {
     // -- everything that can refuse the call, before the handle changes
-    HPRLP_parameters actual = param;
-    if (p) {
-        actual.max_iter = p->max_iter; actual.stop_tol = p->stop_tol; actual.time_limit = p->time_limit;
-        actual.check_iter = p->check_iter; actual.use_bc_scaling = p->use_bc_scaling;
-    }
+    const HPRLP_parameters actual = call_parameters(p);
     stream_check_call(out != nullptr, count, width, C_in && AL_in && AU_in && l_in && u_in, actual.max_iter, actual.check_iter);
-    const int check_iter = std::max(actual.check_iter, 1);
     const size_t nN = static_cast<size_t>(n) * count, mN = static_cast<size_t>(m) * count;
     for (size_t i = 0; X0 && i < nN; ++i)
         if (!std::isfinite(X0[i])) throw std::runtime_error("batched stream: warm start: X0[" + std::to_string(i) + "] is not finite");
     for (size_t i = 0; Y0 && i < mN; ++i)
         if (!std::isfinite(Y0[i])) throw std::runtime_error("batched stream: warm start: Y0[" + std::to_string(i) + "] is not finite");
     const int W = std::min(width, count);
-    const int Bp = padded_batch(W), Bc = choose_chunk(m, n, Bp);  // (HPRLP_BATCH_CHUNK: per call)
-    const char *grid_hook = env_get("HPRLP_BATCH_GRID");
-    const int grid_cap = grid_hook ? std::atoi(grid_hook) : 0;
-    const bool new_geo = !have_geo || Bp != w.geo.Bp || Bc != w.geo.Bw;
+    const Geo plan = plan_geometry(W);
     const bool detect = det && det->on;
-    const bool warm = X0 || Y0;
 
     have_prev = false;  // the panels will hold members of many problems: nothing of this call is carried
     try {
@@ -2244,300 +2490,55 @@ void BatchedSolver::solve_stream(int count, int width, const double *C_in, const
         const auto t_prep = time_now();
         const BatchData q = prepare_batch(m, n, count, C_in, AL_in, AU_in, l_in, u_in, obj_constants, obj_constant, w.rn.data(), w.cn.data(),
                                           actual.use_bc_scaling, norm_rule);
-        BatchData sd;  // the scalars of the problems in the slots: what the loop reads as "the batch" (it reads none of the vectors)
-        sd.m = m; sd.n = n; sd.B = W;
-        auto first_w = [W](const std::vector<double> &v) { return std::vector<double>(v.begin(), v.begin() + W); };
-        sd.b_scale = first_w(q.b_scale); sd.c_scale = first_w(q.c_scale); sd.norm_b = first_w(q.norm_b); sd.norm_c = first_w(q.norm_c);
-        sd.norm_b_org = first_w(q.norm_b_org); sd.norm_c_org = first_w(q.norm_c_org); sd.objc = first_w(q.objc); sd.sigma = first_w(q.sigma);
-        HPRLP_parameters loop_prm = actual;
-        loop_prm.max_iter = std::numeric_limits<int>::max();  // (the limit is each member's own: below)
-        BatchLoop L(sd, Bp, loop_prm, detect ? det : nullptr);
-        const size_t hdr = 4 * static_cast<size_t>(Bp);
-        const size_t stage_count = hdr + 3 * nN + 2 * mN + (X0 ? nN : 0) + (Y0 ? mN : 0) + 3 * static_cast<size_t>(count);
-        const size_t res_count = (2 * nN + mN) * (detect ? 2 : 1);
-        // (the pinned block serves the upload of the queue and the download of the results; its device twin only the queue)
-        if (w.stage_h.n < std::max(stage_count, res_count)) w.stage_h.alloc(std::max(stage_count, res_count), /*zero=*/false);
-        if (w.stage_d.n < stage_count) w.stage_d.alloc(stage_count);
-        if (w.res_d.n < res_count) w.res_d.alloc(res_count);
-        double *sh = w.stage_h.p;
-        const std::vector<double> bs = padded(sd.b_scale, Bp, 1.0), cs = padded(sd.c_scale, Bp, 1.0);
-        std::copy(L.sigma.begin(), L.sigma.end(), sh);
-        std::copy(bs.begin(), bs.end(), sh + Bp);
-        std::copy(cs.begin(), cs.end(), sh + 2 * Bp);
-        std::memcpy(sh + 3 * Bp, L.active.data(), sizeof(int) * Bp);
-        PanelIn in{};  // the initial fill: the first W columns of every region
-        SlotIn sin{};  // ... and a refill's way in from the same regions
-        int nvec = 0;
-        size_t off = hdr;
-        auto region = [&](const double *src, size_t cnt, int rows) {
-            std::memcpy(sh + off, src, cnt * sizeof(double));
-            in.src[nvec] = sin.src[nvec] = w.stage_d.p + off;
-            in.rows[nvec] = sin.rows[nvec] = rows;
-            off += cnt;
-            return nvec++;
-        };
-        const int iC = region(q.C.data(), nN, n), iL = region(q.L.data(), nN, n), iU = region(q.U.data(), nN, n);
-        const int iAL = region(q.AL.data(), mN, m), iAU = region(q.AU.data(), mN, m);
-        int iX = -1, iY = -1;
-        if (X0) {
-            iX = region(X0, nN, n);
-            start_to_scaled(sh + off - nN, n, count, w.cn.data(), q.b_scale);
-        }
-        if (Y0) {
-            iY = region(Y0, mN, m);
-            start_to_scaled(sh + off - mN, m, count, w.rn.data(), q.c_scale);
-        }
-        const size_t q_off = off;  // sigma | b_scale | c_scale of every problem of the queue
-        std::copy(q.sigma.begin(), q.sigma.end(), sh + q_off);
-        std::copy(q.b_scale.begin(), q.b_scale.end(), sh + q_off + count);
-        std::copy(q.c_scale.begin(), q.c_scale.end(), sh + q_off + 2 * static_cast<size_t>(count));
+        StreamRun run(w, q, W, plan.Bp, actual, detect ? det : nullptr, X0 != nullptr, Y0 != nullptr);
+        BatchLoop &L = run.L;
+        run.stage(X0, Y0);
         seconds[2] = time_since(t_prep);
 
-        // -- device: the workspace where the geometry is new, the first W problems into it as a plain solve's batch, their start
+        // -- device: the first W problems as a plain solve's batch (no swap of bsc / csc with their _prev twins: see solve())
         const auto t_fill = time_now();
-        w.lambda_max = lambda_created;
-        if (new_geo) {
-            w.drop_graphs();
-            have_geo = false;
-            ws_matrix_part(w, shared, make_geo(Bp, Bc));
-            ws_panels(w);
-            have_geo = true;
-        }
-        if (grid_cap != w.grid_cap || (!w.graphs.empty() && w.graph_lambda != w.lambda_max)) w.drop_graphs();
-        w.grid_cap = grid_cap;
-        double *panels[kPanelVectors] = {};
-        panels[iC] = w.C.p; panels[iL] = w.L.p; panels[iU] = w.U.p; panels[iAL] = w.AL.p; panels[iAU] = w.AU.p;
-        if (iX >= 0) panels[iX] = w.X.p;
-        if (iY >= 0) panels[iY] = w.Y.p;
-        for (int v = 0; v < nvec; ++v) in.dst[v] = sin.dst[v] = panels[v];
-        const size_t tab_count = 4 * static_cast<size_t>(W) + Bp;  // out pairs | in pairs | the start mask
-        if (w.tab_h.n < tab_count) {
-            w.tab_h.alloc(tab_count);
-            w.tab_d.alloc(tab_count);
-        }
-        HIP_CHECK(hipMemsetAsync(w.res_d.p, 0, res_count * sizeof(double), w.stream));  // (a problem that never started: zero vectors)
-        ws_fill(w, sd, stage_count, in, nvec, X0 != nullptr, Y0 != nullptr, /*carry=*/false, detect);
-        if (warm) ws_start(w);
-        if (detect && w.Zray.n != static_cast<size_t>(n) * Bp) w.Zray.alloc(static_cast<size_t>(n) * Bp);
+        ensure_workspace(plan);
+        const PanelIn in = bind_panels(w, run.regions);  // the initial fill: the first W columns of every region
+        HIP_CHECK(hipMemsetAsync(w.res_d.p, 0, run.res_count * sizeof(double), w.stream));  // (a problem that never started: zero vectors)
+        ws_fill(w, run.sd, run.stage_count, in, run.regions.nvec, X0 != nullptr, Y0 != nullptr, /*carry=*/false, detect);
+        if (X0 || Y0) ws_start(w);
+        run.bind(in);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipStreamSynchronize(w.stream));
         seconds[3] = time_since(t_fill);
 
-        // -- the refill pass's launches: their number does not depend on how many slots a pass hands on
-        const double *qd = w.stage_d.p + q_off;
-        SlotClear sclr{};
-        sclr.n = n; sclr.m = m;
-        for (double *pn : {w.Xh.p, w.Xb.p, w.DX.p, w.Zb.p, w.lastX.p}) sclr.pn[sclr.npn++] = pn;
-        for (double *pm : {w.Yb.p, w.DY.p, w.Yobj.p, w.lastY.p}) sclr.pm[sclr.npm++] = pm;
-        if (!X0) sclr.pn[sclr.npn++] = w.X.p;
-        if (!Y0) sclr.pm[sclr.npm++] = w.Y.p;
-        if (detect) {
-            sclr.pn[sclr.npn++] = w.prevX.p; sclr.pn[sclr.npn++] = w.DS.p;
-            sclr.pm[sclr.npm++] = w.prevY.p; sclr.pm[sclr.npm++] = w.YS.p;
-        }
-        sclr.SC = w.SC.p; sclr.ctl = w.ctl; sclr.bsc = w.bsc.p; sclr.csc = w.csc.p;
-        sclr.q_sigma = qd; sclr.q_bs = qd + count; sclr.q_cs = qd + 2 * static_cast<size_t>(count);
-        double *rd = w.res_d.p;
-        const double *cnd = shared.col_norm.p, *rnd = shared.row_norm.p;
-        SlotOut sout{};
-        {
-            // (the ray d before the rays y, A^T y: a pass without a primal verdict stops short of them -- nobody has written Zray then)
-            const double *src[kSlotOutVectors] = {w.Xb.p, w.Yb.p, w.Zb.p, w.DS.p, w.YS.p, w.Zray.p};
-            double *dst[kSlotOutVectors] = {rd, rd + nN, rd + nN + mN, rd + 3 * nN + 2 * mN, rd + 2 * nN + mN, rd + 2 * nN + 2 * mN};
-            const double *norm[kSlotOutVectors] = {cnd, rnd, cnd, nullptr, nullptr, nullptr};
-            const double *scale[kSlotOutVectors] = {w.bsc.p, w.csc.p, w.csc.p, nullptr, nullptr, nullptr};
-            const int rows[kSlotOutVectors] = {n, m, n, n, m, n};
-            const int map[kSlotOutVectors] = {SLOT_OUT_POINT, SLOT_OUT_POINT, SLOT_OUT_REDUCED_COST, SLOT_OUT_RAW, SLOT_OUT_RAW, SLOT_OUT_RAW};
-            for (int v = 0; v < kSlotOutVectors; ++v) {
-                sout.src[v] = src[v]; sout.dst[v] = dst[v]; sout.norm[v] = norm[v]; sout.scale[v] = scale[v];
-                sout.rows[v] = rows[v]; sout.map[v] = map[v];
-            }
-        }
-        const SlotPair *out_pairs = reinterpret_cast<const SlotPair *>(w.tab_d.p);
-        const SlotPair *in_pairs = reinterpret_cast<const SlotPair *>(w.tab_d.p + 2 * static_cast<size_t>(W));
-        const int *new_mask = w.tab_d.p + 4 * static_cast<size_t>(W);
-        const long longest = std::max(n, m);
-        auto elem_grid = [&](int np, int ny) { return dim3(static_cast<unsigned>((longest * np + 255) / 256), ny); };
-
-        // -- the loop
-        std::vector<Member> done(count);
-        std::vector<int> occ(W), freed(W), ps(W), pp(W);  // the problem in each slot (-1: empty)
-        std::vector<char> is_new(W, 0);
-        std::vector<int> r_slot(count, -1), r_in(count, -1), r_out(count, -1);  // the record: the handle takes it when the call has succeeded
-        for (int k = 0; k < W; ++k) {
-            occ[k] = k;
-            r_slot[k] = k;
-            r_in[k] = 0;
-        }
-        StreamQueue queue;
-        queue.count = count;
-        queue.next = W;
-        long evals = 0, refill_events = 0, refills = 0, passes = 0;
-        const long bumps0 = w.bumps;
         double refill_seconds = 0.0;
         L.solve_start = time_now();
         while (true) {  // one pass per periodic event
             const double elapsed = time_since(L.solve_start);
-            const int event = L.iter / check_iter;
             loop_evaluate(w, L, L.iter == 0);  // 1. every occupied slot, by its local iteration
-            ++evals;
-            const bool time_up = elapsed >= actual.time_limit;
+            ++run.evals;
             const auto t_pass = time_now();
-            bool refilled = false, active_stale = false;
-            while (true) {  // the passes of this event: 2. harvest, 3. refill, 4. the new members' iteration-0 evaluation
-                int nout = 0;
-                bool ray_y = false, any_verdict = false;
-                for (int k = 0; k < W; ++k) {
-                    if (occ[k] < 0) continue;
-                    Member &mb = L.mem[k];
-                    const int local = L.iter - L.base[k];
-                    if (mb.status == "CONTINUE" && (time_up || local >= actual.max_iter)) {  // (the time limit first, as loop_ended)
-                        mb.status = time_up ? "TIME_LIMIT" : "ITER_LIMIT";
-                        mb.final_iter = local;
-                        L.active[k] = 0;
-                        active_stale = true;
-                    }
-                    if (mb.status == "CONTINUE") continue;
-                    freed[nout++] = k;
-                    ray_y = ray_y || mb.verdict == 1;
-                    any_verdict = any_verdict || mb.verdict != 0;
-                }
-                if (!nout) break;
-                const int nin = time_up ? 0 : stream_assign(queue, freed.data(), nout, ps.data(), pp.data());
-                int *th = w.tab_h.p;
-                for (int i = 0; i < nout; ++i) {
-                    th[2 * i] = freed[i];
-                    th[2 * i + 1] = occ[freed[i]];
-                }
-                std::fill(th + 4 * static_cast<size_t>(W), th + tab_count, 0);
-                for (int i = 0; i < nin; ++i) {
-                    th[2 * (W + i)] = ps[i];
-                    th[2 * (W + i) + 1] = pp[i];
-                    th[4 * static_cast<size_t>(W) + ps[i]] = 1;
-                }
-                HIP_CHECK(hipMemcpyAsync(w.tab_d.p, th, tab_count * sizeof(int), hipMemcpyHostToDevice, w.stream));
-                if (ray_y) {  // z = -A^T y of a primal verdict: the plain product of every column, as collect_certificates has it
-                    launch_ray_product(w);
-                    HIP_CHECK(hipGetLastError());
-                }
-                hipLaunchKernelGGL(kb_slot_out, elem_grid(nout, ray_y ? kSlotOutVectors : (any_verdict ? kSlotOutDual : kSlotOutPlain)), dim3(256), 0, w.stream, sout, out_pairs, nout,
-                                   w.geo);
-                HIP_CHECK(hipGetLastError());
-                for (int i = 0; i < nout; ++i) {
-                    const int k = freed[i], pr = occ[k];
-                    done[pr] = L.mem[k];
-                    r_out[pr] = event;
-                    occ[k] = -1;
-                }
-                if (!nin) {
-                    HIP_CHECK(hipStreamSynchronize(w.stream));  // (the pinned table is free again)
-                    break;
-                }
-                hipLaunchKernelGGL(kb_slot_clear, elem_grid(nin, sclr.npn + sclr.npm + 1), dim3(256), 0, w.stream, sclr, in_pairs, nin, w.geo);
-                HIP_CHECK(hipGetLastError());
-                hipLaunchKernelGGL(kb_slot_in, elem_grid(nin, nvec), dim3(256), 0, w.stream, sin, in_pairs, nin, w.geo);
-                HIP_CHECK(hipGetLastError());
-                if (warm) {
-                    ws_start(w, new_mask);
-                    HIP_CHECK(hipGetLastError());
-                }
-                std::fill(is_new.begin(), is_new.end(), 0);
-                for (int i = 0; i < nin; ++i) {
-                    const int k = ps[i], pr = pp[i];
-                    occ[k] = pr;
-                    r_slot[pr] = k;
-                    r_in[pr] = event;
-                    L.mem[k] = Member();
-                    L.mem[k].rs.best_sigma = q.sigma[pr];
-                    L.sigma[k] = q.sigma[pr];
-                    L.active[k] = 1;
-                    L.base[k] = L.iter;
-                    L.ray_prev[k] = 0;
-                    L.ray_tested[k] = 0;
-                    is_new[k] = 1;
-                    sd.b_scale[k] = q.b_scale[pr]; sd.c_scale[k] = q.c_scale[pr]; sd.norm_b[k] = q.norm_b[pr]; sd.norm_c[k] = q.norm_c[pr];
-                    sd.norm_b_org[k] = q.norm_b_org[pr]; sd.norm_c_org[k] = q.norm_c_org[pr]; sd.objc[k] = q.objc[pr]; sd.sigma[k] = q.sigma[pr];
-                }
-                refills += nin;
-                ++passes;
-                refilled = true;
-                loop_evaluate(w, L, /*first=*/true, is_new.data());  // (its fetch ends the pass; it uploads the active mask)
-                active_stale = false;
-            }
+            bool refilled = false, active_stale = false;  // (stale: a limit has changed the active mask and no evaluation has uploaded it)
+            while (run.pass(elapsed >= actual.time_limit, active_stale)) refilled = true;  // 2. harvest, 3. refill, 4. iteration-0 evaluation
             if (active_stale) w.active.upload(L.active.data(), w.Bp);
-            if (refilled) ++refill_events;
+            if (refilled) ++run.refill_events;
             refill_seconds += time_since(t_pass);
-            bool any = false;
-            for (int k = 0; k < W; ++k) any = any || occ[k] >= 0;
-            if (!any) break;
+            if (!run.occupied()) break;
             const bool restarted = loop_restart(w, L, true);  // 5. an empty slot is an inactive one
             loop_advance(w, L, restarted);
         }
         seconds[4] = time_since(L.solve_start);
-        for (int pr = queue.next; pr < count; ++pr) {  // (only the time limit leaves a problem queued)
-            done[pr].status = "TIME_LIMIT";
-            done[pr].final_iter = 0;
-            done[pr].r = Residuals();
-        }
 
         // -- the results: one download
         const auto t_res = time_now();
-        HPRLP_batched_results res = alloc_batched_results(m, n, count);
-        try {
-            HIP_CHECK(hipMemcpyAsync(w.stage_h.p, w.res_d.p, res_count * sizeof(double), hipMemcpyDeviceToHost, w.stream));
-            HIP_CHECK(hipStreamSynchronize(w.stream));
-            const double *rh = w.stage_h.p;
-            std::memcpy(res.x, rh, nN * sizeof(double));
-            std::memcpy(res.y, rh + nN, mN * sizeof(double));
-            std::memcpy(res.z, rh + nN + mN, nN * sizeof(double));
-            if (certs) {
-                certs->assign(count, Certificate());
-                const double *cy = rh + 2 * nN + mN, *cz = cy + mN, *cd = cz + nN;
-                for (int pr = 0; pr < count && detect; ++pr) {
-                    const Member &mb = done[pr];
-                    if (!mb.verdict) continue;
-                    Certificate &c = (*certs)[pr];
-                    const size_t om = static_cast<size_t>(pr) * m, on = static_cast<size_t>(pr) * n;
-                    if (mb.verdict == 1) {
-                        c.y.assign(cy + om, cy + om + m);
-                        c.z.assign(cz + on, cz + on + n);
-                    } else {
-                        c.d.assign(cd + on, cd + on + n);
-                    }
-                    finish_certificate(&c, mb.verdict, mb.final_iter, mb.ray, w.rn.data(), w.cn.data(), q.b_scale[pr], q.c_scale[pr]);
-                }
-            }
-        } catch (...) {
-            free_batched_results(&res);
-            throw;
-        }
-        member_results(done, count, res.primal_obj, res.residuals, res.gap, res.iter, res.status);
+        HPRLP_batched_results res = run.results(certs);
         seconds[5] = time_since(t_res);
-        res.setup_time = seconds[2] + seconds[3]; res.solve_time = seconds[4]; res.power_time = 0.0; res.time = res.setup_time + res.solve_time;
+        set_times(res);
         *out = res;
-        const long stats[8] = {count, width, L.iter, evals, refill_events, refills, passes, w.bumps - bumps0};
+        const long stats[8] = {count, width, L.iter, run.evals, run.refill_events, run.refills, run.passes, w.bumps - run.bumps0};
         std::copy(stats, stats + 8, stream_stats);
-        rec_slot = std::move(r_slot); rec_in = std::move(r_in); rec_out = std::move(r_out);
+        rec_slot = std::move(run.r_slot); rec_in = std::move(run.r_in); rec_out = std::move(run.r_out);
         stream_seconds[0] = refill_seconds;
         stream_seconds[1] = seconds[4] - refill_seconds;
-        staged[0] = static_cast<long>(stage_count * sizeof(double));
-        staged[1] = static_cast<long>(res_count * sizeof(double));
-        w.data = nullptr;
-        streamed = true;
-        have_stream = true;
-        prev_on_device = false;
-        ray_have_prev = false;
-        bars_written = false;
-        lambda_last = w.lambda_max;
-        ++solves;
+        call_succeeded(run.stage_count * sizeof(double), run.res_count * sizeof(double), nullptr, /*device_entry=*/false);
     } catch (...) {
-        // a call that failed half-way: the next call builds its workspace anew
-        (void)hipStreamSynchronize(w.stream);
-        (void)hipGetLastError();
-        w.drop_graphs();
-        w.data = nullptr;
-        have_geo = false;
-        streamed = true;
+        call_failed(/*streamed_call=*/true);
         throw;
     }
 }
@@ -2587,9 +2588,7 @@ void batched_solver_solve_device(BatchedSolver *h, int batch_size, const double 
 void batched_solver_set_matrix_values(BatchedSolver *h, const double *val, long nnz) {
     if (!h) throw std::runtime_error("batched solver: null handle");
     if (!val) throw std::runtime_error("batched solver: null matrix values");
-    const char *lambda_hook = env_get("HPRLP_BATCH_LAMBDA");
-    const double lambda_given = lambda_hook ? std::strtod(lambda_hook, nullptr) : 1.0;
-    if (!(lambda_given > 0.0) || !std::isfinite(lambda_given)) throw std::runtime_error("HPRLP_BATCH_LAMBDA is not a positive finite number");
+    const double hook = lambda_hook();  // (a hook that is no lambda refuses the call here, before anything changes)
     HIP_CHECK(hipStreamSynchronize(h->w.stream));
     const auto t0 = time_now();
     const std::vector<double> zero_m(static_cast<size_t>(std::max(h->m, 1)), 0.0), zero_n(static_cast<size_t>(std::max(h->n, 1)), 0.0);
@@ -2600,7 +2599,7 @@ void batched_solver_set_matrix_values(BatchedSolver *h, const double *val, long 
     h->shared.col_norm.download(h->w.cn.data(), h->n);
     h->seconds[0] += time_since(t0);
     const auto t1 = time_now();
-    h->lambda_created = lambda_hook ? lambda_given : h->shared.power_iteration(5000, 1.0e-4, nullptr) * 1.01;
+    h->lambda_created = hook > 0.0 ? hook : h->shared.power_iteration(5000, 1.0e-4, nullptr) * 1.01;
     h->seconds[1] += time_since(t1);
 }
 void batched_solver_set_norms(BatchedSolver *h, int rule) {
@@ -2642,7 +2641,7 @@ void batched_solver_seconds(const BatchedSolver *h, double out[6]) {
 // detection's panels) as on a handle that never stepped.
 int batched_solver_ray_step(BatchedSolver *h, const int *active, bool restart, double *out, int *tested) {
     if (!h || !active || !out || !tested) throw std::runtime_error("batched ray step: null handle / active / output");
-    if (h->streamed) throw std::runtime_error("batched ray step: refused after a streamed call (its slots held several problems each); a plain solve comes first");
+    h->refuse_after_stream("batched ray step:");
     if (!h->have_prev || !h->have_geo) throw std::runtime_error("batched ray step: needs a successful solve on this handle");
     if (!restart && !h->ray_have_prev)
         throw std::runtime_error("batched ray step: no stored iterate, the first step after a solve needs restart != 0");
@@ -2698,7 +2697,7 @@ const NamedPanel &named_panel(const BatchWS &w, const std::string &name, const c
 // layout, rows x Bp (panel_index).  out null: only the count.  Returns the count of values; throws where `len` is another.
 long batched_solver_get_panel(BatchedSolver *h, const char *name, double *out, long len) {
     if (!h || !name) throw std::runtime_error("batched get_panel: null handle / name");
-    if (h->streamed) throw std::runtime_error("batched get_panel: refused after a streamed call (its slots held several problems each); a plain solve comes first");
+    h->refuse_after_stream("batched get_panel:");
     if (!h->have_prev || !h->have_geo) throw std::runtime_error("batched get_panel: needs a successful solve on this handle");
     BatchWS &w = h->w;
     std::string nm(name);
@@ -2736,7 +2735,7 @@ long batched_solver_get_panel(BatchedSolver *h, const char *name, double *out, l
 // what they hold).  No other panel can be written.  carry is refused until the next successful solve.
 void batched_solver_set_panel(BatchedSolver *h, const char *name, const double *in, long len) {
     if (!h || !name || !in) throw std::runtime_error("batched set_panel: null handle / name / values");
-    if (h->streamed) throw std::runtime_error("batched set_panel: refused after a streamed call (its slots held several problems each); a plain solve comes first");
+    h->refuse_after_stream("batched set_panel:");
     if (!h->have_prev || !h->have_geo) throw std::runtime_error("batched set_panel: needs a successful solve on this handle");
     BatchWS &w = h->w;
     const NamedPanel &p = named_panel(w, name, "batched set_panel");

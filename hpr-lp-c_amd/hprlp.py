@@ -774,33 +774,42 @@ class BatchedSolver:
         if not self._h:
             raise RuntimeError("BatchedSolver: closed")
         B = np.asarray(Cmat).shape[1]
+        X0, Y0 = self._start(X0, self.model.n, B, "X0"), self._start(Y0, self.model.m, B, "Y0")
+        out = self._host_call("hprlp_batched_solver_solve", (), (_dptr(X0), _dptr(Y0), int(bool(carry))), (Cmat, AL, AU, l, u, obj_constants),
+                              param, eps_primal, eps_dual)
+        self._last_B = B
+        return out
 
-        def panel(V, rows, name):
-            if V is None:
-                return None
-            a = np.asfortranarray(V, dtype=np.float64)
-            if a.shape != (rows, B):
-                raise ValueError(f"warm start: {name} must have shape ({rows}, {B}), got {a.shape}")
-            return a
-        X0, Y0 = panel(X0, self.model.n, "X0"), panel(Y0, self.model.m, "Y0")
+    @staticmethod
+    def _start(V, rows, B, name):
+        """A start panel as a column-major float64 array of shape (rows, B) (None stays None); finite entries: by the library."""
+        if V is None:
+            return None
+        a = np.asfortranarray(V, dtype=np.float64)
+        if a.shape != (rows, B):
+            raise ValueError(f"warm start: {name} must have shape ({rows}, {B}), got {a.shape}")
+        return a
+
+    def _host_call(self, entry, before, after, batch, param, eps_primal, eps_dual):
+        """One call of a host entry (solve, solve_stream): entry(handle, B, *before, the batch, param, *after, detection,
+        certificates, results).  The results as _batched_call()'s dict, with "certificates" where detection is on; RuntimeError
+        with the library's message where the call fails."""
         det = _detection_arg(eps_primal, eps_dual)
         cc = CBatchedCertificates()
         cprm = None if param is None else param.to_c()
 
         def call(B, args, cp):
             res = CBatchedResults()
-            rc = lib().hprlp_batched_solver_solve(self._h, B, *args, None if cprm is None else C.byref(cprm), _dptr(X0), _dptr(Y0),
-                                                  int(bool(carry)), C.byref(det) if det is not None else None,
-                                                  C.byref(cc) if det is not None else None, C.byref(res))
+            rc = getattr(lib(), entry)(self._h, B, *before, *args, None if cprm is None else C.byref(cprm), *after,
+                                       C.byref(det) if det is not None else None, C.byref(cc) if det is not None else None, C.byref(res))
             if rc != 0:
                 if det is not None:
                     lib().hprlp_free_batched_certificates(C.byref(cc))
-                raise RuntimeError("hprlp_batched_solver_solve failed: " + last_error())
+                raise RuntimeError(entry + " failed: " + last_error())
             return res
-        out = _batched_call(call, self.model, Cmat, AL, AU, l, u, obj_constants, param)
+        out = _batched_call(call, self.model, *batch, param)
         if det is not None:
             out["certificates"] = _batched_certificates(cc)
-        self._last_B = B
         return out
 
     _STREAM_INFO = ("count", "width", "loop_iterations", "evaluations", "refill_evaluations", "refills", "refill_passes",
@@ -818,32 +827,9 @@ class BatchedSolver:
             raise RuntimeError("BatchedSolver: closed")
         _need_stream()
         N = np.asarray(Cmat).shape[1]
-
-        def panel(V, rows, name):   # (shape here, finite entries by the library, as solve())
-            if V is None:
-                return None
-            a = np.asfortranarray(V, dtype=np.float64)
-            if a.shape != (rows, N):
-                raise ValueError(f"warm start: {name} must have shape ({rows}, {N}), got {a.shape}")
-            return a
-        X0, Y0 = panel(X0, self.model.n, "X0"), panel(Y0, self.model.m, "Y0")
-        det = _detection_arg(eps_primal, eps_dual)
-        cc = CBatchedCertificates()
-        cprm = None if prm is None else prm.to_c()
-
-        def call(B, args, cp):
-            res = CBatchedResults()
-            rc = lib().hprlp_batched_solver_solve_stream(self._h, B, int(width), *args, None if cprm is None else C.byref(cprm),
-                                                         _dptr(X0), _dptr(Y0), C.byref(det) if det is not None else None,
-                                                         C.byref(cc) if det is not None else None, C.byref(res))
-            if rc != 0:
-                if det is not None:
-                    lib().hprlp_free_batched_certificates(C.byref(cc))
-                raise RuntimeError("hprlp_batched_solver_solve_stream failed: " + last_error())
-            return res
-        out = _batched_call(call, self.model, Cmat, AL, AU, l, u, obj_constants, prm)
-        if det is not None:
-            out["certificates"] = _batched_certificates(cc)
+        X0, Y0 = self._start(X0, self.model.n, N, "X0"), self._start(Y0, self.model.m, N, "Y0")
+        out = self._host_call("hprlp_batched_solver_solve_stream", (int(width),), (_dptr(X0), _dptr(Y0)), (Cmat, AL, AU, l, u, obj_constants),
+                              prm, eps_primal, eps_dual)
         rec = [np.zeros(N, dtype=np.intc) for _ in range(3)]
         if lib().hprlp_batched_solver_stream_record(self._h, *(r.ctypes.data_as(c_int_p) for r in rec)) != N:
             raise RuntimeError("hprlp_batched_solver_stream_record failed: " + last_error())

@@ -324,3 +324,62 @@ def test_plain_solves_after_a_stream_and_the_graphs(gpu):
             assert np.array_equal(g[f], w[f]), f
     assert np.array_equal(h.get_panel("X_bar"), never.get_panel("X_bar"))
     h.close(); never.close(); model.free()
+
+
+def test_the_three_entries_on_one_handle(gpu):
+    """Stream, device entry, stream with detection (it allocates the ray panels and Zray), host entry, carry: the staging blocks,
+    the workspace steps and the bookkeeping are shared by the three entries, and each call gives the bits of the same single call
+    on a fresh handle (the carry: of the same pair of calls).  The geometry never changes: nothing is captured after the first call."""
+    from test_gpu_batched_device import T, on_host
+    lp = planted()
+    N, width = 10, 4
+    args = make_batch(lp, N, 2)
+    first = tuple(a[:, :width] for a in args)
+    model = model_of(lp)
+    prm = params(stop_tol=1e-4, check_iter=CHECK)
+    fresh = lambda: hprlp.BatchedSolver(model, prm)
+
+    def same(got, ref, tag, streamed=False):
+        assert got["status"] == ref["status"] and np.array_equal(got["iter"], ref["iter"]), (tag, got["status"], got["iter"], ref["iter"])
+        for f in ("x", "y", "z") + SCALARS + (("slot", "event_in", "event_out") if streamed else ()):
+            assert np.array_equal(got[f], ref[f]), (tag, f)
+
+    h = fresh()
+    # 1. a stream of the 10
+    got = h.solve_stream(*args, width=width)
+    no_bump(h, streamed=True)
+    captures = h.info()["graph_captures"]
+    assert captures > 0 and got["status"] == ["OPTIMAL"] * N
+    f1 = fresh()
+    ref_stream = f1.solve_stream(*args, width=width)
+    no_bump(f1, streamed=True)
+    same(got, ref_stream, "stream", streamed=True)
+    # 2. the device entry, the first 4
+    got = on_host(h.solve_tensors(*[T(a) for a in first]))
+    no_bump(h)
+    f2 = fresh()
+    same(got, on_host(f2.solve_tensors(*[T(a) for a in first])), "tensors")
+    no_bump(f2)
+    # 3. a stream with detection on
+    got = h.solve_stream(*args, width=width, eps_primal=1e-8, eps_dual=1e-8)
+    no_bump(h, streamed=True)
+    f3 = fresh()
+    ref = f3.solve_stream(*args, width=width, eps_primal=1e-8, eps_dual=1e-8)
+    no_bump(f3, streamed=True)
+    same(got, ref, "stream with detection", streamed=True)
+    assert [int(k) for k in got["certificates"]["kind"]] == [int(k) for k in ref["certificates"]["kind"]] == [0] * N
+    # 4. the host entry, the first 4
+    got = h.solve(*first)
+    no_bump(h)
+    assert h.info()["graph_captures"] == captures
+    f4 = fresh()
+    same(got, f4.solve(*first), "host")
+    no_bump(f4)
+    # 5. ... and their carry
+    got = h.solve(*first, carry=True)
+    no_bump(h)
+    same(got, f4.solve(*first, carry=True), "carry")
+    no_bump(f4)
+    for s in (h, f1, f2, f3, f4):
+        s.close()
+    model.free()
