@@ -2680,6 +2680,11 @@ constexpr NamedPanel kNamedPanels[] = {
     {"Y_bar", &BatchWS::Yb, false, false, true},     {"ray_d", &BatchWS::DS, true, true, false},
     {"ray_y", &BatchWS::YS, false, true, false},     {"ray_prev_x", &BatchWS::prevX, true, true, false},
     {"ray_prev_y", &BatchWS::prevY, false, true, false}, {"ray_z", &BatchWS::Zray, true, true, false},
+    // what a warm start seeds and forms (ws_start), for the tests that check it by value
+    {"X", &BatchWS::X, true, false, false},          {"X_hat", &BatchWS::Xh, true, false, false},
+    {"last_X", &BatchWS::lastX, true, false, false}, {"Y", &BatchWS::Y, false, false, false},
+    {"last_Y", &BatchWS::lastY, false, false, false}, {"Z_bar", &BatchWS::Zb, true, false, false},
+    {"Y_obj", &BatchWS::Yobj, false, false, false},
 };
 const NamedPanel &named_panel(const BatchWS &w, const std::string &name, const char *who) {
     for (const NamedPanel &p : kNamedPanels)
@@ -2692,7 +2697,7 @@ const NamedPanel &named_panel(const BatchWS &w, const std::string &name, const c
 }  // namespace
 
 // The first B members of a panel of the last successful solve by name, column-major rows x B (download_panel): C, AL, AU, L, U,
-// X_bar, Y_bar, ray_d, ray_y, ray_prev_x, ray_prev_y; ray_z runs launch_ray_product and returns its product A^T ray_y; row_norm /
+// X_bar, Y_bar, X, X_hat, last_X, Y, last_Y, Z_bar, Y_obj, ray_d, ray_y, ray_prev_x, ray_prev_y; ray_z runs launch_ray_product and returns its product A^T ray_y; row_norm /
 // col_norm: the shared matrix' norms (m / n values).  "raw:" in front of a panel's name: the whole padded panel in the device's
 // layout, rows x Bp (panel_index).  out null: only the count.  Returns the count of values; throws where `len` is another.
 long batched_solver_get_panel(BatchedSolver *h, const char *name, double *out, long len) {

@@ -988,8 +988,9 @@ class BatchedSolver:
 
     def get_panel(self, name):
         """A panel of the last successful solve by name (hprlp_batched_solver_get_panel), scaled units: (rows, B) for C, AL, AU, L,
-        U, X_bar, Y_bar, ray_d, ray_y, ray_prev_x, ray_prev_y, ray_z; a vector for row_norm / col_norm; "raw:" + name: the padded
-        panel as the device holds it, flat (element (i, k) at ((k // Bc) * rows + i) * Bc + k % Bc, see info())."""
+        U, X_bar, Y_bar, ray_d, ray_y, ray_prev_x, ray_prev_y, ray_z, and (read only: what a warm start seeds and forms) X, X_hat,
+        last_X, Y, last_Y, Z_bar, Y_obj; a vector for row_norm / col_norm; "raw:" + name: the padded panel as the device holds
+        it, flat (element (i, k) at ((k // Bc) * rows + i) * Bc + k % Bc, see info())."""
         if not self._h:
             raise RuntimeError("BatchedSolver: closed")
         nm = name.encode()

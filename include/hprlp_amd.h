@@ -281,7 +281,8 @@ int hprlp_batched_solver_transfer(hprlp_batched_solver *h, long out[4]);
 int hprlp_batched_solver_ray_step(hprlp_batched_solver *h, const int *active, int restart, double *out, int *tested);
 /* A panel of the last successful solve by name, the first B members column-major rows x B in SCALED units: C, L, U, X_bar, ray_d,
  * ray_prev_x (n rows), AL, AU, Y_bar, ray_y, ray_prev_y (m rows) -- infinite sides and bounds read +-1e100 -- and ray_z
- * (n rows: the product A^T ray_y of the certificates, computed by the call); row_norm (m values) / col_norm (n values).  "raw:"
+ * (n rows: the product A^T ray_y of the certificates, computed by the call); row_norm (m values) / col_norm (n values).  Read
+ * only, for the warm start's value tests: X, X_hat, last_X, Z_bar (n rows) and Y, last_Y, Y_obj (m rows).  "raw:"
  * before a panel's name: the whole padded panel in the device's layout, rows x Bp.  out NULL: only the count.  Returns the count
  * of values (len must equal it), or -1 + hprlp_last_error() (an unknown name; a ray_* name before a detecting solve or a step). */
 long hprlp_batched_solver_get_panel(hprlp_batched_solver *h, const char *name, double *out, long len);

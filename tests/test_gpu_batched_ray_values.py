@@ -154,7 +154,7 @@ def test_batched_ray_slots_by_value_in_every_geometry(gpu, monkeypatch, kind, B,
     with pytest.raises(RuntimeError, match="no stored iterate"):
         bs.ray_step()
     with pytest.raises(RuntimeError, match="unknown panel"):
-        bs.get_panel("Z_bar")
+        bs.get_panel("Z_hat")
     with pytest.raises(RuntimeError, match="cannot be written"):
         bs.set_panel("C", base["C"])
     assert bs.ray_step(restart=True) is None

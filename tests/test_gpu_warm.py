@@ -106,6 +106,18 @@ assert rs.status == "ITER_LIMIT" and rs.iter == 0 and row["iter"] == 0, (rs.stat
 for k, v in want.items():
     assert abs(row[k] - v) <= 1e-10 * abs(v) + 1e-14, (k, row[k], v)
 np.testing.assert_allclose(rs.x, xp, rtol=1e-12, atol=1e-12 * np.abs(xp).max())
+# ... y in the caller's numbering (the only check of k_start_in's row permutation), and z = the dual completion of the returned y
+# in the caller's units, per element within the start reference's bound plus the allowance for the roundings of scale()
+np.testing.assert_allclose(rs.y, yp, rtol=1e-12, atol=1e-12 * np.abs(yp).max())
+import evalref as E, startref as S
+AT = sparse.csr_matrix(sparse.csr_matrix(lp["A"]).T); AT.sort_indices()
+inp = E.unit_inputs(lp, (AT.indptr, AT.indices, AT.data))
+zr, ez = S.evaluate_start(*inp, rs.x, rs.y)["z_bar"]
+tolz = S.TOL_FACTOR * ez + S.caller_units_z_allowance(inp[1], lp["c"], rs.y, zr, curtis_reid=True)
+dz = np.abs(rs.z.astype(E.LD) - zr)
+assert np.isfinite(rs.z).all() and (dz <= tolz).all(), (int(np.argmax(dz - tolz)), float((dz / tolz)[tolz > 0].max()))
+assert (rs.z > 0).any() and (rs.z == 0).any()
+print("z: largest difference / tolerance", float((dz / tolz)[tolz > 0].max()))
 # (2) a start that meets the tolerance ends OPTIMAL at iteration 0: the planted optimum, through hprlp_solve_warm
 prm = hprlp.Parameters(stop_tol=1e-6, max_iter=20000, use_presolve=False)
 r = model.solve_warm(lp["x_star"], lp["y_star"], prm)
