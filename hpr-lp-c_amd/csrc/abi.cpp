@@ -1352,16 +1352,60 @@ static std::vector<Solver *> group_members(hprlp_solver **h, int count, const ch
     check_group(s.data(), count, who, need_scaled);
     return s;
 }
+// the refusals of a group entry's plain arguments, in their order: the list, the count, then `arg` (data or results, `what` in the
+// message); group_members comes next
+static void check_group_args(hprlp_solver **h, int count, const void *arg, const char *what, const char *who) {
+    const std::string w(who);
+    if (!h) throw std::runtime_error(w + ": null solver list");
+    if (count <= 0) throw std::runtime_error(w + ": count must be positive");
+    if (!arg) throw std::runtime_error(w + ": null " + what);
+}
+
+// the public member structs as many.h's
+static MemberData to_private(const hprlp_member_data &d) {
+    MemberData r;
+    r.c = d.c, r.obj_constant = d.obj_constant, r.AL = d.AL, r.AU = d.AU, r.l = d.l, r.u = d.u;
+    return r;
+}
+static MemberValues to_private(const hprlp_member_values &d) {
+    MemberValues r;
+    r.val = d.val, r.nnz = d.nnz, r.c = d.c, r.obj_constant = d.obj_constant, r.AL = d.AL, r.AU = d.AU, r.l = d.l, r.u = d.u;
+    return r;
+}
+static MemberStart to_private(const hprlp_member_start &b) {
+    MemberStart r;
+    r.x0 = b.x0, r.y0 = b.y0, r.sigma = b.sigma;
+    return r;
+}
+static MemberOut to_private(const hprlp_member_out &o) {
+    MemberOut r;
+    r.x = o.x, r.y = o.y, r.z = o.z;
+    return r;
+}
+// one private struct per member; a null list: every member's default (a cold start, no output wanted)
+template <class Private, class Public>
+static std::vector<Private> private_members(const Public *list, int count) {
+    std::vector<Private> v(static_cast<size_t>(count));
+    for (int k = 0; list && k < count; ++k) v[k] = to_private(list[k]);
+    return v;
+}
+
+// The count blocks of the group calls: eight slots each, the calling thread's own, filled by keep_counts and read by the
+// hprlp_last_*_counts accessors.  Which call zeroes which block, and when, is the call's own business (tests read it).
+static void keep_counts(long (&block)[8], const long (&v)[8]) {
+    for (int i = 0; i < 8; ++i) block[i] = v[i];
+}
+static int read_counts(const long (&block)[8], long out[8]) {
+    if (!out) return -1;
+    for (int i = 0; i < 8; ++i) out[i] = block[i];
+    return 0;
+}
 
 // ---- group set-up, scaling and teardown (DESIGN.md "Many small LPs", group set-up) -------------------------------------------
 // counts of the calling thread's last hprlp_solver_create_many / _scale_many / _destroy_many; each call zeroes and fills its own
 static thread_local long g_setup_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
-extern "C" int hprlp_last_setup_many_counts(long out[8]) {
-    if (!out) return -1;
-    for (int i = 0; i < 8; ++i) out[i] = g_setup_counts[i];
-    return 0;
-}
+extern "C" int hprlp_last_setup_many_counts(long out[8]) { return read_counts(g_setup_counts, out); }
 
 // hprlp_solver_create for every model.  together: the members whose set-up only allocates, zeroes and uploads
 // (Solver::group_setup_fits) are created inside one arena -- a few device blocks, one pinned block, one stream, one copy per
@@ -1511,15 +1555,10 @@ extern "C" int hprlp_solver_restart_many(hprlp_solver **h, int count, const doub
 // counts of the calling thread's last hprlp_solver_run_many / hprlp_solve_many (hprlp_last_run_many_counts)
 static thread_local long g_many_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 static void keep_many_counts(const GroupCounts &gc) {
-    const long v[8] = {gc.rounds, gc.waits, gc.group_launches, gc.copies, gc.own, gc.served, gc.ray_served, gc.certs_served};
-    for (int i = 0; i < 8; ++i) g_many_counts[i] = v[i];
+    keep_counts(g_many_counts, {gc.rounds, gc.waits, gc.group_launches, gc.copies, gc.own, gc.served, gc.ray_served, gc.certs_served});
 }
 
-extern "C" int hprlp_last_run_many_counts(long out[8]) {
-    if (!out) return -1;
-    for (int i = 0; i < 8; ++i) out[i] = g_many_counts[i];
-    return 0;
-}
+extern "C" int hprlp_last_run_many_counts(long out[8]) { return read_counts(g_many_counts, out); }
 
 static void free_results_arrays(HPRLP_results *out, int count) {
     for (int k = 0; k < count; ++k) {
@@ -1546,32 +1585,34 @@ extern "C" int hprlp_solver_run_many(hprlp_solver **h, int count, HPRLP_results 
     GUARD_END(-1)
 }
 
-// ---- group re-solve (DESIGN.md "Many small LPs", group re-solve) -------------------------------------------------------------
-// counts of the calling thread's last hprlp_solver_set_data_many / hprlp_solver_resolve_many (hprlp_last_resolve_many_counts)
+// ---- group re-solve, group matrix values, group device re-solve (DESIGN.md "Many small LPs") ------------------------------------
+// counts of the calling thread's last hprlp_solver_set_data_many / _resolve_many (hprlp_last_resolve_many_counts) and
+// hprlp_solver_set_matrix_values_many (hprlp_last_values_many_counts); the device entries put theirs in the same blocks, and what
+// only a device call has in g_device_counts (hprlp_last_many_device_counts), which many.cpp fills as the call proceeds
 static thread_local long g_resolve_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+static thread_local long g_values_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+static thread_local DeviceCounts g_device_counts;
 static void keep_resolve_counts(const ResolveCounts &rc) {
-    const long v[8] = {rc.h2d, rc.d2h, rc.waits, rc.launches, rc.memsets, rc.served, rc.own, rc.loop_own};
-    for (int i = 0; i < 8; ++i) g_resolve_counts[i] = v[i];
+    keep_counts(g_resolve_counts, {rc.h2d, rc.d2h, rc.waits, rc.launches, rc.memsets, rc.served, rc.own, rc.loop_own});
+}
+static void keep_values_counts(const ValuesCounts &vc) {
+    keep_counts(g_values_counts, {vc.h2d, vc.d2h, vc.waits, vc.launches, vc.memsets, vc.served, vc.own, vc.maps});
 }
 
-extern "C" int hprlp_last_resolve_many_counts(long out[8]) {
-    if (!out) return -1;
-    for (int i = 0; i < 8; ++i) out[i] = g_resolve_counts[i];
-    return 0;
+extern "C" int hprlp_last_resolve_many_counts(long out[8]) { return read_counts(g_resolve_counts, out); }
+extern "C" int hprlp_last_values_many_counts(long out[8]) { return read_counts(g_values_counts, out); }
+extern "C" int hprlp_last_many_device_counts(long out[8]) {
+    const DeviceCounts &d = g_device_counts;
+    return read_counts({d.pointers, d.lookups, d.check_launches, d.flags, d.served, d.own, d.waits_before_write, 0}, out);
 }
 
+// (Each entry zeroes its count blocks where it always did -- before or after the argument checks: the accessors show it.)
 extern "C" int hprlp_solver_set_data_many(hprlp_solver **h, int count, const hprlp_member_data *data) {
     GUARD_BEGIN
-    // (list, count, data, then the members: the order of the refusals)
-    if (!h) throw std::runtime_error("hprlp_solver_set_data_many: null solver list");
-    if (count <= 0) throw std::runtime_error("hprlp_solver_set_data_many: count must be positive");
-    if (!data) throw std::runtime_error("hprlp_solver_set_data_many: null data");
-    std::vector<Solver *> s = group_members(h, count, "hprlp_solver_set_data_many");
-    std::vector<MemberData> d(static_cast<size_t>(count));
-    for (int k = 0; k < count; ++k) {
-        d[k].c = data[k].c, d[k].obj_constant = data[k].obj_constant;
-        d[k].AL = data[k].AL, d[k].AU = data[k].AU, d[k].l = data[k].l, d[k].u = data[k].u;
-    }
+    const char *who = "hprlp_solver_set_data_many";
+    check_group_args(h, count, data, "data", who);
+    std::vector<Solver *> s = group_members(h, count, who);
+    const std::vector<MemberData> d = private_members<MemberData>(data, count);
     keep_resolve_counts(ResolveCounts());
     ResolveCounts rc;
     set_data_many(s.data(), count, d.data(), &rc);
@@ -1582,13 +1623,11 @@ extern "C" int hprlp_solver_set_data_many(hprlp_solver **h, int count, const hpr
 
 extern "C" int hprlp_solver_resolve_many(hprlp_solver **h, int count, const hprlp_member_start *start, HPRLP_results *out) {
     GUARD_BEGIN
-    if (!h) throw std::runtime_error("hprlp_solver_resolve_many: null solver list");
-    if (count <= 0) throw std::runtime_error("hprlp_solver_resolve_many: count must be positive");
-    if (!out) throw std::runtime_error("hprlp_solver_resolve_many: null results");
-    std::vector<Solver *> s = group_members(h, count, "hprlp_solver_resolve_many");
-    std::vector<MemberStart> b(static_cast<size_t>(count));
-    for (int k = 0; start && k < count; ++k) b[k].x0 = start[k].x0, b[k].y0 = start[k].y0, b[k].sigma = start[k].sigma;
-    check_starts(s.data(), count, b.data());  // (before the results are touched: a refusal leaves the output arrays as they were)
+    const char *who = "hprlp_solver_resolve_many";
+    check_group_args(h, count, out, "results", who);
+    std::vector<Solver *> s = group_members(h, count, who);
+    const std::vector<MemberStart> b = private_members<MemberStart>(start, count);
+    check_starts(s.data(), count, b.data(), who, true);  // (before the results are touched: a refusal leaves the output arrays as they were)
     for (int k = 0; k < count; ++k) out[k] = make_error_result("ERROR");
     keep_resolve_counts(ResolveCounts());
     try {
@@ -1603,33 +1642,13 @@ extern "C" int hprlp_solver_resolve_many(hprlp_solver **h, int count, const hprl
     GUARD_END(-1)
 }
 
-// ---- group matrix values (DESIGN.md "Many small LPs", group matrix values) ----------------------------------------------------
-// counts of the calling thread's last hprlp_solver_set_matrix_values_many (hprlp_last_values_many_counts)
-static thread_local long g_values_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-static void keep_values_counts(const ValuesCounts &vc) {
-    const long v[8] = {vc.h2d, vc.d2h, vc.waits, vc.launches, vc.memsets, vc.served, vc.own, vc.maps};
-    for (int i = 0; i < 8; ++i) g_values_counts[i] = v[i];
-}
-
-extern "C" int hprlp_last_values_many_counts(long out[8]) {
-    if (!out) return -1;
-    for (int i = 0; i < 8; ++i) out[i] = g_values_counts[i];
-    return 0;
-}
-
 extern "C" int hprlp_solver_set_matrix_values_many(hprlp_solver **h, int count, const hprlp_member_values *data) {
     GUARD_BEGIN
+    const char *who = "hprlp_solver_set_matrix_values_many";
     keep_values_counts(ValuesCounts());
-    // (list, count, data, then the members: the order of the refusals)
-    if (!h) throw std::runtime_error("hprlp_solver_set_matrix_values_many: null solver list");
-    if (count <= 0) throw std::runtime_error("hprlp_solver_set_matrix_values_many: count must be positive");
-    if (!data) throw std::runtime_error("hprlp_solver_set_matrix_values_many: null data");
-    std::vector<Solver *> s = group_members(h, count, "hprlp_solver_set_matrix_values_many");
-    std::vector<MemberValues> d(static_cast<size_t>(count));
-    for (int k = 0; k < count; ++k) {
-        d[k].val = data[k].val, d[k].nnz = data[k].nnz, d[k].c = data[k].c, d[k].obj_constant = data[k].obj_constant;
-        d[k].AL = data[k].AL, d[k].AU = data[k].AU, d[k].l = data[k].l, d[k].u = data[k].u;
-    }
+    check_group_args(h, count, data, "data", who);
+    std::vector<Solver *> s = group_members(h, count, who);
+    const std::vector<MemberValues> d = private_members<MemberValues>(data, count);
     ValuesCounts vc;
     set_matrix_values_many(s.data(), count, d.data(), &vc);
     keep_values_counts(vc);
@@ -1637,32 +1656,14 @@ extern "C" int hprlp_solver_set_matrix_values_many(hprlp_solver **h, int count, 
     GUARD_END(-1)
 }
 
-// ---- group device re-solve (DESIGN.md "Many small LPs", group device re-solve): the three group entries with the vectors in device
-// memory.  ResolveCounts / ValuesCounts go where the host entries put theirs; what only a device call has is kept here.
-static thread_local DeviceCounts g_device_counts;
-
-extern "C" int hprlp_last_many_device_counts(long out[8]) {
-    if (!out) return -1;
-    const DeviceCounts &d = g_device_counts;
-    const long v[8] = {d.pointers, d.lookups, d.check_launches, d.flags, d.served, d.own, d.waits_before_write, 0};
-    for (int i = 0; i < 8; ++i) out[i] = v[i];
-    return 0;
-}
-
 extern "C" int hprlp_solver_set_data_many_device(hprlp_solver **h, int count, const hprlp_member_data *data, void *stream) {
     GUARD_BEGIN
+    const char *who = "hprlp_solver_set_data_many_device";
     g_device_counts = DeviceCounts();
     keep_resolve_counts(ResolveCounts());
-    // (list, count, data, then the members: the order of the refusals)
-    if (!h) throw std::runtime_error("hprlp_solver_set_data_many_device: null solver list");
-    if (count <= 0) throw std::runtime_error("hprlp_solver_set_data_many_device: count must be positive");
-    if (!data) throw std::runtime_error("hprlp_solver_set_data_many_device: null data");
-    std::vector<Solver *> s = group_members(h, count, "hprlp_solver_set_data_many_device");
-    std::vector<MemberData> d(static_cast<size_t>(count));
-    for (int k = 0; k < count; ++k) {
-        d[k].c = data[k].c, d[k].obj_constant = data[k].obj_constant;
-        d[k].AL = data[k].AL, d[k].AU = data[k].AU, d[k].l = data[k].l, d[k].u = data[k].u;
-    }
+    check_group_args(h, count, data, "data", who);
+    std::vector<Solver *> s = group_members(h, count, who);
+    const std::vector<MemberData> d = private_members<MemberData>(data, count);
     ResolveCounts rc;
     set_data_many_device(s.data(), count, d.data(), static_cast<hipStream_t>(stream), &rc, &g_device_counts);
     keep_resolve_counts(rc);
@@ -1673,16 +1674,14 @@ extern "C" int hprlp_solver_set_data_many_device(hprlp_solver **h, int count, co
 extern "C" int hprlp_solver_resolve_many_device(hprlp_solver **h, int count, const hprlp_member_start *start, const hprlp_member_out *dst,
                                                 void *stream, HPRLP_results *out) {
     GUARD_BEGIN
+    const char *who = "hprlp_solver_resolve_many_device";
     g_device_counts = DeviceCounts();
     keep_resolve_counts(ResolveCounts());
-    if (!h) throw std::runtime_error("hprlp_solver_resolve_many_device: null solver list");
-    if (count <= 0) throw std::runtime_error("hprlp_solver_resolve_many_device: count must be positive");
-    if (!out) throw std::runtime_error("hprlp_solver_resolve_many_device: null results");
-    std::vector<Solver *> s = group_members(h, count, "hprlp_solver_resolve_many_device");
-    std::vector<MemberStart> b(static_cast<size_t>(count));
-    for (int k = 0; start && k < count; ++k) b[k].x0 = start[k].x0, b[k].y0 = start[k].y0, b[k].sigma = start[k].sigma;
-    std::vector<MemberOut> o(static_cast<size_t>(count));
-    for (int k = 0; dst && k < count; ++k) o[k].x = dst[k].x, o[k].y = dst[k].y, o[k].z = dst[k].z;
+    check_group_args(h, count, out, "results", who);
+    std::vector<Solver *> s = group_members(h, count, who);
+    const std::vector<MemberStart> b = private_members<MemberStart>(start, count);
+    const std::vector<MemberOut> o = private_members<MemberOut>(dst, count);
+    check_starts(s.data(), count, b.data(), who, false);  // (the starts' entries are the device check's)
     // (a refusal leaves the output array as it was: the results are touched once the call goes through)
     std::vector<HPRLP_results> res(static_cast<size_t>(count), make_error_result("ERROR"));
     ResolveCounts rc;
@@ -1695,18 +1694,12 @@ extern "C" int hprlp_solver_resolve_many_device(hprlp_solver **h, int count, con
 
 extern "C" int hprlp_solver_set_matrix_values_many_device(hprlp_solver **h, int count, const hprlp_member_values *data, void *stream) {
     GUARD_BEGIN
+    const char *who = "hprlp_solver_set_matrix_values_many_device";
     g_device_counts = DeviceCounts();
     keep_values_counts(ValuesCounts());
-    // (list, count, data, then the members: the order of the refusals)
-    if (!h) throw std::runtime_error("hprlp_solver_set_matrix_values_many_device: null solver list");
-    if (count <= 0) throw std::runtime_error("hprlp_solver_set_matrix_values_many_device: count must be positive");
-    if (!data) throw std::runtime_error("hprlp_solver_set_matrix_values_many_device: null data");
-    std::vector<Solver *> s = group_members(h, count, "hprlp_solver_set_matrix_values_many_device");
-    std::vector<MemberValues> d(static_cast<size_t>(count));
-    for (int k = 0; k < count; ++k) {
-        d[k].val = data[k].val, d[k].nnz = data[k].nnz, d[k].c = data[k].c, d[k].obj_constant = data[k].obj_constant;
-        d[k].AL = data[k].AL, d[k].AU = data[k].AU, d[k].l = data[k].l, d[k].u = data[k].u;
-    }
+    check_group_args(h, count, data, "data", who);
+    std::vector<Solver *> s = group_members(h, count, who);
+    const std::vector<MemberValues> d = private_members<MemberValues>(data, count);
     ValuesCounts vc;
     set_matrix_values_many_device(s.data(), count, d.data(), static_cast<hipStream_t>(stream), &vc, &g_device_counts);
     keep_values_counts(vc);

@@ -10,8 +10,9 @@
 // (Solver::joins_group) issues its own launches inside the same lock-step; so does every member for its iteration-0 evaluation
 // (resolve_many apart: the group re-solve further down).  The ray tests of the infeasibility detection and the certificates of the
 // members that join are the group's as well (DESIGN.md "Many small LPs", group detection).  New matrix values for the whole group
-// (set_matrix_values_many) share scale_many's walk of Solver::scale() (scale_walk).  The three group entries with the vectors in the
-// caller's device memory (DESIGN.md "Many small LPs", group device re-solve) are at the end of this file.
+// (set_matrix_values_many) share scale_many's walk of Solver::scale() (scale_walk).  Each of the three group entries for new data,
+// re-solve and new values has a twin with the vectors in the caller's device memory (DESIGN.md "Many small LPs", group device
+// re-solve): the two share their steps, one body per pair where the arrangement allows (the second half of this file).
 //
 // Ordering is by stream: for the duration of a call every member works on ONE stream (the first member's), after its own stream
 // has been waited for once; the members' streams come back at exit, after one wait for the group's.
@@ -19,6 +20,7 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <exception>
 
 #include "many.h"
 #include "group_pack.h"
@@ -511,10 +513,13 @@ void run_many(Solver **s, int count, HPRLP_results *out, GroupCounts *counts) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// group re-solve (DESIGN.md "Many small LPs", group re-solve): set_data and resolve of every member of a group.  The rule is the
-// group launches': a workgroup runs the single kernel's body as workgroup lb of its member's own grid, so every stored number is
-// the member's own; what changes is who issues the launches, how the caller's vectors travel (one pinned block, one copy) and how
-// often the host waits (once per call outside the loop, never once per member).
+// group re-solve, group matrix values and group device re-solve (DESIGN.md "Many small LPs"): set_data, resolve and
+// set_matrix_values of every member of a group, with the members' vectors in host memory or in device memory of the caller's.
+// The rule is the group launches': a workgroup runs the single kernel's body as workgroup lb of its member's own grid (the bodies
+// of values.hip's kernels included), the zeroing is reset_iterates' fills, the scaling is scale_many's walk, so every stored number
+// is the member's own; what changes is who issues the launches, how the caller's vectors travel and how often the host waits
+// (once per call outside the loop, never once per member).  A host entry and its device twin are ONE body over a Source (below):
+// the shared steps are written once, and where the body branches on the source a comment names the difference.
 // ------------------------------------------------------------------------------------------------
 // The blocks of a group call, kept with member 0 (the owner of the group's stream) and grown on demand: staging of the data / the
 // starts (pinned, and its device copy), the data passes' partials, the solutions (device, and pinned), the launch tables.
@@ -523,11 +528,11 @@ struct GroupBlocks {
     DBuf<double> parts, out_d;
     HBuf<double> out_h;
     GroupLaunches gl;
-    // set_matrix_values_many: the recorder with a table for every kind (what scale_walk asks for), one flag word per member
+    // set_matrix_values: the recorder with a table for every kind (what scale_walk asks for); the flag words of a check stage
     GroupLaunches tables{/*own_launches=*/false};
     DBuf<unsigned long long> flags;
     HBuf<unsigned long long> flags_h;
-    // the device entries (DESIGN.md "Many small LPs", group device re-solve): the event recorded on the caller's stream
+    // the device entries: the event recorded on the caller's stream
     hipEvent_t inputs_ready = nullptr;
     GroupBlocks() = default;
     GroupBlocks(const GroupBlocks &) = delete;
@@ -539,18 +544,148 @@ struct GroupBlocks {
 
 namespace {
 
+// What tells a host group entry from its device twin.  A host entry reads pieces of the pinned staging block after one copy,
+// checks the vectors with host loops, copies the solutions back in one block, and a member that goes its own way runs
+// Solver::set_data / resolve / set_matrix_values.  A device entry reads the caller's buffers after one event wait on `caller`,
+// looks every pointer up (PointerChecks) and checks the vectors where they lie in one stage (check_stage), stores the solutions
+// into the caller's buffers, and a member on its own runs Solver::set_data_device / resolve_device / set_matrix_values_device.
+// The nominal counts of those single entries differ and stay next to the calls.
+struct Source {
+    const char *who;               // the entry's name, in front of every message
+    hipStream_t caller = nullptr;  // a device entry: the stream the inputs were produced on
+    DeviceCounts *dc = nullptr;    // a device entry: filled as the call proceeds, so it also tells what a refused call did
+    bool device() const { return dc != nullptr; }
+};
+
 GroupBlocks &blocks_of(Solver *owner) {
     if (!owner->group_blocks) owner->group_blocks = std::make_shared<GroupBlocks>();
     return *owner->group_blocks;
 }
 
+// The cleanup shell of a group call: on a throw the owner's blocks go, and whatever was recorded into them goes with them.
+struct DropBlocksOnThrow {
+    Solver *owner;  // null: the call holds no blocks
+    int live = std::uncaught_exceptions();
+    ~DropBlocksOnThrow() {
+        if (owner && std::uncaught_exceptions() > live) owner->group_blocks.reset();
+    }
+};
+
 std::string member(const char *who, int k) { return std::string(who) + ": member " + std::to_string(k); }
 
+// The members of the group launches: the wanted ones, two at least (a group of one issues the member's own launches).
+std::vector<int> joiners(const std::vector<char> &wanted, std::vector<char> &mask) {
+    std::vector<int> in;
+    for (size_t k = 0; k < wanted.size(); ++k)
+        if (wanted[k]) in.push_back(static_cast<int>(k));
+    if (in.size() < 2) in.clear();
+    mask.assign(wanted.size(), 0);
+    for (int k : in) mask[k] = 1;
+    return in;
+}
+
+// ---- the checks of host vectors: a host entry's only (a device entry's vectors are checked where they lie, check_stage)
+void host_scan(const char *who, int k, const double *v, long len, const char *what, bool finite, const char *verdict) {
+    for (long i = 0; v && i < len; ++i)
+        if (finite ? !std::isfinite(v[i]) : std::isnan(v[i]))
+            throw std::runtime_error(member(who, k) + ": " + what + "[" + std::to_string(i) + "] " + verdict);
+}
+void host_no_nan(const char *who, int k, const Solver &m, const double *c, const double *AL, const double *AU, const double *l, const double *u) {
+    const struct { const double *v; long len; const char *what; } vecs[5] = {{c, m.n, "c"}, {AL, m.m, "AL"}, {AU, m.m, "AU"}, {l, m.n, "l"}, {u, m.n, "u"}};
+    for (const auto &e : vecs) host_scan(who, k, e.v, e.len, e.what, false, "is NaN");
+}
+
+// ---- the checks of a device entry
+// The pointer checks of one call.  A pointer that lies, with its length, inside a range the runtime has already reported in this
+// call is device memory of the group's device with room for it: no second lookup (a group cut from a few packed tensors costs a
+// few lookups whatever its size).  Everything else goes through check_device_pointer, whose words the refusal carries.
+class PointerChecks {
+  public:
+    PointerChecks(int device, const char *who, DeviceCounts &dc) : device_(device), who_(who), dc_(dc) {}
+    void operator()(int k, const void *p, size_t count, const char *name) {
+        if (!p) return;  // (not given / not wanted)
+        ++dc_.pointers;
+        const char *b = static_cast<const char *>(p), *e = b + count * sizeof(double);
+        if (reinterpret_cast<uintptr_t>(p) % sizeof(double) == 0)
+            for (const DeviceRange &r : seen_)
+                if (b >= r.base && e <= r.base + r.bytes) return;
+        ++dc_.lookups;
+        DeviceRange r;
+        check_device_pointer(p, count, device_, name, member(who_, k).c_str(), &r);
+        if (r.bytes > 0) seen_.push_back(r);
+    }
+    void data_vectors(int k, size_t m, size_t n, const double *c, const double *AL, const double *AU, const double *l, const double *u) {
+        (*this)(k, c, n, "c"); (*this)(k, AL, m, "AL"); (*this)(k, AU, m, "AU"); (*this)(k, l, n, "l"); (*this)(k, u, n, "u");
+    }
+
+  private:
+    int device_;
+    const char *who_;
+    DeviceCounts &dc_;
+    std::vector<DeviceRange> seen_;
+};
+
+// The group's stream waits for what the caller's stream has been given so far (one event per call).
+void wait_for_caller(GroupBlocks &gb, hipStream_t caller, hipStream_t st) {
+    if (!gb.inputs_ready) HIP_CHECK(hipEventCreateWithFlags(&gb.inputs_ready, hipEventDisableTiming));
+    HIP_CHECK(hipEventRecord(gb.inputs_ready, caller));
+    HIP_CHECK(hipStreamWaitEvent(st, gb.inputs_ready, 0));
+}
+
+// ---- the flag block.  `words` flag words of all ones (kDataCheckClean, kValuesAllFinite) by ONE memset; fetch_flags: one copy,
+// one wait
+unsigned long long *cleared_flags(GroupBlocks &gb, size_t words, hipStream_t st) {
+    if (gb.flags.n < words) {
+        gb.flags.alloc(words);
+        gb.flags_h.alloc(words);
+    }
+    HIP_CHECK(hipMemsetAsync(gb.flags.p, 0xff, sizeof(unsigned long long) * words, st));
+    return gb.flags.p;
+}
+const unsigned long long *fetch_flags(GroupBlocks &gb, size_t words, hipStream_t st) {
+    HIP_CHECK(hipMemcpyAsync(gb.flags_h.p, gb.flags.p, sizeof(unsigned long long) * words, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    return gb.flags_h.p;
+}
+// One check stage, before the first write of anything a solver reads: the cleared words, what `record` records against them as ONE
+// stage of the group's launches, the words back.  Counted into the call's counts and, for a device entry, into dc.
+template <class Record>
+const unsigned long long *check_stage(GroupBlocks &gb, size_t words, hipStream_t st, CallCounts &c, DeviceCounts *dc, Record record) {
+    unsigned long long *flags = cleared_flags(gb, words, st);
+    ++c.memsets;
+    GroupLaunches &chk = gb.gl;
+    const long tables0 = chk.tables_sent();
+    record(chk, flags);
+    const int launches = chk.run(st);
+    c.launches += launches;
+    if (dc) dc->check_launches += launches;
+    c.h2d += chk.tables_sent() - tables0;
+    const unsigned long long *back = fetch_flags(gb, words, st);
+    ++c.d2h, ++c.waits;
+    if (dc) dc->flags += static_cast<long>(words), ++dc->waits_before_write;
+    return back;
+}
+DataCheckArgs nan_check(int m, int n, const double *c, const double *AL, const double *AU, const double *l, const double *u) {
+    return DataCheckArgs{{c, AL, AU, l, u}, {n, m, m, n, n}, 0};
+}
+// k_data_check's word of member k as the host group entries' message
+void throw_if_flagged(unsigned long long word, const char *const names[kDataCheckVecs], const std::string &who, const char *what) {
+    if (word == kDataCheckClean) return;
+    const int v = static_cast<int>(word >> kDataCheckShift);
+    const unsigned long long i = word & ((1ULL << kDataCheckShift) - 1);
+    throw std::runtime_error(who + ": " + (v < kDataCheckVecs ? names[v] : "?") + "[" + std::to_string(i) + "] " + what);
+}
+const char *const kDataNames[kDataCheckVecs] = {"c", "AL", "AU", "l", "u"};  // (the host entries' order of vectors)
+const char *const kStartNames[kDataCheckVecs] = {"x0", "y0", "", "", ""};
+
+// ------------------------------------------------------------------------------------------------
+// set_data_many / set_data_many_device
+// ------------------------------------------------------------------------------------------------
 // The two data passes of the members `in`: recorded, run, the scalars packed and fetched, ONE wait, then each member's host
-// formulas.  src[k]: where member k's given vectors are read on the device -- pieces of the staging block, or the caller's own
-// buffers (the device entries); data[k].obj_constant is host memory either way.
-void data_passes(Solver **s, const std::vector<int> &in, const std::vector<PackMember> &pm, const MemberData *data, const MemberData *src,
-                 GroupBlocks &gb, hipStream_t st, ResolveCounts &rc, clock_type::time_point t0, bool device_entry) {
+// formulas.  at[k]: where member k's given vectors are read on the device -- pieces of the staging block, or the caller's own
+// buffers; data[k].obj_constant is host memory either way.
+void data_passes(Solver **s, const std::vector<int> &in, const std::vector<PackMember> &pm, const MemberData *data, const MemberData *at,
+                 GroupBlocks &gb, hipStream_t st, ResolveCounts &rc, clock_type::time_point t0, const Source &src) {
     const int nj = static_cast<int>(in.size());
     const size_t per = static_cast<size_t>(4) * kReduceBlocks;
     if (gb.parts.n < per * nj) gb.parts.alloc(per * nj);
@@ -561,7 +696,7 @@ void data_passes(Solver **s, const std::vector<int> &in, const std::vector<PackM
         Solver &m = *s[k];
         m.data_time[0] = m.data_time[1] = m.data_time[2] = 0.0;
         if (data[k].obj_constant) m.obj_constant = *data[k].obj_constant;
-        m.data_first_pass(src[k].AL, src[k].AU, src[k].l, src[k].u, src[k].c, pm[k].bounds, gb.parts.p + per * j, &gl);
+        m.data_first_pass(at[k].AL, at[k].AU, at[k].l, at[k].u, at[k].c, pm[k].bounds, gb.parts.p + per * j, &gl);
     }
     gl.next_stage();  // (the second pass reads the sums the first pass' finalize leaves in the member's scalars)
     for (int j = 0; j < nj; ++j) {
@@ -585,7 +720,8 @@ void data_passes(Solver **s, const std::vector<int> &in, const std::vector<PackM
         m.invalidate_far();
         m.data_time[1] = m.data_time[2] = wall;
         m.data_since_run += wall;
-        if (device_entry) m.set_transfer(0, 0, true);
+        // (the words that travelled: none for a device entry, the given vectors for a host entry)
+        if (src.device()) m.set_transfer(0, 0, true);
         else
             m.set_transfer((pm[k].bounds ? 2 * static_cast<size_t>(m.m_loc) + 2 * static_cast<size_t>(m.n_loc) : 0) + (pm[k].c ? m.n_loc : 0), 0,
                            false);
@@ -593,101 +729,161 @@ void data_passes(Solver **s, const std::vector<int> &in, const std::vector<PackM
     }
 }
 
-}  // namespace
-
-void set_data_many(Solver **s, int count, const MemberData *data, ResolveCounts *counts) {
-    const char *who = "hprlp_solver_set_data_many";
+void set_data_group(Solver **s, int count, const MemberData *data, const Source &src, ResolveCounts *counts) {
+    const char *who = src.who;
     // (the list, the count, data and the members have been checked by the caller: abi.cpp owns those refusals, group_members)
-    // ---- the host checks of all members, before the first upload (Solver::set_data's rules)
+    // ---- the host rules of all members (Solver::set_data's), before anything is launched or written
+    bool any = false;
     for (int k = 0; k < count; ++k) {
         const MemberData &d = data[k];
         const bool bounds = d.AL || d.AU || d.l || d.u;
         if (bounds && !(d.AL && d.AU && d.l && d.u))
             throw std::runtime_error(member(who, k) + ": AL, AU, l and u are given together or not at all (b_scale couples them)");
-        auto no_nan = [&](const double *v, long len, const char *what) {
-            for (long i = 0; v && i < len; ++i)
-                if (std::isnan(v[i])) throw std::runtime_error(member(who, k) + ": " + what + "[" + std::to_string(i) + "] is NaN");
-        };
-        no_nan(d.c, s[k]->n, "c"); no_nan(d.AL, s[k]->m, "AL"); no_nan(d.AU, s[k]->m, "AU"); no_nan(d.l, s[k]->n, "l"); no_nan(d.u, s[k]->n, "u");
+        if (!src.device()) host_no_nan(who, k, *s[k], d.c, d.AL, d.AU, d.l, d.u);  // (host memory only)
         if (d.obj_constant && std::isnan(*d.obj_constant)) throw std::runtime_error(member(who, k) + ": obj_constant is NaN");
+        any = any || d.c || bounds;
+    }
+    if (src.device()) {  // every pointer of every member: still nothing launched or written
+        PointerChecks pass(s[0]->prm.device_number, who, *src.dc);
+        for (int k = 0; k < count; ++k)
+            pass.data_vectors(k, static_cast<size_t>(s[k]->m_loc), static_cast<size_t>(s[k]->n_loc), data[k].c, data[k].AL, data[k].AU, data[k].l, data[k].u);
     }
     ResolveCounts rc;
     const auto t0 = time_now();
     GroupScope scope(s, count);
     const hipStream_t st = scope.group;
-    std::vector<int> in;  // the members of the group launches
     std::vector<PackMember> pm(static_cast<size_t>(count));
+    std::vector<char> wanted(static_cast<size_t>(count)), joins;
     for (int k = 0; k < count; ++k) {
-        const MemberData &d = data[k];
         pm[k].m = s[k]->m_loc, pm[k].n = s[k]->n_loc;
-        pm[k].c = d.c != nullptr, pm[k].bounds = d.AL != nullptr;
-        if ((pm[k].c || pm[k].bounds) && s[k]->joins_group_resolve()) in.push_back(k);
+        pm[k].c = data[k].c != nullptr, pm[k].bounds = data[k].AL != nullptr;
+        wanted[k] = (pm[k].c || pm[k].bounds) && s[k]->joins_group_resolve();
     }
-    if (in.size() < 2) in.clear();  // (a group of one issues the member's own launches)
-    std::vector<char> joins(static_cast<size_t>(count), 0);
-    for (int k : in) joins[k] = 1;
+    const std::vector<int> in = joiners(wanted, joins);
+    for (int k = 0; k < count; ++k)
+        if (!joins[k]) pm[k].c = pm[k].bounds = false;  // (no room in the group's block)
+    // A device entry always takes the group's blocks (its check needs the flag words), a host entry once somebody joins.
+    GroupBlocks *gb = src.device() || !in.empty() ? &blocks_of(s[0]) : nullptr;
+    DropBlocksOnThrow drop{gb ? s[0] : nullptr};
+    if (src.device() && any) {
+        // ---- a device entry's check: the vectors of ALL members where they lie, one launch, one copy of the flag words, one wait
+        wait_for_caller(*gb, src.caller, st);
+        const unsigned long long *flags = check_stage(*gb, static_cast<size_t>(count), st, rc, src.dc, [&](GroupLaunches &chk, unsigned long long *w) {
+            for (int k = 0; k < count; ++k) chk.data_check(nan_check(s[k]->m_loc, s[k]->n_loc, data[k].c, data[k].AL, data[k].AU, data[k].l, data[k].u), w + k);
+        });
+        for (int k = 0; k < count; ++k) throw_if_flagged(flags[k], kDataNames, member(who, k), "is NaN");  // (the lowest member first)
+    }
+    // -- from here on the call goes through
+    // ---- the members that go their own way: the single entry of the source's kind
     for (int k = 0; k < count; ++k) {
         const MemberData &d = data[k];
-        if (joins[k]) continue;
-        pm[k].c = pm[k].bounds = false;  // (no room in the group's block)
-        if (!(d.c || d.obj_constant || d.AL)) continue;  // nothing given: the member keeps its bits
-        s[k]->set_data(d.c, d.obj_constant, d.AL, d.AU, d.l, d.u);
+        if (joins[k] || !(d.c || d.obj_constant || d.AL)) continue;  // (nothing given: the member keeps its bits)
+        if (src.device()) s[k]->set_data_device(d.c, d.obj_constant, d.AL, d.AU, d.l, d.u, src.caller);
+        else s[k]->set_data(d.c, d.obj_constant, d.AL, d.AU, d.l, d.u);
         if (!(d.c || d.AL)) continue;  // (obj_constant alone is a host assignment)
         ++rc.own;
-        // Solver::set_data, nominal (many.h: ResolveCounts): the staging in one copy, or one per vector from the allocator cache's
-        // block size on; two passes and two finalizes; the scalars' copy and its wait
-        const size_t words = (d.AL ? 2 * static_cast<size_t>(s[k]->m_loc) + 2 * static_cast<size_t>(s[k]->n_loc) : 0) + (d.c ? s[k]->n_loc : 0);
-        rc.h2d += words * sizeof(double) < kDeviceCacheMinBytes ? 1 : (d.AL ? 4 : 0) + (d.c ? 1 : 0);
-        rc.launches += 4, rc.d2h += 1, rc.waits += 1;
+        if (src.device()) {
+            ++src.dc->own;
+            // Solver::set_data_device, nominal (many.h: ResolveCounts): the flag's memset, its check, two passes and two finalizes;
+            // the flag's copy and the scalars', a wait each
+            rc.memsets += 1, rc.launches += 5, rc.d2h += 2, rc.waits += 2;
+        } else {
+            // Solver::set_data, nominal (many.h: ResolveCounts): the staging in one copy, or one per vector from the allocator cache's
+            // block size on; two passes and two finalizes; the scalars' copy and its wait
+            const size_t words = (d.AL ? 2 * static_cast<size_t>(s[k]->m_loc) + 2 * static_cast<size_t>(s[k]->n_loc) : 0) + (d.c ? s[k]->n_loc : 0);
+            rc.h2d += words * sizeof(double) < kDeviceCacheMinBytes ? 1 : (d.AL ? 4 : 0) + (d.c ? 1 : 0);
+            rc.launches += 4, rc.d2h += 1, rc.waits += 1;
+        }
     }
-    const int nj = static_cast<int>(in.size());
-    if (nj > 0) {
-        GroupBlocks &gb = blocks_of(s[0]);
-        try {
+    if (!in.empty()) {
+        // ---- where the joiners' vectors are read: a device entry's in the caller's buffers, a host entry's in pieces of the
+        // staging block after one copy
+        std::vector<MemberData> staged;
+        if (!src.device()) {
             const GroupPackLayout L = group_pack_layout(pm.data(), count);
-            double *host = static_cast<double *>(gb.in.stage(sizeof(double) * L.data_doubles));
+            double *host = static_cast<double *>(gb->in.stage(sizeof(double) * L.data_doubles));
             for (int k : in) group_pack_data(L, k, pm[k], data[k].AL, data[k].AU, data[k].l, data[k].u, data[k].c, host);
-            gb.in.send(sizeof(double) * L.data_doubles, st);
+            gb->in.send(sizeof(double) * L.data_doubles, st);
             ++rc.h2d;
-            const double *dev = static_cast<const double *>(gb.in.dev);
+            const double *dev = static_cast<const double *>(gb->in.dev);
             auto at = [&](size_t off) { return off == kPackAbsent ? nullptr : dev + off; };
-            std::vector<MemberData> src(static_cast<size_t>(count));
+            staged.resize(static_cast<size_t>(count));
             for (int k : in) {
                 const PackSlot &p = L.slot[k];
-                src[k].c = at(p.c), src[k].AL = at(p.AL), src[k].AU = at(p.AU), src[k].l = at(p.l), src[k].u = at(p.u);
+                staged[k].c = at(p.c), staged[k].AL = at(p.AL), staged[k].AU = at(p.AU), staged[k].l = at(p.l), staged[k].u = at(p.u);
             }
-            data_passes(s, in, pm, data, src.data(), gb, st, rc, t0, false);
-        } catch (...) {
-            s[0]->group_blocks.reset();  // (whatever was recorded goes with it)
-            throw;
         }
+        data_passes(s, in, pm, data, src.device() ? data : staged.data(), *gb, st, rc, t0, src);
+        if (src.device()) src.dc->served += static_cast<long>(in.size());
     }
     if (counts) *counts = rc;
 }
 
-void check_starts(Solver *const *s, int count, const MemberStart *start) {
-    const char *who = "hprlp_solver_resolve_many";
+}  // namespace
+
+void set_data_many(Solver **s, int count, const MemberData *data, ResolveCounts *counts) {
+    set_data_group(s, count, data, Source{"hprlp_solver_set_data_many"}, counts);
+}
+void set_data_many_device(Solver **s, int count, const MemberData *data, hipStream_t caller, ResolveCounts *counts, DeviceCounts *dcounts) {
+    DeviceCounts unused;
+    set_data_group(s, count, data, Source{"hprlp_solver_set_data_many_device", caller, dcounts ? dcounts : &unused}, counts);
+}
+
+// ------------------------------------------------------------------------------------------------
+// resolve_many / resolve_many_device.  Two bodies over shared steps: the loop arrangements differ from the first member that goes
+// its own way to the last solution (see each), and folded into one function nearly every line would sit under a branch.
+// ------------------------------------------------------------------------------------------------
+void check_starts(Solver *const *s, int count, const MemberStart *start, const char *who, bool host_vectors) {
     for (int k = 0; start && k < count; ++k) {
         if (std::isnan(start[k].sigma)) throw std::runtime_error(member(who, k) + ": sigma is NaN");
-        auto finite = [&](const double *v, long len, const char *what) {
-            for (long i = 0; v && i < len; ++i)
-                if (!std::isfinite(v[i])) throw std::runtime_error(member(who, k) + ": warm start: " + what + "[" + std::to_string(i) + "] is not finite");
-        };
-        finite(start[k].x0, s[k]->n, "x0");
-        finite(start[k].y0, s[k]->m, "y0");
+        if (!host_vectors) continue;  // (a device entry's starts are checked where they lie: resolve_many_device's check stage)
+        host_scan(who, k, start[k].x0, s[k]->n, "warm start: x0", true, "is not finite");
+        host_scan(who, k, start[k].y0, s[k]->m, "warm start: y0", true, "is not finite");
     }
 }
 
 namespace {
-struct TimeBase {  // (Solver::resolve: the reported time starts from the set_data seconds since the previous loop)
-    Solver **s;
-    int count;
-    ~TimeBase() {
-        for (int k = 0; k < count; ++k) s[k]->time_base = -1.0;
+
+std::vector<int> resolve_joiners(Solver **s, int count, std::vector<char> &grouped) {
+    std::vector<char> wanted(static_cast<size_t>(count));
+    for (int k = 0; k < count; ++k) wanted[k] = s[k]->joins_group_resolve();
+    return joiners(wanted, grouped);
+}
+
+// Zeroing, bound codes, ctrl (a sigma override included) and the starts of the joiners, recorded: they run in front of the first
+// evaluation.  at[k]: where member k's start is read on the device -- pieces of the staging block, or the caller's own buffers.
+void record_starts(Solver **s, const std::vector<int> &in, const MemberStart *start, const MemberStart *at, GroupLaunches &gl, ResolveCounts &rc) {
+    for (int k : in) {
+        Solver &m = *s[k];
+        m.reset_iterates(&gl);
+        m.init_iteration_state(&gl, start[k].sigma);
+        if (start[k].x0 || start[k].y0) {
+            m.invalidate_far();
+            m.start_launch(at[k].x0, at[k].y0, nullptr, nullptr, &gl);
+        }
     }
-};
+    rc.launches += gl.recorded_launches();
+    gl.next_stage();  // (the evaluation's Rd / Rp overwrite the partials the start's finalize reads)
+}
+
+// The lock-step loop as Solver::resolve runs its own: the reported time starts from the set_data seconds since the previous loop.
+void resolve_loop(Solver **s, int count, HPRLP_results *out, GroupCounts &gc, GroupScope &scope, const std::vector<char> &joins, GroupLaunches &gl,
+                  const char *iter0) {
+    struct TimeBase {
+        Solver **s;
+        int count;
+        ~TimeBase() {
+            for (int k = 0; k < count; ++k) s[k]->time_base = -1.0;
+        }
+    } tb{s, count};
+    for (int k = 0; k < count; ++k) s[k]->time_base = s[k]->data_since_run;
+    loop_many(s, count, out, gc, scope, joins, gl, iter0);
+}
+
 }  // namespace
 
+// ALL members stay in one loop_many call -- `grouped` marks whose iteration-0 evaluation is the group's, the others ride along
+// with their own launches (rc.loop_own) -- and the solutions are collected afterwards: the joiners' through one device block.
 void resolve_many(Solver **s, int count, const MemberStart *start, HPRLP_results *out, ResolveCounts *counts) {
     std::vector<MemberStart> cold;
     if (!start) {
@@ -700,12 +896,8 @@ void resolve_many(Solver **s, int count, const MemberStart *start, HPRLP_results
         GroupScope scope(s, count);
         const hipStream_t st = scope.group;
         const std::vector<char> joins = who_joins(s, count);
-        std::vector<int> in;
-        for (int k = 0; k < count; ++k)
-            if (joins[k] && s[k]->joins_group_resolve()) in.push_back(k);
-        if (in.size() < 2) in.clear();  // (a group of one issues the member's own launches)
-        std::vector<char> grouped(static_cast<size_t>(count), 0);
-        for (int k : in) grouped[k] = 1;
+        std::vector<char> grouped;
+        const std::vector<int> in = resolve_joiners(s, count, grouped);
         const int nj = static_cast<int>(in.size());
         // ---- the members that go their own way: Solver::resolve up to its loop
         for (int k = 0; k < count; ++k) {
@@ -726,106 +918,179 @@ void resolve_many(Solver **s, int count, const MemberStart *start, HPRLP_results
         GroupLaunches own_gl;  // (nobody in the group: the loop of run_many with tables of its own)
         GroupBlocks *gb = nj > 0 ? &blocks_of(s[0]) : nullptr;
         GroupLaunches &gl = gb ? gb->gl : own_gl;
-        try {
-            std::vector<PackMember> pm(static_cast<size_t>(count));
-            for (int k : in) {
-                pm[k].m = s[k]->m_loc, pm[k].n = s[k]->n_loc;
-                pm[k].x0 = start[k].x0 != nullptr, pm[k].y0 = start[k].y0 != nullptr, pm[k].result = true;
-            }
-            const GroupPackLayout L = group_pack_layout(pm.data(), count);
-            if (nj > 0) {
-                // ---- zeroing, bound codes, ctrl and the starts of the group, recorded: they run in front of the first evaluation
-                const double *dev = nullptr;
-                if (L.start_doubles > 0) {
-                    double *host = static_cast<double *>(gb->in.stage(sizeof(double) * L.start_doubles));
-                    for (int k : in) group_pack_start(L, k, pm[k], start[k].x0, start[k].y0, host);
-                    gb->in.send(sizeof(double) * L.start_doubles, st);
-                    ++rc.h2d;
-                    dev = static_cast<const double *>(gb->in.dev);  // (it outlives the start kernels: no wait between them and the loop)
-                }
-                for (int k : in) {
-                    Solver &m = *s[k];
-                    m.reset_iterates(&gl);
-                    m.init_iteration_state(&gl, start[k].sigma);
-                    if (pm[k].x0 || pm[k].y0) {
-                        m.invalidate_far();
-                        const PackSlot &p = L.slot[k];
-                        m.start_launch(pm[k].x0 && p.x0 != kPackAbsent ? dev + p.x0 : nullptr, pm[k].y0 && p.y0 != kPackAbsent ? dev + p.y0 : nullptr,
-                                       nullptr, nullptr, &gl);
-                    }
-                }
-                rc.launches += gl.recorded_launches();
-                gl.next_stage();  // (the evaluation's Rd / Rp overwrite the partials the start's finalize reads)
-            }
-            {
-                TimeBase tb{s, count};
-                for (int k = 0; k < count; ++k) s[k]->time_base = s[k]->data_since_run;
-                loop_many(s, count, out, gc, scope, joins, gl, grouped.data());
-            }
-            rc.loop_own = gc.own;
-            // ---- the solutions: the group's through one block, one copy and one wait
-            for (int k = 0; k < count; ++k)
-                if (!grouped[k]) s[k]->collect_solution(&out[k]);
-            if (nj > 0) {
-                if (gb->out_d.n < L.result_doubles) {
-                    gb->out_d.alloc(L.result_doubles);
-                    gb->out_h.alloc(L.result_doubles, false);
-                }
+        DropBlocksOnThrow drop{gb ? s[0] : nullptr};
+        std::vector<PackMember> pm(static_cast<size_t>(count));
+        for (int k : in) {
+            pm[k].m = s[k]->m_loc, pm[k].n = s[k]->n_loc;
+            pm[k].x0 = start[k].x0 != nullptr, pm[k].y0 = start[k].y0 != nullptr, pm[k].result = true;
+        }
+        const GroupPackLayout L = group_pack_layout(pm.data(), count);
+        if (nj > 0) {
+            // ---- the joiners' starts: pieces of the staging block after one copy
+            std::vector<MemberStart> staged(static_cast<size_t>(count));
+            if (L.start_doubles > 0) {
+                double *host = static_cast<double *>(gb->in.stage(sizeof(double) * L.start_doubles));
+                for (int k : in) group_pack_start(L, k, pm[k], start[k].x0, start[k].y0, host);
+                gb->in.send(sizeof(double) * L.start_doubles, st);
+                ++rc.h2d;
+                const double *dev = static_cast<const double *>(gb->in.dev);  // (it outlives the start kernels: no wait between them and the loop)
                 for (int k : in) {
                     const PackSlot &p = L.slot[k];
-                    auto at = [&](size_t off) { return off == kPackAbsent ? nullptr : gb->out_d.p + off; };
-                    s[k]->solution_launch(at(p.x), at(p.y), at(p.z), &gl);
-                }
-                const long tables0 = gl.tables_sent();
-                rc.launches += gl.run(st);
-                rc.h2d += gl.tables_sent() - tables0;  // (the tables of what runs in front of the loop ride on the loop's first copy)
-                HIP_CHECK(hipMemcpyAsync(gb->out_h.p, gb->out_d.p, sizeof(double) * L.result_doubles, hipMemcpyDeviceToHost, st));
-                ++rc.d2h;
-                HIP_CHECK(hipStreamSynchronize(st));
-                ++rc.waits;
-                for (int k : in) {
-                    Solver &m = *s[k];
-                    HPRLP_results *o = &out[k];
-                    o->x = static_cast<double *>(std::malloc(sizeof(double) * std::max(m.n_loc, 1)));
-                    o->y = static_cast<double *>(std::malloc(sizeof(double) * std::max(m.m_loc, 1)));
-                    o->z = static_cast<double *>(std::malloc(sizeof(double) * std::max(m.n_loc, 1)));
-                    if (!o->x || !o->y || !o->z) throw std::runtime_error("host allocation of the solution failed");
-                    group_unpack_result(L, k, pm[k], gb->out_h.p, o->x, o->y, o->z);
-                    ++rc.served;
+                    staged[k].x0 = p.x0 != kPackAbsent ? dev + p.x0 : nullptr, staged[k].y0 = p.y0 != kPackAbsent ? dev + p.y0 : nullptr;
                 }
             }
-            for (int k = 0; k < count; ++k)
-                s[k]->set_transfer((start[k].x0 ? s[k]->n_loc : 0) + static_cast<size_t>(start[k].y0 ? s[k]->m_loc : 0),
-                                   2 * static_cast<size_t>(s[k]->n_loc) + s[k]->m_loc, false);
-        } catch (...) {
-            if (gb) s[0]->group_blocks.reset();  // (whatever was recorded goes with it)
-            throw;
+            record_starts(s, in, start, staged.data(), gl, rc);
+        }
+        resolve_loop(s, count, out, gc, scope, joins, gl, grouped.data());
+        rc.loop_own = gc.own;
+        // ---- the solutions: a member's own collect_solution, the group's through one block, one copy and one wait
+        for (int k = 0; k < count; ++k)
+            if (!grouped[k]) s[k]->collect_solution(&out[k]);
+        if (nj > 0) {
+            if (gb->out_d.n < L.result_doubles) {
+                gb->out_d.alloc(L.result_doubles);
+                gb->out_h.alloc(L.result_doubles, false);
+            }
+            for (int k : in) {
+                const PackSlot &p = L.slot[k];
+                auto at = [&](size_t off) { return off == kPackAbsent ? nullptr : gb->out_d.p + off; };
+                s[k]->solution_launch(at(p.x), at(p.y), at(p.z), &gl);
+            }
+            const long tables0 = gl.tables_sent();
+            rc.launches += gl.run(st);
+            rc.h2d += gl.tables_sent() - tables0;  // (the tables of what runs in front of the loop ride on the loop's first copy)
+            HIP_CHECK(hipMemcpyAsync(gb->out_h.p, gb->out_d.p, sizeof(double) * L.result_doubles, hipMemcpyDeviceToHost, st));
+            ++rc.d2h;
+            HIP_CHECK(hipStreamSynchronize(st));
+            ++rc.waits;
+            for (int k : in) {
+                Solver &m = *s[k];
+                HPRLP_results *o = &out[k];
+                o->x = static_cast<double *>(std::malloc(sizeof(double) * std::max(m.n_loc, 1)));
+                o->y = static_cast<double *>(std::malloc(sizeof(double) * std::max(m.m_loc, 1)));
+                o->z = static_cast<double *>(std::malloc(sizeof(double) * std::max(m.n_loc, 1)));
+                if (!o->x || !o->y || !o->z) throw std::runtime_error("host allocation of the solution failed");
+                group_unpack_result(L, k, pm[k], gb->out_h.p, o->x, o->y, o->z);
+                ++rc.served;
+            }
+        }
+        for (int k = 0; k < count; ++k)
+            s[k]->set_transfer((start[k].x0 ? s[k]->n_loc : 0) + static_cast<size_t>(start[k].y0 ? s[k]->m_loc : 0),
+                               2 * static_cast<size_t>(s[k]->n_loc) + s[k]->m_loc, false);
+    }
+    if (counts) *counts = rc;
+}
+
+// The members that go their own way run Solver::resolve_device from start to solution BEFORE the loop; only the joiners are
+// looped, as a sub-list whose results are copied back, and their solutions are stored straight into the caller's buffers.
+void resolve_many_device(Solver **s, int count, const MemberStart *start, const MemberOut *dst, hipStream_t caller, HPRLP_results *out,
+                         ResolveCounts *counts, DeviceCounts *dcounts) {
+    const char *who = "hprlp_solver_resolve_many_device";
+    DeviceCounts unused;
+    DeviceCounts &dc = dcounts ? *dcounts : unused;
+    std::vector<MemberStart> cold;
+    if (!start) {
+        cold.resize(static_cast<size_t>(count));
+        start = cold.data();
+    }
+    std::vector<MemberOut> none;
+    if (!dst) {
+        none.resize(static_cast<size_t>(count));
+        dst = none.data();
+    }
+    bool warm = false;
+    for (int k = 0; k < count; ++k) warm = warm || start[k].x0 || start[k].y0;
+    PointerChecks pass(s[0]->prm.device_number, who, dc);
+    for (int k = 0; k < count; ++k) {
+        const size_t m = static_cast<size_t>(s[k]->m_loc), n = static_cast<size_t>(s[k]->n_loc);
+        pass(k, start[k].x0, n, "x0"); pass(k, start[k].y0, m, "y0");
+        pass(k, dst[k].x, n, "x"); pass(k, dst[k].y, m, "y"); pass(k, dst[k].z, n, "z");
+    }
+    ResolveCounts rc;
+    GroupCounts gc;
+    {
+        GroupScope scope(s, count);
+        const hipStream_t st = scope.group;
+        std::vector<char> grouped;
+        const std::vector<int> in = resolve_joiners(s, count, grouped);
+        const int nj = static_cast<int>(in.size());
+        GroupBlocks &gb = blocks_of(s[0]);
+        GroupLaunches &gl = gb.gl;
+        DropBlocksOnThrow drop{s[0]};
+        wait_for_caller(gb, caller, st);  // (the outputs too: what the caller's stream still does with them comes first)
+        if (warm) {
+            // ---- the check: the starts of ALL members where they lie, one launch, one copy of the flag words, one wait
+            const unsigned long long *flags = check_stage(gb, static_cast<size_t>(count), st, rc, &dc, [&](GroupLaunches &chk, unsigned long long *w) {
+                for (int k = 0; k < count; ++k)
+                    chk.data_check(DataCheckArgs{{start[k].x0, start[k].y0, nullptr, nullptr, nullptr}, {s[k]->n_loc, s[k]->m_loc, 0, 0, 0}, 1}, w + k);
+            });
+            for (int k = 0; k < count; ++k) throw_if_flagged(flags[k], kStartNames, member(who, k) + ": warm start", "is not finite");
+        }
+        // -- from here on the call goes through
+        // ---- the members that go their own way: Solver::resolve_device, start to solution
+        for (int k = 0; k < count; ++k) {
+            if (grouped[k]) continue;
+            const MemberStart &b = start[k];
+            s[k]->resolve_device(b.sigma, b.x0, b.y0, caller, dst[k].x, dst[k].y, dst[k].z, &out[k]);
+            ++rc.own, ++dc.own;
+            // (nominal, many.h: ResolveCounts -- what Solver::resolve_device issues for a member without a locality ordering)
+            rc.memsets += 17, rc.waits += 1;                                                         // reset_iterates
+            rc.launches += (s[k]->hook_no_bound_codes ? 0 : 2) + 1 + (b.sigma > 0.0 ? 1 : 0);         // bound codes, ctrl, the override
+            if (b.x0 || b.y0) rc.memsets += 1, rc.launches += 1 + 4, rc.d2h += 1, rc.waits += 2;    // the check, the start
+            rc.launches += dst[k].x || dst[k].y || dst[k].z ? 1 : 0, rc.waits += 1;                  // the solution, the final wait
+        }
+        if (nj > 0) {
+            record_starts(s, in, start, start, gl, rc);  // (the starts are read in the caller's buffers)
+            // ---- the lock-step loop over the group's members
+            std::vector<Solver *> js(static_cast<size_t>(nj));
+            std::vector<HPRLP_results> jout(static_cast<size_t>(nj));
+            for (int j = 0; j < nj; ++j) js[j] = s[in[j]], jout[j] = out[in[j]];
+            const std::vector<char> all(static_cast<size_t>(nj), 1);
+            resolve_loop(js.data(), nj, jout.data(), gc, scope, all, gl, all.data());
+            rc.loop_own = gc.own;
+            // ---- the solutions: straight into the callers' buffers (an output that is not wanted: the member's own scratch,
+            // where its collect_solution puts it), one launch, one wait, no copy
+            for (int j = 0; j < nj; ++j) {
+                const int k = in[j];
+                Solver &m = *s[k];
+                out[k] = jout[j];
+                out[k].x = out[k].y = out[k].z = nullptr;
+                const MemberOut &o = dst[k];
+                if (o.x || o.y || o.z) m.solution_launch(o.x ? o.x : m.sn1.p, o.y ? o.y : m.sm1.p, o.z ? o.z : m.gsn.p + m.col_off, &gl);
+            }
+            const long tables0 = gl.tables_sent();
+            rc.launches += gl.run(st);
+            rc.h2d += gl.tables_sent() - tables0;  // (the tables of what runs in front of the loop ride on the loop's first copy)
+            HIP_CHECK(hipStreamSynchronize(st));
+            ++rc.waits;
+            for (int k : in) {
+                s[k]->set_transfer(0, 0, true);
+                ++rc.served, ++dc.served;
+            }
         }
     }
     if (counts) *counts = rc;
 }
 
 // ------------------------------------------------------------------------------------------------
-// group matrix values (DESIGN.md "Many small LPs", group matrix values): Solver::set_matrix_values of every member of a group.
-// The rule is the group launches': the bodies of values.hip's kernels run as workgroup lb of the member's own grid, the zeroing
-// is reset_iterates' fills, the scaling is scale_many's walk, so every stored number is the member's own.
+// set_matrix_values_many / set_matrix_values_many_device
 // ------------------------------------------------------------------------------------------------
 namespace {
 
-// The apply of set_matrix_values_many for the members `in`: scatter, gather and zeroing in one stage, Solver::scale()'s pieces
-// behind them, one recorder; then what Solver::values_apply and set_matrix_values leave, with the group call's wall times.
-// src[k]: where member k's values and vectors are read on the device -- pieces of the staging block, or the caller's own buffers
-// (the device entries); data[k]: nnz and the host pointer obj_constant.
-void values_apply_group(Solver **s, const std::vector<int> &in, const MemberValues *data, const MemberValues *src, const std::vector<char> &built,
+// The apply for the members `in`: scatter, gather and zeroing in one stage, Solver::scale()'s pieces behind them, one recorder;
+// then what Solver::values_apply and set_matrix_values leave, with the group call's wall times.  at[k]: where member k's values
+// and vectors are read on the device -- pieces of the staging block, or the caller's own buffers; data[k]: nnz and the host
+// pointer obj_constant.
+void values_apply_group(Solver **s, const std::vector<int> &in, const MemberValues *data, const MemberValues *at, const std::vector<char> &built,
                         double maps_seconds, double upload_seconds, GroupBlocks &gb, hipStream_t st, ValuesCounts &vc, clock_type::time_point t0,
-                        bool device_entry) {
+                        const Source &src) {
     const auto t_k = time_now();
     GroupLaunches &gl = gb.tables;
     const long tables0 = gl.tables_sent();
     for (int k : in) {
         Solver &m = *s[k];
-        gl.values_in(data[k].nnz, src[k].val, m.map_A.p, m.map_AT.p, m.A.val.p, m.AT.val.p);
-        gl.vectors_in(VectorsInArgs{m.m_loc, m.n_loc, src[k].AL, src[k].AU, src[k].l, src[k].u, src[k].c, m.perm_r_dev.p, m.perm_c_dev.p, m.AL.p,
+        gl.values_in(data[k].nnz, at[k].val, m.map_A.p, m.map_AT.p, m.A.val.p, m.AT.val.p);
+        gl.vectors_in(VectorsInArgs{m.m_loc, m.n_loc, at[k].AL, at[k].AU, at[k].l, at[k].u, at[k].c, m.perm_r_dev.p, m.perm_c_dev.p, m.AL.p,
                                     m.AU.p, m.l.p, m.u.p, m.c.p});
         if (data[k].obj_constant) m.obj_constant = *data[k].obj_constant;
         m.reset_iterates(&gl);
@@ -849,16 +1114,15 @@ void values_apply_group(Solver **s, const std::vector<int> &in, const MemberValu
         m.matrix_time[4] = wall;
         ++m.matrix_calls;
         m.data_since_run += wall;
-        if (device_entry) m.set_transfer(0, 0, true);
+        // (the words that travelled: none for a device entry, values and vectors for a host entry)
+        if (src.device()) m.set_transfer(0, 0, true);
         else m.set_transfer(static_cast<size_t>(data[k].nnz) + 2 * static_cast<size_t>(m.m) + 3 * static_cast<size_t>(m.n), 0, false);
     }
 }
 
-}  // namespace
-
-void set_matrix_values_many(Solver **s, int count, const MemberValues *data, ValuesCounts *counts) {
-    const char *who = "hprlp_solver_set_matrix_values_many";
-    // ---- the host checks of all members, before the first upload (Solver::set_matrix_values' rules and messages)
+void set_matrix_values_group(Solver **s, int count, const MemberValues *data, const Source &src, ValuesCounts *counts) {
+    const char *who = src.who;
+    // ---- the host rules of all members, before the first upload (Solver::set_matrix_values' rules and messages)
     std::vector<char> gave(static_cast<size_t>(count), 0);
     int ngave = 0;
     for (int k = 0; k < count; ++k) {
@@ -869,47 +1133,65 @@ void set_matrix_values_many(Solver **s, int count, const MemberValues *data, Val
         if (d.nnz != static_cast<long>(s[k]->A.view.nnz))
             throw std::runtime_error(member(who, k) + ": nnz is " + std::to_string(d.nnz) + ", the model has " + std::to_string(s[k]->A.view.nnz) +
                                      " entries (the pattern cannot change)");
-        auto no_nan = [&](const double *v, long len, const char *what) {
-            for (long i = 0; i < len; ++i)
-                if (std::isnan(v[i])) throw std::runtime_error(member(who, k) + ": " + what + "[" + std::to_string(i) + "] is NaN");
-        };
-        no_nan(d.c, s[k]->n, "c"); no_nan(d.AL, s[k]->m, "AL"); no_nan(d.AU, s[k]->m, "AU"); no_nan(d.l, s[k]->n, "l"); no_nan(d.u, s[k]->n, "u");
+        if (!src.device()) host_no_nan(who, k, *s[k], d.c, d.AL, d.AU, d.l, d.u);  // (host memory only)
         if (d.obj_constant && std::isnan(*d.obj_constant)) throw std::runtime_error(member(who, k) + ": obj_constant is NaN");
         gave[k] = 1;
         ++ngave;
+    }
+    double ptr_seconds = 0.0;
+    if (src.device()) {  // every pointer of every member that gave: still nothing launched or written
+        const auto t_ptr = time_now();
+        PointerChecks pass(s[0]->prm.device_number, who, *src.dc);
+        for (int k = 0; k < count; ++k) {
+            if (!gave[k]) continue;
+            const MemberValues &d = data[k];
+            pass(k, d.val, static_cast<size_t>(d.nnz), "val");
+            pass.data_vectors(k, static_cast<size_t>(s[k]->m), static_cast<size_t>(s[k]->n), d.c, d.AL, d.AU, d.l, d.u);
+        }
+        ptr_seconds = time_since(t_ptr);
     }
     ValuesCounts vc;
     const auto t0 = time_now();
     GroupScope scope(s, count);
     const hipStream_t st = scope.group;
     const bool fused_norms = env_get("HPRLP_NO_FUSED_NORMS") == nullptr;  // (scale_many's condition)
-    std::vector<int> in;  // the members of the group launches
-    for (int k = 0; k < count; ++k)
-        if (gave[k] && fused_norms && s[k]->joins_group_resolve() && s[k]->m_loc > 0 && s[k]->n_loc > 0) in.push_back(k);
-    if (in.size() < 2) in.clear();  // (a group of one issues the member's own launches)
-    std::vector<char> joins(static_cast<size_t>(count), 0);
-    for (int k : in) joins[k] = 1;
-    const int nj = static_cast<int>(in.size());
+    std::vector<char> wanted(static_cast<size_t>(count)), joins;
+    for (int k = 0; k < count; ++k) wanted[k] = gave[k] && fused_norms && s[k]->joins_group_resolve() && s[k]->m_loc > 0 && s[k]->n_loc > 0;
+    const std::vector<int> in = joiners(wanted, joins);
+    // The scatter of a joining member (no value map for A) loads the values as 16-byte pairs.  A host entry's come from the staging
+    // block, where every vector starts on a multiple of kPackAlign = 32 doubles of a pinned block's copy; a device entry's come from
+    // the caller's buffer: an 8-byte aligned `val` is the single entries' rule, the pairs need 16.  (The stores go to A_val + 2 t and
+    // AT_val + 2 t: hipMalloc's, or pieces of the group's arena, 256-byte aligned both.)
+    if (src.device())
+        for (int k : in)
+            if (reinterpret_cast<uintptr_t>(data[k].val) % 16)
+                throw std::runtime_error(member(who, k) + ": val is not aligned to 16 bytes (the group's scatter loads the values in pairs)");
     // One member alone is checked by its own call before it writes anything, and nobody else is written: no block.
     GroupBlocks *gb = ngave >= 2 ? &blocks_of(s[0]) : nullptr;
-    try {
-        // ---- value maps: a member's own construction, once (joining members have no ordering: map_A stays null, map_AT comes
-        // from the host transpose); the members on their own way build theirs inside their own call
-        const auto t_maps = time_now();
-        std::vector<char> built(static_cast<size_t>(count), 0);
-        for (int k : in) {
-            if (s[k]->have_maps) continue;
-            s[k]->build_value_maps();
-            built[k] = 1;
-            ++vc.maps;
-        }
-        const double maps_seconds = time_since(t_maps);
-        // ---- staging: [val | AL | AU | l | u | c] of the joining members and the values of the others in ONE pinned block, one copy
-        const auto t_up = time_now();
-        std::vector<PackMember> pm(static_cast<size_t>(count));
-        GroupPackLayout L;
+    DropBlocksOnThrow drop{gb ? s[0] : nullptr};
+    // ---- value maps: a member's own construction, once (joining members have no ordering: map_A stays null, map_AT comes from
+    // the host transpose); the members on their own way build theirs inside their own call
+    const auto t_maps = time_now();
+    std::vector<char> built(static_cast<size_t>(count), 0);
+    for (int k : in) {
+        if (s[k]->have_maps) continue;
+        s[k]->build_value_maps();
+        built[k] = 1;
+        ++vc.maps;
+    }
+    const double maps_seconds = time_since(t_maps);
+    const auto t_up = time_now();
+    std::vector<MemberValues> staged;  // a host entry: where the joiners' values and vectors lie in the staging block
+    if (gb) {
+        const size_t K = static_cast<size_t>(count);
         const double *dev = nullptr;
-        if (gb) {
+        GroupPackLayout L;
+        if (src.device()) {
+            wait_for_caller(*gb, src.caller, st);
+        } else {
+            // ---- a host entry's staging: [val | AL | AU | l | u | c] of the joining members and the values of the others in ONE
+            // pinned block, one copy
+            std::vector<PackMember> pm(K);
             for (int k = 0; k < count; ++k) {
                 if (!gave[k]) continue;
                 pm[k].m = s[k]->m_loc, pm[k].n = s[k]->n_loc, pm[k].nnz = data[k].nnz;
@@ -927,460 +1209,92 @@ void set_matrix_values_many(Solver **s, int count, const MemberValues *data, Val
                 ++vc.h2d;
             }
             dev = static_cast<const double *>(gb->in.dev);
-            // ---- the check: one flag word per member (all bits set: clean), one launch over everybody's values, one copy, one wait
-            if (gb->flags.n < static_cast<size_t>(count)) {
-                gb->flags.alloc(static_cast<size_t>(count));
-                gb->flags_h.alloc(static_cast<size_t>(count));
+            auto at = [&](size_t off) { return off == kPackAbsent ? nullptr : dev + off; };
+            staged.resize(K);
+            for (int k : in) {
+                const PackSlot &p = L.slot[k];
+                staged[k].val = at(p.val), staged[k].c = at(p.c), staged[k].AL = at(p.AL), staged[k].AU = at(p.AU), staged[k].l = at(p.l),
+                staged[k].u = at(p.u);
             }
-            HIP_CHECK(hipMemsetAsync(gb->flags.p, 0xff, sizeof(unsigned long long) * count, st));
-            ++vc.memsets;
-            GroupLaunches &chk = gb->gl;
-            const long tables0 = chk.tables_sent();
-            for (int k = 0; k < count; ++k)
-                if (gave[k] && L.slot[k].val != kPackAbsent) chk.values_check(dev + L.slot[k].val, data[k].nnz, gb->flags.p + k);
-            vc.launches += chk.run(st);
-            vc.h2d += chk.tables_sent() - tables0;
-            HIP_CHECK(hipMemcpyAsync(gb->flags_h.p, gb->flags.p, sizeof(unsigned long long) * count, hipMemcpyDeviceToHost, st));
-            ++vc.d2h;
-            HIP_CHECK(hipStreamSynchronize(st));
-            ++vc.waits;
-            for (int k = 0; k < count; ++k)  // (the lowest member, its smallest position)
-                if (gave[k] && gb->flags_h[k] != kValuesAllFinite)
-                    throw std::runtime_error(member(who, k) + ": val[" + std::to_string(gb->flags_h[k]) + "] is not finite");
         }
-        const double upload_seconds = time_since(t_up);
-        // -- from here on the call goes through
-        // ---- the members that go their own way: Solver::set_matrix_values (its own upload and check included)
-        for (int k = 0; k < count; ++k) {
-            if (!gave[k] || joins[k]) continue;
-            Solver &m = *s[k];
-            const MemberValues &d = data[k];
-            const bool had_maps = m.have_maps;
-            const long f0 = m.fetches, l0 = scaling_launch_count();
-            try {
-                m.set_matrix_values(d.val, d.nnz, d.c, d.obj_constant, d.AL, d.AU, d.l, d.u);
-            } catch (const std::exception &e) {  // (a member alone in the call: its own check's refusal, named as the group's)
-                const std::string msg = e.what(), own = "set_matrix_values: ";
-                throw std::runtime_error(member(who, k) + ": " + (msg.compare(0, own.size(), own) == 0 ? msg.substr(own.size()) : msg));
+        // ---- the check, in ONE stage: everybody's values (a host entry: in the staging block) into one flag word per member, all
+        // bits set: clean; a device entry's vectors too, where they lie, into a second word per member (the vectors' at k, the
+        // values' at count + k).  One memset, one copy, one wait.
+        const size_t val_at = src.device() ? K : 0;
+        const unsigned long long *flags = check_stage(*gb, val_at + K, st, vc, src.dc, [&](GroupLaunches &chk, unsigned long long *w) {
+            for (int k = 0; k < count; ++k) {
+                if (!gave[k]) continue;
+                const MemberValues &d = data[k];
+                if (src.device()) {
+                    chk.data_check(nan_check(s[k]->m, s[k]->n, d.c, d.AL, d.AU, d.l, d.u), w + k);
+                    chk.values_check(d.val, d.nnz, w + val_at + k);
+                } else if (L.slot[k].val != kPackAbsent) {
+                    chk.values_check(dev + L.slot[k].val, d.nnz, w + k);
+                }
             }
-            ++vc.own;
-            if (!had_maps) ++vc.maps;
+        });
+        // (a vector's NaN of any member wins: a host entry's host checks of the vectors have come first)
+        if (src.device())
+            for (int k = 0; k < count; ++k)
+                if (gave[k]) throw_if_flagged(flags[k], kDataNames, member(who, k), "is NaN");
+        for (int k = 0; k < count; ++k)  // (the lowest member, its smallest position)
+            if (gave[k] && flags[val_at + k] != kValuesAllFinite)
+                throw std::runtime_error(member(who, k) + ": val[" + std::to_string(flags[val_at + k]) + "] is not finite");
+    }
+    const double upload_seconds = ptr_seconds + time_since(t_up);  // (a device entry's lookups count as its upload)
+    // -- from here on the call goes through
+    // ---- the members that go their own way: the single entry of the source's kind (its own upload and checks included)
+    for (int k = 0; k < count; ++k) {
+        if (!gave[k] || joins[k]) continue;
+        Solver &m = *s[k];
+        const MemberValues &d = data[k];
+        const bool had_maps = m.have_maps;
+        const long f0 = m.fetches, l0 = scaling_launch_count();
+        try {
+            if (src.device()) m.set_matrix_values_device(d.val, d.nnz, d.c, d.obj_constant, d.AL, d.AU, d.l, d.u, src.caller);
+            else m.set_matrix_values(d.val, d.nnz, d.c, d.obj_constant, d.AL, d.AU, d.l, d.u);
+        } catch (const std::exception &e) {  // (a member alone in the call: its own check's refusal, named as the group's)
+            std::string msg = e.what();
+            for (const char *own : {"set_matrix_values: ", "set_matrix_values_device: "})
+                if (msg.compare(0, std::strlen(own), own) == 0) msg = msg.substr(std::strlen(own));
+            throw std::runtime_error(member(who, k) + ": " + msg);
+        }
+        ++vc.own;
+        if (!had_maps) ++vc.maps;
+        vc.memsets += 1 + 17;
+        vc.d2h += 1 + (m.fetches - f0);
+        if (src.device()) {
+            ++src.dc->own;
+            // the flags' memset, the two checks, scatter, gather, the flags' copy and wait; reset_iterates' seventeen memsets and
+            // wait; scale(): its launches, its scalar fetches, its final wait; the wait that ends the call
+            vc.launches += 4 + (scaling_launch_count() - l0);
+            vc.waits += 1 + 1 + (m.fetches - f0) + 1 + 1;
+        } else {
             // its staging in one copy (six from the allocator cache's block size on), the flag's memset, check, scatter, gather, the
             // flag's copy and wait; reset_iterates' seventeen memsets and wait; scale(): its launches, its scalar fetches, its final wait
             const size_t words = static_cast<size_t>(d.nnz) + 2 * static_cast<size_t>(m.m) + 3 * static_cast<size_t>(m.n);
             vc.h2d += words * sizeof(double) < kDeviceCacheMinBytes ? 1 : 6;
-            vc.memsets += 1 + 17;
             vc.launches += 3 + (scaling_launch_count() - l0);
-            vc.d2h += 1 + (m.fetches - f0);
             vc.waits += 1 + 1 + (m.fetches - f0) + 1;
         }
-        if (nj > 0) {
-            std::vector<MemberValues> src(static_cast<size_t>(count));
-            auto at = [&](size_t off) { return off == kPackAbsent ? nullptr : dev + off; };
-            for (int k : in) {
-                const PackSlot &p = L.slot[k];
-                src[k].val = at(p.val), src[k].c = at(p.c), src[k].AL = at(p.AL), src[k].AU = at(p.AU), src[k].l = at(p.l), src[k].u = at(p.u);
-            }
-            // The scatter stores 16 bytes at A_val + 2 t and AT_val + 2 t, and with map_A null it loads 16 bytes at the
-            // staged values + 2 t: the value arrays are hipMalloc's or pieces of the group's arena (256-byte aligned both),
-            // and every vector of the staging block starts on a multiple of kPackAlign = 32 doubles of a pinned block's copy.
-            values_apply_group(s, in, data, src.data(), built, maps_seconds, upload_seconds, *gb, st, vc, t0, false);
-        }
-    } catch (...) {
-        if (gb) s[0]->group_blocks.reset();  // (whatever was recorded goes with it)
-        throw;
+    }
+    if (!in.empty()) {
+        values_apply_group(s, in, data, src.device() ? data : staged.data(), built, maps_seconds, upload_seconds, *gb, st, vc, t0, src);
+        if (src.device()) src.dc->served += static_cast<long>(in.size());
     }
     if (counts) *counts = vc;
 }
-
-// ------------------------------------------------------------------------------------------------
-// group device re-solve (DESIGN.md "Many small LPs", group device re-solve): the three group entries above with every vector in
-// the caller's device memory and the solutions wanted there.  The mechanism is the single device entries': a group task's source
-// is the caller's buffer where the host entries pass a piece of the staging block, and the solution kernel stores into the
-// caller's buffers (a joining member has no locality ordering: nothing to scatter).  What is new is the check: all pointers of
-// all members are looked up before anything is launched, and ONE launch (GroupLaunches::data_check) checks the vectors of all
-// members where they lie, one flag word per member, one copy, one wait -- before anything a solver reads is written.
-// ------------------------------------------------------------------------------------------------
-namespace {
-
-// The pointer checks of one call.  A pointer that lies, with its length, inside a range the runtime has already reported in this
-// call is device memory of the group's device with room for it: no second lookup (a group cut from a few packed tensors costs a
-// few lookups whatever its size).  Everything else goes through check_device_pointer, whose words the refusal carries.
-class PointerChecks {
-  public:
-    PointerChecks(int device, const char *who, DeviceCounts &dc) : device_(device), who_(who), dc_(dc) {}
-    void operator()(int k, const void *p, size_t count, const char *name) {
-        if (!p) return;  // (not given / not wanted)
-        ++dc_.pointers;
-        const char *b = static_cast<const char *>(p), *e = b + count * sizeof(double);
-        if (reinterpret_cast<uintptr_t>(p) % sizeof(double) == 0)
-            for (const DeviceRange &r : seen_)
-                if (b >= r.base && e <= r.base + r.bytes) return;
-        ++dc_.lookups;
-        DeviceRange r;
-        check_device_pointer(p, count, device_, name, member(who_, k).c_str(), &r);
-        if (r.bytes > 0) seen_.push_back(r);
-    }
-
-  private:
-    int device_;
-    const char *who_;
-    DeviceCounts &dc_;
-    std::vector<DeviceRange> seen_;
-};
-
-// The group's stream waits for what the caller's stream has been given so far (one event per call).
-void wait_for_caller(GroupBlocks &gb, hipStream_t caller, hipStream_t st) {
-    if (!gb.inputs_ready) HIP_CHECK(hipEventCreateWithFlags(&gb.inputs_ready, hipEventDisableTiming));
-    HIP_CHECK(hipEventRecord(gb.inputs_ready, caller));
-    HIP_CHECK(hipStreamWaitEvent(st, gb.inputs_ready, 0));
-}
-
-// `words` flag words of all ones (kDataCheckClean, kValuesAllFinite) by ONE memset; fetch_flags: one copy, one wait
-unsigned long long *cleared_flags(GroupBlocks &gb, size_t words, hipStream_t st) {
-    if (gb.flags.n < words) {
-        gb.flags.alloc(words);
-        gb.flags_h.alloc(words);
-    }
-    HIP_CHECK(hipMemsetAsync(gb.flags.p, 0xff, sizeof(unsigned long long) * words, st));
-    return gb.flags.p;
-}
-void fetch_flags(GroupBlocks &gb, size_t words, hipStream_t st, DeviceCounts &dc) {
-    HIP_CHECK(hipMemcpyAsync(gb.flags_h.p, gb.flags.p, sizeof(unsigned long long) * words, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    dc.flags += static_cast<long>(words);
-    ++dc.waits_before_write;
-}
-// k_data_check's word of member k as the host group entries' message
-void throw_if_flagged(unsigned long long word, const char *const names[kDataCheckVecs], const std::string &who, const char *what) {
-    if (word == kDataCheckClean) return;
-    const int v = static_cast<int>(word >> kDataCheckShift);
-    const unsigned long long i = word & ((1ULL << kDataCheckShift) - 1);
-    throw std::runtime_error(who + ": " + (v < kDataCheckVecs ? names[v] : "?") + "[" + std::to_string(i) + "] " + what);
-}
-const char *const kDataNames[kDataCheckVecs] = {"c", "AL", "AU", "l", "u"};  // (the host entries' order of vectors)
-const char *const kStartNames[kDataCheckVecs] = {"x0", "y0", "", "", ""};
 
 }  // namespace
 
-void set_data_many_device(Solver **s, int count, const MemberData *data, hipStream_t caller, ResolveCounts *counts, DeviceCounts *dcounts) {
-    const char *who = "hprlp_solver_set_data_many_device";
-    DeviceCounts unused;
-    DeviceCounts &dc = dcounts ? *dcounts : unused;
-    // ---- the host rules of all members, then every pointer of every member: nothing has been launched or written
-    bool any = false;
-    for (int k = 0; k < count; ++k) {
-        const MemberData &d = data[k];
-        const bool bounds = d.AL || d.AU || d.l || d.u;
-        if (bounds && !(d.AL && d.AU && d.l && d.u))
-            throw std::runtime_error(member(who, k) + ": AL, AU, l and u are given together or not at all (b_scale couples them)");
-        if (d.obj_constant && std::isnan(*d.obj_constant)) throw std::runtime_error(member(who, k) + ": obj_constant is NaN");
-        any = any || d.c || bounds;
-    }
-    PointerChecks pass(s[0]->prm.device_number, who, dc);
-    for (int k = 0; k < count; ++k) {
-        const MemberData &d = data[k];
-        const size_t m = static_cast<size_t>(s[k]->m_loc), n = static_cast<size_t>(s[k]->n_loc);
-        pass(k, d.c, n, "c"); pass(k, d.AL, m, "AL"); pass(k, d.AU, m, "AU"); pass(k, d.l, n, "l"); pass(k, d.u, n, "u");
-    }
-    ResolveCounts rc;
-    const auto t0 = time_now();
-    GroupScope scope(s, count);
-    const hipStream_t st = scope.group;
-    std::vector<int> in;  // the members of the group launches
-    std::vector<PackMember> pm(static_cast<size_t>(count));
-    for (int k = 0; k < count; ++k) {
-        pm[k].c = data[k].c != nullptr, pm[k].bounds = data[k].AL != nullptr;
-        if ((pm[k].c || pm[k].bounds) && s[k]->joins_group_resolve()) in.push_back(k);
-    }
-    if (in.size() < 2) in.clear();  // (a group of one issues the member's own launches)
-    std::vector<char> joins(static_cast<size_t>(count), 0);
-    for (int k : in) joins[k] = 1;
-    GroupBlocks &gb = blocks_of(s[0]);
-    try {
-        if (any) {
-            // ---- the check: the vectors of ALL members where they lie, one launch, one copy of the flag words, one wait
-            wait_for_caller(gb, caller, st);
-            unsigned long long *flags = cleared_flags(gb, static_cast<size_t>(count), st);
-            ++rc.memsets;
-            GroupLaunches &chk = gb.gl;
-            const long tables0 = chk.tables_sent();
-            for (int k = 0; k < count; ++k) {
-                const MemberData &d = data[k];
-                const int m = s[k]->m_loc, n = s[k]->n_loc;
-                chk.data_check(DataCheckArgs{{d.c, d.AL, d.AU, d.l, d.u}, {n, m, m, n, n}, 0}, flags + k);
-            }
-            const int launches = chk.run(st);
-            rc.launches += launches, dc.check_launches += launches;
-            rc.h2d += chk.tables_sent() - tables0;
-            fetch_flags(gb, static_cast<size_t>(count), st, dc);
-            ++rc.d2h, ++rc.waits;
-            for (int k = 0; k < count; ++k) throw_if_flagged(gb.flags_h[k], kDataNames, member(who, k), "is NaN");  // (the lowest member first)
-        }
-        // -- from here on the call goes through
-        for (int k = 0; k < count; ++k) {
-            const MemberData &d = data[k];
-            if (joins[k] || !(d.c || d.obj_constant || d.AL)) continue;  // (nothing given: the member keeps its bits)
-            s[k]->set_data_device(d.c, d.obj_constant, d.AL, d.AU, d.l, d.u, caller);
-            if (!(d.c || d.AL)) continue;  // (obj_constant alone is a host assignment)
-            ++rc.own, ++dc.own;
-            // Solver::set_data_device, nominal (many.h: ResolveCounts): the flag's memset, its check, two passes and two finalizes;
-            // the flag's copy and the scalars', a wait each
-            rc.memsets += 1, rc.launches += 5, rc.d2h += 2, rc.waits += 2;
-        }
-        if (!in.empty()) {
-            data_passes(s, in, pm, data, data, gb, st, rc, t0, true);
-            dc.served += static_cast<long>(in.size());
-        }
-    } catch (...) {
-        s[0]->group_blocks.reset();  // (whatever was recorded goes with it)
-        throw;
-    }
-    if (counts) *counts = rc;
+void set_matrix_values_many(Solver **s, int count, const MemberValues *data, ValuesCounts *counts) {
+    set_matrix_values_group(s, count, data, Source{"hprlp_solver_set_matrix_values_many"}, counts);
 }
-
-void resolve_many_device(Solver **s, int count, const MemberStart *start, const MemberOut *dst, hipStream_t caller, HPRLP_results *out,
-                         ResolveCounts *counts, DeviceCounts *dcounts) {
-    const char *who = "hprlp_solver_resolve_many_device";
-    DeviceCounts unused;
-    DeviceCounts &dc = dcounts ? *dcounts : unused;
-    std::vector<MemberStart> cold;
-    if (!start) {
-        cold.resize(static_cast<size_t>(count));
-        start = cold.data();
-    }
-    std::vector<MemberOut> none;
-    if (!dst) {
-        none.resize(static_cast<size_t>(count));
-        dst = none.data();
-    }
-    bool warm = false;
-    for (int k = 0; k < count; ++k) {
-        if (std::isnan(start[k].sigma)) throw std::runtime_error(member(who, k) + ": sigma is NaN");
-        warm = warm || start[k].x0 || start[k].y0;
-    }
-    PointerChecks pass(s[0]->prm.device_number, who, dc);
-    for (int k = 0; k < count; ++k) {
-        const size_t m = static_cast<size_t>(s[k]->m_loc), n = static_cast<size_t>(s[k]->n_loc);
-        pass(k, start[k].x0, n, "x0"); pass(k, start[k].y0, m, "y0");
-        pass(k, dst[k].x, n, "x"); pass(k, dst[k].y, m, "y"); pass(k, dst[k].z, n, "z");
-    }
-    ResolveCounts rc;
-    GroupCounts gc;
-    {
-        GroupScope scope(s, count);
-        const hipStream_t st = scope.group;
-        std::vector<int> in;
-        for (int k = 0; k < count; ++k)
-            if (s[k]->joins_group_resolve()) in.push_back(k);
-        if (in.size() < 2) in.clear();  // (a group of one issues the member's own launches)
-        std::vector<char> grouped(static_cast<size_t>(count), 0);
-        for (int k : in) grouped[k] = 1;
-        const int nj = static_cast<int>(in.size());
-        GroupBlocks &gb = blocks_of(s[0]);
-        GroupLaunches &gl = gb.gl;
-        try {
-            wait_for_caller(gb, caller, st);  // (the outputs too: what the caller's stream still does with them comes first)
-            if (warm) {
-                // ---- the check: the starts of ALL members where they lie, one launch, one copy of the flag words, one wait
-                unsigned long long *flags = cleared_flags(gb, static_cast<size_t>(count), st);
-                ++rc.memsets;
-                const long tables0 = gl.tables_sent();
-                for (int k = 0; k < count; ++k)
-                    gl.data_check(DataCheckArgs{{start[k].x0, start[k].y0, nullptr, nullptr, nullptr}, {s[k]->n_loc, s[k]->m_loc, 0, 0, 0}, 1}, flags + k);
-                const int launches = gl.run(st);
-                rc.launches += launches, dc.check_launches += launches;
-                rc.h2d += gl.tables_sent() - tables0;
-                fetch_flags(gb, static_cast<size_t>(count), st, dc);
-                ++rc.d2h, ++rc.waits;
-                for (int k = 0; k < count; ++k) throw_if_flagged(gb.flags_h[k], kStartNames, member(who, k) + ": warm start", "is not finite");
-            }
-            // -- from here on the call goes through
-            // ---- the members that go their own way: Solver::resolve_device, start to solution
-            for (int k = 0; k < count; ++k) {
-                if (grouped[k]) continue;
-                const MemberStart &b = start[k];
-                s[k]->resolve_device(b.sigma, b.x0, b.y0, caller, dst[k].x, dst[k].y, dst[k].z, &out[k]);
-                ++rc.own, ++dc.own;
-                // (nominal, many.h: ResolveCounts -- what Solver::resolve_device issues for a member without a locality ordering)
-                rc.memsets += 17, rc.waits += 1;                                                         // reset_iterates
-                rc.launches += (s[k]->hook_no_bound_codes ? 0 : 2) + 1 + (b.sigma > 0.0 ? 1 : 0);         // bound codes, ctrl, the override
-                if (b.x0 || b.y0) rc.memsets += 1, rc.launches += 1 + 4, rc.d2h += 1, rc.waits += 2;    // the check, the start
-                rc.launches += dst[k].x || dst[k].y || dst[k].z ? 1 : 0, rc.waits += 1;                  // the solution, the final wait
-            }
-            if (nj > 0) {
-                // ---- zeroing, bound codes, ctrl and the starts of the group, recorded: they run in front of the first evaluation
-                for (int k : in) {
-                    Solver &m = *s[k];
-                    m.reset_iterates(&gl);
-                    m.init_iteration_state(&gl, start[k].sigma);
-                    if (start[k].x0 || start[k].y0) {
-                        m.invalidate_far();
-                        m.start_launch(start[k].x0, start[k].y0, nullptr, nullptr, &gl);
-                    }
-                }
-                rc.launches += gl.recorded_launches();
-                gl.next_stage();  // (the evaluation's Rd / Rp overwrite the partials the start's finalize reads)
-                // ---- the lock-step loop over the group's members
-                std::vector<Solver *> js(static_cast<size_t>(nj));
-                std::vector<HPRLP_results> jout(static_cast<size_t>(nj));
-                for (int j = 0; j < nj; ++j) js[j] = s[in[j]], jout[j] = out[in[j]];
-                const std::vector<char> all(static_cast<size_t>(nj), 1);
-                {
-                    TimeBase tb{js.data(), nj};
-                    for (Solver *m : js) m->time_base = m->data_since_run;
-                    loop_many(js.data(), nj, jout.data(), gc, scope, all, gl, all.data());
-                }
-                rc.loop_own = gc.own;
-                // ---- the solutions: straight into the callers' buffers (an output that is not wanted: the member's own scratch,
-                // where its collect_solution puts it), one launch, one wait, no copy
-                for (int j = 0; j < nj; ++j) {
-                    const int k = in[j];
-                    Solver &m = *s[k];
-                    out[k] = jout[j];
-                    out[k].x = out[k].y = out[k].z = nullptr;
-                    const MemberOut &o = dst[k];
-                    if (o.x || o.y || o.z) m.solution_launch(o.x ? o.x : m.sn1.p, o.y ? o.y : m.sm1.p, o.z ? o.z : m.gsn.p + m.col_off, &gl);
-                }
-                const long tables0 = gl.tables_sent();
-                rc.launches += gl.run(st);
-                rc.h2d += gl.tables_sent() - tables0;  // (the tables of what runs in front of the loop ride on the loop's first copy)
-                HIP_CHECK(hipStreamSynchronize(st));
-                ++rc.waits;
-                for (int k : in) {
-                    s[k]->set_transfer(0, 0, true);
-                    ++rc.served, ++dc.served;
-                }
-            }
-        } catch (...) {
-            s[0]->group_blocks.reset();  // (whatever was recorded goes with it)
-            throw;
-        }
-    }
-    if (counts) *counts = rc;
-}
-
 void set_matrix_values_many_device(Solver **s, int count, const MemberValues *data, hipStream_t caller, ValuesCounts *counts,
                                    DeviceCounts *dcounts) {
-    const char *who = "hprlp_solver_set_matrix_values_many_device";
     DeviceCounts unused;
-    DeviceCounts &dc = dcounts ? *dcounts : unused;
-    // ---- the host rules of all members (Solver::set_matrix_values_device's, with its messages), then every pointer
-    std::vector<char> gave(static_cast<size_t>(count), 0);
-    int ngave = 0;
-    for (int k = 0; k < count; ++k) {
-        const MemberValues &d = data[k];
-        if (!(d.val || d.c || d.obj_constant || d.AL || d.AU || d.l || d.u)) continue;  // skipped: the member keeps every bit
-        if (!d.val || !d.c || !d.AL || !d.AU || !d.l || !d.u)
-            throw std::runtime_error(member(who, k) + ": val, c, AL, AU, l and u are all required (every scaled vector depends on the values)");
-        if (d.nnz != static_cast<long>(s[k]->A.view.nnz))
-            throw std::runtime_error(member(who, k) + ": nnz is " + std::to_string(d.nnz) + ", the model has " + std::to_string(s[k]->A.view.nnz) +
-                                     " entries (the pattern cannot change)");
-        if (d.obj_constant && std::isnan(*d.obj_constant)) throw std::runtime_error(member(who, k) + ": obj_constant is NaN");
-        gave[k] = 1;
-        ++ngave;
-    }
-    const auto t_ptr = time_now();
-    PointerChecks pass(s[0]->prm.device_number, who, dc);
-    for (int k = 0; k < count; ++k) {
-        if (!gave[k]) continue;
-        const MemberValues &d = data[k];
-        const size_t m = static_cast<size_t>(s[k]->m), n = static_cast<size_t>(s[k]->n);
-        pass(k, d.val, static_cast<size_t>(d.nnz), "val");
-        pass(k, d.c, n, "c"); pass(k, d.AL, m, "AL"); pass(k, d.AU, m, "AU"); pass(k, d.l, n, "l"); pass(k, d.u, n, "u");
-    }
-    const double ptr_seconds = time_since(t_ptr);
-    ValuesCounts vc;
-    const auto t0 = time_now();
-    GroupScope scope(s, count);
-    const hipStream_t st = scope.group;
-    const bool fused_norms = env_get("HPRLP_NO_FUSED_NORMS") == nullptr;  // (scale_many's condition)
-    std::vector<int> in;  // the members of the group launches
-    for (int k = 0; k < count; ++k)
-        if (gave[k] && fused_norms && s[k]->joins_group_resolve() && s[k]->m_loc > 0 && s[k]->n_loc > 0) in.push_back(k);
-    if (in.size() < 2) in.clear();  // (a group of one issues the member's own launches)
-    std::vector<char> joins(static_cast<size_t>(count), 0);
-    for (int k : in) joins[k] = 1;
-    // The scatter of a joining member (no value map for A) loads the values as 16-byte pairs: from the staging block in the host
-    // entry, from the caller's buffer here.  An 8-byte aligned `val` is the single entries' rule; the pairs need 16.
-    for (int k : in)
-        if (reinterpret_cast<uintptr_t>(data[k].val) % 16)
-            throw std::runtime_error(member(who, k) + ": val is not aligned to 16 bytes (the group's scatter loads the values in pairs)");
-    // One member alone is checked by its own call before it writes anything, and nobody else is written: no block.
-    GroupBlocks *gb = ngave >= 2 ? &blocks_of(s[0]) : nullptr;
-    try {
-        const auto t_maps = time_now();
-        std::vector<char> built(static_cast<size_t>(count), 0);
-        for (int k : in) {
-            if (s[k]->have_maps) continue;
-            s[k]->build_value_maps();
-            built[k] = 1;
-            ++vc.maps;
-        }
-        const double maps_seconds = time_since(t_maps);
-        const auto t_up = time_now();
-        if (gb) {
-            // ---- the check: vectors and values of ALL members where they lie, in ONE stage: two flag words per member (the
-            // vectors' at k, the values' at count + k), one memset, one copy, one wait
-            wait_for_caller(*gb, caller, st);
-            const size_t words = 2 * static_cast<size_t>(count);
-            unsigned long long *flags = cleared_flags(*gb, words, st);
-            ++vc.memsets;
-            GroupLaunches &chk = gb->gl;
-            const long tables0 = chk.tables_sent();
-            for (int k = 0; k < count; ++k) {
-                if (!gave[k]) continue;
-                const MemberValues &d = data[k];
-                chk.data_check(DataCheckArgs{{d.c, d.AL, d.AU, d.l, d.u}, {s[k]->n, s[k]->m, s[k]->m, s[k]->n, s[k]->n}, 0}, flags + k);
-                chk.values_check(d.val, d.nnz, flags + count + k);
-            }
-            const int launches = chk.run(st);
-            vc.launches += launches, dc.check_launches += launches;
-            vc.h2d += chk.tables_sent() - tables0;
-            fetch_flags(*gb, words, st, dc);
-            ++vc.d2h, ++vc.waits;
-            // (as the host entry, where the host checks of the vectors come first: a vector's NaN of any member wins)
-            for (int k = 0; k < count; ++k)
-                if (gave[k]) throw_if_flagged(gb->flags_h[k], kDataNames, member(who, k), "is NaN");
-            for (int k = 0; k < count; ++k)
-                if (gave[k] && gb->flags_h[count + k] != kValuesAllFinite)
-                    throw std::runtime_error(member(who, k) + ": val[" + std::to_string(gb->flags_h[count + k]) + "] is not finite");
-        }
-        const double upload_seconds = ptr_seconds + time_since(t_up);
-        // -- from here on the call goes through
-        // ---- the members that go their own way: Solver::set_matrix_values_device (its own checks included)
-        for (int k = 0; k < count; ++k) {
-            if (!gave[k] || joins[k]) continue;
-            Solver &m = *s[k];
-            const MemberValues &d = data[k];
-            const bool had_maps = m.have_maps;
-            const long f0 = m.fetches, l0 = scaling_launch_count();
-            try {
-                m.set_matrix_values_device(d.val, d.nnz, d.c, d.obj_constant, d.AL, d.AU, d.l, d.u, caller);
-            } catch (const std::exception &e) {  // (a member alone in the call: its own check's refusal, named as the group's)
-                std::string msg = e.what();
-                for (const char *own : {"set_matrix_values: ", "set_matrix_values_device: "})
-                    if (msg.compare(0, std::strlen(own), own) == 0) msg = msg.substr(std::strlen(own));
-                throw std::runtime_error(member(who, k) + ": " + msg);
-            }
-            ++vc.own, ++dc.own;
-            if (!had_maps) ++vc.maps;
-            // the flags' memset, the two checks, scatter, gather, the flags' copy and wait; reset_iterates' seventeen memsets and
-            // wait; scale(): its launches, its scalar fetches, its final wait; the wait that ends the call
-            vc.memsets += 1 + 17;
-            vc.launches += 4 + (scaling_launch_count() - l0);
-            vc.d2h += 1 + (m.fetches - f0);
-            vc.waits += 1 + 1 + (m.fetches - f0) + 1 + 1;
-        }
-        if (!in.empty()) {
-            values_apply_group(s, in, data, data, built, maps_seconds, upload_seconds, *gb, st, vc, t0, true);
-            dc.served += static_cast<long>(in.size());
-        }
-    } catch (...) {
-        if (gb) s[0]->group_blocks.reset();  // (whatever was recorded goes with it)
-        throw;
-    }
-    if (counts) *counts = vc;
+    set_matrix_values_group(s, count, data, Source{"hprlp_solver_set_matrix_values_many_device", caller, dcounts ? dcounts : &unused}, counts);
 }
 
 }  // namespace hprlp
+

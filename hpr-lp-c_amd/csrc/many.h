@@ -51,7 +51,16 @@ void ray_step_many(Solver **s, int count, const int *restart, double *out, int *
 // certificates of the members that join are the group's (DESIGN.md "Many small LPs", group detection).
 void run_many(Solver **s, int count, HPRLP_results *out, GroupCounts *counts = nullptr);
 
-// ---- group re-solve (DESIGN.md "Many small LPs", group re-solve) ------------------------------------------------------------
+// ---- group re-solve, group matrix values and their device twins (DESIGN.md "Many small LPs": group re-solve, group matrix values,
+// group device re-solve) -----------------------------------------------------------------------------------------------------------
+// Three pairs of entries.  A host entry takes the members' vectors in host memory; its device twin takes them in DEVICE memory of
+// the caller's (obj_constant and sigma stay host values) and a stream `caller` on which they were produced: one event on it, the
+// group's stream waits for it before its first read, and the call returns after the group's stream has drained.  The two of a
+// pair are one body in many.cpp; a pair is described once below, with what its twin does differently.  For all six: the members
+// have passed check_group and data / out are not null (abi.cpp owns those refusals); every refusal comes before anything a solver
+// reads is written, so it leaves every member as it was; the members that join (two at least) are served by the group launches,
+// every other member runs its own single entry -- Solver::set_data / resolve / set_matrix_values, or their *_device forms --
+// inside the same call.
 struct MemberData {   // Solver::set_data's arguments for one member (hprlp_member_data); all null: nothing changes
     const double *c = nullptr, *obj_constant = nullptr, *AL = nullptr, *AU = nullptr, *l = nullptr, *u = nullptr;
 };
@@ -59,77 +68,71 @@ struct MemberStart {  // Solver::resolve's arguments for one member (hprlp_membe
     const double *x0 = nullptr, *y0 = nullptr;
     double sigma = -1.0;
 };
-// what a set_data_many / resolve_many call did (hprlp_last_resolve_many_counts): copies host -> device (staging blocks and task
-// tables) and device -> host, host waits, kernel launches and memsets, all OUTSIDE the loop and with the operations of the members
-// that went their own way included; members served by the group launches / that went their own way (a member that gave nothing,
-// or obj_constant only, is neither); resolve_many: the loop's operations issued for one member (GroupCounts::own).  What the
-// group issues is counted where it is issued; what a member on its own issues is NOMINAL: the operations its single entries issue
-// in the common case (staging below the allocator cache's block size: one upload; no locality ordering; code arrays in place)
-struct ResolveCounts {
-    long h2d = 0, d2h = 0, waits = 0, launches = 0, memsets = 0, served = 0, own = 0, loop_own = 0;
-};
-// Solver::set_data for every member.  The members that join (Solver::joins_group_resolve, two at least): all given vectors in one
-// pinned block and one copy, k_reduce_many<DataInTask>, finalize, k_reduce_many<DataBcTask>, finalize, the scalars packed, one copy back, ONE wait, then
-// each member's host formulas.  Every other member runs its own set_data inside the same call.  The members have passed
-// check_group and data is not null (abi.cpp owns those refusals); throws before anything is written or launched: an incomplete
-// bounds group, a NaN.
-void set_data_many(Solver **s, int count, const MemberData *data, ResolveCounts *counts = nullptr);
-// Solver::resolve for every member: zeroing, bound codes, ctrl (a sigma override included) and the starts of the joining members
-// recorded into the group's launches, the lock-step loop of run_many with their iteration-0 evaluations recorded as well, the
-// solutions through one device block, one copy and one wait.  start null: all cold.  The members have passed check_group, out
-// is not null (abi.cpp owns those refusals) and the starts have passed check_starts.
-// check_starts: throws, naming `member k`, for a NaN sigma or a non-finite start entry; touches nothing.
-void check_starts(Solver *const *s, int count, const MemberStart *start);
-void resolve_many(Solver **s, int count, const MemberStart *start, HPRLP_results *out, ResolveCounts *counts = nullptr);
-
-// ---- group matrix values (DESIGN.md "Many small LPs", group matrix values) ------------------------------------------------------
 struct MemberValues {  // Solver::set_matrix_values' arguments for one member (hprlp_member_values); all null: the member is skipped
     const double *val = nullptr;
     long nnz = 0;
     const double *c = nullptr, *obj_constant = nullptr, *AL = nullptr, *AU = nullptr, *l = nullptr, *u = nullptr;
 };
-// what a set_matrix_values_many call did (hprlp_last_values_many_counts): copies host -> device (the staging block and the task
-// tables) and device -> host, host waits, kernel launches, memsets; members served by the group launches / that went their own way
-// (for those the operations their own Solver::set_matrix_values issues are added: counted where the solver counts them -- scaling
-// launches, scalar fetches --, nominal otherwise, as ResolveCounts); members whose value maps were built in this call
-struct ValuesCounts {
-    long h2d = 0, d2h = 0, waits = 0, launches = 0, memsets = 0, served = 0, own = 0, maps = 0;
-};
-// Solver::set_matrix_values for every member that gave values.  All host checks of all members first; the values of ALL of them
-// in one pinned block and one copy, checked by ONE launch into one flag word per member, one copy of the flags, one wait -- up to
-// there nothing a solver reads has been written, so a refusal leaves every member as it was.  Then the members that join
-// (values given, Solver::joins_group_resolve, scale_many's conditions, two at least): scatter, gather and the zeroing of
-// reset_iterates recorded in one stage, and Solver::scale()'s pieces walked behind them (scale_many's walk); every other member
-// runs its own set_matrix_values inside the same call.  The members have passed check_group and data is not null (abi.cpp owns
-// those refusals).
-void set_matrix_values_many(Solver **s, int count, const MemberValues *data, ValuesCounts *counts = nullptr);
-
-// ---- group device re-solve (DESIGN.md "Many small LPs", group device re-solve) ---------------------------------------------------
 struct MemberOut {  // where one member's solution goes (hprlp_member_out): device buffers of the caller's, null: not wanted
     double *x = nullptr, *y = nullptr, *z = nullptr;
+};
+// What a group call did outside the loop, the operations of the members that went their own way included: copies host -> device
+// (staging blocks and task tables) and device -> host, host waits, kernel launches and memsets; members served by the group
+// launches / that went their own way (a member that gave nothing, or obj_constant only, is neither).  What the group issues is
+// counted where it is issued; what a member on its own issues is NOMINAL: the operations its single entry issues in the common
+// case (staging below the allocator cache's block size: one upload; no locality ordering; code arrays in place) -- set_matrix_values
+// apart, where scaling launches and scalar fetches are counted where the solver counts them.
+struct CallCounts {
+    long h2d = 0, d2h = 0, waits = 0, launches = 0, memsets = 0, served = 0, own = 0;
+};
+// hprlp_last_resolve_many_counts (set_data_many, resolve_many and twins); resolve: the loop's operations issued for one member
+// (GroupCounts::own)
+struct ResolveCounts : CallCounts {
+    long loop_own = 0;
+};
+// hprlp_last_values_many_counts (set_matrix_values_many and twin); members whose value maps were built in this call
+struct ValuesCounts : CallCounts {
+    long maps = 0;
 };
 // what a device group call did beyond ResolveCounts / ValuesCounts (hprlp_last_many_device_counts): non-null device pointers
 // checked; lookups issued to the runtime for them (a pointer inside a range already reported in the call needs none); launches of
 // the device check; flag words copied back; members served by the group launches / that ran their own device entry; host waits
-// before the first write of anything a solver reads (the check's: 0 where nothing had to be checked)
+// before the first write of anything a solver reads (the check's: 0 where nothing had to be checked).  Filled as the call
+// proceeds, so it also tells what a refused call did.
 struct DeviceCounts {
     long pointers = 0, lookups = 0, check_launches = 0, flags = 0, served = 0, own = 0, waits_before_write = 0;
 };
-// set_data_many, resolve_many and set_matrix_values_many with the members' vectors in DEVICE memory of the caller's (obj_constant
-// and sigma stay host values) and the solutions stored into dst[k] (null: none wanted); out[k].x / y / z stay null.  `caller` is
-// the stream the inputs were produced on: one event on it, the group's stream waits for it before its first read, and the call
-// returns after the group's stream has drained.  Every non-null pointer of every member passes check_device_pointer first (one
-// lookup per distinct range); then ONE launch checks the vectors of all members where they lie (NaN in a data vector, a
-// non-finite start entry; the values in the same stage), one copy of the flag words, one wait -- a refusal of any kind leaves
-// every member as it was.  The members that join read the caller's buffers where the host entries read the staging block, same
-// kernels, same bits; every other member runs its own Solver::set_data_device / resolve_device / set_matrix_values_device inside
-// the same call.  The members have passed check_group and data / out are not null (abi.cpp owns those refusals).  dcounts is
-// filled as the call proceeds, so it also tells what a refused call did.
+
+// Solver::set_data for every member.  Refused first: an incomplete bounds group, a NaN in obj_constant or, host entry, in a vector.
+// The members that join (something given, Solver::joins_group_resolve): all given vectors in one pinned block and one copy,
+// k_reduce_many<DataInTask>, finalize, k_reduce_many<DataBcTask>, finalize, the scalars packed, one copy back, ONE wait, then each
+// member's host formulas.  The device twin: every non-null pointer of every member passes check_device_pointer (one lookup per
+// distinct range), then ONE launch checks the vectors of all members where they lie for NaN, one copy of the flag words, one wait;
+// the joiners' passes read the caller's buffers -- same kernels, same bits.
+void set_data_many(Solver **s, int count, const MemberData *data, ResolveCounts *counts = nullptr);
 void set_data_many_device(Solver **s, int count, const MemberData *data, hipStream_t caller, ResolveCounts *counts = nullptr,
                           DeviceCounts *dcounts = nullptr);
+// check_starts: throws, naming `who: member k`, for a NaN sigma and, host_vectors, for a non-finite start entry; touches nothing.
+void check_starts(Solver *const *s, int count, const MemberStart *start, const char *who, bool host_vectors);
+// Solver::resolve for every member: zeroing, bound codes, ctrl (a sigma override included) and the starts of the joining members
+// (Solver::joins_group_resolve) recorded into the group's launches, the lock-step loop of run_many with their iteration-0
+// evaluations recorded as well, the solutions through one device block, one copy and one wait.  start null: all cold.  The starts
+// have passed check_starts.  The device twin: the pointers of starts and outputs looked up, the starts of all members checked
+// where they lie by one launch (non-finite entries); a member on its own runs from start to solution before the loop, which then
+// holds the joiners alone; the solutions are stored into dst[k] (null: none wanted) and out[k].x / y / z stay null.
+void resolve_many(Solver **s, int count, const MemberStart *start, HPRLP_results *out, ResolveCounts *counts = nullptr);
 void resolve_many_device(Solver **s, int count, const MemberStart *start, const MemberOut *dst, hipStream_t caller, HPRLP_results *out,
                          ResolveCounts *counts = nullptr, DeviceCounts *dcounts = nullptr);
+// Solver::set_matrix_values for every member that gave values.  All host rules of all members first (all six vectors, nnz, NaN
+// in obj_constant or, host entry, in a vector); the values of ALL of them in one pinned block and one copy, checked by ONE launch
+// into one flag word per member, one copy of the flags, one wait.  Then the members that join (values given,
+// Solver::joins_group_resolve, scale_many's conditions): scatter, gather and the zeroing of reset_iterates recorded in one stage,
+// and Solver::scale()'s pieces walked behind them (scale_many's walk).  The device twin: the pointers looked up; vectors and
+// values checked where they lie in the same stage (a second flag word per member; a vector's NaN wins); a joiner's `val` must be
+// aligned to 16 bytes (the scatter loads pairs; the staging block is aligned by construction).
+void set_matrix_values_many(Solver **s, int count, const MemberValues *data, ValuesCounts *counts = nullptr);
 void set_matrix_values_many_device(Solver **s, int count, const MemberValues *data, hipStream_t caller, ValuesCounts *counts = nullptr,
                                    DeviceCounts *dcounts = nullptr);
 
 }  // namespace hprlp
+

@@ -706,6 +706,30 @@ def _dev_dbl(addr):
     return None if addr is None else C.cast(C.c_void_p(addr), c_dbl_p)
 
 
+# The per-vector converters of the group methods' array builders (Solver._member_data / _member_values / _member_starts): one
+# member's vector as (what keeps it alive until the call returns, the pointer for the member struct); None stays (None, None).
+# length None: the matrix values -- one-dimensional, of any length (a wrong count is the library's to refuse, naming the member).
+def _host_vector(sv, v, length, name, who):
+    """numpy in, for the host group entries."""
+    if length is None and v is not None:
+        a = _as(v, np.float64)
+        if a.ndim != 1:
+            raise ValueError(f"{who}: {name} must be one-dimensional, got shape {a.shape}")
+    else:
+        a = sv._data_vector(v, length, name)
+    return a, _dptr(a)
+
+
+def _device_vector(sv, t, length, name, who):
+    """torch tensors in, for the device group entries (*_many_tensors)."""
+    if length is None and t is not None:
+        if getattr(t, "ndim", 0) != 1:
+            raise ValueError(f"{who}: {name} must be a one-dimensional tensor")
+        length = t.shape[0]
+    t, addr = sv._tensor(t, length, name, who)
+    return t, _dev_dbl(addr)
+
+
 def solve_batched(model, Cmat, AL, AU, l, u, obj_constants=None, param=None):
     """Cmat,l,u: (n,B) arrays; AL,AU: (m,B) arrays (any layout; passed column-major as the ABI asks)."""
     return _batched_call(lambda B, args, cp: lib().solve_batched(model._ptr, B, *args, C.byref(cp)),
@@ -1642,27 +1666,76 @@ class Solver:
         """set_data(**data[k]) of every solver with one copy, one launch per kernel and one host wait for the members that join
         (hprlp_solver_set_data_many).  data: one dict per solver with the keys of set_data; None or {} changes nothing."""
         solvers, hs = Solver._handles(solvers)
-        data = list(data)
-        if len(data) != len(solvers):
-            raise ValueError("set_data_many: one dict (or None) per solver")
-        arr = (CMemberData * max(len(solvers), 1))()
-        keep = []  # (the arrays the pointers name live until the call returns)
-        for k, (sv, d) in enumerate(zip(solvers, data)):
-            d = dict(d or {})
-            unknown = set(d) - {"c", "obj_constant", "AL", "AU", "l", "u"}
-            if unknown:
-                raise ValueError(f"set_data_many: member {k}: unknown keys {sorted(unknown)}")
-            m, n = sv.model.m, sv.model.n
-            for key, length in (("c", n), ("AL", m), ("AU", m), ("l", n), ("u", n)):
-                v = sv._data_vector(d.get(key), length, key)
-                keep.append(v)
-                setattr(arr[k], key, _dptr(v))
-            if d.get("obj_constant") is not None:
-                oc = C.c_double(float(d["obj_constant"]))
-                keep.append(oc)
-                arr[k].obj_constant = C.pointer(oc)
+        arr, keep = Solver._member_data("set_data_many", solvers, data, _host_vector)  # (keep: alive until the call returns)
         if lib().hprlp_solver_set_data_many(hs, len(solvers), arr) < 0:
             raise RuntimeError(last_error())
+
+    # ---- the array builders of the group methods: a host method and its *_tensors twin differ in the per-vector converter ----------
+    @staticmethod
+    def _fill_member(who, sv, d, entry, keep, vector, with_values=False):
+        """One member's dict into its CMemberData / CMemberValues entry; what the pointers name is appended to keep."""
+        unknown = set(d) - ({"c", "obj_constant", "AL", "AU", "l", "u"} | ({"values"} if with_values else set()))
+        if unknown:
+            raise ValueError(f"{who}: unknown keys {sorted(unknown)}")
+        m, n = sv.model.m, sv.model.n
+        if with_values and d.get("values") is not None:
+            kept, entry.val = vector(sv, d["values"], None, "values", who)
+            entry.nnz = kept.shape[0]
+            keep.append(kept)
+        for key, length in (("c", n), ("AL", m), ("AU", m), ("l", n), ("u", n)):
+            kept, ptr = vector(sv, d.get(key), length, key, who)
+            keep.append(kept)
+            setattr(entry, key, ptr)
+        if d.get("obj_constant") is not None:
+            oc = C.c_double(float(d["obj_constant"]))
+            keep.append(oc)
+            entry.obj_constant = C.pointer(oc)
+
+    @staticmethod
+    def _member_data(who, solvers, data, vector):
+        """(CMemberData array, keep) of set_data_many / set_data_many_tensors; None or {} leaves a member's entry all NULL."""
+        data = list(data)
+        if len(data) != len(solvers):
+            raise ValueError(f"{who}: one dict (or None) per solver")
+        arr = (CMemberData * max(len(solvers), 1))()
+        keep = []
+        for k, (sv, d) in enumerate(zip(solvers, data)):
+            Solver._fill_member(f"{who}: member {k}", sv, dict(d or {}), arr[k], keep, vector)
+        return arr, keep
+
+    @staticmethod
+    def _member_values(who, solvers, data, vector):
+        """(CMemberValues array, keep) of set_matrix_many / set_matrix_many_tensors; None skips a member."""
+        data = list(data)
+        if len(data) != len(solvers):
+            raise ValueError(f"{who}: one dict (or None) per solver")
+        arr = (CMemberValues * max(len(solvers), 1))()
+        keep = []
+        for k, (sv, d) in enumerate(zip(solvers, data)):
+            if d is not None:
+                Solver._fill_member(f"{who}: member {k}", sv, dict(d), arr[k], keep, vector, with_values=True)
+        return arr, keep
+
+    @staticmethod
+    def _member_starts(who, solvers, vector, **named):
+        """(CMemberStart array, keep, lists) of resolve_many / resolve_many_tensors.  named: x, y, sigma and whatever else the
+        method takes per solver, each a list (None entries allowed) or None for all; lists: the same, one entry per solver."""
+        K = len(solvers)
+        lists = {}
+        for name, v in named.items():
+            v = [None] * K if v is None else list(v)
+            if len(v) != K:
+                raise ValueError(f"{who}: {name} needs one entry (or None) per solver")
+            lists[name] = v
+        arr = (CMemberStart * max(K, 1))()
+        keep = []
+        for k, sv in enumerate(solvers):
+            # (lengths are checked here; a non-finite entry is the library's to refuse, naming the member)
+            xs, arr[k].x0 = vector(sv, lists["x"][k], sv.model.n, "x", f"{who}: member {k}")
+            ys, arr[k].y0 = vector(sv, lists["y"][k], sv.model.m, "y", f"{who}: member {k}")
+            keep += [xs, ys]
+            arr[k].sigma = -1.0 if lists["sigma"][k] is None else float(lists["sigma"][k])
+        return arr, keep, lists
 
     @staticmethod
     def resolve_many(solvers, x=None, y=None, sigma=None):
@@ -1670,20 +1743,7 @@ class Solver:
         entries allowed), or None for all.  Returns a list of Results (no trace)."""
         solvers, hs = Solver._handles(solvers)
         K = len(solvers)
-        lists = []
-        for name, v in (("x", x), ("y", y), ("sigma", sigma)):
-            v = [None] * K if v is None else list(v)
-            if len(v) != K:
-                raise ValueError(f"resolve_many: {name} needs one entry (or None) per solver")
-            lists.append(v)
-        arr = (CMemberStart * max(K, 1))()
-        keep = []
-        for k, sv in enumerate(solvers):
-            # (lengths are checked here; a non-finite entry is the library's to refuse, naming the member)
-            xs, ys = sv._data_vector(lists[0][k], sv.model.n, "x"), sv._data_vector(lists[1][k], sv.model.m, "y")
-            keep += [xs, ys]
-            arr[k].x0, arr[k].y0 = _dptr(xs), _dptr(ys)
-            arr[k].sigma = -1.0 if lists[2][k] is None else float(lists[2][k])
+        arr, keep, _ = Solver._member_starts("resolve_many", solvers, _host_vector, x=x, y=y, sigma=sigma)
         res = (CResults * max(K, 1))()
         if lib().hprlp_solver_resolve_many(hs, K, arr, res) < 0:
             raise RuntimeError(last_error())
@@ -1727,33 +1787,7 @@ class Solver:
         obj_constant).  Unlike set_matrix() this is the C call alone: power_iteration_many(), init() and resolve_many() come next,
         as after scale_many()."""
         solvers, hs = Solver._handles(solvers)
-        data = list(data)
-        if len(data) != len(solvers):
-            raise ValueError("set_matrix_many: one dict (or None) per solver")
-        arr = (CMemberValues * max(len(solvers), 1))()
-        keep = []  # (the arrays the pointers name live until the call returns)
-        for k, (sv, d) in enumerate(zip(solvers, data)):
-            if d is None:
-                continue
-            d = dict(d)
-            unknown = set(d) - {"values", "c", "obj_constant", "AL", "AU", "l", "u"}
-            if unknown:
-                raise ValueError(f"set_matrix_many: member {k}: unknown keys {sorted(unknown)}")
-            m, n = sv.model.m, sv.model.n
-            if d.get("values") is not None:
-                v = _as(d["values"], np.float64)
-                if v.ndim != 1:
-                    raise ValueError(f"set_matrix_many: member {k}: values must be one-dimensional, got shape {v.shape}")
-                keep.append(v)
-                arr[k].val, arr[k].nnz = _dptr(v), v.shape[0]  # (a wrong count is the library's to refuse, naming the member)
-            for key, length in (("c", n), ("AL", m), ("AU", m), ("l", n), ("u", n)):
-                a = sv._data_vector(d.get(key), length, key)
-                keep.append(a)
-                setattr(arr[k], key, _dptr(a))
-            if d.get("obj_constant") is not None:
-                oc = C.c_double(float(d["obj_constant"]))
-                keep.append(oc)
-                arr[k].obj_constant = C.pointer(oc)
+        arr, keep = Solver._member_values("set_matrix_many", solvers, data, _host_vector)  # (keep: alive until the call returns)
         if lib().hprlp_solver_set_matrix_values_many(hs, len(solvers), arr) < 0:
             raise RuntimeError(last_error())
 
@@ -1844,25 +1878,7 @@ class Solver:
         and slices of a packed one are welcome: they are views), taken as ordered on the current torch stream; obj_constant is a
         host number; None or {} changes nothing.  No vector is copied.  Same bits as set_data_many()."""
         solvers, hs = Solver._handles(solvers)
-        data = list(data)
-        if len(data) != len(solvers):
-            raise ValueError("set_data_many_tensors: one dict (or None) per solver")
-        arr = (CMemberData * max(len(solvers), 1))()
-        keep = []  # (what the pointers name lives until the call returns)
-        for k, (sv, d) in enumerate(zip(solvers, data)):
-            d = dict(d or {})
-            unknown = set(d) - {"c", "obj_constant", "AL", "AU", "l", "u"}
-            if unknown:
-                raise ValueError(f"set_data_many_tensors: member {k}: unknown keys {sorted(unknown)}")
-            m, n = sv.model.m, sv.model.n
-            for key, length in (("c", n), ("AL", m), ("AU", m), ("l", n), ("u", n)):
-                t, addr = sv._tensor(d.get(key), length, key, f"set_data_many_tensors: member {k}")
-                keep.append(t)
-                setattr(arr[k], key, _dev_dbl(addr))
-            if d.get("obj_constant") is not None:
-                oc = C.c_double(float(d["obj_constant"]))
-                keep.append(oc)
-                arr[k].obj_constant = C.pointer(oc)
+        arr, keep = Solver._member_data("set_data_many_tensors", solvers, data, _device_vector)  # (keep: alive until the call returns)
         stream = solvers[0]._torch_stream() if solvers else None
         if lib().hprlp_solver_set_data_many_device(hs, len(solvers), arr, stream) < 0:
             raise RuntimeError(last_error())
@@ -1878,12 +1894,8 @@ class Solver:
         import torch
         solvers, hs = Solver._handles(solvers)
         K = len(solvers)
-        lists = []
-        for name, v in (("x", x), ("y", y), ("sigma", sigma), ("out", out)):
-            v = [None] * K if v is None else list(v)
-            if len(v) != K:
-                raise ValueError(f"resolve_many_tensors: {name} needs one entry (or None) per solver")
-            lists.append(v)
+        starts, keep, lists = Solver._member_starts("resolve_many_tensors", solvers, _device_vector, x=x, y=y, sigma=sigma, out=out)
+        wanted = lists["out"]
         if out is None and K > 0:
             device = torch.device("cuda", getattr(solvers[0], "device_number", 0))
             ns, ms = [sv.model.n for sv in solvers], [sv.model.m for sv in solvers]
@@ -1891,19 +1903,14 @@ class Solver:
             ys_all = torch.empty(sum(ms), dtype=torch.float64, device=device)
             an = am = 0
             for k in range(K):
-                lists[3][k] = (xs_all[an:an + ns[k]], ys_all[am:am + ms[k]], zs_all[an:an + ns[k]])
+                wanted[k] = (xs_all[an:an + ns[k]], ys_all[am:am + ms[k]], zs_all[an:an + ns[k]])
                 an, am = an + ns[k], am + ms[k]
-        starts = (CMemberStart * max(K, 1))()
         dst = (CMemberOut * max(K, 1))()
-        keep, outs = [], []
+        outs = []
         for k, sv in enumerate(solvers):
             who = f"resolve_many_tensors: member {k}"
             m, n = sv.model.m, sv.model.n
-            xs, ys = sv._tensor(lists[0][k], n, "x", who), sv._tensor(lists[1][k], m, "y", who)
-            keep += [xs[0], ys[0]]
-            starts[k].x0, starts[k].y0 = _dev_dbl(xs[1]), _dev_dbl(ys[1])
-            starts[k].sigma = -1.0 if lists[2][k] is None else float(lists[2][k])
-            triple = tuple(lists[3][k]) if lists[3][k] is not None else (None, None, None)
+            triple = tuple(wanted[k]) if wanted[k] is not None else (None, None, None)
             if len(triple) != 3:
                 raise ValueError(f"{who}: out is an (x, y, z) triple of tensors or Nones")
             for t, length, name in zip(triple, (n, m, n), ("x", "y", "z")):
@@ -1929,35 +1936,7 @@ class Solver:
         tensors; optionally obj_constant, a host number).  As set_matrix_many() this is the C call alone:
         power_iteration_many(), init() and a re-solve come next.  Same bits as set_matrix_many()."""
         solvers, hs = Solver._handles(solvers)
-        data = list(data)
-        if len(data) != len(solvers):
-            raise ValueError("set_matrix_many_tensors: one dict (or None) per solver")
-        arr = (CMemberValues * max(len(solvers), 1))()
-        keep = []  # (what the pointers name lives until the call returns)
-        for k, (sv, d) in enumerate(zip(solvers, data)):
-            if d is None:
-                continue
-            d = dict(d)
-            unknown = set(d) - {"values", "c", "obj_constant", "AL", "AU", "l", "u"}
-            if unknown:
-                raise ValueError(f"set_matrix_many_tensors: member {k}: unknown keys {sorted(unknown)}")
-            who = f"set_matrix_many_tensors: member {k}"
-            m, n = sv.model.m, sv.model.n
-            v = d.get("values")
-            if v is not None:
-                if getattr(v, "ndim", 0) != 1:
-                    raise ValueError(f"{who}: values must be a one-dimensional tensor")
-                t, addr = sv._tensor(v, v.shape[0], "values", who)  # (a wrong count is the library's to refuse, naming the member)
-                keep.append(t)
-                arr[k].val, arr[k].nnz = _dev_dbl(addr), v.shape[0]
-            for key, length in (("c", n), ("AL", m), ("AU", m), ("l", n), ("u", n)):
-                t, addr = sv._tensor(d.get(key), length, key, who)
-                keep.append(t)
-                setattr(arr[k], key, _dev_dbl(addr))
-            if d.get("obj_constant") is not None:
-                oc = C.c_double(float(d["obj_constant"]))
-                keep.append(oc)
-                arr[k].obj_constant = C.pointer(oc)
+        arr, keep = Solver._member_values("set_matrix_many_tensors", solvers, data, _device_vector)  # (keep: alive until the call returns)
         stream = solvers[0]._torch_stream() if solvers else None
         if lib().hprlp_solver_set_matrix_values_many_device(hs, len(solvers), arr, stream) < 0:
             raise RuntimeError(last_error())
