@@ -1945,6 +1945,148 @@ extern "C" int hprlp_locality_ordering(int m, int n, const int *rowptr, const in
     }
 }
 
+// ---- the ordering step by step (test infrastructure; tests/test_reorderref.py, tests/test_gpu_reorder_steps.py)
+static void check_pattern(int m, int n, const int *rp, const int *ci) {
+    if (m <= 0 || n <= 0 || !rp || !ci) throw std::runtime_error("bad arguments");
+    if (rp[0] != 0) throw std::runtime_error("rowptr[0] != 0");
+    for (int i = 0; i < m; ++i)
+        if (rp[i + 1] < rp[i]) throw std::runtime_error("rowptr decreases");
+    if (rp[m] <= 0) throw std::runtime_error("no entries");
+    for (int k = 0; k < rp[m]; ++k)
+        if (ci[k] < 0 || ci[k] >= n) throw std::runtime_error("column index out of range");
+}
+
+static void check_permutation(int len, const int *p, const char *what) {
+    std::vector<char> seen(static_cast<size_t>(len), 0);
+    for (int i = 0; i < len; ++i) {
+        if (p[i] < 0 || p[i] >= len || seen[p[i]]) throw std::runtime_error(std::string(what) + " is not a permutation");
+        seen[p[i]] = 1;
+    }
+}
+
+extern "C" int hprlp_reorder_steps(int m, int n, const int *rowptr, const int *col, int on_device, int sweeps, int *lab_r, int *lab_c,
+                                   double *pos0_r, double *pos0_c, double *pos_r, double *pos_c, int *row_new2old, int *col_new2old,
+                                   double stats[5]) {
+    try {
+        check_pattern(m, n, rowptr, col);
+        if (sweeps < 0) throw std::runtime_error("negative sweep count");
+        const long nnz = rowptr[m];
+        const size_t M = static_cast<size_t>(m), N = static_cast<size_t>(n);
+        std::vector<int> trp, tci, lr(M), lc(N), hr, hc;
+        transpose_pattern(m, n, rowptr, col, trp, tci);
+        ReorderStats st;
+        std::vector<double> p0r, p0c, pr, pc;
+        if (on_device) {
+            hipStream_t s = nullptr;
+            DBuf<int> drp(M + 1), dci(static_cast<size_t>(nnz)), dtrp(N + 1), dtci(static_cast<size_t>(nnz)), d_r(M), d_c(N);
+            drp.upload(rowptr, M + 1);
+            dci.upload(col, static_cast<size_t>(nnz));
+            dtrp.upload(trp.data(), N + 1);
+            dtci.upload(tci.data(), static_cast<size_t>(nnz));
+            DBuf<double> dpr(M), dpc(N);
+            st.fraction_before = device_tiling_dense_fraction(m, n, nnz, drp.p, dci.p, nullptr, nullptr, s);
+            device_cluster_positions(m, n, nnz, drp.p, dci.p, dtrp.p, dtci.p, dpr.p, dpc.p, &st, s, lr.data(), lc.data());
+            p0r.resize(M); p0c.resize(N); pr.resize(M); pc.resize(N); hr.resize(M); hc.resize(N);
+            dpr.download(p0r.data(), M);
+            dpc.download(p0c.data(), N);
+            device_refine_order(m, n, drp.p, dci.p, dtrp.p, dtci.p, dpr.p, dpc.p, sweeps, d_r.p, d_c.p, s);
+            dpr.download(pr.data(), M);
+            dpc.download(pc.data(), N);
+            d_r.download(hr.data(), M);
+            d_c.download(hc.data(), N);
+            check_permutation(m, hr.data(), "the device's row_new2old");  // (before it indexes anything on the device)
+            check_permutation(n, hc.data(), "the device's col_new2old");
+            st.fraction_after = device_tiling_dense_fraction(m, n, nnz, drp.p, dci.p, d_r.p, d_c.p, s);
+        } else {
+            st.fraction_before = tiling_dense_fraction(m, n, rowptr, col, nullptr, nullptr);
+            cluster_positions(m, n, rowptr, col, trp.data(), tci.data(), &p0r, &p0c, &st, &lr, &lc);
+            pr = p0r;
+            pc = p0c;
+            refine_order(m, n, rowptr, col, trp.data(), tci.data(), pr, pc, sweeps, &hr, &hc);
+            std::vector<int> c_old2new(N);
+            for (int j = 0; j < n; ++j) c_old2new[hc[j]] = j;
+            st.fraction_after = tiling_dense_fraction(m, n, rowptr, col, hr.data(), c_old2new.data());
+        }
+        if (lab_r) std::copy(lr.begin(), lr.end(), lab_r);
+        if (lab_c) std::copy(lc.begin(), lc.end(), lab_c);
+        if (pos0_r) std::copy(p0r.begin(), p0r.end(), pos0_r);
+        if (pos0_c) std::copy(p0c.begin(), p0c.end(), pos0_c);
+        if (pos_r) std::copy(pr.begin(), pr.end(), pos_r);
+        if (pos_c) std::copy(pc.begin(), pc.end(), pos_c);
+        if (row_new2old) std::copy(hr.begin(), hr.end(), row_new2old);
+        if (col_new2old) std::copy(hc.begin(), hc.end(), col_new2old);
+        if (stats) {
+            stats[0] = st.clusters; stats[1] = st.components; stats[2] = st.bfs_levels;
+            stats[3] = st.fraction_before; stats[4] = st.fraction_after;
+        }
+        return 0;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+extern "C" int hprlp_permute_csr_device(int m, int n, const int *rowptr, const int *col, const double *val, const int *row_new2old,
+                                        const int *col_new2old, int *rp_out, int *ci_out, double *val_out) {
+    try {
+        check_pattern(m, n, rowptr, col);
+        if (!val || !row_new2old || !col_new2old || !rp_out || !ci_out || !val_out) throw std::runtime_error("bad arguments");
+        check_permutation(m, row_new2old, "row_new2old");
+        check_permutation(n, col_new2old, "col_new2old");
+        const size_t M = static_cast<size_t>(m), N = static_cast<size_t>(n), Z = static_cast<size_t>(rowptr[m]);
+        DBuf<int> drp(M + 1), dci(Z), d_r(M), d_c(N), orp(M + 1), oci(Z);
+        DBuf<double> dv(Z), ov(Z);
+        drp.upload(rowptr, M + 1);
+        dci.upload(col, Z);
+        dv.upload(val, Z);
+        d_r.upload(row_new2old, M);
+        d_c.upload(col_new2old, N);
+        device_permute_csr(m, n, static_cast<long>(Z), drp.p, dci.p, dv.p, d_r.p, d_c.p, orp.p, oci.p, ov.p, nullptr);
+        orp.download(rp_out, M + 1);
+        oci.download(ci_out, Z);
+        ov.download(val_out, Z);
+        return 0;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+extern "C" int hprlp_tiling_share(int m, int n, const int *rowptr, const int *col, const int *row_new2old, const int *col_new2old,
+                                  int on_device, double *share) {
+    try {
+        check_pattern(m, n, rowptr, col);
+        if (!share || (row_new2old == nullptr) != (col_new2old == nullptr)) throw std::runtime_error("bad arguments");
+        if (row_new2old) {
+            check_permutation(m, row_new2old, "row_new2old");
+            check_permutation(n, col_new2old, "col_new2old");
+        }
+        const size_t M = static_cast<size_t>(m), N = static_cast<size_t>(n), Z = static_cast<size_t>(rowptr[m]);
+        if (on_device) {
+            DBuf<int> drp(M + 1), dci(Z), d_r, d_c;
+            drp.upload(rowptr, M + 1);
+            dci.upload(col, Z);
+            if (row_new2old) {
+                d_r.alloc(M);
+                d_c.alloc(N);
+                d_r.upload(row_new2old, M);
+                d_c.upload(col_new2old, N);
+            }
+            *share = device_tiling_dense_fraction(m, n, static_cast<long>(Z), drp.p, dci.p, d_r.p, d_c.p, nullptr);
+        } else if (row_new2old) {
+            std::vector<int> c_old2new(N);
+            for (int j = 0; j < n; ++j) c_old2new[col_new2old[j]] = j;
+            *share = tiling_dense_fraction(m, n, rowptr, col, row_new2old, c_old2new.data());
+        } else {
+            *share = tiling_dense_fraction(m, n, rowptr, col, nullptr, nullptr);
+        }
+        return 0;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
 // Host only: the stream kernel's row blocks of a CSR pattern (split rows, chunks by column eighths), built and checked as a
 // solver's set-up does.  out = {blocks, split rows, chunk slots, rows cut by column eighths, longest chunk, entries covered}.
 extern "C" int hprlp_row_block_plan(int m, int n, const int *rowptr, const int *col, int with_cuts, long out[6]) {
@@ -2272,6 +2414,21 @@ extern "C" int hprlp_solver_ordering(hprlp_solver *h, int *row_new2old, int *col
     std::copy(s.perm_r.begin(), s.perm_r.end(), row_new2old);
     std::copy(s.perm_c.begin(), s.perm_c.end(), col_new2old);
     return 1;
+    GUARD_END(-1)
+}
+
+// The power iteration's start vector as Solver::power_start leaves it on the device, in the caller's numbering.
+extern "C" int hprlp_solver_power_start(hprlp_solver *h, double *out, int cap) {
+    GUARD_BEGIN
+    if (!h || !out) throw std::runtime_error("hprlp_solver_power_start: null solver / output");
+    Solver &s = h->s;
+    if (s.comm) throw std::runtime_error("hprlp_solver_power_start: single-GPU solvers only");
+    if (cap < s.m_loc) throw std::runtime_error("hprlp_solver_power_start: output too short");
+    s.power_start(s.sm1.p);
+    std::vector<double> z(static_cast<size_t>(std::max(s.m_loc, 1)));
+    HIP_CHECK(hipMemcpy(z.data(), s.sm1.p, sizeof(double) * static_cast<size_t>(s.m_loc), hipMemcpyDeviceToHost));
+    for (int i = 0; i < s.m_loc; ++i) out[s.perm_r.empty() ? i : s.perm_r[i]] = z[i];
+    return s.m_loc;
     GUARD_END(-1)
 }
 

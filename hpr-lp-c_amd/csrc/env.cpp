@@ -56,6 +56,7 @@ static const EnvEntry kTable[] = {
     {"HPRLP_PRESOLVE_MAX_LINKS", EnvKind::Hook, "run one presolve stage alone / cut the chain after n links (tests, debugging)"},
     {"HPRLP_PRESOLVE_OFF", EnvKind::Hook, "switch presolve reductions / stages off (any subset; diagnostics)"},
     {"HPRLP_PRESOLVE_ONLY", EnvKind::Hook, "run one presolve stage alone / cut the chain after n links (tests, debugging)"},
+    {"HPRLP_REORDER_ANYWAY", EnvKind::Hook, "apply the locality ordering although the given order passes the tiling test or has a valid tiled copy already (the ordering inside a solver at a small shape)"},
     {"HPRLP_REORDER_CLUSTER", EnvKind::Hook, "knobs of the HOST reference path of the ordering (hprlp_locality_ordering): nodes per cluster, refinement sweeps, trimming percentage"},
     {"HPRLP_REORDER_HOST", EnvKind::Hook, "run the clustering of the locality ordering on the host (the reference form; default: on the device)"},
     {"HPRLP_REORDER_SWEEPS", EnvKind::Hook, "knobs of the HOST reference path of the ordering (hprlp_locality_ordering): nodes per cluster, refinement sweeps, trimming percentage"},

@@ -24,6 +24,14 @@
 //   5. the permutations are the argsorts; accepted only if the permuted pattern passes the tiling test that the
 //      given order failed.
 // Everything is deterministic (fixed seeds, no races: the parallel loops write disjoint outputs from read-only inputs).
+//
+// Host and device owe the same bits: labels, cluster positions (both hand their edge counts to the one cluster_order), every
+// half-sweep's positions (same sampling, ascending sort, left-to-right sum, one division; ranks (i + 0.5) / n by a division on
+// both sides) and the permutations.  hprlp_reorder_steps hands out each of them for either side and the GPU tests compare them
+// with np.array_equal (tests/test_gpu_reorder_steps.py; tests/reorderref.py restates the rules in numpy).  The one place they
+// may differ: a graph whose Voronoi BFS is not over after the 12 synchronous levels below -- the host finishes with a queue
+// (a node takes the label of whichever labelled neighbour reaches it first in queue order), the device goes on level by level
+// (first labelled neighbour in adjacency order).
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
@@ -61,6 +69,8 @@ void parallel_chunks(long n, int T, F fn) {
     for (auto &x : th) x.join();
 }
 
+}  // namespace
+
 // pattern transpose (counting sort, stable in row order)
 void transpose_pattern(int m, int n, const int *rp, const int *ci, std::vector<int> &trp, std::vector<int> &tci) {
     const long nnz = rp[m];
@@ -73,6 +83,8 @@ void transpose_pattern(int m, int n, const int *rp, const int *ci, std::vector<i
         for (int k = rp[i]; k < rp[i + 1]; ++k) tci[next[ci[k]]++] = i;
 }
 
+namespace {
+
 // ranks / count of `pos` (stable: ties by index), in place
 void rank_normalise(std::vector<double> &pos, int T) {
     const long n = static_cast<long>(pos.size());
@@ -80,9 +92,9 @@ void rank_normalise(std::vector<double> &pos, int T) {
     std::vector<int> ord(static_cast<size_t>(n));
     std::iota(ord.begin(), ord.end(), 0);
     std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return pos[a] < pos[b]; });
-    const double inv = 1.0 / static_cast<double>(n);
+    // (a division, as k_assign_ranks: a product with 1.0 / n differs in the last place for half of the indices)
     parallel_chunks(n, T, [&](int, long b, long e) {
-        for (long i = b; i < e; ++i) pos[ord[i]] = (static_cast<double>(i) + 0.5) * inv;
+        for (long i = b; i < e; ++i) pos[ord[i]] = (static_cast<double>(i) + 0.5) / static_cast<double>(n);
     });
 }
 
@@ -355,7 +367,7 @@ std::vector<double> cluster_order(int K, const std::vector<std::vector<std::pair
 }
 
 void cluster_positions(int m, int n, const int *rp, const int *ci, const int *trp_, const int *tci_, std::vector<double> *pos_r,
-                       std::vector<double> *pos_c, ReorderStats *st) {
+                       std::vector<double> *pos_c, ReorderStats *st, std::vector<int> *lab_r_out, std::vector<int> *lab_c_out) {
     ReorderStats local;
     ReorderStats &S = st ? *st : local;
     auto tphase = time_now();
@@ -526,6 +538,28 @@ void cluster_positions(int m, int n, const int *rp, const int *ci, const int *tr
     for (int j = 0; j < n; ++j) pc_[j] = lab_c[j] >= 0 ? cpos[lab_c[j]] : (static_cast<double>(j) + 0.5) / n;
     *pos_r = std::move(pr_);
     *pos_c = std::move(pc_);
+    if (lab_r_out) *lab_r_out = std::move(lab_r);
+    if (lab_c_out) *lab_c_out = std::move(lab_c);
+}
+
+// Step 4 and the argsorts of step 5 (device_refine_order: the same sequence): on return pos_r / pos_c hold the ranks
+void refine_order(int m, int n, const int *rp, const int *ci, const int *trp, const int *tci, std::vector<double> &pos_r,
+                  std::vector<double> &pos_c, int sweeps, std::vector<int> *row_new2old, std::vector<int> *col_new2old) {
+    const int T = worker_count(m > 0 ? rp[m] : 0);
+    rank_normalise(pos_r, T);
+    for (int sweep = 0; sweep < sweeps; ++sweep) {
+        centre_sweep(n, trp, tci, pos_r, pos_c, T);
+        rank_normalise(pos_c, T);
+        centre_sweep(m, rp, ci, pos_c, pos_r, T);
+        rank_normalise(pos_r, T);
+    }
+    if (sweeps <= 0) rank_normalise(pos_c, T);
+    row_new2old->resize(static_cast<size_t>(m));
+    col_new2old->resize(static_cast<size_t>(n));
+    std::iota(row_new2old->begin(), row_new2old->end(), 0);
+    std::iota(col_new2old->begin(), col_new2old->end(), 0);
+    std::stable_sort(row_new2old->begin(), row_new2old->end(), [&](int a, int b) { return pos_r[a] < pos_r[b]; });
+    std::stable_sort(col_new2old->begin(), col_new2old->end(), [&](int a, int b) { return pos_c[a] < pos_c[b]; });
 }
 
 bool locality_ordering(int m, int n, const int *rp, const int *ci, std::vector<int> *row_new2old, std::vector<int> *col_new2old,
@@ -542,7 +576,6 @@ bool locality_ordering(int m, int n, const int *rp, const int *ci, std::vector<i
     };
     const long nnz = (m > 0) ? rp[m] : 0;
     if (m <= 0 || n <= 0 || nnz <= 0) return false;
-    const int T = worker_count(nnz);
     S.fraction_before = tiling_dense_fraction(m, n, rp, ci, nullptr, nullptr);
     if (S.fraction_before >= accept_fraction) {
         S.seconds = time_since(t0);
@@ -555,27 +588,14 @@ bool locality_ordering(int m, int n, const int *rp, const int *ci, std::vector<i
     std::vector<double> pr_, pc_;
     cluster_positions(m, n, rp, ci, trp.data(), tci.data(), &pr_, &pc_, &S);
     tphase = time_now();
-    rank_normalise(pr_, T);
     const int nsweeps = env_get("HPRLP_REORDER_SWEEPS") ? std::atoi(env_get("HPRLP_REORDER_SWEEPS")) : kReorderSweeps;
-    for (int sweep = 0; sweep < nsweeps; ++sweep) {
-        centre_sweep(n, trp.data(), tci.data(), pr_, pc_, T);
-        rank_normalise(pc_, T);
-        centre_sweep(m, rp, ci, pc_, pr_, T);
-        rank_normalise(pr_, T);
-    }
-
-    tick("median sweeps");
     // ---- 5. permutations, accepted only if they make the pattern tileable
-    row_new2old->resize(static_cast<size_t>(m));
-    col_new2old->resize(static_cast<size_t>(n));
-    std::iota(row_new2old->begin(), row_new2old->end(), 0);
-    std::iota(col_new2old->begin(), col_new2old->end(), 0);
-    std::stable_sort(row_new2old->begin(), row_new2old->end(), [&](int a, int b) { return pr_[a] < pr_[b]; });
-    std::stable_sort(col_new2old->begin(), col_new2old->end(), [&](int a, int b) { return pc_[a] < pc_[b]; });
+    refine_order(m, n, rp, ci, trp.data(), tci.data(), pr_, pc_, nsweeps, row_new2old, col_new2old);
+    tick("median sweeps + sorts");
     std::vector<int> col_old2new(static_cast<size_t>(n));
     for (int j = 0; j < n; ++j) col_old2new[(*col_new2old)[j]] = j;
     S.fraction_after = tiling_dense_fraction(m, n, rp, ci, row_new2old->data(), col_old2new.data());
-    tick("sorts + tiling test (permuted)");
+    tick("tiling test (permuted)");
     S.seconds = time_since(t0);
     if (S.fraction_after < accept_fraction || S.fraction_after <= S.fraction_before) {
         row_new2old->clear();

@@ -28,16 +28,27 @@ bool locality_ordering(int m, int n, const int *rp, const int *ci, std::vector<i
 
 // Steps 1-3 of the method (reorder.cpp): Voronoi clusters, cluster graph, spectral order; pos_r / pos_c = the rank of a
 // node's cluster in (0, 1) (nodes no cluster reached keep their own relative index).  trp / tci: pattern of A^T.
+// lab_r_out / lab_c_out (optional): the cluster labels after the two majority rounds, -1 = unlabelled.
 void cluster_positions(int m, int n, const int *rp, const int *ci, const int *trp, const int *tci, std::vector<double> *pos_r,
-                       std::vector<double> *pos_c, ReorderStats *stats);
+                       std::vector<double> *pos_c, ReorderStats *stats, std::vector<int> *lab_r_out = nullptr,
+                       std::vector<int> *lab_c_out = nullptr);
+
+// pattern of A^T (counting sort, stable in row order)
+void transpose_pattern(int m, int n, const int *rp, const int *ci, std::vector<int> &trp, std::vector<int> &tci);
+
+// Step 4 and the argsorts of step 5 on the host, the sequence of device_refine_order: rank normalisation of pos_r, `sweeps` sweeps
+// (columns from rows, rows from columns, ranks after each half), the stable argsorts.  pos_r / pos_c hold the ranks on return.
+void refine_order(int m, int n, const int *rp, const int *ci, const int *trp, const int *tci, std::vector<double> &pos_r,
+                  std::vector<double> &pos_c, int sweeps, std::vector<int> *row_new2old, std::vector<int> *col_new2old);
 
 // Steps 2b-3 alone: directed cluster-to-cluster edge counts W[a] = {(b, count)}, sorted by b -> rank of every cluster in (0, 1).
 std::vector<double> cluster_order(int K, const std::vector<std::vector<std::pair<int, float>>> &W, ReorderStats *stats);
 
 // cluster_positions with the graph work on the device (level-synchronous Voronoi BFS, majority relabelling, edge counts by
 // radix sort + run lengths); only the K x K cluster graph comes back for cluster_order.  pos_r / pos_c: device arrays.
+// lab_r_out / lab_c_out (optional, HOST arrays of m / n): the labels after the two majority rounds, -1 = unlabelled.
 void device_cluster_positions(int m, int n, long nnz, const int *rp, const int *ci, const int *trp, const int *tci, double *pos_r,
-                              double *pos_c, ReorderStats *stats, hipStream_t s);
+                              double *pos_c, ReorderStats *stats, hipStream_t s, int *lab_r_out = nullptr, int *lab_c_out = nullptr);
 // the tiling test (tiling_dense_fraction) for device patterns; null permutations = the given order
 double device_tiling_dense_fraction(int m, int n, long nnz, const int *rp, const int *ci, const int *row_new2old,
                                     const int *col_new2old, hipStream_t s);

@@ -278,7 +278,7 @@ double device_tiling_dense_fraction(int m, int n, long nnz, const int *rp, const
 }
 
 void device_cluster_positions(int m, int n, long nnz, const int *rp, const int *ci, const int *trp, const int *tci, double *pos_r,
-                              double *pos_c, ReorderStats *st, hipStream_t s) {
+                              double *pos_c, ReorderStats *st, hipStream_t s, int *lab_r_out, int *lab_c_out) {
     ReorderStats local;
     ReorderStats &S = st ? *st : local;
     const long N = static_cast<long>(m) + n;
@@ -316,6 +316,8 @@ void device_cluster_positions(int m, int n, long nnz, const int *rp, const int *
         }
         HIP_CHECK(hipStreamSynchronize(s));
     }
+    if (lab_r_out) lab_r.download(lab_r_out, static_cast<size_t>(m));
+    if (lab_c_out) lab_c.download(lab_c_out, static_cast<size_t>(n));
     // ---- 2. cluster graph: one 32-bit key per entry, sorted, run lengths = directed edge counts
     std::vector<std::vector<std::pair<int, float>>> W(static_cast<size_t>(K));
     {

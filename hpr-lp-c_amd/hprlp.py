@@ -1243,6 +1243,78 @@ def value_maps_host(m, n, rowptr, colind, row_new2old=None, col_new2old=None):
     return a[:nnz].copy(), t[:nnz].copy()
 
 
+def _pattern(what, m, n, rowptr, colind):
+    rp, ci = _as(rowptr, np.int32), _as(colind, np.int32)
+    if rp.ndim != 1 or rp.shape[0] != m + 1:
+        raise ValueError(f"{what}: rowptr must have length {m + 1}, got shape {rp.shape}")
+    if ci.ndim != 1 or ci.shape[0] != int(rp[m]):
+        raise ValueError(f"{what}: colind must have length {int(rp[m])}, got shape {ci.shape}")
+    return rp, ci
+
+
+def _perms(what, m, n, row_new2old, col_new2old):
+    if (row_new2old is None) != (col_new2old is None):
+        raise ValueError(f"{what}: both permutations or neither")
+    if row_new2old is None:
+        return None, None
+    pr, pc = _as(row_new2old, np.int32), _as(col_new2old, np.int32)
+    if pr.shape != (m,) or pc.shape != (n,):
+        raise ValueError(f"{what}: the permutations must have length {m} and {n}")
+    return pr, pc
+
+
+def reorder_steps(m, n, rowptr, colind, device=False, sweeps=3):
+    """Test infrastructure (hprlp_reorder_steps): the locality ordering step by step on the host or on the device, without the
+    acceptance gates.  Returns a dict: lab_r / lab_c (labels after the majority rounds, -1 = unlabelled), pos0_r / pos0_c (cluster
+    positions), pos_r / pos_c (after the sweeps), row_new2old / col_new2old, clusters, components, bfs_levels, share_before,
+    share_after."""
+    rp, ci = _pattern("reorder_steps", m, n, rowptr, colind)
+    L = lib()
+    L.hprlp_reorder_steps.argtypes = [C.c_int, C.c_int, c_int_p, c_int_p, C.c_int, C.c_int, c_int_p, c_int_p] + [c_dbl_p] * 4 + \
+        [c_int_p, c_int_p, c_dbl_p]
+    out = dict(lab_r=np.zeros(m, np.int32), lab_c=np.zeros(n, np.int32), pos0_r=np.zeros(m), pos0_c=np.zeros(n), pos_r=np.zeros(m),
+               pos_c=np.zeros(n), row_new2old=np.zeros(m, np.int32), col_new2old=np.zeros(n, np.int32))
+    stats = np.zeros(5)
+    ptr = lambda a: a.ctypes.data_as(c_int_p if a.dtype == np.int32 else c_dbl_p)
+    if L.hprlp_reorder_steps(m, n, ptr(rp), ptr(ci), int(bool(device)), int(sweeps), *[ptr(out[k]) for k in out], ptr(stats)) != 0:
+        raise RuntimeError(last_error())
+    out.update(clusters=int(stats[0]), components=int(stats[1]), bfs_levels=int(stats[2]), share_before=float(stats[3]),
+               share_after=float(stats[4]))
+    return out
+
+
+def permute_csr_device(m, n, rowptr, colind, values, row_new2old, col_new2old):
+    """Test infrastructure (hprlp_permute_csr_device): (rowptr, colind, values) of P A Q as a solver's set-up forms it on the device."""
+    rp, ci = _pattern("permute_csr_device", m, n, rowptr, colind)
+    v = _as(values, np.float64)
+    if v.shape != ci.shape:
+        raise ValueError("permute_csr_device: one value per entry")
+    pr, pc = _perms("permute_csr_device", m, n, row_new2old, col_new2old)
+    if pr is None:
+        raise ValueError("permute_csr_device: the permutations are required")
+    L = lib()
+    L.hprlp_permute_csr_device.argtypes = [C.c_int, C.c_int, c_int_p, c_int_p, c_dbl_p, c_int_p, c_int_p, c_int_p, c_int_p, c_dbl_p]
+    orp, oci, ov = np.zeros(m + 1, np.int32), np.zeros(len(ci), np.int32), np.zeros(len(ci))
+    ip = lambda a: a.ctypes.data_as(c_int_p)
+    if L.hprlp_permute_csr_device(m, n, ip(rp), ip(ci), v.ctypes.data_as(c_dbl_p), ip(pr), ip(pc), ip(orp), ip(oci),
+                                  ov.ctypes.data_as(c_dbl_p)) != 0:
+        raise RuntimeError(last_error())
+    return orp, oci, ov
+
+
+def tiling_share(m, n, rowptr, colind, row_new2old=None, col_new2old=None, device=False):
+    """Test infrastructure (hprlp_tiling_share): the tiling test of a pattern as given or permuted, host or device form."""
+    rp, ci = _pattern("tiling_share", m, n, rowptr, colind)
+    pr, pc = _perms("tiling_share", m, n, row_new2old, col_new2old)
+    L = lib()
+    L.hprlp_tiling_share.argtypes = [C.c_int, C.c_int] + [c_int_p] * 4 + [C.c_int, c_dbl_p]
+    ip = lambda a: None if a is None else a.ctypes.data_as(c_int_p)
+    out = C.c_double(0.0)
+    if L.hprlp_tiling_share(m, n, ip(rp), ip(ci), ip(pr), ip(pc), int(bool(device)), C.byref(out)) != 0:
+        raise RuntimeError(last_error())
+    return out.value
+
+
 class Solver:
     """Step-level handle (include/hprlp_amd.h) used by the parity tests and bench.py."""
 
@@ -1963,6 +2035,15 @@ class Solver:
         r, c = np.zeros(max(self.model.m, 1), np.int32), np.zeros(max(self.model.n, 1), np.int32)
         rc = self._chk(lib().hprlp_solver_ordering(self.h, r.ctypes.data_as(c_int_p), c.ctypes.data_as(c_int_p)))
         return (r[:self.model.m], c[:self.model.n]) if rc == 1 else None
+
+    def power_start(self):
+        """Test infrastructure (hprlp_solver_power_start): the power iteration's start vector as the solver forms it, read back in
+        the caller's numbering."""
+        L = lib()
+        L.hprlp_solver_power_start.argtypes = [C.c_void_p, c_dbl_p, C.c_int]
+        z = np.zeros(max(self.model.m, 1))
+        k = self._chk(L.hprlp_solver_power_start(self.h, z.ctypes.data_as(c_dbl_p), len(z)))
+        return z[:k].copy()
 
     def certificate(self):
         """The certificate of the last run() (kind 0 without a verdict)."""

@@ -372,6 +372,9 @@ int hprlp_solver_transfer(hprlp_solver *s, long out[4]);
 long hprlp_solver_value_maps(hprlp_solver *s, int *mapA, int *mapAT, long cap);
 /* the locality ordering in place: row_new2old (m), col_new2old (n).  1: filled; 0: no ordering, arrays untouched; -1: error */
 int hprlp_solver_ordering(hprlp_solver *s, int *row_new2old, int *col_new2old);
+/* Test infrastructure: the power iteration's start vector as this solver forms it on the device, read back in the caller's
+ * numbering (m entries; behind a locality ordering the vector is defined in the caller's numbering).  Returns m. */
+int hprlp_solver_power_start(hprlp_solver *s, double *out, int cap);
 /* Host only, no GPU: the rule of the maps restated.  Without an ordering (both NULL) mapA is the identity and mapAT the
  * row-stable transpose's entry permutation; with one, mapA is the entry permutation of P A Q with every row's columns ascending
  * (ties in the caller's order) and mapAT that of its row-stable transpose. */
@@ -730,6 +733,24 @@ int hprlp_original_kkt(const LP_info_cpu *model, const double *x, const double *
  * like the reference's collect_solution (src/utils.cu:143-200).  out = {accepted, tiled share before, after, clusters,
  * components, seconds}. */
 int hprlp_locality_ordering(int m, int n, const int *rowptr, const int *col, int *row_new2old, int *col_new2old, double out[6]);
+/* Test infrastructure: the ordering step by step, on the host (on_device = 0: the functions of reorder.cpp) or on the device
+ * (1: the pattern is uploaded and goes through device_cluster_positions, device_refine_order and device_tiling_dense_fraction,
+ * the functions a solver's set-up calls), with `sweeps` refinement sweeps and NONE of the acceptance gates of
+ * hprlp_locality_ordering / a solver's set-up.  Every output may be NULL: lab_r (m) / lab_c (n) the cluster labels after the two
+ * majority rounds (-1 = unlabelled); pos0_r / pos0_c the positions before refinement (cluster positions); pos_r / pos_c the
+ * positions after the sweeps (ranks); row_new2old / col_new2old; stats = {clusters, components, BFS levels, tiling share
+ * before, after} by that side's own tiling test.  HPRLP_REORDER_CLUSTER (test hook) sizes the clusters on both sides. */
+int hprlp_reorder_steps(int m, int n, const int *rowptr, const int *col, int on_device, int sweeps, int *lab_r, int *lab_c,
+                        double *pos0_r, double *pos0_c, double *pos_r, double *pos_c, int *row_new2old, int *col_new2old,
+                        double stats[5]);
+/* Test infrastructure: P A Q as a solver's set-up forms it on the device (device_permute_csr): rows in the new order, the
+ * entries of a row by new column, duplicates in their old order.  rp_out (m + 1), ci_out / val_out (nnz). */
+int hprlp_permute_csr_device(int m, int n, const int *rowptr, const int *col, const double *val, const int *row_new2old,
+                             const int *col_new2old, int *rp_out, int *ci_out, double *val_out);
+/* Test infrastructure: the tiling test -- share of the entries in (row / 8192, column / 2048) pairs of at least 256 entries --
+ * of a pattern as given (both permutations NULL) or permuted, by the host's or the device's form. */
+int hprlp_tiling_share(int m, int n, const int *rowptr, const int *col, const int *row_new2old, const int *col_new2old,
+                       int on_device, double *share);
 /* host only: the stream kernel's row blocks of a CSR pattern, built and checked as a solver's set-up does (dense rows cut by
  * column eighths when with_cuts != 0); out = {blocks, split rows, chunk slots, rows cut, longest chunk, entries covered};
  * -1 + hprlp_last_error() when the block list would be refused. */

@@ -167,7 +167,7 @@ else:   # tiled forms: a banded matrix
     A = sparse.csr_matrix((v, ci, rp), shape=(m, n)); A.sum_duplicates(); A.sort_indices()
     lp = gen(m, n, 0, 23, A=A)
 model = model_of(lp)
-by_value = form != "reordered"   # (1.6 M rows: the certificate's numbers by value are left to the other forms)
+by_value = form != "reordered"   # (1.6 M rows; a reordered solver's certificate at a small shape: tests/test_gpu_reorder_small.py, bit twin)
 prm = hprlp.Parameters(max_iter=50000, use_presolve=False, use_CR_scaling=not by_value)
 s = hprlp.Solver(model, prm)
 d, info = s.describe(), s.info()

@@ -6,7 +6,9 @@ derived bound of that module and nothing wider.  Every LP carries every bound ki
 iterate comparisons with the oracle also run the coded-bound paths (finite nonzero l, -0.0, l = u, ranged and free rows).
 
 Forms: the hook sets of tests/test_gpu_detect.py: FORM_ENV at the smallest shapes existing tests show selecting them
-(evalcases.CASES).  The REORDERED form needs 1.6 M rows and is left to tests/test_gpu_reorder.py.
+(evalcases.CASES).  The REORDERED form runs these kernels on P A Q; its part is the permutation at the boundary, which
+tests/test_gpu_reorder_small.py checks bit for bit against a solver on the explicitly permuted LP (residuals and weighted_norm
+included, under HPRLP_REORDER_ANYWAY at 20 011 x 26 003); tests/test_gpu_reorder.py keeps the 1.6 M shape of the default thresholds.
 
 The variant-identity tests pin the switches documented as "the same bits": HPRLP_STORE_X, HPRLP_NO_BOUND_CODES,
 HPRLP_NO_FAR_PUSH.  The solver exposes eleven state vectors (NAMES_N + NAMES_M); all of them are compared."""

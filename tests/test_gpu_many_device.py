@@ -324,7 +324,8 @@ def test_a_member_off_the_small_path_and_a_group_of_one(gpu):
 
 
 def test_a_member_with_a_locality_ordering(gpu):
-    """No hook forces an ordering at a small shape, so this is the suite's one reordered shape (a randomly permuted banded
+    """The group's reordered member at the default thresholds (HPRLP_REORDER_ANYWAY, the hook of tests/test_gpu_reorder_small.py,
+    is a single solver's matter), so this is the suite's large reordered shape (a randomly permuted banded
     1 600 000 x 1 600 000 matrix, 10 per row; tests/test_gpu_many_values.py) between two small members that join: new data and a
     re-solve from a start, against the member's own *_tensors calls."""
     from scipy import sparse

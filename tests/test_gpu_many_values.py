@@ -5,7 +5,8 @@ the arithmetic or its order: every member must be bit for bit where its own hprl
 fresh solver on the changed model after scale().  So every assertion on results below is == or np.array_equal; nothing has a
 tolerance.  (Of scalars() the three wall times are left out: they are clock readings, not results.)
 
-A member with a locality ordering needs the suite's one reordered shape (1.6 M rows: no hook forces an ordering at a small one); it
+A member with a locality ordering runs at the suite's large reordered shape (1.6 M rows, the default thresholds; a single solver's
+ordering at a small shape under HPRLP_REORDER_ANYWAY is tests/test_gpu_reorder_small.py, the group's reordered member is not forced there); it
 has a test of its own (about two seconds on an MI355X)."""
 import ctypes as C
 
@@ -290,8 +291,8 @@ def test_who_joins(gpu):
 
 
 def test_a_member_with_a_locality_ordering_goes_its_own_way(gpu):
-    """4, the ordered member: no hook forces an ordering at a small shape, so this is the one shape the suite's other reordered
-    cases use (a randomly permuted banded 1 600 000 x 1 600 000 matrix, 10 per row; tests/test_gpu_matrix_values.py), between two
+    """4, the ordered member, at the default thresholds (the group's reordered member is not run under HPRLP_REORDER_ANYWAY, the
+    hook of tests/test_gpu_reorder_small.py): the one shape the suite's other large reordered cases use (a randomly permuted banded 1 600 000 x 1 600 000 matrix, 10 per row; tests/test_gpu_matrix_values.py), between two
     small members that join.  Its values travel in the group's block and pass the group's check, then it runs its own call."""
     from conftest import lpgen
     m = n = 1_600_000

@@ -13,7 +13,9 @@ it get, for that step, the kind that keeps them out of the maximum: no iterates 
 evaluator with that line (or one entry of it) left out, and for the sums the evaluator with the wrong bound side, is shown to be
 farther than the tolerance from the GPU's number: the comparison can see the fault it is there for.  No vector here is
 kThreads * kReduceBlocks = 131072 long, so k_ray_form's grid-stride loops take one trip; their targets are index 0 and the last.
-The REORDERED form (1.6 M rows) is left to tests/test_gpu_reorder.py, which checks the permutation of the four vector names.
+The REORDERED form: tests/test_gpu_reorder_small.py holds the nine scalars and the four ray vectors of a solver with a locality
+ordering (HPRLP_REORDER_ANYWAY, 20 011 x 26 003) to a solver on the explicitly permuted LP, bit for bit; tests/test_gpu_reorder.py
+checks the permutation of the four vector names at 1.6 M rows.
 
 A step writes nothing but its own buffers (the eleven state vectors keep their bits, later iterations are those of a solver that
 never stepped), and a later run() with detection starts clean.

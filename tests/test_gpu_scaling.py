@@ -13,7 +13,9 @@ clamp, the scaling pass that also leaves Ruiz pass 0 its norms, and the Ruiz, Po
      residual evaluation lies within tests/evalref.py's bound -- a tiled copy refreshed too early or not at all shows here.
 
 Every case asserts its kernel form from describe() and prints its largest ratios.  LOG_ULP and EXP_ULP of scaleref are measured by
-the first test.  The group form, the reordered form, sharded solvers and set_matrix re-scaling have their own tests."""
+the first test.  The group form, the reordered form (tests/test_gpu_reorder_small.py: the scaled data and matrix values of a solver
+with a locality ordering against a solver on the explicitly permuted LP, bit for bit, Curtis-Reid on), sharded solvers and set_matrix
+re-scaling have their own tests."""
 import numpy as np
 import pytest
 

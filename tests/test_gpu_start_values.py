@@ -7,7 +7,9 @@ is x_bar . z_bar, which the start replaces by the bound terms.)
 
 Forms and LPs: the eight entries of evalcases.CASES -- every column and row bound kind, -0.0, l = u, ranged and free rows -- at the
 smallest shapes at which each form is selected.  The starts are startref.case_start (tests/test_startref.py shows on the CPU that
-they reach every branch, and that the deliberately wrong starts lie outside the tolerance).
+they reach every branch, and that the deliberately wrong starts lie outside the tolerance).  The reordered form adds only the gather
+of the caller's x0 / y0 through the ordering's permutation: tests/test_gpu_reorder_small.py holds a warm start of a solver with a
+locality ordering to one on the explicitly permuted LP, bit for bit.
 
 Per case: the start with x0 and y0, with either missing and with neither (a null x0 still projects 0 into [l, u]); the same start
 after seven iterations and a check step gives every vector and number the bits of the first time (invalidate_far on the tiled
