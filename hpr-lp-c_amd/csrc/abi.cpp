@@ -1716,10 +1716,11 @@ extern "C" int hprlp_last_solve_many_phases(double out[8]) {
     return 0;
 }
 
-// hprlp_solve_many and hprlp_solve_many_detect (`who`, for the error messages).  det null: no detection.  certs (may be null):
+// hprlp_solve_many, hprlp_solve_many_detect and hprlp_solve_many_wide (`who`, for the error messages; wide: every member is marked
+// wide before the group's scaling).  det null: no detection.  certs (may be null):
 // count entries, each cleared to its member's m and n on entry (hprlp_solve_detect's contract) and filled where detection ran.
 static int solve_many_entry(const LP_info_cpu *const *models, int count, const HPRLP_parameters *param, const hprlp_detection *det,
-                            HPRLP_results *out, hprlp_certificate *certs, const char *who_) {
+                            HPRLP_results *out, hprlp_certificate *certs, const char *who_, bool wide = false) {
     GUARD_BEGIN
     const std::string w(who_);
     if (!models) throw std::runtime_error(w + ": null model list");
@@ -1765,6 +1766,7 @@ static int solve_many_entry(const LP_info_cpu *const *models, int count, const H
     g_many_phases[0] = time_since(t_setup);
     for (int k = 0; k < count; ++k)
         if (owned[k]) {
+            owned[k]->s.group_wide = wide;  // (hprlp_solve_many_wide: every member asks for the group launches)
             s.push_back(&owned[k]->s);
             who.push_back(k);
         }
@@ -1798,9 +1800,11 @@ static int solve_many_entry(const LP_info_cpu *const *models, int count, const H
                 if (with_det) s[g]->detect = dsel;
             }
             g_many_phases[2] = time_since(t_pw);
+            const WideCounts pw = last_wide_counts();
             const auto t_loop = time_now();
             GroupCounts gc;
             run_many(s.data(), ng, res.data(), &gc);
+            if (wide) last_wide_counts().power_launches = pw.power_launches, last_wide_counts().power_waits = pw.power_waits;
             g_many_phases[3] = time_since(t_loop);  // (the loop and the solutions' way back)
             g_many_phases[5] = static_cast<double>(gc.rounds);
             g_many_phases[6] = static_cast<double>(gc.waits);
@@ -1833,6 +1837,31 @@ extern "C" int hprlp_solve_many_detect(const LP_info_cpu *const *models, int cou
     return solve_many_entry(models, count, param, det, out, certs, "hprlp_solve_many_detect");
 }
 
+// ---- wide members (many.cpp; DESIGN.md "Many small LPs", wide members) -------------------------------------------------------
+extern "C" int hprlp_solver_set_group_wide(hprlp_solver *h, int on) {
+    GUARD_BEGIN
+    if (!h) throw std::runtime_error("hprlp_solver_set_group_wide: null solver");
+    if (h->sharded)
+        throw std::runtime_error("hprlp_solver_set_group_wide: a sharded solver (hprlp_solver_create_dist* / _local*) joins no group; a group runs on one GPU");
+    h->s.group_wide = on != 0;
+    if (h->s.use_small && !h->s.comm) return 1;  // (it joins anyway)
+    return on != 0 && h->s.joins_group() ? 1 : 0;
+    GUARD_END(-1)
+}
+
+extern "C" int hprlp_solve_many_wide(const LP_info_cpu *const *models, int count, const HPRLP_parameters *param, const hprlp_detection *det,
+                                     HPRLP_results *out, hprlp_certificate *certs) {
+    return solve_many_entry(models, count, param, det, out, certs, "hprlp_solve_many_wide", true);
+}
+
+extern "C" int hprlp_last_many_wide_counts(long out[8]) {
+    if (!out) return -1;
+    const WideCounts &wc = last_wide_counts();
+    const long v[8] = {wc.joined, wc.refused, wc.normal_launches, wc.segments, wc.member_iterations, wc.power_launches, wc.power_waits, 0};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return 0;
+}
+
 namespace {
 struct VecRef {
     double *p;
@@ -1860,6 +1889,9 @@ VecRef find_vector(Solver &s, const std::string &name) {
     if (name == "col_norm") return {s.col_norm.p, s.n_loc, 'c'};
     if (name == "A_val") return {s.A.val.p, s.A.view.nnz, '-'};
     if (name == "AT_val") return {s.AT.val.p, s.AT.view.nnz, '-'};
+    // the power iteration's two scratch vectors (the scaling's gathered ones), this rank's slices: zero between the phases
+    if (name == "gsm") return {s.gsm.p + s.row_off, s.m_loc, 'r'};
+    if (name == "gsn") return {s.gsn.p + s.col_off, s.n_loc, 'c'};
     if (s.ray_prev_x.p) {  // the ray test's vectors, once Solver::ray_begin has allocated them (scaled units)
         if (name == "ray_d") return {s.ray_d.p, s.n_loc, 'c'};
         if (name == "ray_prev_x") return {s.ray_prev_x.p, s.n_loc, 'c'};

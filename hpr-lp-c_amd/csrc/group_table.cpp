@@ -90,7 +90,33 @@ const std::vector<GroupLaunch> &GroupTable::finish() {
     return list_;
 }
 
+int group_iteration_plan(const int *counts, int n, std::vector<int> &len, std::vector<int> &min_count) {
+    std::vector<int> c;
+    for (int k = 0; k < n; ++k)
+        if (counts[k] > 0) c.push_back(counts[k]);
+    std::sort(c.begin(), c.end());
+    c.erase(std::unique(c.begin(), c.end()), c.end());
+    int before = 0;
+    for (int v : c) {
+        len.push_back(v - before);
+        min_count.push_back(v);
+        before = v;
+    }
+    return static_cast<int>(c.size());
+}
+
 }  // namespace hprlp
+
+extern "C" int hprlp_group_iteration_plan(const int *counts, int n, int *seg_len, int *seg_min_count, int cap) {
+    if (n < 0 || cap < 0 || (n > 0 && !counts) || (cap > 0 && (!seg_len || !seg_min_count))) return -1;
+    for (int k = 0; k < n; ++k)
+        if (counts[k] < 0) return -1;
+    std::vector<int> len, min_count;
+    const int segs = hprlp::group_iteration_plan(counts, n, len, min_count);
+    if (segs > cap) return -1;
+    for (int j = 0; j < segs; ++j) seg_len[j] = len[j], seg_min_count[j] = min_count[j];
+    return segs;
+}
 
 // Checks, numbered: 1 every table and map offset is a multiple of 16; 2 tables and maps do not overlap and lie inside the block;
 // 3 grids {3, 0, 2} give the map (0,0) (0,1) (0,2) (2,0) (2,1) and 5 workgroups; 4 a kind with one task takes no table under the
@@ -102,7 +128,11 @@ const std::vector<GroupLaunch> &GroupTable::finish() {
 // and the kinds of a stage are issued in ascending order (the form ahead of the two products that gather what it writes); 11 the
 // check stage of a group's device entries (the check of the members' vectors and, for new matrix values, the check of the values:
 // two mapped kinds with one task per member in ONE stage): two launches whatever the number of members, on the sum of the
-// members' own grids, and a group of one issues the member's own two launches and sends no table.
+// members' own grids, and a group of one issues the member's own two launches and sends no table; 12 group_iteration_plan: counts
+// {7, 6, 0, 7, 149} give the segments 6, 1, 142 at 6, 7, 149, every member is in the first segments without a gap and their lengths
+// add up to its count, and counts that are all zero give no segment; 13 the normal iterations of wide members: per segment the
+// x-half's stage and the y-half's stage repeated `len` times from one table each, a segment with one member as its own launches,
+// the check step's stage behind them.
 extern "C" int hprlp_group_table_selftest(void) {
     using namespace hprlp;
     struct Task {
@@ -238,6 +268,55 @@ extern "C" int hprlp_group_table_selftest(void) {
         if (list.size() != 2 || list[0].kind != kDataCheck || list[1].kind != kValuesCheck || list[0].stage != 0 || list[1].stage != 0) return 11;
         if (list[0].own != lone || list[1].own != lone || (lone ? block != 0 : block == 0)) return 11;
         if (!lone && (list[0].nwg != 8 || list[1].nwg != 8 || list[0].ntasks != 5 || list[0].tasks == list[1].tasks)) return 11;
+    }
+    {   // ---- 12, 13
+        const int counts[5] = {7, 6, 0, 7, 149};
+        std::vector<int> len, at;
+        if (group_iteration_plan(counts, 5, len, at) != 3) return 12;
+        const int want_len[3] = {6, 1, 142}, want_at[3] = {6, 7, 149};
+        for (int j = 0; j < 3; ++j)
+            if (len[j] != want_len[j] || at[j] != want_at[j]) return 12;
+        for (int k = 0; k < 5; ++k) {  // (a member's segments are the first ones, without a gap, and add up to its count)
+            int sum = 0;
+            bool out = false;
+            for (int j = 0; j < 3; ++j) {
+                const bool in = counts[k] >= at[j];
+                if (in && out) return 12;
+                out = !in;
+                if (in) sum += len[j];
+            }
+            if (sum != counts[k]) return 12;
+        }
+        len.clear(), at.clear();
+        const int none[2] = {0, 0};
+        if (group_iteration_plan(none, 2, len, at) != 0 || !len.empty()) return 12;
+        // the two stages of a segment's iteration (x-half, y-half: each kind alone in its stage) issued len times from one table
+        // each, segment after segment, with the check step's stage behind them
+        enum { kXn = 0, kYn = 1, kXc = 2 };
+        GroupTable g(true, 512, 256);
+        const int seg_len[2] = {6, 1};
+        for (int j = 0; j < 2; ++j) {
+            g.note(kXn);
+            g.next_stage();
+            g.note(kYn);
+            g.next_stage();
+            g.repeat_last(2, seg_len[j]);
+        }
+        g.note(kXc);
+        if (g.recorded_launches() != 2 * 7 + 1) return 13;
+        g.begin();
+        const int gr[2] = {3, 2};
+        const Odd o2[2] = {{1, 2, 3}, {4, 5, 6}};
+        g.add(0, kXn, kGridMapped, o2, sizeof(Odd), 2, gr, false);
+        g.add(1, kYn, kGridMapped, o2, sizeof(Odd), 2, gr, false);
+        g.add(2, kXn, kGridMapped, o2, sizeof(Odd), 1, gr, true);  // (the second segment holds one member: its own launches)
+        g.add(3, kYn, kGridMapped, o2, sizeof(Odd), 1, gr, true);
+        g.add(4, kXc, kGridMapped, o2, sizeof(Odd), 2, gr, false);
+        const std::vector<GroupLaunch> list = g.finish();
+        if (list.size() != 15) return 13;
+        for (int i = 0; i < 12; ++i)
+            if (list[i].stage != i % 2 || list[i].own || list[i].nwg != 5 || list[i].tasks != list[i % 2].tasks) return 13;
+        if (list[12].stage != 2 || !list[12].own || list[13].stage != 3 || !list[13].own || list[14].stage != 4 || list[14].own) return 13;
     }
     return 0;
 }

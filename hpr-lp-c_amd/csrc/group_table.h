@@ -63,6 +63,16 @@ class GroupTable {
     std::vector<GroupLaunch> list_;
 };
 
+// The normal iterations of a round as SEGMENTS (many.cpp: wide members; DESIGN.md "Many small LPs", wide members).  Members of one
+// round owe different numbers of iterations (a restart costs one, max_iter cuts the last round, iterate_many takes any counts).
+// With c_1 < ... < c_J the distinct positive counts and c_0 = 0, segment j runs c_j - c_{j-1} iterations with the members whose
+// count is >= c_j: every member runs its own count, in a row, and the members of a segment share its launches.  len[j] and
+// min_count[j] = c_j are appended in ascending order; a count <= 0 is in no segment.  Returns J.
+int group_iteration_plan(const int *counts, int n, std::vector<int> &len, std::vector<int> &min_count);
+
 }  // namespace hprlp
 
 extern "C" int hprlp_group_table_selftest(void);  // 0, or the number of the check that failed
+// group_iteration_plan through plain arrays of `cap` entries each.  Returns the number of segments, or -1: a null array, n < 0, a
+// negative count, or more segments than cap.
+extern "C" int hprlp_group_iteration_plan(const int *counts, int n, int *seg_len, int *seg_min_count, int cap);

@@ -408,6 +408,16 @@ class GroupLaunches {
     GroupLaunches(const GroupLaunches &) = delete;
     void x_half_check(const CsrDev &AT, const XHalfArgs &a);
     void y_half_check(const CsrDev &A, const YHalfArgs &a);
+    // Wide members (DESIGN.md "Many small LPs", wide members).  The normal half-steps as launch_x_half / launch_y_half issue them on
+    // a matrix without a tiled copy (a.x_mode 0, no hand-off; anything else is refused): the caller closes the stage after each,
+    // the y-half gathers what the x-half stores.  The regular-kernel power iteration: launch_pw_normalize, launch_spmv_push with an
+    // empty hand-off, launch_spmv_plain with the two dots, launch_pw_err on kReduceBlocks workgroups -- a stage each.
+    void x_half(const CsrDev &AT, const XHalfArgs &a);
+    void y_half(const CsrDev &A, const YHalfArgs &a);
+    void pw_normalize(const double *z, double *q, int m, const double *scalars);
+    void pw_err(const double *z, const double *q, int m, const double *scalars, double *partials);  // kReduceBlocks partials
+    void spmv_push(const CsrDev &M, const double *v_full, double *out);
+    void spmv_dots(const CsrDev &M, const double *v_full, double *out, const double *q, double *partials, int stride);
     void resid_d(const CsrDev &AT, const double *ybar_full, const double *c, const double *z_bar, const double *col_norm, double *partials);
     void resid_p(const CsrDev &A, const double *xbar_full, const double *xtemp_full, const double *AL, const double *AU, const double *row_norm,
                  const double *y_temp, bool with_gap, double *partials, int stride);

@@ -2811,25 +2811,32 @@ void launch_pw_start(int m, unsigned long long seed, long long offset, double *z
     if (m > 0) hipLaunchKernelGGL(k_pw_start, dim3((m + kThreads - 1) / kThreads), dim3(kThreads), 0, s, m, seed, offset, z);
 }
 
-__global__ void __launch_bounds__(kThreads) k_pw_normalize(const double *z, double *q, int m, const double *scalars) {
+// (the bodies take the workgroup's index and the launch's grid: the group forms run them as workgroup bid of the member's own grid)
+__device__ __forceinline__ void pw_normalize_body(const double *z, double *q, int m, const double *scalars, int bid, int grid) {
     const double invn = 1.0 / sqrt(scalars[S_PW_ZZ] + 2.220446049250313e-16);
-    const int tid = blockIdx.x * kThreads + threadIdx.x, nth = gridDim.x * kThreads;
+    const int tid = bid * kThreads + threadIdx.x, nth = grid * kThreads;
     for (int i = tid; i < m; i += nth) q[i] = invn * z[i];
+}
+__global__ void __launch_bounds__(kThreads) k_pw_normalize(const double *z, double *q, int m, const double *scalars) {
+    pw_normalize_body(z, q, m, scalars, blockIdx.x, gridDim.x);
 }
 void launch_pw_normalize(const double *z, double *q, int m, const double *scalars, hipStream_t s) {
     hipLaunchKernelGGL(k_pw_normalize, dim3(vec_grid(m)), dim3(kThreads), 0, s, z, q, m, scalars);
 }
 
-__global__ void __launch_bounds__(kThreads) k_pw_err(const double *z, const double *q, int m, const double *scalars,
-                                                    double *partials) {
+__device__ __forceinline__ void pw_err_body(const double *z, const double *q, int m, const double *scalars, double *partials, int bid, int grid) {
     const double lambda = scalars[S_PW_QZ];
     double acc[1] = {0.0};
-    const int tid = blockIdx.x * kThreads + threadIdx.x, nth = gridDim.x * kThreads;
+    const int tid = bid * kThreads + threadIdx.x, nth = grid * kThreads;
     for (int i = tid; i < m; i += nth) {
         const double d = -lambda * q[i] + 1.0 * z[i];
         acc[0] += d * d;
     }
-    block_store_partials<1>(acc, partials, gridDim.x);
+    block_store_partials_at<1>(acc, partials, grid, bid);
+}
+__global__ void __launch_bounds__(kThreads) k_pw_err(const double *z, const double *q, int m, const double *scalars,
+                                                    double *partials) {
+    pw_err_body(z, q, m, scalars, partials, blockIdx.x, gridDim.x);
 }
 void launch_pw_err(const double *z, const double *q, int m, const double *scalars, double *partials, int nblocks,
                    hipStream_t s) {
@@ -3201,6 +3208,19 @@ __global__ void __launch_bounds__(kThreads) k_spmv_fused_many(const GroupTask<Ep
     Epi epi = tasks[w.x].epi;
     spmv_fused_body<Epi>(A, epi, w.y, A.csr_grid());
 }
+// The normal half-steps of wide members (XEpi<false>, YEpi<false>) run thousands of times per solve.  Compiled as the template
+// above they take 82 VGPRs (the task's pointers are generic ones: flat accesses) -- one wave per SIMD fewer than the 80 of
+// k_spmv_fused<XEpi<false>> allow, the optimum of DESIGN.md section 3.  The same body under a request for six waves per SIMD:
+// the register allocator stays within 80, without scratch (the resource remarks are in DESIGN.md, wide members).  Register
+// allocation only: the instructions on values are the body's.
+template <class Epi>
+__global__ void __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(6, 6)))
+k_spmv_fused_many_six(const GroupTask<Epi> *__restrict__ tasks, const int2 *__restrict__ wgmap) {
+    const int2 w = wgmap[blockIdx.x];
+    const CsrStream A = tasks[w.x].A;
+    Epi epi = tasks[w.x].epi;
+    spmv_fused_body<Epi>(A, epi, w.y, A.csr_grid());
+}
 
 struct FinalizeOne {  // one item of k_finalize; a stage's items that are one member's and at most 8 are its own launch_finalize
     static constexpr GridRule rule = kGridPerTask;
@@ -3322,6 +3342,29 @@ struct CopyTask {
         if (i < n) dst[i] = src[i];
     }
     int own_grid() const { return elem_grid(n); }
+};
+// The regular-kernel power iteration of wide members (DESIGN.md "Many small LPs", wide members; many.cpp: power_iteration_many):
+// k_pw_normalize on the member's vec_grid, k_pw_err on its kReduceBlocks workgroups; the two products are GroupTask<PlainPushEpi>
+// and GroupTask<PlainEpi<true>>, the initial |z|^2 is ReduceTask<false>.
+struct PwNormalizeTask {
+    static constexpr GridRule rule = kGridMapped;
+    const double *z;
+    double *q;
+    int m;
+    const double *scalars;
+    int grid;  // of the member's own launch (vec_grid)
+    __device__ void run(int lb) const { pw_normalize_body(z, q, m, scalars, lb, grid); }
+    int own_grid() const { return grid; }
+    void own(hipStream_t s) const { launch_pw_normalize(z, q, m, scalars, s); }
+};
+struct PwErrTask {
+    static constexpr GridRule rule = kGridReduce;
+    const double *z, *q;
+    int m;
+    const double *scalars;
+    double *partials;
+    __device__ void run(int lb) const { pw_err_body(z, q, m, scalars, partials, lb, kReduceBlocks); }
+    void own(hipStream_t s) const { launch_pw_err(z, q, m, scalars, partials, kReduceBlocks, s); }
 };
 struct DataInTask {
     static constexpr GridRule rule = kGridReduce;
@@ -3451,6 +3494,14 @@ template <class Epi>
 struct GroupKernel<GroupTask<Epi>> {
     static constexpr auto pick() { return &k_spmv_fused_many<Epi>; }
 };
+template <>
+struct GroupKernel<GroupTask<XEpi<false>>> {
+    static constexpr auto pick() { return &k_spmv_fused_many_six<XEpi<false>>; }
+};
+template <>
+struct GroupKernel<GroupTask<YEpi<false>>> {
+    static constexpr auto pick() { return &k_spmv_fused_many_six<YEpi<false>>; }
+};
 template <bool R, bool D, bool N>
 struct GroupKernel<ScaleMatTask<R, D, N>> {
     static constexpr auto pick() { return &k_scale_matrix_many<R, D, N>; }
@@ -3532,10 +3583,20 @@ struct KindList {
 // AT_val, the gather reads the staging block and writes AL, AU, l, u and c, the fills write the iterates, the work vectors, the
 // scalars and ctrl -- three disjoint sets of arrays, none of which another of the three reads, so their order is no statement
 // either; scaling, which reads all of them, begins a stage later.
+//   wide members (normal iterations):  the normal x-half, the normal y-half.  The y-half gathers the x_hat the x-half stores and
+//             the next x-half gathers the y the y-half stores, so many.cpp records every half-step as a stage of its own
+//             (GroupLaunches::x_half / y_half, then next_stage()): each of the two kinds is ALONE in its stage, and its place in
+//             this list is no statement.
+//   wide members (power iteration):  k_pw_normalize, A^T q, A (A^T q) with the two dots, k_pw_err.  Each of the four reads what
+//             the one before it wrote (q; the gathered A^T q; z and, through the finalize items, the slots S_PW_ZZ / S_PW_QZ), so
+//             each is recorded as a stage of its own as well; a stage's finalize items come last, as everywhere.  The initial
+//             |z|^2 is the plain reduction of the scaling line, again in a stage of its own.
 using GroupKinds = KindList<DataCheckTask, ValuesCheckTask, ValuesInTask, VectorsInTask, RowNormTask<false>, RowNormTask<true>, GroupTask<CrEpi>, VecTask, CodesTask<false>, CodesTask<true>, RestartCopyTask, SetCtrlTask,
                             StartInTask, GroupTask<StartColEpi>, GroupTask<StartRowEpi>, GroupTask<XEpi<true>>, GroupTask<YEpi<true>>,
+                            GroupTask<XEpi<false>>, GroupTask<YEpi<false>>,
                             GroupTask<RdEpi>, GroupTask<RpEpi<false>>, GroupTask<RpEpi<true>>, GroupTask<GapEpi>, RayFormTask, GroupTask<RayColEpi>,
-                            GroupTask<RayRowEpi>, CopyTask, GroupTask<PlainEpi<false>>, LuTask, MovementTask, DataInTask, DataBcTask, UnscaleTask, ScaleMat<0>, ScaleMat<1>, ScaleMat<2>, ScaleMat<3>, ScaleMat<4>, ScaleMat<5>, ScaleMat<6>,
+                            GroupTask<RayRowEpi>, CopyTask, GroupTask<PlainEpi<false>>, PwNormalizeTask, GroupTask<PlainPushEpi>, GroupTask<PlainEpi<true>>, PwErrTask,
+                            LuTask, MovementTask, DataInTask, DataBcTask, UnscaleTask, ScaleMat<0>, ScaleMat<1>, ScaleMat<2>, ScaleMat<3>, ScaleMat<4>, ScaleMat<5>, ScaleMat<6>,
                             ScaleMat<7>, ReduceTask<true>, ReduceTask<false>, FinalizeOne>;
 
 struct GroupLaunches::Impl {
@@ -3606,6 +3667,30 @@ void GroupLaunches::x_half_check(const CsrDev &AT, const XHalfArgs &a) {
 void GroupLaunches::y_half_check(const CsrDev &A, const YHalfArgs &a) {
     YEpi<true> e{{a.xhat_full}, a.y, a.AL, a.AU, a.last_y, a.y_bar, a.y_obj, a.y_temp, a.ctrl, a.partials, a.stride, 0, 0, 0, 0, FarPush{}, a.row_code};
     impl->rec<GroupTask<YEpi<true>>>().push_back({stream_part(A), e});
+}
+// The normal half-steps, built as launch_x_half / launch_y_half build them for a matrix without a tiled copy: x_mode 0 and no
+// hand-off (stream_part refuses every other matrix).
+void GroupLaunches::x_half(const CsrDev &AT, const XHalfArgs &a) {
+    if (a.x_mode != 0 || a.push.gptr) throw std::runtime_error("group normal x-half: an x_mode or a hand-off belongs to the tiled kernels");
+    XEpi<false> e{{a.y_full}, a.x, a.x_hat, a.l, a.u, a.c, a.last_x, nullptr, nullptr, nullptr, a.ctrl, nullptr, 0, 0, 0, 0, FarPush{}, a.lu_code};
+    impl->rec<GroupTask<XEpi<false>>>().push_back({stream_part(AT), e});
+}
+void GroupLaunches::y_half(const CsrDev &A, const YHalfArgs &a) {
+    if (a.push.gptr) throw std::runtime_error("group normal y-half: a hand-off belongs to the tiled kernels");
+    YEpi<false> e{{a.xhat_full}, a.y, a.AL, a.AU, a.last_y, nullptr, nullptr, nullptr, a.ctrl, nullptr, 0, 0, 0, 0, 0, FarPush{}, a.row_code};
+    impl->rec<GroupTask<YEpi<false>>>().push_back({stream_part(A), e});
+}
+void GroupLaunches::pw_normalize(const double *z, double *q, int m, const double *scalars) {
+    impl->rec<PwNormalizeTask>().push_back({z, q, m, scalars, vec_grid(m)});
+}
+void GroupLaunches::pw_err(const double *z, const double *q, int m, const double *scalars, double *partials) {
+    impl->rec<PwErrTask>().push_back({z, q, m, scalars, partials});
+}
+void GroupLaunches::spmv_push(const CsrDev &M, const double *v_full, double *out) {
+    impl->rec<GroupTask<PlainPushEpi>>().push_back({stream_part(M), PlainPushEpi{{v_full}, out, FarPush{}}});
+}
+void GroupLaunches::spmv_dots(const CsrDev &M, const double *v_full, double *out, const double *q, double *partials, int stride) {
+    impl->rec<GroupTask<PlainEpi<true>>>().push_back({stream_part(M), PlainEpi<true>{{v_full}, out, q, partials, stride}});
 }
 void GroupLaunches::resid_d(const CsrDev &AT, const double *ybar_full, const double *c, const double *z_bar, const double *col_norm,
                             double *partials) {

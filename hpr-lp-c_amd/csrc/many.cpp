@@ -13,6 +13,9 @@
 // (set_matrix_values_many) share scale_many's walk of Solver::scale() (scale_walk).  Each of the three group entries for new data,
 // re-solve and new values has a twin with the vectors in the caller's device memory (DESIGN.md "Many small LPs", group device
 // re-solve): the two share their steps, one body per pair where the arrangement allows (the second half of this file).
+// A member off the small path that asked for it (Solver::group_wide; DESIGN.md "Many small LPs", wide members) joins the group
+// launches all the same: its normal iterations run as recorded segments of the group kinds of the normal half-steps
+// (record_normal), its power iteration's regular path in group launches (power_wide).
 //
 // Ordering is by stream: for the duration of a call every member works on ONE stream (the first member's), after its own stream
 // has been waited for once; the members' streams come back at exit, after one wait for the group's.
@@ -24,6 +27,7 @@
 
 #include "many.h"
 #include "group_pack.h"
+#include "group_table.h"
 #include "values.h"
 
 namespace hprlp {
@@ -59,10 +63,107 @@ struct GroupScope {
 
 bool on_small_path(const Solver *s) { return s->use_small && !s->comm; }
 
+thread_local WideCounts g_wide;
+
+// The normal iterations counts[i] of the wide members who[i], recorded: segment by segment (group_table.h: group_iteration_plan)
+// the x-halves of the segment's members as one stage, their y-halves as the next, the two issued `len` times from one table each.
+// A member's iterations follow each other in the order of its own launches; a segment with one member goes through that member's
+// own k_spmv_fused launches (the recorder's own-launch rule).  The caller records the check steps behind them.
+void record_normal(Solver **s, const std::vector<int> &who, const std::vector<int> &counts, GroupLaunches &gl) {
+    if (who.size() == 1) {
+        // One wide member in the whole round (a group of one, or the last one still running): what it issues alone, its graph
+        // replays, at once -- everything recorded for it so far has run, and its check step, recorded next, runs behind them.
+        // (Enqueued one by one the same iterations cost 0.025 s against 0.018 s per 2000: profiles/many_wide_ab.txt, K = 1.)
+        s[who[0]]->run_normal(counts[0]);
+        return;
+    }
+    std::vector<int> len, at;
+    const int segs = group_iteration_plan(counts.data(), static_cast<int>(counts.size()), len, at);
+    for (int j = 0; j < segs; ++j) {
+        long members = 0;
+        for (int half = 0; half < 2; ++half) {
+            for (size_t i = 0; i < who.size(); ++i)
+                if (counts[i] >= at[j]) {
+                    s[who[i]]->normal_half(half == 1, gl);
+                    members += half;
+                }
+            gl.next_stage();  // (the y-half gathers what the x-half stores, the next x-half what the y-half stores)
+        }
+        gl.repeat_last(2, len[j]);
+        g_wide.normal_launches += 2L * len[j];
+        ++g_wide.segments;
+        g_wide.member_iterations += members * len[j];
+    }
+}
+
 std::vector<char> who_joins(Solver **s, int count) {
     std::vector<char> j(static_cast<size_t>(count));
     for (int k = 0; k < count; ++k) j[k] = s[k]->joins_group() ? 1 : 0;
     return j;
+}
+
+// Solver::power_iteration's regular path for the wide members `who` (two at least, all joining) in group launches.  The pieces are
+// the member's own (Solver::power_norm / power_piece / power_err), a stage each: every one reads what the one before it wrote.
+// A block is ten iterations -- three stages recorded once, issued ten times -- and the error terms, then one copy of the scalars and
+// one wait for all members; each member's stopping test is its own, and a member that stopped is in no later block.  What is
+// left of a max_iter that is no multiple of ten runs as the member's own path runs it: single iterations, no error terms, no
+// fetch.  lambda is the last fetched one (1.0 if there was no block), as alone.
+void power_wide(Solver **s, const std::vector<int> &who, int max_iter, double tol, double *lambda_out, int *iters_out, hipStream_t st,
+                clock_type::time_point t0) {
+    GroupLaunches gl;
+    for (int k : who) {
+        Solver &m = *s[k];
+        m.finish_tiling();
+        m.invalidate_far();
+        m.power_start(m.sm1.p);
+        m.power_norm(&gl);
+        if (lambda_out) lambda_out[k] = 1.0;
+    }
+    gl.next_stage();
+    std::vector<int> active = who, next;
+    auto record_iterations = [&](int times) {
+        for (int piece = 0; piece < 3; ++piece) {
+            for (int k : active) s[k]->power_piece(piece, &gl);
+            gl.next_stage();
+        }
+        gl.repeat_last(3, times);
+    };
+    int i = 0;
+    for (; !active.empty() && i + 10 <= max_iter; i += 10) {
+        record_iterations(10);
+        for (int k : active) {
+            s[k]->power_err(&gl);
+            gl.pack(s[k]->scal.p, s[k]->scal_h.p);
+        }
+        g_wide.power_launches += gl.run(st);
+        g_wide.power_launches += gl.fetch(st);  // (the packing kernel)
+        HIP_CHECK(hipStreamSynchronize(st));
+        ++g_wide.power_waits;
+        gl.deliver();
+        next.clear();
+        for (int k : active) {
+            Solver &m = *s[k];
+            ++m.fetches;
+            if (lambda_out) lambda_out[k] = m.scal_h[S_PW_QZ];
+            if (std::sqrt(m.scal_h[S_PW_ERR2]) < tol) m.power_iters = i + 10;
+            else next.push_back(k);
+        }
+        active.swap(next);
+    }
+    if (!active.empty() && i < max_iter) record_iterations(max_iter - i);
+    for (int k : active) s[k]->power_iters = max_iter;
+    if (gl.recorded_launches() > 0) g_wide.power_launches += gl.run(st);
+    // leave the scratch vectors clean
+    for (int k : who) {
+        HIP_CHECK(hipMemsetAsync(s[k]->gsm.p, 0, sizeof(double) * s[k]->m_pad, st));
+        HIP_CHECK(hipMemsetAsync(s[k]->gsn.p, 0, sizeof(double) * s[k]->n_pad, st));
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+    ++g_wide.power_waits;
+    for (int k : who) {
+        s[k]->power_time = time_since(t0);  // the group's wall time
+        if (iters_out) iters_out[k] = s[k]->power_iters;
+    }
 }
 
 // what has been recorded and enqueued, then the one copy of the scalars, the wait and each member's scalars into its host block
@@ -179,7 +280,14 @@ void check_group(Solver *const *s, int count, const char *who, bool need_scaled)
         for (int j = 0; j < k; ++j)
             if (s[j] == s[k]) throw std::runtime_error(w + ": members " + std::to_string(j) + " and " + std::to_string(k) + " are the same solver");
     }
+    // (the call goes on: its wide members, for hprlp_last_many_wide_counts)
+    WideCounts wc;
+    for (int k = 0; k < count; ++k)
+        if (s[k]->group_wide && !on_small_path(s[k])) ++(s[k]->joins_group() ? wc.joined : wc.refused);
+    if (wc.joined + wc.refused > 0) g_wide = wc;
 }
+
+WideCounts &last_wide_counts() { return g_wide; }
 
 void scale_many(Solver **s, int count, SetupCounts *counts) {
     check_group(s, count, "scale_many", false);
@@ -244,6 +352,14 @@ void power_iteration_many(Solver **s, int count, int max_iter, double tol, doubl
             done[k] = 1;
         }
     }
+    // ---- wide members that join: the regular path in group launches (a group of one issues the member's own launches below)
+    std::vector<int> wide;
+    for (int k = 0; k < count; ++k)
+        if (!on_small_path(s[k]) && s[k]->joins_group()) wide.push_back(k);
+    if (wide.size() >= 2) {
+        power_wide(s, wide, max_iter, tol, lambda_out, iters_out, scope.group, t0);
+        for (int k : wide) done[k] = 1;
+    }
     for (int k = 0; k < count; ++k) {
         if (done[k]) continue;
         int it = 0;
@@ -267,14 +383,20 @@ void iterate_many(Solver **s, int count, const int *normal, bool then_check) {
     }
     SmallTaskBuf buf;
     launch_small_iterations_many(tasks.data(), static_cast<int>(tasks.size()), buf, scope.group);
-    for (int k = 0; k < count; ++k)
-        if (!on_small_path(s[k])) s[k]->run_normal(normal[k]);
-    if (then_check) {
-        const std::vector<char> joins = who_joins(s, count);
-        GroupLaunches gl;
-        for (int k = 0; k < count; ++k) s[k]->step(true, joins[k] ? &gl : nullptr);
-        gl.run(scope.group);
+    const std::vector<char> joins = who_joins(s, count);
+    // (wide members that join: their iterations recorded in segments, the check steps behind them; everybody else off the small path
+    // on their own)
+    std::vector<int> wide, wide_counts;
+    for (int k = 0; k < count; ++k) {
+        if (on_small_path(s[k])) continue;
+        if (joins[k] && normal[k] > 0) wide.push_back(k), wide_counts.push_back(normal[k]);
+        else if (!joins[k]) s[k]->run_normal(normal[k]);
     }
+    GroupLaunches gl;
+    record_normal(s, wide, wide_counts, gl);
+    if (then_check)
+        for (int k = 0; k < count; ++k) s[k]->step(true, joins[k] ? &gl : nullptr);
+    gl.run(scope.group);
     HIP_CHECK(hipStreamSynchronize(scope.group));
 }
 
@@ -378,7 +500,7 @@ void loop_many(Solver **s, int count, HPRLP_results *out, GroupCounts &gc, Group
     for (int k = 0; k < count; ++k) s[k]->loop_begin(&ls[k], &out[k], joins[k] ? &gl : nullptr);
     SmallTaskBuf buf;
     std::vector<SmallIterTask> tasks;
-    std::vector<int> flagged, verdicts;
+    std::vector<int> flagged, verdicts, wide, wide_counts;
     std::vector<PackMember> cm;  // the certificate block of a round with verdicts: device, and pinned
     DBuf<double> cert_d;
     HBuf<double> cert_h;
@@ -475,21 +597,27 @@ void loop_many(Solver **s, int count, HPRLP_results *out, GroupCounts &gc, Group
             run_fetch_wait(gl, scope.group, gc);
             for (int k : flagged) ++s[k]->fetches;
         }
-        // 10: the normal iterations of all small-path members, one launch per class
+        // 10: the normal iterations of all small-path members, one launch per class; those of the wide members that join, recorded
+        // in segments (they run with the check steps, in front of the next round's evaluation)
         tasks.clear();
+        wide.clear();
+        wide_counts.clear();
         for (int k = 0; k < count; ++k) {
             if (!active[k]) continue;
             s[k]->loop_plan(&ls[k]);  // (a restart's weighted norm consumed: the rare lambda bump inside is the member's own launch)
-            if (on_small_path(s[k]) && ls[k].pending > 0) tasks.push_back(SmallIterTask{s[k]->small_args(), 0, ls[k].pending});
+            if (ls[k].pending <= 0) continue;
+            if (on_small_path(s[k])) tasks.push_back(SmallIterTask{s[k]->small_args(), 0, ls[k].pending});
+            else if (joins[k]) wide.push_back(k), wide_counts.push_back(ls[k].pending);
         }
         const int it_launches = launch_small_iterations_many(tasks.data(), static_cast<int>(tasks.size()), buf, scope.group);
         gc.launches += it_launches;
         gc.group_launches += it_launches;
+        record_normal(s, wide, wide_counts, gl);
         // 11: the check step: recorded for the members of the group launches (it runs in front of the next round's evaluation,
-        // same stream); members off the small path run their normal iterations first
+        // same stream); members outside them run their normal iterations first
         for (int k = 0; k < count; ++k) {
             if (!active[k]) continue;
-            s[k]->loop_advance(&ls[k], on_small_path(s[k]), joins[k] ? &gl : nullptr);
+            s[k]->loop_advance(&ls[k], on_small_path(s[k]) || joins[k], joins[k] ? &gl : nullptr);
             if (!joins[k] && ls[k].pending >= 0) ++gc.own;
         }
         gl.next_stage();  // (the evaluation's Rd overwrites the partials the check step's finalize reads)

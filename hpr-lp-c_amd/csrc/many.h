@@ -23,6 +23,17 @@ struct SetupCounts {
     long device_allocs = 0, pinned_allocs = 0, h2d_copies = 0, scale_launches = 0, scale_waits = 0, served = 0, own = 0, device_frees = 0;
 };
 
+// Wide members (DESIGN.md "Many small LPs", wide members): solvers off the small path with Solver::group_wide set.  What the
+// calling thread's last group call with such a member did (hprlp_last_many_wide_counts): wide members that join the group launches
+// / that cannot (a tiled copy, split rows); launches of the normal iterations issued through the group's recorder, two per
+// iteration of a segment whatever the number of its members; segments (group_table.h: group_iteration_plan); member-iterations
+// served by them; launches of the group power iteration (the packing of the scalars included) and its host waits.
+// check_group zeroes the block and fills the first two slots whenever it sees a wide member.
+struct WideCounts {
+    long joined = 0, refused = 0, normal_launches = 0, segments = 0, member_iterations = 0, power_launches = 0, power_waits = 0;
+};
+WideCounts &last_wide_counts();  // (hprlp_solve_many_wide adds its power iteration to its loop)
+
 // Throws (before anything is launched) unless s[0..count) are distinct, non-null, scaled, unsharded solvers on one device.
 // need_scaled = false: a solver never scaled is welcome (scale_many).
 void check_group(Solver *const *s, int count, const char *who, bool need_scaled = true);
@@ -32,10 +43,16 @@ void check_group(Solver *const *s, int count, const char *who, bool need_scaled 
 // inside the same call, and so does a group with fewer than two joining members.  Every member ends bit for bit where its own
 // scale() leaves it.
 void scale_many(Solver **s, int count, SetupCounts *counts = nullptr);
-// lambda (not x 1.01) and iteration count per member; small-path members in one launch per class, the others on their own
+// lambda (not x 1.01) and iteration count per member; small-path members in one launch per class.  Wide members that join (two at
+// least): the regular path of Solver::power_iteration in group launches -- ten iterations and the error terms recorded once and
+// issued as one run, one copy of the scalars and one wait per block for all of them, each member's own stopping test on the host
+// (a member that stopped is in no later block), the tail of a max_iter that is no multiple of ten as single iterations without
+// error terms, the two scratch vectors zeroed: lambda, iteration count and power_iters are the member's own.  Everybody else on
+// their own.
 void power_iteration_many(Solver **s, int count, int max_iter, double tol, double *lambda_out, int *iters_out);
-// normal[k] normal iterations of member k (small-path members together), then one check step each if then_check (the group's check
-// launches for the members that join them); waits at the end
+// normal[k] normal iterations of member k (small-path members together; wide members that join in segments of group launches, two
+// launches per iteration of a segment), then one check step each if then_check (the group's check launches for the members that
+// join them); waits at the end
 void iterate_many(Solver **s, int count, const int *normal, bool then_check);
 // Solver::compute_residuals for every member: out[8 * k ..] as hprlp_solver_residuals.  Group launches for the members that join
 // them and have iter[k] > 0; one copy of the scalars, one wait.

@@ -1519,11 +1519,84 @@ void Solver::power_start(double *z) {
     }
 }
 
+// The pieces of the regular path: z in sm1, q in gsm, A^T q in gsn.  g records them for the group launches of wide members
+// (many.cpp: power_iteration_many), which have neither a tiled copy nor an exchange: no hand-off, no gather, no all-reduce.
+void Solver::power_norm(GroupLaunches *g) {
+    double *z = sm1.p;
+    FinalizeArgs f0{};
+    f0.n = 1;
+    f0.item[0] = {part_v.p, kReduceBlocks, S_PW_ZZ};
+    if (g) {
+        g->norm2(z, m_loc, part_v.p);
+        g->finalize(f0, scal.p);
+        return;
+    }
+    launch_norm2(z, m_loc, part_v.p, kReduceBlocks, stream);
+    launch_finalize(f0, scal.p, stream);
+    allreduce_slots(this, S_PW_ZZ, 1);
+}
+
+bool Solver::power_piece(int piece, GroupLaunches *g, bool handed) {
+    double *q = gsm.p + row_off, *ATq = gsn.p + col_off, *z = sm1.p;
+    if (piece == 0) {
+        if (g) {
+            g->pw_normalize(z, q, m_loc, scal.p);
+            return false;
+        }
+        launch_pw_normalize(z, q, m_loc, scal.p, stream);
+        gather(gsm.p, true);
+        return false;
+    }
+    if (piece == 1) {
+        if (g) {
+            g->spmv_push(AT.view, gsm.p, ATq);
+            return false;
+        }
+        // A^T q: its epilogue writes the products A's remainder needs (hand-off, as between the half-steps; A then runs without a
+        // pre-pass) -- where the remainder is a large part of A.  With a few per cent of the entries in it the pre-pass is the
+        // cheaper way since round 4: config 5 (5 %), same box: push 104 us of the launch against 64 us of k_far_products, power
+        // iteration 0.385 -> 0.374 s
+        const bool push_pays = A.view.tiled.valid && static_cast<double>(A.tiled.n_rem) >= 0.3 * static_cast<double>(A.view.nnz);
+        const bool h = launch_spmv_push(AT.view, gsm.p, ATq, push_pays ? push_into(A, AT) : FarPush{}, stream);
+        gather(gsn.p, false);
+        return h;
+    }
+    const int gridA = A.view.grid();
+    FinalizeArgs f{};
+    f.n = 2;
+    f.item[0] = {part_y.p, gridA, S_PW_ZZ};
+    f.item[1] = {part_y.p + stride_y, gridA, S_PW_QZ};
+    if (g) {
+        g->spmv_dots(A.view, gsn.p, z, q, part_y.p, stride_y);
+        g->finalize(f, scal.p);
+        return false;
+    }
+    launch_spmv_plain(A.view, gsn.p, z, q, true, part_y.p, stride_y, stream, handed);
+    launch_finalize(f, scal.p, stream);
+    allreduce_slots(this, S_PW_ZZ, 2);
+    return false;
+}
+
+void Solver::power_err(GroupLaunches *g) {
+    double *q = gsm.p + row_off, *z = sm1.p;
+    FinalizeArgs fe{};
+    fe.n = 1;
+    fe.item[0] = {part_v.p, kReduceBlocks, S_PW_ERR2};
+    if (g) {
+        g->pw_err(z, q, m_loc, scal.p, part_v.p);
+        g->finalize(fe, scal.p);
+        return;
+    }
+    launch_pw_err(z, q, m_loc, scal.p, part_v.p, kReduceBlocks, stream);
+    launch_finalize(fe, scal.p, stream);
+    allreduce_slots(this, S_PW_ERR2, 1);
+}
+
 double Solver::power_iteration(int max_iter, double tol, int *iters) {
     finish_tiling();
     invalidate_far();
     const auto t0 = time_now();
-    double *q = gsm.p + row_off, *ATq = gsn.p + col_off, *z = sm1.p;
+    double *z = sm1.p;  // (q in gsm, A^T q in gsn: the pieces below)
     power_start(z);
     if (small_power_wanted()) {
         // Netlib-scale LP: the whole power iteration in one launch of the single-workgroup kernel (small.hip), stopping test on
@@ -1545,42 +1618,16 @@ double Solver::power_iteration(int max_iter, double tol, int *iters) {
         if (verbose) std::cerr << "[hprlp] single-launch power iteration returned lambda = " << lambda_dev << " after " << done_dev
                                << " iterations: falling back to the regular kernels" << std::endl;
     }
-    launch_norm2(z, m_loc, part_v.p, kReduceBlocks, stream);
-    FinalizeArgs f0{};
-    f0.n = 1;
-    f0.item[0] = {part_v.p, kReduceBlocks, S_PW_ZZ};
-    launch_finalize(f0, scal.p, stream);
-    allreduce_slots(this, S_PW_ZZ, 1);
+    power_norm();
 
     double lambda = 1.0;
     int done = max_iter;
-    const int gridA = A.view.grid();
     auto one_iteration = [&]() {
-        launch_pw_normalize(z, q, m_loc, scal.p, stream);
-        gather(gsm.p, true);
-        // A^T q: its epilogue writes the products A's remainder needs (hand-off, as between the half-steps; A then runs without a
-        // pre-pass) -- where the remainder is a large part of A.  With a few per cent of the entries in it the pre-pass is the
-        // cheaper way since round 4: config 5 (5 %), same box: push 104 us of the launch against 64 us of k_far_products, power
-        // iteration 0.385 -> 0.374 s
-        const bool push_pays = A.view.tiled.valid && static_cast<double>(A.tiled.n_rem) >= 0.3 * static_cast<double>(A.view.nnz);
-        const bool handed = launch_spmv_push(AT.view, gsm.p, ATq, push_pays ? push_into(A, AT) : FarPush{}, stream);
-        gather(gsn.p, false);
-        launch_spmv_plain(A.view, gsn.p, z, q, true, part_y.p, stride_y, stream, handed);
-        FinalizeArgs f{};
-        f.n = 2;
-        f.item[0] = {part_y.p, gridA, S_PW_ZZ};
-        f.item[1] = {part_y.p + stride_y, gridA, S_PW_QZ};
-        launch_finalize(f, scal.p, stream);
-        allreduce_slots(this, S_PW_ZZ, 2);
+        power_piece(0);
+        const bool handed = power_piece(1);
+        power_piece(2, nullptr, handed);
     };
-    auto error_terms = [&]() {
-        launch_pw_err(z, q, m_loc, scal.p, part_v.p, kReduceBlocks, stream);
-        FinalizeArgs fe{};
-        fe.n = 1;
-        fe.item[0] = {part_v.p, kReduceBlocks, S_PW_ERR2};
-        launch_finalize(fe, scal.p, stream);
-        allreduce_slots(this, S_PW_ERR2, 1);
-    };
+    auto error_terms = [&]() { power_err(); };
     // One rank: the ten iterations between two stopping tests are one graph launch (about 50 kernels; enqueued one by one the
     // launches of config 5 leave 0.2 ms of every 1.45 ms iteration idle, on config 3 the iteration is launch-bound altogether).
     hipGraphExec_t block = nullptr;
@@ -1636,7 +1683,7 @@ void Solver::set_sigma_lambda(double sigma_, double lambda_, bool reset_k, Group
 }
 
 bool Solver::joins_group() {
-    if (!use_small || comm) return false;
+    if (!(use_small || group_wide) || comm) return false;
     finish_tiling();
     return group_form_fits(A.view) && group_form_fits(AT.view);
 }
@@ -1765,12 +1812,28 @@ int Solver::x_mode_of(int i, int count) const {
     return (i > 0 ? kXRebuild : 0) | (i + 1 < count ? kXNoStore : 0);
 }
 
-void Solver::launch_normal_pair(bool more_follow, hipEvent_t *ev, int x_mode) {
+XHalfArgs Solver::normal_x_args(int x_mode) {
     XHalfArgs xa{gy.p, x.p, x_hat, l.p, u.p, c.p, last_x.p, nullptr, nullptr, nullptr, ctrl.p, nullptr, 0};
     xa.lu_code = lu_code.p;
     xa.x_mode = x_mode;
-    YHalfArgs ya{gxh.p, y, AL.p, AU.p, last_y.p, nullptr, nullptr, nullptr, ctrl.p, nullptr, 0};  // (push / far_ready set below)
+    return xa;
+}
+
+YHalfArgs Solver::normal_y_args() {
+    YHalfArgs ya{gxh.p, y, AL.p, AU.p, last_y.p, nullptr, nullptr, nullptr, ctrl.p, nullptr, 0};  // (push / far_ready: the caller's)
     ya.row_code = row_code.p;
+    return ya;
+}
+
+// (a wide member has neither tiled copies nor an exchange: x_mode_of gives 0, push_into nothing, the gathers do nothing)
+void Solver::normal_half(bool y_half, GroupLaunches &g) {
+    if (y_half) g.y_half(A.view, normal_y_args());
+    else g.x_half(AT.view, normal_x_args(0));
+}
+
+void Solver::launch_normal_pair(bool more_follow, hipEvent_t *ev, int x_mode) {
+    XHalfArgs xa = normal_x_args(x_mode);
+    YHalfArgs ya = normal_y_args();
     if (ev) HIP_CHECK(hipEventRecord(ev[0], stream));
     if (!overlap_enabled) {
         xa.push = push_into(A, AT);

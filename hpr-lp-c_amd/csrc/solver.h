@@ -173,6 +173,9 @@ struct Solver {
     int power_iters = 0;
     bool use_graph = true;
     bool use_small = false;  // Netlib-scale LP on one GPU: normal iterations run in the single-workgroup kernel (small.hip)
+    // hprlp_solver_set_group_wide: off the small path this solver asks for the group launches of the *_many entries all the same
+    // (joins_group; DESIGN.md "Many small LPs", wide members).  Nothing outside those entries reads it.
+    bool group_wide = false;
     int max_row_A = 0, max_row_AT = 0;
     DBuf<int> small_order_x, small_order_y;  // rows of A^T / A sorted by length (row ownership in small.hip)
     DBuf<int> small_ij, small_posA;          // per A^T entry: i | j << 16, position in the CSR order of A
@@ -326,9 +329,22 @@ struct Solver {
     void update_sigma_and_restart(RestartState *rs, const Residuals &r);
     void movement_launch(GroupLaunches *g);                         // the movement and its two norms, not fetched
     void restart_launch(RestartState *rs, const Residuals &r, GroupLaunches *g);  // movement fetched: the sigma rule, restart copy, ctrl
-    // Check step, evaluation and restart run in the group launches (many.cpp): small path, and both matrices run the stream kernel
-    // alone (no tiled copy, no split rows).  Adopts a pending tiled copy first.
+    // Check step, evaluation and restart run in the group launches (many.cpp): small path or group_wide, one GPU, and both matrices
+    // run the stream kernel alone (no tiled copy, no split rows).  Adopts a pending tiled copy first.
     bool joins_group();
+    // the arguments of one normal iteration's half-steps, as launch_normal_pair issues them without an exchange in flight
+    XHalfArgs normal_x_args(int x_mode);
+    YHalfArgs normal_y_args();
+    // One normal half-step of a wide member recorded (y_half: the second one); the caller closes the stage behind it.
+    void normal_half(bool y_half, GroupLaunches &g);
+    // The pieces of power_iteration's regular path (g: recorded; the caller closes the stage behind each piece):
+    //   power_norm   |z|^2 of the start vector and its finalize
+    //   power_piece  0: q = z / |z|;  1: A^T q (true: it handed A's remainder products over -- never with g);  2: z = A (A^T q)
+    //                with the two dots and their finalize (handed: what piece 1 returned)
+    //   power_err    |z - lambda q|^2 and its finalize
+    void power_norm(GroupLaunches *g = nullptr);
+    bool power_piece(int piece, GroupLaunches *g = nullptr, bool handed = false);
+    void power_err(GroupLaunches *g = nullptr);
     void solve_loop(HPRLP_results *out);                            // src/HPRLP.cu:154-310
     // the pieces of solve_loop (LoopState)
     void loop_begin(LoopState *ls, HPRLP_results *out, GroupLaunches *g = nullptr);  // (g: ray_begin's zeroing recorded)

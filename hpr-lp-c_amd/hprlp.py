@@ -261,6 +261,12 @@ def lib():
         L.hprlp_solve_many_detect.argtypes = [C.POINTER(C.POINTER(CLPInfo)), C.c_int, C.POINTER(CParameters), C.POINTER(CDetection),
                                               C.POINTER(CResults), C.POINTER(CCertificate)]
         L.hprlp_solver_ray_step_many.argtypes = [C.POINTER(C.c_void_p), C.c_int, c_int_p, c_dbl_p, c_int_p]
+    if hasattr(L, "hprlp_solver_set_group_wide"):  # (likewise: the A side of tools/many_wide_ab.py)
+        L.hprlp_solver_set_group_wide.argtypes = [C.c_void_p, C.c_int]
+        L.hprlp_solve_many_wide.argtypes = [C.POINTER(C.POINTER(CLPInfo)), C.c_int, C.POINTER(CParameters), C.POINTER(CDetection),
+                                            C.POINTER(CResults), C.POINTER(CCertificate)]
+        L.hprlp_last_many_wide_counts.argtypes = [C.POINTER(C.c_long)]
+        L.hprlp_group_iteration_plan.argtypes = [c_int_p, C.c_int, c_int_p, c_int_p, C.c_int]
     if hasattr(L, "hprlp_solver_create_many"):  # (likewise)
         L.hprlp_solver_create_many.argtypes = [C.POINTER(C.POINTER(CLPInfo)), C.c_int, C.POINTER(CParameters), C.POINTER(C.c_void_p)]
         L.hprlp_solver_scale_many.argtypes = [C.POINTER(C.c_void_p), C.c_int]
@@ -624,6 +630,50 @@ def solve_many_detect(models, param=None, eps_primal=1e-8, eps_dual=1e-8):
     for r, k in zip(results, certificates):
         r.certificate = k
     return results, certificates
+
+
+def solve_many_wide(models, param=None, eps_primal=None, eps_dual=None):
+    """solve_many_detect with every member wide (hprlp_solve_many_wide): a model past the single-workgroup size iterates in the
+    group launches instead of issuing its own launches inside the lock-step (Solver.set_group_wide; DESIGN.md "Many small LPs",
+    wide members).  Same bits per member as Model.solve without presolve.  Detection is off unless eps_primal / eps_dual are
+    given.  Returns (results, certificates) as solve_many_detect."""
+    models = list(models)
+    if not models:
+        raise ValueError("solve_many_wide: no models")
+    cp = (param or Parameters()).to_c()
+    det = _detection_arg(eps_primal, eps_dual)
+    ptrs = (C.POINTER(CLPInfo) * len(models))(*[mod._ptr for mod in models])
+    res = (CResults * len(models))()
+    ccs = (CCertificate * len(models))()
+    if lib().hprlp_solve_many_wide(ptrs, len(models), C.byref(cp), C.byref(det) if det is not None else None, res, ccs) < 0:
+        raise RuntimeError(last_error())
+    results = [Results(res[k], mod.m, mod.n) for k, mod in enumerate(models)]
+    certificates = [Certificate(ccs[k]) for k in range(len(models))]
+    for r, k in zip(results, certificates):
+        r.certificate = k
+    return results, certificates
+
+
+MANY_WIDE_KEYS = ("joined", "refused", "normal_launches", "segments", "member_iterations", "power_launches", "power_waits")
+
+
+def last_many_wide_counts():
+    """Counts of this thread's last *_many call that had a wide member (hprlp_last_many_wide_counts): wide members that joined
+    the group launches / that could not, the group launches of their normal iterations (two per iteration of a segment), the
+    segments, the member-iterations they served, the group launches of the power iteration and its host waits."""
+    out = (C.c_long * 8)()
+    lib().hprlp_last_many_wide_counts(out)
+    return dict(zip(MANY_WIDE_KEYS, [int(v) for v in out]))
+
+
+def group_iteration_plan(counts, cap=None):
+    """The segments of a round's normal iterations (hprlp_group_iteration_plan; no GPU needed): [(length, min_count), ...], or
+    None where the library refuses (a negative count, more segments than cap)."""
+    cnt = _as(counts, np.int32).reshape(-1)
+    cap = len(cnt) if cap is None else int(cap)
+    ln, at = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32)
+    n = lib().hprlp_group_iteration_plan(cnt.ctypes.data_as(c_int_p), len(cnt), ln.ctypes.data_as(c_int_p), at.ctypes.data_as(c_int_p), cap)
+    return None if n < 0 else [(int(ln[j]), int(at[j])) for j in range(n)]
 
 
 def last_solve_many_phases():
@@ -1593,8 +1643,8 @@ class Solver:
 
     @staticmethod
     def power_iteration_many(solvers, max_iter=5000, tol=1e-4):
-        """power_iteration() of every solver, small-path members in one launch per kernel class
-        (hprlp_solver_power_iteration_many).  Returns [(lambda, iterations), ...]."""
+        """power_iteration() of every solver, small-path members in one launch per kernel class, wide members (set_group_wide)
+        through group launches of the regular kernels (hprlp_solver_power_iteration_many).  Returns [(lambda, iterations), ...]."""
         solvers, hs = Solver._handles(solvers)
         lam = np.zeros(max(len(solvers), 1))
         its = np.zeros(max(len(solvers), 1), dtype=np.int32)
@@ -1606,7 +1656,7 @@ class Solver:
     @staticmethod
     def iterate_many(solvers, normals, then_check=False):
         """iterate(normals[k], then_check) of every solver, the normal iterations of small-path members in one launch per
-        kernel class (hprlp_solver_iterate_many)."""
+        kernel class, those of wide members (set_group_wide) in group launches, two per iteration (hprlp_solver_iterate_many)."""
         solvers, hs = Solver._handles(solvers)
         cnt = _as(normals, np.int32)
         if cnt.ndim != 1 or cnt.shape[0] != len(solvers):
@@ -1651,6 +1701,12 @@ class Solver:
         if lib().hprlp_solver_run_many(hs, len(solvers), res) < 0:
             raise RuntimeError(last_error())
         return [Results(res[k], sv.model.m, sv.model.n) for k, sv in enumerate(solvers)]
+
+    def set_group_wide(self, on=True):
+        """Let this solver, off the small path, join the group launches of the *_many calls (hprlp_solver_set_group_wide).  True:
+        it will join; False: the setting is stored but it cannot (a tiled copy, rows past 4096 entries) and goes its own way.  A
+        small-path solver joins anyway (True); a sharded solver raises."""
+        return self._chk(lib().hprlp_solver_set_group_wide(self.h, int(bool(on)))) == 1
 
     def set_detection(self, eps_primal=1e-8, eps_dual=1e-8, on=True):
         """Infeasibility detection for the following run() calls (hprlp_solver_set_detection); on=False switches it off."""

@@ -464,6 +464,57 @@ int hprlp_last_solve_many_phases(double out[8]);
  * certificates collected through the group's block (a round with such a verdict adds one wait and one copy)} */
 int hprlp_last_run_many_counts(long out[8]);
 
+/* ---- wide members: solvers past the single-workgroup size iterate as a group (DESIGN.md "Many small LPs", wide members) -------
+ * Off the small path (nnz >= 12 288, m or n > 2 048, a row or column longer than 256) a member of a *_many call issues its own
+ * launches inside the lock-step, serialised on the group's stream.  A solver marked wide joins the group launches instead: its
+ * normal iterations run in group launches of k_spmv_fused_many (two launches per iteration for all such members of a round, in
+ * segments where their iteration counts differ), its regular-kernel power iteration in group launches as well (ten iterations and
+ * the error terms per host wait for all of them), and check step, evaluation, restart, ray test, certificate, scaling, new data,
+ * re-solve and new matrix values in the group kinds the small-path members use -- those run a member's own grid at any size.
+ * Every member still gets the bits of its own solve.  Opt-in, per solver; without it every path is what it was.
+ * Where it pays (profiles/many_wide_ab.txt: one MI355X, K resident solvers, 2000 iterations each, run_many with the setting on
+ * against run_many without it, median of three rounds, spreads below 4 %): 2500 x 4000 with 15 000 entries: 2.9 x at K = 4,
+ * 9.1 x at K = 16, 18.6 x at K = 64; 20 000 x 30 000 with 150 000 entries: 2.0 x at K = 4, 3.4 x at K = 16; 33 874 x 105 728 with
+ * 230 000 entries (the largest size measured): 1.16 x at K = 2, 1.51 x at K = 4, 1.86 x at K = 8 (the largest K measured there).
+ * With ONE wide member in a call the member runs its own path and nothing is gained or lost (1.00 at K = 1 on all three shapes);
+ * no point was measured at which the setting loses.  The power iteration of the same groups: 1.1 x to 3.8 x.  A member with a
+ * tiled copy (from 458 752 columns on, where the kernel-form rules try one) or with a row past 4096 entries cannot join. */
+/* Let a solver off the small path join the group launches of the *_many entries ("wide" member).
+ * on = 0 switches it off.
+ * Returns 1 when the solver will join, 0 when the setting is stored but the solver cannot join, -1 + hprlp_last_error().
+ * A solver cannot join when a matrix of it has a tiled copy or rows past kSplitRow (4096 entries).
+ * Such a solver keeps going its own way, as today.
+ * A sharded solver is refused with -1.
+ * A small-path solver returns 1: it joins anyway, and the setting changes nothing for it.
+ * Waits for a tiled copy that is still being built (the answer depends on it).
+ * It pays from two wide members in a call on, more the smaller the members and the larger K: 18.6 x at 2500 x 4000 and K = 64,
+ * 1.86 x at 33 874 x 105 728 and K = 8, the largest size and K measured; with one wide member it changes nothing (figures above). */
+int hprlp_solver_set_group_wide(hprlp_solver *s, int on);
+
+/* hprlp_solve_many_detect with every member wide.
+ * det == NULL: no detection.
+ * certs may be NULL. */
+int hprlp_solve_many_wide(const LP_info_cpu *const *models, int count, const HPRLP_parameters *param,
+                          const hprlp_detection *det, HPRLP_results *out, hprlp_certificate *certs);
+
+/* The calling thread's last *_many call that had a wide member (a solver off the small path with the setting on; a call without
+ * one leaves the block as it is).  hprlp_solve_many_wide reports its loop, with its power iteration's two slots.
+ * out = {wide members that joined,
+ *        wide members that could not,
+ *        normal-iteration group launches (two per iteration of a segment),
+ *        iteration segments,
+ *        member-iterations served by them,
+ *        group launches of the power iteration,
+ *        its host waits,
+ *        0} */
+int hprlp_last_many_wide_counts(long out[8]);
+
+/* The segments of a round's normal iterations (wide members), no GPU needed.  counts[0..n): iterations owed per member, >= 0.
+ * With c_1 < ... < c_J the distinct positive counts and c_0 = 0, segment j runs seg_len[j] = c_j - c_{j-1} iterations with the
+ * members whose count is >= seg_min_count[j] = c_j.  Both arrays hold cap entries.  Returns J, or -1: a null array, n < 0, a
+ * negative count, more than cap segments. */
+int hprlp_group_iteration_plan(const int *counts, int n, int *seg_len, int *seg_min_count, int cap);
+
 /* ---- group re-solve: new data, starts and solutions for the whole group (DESIGN.md "Many small LPs", group re-solve) ----------
  * The callers of a group -- scenario sets, MPC horizons, search-tree nodes -- change c and the bounds of K resident solvers and
  * solve again, over and over.  The two entries below are hprlp_solver_set_data and hprlp_solver_resolve for every member, with
