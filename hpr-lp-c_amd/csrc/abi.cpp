@@ -823,6 +823,60 @@ extern "C" int hprlp_batched_solver_solve_device(hprlp_batched_solver *h, int ba
     }
 }
 
+// ---- device-resident streams (DESIGN.md "Device-resident streams") -----------------------------------------------------------------
+// As the host stream: what the arguments alone tell is refused first, with its words, and needs no solver.
+extern "C" int hprlp_batched_solver_solve_stream_device(hprlp_batched_solver *h, int count, int width, const double *dC, const double *dAL,
+                                                        const double *dAU, const double *dl, const double *du, const double *obj_constants,
+                                                        const HPRLP_parameters *param, const double *dX0, const double *dY0,
+                                                        const hprlp_detection *det, hprlp_batched_certificates *certs, void *stream,
+                                                        double *dx, double *dy, double *dz, hprlp_batched_scalars *out) {
+    bool certs_cleared = false;
+    try {
+        stream_check_call(out && dx && dy && dz, count, width, dC && dAL && dAU && dl && du, param ? param->max_iter : 0,
+                          param ? param->check_iter : 1);
+        if (!h || !h->s) throw std::runtime_error("hprlp_batched_solver_solve_stream_device: null solver");
+        long mn[8];
+        batched_solver_info(h->s, mn);
+        const int m = static_cast<int>(mn[0]), n = static_cast<int>(mn[1]);
+        Detection d;
+        const bool with_det = detection_from(det, &d);
+        certs_cleared = certs != nullptr;
+        if (certs && !clear_batched_certificates(certs, count, m, n)) {
+            hprlp_free_batched_certificates(certs);
+            throw std::runtime_error("host allocation of the certificates failed");
+        }
+        std::vector<Certificate> k;
+        DeviceBatch db;
+        db.stream = stream;
+        db.x = dx; db.y = dy; db.z = dz;
+        db.primal_obj = out->primal_obj; db.residuals = out->residuals; db.gap = out->gap; db.iter = out->iter; db.status = out->status;
+        if (out->status) std::memset(out->status, 0, static_cast<size_t>(count) * 64);
+        batched_solver_solve_stream_device(h->s, count, width, dC, dAL, dAU, dl, du, obj_constants, param, dX0, dY0, with_det ? &d : nullptr,
+                                           with_det && certs ? &k : nullptr, &db);
+        if (with_det && certs && !export_batched_certificates(k, certs)) {
+            hprlp_free_batched_certificates(certs);
+            throw std::runtime_error("host allocation of the certificates failed");
+        }
+        out->time = db.time; out->setup_time = db.setup_time; out->solve_time = db.solve_time; out->power_time = db.power_time;
+        return 0;
+    } catch (const std::exception &e) {
+        if (certs_cleared) hprlp_free_batched_certificates(certs);
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
+extern "C" int hprlp_batched_solver_stream_memory(hprlp_batched_solver *h, long out[4]) {
+    try {
+        if (!h || !h->s || !out) throw std::runtime_error("hprlp_batched_solver_stream_memory: null solver / output");
+        batched_solver_stream_memory(h->s, out);
+        return 0;
+    } catch (const std::exception &e) {
+        set_last_error(e.what());
+        return -1;
+    }
+}
+
 extern "C" int hprlp_batched_solver_set_norms(hprlp_batched_solver *h, int rule) {
     try {
         if (!h || !h->s) throw std::runtime_error("hprlp_batched_solver_set_norms: null solver");

@@ -54,6 +54,14 @@ void batched_solver_solve_device(BatchedSolver *h, int batch_size, const HPRLP_F
                                  const HPRLP_FLOAT *l, const HPRLP_FLOAT *u, const HPRLP_FLOAT *obj_constants /* host */,
                                  const HPRLP_parameters *param, const HPRLP_FLOAT *X0, const HPRLP_FLOAT *Y0, bool carry,
                                  const Detection *det, std::vector<Certificate> *certs, DeviceBatch *dev);
+// The stream's device entry (DESIGN.md "Device-resident streams"; hprlp_batched_solver_solve_stream_device): the queue C .. Y0 as
+// DEVICE arrays, column-major rows x count, ordered on dev->stream; dev's x / y / z take rows x count doubles, its host arrays count
+// entries.  The queue is not staged: its scalars are taken where it lies, and a problem is scaled on its way into a slot.
+void batched_solver_solve_stream_device(BatchedSolver *h, int count, int width, const HPRLP_FLOAT *C, const HPRLP_FLOAT *AL,
+                                        const HPRLP_FLOAT *AU, const HPRLP_FLOAT *l, const HPRLP_FLOAT *u,
+                                        const HPRLP_FLOAT *obj_constants /* host */, const HPRLP_parameters *param, const HPRLP_FLOAT *X0,
+                                        const HPRLP_FLOAT *Y0, const Detection *det, std::vector<Certificate> *certs, DeviceBatch *dev);
+void batched_solver_stream_memory(const BatchedSolver *h, long out[4]);  // hprlp_batched_solver_stream_memory
 // New values on the shared matrix' pattern (DESIGN.md "Matrix values"): val = the nnz values of the model's CSR in the caller's order.
 // The shared solver takes them with zero vectors and is scaled again, the host's row / column norms and the created lambda_max
 // follow; panels, staging blocks, order tables and workspace stay.  carry is refused until the next successful solve.

@@ -1146,6 +1146,17 @@ __global__ void __launch_bounds__(kNormLanes) kb_data_bc(DataBc a, int B) {
     if (threadIdx.x == 0) a.part[(static_cast<size_t>(g * 2) * B + k) * a.nseg + s] = acc[0];
 }
 
+// member k's norm_b, norm_c of the final vectors (sum 0 of the second pass) and its first sigma, into scal; returns sigma
+__device__ __forceinline__ double member_norms(const double *part, int B, int k, int n, int m, int nseg, double *scal) {
+    const double nc = sqrt(segment_total(part, 0, 0, B, k, nseg, n)), nb = sqrt(segment_total(part, 1, 0, B, k, nseg, m));
+    double sigma = 1.0;
+    if (nb > 1.0e-8 && nc > 1.0e-8) sigma = nb / nc;
+    scal[DS_NORM_B * B + k] = nb;
+    scal[DS_NORM_C * B + k] = nc;
+    scal[DS_SIGMA * B + k] = sigma;
+    return sigma;
+}
+
 // one thread per member of the PADDED batch: norm_b, norm_c of the final vectors, the first sigma, and the header of the staging
 // block as ws_fill reads it: sigma | b_scale | c_scale (padding members 1.0) | active (ints: 1 for a member, 0 for padding)
 __global__ void __launch_bounds__(256) kb_data_header(const double *part, int B, int Bp, int n, int m, int nseg, double *scal, double *hdr) {
@@ -1153,11 +1164,7 @@ __global__ void __launch_bounds__(256) kb_data_header(const double *part, int B,
     if (k >= Bp) return;
     double sigma = 1.0, bs = 1.0, cs = 1.0;
     if (k < B) {
-        const double nc = sqrt(segment_total(part, 0, 0, B, k, nseg, n)), nb = sqrt(segment_total(part, 1, 0, B, k, nseg, m));
-        if (nb > 1.0e-8 && nc > 1.0e-8) sigma = nb / nc;
-        scal[DS_NORM_B * B + k] = nb;
-        scal[DS_NORM_C * B + k] = nc;
-        scal[DS_SIGMA * B + k] = sigma;
+        sigma = member_norms(part, B, k, n, m, nseg, scal);
         bs = scal[DS_B_SCALE * B + k];
         cs = scal[DS_C_SCALE * B + k];
     }
@@ -1174,6 +1181,133 @@ __global__ void __launch_bounds__(256) kb_flag_nonfinite(const double *x, size_t
     for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < nx + ny; i += stride)
         bad = bad || !isfinite(i < nx ? x[i] : y[i - nx]);
     if (bad) *flag = 1;
+}
+
+// ---- a queue in device memory (DESIGN.md "Device-resident streams") ----------------------------------------------------------------
+// The per-problem scalars of a whole queue from the caller's arrays where they lie: the passes of kb_data_in and kb_data_bc, load
+// for load and operation for operation, but nothing is stored beside the partials -- no scaled copy of the queue exists.  A problem
+// is scaled when it enters a slot (kb_slot_scale).  grid (nseg, problems of the slice, 2); k0: the slice's first problem (a grid's
+// y dimension holds 65535); the partials and scalars are laid out for all `count` problems as the batch's are for B.
+struct QueueIn {
+    const double *C, *AL, *AU;  // the caller's, column-major rows x count
+    const double *cn, *rn;
+    double *part;
+    int n, m, nseg;
+};
+// sum 0: the caller's values' sum of squares; sum 1: the values' after the cn / rn step
+__global__ void __launch_bounds__(kNormLanes) kb_queue_norms(QueueIn a, int count, int k0) {
+    const int s = blockIdx.x, k = k0 + blockIdx.y, g = blockIdx.z;
+    const int rows = g ? a.m : a.n;
+    const int i0 = s * kNormSeg;
+    if (i0 >= rows) return;  // (uniform per workgroup)
+    const int end = min(rows, i0 + kNormSeg);
+    const size_t base = static_cast<size_t>(k) * rows;
+    double acc[2] = {0.0, 0.0};
+    if (g == 0) {
+        for (int i = i0 + threadIdx.x; i < end; i += kNormLanes) {
+            const double c = a.C[base + i];
+            const double t0 = c * c;
+            acc[0] += t0;
+            const double cs = c / a.cn[i];
+            const double t1 = cs * cs;
+            acc[1] += t1;
+        }
+    } else {
+        for (int i = i0 + threadIdx.x; i < end; i += kNormLanes) {
+            const double nrm = a.rn[i];
+            double lo = a.AL[base + i], hi = a.AU[base + i];
+            const double v0 = bound_value_dev(lo, hi);
+            const double t0 = v0 * v0;
+            acc[0] += t0;
+            lo /= nrm;
+            hi /= nrm;
+            const double v1 = bound_value_dev(lo, hi);
+            const double t1 = v1 * v1;
+            acc[1] += t1;
+        }
+    }
+    tree_fold<2>(acc);
+    if (threadIdx.x == 0) {
+        a.part[(static_cast<size_t>(g * 2 + 0) * count + k) * a.nseg + s] = acc[0];
+        a.part[(static_cast<size_t>(g * 2 + 1) * count + k) * a.nseg + s] = acc[1];
+    }
+}
+
+struct QueueBc {
+    const double *C, *AL, *AU, *X0, *Y0;  // the caller's (X0 / Y0 null: none)
+    const double *cn, *rn;
+    const double *scal;
+    double *part;
+    int *flags;
+    int n, m, nseg;
+};
+// sum 0: the final values' sum of squares, (c / cn) / c_scale and bound_value of (AL / rn) / b_scale, (AU / rn) / b_scale, before
+// any +-kInfReplacement; a non-finite entry of the caller's starts raises flags[DF_START]
+__global__ void __launch_bounds__(kNormLanes) kb_queue_norms_bc(QueueBc a, int count, int k0) {
+    const int s = blockIdx.x, k = k0 + blockIdx.y, g = blockIdx.z;
+    const int rows = g ? a.m : a.n;
+    const int i0 = s * kNormSeg;
+    if (i0 >= rows) return;
+    const int end = min(rows, i0 + kNormSeg);
+    const size_t base = static_cast<size_t>(k) * rows;
+    const double bs = a.scal[DS_B_SCALE * count + k], cs = a.scal[DS_C_SCALE * count + k];
+    double acc[1] = {0.0};
+    bool bad = false;
+    if (g == 0) {
+        for (int i = i0 + threadIdx.x; i < end; i += kNormLanes) {
+            const double c1 = a.C[base + i] / a.cn[i];
+            const double c = c1 / cs;
+            const double t = c * c;
+            acc[0] += t;
+            if (a.X0) bad = bad || !isfinite(a.X0[base + i]);
+        }
+    } else {
+        for (int i = i0 + threadIdx.x; i < end; i += kNormLanes) {
+            const double nrm = a.rn[i];
+            const double lo1 = a.AL[base + i] / nrm, hi1 = a.AU[base + i] / nrm;
+            const double lo = lo1 / bs, hi = hi1 / bs;
+            const double v = bound_value_dev(lo, hi);
+            const double t = v * v;
+            acc[0] += t;
+            if (a.Y0) bad = bad || !isfinite(a.Y0[base + i]);
+        }
+    }
+    if (bad) a.flags[DF_START] = 1;  // (every writer writes the same word)
+    tree_fold<1>(acc);
+    if (threadIdx.x == 0) a.part[(static_cast<size_t>(g * 2) * count + k) * a.nseg + s] = acc[0];
+}
+
+// one thread per problem: norm_b, norm_c and the first sigma by kb_data_header's rule (there is no header: the slots' is the host's)
+__global__ void __launch_bounds__(256) kb_queue_sigma(const double *part, int count, int n, int m, int nseg, double *scal) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < count) (void)member_norms(part, count, k, n, m, nseg, scal);
+}
+
+// The listed problems from the CALLER's arrays into their slots' columns in scaled units: kb_slot_in's geometry and table, and per
+// element the composition of kb_data_in and kb_data_bc, each rounding kept -- the cn / rn step (SF_TIMES_NORM: * norm[i], else
+// / norm[i]), then / b_scale[p] (SF_BY_C: / c_scale[p]), then -inf -> -kInfReplacement (SF_LOWER) or +inf -> +kInfReplacement
+// (SF_UPPER).  C: (c / cn) / cs; l, u: (v * cn) / bs; AL, AU: (v / rn) / bs; X0: (x * cn) / bs; Y0: (y * rn) / cs.
+enum SlotScaleOp : int { SF_TIMES_NORM = 1, SF_BY_C = 2, SF_LOWER = 4, SF_UPPER = 8 };
+struct SlotScale {
+    const double *src[kPanelVectors];   // the caller's arrays, column-major rows x count
+    double *dst[kPanelVectors];         // padded panels
+    const double *norm[kPanelVectors];  // cn / rn
+    int rows[kPanelVectors], op[kPanelVectors];
+    const double *q_bs, *q_cs;          // per problem of the queue
+};
+// grid (ceil(max rows * np / 256), vectors)
+__global__ void __launch_bounds__(256) kb_slot_scale(SlotScale a, const SlotPair *pairs, int np, Geo g) {
+    const int v = blockIdx.y, rows = a.rows[v], op = a.op[v];
+    const long e = static_cast<long>(blockIdx.x) * 256 + threadIdx.x;
+    const long i = e / np;
+    if (i >= rows) return;
+    const SlotPair pr = pairs[e % np];
+    const double x = a.src[v][static_cast<size_t>(pr.problem) * rows + i], nrm = a.norm[v][i];
+    const double x1 = (op & SF_TIMES_NORM) ? x * nrm : x / nrm;
+    double r = x1 / ((op & SF_BY_C) ? a.q_cs[pr.problem] : a.q_bs[pr.problem]);
+    if ((op & SF_LOWER) && isinf(r) && r < 0) r = -kInfReplacement;
+    if ((op & SF_UPPER) && isinf(r) && r > 0) r = kInfReplacement;
+    a.dst[v][slot_elem(g, rows, static_cast<int>(i), pr.slot)] = r;
 }
 
 // ---- host side ----------------------------------------------------------------------------------
@@ -1542,6 +1676,7 @@ void ws_ray_panels(BatchWS &w) {
 // wrote all of them there).  carry: X / Y from the panels of the batch before (kb_carry_start, before anything is zeroed;
 // bsc_prev / csc_prev hold that batch's scales).  Zeroed: what a fresh workspace has zeroed -- the work panels, counters, flags, slots and partials.
 // stage_count 0: a device-entry call, whose kernels have left the header and the regions in the staging block already.
+// nvec 0: the header alone (a device-entry stream); no panel of the batch's vectors is written here.
 void ws_fill(BatchWS &w, const BatchData &d, size_t stage_count, const PanelIn &in, int nvec, bool has_x, bool has_y, bool carry,
              bool detect) {
     const int m = w.m, n = w.n;
@@ -1563,6 +1698,7 @@ void ws_fill(BatchWS &w, const BatchData &d, size_t stage_count, const PanelIn &
     if (!has_y && !carry) zero_async(w, w.Y);
     for (DBuf<int> *p : {&w.kx, &w.ky, &w.rflag}) zero_async(w, *p);
     if (detect) ws_ray_panels(w);
+    if (!nvec) return;  // (a device-entry stream: its slots are filled from the caller's arrays, StreamRun::fill_first)
     const int longest = std::max(n, m);
     hipLaunchKernelGGL(kb_panel_in, dim3((longest + kPanelTile - 1) / kPanelTile, (w.Bp + kPanelTile - 1) / kPanelTile, nvec), dim3(256), 0,
                        w.stream, in, w.B, w.geo);
@@ -1859,9 +1995,9 @@ struct Regions {
 };
 
 // Host entries: the staging blocks grow, each by its own size (the pinned one also serves a streamed call's download); into the pinned
-// one go the header of the Bp members the loop starts with, `first`, and d's scaled vectors and the caller's starts, in scaled units.
-void stage_host(BatchWS &w, const BatchLoop &L, const BatchData &first, const Regions &r, const BatchData &d, const double *X0,
-                const double *Y0, size_t pinned, size_t device) {
+// one go the header of the Bp members the loop starts with, `first` (stage_header: all that a device-entry stream uploads), and d's
+// scaled vectors and the caller's starts, in scaled units.
+void stage_header(BatchWS &w, const BatchLoop &L, const BatchData &first, size_t pinned, size_t device) {
     if (w.stage_h.n < pinned) w.stage_h.alloc(pinned, /*zero=*/false);
     if (w.stage_d.n < device) w.stage_d.alloc(device);
     const size_t Bp = L.sigma.size();
@@ -1871,6 +2007,11 @@ void stage_host(BatchWS &w, const BatchLoop &L, const BatchData &first, const Re
     std::copy(bs.begin(), bs.end(), sh + Bp);
     std::copy(cs.begin(), cs.end(), sh + 2 * Bp);
     std::memcpy(sh + 3 * Bp, L.active.data(), sizeof(int) * Bp);
+}
+void stage_host(BatchWS &w, const BatchLoop &L, const BatchData &first, const Regions &r, const BatchData &d, const double *X0,
+                const double *Y0, size_t pinned, size_t device) {
+    stage_header(w, L, first, pinned, device);
+    double *sh = w.stage_h.p;
     const double *src[kPanelVectors] = {d.C.data(), d.L.data(), d.U.data(), d.AL.data(), d.AU.data(), X0 ? X0 : Y0, Y0};
     for (int v = 0; v < r.nvec; ++v) std::memcpy(sh + r.start[v], src[v], r.count[v] * sizeof(double));
     if (X0) start_to_scaled(sh + r.start[r.iX], w.n, d.B, w.cn.data(), d.b_scale);
@@ -1896,6 +2037,30 @@ inline const int *data_flags_host(const BatchWS &w, int B) {
     return reinterpret_cast<const int *>(w.data_scal_h.p + static_cast<size_t>(DS_COUNT) * B);
 }
 
+// the segment partials and the scalars (with their pinned twin) of B members
+void data_buffers(BatchWS &w, int B, int nseg) {
+    const size_t part_count = static_cast<size_t>(4) * B * nseg, scal_count = static_cast<size_t>(DS_COUNT) * B + DF_COUNT;
+    if (w.data_part.n < part_count) w.data_part.alloc(part_count);
+    if (w.data_scal.n != scal_count) {  // (the flag words sit behind the scalars of exactly B members)
+        w.data_scal.alloc(scal_count);
+        w.data_scal_h.alloc(scal_count);
+    }
+}
+// the scalars of B members and the flag words to the host in one copy: the BatchData a loop needs (it reads none of the vectors)
+BatchData fetch_member_scalars(BatchWS &w, int B, const double *obj_constants, double model_obj_constant) {
+    HIP_CHECK(hipMemcpyAsync(w.data_scal_h.p, w.data_scal.p, static_cast<size_t>(DS_COUNT) * B * sizeof(double) + DF_COUNT * sizeof(int),
+                             hipMemcpyDeviceToHost, w.stream));
+    HIP_CHECK(hipStreamSynchronize(w.stream));
+    BatchData d;
+    d.m = w.m; d.n = w.n; d.B = B;
+    const double *h = w.data_scal_h.p;
+    const auto dst = member_scalars(d);
+    for (int i = 0; i < DS_COUNT; ++i) dst[i]->assign(h + static_cast<size_t>(i) * B, h + static_cast<size_t>(i + 1) * B);
+    d.objc.assign(B, model_obj_constant);
+    if (obj_constants) d.objc.assign(obj_constants, obj_constants + B);
+    return d;
+}
+
 // prepare_batch on the device: the caller's vectors (ordered on `stream`) into the regions r of the staging block in scaled units,
 // its header, and the per-member scalars on the host -- the BatchData a loop needs (it reads none of the vectors).
 BatchData device_prep(BatchWS &w, int B, int Bp, const Regions &r, const double *C, const double *AL, const double *AU, const double *l,
@@ -1903,12 +2068,7 @@ BatchData device_prep(BatchWS &w, int B, int Bp, const Regions &r, const double 
                       bool use_bc, hipStream_t stream, hipEvent_t ready) {
     const int m = w.m, n = w.n, nseg = norm_segments(std::max(n, m));
     if (w.stage_d.n < r.end) w.stage_d.alloc(r.end);
-    const size_t part_count = static_cast<size_t>(4) * B * nseg, scal_count = static_cast<size_t>(DS_COUNT) * B + DF_COUNT;
-    if (w.data_part.n < part_count) w.data_part.alloc(part_count);
-    if (w.data_scal.n != scal_count) {  // (the flag words sit behind the scalars of exactly B members)
-        w.data_scal.alloc(scal_count);
-        w.data_scal_h.alloc(scal_count);
-    }
+    data_buffers(w, B, nseg);
     HIP_CHECK(hipEventRecord(ready, stream));
     HIP_CHECK(hipStreamWaitEvent(w.stream, ready, 0));
     double *sd = w.stage_d.p;
@@ -1926,17 +2086,34 @@ BatchData device_prep(BatchWS &w, int B, int Bp, const Regions &r, const double 
     hipLaunchKernelGGL(kb_data_header, dim3((Bp + 255) / 256), dim3(256), 0, w.stream, static_cast<const double *>(w.data_part.p), B, Bp, n, m,
                        nseg, w.data_scal.p, sd);
     HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipMemcpyAsync(w.data_scal_h.p, w.data_scal.p, static_cast<size_t>(DS_COUNT) * B * sizeof(double) + DF_COUNT * sizeof(int),
-                             hipMemcpyDeviceToHost, w.stream));
-    HIP_CHECK(hipStreamSynchronize(w.stream));
-    BatchData d;
-    d.m = m; d.n = n; d.B = B;
-    const double *h = w.data_scal_h.p;
-    const auto dst = member_scalars(d);
-    for (int i = 0; i < DS_COUNT; ++i) dst[i]->assign(h + static_cast<size_t>(i) * B, h + static_cast<size_t>(i + 1) * B);
-    d.objc.assign(B, model_obj_constant);
-    if (obj_constants) d.objc.assign(obj_constants, obj_constants + B);
-    return d;
+    return fetch_member_scalars(w, B, obj_constants, model_obj_constant);
+}
+
+// prepare_batch's scalars for a whole queue of `count` problems that lies in device memory (ordered on `stream`), and nothing else:
+// the two norm passes over the caller's arrays, in slices of what one grid dimension takes.  sigma, b_scale and c_scale stay in
+// w.data_scal for the refills (kb_slot_clear, kb_slot_scale); DF_START is raised for a non-finite start anywhere in the queue.
+BatchData queue_prep(BatchWS &w, int count, const double *C, const double *AL, const double *AU, const double *X0, const double *Y0,
+                     const double *obj_constants, double model_obj_constant, bool use_bc, hipStream_t stream, hipEvent_t ready) {
+    constexpr int kGridSlice = 65535;
+    const int m = w.m, n = w.n, nseg = norm_segments(std::max(n, m));
+    data_buffers(w, count, nseg);
+    HIP_CHECK(hipEventRecord(ready, stream));
+    HIP_CHECK(hipStreamWaitEvent(w.stream, ready, 0));
+    int *flags = data_flags(w, count);
+    HIP_CHECK(hipMemsetAsync(flags, 0, DF_COUNT * sizeof(int), w.stream));
+    const double *cn = w.shared->col_norm.p, *rn = w.shared->row_norm.p;
+    for (int k0 = 0; k0 < count; k0 += kGridSlice)
+        hipLaunchKernelGGL(kb_queue_norms, dim3(nseg, std::min(kGridSlice, count - k0), 2), dim3(kNormLanes), 0, w.stream,
+                           QueueIn{C, AL, AU, cn, rn, w.data_part.p, n, m, nseg}, count, k0);
+    hipLaunchKernelGGL(kb_data_scales, dim3((count + 255) / 256), dim3(256), 0, w.stream, static_cast<const double *>(w.data_part.p), count,
+                       n, m, nseg, use_bc ? 1 : 0, w.data_scal.p);
+    for (int k0 = 0; k0 < count; k0 += kGridSlice)
+        hipLaunchKernelGGL(kb_queue_norms_bc, dim3(nseg, std::min(kGridSlice, count - k0), 2), dim3(kNormLanes), 0, w.stream,
+                           QueueBc{C, AL, AU, X0, Y0, cn, rn, w.data_scal.p, w.data_part.p, flags, n, m, nseg}, count, k0);
+    hipLaunchKernelGGL(kb_queue_sigma, dim3((count + 255) / 256), dim3(256), 0, w.stream, static_cast<const double *>(w.data_part.p), count, n,
+                       m, nseg, w.data_scal.p);
+    HIP_CHECK(hipGetLastError());
+    return fetch_member_scalars(w, count, obj_constants, model_obj_constant);
 }
 
 // the device entry's results, straight into the caller's buffers; the flag word that comes back: x or y holds a non-finite entry
@@ -1959,17 +2136,21 @@ bool device_results(BatchWS &w, const BatchLoop &L, DeviceBatch &dev, std::vecto
 // have ended, the queue, the counters, and the refill pass's argument blocks and tables -------------------------------------------
 struct StreamRun {
     BatchWS &w;
-    const BatchData &q;  // the whole queue in scaled units
+    const BatchData &q;  // the whole queue in scaled units (a device-entry call: its scalars alone)
+    DeviceBatch *const dev;  // a device-entry call (DESIGN.md "Device-resident streams"): the caller's buffers; null: the host entry
     const int count, W, max_iter;  // max_iter: each member's own limit (the loop's own is unlimited)
     const bool warm, detect;
     BatchData sd;  // the scalars of the problems in the slots: what the loop reads as "the batch" (it reads none of the vectors)
     HPRLP_parameters loop_prm;  // the call's, but for max_iter: unlimited
     BatchLoop L;
     const Regions regions;  // of the whole queue; behind them, at regions.end, sigma | b_scale | c_scale of every problem
-    // res_count: x, y, z and, with detection, the rays y, A^T y, d of every problem; tab_count: out pairs | in pairs | the start mask
+                            // (a device-entry call stages no queue: the header alone, and the scalars are in w.data_scal)
+    // res_count: x, y, z and, with detection, the rays y, A^T y, d of every problem (a device-entry call: the rays alone, x, y, z go
+    // to the caller's buffers); tab_count: out pairs | in pairs | the start mask
     const size_t nN, mN, stage_count, res_count, tab_count;
     SlotClear sclr{};
     SlotIn sin{};
+    SlotScale sscale{};  // a device-entry call's way in, in sin's place
     SlotOut sout{};
     std::vector<Member> done;
     std::vector<int> occ, freed, ps, pp;   // the problem in each slot (-1: empty); a pass's freed slots and its (slot, problem) pairs
@@ -1980,22 +2161,28 @@ struct StreamRun {
     const long bumps0;
     bool ray_y = false, any_verdict = false;      // of a pass's freed members: which rays their harvest copies
 
-    StreamRun(BatchWS &w_, const BatchData &q_, int W_, int Bp, const HPRLP_parameters &prm, const Detection *det, bool has_x, bool has_y)
-        : w(w_), q(q_), count(q_.B), W(W_), max_iter(prm.max_iter), warm(has_x || has_y), detect(det != nullptr), sd(first_members(q_, W_)),
-          loop_prm(prm), L(sd, Bp, loop_prm, det), regions(Bp, q_.n, q_.m, q_.B, has_x, has_y), nN(static_cast<size_t>(q_.n) * count),
-          mN(static_cast<size_t>(q_.m) * count), stage_count(regions.end + 3 * static_cast<size_t>(count)),
-          res_count((2 * nN + mN) * (detect ? 2 : 1)), tab_count(4 * static_cast<size_t>(W_) + Bp), done(count), occ(W), freed(W), ps(W),
-          pp(W), is_new(W, 0), r_slot(count, -1), r_in(count, -1), r_out(count, -1), bumps0(w_.bumps) {
+    StreamRun(BatchWS &w_, const BatchData &q_, int W_, int Bp, const HPRLP_parameters &prm, const Detection *det, bool has_x, bool has_y,
+              DeviceBatch *dev_)
+        : w(w_), q(q_), dev(dev_), count(q_.B), W(W_), max_iter(prm.max_iter), warm(has_x || has_y), detect(det != nullptr),
+          sd(first_members(q_, W_)), loop_prm(prm), L(sd, Bp, loop_prm, det), regions(Bp, q_.n, q_.m, dev_ ? 0 : q_.B, has_x, has_y),
+          nN(static_cast<size_t>(q_.n) * count), mN(static_cast<size_t>(q_.m) * count),
+          stage_count(regions.end + (dev_ ? 0 : 3 * static_cast<size_t>(count))),
+          res_count(dev_ ? (detect ? 2 * nN + mN : 0) : (2 * nN + mN) * (detect ? 2 : 1)), tab_count(4 * static_cast<size_t>(W_) + Bp),
+          done(count), occ(W), freed(W), ps(W), pp(W), is_new(W, 0), r_slot(count, -1), r_in(count, -1), r_out(count, -1),
+          bumps0(w_.bumps) {
         loop_prm.max_iter = std::numeric_limits<int>::max();
         for (int k = 0; k < W; ++k) occ[k] = r_slot[k] = k;  // (where the initial fill puts the first W problems)
         std::fill_n(r_in.begin(), W, 0);
         queue = StreamQueue{count, W};
     }
 
-    // the whole queue into the pinned block, behind the header of the first W members; behind it the scalars a refill reads
+    // the whole queue into the pinned block, behind the header of the first W members; behind it the scalars a refill reads.  A
+    // device-entry call: the header alone.
     void stage(const double *X0, const double *Y0) {
-        stage_host(w, L, sd, regions, q, X0, Y0, std::max(stage_count, res_count), stage_count);
+        if (dev) stage_header(w, L, sd, stage_count, stage_count);
+        else stage_host(w, L, sd, regions, q, X0, Y0, std::max(stage_count, res_count), stage_count);
         if (w.res_d.n < res_count) w.res_d.alloc(res_count);
+        if (dev) return;
         double *qh = w.stage_h.p + regions.end;
         std::copy(q.sigma.begin(), q.sigma.end(), qh);
         std::copy(q.b_scale.begin(), q.b_scale.end(), qh + count);
@@ -2026,11 +2213,19 @@ struct StreamRun {
         }
         sclr.SC = w.SC.p; sclr.ctl = w.ctl; sclr.bsc = w.bsc.p; sclr.csc = w.csc.p;
         sclr.q_sigma = qd; sclr.q_bs = qd + count; sclr.q_cs = qd + 2 * static_cast<size_t>(count);
+        if (dev) {  // (where queue_prep left them)
+            const double *sc = w.data_scal.p;
+            sclr.q_sigma = sc + static_cast<size_t>(DS_SIGMA) * count;
+            sclr.q_bs = sc + static_cast<size_t>(DS_B_SCALE) * count;
+            sclr.q_cs = sc + static_cast<size_t>(DS_C_SCALE) * count;
+        }
         double *rd = w.res_d.p;
+        double *const rx = dev ? dev->x : rd, *const ry = dev ? dev->y : rd + nN, *const rz = dev ? dev->z : rd + nN + mN;
+        if (!dev) rd += 2 * nN + mN;  // the rays y, A^T y, d: behind the solutions, or the whole of a device-entry call's block
         const double *cnd = w.shared->col_norm.p, *rnd = w.shared->row_norm.p;
         // (the ray d before the rays y, A^T y: a pass without a primal verdict stops short of them -- nobody has written Zray then)
         sout = SlotOut{{w.Xb.p, w.Yb.p, w.Zb.p, w.DS.p, w.YS.p, w.Zray.p},
-                       {rd, rd + nN, rd + nN + mN, rd + 3 * nN + 2 * mN, rd + 2 * nN + mN, rd + 2 * nN + 2 * mN},
+                       {rx, ry, rz, rd + nN + mN, rd, rd + mN},
                        {cnd, rnd, cnd, nullptr, nullptr, nullptr},
                        {w.bsc.p, w.csc.p, w.csc.p, nullptr, nullptr, nullptr},
                        {n, m, n, n, m, n},
@@ -2039,6 +2234,36 @@ struct StreamRun {
     const SlotPair *out_pairs() const { return reinterpret_cast<const SlotPair *>(w.tab_d.p); }
     const SlotPair *in_pairs() const { return reinterpret_cast<const SlotPair *>(w.tab_d.p + 2 * static_cast<size_t>(W)); }
     const int *new_mask() const { return w.tab_d.p + 4 * static_cast<size_t>(W); }
+
+    // A device-entry call's way into the slots (after bind): the caller's arrays in the regions' order, each with its norm and its
+    // operations (kb_slot_scale).
+    void bind_caller(const double *C, const double *AL, const double *AU, const double *l, const double *u, const double *X0,
+                     const double *Y0) {
+        const double *cnd = w.shared->col_norm.p, *rnd = w.shared->row_norm.p;
+        const double *src[kPanelVectors] = {C, l, u, AL, AU, X0 ? X0 : Y0, Y0};
+        const double *norm[5] = {cnd, cnd, cnd, rnd, rnd};
+        const int op[5] = {SF_BY_C, SF_TIMES_NORM | SF_LOWER, SF_TIMES_NORM | SF_UPPER, SF_LOWER, SF_UPPER};
+        for (int v = 0; v < regions.nvec; ++v) {
+            sscale.src[v] = src[v];
+            sscale.dst[v] = sin.dst[v];
+            sscale.rows[v] = regions.rows[v];
+            sscale.norm[v] = v < 5 ? norm[v] : (v == regions.iX ? cnd : rnd);
+            sscale.op[v] = v < 5 ? op[v] : (v == regions.iX ? SF_TIMES_NORM : SF_TIMES_NORM | SF_BY_C);
+        }
+        sscale.q_bs = sclr.q_bs;
+        sscale.q_cs = sclr.q_cs;
+    }
+    // ... and its initial fill: problems 0 .. W-1 into slots 0 .. W-1 by the refill's own kernel; padding members and dead columns 0.0,
+    // as kb_panel_in leaves them
+    void fill_first() {
+        for (int v = 0; v < regions.nvec; ++v)
+            HIP_CHECK(hipMemsetAsync(sscale.dst[v], 0, static_cast<size_t>(sscale.rows[v]) * w.Bp * sizeof(double), w.stream));
+        int *th = w.tab_h.p;
+        std::fill(th, th + tab_count, 0);
+        for (int k = 0; k < W; ++k) th[2 * (W + k)] = th[2 * (W + k) + 1] = k;
+        HIP_CHECK(hipMemcpyAsync(w.tab_d.p, th, tab_count * sizeof(int), hipMemcpyHostToDevice, w.stream));
+        launch_slot(w, kb_slot_scale, sscale, in_pairs(), W, regions.nvec);
+    }
 
     // the limit rule (time first, as loop_ended; then the member's own max_iter), then the slots whose member has a status: freed[0 .. return)
     int expire_and_collect(bool time_up, bool &active_stale) {
@@ -2092,7 +2317,8 @@ struct StreamRun {
     void refill(int nin) {
         const int event = L.iter / L.check_iter;
         launch_slot(w, kb_slot_clear, sclr, in_pairs(), nin, sclr.npn + sclr.npm + 1);
-        launch_slot(w, kb_slot_in, sin, in_pairs(), nin, regions.nvec);
+        if (dev) launch_slot(w, kb_slot_scale, sscale, in_pairs(), nin, regions.nvec);
+        else launch_slot(w, kb_slot_in, sin, in_pairs(), nin, regions.nvec);
         if (warm) {
             ws_start(w, new_mask());
             HIP_CHECK(hipGetLastError());
@@ -2159,6 +2385,34 @@ struct StreamRun {
         }
         member_results(done, count, res.primal_obj, res.residuals, res.gap, res.iter, res.status);
         return res;
+    }
+
+    // A device-entry call: x, y, z are in the caller's buffers already; the members' evaluations go to its host arrays, and of the
+    // ray block only the columns of the problems with a verdict come to the host.  Returns the bytes of those.
+    size_t results_device(std::vector<Certificate> *certs) {
+        for (int pr = queue.next; pr < count; ++pr) done[pr].status = "TIME_LIMIT";
+        HIP_CHECK(hipStreamSynchronize(w.stream));
+        const size_t m = w.m, n = w.n;
+        size_t ray_doubles = 0;
+        if (certs) {
+            certs->assign(count, Certificate());
+            std::vector<double> cy(m), cz(n), cd(n);
+            const double *ry = w.res_d.p, *rz = ry + mN, *rd = rz + nN;
+            for (int pr = 0; pr < count && detect; ++pr) {
+                if (!done[pr].verdict) continue;
+                if (done[pr].verdict == 1) {
+                    HIP_CHECK(hipMemcpy(cy.data(), ry + pr * m, m * sizeof(double), hipMemcpyDeviceToHost));
+                    HIP_CHECK(hipMemcpy(cz.data(), rz + pr * n, n * sizeof(double), hipMemcpyDeviceToHost));
+                    ray_doubles += m + n;
+                } else {
+                    HIP_CHECK(hipMemcpy(cd.data(), rd + pr * n, n * sizeof(double), hipMemcpyDeviceToHost));
+                    ray_doubles += n;
+                }
+                member_certificate(w, (*certs)[pr], done[pr], 0, cy.data(), cz.data(), cd.data(), q.b_scale[pr], q.c_scale[pr]);
+            }
+        }
+        member_results(done, count, dev->primal_obj, dev->residuals, dev->gap, dev->iter, dev->status);
+        return ray_doubles * sizeof(double);
     }
 };
 
@@ -2230,6 +2484,7 @@ struct BatchedSolver {
     bool streamed = false, have_stream = false;
     std::vector<int> rec_slot, rec_in, rec_out;
     long stream_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    long stream_mem[4] = {0, 0, 0, 0};  // hprlp_batched_solver_stream_memory: what the last one held beside the workspace
     double stream_seconds[2] = {0, 0};  // of the last streamed call: its refill passes (harvest, refill, iteration-0 evaluation); the rest of its loop
     double lambda_last = 0.0;           // lambda_max at the end of the last successful call of either kind (0: none yet)
 
@@ -2242,10 +2497,11 @@ struct BatchedSolver {
     void solve(int B, const double *C, const double *AL, const double *AU, const double *l, const double *u, const double *obj_constants,
                const HPRLP_parameters *p, const double *X0, const double *Y0, bool carry, const Detection *det,
                std::vector<Certificate> *certs, HPRLP_batched_results *out, DeviceBatch *dev = nullptr);
-    // count problems through min(width, count) slots, a freed slot taking the next queued problem at once (host arrays only)
+    // count problems through min(width, count) slots, a freed slot taking the next queued problem at once.  dev null: host arrays,
+    // the results into `out`; dev set: the queue lies in device memory (solve()'s rule for dev)
     void solve_stream(int count, int width, const double *C, const double *AL, const double *AU, const double *l, const double *u,
                       const double *obj_constants, const HPRLP_parameters *p, const double *X0, const double *Y0, const Detection *det,
-                      std::vector<Certificate> *certs, HPRLP_batched_results *out);
+                      std::vector<Certificate> *certs, HPRLP_batched_results *out, DeviceBatch *dev = nullptr);
 
     // the handle's parameters with the caller's max_iter, stop_tol, time_limit, check_iter and use_bc_scaling (p null: the handle's)
     HPRLP_parameters call_parameters(const HPRLP_parameters *p) const {
@@ -2285,18 +2541,20 @@ struct BatchedSolver {
         if (bad) throw std::runtime_error("batched solver: carry refused, the previous batch's solution holds a non-finite value");
     }
     // the device entry: no pointer reaches a kernel before all of them have passed
+    // (stream: a queue of B problems, whose norm passes are launched in slices: no limit on B)
     void check_device_call(const DeviceBatch &dev, int B, const double *C, const double *AL, const double *AU, const double *l,
-                           const double *u, const double *X0, const double *Y0) {
+                           const double *u, const double *X0, const double *Y0, bool stream = false) {
         const size_t nB = static_cast<size_t>(n) * B, mB = static_cast<size_t>(m) * B;
-        if (B > 65535) throw std::runtime_error("batched solver: the device entry takes at most 65535 members");
+        const char *entry = stream ? "batched stream" : "batched solver";
+        if (B > 65535 && !stream) throw std::runtime_error("batched solver: the device entry takes at most 65535 members");
         const std::pair<const double *, size_t> in_ptrs[5] = {{C, nB}, {AL, mB}, {AU, mB}, {l, nB}, {u, nB}};
         const char *in_names[5] = {"C", "AL", "AU", "l", "u"};
-        for (int i = 0; i < 5; ++i) check_device_pointer(in_ptrs[i].first, in_ptrs[i].second, device, in_names[i]);
-        if (X0) check_device_pointer(X0, nB, device, "X0");
-        if (Y0) check_device_pointer(Y0, mB, device, "Y0");
-        check_device_pointer(dev.x, nB, device, "x");
-        check_device_pointer(dev.y, mB, device, "y");
-        check_device_pointer(dev.z, nB, device, "z");
+        for (int i = 0; i < 5; ++i) check_device_pointer(in_ptrs[i].first, in_ptrs[i].second, device, in_names[i], entry);
+        if (X0) check_device_pointer(X0, nB, device, "X0", entry);
+        if (Y0) check_device_pointer(Y0, mB, device, "Y0", entry);
+        check_device_pointer(dev.x, nB, device, "x", entry);
+        check_device_pointer(dev.y, mB, device, "y", entry);
+        check_device_pointer(dev.z, nB, device, "z", entry);
         if (!inputs_ready) HIP_CHECK(hipEventCreateWithFlags(&inputs_ready, hipEventDisableTiming));
     }
     // the workspace of geometry g and lambda_max as created, whatever the handle solved before; the graphs go with a panel, the grid cap or their lambda
@@ -2469,28 +2727,43 @@ void BatchedSolver::solve(int B, const double *C_in, const double *AL_in, const 
 // ---- streamed batches (DESIGN.md "Streamed batches": the rule, the local iteration numbers, the memory of a call) ----------------
 // `count` problems through W = min(width, count) slots of a workspace whose geometry is a plain solve's of W members.  The loop is
 // solve()'s; a member that ends at an evaluation hands its slot on within that event (StreamRun).  No panel moves: the graphs survive.
+// dev set (DESIGN.md "Device-resident streams"): the queue lies in device memory and is never staged -- queue_prep takes its scalars
+// where it lies, a problem is scaled on its way into a slot, and x, y, z go to the caller's buffers.
 void BatchedSolver::solve_stream(int count, int width, const double *C_in, const double *AL_in, const double *AU_in, const double *l_in,
                                  const double *u_in, const double *obj_constants, const HPRLP_parameters *p, const double *X0,
-                                 const double *Y0, const Detection *det, std::vector<Certificate> *certs, HPRLP_batched_results *out) {
+                                 const double *Y0, const Detection *det, std::vector<Certificate> *certs, HPRLP_batched_results *out,
+                                 DeviceBatch *dev) {
     // -- everything that can refuse the call, before the handle changes
     const HPRLP_parameters actual = call_parameters(p);
-    stream_check_call(out != nullptr, count, width, C_in && AL_in && AU_in && l_in && u_in, actual.max_iter, actual.check_iter);
+    stream_check_call(dev ? dev->x && dev->y && dev->z : out != nullptr, count, width, C_in && AL_in && AU_in && l_in && u_in,
+                      actual.max_iter, actual.check_iter);
     const size_t nN = static_cast<size_t>(n) * count, mN = static_cast<size_t>(m) * count;
-    for (size_t i = 0; X0 && i < nN; ++i)
+    for (size_t i = 0; !dev && X0 && i < nN; ++i)
         if (!std::isfinite(X0[i])) throw std::runtime_error("batched stream: warm start: X0[" + std::to_string(i) + "] is not finite");
-    for (size_t i = 0; Y0 && i < mN; ++i)
+    for (size_t i = 0; !dev && Y0 && i < mN; ++i)
         if (!std::isfinite(Y0[i])) throw std::runtime_error("batched stream: warm start: Y0[" + std::to_string(i) + "] is not finite");
+    if (dev) check_device_call(*dev, count, C_in, AL_in, AU_in, l_in, u_in, X0, Y0, /*stream=*/true);
     const int W = std::min(width, count);
     const Geo plan = plan_geometry(W);
     const bool detect = det && det->on;
 
-    have_prev = false;  // the panels will hold members of many problems: nothing of this call is carried
+    const bool had_prev = have_prev;
+    bool refused = false;  // a device-entry call is turned away by its norm passes, before the workspace has changed
+    have_prev = false;     // the panels will hold members of many problems: nothing of this call is carried
     try {
-        // -- the whole queue in scaled units, into the pinned block behind the header of the first W members
+        // -- the whole queue in scaled units, into the pinned block behind the header of the first W members; a device-entry call: its
+        //    scalars from where it lies, and the header
         const auto t_prep = time_now();
-        const BatchData q = prepare_batch(m, n, count, C_in, AL_in, AU_in, l_in, u_in, obj_constants, obj_constant, w.rn.data(), w.cn.data(),
-                                          actual.use_bc_scaling, norm_rule);
-        StreamRun run(w, q, W, plan.Bp, actual, detect ? det : nullptr, X0 != nullptr, Y0 != nullptr);
+        const BatchData q =
+            dev ? queue_prep(w, count, C_in, AL_in, AU_in, X0, Y0, obj_constants, obj_constant, actual.use_bc_scaling,
+                             static_cast<hipStream_t>(dev->stream), inputs_ready)
+                : prepare_batch(m, n, count, C_in, AL_in, AU_in, l_in, u_in, obj_constants, obj_constant, w.rn.data(), w.cn.data(),
+                                actual.use_bc_scaling, norm_rule);
+        if (dev && data_flags_host(w, count)[DF_START]) {
+            refused = true;
+            throw std::runtime_error("batched stream: warm start: X0 or Y0 holds an entry that is not finite");
+        }
+        StreamRun run(w, q, W, plan.Bp, actual, detect ? det : nullptr, X0 != nullptr, Y0 != nullptr, dev);
         BatchLoop &L = run.L;
         run.stage(X0, Y0);
         seconds[2] = time_since(t_prep);
@@ -2499,10 +2772,20 @@ void BatchedSolver::solve_stream(int count, int width, const double *C_in, const
         const auto t_fill = time_now();
         ensure_workspace(plan);
         const PanelIn in = bind_panels(w, run.regions);  // the initial fill: the first W columns of every region
-        HIP_CHECK(hipMemsetAsync(w.res_d.p, 0, run.res_count * sizeof(double), w.stream));  // (a problem that never started: zero vectors)
-        ws_fill(w, run.sd, run.stage_count, in, run.regions.nvec, X0 != nullptr, Y0 != nullptr, /*carry=*/false, detect);
+        if (dev) {  // (a problem that never started: zero vectors)
+            HIP_CHECK(hipMemsetAsync(dev->x, 0, nN * sizeof(double), w.stream));
+            HIP_CHECK(hipMemsetAsync(dev->y, 0, mN * sizeof(double), w.stream));
+            HIP_CHECK(hipMemsetAsync(dev->z, 0, nN * sizeof(double), w.stream));
+        }
+        if (run.res_count) HIP_CHECK(hipMemsetAsync(w.res_d.p, 0, run.res_count * sizeof(double), w.stream));
+        ws_fill(w, run.sd, run.stage_count, in, dev ? 0 : run.regions.nvec, X0 != nullptr, Y0 != nullptr, /*carry=*/false, detect);
+        if (dev) {  // the first W problems from the caller's arrays, by the refill's kernel
+            run.bind(in);
+            run.bind_caller(C_in, AL_in, AU_in, l_in, u_in, X0, Y0);
+            run.fill_first();
+        }
         if (X0 || Y0) ws_start(w);
-        run.bind(in);
+        if (!dev) run.bind(in);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipStreamSynchronize(w.stream));
         seconds[3] = time_since(t_fill);
@@ -2525,19 +2808,37 @@ void BatchedSolver::solve_stream(int count, int width, const double *C_in, const
         }
         seconds[4] = time_since(L.solve_start);
 
-        // -- the results: one download
+        // -- the results: one download; a device-entry call: the members' scalars, and the rays of the verdicts
         const auto t_res = time_now();
-        HPRLP_batched_results res = run.results(certs);
-        seconds[5] = time_since(t_res);
-        set_times(res);
-        *out = res;
+        size_t back = run.res_count * sizeof(double);
+        if (dev) {
+            back = static_cast<size_t>(DS_COUNT) * count * sizeof(double) + DF_COUNT * sizeof(int) + run.results_device(certs);
+            seconds[5] = time_since(t_res);
+            set_times(*dev);
+        } else {
+            HPRLP_batched_results res = run.results(certs);
+            seconds[5] = time_since(t_res);
+            set_times(res);
+            *out = res;
+        }
         const long stats[8] = {count, width, L.iter, run.evals, run.refill_events, run.refills, run.passes, w.bumps - run.bumps0};
         std::copy(stats, stats + 8, stream_stats);
         rec_slot = std::move(run.r_slot); rec_in = std::move(run.r_in); rec_out = std::move(run.r_out);
         stream_seconds[0] = refill_seconds;
         stream_seconds[1] = seconds[4] - refill_seconds;
-        call_succeeded(run.stage_count * sizeof(double), run.res_count * sizeof(double), nullptr, /*device_entry=*/false);
+        const size_t header = 4 * static_cast<size_t>(plan.Bp);  // what the call held: the queue's vectors | the result / ray block |
+        const size_t scalars = dev ? w.data_scal.n + w.data_part.n : 3 * static_cast<size_t>(count);  // scalars, partials, tables | pinned
+        const long mem[4] = {static_cast<long>((run.stage_count - header - (dev ? 0 : scalars)) * sizeof(double)),
+                             static_cast<long>(run.res_count * sizeof(double)),
+                             static_cast<long>((header + scalars) * sizeof(double) + w.tab_d.n * sizeof(int)),
+                             static_cast<long>((w.stage_h.n + (dev ? w.data_scal_h.n : 0)) * sizeof(double) + w.tab_h.n * sizeof(int))};
+        std::copy(mem, mem + 4, stream_mem);
+        call_succeeded(run.stage_count * sizeof(double), back, nullptr, /*device_entry=*/dev != nullptr);
     } catch (...) {
+        if (refused) {  // nothing the previous call left has been touched
+            have_prev = had_prev;
+            throw;
+        }
         call_failed(/*streamed_call=*/true);
         throw;
     }
@@ -2549,6 +2850,18 @@ void batched_solver_solve_stream(BatchedSolver *h, int count, int width, const d
                                  const double *Y0, const Detection *det, std::vector<Certificate> *certs, HPRLP_batched_results *out) {
     if (!h) throw std::runtime_error("batched stream: null handle");
     h->solve_stream(count, width, C, AL, AU, l, u, obj_constants, param, X0, Y0, det, certs, out);
+}
+void batched_solver_solve_stream_device(BatchedSolver *h, int count, int width, const double *C, const double *AL, const double *AU,
+                                        const double *l, const double *u, const double *obj_constants, const HPRLP_parameters *param,
+                                        const double *X0, const double *Y0, const Detection *det, std::vector<Certificate> *certs,
+                                        DeviceBatch *dev) {
+    if (!h || !dev) throw std::runtime_error("batched stream: null handle / device batch");
+    h->solve_stream(count, width, C, AL, AU, l, u, obj_constants, param, X0, Y0, det, certs, nullptr, dev);
+}
+void batched_solver_stream_memory(const BatchedSolver *h, long out[4]) {
+    if (!h || !out) throw std::runtime_error("batched stream memory: null handle / output");
+    if (!h->have_stream) throw std::runtime_error("batched stream memory: no successful stream call on this handle");
+    std::copy(h->stream_mem, h->stream_mem + 4, out);
 }
 int batched_solver_stream_record(const BatchedSolver *h, int *slot, int *event_in, int *event_out) {
     if (!h || !slot || !event_in || !event_out) throw std::runtime_error("batched stream record: null handle / output");

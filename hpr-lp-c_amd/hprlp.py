@@ -227,6 +227,11 @@ def lib():
         L.hprlp_batched_solver_stream_seconds.argtypes = [C.c_void_p, c_dbl_p]
         L.hprlp_batched_solver_lambda.argtypes = [C.c_void_p, c_dbl_p]
         L.hprlp_stream_schedule_host.argtypes = [C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p]
+    if hasattr(L, "hprlp_batched_solver_solve_stream_device"):  # (likewise)
+        L.hprlp_batched_solver_solve_stream_device.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + \
+            [c_dbl_p, C.POINTER(CParameters)] + [C.c_void_p] * 2 + [C.POINTER(CDetection), C.POINTER(CBatchedCertificates)] + \
+            [C.c_void_p] * 4 + [C.POINTER(CBatchedScalars)]
+        L.hprlp_batched_solver_stream_memory.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
     L.hprlp_batched_prepare_host_rule.argtypes =[C.c_int] * 3 + [c_dbl_p] * 9 + [C.c_int, C.c_int, C.POINTER(CBatchedPrepared)]
     L.hprlp_solver_set_start.argtypes = [C.c_void_p, c_dbl_p, c_dbl_p]
     L.hprlp_solver_set_data.argtypes = [C.c_void_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]
@@ -946,28 +951,38 @@ class BatchedSolver:
         scalars and statuses on the host as before.  The inputs are taken as ordered on the current torch stream.  ValueError for a
         wrong type, dtype, device or shape, before the library is called; RuntimeError with the library's message for a call it
         refuses, which leaves the solver usable.  The norms of the scaling follow the tree rule (see set_norms)."""
+        out = self._device_call("solve_tensors", "hprlp_batched_solver_solve_device", (), (int(bool(carry)),),
+                                (Cmat, AL, AU, l, u, obj_constants, X0, Y0), param, eps_primal, eps_dual)
+        self._last_B = out["batch_size"]
+        return out
+
+    def _device_call(self, who, entry, before, after, batch, param, eps_primal, eps_dual):
+        """One call of a device entry (solve_tensors, solve_stream_tensors): entry(handle, B, *before, the five tensors,
+        obj_constants, param, X0, Y0, *after, detection, certificates, the torch stream, x, y, z, the scalars).  The tensors are
+        checked here, before the library is called (ValueError); RuntimeError with the library's message where the call fails."""
         import torch
+        Cmat, AL, AU, l, u, obj_constants, X0, Y0 = batch
         if not self._h:
             raise RuntimeError("BatchedSolver: closed")
         m, n = self.model.m, self.model.n
         if not isinstance(Cmat, torch.Tensor) or Cmat.dim() != 2:
-            raise ValueError("solve_tensors: Cmat must be a 2-D torch tensor")
+            raise ValueError(f"{who}: Cmat must be a 2-D torch tensor")
         B = int(Cmat.shape[1])
         if B <= 0:
-            raise ValueError("solve_tensors: an empty batch")
+            raise ValueError(f"{who}: an empty batch")
 
         def dev(t, rows, name):
             """The tensor as column-major rows x B device memory: (what keeps it alive, its address)."""
             if t is None:
                 return None, None
             if not isinstance(t, torch.Tensor):
-                raise ValueError(f"solve_tensors: {name} must be a torch tensor, got {type(t).__name__}")
+                raise ValueError(f"{who}: {name} must be a torch tensor, got {type(t).__name__}")
             if t.dtype != torch.float64:
-                raise ValueError(f"solve_tensors: {name} must be float64, got {t.dtype}")
+                raise ValueError(f"{who}: {name} must be float64, got {t.dtype}")
             if t.device.type != "cuda" or t.device.index != self.device_number:
-                raise ValueError(f"solve_tensors: {name} must be on the solver's device cuda:{self.device_number}, got {t.device}")
+                raise ValueError(f"{who}: {name} must be on the solver's device cuda:{self.device_number}, got {t.device}")
             if tuple(t.shape) != (rows, B):
-                raise ValueError(f"solve_tensors: {name} must have shape ({rows}, {B}), got {tuple(t.shape)}")
+                raise ValueError(f"{who}: {name} must have shape ({rows}, {B}), got {tuple(t.shape)}")
             tt = t.T
             if not tt.is_contiguous():
                 tt = tt.contiguous()
@@ -976,7 +991,7 @@ class BatchedSolver:
                                                          (X0, n, "X0"), (Y0, m, "Y0"))]
         oc = None if obj_constants is None else _as(obj_constants, np.float64)
         if oc is not None and oc.shape != (B,):
-            raise ValueError(f"solve_tensors: obj_constants must have {B} entries")
+            raise ValueError(f"{who}: obj_constants must have {B} entries")
         det = _detection_arg(eps_primal, eps_dual)
         cc = CBatchedCertificates()
         cprm = None if param is None else param.to_c()
@@ -988,21 +1003,51 @@ class BatchedSolver:
                              iter=res["iter"].ctypes.data_as(c_int_p), status=C.cast(status, C.POINTER(C.c_char)))
         stream = torch.cuda.current_stream(device).cuda_stream
         ptrs = [p for _, p in keep]
-        rc = lib().hprlp_batched_solver_solve_device(self._h, B, *ptrs[:5], _dptr(oc), None if cprm is None else C.byref(cprm), ptrs[5],
-                                                     ptrs[6], int(bool(carry)), C.byref(det) if det is not None else None,
-                                                     C.byref(cc) if det is not None else None, stream, xb.data_ptr(), yb.data_ptr(),
-                                                     zb.data_ptr(), C.byref(sc))
+        rc = getattr(lib(), entry)(self._h, B, *before, *ptrs[:5], _dptr(oc), None if cprm is None else C.byref(cprm), ptrs[5], ptrs[6],
+                                   *after, C.byref(det) if det is not None else None, C.byref(cc) if det is not None else None, stream,
+                                   xb.data_ptr(), yb.data_ptr(), zb.data_ptr(), C.byref(sc))
         if rc != 0:
             if det is not None:
                 lib().hprlp_free_batched_certificates(C.byref(cc))
-            raise RuntimeError("hprlp_batched_solver_solve_device failed: " + last_error())
+            raise RuntimeError(entry + " failed: " + last_error())
         out = dict(batch_size=B, time=sc.time, setup_time=sc.setup_time, solve_time=sc.solve_time, power_time=sc.power_time,
                    x=xb.T, y=yb.T, z=zb.T, **res)
         out["status"] = [status.raw[64 * k:64 * (k + 1)].split(b"\0")[0].decode() for k in range(B)]
         if det is not None:
             out["certificates"] = _batched_certificates(cc)
-        self._last_B = B
         return out
+
+    def solve_stream_tensors(self, Cmat, AL, AU, l, u, obj_constants=None, width=64, X0=None, Y0=None, eps_primal=None, eps_dual=None,
+                             prm=None):
+        """solve_stream() for a queue that is on the GPU already (hprlp_batched_solver_solve_stream_device, DESIGN.md
+        "Device-resident streams"): Cmat, l, u, X0 (n, N) and AL, AU, Y0 (m, N) are float64 torch tensors on the solver's device,
+        taken as ordered on the current torch stream.  A tensor whose transpose is contiguous is passed as it is; any other layout
+        costs one copy on the device.  The queue is not copied: its norms are taken where it lies and a problem is scaled on its
+        way into a slot.  Returns solve_stream()'s dict with x, y, z as device tensors (rows, N) -- a problem that never started
+        has zero columns -- plus "slot", "event_in", "event_out" and, with detection, "certificates".  ValueError for a numpy array,
+        a CPU tensor, a wrong dtype or a wrong shape, before the library is called; RuntimeError with the library's message for a
+        call it refuses, which leaves the solver as it was."""
+        if not hasattr(lib(), "hprlp_batched_solver_solve_stream_device"):
+            raise RuntimeError(f"{LIB_PATH} has no hprlp_batched_solver_solve_stream_device: a build of an earlier commit (HPRLP_LIB?)")
+        out = self._device_call("solve_stream_tensors", "hprlp_batched_solver_solve_stream_device", (int(width),), (),
+                                (Cmat, AL, AU, l, u, obj_constants, X0, Y0), prm, eps_primal, eps_dual)
+        N = out["batch_size"]
+        rec = [np.zeros(N, dtype=np.intc) for _ in range(3)]
+        if lib().hprlp_batched_solver_stream_record(self._h, *(r.ctypes.data_as(c_int_p) for r in rec)) != N:
+            raise RuntimeError("hprlp_batched_solver_stream_record failed: " + last_error())
+        out["slot"], out["event_in"], out["event_out"] = rec
+        return out
+
+    _STREAM_MEMORY = ("queue_vector_bytes", "result_block_bytes", "scalar_table_bytes", "pinned_host_bytes")
+
+    def stream_memory(self):
+        """What the last successful solve_stream() / solve_stream_tensors() held beside the workspace
+        (hprlp_batched_solver_stream_memory): device bytes of queue vectors (the staged queue; 0 for solve_stream_tensors), of
+        the result / ray block, of per-problem scalars, partials and tables, and pinned host bytes.  A list in that order."""
+        out = (C.c_long * 4)()
+        if lib().hprlp_batched_solver_stream_memory(self._h, out) != 0:
+            raise RuntimeError(last_error())
+        return [int(v) for v in out]
 
     def set_matrix(self, values):
         """New values on the shared matrix' pattern (hprlp_batched_solver_set_matrix_values), in the order of the model's CSR.

@@ -206,7 +206,8 @@ int hprlp_batched_solver_seconds(hprlp_batched_solver *h, double out[6]);
  * max_iter is each member's own; time_limit is the call's: at the limit the running members get TIME_LIMIT with their local iter,
  * the queued ones TIME_LIMIT, iter 0, zero vectors and event_in -1.  Refused with -1 + hprlp_last_error() before anything
  * changes: a non-positive count or width, NULL vectors, a non-finite start, and a max_iter that is not a multiple of check_iter
- * (every member's last event has to be a periodic event of the loop).  There is no carry and no device entry.  After a stream
+ * (every member's last event has to be a periodic event of the loop).  There is no carry; the device entry is
+ * hprlp_batched_solver_solve_stream_device below.  After a stream
  * call, carry, hprlp_batched_solver_ray_step and the panels by name are refused until the next plain solve, which gives the bits
  * of a handle that never streamed.
  *
@@ -261,6 +262,41 @@ int hprlp_batched_solver_solve_device(hprlp_batched_solver *h, int batch_size, c
                                       const double *dX0, const double *dY0, int carry, const hprlp_detection *det,
                                       hprlp_batched_certificates *certs, void *stream, double *dx, double *dy, double *dz,
                                       hprlp_batched_scalars *out);
+/* ---- device-resident streams: a queue in device memory (DESIGN.md "Device-resident streams") ----------------------------------
+ * hprlp_batched_solver_solve_stream with the queue already in device memory and the solutions wanted there.  dC, dl, du, dX0,
+ * dx, dz are n x count and dAL, dAU, dY0, dy are m x count, column-major DEVICE arrays like hprlp_batched_solver_solve_device's
+ * with `count` in place of B (dX0 / dY0 may be NULL); obj_constants (count or NULL), param, det, certs and `out` (arrays of
+ * `count`) are host memory.
+ *   Rule: the host stream's, word for word -- slots, events, local iteration numbers, limits, and what a later call may do (carry,
+ * hprlp_batched_solver_ray_step and the panels by name are refused until the next plain solve).  _stream_record, _stream_info,
+ * _stream_seconds, _lambda, _transfer and _scalars report on this call as on its host twin.
+ *   No copy of the queue: the per-problem norms are taken from the caller's arrays where they lie, a problem is scaled in the
+ * launch that puts it into its slot, and x, y, z of a harvested problem go straight into column p of dx, dy, dz (zeroed at entry
+ * on the solver's stream: a problem that never started has zero columns).  Beside the workspace the call holds no device memory
+ * that grows with n x count or m x count, except, with detection, the ray block of (2 n + m) x count doubles.  Across the bus go
+ * the header of the slots, the refill passes' tables, 7 x count scalars with their flag words, the loop's scalar fetches and the
+ * rays of the problems with a verdict.
+ *   Pointers and ordering: hprlp_batched_solver_solve_device's.  Every device pointer is looked up with hipPointerGetAttributes
+ * before anything is launched (the room checked is rows x count), the solver's stream waits for an event recorded on `stream`,
+ * and the outputs are complete on return.
+ *   Refusals: everything the host stream refuses, with its words, and every pointer that fails the lookup.  A non-finite entry of
+ * dX0 / dY0 anywhere in the queue -- in a problem that would only enter at a refill too -- is found by the norm passes and
+ * refused before any panel or control value is written.  After any refusal the handle is what it was; a carry that was valid
+ * before stays valid.
+ *   Bits: the norms follow the tree rule (norm rule 1).  Against the host stream on a handle with
+ * hprlp_batched_solver_set_norms(h, 1) and the same arguments, every problem has the same status, iter, x, y, z, primal_obj,
+ * residuals, gap and certificate bit for bit, the record and the stream_info counts (lambda bumps included) are the same; with
+ * count <= width the call is hprlp_batched_solver_solve_device of `count` members.
+ * 0, or -1 + hprlp_last_error(). */
+int hprlp_batched_solver_solve_stream_device(hprlp_batched_solver *h, int count, int width, const double *dC, const double *dAL,
+                                             const double *dAU, const double *dl, const double *du, const double *obj_constants,
+                                             const HPRLP_parameters *param, const double *dX0, const double *dY0,
+                                             const hprlp_detection *det, hprlp_batched_certificates *certs, void *stream, double *dx,
+                                             double *dy, double *dz, hprlp_batched_scalars *out);
+/* of the last successful stream call of either kind:
+ * {device bytes the call held for queue VECTORS (host entry: the staged queue; device entry: 0),
+ *  device bytes of its result / ray block, device bytes of per-problem scalars, partials and tables, pinned host bytes} */
+int hprlp_batched_solver_stream_memory(hprlp_batched_solver *h, long out[4]);
 /* The norm rule of the HOST entry of this handle: 0 = the reference's long double sums (the default), 1 = the tree rule. */
 int hprlp_batched_solver_set_norms(hprlp_batched_solver *h, int rule);
 /* out (7 x B): b_scale, c_scale, norm_b, norm_c, norm_b_org, norm_c_org, first sigma of the last successful solve, either entry.
