@@ -1,5 +1,5 @@
-// batch_prep.cpp -- see batch_prep.h.  Host only.  The order of the multiplications and divisions below is part of the result:
-// (v * cn) / b_scale is not v * (cn / b_scale), and tests/test_batch_prep.py holds every one of them to its bits.
+// batch_prep.cpp -- see batch_prep.h.  Host only.  The arithmetic of every element and scalar is batch_units.h's, the order of its
+// operations included; tests/test_batch_prep.py holds every one of them to its bits.
 #include "batch_prep.h"
 
 #include <algorithm>
@@ -76,13 +76,6 @@ void from_panel(const std::vector<double> &panel, int rows, int B, const Geo &g,
 
 namespace {
 
-// b_i = max(|AL_i|, |AU_i|), an infinite side counting 0
-inline double bound_value(double lo, double hi) {
-    const double a = (std::isinf(lo) && lo < 0) ? 0.0 : std::abs(lo);
-    const double b = (std::isinf(hi) && hi > 0) ? 0.0 : std::abs(hi);
-    return std::max(a, b);
-}
-
 // the tree rule (batch_prep.h) for the values value(0) .. value(rows - 1)
 template <class F>
 double tree_sum_of_squares(int rows, F value) {
@@ -103,20 +96,22 @@ double tree_sum_of_squares(int rows, F value) {
     return total;
 }
 
-double bound_norm_host(const double *AL, const double *AU, int m, size_t off, int rule) {  // :332-345
-    if (rule == kNormRuleTree) return std::sqrt(tree_sum_of_squares(m, [&](int i) { return bound_value(AL[off + i], AU[off + i]); }));
+// the sum of squares of value(0) .. value(rows - 1) by either rule
+template <class F>
+double sum_of_squares(int rows, int rule, F value) {
+    if (rule == kNormRuleTree) return tree_sum_of_squares(rows, value);
     long double sum = 0.0;
-    for (int i = 0; i < m; ++i) {
-        const double v = bound_value(AL[off + i], AU[off + i]);
+    for (int i = 0; i < rows; ++i) {
+        const double v = value(i);
         sum += static_cast<long double>(v) * v;
     }
-    return std::sqrt(static_cast<double>(sum));
+    return static_cast<double>(sum);
 }
-double column_norm_host(const double *X, int n, size_t off, int rule) {  // :347-354
-    if (rule == kNormRuleTree) return std::sqrt(tree_sum_of_squares(n, [&](int i) { return X[off + i]; }));
-    long double sum = 0.0;
-    for (int i = 0; i < n; ++i) sum += static_cast<long double>(X[off + i]) * X[off + i];
-    return std::sqrt(static_cast<double>(sum));
+double bound_squares(const double *AL, const double *AU, int m, size_t off, int rule) {  // :332-345
+    return sum_of_squares(m, rule, [&](int i) { return bound_value(AL[off + i], AU[off + i]); });
+}
+double column_squares(const double *X, int n, size_t off, int rule) {  // :347-354
+    return sum_of_squares(n, rule, [&](int i) { return X[off + i]; });
 }
 
 }  // namespace
@@ -134,51 +129,53 @@ BatchData prepare_batch(int m, int n, int B, const double *C, const double *AL, 
     for (std::vector<double> *p : {&d.norm_b, &d.norm_c, &d.norm_b_org, &d.norm_c_org, &d.objc}) p->assign(B, 0.0);
     for (int k = 0; k < B; ++k) {
         const size_t om = static_cast<size_t>(k) * m, on = static_cast<size_t>(k) * n;
-        d.norm_b_org[k] = 1.0 + bound_norm_host(hAL.data(), hAU.data(), m, om, norm_rule);
-        d.norm_c_org[k] = 1.0 + column_norm_host(hC.data(), n, on, norm_rule);
-        for (int i = 0; i < m; ++i) { hAL[om + i] /= rn[i]; hAU[om + i] /= rn[i]; }
-        for (int i = 0; i < n; ++i) { hC[on + i] /= cn[i]; hL[on + i] *= cn[i]; hU[on + i] *= cn[i]; }
+        d.norm_b_org[k] = one_plus_norm(bound_squares(hAL.data(), hAU.data(), m, om, norm_rule));
+        d.norm_c_org[k] = one_plus_norm(column_squares(hC.data(), n, on, norm_rule));
+        for (int i = 0; i < m; ++i) { hAL[om + i] = over_norm(hAL[om + i], rn[i]); hAU[om + i] = over_norm(hAU[om + i], rn[i]); }
+        for (int i = 0; i < n; ++i) {
+            hC[on + i] = over_norm(hC[on + i], cn[i]);
+            hL[on + i] = times_norm(hL[on + i], cn[i]);
+            hU[on + i] = times_norm(hU[on + i], cn[i]);
+        }
     }
     if (use_bc_scaling) {
         for (int k = 0; k < B; ++k) {
             const size_t om = static_cast<size_t>(k) * m, on = static_cast<size_t>(k) * n;
-            d.b_scale[k] = 1.0 + bound_norm_host(hAL.data(), hAU.data(), m, om, norm_rule);
-            d.c_scale[k] = 1.0 + column_norm_host(hC.data(), n, on, norm_rule);
-            for (int i = 0; i < m; ++i) { hAL[om + i] /= d.b_scale[k]; hAU[om + i] /= d.b_scale[k]; }
-            for (int i = 0; i < n; ++i) { hC[on + i] /= d.c_scale[k]; hL[on + i] /= d.b_scale[k]; hU[on + i] /= d.b_scale[k]; }
+            const double bs = d.b_scale[k] = one_plus_norm(bound_squares(hAL.data(), hAU.data(), m, om, norm_rule));
+            const double cs = d.c_scale[k] = one_plus_norm(column_squares(hC.data(), n, on, norm_rule));
+            for (int i = 0; i < m; ++i) { hAL[om + i] = by_scale(hAL[om + i], bs); hAU[om + i] = by_scale(hAU[om + i], bs); }
+            for (int i = 0; i < n; ++i) {
+                hC[on + i] = by_scale(hC[on + i], cs);
+                hL[on + i] = by_scale(hL[on + i], bs);
+                hU[on + i] = by_scale(hU[on + i], bs);
+            }
         }
     }
     for (int k = 0; k < B; ++k) {
         const size_t om = static_cast<size_t>(k) * m, on = static_cast<size_t>(k) * n;
-        d.norm_b[k] = bound_norm_host(hAL.data(), hAU.data(), m, om, norm_rule);
-        d.norm_c[k] = column_norm_host(hC.data(), n, on, norm_rule);
-        for (int i = 0; i < m; ++i) {
-            if (std::isinf(hAL[om + i]) && hAL[om + i] < 0) hAL[om + i] = -kInfReplacement;
-            if (std::isinf(hAU[om + i]) && hAU[om + i] > 0) hAU[om + i] = kInfReplacement;
-        }
-        for (int i = 0; i < n; ++i) {
-            if (std::isinf(hL[on + i]) && hL[on + i] < 0) hL[on + i] = -kInfReplacement;
-            if (std::isinf(hU[on + i]) && hU[on + i] > 0) hU[on + i] = kInfReplacement;
-        }
+        d.norm_b[k] = std::sqrt(bound_squares(hAL.data(), hAU.data(), m, om, norm_rule));
+        d.norm_c[k] = std::sqrt(column_squares(hC.data(), n, on, norm_rule));
+        for (int i = 0; i < m; ++i) { hAL[om + i] = lower_replaced(hAL[om + i]); hAU[om + i] = upper_replaced(hAU[om + i]); }
+        for (int i = 0; i < n; ++i) { hL[on + i] = lower_replaced(hL[on + i]); hU[on + i] = upper_replaced(hU[on + i]); }
         d.objc[k] = obj_constants ? obj_constants[k] : model_obj_constant;
-        if (d.norm_b[k] > 1.0e-8 && d.norm_c[k] > 1.0e-8) d.sigma[k] = d.norm_b[k] / d.norm_c[k];
+        d.sigma[k] = first_sigma(d.norm_b[k], d.norm_c[k]);
     }
     return d;
 }
 
 void start_to_scaled(double *v, int rows, int B, const double *norm, const std::vector<double> &scale) {
     for (int k = 0; k < B; ++k)
-        for (int i = 0; i < rows; ++i) v[static_cast<size_t>(k) * rows + i] = (v[static_cast<size_t>(k) * rows + i] * norm[i]) / scale[k];
+        for (int i = 0; i < rows; ++i) v[static_cast<size_t>(k) * rows + i] = start_to_scaled(v[static_cast<size_t>(k) * rows + i], norm[i], scale[k]);
 }
 
 void point_to_caller(double *v, int rows, int B, const double *norm, const std::vector<double> &scale) {
     for (int k = 0; k < B; ++k)
-        for (int i = 0; i < rows; ++i) v[static_cast<size_t>(k) * rows + i] = (v[static_cast<size_t>(k) * rows + i] / norm[i]) * scale[k];
+        for (int i = 0; i < rows; ++i) v[static_cast<size_t>(k) * rows + i] = point_to_caller(v[static_cast<size_t>(k) * rows + i], norm[i], scale[k]);
 }
 
 void reduced_cost_to_caller(double *z, int n, int B, const double *cn, const std::vector<double> &c_scale) {
     for (int k = 0; k < B; ++k)
-        for (int i = 0; i < n; ++i) z[static_cast<size_t>(k) * n + i] = (z[static_cast<size_t>(k) * n + i] * cn[i]) * c_scale[k];
+        for (int i = 0; i < n; ++i) z[static_cast<size_t>(k) * n + i] = reduced_cost_to_caller(z[static_cast<size_t>(k) * n + i], cn[i], c_scale[k]);
 }
 
 }  // namespace hprlp

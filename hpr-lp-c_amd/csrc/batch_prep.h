@@ -1,6 +1,6 @@
 // batch_prep.h -- the host side of solve_batched that needs no device: the panel geometry (shared with the kernels of
-// batched.hip), the per-member scaling of a batch's vectors, the maps between the caller's units and scaled units, and the
-// allocation of the results.  Plain host code: no HIP header, no HIP call; hprlp_batched_prepare_host (abi.cpp) runs it on
+// batched.hip), the per-member scaling of a batch's vectors, the maps between the caller's units and scaled units (per element:
+// batch_units.h, which the kernels call too), and the allocation of the results.  Plain host code: no HIP header, no HIP call; hprlp_batched_prepare_host (abi.cpp) runs it on
 // plain arrays, so that its arithmetic can be held to a restatement bit for bit without a GPU (tests/test_batch_prep.py).
 #pragma once
 
@@ -8,6 +8,7 @@
 #include <cstddef>
 #include <vector>
 
+#include "batch_units.h"
 #include "structs.h"
 
 namespace hprlp {
@@ -17,7 +18,6 @@ HPRLP_batched_results make_batched_error(const char *status, int m, int n, int B
 // ... and one with all eight arrays for B members (status zeroed); throws when the host allocation fails
 HPRLP_batched_results alloc_batched_results(int m, int n, int B);
 
-constexpr double kInfReplacement = 1.0e100;  // reference batched_solver.cu:17
 
 // ---- panel geometry ------------------------------------------------------------------------------------------------------
 // thread -> (row slot, problem): lane l of a wave handles sub-row l / Bw and problem chunk*Bw + l % Bw, Bw = Bc = the
@@ -52,7 +52,7 @@ struct BatchData {
     int m = 0, n = 0, B = 0;
     std::vector<double> C, AL, AU, L, U;  // column-major, n x B / m x B; infinite row sides and bounds are +-kInfReplacement
     std::vector<double> b_scale, c_scale, norm_b, norm_c, norm_b_org, norm_c_org, objc;  // per member
-    std::vector<double> sigma;            // the first sigma: norm_b / norm_c where both exceed 1e-8, else 1
+    std::vector<double> sigma;            // the first sigma (batch_units.h: first_sigma)
 };
 // The per-member scalar vectors of a BatchData, enumerated once: the seven that a device-entry call computes where the batch lies,
 // in the order in which it stores them (batched.hip: DataScalar), then objc.
@@ -88,12 +88,12 @@ BatchData prepare_batch(int m, int n, int B, const double *C, const double *AL, 
                         const double *obj_constants, double model_obj_constant, const double *rn, const double *cn,
                         bool use_bc_scaling, int norm_rule = kNormRuleReference);
 
-// ---- caller's units <-> scaled units, column-major rows x B in place ------------------------------------------------------------
-// a start: X0 -> (x * cn) / b_scale[k], Y0 -> (y * rn) / c_scale[k]
+// ---- caller's units <-> scaled units, column-major rows x B in place: batch_units.h's maps of the same names, element by element --
+// a start: X0 with cn and b_scale, Y0 with rn and c_scale
 void start_to_scaled(double *v, int rows, int B, const double *norm, const std::vector<double> &scale);
-// a solution: x = (X / cn) * b_scale[k], y = (Y / rn) * c_scale[k] ...
+// a solution: x with cn and b_scale, y with rn and c_scale ...
 void point_to_caller(double *v, int rows, int B, const double *norm, const std::vector<double> &scale);
-// ... and z = (Z * cn) * c_scale[k]
+// ... and z
 void reduced_cost_to_caller(double *z, int n, int B, const double *cn, const std::vector<double> &c_scale);
 
 }  // namespace hprlp

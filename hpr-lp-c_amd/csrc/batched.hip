@@ -820,8 +820,8 @@ struct PanelOut {
     const double *scale[3];  // b_scale, c_scale, c_scale (per member)
     int rows[3];
 };
-// The first B members of X_bar / Y_bar / Z_bar in the caller's units, column-major: x = (X / cn) * b_scale[k],
-// y = (Y / rn) * c_scale[k] (point_to_caller) and z = (Z * cn) * c_scale[k] (reduced_cost_to_caller), in that operation order.
+// The first B members of X_bar / Y_bar / Z_bar in the caller's units, column-major: x and y by point_to_caller, z by
+// reduced_cost_to_caller (batch_units.h).
 __global__ void __launch_bounds__(256) kb_panel_out(PanelOut a, int B, Geo g) {
     __shared__ double tile[kPanelTile][kPanelTile + 1];  // [member][row]
     const int v = blockIdx.z, rows = a.rows[v];
@@ -839,7 +839,7 @@ __global__ void __launch_bounds__(256) kb_panel_out(PanelOut a, int B, Geo g) {
         double r = 0.0;
         if (k < B && i < rows) {
             const double p = src[pidx(g, k / g.Bw, rows, i, k % g.Bw)];
-            r = (v == 2 ? p * norm[i] : p / norm[i]) * scale[k];
+            r = v == 2 ? reduced_cost_to_caller(p, norm[i], scale[k]) : point_to_caller(p, norm[i], scale[k]);
         }
         tile[t.kl][t.il] = r;
     }
@@ -852,10 +852,10 @@ __global__ void __launch_bounds__(256) kb_panel_out(PanelOut a, int B, Geo g) {
     }
 }
 
-// carry: every member starts from the previous batch's solution of the same member.  Per element the composition of the results'
-// map with the previous batch's scales and start_to_scaled with this batch's, each rounding kept: x = (Xb / cn) * b_old[k], then
-// X = (x * cn) / b_new[k]; the same for Y with rn and the c scales.  Reads X_bar / Y_bar in place (before they are zeroed), writes
-// X / Y; padding members get 0.0.
+// carry: every member starts from the previous batch's solution of the same member.  Per element the composition of
+// point_to_caller with the previous batch's scales and start_to_scaled with this batch's (batch_units.h), each rounding kept: X with
+// cn and the b scales, Y with rn and the c scales.  Reads X_bar / Y_bar in place (before they are zeroed), writes X / Y; padding
+// members get 0.0.
 __global__ void __launch_bounds__(256) kb_carry_start(int n, int m, int B, Geo g, const double *Xb, const double *Yb, double *X, double *Y,
                                                       const double *col_norm, const double *row_norm, const double *b_old,
                                                       const double *b_new, const double *c_old, const double *c_new) {
@@ -869,14 +869,14 @@ __global__ void __launch_bounds__(256) kb_carry_start(int n, int m, int B, Geo g
     for (int r = r0; r < n; r += rs) {
         const size_t t = pidx(g, blk.chunk, n, r, kl);
         const double cn = col_norm[r];
-        const double x = (Xb[t] / cn) * bo;
-        X[t] = live ? (x * cn) / bn : 0.0;
+        const double x = point_to_caller(Xb[t], cn, bo);
+        X[t] = live ? start_to_scaled(x, cn, bn) : 0.0;
     }
     for (int r = r0; r < m; r += rs) {
         const size_t t = pidx(g, blk.chunk, m, r, kl);
         const double rn = row_norm[r];
-        const double y = (Yb[t] / rn) * co;
-        Y[t] = live ? (y * rn) / cw : 0.0;
+        const double y = point_to_caller(Yb[t], rn, co);
+        Y[t] = live ? start_to_scaled(y, rn, cw) : 0.0;
     }
 }
 
@@ -955,9 +955,9 @@ struct SlotOut {
     const double *scale[kSlotOutVectors];  // per SLOT: b_scale / c_scale
     int rows[kSlotOutVectors], map[kSlotOutVectors];
 };
-// The listed slots' columns into column `problem` of the result block.  x, y, z in the caller's units by kb_panel_out's map:
-// (X / cn) * b_scale, (Y / rn) * c_scale, (Z * cn) * c_scale, in that operation order; the rays as they are (finish_certificate
-// maps them on the host).  grid (ceil(max rows * np / 256), vectors).
+// The listed slots' columns into column `problem` of the result block.  x, y, z in the caller's units by point_to_caller and
+// reduced_cost_to_caller (batch_units.h), as kb_panel_out has them; the rays as they are (finish_certificate maps them on the host).
+// grid (ceil(max rows * np / 256), vectors).
 __global__ void __launch_bounds__(256) kb_slot_out(SlotOut a, const SlotPair *pairs, int np, Geo g) {
     const int v = blockIdx.y, rows = a.rows[v];
     const long e = static_cast<long>(blockIdx.x) * 256 + threadIdx.x;
@@ -966,26 +966,25 @@ __global__ void __launch_bounds__(256) kb_slot_out(SlotOut a, const SlotPair *pa
     const SlotPair pr = pairs[e % np];
     const double p = a.src[v][slot_elem(g, rows, static_cast<int>(i), pr.slot)];
     double r = p;
-    if (a.map[v] == SLOT_OUT_POINT) r = (p / a.norm[v][i]) * a.scale[v][pr.slot];
-    else if (a.map[v] == SLOT_OUT_REDUCED_COST) r = (p * a.norm[v][i]) * a.scale[v][pr.slot];
+    if (a.map[v] == SLOT_OUT_POINT) r = point_to_caller(p, a.norm[v][i], a.scale[v][pr.slot]);
+    else if (a.map[v] == SLOT_OUT_REDUCED_COST) r = reduced_cost_to_caller(p, a.norm[v][i], a.scale[v][pr.slot]);
     a.dst[v][static_cast<size_t>(pr.problem) * rows + i] = r;
 }
 
 // ---- a batch from device memory (DESIGN.md "Device-resident batches") ------------------------------------------------------------
-// prepare_batch (batch_prep.cpp) on the device, operation by operation, the norms by the tree rule of batch_prep.h.  The caller's
-// vectors are column-major rows x B, so a segment of one member is one contiguous run: a 256-thread workgroup per (segment,
-// member, vector group) reads it coalesced, thread j is lane j of the rule, and the workgroup leaves one partial per sum.  Group 0:
-// the n-row vectors C, l, u; group 1: the m-row vectors AL, AU.  Partial (group g, sum a, member k, segment s) sits at
-// part[((g * 2 + a) * B + k) * nseg + s], nseg = the segments of the longer vector.  The per-member scalars live in `scal`,
-// 7 x B in BATCH_SCALARS' order (b_scale, c_scale, norm_b, norm_c, norm_b_org, norm_c_org, sigma), followed by two flag words.
+// prepare_batch (batch_prep.cpp) on the device: the same element and scalar functions (batch_units.h) in the same order, the norms
+// by the tree rule of batch_prep.h.  The caller's vectors are column-major rows x B, so a segment of one member is one contiguous
+// run: a 256-thread workgroup per (segment, member, vector group) reads it coalesced, thread j is lane j of the rule, and the
+// workgroup leaves one partial per sum.  Group 0: the n-row vectors C, l, u; group 1: the m-row vectors AL, AU.  Partial (group g,
+// sum a, member k, segment s) sits at part[((g * 2 + a) * B + k) * nseg + s], nseg = the segments of the longer vector.  The
+// per-member scalars live in `scal`, 7 x B in BATCH_SCALARS' order (b_scale, c_scale, norm_b, norm_c, norm_b_org, norm_c_org,
+// sigma), followed by two flag words.
+// Both norm passes come in two forms.  A batch (DESIGN.md "Device-resident batches") is staged: the passes store what they compute
+// into the staging block's regions.  A queue (DESIGN.md "Device-resident streams") is not: the same loads and operations, nothing
+// stored beside the partials -- no scaled copy of the queue exists, a problem is scaled when it enters a slot (kb_slot_scale).
+// grid (nseg, members of the slice, 2); k0: the slice's first member (a grid's y dimension holds 65535; a batch has one slice).
 enum DataScalar : int { DS_B_SCALE = 0, DS_C_SCALE, DS_NORM_B, DS_NORM_C, DS_NORM_B_ORG, DS_NORM_C_ORG, DS_SIGMA, DS_COUNT };
 enum DataFlag : int { DF_START = 0, DF_RESULT, DF_COUNT };  // a non-finite entry in X0 / Y0; in the x / y of the results
-
-__device__ __forceinline__ double bound_value_dev(double lo, double hi) {  // batch_prep.cpp: bound_value
-    const double a = (isinf(lo) && lo < 0) ? 0.0 : fabs(lo);
-    const double b = (isinf(hi) && hi > 0) ? 0.0 : fabs(hi);
-    return fmax(a, b);
-}
 
 // The fold of the tree rule for NSUM sums at once: acc[i] of thread j is lane j's sum.  Strides 128 and 64 cross the waves
 // through LDS; strides 32 .. 1 stay inside wave 0 (lane j takes lane j + stride's value: for j < stride that is a[j] += a[j + stride]).
@@ -1015,15 +1014,17 @@ __device__ __forceinline__ void tree_fold(double (&acc)[NSUM]) {
 }
 
 struct DataIn {
-    const double *C, *L, *U, *AL, *AU;  // the caller's, column-major
-    double *oC, *oL, *oU, *oAL, *oAU;   // the staging block's regions
+    const double *C, *L, *U, *AL, *AU;  // the caller's, column-major (a queue: L, U unread)
+    double *oC, *oL, *oU, *oAL, *oAU;   // the staging block's regions (a queue: none)
     const double *cn, *rn;
     double *part;
     int n, m, nseg;
 };
-// grid (nseg, B, 2).  AL, AU /= rn; C /= cn; l, u *= cn; sum 0: the caller's values' sum of squares, sum 1: the scaled values'.
-__global__ void __launch_bounds__(kNormLanes) kb_data_in(DataIn a, int B) {
-    const int s = blockIdx.x, k = blockIdx.y, g = blockIdx.z;
+// The first step by cn / rn.  sum 0: the caller's values' sum of squares, sum 1: the values' after the step.  STAGED: the values
+// after the step go to the regions.
+template <bool STAGED>
+__global__ void __launch_bounds__(kNormLanes) kb_data_in(DataIn a, int B, int k0) {
+    const int s = blockIdx.x, k = k0 + blockIdx.y, g = blockIdx.z;
     const int rows = g ? a.m : a.n;
     const int i0 = s * kNormSeg;
     if (i0 >= rows) return;  // (uniform per workgroup)
@@ -1036,27 +1037,31 @@ __global__ void __launch_bounds__(kNormLanes) kb_data_in(DataIn a, int B) {
             const double c = a.C[base + i];
             const double t0 = c * c;
             acc[0] += t0;
-            const double cs = c / nrm;
+            const double cs = over_norm(c, nrm);
             const double t1 = cs * cs;
             acc[1] += t1;
-            a.oC[base + i] = cs;
-            a.oL[base + i] = a.L[base + i] * nrm;
-            a.oU[base + i] = a.U[base + i] * nrm;
+            if (STAGED) {
+                a.oC[base + i] = cs;
+                a.oL[base + i] = times_norm(a.L[base + i], nrm);
+                a.oU[base + i] = times_norm(a.U[base + i], nrm);
+            }
         }
     } else {
         for (int i = i0 + threadIdx.x; i < end; i += kNormLanes) {
             const double nrm = a.rn[i];
             double lo = a.AL[base + i], hi = a.AU[base + i];
-            const double v0 = bound_value_dev(lo, hi);
+            const double v0 = bound_value(lo, hi);
             const double t0 = v0 * v0;
             acc[0] += t0;
-            lo /= nrm;
-            hi /= nrm;
-            const double v1 = bound_value_dev(lo, hi);
+            lo = over_norm(lo, nrm);
+            hi = over_norm(hi, nrm);
+            const double v1 = bound_value(lo, hi);
             const double t1 = v1 * v1;
             acc[1] += t1;
-            a.oAL[base + i] = lo;
-            a.oAU[base + i] = hi;
+            if (STAGED) {
+                a.oAL[base + i] = lo;
+                a.oAU[base + i] = hi;
+            }
         }
     }
     tree_fold<2>(acc);
@@ -1078,27 +1083,30 @@ __device__ __forceinline__ double segment_total(const double *part, int g, int a
 __global__ void __launch_bounds__(256) kb_data_scales(const double *part, int B, int n, int m, int nseg, int use_bc, double *scal) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= B) return;
-    scal[DS_NORM_C_ORG * B + k] = 1.0 + sqrt(segment_total(part, 0, 0, B, k, nseg, n));
-    scal[DS_NORM_B_ORG * B + k] = 1.0 + sqrt(segment_total(part, 1, 0, B, k, nseg, m));
-    scal[DS_C_SCALE * B + k] = use_bc ? 1.0 + sqrt(segment_total(part, 0, 1, B, k, nseg, n)) : 1.0;
-    scal[DS_B_SCALE * B + k] = use_bc ? 1.0 + sqrt(segment_total(part, 1, 1, B, k, nseg, m)) : 1.0;
+    scal[DS_NORM_C_ORG * B + k] = one_plus_norm(segment_total(part, 0, 0, B, k, nseg, n));
+    scal[DS_NORM_B_ORG * B + k] = one_plus_norm(segment_total(part, 1, 0, B, k, nseg, m));
+    scal[DS_C_SCALE * B + k] = use_bc ? one_plus_norm(segment_total(part, 0, 1, B, k, nseg, n)) : 1.0;
+    scal[DS_B_SCALE * B + k] = use_bc ? one_plus_norm(segment_total(part, 1, 1, B, k, nseg, m)) : 1.0;
 }
 
 struct DataBc {
-    double *C, *L, *U, *AL, *AU;  // the staging block's regions, in place
-    const double *X0, *Y0;        // the caller's starts (null: none) ...
-    double *oX0, *oY0;            // ... and their regions
+    const double *C, *L, *U, *AL, *AU;  // STAGED: the staging block's regions after the first pass; else the caller's (L, U unread)
+    double *oC, *oL, *oU, *oAL, *oAU;   // STAGED: the same regions (the pass works in place); else none
+    const double *X0, *Y0;              // the caller's starts (null: none) ...
+    double *oX0, *oY0;                  // ... and, STAGED, their regions
     const double *cn, *rn;
     const double *scal;
     double *part;
     int *flags;
     int n, m, nseg;
 };
-// grid (nseg, B, 2).  The divisions by the scales kb_data_scales left (by 1.0 without use_bc_scaling: exact), sum 0: the final
-// values' sum of squares, and only then +-kInfReplacement for infinite sides and bounds.  The starts as start_to_scaled has them:
-// X0 -> (x * cn) / b_scale[k], Y0 -> (y * rn) / c_scale[k]; a non-finite entry of the caller's raises flags[DF_START].
-__global__ void __launch_bounds__(kNormLanes) kb_data_bc(DataBc a, int B) {
-    const int s = blockIdx.x, k = blockIdx.y, g = blockIdx.z;
+// The second step by the scales kb_data_scales left (by 1.0 without use_bc_scaling: exact); sum 0: the final values' sum of
+// squares, before any +-kInfReplacement.  A non-finite entry of the caller's starts raises flags[DF_START].  STAGED: reads the
+// regions the first pass wrote and rewrites them, infinite sides and bounds replaced, and the starts go to their regions by
+// start_to_scaled.  Not STAGED: reads the caller's arrays, applies the first step again and stores nothing.
+template <bool STAGED>
+__global__ void __launch_bounds__(kNormLanes) kb_data_bc(DataBc a, int B, int k0) {
+    const int s = blockIdx.x, k = k0 + blockIdx.y, g = blockIdx.z;
     const int rows = g ? a.m : a.n;
     const int i0 = s * kNormSeg;
     if (i0 >= rows) return;
@@ -1109,35 +1117,37 @@ __global__ void __launch_bounds__(kNormLanes) kb_data_bc(DataBc a, int B) {
     bool bad = false;
     if (g == 0) {
         for (int i = i0 + threadIdx.x; i < end; i += kNormLanes) {
-            const double c = a.C[base + i] / cs;
+            const double c1 = STAGED ? a.C[base + i] : over_norm(a.C[base + i], a.cn[i]);
+            const double c = by_scale(c1, cs);
             const double t = c * c;
             acc[0] += t;
-            a.C[base + i] = c;
-            double lo = a.L[base + i] / bs, hi = a.U[base + i] / bs;
-            if (isinf(lo) && lo < 0) lo = -kInfReplacement;
-            if (isinf(hi) && hi > 0) hi = kInfReplacement;
-            a.L[base + i] = lo;
-            a.U[base + i] = hi;
+            if (STAGED) {
+                a.oC[base + i] = c;
+                a.oL[base + i] = lower_replaced(by_scale(a.L[base + i], bs));
+                a.oU[base + i] = upper_replaced(by_scale(a.U[base + i], bs));
+            }
             if (a.X0) {
                 const double x = a.X0[base + i];
                 bad = bad || !isfinite(x);
-                a.oX0[base + i] = (x * a.cn[i]) / bs;
+                if (STAGED) a.oX0[base + i] = start_to_scaled(x, a.cn[i], bs);
             }
         }
     } else {
         for (int i = i0 + threadIdx.x; i < end; i += kNormLanes) {
-            double lo = a.AL[base + i] / bs, hi = a.AU[base + i] / bs;
-            const double v = bound_value_dev(lo, hi);
+            const double lo1 = STAGED ? a.AL[base + i] : over_norm(a.AL[base + i], a.rn[i]);
+            const double hi1 = STAGED ? a.AU[base + i] : over_norm(a.AU[base + i], a.rn[i]);
+            const double lo = by_scale(lo1, bs), hi = by_scale(hi1, bs);
+            const double v = bound_value(lo, hi);
             const double t = v * v;
             acc[0] += t;
-            if (isinf(lo) && lo < 0) lo = -kInfReplacement;
-            if (isinf(hi) && hi > 0) hi = kInfReplacement;
-            a.AL[base + i] = lo;
-            a.AU[base + i] = hi;
+            if (STAGED) {
+                a.oAL[base + i] = lower_replaced(lo);
+                a.oAU[base + i] = upper_replaced(hi);
+            }
             if (a.Y0) {
                 const double y = a.Y0[base + i];
                 bad = bad || !isfinite(y);
-                a.oY0[base + i] = (y * a.rn[i]) / cs;
+                if (STAGED) a.oY0[base + i] = start_to_scaled(y, a.rn[i], cs);
             }
         }
     }
@@ -1146,28 +1156,23 @@ __global__ void __launch_bounds__(kNormLanes) kb_data_bc(DataBc a, int B) {
     if (threadIdx.x == 0) a.part[(static_cast<size_t>(g * 2) * B + k) * a.nseg + s] = acc[0];
 }
 
-// member k's norm_b, norm_c of the final vectors (sum 0 of the second pass) and its first sigma, into scal; returns sigma
-__device__ __forceinline__ double member_norms(const double *part, int B, int k, int n, int m, int nseg, double *scal) {
-    const double nc = sqrt(segment_total(part, 0, 0, B, k, nseg, n)), nb = sqrt(segment_total(part, 1, 0, B, k, nseg, m));
-    double sigma = 1.0;
-    if (nb > 1.0e-8 && nc > 1.0e-8) sigma = nb / nc;
-    scal[DS_NORM_B * B + k] = nb;
-    scal[DS_NORM_C * B + k] = nc;
-    scal[DS_SIGMA * B + k] = sigma;
-    return sigma;
-}
-
-// one thread per member of the PADDED batch: norm_b, norm_c of the final vectors, the first sigma, and the header of the staging
-// block as ws_fill reads it: sigma | b_scale | c_scale (padding members 1.0) | active (ints: 1 for a member, 0 for padding)
+// one thread per member of the PADDED batch: norm_b, norm_c of the final vectors (sum 0 of the second pass) and the first sigma
+// into scal, and, where hdr is given, the header of the staging block as ws_fill reads it: sigma | b_scale | c_scale (padding
+// members 1.0) | active (ints: 1 for a member, 0 for padding).  A queue has no header (its slots' is the host's) and no padding.
 __global__ void __launch_bounds__(256) kb_data_header(const double *part, int B, int Bp, int n, int m, int nseg, double *scal, double *hdr) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= Bp) return;
     double sigma = 1.0, bs = 1.0, cs = 1.0;
     if (k < B) {
-        sigma = member_norms(part, B, k, n, m, nseg, scal);
+        const double nc = sqrt(segment_total(part, 0, 0, B, k, nseg, n)), nb = sqrt(segment_total(part, 1, 0, B, k, nseg, m));
+        sigma = first_sigma(nb, nc);
+        scal[DS_NORM_B * B + k] = nb;
+        scal[DS_NORM_C * B + k] = nc;
+        scal[DS_SIGMA * B + k] = sigma;
         bs = scal[DS_B_SCALE * B + k];
         cs = scal[DS_C_SCALE * B + k];
     }
+    if (!hdr) return;
     hdr[k] = sigma;
     hdr[Bp + k] = bs;
     hdr[2 * Bp + k] = cs;
@@ -1184,109 +1189,10 @@ __global__ void __launch_bounds__(256) kb_flag_nonfinite(const double *x, size_t
 }
 
 // ---- a queue in device memory (DESIGN.md "Device-resident streams") ----------------------------------------------------------------
-// The per-problem scalars of a whole queue from the caller's arrays where they lie: the passes of kb_data_in and kb_data_bc, load
-// for load and operation for operation, but nothing is stored beside the partials -- no scaled copy of the queue exists.  A problem
-// is scaled when it enters a slot (kb_slot_scale).  grid (nseg, problems of the slice, 2); k0: the slice's first problem (a grid's
-// y dimension holds 65535); the partials and scalars are laid out for all `count` problems as the batch's are for B.
-struct QueueIn {
-    const double *C, *AL, *AU;  // the caller's, column-major rows x count
-    const double *cn, *rn;
-    double *part;
-    int n, m, nseg;
-};
-// sum 0: the caller's values' sum of squares; sum 1: the values' after the cn / rn step
-__global__ void __launch_bounds__(kNormLanes) kb_queue_norms(QueueIn a, int count, int k0) {
-    const int s = blockIdx.x, k = k0 + blockIdx.y, g = blockIdx.z;
-    const int rows = g ? a.m : a.n;
-    const int i0 = s * kNormSeg;
-    if (i0 >= rows) return;  // (uniform per workgroup)
-    const int end = min(rows, i0 + kNormSeg);
-    const size_t base = static_cast<size_t>(k) * rows;
-    double acc[2] = {0.0, 0.0};
-    if (g == 0) {
-        for (int i = i0 + threadIdx.x; i < end; i += kNormLanes) {
-            const double c = a.C[base + i];
-            const double t0 = c * c;
-            acc[0] += t0;
-            const double cs = c / a.cn[i];
-            const double t1 = cs * cs;
-            acc[1] += t1;
-        }
-    } else {
-        for (int i = i0 + threadIdx.x; i < end; i += kNormLanes) {
-            const double nrm = a.rn[i];
-            double lo = a.AL[base + i], hi = a.AU[base + i];
-            const double v0 = bound_value_dev(lo, hi);
-            const double t0 = v0 * v0;
-            acc[0] += t0;
-            lo /= nrm;
-            hi /= nrm;
-            const double v1 = bound_value_dev(lo, hi);
-            const double t1 = v1 * v1;
-            acc[1] += t1;
-        }
-    }
-    tree_fold<2>(acc);
-    if (threadIdx.x == 0) {
-        a.part[(static_cast<size_t>(g * 2 + 0) * count + k) * a.nseg + s] = acc[0];
-        a.part[(static_cast<size_t>(g * 2 + 1) * count + k) * a.nseg + s] = acc[1];
-    }
-}
-
-struct QueueBc {
-    const double *C, *AL, *AU, *X0, *Y0;  // the caller's (X0 / Y0 null: none)
-    const double *cn, *rn;
-    const double *scal;
-    double *part;
-    int *flags;
-    int n, m, nseg;
-};
-// sum 0: the final values' sum of squares, (c / cn) / c_scale and bound_value of (AL / rn) / b_scale, (AU / rn) / b_scale, before
-// any +-kInfReplacement; a non-finite entry of the caller's starts raises flags[DF_START]
-__global__ void __launch_bounds__(kNormLanes) kb_queue_norms_bc(QueueBc a, int count, int k0) {
-    const int s = blockIdx.x, k = k0 + blockIdx.y, g = blockIdx.z;
-    const int rows = g ? a.m : a.n;
-    const int i0 = s * kNormSeg;
-    if (i0 >= rows) return;
-    const int end = min(rows, i0 + kNormSeg);
-    const size_t base = static_cast<size_t>(k) * rows;
-    const double bs = a.scal[DS_B_SCALE * count + k], cs = a.scal[DS_C_SCALE * count + k];
-    double acc[1] = {0.0};
-    bool bad = false;
-    if (g == 0) {
-        for (int i = i0 + threadIdx.x; i < end; i += kNormLanes) {
-            const double c1 = a.C[base + i] / a.cn[i];
-            const double c = c1 / cs;
-            const double t = c * c;
-            acc[0] += t;
-            if (a.X0) bad = bad || !isfinite(a.X0[base + i]);
-        }
-    } else {
-        for (int i = i0 + threadIdx.x; i < end; i += kNormLanes) {
-            const double nrm = a.rn[i];
-            const double lo1 = a.AL[base + i] / nrm, hi1 = a.AU[base + i] / nrm;
-            const double lo = lo1 / bs, hi = hi1 / bs;
-            const double v = bound_value_dev(lo, hi);
-            const double t = v * v;
-            acc[0] += t;
-            if (a.Y0) bad = bad || !isfinite(a.Y0[base + i]);
-        }
-    }
-    if (bad) a.flags[DF_START] = 1;  // (every writer writes the same word)
-    tree_fold<1>(acc);
-    if (threadIdx.x == 0) a.part[(static_cast<size_t>(g * 2) * count + k) * a.nseg + s] = acc[0];
-}
-
-// one thread per problem: norm_b, norm_c and the first sigma by kb_data_header's rule (there is no header: the slots' is the host's)
-__global__ void __launch_bounds__(256) kb_queue_sigma(const double *part, int count, int n, int m, int nseg, double *scal) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k < count) (void)member_norms(part, count, k, n, m, nseg, scal);
-}
-
 // The listed problems from the CALLER's arrays into their slots' columns in scaled units: kb_slot_in's geometry and table, and per
-// element the composition of kb_data_in and kb_data_bc, each rounding kept -- the cn / rn step (SF_TIMES_NORM: * norm[i], else
-// / norm[i]), then / b_scale[p] (SF_BY_C: / c_scale[p]), then -inf -> -kInfReplacement (SF_LOWER) or +inf -> +kInfReplacement
-// (SF_UPPER).  C: (c / cn) / cs; l, u: (v * cn) / bs; AL, AU: (v / rn) / bs; X0: (x * cn) / bs; Y0: (y * rn) / cs.
+// element the steps of batch_units.h that the two norm passes apply to a staged batch, each rounding kept -- the first by cn / rn
+// (SF_TIMES_NORM: times_norm, else over_norm), the second by b_scale[p] (SF_BY_C: c_scale[p]), then lower_replaced (SF_LOWER) or
+// upper_replaced (SF_UPPER).  A start is a bound without a replacement: times_norm and by_scale are start_to_scaled.
 enum SlotScaleOp : int { SF_TIMES_NORM = 1, SF_BY_C = 2, SF_LOWER = 4, SF_UPPER = 8 };
 struct SlotScale {
     const double *src[kPanelVectors];   // the caller's arrays, column-major rows x count
@@ -1303,10 +1209,10 @@ __global__ void __launch_bounds__(256) kb_slot_scale(SlotScale a, const SlotPair
     if (i >= rows) return;
     const SlotPair pr = pairs[e % np];
     const double x = a.src[v][static_cast<size_t>(pr.problem) * rows + i], nrm = a.norm[v][i];
-    const double x1 = (op & SF_TIMES_NORM) ? x * nrm : x / nrm;
-    double r = x1 / ((op & SF_BY_C) ? a.q_cs[pr.problem] : a.q_bs[pr.problem]);
-    if ((op & SF_LOWER) && isinf(r) && r < 0) r = -kInfReplacement;
-    if ((op & SF_UPPER) && isinf(r) && r > 0) r = kInfReplacement;
+    const double x1 = (op & SF_TIMES_NORM) ? times_norm(x, nrm) : over_norm(x, nrm);
+    double r = by_scale(x1, (op & SF_BY_C) ? a.q_cs[pr.problem] : a.q_bs[pr.problem]);
+    if (op & SF_LOWER) r = lower_replaced(r);
+    if (op & SF_UPPER) r = upper_replaced(r);
     a.dst[v][slot_elem(g, rows, static_cast<int>(i), pr.slot)] = r;
 }
 
@@ -2061,59 +1967,43 @@ BatchData fetch_member_scalars(BatchWS &w, int B, const double *obj_constants, d
     return d;
 }
 
-// prepare_batch on the device: the caller's vectors (ordered on `stream`) into the regions r of the staging block in scaled units,
-// its header, and the per-member scalars on the host -- the BatchData a loop needs (it reads none of the vectors).
-BatchData device_prep(BatchWS &w, int B, int Bp, const Regions &r, const double *C, const double *AL, const double *AU, const double *l,
+// prepare_batch on the device, for B members whose vectors lie in device memory (ordered on `stream`): the per-member scalars on the
+// host -- the BatchData a loop needs (it reads none of the vectors) -- and DF_START for a non-finite start anywhere.  The two norm
+// passes run in slices of what one grid dimension takes.
+// r given (a batch): the vectors in scaled units into the regions r of the staging block, and its header for Bp padded members.
+// r null (a queue): nothing else; sigma, b_scale and c_scale stay in w.data_scal for the refills (kb_slot_clear, kb_slot_scale).
+BatchData device_prep(BatchWS &w, int B, int Bp, const Regions *r, const double *C, const double *AL, const double *AU, const double *l,
                       const double *u, const double *X0, const double *Y0, const double *obj_constants, double model_obj_constant,
                       bool use_bc, hipStream_t stream, hipEvent_t ready) {
+    constexpr int kGridSlice = 65535;
     const int m = w.m, n = w.n, nseg = norm_segments(std::max(n, m));
-    if (w.stage_d.n < r.end) w.stage_d.alloc(r.end);
+    if (r && w.stage_d.n < r->end) w.stage_d.alloc(r->end);
     data_buffers(w, B, nseg);
     HIP_CHECK(hipEventRecord(ready, stream));
     HIP_CHECK(hipStreamWaitEvent(w.stream, ready, 0));
-    double *sd = w.stage_d.p;
-    double *rC = sd + r.start[0], *rL = sd + r.start[1], *rU = sd + r.start[2], *rAL = sd + r.start[3], *rAU = sd + r.start[4];
-    double *rX = X0 ? sd + r.start[r.iX] : nullptr, *rY = Y0 ? sd + r.start[r.iY] : nullptr;
     int *flags = data_flags(w, B);
     HIP_CHECK(hipMemsetAsync(flags, 0, DF_COUNT * sizeof(int), w.stream));
     const double *cn = w.shared->col_norm.p, *rn = w.shared->row_norm.p;
-    const dim3 grid(nseg, B, 2);
-    hipLaunchKernelGGL(kb_data_in, grid, dim3(kNormLanes), 0, w.stream, DataIn{C, l, u, AL, AU, rC, rL, rU, rAL, rAU, cn, rn, w.data_part.p, n, m, nseg}, B);
+    double *sd = r ? w.stage_d.p : nullptr, *reg[kPanelVectors] = {};  // the header and the regions (a queue: none)
+    for (int v = 0; r && v < r->nvec; ++v) reg[v] = sd + r->start[v];
+    double *rX = r && X0 ? reg[r->iX] : nullptr, *rY = r && Y0 ? reg[r->iY] : nullptr;
+    const DataIn in{C, l, u, AL, AU, reg[0], reg[1], reg[2], reg[3], reg[4], cn, rn, w.data_part.p, n, m, nseg};
+    // the second pass reads what the first left: a batch's regions, or again the caller's arrays
+    const DataBc bc{r ? reg[0] : C, reg[1], reg[2], r ? reg[3] : AL, r ? reg[4] : AU, reg[0], reg[1], reg[2], reg[3], reg[4],
+                    X0, Y0, rX, rY, cn, rn, w.data_scal.p, w.data_part.p, flags, n, m, nseg};
+    const auto pass = [&](auto kernel, const auto &args) {
+        for (int k0 = 0; k0 < B; k0 += kGridSlice)
+            hipLaunchKernelGGL(kernel, dim3(nseg, std::min(kGridSlice, B - k0), 2), dim3(kNormLanes), 0, w.stream, args, B, k0);
+    };
+    pass(r ? kb_data_in<true> : kb_data_in<false>, in);
     hipLaunchKernelGGL(kb_data_scales, dim3((B + 255) / 256), dim3(256), 0, w.stream, static_cast<const double *>(w.data_part.p), B, n, m, nseg,
                        use_bc ? 1 : 0, w.data_scal.p);
-    hipLaunchKernelGGL(kb_data_bc, grid, dim3(kNormLanes), 0, w.stream,
-                       DataBc{rC, rL, rU, rAL, rAU, X0, Y0, rX, rY, cn, rn, w.data_scal.p, w.data_part.p, flags, n, m, nseg}, B);
-    hipLaunchKernelGGL(kb_data_header, dim3((Bp + 255) / 256), dim3(256), 0, w.stream, static_cast<const double *>(w.data_part.p), B, Bp, n, m,
-                       nseg, w.data_scal.p, sd);
+    pass(r ? kb_data_bc<true> : kb_data_bc<false>, bc);
+    const int members = r ? Bp : B;
+    hipLaunchKernelGGL(kb_data_header, dim3((members + 255) / 256), dim3(256), 0, w.stream, static_cast<const double *>(w.data_part.p), B,
+                       members, n, m, nseg, w.data_scal.p, sd);
     HIP_CHECK(hipGetLastError());
     return fetch_member_scalars(w, B, obj_constants, model_obj_constant);
-}
-
-// prepare_batch's scalars for a whole queue of `count` problems that lies in device memory (ordered on `stream`), and nothing else:
-// the two norm passes over the caller's arrays, in slices of what one grid dimension takes.  sigma, b_scale and c_scale stay in
-// w.data_scal for the refills (kb_slot_clear, kb_slot_scale); DF_START is raised for a non-finite start anywhere in the queue.
-BatchData queue_prep(BatchWS &w, int count, const double *C, const double *AL, const double *AU, const double *X0, const double *Y0,
-                     const double *obj_constants, double model_obj_constant, bool use_bc, hipStream_t stream, hipEvent_t ready) {
-    constexpr int kGridSlice = 65535;
-    const int m = w.m, n = w.n, nseg = norm_segments(std::max(n, m));
-    data_buffers(w, count, nseg);
-    HIP_CHECK(hipEventRecord(ready, stream));
-    HIP_CHECK(hipStreamWaitEvent(w.stream, ready, 0));
-    int *flags = data_flags(w, count);
-    HIP_CHECK(hipMemsetAsync(flags, 0, DF_COUNT * sizeof(int), w.stream));
-    const double *cn = w.shared->col_norm.p, *rn = w.shared->row_norm.p;
-    for (int k0 = 0; k0 < count; k0 += kGridSlice)
-        hipLaunchKernelGGL(kb_queue_norms, dim3(nseg, std::min(kGridSlice, count - k0), 2), dim3(kNormLanes), 0, w.stream,
-                           QueueIn{C, AL, AU, cn, rn, w.data_part.p, n, m, nseg}, count, k0);
-    hipLaunchKernelGGL(kb_data_scales, dim3((count + 255) / 256), dim3(256), 0, w.stream, static_cast<const double *>(w.data_part.p), count,
-                       n, m, nseg, use_bc ? 1 : 0, w.data_scal.p);
-    for (int k0 = 0; k0 < count; k0 += kGridSlice)
-        hipLaunchKernelGGL(kb_queue_norms_bc, dim3(nseg, std::min(kGridSlice, count - k0), 2), dim3(kNormLanes), 0, w.stream,
-                           QueueBc{C, AL, AU, X0, Y0, cn, rn, w.data_scal.p, w.data_part.p, flags, n, m, nseg}, count, k0);
-    hipLaunchKernelGGL(kb_queue_sigma, dim3((count + 255) / 256), dim3(256), 0, w.stream, static_cast<const double *>(w.data_part.p), count, n,
-                       m, nseg, w.data_scal.p);
-    HIP_CHECK(hipGetLastError());
-    return fetch_member_scalars(w, count, obj_constants, model_obj_constant);
 }
 
 // the device entry's results, straight into the caller's buffers; the flag word that comes back: x or y holds a non-finite entry
@@ -2213,7 +2103,7 @@ struct StreamRun {
         }
         sclr.SC = w.SC.p; sclr.ctl = w.ctl; sclr.bsc = w.bsc.p; sclr.csc = w.csc.p;
         sclr.q_sigma = qd; sclr.q_bs = qd + count; sclr.q_cs = qd + 2 * static_cast<size_t>(count);
-        if (dev) {  // (where queue_prep left them)
+        if (dev) {  // (where device_prep left them)
             const double *sc = w.data_scal.p;
             sclr.q_sigma = sc + static_cast<size_t>(DS_SIGMA) * count;
             sclr.q_bs = sc + static_cast<size_t>(DS_B_SCALE) * count;
@@ -2672,7 +2562,7 @@ void BatchedSolver::solve(int B, const double *C_in, const double *AL_in, const 
         const Regions regions(plan.Bp, n, m, B, X0 != nullptr, Y0 != nullptr);
         const size_t stage_count = dev ? 0 : regions.end;
         const BatchData data =
-            dev ? device_prep(w, B, plan.Bp, regions, C_in, AL_in, AU_in, l_in, u_in, X0, Y0, obj_constants, obj_constant,
+            dev ? device_prep(w, B, plan.Bp, &regions, C_in, AL_in, AU_in, l_in, u_in, X0, Y0, obj_constants, obj_constant,
                               actual.use_bc_scaling, static_cast<hipStream_t>(dev->stream), inputs_ready)
                 : prepare_batch(m, n, B, C_in, AL_in, AU_in, l_in, u_in, obj_constants, obj_constant, w.rn.data(), w.cn.data(),
                                 actual.use_bc_scaling, norm_rule);
@@ -2727,7 +2617,7 @@ void BatchedSolver::solve(int B, const double *C_in, const double *AL_in, const 
 // ---- streamed batches (DESIGN.md "Streamed batches": the rule, the local iteration numbers, the memory of a call) ----------------
 // `count` problems through W = min(width, count) slots of a workspace whose geometry is a plain solve's of W members.  The loop is
 // solve()'s; a member that ends at an evaluation hands its slot on within that event (StreamRun).  No panel moves: the graphs survive.
-// dev set (DESIGN.md "Device-resident streams"): the queue lies in device memory and is never staged -- queue_prep takes its scalars
+// dev set (DESIGN.md "Device-resident streams"): the queue lies in device memory and is never staged -- device_prep takes its scalars
 // where it lies, a problem is scaled on its way into a slot, and x, y, z go to the caller's buffers.
 void BatchedSolver::solve_stream(int count, int width, const double *C_in, const double *AL_in, const double *AU_in, const double *l_in,
                                  const double *u_in, const double *obj_constants, const HPRLP_parameters *p, const double *X0,
@@ -2755,8 +2645,8 @@ void BatchedSolver::solve_stream(int count, int width, const double *C_in, const
         //    scalars from where it lies, and the header
         const auto t_prep = time_now();
         const BatchData q =
-            dev ? queue_prep(w, count, C_in, AL_in, AU_in, X0, Y0, obj_constants, obj_constant, actual.use_bc_scaling,
-                             static_cast<hipStream_t>(dev->stream), inputs_ready)
+            dev ? device_prep(w, count, count, nullptr, C_in, AL_in, AU_in, l_in, u_in, X0, Y0, obj_constants, obj_constant,
+                              actual.use_bc_scaling, static_cast<hipStream_t>(dev->stream), inputs_ready)
                 : prepare_batch(m, n, count, C_in, AL_in, AU_in, l_in, u_in, obj_constants, obj_constant, w.rn.data(), w.cn.data(),
                                 actual.use_bc_scaling, norm_rule);
         if (dev && data_flags_host(w, count)[DF_START]) {

@@ -133,23 +133,62 @@ def segment_batch(B):
     return Cm, AL, AU, L, U
 
 
-@pytest.mark.parametrize("B", [3, 33])
-def test_segment_boundaries_and_a_partly_filled_member_tile(gpu, B):
-    m, n, rowptr, colind, values = segment_lp()
-    z = np.zeros
-    model = hprlp.Model.from_csr(m, n, rowptr, colind, values, z(m), z(m), z(n), z(n), z(n))
-    prm = hprlp.Parameters(check_iter=50, max_iter=50, stop_tol=1e-12, use_presolve=False)
-    args = segment_batch(B)
+@functools.lru_cache(maxsize=None)
+def segment_batch_all_infinities(B):
+    """segment_batch with infinite lower bounds as well: every replacement of batch_units.h on both sides of the boundaries."""
+    Cm, AL, AU, L, U = (np.array(a) for a in segment_batch(B))
+    L[np.random.default_rng(70 + B).random(L.shape) < 0.1] = -INF
+    return Cm, AL, AU, L, U
+
+
+def few_rows_model():
+    """The 2 x 2 LP of the known-answer tests."""
+    return hprlp.Model.from_csr(2, 2, [0, 2, 4], [0, 1, 0, 1], [1.0, 2.0, 3.0, 1.0], [-INF, -INF], [10.0, 12.0], [0.0, 0.0], [INF, INF],
+                                [-3.0, -5.0])
+
+
+def few_rows_batch():
+    """Three members of the 2 x 2 LP (rows x members): the LP itself, one with an infinite upper row side, a finite lower one, an
+    infinite lower bound and a finite upper one, and one with every side and bound finite."""
+    Cm = np.array([[-3.0, -3.3, -2.5], [-5.0, -4.1, -5.5]])
+    AL = np.array([[-INF, -INF, -1.0], [-INF, 2.0, -2.0]])
+    AU = np.array([[10.0, 10.5, 11.0], [12.0, INF, 12.5]])
+    L = np.array([[0.0, -INF, 0.0], [0.0, 0.0, -1.0]])
+    U = np.array([[INF, INF, 6.0], [INF, 4.0, 7.0]])
+    return Cm, AL, AU, L, U
+
+
+@pytest.mark.parametrize("shape,B,use_bc", [pytest.param("segments", 3, True, id="3"), pytest.param("segments", 33, True, id="33"),
+                                            pytest.param("segments+lower", 3, True, id="3-lower_bounds"),
+                                            pytest.param("segments+lower", 3, False, id="3-lower_bounds-no_bc"),
+                                            pytest.param("few_rows", 3, True, id="few_rows"),
+                                            pytest.param("few_rows", 3, False, id="few_rows-no_bc")])
+def test_segment_boundaries_and_a_partly_filled_member_tile(gpu, shape, B, use_bc):
+    """Every function of batch_units.h that the batch entry's kernels call (the two norm passes, kb_data_scales, kb_data_header,
+    kb_panel_out), against the host entry: with and without use_bc_scaling, infinite lower and upper row sides and bounds, no start,
+    X0 alone, Y0 alone and both -- at the smallest shape with segment boundaries and on a few-row LP with a partly filled tile.
+    (The first two cases are older: no infinite lower bound, and no start or both.)"""
+    if shape == "few_rows":
+        model, args = few_rows_model(), few_rows_batch()
+    else:
+        m, n, rowptr, colind, values = segment_lp()
+        z = np.zeros
+        model = hprlp.Model.from_csr(m, n, rowptr, colind, values, z(m), z(m), z(n), z(n), z(n))
+        args = segment_batch(B) if shape == "segments" else segment_batch_all_infinities(B)
+    m, n = model.m, model.n
+    prm = hprlp.Parameters(check_iter=50, max_iter=50, stop_tol=1e-12, use_presolve=False, use_bc_scaling=use_bc)
     rng = np.random.default_rng(9)
     X0, Y0 = rng.normal(size=(n, B)), rng.normal(size=(m, B)) * 0.1  # (the starts' map crosses the segments too)
+    starts = [(None, None), (X0, Y0)] + ([] if shape == "segments" else [(X0, None), (None, Y0)])
     h = tree_handle(model, prm)
-    for step, (x0, y0) in enumerate([(None, None), (X0, Y0)]):
+    for step, (x0, y0) in enumerate(starts):
         ref = h.solve(*args, X0=x0, Y0=y0)
         ref_sc = h.scalars()
         got = h.solve_tensors(*[T(a) for a in args], X0=T(x0), Y0=T(y0))
-        print("B", B, "step", step, "statuses", sorted(set(ref["status"])), "iter", sorted(set(ref["iter"])))
-        assert_same(on_host(got), ref, ("segments", B, step))
-        same_scalars(h.scalars(), ref_sc, ("segments", B, step))
+        print(shape, "B", B, "use_bc", use_bc, "step", step, "statuses", sorted(set(ref["status"])), "iter", sorted(set(ref["iter"])))
+        assert_same(on_host(got), ref, (shape, B, use_bc, step))
+        same_scalars(h.scalars(), ref_sc, (shape, B, use_bc, step))
+        assert use_bc or (ref_sc["b_scale"] == 1.0).all() and (ref_sc["c_scale"] == 1.0).all()
     h.close(); model.free()
 
 

@@ -1,7 +1,7 @@
 """Device-resident streams on the GPU (include/hprlp_amd.h hprlp_batched_solver_solve_stream_device, DESIGN.md "Device-resident
 streams"): BatchedSolver.solve_stream_tensors takes the queue as torch tensors on the GPU, never stages a scaled copy of it -- the
-norms come from kb_queue_norms / kb_queue_norms_bc over the caller's arrays, a problem is scaled by kb_slot_scale on its way into a
-slot -- and writes x, y, z straight into the caller's buffers.
+norms come from kb_data_in / kb_data_bc in their form without stores, over the caller's arrays, a problem is scaled by
+kb_slot_scale on its way into a slot -- and writes x, y, z straight into the caller's buffers.
 
 The reference of every comparison is the HOST stream (numpy in, numpy out) on a handle with set_norms(1), with the same arguments.
 Equality means: the same status and iter of every problem, np.array_equal on x, y, z, == on primal_obj, residuals and gap, the same
@@ -15,7 +15,8 @@ import pytest
 
 from conftest import hprlp
 from test_gpu_batched_detect import MIXED_PRM, _mixed
-from test_gpu_batched_device import T, _loaded_hip_runtime, on_host, planted, segment_batch, segment_lp, torch_, tree_handle
+from test_gpu_batched_device import (T, _loaded_hip_runtime, few_rows_batch, few_rows_model, on_host, planted, segment_batch,
+                                     segment_batch_all_infinities, segment_lp, torch_, tree_handle)
 from test_gpu_batched_stream import CERT_SCALARS, CHECK, SCALARS, params
 from test_gpu_warm import make_batch, model_of
 
@@ -56,7 +57,7 @@ def both(h, args, width, X0=None, Y0=None, **kw):
 @functools.lru_cache(maxsize=None)
 def queue(N, W):
     """make_batch of the stream tests with infinite entries in AL, AU, l, u -- in late problems too -- and C = 0 in a problem that
-    enters at a refill: the substitution and the sigma = 1 rule are met by kb_slot_scale and kb_queue_sigma, not by the initial fill alone."""
+    enters at a refill: the substitution and the sigma = 1 rule are met by kb_slot_scale and kb_data_header, not by the initial fill alone."""
     lp = planted()
     Cm, AL, AU, L, U = (np.array(a) for a in make_batch(lp, N, 2))
     AL[:4, :] = -INF
@@ -90,21 +91,53 @@ def test_device_stream_gives_the_bits_of_the_host_stream(gpu, monkeypatch, width
 
 
 # ---- 2. starts ------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("which", ["xy", "x", "y"])
-def test_starts(gpu, which):
-    lp = planted()
-    N, width = 7, 3
-    args = make_batch(lp, N, 2)
-    model = model_of(lp)
-    h, h2 = tree_handle(model, params(stop_tol=1e-4)), tree_handle(model, params(stop_tol=1e-4))
-    rough = h2.solve(*args, param=params(stop_tol=1e-2))   # (a point on the way: a start that is neither zero nor a solution)
-    X0, Y0 = (rough["x"] if "x" in which else None), (rough["y"] if "y" in which else None)
+def _few_rows_queue():
+    """few_rows_batch twice and once more: 7 problems through 3 slots, so that every kind of member also enters at a refill."""
+    return tuple(np.concatenate([a, a, a[:, :1]], axis=1) for a in few_rows_batch())
+
+
+# The planted LP (the first three cases) has no infinite entry and runs with use_bc_scaling alone.  The others reach every function
+# of batch_units.h that the stream entry's kernels call (the norm passes without stores, kb_data_scales, kb_data_header without a
+# header, kb_slot_scale at the first fill and at a refill, kb_slot_out): infinite lower and upper row sides and bounds throughout,
+# X0 alone, Y0 alone and both, with and without use_bc_scaling.  A start's map takes the member's scale as a number, 1.0 without
+# use_bc_scaling, and whether X0 or Y0 is given decides nothing else: so the few-row LP takes the whole cross and the shape with
+# segment boundaries each start and each setting once.
+@pytest.mark.parametrize("which,shape,use_bc", [pytest.param("xy", "planted", True, id="xy"), pytest.param("x", "planted", True, id="x"),
+                                                pytest.param("y", "planted", True, id="y")]
+                         + [pytest.param(w, "few_rows", bc, id=f"{w}-few_rows" + ("" if bc else "-no_bc"))
+                            for bc in (True, False) for w in ("xy", "x", "y")]
+                         + [pytest.param("x", "segments", True, id="x-segments"), pytest.param("y", "segments", False, id="y-segments-no_bc"),
+                            pytest.param("xy", "segments", False, id="xy-segments-no_bc")])
+def test_starts(gpu, which, shape, use_bc):
+    if shape == "planted":
+        lp = planted()
+        N, width = 7, 3
+        args = make_batch(lp, N, 2)
+        model = model_of(lp)
+        prm = params(stop_tol=1e-4)
+        h2 = tree_handle(model, prm)
+        rough = h2.solve(*args, param=params(stop_tol=1e-2))   # (a point on the way: a start that is neither zero nor a solution)
+        h2.close()
+        X0, Y0 = rough["x"], rough["y"]
+    else:
+        if shape == "few_rows":
+            model, args, (N, width) = few_rows_model(), _few_rows_queue(), (7, 3)
+        else:
+            m, n, rowptr, colind, values = segment_lp()
+            z = np.zeros
+            model = hprlp.Model.from_csr(m, n, rowptr, colind, values, z(m), z(m), z(n), z(n), z(n))
+            args, (N, width) = segment_batch_all_infinities(5), (5, 2)
+        prm = hprlp.Parameters(check_iter=50, max_iter=50, stop_tol=1e-12, use_presolve=False, use_bc_scaling=use_bc)
+        rng = np.random.default_rng(9)
+        X0, Y0 = rng.normal(size=(model.n, N)), rng.normal(size=(model.m, N)) * 0.1
+    X0, Y0 = (X0 if "x" in which else None), (Y0 if "y" in which else None)
+    h = tree_handle(model, prm)
     ref, got, info = both(h, args, width, X0, Y0)
-    same_stream(got, ref, ("starts", which))
+    same_stream(got, ref, ("starts", which, shape, use_bc))
     assert info["refills"] == N - width and (ref["iter"] > 0).any()
     cold = h.solve_stream(*args, width=width)
     assert not np.array_equal(cold["iter"], ref["iter"]) or not np.array_equal(cold["x"], ref["x"])   # (the start was used)
-    h.close(); h2.close(); model.free()
+    h.close(); model.free()
 
 
 def test_a_slot_handed_on_twice_within_one_event(gpu):
