@@ -203,6 +203,88 @@ def test_reference_examples_compile_and_link_unchanged(src, tmp_path):
     assert re.search(r"\b(solve|create_model_from_arrays|create_model_from_mps|solve_batched)\b", nm)
 
 
+def handle_entries():
+    """name -> (return type, parameter types) of every entry of include/hprlp_amd.h whose first parameter is one solver handle
+    (hprlp_solver * or hprlp_batched_solver *), the create / destroy / free entries left out."""
+    from test_resolve import header_prototypes
+    return {name: proto for name, proto in header_prototypes().items()
+            if proto[1] and proto[1][0] in ("hprlp_solver *", "hprlp_batched_solver *")
+            and not re.search(r"_(create|destroy|free)", name)}
+
+
+def _plain_library():
+    """The library once more, its functions without hprlp.py's argtypes: the arguments below are built from the header's types."""
+    hprlp.lib()
+    return C.CDLL(hprlp.LIB_PATH)
+
+
+def _small_valid_arguments(params, keep):
+    """One valid small argument per parameter type after the handle; `keep` holds the buffers alive."""
+    prm = hprlp.Parameters(max_iter=450, use_presolve=False).to_c()   # (a multiple of check_iter = 150: the stream entries ask)
+    keep.append(prm)
+    args = []
+    for p in params[1:]:
+        if p == "int":
+            args.append(C.c_int(1))
+        elif p == "long":
+            args.append(C.c_long(1))
+        elif p == "double":
+            args.append(C.c_double(1.0))
+        elif p == "const char *":
+            args.append(C.c_char_p(b"x"))
+        elif p == "void *":
+            args.append(C.c_void_p(None))             # (a stream: the default one)
+        elif p == "const HPRLP_parameters *":
+            args.append(C.byref(prm))
+        else:
+            assert p.endswith("*"), p
+            buf = C.create_string_buffer(4096)        # (zeroed: arrays of zeros, structs of zeros and null pointers)
+            keep.append(buf)
+            args.append(C.cast(buf, C.c_void_p))
+    return args
+
+
+RESTYPE = {"int": (C.c_int, -1), "long": (C.c_long, -1), "double": (C.c_double, -1.0), "void": (None, None)}
+
+
+def test_handle_entries_are_found_in_the_header():
+    names = handle_entries()
+    assert len(names) >= 55, sorted(names)            # (55 when this test was written; entries are only ever added)
+    assert {"hprlp_solver_scale", "hprlp_solver_run", "hprlp_solver_set_verbose", "hprlp_solver_get_vector", "hprlp_solver_power_iteration",
+            "hprlp_batched_solver_solve_stream", "hprlp_batched_solver_get_panel", "hprlp_solver_resolve_device"} <= set(names)
+    assert not {"hprlp_solver_destroy", "hprlp_batched_solver_destroy", "hprlp_solver_scale_many"} & set(names)
+
+
+@pytest.mark.parametrize("name", sorted(handle_entries()))
+def test_a_null_handle_is_refused_by_every_entry_that_takes_one(name):
+    """A NULL handle with otherwise valid small arguments: the entry's fail value (-1, -1.0), "<entry>: null solver" in
+    hprlp_last_error(), and a process that goes on.  The stream entries refuse a bad count or width before they look at the handle."""
+    ret, params = handle_entries()[name]
+    fn = getattr(_plain_library(), name)
+    fn.restype, fail = RESTYPE[ret]
+    keep = []
+    args = _small_valid_arguments(params, keep)
+    if "_solve_stream" in name:
+        assert params[1:3] == ["int", "int"]          # count, width
+        for count, width in ((0, 1), (1, 0), (-2, 1)):
+            assert fn(None, C.c_int(count), C.c_int(width), *args[2:]) == -1
+            assert "count and width must be positive" in hprlp.last_error(), hprlp.last_error()
+    assert fn(None, *args) == fail
+    assert name in hprlp.last_error() and "null solver" in hprlp.last_error(), hprlp.last_error()
+    assert hprlp.lib().hprlp_backend().decode() == "hip-gfx950"
+
+
+def test_run_with_a_null_handle_and_a_trace_buffer_is_refused():
+    """hprlp_solver_run attaches the caller's trace buffer to the solver for the call: with no solver there is nothing to attach it to."""
+    L = _plain_library()
+    res = hprlp.CResults()
+    trace = (hprlp.CTraceRow * 4)()
+    n_trace = C.c_int(-7)
+    assert L.hprlp_solver_run(None, C.byref(res), trace, C.c_int(4), C.byref(n_trace)) == -1
+    assert "hprlp_solver_run: null solver" in hprlp.last_error()
+    assert n_trace.value == -7
+
+
 def test_device_block_cache_is_keyed_by_the_owning_device():
     """csrc/alloc.cpp: freed device blocks are filed under the device that owns them (not the freeing thread's current
     device) and only handed to requests of that device; the cap is per device.  Pure bookkeeping, runs without a GPU."""

@@ -67,7 +67,7 @@ def test_solve_batched_detect_without_a_gpu_is_an_error_not_a_crash():
 
 
 def test_negative_eps_is_an_error():
-    """detection_from's check (abi.cpp), on any machine: the eps are rejected before anything touches a device."""
+    """detection_from's check (abi_solve.cpp), on any machine: the eps are rejected before anything touches a device."""
     B = 2
     lp, model, (Cm, AL, AU, L, U) = _batch(B)
     for ep, ed in ((-1e-8, 1e-8), (1e-8, -1.0), (float("nan"), 1e-8)):
