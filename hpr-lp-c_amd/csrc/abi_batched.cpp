@@ -290,6 +290,54 @@ extern "C" int hprlp_batched_solver_solve_stream_device(hprlp_batched_solver *h,
     });
 }
 
+// ---- streams with parents (DESIGN.md "Streamed batches", "Parents") --------------------------------------------------------------
+// Beside their twins: the twins' refusals first, then a NULL parent and the pairing of X0 / Y0, all before the solver is looked at;
+// the parent array's values are refused by the solver, before it changes (stream_schedule.h: stream_check_parents_call).
+extern "C" int hprlp_batched_solver_solve_stream_parents(hprlp_batched_solver *h, int count, int width, const double *C, const double *AL,
+                                                         const double *AU, const double *l, const double *u, const double *obj_constants,
+                                                         const HPRLP_parameters *param, const double *X0, const double *Y0,
+                                                         const int *parent, const hprlp_detection *det, hprlp_batched_certificates *certs,
+                                                         HPRLP_batched_results *out) {
+    return guarded(-1, [&] {
+        stream_check_call(out != nullptr, count, width, C && AL && AU && l && u, param ? param->max_iter : 0, param ? param->check_iter : 1);
+        stream_check_parents_call(parent, X0 != nullptr, Y0 != nullptr);
+        BatchedSolver *s = solver_of(h, "hprlp_batched_solver_solve_stream_parents");
+        HPRLP_batched_results r;
+        resident_solve(s, count, nullptr, nullptr, det, certs, [&](const Detection *d, std::vector<Certificate> *k) {
+            batched_solver_solve_stream_parents(s, count, width, C, AL, AU, l, u, obj_constants, param, X0, Y0, parent, d, k, &r, nullptr);
+        }, [&] { free_batched_results(&r); });
+        *out = r;
+        return 0;
+    });
+}
+
+extern "C" int hprlp_batched_solver_solve_stream_parents_device(hprlp_batched_solver *h, int count, int width, const double *dC,
+                                                                const double *dAL, const double *dAU, const double *dl, const double *du,
+                                                                const double *obj_constants, const HPRLP_parameters *param,
+                                                                const double *dX0, const double *dY0, const int *parent,
+                                                                const hprlp_detection *det, hprlp_batched_certificates *certs, void *stream,
+                                                                double *dx, double *dy, double *dz, hprlp_batched_scalars *out) {
+    return guarded(-1, [&] {
+        stream_check_call(out && dx && dy && dz, count, width, dC && dAL && dAU && dl && du, param ? param->max_iter : 0,
+                          param ? param->check_iter : 1);
+        stream_check_parents_call(parent, dX0 != nullptr, dY0 != nullptr);
+        BatchedSolver *s = solver_of(h, "hprlp_batched_solver_solve_stream_parents_device");
+        resident_solve_device(s, count, det, certs, stream, dx, dy, dz, out,
+                              [&](const Detection *d, std::vector<Certificate> *k, DeviceBatch *db) {
+                                  batched_solver_solve_stream_parents(s, count, width, dC, dAL, dAU, dl, du, obj_constants, param, dX0, dY0,
+                                                                      parent, d, k, nullptr, db);
+                              });
+        return 0;
+    });
+}
+
+extern "C" int hprlp_batched_solver_stream_parents_info(hprlp_batched_solver *h, long out[4]) {
+    return guarded(-1, [&] {
+        batched_solver_stream_parents_info(solver_of(h, "hprlp_batched_solver_stream_parents_info", out, "output"), out);
+        return 0;
+    });
+}
+
 extern "C" int hprlp_batched_solver_stream_memory(hprlp_batched_solver *h, long out[4]) {
     return guarded(-1, [&] {
         batched_solver_stream_memory(solver_of(h, "hprlp_batched_solver_stream_memory", out, "output"), out);

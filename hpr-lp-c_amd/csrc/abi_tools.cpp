@@ -219,6 +219,10 @@ extern "C" int hprlp_env_switches(char *buf, int cap) {
 extern "C" int hprlp_stream_schedule_host(int count, int width, const int *events, int *slot, int *event_in, int *event_out) {
     return guarded(-1, [&] { return stream_schedule(count, width, events, slot, event_in, event_out); });
 }
+extern "C" int hprlp_stream_schedule_parents_host(int count, int width, const int *events, const int *parent, int *slot, int *event_in,
+                                                  int *event_out) {
+    return guarded(-1, [&] { return stream_schedule_parents(count, width, events, parent, slot, event_in, event_out); });
+}
 
 // The shared-memory transport's protocol on HOST buffers (no GPU, no HIP call): rank `rank` of `size` attaches to the group the
 // id names and runs `rounds` rounds of all-gather, scalar all-reduce and a neighbour exchange whose payloads every receiver

@@ -62,6 +62,16 @@ void batched_solver_solve_stream_device(BatchedSolver *h, int count, int width, 
                                         const HPRLP_FLOAT *obj_constants /* host */, const HPRLP_parameters *param, const HPRLP_FLOAT *X0,
                                         const HPRLP_FLOAT *Y0, const Detection *det, std::vector<Certificate> *certs, DeviceBatch *dev);
 void batched_solver_stream_memory(const BatchedSolver *h, long out[4]);  // hprlp_batched_solver_stream_memory
+// A stream whose queued problems start from earlier ones' solutions (DESIGN.md "Streamed batches", "Parents";
+// hprlp_batched_solver_solve_stream_parents and its device twin): parent is a HOST array of count entries in both.  dev null: the
+// host entry (host arrays, the results into `out`); dev set: the device entry (device arrays, `out` unused).
+void batched_solver_solve_stream_parents(BatchedSolver *h, int count, int width, const HPRLP_FLOAT *C, const HPRLP_FLOAT *AL,
+                                         const HPRLP_FLOAT *AU, const HPRLP_FLOAT *l, const HPRLP_FLOAT *u, const HPRLP_FLOAT *obj_constants,
+                                         const HPRLP_parameters *param, const HPRLP_FLOAT *X0, const HPRLP_FLOAT *Y0, const int *parent,
+                                         const Detection *det, std::vector<Certificate> *certs, HPRLP_batched_results *out,
+                                         DeviceBatch *dev);
+// {roots, cold members, children started, slot-events a slot stood empty while problems waited} of the last stream call, a parents call
+void batched_solver_stream_parents_info(const BatchedSolver *h, long out[4]);
 // New values on the shared matrix' pattern (DESIGN.md "Matrix values"): val = the nnz values of the model's CSR in the caller's order.
 // The shared solver takes them with zero vectors and is scaled again, the host's row / column norms and the created lambda_max
 // follow; panels, staging blocks, order tables and workspace stay.  carry is refused until the next successful solve.

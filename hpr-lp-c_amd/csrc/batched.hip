@@ -1216,6 +1216,39 @@ __global__ void __launch_bounds__(256) kb_slot_scale(SlotScale a, const SlotPair
     a.dst[v][slot_elem(g, rows, static_cast<int>(i), pr.slot)] = r;
 }
 
+// ---- a start from a result column (DESIGN.md "Streamed batches", "Parents") --------------------------------------------------------
+// The listed problems' starts into their slots' columns of X (v = 0) and Y (v = 1): kb_slot_scale's geometry and table, and beside
+// each pair the pass's table carries the start's SOURCE.  source >= 0: that column of the result x / y -- the parent's returned
+// point, which kb_slot_out wrote in the caller's units earlier on this stream; source <= kSourceOwn: column kSourceOwn - source of
+// the caller's X0 / Y0 (a root's own); kSourceNone: a cold root, whose columns become 0.0.  The stored value is start_to_scaled of
+// the source -- times_norm by cn / rn, then by_scale by the ENTERING problem's b_scale / c_scale: what kb_slot_scale does to a start.
+constexpr int kSourceNone = -1, kSourceOwn = -2;
+struct SlotStart {
+    const double *res[2];   // the result's x, y (a device-entry call: the caller's dx, dy), column-major rows x count
+    const double *own[2];   // the caller's X0, Y0 (null: the call has none)
+    double *dst[2];         // the padded panels X, Y
+    const double *norm[2];  // cn, rn
+    int rows[2];
+    const double *q_bs, *q_cs;  // per problem of the queue
+    const int *source;          // per listed pair
+};
+// grid (ceil(max rows * np / 256), 2)
+__global__ void __launch_bounds__(256) kb_slot_start(SlotStart a, const SlotPair *pairs, int np, Geo g) {
+    const int v = blockIdx.y, rows = a.rows[v];
+    const long e = static_cast<long>(blockIdx.x) * 256 + threadIdx.x;
+    const long i = e / np;
+    if (i >= rows) return;
+    const int j = static_cast<int>(e % np);
+    const SlotPair pr = pairs[j];
+    const int s = a.source[j];
+    double r = 0.0;
+    if (s != kSourceNone) {
+        const double *col = s >= 0 ? a.res[v] + static_cast<size_t>(s) * rows : a.own[v] + static_cast<size_t>(kSourceOwn - s) * rows;
+        r = start_to_scaled(col[i], a.norm[v][i], v == 0 ? a.q_bs[pr.problem] : a.q_cs[pr.problem]);
+    }
+    a.dst[v][slot_elem(g, rows, static_cast<int>(i), pr.slot)] = r;
+}
+
 // ---- host side ----------------------------------------------------------------------------------
 // BatchedSolver::solve at the end of the file is the order of things; every kernel is launched by a named launcher.
 struct BatchWS {
@@ -2028,6 +2061,7 @@ struct StreamRun {
     BatchWS &w;
     const BatchData &q;  // the whole queue in scaled units (a device-entry call: its scalars alone)
     DeviceBatch *const dev;  // a device-entry call (DESIGN.md "Device-resident streams"): the caller's buffers; null: the host entry
+    const int *const parent;  // a parents call (DESIGN.md "Streamed batches", "Parents"): count entries; null: the plain queue
     const int count, W, max_iter;  // max_iter: each member's own limit (the loop's own is unlimited)
     const bool warm, detect;
     BatchData sd;  // the scalars of the problems in the slots: what the loop reads as "the batch" (it reads none of the vectors)
@@ -2037,30 +2071,46 @@ struct StreamRun {
                             // (a device-entry call stages no queue: the header alone, and the scalars are in w.data_scal)
     // res_count: x, y, z and, with detection, the rays y, A^T y, d of every problem (a device-entry call: the rays alone, x, y, z go
     // to the caller's buffers); tab_count: out pairs | in pairs | the start mask
+    // a parents call: behind the scalars the caller's X0 | Y0 as they are (the host entry; kb_slot_start scales a root's columns),
+    // and behind the start mask the source of each in pair
     const size_t nN, mN, stage_count, res_count, tab_count;
     SlotClear sclr{};
     SlotIn sin{};
     SlotScale sscale{};  // a device-entry call's way in, in sin's place
     SlotOut sout{};
+    SlotStart sstart{};  // a parents call's way into X and Y, in the X / Y regions' place
     std::vector<Member> done;
     std::vector<int> occ, freed, ps, pp;   // the problem in each slot (-1: empty); a pass's freed slots and its (slot, problem) pairs
     std::vector<char> is_new;
     std::vector<int> r_slot, r_in, r_out;  // the record: the handle takes it when the call has succeeded
     StreamQueue queue;
+    StreamParentQueue pqueue;  // ... of a parents call
+    std::vector<int> avail;    // a parents call's free slots of a pass: the freed ones and those that stood empty, ascending
+    bool pass_starts = false;  // a parents call's pass lists a member with a start: the masked start kernels run
+    long entered_roots = 0, entered_cold = 0, entered_children = 0, idle_slot_events = 0;  // hprlp_batched_solver_stream_parents_info
     long evals = 0, refill_events = 0, refills = 0, passes = 0;
     const long bumps0;
     bool ray_y = false, any_verdict = false;      // of a pass's freed members: which rays their harvest copies
 
     StreamRun(BatchWS &w_, const BatchData &q_, int W_, int Bp, const HPRLP_parameters &prm, const Detection *det, bool has_x, bool has_y,
-              DeviceBatch *dev_)
-        : w(w_), q(q_), dev(dev_), count(q_.B), W(W_), max_iter(prm.max_iter), warm(has_x || has_y), detect(det != nullptr),
-          sd(first_members(q_, W_)), loop_prm(prm), L(sd, Bp, loop_prm, det), regions(Bp, q_.n, q_.m, dev_ ? 0 : q_.B, has_x, has_y),
+              DeviceBatch *dev_, const int *parent_ = nullptr)
+        : w(w_), q(q_), dev(dev_), parent(parent_), count(q_.B), W(W_), max_iter(prm.max_iter), warm(has_x || has_y), detect(det != nullptr),
+          sd(first_members(q_, W_)), loop_prm(prm), L(sd, Bp, loop_prm, det),
+          regions(Bp, q_.n, q_.m, dev_ ? 0 : q_.B, has_x && !parent_, has_y && !parent_),
           nN(static_cast<size_t>(q_.n) * count), mN(static_cast<size_t>(q_.m) * count),
-          stage_count(regions.end + (dev_ ? 0 : 3 * static_cast<size_t>(count))),
-          res_count(dev_ ? (detect ? 2 * nN + mN : 0) : (2 * nN + mN) * (detect ? 2 : 1)), tab_count(4 * static_cast<size_t>(W_) + Bp),
+          stage_count(regions.end + (dev_ ? 0 : 3 * static_cast<size_t>(count)) + (parent_ && !dev_ && warm ? nN + mN : 0)),
+          res_count(dev_ ? (detect ? 2 * nN + mN : 0) : (2 * nN + mN) * (detect ? 2 : 1)),
+          tab_count(4 * static_cast<size_t>(W_) + Bp + (parent_ ? W_ : 0)),
           done(count), occ(W), freed(W), ps(W), pp(W), is_new(W, 0), r_slot(count, -1), r_in(count, -1), r_out(count, -1),
           bumps0(w_.bumps) {
         loop_prm.max_iter = std::numeric_limits<int>::max();
+        if (parent) {  // every slot empty and inactive: the initial fill is a pass (first_pass)
+            std::fill(occ.begin(), occ.end(), -1);
+            std::fill(L.active.begin(), L.active.end(), 0);
+            pqueue = StreamParentQueue(count, parent);
+            avail.resize(W);
+            return;
+        }
         for (int k = 0; k < W; ++k) occ[k] = r_slot[k] = k;  // (where the initial fill puts the first W problems)
         std::fill_n(r_in.begin(), W, 0);
         queue = StreamQueue{count, W};
@@ -2070,13 +2120,17 @@ struct StreamRun {
     // device-entry call: the header alone.
     void stage(const double *X0, const double *Y0) {
         if (dev) stage_header(w, L, sd, stage_count, stage_count);
-        else stage_host(w, L, sd, regions, q, X0, Y0, std::max(stage_count, res_count), stage_count);
+        else stage_host(w, L, sd, regions, q, parent ? nullptr : X0, parent ? nullptr : Y0, std::max(stage_count, res_count), stage_count);
         if (w.res_d.n < res_count) w.res_d.alloc(res_count);
         if (dev) return;
         double *qh = w.stage_h.p + regions.end;
         std::copy(q.sigma.begin(), q.sigma.end(), qh);
         std::copy(q.b_scale.begin(), q.b_scale.end(), qh + count);
         std::copy(q.c_scale.begin(), q.c_scale.end(), qh + 2 * static_cast<size_t>(count));
+        if (parent && warm) {  // in the caller's units: the roots' columns are scaled on their way in, like a child's start
+            std::memcpy(qh + 3 * static_cast<size_t>(count), X0, nN * sizeof(double));
+            std::memcpy(qh + 3 * static_cast<size_t>(count) + nN, Y0, mN * sizeof(double));
+        }
     }
 
     // Behind the initial fill, when every panel is at its address: the harvest's scratch panel, the tables (they only grow), and the
@@ -2095,8 +2149,8 @@ struct StreamRun {
         sclr.n = n; sclr.m = m;
         for (double *pn : {w.Xh.p, w.Xb.p, w.DX.p, w.Zb.p, w.lastX.p}) sclr.pn[sclr.npn++] = pn;
         for (double *pm : {w.Yb.p, w.DY.p, w.Yobj.p, w.lastY.p}) sclr.pm[sclr.npm++] = pm;
-        if (regions.iX < 0) sclr.pn[sclr.npn++] = w.X.p;
-        if (regions.iY < 0) sclr.pm[sclr.npm++] = w.Y.p;
+        if (regions.iX < 0 && !parent) sclr.pn[sclr.npn++] = w.X.p;  // (a parents call: kb_slot_start writes every listed column)
+        if (regions.iY < 0 && !parent) sclr.pm[sclr.npm++] = w.Y.p;
         if (detect) {
             sclr.pn[sclr.npn++] = w.prevX.p; sclr.pn[sclr.npn++] = w.DS.p;
             sclr.pm[sclr.npm++] = w.prevY.p; sclr.pm[sclr.npm++] = w.YS.p;
@@ -2124,6 +2178,35 @@ struct StreamRun {
     const SlotPair *out_pairs() const { return reinterpret_cast<const SlotPair *>(w.tab_d.p); }
     const SlotPair *in_pairs() const { return reinterpret_cast<const SlotPair *>(w.tab_d.p + 2 * static_cast<size_t>(W)); }
     const int *new_mask() const { return w.tab_d.p + 4 * static_cast<size_t>(W); }
+    const int *sources() const { return new_mask() + w.Bp; }
+
+    // A parents call's way into X and Y (after bind): a child from its parent's column of the results, a root from its own column of
+    // the caller's X0 / Y0 -- the device entry's arrays, or the host entry's staged copy.
+    void bind_starts(const double *X0, const double *Y0) {
+        const double *own = w.stage_d.p + regions.end + 3 * static_cast<size_t>(count);
+        sstart = SlotStart{{sout.dst[0], sout.dst[1]}, {nullptr, nullptr}, {w.X.p, w.Y.p},
+                           {w.shared->col_norm.p, w.shared->row_norm.p}, {w.n, w.m}, sclr.q_bs, sclr.q_cs, sources()};
+        if (warm) {
+            sstart.own[0] = dev ? X0 : own;
+            sstart.own[1] = dev ? Y0 : own + nN;
+        }
+    }
+    int source_of(int pr) const { return parent[pr] >= 0 ? parent[pr] : (warm ? kSourceOwn - pr : kSourceNone); }
+    // ... and its initial fill.  Before the loop: the five data panels 0.0 throughout, as kb_panel_in leaves padding members (a
+    // slot nobody has entered yet is one).  first_pass, at the loop's start: a pass of event 0 with every slot free and nothing to
+    // harvest, in which only roots are ready; it is the iteration-0 evaluation of the members it puts in.
+    void clear_data_panels() {
+        for (int v = 0; v < regions.nvec; ++v)
+            HIP_CHECK(hipMemsetAsync(sin.dst[v], 0, static_cast<size_t>(sin.rows[v]) * w.Bp * sizeof(double), w.stream));
+    }
+    void first_pass() {
+        for (int k = 0; k < W; ++k) avail[k] = k;
+        const int nin = stream_assign_parents(pqueue, avail.data(), W, ps.data(), pp.data());
+        if (!nin) throw std::logic_error("batched stream: no root among the queued problems");  // (parent[0] is -1: checked at entry)
+        harvest(0, nin);
+        refill(nin);
+        refills = passes = 0;  // (the counts are of the entries after the initial fill, as the plain queue's)
+    }
 
     // A device-entry call's way into the slots (after bind): the caller's arrays in the regions' order, each with its norm and its
     // operations (kb_slot_scale).
@@ -2190,12 +2273,18 @@ struct StreamRun {
             occ[k] = -1;
         }
         std::fill(th + 4 * static_cast<size_t>(W), th + tab_count, 0);
+        pass_starts = false;
         for (int i = 0; i < nin; ++i) {
             th[2 * (W + i)] = ps[i];
             th[2 * (W + i) + 1] = pp[i];
+            const int source = parent ? source_of(pp[i]) : 0;
+            if (parent) th[4 * static_cast<size_t>(W) + w.Bp + i] = source;
+            if (source == kSourceNone) continue;  // a cold root: the start kernels' mask leaves it out
             th[4 * static_cast<size_t>(W) + ps[i]] = 1;
+            pass_starts = true;
         }
         HIP_CHECK(hipMemcpyAsync(w.tab_d.p, th, tab_count * sizeof(int), hipMemcpyHostToDevice, w.stream));
+        if (!nout) return;  // (a parents call's initial fill)
         if (ray_y) {  // z = -A^T y of a primal verdict: the plain product of every column, as collect_certificates has it
             launch_ray_product(w);
             HIP_CHECK(hipGetLastError());
@@ -2209,7 +2298,8 @@ struct StreamRun {
         launch_slot(w, kb_slot_clear, sclr, in_pairs(), nin, sclr.npn + sclr.npm + 1);
         if (dev) launch_slot(w, kb_slot_scale, sscale, in_pairs(), nin, regions.nvec);
         else launch_slot(w, kb_slot_in, sin, in_pairs(), nin, regions.nvec);
-        if (warm) {
+        if (parent) launch_slot(w, kb_slot_start, sstart, in_pairs(), nin, 2);
+        if (parent ? pass_starts : warm) {
             ws_start(w, new_mask());
             HIP_CHECK(hipGetLastError());
         }
@@ -2230,17 +2320,47 @@ struct StreamRun {
             L.ray_tested[k] = 0;
             is_new[k] = 1;
             for (int s = 0; s < kMemberScalars; ++s) (*slot[s])[k] = (*queued[s])[pr];
+            if (parent) {
+                const int source = source_of(pr);
+                ++(source >= 0 ? entered_children : entered_roots);
+                if (source == kSourceNone) ++entered_cold;
+            }
         }
         refills += nin;
         ++passes;
         loop_evaluate(w, L, /*first=*/true, is_new.data());
     }
 
+    // A parents call's side of a pass.  The members that end release their children first -- a child is ready in the very pass that
+    // harvests its parent: kb_slot_out writes the column before kb_slot_start reads it, on one stream -- or, where the parent's
+    // final evaluation is not finite, drop them for good.  Then the free slots (the freed ones and those that stood empty),
+    // ascending, take the ready problems, ascending.  Nothing enters once the time is up.
+    int assign_ready(int nout, bool time_up) {
+        for (int i = 0; i < nout; ++i) {
+            const Residuals &r = L.mem[freed[i]].r;
+            pqueue.release(occ[freed[i]], std::isfinite(r.kkt) && std::isfinite(r.primal_obj) && std::isfinite(r.rel_gap));
+        }
+        if (time_up) return 0;
+        int nfree = 0;
+        for (int k = 0, i = 0; k < W; ++k) {
+            const bool ends = i < nout && freed[i] == k;
+            if (ends) ++i;
+            if (ends || occ[k] < 0) avail[nfree++] = k;
+        }
+        return stream_assign_parents(pqueue, avail.data(), nfree, ps.data(), pp.data());
+    }
+    int occupied_slots() const { return static_cast<int>(std::count_if(occ.begin(), occ.end(), [](int pr) { return pr >= 0; })); }
+    // the problems that never entered a slot: the time limit's, and, in a parents call, the descendants of an unusable point
+    void mark_never_entered() {
+        for (int pr = 0; pr < count; ++pr)
+            if (r_slot[pr] < 0) done[pr].status = parent && pqueue.dropped[pr] ? "ERROR" : "TIME_LIMIT";  // (iteration 0, no residuals)
+    }
+
     // one pass of an event; false when it handed no slot on (nobody ended, the queue is empty, the time is up): the event is over
     bool pass(bool time_up, bool &active_stale) {
         const int nout = expire_and_collect(time_up, active_stale);
         if (!nout) return false;
-        const int nin = time_up ? 0 : stream_assign(queue, freed.data(), nout, ps.data(), pp.data());
+        const int nin = parent ? assign_ready(nout, time_up) : (time_up ? 0 : stream_assign(queue, freed.data(), nout, ps.data(), pp.data()));
         harvest(nout, nin);
         if (!nin) {
             HIP_CHECK(hipStreamSynchronize(w.stream));  // (the pinned table is free again)
@@ -2254,7 +2374,7 @@ struct StreamRun {
 
     // all `count` problems: one download of the result block, the members' evaluations, the certificates from the rays beside the solutions
     HPRLP_batched_results results(std::vector<Certificate> *certs) {
-        for (int pr = queue.next; pr < count; ++pr) done[pr].status = "TIME_LIMIT";  // (only the time limit leaves a problem queued: iteration 0, no residuals)
+        mark_never_entered();
         HPRLP_batched_results res = alloc_batched_results(w.m, w.n, count);
         try {
             HIP_CHECK(hipMemcpyAsync(w.stage_h.p, w.res_d.p, res_count * sizeof(double), hipMemcpyDeviceToHost, w.stream));
@@ -2280,7 +2400,7 @@ struct StreamRun {
     // A device-entry call: x, y, z are in the caller's buffers already; the members' evaluations go to its host arrays, and of the
     // ray block only the columns of the problems with a verdict come to the host.  Returns the bytes of those.
     size_t results_device(std::vector<Certificate> *certs) {
-        for (int pr = queue.next; pr < count; ++pr) done[pr].status = "TIME_LIMIT";
+        mark_never_entered();
         HIP_CHECK(hipStreamSynchronize(w.stream));
         const size_t m = w.m, n = w.n;
         size_t ray_doubles = 0;
@@ -2374,6 +2494,8 @@ struct BatchedSolver {
     bool streamed = false, have_stream = false;
     std::vector<int> rec_slot, rec_in, rec_out;
     long stream_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool stream_had_parents = false;       // the last streamed call was a parents call ...
+    long parents_stats[4] = {0, 0, 0, 0};  // ... and its counts (hprlp_batched_solver_stream_parents_info)
     long stream_mem[4] = {0, 0, 0, 0};  // hprlp_batched_solver_stream_memory: what the last one held beside the workspace
     double stream_seconds[2] = {0, 0};  // of the last streamed call: its refill passes (harvest, refill, iteration-0 evaluation); the rest of its loop
     double lambda_last = 0.0;           // lambda_max at the end of the last successful call of either kind (0: none yet)
@@ -2388,10 +2510,13 @@ struct BatchedSolver {
                const HPRLP_parameters *p, const double *X0, const double *Y0, bool carry, const Detection *det,
                std::vector<Certificate> *certs, HPRLP_batched_results *out, DeviceBatch *dev = nullptr);
     // count problems through min(width, count) slots, a freed slot taking the next queued problem at once.  dev null: host arrays,
-    // the results into `out`; dev set: the queue lies in device memory (solve()'s rule for dev)
+    // the results into `out`; dev set: the queue lies in device memory (solve()'s rule for dev).  parents_entry: the call of
+    // hprlp_batched_solver_solve_stream_parents[_device] -- parent (host, count entries) says which problem starts from which
+    // other's returned point (DESIGN.md "Streamed batches", "Parents").
     void solve_stream(int count, int width, const double *C, const double *AL, const double *AU, const double *l, const double *u,
                       const double *obj_constants, const HPRLP_parameters *p, const double *X0, const double *Y0, const Detection *det,
-                      std::vector<Certificate> *certs, HPRLP_batched_results *out, DeviceBatch *dev = nullptr);
+                      std::vector<Certificate> *certs, HPRLP_batched_results *out, DeviceBatch *dev = nullptr, const int *parent = nullptr,
+                      bool parents_entry = false);
 
     // the handle's parameters with the caller's max_iter, stop_tol, time_limit, check_iter and use_bc_scaling (p null: the handle's)
     HPRLP_parameters call_parameters(const HPRLP_parameters *p) const {
@@ -2622,11 +2747,15 @@ void BatchedSolver::solve(int B, const double *C_in, const double *AL_in, const 
 void BatchedSolver::solve_stream(int count, int width, const double *C_in, const double *AL_in, const double *AU_in, const double *l_in,
                                  const double *u_in, const double *obj_constants, const HPRLP_parameters *p, const double *X0,
                                  const double *Y0, const Detection *det, std::vector<Certificate> *certs, HPRLP_batched_results *out,
-                                 DeviceBatch *dev) {
+                                 DeviceBatch *dev, const int *parent, bool parents_entry) {
     // -- everything that can refuse the call, before the handle changes
     const HPRLP_parameters actual = call_parameters(p);
     stream_check_call(dev ? dev->x && dev->y && dev->z : out != nullptr, count, width, C_in && AL_in && AU_in && l_in && u_in,
                       actual.max_iter, actual.check_iter);
+    if (parents_entry) {
+        stream_check_parents_call(parent, X0 != nullptr, Y0 != nullptr);
+        stream_check_parents(count, parent);
+    }
     const size_t nN = static_cast<size_t>(n) * count, mN = static_cast<size_t>(m) * count;
     for (size_t i = 0; !dev && X0 && i < nN; ++i)
         if (!std::isfinite(X0[i])) throw std::runtime_error("batched stream: warm start: X0[" + std::to_string(i) + "] is not finite");
@@ -2653,7 +2782,7 @@ void BatchedSolver::solve_stream(int count, int width, const double *C_in, const
             refused = true;
             throw std::runtime_error("batched stream: warm start: X0 or Y0 holds an entry that is not finite");
         }
-        StreamRun run(w, q, W, plan.Bp, actual, detect ? det : nullptr, X0 != nullptr, Y0 != nullptr, dev);
+        StreamRun run(w, q, W, plan.Bp, actual, detect ? det : nullptr, X0 != nullptr, Y0 != nullptr, dev, parent);
         BatchLoop &L = run.L;
         run.stage(X0, Y0);
         seconds[2] = time_since(t_prep);
@@ -2668,14 +2797,20 @@ void BatchedSolver::solve_stream(int count, int width, const double *C_in, const
             HIP_CHECK(hipMemsetAsync(dev->z, 0, nN * sizeof(double), w.stream));
         }
         if (run.res_count) HIP_CHECK(hipMemsetAsync(w.res_d.p, 0, run.res_count * sizeof(double), w.stream));
-        ws_fill(w, run.sd, run.stage_count, in, dev ? 0 : run.regions.nvec, X0 != nullptr, Y0 != nullptr, /*carry=*/false, detect);
+        // (a parents call: the header alone, every slot inactive, X and Y zero throughout; its initial fill is the loop's first pass)
+        ws_fill(w, run.sd, run.stage_count, in, dev || parent ? 0 : run.regions.nvec, X0 != nullptr && !parent, Y0 != nullptr && !parent,
+                /*carry=*/false, detect);
         if (dev) {  // the first W problems from the caller's arrays, by the refill's kernel
             run.bind(in);
             run.bind_caller(C_in, AL_in, AU_in, l_in, u_in, X0, Y0);
-            run.fill_first();
+            if (!parent) run.fill_first();
         }
-        if (X0 || Y0) ws_start(w);
+        if ((X0 || Y0) && !parent) ws_start(w);
         if (!dev) run.bind(in);
+        if (parent) {
+            run.bind_starts(X0, Y0);
+            run.clear_data_panels();
+        }
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipStreamSynchronize(w.stream));
         seconds[3] = time_since(t_fill);
@@ -2684,15 +2819,27 @@ void BatchedSolver::solve_stream(int count, int width, const double *C_in, const
         L.solve_start = time_now();
         while (true) {  // one pass per periodic event
             const double elapsed = time_since(L.solve_start);
-            loop_evaluate(w, L, L.iter == 0);  // 1. every occupied slot, by its local iteration
+            const bool time_up = elapsed >= actual.time_limit;
+            if (parent && L.iter == 0) {  // 1. a parents call's initial fill: the roots' iteration-0 evaluation (nothing enters once the time is up)
+                if (!time_up) run.first_pass();
+            } else {
+                loop_evaluate(w, L, L.iter == 0);  // 1. every occupied slot, by its local iteration
+            }
             ++run.evals;
             const auto t_pass = time_now();
             bool refilled = false, active_stale = false;  // (stale: a limit has changed the active mask and no evaluation has uploaded it)
-            while (run.pass(elapsed >= actual.time_limit, active_stale)) refilled = true;  // 2. harvest, 3. refill, 4. iteration-0 evaluation
+            while (run.pass(time_up, active_stale)) refilled = true;  // 2. harvest, 3. refill, 4. iteration-0 evaluation
             if (active_stale) w.active.upload(L.active.data(), w.Bp);
             if (refilled) ++run.refill_events;
             refill_seconds += time_since(t_pass);
-            if (!run.occupied()) break;
+            if (!run.occupied()) {
+                // No deadlock: parent[p] < p, so with nothing running the lowest-numbered waiting problem has a parent that has been
+                // harvested, and the pass above has taken it.  Were that ever violated the loop would spin on empty slots: fail instead.
+                if (parent && !time_up && run.pqueue.left() > 0)
+                    throw std::logic_error("batched stream: " + std::to_string(run.pqueue.left()) + " problems wait for a parent and no slot is occupied");
+                break;
+            }
+            if (parent && run.pqueue.left() > 0) run.idle_slot_events += W - run.occupied_slots();
             const bool restarted = loop_restart(w, L, true);  // 5. an empty slot is an inactive one
             loop_advance(w, L, restarted);
         }
@@ -2713,11 +2860,15 @@ void BatchedSolver::solve_stream(int count, int width, const double *C_in, const
         }
         const long stats[8] = {count, width, L.iter, run.evals, run.refill_events, run.refills, run.passes, w.bumps - run.bumps0};
         std::copy(stats, stats + 8, stream_stats);
+        const long pstats[4] = {run.entered_roots, run.entered_cold, run.entered_children, run.idle_slot_events};
+        std::copy(pstats, pstats + 4, parents_stats);
+        stream_had_parents = parent != nullptr;
         rec_slot = std::move(run.r_slot); rec_in = std::move(run.r_in); rec_out = std::move(run.r_out);
         stream_seconds[0] = refill_seconds;
         stream_seconds[1] = seconds[4] - refill_seconds;
         const size_t header = 4 * static_cast<size_t>(plan.Bp);  // what the call held: the queue's vectors | the result / ray block |
         const size_t scalars = dev ? w.data_scal.n + w.data_part.n : 3 * static_cast<size_t>(count);  // scalars, partials, tables | pinned
+        // (a parents call of the host entry: the caller's X0 / Y0, staged as they are, count among the queue's vectors)
         const long mem[4] = {static_cast<long>((run.stage_count - header - (dev ? 0 : scalars)) * sizeof(double)),
                              static_cast<long>(run.res_count * sizeof(double)),
                              static_cast<long>((header + scalars) * sizeof(double) + w.tab_d.n * sizeof(int)),
@@ -2747,6 +2898,19 @@ void batched_solver_solve_stream_device(BatchedSolver *h, int count, int width, 
                                         DeviceBatch *dev) {
     if (!h || !dev) throw std::runtime_error("batched stream: null handle / device batch");
     h->solve_stream(count, width, C, AL, AU, l, u, obj_constants, param, X0, Y0, det, certs, nullptr, dev);
+}
+void batched_solver_solve_stream_parents(BatchedSolver *h, int count, int width, const double *C, const double *AL, const double *AU,
+                                         const double *l, const double *u, const double *obj_constants, const HPRLP_parameters *param,
+                                         const double *X0, const double *Y0, const int *parent, const Detection *det,
+                                         std::vector<Certificate> *certs, HPRLP_batched_results *out, DeviceBatch *dev) {
+    if (!h) throw std::runtime_error("batched stream: null handle");
+    h->solve_stream(count, width, C, AL, AU, l, u, obj_constants, param, X0, Y0, det, certs, out, dev, parent, /*parents_entry=*/true);
+}
+void batched_solver_stream_parents_info(const BatchedSolver *h, long out[4]) {
+    if (!h || !out) throw std::runtime_error("batched stream parents info: null handle / output");
+    if (!h->have_stream || !h->stream_had_parents)
+        throw std::runtime_error("batched stream parents info: the last successful stream call on this handle was not a parents call");
+    std::copy(h->parents_stats, h->parents_stats + 4, out);
 }
 void batched_solver_stream_memory(const BatchedSolver *h, long out[4]) {
     if (!h || !out) throw std::runtime_error("batched stream memory: null handle / output");

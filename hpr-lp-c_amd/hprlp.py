@@ -232,6 +232,15 @@ def lib():
             [c_dbl_p, C.POINTER(CParameters)] + [C.c_void_p] * 2 + [C.POINTER(CDetection), C.POINTER(CBatchedCertificates)] + \
             [C.c_void_p] * 4 + [C.POINTER(CBatchedScalars)]
         L.hprlp_batched_solver_stream_memory.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
+    if hasattr(L, "hprlp_batched_solver_solve_stream_parents"):  # (likewise: _need_parents() says so)
+        L.hprlp_batched_solver_solve_stream_parents.argtypes = [C.c_void_p, C.c_int, C.c_int] + [c_dbl_p] * 6 + \
+            [C.POINTER(CParameters), c_dbl_p, c_dbl_p, c_int_p, C.POINTER(CDetection), C.POINTER(CBatchedCertificates),
+             C.POINTER(CBatchedResults)]
+        L.hprlp_batched_solver_solve_stream_parents_device.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5 + \
+            [c_dbl_p, C.POINTER(CParameters)] + [C.c_void_p] * 2 + [c_int_p, C.POINTER(CDetection), C.POINTER(CBatchedCertificates)] + \
+            [C.c_void_p] * 4 + [C.POINTER(CBatchedScalars)]
+        L.hprlp_batched_solver_stream_parents_info.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
+        L.hprlp_stream_schedule_parents_host.argtypes = [C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p, c_int_p]
     L.hprlp_batched_prepare_host_rule.argtypes =[C.c_int] * 3 + [c_dbl_p] * 9 + [C.c_int, C.c_int, C.POINTER(CBatchedPrepared)]
     L.hprlp_solver_set_start.argtypes = [C.c_void_p, c_dbl_p, c_dbl_p]
     L.hprlp_solver_set_data.argtypes = [C.c_void_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p, c_dbl_p]
@@ -785,6 +794,19 @@ def _device_vector(sv, t, length, name, who):
     return t, _dev_dbl(addr)
 
 
+def _need_parents():
+    if not hasattr(lib(), "hprlp_batched_solver_solve_stream_parents"):
+        raise RuntimeError(f"{LIB_PATH} has no hprlp_batched_solver_solve_stream_parents: a build of an earlier commit (HPRLP_LIB?)")
+
+
+def _parent_array(parent, N):
+    """A parent list as a contiguous C int array of N entries (its values: by the library)."""
+    a = np.ascontiguousarray(parent, dtype=np.intc)
+    if a.shape != (N,):
+        raise ValueError(f"parent must have {N} entries, got shape {a.shape}")
+    return a
+
+
 def solve_batched(model, Cmat, AL, AU, l, u, obj_constants=None, param=None):
     """Cmat,l,u: (n,B) arrays; AL,AU: (m,B) arrays (any layout; passed column-major as the ABI asks)."""
     return _batched_call(lambda B, args, cp: lib().solve_batched(model._ptr, B, *args, C.byref(cp)),
@@ -895,20 +917,33 @@ class BatchedSolver:
                     "lambda_bumps")
 
     def solve_stream(self, Cmat, AL, AU, l, u, obj_constants=None, width=64, X0=None, Y0=None, eps_primal=None, eps_dual=None,
-                     prm=None):
+                     prm=None, parent=None):
         """N problems through `width` slots (hprlp_batched_solver_solve_stream, DESIGN.md "Streamed batches"): Cmat, l, u (n, N),
         AL, AU (m, N), X0 (n, N) / Y0 (m, N) or None.  A member that ends hands its slot to the next queued problem at the same
         evaluation.  Returns solve()'s dict for the N problems plus "slot", "event_in", "event_out" (the evaluation, loop iteration
         / check_iter, at which each problem entered and left its slot; event_in -1: never started) and, with detection,
         "certificates".  prm None: the constructor's parameters; max_iter, each member's own limit, must be a multiple of
-        check_iter.  carry, ray_step() and get_panel() are refused afterwards until the next solve()."""
+        check_iter.  carry, ray_step() and get_panel() are refused afterwards until the next solve().
+        parent (N ints; hprlp_batched_solver_solve_stream_parents, DESIGN.md "Streamed batches", "Parents"): parent[p] == -1 makes
+        problem p a root, else 0 <= parent[p] < p and p starts from the x, y that problem parent[p] returned, whatever its status,
+        as soon as that problem has ended and a slot is free.  X0 and Y0 then come together or not at all: with them a root starts
+        from its own columns, without them it is a cold member; a child ignores its own columns.  Slots without a ready problem
+        stand empty (stream_parents_info() counts them).  A problem below a parent whose final evaluation is not finite is ERROR
+        with event_in -1.  parent None: the call without parents, untouched."""
         if not self._h:
             raise RuntimeError("BatchedSolver: closed")
         _need_stream()
         N = np.asarray(Cmat).shape[1]
         X0, Y0 = self._start(X0, self.model.n, N, "X0"), self._start(Y0, self.model.m, N, "Y0")
-        out = self._host_call("hprlp_batched_solver_solve_stream", (int(width),), (_dptr(X0), _dptr(Y0)), (Cmat, AL, AU, l, u, obj_constants),
-                              prm, eps_primal, eps_dual)
+        if parent is None:
+            out = self._host_call("hprlp_batched_solver_solve_stream", (int(width),), (_dptr(X0), _dptr(Y0)),
+                                  (Cmat, AL, AU, l, u, obj_constants), prm, eps_primal, eps_dual)
+        else:
+            _need_parents()
+            par = _parent_array(parent, N)
+            out = self._host_call("hprlp_batched_solver_solve_stream_parents", (int(width),),
+                                  (_dptr(X0), _dptr(Y0), par.ctypes.data_as(c_int_p)), (Cmat, AL, AU, l, u, obj_constants), prm, eps_primal,
+                                  eps_dual)
         rec = [np.zeros(N, dtype=np.intc) for _ in range(3)]
         if lib().hprlp_batched_solver_stream_record(self._h, *(r.ctypes.data_as(c_int_p) for r in rec)) != N:
             raise RuntimeError("hprlp_batched_solver_stream_record failed: " + last_error())
@@ -924,6 +959,19 @@ class BatchedSolver:
         if lib().hprlp_batched_solver_stream_info(self._h, out) != 0:
             raise RuntimeError(last_error())
         return dict(zip(self._STREAM_INFO, [int(v) for v in out]))
+
+    _STREAM_PARENTS_INFO = ("roots", "cold_members", "children_started", "idle_slot_events")
+
+    def stream_parents_info(self):
+        """The counts of the last solve_stream() / solve_stream_tensors() with parents (hprlp_batched_solver_stream_parents_info):
+        roots that entered, cold_members among them, children_started, and idle_slot_events -- summed over the evaluations after
+        which the loop went on, the slots that stood empty while a problem was still waiting for its parent.  RuntimeError where
+        the last stream call had no parents."""
+        _need_parents()
+        out = (C.c_long * 4)()
+        if lib().hprlp_batched_solver_stream_parents_info(self._h, out) != 0:
+            raise RuntimeError(last_error())
+        return dict(zip(self._STREAM_PARENTS_INFO, [int(v) for v in out]))
 
     def stream_seconds(self):
         """Wall seconds of the last solve_stream()'s loop: its refill passes (harvest, refill, the new members' evaluation), the rest."""
@@ -1018,7 +1066,7 @@ class BatchedSolver:
         return out
 
     def solve_stream_tensors(self, Cmat, AL, AU, l, u, obj_constants=None, width=64, X0=None, Y0=None, eps_primal=None, eps_dual=None,
-                             prm=None):
+                             prm=None, parent=None):
         """solve_stream() for a queue that is on the GPU already (hprlp_batched_solver_solve_stream_device, DESIGN.md
         "Device-resident streams"): Cmat, l, u, X0 (n, N) and AL, AU, Y0 (m, N) are float64 torch tensors on the solver's device,
         taken as ordered on the current torch stream.  A tensor whose transpose is contiguous is passed as it is; any other layout
@@ -1026,11 +1074,23 @@ class BatchedSolver:
         way into a slot.  Returns solve_stream()'s dict with x, y, z as device tensors (rows, N) -- a problem that never started
         has zero columns -- plus "slot", "event_in", "event_out" and, with detection, "certificates".  ValueError for a numpy array,
         a CPU tensor, a wrong dtype or a wrong shape, before the library is called; RuntimeError with the library's message for a
-        call it refuses, which leaves the solver as it was."""
+        call it refuses, which leaves the solver as it was.
+        parent (N ints on the host; hprlp_batched_solver_solve_stream_parents_device): as solve_stream()'s.  A child's start is read
+        from the returned x, y on the device, where its parent's harvest wrote it: no start crosses the bus.  parent None: the call
+        without parents, untouched."""
         if not hasattr(lib(), "hprlp_batched_solver_solve_stream_device"):
             raise RuntimeError(f"{LIB_PATH} has no hprlp_batched_solver_solve_stream_device: a build of an earlier commit (HPRLP_LIB?)")
-        out = self._device_call("solve_stream_tensors", "hprlp_batched_solver_solve_stream_device", (int(width),), (),
-                                (Cmat, AL, AU, l, u, obj_constants, X0, Y0), prm, eps_primal, eps_dual)
+        if parent is None:
+            out = self._device_call("solve_stream_tensors", "hprlp_batched_solver_solve_stream_device", (int(width),), (),
+                                    (Cmat, AL, AU, l, u, obj_constants, X0, Y0), prm, eps_primal, eps_dual)
+        else:
+            _need_parents()
+            import torch
+            if not isinstance(Cmat, torch.Tensor) or Cmat.dim() != 2:
+                raise ValueError("solve_stream_tensors: Cmat must be a 2-D torch tensor")
+            par = _parent_array(parent, int(Cmat.shape[1]))
+            out = self._device_call("solve_stream_tensors", "hprlp_batched_solver_solve_stream_parents_device", (int(width),),
+                                    (par.ctypes.data_as(c_int_p),), (Cmat, AL, AU, l, u, obj_constants, X0, Y0), prm, eps_primal, eps_dual)
         N = out["batch_size"]
         rec = [np.zeros(N, dtype=np.intc) for _ in range(3)]
         if lib().hprlp_batched_solver_stream_record(self._h, *(r.ctypes.data_as(c_int_p) for r in rec)) != N:
@@ -1161,15 +1221,25 @@ class BatchedSolver:
             self._h = None
 
 
-def stream_schedule(events, width):
+def stream_schedule(events, width, parent=None):
     """The schedule BatchedSolver.solve_stream() follows (hprlp_stream_schedule_host; host only, no GPU), from each problem's
     length in evaluations (iter // check_iter; 0: it ends at its iteration-0 evaluation): (slot, event_in, event_out), arrays of
-    len(events).  The makespan in evaluations is event_out.max().  ValueError for what the library refuses."""
+    len(events).  The makespan in evaluations is event_out.max().  parent (len(events) ints, -1 for a root; DESIGN.md "Streamed
+    batches", "Parents"): the schedule of solve_stream(..., parent=parent) (hprlp_stream_schedule_parents_host); all -1 gives what
+    None gives.  ValueError for what the library refuses."""
     _need_stream()
     ev = np.ascontiguousarray(events, dtype=np.intc)
     if ev.ndim != 1:
         raise ValueError("stream_schedule: events must be one-dimensional")
     out = [np.zeros(max(ev.shape[0], 1), dtype=np.intc) for _ in range(3)]
+    if parent is not None:
+        _need_parents()
+        par = _parent_array(parent, ev.shape[0])
+        rc = lib().hprlp_stream_schedule_parents_host(ev.shape[0], int(width), ev.ctypes.data_as(c_int_p), par.ctypes.data_as(c_int_p),
+                                                      *(o.ctypes.data_as(c_int_p) for o in out))
+        if rc < 0:
+            raise ValueError("hprlp_stream_schedule_parents_host: " + last_error())
+        return tuple(o[:ev.shape[0]] for o in out)
     rc = lib().hprlp_stream_schedule_host(ev.shape[0], int(width), ev.ctypes.data_as(c_int_p), *(o.ctypes.data_as(c_int_p) for o in out))
     if rc < 0:
         raise ValueError("hprlp_stream_schedule_host: " + last_error())

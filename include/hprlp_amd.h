@@ -297,6 +297,49 @@ int hprlp_batched_solver_solve_stream_device(hprlp_batched_solver *h, int count,
  * {device bytes the call held for queue VECTORS (host entry: the staged queue; device entry: 0),
  *  device bytes of its result / ray block, device bytes of per-problem scalars, partials and tables, pinned host bytes} */
 int hprlp_batched_solver_stream_memory(hprlp_batched_solver *h, long out[4]);
+/* ---- streams with parents: queued problems start from earlier ones' solutions (DESIGN.md "Streamed batches", "Parents") ---------
+ * hprlp_batched_solver_solve_stream / _solve_stream_device with one more argument, parent: a HOST array of `count` ints in both
+ * entries.  parent[p] == -1: problem p is a root; else 0 <= parent[p] < p, and p starts from the x, y that problem parent[p]
+ * returned, whatever its status (OPTIMAL, ITER_LIMIT, a verdict's iterate) -- a rolling horizon's period t+1 from period t, a search
+ * tree's node from its parent -- in ONE call, without a level waiting for its slowest member.
+ *   Starts: X0 / Y0 are given together or not at all.  With them a root starts from its own columns; without them a root is a cold
+ * member, bit for bit a cold plain member.  A child ignores its own columns.  A start is scaled on its way into the slot by the
+ * kernel that reads it (kb_slot_start): from the parent's column of the results on the device, or the root's column of X0 / Y0.
+ *   Rule: p is READY when it is a root or its parent has been harvested, in an earlier pass or in the very pass that is being
+ * assigned.  In one refill pass the FREE slots -- those just harvested and those that stood empty -- in ascending order take the
+ * ready problems in ascending number, as many as both last.  The initial fill is a pass of event 0 with every slot free, in which
+ * only roots are ready; slots without a problem stay empty and inactive until a pass gives them one.  The geometry is a plain
+ * solve's of min(width, count) members.  A member that ends at its iteration-0 evaluation frees its slot, and readies its children,
+ * for the same event's next pass.  Everything else -- events, local iteration numbers, limits, the record, what a later call may
+ * do -- is the stream's.
+ *   Never entered: once the time is up nothing enters, and a problem that never entered is TIME_LIMIT, iter 0, zero vectors,
+ * event_in -1.  Where a parent's final residuals, primal_obj or gap is not finite, its children do not enter: they and their
+ * descendants are ERROR, iter 0, zero vectors, event_in -1.
+ *   Bits: for problem p in slot k, status, iter, x, y, z, primal_obj, residuals, gap and certificate are those of a plain solve of
+ * min(width, count) members whose slot k holds p -- cold for a cold root, else warm with X0[:, k], Y0[:, k] equal to the returned
+ * x, y of p's parent (a started root: its own columns) -- provided neither call raised lambda_max.  With parent all -1 the results
+ * and the record are those of the twin without parents.
+ *   Refused with -1 + hprlp_last_error() before anything changes: everything the twin refuses, a NULL parent, one of X0 / Y0 without
+ * the other, and a parent[p] outside -1 .. p-1 (the message names p and the value; no device call is made for it). */
+int hprlp_batched_solver_solve_stream_parents(hprlp_batched_solver *h, int count, int width, const double *C, const double *AL,
+                                              const double *AU, const double *l, const double *u, const double *obj_constants,
+                                              const HPRLP_parameters *param, const double *X0, const double *Y0, const int *parent,
+                                              const hprlp_detection *det, hprlp_batched_certificates *certs, HPRLP_batched_results *out);
+/* the device twin: hprlp_batched_solver_solve_stream_device's arguments plus parent (host).  A child's start is read from the
+ * caller's dx, dy, where its parent's harvest wrote it on the solver's stream; nothing of a start crosses the bus. */
+int hprlp_batched_solver_solve_stream_parents_device(hprlp_batched_solver *h, int count, int width, const double *dC, const double *dAL,
+                                                     const double *dAU, const double *dl, const double *du, const double *obj_constants,
+                                                     const HPRLP_parameters *param, const double *dX0, const double *dY0,
+                                                     const int *parent, const hprlp_detection *det, hprlp_batched_certificates *certs,
+                                                     void *stream, double *dx, double *dy, double *dz, hprlp_batched_scalars *out);
+/* of the last stream call, which was one with parents (else -1): {roots that entered, cold members among them, children that
+ * entered, slot-events: summed over the loop's evaluations after which it went on, the slots that stood empty while a problem was
+ * still waiting for its parent} */
+int hprlp_batched_solver_stream_parents_info(hprlp_batched_solver *h, long out[4]);
+/* host only, no GPU: hprlp_stream_schedule_host for a queue with parents (parent as above; all -1: hprlp_stream_schedule_host's
+ * arrays and makespan).  -1 + hprlp_last_error() also for a NULL parent or a parent[p] outside -1 .. p-1. */
+int hprlp_stream_schedule_parents_host(int count, int width, const int *events, const int *parent, int *slot, int *event_in,
+                                       int *event_out);
 /* The norm rule of the HOST entry of this handle: 0 = the reference's long double sums (the default), 1 = the tree rule. */
 int hprlp_batched_solver_set_norms(hprlp_batched_solver *h, int rule);
 /* out (7 x B): b_scale, c_scale, norm_b, norm_c, norm_b_org, norm_c_org, first sigma of the last successful solve, either entry.
